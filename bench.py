@@ -20,6 +20,9 @@ The JSON line also carries
                   the reference CLI's own B = 1 shape, the 10-block rollout rate (the region sim_inference.py:109-115
                   times), one DDP-less training step of configs[4]'s per-GPU shape, and a box probe (HBM copy rate,
                   bf16 GEMM rate) that makes a slow box recognisable.  `--no-extra` skips them.
+
+`--dump-outputs DIR` writes what the last timed step returned (float32 .npy files, see dump_outputs); the inputs are seeded,
+so the files of two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -382,6 +385,23 @@ def timed_region(step, steps, warmup, dist, sync):
     return out, time.perf_counter() - t0, dt_own
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs DIR`: write each array as DIR/<name>.npy in float32.  Above DUMP_LIMIT_BYTES in all, every array is cut
+    to the same fixed, seeded sample of its flattened elements (in index order), so that two builds stay comparable."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(v.numel() * 4 for v in arrays.values())
+    for name, v in arrays.items():
+        v = v.detach().to("cpu", torch.float32)
+        if total > DUMP_LIMIT_BYTES:
+            n = max(1, v.numel() * DUMP_LIMIT_BYTES // total)
+            v = v.reshape(-1)[torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:n].sort().values]
+        np.save(os.path.join(out_dir, name + ".npy"), v.numpy())
+
+
 def headline(a, world, B, T, L, S, dt, per_rank, use_graph, roof=None, cpu=None, extra=None, data=None):
     value = B * T * a.steps * world / dt
     return {
@@ -435,9 +455,14 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the extra legs (ATLAS, TPS, B = 1, rollout, training step, box probe)")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="library run-time option (mdgen_ctx_set_option), e.g. mlp_path=1; repeatable")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, float32: "
+                         "atom14 and aa_out of inference(), and the sampled latents (wrapper.last_samples)")
     ap.add_argument("--fake-sampler", action="store_true", help=argparse.SUPPRESS)   # test hook, see fake_sampler_main
     ap.add_argument("--dist-selftest", action="store_true", help=argparse.SUPPRESS)  # one-rank RCCL self-test, see dist_selftest
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     options = {kv.split("=")[0]: int(kv.split("=")[1]) for kv in a.option}
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -484,7 +509,9 @@ def main():
     def step():
         return w.inference(batch, zs=zs, num_steps=S, use_graph=use_graph)
 
-    (atom14, _), dt, dt_own = timed_region(step, a.steps, a.warmup, dist, torch.cuda.synchronize)
+    (atom14, aa_out), dt, dt_own = timed_region(step, a.steps, a.warmup, dist, torch.cuda.synchronize)
+    if a.dump_outputs and rank == 0:   # before anything below runs the sampler again
+        dump_outputs(a.dump_outputs, {"atom14": atom14, "aa_out": aa_out, "samples": w.last_samples})
     from mdgen_amd.sharding import gather_over_ranks, max_over_ranks
     dt = max_over_ranks(dt, dist, dev)
     per_rank = [B * T * a.steps / s for s in gather_over_ranks(dt_own, dist, dev)]

@@ -109,9 +109,13 @@ def to_tensor_7(R, t, quat_sign="eigh"):
     quat_sign: the reference takes whatever sign LAPACK's eigh returns (arbitrary, rigid_utils.py:208-210).
     "eigh" reproduces that (same torch build -> same signs; this is what the reference goldens pin);
     "w_nonneg" flips each quaternion so that w >= 0, the convention the HIP kernel (k_se3.hip rot2quat) uses,
-    so that device parity can be asserted on the TPS relative-frame path where the sign reaches a Linear."""
+    so that device parity can be asserted on the TPS relative-frame path where the sign reaches a Linear;
+    a tensor [..., >=4]: each quaternion takes the sign of the given one (the reference's, as a fixture stores it: LAPACK's
+    sign also depends on the host's BLAS code path, so "eigh" reproduces a fixture only on a host like the one that made it)."""
     q = rot_to_quat(R)
-    if quat_sign == "w_nonneg":
+    if torch.is_tensor(quat_sign):
+        q = torch.where((q * quat_sign[..., :4]).sum(-1, keepdim=True) < 0, -q, q)
+    elif quat_sign == "w_nonneg":
         q = torch.where(q[..., :1] < 0, -q, q)
     return torch.cat([q, t], -1)
 
@@ -371,9 +375,10 @@ def run_ipa(P, cfg, temb, mask_bl, start, end, aatype):
     if cfg.get("tps_condition", False):
         iR, it = rigid_invert(*start)
         qs = cfg.get("quat_sign", "eigh")
-        x_f = to_tensor_7(*rigid_compose(iR, it, *end), quat_sign=qs)    # :194
+        qf, qr = (qs[0], qs[1]) if torch.is_tensor(qs) else (qs, qs)    # tensor: the reference's rel7 (2, B, L, 7), [x_f, x_r]
+        x_f = to_tensor_7(*rigid_compose(iR, it, *end), quat_sign=qf)    # :194
         iR, it = rigid_invert(*end)
-        x_r = to_tensor_7(*rigid_compose(iR, it, *start), quat_sign=qs)  # :195
+        x_r = to_tensor_7(*rigid_compose(iR, it, *start), quat_sign=qr)  # :195
         x_f = linear(P, "latent_to_emb_f", x_f) + aa
         x_r = linear(P, "latent_to_emb_r", x_r) + aa
         for i in range(nl):
