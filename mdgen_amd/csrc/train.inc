@@ -188,11 +188,21 @@ static size_t carve_train(Train* t, const mdgen_ctx* c, long B, long T, long L, 
 
 static const ModMap kNoMod{nullptr, 1, 1, 0, 0};
 
+// Whether the bf16 row stores below may be used: their consumers are the streamed / wide kernels only (k_wide16.hip), so the
+// producer must know before it writes that every consumer will take its launch.  Of the consumers' conditions, the rows (>= 4096,
+// launch16_dw_wide), the shapes and strides and the scratch sizes (part_floats, the slice plans) are fixed by the sub-layer; what
+// is not is the 16-byte alignment of its weights (launch16_pack_wstream): a bound parameter buffer may put them anywhere
+// (mdgen_train_bind_params).  `wide`: every weight of the sub-layer 16-byte aligned (sub_wide).
+static bool sub_wide(std::initializer_list<const float*> w) {
+    for (const float* p : w)
+        if ((uintptr_t)p & 15) return false;
+    return true;
+}
 // whether SubTapeMlp::hid of a sub-layer with `nrows` rows holds bf16 (both of its readers are then the wide kernels)
-static bool hid_is_bf16(long nrows) { return g_k32_bf16_operands && nrows >= 4096; }
+static bool hid_is_bf16(long nrows, bool wide) { return g_k32_bf16_operands && nrows >= 4096 && wide; }
 // the taped LayerNorm + modulate output of a trunk sub-layer likewise (token rows of the q | k | v / fc1 products, X of their weight
 // gradients: all of them the streamed / wide kernels at these sizes); option train_y_bf16
-static bool y_is_bf16(const Train& t, long nrows);
+static bool y_is_bf16(const Train& t, long nrows, bool wide);
 
 // bf16-operand mode, launches big enough for the streamed 128 x 384 kernel: the weight W(col < m, kk < k) of ONE layer as a
 // bf16 fragment stream in the scratch t.wt (turned: the fp32 matrix is [k][m], dX = dY W).  nullptr: not eligible -- the
@@ -202,7 +212,7 @@ static const void* wpack1(const Train& t, const float* w, int ld, long n, int m,
     return launch16_pack_wstream(&w, 1, turned ? k : m, ld, n, m, k, turned, t.wt, t.r.s) ? t.wt : nullptr;
 }
 
-static bool y_is_bf16(const Train& t, long nrows) { return t.c->opt_train_y_bf16 && hid_is_bf16(nrows); }
+static bool y_is_bf16(const Train& t, long nrows, bool wide) { return t.c->opt_train_y_bf16 && hid_is_bf16(nrows, wide); }
 
 // ---- forward sub-layers with tape ---------------------------------------------------------------------------------
 // LayerNorm + modulate of the residual stream into y, the stream's rows copied to the tape (h_in) -- with the previous sub-layer's
@@ -237,7 +247,7 @@ static int attn_fwd_tape(const Train& t, const std::string& pre, float* h, long 
     TW32(wv, pre + "v_proj.weight"); TW32(bv, pre + "v_proj.bias");
     TW32(wo, pre + "out_proj.weight"); TW32(bo, pre + "out_proj.bias");
     TW32(biask, pre + "bias_k"); TW32(biasv, pre + "bias_v");
-    const bool y16 = y_is_bf16(t, nrows);
+    const bool y16 = y_is_bf16(t, nrows, sub_wide({wq, wk, wv, wo}));
     ln_mod_tape(t, h, nrows, mm, shift, scale, tp.y, tp.h_in, y16);     // y (taped), and the tape's copy of h
     const float qscale = 1.0f / std::sqrt((float)kDH);
     const float* w3[3] = {wq, wk, wv};
@@ -272,11 +282,12 @@ static int mlp_fwd_tape(const Train& t, const std::string& pre, float* h, long n
     const F32Bufs b = f32_bufs(r);
     TW32(w1, pre + "fc1.weight"); TW32(b1, pre + "fc1.bias");
     TW32(w2, pre + "fc2.weight"); TW32(b2, pre + "fc2.bias");
-    const bool y16 = y_is_bf16(t, nrows);
+    const bool wide = sub_wide({w1, w2});
+    const bool y16 = y_is_bf16(t, nrows, wide);
     ln_mod_tape(t, h, nrows, mm, shift, scale, tp.y, tp.h_in, y16);     // y (taped), and the tape's copy of h
     // hid = gelu(pre) is only ever a GEMM operand (fc2's input here, X of fc2's weight gradient): in the bf16-operand mode,
     // at sizes where both consumers are the wide kernels, it is stored rounded (identical products, half the bytes)
-    const bool h16 = hid_is_bf16(nrows);
+    const bool h16 = hid_is_bf16(nrows, wide);
     const void* pk1 = wpack1(t, w1, kC, nrows, kF, kC, 0);
     if (y16 && !pk1) return fail(-7, "internal: bf16 LayerNorm output without the streamed fc1 kernel (rows %ld)", nrows);
     launch32_linear(tp.y, kC, w1, kC, b1, nrows, kF, kC, 6, tp.pre, kF, 0, kNoMod, 0, 0, 0.f, r.s, 0, tp.hid, pk1, (h16 ? 2 : 0) | (y16 ? 1 : 0));
@@ -360,7 +371,7 @@ static int lin_bwd(const Train& t, const float* dy, int ldy, const float* x, int
 // gated residual h_out = h_in + gate * u:  du = gate * dh (into t.du);  dgate[g] += sum_t dh * u
 // du16: t.du is written as bf16 rows (du_is_bf16: it is only ever the token operand of the dX product and dY of the weight gradient
 // of the sub-layer's last linear layer)
-static bool du_is_bf16(const Train& t, long nrows) { return t.c->opt_train_du_bf16 && hid_is_bf16(nrows); }
+static bool du_is_bf16(const Train& t, long nrows, bool wide) { return t.c->opt_train_du_bf16 && hid_is_bf16(nrows, wide); }
 static int gate_bwd(const Train& t, const float* dh, const float* u, long nrows, const ModMap& mm, int gate_chunk,
                     long tokens_per_group, long mod_ld, float* dmod_base, bool du16 = false) {
     hipStream_t s = t.r.s;
@@ -396,16 +407,17 @@ static int mlp_bwd(const Train& t, const std::string& pre, float* dh, long nrows
     TW32(w1, pre + "fc1.weight");
     TW32(w2, pre + "fc2.weight");
     if (int e = t.begin_sub()) return e;
-    const bool du16 = du_is_bf16(t, nrows);
+    const bool wide = sub_wide({w1, w2});   // (as mlp_fwd_tape decided the tape's storage)
+    const bool du16 = du_is_bf16(t, nrows, wide);
     if (int e = gate_bwd(t, dh, tp.u, nrows, mm, gate, tpg, mod_ld, dmod_base, du16)) return e;   // t.du = gate * dh
     // d pre = (du W2) * gelu'(pre): the GELU derivative is the epilogue of the dX product
     // (round 6) d pre is stored as bf16 rows: the token operand of fc1's dX product and dY of fc1's weight gradient (option train_dhid_bf16)
-    const bool dh16 = t.c->opt_train_dhid_bf16 && hid_is_bf16(nrows);
+    const bool dh16 = t.c->opt_train_dhid_bf16 && hid_is_bf16(nrows, wide);
     if (int e = lin_bwd(t, t.du, kC, tp.hid, kF, w2, nrows, kC, kF, t.dhid, kF, false, pre + "fc2.weight", pre + "fc2.bias", tp.pre,
-                        hid_is_bf16(nrows), true, du16, dh16))
+                        hid_is_bf16(nrows, wide), true, du16, dh16))
         return e;
     if (int e = lin_bwd(t, t.dhid, kF, tp.y, kC, w1, nrows, kF, kC, t.dy, kC, false, pre + "fc1.weight", pre + "fc1.bias", nullptr,
-                        y_is_bf16(t, nrows), true, dh16))
+                        y_is_bf16(t, nrows, wide), true, dh16))
         return e;
     lnmod_bwd(t, tp.h_in, t.dy, nrows, mm, shift, scale, tpg, mod_ld, dmod_base, dh, true);
     LAUNCHCHK();
@@ -421,14 +433,15 @@ static int attn_bwd(const Train& t, const std::string& pre, float* dh, long nrow
     TW32(wo, pre + "out_proj.weight");
     TW32(biask, pre + "bias_k"); TW32(biasv, pre + "bias_v");
     if (int e = t.begin_sub()) return e;
-    const bool du16 = du_is_bf16(t, nrows);
+    const bool wide = sub_wide({wq, wk, wv, wo});   // (as attn_fwd_tape decided the tape's storage)
+    const bool du16 = du_is_bf16(t, nrows, wide);
     if (int e = gate_bwd(t, dh, tp.u, nrows, mm, gate, tpg, mod_ld, dmod_base, du16)) return e;   // t.du
     if (int e = lin_bwd(t, t.du, kC, tp.att, kC, wo, nrows, kC, kC, t.dy, kC, false, pre + "out_proj.weight", pre + "out_proj.bias",
                         nullptr, false, true, du16))
         return e;                                                                        // t.dy = d att
     // (round 6) the sequence-resident kernels write dq | dk | dv as bf16 rows: the buffer is only ever the token operand of the dX
     // product and dY of the weight gradient (option train_dqkv_bf16; the bias gradients then sum the rounded values)
-    const bool dq16 = g_k32_bf16_operands && t.c->opt_train_dqkv_bf16 && attn16_seq_form(ax) && nrows >= 4096;
+    const bool dq16 = t.c->opt_train_dqkv_bf16 && attn16_seq_form(ax) && hid_is_bf16(nrows, wide);
     if (g_k32_bf16_operands)
         launch16_attn_bwd(tp.qkv, 3 * kC, ax, mk, biask, biasv, t.c->inv_freq, tp.att, t.dy, t.dqkv, t.stats, t.dbias, s, tp.lse,
                           attn16_seq_form(ax), dq16);   // (RoPE inside as the forward pass decided: attn_fwd_tape)
@@ -467,7 +480,7 @@ static int attn_bwd(const Train& t, const std::string& pre, float* dh, long nrow
         }
         if (want_g) {
             const bool bias_done = launch32_dw_seg(t.dqkv, 3 * kC, tp.y, kC, nrows, kC, 3, kC, gw3, gb3, pt, t.part_floats, sw,
-                                                   y_is_bf16(t, nrows), dq16);
+                                                   y_is_bf16(t, nrows, wide), dq16);
             if (dq16 && !bias_done && (gb3[0] || gb3[1] || gb3[2]))
                 return fail(-7, "internal: bf16 q | k | v gradients without the wide weight-gradient kernel (rows %ld)", nrows);
             for (int j = 0; j < 3 && !bias_done; ++j)

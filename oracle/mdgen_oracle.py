@@ -43,16 +43,40 @@ def tables():
 
 
 # ----------------------------------------------------------------------------------------------
+# compute precision.  cfg["compute_dtype"] = "float64" runs every step in fp64: the entry points (forward, training_losses,
+# prep_batch) cast their floating inputs and weights, and each step below that the reference pins to fp32 follows the
+# dtype of its operands instead.  Without the key the fp32 path is unchanged, bit for bit.
+# ----------------------------------------------------------------------------------------------
+def compute_dtype(cfg):
+    dt = cfg.get("compute_dtype", "float32")
+    if dt not in ("float32", "float64"):
+        raise ValueError(f"compute_dtype {dt!r}: float32 | float64")
+    return torch.float64 if dt == "float64" else torch.float32
+
+
+def _real(x):
+    """x.float(), except that fp64 stays fp64 (the reference's fp32 casts, under compute_dtype float64)."""
+    return x if x.dtype == torch.float64 else x.float()
+
+
+def _cast(dt, x):
+    """A floating tensor (or a tuple of them) to the compute dtype; integer tensors and None untouched."""
+    if isinstance(x, (tuple, list)):
+        return type(x)(_cast(dt, v) for v in x)
+    return x.to(dt) if torch.is_tensor(x) and x.is_floating_point() and dt == torch.float64 else x
+
+
+# ----------------------------------------------------------------------------------------------
 # SE(3) algebra  (mdgen/rigid_utils.py) -- functional: a rigid is a pair (R [...,3,3], t [...,3])
 # ----------------------------------------------------------------------------------------------
 def rot_matmul(a, b):
     """rigid_utils.py:24-61  c_ik = sum_j a_ij b_jk (fp32, written out to dodge AMP)."""
-    return torch.einsum("...ij,...jk->...ik", a.float(), b.float())
+    return torch.einsum("...ij,...jk->...ik", _real(a), _real(b))
 
 
 def rot_vec_mul(r, v):
     """rigid_utils.py:64-86  y_i = sum_j r_ij v_j."""
-    return torch.einsum("...ij,...j->...i", r.float(), v.float())
+    return torch.einsum("...ij,...j->...i", _real(r), _real(v))
 
 
 def rigid_compose(R1, t1, R2, t2):
@@ -122,7 +146,7 @@ def to_tensor_7(R, t, quat_sign="eigh"):
 
 def from_tensor_7(x, normalize_quats=True):
     """rigid_utils.py:1157-1173 + Rotation.__init__ :318-325 (q/|q|) + get_rot_mats :500-514."""
-    q, t = x[..., :4].float(), x[..., 4:].float()
+    q, t = _real(x[..., :4]), _real(x[..., 4:])
     if normalize_quats:
         q = q / torch.linalg.norm(q, dim=-1, keepdim=True)
     return quat_to_rot(q), t
@@ -184,14 +208,14 @@ def atom37_to_torsions(atom37, aatype):
     rel = rigid_invert_apply(R, t, pos[..., 3, :])
     sc = torch.stack([rel[..., 2], rel[..., 1]], dim=-1)
     sc = sc / torch.sqrt((sc * sc).sum(-1, keepdim=True) + 1e-8)
-    sign = torch.tensor([1.0, 1.0, -1.0, 1.0, 1.0, 1.0, 1.0])[:, None]
+    sign = torch.tensor([1.0, 1.0, -1.0, 1.0, 1.0, 1.0, 1.0], dtype=_real(sc).dtype)[:, None]
     return sc * sign, tmask
 
 
 def torsion_angles_to_frames(R, t, alpha, aatype):
     """geometry.py:273-334  8 rigid-group frames per residue in the global frame."""
     T = tables()
-    d4 = T["default_frames"][aatype]                          # [...,8,4,4]
+    d4 = T["default_frames"][aatype].to(_real(alpha).dtype)   # [...,8,4,4]
     dR, dt = d4[..., :3, :3], d4[..., :3, 3]
     bb = alpha.new_zeros(*alpha.shape[:-2], 1, 2)
     bb[..., 1] = 1
@@ -220,7 +244,7 @@ def frames_torsions_to_atom14(R, t, torsions, aatype):
     grp = T["atom14_group"][aatype]                                    # [...,14]
     aR = torch.gather(gR, -3, grp[..., None, None].expand(*grp.shape, 3, 3))
     at = torch.gather(gt, -2, grp[..., None].expand(*grp.shape, 3))
-    lit = T["lit_positions"][aatype]
+    lit = T["lit_positions"][aatype].to(_real(R).dtype)
     pos = rot_vec_mul(aR, lit) + at
     return pos * T["atom14_mask"][aatype][..., None]
 
@@ -249,8 +273,9 @@ def ln(x, eps=1e-6):
 def timestep_embedding(t, dim=256, max_period=10000):
     """layers.py:31-50  [cos | sin] of t * exp(-ln(1e4) i/half)."""
     half = dim // 2
-    freqs = torch.exp(-math.log(max_period) * torch.arange(half, dtype=torch.float32) / half)
-    args = t[:, None].float() * freqs[None]
+    t = _real(t)
+    freqs = torch.exp(-math.log(max_period) * torch.arange(half, dtype=t.dtype) / half)
+    args = t[:, None] * freqs[None]
     return torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
 
 
@@ -260,10 +285,10 @@ def t_embedder(P, t):
     return linear(P, "t_embedder.mlp.2", F.silu(h))
 
 
-def rope_tables(n_pos, head_dim):
+def rope_tables(n_pos, head_dim, dtype=torch.float32):
     """esm.rotary_embedding (fair-esm, not vendored): angle[pos, i] = pos * 10000^(-2(i mod d/2)/d)."""
-    inv = 1.0 / (10000 ** (torch.arange(0, head_dim, 2).float() / head_dim))
-    fr = torch.einsum("i,j->ij", torch.arange(n_pos).float(), inv)
+    inv = 1.0 / (10000 ** (torch.arange(0, head_dim, 2).to(dtype) / head_dim))
+    fr = torch.einsum("i,j->ij", torch.arange(n_pos).to(dtype), inv)
     emb = torch.cat([fr, fr], -1)
     return emb.cos(), emb.sin()
 
@@ -287,12 +312,13 @@ def mha_rope(P, pre, y, mask, heads):
     q = q.view(bsz, n, heads, dh).transpose(1, 2)                       # [bsz,H,n,dh]
     k = k.view(bsz, n + 1, heads, dh).transpose(1, 2)
     v = v.view(bsz, n + 1, heads, dh).transpose(1, 2)
-    cos, sin = rope_tables(n + 1, dh)                                   # :356-357
+    dt = _real(y).dtype                                                 # fp32, or fp64 under compute_dtype float64
+    cos, sin = rope_tables(n + 1, dh, dt)                               # :356-357
     q = q * cos[:n] + rotate_half(q) * sin[:n]
     k = k * cos + rotate_half(k) * sin
     s = q @ k.transpose(-1, -2)                                         # :359
     s = s.masked_fill(pad[:, None, None, :], float("-inf"))             # :370-376
-    p = F.softmax(s, dim=-1, dtype=torch.float32)                       # :381
+    p = F.softmax(s, dim=-1, dtype=dt)                                  # :381
     o = (p @ v).transpose(1, 2).reshape(bsz, n, C)                      # :389-396
     return linear(P, pre + "out_proj", o)                               # :397
 
@@ -394,6 +420,12 @@ def run_ipa(P, cfg, temb, mask_bl, start, end, aatype):
 def forward(P, cfg, x, t, mask, start_frames, end_frames, x_cond, x_cond_mask, aatype, return_trace=False):
     """LatentMDGenModel.forward (latent_model.py:212-260), non-design path == forward_inference."""
     H = cfg["mha_heads"]
+    dt = compute_dtype(cfg)
+    if dt == torch.float64:
+        P = {k: _cast(dt, v) for k, v in P.items()}
+        x, t, mask, start_frames, end_frames, x_cond = _cast(dt, (x, t, mask, start_frames, end_frames, x_cond))
+        if torch.is_tensor(cfg.get("quat_sign")):
+            cfg = dict(cfg, quat_sign=_cast(dt, cfg["quat_sign"]))
     h = linear(P, "latent_to_emb", x)                                    # :233
     if cfg.get("abs_pos_emb", False):
         h = h + P["pos_embed"]                                           # :234-235 ([1,L,C] bcast over T)
@@ -427,7 +459,8 @@ def get_offsets(ref, rig):
 
 def prep_batch(batch, cfg):
     """NewMDGenWrapper.prep_batch (wrapper.py:283-365), sim_condition / tps_condition paths."""
-    R, t = batch["rots"].float(), batch["trans"].float()
+    dt = compute_dtype(cfg)
+    R, t = batch["rots"].to(dt), batch["trans"].to(dt)
     B, T, L = t.shape[:3]
     off = get_offsets((R[:, 0:1], t[:, 0:1]), (R, t))                    # :307
     off[..., :4] *= torch.where(off[..., 0:1] < 0, -1, 1)                # :309
@@ -439,7 +472,7 @@ def prep_batch(batch, cfg):
         off_r[..., :4] *= torch.where(off_r[..., 0:1] < 0, -1, 1)
         off = torch.cat([off, off_r], -1)
         frame_lm = torch.cat([frame_lm, frame_lm], -1)
-    latents = torch.cat([off, batch["torsions"].reshape(B, T, L, 14).float()], -1)   # :327
+    latents = torch.cat([off, batch["torsions"].reshape(B, T, L, 14).to(dt)], -1)   # :327
     loss_mask = torch.cat([frame_lm, tors_lm], -1).unsqueeze(1).expand(-1, T, -1, -1)
     cond_mask = torch.zeros(B, T, L, dtype=torch.long)
     if cfg.get("sim_condition", False):
@@ -456,7 +489,7 @@ def prep_batch(batch, cfg):
         "model_kwargs": {
             "start_frames": (R[:, 0], t[:, 0]),
             "end_frames": (R[:, -1], t[:, -1]),
-            "mask": batch["mask"].unsqueeze(1).expand(-1, T, -1).float(),
+            "mask": batch["mask"].unsqueeze(1).expand(-1, T, -1).to(dt),
             "aatype": batch["seqres"],
             "x_cond": torch.where(cond_mask.unsqueeze(-1).bool(), latents, 0.0),
             "x_cond_mask": cond_mask,
@@ -468,11 +501,11 @@ def sample_euler(P, cfg, zs, model_kwargs, num_steps):
     """Sampler.sample_ode -> ode.sample -> torchdiffeq fixed-grid Euler (transport.py:408-451,
     integrators.py:95-114).  `num_steps` = number of Euler steps S; the grid is linspace(0,1,S+1)
     (the reference hard-codes 50 grid points = 49 steps).  Returns the final state only."""
-    tg = torch.linspace(0, 1, num_steps + 1)
+    tg = torch.linspace(0, 1, num_steps + 1, dtype=_real(zs).dtype)
     x = zs
     B = zs.shape[0]
     for i in range(num_steps):
-        tt = torch.ones(B) * tg[i]                                       # integrators.py:99
+        tt = torch.ones(B, dtype=tg.dtype) * tg[i]                                       # integrators.py:99
         v = forward(P, cfg, x, tt, **model_kwargs)
         x = x + (tg[i + 1] - tg[i]) * v
     return x
@@ -495,6 +528,7 @@ def postprocess(samples, rigids, seqres, cfg):
 def inference(P, cfg, batch, zs, num_steps):
     """NewMDGenWrapper.inference (wrapper.py:405-484) with explicit noise `zs` and step count."""
     prep = prep_batch(batch, cfg)
+    zs = _cast(compute_dtype(cfg), zs)
     samples = sample_euler(P, cfg, zs, prep["model_kwargs"], num_steps)
     atom14, aa = postprocess(samples, prep["rigids"], batch["seqres"], cfg)
     return atom14, aa, samples
@@ -540,6 +574,8 @@ def mean_flat(x, mask):
 def training_losses(P, cfg, x1, mask, model_kwargs, t, x0, path_type="GVP"):
     """Transport.training_losses (transport.py:138-189), velocity model, non-design path, with the noise x0 and
     the times t given explicitly (the reference draws them at :126-136)."""
+    dt = compute_dtype(cfg)
+    x1, mask, t, x0 = _cast(dt, (x1, mask, t, x0))
     xt, ut = path_plan(t, x0, x1, path_type)
     pred = forward(P, cfg, xt, t, **model_kwargs)
     return {"t": t, "pred": pred, "loss": mean_flat((pred - ut) ** 2, mask), "xt": xt, "ut": ut}

@@ -316,3 +316,60 @@ def test_ten_chained_blocks_vs_reference():
         cur = dict(cur, **O.rollout_glue(atom14[:, -1], seqres))
         cur["torsions"] = cur["torsions"].clone()
         cur["torsions"][:, :, 0, 0] = pinned[blk]
+
+
+def _fp64_training_case(name):
+    """Fixture `name` under compute_dtype float64: weights, inputs and the trainable leaves all fp64."""
+    g = load_golden(name)
+    cfg, sd = weights_for(g)
+    from mdgen_amd.train import trainable_shapes
+    names = list(trainable_shapes(cfg))
+    P = {k: (v.double().requires_grad_(k in names) if v.is_floating_point() else v) for k, v in sd.items()}
+    kw = dict(mask=g["mask"].double(), start_frames=(g["start_rot"].double(), g["start_trans"].double()),
+              end_frames=(g["start_rot"].double(), g["start_trans"].double()), x_cond=g["x_cond"].double(),
+              x_cond_mask=g["x_cond_mask"], aatype=g["aatype"])
+    cd = dict(O.cfg_dict(cfg), compute_dtype="float64")
+    args = (g["x1"].double(), g["loss_mask"].double(), kw, g["t"].double(), g["x0"].double())
+    return g, names, P, cd, args
+
+
+def test_fp64_mode_finite_differences():
+    """compute_dtype float64 leaves no fp32 step in the training loss: along 3 random directions over every trainable
+    tensor, the central difference (h = 1e-6) matches autograd's directional derivative to 1e-7 relative.  A single fp32
+    step puts its rounding over h: the attention softmax alone left in fp32 gives 6e-4."""
+    g, names, P, cd, args = _fp64_training_case("train_tiny_sim")
+    with torch.enable_grad():
+        out = O.training_losses(P, cd, *args)
+        out["loss"].mean().backward()
+    assert out["pred"].dtype == torch.float64 and out["loss"].dtype == torch.float64
+    gen = torch.Generator().manual_seed(3)
+    h = 1e-6
+    for _ in range(3):
+        v = {k: torch.randn(P[k].shape, generator=gen, dtype=torch.float64) for k in names}
+
+        def f(s):
+            Q = dict(P)
+            for k in names:
+                Q[k] = P[k].detach() + s * v[k]
+            return float(O.training_losses(Q, cd, *args)["loss"].mean())
+
+        fd = (f(h) - f(-h)) / (2 * h)
+        ad = float(sum((P[k].grad * v[k]).sum() for k in names))
+        assert abs(fd - ad) <= 1e-7 * abs(ad), (fd, ad)
+
+
+def test_fp64_mode_gradients_vs_reference_autograd():
+    """The fp64 oracle's gradients against the reference's own fp32 backward pass (train_grads_sim): the same gates as
+    the fp32 oracle meets in test_training_gradients_vs_reference_autograd."""
+    g, names, P, cd, args = _fp64_training_case("train_grads_sim")
+    with torch.enable_grad():
+        out = O.training_losses(P, cd, *args)
+        out["loss"].mean().backward()
+    assert torch.allclose(out["loss"].detach().float(), g["loss"], rtol=2e-5)
+    assert sorted(names) == sorted(str(n) for n in g["grad_names"])
+    for k in names:
+        gr = P[k].grad.reshape(-1)
+        assert gr.dtype == torch.float64, k
+        ref = g["gsamp_" + k]
+        assert rel_l2(gr[::int(g["gstride_" + k])][:2048], ref) < 1e-4, k
+        assert abs(float(gr.norm()) - float(g["gnorm_" + k])) <= 1e-4 * float(g["gnorm_" + k]) + 1e-9, k
