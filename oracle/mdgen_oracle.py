@@ -417,32 +417,52 @@ def run_ipa(P, cfg, temb, mask_bl, start, end, aatype):
     return x
 
 
+def to_fp64(P, *xs):
+    """(P, xs) with every floating tensor in fp64 -- what compute_dtype "float64" does to the entry points' weights and inputs --
+    so that a test can run any single stage (embed, temb, run_ipa, trunk_layer, final_layer) in fp64."""
+    return {k: _cast(torch.float64, v) for k, v in P.items()}, _cast(torch.float64, xs)
+
+
+def embed(P, cfg, x, x_cond, x_cond_mask):
+    """latent_model.py:233-241: the token embedding, h0 without the IPA output."""
+    h = linear(P, "latent_to_emb", x)                                    # :233
+    if cfg.get("abs_pos_emb", False):
+        h = h + P["pos_embed"]                                           # :234-235 ([1,L,C] bcast over T)
+    return h + linear(P, "cond_to_emb", x_cond) + P["mask_to_emb.weight"][x_cond_mask]   # :240-241
+
+
+def temb(P, cfg, t):
+    """latent_model.py:243: the time embedding [B,1,C]."""
+    return t_embedder(P, t * cfg.get("time_multiplier", 100.0))[:, None]
+
+
+def final_layer(P, h, te):
+    """FinalLayer (layers.py:70-74): adaLN-modulated LayerNorm of the last residual stream -> latent velocity."""
+    mod = linear(P, "emb_to_latent.adaLN_modulation.1", F.silu(te))
+    shift, scale = mod.chunk(2, dim=-1)
+    return linear(P, "emb_to_latent.linear", modulate(ln(h), shift, scale))
+
+
 def forward(P, cfg, x, t, mask, start_frames, end_frames, x_cond, x_cond_mask, aatype, return_trace=False):
     """LatentMDGenModel.forward (latent_model.py:212-260), non-design path == forward_inference."""
     H = cfg["mha_heads"]
     dt = compute_dtype(cfg)
     if dt == torch.float64:
-        P = {k: _cast(dt, v) for k, v in P.items()}
-        x, t, mask, start_frames, end_frames, x_cond = _cast(dt, (x, t, mask, start_frames, end_frames, x_cond))
+        P, (x, t, mask, start_frames, end_frames, x_cond) = to_fp64(P, x, t, mask, start_frames, end_frames, x_cond)
         if torch.is_tensor(cfg.get("quat_sign")):
             cfg = dict(cfg, quat_sign=_cast(dt, cfg["quat_sign"]))
-    h = linear(P, "latent_to_emb", x)                                    # :233
-    if cfg.get("abs_pos_emb", False):
-        h = h + P["pos_embed"]                                           # :234-235 ([1,L,C] bcast over T)
-    h = h + linear(P, "cond_to_emb", x_cond) + P["mask_to_emb.weight"][x_cond_mask]   # :240-241
-    temb = t_embedder(P, t * cfg.get("time_multiplier", 100.0))[:, None]  # :243
+    h = embed(P, cfg, x, x_cond, x_cond_mask)
+    te = temb(P, cfg, t)
     trace = {}
     if cfg.get("prepend_ipa", True):
-        ipa_out = run_ipa(P, cfg, temb[:, 0], mask[:, 0], start_frames, end_frames, aatype)
+        ipa_out = run_ipa(P, cfg, te[:, 0], mask[:, 0], start_frames, end_frames, aatype)
         trace["ipa_out"] = ipa_out
         h = h + ipa_out[:, None]                                         # :245-246
     trace["h0"] = h
     for i in range(cfg["num_layers"]):
-        h = trunk_layer(P, f"layers.{i}.", h, temb, mask, H, cfg.get("debug_skip", 0))   # :248-249
+        h = trunk_layer(P, f"layers.{i}.", h, te, mask, H, cfg.get("debug_skip", 0))   # :248-249
         trace[f"h{i + 1}"] = h
-    mod = linear(P, "emb_to_latent.adaLN_modulation.1", F.silu(temb))    # layers.py:70-74
-    shift, scale = mod.chunk(2, dim=-1)
-    out = linear(P, "emb_to_latent.linear", modulate(ln(h), shift, scale))
+    out = final_layer(P, h, te)
     if return_trace:
         return out, trace
     return out

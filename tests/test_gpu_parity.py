@@ -14,6 +14,9 @@ import torch
 
 from conftest import ROOT, load_golden, weights_for, rel_l2, model_config_from
 
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import layer_parity as LP  # noqa: E402  (per-layer, per-row parity against the fp64 oracle)
+
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 TOL_FWD = 1e-2
@@ -128,6 +131,7 @@ def test_forward_vs_oracle_shapes(shape):
     print(shape, {k: f"{v:.2e}" for k, v in rep.items()})
     assert torch.isfinite(out).all()
     assert rep["out"] < TOL_FWD and rep["ipa_out"] < TOL_FWD and rep[f"h{cfg.num_layers}"] < TOL_FWD
+    LP.check_forward(str(shape), cfg, sd, kw, out, tr)
 
 
 def test_forward_tps_vs_oracle_with_reference_inputs():
@@ -161,6 +165,7 @@ def test_forward_tps_vs_oracle_with_reference_inputs():
     assert torch.isfinite(out).all()
     for k in ("ipa_out", "h0", f"h{cfg.num_layers}", "out"):
         assert rep[k] < TOL_FWD, (k, rep[k])
+    LP.check_forward("fwd_full_tps", cfg, sd, kw, out, tr, cd=c)
     # (b) the REFERENCE's own output, directly: the caller hands over the reference's to_tensor_7() outputs (fixture key
     # `rel7`, latent_model.py:194-195 run by oracle/gen_golden.py; quaternion sign as eigh chose it there) through the
     # `rel7` argument of mdgen_denoiser_forward -- what a drop-in caller holding a reference-trained checkpoint does
@@ -625,6 +630,7 @@ def test_forward_cfg4_full_size_vs_reference_and_oracle():
     print("cfg-4 full vs oracle (all elements):", {k: f"{v:.2e}" for k, v in rep2.items()})
     for k in ("ipa_out", "h0", f"h{nl}", "out"):
         assert rep2[k] < TOL_FWD, (k, rep2[k])
+    LP.check_forward("cfg-4 full", cfg, sd, kw, out, tr)
     # padded residues never influence the valid ones: same call with garbage in the padded inputs
     x2 = inp["x"].clone()
     x2[:, :, L - n_pad:] = 1e3
@@ -693,6 +699,8 @@ def test_forward_headline_regime_vs_reference_and_oracle(name):
         print(f"{name} {prec} vs oracle (all elements):", {k: f"{v:.2e}" for k, v in rep2.items()})
         for k, v in list(rep.items()) + list(rep2.items()):
             assert v < (3 * tol if k == "out_worst_frame" else tol), (prec, k, v)
+        if prec != "fp32":
+            LP.check_forward(f"{name} {prec}", cfg, sd, kw, out, tr)
         del m
     torch.cuda.empty_cache()
 
@@ -2616,6 +2624,7 @@ def test_small_launches_split_a_panel_over_workgroups_vs_oracle(shape):
         assert torch.isfinite(out).all()
         for k, v in rep.items():
             assert v < TOL_FWD, (key, k, v)
+        LP.check_forward(f"{shape} {key}", cfg, sd, kw, out, tr)
         split = key == "split"
         nl = cfg.num_layers
         assert (ran.get("proj_mlp@p8x3", 0) + ran.get("mlp@p8x3", 0) == nl) == split, ran
@@ -2688,6 +2697,7 @@ def test_panel_kernels_257_to_383_panels_vs_oracle(case):
     assert torch.isfinite(out).all()
     for k, v in rep.items():
         assert v < TOL_FWD, (k, v)
+    LP.check_forward(case, cfg, sd, kw, out, tr)
     nl = cfg.num_layers
     assert ran.get("proj_mlp@p4") == nl and "mlp" not in ran and "proj_mlp@p8" not in ran, ran   # k_mlp<3, true>, not k_mlp8 / k_mlp_rows
     if L > 8:
@@ -2879,6 +2889,7 @@ def test_headline_kernel_mix_at_B8_T1000_vs_oracle():
     assert torch.isfinite(out).all()
     for k, v in rep.items():
         assert v < TOL_FWD, (k, v)
+    LP.check_forward("B8 T1000 L4 forward", cfg, sd, kw, out, tr)
     want = {"flash_proj_T@q128": nl, "mlp": nl, "ln_qkv_T": nl, "attn_L_fused": nl, "embed": 1, "final_euler": 1}
     for k, n in want.items():
         assert ran.get(k) == n, (k, ran)
@@ -2910,10 +2921,11 @@ def test_headline_kernel_mix_at_B8_T1000_vs_oracle():
     for k, n in {"mlp@fold": 2 * (nl - 1), "mlp@fold+final+embed": 1, "mlp@fold+final": 1, "embed": 1, "embed_base": 1}.items():
         assert ran.get(k) == n, (k, ran)
     assert torch.equal(m.sample_euler(dkw["x"], 2, use_graph=True, **ekw), x2)
-    x2r = _oracle_two_euler_steps(sd, cfg, kw, v0=ref)
+    x2r = _oracle_two_euler_steps(sd, cfg, kw, cd=dict(O.cfg_dict(cfg), compute_dtype="float64"))   # (fp64)
     e2 = rel_l2((x2 - dkw["x"]).cpu(), x2r - kw["x"])
     print(f"B8 T1000 L4 two Euler steps (second step's embedding from the first step's MLP tail): x2 - x0 vs oracle {e2:.2e}")
     assert e2 < TOL_FWD
+    LP.check_euler("B8 T1000 L4 two Euler steps", x2 - dkw["x"], x2r - kw["x"])
 
 
 def test_sample_euler_B16_graph_eager_and_stream_counts_agree():
@@ -2962,7 +2974,8 @@ def test_dispatch_registry_case_vs_oracle(case):
         dkw["t"] = kw["t"].to(dkw["x"].device)
     # (two-sided model: the library's relative-frame quaternions carry w >= 0; the oracle is told to do the same)
     cd = dict(O.cfg_dict(cfg), quat_sign="w_nonneg") if tps else O.cfg_dict(cfg)
-    ref, rtr = O.forward(sd, cd, return_trace=True, **kw)
+    if not euler:
+        ref, rtr = O.forward(sd, cd, return_trace=True, **kw)
     m = LatentMDGenModel(cfg)
     m.load_state_dict(sd)
     copts = case.get("options") or {}
@@ -2988,7 +3001,7 @@ def test_dispatch_registry_case_vs_oracle(case):
         info = m.context_info
         m.profile(False)
         xg = m.sample_euler(dkw["x"], 2, use_graph=True, **ekw)   # the product's path: graph, sub-batch streams
-        d_ref = _oracle_two_euler_steps(sd, cfg, kw, v0=ref, cd=cd) - kw["x"]
+        d_ref = _oracle_two_euler_steps(sd, cfg, kw, cd=dict(cd, compute_dtype="float64")) - kw["x"]   # (fp64: also the per-row reference)
         rep = {"x2 - x0": rel_l2((xg - dkw["x"]).cpu(), d_ref), "eager": rel_l2((x2 - dkw["x"]).cpu(), d_ref)}
         want = dispatch_plan(B, T, L, n_steps=2, mode=2, tps=tps, ncu=info["ncu"], xcd_round_robin=bool(info["xcd_round_robin"]), options=copts)
     planned = dict(want["prepare"])
@@ -2999,6 +3012,10 @@ def test_dispatch_registry_case_vs_oracle(case):
     assert ran == planned, (case["name"], ran, planned)
     for k, e in rep.items():
         assert e < TOL_FWD, (case["name"], k, e)
+    if euler:
+        LP.check_euler(case["name"], xg - dkw["x"], d_ref)
+    else:
+        LP.check_forward(case["name"], cfg, sd, kw, out, tr, cd=cd)
 
 
 @pytest.mark.parametrize("shape", [(1, 256, 16, 49), (32, 4, 0, 49)], ids=["ATLAS_L256_S49", "shard_B32_L4_S49"])
@@ -3055,7 +3072,8 @@ def test_rccl_paths_execute_with_one_rank(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dist-selftest"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
+    line = [s for s in r.stdout.splitlines() if s.startswith('{"dist_selftest"')][-1]   # (RCCL's banner may follow it)
+    res = json.loads(line)
     print("bench.py --dist-selftest:", res)
     assert res["dist_selftest"] == "ok" and res["backend"] == "nccl" and res["world"] == 1
     s = socket.socket()
