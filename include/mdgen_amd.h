@@ -136,13 +136,11 @@ int32_t mdgen_ctx_finalize(mdgen_ctx* ctx, void* stream);
  *                      compute the NEXT step's token embedding (latent_model.py:233-246) from the state it has just updated and
  *                      writes it as that step's residual stream ("mlp@fold+final+embed"): steps 1 .. S-1 launch no k_embed (value 2;
  *                      1: the FinalLayer + Euler update only; workspace: mdgen_ws_layout.embase).
- *   "embed_split"      1 (default) / 0: the products of that embedding tail (W_l x, W_c x_cond: K = 21 / 28) on the bf16 MFMA with each operand
- *                      split into a bf16 pair hi + lo (16 mantissa bits per side, the lo x lo term dropped: 2^-17 of a product)
- *                      instead of v_mfma_f32_32x32x2_f32, which runs at a quarter of its nominal rate on gfx950.  0: the exact fp32 form.
- *   "fuse_proj"        the temporal attention's out-projection + gated residual (mha.py:397, latent_model.py:476) inside the
- *                      MLP kernel, ahead of the MLP: 0 off / 1 inside the row-owner kernel / 2 as a prologue phase of the
- *                      64-row panel kernel (k_mlp<3, true>; selects the panel kernel) / 3 (default) as 2 where the launch
- *                      takes the panel kernel anyway (fewer than 768 row tiles: one launch less per layer, +2 %).
+ *                      The products of that embedding tail (W_l x, W_c x_cond: K = 21 / 28) run on the bf16 MFMA with each operand
+ *                      split into a bf16 pair hi + lo (16 mantissa bits per side, the lo x lo term dropped: 2^-17 of a product).
+ *   "fuse_proj"        the temporal attention's out-projection + gated residual (mha.py:397, latent_model.py:476) as a prologue
+ *                      phase of the 64-row panel MLP kernel (k_mlp<3, true>), ahead of the MLP: 3 (default) where the launch
+ *                      takes the panel kernel (fewer than 768 row tiles, or mlp_path 0: one launch less per layer, +2 %), 0 off.
  *   "fuse_proj_qkv"    1 (default) / 0: residue axis on the tiled-attention path (L > 8): its out-projection + gated residual
  *                      (mha.py:397, latent_model.py:462) runs inside the temporal sub-layer's LN -> q, k, v kernel, whose panels
  *                      then normalise rows that are still in L2 (k_ln_qkv<false, true>; one launch and one HBM read of the

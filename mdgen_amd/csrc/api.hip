@@ -66,7 +66,6 @@ constexpr size_t kPackCC = (size_t)12 * kKS * 64;  // bf16x8 elements of a packe
 
 struct MhaW {
     bf16x8 *wq = nullptr, *wk = nullptr, *wv_flash = nullptr, *wv_small = nullptr, *wo = nullptr;
-    bf16x8* wo_stream = nullptr;   // W_o as the 288-fragment prefix of the row-owner MLP kernel's weight stream (proj_stream_table)
     float *bq = nullptr, *bk = nullptr, *bv_flash = nullptr, *bv_small = nullptr, *bo = nullptr;
     float *bias_k = nullptr, *bias_v = nullptr;
 };
@@ -113,11 +112,9 @@ struct mdgen_ctx {
     // fp32 small weights
     float *wl = nullptr, *bl = nullptr, *wc = nullptr, *bc = nullptr, *mask_emb = nullptr, *aa_emb = nullptr;
     float *wl_pack = nullptr, *wc_pack = nullptr;   // latent_to_emb / cond_to_emb in k_embed's operand order (launch_pack_embed)
-    float *wl_rows = nullptr, *wc_rows = nullptr;   // ... and in rows_embed_gemm's (the embedding as the tail of the last layer's MLP kernel)
     float* mask_delta = nullptr;                    // mask_to_emb[1] - mask_to_emb[0]
-    bf16x8 *wl_hi = nullptr, *wl_lo = nullptr, *wc_hi = nullptr, *wc_lo = nullptr;   // ... as bf16 pairs, K padded to 32 in kappa order
-    int opt_trace_tail = 0;     // measurement: mdgen_profile_phase_trace targets the row-owner MLP launch that carries both tails
-    int opt_embed_split = 1;    // the embedding tail's products on the bf16 MFMA with hi + lo operand pairs (0: fp32 MFMA, exact)
+    // ... as bf16 pairs, K padded to 32 in kappa order (the embedding as the tail of the last layer's MLP kernel: rows_embed_tail)
+    bf16x8 *wl_hi = nullptr, *wl_lo = nullptr, *wc_hi = nullptr, *wc_lo = nullptr;
     float *pos_embed = nullptr, *t_w0 = nullptr, *t_b0 = nullptr, *t_w2 = nullptr, *t_b2 = nullptr;
     float *wf7 = nullptr, *bf7 = nullptr, *wr7 = nullptr, *br7 = nullptr;
     float *ada_w = nullptr, *ada_b = nullptr;
@@ -131,7 +128,6 @@ struct mdgen_ctx {
     int *map_nat = nullptr, *map_qk = nullptr, *map_vflash = nullptr, *map_vsmall = nullptr, *map_fin = nullptr;
     int *perm_qk = nullptr, *perm_vsmall = nullptr;
     int* mlp_tab = nullptr;     // device copy of mlp_stream_table()
-    int* proj_tab = nullptr;    // device copy of proj_stream_table()
     std::vector<GraphEntry> graphs;
     bool inv_freq_set = false;
     bool prof_on = false;
@@ -146,8 +142,8 @@ struct mdgen_ctx {
     int opt_mlp_path = 1;       // MLP block: 0 resident-panel kernel (k_mlp), 1 row-owner kernel (k_mlp_rows) when the launch
                                 // fills the chip, 2 row-owner kernel always
     int opt_fuse_proj_qkv = 1;  // tiled residue axis (L > 8): its out-projection + gated residual runs inside the temporal q / k / v kernel
-    int opt_fuse_proj = 3;      // the temporal attention's out-projection inside the MLP kernel: 0 off, 1 row-owner kernel (same wall time),
-                                // 2 panel kernel always, 3 (default) panel kernel where the launch takes the panel kernel anyway (small N: +2 %)
+    int opt_fuse_proj = 3;      // the temporal attention's out-projection inside the panel MLP kernel: 0 off, 3 (default) where the launch
+                                // takes the panel kernel (small N: +2 %)
     int opt_panel_waves = 0;    // 64-row panel kernels with a four- and an eight-wave form (k_mlp / k_mlp8, k_ln_qkv<false> / k_ln_qkv8): 0 (default)
                                 // eight waves where a launch is at most one workgroup per CU, 4 / 8 force one form (tests, A/B runs)
     int ncu = 256;              // compute units of the device the context was created on (hipDeviceAttributeMultiprocessorCount)
@@ -321,15 +317,6 @@ static std::vector<int> mlp_stream_table() {
     return t;
 }
 constexpr int kMlpFrags = 2304;
-// Out-projection prefix of the fused kernel (k_mlp_rows<NW, true>): 288 fragments, k-step major (one block = the 12 feature
-// tiles of one k-step), natural k order inside a fragment.  Entry = 2 << 16 | feature tile << 8 | k-step.
-static std::vector<int> proj_stream_table() {
-    std::vector<int> t;
-    for (int ks = 0; ks < 24; ++ks)
-        for (int ft = 0; ft < 12; ++ft) t.push_back(2 << 16 | ft << 8 | ks);
-    return t;
-}
-constexpr int kProjFrags = 288;
 extern "C" int32_t mdgen_debug_mlp_stream_table(int32_t* out, int32_t capacity) {
     const std::vector<int> t = mlp_stream_table();
     if (!out || capacity < (int)t.size()) return fail(-1, "need room for %d entries", (int)t.size());
@@ -391,11 +378,9 @@ static int register_mha(mdgen_ctx* c, const std::string& pre, MhaW* m) {
         launch_gather_f32(data, c->map_vflash, 1.f, m->bv_flash, kC, s);
         launch_gather_f32(data, c->perm_vsmall, 1.f, m->bv_small, kC, s);
     });
-    if (int r = c->dalloc(&m->wo_stream, (size_t)kProjFrags * 64)) return r;
     SETTER(pre + "out_proj.weight", {
         WANT(kC, kC);
         launch_pack_rows(data, kC, c->map_nat, 12, kKS, 1.f, m->wo, s);
-        launch_pack_stream(data, kC, 2, c->proj_tab, kProjFrags, 1.f, 0, m->wo_stream, s);
     });
     SETTER(pre + "out_proj.bias", { WANT(kC); if (int r = copy_f32(m->bo, data, kC, s)) return r; });
     SETTER(pre + "bias_k", { WANT(kC); if (int r = copy_f32(m->bias_k, data, kC, s)) return r; });
@@ -490,14 +475,11 @@ extern "C" int32_t mdgen_ctx_create(mdgen_ctx** out, const mdgen_model_desc* d) 
     TRY(upload_ints(c, &c->map_vsmall, vs));
     TRY(upload_ints(c, &c->map_fin, fin));
     TRY(upload_ints(c, &c->mlp_tab, mlp_stream_table()));
-    TRY(upload_ints(c, &c->proj_tab, proj_stream_table()));
     TRY(upload_ints(c, &c->perm_qk, pqk));
     TRY(upload_ints(c, &c->perm_vsmall, pvs));
     TRY(c->dalloc(&c->wl, (size_t)kC * D));
     TRY(c->dalloc(&c->wl_pack, (size_t)kEmbPackFloats));
     TRY(c->dalloc(&c->wc_pack, (size_t)kEmbPackFloats));
-    TRY(c->dalloc(&c->wl_rows, (size_t)kEmbRowsFloats));
-    TRY(c->dalloc(&c->wc_rows, (size_t)kEmbRowsFloats));
     TRY(c->dalloc(&c->mask_delta, (size_t)kC));
     for (bf16x8** q : {&c->wl_hi, &c->wl_lo, &c->wc_hi, &c->wc_lo}) TRY(c->dalloc(q, (size_t)12 * 2 * 64));
     TRY(c->dalloc(&c->bl, (size_t)kC));
@@ -532,10 +514,10 @@ extern "C" int32_t mdgen_ctx_create(mdgen_ctx** out, const mdgen_model_desc* d) 
     TRY(c->dalloc(&c->bfin, (size_t)32));
     TRYHIP(hipMemset(c->bfin, 0, 32 * sizeof(float)));
 #undef TRYHIP
-    SETTER("latent_to_emb.weight", { WANT(kC, c->D); if (int r = copy_f32(c->wl, data, (size_t)kC * c->D, s)) return r; launch_pack_embed(c->wl, c->D, c->wl_pack, s); launch_pack_embed_rows(c->wl, c->D, c->wl_rows, s);
+    SETTER("latent_to_emb.weight", { WANT(kC, c->D); if (int r = copy_f32(c->wl, data, (size_t)kC * c->D, s)) return r; launch_pack_embed(c->wl, c->D, c->wl_pack, s);
         launch_pack_rows(c->wl, c->D, c->map_nat, 12, 2, 1.f, c->wl_hi, s, 1, 0); launch_pack_rows(c->wl, c->D, c->map_nat, 12, 2, 1.f, c->wl_lo, s, 1, 1); });
     SETTER("latent_to_emb.bias", { WANT(kC); if (int r = copy_f32(c->bl, data, kC, s)) return r; });
-    SETTER("cond_to_emb.weight", { WANT(kC, c->D); if (int r = copy_f32(c->wc, data, (size_t)kC * c->D, s)) return r; launch_pack_embed(c->wc, c->D, c->wc_pack, s); launch_pack_embed_rows(c->wc, c->D, c->wc_rows, s);
+    SETTER("cond_to_emb.weight", { WANT(kC, c->D); if (int r = copy_f32(c->wc, data, (size_t)kC * c->D, s)) return r; launch_pack_embed(c->wc, c->D, c->wc_pack, s);
         launch_pack_rows(c->wc, c->D, c->map_nat, 12, 2, 1.f, c->wc_hi, s, 1, 0); launch_pack_rows(c->wc, c->D, c->map_nat, 12, 2, 1.f, c->wc_lo, s, 1, 1); });
     SETTER("cond_to_emb.bias", { WANT(kC); if (int r = copy_f32(c->bc, data, kC, s)) return r; });
     SETTER("mask_to_emb.weight", { WANT(2, kC); if (int r = copy_f32(c->mask_emb, data, 2 * kC, s)) return r; launch_sub_f32(c->mask_emb + kC, c->mask_emb, c->mask_delta, kC, s); });
@@ -710,8 +692,7 @@ extern "C" int32_t mdgen_ctx_set_option(mdgen_ctx* c, const char* name, int32_t 
         if (value != 0 && value != 1) return fail(-2, "attention_path must be 0 (auto) or 1 (robust loop always)");
         c->opt_attn_path = value;
     } else if (n == "fuse_proj") {
-        if (value < 0 || value > 3)
-            return fail(-2, "fuse_proj must be 0 (off), 1 (inside the row-owner MLP kernel), 2 (inside the panel MLP kernel) or 3 (panel kernel where it runs anyway)");
+        if (value != 0 && value != 3) return fail(-2, "fuse_proj must be 0 (off) or 3 (inside the panel MLP kernel where that kernel runs)");
         c->opt_fuse_proj = value;
     } else if (n == "fuse_proj_qkv") {
         if (value != 0 && value != 1) return fail(-2, "fuse_proj_qkv must be 0 or 1");
@@ -765,11 +746,6 @@ extern "C" int32_t mdgen_ctx_set_option(mdgen_ctx* c, const char* name, int32_t 
     } else if (n == "mlp_fold") {
         if (value != 0 && value != 1) return fail(-2, "mlp_fold must be 0 or 1");
         c->opt_mlp_fold = value;
-    } else if (n == "trace_tail") {
-        c->opt_trace_tail = value != 0;
-    } else if (n == "embed_split") {
-        if (value != 0 && value != 1) return fail(-2, "embed_split must be 0 or 1");
-        c->opt_embed_split = value;
     } else if (n == "mlp_tail") {
         if (value < 0 || value > 2) return fail(-2, "mlp_tail must be 0 (off), 1 (FinalLayer + Euler update) or 2 (... + the next step's token embedding)");
         c->opt_mlp_tail = value;
@@ -1200,14 +1176,14 @@ static bool mlp_uses_rows(const mdgen_ctx* c, long nrows) {
     return c->opt_mlp_path == 2 || (c->opt_mlp_path == 1 && tiles >= 3L * c->ncu);   // (768 row tiles = 192 four-wave workgroups on the 256-CU part)
 }
 
-// `proj`: a deferred out-projection (attn_sublayer) to run inside the MLP kernel, ahead of the MLP
+// `proj`: a deferred out-projection (attn_sublayer) to run in the panel MLP kernel's prologue, ahead of the MLP
 // `fold_sl` >= 0 (trunk, gate fold active): index step * nl + layer of the folded stream / b2' of this launch
 // `tail` (last trunk layer; nullable): the FinalLayer's parameters; *tail_done = true when the launch ran it (folded row-owner form only)
 static int mlp_sublayer(const Run& r, const FfnW& f, float* h, long nrows, const ModMap& mm, int shift, int scale,
-                        int gate, bool trunk, const ProjParams* proj = nullptr, const bf16x8* wo_stream = nullptr, long fold_sl = -1,
+                        int gate, bool trunk, const ProjParams* proj = nullptr, long fold_sl = -1,
                         const FinalParams* tail = nullptr, bool* tail_done = nullptr, int next_step = -1, bool* next_h0 = nullptr) {
     if (int e = check_launch_rows(nrows)) return e;
-    const bool panel_fused = proj && proj->a_bf16 && r.c->opt_fuse_proj >= 2;   // (3: only handed a projection when the panel kernel runs anyway)
+    const bool panel_fused = proj && proj->a_bf16;   // (only handed a projection when the panel kernel runs anyway)
     if (!panel_fused && mlp_uses_rows(r.c, nrows)) {
         MlpRowsParams q{};
         bool tail_on = false, emb_on = false;
@@ -1220,12 +1196,7 @@ static int mlp_sublayer(const Run& r, const FfnW& f, float* h, long nrows, const
         q.wstream = (const unsigned char*)f.wstream;
         q.b1 = f.b1;
         q.b2 = f.b2;
-        if (proj && proj->a_bf16) {
-            q.o = proj->a_bf16;
-            q.wo_stream = (const unsigned char*)wo_stream;
-            q.bo = proj->bias;
-            q.gate_chunk_o = proj->gate_chunk;
-        } else if (fold_sl >= 0 && r.fold_ready && mm.group_stride == 0 && mm.step_stride == 0) {
+        if (fold_sl >= 0 && r.fold_ready && mm.group_stride == 0 && mm.step_stride == 0) {
             q.wstream = r.fold_streams + (size_t)fold_sl * kFoldStreamBytes;
             q.b2g = r.fold_b2g + (size_t)fold_sl * kC;
             if (tail && tail_done && r.c->opt_mlp_tail && tail->mm.group_stride == 0 && tail->mm.step_stride == 0) {
@@ -1240,14 +1211,10 @@ static int mlp_sublayer(const Run& r, const FfnW& f, float* h, long nrows, const
                 q.tail_out = tail->out;
                 *tail_done = true;
                 if (next_step >= 0 && next_h0 && r.embase_p && tail->euler) {   // ... and the next step's token embedding
-                    q.emb_wl = r.c->wl_rows;
-                    q.emb_wc = r.c->wc_rows;
-                    if (r.c->opt_embed_split) {
-                        q.emb_wl_hi = r.c->wl_hi;
-                        q.emb_wl_lo = r.c->wl_lo;
-                        q.emb_wc_hi = r.c->wc_hi;
-                        q.emb_wc_lo = r.c->wc_lo;
-                    }
+                    q.emb_wl_hi = r.c->wl_hi;
+                    q.emb_wl_lo = r.c->wl_lo;
+                    q.emb_wc_hi = r.c->wc_hi;
+                    q.emb_wc_lo = r.c->wc_lo;
                     q.emb_base = r.embase_p + (long)next_step * r.embase_step_stride;
                     q.emb_mdelta = r.c->mask_delta;
                     q.emb_xcond = r.x_cond;
@@ -1259,19 +1226,19 @@ static int mlp_sublayer(const Run& r, const FfnW& f, float* h, long nrows, const
                 }
             }
         }
-        if (trunk && r.c->phase_trace && (!r.c->opt_trace_tail || emb_on)) {   // (trace_tail: the launch with both tails is the one traced)
+        if (trunk && r.c->phase_trace) {   // one-shot: the next trunk MLP launch records its phase stamps
             q.trace = r.c->phase_trace;
             q.trace_cap = r.c->phase_trace_cap;
             r.c->phase_trace = nullptr;
         }
         // (class "mlp@fold": the folded form ran -- tests assert it)
         // ("mlp@fold+final": ... with the FinalLayer + Euler update as its tail)
-        { ProfScope ps(r.c, !trunk ? "ipa.mlp" : q.o ? "proj_mlp" : emb_on ? "mlp@fold+final+embed" : tail_on ? "mlp@fold+final" : q.b2g ? "mlp@fold" : "mlp", r.s); if (!g_dry) launch_mlp_rows(q, 4, r.s); }
+        { ProfScope ps(r.c, !trunk ? "ipa.mlp" : emb_on ? "mlp@fold+final+embed" : tail_on ? "mlp@fold+final" : q.b2g ? "mlp@fold" : "mlp", r.s); if (!g_dry) launch_mlp_rows(q, r.s); }
         LAUNCHCHK();
         return 0;
     }
     MlpParams p{};
-    if (proj && proj->a_bf16) {   // fuse_proj = 2: the deferred out-projection runs in the panel kernel's prologue
+    if (panel_fused) {   // the deferred out-projection runs in the panel kernel's prologue
         p.o = proj->a_bf16;
         p.wo = proj->w;
         p.bo = proj->bias;
@@ -1547,14 +1514,13 @@ static int denoise_step(const Run& r, int step, float* x, float* out, int euler,
             if (int er = attn_sublayer(r, w.mha_l, h, r.N, axL, mm, 0, 1, 2, mk, true, true, fuse_lt ? &def_l : nullptr)) return er;
         }
         ProjParams deferred{};
-        const bool fuse = c->opt_fuse_proj == 2 || (c->opt_fuse_proj == 1 && mlp_uses_rows(c, r.N)) ||
-                          (c->opt_fuse_proj == 3 && !mlp_uses_rows(c, r.N));
+        const bool fuse = c->opt_fuse_proj == 3 && !mlp_uses_rows(c, r.N);
         if (int er = attn_sublayer(r, w.mha_t, h, r.N, axT, mm, 3, 4, 5, mk, false, true, fuse ? &deferred : nullptr,
                                    def_l.a_bf16 ? &def_l : nullptr))
             return er;
         // the last layer's MLP may run the FinalLayer as its tail (then h is NOT written: not with a residual-stream trace)
         const bool last = i == c->nl - 1 && !trace_h;
-        if (int er = mlp_sublayer(r, w.ffn, h, r.N, mm, 6, 7, 8, true, &deferred, w.mha_t.wo_stream, (long)step * c->nl + i,
+        if (int er = mlp_sublayer(r, w.ffn, h, r.N, mm, 6, 7, 8, true, &deferred, (long)step * c->nl + i,
                                   last ? &f : nullptr, last ? &tail_done : nullptr, next_h0 ? step + 1 : -1, next_h0))
             return er;
         if (trace_h) HIPCHK(hipMemcpyAsync(trace_h + (size_t)(i + 1) * r.N * kC, h, hbytes, hipMemcpyDeviceToDevice, r.s));
@@ -1722,6 +1688,17 @@ static int euler_body(const Run& r_in, const std::vector<float>& tg, float* x) {
     return 0;
 }
 
+// The part of a graph's cache key that the run-time options give: every option that changes what a captured call launches,
+// four bits each (mdgen_ctx_set_option keeps every value below 16; precision is 16 or 32)
+static uint64_t graph_option_key(const mdgen_ctx* c) {
+    const int v[] = {c->opt_precision == 32, c->opt_attn_path, c->opt_residue_l4, c->opt_mlp_path, c->opt_fuse_proj,
+                     c->opt_fuse_proj_qkv, c->opt_flash_proj, c->opt_panel_waves, c->opt_flash_rotate, c->opt_flash_proj_form,
+                     c->opt_small_split, c->opt_mlp_fold, c->opt_mlp_tail};
+    uint64_t k = 0;
+    for (int x : v) k = k << 4 | (uint64_t)x;
+    return k;
+}
+
 // Replay the cached hipGraph for `key`, or capture `body` (which enqueues work on `s`, possibly forking onto the
 // context's side streams and joining back) into a new one, cache it (LRU, 8 entries) and launch it.
 static int replay_or_capture(mdgen_ctx* c, const std::vector<uint64_t>& key, hipStream_t s, const std::function<int()>& body) {
@@ -1790,8 +1767,7 @@ extern "C" int32_t mdgen_sample_euler(mdgen_ctx* c, const mdgen_shape* sh, int32
     std::vector<uint64_t> key = {0u, (uint64_t)sh->B, (uint64_t)sh->T, (uint64_t)sh->L, (uint64_t)S, (uint64_t)x,
                                  (uint64_t)mask, (uint64_t)start_rot, (uint64_t)start_trans, (uint64_t)end_rot,
                                  (uint64_t)end_trans, (uint64_t)x_cond, (uint64_t)x_cond_mask, (uint64_t)aatype,
-                                 (uint64_t)ws, (uint64_t)n_streams(r), (uint64_t)(c->opt_residue_l4 | c->opt_mlp_path << 8 | c->opt_fuse_proj << 12 | c->opt_fuse_proj_qkv << 20 | c->opt_flash_proj << 24 | (uint64_t)c->opt_panel_waves << 32 | (uint64_t)c->opt_flash_rotate << 36 | (uint64_t)c->opt_flash_proj_form << 40 | (uint64_t)c->opt_small_split << 44 | (uint64_t)c->opt_mlp_fold << 45 | (uint64_t)c->opt_mlp_tail << 46 | (uint64_t)c->opt_embed_split << 48), (uint64_t)c->opt_precision,
-                                 (uint64_t)c->opt_attn_path, (uint64_t)rel7};
+                                 (uint64_t)ws, (uint64_t)n_streams(r), graph_option_key(c), (uint64_t)rel7};
     return replay_or_capture(c, key, r.s, [&]() { return euler_body(r, tg, x); });
 }
 
@@ -1850,9 +1826,8 @@ extern "C" int32_t mdgen_rollout_euler(mdgen_ctx* c, const mdgen_shape* sh, int3
     std::vector<uint64_t> key = {1u, (uint64_t)sh->B, (uint64_t)sh->T, (uint64_t)sh->L, (uint64_t)S, (uint64_t)n_blocks,
                                  (uint64_t)zs, (uint64_t)mask, (uint64_t)cond_rots, (uint64_t)cond_trans,
                                  (uint64_t)cond_torsions, (uint64_t)seqres, (uint64_t)x_cond, (uint64_t)x_cond_mask,
-                                 (uint64_t)atom14, (uint64_t)ws, (uint64_t)n_streams(r), (uint64_t)(c->opt_residue_l4 | c->opt_mlp_path << 8 | c->opt_fuse_proj << 12 | c->opt_fuse_proj_qkv << 20 | c->opt_flash_proj << 24 | (uint64_t)c->opt_panel_waves << 32 | (uint64_t)c->opt_flash_rotate << 36 | (uint64_t)c->opt_flash_proj_form << 40 | (uint64_t)c->opt_small_split << 44 | (uint64_t)c->opt_mlp_fold << 45 | (uint64_t)c->opt_mlp_tail << 46 | (uint64_t)c->opt_embed_split << 48),
-                                 (uint64_t)t.default_frames, (uint64_t)t.atom37_to_atom14, (uint64_t)c->opt_precision,
-                                 (uint64_t)c->opt_attn_path};
+                                 (uint64_t)atom14, (uint64_t)ws, (uint64_t)n_streams(r), graph_option_key(c),
+                                 (uint64_t)t.default_frames, (uint64_t)t.atom37_to_atom14};
     return replay_or_capture(c, key, r.s, body);
 }
 

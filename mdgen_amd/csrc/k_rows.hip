@@ -163,8 +163,7 @@ __device__ __forceinline__ void gelu_stage_q(MlpPipe& m, f32x16 (&a1r)[2], int g
 // One block of 12 fragments, one fenced scheduling region per fragment: [look-ahead LDS read of fragment I + PF]
 // [MFMA of fragment I] [a slice of the GELU group] (+ this wave's share of the ring refill).
 //   I0    ring-relative index of its first fragment (multiple of 12)
-//   KIND  0: X block (k-steps 6 KI .. 6 KI + 5 of both hidden tiles -> a1w), 1: Y block (k-step KI of the chunk, 12 feature tiles),
-//         2: out-projection block (k-step KI of the 24, 12 feature tiles, B operand = xf[KI])
+//   KIND  0: X block (k-steps 6 KI .. 6 KI + 5 of both hidden tiles -> a1w), 1: Y block (k-step KI of the chunk, 12 feature tiles)
 //   GG    GELU group riding along (reads a1r, writes hfw), or -1.  REARM: afterwards its four accumulator registers are
 //         re-armed with the bias at b1n (LDS; the same group of the chunk two further on)
 //   BARVM >= 0: the block opens a ring slot: barrier with that vmcnt first
@@ -186,10 +185,8 @@ __device__ __forceinline__ void pipe_block(MlpPipe& m, const bf16x8 (&xf)[24], f
         if (KIND == 0) {
             const int ks = 6 * KI + (q >> 1), tile = q & 1;
             a1w[tile] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(m.wr[I % kWRing], xf[ks], a1w[tile], 0, 0, 0);
-        } else if (KIND == 1) {
+        } else {
             m.y[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(m.wr[I % kWRing], hfr[KI], m.y[q], 0, 0, 0);
-        } else {   // KIND 2: out-projection, k-step KI of the attention output rows (xf), 12 feature tiles
-            m.y[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(m.wr[I % kWRing], xf[KI], m.y[q], 0, 0, 0);
         }
 #ifndef MDGEN_DEV_ROWS_NOGELU   // (experiment build, timing only: the main loop without its VALU work)
         if (GG >= 0) gelu_stage_q<REARM>(m, a1r, GG, q, hfw);
@@ -212,43 +209,27 @@ __device__ __forceinline__ void gelu_group_plain(MlpPipe& m, f32x16 (&a1r)[2], c
     st[i] = __builtin_amdgcn_s_memtime();              \
     __builtin_amdgcn_sched_barrier(0)
 
-// out-projection blocks KS .. 23 of the fused form (one block = one k-step of the attention output rows x 12 feature tiles;
-// two blocks per ring slot, slot s = global slot: barrier + refill of slot s + 3)
-template <int NW, int KS, class WS>
-__device__ __forceinline__ void proj_blocks(MlpPipe& m, const bf16x8 (&xf)[24], const unsigned char* ring_lane, const WS& ws) {
-    constexpr int FPW = WS::FPW;
-    pipe_block<NW, (12 * KS) % kRingFrags, 2, KS, -1, false, (KS & 1) == 0 ? FPW : -1, true>(
-        m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], nullptr, ring_lane, ws, KS / 2 + 3);
-    if constexpr (KS + 1 < 24) proj_blocks<NW, KS + 1>(m, xf, ring_lane, ws);
-}
-
-// PROJ: the temporal attention's out-projection + gated residual (mha.py:397, latent_model.py:476) runs in the same kernel,
-// ahead of the MLP, on the same 32 rows per wave: the attention output rows are loaded straight into B-operand fragments,
-// the 288 fragments of W_o lead the weight stream (12 ring slots = three ring revolutions), the updated residual rows are
-// written once and KEPT in registers for the MLP's LayerNorm -- one kernel, one read of the rows less (98 MB at cfg-2), no
-// launch boundary (k_proj<0> was an HBM-bound 58 us kernel of its own).
 // MODLDS: every 32-row tile of the launch lies inside one modulation group (launch_mlp_rows checks the ModMap): the wave's
 // scale / shift / gate chunks are DMA'd into LDS once and read from there (rows_norm_lds, rows_gate_residual_lds).
-// FOLD (round 6; MODLDS, no PROJ): the launch's gate is one vector and is folded into the stream's W2 fragments and into b2'
+// FOLD (round 6; MODLDS): the launch's gate is one vector and is folded into the stream's W2 fragments and into b2'
 // (p.b2g; k_pack_fold, once per call): the fc2 accumulators start from the residual rows + b2' (rows_norm_lds_fold) and the
 // epilogue only stores -- one HBM read of the rows instead of two (98 MB of 332 per launch at cfg-2).
 // TAIL (with FOLD; the trunk's last layer in a sampling call): the FinalLayer -- LN + modulate, Linear C -> D, Euler update of x
 // (layers.py:57-74, integrators.py:106; k_final's work) -- runs on the updated rows straight from the accumulators (the row image is
 // the LayerNorm image) and the rows are never stored.
-template <int NW, bool PROJ, bool MODLDS, bool FOLD = false, bool TAIL = false>
+template <int NW, bool MODLDS, bool FOLD = false, bool TAIL = false>
 __global__ __launch_bounds__(NW * 64, 1) void k_mlp_rows(const MlpRowsParams p) {
-    static_assert(!FOLD || (MODLDS && !PROJ), "the folded form: one modulation group per launch, no fused out-projection");
+    static_assert(!FOLD || MODLDS, "the folded form: one modulation group per launch");
     static_assert(!TAIL || FOLD, "the tail runs on the folded form's accumulators");
     // ring | fc1 bias | slack: the last re-arm reads the (non-existent) chunk 24 | per wave: scale, shift, gate chunks (2 KiB slots)
     // | TAIL: the final layer's shift, scale chunks (2 KiB slots, shared by the waves)
     __shared__ __attribute__((aligned(1024))) unsigned char smem[kRingBytes + 8192 + NW * 6144 + (TAIL ? 4096 : 0)];
-    constexpr int NPRE = PROJ ? 12 : 0;   // ring slots of the out-projection ahead of the MLP stream
-    using WS = WStream<NW, NPRE>;
+    using WS = WStream<NW>;
     constexpr int FPW = WS::FPW;
     const int w = __builtin_amdgcn_readfirstlane(wave_id()), lane = lane_id(), hh = lane >> 5, n = lane & 31;
     unsigned long long st[8] = {};
     ROWS_STAMP(0);
-    WS ws{p.wstream, p.wo_stream, lds_addr(smem), (unsigned)lane * 16u, w};
+    WS ws{p.wstream, lds_addr(smem), (unsigned)lane * 16u, w};
     // fc1 bias -> LDS, six 1 KiB DMAs (wave w: pieces w, w + NW, ...), BEFORE the stream's: barrier 0 then certifies them too.
     // (A load + ds_write loop here cost two serialised memory round trips ahead of the row loads.)
 #pragma unroll
@@ -291,22 +272,7 @@ __global__ __launch_bounds__(NW * 64, 1) void k_mlp_rows(const MlpRowsParams p) 
     bf16x8 xf[24];
     MlpPipe m;
     const unsigned char* ring_lane = smem + lane * 16;
-    if (PROJ) {
-        rows_load_bf16(p.o, tok, xf);
-        rows_acc_init(m.y, p.bo);
-        ring_barrier<FPW>();   // barrier 0: slots 0 and 1 of the out-projection (and the fc1 bias table) have landed
-#pragma unroll
-        for (int i = 0; i < kWPF; ++i) m.wr[i] = *reinterpret_cast<const bf16x8*>(ring_lane + i * 1024);
-        // the first block's barrier is the one just passed: blocks 0 .. 23 open slots 0 .. 11 at their even members
-        pipe_block<NW, 0, 2, 0, -1, false, -1, true>(m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], nullptr, ring_lane, ws, 3);
-        proj_blocks<NW, 1>(m, xf, ring_lane, ws);
-        ROWS_STAMP(6);
-        f32x4 v[48];
-        rows_gate_residual_keep(m.y, tok, p.mm, p.gate_chunk_o, p.h, v);
-        ROWS_STAMP(7);
-        if (MODLDS) rows_norm_lds(v, tok, modl, modl + 512, 1e-6f, xf);
-        else rows_norm(v, tok, p.mm, p.shift_chunk, p.scale_chunk, 1e-6f, xf);
-    } else if (MODLDS) {
+    if (MODLDS) {
         f32x4 v[48];
         rows_load(p.h, tok, v);
         // the row loads AND this wave's modulation DMAs have landed (the asm keeps hipcc from lifting the LDS reads above it)
@@ -325,19 +291,19 @@ __global__ __launch_bounds__(NW * 64, 1) void k_mlp_rows(const MlpRowsParams p) 
     for (int i = 0; i < kWPF; ++i) m.wr[i] = *reinterpret_cast<const bf16x8*>(ring_lane + i * 1024);
     arm_chunk(m.a1[0], b1l);
     arm_chunk(m.a1[1], b1l + 64);
-    pipe_block<NW, 0, 0, 0, -1, false, -1, true>(m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], b1l, ring_lane, ws, NPRE + 3);
-    pipe_block<NW, 12, 0, 1, -1, false, -1, true>(m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], b1l, ring_lane, ws, NPRE + 3);
-    pipe_block<NW, 24, 0, 2, -1, false, FPW, true>(m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], b1l, ring_lane, ws, NPRE + 4);
-    pipe_block<NW, 36, 0, 3, -1, false, -1, true>(m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], b1l, ring_lane, ws, NPRE + 4);
+    pipe_block<NW, 0, 0, 0, -1, false, -1, true>(m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], b1l, ring_lane, ws, 3);
+    pipe_block<NW, 12, 0, 1, -1, false, -1, true>(m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], b1l, ring_lane, ws, 3);
+    pipe_block<NW, 24, 0, 2, -1, false, FPW, true>(m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], b1l, ring_lane, ws, 4);
+    pipe_block<NW, 36, 0, 3, -1, false, -1, true>(m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], b1l, ring_lane, ws, 4);
     // ---- P1: X(1) -> a1[1] with GELU(0): a1[0] -> hf[0] (even groups ride in the blocks, odd ones run between them);
     //          a1[0] is re-armed with the bias of chunk 2
-    pipe_block<NW, 48, 0, 0, 0, true, FPW, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], b1l + 128, ring_lane, ws, NPRE + 5);
+    pipe_block<NW, 48, 0, 0, 0, true, FPW, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], b1l + 128, ring_lane, ws, 5);
     gelu_group_plain<true>(m, m.a1[0], b1l + 128, 1, m.hf[0]);
-    pipe_block<NW, 60, 0, 1, 2, true, -1, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], b1l + 128, ring_lane, ws, NPRE + 5);
+    pipe_block<NW, 60, 0, 1, 2, true, -1, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], b1l + 128, ring_lane, ws, 5);
     gelu_group_plain<true>(m, m.a1[0], b1l + 128, 3, m.hf[0]);
-    pipe_block<NW, 72, 0, 2, 4, true, FPW, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], b1l + 128, ring_lane, ws, NPRE + 6);
+    pipe_block<NW, 72, 0, 2, 4, true, FPW, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], b1l + 128, ring_lane, ws, 6);
     gelu_group_plain<true>(m, m.a1[0], b1l + 128, 5, m.hf[0]);
-    pipe_block<NW, 84, 0, 3, 6, true, -1, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], b1l + 128, ring_lane, ws, NPRE + 6);
+    pipe_block<NW, 84, 0, 3, 6, true, -1, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], b1l + 128, ring_lane, ws, 6);
     gelu_group_plain<true>(m, m.a1[0], b1l + 128, 7, m.hf[0]);
     ROWS_STAMP(2);
     // ---- iterations c = 1 .. 22 (two per trip: the register double buffers a1 / hf alternate)
@@ -346,43 +312,43 @@ __global__ __launch_bounds__(NW * 64, 1) void k_mlp_rows(const MlpRowsParams p) 
         {   // odd c: X(c + 1) -> a1[0], GELU(c): a1[1] -> hf[1] (a1[1] re-armed for chunk c + 2), Y(c - 1) <- hf[0]
             const long s0 = 4 * c;
             const float* bn = b1l + 64 * (c + 2);
-            pipe_block<NW, 0, 0, 0, 0, true, FPW, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], bn, ring_lane, ws, NPRE + s0 + 3);
-            pipe_block<NW, 12, 1, 0, 1, true, -1, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], bn, ring_lane, ws, NPRE + s0 + 3);
-            pipe_block<NW, 24, 0, 1, 2, true, FPW, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], bn, ring_lane, ws, NPRE + s0 + 4);
-            pipe_block<NW, 36, 1, 1, 3, true, -1, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], bn, ring_lane, ws, NPRE + s0 + 4);
-            pipe_block<NW, 48, 0, 2, 4, true, FPW, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], bn, ring_lane, ws, NPRE + s0 + 5);
-            pipe_block<NW, 60, 1, 2, 5, true, -1, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], bn, ring_lane, ws, NPRE + s0 + 5);
-            pipe_block<NW, 72, 0, 3, 6, true, FPW, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], bn, ring_lane, ws, NPRE + s0 + 6);
-            pipe_block<NW, 84, 1, 3, 7, true, -1, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], bn, ring_lane, ws, NPRE + s0 + 6);
+            pipe_block<NW, 0, 0, 0, 0, true, FPW, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], bn, ring_lane, ws, s0 + 3);
+            pipe_block<NW, 12, 1, 0, 1, true, -1, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], bn, ring_lane, ws, s0 + 3);
+            pipe_block<NW, 24, 0, 1, 2, true, FPW, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], bn, ring_lane, ws, s0 + 4);
+            pipe_block<NW, 36, 1, 1, 3, true, -1, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], bn, ring_lane, ws, s0 + 4);
+            pipe_block<NW, 48, 0, 2, 4, true, FPW, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], bn, ring_lane, ws, s0 + 5);
+            pipe_block<NW, 60, 1, 2, 5, true, -1, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], bn, ring_lane, ws, s0 + 5);
+            pipe_block<NW, 72, 0, 3, 6, true, FPW, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], bn, ring_lane, ws, s0 + 6);
+            pipe_block<NW, 84, 1, 3, 7, true, -1, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], bn, ring_lane, ws, s0 + 6);
         }
         {   // even c + 1: X(c + 2) -> a1[1], GELU(c + 1): a1[0] -> hf[0] (a1[0] re-armed for chunk c + 3), Y(c) <- hf[1]
             const long s0 = 4 * (c + 1);
             const float* bn = b1l + 64 * (c + 3);   // c + 3 = 24 on the last trip: slack behind the table, never consumed
-            pipe_block<NW, 0, 0, 0, 0, true, FPW, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], bn, ring_lane, ws, NPRE + s0 + 3);
-            pipe_block<NW, 12, 1, 0, 1, true, -1, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], bn, ring_lane, ws, NPRE + s0 + 3);
-            pipe_block<NW, 24, 0, 1, 2, true, FPW, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], bn, ring_lane, ws, NPRE + s0 + 4);
-            pipe_block<NW, 36, 1, 1, 3, true, -1, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], bn, ring_lane, ws, NPRE + s0 + 4);
-            pipe_block<NW, 48, 0, 2, 4, true, FPW, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], bn, ring_lane, ws, NPRE + s0 + 5);
-            pipe_block<NW, 60, 1, 2, 5, true, -1, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], bn, ring_lane, ws, NPRE + s0 + 5);
-            pipe_block<NW, 72, 0, 3, 6, true, FPW, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], bn, ring_lane, ws, NPRE + s0 + 6);
-            pipe_block<NW, 84, 1, 3, 7, true, -1, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], bn, ring_lane, ws, NPRE + s0 + 6);
+            pipe_block<NW, 0, 0, 0, 0, true, FPW, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], bn, ring_lane, ws, s0 + 3);
+            pipe_block<NW, 12, 1, 0, 1, true, -1, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], bn, ring_lane, ws, s0 + 3);
+            pipe_block<NW, 24, 0, 1, 2, true, FPW, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], bn, ring_lane, ws, s0 + 4);
+            pipe_block<NW, 36, 1, 1, 3, true, -1, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], bn, ring_lane, ws, s0 + 4);
+            pipe_block<NW, 48, 0, 2, 4, true, FPW, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], bn, ring_lane, ws, s0 + 5);
+            pipe_block<NW, 60, 1, 2, 5, true, -1, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], bn, ring_lane, ws, s0 + 5);
+            pipe_block<NW, 72, 0, 3, 6, true, FPW, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], bn, ring_lane, ws, s0 + 6);
+            pipe_block<NW, 84, 1, 3, 7, true, -1, true>(m, xf, m.a1[1], m.a1[0], m.hf[0], m.hf[1], bn, ring_lane, ws, s0 + 6);
         }
     }
     ROWS_STAMP(3);
     // ---- E0: Y(22) <- hf[0] with GELU(23): a1[1] -> hf[1] (slots 92, 93; slot 95 is the last one to fetch)
-    pipe_block<NW, 0, 1, 0, 0, false, FPW, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], b1l, ring_lane, ws, NPRE + 95);
+    pipe_block<NW, 0, 1, 0, 0, false, FPW, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], b1l, ring_lane, ws, 95);
     gelu_group_plain<false>(m, m.a1[1], b1l, 1, m.hf[1]);
-    pipe_block<NW, 12, 1, 1, 2, false, -1, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], b1l, ring_lane, ws, NPRE + 95);
+    pipe_block<NW, 12, 1, 1, 2, false, -1, true>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], b1l, ring_lane, ws, 95);
     gelu_group_plain<false>(m, m.a1[1], b1l, 3, m.hf[1]);
-    pipe_block<NW, 24, 1, 2, 4, false, FPW, false>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], b1l, ring_lane, ws, NPRE + 0);
+    pipe_block<NW, 24, 1, 2, 4, false, FPW, false>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], b1l, ring_lane, ws, 0);
     gelu_group_plain<false>(m, m.a1[1], b1l, 5, m.hf[1]);
-    pipe_block<NW, 36, 1, 3, 6, false, -1, false>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], b1l, ring_lane, ws, NPRE + 0);
+    pipe_block<NW, 36, 1, 3, 6, false, -1, false>(m, xf, m.a1[0], m.a1[1], m.hf[1], m.hf[0], b1l, ring_lane, ws, 0);
     gelu_group_plain<false>(m, m.a1[1], b1l, 7, m.hf[1]);
     // ---- E1: Y(23) <- hf[1] (slots 94, 95: everything has been requested; barrier 94 waits for all of it)
-    pipe_block<NW, 48, 1, 0, -1, false, 0, false>(m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], b1l, ring_lane, ws, NPRE + 0);
-    pipe_block<NW, 60, 1, 1, -1, false, -1, false>(m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], b1l, ring_lane, ws, NPRE + 0);
-    pipe_block<NW, 72, 1, 2, -1, false, 0, false>(m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], b1l, ring_lane, ws, NPRE + 0);
-    pipe_block<NW, 84, 1, 3, -1, false, -1, false, 12 - kWPF>(m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], b1l, ring_lane, ws, NPRE + 0);
+    pipe_block<NW, 48, 1, 0, -1, false, 0, false>(m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], b1l, ring_lane, ws, 0);
+    pipe_block<NW, 60, 1, 1, -1, false, -1, false>(m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], b1l, ring_lane, ws, 0);
+    pipe_block<NW, 72, 1, 2, -1, false, 0, false>(m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], b1l, ring_lane, ws, 0);
+    pipe_block<NW, 84, 1, 3, -1, false, -1, false, 12 - kWPF>(m, xf, m.a1[0], m.a1[1], m.hf[0], m.hf[1], b1l, ring_lane, ws, 0);
     ROWS_STAMP(4);
     // ---- gated residual
     if (TAIL) {
@@ -391,12 +357,12 @@ __global__ __launch_bounds__(NW * 64, 1) void k_mlp_rows(const MlpRowsParams p) 
         rows_final_tail(m.y, tok, fmod + 512, fmod, p.tail_w, p.tail_b, p.tail_D, p.tail_euler, p.tail_dt, p.tail_x, p.tail_out, xf, xnew);
         ROWS_STAMP(6);
         if (p.emb_base) {   // (uniform) the next step's token embedding, from the state just updated: that step launches no k_embed
-            rows_embed_tail(m.y, tok, xnew, EmbedTail{p.emb_wl, p.emb_wc, p.emb_wl_hi, p.emb_wl_lo, p.emb_wc_hi, p.emb_wc_lo, p.emb_base, p.emb_mdelta, p.emb_xcond, p.emb_cmask, p.emb_T, p.emb_L, p.tail_D});
+            rows_embed_tail(m.y, tok, xnew, EmbedTail{p.emb_wl_hi, p.emb_wl_lo, p.emb_wc_hi, p.emb_wc_lo, p.emb_base, p.emb_mdelta, p.emb_xcond, p.emb_cmask, p.emb_T, p.emb_L, p.tail_D});
             ROWS_STAMP(7);
-            rows_store<0, 12>(m.y, tok, p.h);
+            rows_write<0, 12>(m.y, tok, p.h);
         }
     } else if (FOLD) {
-        rows_store<0, 12>(m.y, tok, p.h);
+        rows_write<0, 12>(m.y, tok, p.h);
     } else if (MODLDS) {
         rows_gate_residual_lds<0, 6>(m.y, tok, modl + 1024, p.h);
         rows_gate_residual_lds<6, 12>(m.y, tok, modl + 1024, p.h);
@@ -417,7 +383,7 @@ __global__ __launch_bounds__(NW * 64, 1) void k_mlp_rows(const MlpRowsParams p) 
 // ---- weight-stream packing ------------------------------------------------------------------------------------------
 // dst fragment f (1 KiB = 64 lanes x 8 bf16) <- rows 32 tile .. + 31 of the matrix tab[f] names, K slice of k-step ks in
 // kappa order (rows.h).  tab[f] = mat << 16 | tile << 8 | ks; only entries with mat == which are written.
-// `kappa` = 0: natural K order k = 16 ks + 8 hh + j instead (operands whose B fragments are loaded from memory: the out-projection).
+// `kappa` = 0: natural K order k = 16 ks + 8 hh + j instead.
 // rowmap (nullable): packed row r reads source row rowmap[r].
 __global__ void k_pack_stream(const float* __restrict__ wsrc, int ld, int which, const int* __restrict__ tab, int nfrag,
                               float scale, int kappa, bf16x8* __restrict__ dst, const int* __restrict__ rowmap) {
@@ -497,28 +463,12 @@ void launch_pack_fold(const float* mod, long mod_step_stride, int S, int nl, con
     hipLaunchKernelGGL(k_pack_fold, dim3(2304 * 64 / 256, (unsigned)(S * nl)), dim3(256), 0, s, p);
 }
 
-__global__ void k_pack_embed_rows(const float* __restrict__ w, int D, float* __restrict__ pack) {
-    const int i = blockIdx.x * 256 + threadIdx.x;   // < 12 * NK4 * 64
-    const int nk4 = D <= 24 ? 3 : 4;
-    if (i >= 12 * nk4 * 64) return;
-    const int lane = i & 63, q = (i >> 6) % nk4, ft = (i >> 6) / nk4;
-    f32x4 v;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int f = 8 * q + 4 * (lane >> 5) + k;
-        v[k] = f < D ? w[(size_t)(32 * ft + (lane & 31)) * D + f] : 0.f;
-    }
-    reinterpret_cast<f32x4*>(pack)[i] = v;
-}
 __global__ void k_sub_f32(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ dst, int n) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) dst[i] = a[i] - b[i];
 }
 void launch_sub_f32(const float* a, const float* b, float* dst, int n, hipStream_t s) {
     hipLaunchKernelGGL(k_sub_f32, dim3((n + 255) / 256), dim3(256), 0, s, a, b, dst, n);
-}
-void launch_pack_embed_rows(const float* w, int D, float* pack, hipStream_t s) {
-    hipLaunchKernelGGL(k_pack_embed_rows, dim3(12), dim3(256), 0, s, w, D, pack);
 }
 __global__ __launch_bounds__(96) void k_embed_base(const float* __restrict__ bl, const float* __restrict__ bc, const float* __restrict__ mask_emb,
                                                    const float* __restrict__ pos_embed, const float* __restrict__ ipa_out, int BL, int L,
@@ -546,27 +496,16 @@ void launch_pack_stream(const float* w, int ld, int which, const int* tab, int n
                        rowmap);
 }
 
-template <int NW>
-static void launch_mlp_rows_nw(const MlpRowsParams& p, long tiles, hipStream_t s) {
-    const bool proj = p.o != nullptr;
+void launch_mlp_rows(const MlpRowsParams& p, hipStream_t s) {
+    constexpr int NW = 4;   // four waves per workgroup: the only form the orchestration launches
     // a 32-row tile never straddles two modulation groups: groups are whole tiles, or every group reads the same row
     const bool uni = p.mm.tokens_per_group % 32 == 0 || (p.mm.step_stride == 0 && p.mm.group_stride == 0);
-    const dim3 g((unsigned)((tiles + NW - 1) / NW)), b(NW * 64);
-    if (proj) {
-        if (uni) hipLaunchKernelGGL((k_mlp_rows<NW, true, true>), g, b, 0, s, p);
-        else hipLaunchKernelGGL((k_mlp_rows<NW, true, false>), g, b, 0, s, p);
-    } else {
-        if (p.b2g && p.tail_w) hipLaunchKernelGGL((k_mlp_rows<NW, false, true, true, true>), g, b, 0, s, p);
-        else if (p.b2g) hipLaunchKernelGGL((k_mlp_rows<NW, false, true, true>), g, b, 0, s, p);   // (the caller has checked: one modulation group)
-        else if (uni) hipLaunchKernelGGL((k_mlp_rows<NW, false, true>), g, b, 0, s, p);
-        else hipLaunchKernelGGL((k_mlp_rows<NW, false, false>), g, b, 0, s, p);
-    }
-}
-void launch_mlp_rows(const MlpRowsParams& p, int nw, hipStream_t s) {
     const long tiles = (p.nrows + 31) / 32;
-    // (the orchestration only uses four waves; the one- and two-wave instantiations of rounds 3-5 were dead weight in the build)
-    if (nw == 4) launch_mlp_rows_nw<4>(p, tiles, s);
-    else g_k32_launch_error = "launch_mlp_rows: only the four-wave workgroup is built";
+    const dim3 g((unsigned)((tiles + NW - 1) / NW)), b(NW * 64);
+    if (p.b2g && p.tail_w) hipLaunchKernelGGL((k_mlp_rows<NW, true, true, true>), g, b, 0, s, p);
+    else if (p.b2g) hipLaunchKernelGGL((k_mlp_rows<NW, true, true>), g, b, 0, s, p);   // (the caller has checked: one modulation group)
+    else if (uni) hipLaunchKernelGGL((k_mlp_rows<NW, true>), g, b, 0, s, p);
+    else hipLaunchKernelGGL((k_mlp_rows<NW, false>), g, b, 0, s, p);
 }
 
 }  // namespace mdg

@@ -80,15 +80,9 @@ struct MlpRowsParams {
     int shift_chunk, scale_chunk, gate_chunk;
     const unsigned char* wstream;   // 2304 fragments of 1 KiB
     const float *b1, *b2;
-    // fused out-projection of the preceding attention sub-layer (o != null): attention output rows, W_o as 288 fragments in
-    // consumption order (k-step major, natural k), its bias and gate chunk
-    const __bf16* o;
-    const unsigned char* wo_stream;
-    const float* bo;
-    int gate_chunk_o;
     unsigned long long* trace;      // measurement only: [wave][8] s_memtime stamps, or null
     long trace_cap;
-    // gate fold (non-null; o == null, every row of the launch shares the modulation row): `wstream` is the (step, layer) stream with
+    // gate fold (non-null; every row of the launch shares the modulation row): `wstream` is the (step, layer) stream with
     // the gate folded into fc2 and b2g = gate * b2 (launch_pack_fold): accumulators start from the residual rows, store-only epilogue
     const float* b2g;
     // tail (with b2g, the trunk's LAST layer): FinalLayer + Euler update (layers.py:57-74, integrators.py:106) run on the updated rows while
@@ -103,17 +97,13 @@ struct MlpRowsParams {
     float* tail_x;      // euler: state updated in place
     float* tail_out;    // !euler: velocity
     // ... and (emb_base != null; euler) the NEXT step's token embedding from the updated state (k_embed's work) written to h: see rows.h
-    // rows_embed_tail.  emb_wl / emb_wc: launch_pack_embed_rows; emb_base: the next step's base rows of this view (launch_embed_base)
-    const float *emb_wl, *emb_wc, *emb_base, *emb_mdelta, *emb_xcond;
-    const bf16x8 *emb_wl_hi, *emb_wl_lo, *emb_wc_hi, *emb_wc_lo;   // the weights as bf16 pairs (launch_pack_rows kappa = 1, part 0 / 1); null: exact fp32 form
+    // rows_embed_tail.  emb_base: the next step's base rows of this view (launch_embed_base)
+    const float *emb_base, *emb_mdelta, *emb_xcond;
+    const bf16x8 *emb_wl_hi, *emb_wl_lo, *emb_wc_hi, *emb_wc_lo;   // the weights as bf16 pairs (launch_pack_rows kappa = 1, part 0 / 1)
     const int64_t* emb_cmask;
     int emb_T, emb_L;
 };
-// latent_to_emb / cond_to_emb weight [384][D] -> [12 ft][NK4][64 lanes][4]: value (ft, q, lane, i) = W[32 ft + (lane & 31)][8 q + 4 (lane >> 5) + i]
-// (0 past D), NK4 = 3 (D <= 24) or 4: the A operands of rows_embed_gemm
-void launch_pack_embed_rows(const float* w, int D, float* pack, hipStream_t s);
 void launch_sub_f32(const float* a, const float* b, float* dst, int n, hipStream_t s);   // dst = a - b
-constexpr int kEmbRowsFloats = 12 * 4 * 64 * 4;
 // base[s][bl][c] = bl[c] + bc[c] + mask_emb[0][c] + (pos_embed ? pos_embed[l][c] : 0) + ipa_out[s][bl][c]   (S * BL rows)
 void launch_embed_base(const float* bl, const float* bc, const float* mask_emb, const float* pos_embed, const float* ipa_out, int S,
                        int BL, int L, float* base, hipStream_t s);
@@ -218,7 +208,7 @@ void launch_xcc_probe(int* out, int nblocks, hipStream_t s);
 void launch_ln_qkv_attn4(const QkvParams& p, bool fuse_proj, hipStream_t s, bool half = false);   // half: 32-row workgroups (fuse_proj only)
 void launch_proj(const ProjParams& p, int mode, hipStream_t s);
 void launch_mlp(const MlpParams& p, hipStream_t s, int waves = 4);
-void launch_mlp_rows(const MlpRowsParams& p, int nw, hipStream_t s);
+void launch_mlp_rows(const MlpRowsParams& p, hipStream_t s);
 constexpr int kMlpStreamFrags = 2304;   // 1 KiB fragments of one MLP weight stream (api.hip mlp_stream_table)
 // per-(step, layer) MLP streams with the step's gate folded into fc2 (+ b2g = gate * b2); S * nl streams, nl <= 8
 void launch_pack_fold(const float* mod, long mod_step_stride, int S, int nl, const int* goff, const float* const* w2,

@@ -71,24 +71,20 @@ __device__ __forceinline__ void ring_barrier() {
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(VM) : "memory");
 }
 
-// NW waves share the stream; the first NPRE slots come from `pre` (a second matrix in front of the main stream: the
-// out-projection ahead of the MLP), the rest from `src`.  Slot numbers are GLOBAL (prefix included); NPRE is a multiple of
-// the ring size, so a slot's ring position does not depend on it.
-template <int NW, int NPRE = 0>
+// NW waves share the stream `src`
+template <int NW>
 struct WStream {
-    static_assert(NPRE % kRingSlots == 0, "the prefix must cover whole ring revolutions");
     static constexpr int FPW = kSlotFrags / NW;   // DMAs per wave per slot
-    const unsigned char* src;   // main stream (uniform)
-    const unsigned char* pre;   // prefix stream (uniform; unused when NPRE == 0)
+    const unsigned char* src;   // the stream (uniform)
     unsigned ring;              // LDS byte address of the ring
     unsigned voff;              // lane * 16
     int w;                      // wave index (uniform)
-    // the D-th (0 .. FPW - 1) DMA of this wave for global slot `slot`; DMAs are grouped in fours that share an M0 value
-    // and a source base (the statements of a group must follow each other with no other M0 writer in between)
+    // the D-th (0 .. FPW - 1) DMA of this wave for slot `slot`; DMAs are grouped in fours that share an M0 value and a source
+    // base (the statements of a group must follow each other with no other M0 writer in between)
     template <int D>
     __device__ __forceinline__ void issue(long slot) const {
         const int f = w * FPW + (D & ~3);
-        const unsigned char* base = (NPRE > 0 && slot < NPRE) ? pre + slot * kSlotBytes : src + (slot - NPRE) * kSlotBytes;
+        const unsigned char* base = src + slot * kSlotBytes;
         dma_frag<(D & 3) * 1024, (D & 3) == 0>(base + f * 1024, voff, ring + ((unsigned)slot & 3u) * kSlotBytes + f * 1024);
     }
     template <int D0 = 0>
@@ -289,7 +285,7 @@ __device__ __forceinline__ void rows_norm_lds_fold(const f32x4 (&v)[48], int tok
 
 // ... and its epilogue: h[tok][32 ft + 8 a + 4 hh + j] = y[ft][4 a + j], stores only
 template <int FT0, int FT1>
-__device__ __forceinline__ void rows_store(const f32x16 (&y)[12], int tok, float* __restrict__ h) {
+__device__ __forceinline__ void rows_write(const f32x16 (&y)[12], int tok, float* __restrict__ h) {
     const int hh = lane_id() >> 5;
     const unsigned tokc = tok < 0 ? 0u : (unsigned)tok;
     unsigned char* hb = reinterpret_cast<unsigned char*>(h);
@@ -352,15 +348,14 @@ __device__ __forceinline__ void rows_final_tail(const f32x16 (&y)[12], int tok, 
 
 // The NEXT step's token embedding from the state the tail has just updated (k_embed's work, latent_model.py:233-246):
 //   h0[tok] = W_l x_new + [W_c x_cond] + (b_l + b_c + mask_to_emb[0] + pos_embed[l] + ipa_out[step + 1][b, l])  + [mask delta]
-// computed transposed on the fp32 MFMA (v_mfma_f32_32x32x2_f32, exact fp32 products as k_embed): A = the weight (lane m = output
-// feature of the tile, k = hh), B = the state -- and the B operand of k-step j IS xnew[j]: the weights are packed with their K
-// dimension in the order the FinalLayer's accumulators hold the features (api.hip launch_pack_embed_rows).  The accumulators
-// start from the per-(step, b, l) base row (k_embed_base, once per call) loaded as a row image; result stored as rows of h.
-// wl / wc: [12 ft][NK4][64 lanes][4] floats, NK4 = 3 (D <= 24) or 4; base: rows of 384 floats, row = b * L + l of the launch's view.
-// The same product on the bf16 MFMA with both operands split into a bf16 pair hi + lo (16 mantissa bits each side; the lo x lo
+// computed transposed: A = the weight (lane m = output feature of the tile), B = the state -- and the B operand of k-step s IS
+// xnew[8 s .. 8 s + 7]: the weights are packed with their K dimension in the order the FinalLayer's accumulators hold the features.
+// The accumulators start from the per-(step, b, l) base row (k_embed_base, once per call) loaded as a row image; result stored as
+// rows of h.  base: rows of 384 floats, row = b * L + l of the launch's view.
+// The products run on the bf16 MFMA with both operands split into a bf16 pair hi + lo (16 mantissa bits each side; the lo x lo
 // term, 2^-18 of the product, is dropped): 3 x 2 v_mfma_f32_32x32x16_bf16 per feature tile instead of 12 v_mfma_f32_32x32x2_f32 --
 // the fp32 MFMA runs at a quarter of its nominal rate on gfx950 (profiles/r06_experiments.txt #5: the 144 of them were 30 us of this
-// launch).  whi / wlo: [12 ft][2 k-steps][64 lanes] bf16x8, K (padded to 32) in kappa order: k-step s of a lane half IS xnew[8 s .. 8 s + 7].
+// launch).  whi / wlo: [12 ft][2 k-steps][64 lanes] bf16x8, K (padded to 32) in kappa order.
 __device__ __forceinline__ void rows_embed_gemm_split(f32x16 (&y)[12], const bf16x8* __restrict__ whi, const bf16x8* __restrict__ wlo,
                                                       const float (&xv)[16]) {
     const int lane = lane_id();
@@ -400,38 +395,15 @@ __device__ __forceinline__ void rows_embed_gemm_split(f32x16 (&y)[12], const bf1
         __builtin_amdgcn_sched_barrier(0);
     }
 }
-template <int NK4>
-__device__ __forceinline__ void rows_embed_gemm(f32x16 (&y)[12], const float* __restrict__ wrows, const float (&xv)[16]) {
-    const int lane = lane_id();
-    const f32x4* wp = reinterpret_cast<const f32x4*>(wrows) + lane;
-    f32x4 w[2][NK4];
-#pragma unroll
-    for (int q = 0; q < NK4; ++q) w[0][q] = wp[q * 64];
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int ft = 0; ft < 12; ++ft) {
-        if (ft + 1 < 12) {
-#pragma unroll
-            for (int q = 0; q < NK4; ++q) w[(ft + 1) & 1][q] = wp[((ft + 1) * NK4 + q) * 64];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < NK4; ++q)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) y[ft] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[ft & 1][q][i], xv[4 * q + i], y[ft], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
 struct EmbedTail {
-    const float *wl, *wc;        // packed latent_to_emb / cond_to_emb weights (rows order, fp32: the exact form)
-    const bf16x8 *wl_hi, *wl_lo, *wc_hi, *wc_lo;   // ... as bf16 pairs for rows_embed_gemm_split (null: the exact form runs)
+    const bf16x8 *wl_hi, *wl_lo, *wc_hi, *wc_lo;   // latent_to_emb / cond_to_emb weights as bf16 pairs for rows_embed_gemm_split
     const float* base;           // base rows of the NEXT step for this launch's view: [B_view * L][384]
     const float* mdelta;         // mask_to_emb[1] - mask_to_emb[0]  [384]
     const float* x_cond;         // [N][D]
     const int64_t* x_cond_mask;  // [N]
     int T, L, D;
 };
-// (computes into y; the caller stores the rows: rows_store)
+// (computes into y; the caller stores the rows: rows_write)
 __device__ __forceinline__ void rows_embed_tail(f32x16 (&y)[12], int tok, const float (&xnew)[16], const EmbedTail e) {
     const int lane = lane_id(), hh = lane >> 5;
     const unsigned tokc = tok < 0 ? 0u : (unsigned)tok;
@@ -453,16 +425,12 @@ __device__ __forceinline__ void rows_embed_tail(f32x16 (&y)[12], int tok, const 
         xc[r] = f < e.D && tok >= 0 ? v : 0.f;
     }
     const bool cm = tok >= 0 && e.x_cond_mask[tokc] != 0;
-    if (e.wl_hi) rows_embed_gemm_split(y, e.wl_hi, e.wl_lo, xnew);
-    else if (e.D <= 24) rows_embed_gemm<3>(y, e.wl, xnew);
-    else rows_embed_gemm<4>(y, e.wl, xnew);
+    rows_embed_gemm_split(y, e.wl_hi, e.wl_lo, xnew);
     bool anyc = false;
 #pragma unroll
     for (int r = 0; r < 16; ++r) anyc |= xc[r] != 0.f;
     if (__builtin_amdgcn_ballot_w64(anyc) != 0) {   // some token of the tile is conditioned (k_embed skips the product likewise)
-        if (e.wc_hi) rows_embed_gemm_split(y, e.wc_hi, e.wc_lo, xc);
-        else if (e.D <= 24) rows_embed_gemm<3>(y, e.wc, xc);
-        else rows_embed_gemm<4>(y, e.wc, xc);
+        rows_embed_gemm_split(y, e.wc_hi, e.wc_lo, xc);
     }
     if (__builtin_amdgcn_ballot_w64(cm) != 0) {     // mask_to_emb[1] instead of [0] for the tokens whose x_cond_mask is set
         const unsigned char* mb = reinterpret_cast<const unsigned char*>(e.mdelta) + hh * 16;
@@ -548,57 +516,6 @@ __device__ __forceinline__ void rows_gate_residual_lds(const f32x16 (&y)[12], in
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] += g[j] * y[ft][4 * a + j];
         if (tok >= 0) *reinterpret_cast<f32x4*>(hb + off + 32u * (unsigned)(FT0 * 4 + i)) = o;
-    }
-}
-
-// The same update, keeping the updated rows in registers (rows_load's image) for the LayerNorm of the NEXT sub-layer: the
-// residual stream is written (the next epilogue needs it back) but not read again by the next prologue.  The gate vectors
-// are requested one feature tile ahead (fenced: left alone hipcc either serialises a round trip per tile or hoists all 48).
-__device__ __forceinline__ void rows_gate_residual_keep(const f32x16 (&y)[12], int tok, const ModMap mm, int gate_chunk,
-                                                        float* __restrict__ h, f32x4 (&v)[48]) {
-    const int hh = lane_id() >> 5;
-    const unsigned tokc = tok < 0 ? 0u : (unsigned)tok;
-    unsigned char* hb = reinterpret_cast<unsigned char*>(h);
-    const unsigned off = tokc * (unsigned)(kC * 4) + (unsigned)hh * 16u;
-    const unsigned mo = tok < 0 ? 0u : (unsigned)mm.row_off(tokc);
-    const unsigned char* mb = reinterpret_cast<const unsigned char*>(mm.mod);
-    const unsigned og = (mo + (unsigned)(gate_chunk * kC)) * 4u + (unsigned)hh * 16u;
-    f32x4 g[2][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) g[0][a] = *reinterpret_cast<const f32x4*>(mb + og + 32u * a);
-#pragma unroll
-    for (int i = 0; i < 48; ++i) v[i] = *reinterpret_cast<const f32x4*>(hb + off + 32u * i);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int ft = 0; ft < 12; ++ft) {
-        if (ft + 1 < 12) {
-#pragma unroll
-            for (int a = 0; a < 4; ++a) g[(ft + 1) & 1][a] = *reinterpret_cast<const f32x4*>(mb + og + 32u * (4 * (ft + 1) + a));
-        }
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            f32x4 o = v[4 * ft + a];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] += g[ft & 1][a][j] * y[ft][4 * a + j];
-            v[4 * ft + a] = o;
-            if (tok >= 0) *reinterpret_cast<f32x4*>(hb + off + 32u * (4 * ft + a)) = o;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-// bf16 rows [token][384] (the attention kernel's output) -> B-operand fragments in NATURAL k order: lane (n, hh), k-step ks
-// = the 16 bytes at feature 16 ks + 8 hh of its row.  24 unconditional 16-byte loads.
-__device__ __forceinline__ void rows_load_bf16(const __bf16* __restrict__ o, int tok, bf16x8 (&xf)[24]) {
-    const int hh = lane_id() >> 5;
-    const unsigned tokc = tok < 0 ? 0u : (unsigned)tok;
-    const unsigned char* ob = reinterpret_cast<const unsigned char*>(o);
-    const unsigned off = tokc * (unsigned)(kC * 2) + (unsigned)hh * 16u;
-    const u32x4 z = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int ks = 0; ks < 24; ++ks) {
-        const u32x4 t = *reinterpret_cast<const u32x4*>(ob + off + 32u * ks);
-        xf[ks] = __builtin_bit_cast(bf16x8, tok >= 0 ? t : z);
     }
 }
 

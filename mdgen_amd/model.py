@@ -121,8 +121,9 @@ class LatentMDGenModel:
         return self
 
     def set_option(self, name: str, value: int):
-        """Library run-time options (include/mdgen_amd.h `mdgen_ctx_set_option`): "streams", "residue_l4_path",
-        "attention_path", "mlp_path", "precision", "keep_fp32_weights"."""
+        """Library run-time options (include/mdgen_amd.h `mdgen_ctx_set_option`), e.g. "streams", "precision",
+        "keep_fp32_weights", "attention_path", "mlp_path", "residue_l4_path" (2 one kernel | 1 | 0 general path), "fuse_proj"
+        (3 panel MLP prologue | 0 off).  An unknown name or a value the library does not accept raises MdgenError."""
         check(lib.mdgen_ctx_set_option(self._ctx, name.encode(), int(value)))
         return self
 

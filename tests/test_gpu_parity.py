@@ -449,6 +449,9 @@ def test_residue_axis_paths_agree():
     from mdgen_amd._lib import MdgenError
     with pytest.raises(MdgenError):
         m.set_option("residue_l4_path", 7)
+    for name, value in (("fuse_proj", 1), ("fuse_proj", 2), ("embed_split", 0), ("trace_tail", 1)):
+        with pytest.raises(MdgenError):
+            m.set_option(name, value)
     with pytest.raises(MdgenError):
         m.set_option("no_such_option", 1)
 
@@ -2345,10 +2348,10 @@ def test_training_attention_kernels_unit(ln, layout):
                 assert e < (3e-2 if name == "dbias_k" else 1e-2), (ln, layout, leg, name, e)
 
 
-def test_row_owner_mlp_paths_agree():
+def test_mlp_and_qkv_kernel_forms_agree():
     """The MLP block has these forms: the 64-row resident-panel kernel with four waves (k_mlp<3>) or eight (k_mlp8; `panel_waves`),
-    each with or without the temporal out-projection as a prologue phase (`fuse_proj` 2), the row-owner kernel (`mlp_path` 2:
-    activations in registers, LDS-DMA weight stream) with or without the out-projection fused in front (`fuse_proj` 1); the
+    each with or without the temporal out-projection as a prologue phase (`fuse_proj` 3 with `mlp_path` 0), the row-owner kernel
+    (`mlp_path` 2: activations in registers, LDS-DMA weight stream); the
     temporal LN -> q, k, v kernel has a four- and an eight-wave form too (k_ln_qkv<false> / k_ln_qkv8) and, on the tiled residue
     axis, the residue out-projection as a prologue phase (`fuse_proj_qkv`).  Every form against the reference golden at the bf16
     gate and against each other (summation orders / GELU polynomial: a few 1e-3) -- and the profile report must name the
@@ -2360,9 +2363,9 @@ def test_row_owner_mlp_paths_agree():
     P4, P8 = {"panel_waves": 4}, {"panel_waves": 8, "small_split": 0}
     X8 = {"panel_waves": 8, "small_split": 1}   # (round 5) a panel's work over several workgroups: k_mlp8<., 3>, k_ln_qkv8<true>
     forms = (("panel4", dict(P4, mlp_path=0, fuse_proj=0), "mlp@p4"), ("panel8", dict(P8, mlp_path=0, fuse_proj=0), "mlp@p8"),
-             ("panel4+proj", dict(P4, mlp_path=0, fuse_proj=2), "proj_mlp@p4"), ("panel8+proj", dict(P8, mlp_path=0, fuse_proj=2), "proj_mlp@p8"),
-             ("panel8 split", dict(X8, mlp_path=0, fuse_proj=0), "mlp@p8x3"), ("panel8+proj split", dict(X8, mlp_path=0, fuse_proj=2), "proj_mlp@p8x3"),
-             ("rows", {"mlp_path": 2, "fuse_proj": 0, "mlp_fold": 0}, "mlp"), ("rows+proj", {"mlp_path": 2, "fuse_proj": 1}, "proj_mlp"),
+             ("panel4+proj", dict(P4, mlp_path=0, fuse_proj=3), "proj_mlp@p4"), ("panel8+proj", dict(P8, mlp_path=0, fuse_proj=3), "proj_mlp@p8"),
+             ("panel8 split", dict(X8, mlp_path=0, fuse_proj=0), "mlp@p8x3"), ("panel8+proj split", dict(X8, mlp_path=0, fuse_proj=3), "proj_mlp@p8x3"),
+             ("rows", {"mlp_path": 2, "fuse_proj": 0, "mlp_fold": 0}, "mlp"),
              # (round 6) a forward of B = 1 shares t: the gate-folded form of the row-owner kernel (option mlp_fold, default on)
              ("rows fold", {"mlp_path": 2, "fuse_proj": 0}, "mlp@fold|mlp"),
              ("no-qkv-prologue p4", dict(P4, mlp_path=0, fuse_proj=0, fuse_proj_qkv=0), "ln_qkv_T"),
@@ -2407,7 +2410,7 @@ def test_row_owner_mlp_paths_agree():
                 assert ("projL_qkvT" in ran) == (L_ > 8 and T_ > 8), ran   # (neither golden has both: test_panel_kernels_257_to_383_panels_vs_oracle does)
             del m
         assert rel_l2(outs["panel8"], outs["panel4"]) < 6e-3 and rel_l2(outs["panel8+proj"], outs["panel4+proj"]) < 6e-3
-        assert rel_l2(outs["rows"], outs["panel4"]) < 6e-3 and rel_l2(outs["rows+proj"], outs["rows"]) < 6e-3
+        assert rel_l2(outs["rows"], outs["panel4"]) < 6e-3
         assert rel_l2(outs["rows fold"], outs["rows"]) < 3e-3
         assert rel_l2(outs["panel4+proj"], outs["panel4"]) < 6e-3
         assert rel_l2(outs["no-qkv-prologue p8"], outs["no-qkv-prologue p4"]) < 6e-3
@@ -2708,9 +2711,9 @@ def test_panel_kernels_257_to_383_panels_vs_oracle(case):
     assert (out.cpu() - ref).abs().max() < 0.1 * ref.abs().max()
 
 
-def test_two_stream_views_in_the_panel_window_match_one_stream():
+def test_two_stream_panel_views_match_one_stream():
     """sample_euler B 10 x T 1000 x L 4 with `streams` 2 = two views of B 5 (313 panels each: k_mlp<3, true>, k_ln_qkv<false>)
-    against one stream -- (a) with the same kernels forced (`mlp_path` 0, `fuse_proj` 2: bit-identical, a panel's arithmetic does
+    against one stream -- (a) with the same kernels forced (`mlp_path` 0, `fuse_proj` 3: bit-identical, a panel's arithmetic does
     not depend on the launch it is in) and (b) with the defaults (one view of 625 panels takes the row-owner MLP: rounding level)."""
     from mdgen_amd.config import ModelConfig
     from mdgen_amd.model import LatentMDGenModel
@@ -2733,7 +2736,7 @@ def test_two_stream_views_in_the_panel_window_match_one_stream():
     # (`flash_proj_form` 4 in the pair that must agree bit for bit: by shape a 5-sample view takes the 64-query fused attention kernel
     # and the 10-sample launch the 128-query one, which rotates its key-tile walk by 128-query chunks -- another order of the same sum)
     for key, opts in (("two streams", {"streams": 2, "flash_proj_form": 4}),
-                      ("one stream, same kernels", {"streams": 1, "mlp_path": 0, "fuse_proj": 2, "flash_proj_form": 4}),
+                      ("one stream, same kernels", {"streams": 1, "mlp_path": 0, "fuse_proj": 3, "flash_proj_form": 4}),
                       ("one stream, defaults", {"streams": 1})):
         m = LatentMDGenModel(cfg)
         m.load_state_dict(sd)
