@@ -179,30 +179,9 @@ int32_t mdgen_ctx_finalize(mdgen_ctx* ctx, void* stream);
  *                      the attention's q k^T / p v and their backward): 32 (default) fp32, the exact mode; 16 rounded to
  *                      bf16 on the MFMA, fp32 accumulation, fp32 master weights and activations (train.py:13
  *                      set_float32_matmul_precision('medium')); softmax, LayerNorm, reductions stay fp32, GELU to 5e-6.
- *   "train_attn_form"  1 (default) / 0: with train_precision 16, attention axes of 129 .. 256 positions (the ATLAS training shapes)
- *                      run their backward pass in ONE launch of one workgroup per (sequence, head) that converts the sequence's
- *                      q, k, v, dO to bf16 tiles in LDS once and runs the query pass and the key pass out of LDS
- *                      (k16_attn_bwd_seq: the query pass and the key pass of a sequence as neighbouring workgroups of one XCD, each
- *                      with the other side's rows resident) instead of the chunked pair k16_attn_bwd_q / _kv; the forward likewise
- *                      (k16_attn_seq); these kernels apply RoPE to q, k while they convert them, so no RoPE pass is launched for
- *                      such an axis.  Same products; q is rounded to bf16 after the factor log2(e) (scores in log2 units), the
- *                      rotation uses the hardware sine / cosine (3e-5 rad); 0 keeps the chunked kernels for every length.
- *                      586 -> 419 us per backward launch, 28.9 -> 27.4 ms per step at cfg-5's per-GPU size.
- *   "train_defer_gate" 1 (default) / 0: forward pass of mdgen_train_forward_backward, trunk layers: a sub-layer does not apply its gated
- *                      residual update h += gate * u in a pass of its own; the next sub-layer's LayerNorm launch forms x + gate * u in
- *                      registers, writes it to the tape and normalises it (k32_gate_ln_mod); the stream is materialised once, after
- *                      the last layer.  Same arithmetic per element; 26.9 -> 25.9 ms per step at cfg-5's per-GPU size.
- *   "train_turn_ahead" 1 (default) / 0: with train_streams 2 and train_precision 16, the turned weights of the dX products too small
- *                      for the streamed kernel (W^T through k32_transpose: the IPA stack's 256-row launches, ~50 per step) are
- *                      computed on the second stream at the START of the call, beside the forward pass, from the list of requests the
- *                      previous call recorded; a call that asks for something else falls back to a launch in place and records
- *                      anew.  Same values; 25.6 -> 25.2 ms per step.  (Images live in a context-owned buffer, ~30 MB at cfg-5.)
- *   "train_y_bf16", "train_dqkv_bf16", "train_du_bf16", "train_dhid_bf16"   1 (default) / 0, each: with train_precision 16, a
- *                      tensor of the training step that is only ever a GEMM operand is stored as bf16 rows by its producer (launches of
- *                      >= 4096 rows: the trunk) -- the trunk's taped LayerNorm + modulate outputs; dq | dk | dv of the
- *                      sequence-resident attention backward; du = gate * dh; d pre = d hid * gelu'(pre).  The kernels that read them
- *                      round them to bf16 anyway: weight and activation gradients are bit-identical, the bias gradients of the
- *                      layers whose dY is stored rounded differ by ~1e-3 (column sums of the stored values).  25.2 -> 24.2 ms per step.
+ *                      With 16, attention axes of 129 .. 256 positions take the sequence-resident kernels (RoPE applied inside),
+ *                      the trunk's GEMM-only tensors are stored as bf16 rows, and with train_streams 2 the turned weights of the
+ *                      small dX products are computed ahead on the second stream (~30 MB context-owned buffer at cfg-5).
  *   "train_streams"    2 (default) / 1: mdgen_train_forward_backward launches the weight / bias gradients (nothing reads them
  *                      before the optimiser) on a second stream of the context, beside the backward pass's critical path on the
  *                      caller's stream; it joins the caller's stream before the call returns, and milestone events are recorded
@@ -364,7 +343,7 @@ int32_t mdgen_debug_train_dw(int32_t precision, const float* dy, int32_t ldy, co
  * Forward: out[ntok][384], lse[ntok][16].  Backward from dout[ntok][384]: dqkv[ntok][1152] = (d q, d k taken back through RoPE,
  * d q also through the q scale; d v), dbias[nseq][768] = per-sequence (d bias_k | d bias_v); stats[ntok][16][2] scratch.
  * precision 32: k32_attn* + k32_rope_bwd; 16: k16_attn* (bf16 operands on the MFMA, inverse RoPE in the store stage) as the training
- * step dispatches them; 160: the chunked k16 kernels for every length (the A/B of option "train_attn_form"); 161 (len 129 .. 256
+ * step dispatches them; 160: the chunked k16 kernels for every length (against the sequence-resident ones); 161 (len 129 .. 256
  * only): q, k of `qkv` are given UNROTATED (q scaled) and the sequence-resident kernels rotate them while they convert them,
  * as the training step runs them (it launches no RoPE pass for such an axis). */
 int32_t mdgen_debug_train_attention(int32_t precision, const float* qkv, int64_t ntok, int32_t nseq, int32_t len, int32_t inner,

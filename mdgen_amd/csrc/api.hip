@@ -161,22 +161,15 @@ struct mdgen_ctx {
                                 // k_proj<0> or a deferred projection), 1 (default) when the launch has >= 2 x CUs workgroups
                                 // of (sequence, 64 queries), 2 always
     int opt_train_precision = 32;   // operands of the training step's linear layers / weight gradients: 32 exact fp32, 16 bf16 MFMA
-    int opt_train_attn_form = 1;    // training step, bf16 operands: 1 = axes of 129 .. 256 positions take the sequence-resident attention kernels (k_attn16.hip)
-    int opt_train_defer_gate = 1;   // training step, trunk forward: 1 = a sub-layer's gated residual update is formed by the next sub-layer's LayerNorm launch
-    int opt_train_y_bf16 = 1;       // training step, bf16 operands: the trunk's taped LayerNorm outputs are stored as bf16 rows (GEMM operands only)
-    int opt_train_dqkv_bf16 = 1;    // training step, bf16 operands: the sequence-resident attention backward writes dq | dk | dv as bf16 rows
-    int opt_train_du_bf16 = 1;      // training step, bf16 operands: the gated gradient du = gate * dh of a trunk sub-layer is stored as bf16 rows
-    int opt_train_dhid_bf16 = 1;    // training step, bf16 operands: d pre = d hid * gelu'(pre) of a trunk MLP is stored as bf16 rows
     int opt_train_streams = 2;      // training step: 2 = weight / bias gradients of the linear layers on a second stream (train.inc)
     hipStream_t train_side = nullptr;   // that stream (created on first use, default priority)
     // Turned weights of the small launches' dX products (train.inc `turned`): the requests of one call in order, their images in
-    // tr_buf, computed on the second stream at the start of the next call with the same requests
+    // tr_buf, computed on the second stream at the start of the next call with the same requests (bf16 operands, train_streams 2)
     struct TurnReq { const float* w[3]; int nseg, rows, cols; size_t off; };
     std::vector<TurnReq> tr_plan;
     float* tr_buf = nullptr;
     size_t tr_buf_floats = 0;
     bool tr_plan_ok = false;
-    int opt_train_turn_ahead = 1;       // 1: those images are computed ahead on the second stream (needs train_streams 2)
     std::vector<hipEvent_t> train_ev;   // event pool of that fork / join traffic (created on first use, round-robin)
     size_t train_ev_next = 0;
     int opt_mlp_fold = 1;       // sampling (t shared by the batch): the MLP gate folded into per-(step, layer) fc2 streams, k_mlp_rows starts its
@@ -718,28 +711,6 @@ extern "C" int32_t mdgen_ctx_set_option(mdgen_ctx* c, const char* name, int32_t 
     } else if (n == "train_precision") {
         if (value != 16 && value != 32) return fail(-2, "train_precision must be 32 (fp32 operands, exact) or 16 (bf16 operands, fp32 accumulate)");
         c->opt_train_precision = value;
-    } else if (n == "train_attn_form") {
-        if (value != 0 && value != 1) return fail(-2, "train_attn_form must be 0 (chunked attention kernels) or 1 (sequence-resident for axes of 129 .. 256 positions)");
-        c->opt_train_attn_form = value;
-    } else if (n == "train_defer_gate") {
-        if (value != 0 && value != 1) return fail(-2, "train_defer_gate must be 0 or 1");
-        c->opt_train_defer_gate = value;
-    } else if (n == "train_turn_ahead") {
-        if (value != 0 && value != 1) return fail(-2, "train_turn_ahead must be 0 or 1");
-        c->opt_train_turn_ahead = value;
-        c->tr_plan_ok = false;
-    } else if (n == "train_y_bf16") {
-        if (value != 0 && value != 1) return fail(-2, "train_y_bf16 must be 0 or 1");
-        c->opt_train_y_bf16 = value;
-    } else if (n == "train_dqkv_bf16") {
-        if (value != 0 && value != 1) return fail(-2, "train_dqkv_bf16 must be 0 or 1");
-        c->opt_train_dqkv_bf16 = value;
-    } else if (n == "train_du_bf16") {
-        if (value != 0 && value != 1) return fail(-2, "train_du_bf16 must be 0 or 1");
-        c->opt_train_du_bf16 = value;
-    } else if (n == "train_dhid_bf16") {
-        if (value != 0 && value != 1) return fail(-2, "train_dhid_bf16 must be 0 or 1");
-        c->opt_train_dhid_bf16 = value;
     } else if (n == "train_streams") {
         if (value != 1 && value != 2) return fail(-2, "train_streams must be 1 (one stream) or 2 (weight gradients on a second stream)");
         c->opt_train_streams = value;

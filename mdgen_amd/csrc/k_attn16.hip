@@ -22,8 +22,10 @@
 //
 // Round 6: axes of 129 .. 256 positions (the ATLAS training shapes) take the SEQUENCE-RESIDENT forms further down --
 // k16_attn_seq / k16_attn_bwd_seq: eight waves own all rows of one (sequence, head), the other side is converted into LDS once,
-// scores in log2 units, per-row addends in the padding features of the operands, RoPE applied while converting (option
-// train_attn_form; launch16_attn / launch16_attn_bwd choose).  The kernels right below remain for every other length.
+// scores in log2 units, per-row addends in the padding features of the operands, RoPE applied while converting (the caller
+// chooses: launch16_attn / launch16_attn_bwd `seq_form`).  The kernels right below remain for every other length.  At the ATLAS
+// lengths the chunked backward re-staged the other side of every 128-row block through LDS and ran at 586 us per launch; the
+// sequence-resident pass takes ~380 us in the step, the forward ~100 instead of 134 with the rotation inside.
 #include "common.h"
 #include "kernels.h"
 
@@ -1115,19 +1117,15 @@ __global__ __launch_bounds__(512, 2) void k16_attn_seq(const float* __restrict__
     if (lse_out && hh == 0) lse_out[qtok * kH + g.hd] = mrun * 0.6931471805599453f + logf(den);
 }
 
-// 1 (default): axes of 129 .. 256 positions take the sequence-resident backward kernel; 0: the chunked pair for every length
-// (context option "train_attn_form"; mdgen_debug_train_attention: precision 160)
-thread_local int g_k16_attn_form = 1;
-
 static unsigned wg_grid(int nseq, int nblk) { return (unsigned)((long)((nseq + 7) / 8) * 8 * kH * nblk); }   // see wg_of
 
 // Forward: 256 queries per workgroup (eight waves) once an axis is longer than 128 -- K / V are then staged once per
 // (sequence, head) at the ATLAS lengths instead of once per 128-query block (124 -> 104 us); four waves below that.
-bool attn16_seq_form(const AxisMap& ax) { return g_k16_attn_form && ax.len > 128 && ax.len <= kSeqQ; }
+bool attn16_seq_form(const AxisMap& ax) { return ax.len > 128 && ax.len <= kSeqQ; }
 
 void launch16_attn(const float* qkv, int ld, const AxisMap& ax, const MaskMap& mk, const float* bias_k, const float* bias_v,
-                   const float* inv_freq, float* out, hipStream_t s, float* lse_out, bool rope_inside) {
-    if (attn16_seq_form(ax)) {
+                   const float* inv_freq, float* out, hipStream_t s, float* lse_out, bool seq_form, bool rope_inside) {
+    if (seq_form && attn16_seq_form(ax)) {
         hipLaunchKernelGGL(k16_attn_seq, dim3(wg_grid(ax.nseq, 1)), dim3(512), 0, s, qkv, ld, ax, mk, bias_k, bias_v, inv_freq, out, lse_out,
                            rope_inside);
     } else if (ax.len > 128) {
@@ -1143,8 +1141,9 @@ void launch16_attn(const float* qkv, int ld, const AxisMap& ax, const MaskMap& m
 // threads -- the query pass went 168 -> 186 us and the key pass 172 -> 221 us at the ATLAS lengths)
 void launch16_attn_bwd(const float* qkv, int ld, const AxisMap& ax, const MaskMap& mk, const float* bias_k,
                        const float* bias_v, const float* inv_freq, const float* o, const float* dout, float* dqkv,
-                       float* stats, float* dbias, hipStream_t s, const float* lse_in, bool rope_inside, bool out_bf16) {
-    if (attn16_seq_form(ax)) {   // one workgroup per (sequence, head) and pass, the other side resident in LDS
+                       float* stats, float* dbias, hipStream_t s, const float* lse_in, bool seq_form, bool rope_inside,
+                       bool out_bf16) {
+    if (seq_form && attn16_seq_form(ax)) {   // one workgroup per (sequence, head) and pass, the other side resident in LDS
         hipLaunchKernelGGL(k16_attn_bwd_seq, dim3(2 * wg_grid(ax.nseq, 1)), dim3(512), 0, s, qkv, ld, ax, mk, bias_k, bias_v, inv_freq, o, dout,
                            dqkv, dbias, lse_in, rope_inside, out_bf16);
         return;

@@ -104,15 +104,6 @@ __global__ __launch_bounds__(256) void k32_gate_ln_mod(const float* __restrict__
     }
 }
 
-// Operand precision of the training step's linear layers / weight gradients: 0 = fp32 products (k32_linear / k32_dw on
-// v_mfma_f32_32x32x2_f32, the exact mode), 1 = k16_linear / k16_dw: operands rounded
-// to bf16 on their way into LDS and multiplied on v_mfma_f32_32x32x16_bf16 with fp32 accumulation -- what the reference
-// trains with (train.py:13 `torch.set_float32_matmul_precision('medium')` = bf16-class products, fp32 accumulate, fp32
-// master weights).  Set by mdgen_train_forward_backward from the context option "train_precision" for the duration of the
-// call; the sampler's fp32 tolerance mode always runs with 0.  Per THREAD: two contexts training on two host threads do not
-// see each other's mode.
-thread_local int g_k32_bf16_operands = 0;
-
 // A launcher that is handed a shape its caller should have ruled out (bf16-stored operands outside the streamed kernels)
 // launches nothing and leaves a message here; the C-ABI entry points turn it into an error return (api.hip LAUNCHCHK).
 thread_local const char* g_k32_launch_error = nullptr;
@@ -653,28 +644,34 @@ void launch32_gate_ln_mod(const float* xp, const float* up, long nrows, const Mo
     hipLaunchKernelGGL(k32_gate_ln_mod, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, s, xp, up, nrows, gm, gate_chunk, mm, shift_chunk,
                        scale_chunk, eps, y, keep, y_bf16 ? reinterpret_cast<unsigned short*>(y) : nullptr);
 }
+// Exact fp32 products (k32_linear on v_mfma_f32_32x32x2_f32): the sampler's fp32 tolerance mode and the training step's exact mode.
 void launch32_linear(const float* a, int lda, const float* w, int ldw, const float* bias, long n, int m, int k, int mode,
+                     float* c, int ldc, int col0, const ModMap& mm, int gate_chunk, int gated, float scalar, hipStream_t s,
+                     int wtrans, float* c2) {
+    LinearParams p{a, lda, w, ldw, bias, n, m, k, mode, wtrans, c, ldc, col0, mm, gate_chunk, gated, scalar, c2, 0, {}, {}, {},
+                   nullptr, 0, 0, 0, 0};
+    hipLaunchKernelGGL(k32_linear, dim3((unsigned)((m + 127) / 128), (unsigned)((n + 127) / 128)), dim3(256), 0, s, p);
+}
+// bf16 operands (the training step's option train_precision = 16): k16_linear* round the operands to bf16 on their way into LDS
+// and multiply on v_mfma_f32_32x32x16_bf16 with fp32 accumulation -- what the reference trains with (train.py:13
+// `torch.set_float32_matmul_precision('medium')` = bf16-class products, fp32 accumulate, fp32 master weights).
+void launch16_linear(const float* a, int lda, const float* w, int ldw, const float* bias, long n, int m, int k, int mode,
                      float* c, int ldc, int col0, const ModMap& mm, int gate_chunk, int gated, float scalar, hipStream_t s,
                      int wtrans, float* c2, const void* wpack, int flags) {
     LinearParams p{a, lda, w, ldw, bias, n, m, k, mode, wtrans, c, ldc, col0, mm, gate_chunk, gated, scalar, c2, 0, {}, {}, {},
-                   static_cast<const unsigned char*>(wpack), g_k32_bf16_operands, flags & 1, (flags >> 1) & 1, (flags >> 2) & 1};
-    if ((flags & 4) && !(g_k32_bf16_operands && mode == 7)) {   // (fast_gelu turns mode 7 into 17, the only one that stores bf16)
-        g_k32_launch_error = "launch32_linear: a bf16 result is the GELU-derivative epilogue's in the bf16-operand mode only";
+                   static_cast<const unsigned char*>(wpack), 1, flags & 1, (flags >> 1) & 1, (flags >> 2) & 1};
+    if ((flags & 4) && mode != 7) {   // (fast_gelu turns mode 7 into 17, the only one that stores bf16)
+        g_k32_launch_error = "launch16_linear: a bf16 result is the GELU-derivative epilogue's only";
         return;
     }
-    if ((flags & 3) && !(g_k32_bf16_operands && (!(flags & 1) || wpack))) {
-        g_k32_launch_error = "launch32_linear: bf16 operand storage outside the streamed bf16-operand kernel";
-        return;
-    }
-    const dim3 grid((unsigned)((m + 127) / 128), (unsigned)((n + 127) / 128));
-    if (!g_k32_bf16_operands) {
-        hipLaunchKernelGGL(k32_linear, grid, dim3(256), 0, s, p);
+    if ((flags & 1) && !wpack) {
+        g_k32_launch_error = "launch16_linear: bf16 operand storage outside the streamed kernel";
         return;
     }
     const auto al = [](const void* q) { return ((unsigned long long)q & 15) == 0; };
     if (launch16_linear_wide(p, s)) return;    // 128 x 384 tiles: every trunk-sized layer (k_wide16.hip)
     if (flags & 1) {
-        g_k32_launch_error = "launch32_linear: bf16 token rows need the streamed kernel (n >= 1024, m % 384 == 0)";
+        g_k32_launch_error = "launch16_linear: bf16 token rows need the streamed kernel (n >= 1024, m % 384 == 0)";
         return;
     }
     if (n <= 2048 && !wtrans && k % 64 == 0 && (lda & 3) == 0 && (ldw & 3) == 0 && ((unsigned long long)a & 15) == 0 &&
@@ -684,18 +681,18 @@ void launch32_linear(const float* a, int lda, const float* w, int ldw, const flo
     }
     const bool fast = !wtrans && k % 64 == 0 && (lda & 3) == 0 && (ldw & 3) == 0 && al(a) && al(w);
     if (!fast) {
-        hipLaunchKernelGGL(k16_linear, grid, dim3(256), 0, s, p);
+        hipLaunchKernelGGL(k16_linear, dim3((unsigned)((m + 127) / 128), (unsigned)((n + 127) / 128)), dim3(256), 0, s, p);
         return;
     }
     const int nrt = (int)((n + 127) / 128), nct = (m + 127) / 128;
     hipLaunchKernelGGL(k16_linear_fast, dim3((unsigned)(8 * ((nrt + 7) / 8) * nct)), dim3(256), 0, s, p, nrt, nct);
 }
 // q | k | v (three [mseg][k] layers of the same input) in one pass of k16_linear_fast: c[n][col0 + j mseg + i] =
-// (a . w[j][i] + bias[j][i]) * scale[j].  false: shape not eligible (or exact-fp32 mode), nothing launched.
+// (a . w[j][i] + bias[j][i]) * scale[j], bf16 operands.  false: shape not eligible, nothing launched.
 bool launch16_linear_seg3(const float* a, int lda, const float* const* w, int ldw, const float* const* bias, const float* scale,
                           long n, int mseg, int k, float* c, int ldc, int col0, hipStream_t s, const void* wpack, bool a_bf16) {
     const auto al = [](const void* q) { return ((unsigned long long)q & 15) == 0; };
-    if (!g_k32_bf16_operands || mseg % 128 || k % 64 || (lda & 3) || (ldw & 3) || !al(a) || !al(w[0]) || !al(w[1]) || !al(w[2]))
+    if (mseg % 128 || k % 64 || (lda & 3) || (ldw & 3) || !al(a) || !al(w[0]) || !al(w[1]) || !al(w[2]))
         return false;
     LinearParams p{a, lda, w[0], ldw, nullptr, n, 3 * mseg, k, 0, 0, c, ldc, col0, ModMap{nullptr, 1, 1, 0, 0}, 0, 0, 0.f, nullptr,
                    mseg, {w[0], w[1], w[2]}, {bias[0], bias[1], bias[2]}, {scale[0], scale[1], scale[2]},

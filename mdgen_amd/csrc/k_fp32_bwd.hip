@@ -885,11 +885,32 @@ __global__ void k32_sum_frames(const float* __restrict__ a, int B, int T, int L,
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------
+// Slices of the k32_dw / k16_dw grid over n: enough to fill the chip ONCE with 128 x 128 tiles at two workgroups per CU (a
+// 384 x 384 weight is only 9 of them); more slices only add partial-sum traffic (113 slices of a 384 x 384 weight: 66 MB
+// written and read back)
+static int dw_nsplit(long n, int m, int k, size_t part_floats) {
+    const int tiles = ((m + 127) / 128) * ((k + 127) / 128);
+    int nsplit = (int)((n + 511) / 512);
+    const int want = (512 + tiles - 1) / tiles;
+    if (nsplit > want) nsplit = want;
+    if (nsplit > 128) nsplit = 128;
+    if (nsplit < 1) nsplit = 1;
+    while (nsplit > 1 && (size_t)nsplit * m * (k + 1) > part_floats) --nsplit;
+    return nsplit;
+}
+// exact fp32 products (k32_dw)
+void launch32_dw(const float* dy, int ldy, const float* x, int ldx, long n, int m, int k, float* dw, float* part,
+                 size_t part_floats, hipStream_t s) {
+    const int nsplit = dw_nsplit(n, m, k, part_floats);
+    hipLaunchKernelGGL(k32_dw, dim3((m + 127) / 128, (k + 127) / 128, nsplit), dim3(256), 0, s, dy, ldy, x, ldx, n, m, k, part);
+    const long count = (long)m * k;
+    hipLaunchKernelGGL(k32_reduce_add, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, part, nsplit, count, count, dw);
+}
 // dW of nseg layers that share the input x and whose dY sit side by side (dy[n][j mseg + i]): one pass over x and dY,
 // m = nseg * mseg.  dw[j] / db[j] may be null.  Returns true if the bias gradients were computed by the same pass.
 int launch16_dw_wide(const float* dy, int ldy, const float* x, int ldx, long n, int m, int k, float* part, size_t part_floats,
                      bool want_db, float** bpart_out, hipStream_t s, bool x_bf16, bool dy_bf16);   // k_wide16.hip
-bool launch32_dw_seg(const float* dy, int ldy, const float* x, int ldx, long n, int mseg, int nseg, int k, float* const* dw,
+bool launch16_dw_seg(const float* dy, int ldy, const float* x, int ldx, long n, int mseg, int nseg, int k, float* const* dw,
                      float* const* db, float* part, size_t part_floats, hipStream_t s, bool x_bf16, bool dy_bf16) {
     const int m = mseg * nseg;
     bool want_db = false;
@@ -905,7 +926,7 @@ bool launch32_dw_seg(const float* dy, int ldy, const float* x, int ldx, long n, 
                                    (long)m, (long)mseg, db[j]);
         }
     };
-    if (g_k32_bf16_operands) {   // 128 x 384 tiles (k_wide16.hip): each dY tile read once
+    {   // 128 x 384 tiles (k_wide16.hip): each dY tile read once
         float* bpart = nullptr;
         if (const int ns = launch16_dw_wide(dy, ldy, x, ldx, n, m, k, part, part_floats, want_db, &bpart, s, x_bf16, dy_bf16)) {
             reduce(ns, bpart);
@@ -913,31 +934,22 @@ bool launch32_dw_seg(const float* dy, int ldy, const float* x, int ldx, long n, 
         }
     }
     if (x_bf16 || dy_bf16) {
-        g_k32_launch_error = "launch32_dw: bf16 X / dY rows need the wide kernel (bf16-operand mode, n >= 4096)";
+        g_k32_launch_error = "launch16_dw: bf16 X / dY rows need the wide kernel (n >= 4096)";
         return false;
     }
-    // enough slices to fill the chip ONCE with 128 x 128 tiles at two workgroups per CU (a 384 x 384 weight is only 9 of
-    // them); more slices only add partial-sum traffic (113 slices of a 384 x 384 weight: 66 MB written and read back)
-    const int tiles = ((m + 127) / 128) * ((k + 127) / 128);
-    int nsplit = (int)((n + 511) / 512);
-    const int want = (512 + tiles - 1) / tiles;
-    if (nsplit > want) nsplit = want;
-    if (nsplit > 128) nsplit = 128;
-    if (nsplit < 1) nsplit = 1;
-    while (nsplit > 1 && (size_t)nsplit * m * (k + 1) > part_floats) --nsplit;
+    const int nsplit = dw_nsplit(n, m, k, part_floats);
     const dim3 grid((m + 127) / 128, (k + 127) / 128, nsplit);
     const bool fast = ((ldy | m | ldx | k) & 7) == 0 && (((unsigned long long)dy | (unsigned long long)x) & 15) == 0;
-    // bf16-operand fast path: the bias gradient (column sums of dY) rides along, partials behind the dW partials
-    float* bpart = (g_k32_bf16_operands && fast && want_db && (size_t)nsplit * m * (k + 1) <= part_floats) ? part + (size_t)nsplit * m * k : nullptr;
-    if (g_k32_bf16_operands && fast) hipLaunchKernelGGL(k16_dw<true>, grid, dim3(256), 0, s, dy, ldy, x, ldx, n, m, k, part, bpart);
-    else if (g_k32_bf16_operands) hipLaunchKernelGGL(k16_dw<false>, grid, dim3(256), 0, s, dy, ldy, x, ldx, n, m, k, part, bpart);
-    else hipLaunchKernelGGL(k32_dw, grid, dim3(256), 0, s, dy, ldy, x, ldx, n, m, k, part);
+    // fast path: the bias gradient (column sums of dY) rides along, partials behind the dW partials
+    float* bpart = (fast && want_db && (size_t)nsplit * m * (k + 1) <= part_floats) ? part + (size_t)nsplit * m * k : nullptr;
+    if (fast) hipLaunchKernelGGL(k16_dw<true>, grid, dim3(256), 0, s, dy, ldy, x, ldx, n, m, k, part, bpart);
+    else hipLaunchKernelGGL(k16_dw<false>, grid, dim3(256), 0, s, dy, ldy, x, ldx, n, m, k, part, bpart);
     reduce(nsplit, bpart);
     return bpart != nullptr;
 }
-bool launch32_dw(const float* dy, int ldy, const float* x, int ldx, long n, int m, int k, float* dw, float* part,
+bool launch16_dw(const float* dy, int ldy, const float* x, int ldx, long n, int m, int k, float* dw, float* part,
                  size_t part_floats, hipStream_t s, float* db, bool x_bf16, bool dy_bf16) {
-    return launch32_dw_seg(dy, ldy, x, ldx, n, m, 1, k, &dw, &db, part, part_floats, s, x_bf16, dy_bf16);
+    return launch16_dw_seg(dy, ldy, x, ldx, n, m, 1, k, &dw, &db, part, part_floats, s, x_bf16, dy_bf16);
 }
 // out[g][c] (ldo) += sum_{t in group g} a[t][c] * B(t, c); groups of tokens_per_group rows
 void launch32_colsum(const float* a, int lda, const float* b, int ldb, const float* roww, int mode, long nrows, int ncols,

@@ -232,24 +232,31 @@ void launch_masked_mse(const float* pred, const float* target, const float* mask
 void launch_ipa_attn(const IpaAttnParams& p, hipStream_t s);
 
 // fp32-operand path (k_fp32.hip)
-extern thread_local int g_k16_attn_form;       // k_attn16.hip: 1 = sequence-resident attention backward for axes of 129 .. 256 positions
-extern thread_local int g_k32_bf16_operands;   // 1: k32_linear / k32_dw multiply bf16-rounded operands (training option train_precision = 16)
 extern thread_local const char* g_k32_launch_error;   // set by a launcher that refused a shape (nothing launched)
 const char* k32_take_launch_error();                  // ... and cleared by the entry point that reports it
 void launch32_ln_mod(const float* x, long nrows, const ModMap& mm, int shift_chunk, int scale_chunk, int affine, float eps,
                      float* y, hipStream_t s, float* keep = nullptr, bool y_bf16 = false);   // keep: copy of x (training tape); y_bf16: y holds bf16 rows
+// exact fp32 products (k32_linear)
 void launch32_linear(const float* a, int lda, const float* w, int ldw, const float* bias, long n, int m, int k, int mode,
+                     float* c, int ldc, int col0, const ModMap& mm, int gate_chunk, int gated, float scalar, hipStream_t s,
+                     int wtrans = 0, float* c2 = nullptr);
+// the same layer with bf16-rounded operands on the bf16 MFMA, fp32 accumulation (the training step's train_precision = 16)
+void launch16_linear(const float* a, int lda, const float* w, int ldw, const float* bias, long n, int m, int k, int mode,
                      float* c, int ldc, int col0, const ModMap& mm, int gate_chunk, int gated, float scalar, hipStream_t s,
                      int wtrans = 0, float* c2 = nullptr,
                      const void* wpack = nullptr,    // launch16_pack_wstream's bf16 fragment stream of w (k_wide16.hip)
-                     int flags = 0);                 // 1: a is bf16 rows (needs wpack), 2: c2 (mode 6) is written as bf16
+                     int flags = 0);                 // 1: a is bf16 rows (needs wpack), 2: c2 (mode 6) is written as bf16,
+                                                     // 4: the result of mode 7 is written as bf16
 // backward kernels of the training step (k_fp32_bwd.hip)
-// db != nullptr: the bias gradient db[m] += column sums of dY may be computed by the same pass (returns true if it was;
-// otherwise the caller runs launch32_colsum)
-bool launch32_dw_seg(const float* dy, int ldy, const float* x, int ldx, long n, int mseg, int nseg, int k, float* const* dw,
+// dW += dY^T X, exact fp32 products (k32_dw)
+void launch32_dw(const float* dy, int ldy, const float* x, int ldx, long n, int m, int k, float* dw, float* part,
+                 size_t part_floats, hipStream_t s);
+// ... with bf16-rounded operands.  db != nullptr: the bias gradient db[m] += column sums of dY may be computed by the same pass
+// (returns true if it was; otherwise the caller runs launch32_colsum)
+bool launch16_dw_seg(const float* dy, int ldy, const float* x, int ldx, long n, int mseg, int nseg, int k, float* const* dw,
                      float* const* db, float* part, size_t part_floats, hipStream_t s,
                      bool x_bf16 = false, bool dy_bf16 = false);   // nseg layers sharing x, dY side by side; *_bf16: stored as bf16 rows (wide kernel only)
-bool launch32_dw(const float* dy, int ldy, const float* x, int ldx, long n, int m, int k, float* dw, float* part,
+bool launch16_dw(const float* dy, int ldy, const float* x, int ldx, long n, int m, int k, float* dw, float* part,
                  size_t part_floats, hipStream_t s, float* db = nullptr, bool x_bf16 = false,
                  bool dy_bf16 = false);   // x_bf16 / dy_bf16: x / dy are bf16 rows (wide kernel only)
 void launch32_colsum(const float* a, int lda, const float* b, int ldb, const float* roww, int mode, long nrows, int ncols,
@@ -296,14 +303,15 @@ bool launch16_linear_seg3(const float* a, int lda, const float* const* w, int ld
 bool launch16_pack_wstream(const float* const* src, int nsrc, int seg, int ld, long n, int m, int k, int turned, void* out, hipStream_t s);
 // bf16-operand (MFMA) attention of the training step, k_attn16.hip: same arguments as launch32_attn / launch32_attn_bwd; the
 // backward needs the forward's log-sum-exp tape (lse_in != nullptr).
-// rope_inside (only where attn16_seq_form(ax): the sequence-resident kernels): q, k of `qkv` are NOT rotated yet -- the kernels
-// rotate them while they convert them (no k32_rope pass); forward and backward of a sub-layer must agree on it
+// seq_form: the sequence-resident kernels, on axes where attn16_seq_form(ax) (129 .. 256 positions); else the chunked ones.
+// rope_inside (sequence-resident kernels only): q, k of `qkv` are NOT rotated yet -- the kernels rotate them while they convert
+// them (no k32_rope pass); forward and backward of a sub-layer must agree on it
 bool attn16_seq_form(const AxisMap& ax);
 void launch16_attn(const float* qkv, int ld, const AxisMap& ax, const MaskMap& mk, const float* bias_k, const float* bias_v,
-                   const float* inv_freq, float* out, hipStream_t s, float* lse_out = nullptr, bool rope_inside = false);
+                   const float* inv_freq, float* out, hipStream_t s, float* lse_out, bool seq_form, bool rope_inside);
 void launch16_attn_bwd(const float* qkv, int ld, const AxisMap& ax, const MaskMap& mk, const float* bias_k,
                        const float* bias_v, const float* inv_freq, const float* o, const float* dout, float* dqkv,
-                       float* stats, float* dbias, hipStream_t s, const float* lse_in, bool rope_inside = false,
+                       float* stats, float* dbias, hipStream_t s, const float* lse_in, bool seq_form, bool rope_inside,
                        bool out_bf16 = false);   // out_bf16 (sequence-resident form only): dqkv is written as bf16 rows (ld in elements)
 void launch32_attn(const float* qkv, int ld, const AxisMap& ax, const MaskMap& mk, const float* bias_k, const float* bias_v,
                    const float* inv_freq, float* out, hipStream_t s, float* lse_out = nullptr);

@@ -22,6 +22,9 @@ struct Train {
     float* grads;
     const int64_t* goff;     // per ctx weight index
     std::map<std::string, int> idx;
+    // Operand mode of the call's linear layers / weight gradients (option train_precision): false = exact fp32 products
+    // (k32_linear / k32_dw), true = bf16-rounded operands on the bf16 MFMA with fp32 accumulation (launch16_linear / launch16_dw).
+    bool bf16 = false;
     // scratch (backward)
     float *dh, *dy, *ytmp, *act, *stats, *part, *cpart, *dmod, *dhi, *dsilu, *wt;
     size_t part_floats, cpart_floats;
@@ -32,14 +35,19 @@ struct Train {
     // a sub-layer starts once the second stream has finished the sub-layer before the previous one (begin_sub / end_sub).
     // Forward pass of the trunk (defer_gate): a sub-layer does not apply its gated residual update; it leaves it PENDING (the stream
     // is x + gate * u with x = the sub-layer's taped input), and the next sub-layer's LayerNorm launch forms it in registers, tapes it
-    // and normalises it (k32_gate_ln_mod).  flush_pending() materialises the stream into h (after the last layer).
+    // and normalises it (k32_gate_ln_mod).  flush_pending() materialises the stream into h (after the last layer).  14 launches and
+    // 28 passes over the 98 MB stream less per ATLAS step (26.9 -> 25.9 ms).  The IPA stack applies its updates at once.
     struct Pending { const float* x = nullptr; const float* u = nullptr; ModMap mm{}; int gate = 0; long nrows = 0; };
     mutable Pending pend;
     mutable bool defer_gate = false;
     // Turned weights (dX = dY W of the launches too small for the streamed kernel runs through the forward kernel on W^T): with a
-    // second stream the images of ALL such products of the call are computed there at the start of the call, while the main stream
-    // runs the forward pass, from the list of requests the previous call recorded (mdgen_ctx::tr_plan); a request that does not
-    // match the list falls back to a k32_transpose launch in place and the list is recorded anew.
+    // second stream and bf16 operands the images of ALL such products of the call are computed there at the start of the call, while
+    // the main stream runs the forward pass, from the list of requests the previous call recorded (mdgen_ctx::tr_plan); a request that
+    // does not match the list falls back to a k32_transpose launch in place, and a call that deviates from the list or leaves part of
+    // it unused has the next call record it anew.  (The second stream is otherwise idle during the forward pass, and the IPA stack's
+    // backward, ~330 launches of 5-12 us on 256 rows, leaves the chip half idle: its 50 transposes moved off the critical path took
+    // the ATLAS step 25.6 -> 25.2 ms.  Packing the streamed kernel's bf16 fragment streams ahead the same way is slower: a stream
+    // packed right in front of its consumer is read out of the L2 it was just written to.)
     mutable size_t tr_cursor = 0;
     mutable bool tr_use = false, tr_waited = false, tr_record = false;
     mutable hipEvent_t tr_done = nullptr;
@@ -198,34 +206,52 @@ static bool sub_wide(std::initializer_list<const float*> w) {
         if ((uintptr_t)p & 15) return false;
     return true;
 }
-// whether SubTapeMlp::hid of a sub-layer with `nrows` rows holds bf16 (both of its readers are then the wide kernels)
-static bool hid_is_bf16(long nrows, bool wide) { return g_k32_bf16_operands && nrows >= 4096 && wide; }
-// the taped LayerNorm + modulate output of a trunk sub-layer likewise (token rows of the q | k | v / fc1 products, X of their weight
-// gradients: all of them the streamed / wide kernels at these sizes); option train_y_bf16
-static bool y_is_bf16(const Train& t, long nrows, bool wide);
+// Whether a sub-layer with `nrows` rows stores its GEMM-only tensors as bf16 rows: the GELU output SubTapeMlp::hid, the taped
+// LayerNorm + modulate output y (token rows of the q | k | v / fc1 products, X of their weight gradients), du = gate * dh, d pre =
+// d hid * gelu'(pre) and, on axes of the sequence-resident attention, dq | dk | dv.  Each is only ever the token operand of a dX
+// product and dY / X of a weight gradient, whose kernels round it to bf16 on its way into LDS anyway (k16_linear_wdma<true>,
+// k16_dw_wide<XBF, DYBF>): written rounded by its producer, the same values enter the MFMAs and half the bytes cross HBM two or
+// three times (ATLAS step: y 25.2 -> 24.6, dq | dk | dv -> 24.2, du -0.3, d pre -0.2 ms).  Weight and activation gradients are
+// unchanged; the bias gradients of the layers whose dY is stored rounded are column sums of the stored values.
+static bool rows_bf16(const Train& t, long nrows, bool wide) { return t.bf16 && nrows >= 4096 && wide; }
+
+// the call's linear layer (kernels.h launch32_linear / launch16_linear); wpack / flags: bf16 operands only
+static void step_linear(const Train& t, const float* a, int lda, const float* w, int ldw, const float* bias, long n, int m, int k,
+                        int mode, float* c, int ldc, int col0, float scalar, hipStream_t s, int wtrans = 0, float* c2 = nullptr,
+                        const void* wpack = nullptr, int flags = 0) {
+    if (t.bf16) launch16_linear(a, lda, w, ldw, bias, n, m, k, mode, c, ldc, col0, kNoMod, 0, 0, scalar, s, wtrans, c2, wpack, flags);
+    else launch32_linear(a, lda, w, ldw, bias, n, m, k, mode, c, ldc, col0, kNoMod, 0, 0, scalar, s, wtrans, c2);
+}
+// the call's weight gradient (launch32_dw / launch16_dw); true: db was computed by the same pass
+static bool step_dw(const Train& t, const float* dy, int ldy, const float* x, int ldx, long n, int m, int k, float* dw, float* part,
+                    hipStream_t s, float* db = nullptr, bool x_bf16 = false, bool dy_bf16 = false) {
+    if (t.bf16) return launch16_dw(dy, ldy, x, ldx, n, m, k, dw, part, t.part_floats, s, db, x_bf16, dy_bf16);
+    launch32_dw(dy, ldy, x, ldx, n, m, k, dw, part, t.part_floats, s);
+    return false;
+}
 
 // bf16-operand mode, launches big enough for the streamed 128 x 384 kernel: the weight W(col < m, kk < k) of ONE layer as a
 // bf16 fragment stream in the scratch t.wt (turned: the fp32 matrix is [k][m], dX = dY W).  nullptr: not eligible -- the
 // caller's launch then reads the fp32 weight.  The scratch is reused by the next call on the stream.
 static const void* wpack1(const Train& t, const float* w, int ld, long n, int m, int k, int turned) {
-    if (!g_k32_bf16_operands) return nullptr;
+    if (!t.bf16) return nullptr;
     return launch16_pack_wstream(&w, 1, turned ? k : m, ld, n, m, k, turned, t.wt, t.r.s) ? t.wt : nullptr;
 }
-
-static bool y_is_bf16(const Train& t, long nrows, bool wide) { return t.c->opt_train_y_bf16 && hid_is_bf16(nrows, wide); }
 
 // ---- forward sub-layers with tape ---------------------------------------------------------------------------------
 // LayerNorm + modulate of the residual stream into y, the stream's rows copied to the tape (h_in) -- with the previous sub-layer's
 // pending gated update formed on the way when there is one (Train::Pending)
-// y_bf16: y is stored as bf16 rows (y_is_bf16: it is only ever a GEMM operand)
-static void ln_mod_tape(const Train& t, const float* h, long nrows, const ModMap& mm, int shift, int scale, float* y, float* h_in,
-                        bool y_bf16) {
-    if (t.pend.x && t.pend.nrows == nrows) {
-        launch32_gate_ln_mod(t.pend.x, t.pend.u, nrows, t.pend.mm, t.pend.gate, mm, shift, scale, 1e-6f, y, h_in, t.r.s, y_bf16);
-        t.pend = Train::Pending{};
-    } else {
+// y_bf16: y is stored as bf16 rows (rows_bf16: it is only ever a GEMM operand)
+static int ln_mod_tape(const Train& t, const float* h, long nrows, const ModMap& mm, int shift, int scale, float* y, float* h_in,
+                       bool y_bf16) {
+    if (!t.pend.x) {
         launch32_ln_mod(h, nrows, mm, shift, scale, 0, 1e-6f, y, t.r.s, h_in, y_bf16);
+        return 0;
     }
+    if (t.pend.nrows != nrows) return fail(-7, "internal: pending gated update of %ld rows before a LayerNorm of %ld", t.pend.nrows, nrows);
+    launch32_gate_ln_mod(t.pend.x, t.pend.u, nrows, t.pend.mm, t.pend.gate, mm, shift, scale, 1e-6f, y, h_in, t.r.s, y_bf16);
+    t.pend = Train::Pending{};
+    return 0;
 }
 // the sub-layer's residual update h += gate * u, or its deferral (x = the sub-layer's taped input rows = the stream before it)
 static void gated_update(const Train& t, float* h, const float* x, const float* u, long nrows, const ModMap& mm, int gate) {
@@ -241,36 +267,34 @@ static void flush_pending(const Train& t, float* h) {
 static int attn_fwd_tape(const Train& t, const std::string& pre, float* h, long nrows, const AxisMap& ax, const ModMap& mm,
                          int shift, int scale, int gate, const MaskMap& mk, long pos_div, int pos_mod, const SubTapeAttn& tp) {
     const Run& r = t.r;
-    const F32Bufs b = f32_bufs(r);
     TW32(wq, pre + "q_proj.weight"); TW32(bq, pre + "q_proj.bias");
     TW32(wk, pre + "k_proj.weight"); TW32(bk, pre + "k_proj.bias");
     TW32(wv, pre + "v_proj.weight"); TW32(bv, pre + "v_proj.bias");
     TW32(wo, pre + "out_proj.weight"); TW32(bo, pre + "out_proj.bias");
     TW32(biask, pre + "bias_k"); TW32(biasv, pre + "bias_v");
-    const bool y16 = y_is_bf16(t, nrows, sub_wide({wq, wk, wv, wo}));
-    ln_mod_tape(t, h, nrows, mm, shift, scale, tp.y, tp.h_in, y16);     // y (taped), and the tape's copy of h
+    const bool y16 = rows_bf16(t, nrows, sub_wide({wq, wk, wv, wo}));
+    if (int e = ln_mod_tape(t, h, nrows, mm, shift, scale, tp.y, tp.h_in, y16)) return e;     // y (taped), and the tape's copy of h
     const float qscale = 1.0f / std::sqrt((float)kDH);
     const float* w3[3] = {wq, wk, wv};
     const float* b3[3] = {bq, bk, bv};
     const float s3[3] = {qscale, 1.0f, 1.0f};
     // bf16 operands: one pass over y, the three weights as one fragment stream (k_wide16.hip) when the launch is big enough
-    const void* pk = g_k32_bf16_operands && launch16_pack_wstream(w3, 3, kC, kC, nrows, 3 * kC, kC, 0, t.wt, r.s) ? t.wt : nullptr;
+    const void* pk = t.bf16 && launch16_pack_wstream(w3, 3, kC, kC, nrows, 3 * kC, kC, 0, t.wt, r.s) ? t.wt : nullptr;
     if (y16 && !pk) return fail(-7, "internal: bf16 LayerNorm output without the streamed q | k | v kernel (rows %ld)", nrows);
-    if (!launch16_linear_seg3(tp.y, kC, w3, kC, b3, s3, nrows, kC, kC, tp.qkv, 3 * kC, 0, r.s, pk, y16)) {
+    if (!t.bf16 || !launch16_linear_seg3(tp.y, kC, w3, kC, b3, s3, nrows, kC, kC, tp.qkv, 3 * kC, 0, r.s, pk, y16)) {
         if (y16) return fail(-7, "internal: bf16 LayerNorm output without the one-pass q | k | v kernel (rows %ld)", nrows);
-        launch32_linear(tp.y, kC, wq, kC, bq, nrows, kC, kC, 4, tp.qkv, 3 * kC, 0, kNoMod, 0, 0, qscale, r.s);
-        launch32_linear(tp.y, kC, wk, kC, bk, nrows, kC, kC, 0, tp.qkv, 3 * kC, kC, kNoMod, 0, 0, 0.f, r.s);
-        launch32_linear(tp.y, kC, wv, kC, bv, nrows, kC, kC, 0, tp.qkv, 3 * kC, 2 * kC, kNoMod, 0, 0, 0.f, r.s);
+        step_linear(t, tp.y, kC, wq, kC, bq, nrows, kC, kC, 4, tp.qkv, 3 * kC, 0, qscale, r.s);
+        step_linear(t, tp.y, kC, wk, kC, bk, nrows, kC, kC, 0, tp.qkv, 3 * kC, kC, 0.f, r.s);
+        step_linear(t, tp.y, kC, wv, kC, bv, nrows, kC, kC, 0, tp.qkv, 3 * kC, 2 * kC, 0.f, r.s);
     }
     // (the sequence-resident bf16-operand kernels rotate q, k while they convert them: no RoPE pass, the tape keeps them unrotated)
-    const bool rope_inside = g_k32_bf16_operands && attn16_seq_form(ax);
+    const bool rope_inside = t.bf16 && attn16_seq_form(ax);
     if (!rope_inside) launch32_rope(tp.qkv, nrows, 3 * kC, pos_div, pos_mod, t.c->inv_freq, r.s);
-    if (g_k32_bf16_operands) launch16_attn(tp.qkv, 3 * kC, ax, mk, biask, biasv, t.c->inv_freq, tp.att, r.s, tp.lse, rope_inside);
+    if (t.bf16) launch16_attn(tp.qkv, 3 * kC, ax, mk, biask, biasv, t.c->inv_freq, tp.att, r.s, tp.lse, attn16_seq_form(ax), rope_inside);
     else launch32_attn(tp.qkv, 3 * kC, ax, mk, biask, biasv, t.c->inv_freq, tp.att, r.s, tp.lse);
     // (the gated residual as an epilogue of this product, with u kept at a second address, was measured: the store phase is
     // what bounds the wide kernels, and the heavier epilogue cost 1.5 ms per step where the separate pass costs 1.3)
-    launch32_linear(tp.att, kC, wo, kC, bo, nrows, kC, kC, 0, tp.u, kC, 0, kNoMod, 0, 0, 0.f, r.s, 0, nullptr,
-                    wpack1(t, wo, kC, nrows, kC, kC, 0));
+    step_linear(t, tp.att, kC, wo, kC, bo, nrows, kC, kC, 0, tp.u, kC, 0, 0.f, r.s, 0, nullptr, wpack1(t, wo, kC, nrows, kC, kC, 0));
     gated_update(t, h, tp.h_in, tp.u, nrows, mm, gate);
     LAUNCHCHK();
     return 0;
@@ -279,21 +303,17 @@ static int attn_fwd_tape(const Train& t, const std::string& pre, float* h, long 
 static int mlp_fwd_tape(const Train& t, const std::string& pre, float* h, long nrows, const ModMap& mm, int shift, int scale,
                         int gate, const SubTapeMlp& tp) {
     const Run& r = t.r;
-    const F32Bufs b = f32_bufs(r);
     TW32(w1, pre + "fc1.weight"); TW32(b1, pre + "fc1.bias");
     TW32(w2, pre + "fc2.weight"); TW32(b2, pre + "fc2.bias");
     const bool wide = sub_wide({w1, w2});
-    const bool y16 = y_is_bf16(t, nrows, wide);
-    ln_mod_tape(t, h, nrows, mm, shift, scale, tp.y, tp.h_in, y16);     // y (taped), and the tape's copy of h
-    // hid = gelu(pre) is only ever a GEMM operand (fc2's input here, X of fc2's weight gradient): in the bf16-operand mode,
-    // at sizes where both consumers are the wide kernels, it is stored rounded (identical products, half the bytes)
-    const bool h16 = hid_is_bf16(nrows, wide);
+    const bool y16 = rows_bf16(t, nrows, wide);   // (y and hid = gelu(pre) alike)
+    if (int e = ln_mod_tape(t, h, nrows, mm, shift, scale, tp.y, tp.h_in, y16)) return e;     // y (taped), and the tape's copy of h
     const void* pk1 = wpack1(t, w1, kC, nrows, kF, kC, 0);
     if (y16 && !pk1) return fail(-7, "internal: bf16 LayerNorm output without the streamed fc1 kernel (rows %ld)", nrows);
-    launch32_linear(tp.y, kC, w1, kC, b1, nrows, kF, kC, 6, tp.pre, kF, 0, kNoMod, 0, 0, 0.f, r.s, 0, tp.hid, pk1, (h16 ? 2 : 0) | (y16 ? 1 : 0));
+    step_linear(t, tp.y, kC, w1, kC, b1, nrows, kF, kC, 6, tp.pre, kF, 0, 0.f, r.s, 0, tp.hid, pk1, y16 ? 3 : 0);
     const void* pk2 = wpack1(t, w2, kF, nrows, kC, kF, 0);
-    if (h16 && !pk2) return fail(-7, "internal: bf16 GELU output without the streamed fc2 kernel (rows %ld)", nrows);
-    launch32_linear(tp.hid, kF, w2, kF, b2, nrows, kC, kF, 0, tp.u, kC, 0, kNoMod, 0, 0, 0.f, r.s, 0, nullptr, pk2, h16 ? 1 : 0);
+    if (y16 && !pk2) return fail(-7, "internal: bf16 GELU output without the streamed fc2 kernel (rows %ld)", nrows);
+    step_linear(t, tp.hid, kF, w2, kF, b2, nrows, kC, kF, 0, tp.u, kC, 0, 0.f, r.s, 0, nullptr, pk2, y16 ? 1 : 0);
     gated_update(t, h, tp.h_in, tp.u, nrows, mm, gate);
     LAUNCHCHK();
     return 0;
@@ -344,23 +364,22 @@ static int lin_bwd(const Train& t, const float* dy, int ldy, const float* x, int
         if (int e = t.fork(&sw, &pt, &cpt)) return e;
     const int mode = gelu_pre ? 7 : (accumulate ? 5 : 0);
     float* c2 = const_cast<float*>(gelu_pre);
-    if (dx && g_k32_bf16_operands && M % 64 == 0 && (size_t)M * K <= (size_t)kF * kC) {
+    if (dx && t.bf16 && M % 64 == 0 && (size_t)M * K <= (size_t)kF * kC) {
         // bf16-operand mode: the weight turned once per use -- as a bf16 fragment stream for the streamed kernel, else as
         // an fp32 matrix [K][M] (the contraction contiguous) for the forward layers' kernels
         if (const void* pk = wpack1(t, W, K, n, K, M, 1)) {
-            launch32_linear(dy, ldy, W, M, nullptr, n, K, M, mode, dx, ldx_out, 0, kNoMod, 0, 0, 0.f, s, 0, c2, pk,
-                            (dy_bf16 ? 1 : 0) | (dx_bf16 ? 4 : 0));
+            step_linear(t, dy, ldy, W, M, nullptr, n, K, M, mode, dx, ldx_out, 0, 0.f, s, 0, c2, pk, (dy_bf16 ? 1 : 0) | (dx_bf16 ? 4 : 0));
         } else {
             if (dy_bf16 || dx_bf16) return fail(-7, "internal: bf16 dY / dX rows without the streamed dX kernel (rows %ld)", n);
             const float* wt = turned(t, &W, 1, M, K);
-            launch32_linear(dy, ldy, wt, M, nullptr, n, K, M, mode, dx, ldx_out, 0, kNoMod, 0, 0, 0.f, s, 0, c2);
+            step_linear(t, dy, ldy, wt, M, nullptr, n, K, M, mode, dx, ldx_out, 0, 0.f, s, 0, c2);
         }
     } else if (dx) {
         if (dy_bf16 || dx_bf16) return fail(-7, "internal: bf16 dY / dX rows outside the bf16-operand kernels (rows %ld)", n);
-        launch32_linear(dy, ldy, W, K, nullptr, n, K, M, mode, dx, ldx_out, 0, kNoMod, 0, 0, 0.f, s, 1, c2);
+        step_linear(t, dy, ldy, W, K, nullptr, n, K, M, mode, dx, ldx_out, 0, 0.f, s, 1, c2);
     }
     bool bias_done = false;
-    if (gw) bias_done = launch32_dw(dy, ldy, x, ldx, n, M, K, gw, pt, t.part_floats, sw, gb, x_bf16, dy_bf16);
+    if (gw) bias_done = step_dw(t, dy, ldy, x, ldx, n, M, K, gw, pt, sw, gb, x_bf16, dy_bf16);
     if (dy_bf16 && ((gw && !bias_done && gb) || (!gw && gb)))
         return fail(-7, "internal: bf16 dY rows without the wide weight-gradient kernel (rows %ld)", n);
     if (gb && !bias_done) launch32_colsum(dy, ldy, nullptr, 0, nullptr, 0, n, M, n, 0.f, gb, 0, cpt, t.cpart_floats, sw);
@@ -369,9 +388,8 @@ static int lin_bwd(const Train& t, const float* dy, int ldy, const float* x, int
 }
 
 // gated residual h_out = h_in + gate * u:  du = gate * dh (into t.du);  dgate[g] += sum_t dh * u
-// du16: t.du is written as bf16 rows (du_is_bf16: it is only ever the token operand of the dX product and dY of the weight gradient
+// du16: t.du is written as bf16 rows (rows_bf16: it is only ever the token operand of the dX product and dY of the weight gradient
 // of the sub-layer's last linear layer)
-static bool du_is_bf16(const Train& t, long nrows, bool wide) { return t.c->opt_train_du_bf16 && hid_is_bf16(nrows, wide); }
 static int gate_bwd(const Train& t, const float* dh, const float* u, long nrows, const ModMap& mm, int gate_chunk,
                     long tokens_per_group, long mod_ld, float* dmod_base, bool du16 = false) {
     hipStream_t s = t.r.s;
@@ -403,21 +421,18 @@ static void lnmod_bwd(const Train& t, const float* h_in, const float* dy, long n
 // backward of one MLP sub-layer; dh is updated in place (dh_in = dh_out + ...)
 static int mlp_bwd(const Train& t, const std::string& pre, float* dh, long nrows, const ModMap& mm, int shift, int scale, int gate,
                    long tpg, long mod_ld, float* dmod_base, const SubTapeMlp& tp) {
-    hipStream_t s = t.r.s;
     TW32(w1, pre + "fc1.weight");
     TW32(w2, pre + "fc2.weight");
     if (int e = t.begin_sub()) return e;
-    const bool wide = sub_wide({w1, w2});   // (as mlp_fwd_tape decided the tape's storage)
-    const bool du16 = du_is_bf16(t, nrows, wide);
-    if (int e = gate_bwd(t, dh, tp.u, nrows, mm, gate, tpg, mod_ld, dmod_base, du16)) return e;   // t.du = gate * dh
+    // (as mlp_fwd_tape decided the tape's storage): hid, y, du = gate * dh and d pre as bf16 rows, or all of them fp32
+    const bool r16 = rows_bf16(t, nrows, sub_wide({w1, w2}));
+    if (int e = gate_bwd(t, dh, tp.u, nrows, mm, gate, tpg, mod_ld, dmod_base, r16)) return e;   // t.du = gate * dh
     // d pre = (du W2) * gelu'(pre): the GELU derivative is the epilogue of the dX product
-    // (round 6) d pre is stored as bf16 rows: the token operand of fc1's dX product and dY of fc1's weight gradient (option train_dhid_bf16)
-    const bool dh16 = t.c->opt_train_dhid_bf16 && hid_is_bf16(nrows, wide);
     if (int e = lin_bwd(t, t.du, kC, tp.hid, kF, w2, nrows, kC, kF, t.dhid, kF, false, pre + "fc2.weight", pre + "fc2.bias", tp.pre,
-                        hid_is_bf16(nrows, wide), true, du16, dh16))
+                        r16, true, r16, r16))
         return e;
     if (int e = lin_bwd(t, t.dhid, kF, tp.y, kC, w1, nrows, kF, kC, t.dy, kC, false, pre + "fc1.weight", pre + "fc1.bias", nullptr,
-                        y_is_bf16(t, nrows, wide), true, dh16))
+                        r16, true, r16))
         return e;
     lnmod_bwd(t, tp.h_in, t.dy, nrows, mm, shift, scale, tpg, mod_ld, dmod_base, dh, true);
     LAUNCHCHK();
@@ -433,18 +448,16 @@ static int attn_bwd(const Train& t, const std::string& pre, float* dh, long nrow
     TW32(wo, pre + "out_proj.weight");
     TW32(biask, pre + "bias_k"); TW32(biasv, pre + "bias_v");
     if (int e = t.begin_sub()) return e;
-    const bool wide = sub_wide({wq, wk, wv, wo});   // (as attn_fwd_tape decided the tape's storage)
-    const bool du16 = du_is_bf16(t, nrows, wide);
-    if (int e = gate_bwd(t, dh, tp.u, nrows, mm, gate, tpg, mod_ld, dmod_base, du16)) return e;   // t.du
+    const bool r16 = rows_bf16(t, nrows, sub_wide({wq, wk, wv, wo}));   // (as attn_fwd_tape decided the tape's storage: y)
+    if (int e = gate_bwd(t, dh, tp.u, nrows, mm, gate, tpg, mod_ld, dmod_base, r16)) return e;   // t.du
     if (int e = lin_bwd(t, t.du, kC, tp.att, kC, wo, nrows, kC, kC, t.dy, kC, false, pre + "out_proj.weight", pre + "out_proj.bias",
-                        nullptr, false, true, du16))
+                        nullptr, false, true, r16))
         return e;                                                                        // t.dy = d att
-    // (round 6) the sequence-resident kernels write dq | dk | dv as bf16 rows: the buffer is only ever the token operand of the dX
-    // product and dY of the weight gradient (option train_dqkv_bf16; the bias gradients then sum the rounded values)
-    const bool dq16 = t.c->opt_train_dqkv_bf16 && attn16_seq_form(ax) && hid_is_bf16(nrows, wide);
-    if (g_k32_bf16_operands)
+    // the sequence-resident kernels write dq | dk | dv as bf16 rows (rows_bf16)
+    const bool dq16 = attn16_seq_form(ax) && r16;
+    if (t.bf16)
         launch16_attn_bwd(tp.qkv, 3 * kC, ax, mk, biask, biasv, t.c->inv_freq, tp.att, t.dy, t.dqkv, t.stats, t.dbias, s, tp.lse,
-                          attn16_seq_form(ax), dq16);   // (RoPE inside as the forward pass decided: attn_fwd_tape)
+                          attn16_seq_form(ax), attn16_seq_form(ax), dq16);   // (RoPE inside as the forward pass decided: attn_fwd_tape)
     else
         launch32_attn_bwd(tp.qkv, 3 * kC, ax, mk, biask, biasv, t.c->inv_freq, tp.att, t.dy, t.dqkv, t.stats, t.dbias, s, tp.lse);
     // bias key / value: rows [seq][dk: head x 24 | dv: head x 24] summed over sequences = the (1, 1, C) tensors
@@ -457,9 +470,9 @@ static int attn_bwd(const Train& t, const std::string& pre, float* dh, long nrow
         if (gk) launch32_colsum(t.dbias, 2 * kC, nullptr, 0, nullptr, 0, ax.nseq, kC, ax.nseq, 0.f, gk, 0, cpt, t.cpart_floats, sw);
         if (gv) launch32_colsum(t.dbias + kC, 2 * kC, nullptr, 0, nullptr, 0, ax.nseq, kC, ax.nseq, 0.f, gv, 0, cpt, t.cpart_floats, sw);
     }
-    if (!g_k32_bf16_operands)    // (the bf16-operand attention backward stores dq, dk already taken back through RoPE)
+    if (!t.bf16)    // (the bf16-operand attention backward stores dq, dk already taken back through RoPE)
         launch32_rope_bwd(t.dqkv, nrows, 3 * kC, pos_div, pos_mod, t.c->inv_freq, 1.0f / std::sqrt((float)kDH), s);
-    if (g_k32_bf16_operands) {
+    if (t.bf16) {
         // q | k | v as one layer of 1152 outputs: dy = dqkv [Wq; Wk; Wv] (one product with the contraction over all three,
         // the weights turned side by side into the scratch), dW and db of all three from one pass over (dqkv, y)
         const float* w3[3] = {wq, wk, wv};
@@ -471,16 +484,15 @@ static int attn_bwd(const Train& t, const std::string& pre, float* dh, long nrow
         if (want_g)                                    // (dqkv, y) are complete: the gradients go to the second stream
             if (int e = t.fork(&sw, &pt, &cpt)) return e;
         if (launch16_pack_wstream(w3, 3, kC, kC, nrows, kC, 3 * kC, 1, t.wt, s)) {
-            launch32_linear(t.dqkv, 3 * kC, wq, 3 * kC, nullptr, nrows, kC, 3 * kC, 0, t.dy, kC, 0, kNoMod, 0, 0, 0.f, s, 0, nullptr, t.wt,
+            launch16_linear(t.dqkv, 3 * kC, wq, 3 * kC, nullptr, nrows, kC, 3 * kC, 0, t.dy, kC, 0, kNoMod, 0, 0, 0.f, s, 0, nullptr, t.wt,
                             dq16 ? 1 : 0);
         } else {
             if (dq16) return fail(-7, "internal: bf16 q | k | v gradients without the streamed dX kernel (rows %ld)", nrows);
             const float* wt = turned(t, w3, 3, kC, kC);
-            launch32_linear(t.dqkv, 3 * kC, wt, 3 * kC, nullptr, nrows, kC, 3 * kC, 0, t.dy, kC, 0, kNoMod, 0, 0, 0.f, s, 0);
+            launch16_linear(t.dqkv, 3 * kC, wt, 3 * kC, nullptr, nrows, kC, 3 * kC, 0, t.dy, kC, 0, kNoMod, 0, 0, 0.f, s);
         }
         if (want_g) {
-            const bool bias_done = launch32_dw_seg(t.dqkv, 3 * kC, tp.y, kC, nrows, kC, 3, kC, gw3, gb3, pt, t.part_floats, sw,
-                                                   y_is_bf16(t, nrows, wide), dq16);
+            const bool bias_done = launch16_dw_seg(t.dqkv, 3 * kC, tp.y, kC, nrows, kC, 3, kC, gw3, gb3, pt, t.part_floats, sw, r16, dq16);
             if (dq16 && !bias_done && (gb3[0] || gb3[1] || gb3[2]))
                 return fail(-7, "internal: bf16 q | k | v gradients without the wide weight-gradient kernel (rows %ld)", nrows);
             for (int j = 0; j < 3 && !bias_done; ++j)
@@ -572,12 +584,10 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
     for (size_t i = 0; i < c->names.size(); ++i) t.idx[c->names[i]] = (int)i;
     const int saved_precision = c->opt_precision;
     c->opt_precision = 32;
-    // option train_precision = 16: the linear layers and weight gradients of THIS call multiply bf16-rounded operands on
-    // the bf16 MFMA (fp32 accumulate, fp32 master weights, everything else fp32) -- k_fp32.hip g_k32_bf16_operands
-    g_k32_bf16_operands = c->opt_train_precision == 16;
-    const int saved_form = g_k16_attn_form;
-    g_k16_attn_form = c->opt_train_attn_form;
-    struct Restore { mdgen_ctx* c; int p, f; ~Restore() { c->opt_precision = p; g_k32_bf16_operands = 0; g_k16_attn_form = f; } } restore{c, saved_precision, saved_form};
+    struct Restore { mdgen_ctx* c; int p; ~Restore() { c->opt_precision = p; } } restore{c, saved_precision};
+    // option train_precision = 16: the linear layers and weight gradients of this call multiply bf16-rounded operands on
+    // the bf16 MFMA (fp32 accumulate, fp32 master weights, everything else fp32)
+    t.bf16 = c->opt_train_precision == 16;
     if (int e = make_run(&t.r, c, sh, 1, 0, ws, ws_bytes, stream)) return e;
     Run& r = t.r;
     r.mask = mask; r.start_rot = start_rot; r.start_trans = start_trans; r.end_rot = two ? end_rot : nullptr; r.end_trans = two ? end_trans : nullptr; r.rel7_in = two ? rel7 : nullptr;
@@ -592,7 +602,7 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
     // profiles/r06_experiments.txt #19)
     if (c->opt_train_streams == 2 && !c->train_side) HIPCHK(hipStreamCreateWithFlags(&c->train_side, hipStreamNonBlocking));
     t.side = c->opt_train_streams == 2 ? c->train_side : nullptr;
-    if (t.side && c->opt_train_turn_ahead && g_k32_bf16_operands) {
+    if (t.side && t.bf16) {
         if (c->tr_plan_ok && c->tr_buf) {   // every turned weight of the call, on the second stream, beside the forward pass
             hipEvent_t e0 = t.next_event(), e1 = t.next_event();
             if (e0 && e1) {
@@ -664,10 +674,10 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
             TW32(wout, pre + "ipa.linear_out.weight"); TW32(bout, pre + "ipa.linear_out.bias");
             HIPCHK(hipMemcpyAsync(tp.h_in, hx, (size_t)Mp * kC * 4, hipMemcpyDeviceToDevice, s));
             launch32_ln_mod(hx, Mp, ModMap{w.gamma_beta, 1, 1, 0, 0}, 1, 0, 1, 1e-5f, fb.y, s);
-            launch32_linear(fb.y, kC, wq, kC, bq, Mp, 128, kC, 0, tp.proj, kIpaProj, 0, kNoMod, 0, 0, 0.f, s);
-            launch32_linear(fb.y, kC, wkv, kC, bkv, Mp, 256, kC, 0, tp.proj, kIpaProj, 128, kNoMod, 0, 0, 0.f, s);
-            launch32_linear(fb.y, kC, wqp, kC, bqp, Mp, 96, kC, 0, tp.proj, kIpaProj, 384, kNoMod, 0, 0, 0.f, s);
-            launch32_linear(fb.y, kC, wkp, kC, bkp, Mp, 192, kC, 0, tp.proj, kIpaProj, 480, kNoMod, 0, 0, 0.f, s);
+            step_linear(t, fb.y, kC, wq, kC, bq, Mp, 128, kC, 0, tp.proj, kIpaProj, 0, 0.f, s);
+            step_linear(t, fb.y, kC, wkv, kC, bkv, Mp, 256, kC, 0, tp.proj, kIpaProj, 128, 0.f, s);
+            step_linear(t, fb.y, kC, wqp, kC, bqp, Mp, 96, kC, 0, tp.proj, kIpaProj, 384, 0.f, s);
+            step_linear(t, fb.y, kC, wkp, kC, bkp, Mp, 192, kC, 0, tp.proj, kIpaProj, 480, 0.f, s);
             IpaAttnParams ap{};
             ap.proj = tp.proj; ap.rot = rot; ap.trans = trans;
             ap.mask_bl = (const float*)(r.ws + r.lay.mask_bl);
@@ -675,7 +685,7 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
             ap.ngroups = r.B; ap.B = r.B; ap.L = r.L;
             ap.part = t.part; ap.part_floats = t.part_floats;      // few groups: key loop sliced over workgroups
             launch_ipa_attn(ap, s);
-            launch32_linear(tp.feat, kIpaFeat, wout, kIpaFeat, bout, Mp, kC, kIpaFeat, 2, hx, kC, 0, kNoMod, 0, 0, 0.f, s);
+            step_linear(t, tp.feat, kIpaFeat, wout, kIpaFeat, bout, Mp, kC, kIpaFeat, 2, hx, kC, 0, 0.f, s);
             LAUNCHCHK();
             if (int e = attn_fwd_tape(t, pre + "mha_l.attn.", hx, Mp, axI, mm, 0, 1, 2, mkI, 1, r.L, ils[i])) return e;
             if (int e = mlp_fwd_tape(t, pre, hx, Mp, mm, 3, 4, 5, ims[i])) return e;
@@ -717,7 +727,7 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
     const AxisMap axL{r.B * r.T, r.L, r.B * r.T, 0, r.L, 1};
     const AxisMap axT{r.B * r.L, r.T, r.L, r.T * r.L, 1, r.L};
     const MaskMap mk{r.mask, 0};
-    t.defer_gate = c->opt_train_defer_gate != 0;   // the trunk's residual updates ride in the next sub-layer's LayerNorm launch
+    t.defer_gate = true;   // the trunk's residual updates ride in the next sub-layer's LayerNorm launch
     for (int i = 0; i < nl; ++i) {
         const std::string pre = "layers." + std::to_string(i) + ".";
         const ModMap mm{r.mod() + c->trunk_off(i), r.T * r.L, r.B, 0, r.mod_group_stride};
@@ -734,7 +744,7 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
     {
         const F32Bufs fb = f32_bufs(r);
         launch32_ln_mod(h, N, fm, 0, 1, 0, 1e-6f, fb.y, s);
-        launch32_linear(fb.y, kC, wfin, kC, bfin, N, r.D, kC, 0, pred, r.D, 0, kNoMod, 0, 0, 0.f, s);
+        step_linear(t, fb.y, kC, wfin, kC, bfin, N, r.D, kC, 0, pred, r.D, 0, 0.f, s);
         launch_masked_mse(pred, target, loss_mask, loss, TL * r.D, r.B, s, t.cpart, t.cpart_floats);
         LAUNCHCHK();
     }
@@ -769,7 +779,7 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
         float *pt = t.part, *cpt = t.cpart;
         if (gw || gb)   // (the block's d mod rows are complete here and nothing writes them again)
             if (int e = t.fork(&sw, &pt, &cpt)) return e;
-        if (gw) launch32_dw(t.dmod + off, (int)modld, silu_bwd, kC, r.B, rows, kC, gw, pt, t.part_floats, sw);
+        if (gw) step_dw(t, t.dmod + off, (int)modld, silu_bwd, kC, r.B, rows, kC, gw, pt, sw);
         if (gb) launch32_colsum(t.dmod + off, (int)modld, nullptr, 0, nullptr, 0, r.B, rows, r.B, 0.f, gb, 0, cpt, t.cpart_floats, sw);
         return 0;
     };
@@ -804,8 +814,8 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
             hipStream_t sw = s;
             float *pt = t.part, *cpt = t.cpart;
             if (int e = t.fork(&sw, &pt, &cpt)) return e;
-            if (float* g = t.G("latent_to_emb.weight")) launch32_dw(t.dh, kC, xt, r.D, N, kC, r.D, g, pt, t.part_floats, sw);
-            if (float* g = t.G("cond_to_emb.weight")) launch32_dw(t.dh, kC, r.x_cond, r.D, N, kC, r.D, g, pt, t.part_floats, sw);
+            if (float* g = t.G("latent_to_emb.weight")) step_dw(t, t.dh, kC, xt, r.D, N, kC, r.D, g, pt, sw);
+            if (float* g = t.G("cond_to_emb.weight")) step_dw(t, t.dh, kC, r.x_cond, r.D, N, kC, r.D, g, pt, sw);
             if (float* g = t.G("latent_to_emb.bias")) launch32_colsum(t.dh, kC, nullptr, 0, nullptr, 0, N, kC, N, 0.f, g, 0, cpt, t.cpart_floats, sw);
             if (float* g = t.G("cond_to_emb.bias")) launch32_colsum(t.dh, kC, nullptr, 0, nullptr, 0, N, kC, N, 0.f, g, 0, cpt, t.cpart_floats, sw);
         }
@@ -841,7 +851,7 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
         // stack input: aatype_to_emb[aatype] (+ latent_to_emb_{f,r}(rel7))
         if (float* g = t.G("aatype_to_emb.weight")) launch32_embed_rows_bwd(dhx, r.aatype, r.B, r.B, r.L, g, s);
         if (rel) {
-            if (float* g = t.G(w7name)) launch32_dw(dhx, kC, rel, 7, Mp, kC, 7, g, t.part, t.part_floats, s);
+            if (float* g = t.G(w7name)) step_dw(t, dhx, kC, rel, 7, Mp, kC, 7, g, t.part, s);
             if (float* g = t.G(b7name)) launch32_colsum(dhx, kC, nullptr, 0, nullptr, 0, Mp, kC, Mp, 0.f, g, 0, t.cpart, t.cpart_floats, s);
         }
         LAUNCHCHK();
@@ -864,16 +874,17 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
         float* dp1 = h1 + (size_t)r.B * kC;
         float* dp2 = dp1 + (size_t)r.B * kC;
         if (!launch32_skinny_wt(t.dmod, (int)modld, c->ada_w, kC, r.B, kC, c->modrow, dst, t.cpart, t.cpart_floats, s))
-            launch32_linear(t.dmod, (int)modld, c->ada_w, kC, nullptr, r.B, kC, c->modrow, 0, dst, kC, 0, kNoMod, 0, 0, 0.f, s, 1);
+            step_linear(t, t.dmod, (int)modld, c->ada_w, kC, nullptr, r.B, kC, c->modrow, 0, dst, kC, 0, 0.f, s, 1);
         launch32_temb_bwd(tvals, r.B, c->d.time_multiplier, c->t_w0, c->t_b0, c->t_w2, c->t_b2, dst, emb, h1, dp1, dp2, s);
-        if (float* g = t.G("t_embedder.mlp.2.weight")) launch32_dw(dp2, kC, h1, kC, r.B, kC, kC, g, t.part, t.part_floats, s);
+        if (float* g = t.G("t_embedder.mlp.2.weight")) step_dw(t, dp2, kC, h1, kC, r.B, kC, kC, g, t.part, s);
         if (float* g = t.G("t_embedder.mlp.2.bias")) launch32_colsum(dp2, kC, nullptr, 0, nullptr, 0, r.B, kC, r.B, 0.f, g, 0, t.cpart, t.cpart_floats, s);
-        if (float* g = t.G("t_embedder.mlp.0.weight")) launch32_dw(dp1, kC, emb, 256, r.B, kC, 256, g, t.part, t.part_floats, s);
+        if (float* g = t.G("t_embedder.mlp.0.weight")) step_dw(t, dp1, kC, emb, 256, r.B, kC, 256, g, t.part, s);
         if (float* g = t.G("t_embedder.mlp.0.bias")) launch32_colsum(dp1, kC, nullptr, 0, nullptr, 0, r.B, kC, r.B, 0.f, g, 0, t.cpart, t.cpart_floats, s);
         LAUNCHCHK();
     }
     if (int e = mark()) return e;
-    if (t.tr_record || (c->opt_train_turn_ahead && !c->tr_plan_ok && !t.tr_new.empty())) {   // the list for the next call
+    if (t.tr_use && t.tr_cursor != c->tr_plan.size()) c->tr_plan_ok = false;   // the list was not used up: record anew next call
+    if (t.tr_record) {   // the list for the next call
         size_t off = 0;
         for (mdgen_ctx::TurnReq& q : t.tr_new) {
             q.off = off;
@@ -928,12 +939,12 @@ extern "C" int32_t mdgen_debug_train_linear(int32_t precision, const float* a, i
     NONNULL(a, w, c);
     if ((precision != 16 && precision != 32) || n < 1 || m < 1 || k < 1) return fail(-2, "precision 16 | 32; n, m, k >= 1");
     hipStream_t s = (hipStream_t)stream;
-    const int saved = g_k32_bf16_operands;
-    g_k32_bf16_operands = precision == 16;
-    const void* pk = nullptr;
-    if (precision == 16 && scratch && launch16_pack_wstream(&w, 1, m, ldw, n, m, k, 0, scratch, s)) pk = scratch;
-    launch32_linear(a, lda, w, ldw, bias, n, m, k, 0, c, ldc, 0, kNoMod, 0, 0, 0.f, s, 0, nullptr, pk);
-    g_k32_bf16_operands = saved;
+    if (precision == 16) {
+        const void* pk = scratch && launch16_pack_wstream(&w, 1, m, ldw, n, m, k, 0, scratch, s) ? scratch : nullptr;
+        launch16_linear(a, lda, w, ldw, bias, n, m, k, 0, c, ldc, 0, kNoMod, 0, 0, 0.f, s, 0, nullptr, pk);
+    } else {
+        launch32_linear(a, lda, w, ldw, bias, n, m, k, 0, c, ldc, 0, kNoMod, 0, 0, 0.f, s);
+    }
     LAUNCHCHK();
     return 0;
 }
@@ -943,11 +954,10 @@ extern "C" int32_t mdgen_debug_train_dw(int32_t precision, const float* dy, int3
     if ((precision != 16 && precision != 32) || n < 1 || m < 1 || k < 1) return fail(-2, "precision 16 | 32; n, m, k >= 1");
     if (part_floats < (int64_t)2 * m * (k + 1)) return fail(-2, "part_floats must be >= 2 m (k + 1)");
     hipStream_t s = (hipStream_t)stream;
-    const int saved = g_k32_bf16_operands;
-    g_k32_bf16_operands = precision == 16;
-    const bool bias_done = launch32_dw(dy, ldy, x, ldx, n, m, k, dw, part, (size_t)part_floats, s, db);
+    bool bias_done = false;
+    if (precision == 16) bias_done = launch16_dw(dy, ldy, x, ldx, n, m, k, dw, part, (size_t)part_floats, s, db);
+    else launch32_dw(dy, ldy, x, ldx, n, m, k, dw, part, (size_t)part_floats, s);
     if (db && !bias_done) launch32_colsum(dy, ldy, nullptr, 0, nullptr, 0, n, m, n, 0.f, db, 0, part, (size_t)part_floats, s);
-    g_k32_bf16_operands = saved;
     LAUNCHCHK();
     return 0;
 }
@@ -961,23 +971,19 @@ extern "C" int32_t mdgen_debug_train_attention(int32_t precision, const float* q
     if ((precision != 16 && precision != 160 && precision != 161 && precision != 32) || ntok < 1 || nseq < 1 || len < 1 || inner < 1)
         return fail(-2, "precision 16 | 160 | 161 | 32; ntok, nseq, len, inner >= 1");
     hipStream_t s = (hipStream_t)stream;
-    const int saved_form = g_k16_attn_form;
-    struct RestoreForm { int f; ~RestoreForm() { g_k16_attn_form = f; } } restore_form{saved_form};
-    if (precision == 160) { g_k16_attn_form = 0; precision = 16; }   // the chunked kernels for every length
-    bool rope_inside = false;
-    if (precision == 161) {   // q, k given UNROTATED: the sequence-resident kernels rotate them (as the training step runs them)
-        g_k16_attn_form = 1;
-        precision = 16;
-        rope_inside = true;
-    }
     const AxisMap ax{nseq, len, inner, outer_stride, inner_stride, pos_stride};
+    // 16: the training step's attention form for the axis; 160: the chunked kernels for every length; 161: q, k given UNROTATED,
+    // the sequence-resident kernels rotate them (as the training step runs them)
+    const bool seq_form = precision != 160 && attn16_seq_form(ax);
+    const bool rope_inside = precision == 161;
+    if (precision == 160 || precision == 161) precision = 16;
     const MaskMap mk{mask, 0};
     // position of a token on this axis, as k32_rope_bwd wants it: (token / pos_div) % pos_mod
     const long pos_div = pos_stride;
-    if (rope_inside && !attn16_seq_form(ax)) return fail(-2, "precision 161: only axes of 129 .. 256 positions rotate q, k inside the kernels");
+    if (rope_inside && !seq_form) return fail(-2, "precision 161: only axes of 129 .. 256 positions rotate q, k inside the kernels");
     if (precision == 16) {
-        launch16_attn(qkv, 3 * kC, ax, mk, bias_k, bias_v, inv_freq, out, s, lse, rope_inside);
-        launch16_attn_bwd(qkv, 3 * kC, ax, mk, bias_k, bias_v, inv_freq, out, dout, dqkv, stats, dbias, s, lse, rope_inside);
+        launch16_attn(qkv, 3 * kC, ax, mk, bias_k, bias_v, inv_freq, out, s, lse, seq_form, rope_inside);
+        launch16_attn_bwd(qkv, 3 * kC, ax, mk, bias_k, bias_v, inv_freq, out, dout, dqkv, stats, dbias, s, lse, seq_form, rope_inside);
     } else {
         launch32_attn(qkv, 3 * kC, ax, mk, bias_k, bias_v, inv_freq, out, s, lse);
         launch32_attn_bwd(qkv, 3 * kC, ax, mk, bias_k, bias_v, inv_freq, out, dout, dqkv, stats, dbias, s, lse);

@@ -75,6 +75,18 @@ def test_plan_is_available_without_a_gpu_and_names_the_headline_kernels():
     assert [v["B"] for v in plan(16, 1000, 4, "euler_profiled")["views"]] == [16]
 
 
+def test_training_options_are_the_kept_ones():
+    """The training step's options are `train_precision` and `train_streams`; the switches of its bf16-operand forms (each form is
+    always taken where its shape allows) are unknown names, refused like any other (-4)."""
+    from mdgen_amd._lib import MdgenError
+    for name in ("train_y_bf16", "train_dqkv_bf16", "train_du_bf16", "train_dhid_bf16", "train_defer_gate", "train_turn_ahead",
+                 "train_attn_form"):
+        with pytest.raises(MdgenError, match="error -4: unknown option"):
+            plan(1, 250, 256, "forward", S=1, options={name: 1})
+    for opts in ({"train_precision": 16}, {"train_precision": 32}, {"train_streams": 1}, {"train_streams": 2}):
+        plan(1, 250, 256, "forward", S=1, options=opts)
+
+
 def test_every_registry_entry_names_an_existing_gpu_test():
     src = open(os.path.join(ROOT, "tests", "test_gpu_parity.py")).read()
     names = set(re.findall(r"^def (test_\w+)\(", src, re.M))

@@ -1900,12 +1900,14 @@ def test_training_gradients_bf16_operands_vs_reference_fixture():
     tm.model.set_option("train_precision", 32)
 
 
-def test_training_turned_weights_ahead_of_time():
-    """Option `train_turn_ahead` (default on): the turned weights of the small launches' dX products are computed on the second stream
+def test_training_turned_weights_ahead_match_one_stream():
+    """bf16 operands with a second stream: the turned weights of the small launches' dX products are computed on the second stream
     at the start of a call, from the request list the previous call recorded.  Call 1 records (everything in place), call 2 uses the
-    images, a call at another shape deviates from the list (falls back in place, records anew), the call after that uses the new
-    list: every call's loss and gradients are bit-identical to the same call with the option off -- also after the weights were
-    changed in place between two calls (the images are recomputed every call)."""
+    images, a call at a batch whose trunk takes the streamed kernels (>= 4 096 rows: fewer turned weights) deviates from the list
+    (falls back in place, the next call records anew), the calls after that record and use the new list; a second context at
+    another shape keeps a list of its own.  Every call's loss and gradients are bit-identical to the same call on one stream
+    (train_streams 1: no second stream, nothing turned ahead) -- also after the weights were changed in place between two calls
+    (the images are recomputed every call)."""
     from mdgen_amd.config import ModelConfig
     from mdgen_amd.synthetic import synth_state_dict, synth_forward_inputs
     from mdgen_amd.train import TrainableModel
@@ -1921,106 +1923,44 @@ def test_training_turned_weights_ahead_of_time():
                 inp["aatype"].to(dev))
 
     results = {}
-    for ahead in (1, 0):
+    for streams in (2, 1):
         out = []
         tms = {}
         for T, L in ((12, 40), (6, 24)):        # two models (num_frames is part of the config), sharing nothing
             cfg = ModelConfig.atlas(num_frames=T, crop=L)
             tm = TrainableModel(cfg, dev).load_state_dict(synth_state_dict(cfg, 11))
             tm.model.set_option("train_precision", 16)
-            tm.model.set_option("train_turn_ahead", ahead)
+            tm.model.set_option("train_streams", streams)
             tms[(T, L)] = (tm, make_args(cfg, 1, T, L, 3, 5))
         tm, args = tms[(12, 40)]
-        for call in range(4):
-            if call == 2:                       # the weights change in place (as after an optimiser step)
+        big = make_args(ModelConfig.atlas(num_frames=12, crop=40), 9, 12, 40, 3, 6)   # 9 x 12 x 40 = 4 320 trunk rows
+        for call in range(5):
+            if call == 3:                       # the weights change in place (as after an optimiser step)
                 with torch.no_grad():
                     tm.params.data.mul_(1.001)
                 tm.mark_updated()
             tm.zero_grad()
-            loss, _ = tm.forward_backward(*args)
+            loss, _ = tm.forward_backward(*(big if call == 2 else args))
             torch.cuda.synchronize()
-            out.append((float(loss), {k: v.detach().float().cpu().clone() for k, v in tm.params.state_dict(tm.grads).items()}))
+            out.append((loss.detach().cpu().clone(), {k: v.detach().float().cpu().clone() for k, v in tm.params.state_dict(tm.grads).items()}))
         tm2, args2 = tms[(6, 24)]               # a second context: its own list
         for call in range(2):
             tm2.zero_grad()
             loss, _ = tm2.forward_backward(*args2)
             torch.cuda.synchronize()
-            out.append((float(loss), {k: v.detach().float().cpu().clone() for k, v in tm2.params.state_dict(tm2.grads).items()}))
+            out.append((loss.detach().cpu().clone(), {k: v.detach().float().cpu().clone() for k, v in tm2.params.state_dict(tm2.grads).items()}))
         for tm_, _ in tms.values():
             tm_.model.set_option("train_precision", 32)
-        results[ahead] = out
-    for i, ((l1, g1), (l0, g0)) in enumerate(zip(results[1], results[0])):
-        assert l1 == l0, (i, l1, l0)
+        results[streams] = out
+    assert len(results[2]) == len(results[1]) == 7
+    for i, ((l1, g1), (l0, g0)) in enumerate(zip(results[2], results[1])):
+        assert torch.equal(l1, l0), (i, l1, l0)
         for k in g0:
             assert torch.equal(g1[k], g0[k]), (i, k)
     # call 1 (recorded in place) against call 2 (images computed ahead): the same inputs, the same bits
-    assert results[1][0][0] == results[1][1][0]
-    for k in results[1][0][1]:
-        assert torch.equal(results[1][0][1][k], results[1][1][1][k]), k
-
-
-def test_training_round6_options_agree():
-    """Options `train_defer_gate` (the trunk's gated residual updates formed by the next sub-layer's LayerNorm launch) and
-    `train_attn_form` (sequence-resident attention kernels, RoPE inside, for axes of 129 .. 256 positions), each against its off
-    value on one step of 160 frames x 130 residues with bf16 operands: deferring the update changes no arithmetic -- loss and every
-    gradient bit-identical; `train_y_bf16` (the trunk's taped LayerNorm outputs stored as bf16 rows: the kernels that read them round
-    them to bf16 anyway) likewise bit-identical; the attention forms round q at a different point (q log2 e instead of q) -- loss to 2e-3, every
-    gradient above the noise floor to rel-L2 2e-2."""
-    from mdgen_amd.config import ModelConfig
-    from mdgen_amd.synthetic import synth_state_dict, synth_forward_inputs
-    from mdgen_amd.train import TrainableModel
-    dev = _cuda()
-    B, T, L, npad = 1, 160, 130, 9
-    cfg = ModelConfig.atlas(num_frames=T, crop=L)
-    sd = synth_state_dict(cfg, 11)
-    inp = synth_forward_inputs(cfg, B, T, L, npad, 5)
-    gen = torch.Generator().manual_seed(9)
-    ut = torch.randn(B, T, L, cfg.latent_dim, generator=gen)
-    lm = (torch.rand(B, T, L, cfg.latent_dim, generator=gen) > 0.1).float() * inp["mask"][..., None]
-    args = (inp["x"].to(dev), inp["t"].to(dev), ut.to(dev), lm.to(dev), inp["mask"].to(dev),
-            (inp["start_rot"].to(dev), inp["start_trans"].to(dev)), inp["x_cond"].to(dev), inp["x_cond_mask"].to(dev),
-            inp["aatype"].to(dev))
-    res = {}
-    for name, opts in (("default", {}), ("gate_now", {"train_defer_gate": 0}), ("y_fp32", {"train_y_bf16": 0}),
-                       ("dqkv_fp32", {"train_dqkv_bf16": 0}), ("du_fp32", {"train_du_bf16": 0}), ("dhid_fp32", {"train_dhid_bf16": 0}),
-                       ("chunked", {"train_attn_form": 0})):
-        tm = TrainableModel(cfg, dev).load_state_dict(sd)
-        tm.model.set_option("train_precision", 16)
-        for k, v in opts.items():
-            tm.model.set_option(k, v)
-        tm.zero_grad()
-        loss, _ = tm.forward_backward(*args)
-        torch.cuda.synchronize()
-        res[name] = (float(loss), {k: v.detach().float().cpu().clone() for k, v in tm.params.state_dict(tm.grads).items()})
-        tm.model.set_option("train_precision", 32)
-    l0, g0 = res["default"]
-    for other in ("gate_now", "y_fp32"):
-        l1, g1 = res[other]
-        assert l0 == l1, (other, l0, l1)
-        for k in g0:
-            assert torch.equal(g0[k], g1[k]), (other, k)
-    # `train_dqkv_bf16` (the q | k | v gradients stored as bf16 rows): the dX product and the weight gradient round them to bf16 anyway
-    # -- bit-identical -- but the q / k / v BIAS gradients are column sums of the stored values: rounded then, to 5e-3
-    # `train_du_bf16` (the gated gradients du = gate * dh) likewise: only the out-projection / fc2 bias gradients may differ
-    # ... and `train_dhid_bf16` (d pre = d hid * gelu'(pre) of the MLPs): only the fc1 bias gradients
-    for other, biases in (("dqkv_fp32", ("q_proj.bias", "k_proj.bias", "v_proj.bias")), ("du_fp32", ("out_proj.bias", "fc2.bias")),
-                          ("dhid_fp32", ("fc1.bias",))):
-        l3, g3 = res[other]
-        assert l0 == l3, (other, l0, l3)
-        for k in g0:
-            if torch.equal(g0[k], g3[k]):
-                continue
-            assert k.endswith(biases), (other, k)
-            e = float((g0[k].double() - g3[k].double()).norm() / (g3[k].double().norm() + 1e-300))
-            assert e < 5e-3, (other, k, e)
-    l2, g2 = res["chunked"]
-    assert abs(l0 - l2) <= 2e-3 * abs(l2), (l0, l2)
-    gmax = max(float(v.norm()) for v in g2.values())
-    for k, ref in g2.items():
-        if float(ref.norm()) < 1e-4 * gmax:
-            continue
-        e = float((g0[k].double() - ref.double()).norm() / ref.double().norm())
-        assert e < 2e-2, (k, e)
+    assert torch.equal(results[2][0][0], results[2][1][0])
+    for k in results[2][0][1]:
+        assert torch.equal(results[2][0][1][k], results[2][1][1][k]), k
 
 
 @pytest.mark.parametrize("shape", [(1, 24, 203, 37), (1, 300, 5, 1), (1, 160, 130, 9), (1, 250, 256, 16)],
@@ -2032,8 +1972,8 @@ def test_training_bf16_operand_kernels_vs_exact_mode_at_tile_sizes(shape):
     two backward passes (k_attn16.hip) on both axes with ragged tiles (24 frames, 203 residues: partial 32-row tiles, the bias
     key inside a tile; 300 frames: three 128-query blocks, five 64-key chunks; 5 residues: one partial tile) and key padding,
     the bf16-stored GELU output (>= 4096 rows); (round 6) 203 residues and 160 frames x 130 residues: axes of 129 .. 256 positions
-    take the sequence-resident attention kernels with RoPE inside (no rotation pass; `train_attn_form`), and every trunk sub-layer's gated
-    update rides in the next LayerNorm launch (`train_defer_gate`); 250 frames x 256 residues = the shape bench.py's training leg
+    take the sequence-resident attention kernels with RoPE inside (no rotation pass), and every trunk sub-layer's gated
+    update rides in the next LayerNorm launch; 250 frames x 256 residues = the shape bench.py's training leg
     times (len 256: the bias key opens a ninth key tile) -- and compares train_precision 16 against the exact fp32 mode (itself gated against
     the reference's autograd above) on identical inputs: loss to 1e-2 relative, every parameter's gradient to rel-L2 5e-2 and
     cosine 0.999 (gradients at the noise floor excepted)."""
@@ -2278,7 +2218,7 @@ def test_training_attention_kernels_unit(ln, layout):
     chunks, 128- and 256-row workgroups; the bias key first / last in a tile; 1000 / 1001 = the tetrapeptide headline's temporal length), both token layouts of the trunk, random key
     padding plus a sequence whose first 40 keys are all padded (whole masked tiles) and one with every real key padded (only
     the bias key left).  Exact mode to 2e-5; bf16 operands: output 1e-2, gradients 3e-2, the bias key's 1e-1 (rel-L2 per tensor).
-    Lengths 129 .. 256 take the sequence-resident kernels (round 6, option `train_attn_form`: one workgroup per (sequence, head), the
+    Lengths 129 .. 256 take the sequence-resident kernels (round 6: one workgroup per (sequence, head), the
     whole sequence in LDS; 256 = the bias key opens a ninth tile that is shared out over the waves; 160 / 192 / 224: it is the first
     key of an owned tile) -- there the chunked kernels run as a third leg (precision 160) and the two forms must agree to 1e-2 (the sequence-resident
     forms round q log2(e) to bf16 where the chunked ones round q: measured 4e-3)."""

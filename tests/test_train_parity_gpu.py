@@ -197,8 +197,8 @@ def test_training_step_with_misaligned_parameter_binding():
     """The bf16 step with every bound weight 4 bytes off a 16-byte boundary (TrainableModel's flat buffer one float into an
     allocation): the streamed / wide kernels cannot take such weights, so the bf16 row stores of the tape (y, hid, du, d pre,
     dq | dk | dv) must not be chosen either -- the step falls back to fp32 storage instead of stopping with the -7 'internal: bf16
-    ...' error.  Against the aligned step: rel-L2 <= 1e-4 per tensor, the bias gradients of the storage options to 5e-3 (they
-    sum the rounded bf16 rows on the aligned step: test_training_round6_options_agree); and the fp64 gates of the bf16 mode."""
+    ...' error.  Against the aligned step: rel-L2 <= 1e-4 per tensor, the bias gradients of the layers whose dY is stored as
+    bf16 rows to 5e-3 (on the aligned step they sum the rounded rows); and the fp64 gates of the bf16 mode."""
     from mdgen_amd.train import TrainableModel
     dev = _cuda()
     ref = _fp64_reference("B1_T100_L83")
@@ -236,9 +236,8 @@ def test_training_batch_equals_mean_of_samples(name, prec):
     batch gradient equals (1/B) x the sum of the single-sample gradients.  Token rows are independent, so only the order of the
     weight-gradient reductions changes: rel-L2 <= 1e-5 per tensor in exact mode, 1e-4 in bf16 mode.  Where the single-sample run
     has fewer than 4 096 trunk rows and the batch has more (the CLI default: 4 000 per sample) the bf16 row stores of the batch
-    are fp32 in the single runs: the bias gradients that sum those stored rows (out-projection and fc2: train_du_bf16; fc1:
-    train_dhid_bf16; q / k / v on axes of 129 .. 256 positions: train_dqkv_bf16) are then gated at 5e-3, as in
-    test_training_round6_options_agree.  In bf16 mode the adaLN weight gradients are gated at 3e-4: their dY is the per-sample
+    are fp32 in the single runs: the bias gradients that sum those stored rows (out-projection and fc2: du; fc1: d pre; q / k / v
+    on axes of 129 .. 256 positions: dq | dk | dv) are then gated at 5e-3.  In bf16 mode the adaLN weight gradients are gated at 3e-4: their dY is the per-sample
     modulation gradient, itself a sum over the sample's rows whose slice plan (and so its last fp32 bits) follows the row count,
     and the product rounds it to bf16 -- a last-bit difference flips single bf16 ulps (measured 1.3e-4, layers.4 at ATLAS B2;
     the adaLN bias gradients, the same sums unrounded, agree to 2e-7)."""
