@@ -14,7 +14,8 @@
  *   - every launch goes on the caller's `stream` (a hipStream_t passed as void*) and nothing inside a
  *     call synchronises the device (graph-capturable).  One exception, documented: `mdgen_sample_euler`
  *     forks the second half of the batch onto one context-owned stream and joins it back onto `stream`
- *     before returning (event fork/join, no host wait; option "streams" = 1 disables it).
+ *     before returning (event fork/join, no host wait; option "streams" = 1 disables it).  A second:
+ *     `mdgen_sample_dopri5` reads its error ratio back once per attempted step (8 bytes, stream synchronised).
  *   - return 0 on success, negative = invalid argument / state, positive = hipError_t.
  *     `mdgen_last_error()` returns a thread-local message.  No exceptions cross the ABI.
  *   - a context is not thread-safe; use one per device per process.
@@ -235,6 +236,37 @@ int32_t mdgen_sample_euler(mdgen_ctx* ctx, const mdgen_shape* shape, int32_t n_s
                            const float* x_cond, const int64_t* x_cond_mask, const int64_t* aatype,
                            void* workspace, size_t workspace_bytes, int32_t use_graph, void* stream);
 
+/* The reference's default solver: `sample_ode(sampling_method='dopri5')` -> torchdiffeq 0.2.x
+ * odeint(f, x0, linspace(0, 1, 50), method='dopri5', atol=[atol], rtol=[rtol])[-1] (transport.py:408-451,
+ * integrators.py:74-113; wrapper.py:441-447 takes the method from the checkpoint's args, default 'dopri5', parsing.py:102).
+ * Adaptive Dormand-Prince with torchdiffeq's mixed precision (fp32 state, fp64 times / tolerances / norms; csrc/ode.inc):
+ * the error norm is the RMS over the WHOLE (B, T, L, D) state, so one step size is shared by the batch -- a B = 2 call is a
+ * valid solve, but not the two B = 1 solves the reference would run for two separate calls.
+ *   x            (B,T,L,D) fp32, 16-byte aligned: the noise on entry, the state at t = 1 on exit (the step's dense output)
+ *   max_steps    limit on attempted steps (an error when exceeded)
+ *   stats_host   [3] out: network evaluations (2 + 6 x attempted steps), accepted steps, rejected steps (also on error)
+ *   steps_host   nullable, [max_steps][2] out: (t0, dt) of every accepted step, fp64
+ *   workspace    mdgen_dopri5_workspace_bytes: the network workspace for six t-shared time rows + 9 state buffers + partials
+ * Exception to "nothing synchronises": after every attempted step the error ratio (8 bytes) is copied into pinned memory
+ * and `stream` is synchronised.  A stream that is being captured is refused (-8) before anything is enqueued.  Errors:
+ * -9 non-finite norm / error ratio, -10 more than max_steps attempts, -11 dt underflow (t0 + dt == t0). */
+int32_t mdgen_sample_dopri5(mdgen_ctx* ctx, const mdgen_shape* shape, double atol, double rtol, int32_t max_steps,
+                            float* x, const float* mask,
+                            const float* start_rot, const float* start_trans,
+                            const float* end_rot, const float* end_trans, const float* rel7,
+                            const float* x_cond, const int64_t* x_cond_mask, const int64_t* aatype,
+                            void* workspace, size_t workspace_bytes, int32_t* stats_host, double* steps_host, void* stream);
+int32_t mdgen_dopri5_workspace_bytes(const mdgen_ctx* ctx, const mdgen_shape* shape, size_t* bytes);
+
+/* Host-only test hook (no GPU): mdgen_sample_dopri5's step-size controller replayed on given norms.  init = {d0, d1,
+ * rms((f1 - k1) / scale)} of the initial-step rule; ratios[i]: the error ratio of attempted step i.  Writes per attempt
+ * t0[i], dt[i], the six stage times as fp32 bits stage_bits[6 i .. 6 i + 5], accept[i]; probe[2]: the fp32 coefficient
+ * of x0 + h0 k1 and the probe's model time; *dense_s: the dense-output fraction once an accepted step reached t = 1.
+ * Returns 0 (reached t = 1), 1 (ratios ran out first) or the sampler's error codes (-9, -10, -11). */
+int32_t mdgen_debug_dopri5_controller(const double* init, const double* ratios, int32_t n_ratios, int32_t max_steps,
+                                      float* probe, double* t0, double* dt, uint32_t* stage_bits, int32_t* accept,
+                                      float* dense_s, int32_t* n_attempts);
+
 /* Residue constant tables (device pointers; data of mdgen/residue_constants.py:1124-1216, 1367-1480), as the two
  * geometry entry points below take them one by one. */
 typedef struct mdgen_residue_tables {
@@ -293,7 +325,8 @@ int32_t mdgen_profile_report(mdgen_ctx* ctx, void* stream, char* buf, size_t buf
 /* Host only (no device, no context): which kernel classes a call of this shape launches and how often -- the library's own
  * orchestration code (the code path of latent_model.py:212-260 / transport.py:408-451's replacements above) run in a plan mode
  * that skips every HIP call.  mode 0: mdgen_sample_euler as the product runs it (sub-batch streams); 1: mdgen_denoiser_forward;
- * 2: mdgen_sample_euler as it runs under mdgen_profile_enable (one stream); 3: mdgen_denoiser_forward with trace_h.  options: "name=value,..." with mdgen_ctx_set_option's
+ * 2: mdgen_sample_euler as it runs under mdgen_profile_enable (one stream); 3: mdgen_denoiser_forward with trace_h; 4: one attempted
+ * step of mdgen_sample_dopri5 (n_steps ignored; adds "integrator": {class: launches}).  options: "name=value,..." with mdgen_ctx_set_option's
  * names (bf16 path only).  ncu / xcd_round_robin: the two device facts mdgen_ctx_create would have probed (see "@context" of
  * mdgen_profile_report).  Writes {"streams": n, "prepare": {"<class>": launches, ...} (the step-invariant part: adaLN table, IPA stack, fold pack),
  * "views": [{"B": samples of the sub-batch view, "classes": {...}}, ...]} with the class names of mdgen_profile_report.  tests/test_dispatch_cpu.py sweeps shapes with it and fails when a combination of

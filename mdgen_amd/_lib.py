@@ -23,6 +23,7 @@ EXPORTS = [
     "mdgen_train_forward_backward",
     "mdgen_train_num_milestones", "mdgen_train_bind_params",
     "mdgen_train_set_milestone_events",
+    "mdgen_sample_dopri5", "mdgen_dopri5_workspace_bytes", "mdgen_debug_dopri5_controller",
 ]
 
 
@@ -69,6 +70,10 @@ def _load():
     lib.mdgen_workspace_layout.argtypes = [vp, C.POINTER(Shape), i32, i32, C.POINTER(WsLayout)]
     lib.mdgen_denoiser_forward.argtypes = [vp, C.POINTER(Shape)] + [vp] * 15 + [sz, vp]
     lib.mdgen_sample_euler.argtypes = [vp, C.POINTER(Shape), i32] + [vp] * 11 + [sz, i32, vp]
+    f64 = C.c_double
+    lib.mdgen_sample_dopri5.argtypes = [vp, C.POINTER(Shape), f64, f64, i32] + [vp] * 10 + [vp, sz, C.POINTER(i32), vp, vp]
+    lib.mdgen_dopri5_workspace_bytes.argtypes = [vp, C.POINTER(Shape), C.POINTER(sz)]
+    lib.mdgen_debug_dopri5_controller.argtypes = [vp, vp, i32, i32] + [vp] * 7
     lib.mdgen_rollout_euler.argtypes = [vp, C.POINTER(Shape), i32, i32] + [vp] * 8 + [C.POINTER(ResidueTables), vp, vp, sz, i32, vp]
     lib.mdgen_profile_enable.argtypes = [vp, i32]
     lib.mdgen_profile_phase_trace.argtypes = [vp, vp, i64]
@@ -161,7 +166,8 @@ def launch(fn, like, *args):
 
 def dispatch_plan(B, T, L_, n_steps=1, mode=0, tps=False, num_layers=5, ncu=256, xcd_round_robin=True, options=None):
     """`mdgen_debug_dispatch_plan` (host only): {"streams", "prepare": {kernel class: launches}, "views": [{"B", "classes"}]} of a call of this shape.
-    mode 0: sample_euler (product path), 1: forward, 2: sample_euler under the profiler (one stream)."""
+    mode 0: sample_euler (product path), 1: forward, 2: sample_euler under the profiler (one stream), 3: forward with trace_h,
+    4: one attempted step of sample_dopri5 (adds "integrator": {kernel class: launches})."""
     import json
     buf = C.create_string_buffer(1 << 14)
     sh = Shape(B, T, L_)

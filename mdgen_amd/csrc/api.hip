@@ -172,6 +172,7 @@ struct mdgen_ctx {
     bool tr_plan_ok = false;
     std::vector<hipEvent_t> train_ev;   // event pool of that fork / join traffic (created on first use, round-robin)
     size_t train_ev_next = 0;
+    double* ode_host = nullptr;     // mdgen_sample_dopri5: pinned 2 x fp64 the norms / error ratio are read back through (first use)
     int opt_mlp_fold = 1;       // sampling (t shared by the batch): the MLP gate folded into per-(step, layer) fc2 streams, k_mlp_rows starts its
                                 // accumulators from the residual rows and only stores (one HBM read of the rows instead of two)
     int opt_mlp_tail = 2;       // ... and the FinalLayer + Euler update run inside the last layer's (folded) MLP kernel, which then does not store
@@ -608,6 +609,7 @@ extern "C" int32_t mdgen_ctx_destroy(mdgen_ctx* c) {
     for (hipEvent_t e : c->train_ev) (void)hipEventDestroy(e);
     if (c->train_side) (void)hipStreamDestroy(c->train_side);
     if (c->tr_buf) (void)hipFree(c->tr_buf);
+    if (c->ode_host) (void)hipHostFree(c->ode_host);
     for (int i = 0; i < mdgen_ctx::kMaxSide; ++i) {
         if (c->ev_join[i]) (void)hipEventDestroy(c->ev_join[i]);
         if (c->side[i]) (void)hipStreamDestroy(c->side[i]);
@@ -881,6 +883,7 @@ struct Run {
     // embedding-as-tail: base rows [S][B*L][384] (step 0, first batch element of this view), null when off; floats between steps
     const float* embase_p;
     long embase_step_stride;
+    bool no_embed_tail;          // the call never runs the embedding-as-tail form (mdgen_sample_dopri5): prepare() skips its base rows
     float* h() const { return hp; }
     float* mod() const { return modp; }
 };
@@ -1396,7 +1399,7 @@ static int prepare(Run& r, const float* t_dev, const float* t_host, long view_ro
         if (!g_dry) launch_add_inplace(ipa_out, h2, r.Mp * kC, r.s);
         LAUNCHCHK();
     }
-    if (r.fold_ready && c->opt_mlp_tail == 2 && r.S > 1) {
+    if (r.fold_ready && c->opt_mlp_tail == 2 && r.S > 1 && !r.no_embed_tail) {
         // steps 1 .. S-1 take their token embedding from the previous step's last MLP launch (rows_embed_tail): the part of it that does
         // not depend on x, per (step, b, l)
         float* eb = (float*)(r.ws + r.lay.embase);
@@ -1549,6 +1552,7 @@ static int make_run(Run* r, mdgen_ctx* c, const mdgen_shape* sh, int S, int t_sh
     r->fold_ready = false;
     r->embase_p = nullptr;
     r->embase_step_stride = (long)sh->B * sh->L * kC;
+    r->no_embed_tail = false;
     if (fold_on(c, r->N, t_shared, S)) {
         r->fold_streams = r->ws + r->lay.fold;
         r->fold_b2g = (float*)(r->fold_streams + (size_t)S * c->nl * kFoldStreamBytes);
@@ -1802,19 +1806,23 @@ extern "C" int32_t mdgen_rollout_euler(mdgen_ctx* c, const mdgen_shape* sh, int3
     return replay_or_capture(c, key, r.s, body);
 }
 
+#include "ode.inc"
+
 // ---------------------------------------------------------------------------------------------
 // dispatch plan (host only)
 // ---------------------------------------------------------------------------------------------
 // Which kernel classes a call of this shape launches, and how often: the sampler's orchestration code above, run in plan mode
 // (g_dry) on a context that owns no device memory.  mode 0: mdgen_sample_euler as the product runs it (sub-batch streams);
-// 1: mdgen_denoiser_forward; 2: mdgen_sample_euler as mdgen_profile_enable sees it (one stream); 3: mdgen_denoiser_forward with trace_h.  options: "name=value,..."
+// 1: mdgen_denoiser_forward; 2: mdgen_sample_euler as mdgen_profile_enable sees it (one stream); 3: mdgen_denoiser_forward with trace_h;
+// 4: one attempted step of mdgen_sample_dopri5 (ode.inc dopri5_plan; n_steps is ignored).  options: "name=value,..."
 // (mdgen_ctx_set_option names).  ncu / xcd_round_robin: what mdgen_ctx_create would have found on the device.
 // Output: {"streams": n, "prepare": {"<class>": launches, ...}, "views": [{"B": samples of the view, "classes": {...}}, ...]}.
 extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_steps, int32_t mode, int32_t tps_condition,
                                              int32_t num_layers, int32_t ncu, int32_t xcd_round_robin, const char* options,
                                              char* buf, size_t buflen) {
     if (!sh || !buf || buflen < 64) return fail(-1, "null argument");
-    if (mode < 0 || mode > 3) return fail(-2, "mode: 0 sample_euler, 1 forward, 2 sample_euler under the profiler, 3 forward with trace_h");
+    if (mode < 0 || mode > 4)
+        return fail(-2, "mode: 0 sample_euler, 1 forward, 2 sample_euler under the profiler, 3 forward with trace_h, 4 one dopri5 step");
     if (num_layers < 1 || num_layers > 8 || ncu < 1) return fail(-2, "num_layers in 1..8, ncu >= 1");
     mdgen_ctx ctx;   // no device memory, no streams: plan mode never touches them
     mdgen_ctx* c = &ctx;
@@ -1844,6 +1852,7 @@ extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_st
         Dry(std::vector<std::string>* p) { g_dry = p; }
         ~Dry() { g_dry = nullptr; }
     } dry(&plan);
+    if (mode == 4) return dopri5_plan(c, sh, plan, buf, buflen);
     const bool fwd = mode == 1 || mode == 3;
     const int S = fwd ? 1 : n_steps;
     const int t_shared = fwd ? (sh->B == 1 ? 1 : 0) : 1;

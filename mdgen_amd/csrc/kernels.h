@@ -338,6 +338,30 @@ void launch_add_inplace(float* dst, const float* src, long n, hipStream_t s);
 void launch_write_floats(const float* host_vals, int n, float* dst, hipStream_t s);
 void launch_rel7(const float* r1, const float* t1, const float* r2, const float* t2, float* out7, long n, hipStream_t s);
 
+// adaptive dopri5 sampler (k_ode.hip; orchestration in ode.inc).  Buffers: fp32 (B, T, L, D) states, 16-byte aligned.
+constexpr int kOdeMaxTerms = 7;
+constexpr int kOdeMaxParts = 1024;   // workgroups of a norm launch (its partials: [parts][2] fp64)
+struct OdeTerms {                    // y = y0 + sum_{j < nk} c[j] k[j]
+    const float* k[kOdeMaxTerms];
+    float c[kOdeMaxTerms];
+    int nk;
+};
+struct OdeNorm {
+    // mode 0: a = x0, b = k1 -> rms(x0 / scale), rms(k1 / scale) with scale = atol + |x0| rtol
+    // mode 1: a = x0, b = k1, k[0] = f1 -> rms((f1 - k1) / scale)
+    // mode 2: a = y0, b = y1, k[0..6], e -> rms(sum_j e_j k_j / (atol + rtol max(|y0|, |y1|)))
+    const float *a, *b;
+    const float* k[kOdeMaxTerms];
+    float e[kOdeMaxTerms];
+    double atol, rtol;
+    int mode;
+};
+void launch_ode_combine(float* out, const float* y0, const OdeTerms& p, long n, hipStream_t s);
+int ode_norm_parts(long n);
+void launch_ode_norm(const OdeNorm& p, long n, double* part, double* out, hipStream_t s);   // out[0], out[1]: the two rms values
+void launch_ode_dense(float* out, const float* y0, const float* y1, const float* f0, const float* f1, const float* ym, float dt,
+                      float sfrac, long n, hipStream_t s);
+
 // SE(3) / pre / post (k_se3.hip)
 void launch_rigid_compose(long n, const float* r1, const float* t1, const float* r2, const float* t2, float* ro,
                           float* to, hipStream_t s);

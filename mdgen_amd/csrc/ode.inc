@@ -1,0 +1,419 @@
+// ode.inc -- adaptive Dormand-Prince sampling (included by api.hip; kernels in k_ode.hip).
+//
+// The reference's NewMDGenWrapper.inference() integrates with the checkpoint's own `sampling_method` (wrapper.py:441-447), by
+// default 'dopri5' (parsing.py:102): transport.py:408-451 / integrators.py:74-113 call
+//     odeint(f, x0, t = linspace(0, 1, 50) fp32, method='dopri5', atol=[1e-6], rtol=[1e-3])[-1],   f(t, x) = model(x, ones(B) t)
+// (velocity drift, transport.py:242-244).  This file restates torchdiffeq 0.2.x's dopri5 (rk_common.py
+// RKAdaptiveStepsizeODESolver, misc.py _select_initial_step / _optimal_step_size, dopri5.py tableau) with its mixed precision:
+//   - state, stages and k are fp32; time-like values (t0, dt, t1) fp64; atol / rtol are 1-element fp64 tensors, so the
+//     tolerances, the norms and the error ratio are fp64; every time that reaches the model is cast to fp32 first;
+//   - the norm is the RMS over every element of the whole (B, T, L, D) state (all samples, conditioning frames, padded
+//     residues): ONE step size for the whole batch -- a B = 2 call is not two B = 1 solves;
+//   - the 50-point output grid only decides where the solve stops: the steps are taken until an accepted step ends at
+//     t1 >= 1 (the model is evaluated past t = 1, nothing is clamped) and the output is that step's 4th-order dense output
+//     at t = 1;
+//   - network evaluations: 2 (k1, and the initial-step probe) + 6 per attempted step (FSAL: k7 of an accepted step is k1
+//     of the next).
+// Orchestration: per attempted step ONE prepare() for its six stage times as t-shared rows (adaLN table, IPA stack, folded
+// fc2 streams), then six denoise_step(..., out = k_i, euler = 0) -- the sampler's own network path; the FinalLayer tail of
+// the last MLP launch writes the velocity.  The embedding-as-tail form is not used (the next stage's input is not known
+// inside the launch).  Batches that need several launch views run them per stage on the caller's stream.
+// Controller: plain host C++ in fp64 (Dopri5Ctl).  Once per attempted step the error ratio (8 bytes) is copied into pinned
+// memory and the caller's stream is synchronised -- the documented exception to "nothing synchronises".
+
+namespace ode {
+constexpr int kStages = 6;     // network evaluations per attempted step (k2 .. k7)
+constexpr int kBufs = 9;       // Y1 (stage inputs; y1 after stage 7), K0 .. K6, Y_mid; Y0 starts as the caller's x
+// dopri5.py _DORMAND_PRINCE_SHAMPINE_TABLEAU and DPS_C_MID: fp64 expressions, cast to the state's dtype (fp32) by the solver
+const double kAlpha[kStages] = {1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0, 1.0};
+const double kBeta[kStages][kStages] = {
+    {1.0 / 5},
+    {3.0 / 40, 9.0 / 40},
+    {44.0 / 45, -56.0 / 15, 32.0 / 9},
+    {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729},
+    {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656},
+    {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84}};
+const double kErr[7] = {35.0 / 384 - 1951.0 / 21600, 0, 500.0 / 1113 - 22642.0 / 50085, 125.0 / 192 - 451.0 / 720,
+                        -2187.0 / 6784 - -12231.0 / 42400, 11.0 / 84 - 649.0 / 6300, -1.0 / 60.0};
+const double kMid[7] = {6025192743.0 / 30085553152.0 / 2, 0, 51252292925.0 / 65400821598.0 / 2, -2691868925.0 / 45128329728.0 / 2,
+                        187940372067.0 / 1594534317056.0 / 2, -1776094331.0 / 19743644256.0 / 2, 11237099.0 / 235043384.0 / 2};
+}  // namespace ode
+
+// The step-size controller: a pure state machine over the norms the device reports (no HIP call).
+struct Dopri5Ctl {
+    double t0 = 0.0, dt = 0.0;         // time of the current state; step to attempt next
+    double last_t0 = 0.0, last_dt = 0.0, last_t1 = 0.0;   // the last accepted step (its dense output gives the result)
+    double h0 = 0.0;                   // initial-step probe (misc.py _select_initial_step)
+    bool h0_f32 = false;               // ... the d0 | d1 < 1e-5 branch makes h0 an fp32 tensor
+    bool done = false;
+    int accepted = 0, rejected = 0;
+
+    // from d0 = rms(x0 / scale), d1 = rms(k1 / scale): h0; the probe evaluates f(t0 + h0, x0 + h0 k1)
+    void probe(double d0, double d1) {
+        if (d0 < 1e-5 || d1 < 1e-5) {
+            h0 = (double)1e-6f;
+            h0_f32 = true;
+        } else {
+            h0 = 0.01 * d0 / d1;
+            h0_f32 = false;
+        }
+        h0 = std::fabs(h0);
+    }
+    float probe_coef() const { return (float)h0; }             // y1 = y0 + h0 * f0 in fp32
+    float probe_time() const { return (float)(t0 + h0); }      // t0 + h0 in fp64, cast for the model
+    // d2n = rms((f1 - k1) / scale): the first step
+    void first_step(double d1, double d2n) {
+        const double d2 = std::fabs(d2n / h0);
+        double h1;
+        if (d1 <= 1e-15 && d2 <= 1e-15) {
+            if (h0_f32) {
+                const float a = 1e-6f, b = (float)h0 * (float)1e-3;
+                h1 = (double)(a < b ? b : a);
+            } else {
+                const double a = (double)1e-6f, b = h0 * 1e-3;
+                h1 = a < b ? b : a;
+            }
+        } else {
+            h1 = std::pow(0.01 / std::max(d1, d2), 1.0 / (double)(4 + 1));   // order - 1 = 4
+        }
+        h1 = std::fabs(h1);
+        const double big = h0_f32 ? (double)(100.f * (float)h0) : 100 * h0;
+        dt = std::min(big, h1);
+    }
+    // model times of the six stages (rk_common.py _runge_kutta_step): fp32 t0 + alpha dt; the alpha = 1 stages at
+    // nextafter(fp32(t0 + dt), -inf) (Perturb.PREV)
+    void stage_times(float* t) const {
+#pragma clang fp contract(off)
+        const float t0f = (float)t0, dtf = (float)dt, t1f = (float)(t0 + dt);
+        for (int i = 0; i < ode::kStages; ++i) {
+            const float a = (float)ode::kAlpha[i];
+            t[i] = a == 1.f ? std::nextafter(t1f, -INFINITY) : t0f + a * dtf;
+        }
+    }
+    float dt32() const { return (float)dt; }
+    bool underflow() const { return !(t0 + dt > t0); }
+    // one attempted step's error ratio: accept iff ratio <= 1; the next dt (misc.py _optimal_step_size: safety 0.9,
+    // ifactor 10, dfactor 0.2, order 5)
+    bool step(double ratio) {
+        const bool accept = ratio <= 1;
+        const double t1 = t0 + dt;
+        if (accept) {
+            last_t0 = t0;
+            last_dt = dt;
+            last_t1 = t1;
+            t0 = t1;
+            ++accepted;
+            done = t0 >= 1.0;   // torchdiffeq _advance: while next_t (= 1.0) > t1
+        } else {
+            ++rejected;
+        }
+        double f;
+        if (ratio == 0) {
+            f = 10.0;
+        } else {
+            const double dfac = ratio < 1 ? 1.0 : 0.2;
+            const double g = 0.9 / std::pow(ratio, 1.0 / 5.0);
+            f = std::min(10.0, std::max(g, dfac));
+        }
+        dt = dt * f;
+        return accept;
+    }
+    // rk_common.py _interp_evaluate: s = (t - t0) / (t1 - t0) at t = 1, cast to fp32
+    float dense_s() const { return (float)((1.0 - last_t0) / (last_t1 - last_t0)); }
+};
+
+struct OdeBufs {
+    float *y0, *y1, *k[7], *ym;
+    double *part, *out;
+};
+
+static size_t ode_state_bytes(const mdgen_ctx* c, const mdgen_shape* sh) {
+    return align256((size_t)sh->B * sh->T * sh->L * c->D * 4);
+}
+
+extern "C" int32_t mdgen_dopri5_workspace_bytes(const mdgen_ctx* c, const mdgen_shape* sh, size_t* bytes) {
+    if (!bytes) return fail(-1, "null argument");
+    mdgen_ws_layout lay;
+    if (int e = mdgen_workspace_layout(c, sh, ode::kStages, 1, &lay)) return e;
+    *bytes = align256(lay.total_bytes) + ode::kBufs * ode_state_bytes(c, sh) + align256((size_t)kOdeMaxParts * 2 * 8) + 256;
+    return 0;
+}
+
+// y = y0 + sum_{j < n} fp32(fp32(coef_j) * dt) k_j
+static int ode_combine(const Run& r, float* y, const float* y0, float* const* k, const double* coef, int n, float dt) {
+#pragma clang fp contract(off)
+    OdeTerms p{};
+    for (int j = 0; j < n; ++j) {
+        p.k[j] = k[j];
+        p.c[j] = (float)coef[j] * dt;
+    }
+    p.nk = n;
+    { ProfScope ps(r.c, "ode_combine", r.s); if (!g_dry) launch_ode_combine(y, y0, p, (long)r.N * r.D, r.s); }
+    LAUNCHCHK();
+    return 0;
+}
+
+static int ode_norm(const Run& r, const OdeBufs& b, const OdeNorm& p) {
+    { ProfScope ps(r.c, "ode_norm", r.s); if (!g_dry) launch_ode_norm(p, (long)r.N * r.D, b.part, b.out, r.s); }
+    LAUNCHCHK();
+    return 0;
+}
+
+// prepare() for `n` time rows shared by the batch (the workspace is carved for kStages rows)
+static int ode_prepare(Run& r, const float* times, int n, long view_rows) {
+    r.S = n;
+    r.Mp = (long)n * r.B * r.L;
+    return prepare(r, nullptr, times, view_rows);
+}
+
+// one network evaluation at prepared row `row`: y -> velocity k, over the call's launch views
+static int ode_eval(const Run& r, int nv, int row, const float* y, float* k) {
+    if (nv <= 1) {
+        if (g_dry) g_dry->push_back("@view0");
+        return denoise_step(r, row, const_cast<float*>(y), k, 0, 0.f, nullptr);
+    }
+    int b0 = 0;
+    for (int i = 0; i < nv; ++i) {   // sequential sub-batch views on the caller's stream
+        const int Bs = r.B / nv + (i < r.B % nv ? 1 : 0);
+        const Run v = sub_run(r, b0, Bs, r.s);
+        const long o = (long)b0 * r.T * r.L * r.D;
+        if (g_dry) g_dry->push_back("@view" + std::to_string(i));
+        if (int e = denoise_step(v, row, const_cast<float*>(y) + o, k + o, 0, 0.f, nullptr)) return e;
+        b0 += Bs;
+    }
+    return 0;
+}
+
+// One attempted step from (t0, Y0, K0, dt): prepare the six stage rows, y_i = y0 + sum_j beta_ij dt k_j -> k_i (Y1 = y1
+// after stage 7), then the error ratio into b.out[0] (on the device; the caller reads it back).
+static int dopri5_attempt(Run& r, const OdeBufs& b, const Dopri5Ctl& ctl, int nv, long view_rows, double atol, double rtol) {
+#pragma clang fp contract(off)
+    float ts[ode::kStages];
+    ctl.stage_times(ts);
+    if (int e = ode_prepare(r, ts, ode::kStages, view_rows)) return e;
+    const float dtf = ctl.dt32();
+    for (int i = 1; i <= ode::kStages; ++i) {
+        if (int e = ode_combine(r, b.y1, b.y0, b.k, ode::kBeta[i - 1], i, dtf)) return e;
+        if (int e = ode_eval(r, nv, i - 1, b.y1, b.k[i])) return e;
+    }
+    OdeNorm p{};
+    p.a = b.y0;
+    p.b = b.y1;
+    for (int j = 0; j < 7; ++j) {
+        p.k[j] = b.k[j];
+        p.e[j] = (float)ode::kErr[j] * dtf;
+    }
+    p.atol = atol;
+    p.rtol = rtol;
+    p.mode = 2;
+    return ode_norm(r, b, p);
+}
+
+static OdeBufs ode_bufs(unsigned char* ws, size_t net_bytes, size_t state_bytes, float* x) {
+    OdeBufs b;
+    unsigned char* p = ws + align256(net_bytes);
+    b.y0 = x;
+    b.y1 = (float*)p;
+    p += state_bytes;
+    for (int j = 0; j < 7; ++j, p += state_bytes) b.k[j] = (float*)p;
+    b.ym = (float*)p;
+    p += state_bytes;
+    b.part = (double*)p;
+    b.out = (double*)(p + align256((size_t)kOdeMaxParts * 2 * 8));
+    return b;
+}
+
+static int ode_read(mdgen_ctx* c, const OdeBufs& b, hipStream_t s, double* v0, double* v1) {
+    HIPCHK(hipMemcpyAsync(c->ode_host, b.out, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *v0 = c->ode_host[0];
+    if (v1) *v1 = c->ode_host[1];
+    return 0;
+}
+
+extern "C" int32_t mdgen_sample_dopri5(mdgen_ctx* c, const mdgen_shape* sh, double atol, double rtol, int32_t max_steps, float* x,
+                                       const float* mask, const float* start_rot, const float* start_trans, const float* end_rot,
+                                       const float* end_trans, const float* rel7, const float* x_cond, const int64_t* x_cond_mask,
+                                       const int64_t* aatype, void* ws, size_t ws_bytes, int32_t* stats_host, double* steps_host,
+                                       void* stream) {
+    if (!x || !mask || !start_rot || !start_trans || !x_cond || !x_cond_mask || !aatype || !stats_host)
+        return fail(-1, "null argument");
+    stats_host[0] = stats_host[1] = stats_host[2] = 0;
+    if (!(atol >= 0) || !(rtol >= 0) || !(atol + rtol > 0) || !std::isfinite(atol) || !std::isfinite(rtol))
+        return fail(-2, "atol, rtol must be finite, >= 0, not both 0");
+    if (max_steps < 1) return fail(-2, "max_steps must be >= 1");
+    const hipStream_t s = (hipStream_t)stream;
+    {   // the controller reads the error ratio back after every attempted step: not capturable
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        const hipError_t e = hipStreamIsCapturing(s, &cs);
+        if (e != hipSuccess) return fail((int)e, "hipStreamIsCapturing failed: %s", hipGetErrorString(e));
+        if (cs != hipStreamCaptureStatusNone) return fail(-8, "mdgen_sample_dopri5 synchronises its stream: it cannot be captured");
+    }
+    if (((uintptr_t)x & 15) != 0) return fail(-7, "x must be 16-byte aligned");
+    size_t need = 0;
+    if (int e = mdgen_dopri5_workspace_bytes(c, sh, &need)) return e;
+    if (ws_bytes < need) return fail(-7, "workspace too small: %zu < %zu bytes (mdgen_dopri5_workspace_bytes)", ws_bytes, need);
+    mdgen_ws_layout lay;
+    if (int e = mdgen_workspace_layout(c, sh, ode::kStages, 1, &lay)) return e;
+    Run r{};
+    if (int e = make_run(&r, c, sh, ode::kStages, 1, ws, lay.total_bytes, stream)) return e;
+    r.mask = mask;
+    r.start_rot = start_rot;
+    r.start_trans = start_trans;
+    r.end_rot = end_rot;
+    r.end_trans = end_trans;
+    r.rel7_in = rel7;
+    r.x_cond = x_cond;
+    r.x_cond_mask = x_cond_mask;
+    r.aatype = aatype;
+    r.no_embed_tail = true;
+    if (!c->ode_host) HIPCHK(hipHostMalloc((void**)&c->ode_host, 2 * sizeof(double), hipHostMallocDefault));
+    const int nv = c->opt_precision == 32 ? 1 : plan_views(r.B, r.T, r.L, 1);
+    if (nv == 0) return fail(-2, "sample too large for one launch");
+    const long view_rows = (long)((r.B + nv - 1) / nv) * r.T * r.L;
+    OdeBufs b = ode_bufs((unsigned char*)ws, lay.total_bytes, ode_state_bytes(c, sh), x);
+    Dopri5Ctl ctl;
+    int nfe = 0;
+    // ---- initial step (misc.py _select_initial_step, order 4): k1 = f(0, x0), probe f(h0, x0 + h0 k1)
+    {
+        const float t0f = 0.f;
+        if (int e = ode_prepare(r, &t0f, 1, view_rows)) return e;
+        if (int e = ode_eval(r, nv, 0, b.y0, b.k[0])) return e;
+        ++nfe;
+        OdeNorm p{};
+        p.a = b.y0;
+        p.b = b.k[0];
+        p.atol = atol;
+        p.rtol = rtol;
+        p.mode = 0;
+        if (int e = ode_norm(r, b, p)) return e;
+        double d0 = 0, d1 = 0;
+        if (int e = ode_read(c, b, s, &d0, &d1)) return e;
+        ctl.probe(d0, d1);
+        const double one = 1.0;
+        float* k0 = b.k[0];
+        if (int e = ode_combine(r, b.y1, b.y0, &k0, &one, 1, ctl.probe_coef())) return e;
+        const float th = ctl.probe_time();
+        if (int e = ode_prepare(r, &th, 1, view_rows)) return e;
+        if (int e = ode_eval(r, nv, 0, b.y1, b.k[1])) return e;
+        ++nfe;
+        p.k[0] = b.k[1];
+        p.mode = 1;
+        if (int e = ode_norm(r, b, p)) return e;
+        double d2n = 0;
+        if (int e = ode_read(c, b, s, &d2n, nullptr)) return e;
+        if (!std::isfinite(d0) || !std::isfinite(d1) || !std::isfinite(d2n))
+            return fail(-9, "non-finite initial-step norm (d0 %g, d1 %g, d2 %g)", d0, d1, d2n);
+        ctl.first_step(d1, d2n);
+        stats_host[0] = nfe;
+    }
+    // ---- attempted steps until an accepted one ends at t1 >= 1
+    for (int attempt = 0; !ctl.done; ++attempt) {
+        if (attempt >= max_steps) return fail(-10, "dopri5: max_steps = %d attempted steps exceeded at t = %.9g", max_steps, ctl.t0);
+        if (ctl.underflow()) return fail(-11, "dopri5: underflow in dt %g at t = %.17g", ctl.dt, ctl.t0);
+        if (int e = dopri5_attempt(r, b, ctl, nv, view_rows, atol, rtol)) return e;
+        nfe += ode::kStages;
+        stats_host[0] = nfe;
+        double ratio = 0;
+        if (int e = ode_read(c, b, s, &ratio, nullptr)) return e;
+        if (!std::isfinite(ratio)) return fail(-9, "dopri5: non-finite error ratio at t = %.9g, dt = %g", ctl.t0, ctl.dt);
+        const double t_start = ctl.t0, dt_used = ctl.dt;
+        const bool acc = ctl.step(ratio);
+        stats_host[1] = ctl.accepted;
+        stats_host[2] = ctl.rejected;
+        if (!acc) continue;
+        if (steps_host) {
+            steps_host[2 * (ctl.accepted - 1)] = t_start;
+            steps_host[2 * (ctl.accepted - 1) + 1] = dt_used;
+        }
+        if (ctl.done) {   // dense output of this step at t = 1 into the caller's x (which is b.y0 or b.y1)
+            const float dtf = (float)ctl.last_dt;
+            if (int e = ode_combine(r, b.ym, b.y0, b.k, ode::kMid, 7, dtf)) return e;
+            { ProfScope ps(c, "ode_dense", s); launch_ode_dense(x, b.y0, b.y1, b.k[0], b.k[6], b.ym, dtf, ctl.dense_s(), (long)r.N * r.D, s); }
+            LAUNCHCHK();
+            break;
+        }
+        std::swap(b.y0, b.y1);   // FSAL: y1 -> y0, k7 -> k1
+        std::swap(b.k[0], b.k[6]);
+    }
+    return 0;
+}
+
+// Host-only test hook: the library's controller replayed on given norms.  init = {d0, d1, rms((f1 - k1) / scale)}; ratios[i] is
+// the error ratio of attempted step i.  Per attempt i < *n_attempts: t0[i], dt[i] (fp64), the six stage times as fp32 bits
+// stage_bits[6 i ..], accept[i].  probe[0..1]: the probe's x0 + h0 k1 coefficient and model time (fp32); *dense_s: s of the dense
+// output (when the replay finished).  Returns 0 when an accepted step reached t = 1 within the ratios, 1 when the ratios ran out
+// first, or the sampler's error codes (-9 non-finite ratio, -10 more than max_steps attempts, -11 dt underflow).
+extern "C" int32_t mdgen_debug_dopri5_controller(const double* init, const double* ratios, int32_t n_ratios, int32_t max_steps,
+                                                 float* probe, double* t0, double* dt, uint32_t* stage_bits, int32_t* accept,
+                                                 float* dense_s, int32_t* n_attempts) {
+    if (!init || (!ratios && n_ratios > 0) || !probe || !t0 || !dt || !stage_bits || !accept || !dense_s || !n_attempts)
+        return fail(-1, "null argument");
+    Dopri5Ctl ctl;
+    ctl.probe(init[0], init[1]);
+    probe[0] = ctl.probe_coef();
+    probe[1] = ctl.probe_time();
+    ctl.first_step(init[1], init[2]);
+    *n_attempts = 0;
+    for (int i = 0; !ctl.done; ++i) {
+        if (i >= max_steps) return fail(-10, "max_steps exceeded");
+        if (ctl.underflow()) return fail(-11, "underflow in dt");
+        if (i >= n_ratios) return 1;
+        t0[i] = ctl.t0;
+        dt[i] = ctl.dt;
+        float ts[ode::kStages];
+        ctl.stage_times(ts);
+        std::memcpy(stage_bits + (size_t)ode::kStages * i, ts, sizeof(ts));
+        if (!std::isfinite(ratios[i])) return fail(-9, "non-finite error ratio");
+        accept[i] = ctl.step(ratios[i]) ? 1 : 0;
+        *n_attempts = i + 1;
+    }
+    *dense_s = ctl.dense_s();
+    return 0;
+}
+
+// mdgen_debug_dispatch_plan mode 4: one attempted step of mdgen_sample_dopri5 in plan mode (g_dry records the classes).
+// Output: {"streams": 1, "prepare": {...} (the stage rows' preparation), "views": [{"B", "classes": the six evaluations of that
+// view}], "integrator": {"ode_combine": 6, "ode_norm": 1}}
+static int dopri5_plan(mdgen_ctx* c, const mdgen_shape* sh, std::vector<std::string>& plan, char* buf, size_t buflen) {
+    Run r{};
+    if (int e = make_run(&r, c, sh, ode::kStages, 1, (void*)4096, (size_t)1 << 60, nullptr)) return e;
+    float* fake = (float*)4096;   // never dereferenced: plan mode launches nothing
+    r.mask = r.start_rot = r.start_trans = r.end_rot = r.end_trans = r.x_cond = fake;
+    r.x_cond_mask = r.aatype = (const int64_t*)fake;
+    r.no_embed_tail = true;
+    const int nv = plan_views(r.B, r.T, r.L, 1);
+    if (nv == 0) return fail(-2, "sample too large for one launch");
+    OdeBufs b;
+    b.y0 = b.y1 = b.ym = fake;
+    for (int j = 0; j < 7; ++j) b.k[j] = fake;
+    b.part = b.out = (double*)fake;
+    Dopri5Ctl ctl;
+    ctl.dt = 0.01;
+    if (int e = dopri5_attempt(r, b, ctl, nv, (long)((r.B + nv - 1) / nv) * r.T * r.L, 1e-6, 1e-3)) return e;
+    std::map<std::string, long> prep, integ;
+    std::vector<std::map<std::string, long>> views(nv);
+    int cur = -1;
+    for (const auto& k : plan) {
+        if (k.rfind("@view", 0) == 0) cur = std::atoi(k.c_str() + 5);
+        else if (k.rfind("ode_", 0) == 0) ++integ[k];
+        else if (cur < 0) ++prep[k];
+        else ++views[cur][k];
+    }
+    auto dump = [](const std::map<std::string, long>& agg) {
+        std::string o = "{";
+        bool first = true;
+        for (const auto& kv : agg) {
+            o += std::string(first ? "" : ", ") + "\"" + kv.first + "\": " + std::to_string(kv.second);
+            first = false;
+        }
+        return o + "}";
+    };
+    std::string js = "{\"streams\": 1, \"prepare\": " + dump(prep) + ", \"views\": [";
+    for (int i = 0; i < nv; ++i)
+        js += std::string(i ? ", " : "") + "{\"B\": " + std::to_string(r.B / nv + (i < r.B % nv ? 1 : 0)) + ", \"classes\": " + dump(views[i]) + "}";
+    js += "], \"integrator\": " + dump(integ) + "}";
+    if (js.size() + 1 > buflen) return fail(-7, "plan buffer too small");
+    std::memcpy(buf, js.c_str(), js.size() + 1);
+    return 0;
+}

@@ -306,6 +306,53 @@ class LatentMDGenModel:
                 cur.wait_stream(self._side)
         return stg["x"].clone()
 
+    # ---- adaptive dopri5 ----------------------------------------------------------------------
+    def sample_dopri5(self, zs, mask=None, start_frames=None, end_frames=None, x_cond=None, x_cond_mask=None, aatype=None,
+                      atol: float = 1e-6, rtol: float = 1e-3, rel_quats=None, max_steps: int = 10000):
+        """The reference's default solver (`mdgen_sample_dopri5`): torchdiffeq 0.2.x odeint(model, zs, linspace(0, 1, 50),
+        method='dopri5', atol=[atol], rtol=[rtol])[-1] (transport.py:408-451, integrators.py:74-113).  One step size for the
+        whole batch (the error norm spans every element).  Returns (x at t = 1, stats) with stats = {"nfe", "accepted",
+        "rejected", "steps": [(t0, dt) of every accepted step]}.  Synchronises the current stream once per attempted step."""
+        if self._pre_run is not None:
+            self._pre_run()
+        B, T, L_ = self._check_inputs(zs, mask, x_cond, x_cond_mask, aatype)
+        require_cuda(zs, mask, x_cond, x_cond_mask, aatype)
+        sr, st = _frames(start_frames)
+        er, et = _frames(end_frames)
+        if sr is None:
+            raise L.MdgenError("start_frames is required")
+        sh = L.Shape(B, T, L_)
+        nbytes = C.c_size_t()
+        check(lib.mdgen_dopri5_workspace_bytes(self._ctx, C.byref(sh), C.byref(nbytes)))
+        key = ("dopri5", B, T, L_)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < nbytes.value:
+            while len(self._ws) >= self.max_cached_shapes:
+                self._ws.popitem(last=False)
+            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+            if self.poison_workspace:
+                ws.fill_(255)
+            self._ws[key] = ws
+        else:
+            self._ws.move_to_end(key)
+        x = zs.to(torch.float32).contiguous().clone()
+        mask = mask.to(torch.float32).contiguous()
+        x_cond = x_cond.to(torch.float32).contiguous()
+        x_cond_mask = x_cond_mask.to(torch.int64).contiguous()
+        aatype = aatype.to(torch.int64).contiguous()
+        rel7 = self._rel7(rel_quats, B, L_)
+        stats = (C.c_int32 * 3)()
+        steps = (C.c_double * (2 * int(max_steps)))()
+        with torch.cuda.device(self.device):
+            check(lib.mdgen_sample_dopri5(
+                self._ctx, C.byref(sh), float(atol), float(rtol), int(max_steps), ptr(x), ptr(mask), ptr(sr), ptr(st),
+                ptr(er), ptr(et), ptr(rel7), ptr(x_cond), ptr(x_cond_mask), ptr(aatype), ptr(ws), ws.numel(), stats, steps,
+                L.stream_ptr()))
+        acc = stats[1]
+        info = {"nfe": stats[0], "accepted": acc, "rejected": stats[2],
+                "steps": [(steps[2 * i], steps[2 * i + 1]) for i in range(acc)]}
+        return x, info
+
     # ---- multi-block rollout -----------------------------------------------------------------
     def rollout_euler(self, zs, num_steps: int, mask, cond_rots, cond_trans, cond_torsions, seqres, tables,
                       use_graph: bool = True):

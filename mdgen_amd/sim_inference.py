@@ -1,8 +1,11 @@
 """Forward-simulation driver, command-line compatible with the reference's `sim_inference.py:1-14`
 (`--sim_ckpt --data_dir --suffix --pdb_id --num_frames --num_rollouts --out_dir --split`), plus
 
-  --num_steps S      Euler steps per block (the reference samples with its checkpoint's `sampling_method`; this
-                     build has fixed-grid Euler only and refuses a non-Euler checkpoint unless S is given);
+  --num_steps S      Euler steps per block (the reference samples with its checkpoint's `sampling_method`; a non-Euler
+                     checkpoint is refused unless S or --sampling_method is given);
+  --sampling_method {euler,dopri5}   the solver: dopri5 is the reference's adaptive default (torchdiffeq, atol 1e-6,
+                     rtol 1e-3), run per block through `inference()` (one step size per call, shared by a --batch
+                     group); euler without --num_steps takes the reference's 49-step grid.  No flag: as before;
   --batch N          peptides of equal length sampled together in one `inference()` call (the reference runs
                      B = 1, sim_inference.py:101-102; B = 16 is the regime BASELINE.json's metric is quoted on);
   --chunk_idx/--n_chunks   the reference's own sharding switches (tps_inference.py:17-18,160-161): this process
@@ -78,14 +81,20 @@ def collate(batches):
     return {k: torch.cat([b[k] for b in batches], 0) for k in batches[0]}
 
 
-def rollout(model, batch, num_frames, num_steps, zs=None):
+def rollout(model, batch, num_frames, num_steps, zs=None, sampling_method=None):
     """sim_inference.rollout (:61-98) with the glue on the device."""
     from .geometry import atom14_to_cond
     ex = dict(batch)
     ex["torsions"] = batch["torsions"].expand(-1, num_frames, -1, -1, -1)
     ex["trans"] = batch["trans"].expand(-1, num_frames, -1, -1)
     ex["rots"] = batch["rots"].expand(-1, num_frames, -1, -1, -1)
-    atom14, _ = model.inference(ex, zs=zs, num_steps=num_steps)
+    if sampling_method is None:
+        atom14, _ = model.inference(ex, zs=zs, num_steps=num_steps)
+    else:
+        atom14, _ = model.inference(ex, zs=zs, num_steps=num_steps, sampling_method=sampling_method)
+        if sampling_method == "dopri5":
+            st = model.last_stats
+            print(f"dopri5: {st['nfe']} network evaluations ({st['accepted']} accepted, {st['rejected']} rejected steps)")
     c = atom14_to_cond(atom14[:, -1], batch["seqres"])
     new = dict(batch)
     new["trans"], new["rots"], new["torsions"] = c["trans"][:, None], c["rots"][:, None], c["torsions"][:, None]
@@ -99,11 +108,13 @@ def make_group_batch(names, arrs, seqres, device):
 
 def sample_group(model, batch, args):
     """`num_rollouts` chained blocks for one batch; returns atom14 [B, R*T, L, 14, 3]."""
-    if hasattr(model, "rollout") and not getattr(args, "per_block", False):
-        return model.rollout(batch, args.num_frames, args.num_rollouts, num_steps=args.num_steps)
+    method = getattr(args, "sampling_method", None)
+    num_steps = 49 if method == "euler" and args.num_steps is None else args.num_steps
+    if hasattr(model, "rollout") and not getattr(args, "per_block", False) and method != "dopri5":
+        return model.rollout(batch, args.num_frames, args.num_rollouts, num_steps=num_steps)
     out = []
-    for _ in range(args.num_rollouts):
-        atom14, batch = rollout(model, batch, args.num_frames, args.num_steps)
+    for _ in range(args.num_rollouts):   # (dopri5: one inference() call per block; the device rollout is Euler only)
+        atom14, batch = rollout(model, batch, args.num_frames, num_steps, sampling_method=method)
         out.append(atom14)
     return torch.cat(out, 1)
 
@@ -194,6 +205,8 @@ def build_parser():
     p.add_argument("--split", type=str, default="splits/4AA_test.csv")
     p.add_argument("--num_steps", type=int, default=None,
                    help="Euler steps per block (default: 49 = the reference's 50-point grid, Euler checkpoints only)")
+    p.add_argument("--sampling_method", choices=["euler", "dopri5"], default=None,
+                   help="solver (default: the checkpoint's, refused unless it is euler or --num_steps is given)")
     p.add_argument("--batch", type=int, default=1, help="peptides of equal length per inference() call")
     p.add_argument("--chunk_idx", type=int, default=0)
     p.add_argument("--n_chunks", type=int, default=1)
@@ -208,6 +221,8 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.sampling_method == "dopri5" and args.num_steps is not None:
+        raise SystemExit("--num_steps sets the Euler grid; dopri5 chooses its own steps (pass one or the other)")
     if args.no_frames or args.tps:
         raise SystemExit("--no_frames / --tps are outside this build's scope (see DESIGN.md)")
     import pandas as pd

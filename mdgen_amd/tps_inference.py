@@ -65,6 +65,9 @@ def build_parser():
     p.add_argument("--start_frame", type=int, default=0, help="MD frame of {name}.npy used as the start state")
     p.add_argument("--end_frame", type=int, default=-1, help="MD frame of {name}.npy used as the end state")
     p.add_argument("--num_steps", type=int, default=None)
+    p.add_argument("--sampling_method", choices=["euler", "dopri5"], default=None,
+                   help="solver (default: the checkpoint's, refused unless it is euler or --num_steps is given); dopri5: "
+                        "the reference's adaptive solver, one step size per call shared by the --batch_size paths")
     p.add_argument("--synthetic", action="store_true")
     return p
 
@@ -86,7 +89,15 @@ def run(args, model, device, names_seqres, rank=0, world=1):
         batch = collate([one] * args.batch_size)
         aat = np.array([restype_order[c] for c in seq])
         for i in range(args.num_batches):
-            atom14s, _ = model.inference(batch, num_steps=args.num_steps)
+            method = getattr(args, "sampling_method", None)
+            if method is None:
+                atom14s, _ = model.inference(batch, num_steps=args.num_steps)
+            else:
+                atom14s, _ = model.inference(batch, num_steps=args.num_steps, sampling_method=method)
+                if method == "dopri5":
+                    st = model.last_stats
+                    print(f"{name} batch {i}: dopri5 {st['nfe']} network evaluations ({st['accepted']} accepted, "
+                          f"{st['rejected']} rejected steps)")
             host = atom14s.cpu().numpy()
             for j in range(args.batch_size):
                 idx = i * args.batch_size + j
@@ -102,6 +113,8 @@ def main(argv=None):
     from .synthetic import synth_state_dict
     from .wrapper import NewMDGenWrapper
     args = build_parser().parse_args(argv)
+    if args.sampling_method == "dopri5" and args.num_steps is not None:
+        raise SystemExit("--num_steps sets the Euler grid; dopri5 chooses its own steps (pass one or the other)")
     rank, world, local_rank = dist_env()
     device = torch.device("cuda", local_rank)
     torch.cuda.set_device(device)

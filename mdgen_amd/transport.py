@@ -84,8 +84,8 @@ class Sampler:
         state, shape [1, *x0.shape], so that the caller's `[-1]` (wrapper.py:447) is unchanged."""
         if sampling_method != "euler":
             raise NotImplementedError(
-                "mdgen_amd implements the fixed-grid Euler sampler (pass sampling_method='euler'); "
-                "adaptive dopri5 is not on the graph-captured path")
+                "Sampler.sample_ode implements the fixed-grid Euler sampler (pass sampling_method='euler'); adaptive "
+                "dopri5 is NewMDGenWrapper.inference(..., sampling_method='dopri5') / LatentMDGenModel.sample_dopri5")
         if reverse:
             raise NotImplementedError("reverse-time sampling is not used by the wrapper")
         S = int(num_steps) - 1

@@ -159,33 +159,44 @@ class NewMDGenWrapper:
                                              mask=prep["loss_mask"], model_kwargs=prep["model_kwargs"], t=t, x0=x0)
         return out["loss"], out
 
-    def inference(self, batch, zs=None, num_steps=None, use_graph=True, rel_quats=None):
+    def inference(self, batch, zs=None, num_steps=None, use_graph=True, rel_quats=None, sampling_method=None, atol=1e-6,
+                  rtol=1e-3):
         """wrapper.py:405-484.  Extra keywords (defaults reproduce the reference): `zs` explicit noise
         (reference: device randn, wrapper.py:439), `num_steps` Euler steps S (reference: 50 grid points = 49
         steps, wrapper.py:441-442 / transport.py:412), `rel_quats` (two-sided models): the relative-frame 7-vectors
-        (2,B,L,7) as the caller's reference computes them (`LatentMDGenModel._rel7`; default: w >= 0 convention)."""
+        (2,B,L,7) as the caller's reference computes them (`LatentMDGenModel._rel7`; default: w >= 0 convention).
+        `sampling_method="dopri5"`: the reference's adaptive solver (torchdiffeq dopri5 with `atol` / `rtol`,
+        `LatentMDGenModel.sample_dopri5`; one step size for the whole batch); its counts are kept in `last_stats`."""
         prep = self.prep_batch(batch)
         rigids = prep["rigids"]
         B, T, L_ = rigids.shape
         dev = prep["latents"].device
         if zs is None:
             zs = torch.randn(B, T, L_, self.latent_dim, device=dev)
+        if sampling_method not in (None, "euler", "dopri5"):
+            raise L.MdgenError(f"sampling_method must be None, 'euler' or 'dopri5', got {sampling_method!r}")
+        if sampling_method == "dopri5" and num_steps is not None:
+            raise L.MdgenError("num_steps sets the fixed Euler grid; dopri5 chooses its own steps (pass one or the other)")
         # wrapper.py:441 samples with args.sampling_method (argparse default 'dopri5', parsing.py:102) on the
-        # solver's own 50-point grid.  Only fixed-grid Euler exists here: without an explicit `num_steps` a
-        # non-Euler checkpoint is rejected instead of being silently sampled with a different solver.
+        # solver's own 50-point grid.  Without an explicit choice (sampling_method / num_steps) a non-Euler checkpoint is
+        # rejected instead of being silently sampled with a different solver.
         method = getattr(self.args, "sampling_method", "euler")
-        if num_steps is None and method != "euler":
-            raise L.MdgenError(f"checkpoint args say sampling_method={method!r}; this build implements fixed-grid "
-                               "Euler only -- pass num_steps=... (CLI: --num_steps) to sample with Euler explicitly")
-        S = 49 if num_steps is None else int(num_steps)
+        if sampling_method is None and num_steps is None and method != "euler":
+            raise L.MdgenError(f"checkpoint args say sampling_method={method!r}; pass sampling_method='dopri5' (CLI: "
+                               "--sampling_method dopri5) for the reference's solver, or num_steps=... (CLI: --num_steps) "
+                               "to sample with fixed-grid Euler")
         kw = dict(prep["model_kwargs"])
         kw["mask"] = kw["mask"].contiguous()
         if not self.args.tps_condition:
             kw["end_frames"] = None
         if rel_quats is not None:
             kw["rel_quats"] = rel_quats
-        sample_fn = self.transport_sampler.sample_ode(sampling_method="euler", num_steps=S + 1)
-        samples = sample_fn(zs, partial(self.model.forward_inference, **kw), use_graph=use_graph)[-1]
+        if sampling_method == "dopri5":
+            samples, self.last_stats = self.model.sample_dopri5(zs, atol=atol, rtol=rtol, **kw)
+        else:
+            S = 49 if num_steps is None else int(num_steps)
+            sample_fn = self.transport_sampler.sample_ode(sampling_method="euler", num_steps=S + 1)
+            samples = sample_fn(zs, partial(self.model.forward_inference, **kw), use_graph=use_graph)[-1]
         r0 = rigids[:, 0]
         atom14 = samples_to_atom14(samples, r0.get_rots().get_rot_mats(), r0.get_trans(), batch["seqres"],
                                    bool(self.args.tps_condition))
