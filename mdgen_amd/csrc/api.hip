@@ -3,6 +3,7 @@
 #include "../../include/mdgen_amd.h"
 #include "kernels.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -64,20 +65,28 @@ constexpr int kMaxPos = 8160;        // positions covered by the rotary table / 
 constexpr int kKS = 24;              // k-steps at K = 384
 constexpr size_t kPackCC = (size_t)12 * kKS * 64;  // bf16x8 elements of a packed [384][384] matrix
 
+// A parameter is addressed by its SLOT: its index in mdgen_ctx::weights = registration order = the index of mdgen_ctx_weight_name,
+// of mdgen_train_bind_params' offsets and of mdgen_train_forward_backward's grad_offsets.  The structs below keep, next to the
+// packed bf16 operands of the sampler, the slots of their parameters (`slot`): the fp32 path and the training step read
+// mdgen_ctx::f32(slot) at the moment of use.  -1: the model has no such parameter.
+struct Lin { int w = -1, b = -1; };   // a linear layer: the slots of its weight and its bias
 struct MhaW {
     bf16x8 *wq = nullptr, *wk = nullptr, *wv_flash = nullptr, *wv_small = nullptr, *wo = nullptr;
     float *bq = nullptr, *bk = nullptr, *bv_flash = nullptr, *bv_small = nullptr, *bo = nullptr;
     float *bias_k = nullptr, *bias_v = nullptr;
+    struct { Lin q, k, v, o; int bias_k = -1, bias_v = -1; } slot;
 };
 struct FfnW {
     bf16x8 *w1 = nullptr, *w2 = nullptr;
     float *b1 = nullptr, *b2 = nullptr;
     bf16x8* wstream = nullptr;   // both matrices as ONE fragment stream in the consumption order of k_mlp_rows (mlp_stream_table)
     float* w2f = nullptr;        // trunk layers: fp32 fc2.weight [384][1536], the source of the per-step gate-folded streams (option mlp_fold)
+    struct { Lin fc1, fc2; } slot;
 };
 struct TrunkW {
     MhaW mha_l, mha_t;
     FfnW ffn;
+    Lin ada;                     // slots of the block's adaLN head
 };
 struct IpaW {
     float* gamma_beta = nullptr;  // [gamma(C) | beta(C)]
@@ -88,6 +97,7 @@ struct IpaW {
     float* bout = nullptr;
     MhaW mha_l;
     FfnW ffn;
+    struct { Lin ada, norm, q, kv, q_points, kv_points, out; int head_w = -1; } slot;
 };
 
 struct ProfRec {
@@ -101,13 +111,21 @@ struct GraphEntry {
     hipGraphExec_t exec = nullptr;
 };
 
+struct WeightSlot {
+    std::string name;            // the reference's state_dict key
+    std::function<int(const float*, const int64_t*, int, hipStream_t)> set;   // packs / copies the tensor into the sampler's operands
+    bool provided = false;
+    float* f32 = nullptr;        // fp32 copy, natural layout (option keep_fp32_weights) ...
+    bool bound = false;          // ... or a pointer into the caller's flat parameter buffer (mdgen_train_bind_params)
+};
+
 struct mdgen_ctx {
     mdgen_model_desc d;
     int nl = 0, D = 0, modrow = 0;
     std::vector<void*> allocs;
-    std::vector<std::string> names;
-    std::map<std::string, std::function<int(const float*, const int64_t*, int, hipStream_t)>> setters;
-    std::map<std::string, bool> provided;
+    std::vector<WeightSlot> weights;
+    std::map<std::string, int> slot_of;   // name -> slot, for the entry point that receives a name (mdgen_ctx_set_weight)
+    struct { Lin latent, cond, t0, t2, rel_f, rel_r, fin, fin_ada; int mask = -1, aatype = -1; } slot;   // parameters outside the layers
     bool finalized = false;
     // fp32 small weights
     float *wl = nullptr, *bl = nullptr, *wc = nullptr, *bc = nullptr, *mask_emb = nullptr, *aa_emb = nullptr;
@@ -134,8 +152,6 @@ struct mdgen_ctx {
     // run-time options (mdgen_ctx_set_option)
     int opt_precision = 16;     // GEMM / attention operand precision: 16 = bf16 MFMA path, 32 = fp32 path (k_fp32.hip)
     int opt_keep_fp32 = 0;      // keep an fp32 copy of every weight handed over (required by precision 32)
-    std::map<std::string, float*> w32;   // fp32 copies, natural layout, keyed by the reference's state_dict key
-    std::map<std::string, bool> w32_bound;   // keys whose w32 entry points into the caller's flat parameter buffer (mdgen_train_bind_params)
     int opt_streams = 2;        // concurrent sub-batch streams of the Euler rollout (1 = caller's stream only)
     bool opt_streams_auto = true;   // not set by the caller: the count also follows the fill of the chip (n_streams)
     int opt_attn_path = 0;      // tiled attention: 0 fixed-anchor fast loop with overflow check + fallback, 1 robust loop always
@@ -188,6 +204,10 @@ struct mdgen_ctx {
 
     std::set<std::string> cls_names;   // storage of composed profile class names (ProfRec keeps a const char*)
     const char* intern(const std::string& n) { return cls_names.insert(n).first->c_str(); }
+    const float* f32(int slot) const { return weights[slot].f32; }
+    bool any_f32() const {
+        return std::any_of(weights.begin(), weights.end(), [](const WeightSlot& w) { return w.f32 != nullptr; });
+    }
     template <typename T>
     int dalloc(T** p, size_t count) {
         void* q = nullptr;
@@ -331,10 +351,15 @@ static bool shape_is(const int64_t* s, int nd, std::initializer_list<int64_t> wa
     return a == b;
 }
 
-#define SETTER(key, body)                                                                        \
-    c->names.push_back(key);                                                                     \
-    c->setters[key] = [=](const float* data, const int64_t* shp, int nd, hipStream_t s) -> int { \
-        (void)shp; (void)nd; body; return 0; }
+// registers a parameter; the value of the expression is its slot
+static int add_weight(mdgen_ctx* c, const std::string& key, std::function<int(const float*, const int64_t*, int, hipStream_t)> set) {
+    c->slot_of[key] = (int)c->weights.size();
+    c->weights.push_back(WeightSlot{key, std::move(set)});
+    return (int)c->weights.size() - 1;
+}
+#define SETTER(key, body)                                                                          \
+    add_weight(c, key, [=](const float* data, const int64_t* shp, int nd, hipStream_t s) -> int {  \
+        (void)shp; (void)nd; body; return 0; })
 #define WANT(...) \
     if (!shape_is(shp, nd, {__VA_ARGS__})) return fail(-3, "unexpected shape for weight")
 
@@ -352,33 +377,33 @@ static int register_mha(mdgen_ctx* c, const std::string& pre, MhaW* m) {
     if (int r = c->dalloc(&m->wo, kPackCC)) return r;
     for (float** p : {&m->bq, &m->bk, &m->bv_flash, &m->bv_small, &m->bo, &m->bias_k, &m->bias_v})
         if (int r = c->dalloc(p, (size_t)kC)) return r;
-    SETTER(pre + "q_proj.weight", {
+    m->slot.q.w = SETTER(pre + "q_proj.weight", {
         WANT(kC, kC);
         launch_pack_rows(data, kC, c->map_qk, 12, kKS, qscale, m->wq, s);
     });
-    SETTER(pre + "q_proj.bias", { WANT(kC); launch_gather_f32(data, c->perm_qk, qscale, m->bq, kC, s); });
-    SETTER(pre + "k_proj.weight", {
+    m->slot.q.b = SETTER(pre + "q_proj.bias", { WANT(kC); launch_gather_f32(data, c->perm_qk, qscale, m->bq, kC, s); });
+    m->slot.k.w = SETTER(pre + "k_proj.weight", {
         WANT(kC, kC);
         launch_pack_rows(data, kC, c->map_qk, 12, kKS, 1.f, m->wk, s);
     });
-    SETTER(pre + "k_proj.bias", { WANT(kC); launch_gather_f32(data, c->perm_qk, 1.f, m->bk, kC, s); });
-    SETTER(pre + "v_proj.weight", {
+    m->slot.k.b = SETTER(pre + "k_proj.bias", { WANT(kC); launch_gather_f32(data, c->perm_qk, 1.f, m->bk, kC, s); });
+    m->slot.v.w = SETTER(pre + "v_proj.weight", {
         WANT(kC, kC);
         launch_pack_rows(data, kC, c->map_vflash, 12, kKS, 1.f, m->wv_flash, s);
         launch_pack_rows(data, kC, c->map_vsmall, 12, kKS, 1.f, m->wv_small, s);
     });
-    SETTER(pre + "v_proj.bias", {
+    m->slot.v.b = SETTER(pre + "v_proj.bias", {
         WANT(kC);
         launch_gather_f32(data, c->map_vflash, 1.f, m->bv_flash, kC, s);
         launch_gather_f32(data, c->perm_vsmall, 1.f, m->bv_small, kC, s);
     });
-    SETTER(pre + "out_proj.weight", {
+    m->slot.o.w = SETTER(pre + "out_proj.weight", {
         WANT(kC, kC);
         launch_pack_rows(data, kC, c->map_nat, 12, kKS, 1.f, m->wo, s);
     });
-    SETTER(pre + "out_proj.bias", { WANT(kC); if (int r = copy_f32(m->bo, data, kC, s)) return r; });
-    SETTER(pre + "bias_k", { WANT(kC); if (int r = copy_f32(m->bias_k, data, kC, s)) return r; });
-    SETTER(pre + "bias_v", { WANT(kC); if (int r = copy_f32(m->bias_v, data, kC, s)) return r; });
+    m->slot.o.b = SETTER(pre + "out_proj.bias", { WANT(kC); if (int r = copy_f32(m->bo, data, kC, s)) return r; });
+    m->slot.bias_k = SETTER(pre + "bias_k", { WANT(kC); if (int r = copy_f32(m->bias_k, data, kC, s)) return r; });
+    m->slot.bias_v = SETTER(pre + "bias_v", { WANT(kC); if (int r = copy_f32(m->bias_v, data, kC, s)) return r; });
     SETTER(pre + "rot_emb.inv_freq", {
         WANT(12);
         if (int r = copy_f32(c->inv_freq, data, 12, s)) return r;
@@ -395,20 +420,20 @@ static int register_ffn(mdgen_ctx* c, const std::string& pre, FfnW* f, bool trun
     if (int r = c->dalloc(&f->b1, (size_t)kF)) return r;
     if (int r = c->dalloc(&f->b2, (size_t)kC)) return r;
     if (int r = c->dalloc(&f->wstream, (size_t)kMlpFrags * 64)) return r;
-    SETTER(pre + "fc1.weight", {
+    f->slot.fc1.w = SETTER(pre + "fc1.weight", {
         WANT(kF, kC);
         launch_pack_rows(data, kC, c->map_nat, 48, kKS, 1.f, f->w1, s);
         launch_pack_stream(data, kC, 0, c->mlp_tab, kMlpFrags, 1.f, 1, f->wstream, s);
     });
-    SETTER(pre + "fc1.bias", { WANT(kF); if (int r = copy_f32(f->b1, data, kF, s)) return r; });
-    SETTER(pre + "fc2.weight", {
+    f->slot.fc1.b = SETTER(pre + "fc1.bias", { WANT(kF); if (int r = copy_f32(f->b1, data, kF, s)) return r; });
+    f->slot.fc2.w = SETTER(pre + "fc2.weight", {
         WANT(kC, kF);
         launch_pack_rows(data, kF, c->map_nat, 12, 96, 1.f, f->w2, s);
         launch_pack_stream(data, kF, 1, c->mlp_tab, kMlpFrags, 1.f, 1, f->wstream, s);
         if (f->w2f)
             if (int r = copy_f32(f->w2f, data, (size_t)kC * kF, s)) return r;
     });
-    SETTER(pre + "fc2.bias", { WANT(kC); if (int r = copy_f32(f->b2, data, kC, s)) return r; });
+    f->slot.fc2.b = SETTER(pre + "fc2.bias", { WANT(kC); if (int r = copy_f32(f->b2, data, kC, s)) return r; });
     return 0;
 }
 
@@ -508,18 +533,18 @@ extern "C" int32_t mdgen_ctx_create(mdgen_ctx** out, const mdgen_model_desc* d) 
     TRY(c->dalloc(&c->bfin, (size_t)32));
     TRYHIP(hipMemset(c->bfin, 0, 32 * sizeof(float)));
 #undef TRYHIP
-    SETTER("latent_to_emb.weight", { WANT(kC, c->D); if (int r = copy_f32(c->wl, data, (size_t)kC * c->D, s)) return r; launch_pack_embed(c->wl, c->D, c->wl_pack, s);
+    c->slot.latent.w = SETTER("latent_to_emb.weight", { WANT(kC, c->D); if (int r = copy_f32(c->wl, data, (size_t)kC * c->D, s)) return r; launch_pack_embed(c->wl, c->D, c->wl_pack, s);
         launch_pack_rows(c->wl, c->D, c->map_nat, 12, 2, 1.f, c->wl_hi, s, 1, 0); launch_pack_rows(c->wl, c->D, c->map_nat, 12, 2, 1.f, c->wl_lo, s, 1, 1); });
-    SETTER("latent_to_emb.bias", { WANT(kC); if (int r = copy_f32(c->bl, data, kC, s)) return r; });
-    SETTER("cond_to_emb.weight", { WANT(kC, c->D); if (int r = copy_f32(c->wc, data, (size_t)kC * c->D, s)) return r; launch_pack_embed(c->wc, c->D, c->wc_pack, s);
+    c->slot.latent.b = SETTER("latent_to_emb.bias", { WANT(kC); if (int r = copy_f32(c->bl, data, kC, s)) return r; });
+    c->slot.cond.w = SETTER("cond_to_emb.weight", { WANT(kC, c->D); if (int r = copy_f32(c->wc, data, (size_t)kC * c->D, s)) return r; launch_pack_embed(c->wc, c->D, c->wc_pack, s);
         launch_pack_rows(c->wc, c->D, c->map_nat, 12, 2, 1.f, c->wc_hi, s, 1, 0); launch_pack_rows(c->wc, c->D, c->map_nat, 12, 2, 1.f, c->wc_lo, s, 1, 1); });
-    SETTER("cond_to_emb.bias", { WANT(kC); if (int r = copy_f32(c->bc, data, kC, s)) return r; });
-    SETTER("mask_to_emb.weight", { WANT(2, kC); if (int r = copy_f32(c->mask_emb, data, 2 * kC, s)) return r; launch_sub_f32(c->mask_emb + kC, c->mask_emb, c->mask_delta, kC, s); });
-    SETTER("aatype_to_emb.weight", { WANT(21, kC); if (int r = copy_f32(c->aa_emb, data, 21 * kC, s)) return r; });
-    SETTER("t_embedder.mlp.0.weight", { WANT(kC, 256); if (int r = copy_f32(c->t_w0, data, (size_t)kC * 256, s)) return r; });
-    SETTER("t_embedder.mlp.0.bias", { WANT(kC); if (int r = copy_f32(c->t_b0, data, kC, s)) return r; });
-    SETTER("t_embedder.mlp.2.weight", { WANT(kC, kC); if (int r = copy_f32(c->t_w2, data, (size_t)kC * kC, s)) return r; });
-    SETTER("t_embedder.mlp.2.bias", { WANT(kC); if (int r = copy_f32(c->t_b2, data, kC, s)) return r; });
+    c->slot.cond.b = SETTER("cond_to_emb.bias", { WANT(kC); if (int r = copy_f32(c->bc, data, kC, s)) return r; });
+    c->slot.mask = SETTER("mask_to_emb.weight", { WANT(2, kC); if (int r = copy_f32(c->mask_emb, data, 2 * kC, s)) return r; launch_sub_f32(c->mask_emb + kC, c->mask_emb, c->mask_delta, kC, s); });
+    c->slot.aatype = SETTER("aatype_to_emb.weight", { WANT(21, kC); if (int r = copy_f32(c->aa_emb, data, 21 * kC, s)) return r; });
+    c->slot.t0.w = SETTER("t_embedder.mlp.0.weight", { WANT(kC, 256); if (int r = copy_f32(c->t_w0, data, (size_t)kC * 256, s)) return r; });
+    c->slot.t0.b = SETTER("t_embedder.mlp.0.bias", { WANT(kC); if (int r = copy_f32(c->t_b0, data, kC, s)) return r; });
+    c->slot.t2.w = SETTER("t_embedder.mlp.2.weight", { WANT(kC, kC); if (int r = copy_f32(c->t_w2, data, (size_t)kC * kC, s)) return r; });
+    c->slot.t2.b = SETTER("t_embedder.mlp.2.bias", { WANT(kC); if (int r = copy_f32(c->t_b2, data, kC, s)) return r; });
     if (d->abs_pos_emb) {
         if (d->crop < 1) { mdgen_ctx_destroy(c); return fail(-2, "abs_pos_emb requires crop >= 1"); }
         TRY(c->dalloc(&c->pos_embed, (size_t)d->crop * kC));
@@ -530,30 +555,30 @@ extern "C" int32_t mdgen_ctx_create(mdgen_ctx** out, const mdgen_model_desc* d) 
         TRY(c->dalloc(&c->bf7, (size_t)kC));
         TRY(c->dalloc(&c->wr7, (size_t)kC * 7));
         TRY(c->dalloc(&c->br7, (size_t)kC));
-        SETTER("latent_to_emb_f.weight", { WANT(kC, 7); if (int r = copy_f32(c->wf7, data, kC * 7, s)) return r; });
-        SETTER("latent_to_emb_f.bias", { WANT(kC); if (int r = copy_f32(c->bf7, data, kC, s)) return r; });
-        SETTER("latent_to_emb_r.weight", { WANT(kC, 7); if (int r = copy_f32(c->wr7, data, kC * 7, s)) return r; });
-        SETTER("latent_to_emb_r.bias", { WANT(kC); if (int r = copy_f32(c->br7, data, kC, s)) return r; });
+        c->slot.rel_f.w = SETTER("latent_to_emb_f.weight", { WANT(kC, 7); if (int r = copy_f32(c->wf7, data, kC * 7, s)) return r; });
+        c->slot.rel_f.b = SETTER("latent_to_emb_f.bias", { WANT(kC); if (int r = copy_f32(c->bf7, data, kC, s)) return r; });
+        c->slot.rel_r.w = SETTER("latent_to_emb_r.weight", { WANT(kC, 7); if (int r = copy_f32(c->wr7, data, kC * 7, s)) return r; });
+        c->slot.rel_r.b = SETTER("latent_to_emb_r.bias", { WANT(kC); if (int r = copy_f32(c->br7, data, kC, s)) return r; });
     }
-    SETTER("emb_to_latent.linear.weight",
+    c->slot.fin.w = SETTER("emb_to_latent.linear.weight",
            { WANT(c->D, kC); launch_pack_rows(data, kC, c->map_fin, 1, kKS, 1.f, c->wfin, s); launch_pack_rows(data, kC, c->map_fin, 1, kKS, 1.f, c->wfin_k, s, 1); });
-    SETTER("emb_to_latent.linear.bias", { WANT(c->D); if (int r = copy_f32(c->bfin, data, c->D, s)) return r; });
-    SETTER("emb_to_latent.adaLN_modulation.1.weight", {
+    c->slot.fin.b = SETTER("emb_to_latent.linear.bias", { WANT(c->D); if (int r = copy_f32(c->bfin, data, c->D, s)) return r; });
+    c->slot.fin_ada.w = SETTER("emb_to_latent.adaLN_modulation.1.weight", {
         WANT(2 * kC, kC);
         if (int r = copy_f32(c->ada_w + (size_t)c->final_off() * kC, data, (size_t)2 * kC * kC, s)) return r;
     });
-    SETTER("emb_to_latent.adaLN_modulation.1.bias",
+    c->slot.fin_ada.b = SETTER("emb_to_latent.adaLN_modulation.1.bias",
            { WANT(2 * kC); if (int r = copy_f32(c->ada_b + c->final_off(), data, 2 * kC, s)) return r; });
     c->trunk.resize(nl);
     c->ipa.resize(nl);
     for (int i = 0; i < nl; ++i) {
         const std::string p = "layers." + std::to_string(i) + ".";
         TrunkW* t = &c->trunk[i];
-        SETTER(p + "adaLN_modulation.1.weight", {
+        t->ada.w = SETTER(p + "adaLN_modulation.1.weight", {
             WANT(9 * kC, kC);
             if (int r = copy_f32(c->ada_w + (size_t)c->trunk_off(i) * kC, data, (size_t)9 * kC * kC, s)) return r;
         });
-        SETTER(p + "adaLN_modulation.1.bias",
+        t->ada.b = SETTER(p + "adaLN_modulation.1.bias",
                { WANT(9 * kC); if (int r = copy_f32(c->ada_b + c->trunk_off(i), data, 9 * kC, s)) return r; });
         TRY(register_mha(c, p + "mha_t.attn.", &t->mha_t));
         TRY(register_mha(c, p + "mha_l.attn.", &t->mha_l));
@@ -568,29 +593,29 @@ extern "C" int32_t mdgen_ctx_create(mdgen_ctx** out, const mdgen_model_desc* d) 
         TRY(c->dalloc(&w->head_w, (size_t)4));
         TRY(c->dalloc(&w->wout, (size_t)12 * 16 * 64));
         TRY(c->dalloc(&w->bout, (size_t)kC));
-        SETTER(p + "adaLN_modulation.1.weight", {
+        w->slot.ada.w = SETTER(p + "adaLN_modulation.1.weight", {
             WANT(6 * kC, kC);
             if (int r = copy_f32(c->ada_w + (size_t)c->ipa_off(i) * kC, data, (size_t)6 * kC * kC, s)) return r;
         });
-        SETTER(p + "adaLN_modulation.1.bias",
+        w->slot.ada.b = SETTER(p + "adaLN_modulation.1.bias",
                { WANT(6 * kC); if (int r = copy_f32(c->ada_b + c->ipa_off(i), data, 6 * kC, s)) return r; });
-        SETTER(p + "ipa_norm.weight", { WANT(kC); if (int r = copy_f32(w->gamma_beta, data, kC, s)) return r; });
-        SETTER(p + "ipa_norm.bias", { WANT(kC); if (int r = copy_f32(w->gamma_beta + kC, data, kC, s)) return r; });
-        SETTER(p + "ipa.head_weights", { WANT(4); if (int r = copy_f32(w->head_w, data, 4, s)) return r; });
-        SETTER(p + "ipa.linear_q.weight", { WANT(128, kC); launch_pack_rows(data, kC, c->map_nat, 4, kKS, 1.f, w->wproj, s); });
-        SETTER(p + "ipa.linear_q.bias", { WANT(128); if (int r = copy_f32(w->bproj, data, 128, s)) return r; });
-        SETTER(p + "ipa.linear_kv.weight",
+        w->slot.norm.w = SETTER(p + "ipa_norm.weight", { WANT(kC); if (int r = copy_f32(w->gamma_beta, data, kC, s)) return r; });
+        w->slot.norm.b = SETTER(p + "ipa_norm.bias", { WANT(kC); if (int r = copy_f32(w->gamma_beta + kC, data, kC, s)) return r; });
+        w->slot.head_w = SETTER(p + "ipa.head_weights", { WANT(4); if (int r = copy_f32(w->head_w, data, 4, s)) return r; });
+        w->slot.q.w = SETTER(p + "ipa.linear_q.weight", { WANT(128, kC); launch_pack_rows(data, kC, c->map_nat, 4, kKS, 1.f, w->wproj, s); });
+        w->slot.q.b = SETTER(p + "ipa.linear_q.bias", { WANT(128); if (int r = copy_f32(w->bproj, data, 128, s)) return r; });
+        w->slot.kv.w = SETTER(p + "ipa.linear_kv.weight",
                { WANT(256, kC); launch_pack_rows(data, kC, c->map_nat, 8, kKS, 1.f, w->wproj + (size_t)4 * kKS * 64, s); });
-        SETTER(p + "ipa.linear_kv.bias", { WANT(256); if (int r = copy_f32(w->bproj + 128, data, 256, s)) return r; });
-        SETTER(p + "ipa.linear_q_points.weight",
+        w->slot.kv.b = SETTER(p + "ipa.linear_kv.bias", { WANT(256); if (int r = copy_f32(w->bproj + 128, data, 256, s)) return r; });
+        w->slot.q_points.w = SETTER(p + "ipa.linear_q_points.weight",
                { WANT(96, kC); launch_pack_rows(data, kC, c->map_nat, 3, kKS, 1.f, w->wproj + (size_t)12 * kKS * 64, s); });
-        SETTER(p + "ipa.linear_q_points.bias", { WANT(96); if (int r = copy_f32(w->bproj + 384, data, 96, s)) return r; });
-        SETTER(p + "ipa.linear_kv_points.weight",
+        w->slot.q_points.b = SETTER(p + "ipa.linear_q_points.bias", { WANT(96); if (int r = copy_f32(w->bproj + 384, data, 96, s)) return r; });
+        w->slot.kv_points.w = SETTER(p + "ipa.linear_kv_points.weight",
                { WANT(192, kC); launch_pack_rows(data, kC, c->map_nat, 6, kKS, 1.f, w->wproj + (size_t)15 * kKS * 64, s); });
-        SETTER(p + "ipa.linear_kv_points.bias", { WANT(192); if (int r = copy_f32(w->bproj + 480, data, 192, s)) return r; });
-        SETTER(p + "ipa.linear_out.weight",
+        w->slot.kv_points.b = SETTER(p + "ipa.linear_kv_points.bias", { WANT(192); if (int r = copy_f32(w->bproj + 480, data, 192, s)) return r; });
+        w->slot.out.w = SETTER(p + "ipa.linear_out.weight",
                { WANT(kC, kIpaFeat); launch_pack_rows(data, kIpaFeat, c->map_nat, 12, 16, 1.f, w->wout, s); });
-        SETTER(p + "ipa.linear_out.bias", { WANT(kC); if (int r = copy_f32(w->bout, data, kC, s)) return r; });
+        w->slot.out.b = SETTER(p + "ipa.linear_out.bias", { WANT(kC); if (int r = copy_f32(w->bout, data, kC, s)) return r; });
         TRY(register_mha(c, p + "mha_l.attn.", &w->mha_l));
         TRY(register_ffn(c, p, &w->ffn, false));
     }
@@ -619,18 +644,19 @@ extern "C" int32_t mdgen_ctx_destroy(mdgen_ctx* c) {
     return 0;
 }
 
-extern "C" int32_t mdgen_ctx_num_weights(const mdgen_ctx* c) { return c ? (int32_t)c->names.size() : 0; }
+extern "C" int32_t mdgen_ctx_num_weights(const mdgen_ctx* c) { return c ? (int32_t)c->weights.size() : 0; }
 extern "C" const char* mdgen_ctx_weight_name(const mdgen_ctx* c, int32_t i) {
-    if (!c || i < 0 || i >= (int32_t)c->names.size()) return nullptr;
-    return c->names[i].c_str();
+    if (!c || i < 0 || i >= (int32_t)c->weights.size()) return nullptr;
+    return c->weights[i].name.c_str();
 }
 
 extern "C" int32_t mdgen_ctx_set_weight(mdgen_ctx* c, const char* key, const float* data, const int64_t* shape,
                                         int32_t ndim, void* stream) {
     if (!c || !key || !data || !shape) return fail(-1, "null argument");
-    auto it = c->setters.find(key);
-    if (it == c->setters.end()) return fail(-4, "unknown weight key '%s'", key);
-    const int r = it->second(data, shape, ndim, (hipStream_t)stream);
+    auto it = c->slot_of.find(key);
+    if (it == c->slot_of.end()) return fail(-4, "unknown weight key '%s'", key);
+    WeightSlot& w = c->weights[it->second];
+    const int r = w.set(data, shape, ndim, (hipStream_t)stream);
     if (r) {
         if (r == -3) {
             char buf[160] = "";
@@ -644,23 +670,22 @@ extern "C" int32_t mdgen_ctx_set_weight(mdgen_ctx* c, const char* key, const flo
     if (c->opt_keep_fp32) {
         size_t n = 1;
         for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
-        float*& dst = c->w32[key];
-        if (!dst)
-            if (int e = c->dalloc(&dst, n)) return e;
+        if (!w.f32)
+            if (int e = c->dalloc(&w.f32, n)) return e;
         // a BOUND entry (mdgen_train_bind_params) is the caller's master copy of the parameter: never written from here -- a
         // set_weight with other values (EMA weights swapped in for validation) only re-packs the sampler's operands
-        if (dst != data && !c->w32_bound.count(key))
-            HIPCHK(hipMemcpyAsync(dst, data, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        if (w.f32 != data && !w.bound)
+            HIPCHK(hipMemcpyAsync(w.f32, data, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     }
-    c->provided[key] = true;
+    w.provided = true;
     c->finalized = false;
     return 0;
 }
 
 extern "C" int32_t mdgen_ctx_finalize(mdgen_ctx* c, void* stream) {
     if (!c) return fail(-1, "null context");
-    for (const auto& n : c->names)
-        if (!c->provided.count(n)) return fail(-5, "weight '%s' was not provided", n.c_str());
+    for (const WeightSlot& w : c->weights)
+        if (!w.provided) return fail(-5, "weight '%s' was not provided", w.name.c_str());
     if (!c->inv_freq_set) return fail(-5, "rot_emb.inv_freq was not provided");
     launch_rope_table(c->rope, c->inv_freq, kMaxPos + 1, (hipStream_t)stream);
     LAUNCHCHK();
@@ -680,7 +705,7 @@ extern "C" int32_t mdgen_ctx_set_option(mdgen_ctx* c, const char* name, int32_t 
         c->opt_keep_fp32 = value;
     } else if (n == "precision") {
         if (value != 16 && value != 32) return fail(-2, "precision must be 16 (bf16 operands) or 32 (fp32 operands)");
-        if (value == 32 && (!c->opt_keep_fp32 || c->w32.empty()))
+        if (value == 32 && (!c->opt_keep_fp32 || !c->any_f32()))
             return fail(-6, "precision 32 needs the fp32 weight copies: set option keep_fp32_weights = 1 before loading weights");
         c->opt_precision = value;
     } else if (n == "attention_path") {
@@ -933,45 +958,41 @@ static F32Bufs f32_bufs(const Run& r) {
     o.feat = o.hid + maxrows * kF;
     return o;
 }
-static const float* w32(const mdgen_ctx* c, const std::string& key) {
-    auto it = c->w32.find(key);
-    return it == c->w32.end() ? nullptr : it->second;
+// The fp32 path and the training step read every parameter's fp32 copy: all of them are checked here, before the call's first
+// launch (make_run), so that the code below reads c->f32(slot) without a test.  A slot lacks its copy when option keep_fp32_weights
+// was switched on after that weight had been handed over.
+static int check_f32_weights(const mdgen_ctx* c) {
+    for (const WeightSlot& w : c->weights)
+        if (!w.f32) return fail(-6, "fp32 copy of weight '%s' is missing (option keep_fp32_weights)", w.name.c_str());
+    return 0;
 }
-#define W32(var, key)                                                                      \
-    const float* var = w32(r.c, key);                                                      \
-    if (!var) return fail(-6, "fp32 copy of weight '%s' is missing (option keep_fp32_weights)", std::string(key).c_str())
 
 // one attention sub-layer, fp32: LN + modulate -> q, k, v -> RoPE -> softmax attention -> out-projection + gated residual
-static int attn_sublayer_fp32(const Run& r, const std::string& pre, float* h, long nrows, const AxisMap& ax,
-                              const ModMap& mm, int shift, int scale, int gate, const MaskMap& mk, long pos_div, int pos_mod) {
+static int attn_sublayer_fp32(const Run& r, const MhaW& m, float* h, long nrows, const AxisMap& ax, const ModMap& mm, int shift,
+                              int scale, int gate, const MaskMap& mk, long pos_div, int pos_mod) {
+    const mdgen_ctx* c = r.c;
     const F32Bufs b = f32_bufs(r);
-    W32(wq, pre + "q_proj.weight"); W32(bq, pre + "q_proj.bias");
-    W32(wk, pre + "k_proj.weight"); W32(bk, pre + "k_proj.bias");
-    W32(wv, pre + "v_proj.weight"); W32(bv, pre + "v_proj.bias");
-    W32(wo, pre + "out_proj.weight"); W32(bo, pre + "out_proj.bias");
-    W32(biask, pre + "bias_k"); W32(biasv, pre + "bias_v");
+    const auto& p = m.slot;
     const ModMap none{nullptr, 1, 1, 0, 0};
     launch32_ln_mod(h, nrows, mm, shift, scale, 0, 1e-6f, b.y, r.s);
     const float qscale = 1.0f / std::sqrt((float)kDH);   // mha.py:263 q *= head_dim ** -0.5
-    launch32_linear(b.y, kC, wq, kC, bq, nrows, kC, kC, 4, b.qkv, 3 * kC, 0, none, 0, 0, qscale, r.s);
-    launch32_linear(b.y, kC, wk, kC, bk, nrows, kC, kC, 0, b.qkv, 3 * kC, kC, none, 0, 0, 0.f, r.s);
-    launch32_linear(b.y, kC, wv, kC, bv, nrows, kC, kC, 0, b.qkv, 3 * kC, 2 * kC, none, 0, 0, 0.f, r.s);
-    launch32_rope(b.qkv, nrows, 3 * kC, pos_div, pos_mod, r.c->inv_freq, r.s);
-    launch32_attn(b.qkv, 3 * kC, ax, mk, biask, biasv, r.c->inv_freq, b.att, r.s);
-    launch32_linear(b.att, kC, wo, kC, bo, nrows, kC, kC, 2, h, kC, 0, mm, gate, 1, 0.f, r.s);
+    launch32_linear(b.y, kC, c->f32(p.q.w), kC, c->f32(p.q.b), nrows, kC, kC, 4, b.qkv, 3 * kC, 0, none, 0, 0, qscale, r.s);
+    launch32_linear(b.y, kC, c->f32(p.k.w), kC, c->f32(p.k.b), nrows, kC, kC, 0, b.qkv, 3 * kC, kC, none, 0, 0, 0.f, r.s);
+    launch32_linear(b.y, kC, c->f32(p.v.w), kC, c->f32(p.v.b), nrows, kC, kC, 0, b.qkv, 3 * kC, 2 * kC, none, 0, 0, 0.f, r.s);
+    launch32_rope(b.qkv, nrows, 3 * kC, pos_div, pos_mod, c->inv_freq, r.s);
+    launch32_attn(b.qkv, 3 * kC, ax, mk, c->f32(p.bias_k), c->f32(p.bias_v), c->inv_freq, b.att, r.s);
+    launch32_linear(b.att, kC, c->f32(p.o.w), kC, c->f32(p.o.b), nrows, kC, kC, 2, h, kC, 0, mm, gate, 1, 0.f, r.s);
     LAUNCHCHK();
     return 0;
 }
 
-static int mlp_sublayer_fp32(const Run& r, const std::string& pre, float* h, long nrows, const ModMap& mm, int shift, int scale,
-                             int gate) {
+static int mlp_sublayer_fp32(const Run& r, const FfnW& f, float* h, long nrows, const ModMap& mm, int shift, int scale, int gate) {
+    const mdgen_ctx* c = r.c;
     const F32Bufs b = f32_bufs(r);
-    W32(w1, pre + "fc1.weight"); W32(b1, pre + "fc1.bias");
-    W32(w2, pre + "fc2.weight"); W32(b2, pre + "fc2.bias");
     const ModMap none{nullptr, 1, 1, 0, 0};
     launch32_ln_mod(h, nrows, mm, shift, scale, 0, 1e-6f, b.y, r.s);
-    launch32_linear(b.y, kC, w1, kC, b1, nrows, kF, kC, 1, b.hid, kF, 0, none, 0, 0, 0.f, r.s);
-    launch32_linear(b.hid, kF, w2, kF, b2, nrows, kC, kF, 2, h, kC, 0, mm, gate, 1, 0.f, r.s);
+    launch32_linear(b.y, kC, c->f32(f.slot.fc1.w), kC, c->f32(f.slot.fc1.b), nrows, kF, kC, 1, b.hid, kF, 0, none, 0, 0, 0.f, r.s);
+    launch32_linear(b.hid, kF, c->f32(f.slot.fc2.w), kF, c->f32(f.slot.fc2.b), nrows, kC, kF, 2, h, kC, 0, mm, gate, 1, 0.f, r.s);
     LAUNCHCHK();
     return 0;
 }
@@ -1263,20 +1284,15 @@ static int ipa_stack(const Run& r, float* hbuf, const float* rel7, const float* 
         const IpaW& w = c->ipa[i];
         ModMap mm{r.mod() + c->ipa_off(i), r.L, r.B, r.mod_step_stride, r.mod_group_stride};
         if (c->opt_precision == 32) {   // ---- fp32 operands: ipa_norm -> four projections -> point attention -> linear_out
-            const std::string pre = "ipa_layers." + std::to_string(i) + ".";
             const F32Bufs fb = f32_bufs(r);
-            W32(wq, pre + "ipa.linear_q.weight"); W32(bq, pre + "ipa.linear_q.bias");
-            W32(wkv, pre + "ipa.linear_kv.weight"); W32(bkv, pre + "ipa.linear_kv.bias");
-            W32(wqp, pre + "ipa.linear_q_points.weight"); W32(bqp, pre + "ipa.linear_q_points.bias");
-            W32(wkp, pre + "ipa.linear_kv_points.weight"); W32(bkp, pre + "ipa.linear_kv_points.bias");
-            W32(wout, pre + "ipa.linear_out.weight"); W32(bout, pre + "ipa.linear_out.bias");
+            const auto& p = w.slot;
             const ModMap none{nullptr, 1, 1, 0, 0};
             float* proj = (float*)(r.ws + r.lay.ipa_proj);
             launch32_ln_mod(hbuf, r.Mp, ModMap{w.gamma_beta, 1, 1, 0, 0}, 1, 0, 1, 1e-5f, fb.y, r.s);
-            launch32_linear(fb.y, kC, wq, kC, bq, r.Mp, 128, kC, 0, proj, kIpaProj, 0, none, 0, 0, 0.f, r.s);
-            launch32_linear(fb.y, kC, wkv, kC, bkv, r.Mp, 256, kC, 0, proj, kIpaProj, 128, none, 0, 0, 0.f, r.s);
-            launch32_linear(fb.y, kC, wqp, kC, bqp, r.Mp, 96, kC, 0, proj, kIpaProj, 384, none, 0, 0, 0.f, r.s);
-            launch32_linear(fb.y, kC, wkp, kC, bkp, r.Mp, 192, kC, 0, proj, kIpaProj, 480, none, 0, 0, 0.f, r.s);
+            launch32_linear(fb.y, kC, c->f32(p.q.w), kC, c->f32(p.q.b), r.Mp, 128, kC, 0, proj, kIpaProj, 0, none, 0, 0, 0.f, r.s);
+            launch32_linear(fb.y, kC, c->f32(p.kv.w), kC, c->f32(p.kv.b), r.Mp, 256, kC, 0, proj, kIpaProj, 128, none, 0, 0, 0.f, r.s);
+            launch32_linear(fb.y, kC, c->f32(p.q_points.w), kC, c->f32(p.q_points.b), r.Mp, 96, kC, 0, proj, kIpaProj, 384, none, 0, 0, 0.f, r.s);
+            launch32_linear(fb.y, kC, c->f32(p.kv_points.w), kC, c->f32(p.kv_points.b), r.Mp, 192, kC, 0, proj, kIpaProj, 480, none, 0, 0, 0.f, r.s);
             IpaAttnParams ap{};
             ap.proj = proj;
             ap.rot = rot;
@@ -1289,10 +1305,10 @@ static int ipa_stack(const Run& r, float* hbuf, const float* rel7, const float* 
             ap.B = r.B;
             ap.L = r.L;
             launch_ipa_attn(ap, r.s);
-            launch32_linear(fb.feat, kIpaFeat, wout, kIpaFeat, bout, r.Mp, kC, kIpaFeat, 2, hbuf, kC, 0, none, 0, 0, 0.f, r.s);
+            launch32_linear(fb.feat, kIpaFeat, c->f32(p.out.w), kIpaFeat, c->f32(p.out.b), r.Mp, kC, kIpaFeat, 2, hbuf, kC, 0, none, 0, 0, 0.f, r.s);
             LAUNCHCHK();
-            if (int e = attn_sublayer_fp32(r, pre + "mha_l.attn.", hbuf, r.Mp, ax, mm, 0, 1, 2, mk, 1, r.L)) return e;
-            if (int e = mlp_sublayer_fp32(r, pre, hbuf, r.Mp, mm, 3, 4, 5)) return e;
+            if (int e = attn_sublayer_fp32(r, w.mha_l, hbuf, r.Mp, ax, mm, 0, 1, 2, mk, 1, r.L)) return e;
+            if (int e = mlp_sublayer_fp32(r, w.ffn, hbuf, r.Mp, mm, 3, 4, 5)) return e;
             continue;
         }
         LnLinearParams lp{};
@@ -1447,20 +1463,19 @@ static int denoise_step(const Run& r, int step, float* x, float* out, int euler,
     MaskMap mk{r.mask, 0};
     if (c->opt_precision == 32) {   // ---- fp32 operands (k_fp32.hip): same dataflow, one kernel per reference op group
         for (int i = 0; i < c->nl; ++i) {
-            const std::string pre = "layers." + std::to_string(i) + ".";
+            const TrunkW& w = c->trunk[i];
             ModMap mm{modstep + c->trunk_off(i), r.T * r.L, r.B, 0, r.mod_group_stride};
-            if (int er = attn_sublayer_fp32(r, pre + "mha_l.attn.", h, r.N, axL, mm, 0, 1, 2, mk, 1, r.L)) return er;
-            if (int er = attn_sublayer_fp32(r, pre + "mha_t.attn.", h, r.N, axT, mm, 3, 4, 5, mk, r.L, r.T)) return er;
-            if (int er = mlp_sublayer_fp32(r, pre, h, r.N, mm, 6, 7, 8)) return er;
+            if (int er = attn_sublayer_fp32(r, w.mha_l, h, r.N, axL, mm, 0, 1, 2, mk, 1, r.L)) return er;
+            if (int er = attn_sublayer_fp32(r, w.mha_t, h, r.N, axT, mm, 3, 4, 5, mk, r.L, r.T)) return er;
+            if (int er = mlp_sublayer_fp32(r, w.ffn, h, r.N, mm, 6, 7, 8)) return er;
             if (trace_h) HIPCHK(hipMemcpyAsync(trace_h + (size_t)(i + 1) * r.N * kC, h, hbytes, hipMemcpyDeviceToDevice, r.s));
         }
-        W32(wfin, "emb_to_latent.linear.weight");
-        W32(bfin, "emb_to_latent.linear.bias");
         const F32Bufs fb = f32_bufs(r);
         const ModMap fm{modstep + c->final_off(), r.T * r.L, r.B, 0, r.mod_group_stride};
         const ModMap none{nullptr, 1, 1, 0, 0};
         launch32_ln_mod(h, r.N, fm, 0, 1, 0, 1e-6f, fb.y, r.s);
-        launch32_linear(fb.y, kC, wfin, kC, bfin, r.N, r.D, kC, euler ? 3 : 0, euler ? x : out, r.D, 0, none, 0, 0, dt, r.s);
+        launch32_linear(fb.y, kC, c->f32(c->slot.fin.w), kC, c->f32(c->slot.fin.b), r.N, r.D, kC, euler ? 3 : 0, euler ? x : out, r.D, 0,
+                        none, 0, 0, dt, r.s);
         LAUNCHCHK();
         return 0;
     }
@@ -1515,6 +1530,8 @@ static int make_run(Run* r, mdgen_ctx* c, const mdgen_shape* sh, int S, int t_sh
         return fail(-7, "workspace too small: %zu < %zu bytes", ws_bytes, r->lay.total_bytes);
     if (((uintptr_t)ws & 255) != 0) return fail(-7, "workspace must be 256-byte aligned");
     if (c->opt_precision == 32 && !c->opt_keep_fp32) return fail(-6, "precision 32 requires option keep_fp32_weights");
+    if (c->opt_precision == 32)
+        if (int e = check_f32_weights(c)) return e;
     if (g_dry && c->opt_precision == 32) return fail(-2, "the dispatch plan covers the bf16 path");
     r->c = c;
     r->B = sh->B;

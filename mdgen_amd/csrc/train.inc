@@ -20,8 +20,7 @@ struct Train {
     Run r;
     mdgen_ctx* c;
     float* grads;
-    const int64_t* goff;     // per ctx weight index
-    std::map<std::string, int> idx;
+    const int64_t* goff;     // per weight slot; < 0: no gradient wanted
     // Operand mode of the call's linear layers / weight gradients (option train_precision): false = exact fp32 products
     // (k32_linear / k32_dw), true = bf16-rounded operands on the bf16 MFMA with fp32 accumulation (launch16_linear / launch16_dw).
     bool bf16 = false;
@@ -38,8 +37,8 @@ struct Train {
     // and normalises it (k32_gate_ln_mod).  flush_pending() materialises the stream into h (after the last layer).  14 launches and
     // 28 passes over the 98 MB stream less per ATLAS step (26.9 -> 25.9 ms).  The IPA stack applies its updates at once.
     struct Pending { const float* x = nullptr; const float* u = nullptr; ModMap mm{}; int gate = 0; long nrows = 0; };
-    mutable Pending pend;
-    mutable bool defer_gate = false;
+    Pending pend;
+    bool defer_gate = false;
     // Turned weights (dX = dY W of the launches too small for the streamed kernel runs through the forward kernel on W^T): with a
     // second stream and bf16 operands the images of ALL such products of the call are computed there at the start of the call, while
     // the main stream runs the forward pass, from the list of requests the previous call recorded (mdgen_ctx::tr_plan); a request that
@@ -48,21 +47,21 @@ struct Train {
     // backward, ~330 launches of 5-12 us on 256 rows, leaves the chip half idle: its 50 transposes moved off the critical path took
     // the ATLAS step 25.6 -> 25.2 ms.  Packing the streamed kernel's bf16 fragment streams ahead the same way is slower: a stream
     // packed right in front of its consumer is read out of the L2 it was just written to.)
-    mutable size_t tr_cursor = 0;
-    mutable bool tr_use = false, tr_waited = false, tr_record = false;
-    mutable hipEvent_t tr_done = nullptr;
-    mutable std::vector<mdgen_ctx::TurnReq> tr_new;
+    size_t tr_cursor = 0;
+    bool tr_use = false, tr_waited = false, tr_record = false;
+    hipEvent_t tr_done = nullptr;
+    std::vector<mdgen_ctx::TurnReq> tr_new;
     hipStream_t side = nullptr;                  // null: one stream
-    mutable float *du = nullptr, *dhid = nullptr, *dqkv = nullptr, *dbias = nullptr;   // the instance of the current sub-layer
+    float *du = nullptr, *dhid = nullptr, *dqkv = nullptr, *dbias = nullptr;   // the instance of the current sub-layer
     float *du_[2], *dhid_[2], *dqkv_[2], *dbias_[2], *part2, *cpart2;
-    mutable int sub = 0;
-    mutable hipEvent_t done[2] = {nullptr, nullptr};
+    int sub = 0;
+    hipEvent_t done[2] = {nullptr, nullptr};
     // Event pool of the fork / join traffic, round-robin.  A call takes 6 events per attention sub-layer, 5 per IPA block, 3 per
     // MLP block, plus heads, milestones and the join: 80 per layer of the stack (two-sided model) is a safe bound, and the pool is
     // sized from that, so an event is not re-recorded within one call.  (Re-recording would still be safe -- a wait captures the
     // record that precedes it at enqueue time, and done[p] is consumed ~15 events later -- but the pool does not rely on it.)
-    mutable int events_used = 0;
-    hipEvent_t next_event() const {
+    int events_used = 0;
+    hipEvent_t next_event() {
         const size_t want = (size_t)96 * (size_t)(c->nl > 0 ? c->nl : 1) + 64;
         while (c->train_ev.size() < want) {
             hipEvent_t e = nullptr;
@@ -72,13 +71,13 @@ struct Train {
         if (c->train_ev.empty() || (size_t)++events_used > c->train_ev.size()) return nullptr;   // (callers report -8)
         return c->train_ev[c->train_ev_next++ % c->train_ev.size()];
     }
-    int begin_sub() const {
+    int begin_sub() {
         const int p = sub & 1;
         if (side && done[p]) HIPCHK(hipStreamWaitEvent(r.s, done[p], 0));
         du = du_[p]; dhid = dhid_[p]; dqkv = dqkv_[p]; dbias = dbias_[p];
         return 0;
     }
-    int end_sub() const {
+    int end_sub() {
         if (side) {
             hipEvent_t e = next_event();
             if (!e) return fail(-8, "hipEventCreate failed (training event pool)");
@@ -89,7 +88,7 @@ struct Train {
         return 0;
     }
     // where a weight gradient whose operands are complete on the main stream NOW is to be launched
-    int fork(hipStream_t* sw, float** pt, float** cpt) const {
+    int fork(hipStream_t* sw, float** pt, float** cpt) {
         *sw = r.s; *pt = part; *cpt = cpart;
         if (!side) return 0;
         hipEvent_t e = next_event();
@@ -106,11 +105,8 @@ struct Train {
     std::vector<SubTapeMlp> im2;
     std::vector<SubTapeIpa> ip2;
     float *dhi2 = nullptr, *rel7 = nullptr;
-    float* G(const std::string& name) const {
-        auto it = idx.find(name);
-        if (it == idx.end() || goff[it->second] < 0) return nullptr;
-        return grads + goff[it->second];
-    }
+    const float* w(int slot) const { return c->f32(slot); }   // (every slot has its copy: check_f32_weights ran before the first launch)
+    float* grad(int slot) const { return goff[slot] < 0 ? nullptr : grads + goff[slot]; }
 };
 
 struct Carver {
@@ -190,10 +186,6 @@ static size_t carve_train(Train* t, const mdgen_ctx* c, long B, long T, long L, 
     return cv.off;
 }
 
-#define TW32(var, key)                                                                      \
-    const float* var = w32(t.c, key);                                                       \
-    if (!var) return fail(-6, "fp32 copy of weight '%s' is missing (option keep_fp32_weights)", std::string(key).c_str())
-
 static const ModMap kNoMod{nullptr, 1, 1, 0, 0};
 
 // Whether the bf16 row stores below may be used: their consumers are the streamed / wide kernels only (k_wide16.hip), so the
@@ -242,7 +234,7 @@ static const void* wpack1(const Train& t, const float* w, int ld, long n, int m,
 // LayerNorm + modulate of the residual stream into y, the stream's rows copied to the tape (h_in) -- with the previous sub-layer's
 // pending gated update formed on the way when there is one (Train::Pending)
 // y_bf16: y is stored as bf16 rows (rows_bf16: it is only ever a GEMM operand)
-static int ln_mod_tape(const Train& t, const float* h, long nrows, const ModMap& mm, int shift, int scale, float* y, float* h_in,
+static int ln_mod_tape(Train& t, const float* h, long nrows, const ModMap& mm, int shift, int scale, float* y, float* h_in,
                        bool y_bf16) {
     if (!t.pend.x) {
         launch32_ln_mod(h, nrows, mm, shift, scale, 0, 1e-6f, y, t.r.s, h_in, y_bf16);
@@ -254,24 +246,23 @@ static int ln_mod_tape(const Train& t, const float* h, long nrows, const ModMap&
     return 0;
 }
 // the sub-layer's residual update h += gate * u, or its deferral (x = the sub-layer's taped input rows = the stream before it)
-static void gated_update(const Train& t, float* h, const float* x, const float* u, long nrows, const ModMap& mm, int gate) {
+static void gated_update(Train& t, float* h, const float* x, const float* u, long nrows, const ModMap& mm, int gate) {
     if (t.defer_gate) t.pend = Train::Pending{x, u, mm, gate, nrows};
     else launch32_gated_add(h, u, nrows, mm, gate, 1, t.r.s);
 }
-static void flush_pending(const Train& t, float* h) {
+static void flush_pending(Train& t, float* h) {
     if (!t.pend.x) return;
     launch32_gated_sum(h, t.pend.x, t.pend.u, t.pend.nrows, t.pend.mm, t.pend.gate, t.r.s);
     t.pend = Train::Pending{};
 }
 
-static int attn_fwd_tape(const Train& t, const std::string& pre, float* h, long nrows, const AxisMap& ax, const ModMap& mm,
-                         int shift, int scale, int gate, const MaskMap& mk, long pos_div, int pos_mod, const SubTapeAttn& tp) {
+static int attn_fwd_tape(Train& t, const MhaW& m, float* h, long nrows, const AxisMap& ax, const ModMap& mm, int shift, int scale,
+                         int gate, const MaskMap& mk, long pos_div, int pos_mod, const SubTapeAttn& tp) {
     const Run& r = t.r;
-    TW32(wq, pre + "q_proj.weight"); TW32(bq, pre + "q_proj.bias");
-    TW32(wk, pre + "k_proj.weight"); TW32(bk, pre + "k_proj.bias");
-    TW32(wv, pre + "v_proj.weight"); TW32(bv, pre + "v_proj.bias");
-    TW32(wo, pre + "out_proj.weight"); TW32(bo, pre + "out_proj.bias");
-    TW32(biask, pre + "bias_k"); TW32(biasv, pre + "bias_v");
+    const auto& p = m.slot;
+    const float *wq = t.w(p.q.w), *wk = t.w(p.k.w), *wv = t.w(p.v.w), *wo = t.w(p.o.w);
+    const float *bq = t.w(p.q.b), *bk = t.w(p.k.b), *bv = t.w(p.v.b), *bo = t.w(p.o.b);
+    const float *biask = t.w(p.bias_k), *biasv = t.w(p.bias_v);
     const bool y16 = rows_bf16(t, nrows, sub_wide({wq, wk, wv, wo}));
     if (int e = ln_mod_tape(t, h, nrows, mm, shift, scale, tp.y, tp.h_in, y16)) return e;     // y (taped), and the tape's copy of h
     const float qscale = 1.0f / std::sqrt((float)kDH);
@@ -300,11 +291,10 @@ static int attn_fwd_tape(const Train& t, const std::string& pre, float* h, long 
     return 0;
 }
 
-static int mlp_fwd_tape(const Train& t, const std::string& pre, float* h, long nrows, const ModMap& mm, int shift, int scale,
-                        int gate, const SubTapeMlp& tp) {
+static int mlp_fwd_tape(Train& t, const FfnW& f, float* h, long nrows, const ModMap& mm, int shift, int scale, int gate,
+                        const SubTapeMlp& tp) {
     const Run& r = t.r;
-    TW32(w1, pre + "fc1.weight"); TW32(b1, pre + "fc1.bias");
-    TW32(w2, pre + "fc2.weight"); TW32(b2, pre + "fc2.bias");
+    const float *w1 = t.w(f.slot.fc1.w), *b1 = t.w(f.slot.fc1.b), *w2 = t.w(f.slot.fc2.w), *b2 = t.w(f.slot.fc2.b);
     const bool wide = sub_wide({w1, w2});
     const bool y16 = rows_bf16(t, nrows, wide);   // (y and hid = gelu(pre) alike)
     if (int e = ln_mod_tape(t, h, nrows, mm, shift, scale, tp.y, tp.h_in, y16)) return e;     // y (taped), and the tape's copy of h
@@ -321,7 +311,7 @@ static int mlp_fwd_tape(const Train& t, const std::string& pre, float* h, long n
 
 // W^T of one weight [rows][cols] (nseg = 1) or of three [rows][cols] weights side by side (row stride 3 * rows): the image computed
 // ahead (Train::tr_*), else a launch in place into t.wt
-static const float* turned(const Train& t, const float* const* w, int nseg, int rows, int cols) {
+static const float* turned(Train& t, const float* const* w, int nseg, int rows, int cols) {
     hipStream_t s = t.r.s;
     if (t.tr_use && t.tr_cursor < t.c->tr_plan.size()) {
         const mdgen_ctx::TurnReq& q = t.c->tr_plan[t.tr_cursor];
@@ -347,17 +337,17 @@ static const float* turned(const Train& t, const float* const* w, int nseg, int 
 }
 
 // ---- backward helpers ---------------------------------------------------------------------------------------------
-// y = x W^T + b  (W [M][K]):  dx (store / accumulate) = dy W;  dW += dy^T x;  db += colsum(dy)
+// y = x W^T + b  (the layer `lin`, W [M][K]):  dx (store / accumulate) = dy W;  dW += dy^T x;  db += colsum(dy)
 // gelu_pre != nullptr: dx = (dy W) * gelu'(gelu_pre) (same shape and row stride as dx; not with accumulate)
-static int lin_bwd(const Train& t, const float* dy, int ldy, const float* x, int ldx, const float* W, long n, int M, int K,
-                   float* dx, int ldx_out, bool accumulate, const std::string& wname, const std::string& bname,
-                   const float* gelu_pre = nullptr, bool x_bf16 = false, bool side_ok = true, bool dy_bf16 = false,
-                   bool dx_bf16 = false) {   // dx_bf16 (with gelu_pre only): dx is written as bf16 rows
+static int lin_bwd(Train& t, const float* dy, int ldy, const float* x, int ldx, const Lin& lin, long n, int M, int K, float* dx,
+                   int ldx_out, bool accumulate, const float* gelu_pre = nullptr, bool x_bf16 = false, bool side_ok = true,
+                   bool dy_bf16 = false, bool dx_bf16 = false) {   // dx_bf16 (with gelu_pre only): dx is written as bf16 rows
     hipStream_t s = t.r.s;
+    const float* W = t.w(lin.w);
     // dW / db: second stream (dy and x are complete at this point of the main stream).  side_ok = false: dy is a buffer the
     // main stream goes on updating in place (the IPA block's ungated residual), the gradient stays on the main stream.
-    float* gb = t.G(bname);
-    float* gw = t.G(wname);
+    float* gb = t.grad(lin.b);
+    float* gw = t.grad(lin.w);
     hipStream_t sw = s;
     float *pt = t.part, *cpt = t.cpart;
     if ((gw || gb) && side_ok)
@@ -419,40 +409,32 @@ static void lnmod_bwd(const Train& t, const float* h_in, const float* dy, long n
 }
 
 // backward of one MLP sub-layer; dh is updated in place (dh_in = dh_out + ...)
-static int mlp_bwd(const Train& t, const std::string& pre, float* dh, long nrows, const ModMap& mm, int shift, int scale, int gate,
-                   long tpg, long mod_ld, float* dmod_base, const SubTapeMlp& tp) {
-    TW32(w1, pre + "fc1.weight");
-    TW32(w2, pre + "fc2.weight");
+static int mlp_bwd(Train& t, const FfnW& f, float* dh, long nrows, const ModMap& mm, int shift, int scale, int gate, long tpg,
+                   long mod_ld, float* dmod_base, const SubTapeMlp& tp) {
     if (int e = t.begin_sub()) return e;
     // (as mlp_fwd_tape decided the tape's storage): hid, y, du = gate * dh and d pre as bf16 rows, or all of them fp32
-    const bool r16 = rows_bf16(t, nrows, sub_wide({w1, w2}));
+    const bool r16 = rows_bf16(t, nrows, sub_wide({t.w(f.slot.fc1.w), t.w(f.slot.fc2.w)}));
     if (int e = gate_bwd(t, dh, tp.u, nrows, mm, gate, tpg, mod_ld, dmod_base, r16)) return e;   // t.du = gate * dh
     // d pre = (du W2) * gelu'(pre): the GELU derivative is the epilogue of the dX product
-    if (int e = lin_bwd(t, t.du, kC, tp.hid, kF, w2, nrows, kC, kF, t.dhid, kF, false, pre + "fc2.weight", pre + "fc2.bias", tp.pre,
-                        r16, true, r16, r16))
-        return e;
-    if (int e = lin_bwd(t, t.dhid, kF, tp.y, kC, w1, nrows, kF, kC, t.dy, kC, false, pre + "fc1.weight", pre + "fc1.bias", nullptr,
-                        r16, true, r16))
-        return e;
+    if (int e = lin_bwd(t, t.du, kC, tp.hid, kF, f.slot.fc2, nrows, kC, kF, t.dhid, kF, false, tp.pre, r16, true, r16, r16)) return e;
+    if (int e = lin_bwd(t, t.dhid, kF, tp.y, kC, f.slot.fc1, nrows, kF, kC, t.dy, kC, false, nullptr, r16, true, r16)) return e;
     lnmod_bwd(t, tp.h_in, t.dy, nrows, mm, shift, scale, tpg, mod_ld, dmod_base, dh, true);
     LAUNCHCHK();
     return t.end_sub();
 }
 
 // backward of one attention sub-layer
-static int attn_bwd(const Train& t, const std::string& pre, float* dh, long nrows, const AxisMap& ax, const ModMap& mm, int shift,
-                    int scale, int gate, const MaskMap& mk, long pos_div, int pos_mod, long tpg, long mod_ld, float* dmod_base,
+static int attn_bwd(Train& t, const MhaW& m, float* dh, long nrows, const AxisMap& ax, const ModMap& mm, int shift, int scale,
+                    int gate, const MaskMap& mk, long pos_div, int pos_mod, long tpg, long mod_ld, float* dmod_base,
                     const SubTapeAttn& tp) {
     hipStream_t s = t.r.s;
-    TW32(wq, pre + "q_proj.weight"); TW32(wk, pre + "k_proj.weight"); TW32(wv, pre + "v_proj.weight");
-    TW32(wo, pre + "out_proj.weight");
-    TW32(biask, pre + "bias_k"); TW32(biasv, pre + "bias_v");
+    const auto& p = m.slot;
+    const float *wq = t.w(p.q.w), *wk = t.w(p.k.w), *wv = t.w(p.v.w), *wo = t.w(p.o.w);
+    const float *biask = t.w(p.bias_k), *biasv = t.w(p.bias_v);
     if (int e = t.begin_sub()) return e;
     const bool r16 = rows_bf16(t, nrows, sub_wide({wq, wk, wv, wo}));   // (as attn_fwd_tape decided the tape's storage: y)
     if (int e = gate_bwd(t, dh, tp.u, nrows, mm, gate, tpg, mod_ld, dmod_base, r16)) return e;   // t.du
-    if (int e = lin_bwd(t, t.du, kC, tp.att, kC, wo, nrows, kC, kC, t.dy, kC, false, pre + "out_proj.weight", pre + "out_proj.bias",
-                        nullptr, false, true, r16))
-        return e;                                                                        // t.dy = d att
+    if (int e = lin_bwd(t, t.du, kC, tp.att, kC, p.o, nrows, kC, kC, t.dy, kC, false, nullptr, false, true, r16)) return e;   // t.dy = d att
     // the sequence-resident kernels write dq | dk | dv as bf16 rows (rows_bf16)
     const bool dq16 = attn16_seq_form(ax) && r16;
     if (t.bf16)
@@ -462,7 +444,7 @@ static int attn_bwd(const Train& t, const std::string& pre, float* dh, long nrow
         launch32_attn_bwd(tp.qkv, 3 * kC, ax, mk, biask, biasv, t.c->inv_freq, tp.att, t.dy, t.dqkv, t.stats, t.dbias, s, tp.lse);
     // bias key / value: rows [seq][dk: head x 24 | dv: head x 24] summed over sequences = the (1, 1, C) tensors
     {
-        float *gk = t.G(pre + "bias_k"), *gv = t.G(pre + "bias_v");
+        float *gk = t.grad(p.bias_k), *gv = t.grad(p.bias_v);
         hipStream_t sw = s;
         float *pt = t.part, *cpt = t.cpart;
         if (gk || gv)
@@ -476,8 +458,8 @@ static int attn_bwd(const Train& t, const std::string& pre, float* dh, long nrow
         // q | k | v as one layer of 1152 outputs: dy = dqkv [Wq; Wk; Wv] (one product with the contraction over all three,
         // the weights turned side by side into the scratch), dW and db of all three from one pass over (dqkv, y)
         const float* w3[3] = {wq, wk, wv};
-        float* gw3[3] = {t.G(pre + "q_proj.weight"), t.G(pre + "k_proj.weight"), t.G(pre + "v_proj.weight")};
-        float* gb3[3] = {t.G(pre + "q_proj.bias"), t.G(pre + "k_proj.bias"), t.G(pre + "v_proj.bias")};
+        float* gw3[3] = {t.grad(p.q.w), t.grad(p.k.w), t.grad(p.v.w)};
+        float* gb3[3] = {t.grad(p.q.b), t.grad(p.k.b), t.grad(p.v.b)};
         const bool want_g = gw3[0] || gw3[1] || gw3[2] || gb3[0] || gb3[1] || gb3[2];
         hipStream_t sw = s;
         float *pt = t.part, *cpt = t.cpart;
@@ -502,9 +484,9 @@ static int attn_bwd(const Train& t, const std::string& pre, float* dh, long nrow
         }
         LAUNCHCHK();
     } else {
-        if (int e = lin_bwd(t, t.dqkv, 3 * kC, tp.y, kC, wq, nrows, kC, kC, t.dy, kC, false, pre + "q_proj.weight", pre + "q_proj.bias")) return e;
-        if (int e = lin_bwd(t, t.dqkv + kC, 3 * kC, tp.y, kC, wk, nrows, kC, kC, t.dy, kC, true, pre + "k_proj.weight", pre + "k_proj.bias")) return e;
-        if (int e = lin_bwd(t, t.dqkv + 2 * kC, 3 * kC, tp.y, kC, wv, nrows, kC, kC, t.dy, kC, true, pre + "v_proj.weight", pre + "v_proj.bias")) return e;
+        if (int e = lin_bwd(t, t.dqkv, 3 * kC, tp.y, kC, p.q, nrows, kC, kC, t.dy, kC, false)) return e;
+        if (int e = lin_bwd(t, t.dqkv + kC, 3 * kC, tp.y, kC, p.k, nrows, kC, kC, t.dy, kC, true)) return e;
+        if (int e = lin_bwd(t, t.dqkv + 2 * kC, 3 * kC, tp.y, kC, p.v, nrows, kC, kC, t.dy, kC, true)) return e;
     }
     lnmod_bwd(t, tp.h_in, t.dy, nrows, mm, shift, scale, tpg, mod_ld, dmod_base, dh, true);
     LAUNCHCHK();
@@ -512,15 +494,11 @@ static int attn_bwd(const Train& t, const std::string& pre, float* dh, long nrow
 }
 
 // backward of the IPA block of layer i:  x_out = x_in + linear_out(ipa(LN_affine(x_in)))   (latent_model.py:373)
-static int ipa_block_bwd(const Train& t, int i, const std::string& pre, const SubTapeIpa& tp, float* dhi, const float* rot,
-                         const float* trans) {
+static int ipa_block_bwd(Train& t, const IpaW& w, const SubTapeIpa& tp, float* dhi, const float* rot, const float* trans) {
     const Run& r = t.r;
     hipStream_t s = r.s;
-    const IpaW& w = t.c->ipa[i];
+    const auto& p = w.slot;
     const long Mp = r.Mp;
-    TW32(wq, pre + "ipa.linear_q.weight"); TW32(wkv, pre + "ipa.linear_kv.weight");
-    TW32(wqp, pre + "ipa.linear_q_points.weight"); TW32(wkp, pre + "ipa.linear_kv_points.weight");
-    TW32(wout, pre + "ipa.linear_out.weight");
     if (int e = t.begin_sub()) return e;
     float* dfeat = t.dhid;                    // [Mp][256]
     float* dproj = t.dqkv;                    // [Mp][672]
@@ -528,26 +506,24 @@ static int ipa_block_bwd(const Train& t, int i, const std::string& pre, const Su
     float* qrec = t.act;                      // [Mp][4][49]
     // linear_out (ungated residual: d u = d x_out)
     // (its dY is the residual stream's gradient itself, which this block updates in place below: main stream)
-    if (int e = lin_bwd(t, dhi, kC, tp.feat, kIpaFeat, wout, Mp, kC, kIpaFeat, dfeat, kIpaFeat, false,
-                        pre + "ipa.linear_out.weight", pre + "ipa.linear_out.bias", nullptr, false, false))
-        return e;
+    if (int e = lin_bwd(t, dhi, kC, tp.feat, kIpaFeat, p.out, Mp, kC, kIpaFeat, dfeat, kIpaFeat, false, nullptr, false, false)) return e;
     IpaAttnParams ap{};
     ap.proj = tp.proj; ap.rot = rot; ap.trans = trans;
     ap.mask_bl = (const float*)(r.ws + r.lay.mask_bl);
     ap.head_w = w.head_w; ap.feat = nullptr; ap.feat32 = tp.feat; ap.stats = tp.stats;
     ap.ngroups = r.B; ap.B = r.B; ap.L = r.L;
-    launch32_ipa_bwd(ap, dfeat, dproj, dhw, qrec, t.G(pre + "ipa.head_weights"), s, t.part, t.part_floats);
+    launch32_ipa_bwd(ap, dfeat, dproj, dhw, qrec, t.grad(p.head_w), s, t.part, t.part_floats);
     LAUNCHCHK();
     // the four input projections of xn = LN_affine(x_in)
     launch32_ln_mod(tp.h_in, Mp, ModMap{w.gamma_beta, 1, 1, 0, 0}, 1, 0, 1, 1e-5f, t.ytmp, s);
-    if (int e = lin_bwd(t, dproj, kIpaProj, t.ytmp, kC, wq, Mp, 128, kC, t.dy, kC, false, pre + "ipa.linear_q.weight", pre + "ipa.linear_q.bias")) return e;
-    if (int e = lin_bwd(t, dproj + 128, kIpaProj, t.ytmp, kC, wkv, Mp, 256, kC, t.dy, kC, true, pre + "ipa.linear_kv.weight", pre + "ipa.linear_kv.bias")) return e;
-    if (int e = lin_bwd(t, dproj + 384, kIpaProj, t.ytmp, kC, wqp, Mp, 96, kC, t.dy, kC, true, pre + "ipa.linear_q_points.weight", pre + "ipa.linear_q_points.bias")) return e;
-    if (int e = lin_bwd(t, dproj + 480, kIpaProj, t.ytmp, kC, wkp, Mp, 192, kC, t.dy, kC, true, pre + "ipa.linear_kv_points.weight", pre + "ipa.linear_kv_points.bias")) return e;
+    if (int e = lin_bwd(t, dproj, kIpaProj, t.ytmp, kC, p.q, Mp, 128, kC, t.dy, kC, false)) return e;
+    if (int e = lin_bwd(t, dproj + 128, kIpaProj, t.ytmp, kC, p.kv, Mp, 256, kC, t.dy, kC, true)) return e;
+    if (int e = lin_bwd(t, dproj + 384, kIpaProj, t.ytmp, kC, p.q_points, Mp, 96, kC, t.dy, kC, true)) return e;
+    if (int e = lin_bwd(t, dproj + 480, kIpaProj, t.ytmp, kC, p.kv_points, Mp, 192, kC, t.dy, kC, true)) return e;
     // affine LayerNorm (eps 1e-5): d gamma = sum dy * xhat, d beta = sum dy, d x
-    if (float* g = t.G(pre + "ipa_norm.weight"))
+    if (float* g = t.grad(p.norm.w))
         launch32_colsum(t.dy, kC, tp.h_in, kC, nullptr, 2, Mp, kC, Mp, 1e-5f, g, 0, t.cpart, t.cpart_floats, s);
-    if (float* g = t.G(pre + "ipa_norm.bias"))
+    if (float* g = t.grad(p.norm.b))
         launch32_colsum(t.dy, kC, nullptr, 0, nullptr, 0, Mp, kC, Mp, 0.f, g, 0, t.cpart, t.cpart_floats, s);
     launch32_ln_bwd(tp.h_in, t.dy, Mp, ModMap{w.gamma_beta, 1, 1, 0, 0}, 0, 1, 1e-5f, dhi, 1, s);
     LAUNCHCHK();
@@ -576,19 +552,18 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
     if (!c) return fail(-1, "null context");
     const bool two = c->d.tps_condition != 0;
     if (two && (!end_rot || !end_trans)) return fail(-2, "tps_condition requires end frames");
-    if (!c->opt_keep_fp32 || c->w32.empty()) return fail(-6, "the training step runs on the fp32 weight copies: option keep_fp32_weights");
+    if (!c->opt_keep_fp32 || !c->any_f32()) return fail(-6, "the training step runs on the fp32 weight copies: option keep_fp32_weights");
     Train t;
     t.c = c;
     t.grads = grads;
     t.goff = grad_offsets;
-    for (size_t i = 0; i < c->names.size(); ++i) t.idx[c->names[i]] = (int)i;
     const int saved_precision = c->opt_precision;
     c->opt_precision = 32;
     struct Restore { mdgen_ctx* c; int p; ~Restore() { c->opt_precision = p; } } restore{c, saved_precision};
     // option train_precision = 16: the linear layers and weight gradients of this call multiply bf16-rounded operands on
     // the bf16 MFMA (fp32 accumulate, fp32 master weights, everything else fp32)
     t.bf16 = c->opt_train_precision == 16;
-    if (int e = make_run(&t.r, c, sh, 1, 0, ws, ws_bytes, stream)) return e;
+    if (int e = make_run(&t.r, c, sh, 1, 0, ws, ws_bytes, stream)) return e;   // (with check_f32_weights: precision is 32 here)
     Run& r = t.r;
     r.mask = mask; r.start_rot = start_rot; r.start_trans = start_trans; r.end_rot = two ? end_rot : nullptr; r.end_trans = two ? end_trans : nullptr; r.rel7_in = two ? rel7 : nullptr;
     r.x_cond = x_cond; r.x_cond_mask = x_cond_mask; r.aatype = aatype;
@@ -623,7 +598,7 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
     // on its own stream -- also when the call returns an error half-way (a caller that then zeroes or reuses `grads` or the tape
     // must not race with gradient kernels still running over there).  The error path's own HIP status is not reported twice.
     struct Join {
-        const Train& t;
+        Train& t;
         hipStream_t s;
         bool done = false;
         int run() {
@@ -662,22 +637,17 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
                            const std::vector<SubTapeMlp>& ims) -> int {
         launch_ipa_init(c->aa_emb, r.aatype, rel, w7, b7, hx, r.B, r.B, r.L, s);
         for (int i = 0; i < nl; ++i) {
-            const std::string pre = "ipa_layers." + std::to_string(i) + ".";
             const IpaW& w = c->ipa[i];
+            const auto& p = w.slot;
             const ModMap mm{r.mod() + c->ipa_off(i), r.L, r.B, r.mod_step_stride, r.mod_group_stride};
             const SubTapeIpa& tp = ips[i];
             const F32Bufs fb = f32_bufs(r);
-            TW32(wq, pre + "ipa.linear_q.weight"); TW32(bq, pre + "ipa.linear_q.bias");
-            TW32(wkv, pre + "ipa.linear_kv.weight"); TW32(bkv, pre + "ipa.linear_kv.bias");
-            TW32(wqp, pre + "ipa.linear_q_points.weight"); TW32(bqp, pre + "ipa.linear_q_points.bias");
-            TW32(wkp, pre + "ipa.linear_kv_points.weight"); TW32(bkp, pre + "ipa.linear_kv_points.bias");
-            TW32(wout, pre + "ipa.linear_out.weight"); TW32(bout, pre + "ipa.linear_out.bias");
             HIPCHK(hipMemcpyAsync(tp.h_in, hx, (size_t)Mp * kC * 4, hipMemcpyDeviceToDevice, s));
             launch32_ln_mod(hx, Mp, ModMap{w.gamma_beta, 1, 1, 0, 0}, 1, 0, 1, 1e-5f, fb.y, s);
-            step_linear(t, fb.y, kC, wq, kC, bq, Mp, 128, kC, 0, tp.proj, kIpaProj, 0, 0.f, s);
-            step_linear(t, fb.y, kC, wkv, kC, bkv, Mp, 256, kC, 0, tp.proj, kIpaProj, 128, 0.f, s);
-            step_linear(t, fb.y, kC, wqp, kC, bqp, Mp, 96, kC, 0, tp.proj, kIpaProj, 384, 0.f, s);
-            step_linear(t, fb.y, kC, wkp, kC, bkp, Mp, 192, kC, 0, tp.proj, kIpaProj, 480, 0.f, s);
+            step_linear(t, fb.y, kC, t.w(p.q.w), kC, t.w(p.q.b), Mp, 128, kC, 0, tp.proj, kIpaProj, 0, 0.f, s);
+            step_linear(t, fb.y, kC, t.w(p.kv.w), kC, t.w(p.kv.b), Mp, 256, kC, 0, tp.proj, kIpaProj, 128, 0.f, s);
+            step_linear(t, fb.y, kC, t.w(p.q_points.w), kC, t.w(p.q_points.b), Mp, 96, kC, 0, tp.proj, kIpaProj, 384, 0.f, s);
+            step_linear(t, fb.y, kC, t.w(p.kv_points.w), kC, t.w(p.kv_points.b), Mp, 192, kC, 0, tp.proj, kIpaProj, 480, 0.f, s);
             IpaAttnParams ap{};
             ap.proj = tp.proj; ap.rot = rot; ap.trans = trans;
             ap.mask_bl = (const float*)(r.ws + r.lay.mask_bl);
@@ -685,10 +655,10 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
             ap.ngroups = r.B; ap.B = r.B; ap.L = r.L;
             ap.part = t.part; ap.part_floats = t.part_floats;      // few groups: key loop sliced over workgroups
             launch_ipa_attn(ap, s);
-            step_linear(t, tp.feat, kIpaFeat, wout, kIpaFeat, bout, Mp, kC, kIpaFeat, 2, hx, kC, 0, 0.f, s);
+            step_linear(t, tp.feat, kIpaFeat, t.w(p.out.w), kIpaFeat, t.w(p.out.b), Mp, kC, kIpaFeat, 2, hx, kC, 0, 0.f, s);
             LAUNCHCHK();
-            if (int e = attn_fwd_tape(t, pre + "mha_l.attn.", hx, Mp, axI, mm, 0, 1, 2, mkI, 1, r.L, ils[i])) return e;
-            if (int e = mlp_fwd_tape(t, pre, hx, Mp, mm, 3, 4, 5, ims[i])) return e;
+            if (int e = attn_fwd_tape(t, w.mha_l, hx, Mp, axI, mm, 0, 1, 2, mkI, 1, r.L, ils[i])) return e;
+            if (int e = mlp_fwd_tape(t, w.ffn, hx, Mp, mm, 3, 4, 5, ims[i])) return e;
         }
         return 0;
     };
@@ -729,22 +699,20 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
     const MaskMap mk{r.mask, 0};
     t.defer_gate = true;   // the trunk's residual updates ride in the next sub-layer's LayerNorm launch
     for (int i = 0; i < nl; ++i) {
-        const std::string pre = "layers." + std::to_string(i) + ".";
+        const TrunkW& w = c->trunk[i];
         const ModMap mm{r.mod() + c->trunk_off(i), r.T * r.L, r.B, 0, r.mod_group_stride};
-        if (int e = attn_fwd_tape(t, pre + "mha_l.attn.", h, N, axL, mm, 0, 1, 2, mk, 1, r.L, t.tl[i])) return e;
-        if (int e = attn_fwd_tape(t, pre + "mha_t.attn.", h, N, axT, mm, 3, 4, 5, mk, r.L, r.T, t.tt[i])) return e;
-        if (int e = mlp_fwd_tape(t, pre, h, N, mm, 6, 7, 8, t.tm[i])) return e;
+        if (int e = attn_fwd_tape(t, w.mha_l, h, N, axL, mm, 0, 1, 2, mk, 1, r.L, t.tl[i])) return e;
+        if (int e = attn_fwd_tape(t, w.mha_t, h, N, axT, mm, 3, 4, 5, mk, r.L, r.T, t.tt[i])) return e;
+        if (int e = mlp_fwd_tape(t, w.ffn, h, N, mm, 6, 7, 8, t.tm[i])) return e;
     }
     t.defer_gate = false;
     flush_pending(t, h);
     LAUNCHCHK();
-    TW32(wfin, "emb_to_latent.linear.weight");
-    TW32(bfin, "emb_to_latent.linear.bias");
     const ModMap fm{r.mod() + c->final_off(), r.T * r.L, r.B, 0, r.mod_group_stride};
     {
         const F32Bufs fb = f32_bufs(r);
         launch32_ln_mod(h, N, fm, 0, 1, 0, 1e-6f, fb.y, s);
-        step_linear(t, fb.y, kC, wfin, kC, bfin, N, r.D, kC, 0, pred, r.D, 0, 0.f, s);
+        step_linear(t, fb.y, kC, t.w(c->slot.fin.w), kC, t.w(c->slot.fin.b), N, r.D, kC, 0, pred, r.D, 0, 0.f, s);
         launch_masked_mse(pred, target, loss_mask, loss, TL * r.D, r.B, s, t.cpart, t.cpart_floats);
         LAUNCHCHK();
     }
@@ -773,8 +741,8 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
     const float* silu_bwd = (const float*)(r.ws + r.lay.silu_t);
     // adaLN head of one parameter block: mod[b] = W_ada silu_t[b] + b_ada  (its d mod rows are complete once the
     // block's own backward is done)
-    auto head = [&](const std::string& pfx, int off, int rows) -> int {
-        float *gw = t.G(pfx + "adaLN_modulation.1.weight"), *gb = t.G(pfx + "adaLN_modulation.1.bias");
+    auto head = [&](const Lin& ada, int off, int rows) -> int {
+        float *gw = t.grad(ada.w), *gb = t.grad(ada.b);
         hipStream_t sw = s;
         float *pt = t.part, *cpt = t.cpart;
         if (gw || gb)   // (the block's d mod rows are complete here and nothing writes them again)
@@ -789,23 +757,21 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
     launch32_loss_grad(pred, target, loss_mask, TL * r.D, r.B, t.dsilu, dpred, s, t.cpart, t.cpart_floats);   // t.dsilu[0..B) = mask sums (scratch)
     {   // final layer: out = linear(modulate(LN(h)))
         launch32_ln_mod(h, N, fm, 0, 1, 0, 1e-6f, t.ytmp, s);
-        if (int e = lin_bwd(t, dpred, r.D, t.ytmp, kC, wfin, N, r.D, kC, t.dy, kC, false, "emb_to_latent.linear.weight",
-                            "emb_to_latent.linear.bias"))
-            return e;
+        if (int e = lin_bwd(t, dpred, r.D, t.ytmp, kC, c->slot.fin, N, r.D, kC, t.dy, kC, false)) return e;
         lnmod_bwd(t, h, t.dy, N, fm, 0, 1, TL, modld, t.dmod + c->final_off(), t.dh, false);
-        if (int e = head("emb_to_latent.", c->final_off(), 2 * kC)) return e;
+        if (int e = head(c->slot.fin_ada, c->final_off(), 2 * kC)) return e;
         LAUNCHCHK();
         if (int e = t.end_sub()) return e;
         if (int e = mark()) return e;
     }
     for (int i = nl - 1; i >= 0; --i) {
-        const std::string pre = "layers." + std::to_string(i) + ".";
+        const TrunkW& w = c->trunk[i];
         const ModMap mm{r.mod() + c->trunk_off(i), r.T * r.L, r.B, 0, r.mod_group_stride};
         float* dm = t.dmod + c->trunk_off(i);
-        if (int e = mlp_bwd(t, pre, t.dh, N, mm, 6, 7, 8, TL, modld, dm, t.tm[i])) return e;
-        if (int e = attn_bwd(t, pre + "mha_t.attn.", t.dh, N, axT, mm, 3, 4, 5, mk, r.L, r.T, TL, modld, dm, t.tt[i])) return e;
-        if (int e = attn_bwd(t, pre + "mha_l.attn.", t.dh, N, axL, mm, 0, 1, 2, mk, 1, r.L, TL, modld, dm, t.tl[i])) return e;
-        if (int e = head(pre, c->trunk_off(i), 9 * kC)) return e;
+        if (int e = mlp_bwd(t, w.ffn, t.dh, N, mm, 6, 7, 8, TL, modld, dm, t.tm[i])) return e;
+        if (int e = attn_bwd(t, w.mha_t, t.dh, N, axT, mm, 3, 4, 5, mk, r.L, r.T, TL, modld, dm, t.tt[i])) return e;
+        if (int e = attn_bwd(t, w.mha_l, t.dh, N, axL, mm, 0, 1, 2, mk, 1, r.L, TL, modld, dm, t.tl[i])) return e;
+        if (int e = head(w.ada, c->trunk_off(i), 9 * kC)) return e;
         LAUNCHCHK();
         if (int e = mark()) return e;
     }
@@ -814,12 +780,12 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
             hipStream_t sw = s;
             float *pt = t.part, *cpt = t.cpart;
             if (int e = t.fork(&sw, &pt, &cpt)) return e;
-            if (float* g = t.G("latent_to_emb.weight")) step_dw(t, t.dh, kC, xt, r.D, N, kC, r.D, g, pt, sw);
-            if (float* g = t.G("cond_to_emb.weight")) step_dw(t, t.dh, kC, r.x_cond, r.D, N, kC, r.D, g, pt, sw);
-            if (float* g = t.G("latent_to_emb.bias")) launch32_colsum(t.dh, kC, nullptr, 0, nullptr, 0, N, kC, N, 0.f, g, 0, cpt, t.cpart_floats, sw);
-            if (float* g = t.G("cond_to_emb.bias")) launch32_colsum(t.dh, kC, nullptr, 0, nullptr, 0, N, kC, N, 0.f, g, 0, cpt, t.cpart_floats, sw);
+            if (float* g = t.grad(c->slot.latent.w)) step_dw(t, t.dh, kC, xt, r.D, N, kC, r.D, g, pt, sw);
+            if (float* g = t.grad(c->slot.cond.w)) step_dw(t, t.dh, kC, r.x_cond, r.D, N, kC, r.D, g, pt, sw);
+            if (float* g = t.grad(c->slot.latent.b)) launch32_colsum(t.dh, kC, nullptr, 0, nullptr, 0, N, kC, N, 0.f, g, 0, cpt, t.cpart_floats, sw);
+            if (float* g = t.grad(c->slot.cond.b)) launch32_colsum(t.dh, kC, nullptr, 0, nullptr, 0, N, kC, N, 0.f, g, 0, cpt, t.cpart_floats, sw);
         }
-        if (float* g = t.G("mask_to_emb.weight")) {
+        if (float* g = t.grad(c->slot.mask)) {
             float* ind0 = t.stats;          // [N] + [N] floats fit the stats scratch (N * 32 floats)
             float* ind1 = t.stats + N;
             launch32_indicator(r.x_cond_mask, N, ind0, ind1, s);
@@ -832,40 +798,36 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
     }
     // IPA stack(s), tokens (b, l): groups of L tokens.  d ipa_out reaches both streams of the two-sided model unchanged.
     if (two) HIPCHK(hipMemcpyAsync(t.dhi2, t.dhi, (size_t)Mp * kC * 4, hipMemcpyDeviceToDevice, s));
-    auto ipa_backward = [&](float* dhx, const float* rel, const char* w7name, const char* b7name, const float* rot,
-                            const float* trans, const std::vector<SubTapeIpa>& ips, const std::vector<SubTapeAttn>& ils,
+    auto ipa_backward = [&](float* dhx, const float* rel, const Lin& rel7, const float* rot, const float* trans,
+                            const std::vector<SubTapeIpa>& ips, const std::vector<SubTapeAttn>& ils,
                             const std::vector<SubTapeMlp>& ims, bool last) -> int {
         for (int i = nl - 1; i >= 0; --i) {
-            const std::string pre = "ipa_layers." + std::to_string(i) + ".";
+            const IpaW& w = c->ipa[i];
             const ModMap mm{r.mod() + c->ipa_off(i), r.L, r.B, r.mod_step_stride, r.mod_group_stride};
             float* dm = t.dmod + c->ipa_off(i);
-            if (int e = mlp_bwd(t, pre, dhx, Mp, mm, 3, 4, 5, r.L, modld, dm, ims[i])) return e;
-            if (int e = attn_bwd(t, pre + "mha_l.attn.", dhx, Mp, axI, mm, 0, 1, 2, mkI, 1, r.L, r.L, modld, dm, ils[i])) return e;
-            if (int e = ipa_block_bwd(t, i, pre, ips[i], dhx, rot, trans)) return e;
+            if (int e = mlp_bwd(t, w.ffn, dhx, Mp, mm, 3, 4, 5, r.L, modld, dm, ims[i])) return e;
+            if (int e = attn_bwd(t, w.mha_l, dhx, Mp, axI, mm, 0, 1, 2, mkI, 1, r.L, r.L, modld, dm, ils[i])) return e;
+            if (int e = ipa_block_bwd(t, w, ips[i], dhx, rot, trans)) return e;
             if (last) {   // (the two-sided model's first stream leaves this layer's gradients half done)
-                if (int e = head(pre, c->ipa_off(i), 6 * kC)) return e;
+                if (int e = head(w.slot.ada, c->ipa_off(i), 6 * kC)) return e;
                 LAUNCHCHK();
                 if (int e = mark()) return e;
             }
         }
         // stack input: aatype_to_emb[aatype] (+ latent_to_emb_{f,r}(rel7))
-        if (float* g = t.G("aatype_to_emb.weight")) launch32_embed_rows_bwd(dhx, r.aatype, r.B, r.B, r.L, g, s);
+        if (float* g = t.grad(c->slot.aatype)) launch32_embed_rows_bwd(dhx, r.aatype, r.B, r.B, r.L, g, s);
         if (rel) {
-            if (float* g = t.G(w7name)) step_dw(t, dhx, kC, rel, 7, Mp, kC, 7, g, t.part, s);
-            if (float* g = t.G(b7name)) launch32_colsum(dhx, kC, nullptr, 0, nullptr, 0, Mp, kC, Mp, 0.f, g, 0, t.cpart, t.cpart_floats, s);
+            if (float* g = t.grad(rel7.w)) step_dw(t, dhx, kC, rel, 7, Mp, kC, 7, g, t.part, s);
+            if (float* g = t.grad(rel7.b)) launch32_colsum(dhx, kC, nullptr, 0, nullptr, 0, Mp, kC, Mp, 0.f, g, 0, t.cpart, t.cpart_floats, s);
         }
         LAUNCHCHK();
         return 0;
     };
     if (!two) {
-        if (int e = ipa_backward(t.dhi, nullptr, "", "", r.start_rot, r.start_trans, t.ip, t.il, t.im, true)) return e;
+        if (int e = ipa_backward(t.dhi, nullptr, Lin{}, r.start_rot, r.start_trans, t.ip, t.il, t.im, true)) return e;
     } else {
-        if (int e = ipa_backward(t.dhi, rel_r, "latent_to_emb_r.weight", "latent_to_emb_r.bias", r.start_rot, r.start_trans,
-                                 t.ip, t.il, t.im, false))
-            return e;
-        if (int e = ipa_backward(t.dhi2, rel_f, "latent_to_emb_f.weight", "latent_to_emb_f.bias", r.end_rot, r.end_trans,
-                                 t.ip2, t.il2, t.im2, true))
-            return e;
+        if (int e = ipa_backward(t.dhi, rel_r, c->slot.rel_r, r.start_rot, r.start_trans, t.ip, t.il, t.im, false)) return e;
+        if (int e = ipa_backward(t.dhi2, rel_f, c->slot.rel_f, r.end_rot, r.end_trans, t.ip2, t.il2, t.im2, true)) return e;
     }
     {   // the time embedder behind all adaLN heads: d silu_t = d mod . W_ada
         float* dst = t.dsilu;                         // [B][384]
@@ -876,10 +838,10 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
         if (!launch32_skinny_wt(t.dmod, (int)modld, c->ada_w, kC, r.B, kC, c->modrow, dst, t.cpart, t.cpart_floats, s))
             step_linear(t, t.dmod, (int)modld, c->ada_w, kC, nullptr, r.B, kC, c->modrow, 0, dst, kC, 0, 0.f, s, 1);
         launch32_temb_bwd(tvals, r.B, c->d.time_multiplier, c->t_w0, c->t_b0, c->t_w2, c->t_b2, dst, emb, h1, dp1, dp2, s);
-        if (float* g = t.G("t_embedder.mlp.2.weight")) step_dw(t, dp2, kC, h1, kC, r.B, kC, kC, g, t.part, s);
-        if (float* g = t.G("t_embedder.mlp.2.bias")) launch32_colsum(dp2, kC, nullptr, 0, nullptr, 0, r.B, kC, r.B, 0.f, g, 0, t.cpart, t.cpart_floats, s);
-        if (float* g = t.G("t_embedder.mlp.0.weight")) step_dw(t, dp1, kC, emb, 256, r.B, kC, 256, g, t.part, s);
-        if (float* g = t.G("t_embedder.mlp.0.bias")) launch32_colsum(dp1, kC, nullptr, 0, nullptr, 0, r.B, kC, r.B, 0.f, g, 0, t.cpart, t.cpart_floats, s);
+        if (float* g = t.grad(c->slot.t2.w)) step_dw(t, dp2, kC, h1, kC, r.B, kC, kC, g, t.part, s);
+        if (float* g = t.grad(c->slot.t2.b)) launch32_colsum(dp2, kC, nullptr, 0, nullptr, 0, r.B, kC, r.B, 0.f, g, 0, t.cpart, t.cpart_floats, s);
+        if (float* g = t.grad(c->slot.t0.w)) step_dw(t, dp1, kC, emb, 256, r.B, kC, 256, g, t.part, s);
+        if (float* g = t.grad(c->slot.t0.b)) launch32_colsum(dp1, kC, nullptr, 0, nullptr, 0, r.B, kC, r.B, 0.f, g, 0, t.cpart, t.cpart_floats, s);
         LAUNCHCHK();
     }
     if (int e = mark()) return e;
@@ -904,8 +866,8 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
     return join.run();   // (the destructor covers the error returns above)
 }
 
-// The training kernels read the fp32 weights through c->w32 (natural layout, keyed by state_dict key).  Binding makes
-// those entries POINT INTO the caller's flat parameter buffer instead of at private copies, so an optimiser step that
+// The training kernels read the fp32 weights through WeightSlot::f32 (natural layout).  Binding makes
+// those pointers POINT INTO the caller's flat parameter buffer instead of at private copies, so an optimiser step that
 // updates the flat buffer in place is seen by the next mdgen_train_forward_backward without any hand-back
 // (round 2 re-uploaded and re-packed all 124 tensors through mdgen_ctx_set_weight after every step).
 // The bf16 fragment-packed weights of the SAMPLER are not touched: refresh them with mdgen_ctx_set_weight before sampling.
@@ -914,11 +876,12 @@ extern "C" int32_t mdgen_train_bind_params(mdgen_ctx* c, float* flat, const int6
     if (!c->opt_keep_fp32) return fail(-6, "binding needs option keep_fp32_weights = 1 (fp32 training path)");
     c->tr_plan_ok = false;   // the recorded weight-image requests point at the old locations: never read through them again
     c->tr_plan.clear();
-    for (size_t i = 0; i < c->names.size(); ++i) {
+    for (size_t i = 0; i < c->weights.size(); ++i) {
+        WeightSlot& w = c->weights[i];
         if (offsets[i] < 0) continue;
-        if (!c->w32.count(c->names[i])) return fail(-5, "weight '%s' has not been loaded yet", c->names[i].c_str());
-        c->w32[c->names[i]] = flat + offsets[i];   // (the private copy stays owned by the context and is freed with it)
-        c->w32_bound[c->names[i]] = true;
+        if (!w.f32) return fail(-5, "weight '%s' has not been loaded yet", w.name.c_str());
+        w.f32 = flat + offsets[i];   // (the private copy stays owned by the context and is freed with it)
+        w.bound = true;
     }
     return 0;
 }

@@ -221,6 +221,56 @@ def test_training_step_with_misaligned_parameter_binding():
     _check_vs_fp64(ref, loss, pred, got, 16, "misaligned")
 
 
+# ---- (d) a weight without its fp32 copy is refused before the step's first launch ----------------------------------------------
+def test_training_step_refuses_a_missing_fp32_copy_before_its_first_launch():
+    """A slot lacks its fp32 copy only when `keep_fp32_weights` was switched on after that weight had been handed over
+    (`mdgen_ctx_finalize` refuses a weight that was never provided).  So: the last trunk layer's fc2.weight goes over with the
+    option off, every other weight with it on.  `mdgen_train_forward_backward`, called directly so that the test owns the tape,
+    returns -6, `mdgen_last_error` names that key, and the tape, filled with a sentinel byte beforehand, still holds it in every
+    byte after a device synchronise: the copies are checked once, before anything is launched (the earlier layers' sub-layers
+    are NOT taped first)."""
+    import ctypes as C
+    from mdgen_amd import _lib as L
+    from mdgen_amd._lib import lib, ptr, check
+    from mdgen_amd.model import LatentMDGenModel
+    from mdgen_amd.synthetic import synth_state_dict
+    dev = _cuda()
+    B, T, L_, nl = 1, 16, 12, 2
+    cfg = _cfg("sim", T, L_, nl)
+    sd = {k: v.to(device=dev, dtype=torch.float32).contiguous() for k, v in synth_state_dict(cfg, 23).items()}
+    late = f"layers.{nl - 1}.fc2.weight"
+    m = LatentMDGenModel(cfg, dev)            # (bf16 model: keep_fp32_weights is off)
+    names = m.weight_names()
+    assert late in names
+    with torch.cuda.device(dev):
+        s = L.stream_ptr()
+        for k in [late] + [n for n in names if n != late]:
+            shp = (C.c_int64 * sd[k].dim())(*sd[k].shape)
+            check(lib.mdgen_ctx_set_weight(m._ctx, k.encode(), ptr(sd[k]), shp, sd[k].dim(), s))
+            if k == late:
+                check(lib.mdgen_ctx_set_option(m._ctx, b"keep_fp32_weights", 1))
+        check(lib.mdgen_ctx_finalize(m._ctx, s))
+        g = {k: v.to(dev).contiguous() for k, v in _case(cfg, B, T, L_, 0, 77).items()}
+        sh = L.Shape(B, T, L_)
+        nbytes = C.c_size_t()
+        check(lib.mdgen_train_workspace_bytes(m._ctx, C.byref(sh), C.byref(nbytes)))
+        tape = torch.full((nbytes.value,), 0xA5, dtype=torch.uint8, device=dev)
+        ws = m._workspace(B, T, L_, 1, False)
+        loss, pred, grads = torch.empty(B, device=dev), torch.empty_like(g["xt"]), torch.zeros(16, device=dev)
+        goff = (C.c_int64 * len(names))(*[-1] * len(names))
+        torch.cuda.synchronize()
+        rc = lib.mdgen_train_forward_backward(
+            m._ctx, C.byref(sh), ptr(g["xt"]), ptr(g["t"]), ptr(g["mask"]), ptr(g["sR"]), ptr(g["st"]), None, None, None,
+            ptr(g["x_cond"]), ptr(g["cm"]), ptr(g["aatype"]), ptr(g["ut"]), ptr(g["loss_mask"]), ptr(loss), ptr(pred), ptr(grads),
+            goff, ptr(ws), ws.numel(), ptr(tape), tape.numel(), s)
+        msg = lib.mdgen_last_error().decode()
+        torch.cuda.synchronize()
+    assert rc == -6, (rc, msg)
+    assert f"'{late}'" in msg, msg
+    touched = int((tape != 0xA5).sum())
+    assert touched == 0, f"{touched} of {tape.numel()} tape bytes were written before the step was refused"
+
+
 # ---- (b) a batch is the mean of its samples --------------------------------------------------------------------------------
 # (name, kind, B, T, L, pad, layers)
 BATCHES = [
