@@ -324,7 +324,7 @@ int32_t mdgen_profile_phase_trace(mdgen_ctx* ctx, uint64_t* dev_buf, int64_t cap
 int32_t mdgen_profile_report(mdgen_ctx* ctx, void* stream, char* buf, size_t buflen);
 /* Host only (no device, no context): which kernel classes a call of this shape launches and how often -- the library's own
  * orchestration code (the code path of latent_model.py:212-260 / transport.py:408-451's replacements above) run in a plan mode
- * that skips every HIP call.  mode 0: mdgen_sample_euler as the product runs it (sub-batch streams); 1: mdgen_denoiser_forward;
+ * that skips every HIP call; a call the entry point refuses (trace_h with a batch of several launch views) is refused here too.  mode 0: mdgen_sample_euler as the product runs it (sub-batch streams); 1: mdgen_denoiser_forward;
  * 2: mdgen_sample_euler as it runs under mdgen_profile_enable (one stream); 3: mdgen_denoiser_forward with trace_h; 4: one attempted
  * step of mdgen_sample_dopri5 (n_steps ignored; adds "integrator": {class: launches}).  options: "name=value,..." with mdgen_ctx_set_option's
  * names (bf16 path only).  ncu / xcd_round_robin: the two device facts mdgen_ctx_create would have probed (see "@context" of

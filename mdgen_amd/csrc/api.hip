@@ -12,7 +12,6 @@
 #include <climits>
 #include <functional>
 #include <map>
-#include <set>
 #include <string>
 #include <vector>
 
@@ -29,10 +28,15 @@ static int fail(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
-// Plan mode (mdgen_debug_dispatch_plan): the orchestration code below runs on the host ONLY -- every HIP call and every launch is
-// skipped, and each launch site's profile class is appended to *g_dry instead.  The plan is therefore the product's own dispatch
-// logic, not a restatement of it.
-static thread_local std::vector<std::string>* g_dry = nullptr;
+// Plan mode (mdgen_debug_dispatch_plan): the orchestration code below runs on the host ONLY -- every HIP call (HIPCHK) and every
+// launch (launch()) is skipped, and each launch's profile class is appended to g_dry->rec instead, with the sub-batch view it
+// belongs to (for_each_view; -1: the call's shared preparation).  The plan is therefore the product's own dispatch logic, not a
+// restatement of it.
+struct DryPlan {
+    int view = -1;
+    std::vector<std::pair<int, const char*>> rec;
+};
+static thread_local DryPlan* g_dry = nullptr;
 #define HIPCHK(expr)                                                                           \
     do {                                                                                       \
         if (g_dry) break;                                                                      \
@@ -41,7 +45,6 @@ static thread_local std::vector<std::string>* g_dry = nullptr;
     } while (0)
 #define LAUNCHCHK()                                                                            \
     do {                                                                                       \
-        if (g_dry) break;                                                                      \
         hipError_t e_ = hipGetLastError();                                                     \
         if (e_ != hipSuccess) return fail((int)e_, "kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); \
         if (const char* m_ = k32_take_launch_error()) return fail(-7, "internal: %s (%s:%d)", m_, __FILE__, __LINE__); \
@@ -168,7 +171,6 @@ struct mdgen_ctx {
                                 // k_ln_qkv8<true> (q, k | v over 2 workgroups; panels <= ncu / 2).  0 off, 1 (default) on
     bool xcd_round_robin = false;   // placement probe: workgroups with equal blockIdx % 8 share an XCD (k_mlp8's split form relies on it)
     long n_split_launches = 0;  // k_mlp8<., kMlpSplit> launches enqueued (or captured) since the last mdgen_profile_report
-    int live_streams = 1;       // sub-batch streams of the call being recorded / run (the workspace's split scratch serves one launch at a time)
     int opt_flash_rotate = 1;   // tiled attention: the 64-query chunks of a sequence start their walk over the key tiles at different tiles (k_flash.hip)
     int opt_flash_proj_form = 0;   // ... 0 (default): k_flash_proj8 (eight waves, 128-row panel, four query tiles per wave) for sequences of >= 512
                                    // positions whose launch gives every CU such a workgroup (cfg-2), else k_flash_proj (four waves, 64-row
@@ -202,8 +204,6 @@ struct mdgen_ctx {
     hipStream_t side[kMaxSide] = {};
     hipEvent_t ev_fork = nullptr, ev_join[kMaxSide] = {};
 
-    std::set<std::string> cls_names;   // storage of composed profile class names (ProfRec keeps a const char*)
-    const char* intern(const std::string& n) { return cls_names.insert(n).first->c_str(); }
     const float* f32(int slot) const { return weights[slot].f32; }
     bool any_f32() const {
         return std::any_of(weights.begin(), weights.end(), [](const WeightSlot& w) { return w.f32 != nullptr; });
@@ -220,29 +220,6 @@ struct mdgen_ctx {
     int trunk_off(int i) const { return i * 9 * kC; }
     int ipa_off(int i) const { return nl * 9 * kC + i * 6 * kC; }
     int final_off() const { return nl * 15 * kC; }
-};
-
-// RAII bracket of one launch with a hipEvent pair on the launch stream (profiling mode only)
-struct ProfScope {
-    mdgen_ctx* c;
-    hipStream_t s;
-    ProfRec r;
-    bool on;
-    ProfScope(mdgen_ctx* c_, const char* cls, hipStream_t s_) : c(c_), s(s_), on(c_->prof_on) {
-        if (g_dry) {   // plan mode: the class is the record
-            g_dry->push_back(cls);
-            on = false;
-            return;
-        }
-        if (on) {
-            r.cls = cls;
-            on = hipEventCreate(&r.a) == hipSuccess && hipEventCreate(&r.b) == hipSuccess &&
-                 hipEventRecord(r.a, s) == hipSuccess;
-        }
-    }
-    ~ProfScope() {
-        if (on && hipEventRecord(r.b, s) == hipSuccess) c->prof.push_back(r);
-    }
 };
 
 // ---- host-side index maps (DESIGN.md "fragment layout") -------------------------------------
@@ -772,14 +749,26 @@ constexpr size_t kSplitCounterBytes = 1024;   // kMlpSplitMaxPanels counters, pa
 static_assert(kMlpSplitMaxPanels * sizeof(unsigned) <= kSplitCounterBytes, "counter block");
 static size_t split_bytes(long panels) { return kSplitCounterBytes + 2 * (size_t)panels * kMlpSplit * kPanel * kC * 4; }
 
+// Row-owner MLP kernel: one workgroup = 4 waves x 32 rows and one workgroup per CU, so it needs ~200 workgroups to fill the
+// chip; smaller launches (IPA stack, B = 1 tetrapeptides) stay on the 64-row panel kernel.  Monotone in nrows.
+static bool mlp_uses_rows(const mdgen_ctx* c, long nrows) {
+    const long tiles = (nrows + 31) / 32;
+    return c->opt_mlp_path == 2 || (c->opt_mlp_path == 1 && tiles >= 3L * c->ncu);   // (768 row tiles = 192 four-wave workgroups on the 256-CU part)
+}
 // Gate fold (option mlp_fold): per (step, trunk layer) one MLP weight stream with that step's gate folded into fc2, and b2' = gate * b2.
-// Carved when the call shares t across the batch and its trunk launches can take the row-owner kernel.
-static bool mlp_uses_rows(const mdgen_ctx* c, long nrows);
+// For a call that shares t across the batch and whose trunk launches of `nrows` rows take the row-owner kernel.  Asked with two
+// row counts: mdgen_workspace_layout (public, knows no views) carves the region from the whole call's N, an upper bound of any
+// view's rows; prepare() packs the streams when the call's largest VIEW passes, the launches that would consume them.
 constexpr size_t kFoldStreamBytes = (size_t)kMlpFrags * 1024;
 constexpr size_t kFoldMaxBytes = (size_t)8 << 30;   // a call with so many steps that its streams would pass 8 GiB keeps the unfolded kernel
 static size_t fold_bytes(const mdgen_ctx* c, int S) { return (size_t)S * c->nl * (kFoldStreamBytes + (size_t)kC * 4); }
-static bool fold_on(const mdgen_ctx* c, long N, int t_shared, int S) {
-    return t_shared && c->opt_mlp_fold && c->opt_precision == 16 && mlp_uses_rows(c, N) && fold_bytes(c, S) <= kFoldMaxBytes;
+static bool fold_on(const mdgen_ctx* c, long nrows, int t_shared, int S) {
+    return t_shared && c->opt_mlp_fold && c->opt_precision == 16 && mlp_uses_rows(c, nrows) && fold_bytes(c, S) <= kFoldMaxBytes;
+}
+// ... and (option mlp_tail 2) steps 1 .. S-1 take their token embedding from the previous step's last MLP launch, which needs the
+// embedding's base rows per (step, b, l)
+static bool embed_base_on(const mdgen_ctx* c, long nrows, int t_shared, int S) {
+    return fold_on(c, nrows, t_shared, S) && c->opt_mlp_tail == 2 && S > 1;
 }
 
 static size_t frag_bytes(long nseq, int len) { return (size_t)nseq * kH * (len / 32 + 1) * kFragBytes; }
@@ -869,8 +858,8 @@ extern "C" int32_t mdgen_workspace_layout(const mdgen_ctx* c, const mdgen_shape*
     o->split = take(split_bytes(split_panels(c, maxrows)));
     // per-(step, layer) gate-folded MLP streams [S][nl][2304 KiB] | b2' [S][nl][384] fp32 (0 bytes unless fold_on)
     o->fold = take(fold_on(c, N, t_shared, S) ? fold_bytes(c, S) : 0);
-    // base rows of the token embedding per (step, b, l) for the embedding-as-tail form [S][B*L][384] fp32 (0 bytes unless fold and S > 1)
-    o->embase = take(fold_on(c, N, t_shared, S) && c->opt_mlp_tail == 2 && S > 1 ? (size_t)Mp * kC * 4 : 0);
+    // base rows of the token embedding per (step, b, l) for the embedding-as-tail form [S][B*L][384] fp32 (0 bytes unless embed_base_on)
+    o->embase = take(embed_base_on(c, N, t_shared, S) ? (size_t)Mp * kC * 4 : 0);
     o->total_bytes = off;
     return 0;
 }
@@ -909,6 +898,8 @@ struct Run {
     const float* embase_p;
     long embase_step_stride;
     bool no_embed_tail;          // the call never runs the embedding-as-tail form (mdgen_sample_dopri5): prepare() skips its base rows
+    bool concurrent;             // a view whose launches run beside other views' on other streams: kernels that use the call's split
+                                 // scratch (one launch at a time) stay off meanwhile (for_each_view)
     float* h() const { return hp; }
     float* mod() const { return modp; }
 };
@@ -942,6 +933,25 @@ static Run sub_run(const Run& r, int b0, int Bs, hipStream_t stream) {
     if (r.embase_p) v.embase_p = r.embase_p + (long)b0 * r.L * kC;
     return v;
 }
+
+// The nv contiguous sub-batch views of a prepared call (plan_views), view i on stream i % ns (0: the call's own): fn(view, b0), b0 =
+// the view's first sample.  The launches that follow belong to the view (plan mode), until the loop ends.
+template <typename F>
+static int for_each_view(const Run& r, int nv, int ns, F&& fn) {
+    int b0 = 0, e = 0;
+    for (int i = 0; i < nv && !e; ++i) {
+        const int Bs = r.B / nv + (i < r.B % nv ? 1 : 0);
+        Run v = sub_run(r, b0, Bs, i % ns == 0 ? r.s : r.c->side[i % ns - 1]);
+        v.concurrent = ns > 1;
+        if (g_dry) g_dry->view = i;
+        e = fn(v, b0);
+        b0 += Bs;
+    }
+    if (g_dry) g_dry->view = -1;
+    return e;
+}
+// token rows of the largest of them: what prepare() sizes its decisions by
+static long largest_view_rows(const Run& r, int nv) { return (long)((r.B + nv - 1) / nv) * r.T * r.L; }
 
 // ---- fp32-operand path (option "precision" = 32; kernels in k_fp32.hip) ------------------------------------------
 struct F32Bufs {
@@ -1007,6 +1017,101 @@ static int check_launch_rows(long nrows) {
     return 0;
 }
 
+// One launch of the bf16 sampler: the enqueue between a hipEvent pair on its stream (profiling mode only), then the launch check;
+// in plan mode only its class is recorded.  cls == nullptr: a set-up kernel outside the profile classes.
+template <typename F>
+static int launch(const Run& r, const char* cls, F&& enqueue) {
+    if (!g_dry) {
+        ProfRec pr{cls, nullptr, nullptr};
+        const bool prof = r.c->prof_on && cls && hipEventCreate(&pr.a) == hipSuccess && hipEventCreate(&pr.b) == hipSuccess &&
+                          hipEventRecord(pr.a, r.s) == hipSuccess;
+        enqueue();
+        if (prof && hipEventRecord(pr.b, r.s) == hipSuccess) r.c->prof.push_back(pr);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail((int)e, "kernel launch failed: %s (%s)", hipGetErrorString(e), cls ? cls : "set-up");
+        if (const char* m = k32_take_launch_error()) return fail(-7, "internal: %s (%s)", m, cls ? cls : "set-up");
+    } else if (cls) {
+        g_dry->rec.emplace_back(g_dry->view, cls);
+    }
+    return 0;
+}
+
+// ---- kernel forms: which instantiation each launch of a sub-layer takes (kernels.h), decided here, ONCE, from the options, the
+// device and the launch's size; the launchers switch on the form and the profile class (tag) is a function of (position, form) ----
+enum class Pos { Ipa, ResL, TimeT };   // attention sub-layer: IPA stack (residue axis), trunk residue axis, trunk temporal axis
+static const char* by_pos(Pos p, const char* ipa, const char* l, const char* t) { return p == Pos::Ipa ? ipa : p == Pos::ResL ? l : t; }
+static const char* tag(Pos p, QkvForm f) {
+    switch (f) {
+    case QkvForm::Small:
+    case QkvForm::Panel4: return by_pos(p, "ipa.ln_qkv", "ln_qkv_L", "ln_qkv_T");
+    case QkvForm::Panel8: return by_pos(p, "ipa.ln_qkv@p8", "ln_qkv_L@p8", "ln_qkv_T@p8");
+    case QkvForm::Panel8Split: return by_pos(p, "ipa.ln_qkv@p8x2", "ln_qkv_L@p8x2", "ln_qkv_T@p8x2");
+    case QkvForm::Panel8SplitHalf: return by_pos(p, "ipa.ln_qkv@h32x2", "ln_qkv_L@h32x2", "ln_qkv_T@h32x2");
+    case QkvForm::PreProj: return "projL_qkvT";
+    }
+    return nullptr;
+}
+static const char* tag(Pos p, Attn4Form f) {
+    switch (f) {
+    case Attn4Form::AttnOnly: return by_pos(p, "ipa.ln_qkv", "ln_qkv_L", "ln_qkv_T");
+    case Attn4Form::Fused: return by_pos(p, "ipa.ln_qkv", "attn_L_fused", "ln_qkv_T");
+    case Attn4Form::FusedHalf: return by_pos(p, "ipa.ln_qkv@h32", "attn_L_fused@h32", "ln_qkv_T@h32");
+    }
+    return nullptr;
+}
+static const char* tag(Pos p, FlashProjForm f) {
+    switch (f) {
+    case FlashProjForm::Q64: return by_pos(p, "ipa.flash_proj@q64", "flash_proj_L@q64", "flash_proj_T@q64");
+    case FlashProjForm::Q128: return by_pos(p, "ipa.flash_proj@q128", "flash_proj_L@q128", "flash_proj_T@q128");
+    }
+    return nullptr;
+}
+static const char* tag_flash(Pos p) { return by_pos(p, "ipa.flash", "flash_L", "flash_T"); }
+static const char* tag_proj(Pos p) { return by_pos(p, "ipa.proj", "proj_L", "proj_T"); }
+static const char* tag(bool trunk, MlpRowsForm f) {
+    if (!trunk) return "ipa.mlp";
+    switch (f) {
+    case MlpRowsForm::Plain: return "mlp";
+    case MlpRowsForm::Fold: return "mlp@fold";
+    case MlpRowsForm::FoldFinal: return "mlp@fold+final";
+    case MlpRowsForm::FoldFinalEmbed: return "mlp@fold+final+embed";
+    }
+    return nullptr;
+}
+static const char* tag(bool trunk, MlpPanelForm f) {
+    switch (f) {
+    case MlpPanelForm::W4: return trunk ? "mlp@p4" : "ipa.mlp@p4";
+    case MlpPanelForm::W8: return trunk ? "mlp@p8" : "ipa.mlp@p8";
+    case MlpPanelForm::W8Split: return trunk ? "mlp@p8x3" : "ipa.mlp@p8x3";
+    case MlpPanelForm::PreW4: return trunk ? "proj_mlp@p4" : "ipa.mlp@p4";
+    case MlpPanelForm::PreW8: return trunk ? "proj_mlp@p8" : "ipa.mlp@p8";
+    case MlpPanelForm::PreW8Split: return trunk ? "proj_mlp@p8x3" : "ipa.mlp@p8x3";
+    }
+    return nullptr;
+}
+
+// Four or eight waves per 64-row panel (k_mlp / k_mlp8, k_ln_qkv<false> / k_ln_qkv8): eight where a launch is at most one
+// workgroup per CU, unless option panel_waves forces one form
+static int panel_waves_for(const mdgen_ctx* c, long panels) {
+    return c->opt_panel_waves == 4 || c->opt_panel_waves == 8 ? c->opt_panel_waves : (panels <= c->ncu ? 8 : 4);
+}
+// q, k, v of a tiled-attention sub-layer in a launch of its own.  Far below one workgroup per CU (option small_split): q, k | v
+// over a workgroup pair per panel, and 32 positions per pair where even those fit one per CU (B = 1 at T 1000: 256)
+static QkvForm qkv_form(const mdgen_ctx* c, const AxisMap& ax) {
+    const long panels = (long)ax.nseq * ((ax.len + kPanel - 1) / kPanel);
+    if (panel_waves_for(c, panels) != 8) return QkvForm::Panel4;
+    if (!c->opt_small_split || 2 * panels > c->ncu) return QkvForm::Panel8;
+    return 2L * ax.nseq * ((ax.len + 31) / 32) <= c->ncu ? QkvForm::Panel8SplitHalf : QkvForm::Panel8Split;
+}
+// the whole L == 4 residue sub-layer in one kernel: launches of at most one 32-row workgroup per CU (B <= 2 at T 1000, the IPA
+// stack) take half panels, twice the CUs at work (option small_split)
+static Attn4Form attn4_fused_form(const mdgen_ctx* c, long nrows) {
+#ifdef MDGEN_DEV_ATTN4_FULL   // (experiment build, A/B of the half-panel form: every launch takes 64-row panels)
+    return Attn4Form::Fused;
+#else
+    return c->opt_small_split && (nrows + 31) / 32 <= c->ncu ? Attn4Form::FusedHalf : Attn4Form::Fused;
+#endif
+}
 // k_flash_proj owns a (sequence, 64-query chunk) for all 16 heads: four times the work of a k_flash workgroup, a quarter of the
 // workgroups.  It pays where those still fill the chip (cfg-2: 1024 per launch, ATLAS: 1000 / 1024); small launches (B = 1: 64,
 // the IPA stack) keep the finer-grained k_flash + projection.
@@ -1014,23 +1119,125 @@ static int check_launch_rows(long nrows) {
 static bool flash_proj_on(const mdgen_ctx* c, const AxisMap& ax) {
     return c->opt_precision == 16 && (c->opt_flash_proj == 2 || (c->opt_flash_proj == 1 && flash_proj_jobs(ax) >= 2L * c->ncu));
 }
+// ... in the 128-row form where that still gives every CU a workgroup (cfg-2: 256 per sub-batch stream)
+static FlashProjForm flash_proj_form(const mdgen_ctx* c, const AxisMap& ax) {
+    const long jobs8 = (long)ax.nseq * ((ax.len + 2 * kPanel - 1) / (2 * kPanel));
+    const int w = c->opt_flash_proj_form ? c->opt_flash_proj_form : (ax.len >= 512 && jobs8 >= c->ncu) ? 8 : 4;
+    return w == 8 ? FlashProjForm::Q128 : FlashProjForm::Q64;
+}
 
-// `defer`: when non-null and the sub-layer takes the tiled-attention path, its out-projection is NOT launched; *defer receives
-// what the fused kernel (k_mlp_rows<NW, true>) needs to run it ahead of the MLP (a_bf16 stays null otherwise).
-static int attn_sublayer(const Run& r, const MhaW& m, float* h, long nrows, const AxisMap& ax, const ModMap& mm,
-                         int shift, int scale, int gate, const MaskMap& mk, bool residue_axis, bool trunk,
-                         ProjParams* defer = nullptr, const ProjParams* pre = nullptr) {
-    if (int e = check_launch_rows(nrows)) return e;
-    const char* c_qkv = !trunk ? "ipa.ln_qkv" : residue_axis ? "ln_qkv_L" : "ln_qkv_T";
-    const char* c_att = !trunk ? "ipa.flash" : residue_axis ? "flash_L" : "flash_T";
-    const char* c_prj = !trunk ? "ipa.proj" : residue_axis ? "proj_L" : "proj_T";
+// An attention sub-layer's launches.  Quad: L == 4, the 5-key attention inside the q / k / v kernel (k_ln_qkv_attn4); Micro: L <= 8,
+// attention inside the projection kernel (k_proj<2>); Tiled: k_ln_qkv -> k_flash -> out-projection, or k_flash_proj.
+enum class AttnPath { Quad, Micro, Tiled };
+// Where the out-projection + gated residual runs: a k_proj launch of its own, the kernel that computed the attention
+// (k_ln_qkv_attn4<true>, k_flash_proj), the prologue of the temporal sub-layer's q / k / v kernel, the prologue of the panel MLP kernel
+enum class ProjAt { Own, Attention, NextQkv, Mlp };
+struct AttnPlan {
+    Pos pos;
+    AttnPath path;
+    Attn4Form a4;        // Quad
+    QkvForm qkv;         // Micro, Tiled
+    bool flash_proj;     // Tiled: one k_flash_proj launch (form fp) instead of k_flash + projection
+    FlashProjForm fp;
+    ProjAt proj;
+};
+// pre: the previous sub-layer left its out-projection to this one's q / k / v kernel; later: where a tiled sub-layer without
+// k_flash_proj may leave its own (Own, NextQkv or Mlp)
+static AttnPlan attn_plan(const mdgen_ctx* c, Pos pos, const AxisMap& ax, long nrows, bool pre, ProjAt later) {
+    AttnPlan a{pos, AttnPath::Tiled, Attn4Form::AttnOnly, QkvForm::Small, false, FlashProjForm::Q64, ProjAt::Own};
+    const bool small = pos != Pos::TimeT && ax.len <= 8;
+    if (small && ax.len == 4 && c->opt_residue_l4 != 0) {
+        a.path = AttnPath::Quad;
+        if (c->opt_residue_l4 == 2) {   // whole residue-axis sub-layer in one kernel (option 1: attention only)
+            a.a4 = attn4_fused_form(c, nrows);
+            a.proj = ProjAt::Attention;
+        }
+    } else if (small) {
+        a.path = AttnPath::Micro;
+    } else {
+        a.qkv = pre ? QkvForm::PreProj : qkv_form(c, ax);
+        a.flash_proj = flash_proj_on(c, ax);
+        a.fp = flash_proj_form(c, ax);
+        a.proj = a.flash_proj ? ProjAt::Attention : later;
+    }
+    return a;
+}
+
+// The MLP block's launch: the row-owner kernel (rows) or the 64-row panel kernel
+struct MlpPlan {
+    bool trunk, use_rows;
+    MlpRowsForm rows;
+    MlpPanelForm panel;
+};
+// pre: the temporal sub-layer left its out-projection to this launch (ProjAt::Mlp; only where the panel kernel runs anyway);
+// rows: the form a row-owner launch takes (trunk: a Fold* form where the call's gate-folded streams are packed); concurrent: other
+// views' launches run beside this one; split_cap: panels the call's split scratch covers; trace: this launch records phase stamps
+static MlpPlan mlp_plan(const mdgen_ctx* c, bool trunk, long nrows, bool pre, MlpRowsForm rows, bool concurrent, long split_cap, bool trace) {
+    MlpPlan m{trunk, !pre && mlp_uses_rows(c, nrows), rows, MlpPanelForm::W4};
+    if (m.use_rows) return m;
+    const long panels = (nrows + kPanel - 1) / kPanel;
+    // (the phase stamps stay with k_mlp: a traced launch takes the four-wave kernel)
+    const int pw = trace ? 4 : panel_waves_for(c, panels);
+    // the split form: the call's scratch serves one launch at a time (one stream), and its workgroups must meet in one L2
+    const bool split = pw == 8 && c->opt_small_split && c->xcd_round_robin && !concurrent && panels * kMlpSplit <= c->ncu && panels <= split_cap;
+    m.panel = split ? (pre ? MlpPanelForm::PreW8Split : MlpPanelForm::W8Split)
+              : pw == 8 ? (pre ? MlpPanelForm::PreW8 : MlpPanelForm::W8)
+                        : (pre ? MlpPanelForm::PreW4 : MlpPanelForm::W4);
+    return m;
+}
+
+// One trunk layer: residue-axis attention, temporal attention, MLP
+struct LayerPlan {
+    AttnPlan l, t;
+    MlpPlan mlp;
+};
+// in an Euler rollout on view `r`, the last layer's (folded, row-owner) MLP launch writes the next step's token embedding
+static bool embed_tail_runs(const Run& r) { return r.fold_ready && mlp_uses_rows(r.c, r.N) && r.c->opt_mlp_tail && r.embase_p; }
+// last: the trunk's last layer, without a residual-stream trace: its folded MLP launch may run the FinalLayer as its tail (then h is
+// NOT written), and with embed_next the next step's embedding; trace: the layer's MLP launch records phase stamps
+static LayerPlan layer_plan(const Run& r, const AxisMap& axL, const AxisMap& axT, bool last, bool embed_next, bool trace) {
+    const mdgen_ctx* c = r.c;
+    LayerPlan p;
+    const MlpRowsForm rows = !r.fold_ready                   ? MlpRowsForm::Plain
+                             : !(last && c->opt_mlp_tail)    ? MlpRowsForm::Fold
+                             : embed_next                    ? MlpRowsForm::FoldFinalEmbed
+                                                             : MlpRowsForm::FoldFinal;
+    // residue axis on the tiled-attention path (L > 8): its out-projection may run inside the temporal q / k / v kernel
+    const bool fuse_lt = c->opt_fuse_proj_qkv && r.L > 8 && r.T > 8;
+    p.l = attn_plan(c, Pos::ResL, axL, r.N, false, fuse_lt ? ProjAt::NextQkv : ProjAt::Own);
+    // the temporal out-projection inside the panel MLP kernel, where that kernel runs
+    const bool fuse = c->opt_fuse_proj == 3 && !mlp_uses_rows(c, r.N);
+    p.t = attn_plan(c, Pos::TimeT, axT, r.N, p.l.proj == ProjAt::NextQkv, fuse ? ProjAt::Mlp : ProjAt::Own);
+    p.mlp = mlp_plan(c, true, r.N, p.t.proj == ProjAt::Mlp, rows, r.concurrent, r.split_cap, trace);
+    return p;
+}
+
+// The rows a sub-layer updates and its three adaLN chunks (shift, scale, gate = chunk0, +1, +2)
+struct Rows {
+    float* h;
+    long nrows;
+    ModMap mm;
+    int chunk0;
+};
+// An out-projection + gated residual that another sub-layer's kernel runs in its prologue (attention output rows: r.obufp)
+struct OutProj {
+    const bf16x8* w;
+    const float* bias;
+    int gate_chunk;
+};
+
+// pre: the previous sub-layer's out-projection (pl.qkv == QkvForm::PreProj only)
+static int attn_sublayer(const Run& r, const AttnPlan& pl, const MhaW& m, const Rows& rw, const AxisMap& ax, const MaskMap& mk,
+                         const OutProj& pre) {
+    if (int e = check_launch_rows(rw.nrows)) return e;
+    const int gate = rw.chunk0 + 2;
     QkvParams q{};
-    q.h = h;
-    q.nrows = nrows;
+    q.h = rw.h;
+    q.nrows = rw.nrows;
     q.ax = ax;
-    q.mm = mm;
-    q.shift_chunk = shift;
-    q.scale_chunk = scale;
+    q.mm = rw.mm;
+    q.shift_chunk = rw.chunk0;
+    q.scale_chunk = rw.chunk0 + 1;
     q.wq = m.wq;
     q.wk = m.wk;
     q.bq = m.bq;
@@ -1040,17 +1247,19 @@ static int attn_sublayer(const Run& r, const MhaW& m, float* h, long nrows, cons
     q.kf = r.kfp;
     q.vf = r.vfp;
     q.qkv_small = (__bf16*)r.qfp;
-    q.panels_per_seq = (ax.len + kPanel - 1) / kPanel;
+    const int ppanel = pl.qkv == QkvForm::Panel8SplitHalf ? 32 : kPanel;   // positions per workgroup (pair)
+    q.panels_per_seq = (ax.len + ppanel - 1) / ppanel;
     ProjParams p{};
-    p.h = h;
-    p.nrows = nrows;
-    p.mm = mm;
+    p.h = rw.h;
+    p.nrows = rw.nrows;
+    p.mm = rw.mm;
     p.gate_chunk = gate;
     p.gated = 1;
     p.w = m.wo;
     p.bias = m.bo;
-    const bool small = residue_axis && ax.len <= 8;
-    if (small && ax.len == 4 && r.c->opt_residue_l4 != 0) {
+    p.a_bf16 = r.obufp;
+    switch (pl.path) {
+    case AttnPath::Quad:
         // L == 4: the 5-key attention runs inside the QKV kernel (quad-local), which writes the attention output
         q.wv = m.wv_small;
         q.bv = m.bv_small;
@@ -1058,38 +1267,27 @@ static int attn_sublayer(const Run& r, const MhaW& m, float* h, long nrows, cons
         q.bias_v = m.bias_v;
         q.mk = mk;
         q.obuf = r.obufp;
-        if (r.c->opt_residue_l4 == 2) {   // whole residue-axis sub-layer in one kernel (option 1: attention only)
-            q.h_rw = h;
+        if (pl.proj == ProjAt::Attention) {
+            q.h_rw = rw.h;
             q.wo = m.wo;
             q.bo = m.bo;
             q.gate_chunk = gate;
-            // launches of at most one 32-row workgroup per CU (B <= 2 at T 1000, the IPA stack): half panels, twice the CUs at work
-            // (k_ln_qkv_attn4<true, true>; option small_split; tag "@h32")
-            const bool half = r.c->opt_small_split && (nrows + 31) / 32 <= r.c->ncu;
-            const std::string cls = std::string(residue_axis && trunk ? "attn_L_fused" : c_qkv) + (half ? "@h32" : "");
-            { ProfScope ps(r.c, r.c->intern(cls), r.s); if (!g_dry) launch_ln_qkv_attn4(q, true, r.s, half); }
-            LAUNCHCHK();
-        } else {
-            { ProfScope ps(r.c, c_qkv, r.s); if (!g_dry) launch_ln_qkv_attn4(q, false, r.s); }
-            LAUNCHCHK();
-            p.a_bf16 = r.obufp;
-            { ProfScope ps(r.c, c_prj, r.s); if (!g_dry) launch_proj(p, 0, r.s); }
-            LAUNCHCHK();
         }
-    } else if (small) {
+        if (int e = launch(r, tag(pl.pos, pl.a4), [&] { launch_ln_qkv_attn4(q, pl.a4, r.s); })) return e;
+        break;
+    case AttnPath::Micro:
         q.wv = m.wv_small;
         q.bv = m.bv_small;
-        { ProfScope ps(r.c, c_qkv, r.s); if (!g_dry) launch_ln_qkv(q, true, r.s); }
-        LAUNCHCHK();
+        if (int e = launch(r, tag(pl.pos, pl.qkv), [&] { launch_ln_qkv(q, pl.qkv, r.s); })) return e;
+        p.a_bf16 = nullptr;
         p.qkv_small = q.qkv_small;
         p.ax = ax;
         p.mk = mk;
         p.bias_k = m.bias_k;
         p.bias_v = m.bias_v;
         p.rope = r.c->rope;
-        { ProfScope ps(r.c, c_prj, r.s); if (!g_dry) launch_proj(p, 2, r.s); }
-        LAUNCHCHK();
-    } else {
+        return launch(r, tag_proj(pl.pos), [&] { launch_proj(p, ProjMode::MicroAttn, r.s); });
+    case AttnPath::Tiled: {
         q.wv = m.wv_flash;
         q.bv = m.bv_flash;
         q.bias_k = m.bias_k;   // written into key slot `len` of the K / V^T fragments by the sequence's last panel
@@ -1097,28 +1295,16 @@ static int attn_sublayer(const Run& r, const MhaW& m, float* h, long nrows, cons
         q.mk = mk;   // key-validity words for the attention kernel, in the slack behind the V^T fragments
         q.vmask = (uint32_t*)(q.vf + flash_vmask_offset(ax.nseq, ax.ntile()));
         q.vmask_stride = flash_vmask_stride(ax.ntile());
-        if (pre && pre->a_bf16) {
-            // the PREVIOUS sub-layer's deferred out-projection + gated residual runs in this kernel's panels first (option
-            // fuse_proj_qkv): its rows then come back from L2 for the LayerNorm instead of from HBM in a launch of their own
-            q.obuf = const_cast<__bf16*>(pre->a_bf16);
-            q.wo = pre->w;
-            q.bo = pre->bias;
-            q.gate_chunk = pre->gate_chunk;
-            q.h_rw = h;
-            { ProfScope ps(r.c, "projL_qkvT", r.s); if (!g_dry) launch_ln_qkv(q, false, r.s, true); }
-            LAUNCHCHK();
-        } else {
-            // (profile class "...@p8": the eight-wave form ran -- tests assert which kernel a launch took)
-            const int pw = panel_waves_for((long)ax.nseq * q.panels_per_seq, r.c->opt_panel_waves, r.c->ncu);
-            const bool split = pw == 8 && r.c->opt_small_split && 2L * ax.nseq * q.panels_per_seq <= r.c->ncu;
-            // ... and 32 positions per workgroup pair where even those fit one per CU (B = 1 at T 1000: 256; tag "@h32x2")
-            const int pps32 = (ax.len + 31) / 32;
-            const bool half = split && 2L * ax.nseq * pps32 <= r.c->ncu;
-            if (half) q.panels_per_seq = pps32;
-            const std::string cls = std::string(c_qkv) + (half ? "@h32x2" : split ? "@p8x2" : pw == 8 ? "@p8" : "");
-            { ProfScope ps(r.c, r.c->intern(cls), r.s); if (!g_dry) launch_ln_qkv(q, false, r.s, false, pw, split, half); }
-            LAUNCHCHK();
+        if (pl.qkv == QkvForm::PreProj) {
+            // the PREVIOUS sub-layer's out-projection + gated residual runs in this kernel's panels first (option fuse_proj_qkv):
+            // its rows then come back from L2 for the LayerNorm instead of from HBM in a launch of their own
+            q.obuf = r.obufp;
+            q.wo = pre.w;
+            q.bo = pre.bias;
+            q.gate_chunk = pre.gate_chunk;
+            q.h_rw = rw.h;
         }
+        if (int e = launch(r, tag(pl.pos, pl.qkv), [&] { launch_ln_qkv(q, pl.qkv, r.s); })) return e;
         FlashParams f{};
         f.ax = ax;
         f.mk = mk;
@@ -1133,142 +1319,108 @@ static int attn_sublayer(const Run& r, const MhaW& m, float* h, long nrows, cons
         f.rotate = r.c->opt_flash_rotate;
         f.vmask = q.vmask;
         f.vmask_stride = q.vmask_stride;
-        if (flash_proj_on(r.c, ax)) {
-            // attention of all heads + out-projection + gated residual in one launch: nothing is deferred, no k_proj<0>
+        if (pl.flash_proj) {   // attention of all heads + out-projection + gated residual in one launch
             FlashProjParams fp{};
             fp.f = f;
-            fp.h = h;
-            fp.mm = mm;
+            fp.h = rw.h;
+            fp.mm = rw.mm;
             fp.gate_chunk = gate;
             fp.wo = m.wo;
             fp.bo = m.bo;
-            // the 128-row form where it still gives every CU a workgroup (cfg-2: 256 per sub-batch stream)
-            const long jobs8 = (long)ax.nseq * ((ax.len + 2 * kPanel - 1) / (2 * kPanel));
-            const int form = r.c->opt_flash_proj_form ? r.c->opt_flash_proj_form : (ax.len >= 512 && jobs8 >= r.c->ncu) ? 8 : 4;
-            // (class "...@q64" / "@q128": which fused form ran -- k_flash_proj / k_flash_proj8; tests assert it)
-            const std::string cls = std::string(!trunk ? "ipa.flash_proj" : residue_axis ? "flash_proj_L" : "flash_proj_T") + (form == 8 ? "@q128" : "@q64");
-            { ProfScope ps(r.c, r.c->intern(cls), r.s); if (!g_dry) launch_flash_proj(fp, form, r.s); }
-            LAUNCHCHK();
-            return 0;
+            return launch(r, tag(pl.pos, pl.fp), [&] { launch_flash_proj(fp, pl.fp, r.s); });
         }
-        { ProfScope ps(r.c, c_att, r.s); if (!g_dry) launch_flash(f, r.s); }
-        LAUNCHCHK();
-        p.a_bf16 = f.obuf;
-        if (defer) {
-            *defer = p;
-            return 0;
-        }
-        { ProfScope ps(r.c, c_prj, r.s); if (!g_dry) launch_proj(p, 0, r.s); }
-        LAUNCHCHK();
+        if (int e = launch(r, tag_flash(pl.pos), [&] { launch_flash(f, r.s); })) return e;
+        break;
     }
-    return 0;
+    }
+    if (pl.proj != ProjAt::Own) return 0;
+    return launch(r, tag_proj(pl.pos), [&] { launch_proj(p, ProjMode::Plain, r.s); });
 }
 
-// Row-owner kernel: one workgroup = 4 waves x 32 rows and one workgroup per CU, so it needs ~200 workgroups to fill the
-// chip; smaller launches (IPA stack, B = 1 tetrapeptides) stay on the 64-row panel kernel.
-static bool mlp_uses_rows(const mdgen_ctx* c, long nrows) {
-    const long tiles = (nrows + 31) / 32;
-    return c->opt_mlp_path == 2 || (c->opt_mlp_path == 1 && tiles >= 3L * c->ncu);   // (768 row tiles = 192 four-wave workgroups on the 256-CU part)
-}
-
-// `proj`: a deferred out-projection (attn_sublayer) to run in the panel MLP kernel's prologue, ahead of the MLP
-// `fold_sl` >= 0 (trunk, gate fold active): index step * nl + layer of the folded stream / b2' of this launch
-// `tail` (last trunk layer; nullable): the FinalLayer's parameters; *tail_done = true when the launch ran it (folded row-owner form only)
-static int mlp_sublayer(const Run& r, const FfnW& f, float* h, long nrows, const ModMap& mm, int shift, int scale,
-                        int gate, bool trunk, const ProjParams* proj = nullptr, long fold_sl = -1,
-                        const FinalParams* tail = nullptr, bool* tail_done = nullptr, int next_step = -1, bool* next_h0 = nullptr) {
-    if (int e = check_launch_rows(nrows)) return e;
-    const bool panel_fused = proj && proj->a_bf16;   // (only handed a projection when the panel kernel runs anyway)
-    if (!panel_fused && mlp_uses_rows(r.c, nrows)) {
+// Operands of the forms only a trunk MLP launch takes
+struct MlpTrunk {
+    long fold_sl;                // index step * nl + layer of the launch's folded stream / b2'
+    const FinalParams* fin;      // the FinalLayer (FoldFinal, FoldFinalEmbed)
+    int next_step;               // the step whose token embedding the launch writes (FoldFinalEmbed)
+    unsigned long long* trace;   // phase stamps of this launch, or null (mdgen_profile_phase_trace)
+    long trace_cap;
+};
+// pre: the temporal sub-layer's out-projection (panel forms Pre* only); tk: null for the IPA stack
+static int mlp_sublayer(const Run& r, const MlpPlan& pl, const FfnW& f, const Rows& rw, const OutProj& pre, const MlpTrunk* tk) {
+    if (int e = check_launch_rows(rw.nrows)) return e;
+    if (pl.use_rows) {
         MlpRowsParams q{};
-        bool tail_on = false, emb_on = false;
-        q.h = h;
-        q.nrows = nrows;
-        q.mm = mm;
-        q.shift_chunk = shift;
-        q.scale_chunk = scale;
-        q.gate_chunk = gate;
+        q.h = rw.h;
+        q.nrows = rw.nrows;
+        q.mm = rw.mm;
+        q.shift_chunk = rw.chunk0;
+        q.scale_chunk = rw.chunk0 + 1;
+        q.gate_chunk = rw.chunk0 + 2;
         q.wstream = (const unsigned char*)f.wstream;
         q.b1 = f.b1;
         q.b2 = f.b2;
-        if (fold_sl >= 0 && r.fold_ready && mm.group_stride == 0 && mm.step_stride == 0) {
-            q.wstream = r.fold_streams + (size_t)fold_sl * kFoldStreamBytes;
-            q.b2g = r.fold_b2g + (size_t)fold_sl * kC;
-            if (tail && tail_done && r.c->opt_mlp_tail && tail->mm.group_stride == 0 && tail->mm.step_stride == 0) {
-                tail_on = true;
-                q.tail_w = r.c->wfin_k;
-                q.tail_b = tail->bias;
-                q.tail_mod = tail->mm.mod;
-                q.tail_D = tail->D;
-                q.tail_euler = tail->euler;
-                q.tail_dt = tail->dt;
-                q.tail_x = tail->x;
-                q.tail_out = tail->out;
-                *tail_done = true;
-                if (next_step >= 0 && next_h0 && r.embase_p && tail->euler) {   // ... and the next step's token embedding
-                    q.emb_wl_hi = r.c->wl_hi;
-                    q.emb_wl_lo = r.c->wl_lo;
-                    q.emb_wc_hi = r.c->wc_hi;
-                    q.emb_wc_lo = r.c->wc_lo;
-                    q.emb_base = r.embase_p + (long)next_step * r.embase_step_stride;
-                    q.emb_mdelta = r.c->mask_delta;
-                    q.emb_xcond = r.x_cond;
-                    q.emb_cmask = r.x_cond_mask;
-                    q.emb_T = r.T;
-                    q.emb_L = r.L;
-                    emb_on = true;
-                    *next_h0 = true;
-                }
-            }
+        if (pl.rows != MlpRowsForm::Plain) {
+            q.wstream = r.fold_streams + (size_t)tk->fold_sl * kFoldStreamBytes;
+            q.b2g = r.fold_b2g + (size_t)tk->fold_sl * kC;
         }
-        if (trunk && r.c->phase_trace) {   // one-shot: the next trunk MLP launch records its phase stamps
-            q.trace = r.c->phase_trace;
-            q.trace_cap = r.c->phase_trace_cap;
-            r.c->phase_trace = nullptr;
+        if (pl.rows == MlpRowsForm::FoldFinal || pl.rows == MlpRowsForm::FoldFinalEmbed) {
+            const FinalParams* tail = tk->fin;
+            q.tail_w = r.c->wfin_k;
+            q.tail_b = tail->bias;
+            q.tail_mod = tail->mm.mod;
+            q.tail_D = tail->D;
+            q.tail_euler = tail->euler;
+            q.tail_dt = tail->dt;
+            q.tail_x = tail->x;
+            q.tail_out = tail->out;
         }
-        // (class "mlp@fold": the folded form ran -- tests assert it)
-        // ("mlp@fold+final": ... with the FinalLayer + Euler update as its tail)
-        { ProfScope ps(r.c, !trunk ? "ipa.mlp" : emb_on ? "mlp@fold+final+embed" : tail_on ? "mlp@fold+final" : q.b2g ? "mlp@fold" : "mlp", r.s); if (!g_dry) launch_mlp_rows(q, r.s); }
-        LAUNCHCHK();
-        return 0;
+        if (pl.rows == MlpRowsForm::FoldFinalEmbed) {   // ... and the next step's token embedding
+            q.emb_wl_hi = r.c->wl_hi;
+            q.emb_wl_lo = r.c->wl_lo;
+            q.emb_wc_hi = r.c->wc_hi;
+            q.emb_wc_lo = r.c->wc_lo;
+            q.emb_base = r.embase_p + (long)tk->next_step * r.embase_step_stride;
+            q.emb_mdelta = r.c->mask_delta;
+            q.emb_xcond = r.x_cond;
+            q.emb_cmask = r.x_cond_mask;
+            q.emb_T = r.T;
+            q.emb_L = r.L;
+        }
+        if (tk && tk->trace) {
+            q.trace = tk->trace;
+            q.trace_cap = tk->trace_cap;
+        }
+        return launch(r, tag(pl.trunk, pl.rows), [&] { launch_mlp_rows(q, pl.rows, r.s); });
     }
     MlpParams p{};
-    if (panel_fused) {   // the deferred out-projection runs in the panel kernel's prologue
-        p.o = proj->a_bf16;
-        p.wo = proj->w;
-        p.bo = proj->bias;
-        p.gate_chunk_o = proj->gate_chunk;
+    const bool fused = pl.panel == MlpPanelForm::PreW4 || pl.panel == MlpPanelForm::PreW8 || pl.panel == MlpPanelForm::PreW8Split;
+    if (fused) {   // the temporal out-projection runs in the panel kernel's prologue
+        p.o = r.obufp;
+        p.wo = pre.w;
+        p.bo = pre.bias;
+        p.gate_chunk_o = pre.gate_chunk;
     }
-    p.h = h;
-    p.nrows = nrows;
-    p.mm = mm;
-    p.shift_chunk = shift;
-    p.scale_chunk = scale;
-    p.gate_chunk = gate;
+    p.h = rw.h;
+    p.nrows = rw.nrows;
+    p.mm = rw.mm;
+    p.shift_chunk = rw.chunk0;
+    p.scale_chunk = rw.chunk0 + 1;
+    p.gate_chunk = rw.chunk0 + 2;
     p.w1 = f.w1;
     p.w2 = f.w2;
     p.b1 = f.b1;
     p.b2 = f.b2;
-    if (trunk && r.c->phase_trace) {   // one-shot: the next trunk MLP launch records its phase stamps
-        p.trace = r.c->phase_trace;
-        p.trace_cap = r.c->phase_trace_cap;
-        r.c->phase_trace = nullptr;
+    if (tk && tk->trace) {
+        p.trace = tk->trace;
+        p.trace_cap = tk->trace_cap;
     }
-    const long panels = (nrows + kPanel - 1) / kPanel;
-    const int pw = p.trace ? 4 : panel_waves_for(panels, r.c->opt_panel_waves, r.c->ncu);
-    // the split form: the context's scratch serves one launch at a time (one stream), and its workgroups must meet in one L2
-    const bool split = pw == 8 && r.c->opt_small_split && r.c->xcd_round_robin && r.c->live_streams <= 1 &&
-                       panels * kMlpSplit <= r.c->ncu && panels <= r.split_cap;
-    if (split) {
+    if (pl.panel == MlpPanelForm::W8Split || pl.panel == MlpPanelForm::PreW8Split) {
         ++r.c->n_split_launches;
         p.part = r.split_part;
         p.hupd = r.split_hupd;
         p.counters = r.split_counters;
     }
-    const std::string cls = std::string(!trunk ? "ipa.mlp" : p.o ? "proj_mlp" : "mlp") + (split ? "@p8x3" : pw == 8 ? "@p8" : "@p4");
-    { ProfScope ps(r.c, r.c->intern(cls), r.s); if (!g_dry) launch_mlp(p, r.s, pw); }
-    LAUNCHCHK();
-    return 0;
+    return launch(r, tag(pl.trunk, pl.panel), [&] { launch_mlp(p, pl.panel, r.s); });
 }
 
 // IPA stack for all prepared steps at once (latent_model.py:175-210): tokens (step, b, l).
@@ -1276,8 +1428,7 @@ static int ipa_stack(const Run& r, float* hbuf, const float* rel7, const float* 
                      const float* trans) {
     mdgen_ctx* c = r.c;
     const int G = r.S * r.B;
-    if (!g_dry) launch_ipa_init(c->aa_emb, r.aatype, rel7, w7, b7, hbuf, G, r.B, r.L, r.s);
-    LAUNCHCHK();
+    if (int e = launch(r, nullptr, [&] { launch_ipa_init(c->aa_emb, r.aatype, rel7, w7, b7, hbuf, G, r.B, r.L, r.s); })) return e;
     AxisMap ax{G, r.L, G, 0, r.L, 1};
     MaskMap mk{(const float*)(r.ws + r.lay.mask_bl), (long)r.B * r.L};
     for (int i = 0; i < c->nl; ++i) {
@@ -1319,8 +1470,7 @@ static int ipa_stack(const Run& r, float* hbuf, const float* rel7, const float* 
         lp.bias = w.bproj;
         lp.out = (float*)(r.ws + r.lay.ipa_proj);
         lp.nout = kIpaProj;
-        { ProfScope ps(c, "ipa.ln_linear", r.s); if (!g_dry) launch_ln_linear(lp, r.s); }
-        LAUNCHCHK();
+        if (int e = launch(r, "ipa.ln_linear", [&] { launch_ln_linear(lp, r.s); })) return e;
         IpaAttnParams ap{};
         ap.proj = lp.out;
         ap.rot = rot;
@@ -1331,8 +1481,7 @@ static int ipa_stack(const Run& r, float* hbuf, const float* rel7, const float* 
         ap.ngroups = G;
         ap.B = r.B;
         ap.L = r.L;
-        { ProfScope ps(c, "ipa.point_attn", r.s); if (!g_dry) launch_ipa_attn(ap, r.s); }
-        LAUNCHCHK();
+        if (int e = launch(r, "ipa.point_attn", [&] { launch_ipa_attn(ap, r.s); })) return e;
         ProjParams pp{};
         pp.h = hbuf;
         pp.nrows = r.Mp;
@@ -1341,10 +1490,11 @@ static int ipa_stack(const Run& r, float* hbuf, const float* rel7, const float* 
         pp.w = w.wout;
         pp.bias = w.bout;
         pp.a_bf16 = ap.feat;
-        { ProfScope ps(c, "ipa.linear_out", r.s); if (!g_dry) launch_proj(pp, 1, r.s); }
-        LAUNCHCHK();
-        if (int e = attn_sublayer(r, w.mha_l, hbuf, r.Mp, ax, mm, 0, 1, 2, mk, true, false)) return e;
-        if (int e = mlp_sublayer(r, w.ffn, hbuf, r.Mp, mm, 3, 4, 5, false)) return e;
+        if (int e = launch(r, "ipa.linear_out", [&] { launch_proj(pp, ProjMode::Linear, r.s); })) return e;
+        const OutProj none{};
+        if (int e = attn_sublayer(r, attn_plan(c, Pos::Ipa, ax, r.Mp, false, ProjAt::Own), w.mha_l, Rows{hbuf, r.Mp, mm, 0}, ax, mk, none)) return e;
+        const MlpPlan mp = mlp_plan(c, false, r.Mp, false, MlpRowsForm::Plain, r.concurrent, r.split_cap, false);
+        if (int e = mlp_sublayer(r, mp, w.ffn, Rows{hbuf, r.Mp, mm, 3}, none, nullptr)) return e;
     }
     return 0;
 }
@@ -1361,19 +1511,16 @@ static int prepare(Run& r, const float* t_dev, const float* t_host, long view_ro
     HIPCHK(hipMemsetAsync(r.ws + r.lay.kf, 0, r.lay.obuf - r.lay.kf, r.s));
     if (t_dev) {
         if (r.t_shared && r.B > 1) return fail(-2, "device t rows require t_shared == 0 or B == 1");
-        if (!g_dry) launch_temb(t_dev, R, c->d.time_multiplier, c->t_w0, c->t_b0, c->t_w2, c->t_b2, silu, r.s);
-        LAUNCHCHK();
+        if (int e = launch(r, nullptr, [&] { launch_temb(t_dev, R, c->d.time_multiplier, c->t_w0, c->t_b0, c->t_w2, c->t_b2, silu, r.s); })) return e;
     } else {
         // the (tiny) host time grid travels as kernel arguments: capturable, no host buffer lifetime issue
         float* tg = (float*)(r.ws + r.lay.tgrid);
-        if (!g_dry) launch_write_floats(t_host, r.S, tg, r.s);
-        LAUNCHCHK();
-        if (!g_dry) launch_temb(tg, r.S, c->d.time_multiplier, c->t_w0, c->t_b0, c->t_w2, c->t_b2, silu, r.s);
-        LAUNCHCHK();
+        if (int e = launch(r, nullptr, [&] { launch_write_floats(t_host, r.S, tg, r.s); })) return e;
+        if (int e = launch(r, nullptr, [&] { launch_temb(tg, r.S, c->d.time_multiplier, c->t_w0, c->t_b0, c->t_w2, c->t_b2, silu, r.s); })) return e;
     }
-    { ProfScope ps(c, "adaln_table", r.s); if (!g_dry) launch_adaln(silu, R, c->ada_w, c->ada_b, c->modrow, r.mod(), r.s); }
-    LAUNCHCHK();
-    r.fold_ready = r.fold_streams && mlp_uses_rows(c, view_rows);
+    if (int e = launch(r, "adaln_table", [&] { launch_adaln(silu, R, c->ada_w, c->ada_b, c->modrow, r.mod(), r.s); })) return e;
+    // (view_rows, not N: see fold_on.  r.S may be below the S the workspace was carved for: ode.inc)
+    r.fold_ready = r.fold_streams && fold_on(c, view_rows, r.t_shared, r.S);
     if (r.fold_ready) {   // the steps' MLP gates folded into per-(step, layer) fc2 streams (t_shared: R == S rows)
         int goff[8];
         const float *w2[8], *b2[8];
@@ -1384,8 +1531,7 @@ static int prepare(Run& r, const float* t_dev, const float* t_host, long view_ro
             b2[i] = c->trunk[i].ffn.b2;
             base[i] = c->trunk[i].ffn.wstream;
         }
-        { ProfScope ps(c, "fold_pack", r.s); if (!g_dry) launch_pack_fold(r.mod(), r.mod_step_stride, r.S, c->nl, goff, w2, b2, base, c->mlp_tab, (bf16x8*)r.fold_streams, r.fold_b2g, r.s); }
-        LAUNCHCHK();
+        if (int e = launch(r, "fold_pack", [&] { launch_pack_fold(r.mod(), r.mod_step_stride, r.S, c->nl, goff, w2, b2, base, c->mlp_tab, (bf16x8*)r.fold_streams, r.fold_b2g, r.s); })) return e;
     }
     // mask_bl[b][l] = mask[b][0][l]  (latent_model.py:246 passes mask[:,0])
     HIPCHK(hipMemcpy2DAsync(r.ws + r.lay.mask_bl, (size_t)r.L * 4, r.mask, (size_t)r.T * r.L * 4, (size_t)r.L * 4, r.B,
@@ -1404,34 +1550,34 @@ static int prepare(Run& r, const float* t_dev, const float* t_host, long view_ro
         if (r.rel7_in) {
             HIPCHK(hipMemcpyAsync(rel, r.rel7_in, (size_t)2 * BL * 7 * 4, hipMemcpyDeviceToDevice, r.s));
         } else {
-            if (!g_dry) launch_rel7(r.start_rot, r.start_trans, r.end_rot, r.end_trans, rel, BL, r.s);
-            if (!g_dry) launch_rel7(r.end_rot, r.end_trans, r.start_rot, r.start_trans, rel + BL * 7, BL, r.s);
-            LAUNCHCHK();
+            if (int e = launch(r, nullptr, [&] {
+                    launch_rel7(r.start_rot, r.start_trans, r.end_rot, r.end_trans, rel, BL, r.s);
+                    launch_rel7(r.end_rot, r.end_trans, r.start_rot, r.start_trans, rel + BL * 7, BL, r.s);
+                }))
+                return e;
         }
         float* h2 = (float*)(r.ws + r.lay.h_ipa);
         // x_r stream runs on the start frames, x_f stream on the end frames (latent_model.py:203-205)
         if (int e = ipa_stack(r, ipa_out, rel + BL * 7, c->wr7, c->br7, r.start_rot, r.start_trans)) return e;
         if (int e = ipa_stack(r, h2, rel, c->wf7, c->bf7, r.end_rot, r.end_trans)) return e;
-        if (!g_dry) launch_add_inplace(ipa_out, h2, r.Mp * kC, r.s);
-        LAUNCHCHK();
+        if (int e = launch(r, nullptr, [&] { launch_add_inplace(ipa_out, h2, r.Mp * kC, r.s); })) return e;
     }
-    if (r.fold_ready && c->opt_mlp_tail == 2 && r.S > 1 && !r.no_embed_tail) {
+    if (r.fold_ready && embed_base_on(c, view_rows, r.t_shared, r.S) && !r.no_embed_tail) {
         // steps 1 .. S-1 take their token embedding from the previous step's last MLP launch (rows_embed_tail): the part of it that does
         // not depend on x, per (step, b, l)
         float* eb = (float*)(r.ws + r.lay.embase);
-        { ProfScope ps(c, "embed_base", r.s); if (!g_dry) launch_embed_base(c->bl, c->bc, c->mask_emb, c->d.abs_pos_emb ? c->pos_embed : nullptr, ipa_out, r.S, r.B * r.L, r.L, eb, r.s); }
-        LAUNCHCHK();
+        if (int e = launch(r, "embed_base", [&] { launch_embed_base(c->bl, c->bc, c->mask_emb, c->d.abs_pos_emb ? c->pos_embed : nullptr, ipa_out, r.S, r.B * r.L, r.L, eb, r.s); })) return e;
         r.embase_p = eb;
     }
     return 0;
 }
 
 // One network evaluation at prepared step `step`: x -> velocity (out) or Euler update of x in place.
-// h0_ready: the previous step's last MLP launch has already written this step's token embedding into h (no k_embed launch);
-// next_h0 (nullable): ask this step to do the same for step + 1; *next_h0 = true when it did.
-static int denoise_step(const Run& r, int step, float* x, float* out, int euler, float dt, float* trace_h, bool h0_ready = false,
-                        bool* next_h0 = nullptr) {
+// euler: the call runs the prepared steps 0 .. S-1 in order on this view (euler_steps).  Where embed_tail_runs(r), step i's last MLP
+// launch then writes step i + 1's token embedding into h, and step i + 1 launches no k_embed.
+static int denoise_step(const Run& r, int step, float* x, float* out, int euler, float dt, float* trace_h) {
     mdgen_ctx* c = r.c;
+    const bool embed_tail = euler && embed_tail_runs(r);
     float* h = r.h();
     EmbedParams e{};
     e.x = x;
@@ -1451,10 +1597,8 @@ static int denoise_step(const Run& r, int step, float* x, float* out, int euler,
     e.T = r.T;
     e.L = r.L;
     e.D = r.D;
-    if (!h0_ready) {
-        { ProfScope ps(c, "embed", r.s); if (!g_dry) launch_embed(e, r.s); }
-        LAUNCHCHK();
-    }
+    if (!(embed_tail && step > 0))
+        if (int er = launch(r, "embed", [&] { launch_embed(e, r.s); })) return er;
     const size_t hbytes = (size_t)r.N * kC * 4;
     if (trace_h) HIPCHK(hipMemcpyAsync(trace_h, h, hbytes, hipMemcpyDeviceToDevice, r.s));
     const float* modstep = r.mod() + (long)step * r.mod_step_stride;
@@ -1492,32 +1636,25 @@ static int denoise_step(const Run& r, int step, float* x, float* out, int euler,
     f.dt = dt;
     f.x = x;
     f.out = out;
-    bool tail_done = false;
+    // the one-shot phase trace (mdgen_profile_phase_trace) goes to the first trunk MLP launch after it was armed: taken here
+    MlpTrunk tk{0, &f, step + 1, c->phase_trace, c->phase_trace_cap};
+    c->phase_trace = nullptr;
+    bool final_done = false;
     for (int i = 0; i < c->nl; ++i) {
         const TrunkW& w = c->trunk[i];
-        ModMap mm{modstep + c->trunk_off(i), r.T * r.L, r.B, 0, r.mod_group_stride};
-        // residue axis on the tiled-attention path (L > 8): its out-projection may run inside the temporal q / k / v kernel
-        ProjParams def_l{};
-        {
-            const bool fuse_lt = c->opt_fuse_proj_qkv && r.L > 8 && r.T > 8;
-            if (int er = attn_sublayer(r, w.mha_l, h, r.N, axL, mm, 0, 1, 2, mk, true, true, fuse_lt ? &def_l : nullptr)) return er;
-        }
-        ProjParams deferred{};
-        const bool fuse = c->opt_fuse_proj == 3 && !mlp_uses_rows(c, r.N);
-        if (int er = attn_sublayer(r, w.mha_t, h, r.N, axT, mm, 3, 4, 5, mk, false, true, fuse ? &deferred : nullptr,
-                                   def_l.a_bf16 ? &def_l : nullptr))
-            return er;
-        // the last layer's MLP may run the FinalLayer as its tail (then h is NOT written: not with a residual-stream trace)
-        const bool last = i == c->nl - 1 && !trace_h;
-        if (int er = mlp_sublayer(r, w.ffn, h, r.N, mm, 6, 7, 8, true, &deferred, (long)step * c->nl + i,
-                                  last ? &f : nullptr, last ? &tail_done : nullptr, next_h0 ? step + 1 : -1, next_h0))
-            return er;
+        const ModMap mm{modstep + c->trunk_off(i), r.T * r.L, r.B, 0, r.mod_group_stride};
+        const LayerPlan pl = layer_plan(r, axL, axT, i == c->nl - 1 && !trace_h, embed_tail && step + 1 < r.S, tk.trace != nullptr);
+        const OutProj proj_l{w.mha_l.wo, w.mha_l.bo, 2}, proj_t{w.mha_t.wo, w.mha_t.bo, 5};
+        if (int er = attn_sublayer(r, pl.l, w.mha_l, Rows{h, r.N, mm, 0}, axL, mk, OutProj{})) return er;
+        if (int er = attn_sublayer(r, pl.t, w.mha_t, Rows{h, r.N, mm, 3}, axT, mk, proj_l)) return er;
+        tk.fold_sl = (long)step * c->nl + i;
+        if (int er = mlp_sublayer(r, pl.mlp, w.ffn, Rows{h, r.N, mm, 6}, proj_t, &tk)) return er;
+        tk.trace = nullptr;
+        final_done = pl.mlp.use_rows && (pl.mlp.rows == MlpRowsForm::FoldFinal || pl.mlp.rows == MlpRowsForm::FoldFinalEmbed);
         if (trace_h) HIPCHK(hipMemcpyAsync(trace_h + (size_t)(i + 1) * r.N * kC, h, hbytes, hipMemcpyDeviceToDevice, r.s));
     }
-    if (tail_done) return 0;
-    { ProfScope ps(c, "final_euler", r.s); if (!g_dry) launch_final(f, r.s); }
-    LAUNCHCHK();
-    return 0;
+    if (final_done) return 0;
+    return launch(r, "final_euler", [&] { launch_final(f, r.s); });
 }
 
 static int make_run(Run* r, mdgen_ctx* c, const mdgen_shape* sh, int S, int t_shared, void* ws, size_t ws_bytes,
@@ -1532,7 +1669,6 @@ static int make_run(Run* r, mdgen_ctx* c, const mdgen_shape* sh, int S, int t_sh
     if (c->opt_precision == 32 && !c->opt_keep_fp32) return fail(-6, "precision 32 requires option keep_fp32_weights");
     if (c->opt_precision == 32)
         if (int e = check_f32_weights(c)) return e;
-    if (g_dry && c->opt_precision == 32) return fail(-2, "the dispatch plan covers the bf16 path");
     r->c = c;
     r->B = sh->B;
     r->T = sh->T;
@@ -1570,11 +1706,26 @@ static int make_run(Run* r, mdgen_ctx* c, const mdgen_shape* sh, int S, int t_sh
     r->embase_p = nullptr;
     r->embase_step_stride = (long)sh->B * sh->L * kC;
     r->no_embed_tail = false;
+    r->concurrent = false;
     if (fold_on(c, r->N, t_shared, S)) {
         r->fold_streams = r->ws + r->lay.fold;
         r->fold_b2g = (float*)(r->fold_streams + (size_t)S * c->nl * kFoldStreamBytes);
     }
     return 0;
+}
+
+// mdgen_denoiser_forward on a made run: the batch's views one after the other on the caller's stream
+static int forward_body(Run& r, const float* x, const float* t, float* out, float* trace_h, float* trace_ipa) {
+    const int nv = r.c->opt_precision == 32 ? 1 : plan_views(r.B, r.T, r.L, 1);
+    if (nv == 0) return fail(-2, "sample too large for one launch");
+    if (int e = prepare(r, t, nullptr, largest_view_rows(r, nv))) return e;
+    if (trace_ipa)
+        HIPCHK(hipMemcpyAsync(trace_ipa, r.ws + r.lay.ipa_out, (size_t)r.B * r.L * kC * 4, hipMemcpyDeviceToDevice, r.s));
+    if (nv > 1 && trace_h) return fail(-2, "trace_h is not available when the batch needs more than one launch view");
+    return for_each_view(r, nv, 1, [&](const Run& v, int b0) {
+        const long o = (long)b0 * r.T * r.L * r.D;
+        return denoise_step(v, 0, const_cast<float*>(x) + o, out + o, 0, 0.f, trace_h);
+    });
 }
 
 extern "C" int32_t mdgen_denoiser_forward(mdgen_ctx* c, const mdgen_shape* sh, const float* x, const float* t,
@@ -1596,21 +1747,7 @@ extern "C" int32_t mdgen_denoiser_forward(mdgen_ctx* c, const mdgen_shape* sh, c
     r.x_cond = x_cond;
     r.x_cond_mask = x_cond_mask;
     r.aatype = aatype;
-    const int nv = c->opt_precision == 32 ? 1 : plan_views(r.B, r.T, r.L, 1);
-    if (int e = prepare(r, t, nullptr, nv > 0 ? (long)((r.B + nv - 1) / nv) * r.T * r.L : r.N)) return e;
-    if (trace_ipa)
-        HIPCHK(hipMemcpyAsync(trace_ipa, r.ws + r.lay.ipa_out, (size_t)r.B * r.L * kC * 4, hipMemcpyDeviceToDevice, r.s));
-    if (nv <= 1) return denoise_step(r, 0, const_cast<float*>(x), out, 0, 0.f, trace_h);
-    if (trace_h) return fail(-2, "trace_h is not available when the batch needs more than one launch view");
-    int b0 = 0;
-    for (int i = 0; i < nv; ++i) {   // sequential sub-batch views on the caller's stream
-        const int Bs = r.B / nv + (i < r.B % nv ? 1 : 0);
-        const Run v = sub_run(r, b0, Bs, r.s);
-        const long o = (long)b0 * r.T * r.L * r.D;
-        if (int e = denoise_step(v, 0, const_cast<float*>(x) + o, out + o, 0, 0.f, nullptr)) return e;
-        b0 += Bs;
-    }
-    return 0;
+    return forward_body(r, x, t, out, trace_h, trace_ipa);
 }
 
 // torch.linspace(0, 1, n) in fp32 (ATen RangeFactories: symmetric evaluation around the midpoint)
@@ -1635,44 +1772,23 @@ static int n_streams(const Run& r) {
 }
 
 static int euler_steps(const Run& v, const std::vector<float>& tg, float* x) {
-    if (g_dry) g_dry->push_back("@view");   // plan mode: a sub-batch view's launches start here
-    bool h0_ready = false;
-    for (int i = 0; i < v.S; ++i) {
-        const float dt = tg[i + 1] - tg[i];
-        bool next = false;
-        if (int e = denoise_step(v, i, x, nullptr, 1, dt, nullptr, h0_ready, i + 1 < v.S ? &next : nullptr)) return e;
-        h0_ready = next;
-    }
+    for (int i = 0; i < v.S; ++i)
+        if (int e = denoise_step(v, i, x, nullptr, 1, tg[i + 1] - tg[i], nullptr)) return e;
     return 0;
 }
 
-
 static int euler_body(const Run& r_in, const std::vector<float>& tg, float* x) {
     Run r = r_in;
+    mdgen_ctx* c = r.c;
     const int ns = n_streams(r);
     // >= ns views; more when a view would exceed kMaxViewTokens (the fp32 kernels index with 64 bits: one view)
-    const int nv = r.c->opt_precision == 32 ? 1 : plan_views(r.B, r.T, r.L, ns);
+    const int nv = c->opt_precision == 32 ? 1 : plan_views(r.B, r.T, r.L, ns);
     if (nv == 0) return fail(-2, "sample too large for one launch");
-    if (int e = prepare(r, nullptr, tg.data(), (long)((r.B + nv - 1) / nv) * r.T * r.L)) return e;
-    r.c->live_streams = 1;
-    if (nv == 1) return euler_steps(r, tg, x);
-    struct Live {   // the views below run on ns streams at once: kernels that use context-owned scratch stay off meanwhile
-        mdgen_ctx* c;
-        ~Live() { c->live_streams = 1; }
-    } live{r.c};
-    r.c->live_streams = ns;
+    if (int e = prepare(r, nullptr, tg.data(), largest_view_rows(r, nv))) return e;
     // contiguous sub-batch views, view i on stream i % ns (fork after the shared preparation, join at the end)
-    mdgen_ctx* c = r.c;
     if (ns > 1) HIPCHK(hipEventRecord(c->ev_fork, r.s));
     for (int i = 1; i < ns; ++i) HIPCHK(hipStreamWaitEvent(c->side[i - 1], c->ev_fork, 0));
-    int b0 = 0;
-    for (int i = 0; i < nv; ++i) {
-        const int Bs = r.B / nv + (i < r.B % nv ? 1 : 0);
-        hipStream_t st = (i % ns) == 0 ? r.s : c->side[i % ns - 1];
-        const Run v = sub_run(r, b0, Bs, st);
-        if (int e = euler_steps(v, tg, x + (long)b0 * r.T * r.L * r.D)) return e;
-        b0 += Bs;
-    }
+    if (int e = for_each_view(r, nv, ns, [&](const Run& v, int b0) { return euler_steps(v, tg, x + (long)b0 * r.T * r.L * r.D); })) return e;
     for (int i = 1; i < ns; ++i) {
         HIPCHK(hipEventRecord(c->ev_join[i - 1], c->side[i - 1]));
         HIPCHK(hipStreamWaitEvent(r.s, c->ev_join[i - 1], 0));
@@ -1828,12 +1944,41 @@ extern "C" int32_t mdgen_rollout_euler(mdgen_ctx* c, const mdgen_shape* sh, int3
 // ---------------------------------------------------------------------------------------------
 // dispatch plan (host only)
 // ---------------------------------------------------------------------------------------------
-// Which kernel classes a call of this shape launches, and how often: the sampler's orchestration code above, run in plan mode
-// (g_dry) on a context that owns no device memory.  mode 0: mdgen_sample_euler as the product runs it (sub-batch streams);
+// Which kernel classes a call of this shape launches, and how often: the entry points' own bodies (euler_body, forward_body,
+// ode.inc dopri5_attempt) run in plan mode (g_dry) on a context that owns no device memory -- the same view loop, layer plans and
+// launch sites as a real call.  mode 0: mdgen_sample_euler as the product runs it (sub-batch streams);
 // 1: mdgen_denoiser_forward; 2: mdgen_sample_euler as mdgen_profile_enable sees it (one stream); 3: mdgen_denoiser_forward with trace_h;
-// 4: one attempted step of mdgen_sample_dopri5 (ode.inc dopri5_plan; n_steps is ignored).  options: "name=value,..."
+// 4: one attempted step of mdgen_sample_dopri5 (n_steps is ignored).  options: "name=value,..."
 // (mdgen_ctx_set_option names).  ncu / xcd_round_robin: what mdgen_ctx_create would have found on the device.
-// Output: {"streams": n, "prepare": {"<class>": launches, ...}, "views": [{"B": samples of the view, "classes": {...}}, ...]}.
+// Output: {"streams": n, "prepare": {"<class>": launches, ...}, "views": [{"B": samples of the view, "classes": {...}}, ...]}
+// and, mode 4, "integrator": {"ode_combine": 6, "ode_norm": 1}.
+static int plan_json(const DryPlan& plan, int B, int nv, int ns, bool integrator, char* buf, size_t buflen) {
+    std::map<std::string, long> prep, integ;
+    std::vector<std::map<std::string, long>> views(nv);
+    for (const auto& k : plan.rec) {
+        if (k.first >= nv) return fail(-7, "internal: %d views planned, view %d recorded", nv, k.first);
+        ++(std::strncmp(k.second, "ode_", 4) == 0 ? integ : k.first < 0 ? prep : views[k.first])[k.second];
+    }
+    auto dump = [](const std::map<std::string, long>& agg) {
+        std::string o = "{";
+        bool first = true;
+        for (const auto& kv : agg) {
+            o += std::string(first ? "" : ", ") + "\"" + kv.first + "\": " + std::to_string(kv.second);
+            first = false;
+        }
+        return o + "}";
+    };
+    std::string js = "{\"streams\": " + std::to_string(ns) + ", \"prepare\": " + dump(prep) + ", \"views\": [";
+    for (int i = 0; i < nv; ++i)
+        js += std::string(i ? ", " : "") + "{\"B\": " + std::to_string(B / nv + (i < B % nv ? 1 : 0)) + ", \"classes\": " + dump(views[i]) + "}";
+    js += "]";
+    if (integrator) js += ", \"integrator\": " + dump(integ);
+    js += "}";
+    if (js.size() + 1 > buflen) return fail(-7, "plan buffer too small");
+    std::memcpy(buf, js.c_str(), js.size() + 1);
+    return 0;
+}
+
 extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_steps, int32_t mode, int32_t tps_condition,
                                              int32_t num_layers, int32_t ncu, int32_t xcd_round_robin, const char* options,
                                              char* buf, size_t buflen) {
@@ -1864,62 +2009,31 @@ extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_st
         if (eq == std::string::npos) return fail(-2, "options: name=value[,name=value...]");
         if (int e = mdgen_ctx_set_option(c, kv.substr(0, eq).c_str(), std::atoi(kv.c_str() + eq + 1))) return e;
     }
-    std::vector<std::string> plan;
+    DryPlan plan;
     struct Dry {
-        Dry(std::vector<std::string>* p) { g_dry = p; }
+        Dry(DryPlan* p) { g_dry = p; }
         ~Dry() { g_dry = nullptr; }
     } dry(&plan);
-    if (mode == 4) return dopri5_plan(c, sh, plan, buf, buflen);
     const bool fwd = mode == 1 || mode == 3;
-    const int S = fwd ? 1 : n_steps;
+    const int S = mode == 4 ? ode::kStages : fwd ? 1 : n_steps;
     const int t_shared = fwd ? (sh->B == 1 ? 1 : 0) : 1;
     Run r{};
     if (int e = make_run(&r, c, sh, S, t_shared, (void*)4096, (size_t)1 << 60, nullptr)) return e;
     float* fake = (float*)4096;   // never dereferenced: plan mode launches nothing
     r.mask = r.start_rot = r.start_trans = r.end_rot = r.end_trans = r.x_cond = fake;
     r.x_cond_mask = r.aatype = (const int64_t*)fake;
-    int ns = 1, nv = 1;
-    if (fwd) {
-        nv = plan_views(r.B, r.T, r.L, 1);
-        if (int e = prepare(r, fake, nullptr, (long)((r.B + nv - 1) / nv) * r.T * r.L)) return e;
-        int b0 = 0;
-        for (int i = 0; i < nv; ++i) {
-            const int Bs = r.B / nv + (i < r.B % nv ? 1 : 0);
-            const Run v = nv > 1 ? sub_run(r, b0, Bs, r.s) : r;
-            plan.push_back("@view");
-            if (int e = denoise_step(v, 0, fake, fake, 0, 0.f, mode == 3 ? fake : nullptr)) return e;
-            b0 += Bs;
-        }
+    const int ns = fwd || mode == 4 ? 1 : n_streams(r);
+    const int nv = plan_views(r.B, r.T, r.L, ns);
+    if (mode == 4) {
+        if (int e = dopri5_plan(r, nv)) return e;
+    } else if (fwd) {
+        if (int e = forward_body(r, fake, fake, fake, mode == 3 ? fake : nullptr, nullptr)) return e;
     } else {
         std::vector<float> tg;
         linspace01(S + 1, &tg);
-        ns = n_streams(r);
-        nv = plan_views(r.B, r.T, r.L, ns);
         if (int e = euler_body(r, tg, fake)) return e;
     }
-    // {"streams": n, "prepare": {class: launches}, "views": [{"B": samples, "classes": {class: launches}}, ...]}
-    auto dump = [](const std::map<std::string, long>& agg) {
-        std::string o = "{";
-        bool first = true;
-        for (const auto& kv : agg) {
-            o += std::string(first ? "" : ", ") + "\"" + kv.first + "\": " + std::to_string(kv.second);
-            first = false;
-        }
-        return o + "}";
-    };
-    std::vector<std::map<std::string, long>> parts(1);
-    for (const auto& k : plan) {
-        if (k == "@view") parts.emplace_back();
-        else ++parts.back()[k];
-    }
-    if ((int)parts.size() != nv + 1) return fail(-7, "internal: %d views planned, %d recorded", nv, (int)parts.size() - 1);
-    std::string js = "{\"streams\": " + std::to_string(ns) + ", \"prepare\": " + dump(parts[0]) + ", \"views\": [";
-    for (int i = 0; i < nv; ++i)
-        js += std::string(i ? ", " : "") + "{\"B\": " + std::to_string(r.B / nv + (i < r.B % nv ? 1 : 0)) + ", \"classes\": " + dump(parts[i + 1]) + "}";
-    js += "]}";
-    if (js.size() + 1 > buflen) return fail(-7, "plan buffer too small");
-    std::memcpy(buf, js.c_str(), js.size() + 1);
-    return 0;
+    return plan_json(plan, r.B, nv, ns, mode == 4, buf, buflen);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -753,15 +753,14 @@ void launch_flash(const FlashParams& p, hipStream_t s) {
 // jobs of a fused launch: one workgroup per (sequence, 64-query chunk)
 long flash_proj_jobs(const AxisMap& ax) { return (long)ax.nseq * ((ax.len + kPanel - 1) / kPanel); }
 
-void launch_flash_proj(const FlashProjParams& p, int form, hipStream_t s) {
+void launch_flash_proj(const FlashProjParams& p, FlashProjForm form, hipStream_t s) {
     const int nseq8 = (p.f.ax.nseq + 7) / 8;   // sequences, in groups of 8 (one per XCD)
-    if (form == 8) {
-        const int nqc = (p.f.ax.len + 2 * kPanel - 1) / (2 * kPanel);
-        hipLaunchKernelGGL(k_flash_proj8, dim3(nseq8 * nqc * 8), dim3(512), 0, s, p);
-        return;
+    const int rows = form == FlashProjForm::Q128 ? 2 * kPanel : kPanel;
+    const dim3 grid(nseq8 * ((p.f.ax.len + rows - 1) / rows) * 8);
+    switch (form) {   // (cases in the kernels' order of appearance in the code object)
+    case FlashProjForm::Q128: hipLaunchKernelGGL(k_flash_proj8, grid, dim3(512), 0, s, p); return;
+    case FlashProjForm::Q64: hipLaunchKernelGGL(k_flash_proj, grid, dim3(256), 0, s, p); return;
     }
-    const int nqc = (p.f.ax.len + kPanel - 1) / kPanel;
-    hipLaunchKernelGGL(k_flash_proj, dim3(nseq8 * nqc * 8), dim3(256), 0, s, p);
 }
 
 }  // namespace mdg

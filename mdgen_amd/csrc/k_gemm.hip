@@ -1402,26 +1402,18 @@ __global__ __launch_bounds__(256, 2) void k_final(const FinalParams p) {
 }
 
 // ---- launchers ----------------------------------------------------------------------------------
-// Four or eight waves per 64-row panel (k_mlp / k_mlp8, k_ln_qkv<false> / k_ln_qkv8): eight where a launch is at most one
-// workgroup per CU, unless the caller forces one form (option panel_waves: 4 / 8).
-int panel_waves_for(long grid, int forced, int ncu) { return forced == 4 || forced == 8 ? forced : (grid <= ncu ? 8 : 4); }
-
-void launch_ln_qkv(const QkvParams& p, bool small, hipStream_t s, bool pre, int waves, bool split, bool half) {
-    if (pre) {
-        const int grid = p.ax.nseq * p.panels_per_seq;
-        hipLaunchKernelGGL((k_ln_qkv<false, true>), dim3(grid), dim3(256), 0, s, p);
+void launch_ln_qkv(const QkvParams& p, QkvForm form, hipStream_t s) {
+    const int grid = p.ax.nseq * p.panels_per_seq;
+    switch (form) {   // (cases in the kernels' order of appearance in the code object)
+    case QkvForm::PreProj:
+        if (!p.obuf || !p.wo || !p.bo || !p.h_rw) g_k32_launch_error = "launch_ln_qkv: PreProj without the out-projection's operands";
+        else hipLaunchKernelGGL((k_ln_qkv<false, true>), dim3(grid), dim3(256), 0, s, p);
         return;
-    }
-    if (small) {
-        const int grid = (int)((p.nrows + kPanel - 1) / kPanel);
-        hipLaunchKernelGGL(k_ln_qkv<true>, dim3(grid), dim3(256), 0, s, p);
-    } else {
-        const int grid = p.ax.nseq * p.panels_per_seq;
-        // (half: p.panels_per_seq counts 32-position panels)
-        if (waves == 8 && split && half) hipLaunchKernelGGL((k_ln_qkv8<true, true>), dim3(2 * grid), dim3(512), 0, s, p);
-        else if (waves == 8 && split) hipLaunchKernelGGL(k_ln_qkv8<true>, dim3(2 * grid), dim3(512), 0, s, p);
-        else if (waves == 8) hipLaunchKernelGGL(k_ln_qkv8<false>, dim3(grid), dim3(512), 0, s, p);
-        else hipLaunchKernelGGL(k_ln_qkv<false>, dim3(grid), dim3(256), 0, s, p);
+    case QkvForm::Small: hipLaunchKernelGGL(k_ln_qkv<true>, dim3((unsigned)((p.nrows + kPanel - 1) / kPanel)), dim3(256), 0, s, p); return;
+    case QkvForm::Panel8SplitHalf: hipLaunchKernelGGL((k_ln_qkv8<true, true>), dim3(2 * grid), dim3(512), 0, s, p); return;
+    case QkvForm::Panel8Split: hipLaunchKernelGGL(k_ln_qkv8<true>, dim3(2 * grid), dim3(512), 0, s, p); return;
+    case QkvForm::Panel8: hipLaunchKernelGGL(k_ln_qkv8<false>, dim3(grid), dim3(512), 0, s, p); return;
+    case QkvForm::Panel4: hipLaunchKernelGGL(k_ln_qkv<false>, dim3(grid), dim3(256), 0, s, p); return;
     }
 }
 // placement probe (mdgen_ctx_create): the XCD each of `nblocks` workgroups ran on (HW_REG_XCC_ID, 4 bits)
@@ -1430,36 +1422,51 @@ __global__ void k_xcc_probe(int* out) {
 }
 void launch_xcc_probe(int* out, int nblocks, hipStream_t s) { hipLaunchKernelGGL(k_xcc_probe, dim3(nblocks), dim3(64), 0, s, out); }
 
-void launch_ln_qkv_attn4(const QkvParams& p, bool fuse_proj, hipStream_t s, bool half) {
+void launch_ln_qkv_attn4(const QkvParams& p, Attn4Form form, hipStream_t s) {
     const int grid = (int)((p.nrows + kPanel - 1) / kPanel);
-#ifdef MDGEN_DEV_ATTN4_FULL   // (experiment build, A/B of the half-panel form: every launch takes 64-row panels, whatever the tag says)
-    half = false;
-#endif
-    if (fuse_proj && half) hipLaunchKernelGGL((k_ln_qkv_attn4<true, true>), dim3((unsigned)((p.nrows + 31) / 32)), dim3(256), 0, s, p);
-    else if (fuse_proj) hipLaunchKernelGGL((k_ln_qkv_attn4<true>), dim3(grid), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((k_ln_qkv_attn4<false>), dim3(grid), dim3(256), 0, s, p);
-}
-void launch_proj(const ProjParams& p, int mode, hipStream_t s) {
-    const int grid = (int)((p.nrows + kPanel - 1) / kPanel);
-    if (mode == 0) hipLaunchKernelGGL(k_proj<0>, dim3(grid), dim3(256), 0, s, p);
-    else if (mode == 1) hipLaunchKernelGGL(k_proj<1>, dim3(grid), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(k_proj<2>, dim3(grid), dim3(256), 0, s, p);
-}
-void launch_mlp(const MlpParams& p, hipStream_t s, int waves) {
-    const int grid = (int)((p.nrows + kPanel - 1) / kPanel);
-    if (waves == 8 && !p.trace && p.part) {   // hidden chunks over kMlpSplit workgroups per panel (same XCD), last arriver finishes
-        const int g3 = (grid + 7) / 8 * 8 * kMlpSplit;
-        if (p.o) hipLaunchKernelGGL((k_mlp8<true, kMlpSplit>), dim3(g3), dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((k_mlp8<false, kMlpSplit>), dim3(g3), dim3(512), 0, s, p);
+    if (!p.obuf || (form != Attn4Form::AttnOnly && (!p.wo || !p.bo || !p.h_rw))) {
+        g_k32_launch_error = "launch_ln_qkv_attn4: the form's output / out-projection operands are missing";
         return;
     }
-    if (waves == 8 && !p.trace) {   // (the phase stamps stay with k_mlp: mdgen_profile_phase_trace selects the four-wave kernel)
-        if (p.o) hipLaunchKernelGGL((k_mlp8<true>), dim3(grid), dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((k_mlp8<false>), dim3(grid), dim3(512), 0, s, p);
+    switch (form) {   // (cases in the kernels' order of appearance in the code object)
+    case Attn4Form::FusedHalf: hipLaunchKernelGGL((k_ln_qkv_attn4<true, true>), dim3((unsigned)((p.nrows + 31) / 32)), dim3(256), 0, s, p); return;
+    case Attn4Form::Fused: hipLaunchKernelGGL((k_ln_qkv_attn4<true>), dim3(grid), dim3(256), 0, s, p); return;
+    case Attn4Form::AttnOnly: hipLaunchKernelGGL((k_ln_qkv_attn4<false>), dim3(grid), dim3(256), 0, s, p); return;
+    }
+}
+void launch_proj(const ProjParams& p, ProjMode mode, hipStream_t s) {
+    const int grid = (int)((p.nrows + kPanel - 1) / kPanel);
+    switch (mode) {
+    case ProjMode::Plain: hipLaunchKernelGGL(k_proj<0>, dim3(grid), dim3(256), 0, s, p); return;
+    case ProjMode::Linear: hipLaunchKernelGGL(k_proj<1>, dim3(grid), dim3(256), 0, s, p); return;
+    case ProjMode::MicroAttn: hipLaunchKernelGGL(k_proj<2>, dim3(grid), dim3(256), 0, s, p); return;
+    }
+}
+void launch_mlp(const MlpParams& p, MlpPanelForm form, hipStream_t s) {
+    const int grid = (int)((p.nrows + kPanel - 1) / kPanel);
+    const int g3 = (grid + 7) / 8 * 8 * kMlpSplit;   // split forms: hidden chunks over kMlpSplit workgroups per panel (same XCD), last arriver finishes
+    const bool pre = form == MlpPanelForm::PreW4 || form == MlpPanelForm::PreW8 || form == MlpPanelForm::PreW8Split;
+    const bool split = form == MlpPanelForm::W8Split || form == MlpPanelForm::PreW8Split;
+    if (pre != (p.o != nullptr) || (pre && (!p.wo || !p.bo))) {
+        g_k32_launch_error = "launch_mlp: the form and the out-projection operands disagree";
         return;
     }
-    if (p.o) hipLaunchKernelGGL((k_mlp<3, true>), dim3(grid), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((k_mlp<3>), dim3(grid), dim3(256), 0, s, p);
+    if (split != (p.part != nullptr) || (split && (!p.hupd || !p.counters))) {
+        g_k32_launch_error = "launch_mlp: the form and the split scratch disagree";
+        return;
+    }
+    if (p.trace && form != MlpPanelForm::W4 && form != MlpPanelForm::PreW4) {   // (the phase stamps stay with k_mlp)
+        g_k32_launch_error = "launch_mlp: a phase trace needs a four-wave form";
+        return;
+    }
+    switch (form) {   // (cases in the kernels' order of appearance in the code object)
+    case MlpPanelForm::PreW8Split: hipLaunchKernelGGL((k_mlp8<true, kMlpSplit>), dim3(g3), dim3(512), 0, s, p); return;
+    case MlpPanelForm::W8Split: hipLaunchKernelGGL((k_mlp8<false, kMlpSplit>), dim3(g3), dim3(512), 0, s, p); return;
+    case MlpPanelForm::PreW8: hipLaunchKernelGGL((k_mlp8<true>), dim3(grid), dim3(512), 0, s, p); return;
+    case MlpPanelForm::W8: hipLaunchKernelGGL((k_mlp8<false>), dim3(grid), dim3(512), 0, s, p); return;
+    case MlpPanelForm::PreW4: hipLaunchKernelGGL((k_mlp<3, true>), dim3(grid), dim3(256), 0, s, p); return;
+    case MlpPanelForm::W4: hipLaunchKernelGGL((k_mlp<3>), dim3(grid), dim3(256), 0, s, p); return;
+    }
 }
 void launch_ln_linear(const LnLinearParams& p, hipStream_t s) {
     const int grid = (int)((p.nrows + kPanel - 1) / kPanel);

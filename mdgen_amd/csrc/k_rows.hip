@@ -496,16 +496,28 @@ void launch_pack_stream(const float* w, int ld, int which, const int* tab, int n
                        rowmap);
 }
 
-void launch_mlp_rows(const MlpRowsParams& p, hipStream_t s) {
+void launch_mlp_rows(const MlpRowsParams& p, MlpRowsForm form, hipStream_t s) {
     constexpr int NW = 4;   // four waves per workgroup: the only form the orchestration launches
     // a 32-row tile never straddles two modulation groups: groups are whole tiles, or every group reads the same row
     const bool uni = p.mm.tokens_per_group % 32 == 0 || (p.mm.step_stride == 0 && p.mm.group_stride == 0);
     const long tiles = (p.nrows + 31) / 32;
     const dim3 g((unsigned)((tiles + NW - 1) / NW)), b(NW * 64);
-    if (p.b2g && p.tail_w) hipLaunchKernelGGL((k_mlp_rows<NW, true, true, true>), g, b, 0, s, p);
-    else if (p.b2g) hipLaunchKernelGGL((k_mlp_rows<NW, true, true>), g, b, 0, s, p);   // (the caller has checked: one modulation group)
-    else if (uni) hipLaunchKernelGGL((k_mlp_rows<NW, true>), g, b, 0, s, p);
-    else hipLaunchKernelGGL((k_mlp_rows<NW, false>), g, b, 0, s, p);
+    const bool fold = form != MlpRowsForm::Plain, tail = form == MlpRowsForm::FoldFinal || form == MlpRowsForm::FoldFinalEmbed;
+    // (FoldFinal and FoldFinalEmbed share an instantiation that tests emb_base: the operands must match the form exactly)
+    if (fold != (p.b2g != nullptr) || tail != (p.tail_w != nullptr) || (form == MlpRowsForm::FoldFinalEmbed) != (p.emb_base != nullptr) ||
+        (fold && (p.mm.step_stride != 0 || p.mm.group_stride != 0))) {
+        g_k32_launch_error = "launch_mlp_rows: the form and the fold / tail / embedding operands disagree";
+        return;
+    }
+    switch (form) {   // (cases in the kernels' order of appearance in the code object)
+    case MlpRowsForm::FoldFinal:
+    case MlpRowsForm::FoldFinalEmbed: hipLaunchKernelGGL((k_mlp_rows<NW, true, true, true>), g, b, 0, s, p); return;
+    case MlpRowsForm::Fold: hipLaunchKernelGGL((k_mlp_rows<NW, true, true>), g, b, 0, s, p); return;
+    case MlpRowsForm::Plain:
+        if (uni) hipLaunchKernelGGL((k_mlp_rows<NW, true>), g, b, 0, s, p);
+        else hipLaunchKernelGGL((k_mlp_rows<NW, false>), g, b, 0, s, p);
+        return;
+    }
 }
 
 }  // namespace mdg

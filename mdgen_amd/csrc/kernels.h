@@ -202,13 +202,41 @@ struct FloatChunk {
     int n;
 };
 
-int panel_waves_for(long grid, int forced, int ncu);   // 4 or 8 waves per 64-row panel for a launch of `grid` panels
-void launch_ln_qkv(const QkvParams& p, bool small, hipStream_t s, bool pre = false, int waves = 4, bool split = false, bool half = false);
+// Kernel forms: one value = one kernel instantiation.  The orchestration (api.hip) decides the form of a launch and fills the
+// operands the form reads; the launcher switches on it.  A form whose operands are missing launches nothing and leaves a message
+// for k32_take_launch_error.
+enum class QkvForm {
+    Small,             // k_ln_qkv<true>: SMALL layout (L <= 8)
+    Panel4,            // k_ln_qkv<false>: fragment layout, four waves per 64-row panel
+    Panel8,            // k_ln_qkv8<false>: eight waves
+    Panel8Split,       // k_ln_qkv8<true>: q, k | v over a workgroup pair
+    Panel8SplitHalf,   // k_ln_qkv8<true, true>: ... of 32 positions (panels_per_seq counts 32-position panels)
+    PreProj            // k_ln_qkv<false, true>: the previous sub-layer's out-projection + gated residual first (obuf, wo, bo, h_rw)
+};
+enum class Attn4Form {
+    AttnOnly,    // k_ln_qkv_attn4<false>: writes the attention output (obuf)
+    Fused,       // k_ln_qkv_attn4<true>: ... and runs the out-projection + gated residual (wo, bo, h_rw)
+    FusedHalf    // k_ln_qkv_attn4<true, true>: 32-row workgroups
+};
+enum class ProjMode { Plain, Linear, MicroAttn };   // k_proj<0 | 1 | 2>: attention output rows, IPA linear_out (K = 256), micro attention (L <= 8)
+enum class MlpPanelForm {   // Pre*: the temporal out-projection in the prologue (o, wo, bo); *Split: part, hupd, counters
+    W4, W8, W8Split,             // k_mlp<3>, k_mlp8<false>, k_mlp8<false, kMlpSplit>
+    PreW4, PreW8, PreW8Split     // k_mlp<3, true>, k_mlp8<true>, k_mlp8<true, kMlpSplit>
+};
+enum class MlpRowsForm {
+    Plain,            // k_mlp_rows<4, uni>, uni: no 32-row tile straddles two modulation groups (follows from the ModMap)
+    Fold,             // k_mlp_rows<4, true, true>: gate folded into the stream (b2g); one modulation group
+    FoldFinal,        // k_mlp_rows<4, true, true, true>: ... + FinalLayer tail (tail_*) ...
+    FoldFinalEmbed    // ... + the next step's token embedding (emb_*): the same instantiation, which tests emb_base
+};
+enum class FlashProjForm { Q64, Q128 };   // k_flash_proj (four waves, 64-row panel), k_flash_proj8 (eight waves, 128-row panel)
+
+void launch_ln_qkv(const QkvParams& p, QkvForm form, hipStream_t s);
 void launch_xcc_probe(int* out, int nblocks, hipStream_t s);
-void launch_ln_qkv_attn4(const QkvParams& p, bool fuse_proj, hipStream_t s, bool half = false);   // half: 32-row workgroups (fuse_proj only)
-void launch_proj(const ProjParams& p, int mode, hipStream_t s);
-void launch_mlp(const MlpParams& p, hipStream_t s, int waves = 4);
-void launch_mlp_rows(const MlpRowsParams& p, hipStream_t s);
+void launch_ln_qkv_attn4(const QkvParams& p, Attn4Form form, hipStream_t s);
+void launch_proj(const ProjParams& p, ProjMode mode, hipStream_t s);
+void launch_mlp(const MlpParams& p, MlpPanelForm form, hipStream_t s);
+void launch_mlp_rows(const MlpRowsParams& p, MlpRowsForm form, hipStream_t s);
 constexpr int kMlpStreamFrags = 2304;   // 1 KiB fragments of one MLP weight stream (api.hip mlp_stream_table)
 // per-(step, layer) MLP streams with the step's gate folded into fc2 (+ b2g = gate * b2); S * nl streams, nl <= 8
 void launch_pack_fold(const float* mod, long mod_step_stride, int S, int nl, const int* goff, const float* const* w2,
@@ -221,7 +249,7 @@ void launch_ln_linear(const LnLinearParams& p, hipStream_t s);
 void launch_final(const FinalParams& p, hipStream_t s);
 void launch_flash(const FlashParams& p, hipStream_t s);
 long flash_proj_jobs(const AxisMap& ax);
-void launch_flash_proj(const FlashProjParams& p, int form, hipStream_t s);   // form 4: k_flash_proj (64-row panels), 8: k_flash_proj8 (128-row)
+void launch_flash_proj(const FlashProjParams& p, FlashProjForm form, hipStream_t s);
 void launch_pack_embed(const float* w, int D, float* pack, hipStream_t s);   // pack: kEmbPackFloats floats
 constexpr int kEmbPackFloats = 4 * 3 * 14 * 64;
 void launch_embed(const EmbedParams& p, hipStream_t s);

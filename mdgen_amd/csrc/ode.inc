@@ -148,15 +148,11 @@ static int ode_combine(const Run& r, float* y, const float* y0, float* const* k,
         p.c[j] = (float)coef[j] * dt;
     }
     p.nk = n;
-    { ProfScope ps(r.c, "ode_combine", r.s); if (!g_dry) launch_ode_combine(y, y0, p, (long)r.N * r.D, r.s); }
-    LAUNCHCHK();
-    return 0;
+    return launch(r, "ode_combine", [&] { launch_ode_combine(y, y0, p, (long)r.N * r.D, r.s); });
 }
 
 static int ode_norm(const Run& r, const OdeBufs& b, const OdeNorm& p) {
-    { ProfScope ps(r.c, "ode_norm", r.s); if (!g_dry) launch_ode_norm(p, (long)r.N * r.D, b.part, b.out, r.s); }
-    LAUNCHCHK();
-    return 0;
+    return launch(r, "ode_norm", [&] { launch_ode_norm(p, (long)r.N * r.D, b.part, b.out, r.s); });
 }
 
 // prepare() for `n` time rows shared by the batch (the workspace is carved for kStages rows)
@@ -166,22 +162,12 @@ static int ode_prepare(Run& r, const float* times, int n, long view_rows) {
     return prepare(r, nullptr, times, view_rows);
 }
 
-// one network evaluation at prepared row `row`: y -> velocity k, over the call's launch views
+// one network evaluation at prepared row `row`: y -> velocity k, over the call's launch views on the caller's stream
 static int ode_eval(const Run& r, int nv, int row, const float* y, float* k) {
-    if (nv <= 1) {
-        if (g_dry) g_dry->push_back("@view0");
-        return denoise_step(r, row, const_cast<float*>(y), k, 0, 0.f, nullptr);
-    }
-    int b0 = 0;
-    for (int i = 0; i < nv; ++i) {   // sequential sub-batch views on the caller's stream
-        const int Bs = r.B / nv + (i < r.B % nv ? 1 : 0);
-        const Run v = sub_run(r, b0, Bs, r.s);
+    return for_each_view(r, nv, 1, [&](const Run& v, int b0) {
         const long o = (long)b0 * r.T * r.L * r.D;
-        if (g_dry) g_dry->push_back("@view" + std::to_string(i));
-        if (int e = denoise_step(v, row, const_cast<float*>(y) + o, k + o, 0, 0.f, nullptr)) return e;
-        b0 += Bs;
-    }
-    return 0;
+        return denoise_step(v, row, const_cast<float*>(y) + o, k + o, 0, 0.f, nullptr);
+    });
 }
 
 // One attempted step from (t0, Y0, K0, dt): prepare the six stage rows, y_i = y0 + sum_j beta_ij dt k_j -> k_i (Y1 = y1
@@ -270,14 +256,14 @@ extern "C" int32_t mdgen_sample_dopri5(mdgen_ctx* c, const mdgen_shape* sh, doub
     if (!c->ode_host) HIPCHK(hipHostMalloc((void**)&c->ode_host, 2 * sizeof(double), hipHostMallocDefault));
     const int nv = c->opt_precision == 32 ? 1 : plan_views(r.B, r.T, r.L, 1);
     if (nv == 0) return fail(-2, "sample too large for one launch");
-    const long view_rows = (long)((r.B + nv - 1) / nv) * r.T * r.L;
+    const long vrows = largest_view_rows(r, nv);
     OdeBufs b = ode_bufs((unsigned char*)ws, lay.total_bytes, ode_state_bytes(c, sh), x);
     Dopri5Ctl ctl;
     int nfe = 0;
     // ---- initial step (misc.py _select_initial_step, order 4): k1 = f(0, x0), probe f(h0, x0 + h0 k1)
     {
         const float t0f = 0.f;
-        if (int e = ode_prepare(r, &t0f, 1, view_rows)) return e;
+        if (int e = ode_prepare(r, &t0f, 1, vrows)) return e;
         if (int e = ode_eval(r, nv, 0, b.y0, b.k[0])) return e;
         ++nfe;
         OdeNorm p{};
@@ -294,7 +280,7 @@ extern "C" int32_t mdgen_sample_dopri5(mdgen_ctx* c, const mdgen_shape* sh, doub
         float* k0 = b.k[0];
         if (int e = ode_combine(r, b.y1, b.y0, &k0, &one, 1, ctl.probe_coef())) return e;
         const float th = ctl.probe_time();
-        if (int e = ode_prepare(r, &th, 1, view_rows)) return e;
+        if (int e = ode_prepare(r, &th, 1, vrows)) return e;
         if (int e = ode_eval(r, nv, 0, b.y1, b.k[1])) return e;
         ++nfe;
         p.k[0] = b.k[1];
@@ -311,7 +297,7 @@ extern "C" int32_t mdgen_sample_dopri5(mdgen_ctx* c, const mdgen_shape* sh, doub
     for (int attempt = 0; !ctl.done; ++attempt) {
         if (attempt >= max_steps) return fail(-10, "dopri5: max_steps = %d attempted steps exceeded at t = %.9g", max_steps, ctl.t0);
         if (ctl.underflow()) return fail(-11, "dopri5: underflow in dt %g at t = %.17g", ctl.dt, ctl.t0);
-        if (int e = dopri5_attempt(r, b, ctl, nv, view_rows, atol, rtol)) return e;
+        if (int e = dopri5_attempt(r, b, ctl, nv, vrows, atol, rtol)) return e;
         nfe += ode::kStages;
         stats_host[0] = nfe;
         double ratio = 0;
@@ -329,8 +315,7 @@ extern "C" int32_t mdgen_sample_dopri5(mdgen_ctx* c, const mdgen_shape* sh, doub
         if (ctl.done) {   // dense output of this step at t = 1 into the caller's x (which is b.y0 or b.y1)
             const float dtf = (float)ctl.last_dt;
             if (int e = ode_combine(r, b.ym, b.y0, b.k, ode::kMid, 7, dtf)) return e;
-            { ProfScope ps(c, "ode_dense", s); launch_ode_dense(x, b.y0, b.y1, b.k[0], b.k[6], b.ym, dtf, ctl.dense_s(), (long)r.N * r.D, s); }
-            LAUNCHCHK();
+            if (int e = launch(r, "ode_dense", [&] { launch_ode_dense(x, b.y0, b.y1, b.k[0], b.k[6], b.ym, dtf, ctl.dense_s(), (long)r.N * r.D, s); })) return e;
             break;
         }
         std::swap(b.y0, b.y1);   // FSAL: y1 -> y0, k7 -> k1
@@ -372,48 +357,16 @@ extern "C" int32_t mdgen_debug_dopri5_controller(const double* init, const doubl
     return 0;
 }
 
-// mdgen_debug_dispatch_plan mode 4: one attempted step of mdgen_sample_dopri5 in plan mode (g_dry records the classes).
-// Output: {"streams": 1, "prepare": {...} (the stage rows' preparation), "views": [{"B", "classes": the six evaluations of that
-// view}], "integrator": {"ode_combine": 6, "ode_norm": 1}}
-static int dopri5_plan(mdgen_ctx* c, const mdgen_shape* sh, std::vector<std::string>& plan, char* buf, size_t buflen) {
-    Run r{};
-    if (int e = make_run(&r, c, sh, ode::kStages, 1, (void*)4096, (size_t)1 << 60, nullptr)) return e;
-    float* fake = (float*)4096;   // never dereferenced: plan mode launches nothing
-    r.mask = r.start_rot = r.start_trans = r.end_rot = r.end_trans = r.x_cond = fake;
-    r.x_cond_mask = r.aatype = (const int64_t*)fake;
-    r.no_embed_tail = true;
-    const int nv = plan_views(r.B, r.T, r.L, 1);
+// mdgen_debug_dispatch_plan mode 4: one attempted step of mdgen_sample_dopri5 on a made run, in plan mode
+static int dopri5_plan(Run& r, int nv) {
     if (nv == 0) return fail(-2, "sample too large for one launch");
+    r.no_embed_tail = true;
+    float* fake = (float*)4096;   // never dereferenced: plan mode launches nothing
     OdeBufs b;
     b.y0 = b.y1 = b.ym = fake;
     for (int j = 0; j < 7; ++j) b.k[j] = fake;
     b.part = b.out = (double*)fake;
     Dopri5Ctl ctl;
     ctl.dt = 0.01;
-    if (int e = dopri5_attempt(r, b, ctl, nv, (long)((r.B + nv - 1) / nv) * r.T * r.L, 1e-6, 1e-3)) return e;
-    std::map<std::string, long> prep, integ;
-    std::vector<std::map<std::string, long>> views(nv);
-    int cur = -1;
-    for (const auto& k : plan) {
-        if (k.rfind("@view", 0) == 0) cur = std::atoi(k.c_str() + 5);
-        else if (k.rfind("ode_", 0) == 0) ++integ[k];
-        else if (cur < 0) ++prep[k];
-        else ++views[cur][k];
-    }
-    auto dump = [](const std::map<std::string, long>& agg) {
-        std::string o = "{";
-        bool first = true;
-        for (const auto& kv : agg) {
-            o += std::string(first ? "" : ", ") + "\"" + kv.first + "\": " + std::to_string(kv.second);
-            first = false;
-        }
-        return o + "}";
-    };
-    std::string js = "{\"streams\": 1, \"prepare\": " + dump(prep) + ", \"views\": [";
-    for (int i = 0; i < nv; ++i)
-        js += std::string(i ? ", " : "") + "{\"B\": " + std::to_string(r.B / nv + (i < r.B % nv ? 1 : 0)) + ", \"classes\": " + dump(views[i]) + "}";
-    js += "], \"integrator\": " + dump(integ) + "}";
-    if (js.size() + 1 > buflen) return fail(-7, "plan buffer too small");
-    std::memcpy(buf, js.c_str(), js.size() + 1);
-    return 0;
+    return dopri5_attempt(r, b, ctl, nv, largest_view_rows(r, nv), 1e-6, 1e-3);
 }

@@ -100,7 +100,7 @@ def test_library_never_aborts_reads_the_environment_or_keeps_a_mode_global():
     assert "k32_take_launch_error()" in open(os.path.join(csrc, "api.hip")).read()
     # parameters are addressed by slots that the registration code records in typed structs, never by building a key: the
     # training step holds no strings or maps and no `mutable` state behind a const reference, the fp32 sampler path has no
-    # lookup macro, and the context keeps ONE name -> slot map (beside `cls_names`, the profile classes)
+    # lookup macro, and the context keeps ONE name -> slot map (the profile classes are string literals)
     train = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "train.inc")).read())
     api = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "api.hip")).read())
     for word in ("std::string", "std::to_string", "std::map", "mutable", "TW32"):
@@ -108,7 +108,7 @@ def test_library_never_aborts_reads_the_environment_or_keeps_a_mode_global():
     assert "W32(" not in api and not re.search(r"\bw32\s*\(", api)
     ctx = re.search(r"\nstruct mdgen_ctx \{.*?\n\};", api, re.S).group(0)
     keyed = re.findall(r"std::(?:unordered_)?(?:map|set)\s*<\s*std::string\b[^;]*?(\w+);", ctx)
-    assert keyed == ["slot_of", "cls_names"], keyed
+    assert keyed == ["slot_of"], keyed
 
 
 def test_config_from_reference_namespace():
