@@ -354,8 +354,8 @@ int32_t mdgen_debug_layout_maps(int32_t* map_qk, int32_t* map_vflash, int32_t* m
  * Returns the number of entries, or a negative status. */
 int32_t mdgen_debug_mlp_stream_table(int32_t* out, int32_t capacity);
 
-/* Test hooks (GPU): the training step's linear layer and weight gradient on raw device buffers, through exactly the
- * kernel dispatch of mdgen_train_forward_backward -- precision 32: fp32 products (k32_linear / k32_dw); 16: bf16-rounded
+/* Test hooks (GPU): the training step's linear layer and weight gradient on raw device buffers, launched in the form that the
+ * form functions of mdgen_train_forward_backward give for the shape -- precision 32: fp32 products (k32_linear / k32_dw); 16: bf16-rounded
  * operands with fp32 accumulation (128 x 384-tile streamed kernels for >= 1024 / 4096 rows, one-wave tiles for a few
  * hundred rows, the general kernels otherwise).  All pointers are fp32 device memory.
  *   linear: c[n][m] (row stride ldc) = a[n][k] (lda) . w[m][k]^T (ldw) + bias[m] (bias may be NULL);
@@ -383,6 +383,15 @@ int32_t mdgen_debug_train_attention(int32_t precision, const float* qkv, int64_t
                                     int32_t outer_stride, int32_t inner_stride, int32_t pos_stride, const float* mask,
                                     const float* bias_k, const float* bias_v, const float* inv_freq, const float* dout,
                                     float* out, float* lse, float* dqkv, float* dbias, float* stats, void* stream);
+
+/* Host-only (no GPU): the plans of one mdgen_train_forward_backward call -- the kernel form of every launch whose kernel depends on
+ * train_precision (16 | 32), the row count, the attention axis or the 16-byte alignment of the weights (weight_misalign_bytes: every
+ * weight that many bytes off a 16-byte boundary, as a bound parameter buffer may put them; 0 = aligned).  Writes JSON: {"rows",
+ * "ipa_block", "ipa_attn", "ipa_mlp" (B L rows), "trunk_attn_l", "trunk_attn_t", "trunk_mlp" (B T L rows), "final"}; a form is named by
+ * its kernel, a dX product as [route ("streamed" | "turned" | "wtrans"), form], a weight gradient as [form, the bias gradient rides
+ * along], "rows" of a sub-layer: its GEMM-only tensors are stored as "bf16" or "fp32" rows.  tests/test_train_plan_cpu.py. */
+int32_t mdgen_debug_train_plan(const mdgen_shape* shape, int32_t tps_condition, int32_t num_layers, int32_t train_precision,
+                               int32_t weight_misalign_bytes, char* buf, size_t buflen);
 
 /* ---- SE(3) frame algebra, fp32 (mdgen/rigid_utils.py) --------------------------------------
  * n = number of frames; rot: [n][3][3]; trans/pts: [n][3]; quat: [n][4] (w,x,y,z). */

@@ -2,6 +2,7 @@
 // layout, the denoiser forward / Euler rollout orchestration and hipGraph capture.
 #include "../../include/mdgen_amd.h"
 #include "kernels.h"
+#include "linear.h"
 
 #include <algorithm>
 #include <cmath>
@@ -977,21 +978,47 @@ static int check_f32_weights(const mdgen_ctx* c) {
     return 0;
 }
 
+static const ModMap kNoMod{nullptr, 1, 1, 0, 0};
+// the IPA block's four input projections q | kv | q_points | kv_points of LN(x): output columns [col0, col0 + m) of the kIpaProj-wide rows
+struct IpaProjCols { int col0, m; };
+static const IpaProjCols kIpaProjCols[4] = {{0, 128}, {128, 256}, {384, 96}, {480, 192}};
+// The operands of one linear layer c[n][0 .. m) (ldc) = a[n][k] (lda) w[m][k]^T (ldw) + bias, plain store (linear.h LinearParams);
+// the caller sets what its launch has beyond that: mode and the mode's operands, col0, wtrans, the bf16-operand mode's fields
+static LinearParams lin_op(const float* a, int lda, const float* w, int ldw, const float* bias, long n, int m, int k, float* c, int ldc) {
+    LinearParams p{};
+    p.a = a; p.lda = lda; p.w = w; p.ldw = ldw; p.bias = bias;
+    p.n = n; p.m = m; p.k = k;
+    p.mode = kLinStore;
+    p.c = c; p.ldc = ldc;
+    p.mm = kNoMod;
+    return p;
+}
+// ... with the gated residual as the epilogue: c += gate * (a w^T + bias), gate = chunk `gate` of the row's modulation
+static LinearParams lin_op_gated(LinearParams p, const ModMap& mm, int gate) {
+    p.mode = kLinGated; p.mm = mm; p.gate_chunk = gate; p.gated = 1;
+    return p;
+}
+
 // one attention sub-layer, fp32: LN + modulate -> q, k, v -> RoPE -> softmax attention -> out-projection + gated residual
 static int attn_sublayer_fp32(const Run& r, const MhaW& m, float* h, long nrows, const AxisMap& ax, const ModMap& mm, int shift,
                               int scale, int gate, const MaskMap& mk, long pos_div, int pos_mod) {
     const mdgen_ctx* c = r.c;
     const F32Bufs b = f32_bufs(r);
     const auto& p = m.slot;
-    const ModMap none{nullptr, 1, 1, 0, 0};
-    launch32_ln_mod(h, nrows, mm, shift, scale, 0, 1e-6f, b.y, r.s);
-    const float qscale = 1.0f / std::sqrt((float)kDH);   // mha.py:263 q *= head_dim ** -0.5
-    launch32_linear(b.y, kC, c->f32(p.q.w), kC, c->f32(p.q.b), nrows, kC, kC, 4, b.qkv, 3 * kC, 0, none, 0, 0, qscale, r.s);
-    launch32_linear(b.y, kC, c->f32(p.k.w), kC, c->f32(p.k.b), nrows, kC, kC, 0, b.qkv, 3 * kC, kC, none, 0, 0, 0.f, r.s);
-    launch32_linear(b.y, kC, c->f32(p.v.w), kC, c->f32(p.v.b), nrows, kC, kC, 0, b.qkv, 3 * kC, 2 * kC, none, 0, 0, 0.f, r.s);
+    launch32_ln_mod(h, nrows, mm, shift, scale, 0, 1e-6f, b.y, r.s, nullptr, false);
+    LinearParams q = lin_op(b.y, kC, c->f32(p.q.w), kC, c->f32(p.q.b), nrows, kC, kC, b.qkv, 3 * kC);
+    q.mode = kLinScaled;
+    q.scalar = 1.0f / std::sqrt((float)kDH);   // mha.py:263 q *= head_dim ** -0.5
+    LinearParams k = lin_op(b.y, kC, c->f32(p.k.w), kC, c->f32(p.k.b), nrows, kC, kC, b.qkv, 3 * kC);
+    k.col0 = kC;
+    LinearParams v = lin_op(b.y, kC, c->f32(p.v.w), kC, c->f32(p.v.b), nrows, kC, kC, b.qkv, 3 * kC);
+    v.col0 = 2 * kC;
+    launch32_linear(q, r.s);
+    launch32_linear(k, r.s);
+    launch32_linear(v, r.s);
     launch32_rope(b.qkv, nrows, 3 * kC, pos_div, pos_mod, c->inv_freq, r.s);
-    launch32_attn(b.qkv, 3 * kC, ax, mk, c->f32(p.bias_k), c->f32(p.bias_v), c->inv_freq, b.att, r.s);
-    launch32_linear(b.att, kC, c->f32(p.o.w), kC, c->f32(p.o.b), nrows, kC, kC, 2, h, kC, 0, mm, gate, 1, 0.f, r.s);
+    launch32_attn(b.qkv, 3 * kC, ax, mk, c->f32(p.bias_k), c->f32(p.bias_v), c->inv_freq, b.att, r.s, nullptr);
+    launch32_linear(lin_op_gated(lin_op(b.att, kC, c->f32(p.o.w), kC, c->f32(p.o.b), nrows, kC, kC, h, kC), mm, gate), r.s);
     LAUNCHCHK();
     return 0;
 }
@@ -999,10 +1026,11 @@ static int attn_sublayer_fp32(const Run& r, const MhaW& m, float* h, long nrows,
 static int mlp_sublayer_fp32(const Run& r, const FfnW& f, float* h, long nrows, const ModMap& mm, int shift, int scale, int gate) {
     const mdgen_ctx* c = r.c;
     const F32Bufs b = f32_bufs(r);
-    const ModMap none{nullptr, 1, 1, 0, 0};
-    launch32_ln_mod(h, nrows, mm, shift, scale, 0, 1e-6f, b.y, r.s);
-    launch32_linear(b.y, kC, c->f32(f.slot.fc1.w), kC, c->f32(f.slot.fc1.b), nrows, kF, kC, 1, b.hid, kF, 0, none, 0, 0, 0.f, r.s);
-    launch32_linear(b.hid, kF, c->f32(f.slot.fc2.w), kF, c->f32(f.slot.fc2.b), nrows, kC, kF, 2, h, kC, 0, mm, gate, 1, 0.f, r.s);
+    launch32_ln_mod(h, nrows, mm, shift, scale, 0, 1e-6f, b.y, r.s, nullptr, false);
+    LinearParams fc1 = lin_op(b.y, kC, c->f32(f.slot.fc1.w), kC, c->f32(f.slot.fc1.b), nrows, kF, kC, b.hid, kF);
+    fc1.mode = kLinGelu;
+    launch32_linear(fc1, r.s);
+    launch32_linear(lin_op_gated(lin_op(b.hid, kF, c->f32(f.slot.fc2.w), kF, c->f32(f.slot.fc2.b), nrows, kC, kF, h, kC), mm, gate), r.s);
     LAUNCHCHK();
     return 0;
 }
@@ -1437,13 +1465,14 @@ static int ipa_stack(const Run& r, float* hbuf, const float* rel7, const float* 
         if (c->opt_precision == 32) {   // ---- fp32 operands: ipa_norm -> four projections -> point attention -> linear_out
             const F32Bufs fb = f32_bufs(r);
             const auto& p = w.slot;
-            const ModMap none{nullptr, 1, 1, 0, 0};
             float* proj = (float*)(r.ws + r.lay.ipa_proj);
-            launch32_ln_mod(hbuf, r.Mp, ModMap{w.gamma_beta, 1, 1, 0, 0}, 1, 0, 1, 1e-5f, fb.y, r.s);
-            launch32_linear(fb.y, kC, c->f32(p.q.w), kC, c->f32(p.q.b), r.Mp, 128, kC, 0, proj, kIpaProj, 0, none, 0, 0, 0.f, r.s);
-            launch32_linear(fb.y, kC, c->f32(p.kv.w), kC, c->f32(p.kv.b), r.Mp, 256, kC, 0, proj, kIpaProj, 128, none, 0, 0, 0.f, r.s);
-            launch32_linear(fb.y, kC, c->f32(p.q_points.w), kC, c->f32(p.q_points.b), r.Mp, 96, kC, 0, proj, kIpaProj, 384, none, 0, 0, 0.f, r.s);
-            launch32_linear(fb.y, kC, c->f32(p.kv_points.w), kC, c->f32(p.kv_points.b), r.Mp, 192, kC, 0, proj, kIpaProj, 480, none, 0, 0, 0.f, r.s);
+            launch32_ln_mod(hbuf, r.Mp, ModMap{w.gamma_beta, 1, 1, 0, 0}, 1, 0, 1, 1e-5f, fb.y, r.s, nullptr, false);
+            const Lin* lins[4] = {&p.q, &p.kv, &p.q_points, &p.kv_points};
+            for (int j = 0; j < 4; ++j) {
+                LinearParams q = lin_op(fb.y, kC, c->f32(lins[j]->w), kC, c->f32(lins[j]->b), r.Mp, kIpaProjCols[j].m, kC, proj, kIpaProj);
+                q.col0 = kIpaProjCols[j].col0;
+                launch32_linear(q, r.s);
+            }
             IpaAttnParams ap{};
             ap.proj = proj;
             ap.rot = rot;
@@ -1456,7 +1485,9 @@ static int ipa_stack(const Run& r, float* hbuf, const float* rel7, const float* 
             ap.B = r.B;
             ap.L = r.L;
             launch_ipa_attn(ap, r.s);
-            launch32_linear(fb.feat, kIpaFeat, c->f32(p.out.w), kIpaFeat, c->f32(p.out.b), r.Mp, kC, kIpaFeat, 2, hbuf, kC, 0, none, 0, 0, 0.f, r.s);
+            LinearParams lo = lin_op(fb.feat, kIpaFeat, c->f32(p.out.w), kIpaFeat, c->f32(p.out.b), r.Mp, kC, kIpaFeat, hbuf, kC);
+            lo.mode = kLinGated;   // (gated = 0: the ungated residual hbuf += linear_out(feat))
+            launch32_linear(lo, r.s);
             LAUNCHCHK();
             if (int e = attn_sublayer_fp32(r, w.mha_l, hbuf, r.Mp, ax, mm, 0, 1, 2, mk, 1, r.L)) return e;
             if (int e = mlp_sublayer_fp32(r, w.ffn, hbuf, r.Mp, mm, 3, 4, 5)) return e;
@@ -1616,10 +1647,11 @@ static int denoise_step(const Run& r, int step, float* x, float* out, int euler,
         }
         const F32Bufs fb = f32_bufs(r);
         const ModMap fm{modstep + c->final_off(), r.T * r.L, r.B, 0, r.mod_group_stride};
-        const ModMap none{nullptr, 1, 1, 0, 0};
-        launch32_ln_mod(h, r.N, fm, 0, 1, 0, 1e-6f, fb.y, r.s);
-        launch32_linear(fb.y, kC, c->f32(c->slot.fin.w), kC, c->f32(c->slot.fin.b), r.N, r.D, kC, euler ? 3 : 0, euler ? x : out, r.D, 0,
-                        none, 0, 0, dt, r.s);
+        launch32_ln_mod(h, r.N, fm, 0, 1, 0, 1e-6f, fb.y, r.s, nullptr, false);
+        LinearParams fin = lin_op(fb.y, kC, c->f32(c->slot.fin.w), kC, c->f32(c->slot.fin.b), r.N, r.D, kC, euler ? x : out, r.D);
+        fin.mode = euler ? kLinEuler : kLinStore;
+        fin.scalar = dt;
+        launch32_linear(fin, r.s);
         LAUNCHCHK();
         return 0;
     }

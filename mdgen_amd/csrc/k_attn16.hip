@@ -23,7 +23,7 @@
 // Round 6: axes of 129 .. 256 positions (the ATLAS training shapes) take the SEQUENCE-RESIDENT forms further down --
 // k16_attn_seq / k16_attn_bwd_seq: eight waves own all rows of one (sequence, head), the other side is converted into LDS once,
 // scores in log2 units, per-row addends in the padding features of the operands, RoPE applied while converting (the caller
-// chooses: launch16_attn / launch16_attn_bwd `seq_form`).  The kernels right below remain for every other length.  At the ATLAS
+// chooses: kernels.h train_attn_form).  The kernels right below remain for every other length.  At the ATLAS
 // lengths the chunked backward re-staged the other side of every 128-row block through LDS and ran at 586 us per launch; the
 // sequence-resident pass takes ~380 us in the step, the forward ~100 instead of 134 with the rotation inside.
 #include "common.h"
@@ -1123,36 +1123,46 @@ static unsigned wg_grid(int nseq, int nblk) { return (unsigned)((long)((nseq + 7
 // (sequence, head) at the ATLAS lengths instead of once per 128-query block (124 -> 104 us); four waves below that.
 bool attn16_seq_form(const AxisMap& ax) { return ax.len > 128 && ax.len <= kSeqQ; }
 
-void launch16_attn(const float* qkv, int ld, const AxisMap& ax, const MaskMap& mk, const float* bias_k, const float* bias_v,
-                   const float* inv_freq, float* out, hipStream_t s, float* lse_out, bool seq_form, bool rope_inside) {
-    if (seq_form && attn16_seq_form(ax)) {
-        hipLaunchKernelGGL(k16_attn_seq, dim3(wg_grid(ax.nseq, 1)), dim3(512), 0, s, qkv, ld, ax, mk, bias_k, bias_v, inv_freq, out, lse_out,
-                           rope_inside);
-    } else if (ax.len > 128) {
-        const int nqb = (ax.len + 255) / 256;
-        hipLaunchKernelGGL(k16_attn<8>, dim3(wg_grid(ax.nseq, nqb)), dim3(512), 0, s, qkv, ld, ax, mk, bias_k, bias_v,
-                           inv_freq, out, lse_out);
+// The attention of the training step (kernels.h TrainAttnParams).  A Seq* form on an axis it does not cover launches nothing.
+static bool train_attn_ok(const TrainAttnParams& p, TrainAttnForm form) {
+    if ((!attn_seq(form) || attn16_seq_form(p.ax)) && p.lse && (attn_seq(form) || !p.dqkv_bf16)) return true;
+    g_k32_launch_error = "launch_train_attn: the axis or the operands do not fit the form";
+    return false;
+}
+void launch_train_attn(const TrainAttnParams& p, TrainAttnForm form, hipStream_t s) {
+    if (!train_attn_ok(p, form)) return;
+    if (form == TrainAttnForm::Exact) {
+        launch32_attn(p.qkv, p.ld, p.ax, p.mk, p.bias_k, p.bias_v, p.inv_freq, p.out, s, p.lse);
+    } else if (attn_seq(form)) {
+        hipLaunchKernelGGL(k16_attn_seq, dim3(wg_grid(p.ax.nseq, 1)), dim3(512), 0, s, p.qkv, p.ld, p.ax, p.mk, p.bias_k, p.bias_v, p.inv_freq,
+                           p.out, p.lse, form == TrainAttnForm::SeqRope);
+    } else if (p.ax.len > 128) {
+        const int nqb = (p.ax.len + 255) / 256;
+        hipLaunchKernelGGL(k16_attn<8>, dim3(wg_grid(p.ax.nseq, nqb)), dim3(512), 0, s, p.qkv, p.ld, p.ax, p.mk, p.bias_k, p.bias_v,
+                           p.inv_freq, p.out, p.lse);
     } else {
-        hipLaunchKernelGGL(k16_attn<4>, dim3(wg_grid(ax.nseq, 1)), dim3(256), 0, s, qkv, ld, ax, mk, bias_k, bias_v, inv_freq,
-                           out, lse_out);
+        hipLaunchKernelGGL(k16_attn<4>, dim3(wg_grid(p.ax.nseq, 1)), dim3(256), 0, s, p.qkv, p.ld, p.ax, p.mk, p.bias_k, p.bias_v, p.inv_freq,
+                           p.out, p.lse);
     }
 }
 // (the backward passes stay at four waves: with eight -- 148 registers, one workgroup per CU, staging done by 192 of 512
 // threads -- the query pass went 168 -> 186 us and the key pass 172 -> 221 us at the ATLAS lengths)
-void launch16_attn_bwd(const float* qkv, int ld, const AxisMap& ax, const MaskMap& mk, const float* bias_k,
-                       const float* bias_v, const float* inv_freq, const float* o, const float* dout, float* dqkv,
-                       float* stats, float* dbias, hipStream_t s, const float* lse_in, bool seq_form, bool rope_inside,
-                       bool out_bf16) {
-    if (seq_form && attn16_seq_form(ax)) {   // one workgroup per (sequence, head) and pass, the other side resident in LDS
-        hipLaunchKernelGGL(k16_attn_bwd_seq, dim3(2 * wg_grid(ax.nseq, 1)), dim3(512), 0, s, qkv, ld, ax, mk, bias_k, bias_v, inv_freq, o, dout,
-                           dqkv, dbias, lse_in, rope_inside, out_bf16);
+void launch_train_attn_bwd(const TrainAttnParams& p, TrainAttnForm form, hipStream_t s) {
+    if (!train_attn_ok(p, form)) return;
+    if (form == TrainAttnForm::Exact) {
+        launch32_attn_bwd(p.qkv, p.ld, p.ax, p.mk, p.bias_k, p.bias_v, p.inv_freq, p.out, p.dout, p.dqkv, p.stats, p.dbias, s, p.lse);
         return;
     }
-    const int nqb = (ax.len + 127) / 128, nkb = (ax.len + 128) / 128;
-    hipLaunchKernelGGL(k16_attn_bwd_q<4>, dim3(wg_grid(ax.nseq, nqb)), dim3(256), 0, s, qkv, ld, ax, mk, bias_k, bias_v,
-                       inv_freq, o, dout, dqkv, stats, lse_in);
-    hipLaunchKernelGGL(k16_attn_bwd_kv<4>, dim3(wg_grid(ax.nseq, nkb)), dim3(256), 0, s, qkv, ld, ax, mk, bias_k,
-                       bias_v, inv_freq, dout, stats, dqkv, dbias);
+    if (attn_seq(form)) {   // one workgroup per (sequence, head) and pass, the other side resident in LDS
+        hipLaunchKernelGGL(k16_attn_bwd_seq, dim3(2 * wg_grid(p.ax.nseq, 1)), dim3(512), 0, s, p.qkv, p.ld, p.ax, p.mk, p.bias_k, p.bias_v,
+                           p.inv_freq, p.out, p.dout, p.dqkv, p.dbias, p.lse, form == TrainAttnForm::SeqRope, p.dqkv_bf16);
+        return;
+    }
+    const int nqb = (p.ax.len + 127) / 128, nkb = (p.ax.len + 128) / 128;
+    hipLaunchKernelGGL(k16_attn_bwd_q<4>, dim3(wg_grid(p.ax.nseq, nqb)), dim3(256), 0, s, p.qkv, p.ld, p.ax, p.mk, p.bias_k, p.bias_v,
+                       p.inv_freq, p.out, p.dout, p.dqkv, p.stats, p.lse);
+    hipLaunchKernelGGL(k16_attn_bwd_kv<4>, dim3(wg_grid(p.ax.nseq, nkb)), dim3(256), 0, s, p.qkv, p.ld, p.ax, p.mk, p.bias_k,
+                       p.bias_v, p.inv_freq, p.dout, p.stats, p.dqkv, p.dbias);
 }
 
 }  // namespace mdg

@@ -21,7 +21,7 @@
 #include "linear.h"
 
 namespace mdg {
-bool launch16_linear_wide(const LinearParams& p, hipStream_t s);   // k_wide16.hip; false: shape not eligible, nothing launched
+void launch16_linear_wide(const LinearParams& p, LinearForm form, hipStream_t s);   // k_wide16.hip: the Stream* and Wide forms
 }
 
 namespace mdg {
@@ -645,70 +645,38 @@ void launch32_gate_ln_mod(const float* xp, const float* up, long nrows, const Mo
                        scale_chunk, eps, y, keep, y_bf16 ? reinterpret_cast<unsigned short*>(y) : nullptr);
 }
 // Exact fp32 products (k32_linear on v_mfma_f32_32x32x2_f32): the sampler's fp32 tolerance mode and the training step's exact mode.
-void launch32_linear(const float* a, int lda, const float* w, int ldw, const float* bias, long n, int m, int k, int mode,
-                     float* c, int ldc, int col0, const ModMap& mm, int gate_chunk, int gated, float scalar, hipStream_t s,
-                     int wtrans, float* c2) {
-    LinearParams p{a, lda, w, ldw, bias, n, m, k, mode, wtrans, c, ldc, col0, mm, gate_chunk, gated, scalar, c2, 0, {}, {}, {},
-                   nullptr, 0, 0, 0, 0};
-    hipLaunchKernelGGL(k32_linear, dim3((unsigned)((m + 127) / 128), (unsigned)((n + 127) / 128)), dim3(256), 0, s, p);
+void launch32_linear(const LinearParams& p, hipStream_t s) {
+    hipLaunchKernelGGL(k32_linear, dim3((unsigned)((p.m + 127) / 128), (unsigned)((p.n + 127) / 128)), dim3(256), 0, s, p);
 }
 // bf16 operands (the training step's option train_precision = 16): k16_linear* round the operands to bf16 on their way into LDS
 // and multiply on v_mfma_f32_32x32x16_bf16 with fp32 accumulation -- what the reference trains with (train.py:13
 // `torch.set_float32_matmul_precision('medium')` = bf16-class products, fp32 accumulate, fp32 master weights).
-void launch16_linear(const float* a, int lda, const float* w, int ldw, const float* bias, long n, int m, int k, int mode,
-                     float* c, int ldc, int col0, const ModMap& mm, int gate_chunk, int gated, float scalar, hipStream_t s,
-                     int wtrans, float* c2, const void* wpack, int flags) {
-    LinearParams p{a, lda, w, ldw, bias, n, m, k, mode, wtrans, c, ldc, col0, mm, gate_chunk, gated, scalar, c2, 0, {}, {}, {},
-                   static_cast<const unsigned char*>(wpack), 1, flags & 1, (flags >> 1) & 1, (flags >> 2) & 1};
-    if ((flags & 4) && mode != 7) {   // (fast_gelu turns mode 7 into 17, the only one that stores bf16)
-        g_k32_launch_error = "launch16_linear: a bf16 result is the GELU-derivative epilogue's only";
-        return;
-    }
-    if ((flags & 1) && !wpack) {
-        g_k32_launch_error = "launch16_linear: bf16 operand storage outside the streamed kernel";
-        return;
-    }
+// With p.seg_cols: q | k | v (three [seg_cols][k] layers of the same input) in one pass.
+void launch_linear(const LinearParams& p, LinearForm form, hipStream_t s) {
     const auto al = [](const void* q) { return ((unsigned long long)q & 15) == 0; };
-    if (launch16_linear_wide(p, s)) return;    // 128 x 384 tiles: every trunk-sized layer (k_wide16.hip)
-    if (flags & 1) {
-        g_k32_launch_error = "launch16_linear: bf16 token rows need the streamed kernel (n >= 1024, m % 384 == 0)";
+    const bool w_al = p.seg_cols ? al(p.w_seg[0]) && al(p.w_seg[1]) && al(p.w_seg[2]) : al(p.w);
+    const bool vec = linear_vec(LinShape{p.n, p.m, p.k, p.lda, p.ldw, p.wtrans, al(p.a), w_al, p.a_bf16 != 0});
+    const bool plain = form == LinearForm::F32 || form == LinearForm::Plain;
+    if ((!plain && !vec) || (plain && p.seg_cols) || (p.seg_cols && p.seg_cols % 128) || (p.c_bf16 && p.mode != kLinGeluBwd) ||
+        (p.a_bf16 != 0) != (form == LinearForm::StreamBf16Rows) || (linear_streams(form) && (!p.wpack || p.m % 384)) ||
+        (form == LinearForm::Small && p.n > 2048)) {
+        g_k32_launch_error = "launch_linear: the operands do not fit the form";
         return;
     }
-    if (n <= 2048 && !wtrans && k % 64 == 0 && (lda & 3) == 0 && (ldw & 3) == 0 && ((unsigned long long)a & 15) == 0 &&
-        ((unsigned long long)w & 15) == 0) {   // a few hundred rows: one wave per 32 x 32 tile
-        hipLaunchKernelGGL(k16_linear_small, dim3((unsigned)((m + 31) / 32), (unsigned)((n + 31) / 32)), dim3(64), 0, s, p);
-        return;
+    const int nrt = (int)((p.n + 127) / 128), nct = (p.m + 127) / 128;
+    switch (form) {
+        case LinearForm::F32: launch32_linear(p, s); break;
+        case LinearForm::StreamF32Rows:
+        case LinearForm::StreamBf16Rows:
+        case LinearForm::Wide: launch16_linear_wide(p, form, s); break;    // 128 x 384 tiles: every trunk-sized layer (k_wide16.hip)
+        case LinearForm::Small:   // a few hundred rows: one wave per 32 x 32 tile
+            hipLaunchKernelGGL(k16_linear_small, dim3((unsigned)((p.m + 31) / 32), (unsigned)((p.n + 31) / 32)), dim3(64), 0, s, p);
+            break;
+        case LinearForm::Fast:
+            hipLaunchKernelGGL(k16_linear_fast, dim3((unsigned)(8 * ((nrt + 7) / 8) * nct)), dim3(256), 0, s, p, nrt, nct);
+            break;
+        case LinearForm::Plain: hipLaunchKernelGGL(k16_linear, dim3((unsigned)nct, (unsigned)nrt), dim3(256), 0, s, p); break;
     }
-    const bool fast = !wtrans && k % 64 == 0 && (lda & 3) == 0 && (ldw & 3) == 0 && al(a) && al(w);
-    if (!fast) {
-        hipLaunchKernelGGL(k16_linear, dim3((unsigned)((m + 127) / 128), (unsigned)((n + 127) / 128)), dim3(256), 0, s, p);
-        return;
-    }
-    const int nrt = (int)((n + 127) / 128), nct = (m + 127) / 128;
-    hipLaunchKernelGGL(k16_linear_fast, dim3((unsigned)(8 * ((nrt + 7) / 8) * nct)), dim3(256), 0, s, p, nrt, nct);
-}
-// q | k | v (three [mseg][k] layers of the same input) in one pass of k16_linear_fast: c[n][col0 + j mseg + i] =
-// (a . w[j][i] + bias[j][i]) * scale[j], bf16 operands.  false: shape not eligible, nothing launched.
-bool launch16_linear_seg3(const float* a, int lda, const float* const* w, int ldw, const float* const* bias, const float* scale,
-                          long n, int mseg, int k, float* c, int ldc, int col0, hipStream_t s, const void* wpack, bool a_bf16) {
-    const auto al = [](const void* q) { return ((unsigned long long)q & 15) == 0; };
-    if (mseg % 128 || k % 64 || (lda & 3) || (ldw & 3) || !al(a) || !al(w[0]) || !al(w[1]) || !al(w[2]))
-        return false;
-    LinearParams p{a, lda, w[0], ldw, nullptr, n, 3 * mseg, k, 0, 0, c, ldc, col0, ModMap{nullptr, 1, 1, 0, 0}, 0, 0, 0.f, nullptr,
-                   mseg, {w[0], w[1], w[2]}, {bias[0], bias[1], bias[2]}, {scale[0], scale[1], scale[2]},
-                   static_cast<const unsigned char*>(wpack), 1, a_bf16 ? 1 : 0, 0};
-    if (launch16_linear_wide(p, s)) return true;
-    if (a_bf16) {
-        g_k32_launch_error = "launch16_linear_seg3: bf16 token rows need the streamed kernel";
-        return true;
-    }
-    if (n <= 2048) {
-        hipLaunchKernelGGL(k16_linear_small, dim3((unsigned)(3 * mseg / 32), (unsigned)((n + 31) / 32)), dim3(64), 0, s, p);
-        return true;
-    }
-    const int nrt = (int)((n + 127) / 128), nct = 3 * mseg / 128;
-    hipLaunchKernelGGL(k16_linear_fast, dim3((unsigned)(8 * ((nrt + 7) / 8) * nct)), dim3(256), 0, s, p, nrt, nct);
-    return true;
 }
 void launch32_rope(float* buf, long ntok, int ld, long pos_div, int pos_mod, const float* inv_freq, hipStream_t s) {
     const long total = ntok * kH * 12 * 2;

@@ -885,71 +885,38 @@ __global__ void k32_sum_frames(const float* __restrict__ a, int B, int T, int L,
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------
-// Slices of the k32_dw / k16_dw grid over n: enough to fill the chip ONCE with 128 x 128 tiles at two workgroups per CU (a
-// 384 x 384 weight is only 9 of them); more slices only add partial-sum traffic (113 slices of a 384 x 384 weight: 66 MB
-// written and read back)
-static int dw_nsplit(long n, int m, int k, size_t part_floats) {
-    const int tiles = ((m + 127) / 128) * ((k + 127) / 128);
-    int nsplit = (int)((n + 511) / 512);
-    const int want = (512 + tiles - 1) / tiles;
-    if (nsplit > want) nsplit = want;
-    if (nsplit > 128) nsplit = 128;
-    if (nsplit < 1) nsplit = 1;
-    while (nsplit > 1 && (size_t)nsplit * m * (k + 1) > part_floats) --nsplit;
-    return nsplit;
-}
-// exact fp32 products (k32_dw)
-void launch32_dw(const float* dy, int ldy, const float* x, int ldx, long n, int m, int k, float* dw, float* part,
-                 size_t part_floats, hipStream_t s) {
-    const int nsplit = dw_nsplit(n, m, k, part_floats);
-    hipLaunchKernelGGL(k32_dw, dim3((m + 127) / 128, (k + 127) / 128, nsplit), dim3(256), 0, s, dy, ldy, x, ldx, n, m, k, part);
-    const long count = (long)m * k;
-    hipLaunchKernelGGL(k32_reduce_add, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, part, nsplit, count, count, dw);
-}
-// dW of nseg layers that share the input x and whose dY sit side by side (dy[n][j mseg + i]): one pass over x and dY,
-// m = nseg * mseg.  dw[j] / db[j] may be null.  Returns true if the bias gradients were computed by the same pass.
-int launch16_dw_wide(const float* dy, int ldy, const float* x, int ldx, long n, int m, int k, float* part, size_t part_floats,
-                     bool want_db, float** bpart_out, hipStream_t s, bool x_bf16, bool dy_bf16);   // k_wide16.hip
-bool launch16_dw_seg(const float* dy, int ldy, const float* x, int ldx, long n, int mseg, int nseg, int k, float* const* dw,
-                     float* const* db, float* part, size_t part_floats, hipStream_t s, bool x_bf16, bool dy_bf16) {
-    const int m = mseg * nseg;
-    bool want_db = false;
-    for (int j = 0; j < nseg; ++j) want_db = want_db || (db && db[j]);
-    const long count = (long)mseg * k;
-    auto reduce = [&](int nsplit, float* bpart) {
-        for (int j = 0; j < nseg; ++j) {
-            if (dw[j])
-                hipLaunchKernelGGL(k32_reduce_add, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, part + (size_t)j * count, nsplit,
-                                   (long)m * k, count, dw[j]);
-            if (bpart && db[j])
-                hipLaunchKernelGGL(k32_reduce_add, dim3((unsigned)((mseg + 255) / 256)), dim3(256), 0, s, bpart + (size_t)j * mseg, nsplit,
-                                   (long)m, (long)mseg, db[j]);
-        }
-    };
-    {   // 128 x 384 tiles (k_wide16.hip): each dY tile read once
-        float* bpart = nullptr;
-        if (const int ns = launch16_dw_wide(dy, ldy, x, ldx, n, m, k, part, part_floats, want_db, &bpart, s, x_bf16, dy_bf16)) {
-            reduce(ns, bpart);
-            return bpart != nullptr;
-        }
+int launch16_dw_wide(const DwParams& p, DwForm form, bool want_db, float** bpart_out, hipStream_t s);   // k_wide16.hip
+// the weight gradients of kernels.h DwParams: partial sums per n-slice (kernels.h dw_nsplit), then their reduction into dw[j] / db[j]
+void launch_dw(const DwParams& p, DwForm form, hipStream_t s) {
+    const int m = p.mseg * p.nseg, k = p.k;
+    const DwShape q = dw_shape(p);
+    if ((form != DwForm::F32 && form != DwForm::Plain && !dw_vec(q)) || (dw_wide(form) && (size_t)m * (k + 1) > p.part_floats) ||
+        p.nseg < 1 || p.nseg > 3 || (form == DwForm::F32 && p.nseg != 1)) {
+        g_k32_launch_error = "launch_dw: the operands do not fit the form";
+        return;
     }
-    if (x_bf16 || dy_bf16) {
-        g_k32_launch_error = "launch16_dw: bf16 X / dY rows need the wide kernel (n >= 4096)";
-        return false;
+    const bool want_db = dw_bias_rides(form, q, p.part_floats) && (p.db[0] || (p.nseg > 1 && p.db[1]) || (p.nseg > 2 && p.db[2]));
+    int nsplit;
+    float* bpart;   // the bias gradient's partials, behind the dW partials
+    if (dw_wide(form)) {
+        nsplit = launch16_dw_wide(p, form, want_db, &bpart, s);   // 128 x 384 tiles (k_wide16.hip): each dY tile read once
+    } else {
+        nsplit = dw_nsplit(p.n, m, k, p.part_floats);
+        bpart = want_db ? p.part + (size_t)nsplit * m * k : nullptr;
+        const dim3 grid((m + 127) / 128, (k + 127) / 128, nsplit);
+        if (form == DwForm::F32) hipLaunchKernelGGL(k32_dw, grid, dim3(256), 0, s, p.dy, p.ldy, p.x, p.ldx, p.n, m, k, p.part);
+        else if (form == DwForm::Fast) hipLaunchKernelGGL(k16_dw<true>, grid, dim3(256), 0, s, p.dy, p.ldy, p.x, p.ldx, p.n, m, k, p.part, bpart);
+        else hipLaunchKernelGGL(k16_dw<false>, grid, dim3(256), 0, s, p.dy, p.ldy, p.x, p.ldx, p.n, m, k, p.part, bpart);
     }
-    const int nsplit = dw_nsplit(n, m, k, part_floats);
-    const dim3 grid((m + 127) / 128, (k + 127) / 128, nsplit);
-    const bool fast = ((ldy | m | ldx | k) & 7) == 0 && (((unsigned long long)dy | (unsigned long long)x) & 15) == 0;
-    // fast path: the bias gradient (column sums of dY) rides along, partials behind the dW partials
-    float* bpart = (fast && want_db && (size_t)nsplit * m * (k + 1) <= part_floats) ? part + (size_t)nsplit * m * k : nullptr;
-    if (fast) hipLaunchKernelGGL(k16_dw<true>, grid, dim3(256), 0, s, dy, ldy, x, ldx, n, m, k, part, bpart);
-    else hipLaunchKernelGGL(k16_dw<false>, grid, dim3(256), 0, s, dy, ldy, x, ldx, n, m, k, part, bpart);
-    reduce(nsplit, bpart);
-    return bpart != nullptr;
-}
-bool launch16_dw(const float* dy, int ldy, const float* x, int ldx, long n, int m, int k, float* dw, float* part,
-                 size_t part_floats, hipStream_t s, float* db, bool x_bf16, bool dy_bf16) {
-    return launch16_dw_seg(dy, ldy, x, ldx, n, m, 1, k, &dw, &db, part, part_floats, s, x_bf16, dy_bf16);
+    const long count = (long)p.mseg * k;
+    for (int j = 0; j < p.nseg; ++j) {
+        if (p.dw[j])
+            hipLaunchKernelGGL(k32_reduce_add, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, p.part + (size_t)j * count, nsplit,
+                               (long)m * k, count, p.dw[j]);
+        if (bpart && p.db[j])
+            hipLaunchKernelGGL(k32_reduce_add, dim3((unsigned)((p.mseg + 255) / 256)), dim3(256), 0, s, bpart + (size_t)j * p.mseg, nsplit,
+                               (long)m, (long)p.mseg, p.db[j]);
+    }
 }
 // out[g][c] (ldo) += sum_{t in group g} a[t][c] * B(t, c); groups of tokens_per_group rows
 void launch32_colsum(const float* a, int lda, const float* b, int ldb, const float* roww, int mode, long nrows, int ncols,
@@ -970,41 +937,44 @@ void launch32_ln_bwd(const float* x, const float* dy, long nrows, const ModMap& 
     hipLaunchKernelGGL(k32_ln_bwd, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, s, x, dy, nrows, mm, scale_chunk, affine,
                        eps, dx, accumulate);
 }
-static bool slice_plan(long nrows, long tokens_per_group, int ncols, size_t part_floats, long* ng, int* rps, int* spg) {
-    *ng = (nrows + tokens_per_group - 1) / tokens_per_group;
-    *rps = 64;
-    while (*rps > 4 && *ng * ((tokens_per_group + *rps - 1) / *rps) < 256) *rps /= 2;   // a few hundred rows: still fill the chip
-    *spg = (int)((tokens_per_group + *rps - 1) / *rps);
-    while ((size_t)*ng * *spg * ncols > part_floats && *rps < (1 << 24)) {
-        *rps *= 2;
-        *spg = (int)((tokens_per_group + *rps - 1) / *rps);
+// the LN + modulate backward of kernels.h LnBwdParams
+void launch32_ln_mod_bwd(const LnBwdParams& p, LnBwdForm form, hipStream_t s) {
+    long ng; int rps, spg;
+    if (form == LnBwdForm::Sums) {   // one pass
+        if (p.dscale != p.dshift + kC || !slice_plan(p.nrows, p.tokens_per_group, 2 * kC, p.part_floats, &ng, &rps, &spg)) {
+            g_k32_launch_error = "launch32_ln_mod_bwd: the operands do not fit the one-pass form";
+            return;
+        }
+        hipLaunchKernelGGL(k32_ln_bwd_sums, dim3((unsigned)(ng * spg)), dim3(256), 0, s, p.x, p.dy, p.nrows, p.mm, p.scale_chunk, p.eps, p.dx,
+                           p.accumulate, p.tokens_per_group, rps, spg, p.part);
+        hipLaunchKernelGGL(k32_colsum_final, dim3((unsigned)(ng * ((2 * kC + 15) / 16))), dim3(256), 0, s, p.part, (int)ng, spg, 2 * kC,
+                           p.dshift, p.ldo);
+        return;
     }
-    return (size_t)*ng * *spg * ncols <= part_floats;
-}
-// dx (+)= LN'(dy (1 + scale)); out[g][0:384] += sum dy, out[g][384:768] += sum dy xhat  (out = the shift chunk of the group's
-// modulation-gradient row, the scale chunk right behind it).  false: partial buffer too small, nothing launched.
-bool launch32_ln_bwd_sums(const float* x, const float* dy, long nrows, const ModMap& mm, int scale_chunk, float eps, float* dx,
-                          int accumulate, long tokens_per_group, float* out, long ldo, float* part, size_t part_floats, hipStream_t s) {
-    long ng; int rps, spg;
-    if (!slice_plan(nrows, tokens_per_group, 2 * kC, part_floats, &ng, &rps, &spg)) return false;
-    hipLaunchKernelGGL(k32_ln_bwd_sums, dim3((unsigned)(ng * spg)), dim3(256), 0, s, x, dy, nrows, mm, scale_chunk, eps, dx, accumulate,
-                       tokens_per_group, rps, spg, part);
-    hipLaunchKernelGGL(k32_colsum_final, dim3((unsigned)(ng * ((2 * kC + 15) / 16))), dim3(256), 0, s, part, (int)ng, spg, 2 * kC, out, ldo);
-    return true;
-}
-// du = gate * dh; out[g][0:384] += sum dh u
-bool launch32_gate_bwd_sums(const float* dh, const float* u, long nrows, const ModMap& mm, int gate_chunk, float* du,
-                            long tokens_per_group, float* out, long ldo, float* part, size_t part_floats, hipStream_t s, bool du_bf16) {
-    long ng; int rps, spg;
-    if (!slice_plan(nrows, tokens_per_group, kC, part_floats, &ng, &rps, &spg)) return false;
-    hipLaunchKernelGGL(k32_gate_bwd_sums, dim3((unsigned)(ng * spg)), dim3(256), 0, s, dh, u, nrows, mm, gate_chunk, du, tokens_per_group,
-                       rps, spg, part, du_bf16 ? 1 : 0);
-    hipLaunchKernelGGL(k32_colsum_final, dim3((unsigned)(ng * ((kC + 15) / 16))), dim3(256), 0, s, part, (int)ng, spg, kC, out, ldo);
-    return true;
+    launch32_colsum(p.dy, kC, nullptr, 0, nullptr, 0, p.nrows, kC, p.tokens_per_group, 0.f, p.dshift, p.ldo, p.part, p.part_floats, s);
+    launch32_colsum(p.dy, kC, p.x, kC, nullptr, 2, p.nrows, kC, p.tokens_per_group, p.eps, p.dscale, p.ldo, p.part, p.part_floats, s);
+    launch32_ln_bwd(p.x, p.dy, p.nrows, p.mm, p.scale_chunk, 0, p.eps, p.dx, p.accumulate, s);
 }
 void launch32_gate_mul(const float* a, long nrows, const ModMap& mm, int gate_chunk, int gated, float* out, hipStream_t s) {
     const long n = nrows * kC;
     hipLaunchKernelGGL(k32_gate_mul, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, nrows, mm, gate_chunk, gated, out);
+}
+// the gated residual's backward of kernels.h GateBwdParams
+void launch32_gate_bwd(const GateBwdParams& p, GateBwdForm form, hipStream_t s) {
+    long ng; int rps, spg;
+    const bool fits = slice_plan(p.nrows, p.tokens_per_group, kC, p.part_floats, &ng, &rps, &spg);
+    if (form == GateBwdForm::Sums ? !fits : p.du_bf16) {   // (bf16 rows are the one-pass kernel's only)
+        g_k32_launch_error = "launch32_gate_bwd: the operands do not fit the form";
+        return;
+    }
+    if (form == GateBwdForm::Sums) {   // one pass
+        hipLaunchKernelGGL(k32_gate_bwd_sums, dim3((unsigned)(ng * spg)), dim3(256), 0, s, p.dh, p.u, p.nrows, p.mm, p.gate_chunk, p.du,
+                           p.tokens_per_group, rps, spg, p.part, p.du_bf16 ? 1 : 0);
+        hipLaunchKernelGGL(k32_colsum_final, dim3((unsigned)(ng * ((kC + 15) / 16))), dim3(256), 0, s, p.part, (int)ng, spg, kC, p.out, p.ldo);
+        return;
+    }
+    launch32_gate_mul(p.dh, p.nrows, p.mm, p.gate_chunk, 1, p.du, s);
+    launch32_colsum(p.dh, kC, p.u, kC, nullptr, 1, p.nrows, kC, p.tokens_per_group, 0.f, p.out, p.ldo, p.part, p.part_floats, s);
 }
 void launch32_attn_bwd(const float* qkv, int ld, const AxisMap& ax, const MaskMap& mk, const float* bias_k,
                        const float* bias_v, const float* inv_freq, const float* o, const float* dout, float* dqkv,

@@ -212,17 +212,16 @@ __global__ __launch_bounds__(256) void k16_pack_wstream(const float* __restrict_
     out[gid] = u32x4{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7])};
 }
 
-bool launch16_pack_wstream(const float* const* src, int nsrc, int seg, int ld, long n, int m, int k, int turned, void* out,
-                           hipStream_t s) {
-    const auto al = [](const void* q) { return ((unsigned long long)q & 15) == 0; };
-    if (n < 1024 || m % kWideCols || k % 64 || seg % 64 || nsrc < 1 || nsrc > 3 || (ld & 3)) return false;
-    if ((long)nsrc * seg != (turned ? k : m)) return false;
-    for (int i = 0; i < nsrc; ++i)
-        if (!al(src[i])) return false;
+void launch16_pack_wstream(const float* const* src, int nsrc, int seg, int ld, int m, int k, int turned, void* out, hipStream_t s) {
+    bool ok = m % kWideCols == 0 && k % 64 == 0 && seg % 64 == 0 && nsrc >= 1 && nsrc <= 3 && (ld & 3) == 0 && (long)nsrc * seg == (turned ? k : m);
+    for (int i = 0; ok && i < nsrc; ++i) ok = ((unsigned long long)src[i] & 15) == 0;
+    if (!ok) {
+        g_k32_launch_error = "launch16_pack_wstream: the weights do not fit the streamed form";
+        return;
+    }
     const long items = (long)m * k / 8;
     hipLaunchKernelGGL(k16_pack_wstream, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, src[0], src[nsrc > 1 ? 1 : 0],
                        src[nsrc > 2 ? 2 : 0], seg, ld, m, k, turned, static_cast<u32x4*>(out));
-    return true;
 }
 
 // Requires (launcher): p.wpack (k16_pack_wstream of this layer), k % 64 == 0, m % 384 == 0, 16-byte aligned token operand.
@@ -481,45 +480,34 @@ __global__ __launch_bounds__(512) void k16_dw_wide(const float* __restrict__ dy,
     }
 }
 
-bool launch16_linear_wide(const LinearParams& p, hipStream_t s) {
-    const auto al = [](const void* q) { return ((unsigned long long)q & 15) == 0; };
-    bool ok = !p.wtrans && p.k % 64 == 0 && (p.lda & (p.a_bf16 ? 7 : 3)) == 0 && (p.ldw & 3) == 0 && al(p.a) && p.m > 128 && p.n >= 1024;
-    if (p.seg_cols) ok = ok && p.seg_cols % kWideCols == 0 && al(p.w_seg[0]) && al(p.w_seg[1]) && al(p.w_seg[2]);
-    else ok = ok && al(p.w);
-    if (!ok) return false;
+// (launch_linear has checked the operands against the form)
+void launch16_linear_wide(const LinearParams& p, LinearForm form, hipStream_t s) {
     const int nrt = (int)((p.n + kWideRows - 1) / kWideRows), ncg = (p.m + kWideCols - 1) / kWideCols;
-    if (p.wpack && p.m % kWideCols == 0) {
-        const dim3 grid((unsigned)(8 * ((nrt + 7) / 8) * ncg));
-        if (p.a_bf16) hipLaunchKernelGGL(k16_linear_wdma<true>, grid, dim3(512), 0, s, p, nrt, ncg);
-        else hipLaunchKernelGGL(k16_linear_wdma<false>, grid, dim3(512), 0, s, p, nrt, ncg);
-        return true;
-    }
-    if (p.a_bf16) return false;   // only the streamed kernel reads bf16 rows (the caller checks eligibility first)
-    hipLaunchKernelGGL(k16_linear_wide, dim3((unsigned)(8 * ((nrt + 7) / 8) * ncg)), dim3(512), 0, s, p, nrt, ncg);
-    return true;
+    const dim3 grid((unsigned)(8 * ((nrt + 7) / 8) * ncg));
+    if (form == LinearForm::StreamBf16Rows) hipLaunchKernelGGL(k16_linear_wdma<true>, grid, dim3(512), 0, s, p, nrt, ncg);
+    else if (form == LinearForm::StreamF32Rows) hipLaunchKernelGGL(k16_linear_wdma<false>, grid, dim3(512), 0, s, p, nrt, ncg);
+    else hipLaunchKernelGGL(k16_linear_wide, grid, dim3(512), 0, s, p, nrt, ncg);
 }
 
-// Same contract as the k16_dw launch inside launch32_dw_seg (k_fp32_bwd.hip): fills part[nsplit][m][k] (and bpart[nsplit][m]).
-// Returns the number of slices used, 0 if the shape is not eligible (nothing launched).
-int launch16_dw_wide(const float* dy, int ldy, const float* x, int ldx, long n, int m, int k, float* part, size_t part_floats,
-                     bool want_db, float** bpart_out, hipStream_t s, bool x_bf16, bool dy_bf16) {
-    const bool fast = ((ldy | m | ldx | k) & 7) == 0 && (((unsigned long long)dy | (unsigned long long)x) & 15) == 0;
-    if (!fast || n < 4096) return 0;
+// The Wide* forms of launch_dw (k_fp32_bwd.hip), same contract as its k16_dw launch: fills part[nsplit][m][k] (and, want_db,
+// *bpart_out = [nsplit][m] behind it); returns the number of slices (dw_form has checked that one fits part_floats).
+int launch16_dw_wide(const DwParams& p, DwForm form, bool want_db, float** bpart_out, hipStream_t s) {
+    const int m = p.mseg * p.nseg, k = p.k;
     const int mt = (m + kWideRows - 1) / kWideRows, kg = (k + kWideCols - 1) / kWideCols, nt = mt * kg;
     // one workgroup per CU (147 KB of LDS): as many n-slices as fill the chip ONCE -- rounded DOWN: with 86 slices x 3 tiles =
     // 258 workgroups on 256 CUs the last two wait for a free CU and the launch takes two rounds instead of one
     int nsplit = 256 / nt;
-    const int cap = (int)((n + 255) / 256);
+    const int cap = (int)((p.n + 255) / 256);
     if (nsplit > cap) nsplit = cap;
     if (nsplit < 1) nsplit = 1;
-    while (nsplit > 1 && (size_t)nsplit * m * (k + 1) > part_floats) --nsplit;
-    if ((size_t)nsplit * m * (k + 1) > part_floats) return 0;
-    float* bpart = want_db ? part + (size_t)nsplit * m * k : nullptr;
+    while (nsplit > 1 && (size_t)nsplit * m * (k + 1) > p.part_floats) --nsplit;
+    float* bpart = want_db ? p.part + (size_t)nsplit * m * k : nullptr;
     const dim3 grid((unsigned)(8 * ((nsplit + 7) / 8) * nt));
-    if (x_bf16 && dy_bf16) hipLaunchKernelGGL((k16_dw_wide<true, true>), grid, dim3(512), 0, s, dy, ldy, x, ldx, n, m, k, nsplit, part, bpart);
-    else if (x_bf16) hipLaunchKernelGGL((k16_dw_wide<true, false>), grid, dim3(512), 0, s, dy, ldy, x, ldx, n, m, k, nsplit, part, bpart);
-    else if (dy_bf16) hipLaunchKernelGGL((k16_dw_wide<false, true>), grid, dim3(512), 0, s, dy, ldy, x, ldx, n, m, k, nsplit, part, bpart);
-    else hipLaunchKernelGGL((k16_dw_wide<false, false>), grid, dim3(512), 0, s, dy, ldy, x, ldx, n, m, k, nsplit, part, bpart);
+    const dim3 blk(512);
+    if (form == DwForm::WideXbfDYbf) hipLaunchKernelGGL((k16_dw_wide<true, true>), grid, blk, 0, s, p.dy, p.ldy, p.x, p.ldx, p.n, m, k, nsplit, p.part, bpart);
+    else if (form == DwForm::WideXbf) hipLaunchKernelGGL((k16_dw_wide<true, false>), grid, blk, 0, s, p.dy, p.ldy, p.x, p.ldx, p.n, m, k, nsplit, p.part, bpart);
+    else if (form == DwForm::WideDYbf) hipLaunchKernelGGL((k16_dw_wide<false, true>), grid, blk, 0, s, p.dy, p.ldy, p.x, p.ldx, p.n, m, k, nsplit, p.part, bpart);
+    else hipLaunchKernelGGL((k16_dw_wide<false, false>), grid, blk, 0, s, p.dy, p.ldy, p.x, p.ldx, p.n, m, k, nsplit, p.part, bpart);
     *bpart_out = bpart;
     return nsplit;
 }

@@ -204,7 +204,7 @@ struct FloatChunk {
 
 // Kernel forms: one value = one kernel instantiation.  The orchestration (api.hip) decides the form of a launch and fills the
 // operands the form reads; the launcher switches on it.  A form whose operands are missing launches nothing and leaves a message
-// for k32_take_launch_error.
+// for k32_take_launch_error (error -7 from the entry point).
 enum class QkvForm {
     Small,             // k_ln_qkv<true>: SMALL layout (L <= 8)
     Panel4,            // k_ln_qkv<false>: fragment layout, four waves per 64-row panel
@@ -259,34 +259,139 @@ void launch_masked_mse(const float* pred, const float* target, const float* mask
                        hipStream_t s, float* scratch = nullptr, size_t scratch_floats = 0, float* den_out = nullptr);
 void launch_ipa_attn(const IpaAttnParams& p, hipStream_t s);
 
-// fp32-operand path (k_fp32.hip)
+// fp32-operand path (k_fp32.hip) and the training step (k_fp32_bwd.hip, k_wide16.hip, k_attn16.hip)
 extern thread_local const char* g_k32_launch_error;   // set by a launcher that refused a shape (nothing launched)
 const char* k32_take_launch_error();                  // ... and cleared by the entry point that reports it
+
+// Kernel forms of the training step, as above: one value = one instantiation or one fixed launch sequence.  The form
+// functions below are pure host functions of the operand mode (bf16: option train_precision = 16), the shape, the strides and the
+// 16-byte alignment of the operands; the step evaluates them once per sub-layer, before its first launch (train.inc *Plan), and
+// the launchers check with the same predicates that the operands fit the form they are handed.
+enum class LinearForm {
+    F32,              // k32_linear: exact fp32 products
+    StreamF32Rows,    // k16_linear_wdma<false>: the weight as a bf16 fragment stream (wpack), fp32 token rows
+    StreamBf16Rows,   // k16_linear_wdma<true>: ... token rows stored as bf16 (a_bf16)
+    Wide,             // k16_linear_wide: 128 x 384 tiles, fp32 weight rows
+    Small,            // k16_linear_small: one wave per 32 x 32 tile (at most 2048 rows)
+    Fast,             // k16_linear_fast
+    Plain             // k16_linear: any stride, alignment or wtrans
+};
+enum class DwForm {
+    F32,                                        // k32_dw
+    Wide, WideXbf, WideDYbf, WideXbfDYbf,       // k16_dw_wide<XBF, DYBF>: X / dY stored as bf16 rows
+    Fast, Plain                                 // k16_dw<true>, k16_dw<false>
+};
+enum class GateBwdForm { Sums, MulColsum };     // k32_gate_bwd_sums + k32_colsum_final | k32_gate_mul, k32_colsum + k32_colsum_final
+enum class LnBwdForm { Sums, ColsumsLnBwd };    // k32_ln_bwd_sums + k32_colsum_final | two launch32_colsum, k32_ln_bwd
+enum class TrainAttnForm {
+    Exact,     // k32_attn | k32_attn_bwd_q, k32_attn_bwd_kv (q, k rotated by k32_rope before, dq, dk taken back by k32_rope_bwd)
+    Chunked,   // k16_attn<8 | 4> | k16_attn_bwd_q<4>, k16_attn_bwd_kv<4> (q, k rotated before; dq, dk come back unrotated)
+    Seq,       // k16_attn_seq | k16_attn_bwd_seq: axes of 129 .. 256 positions (attn16_seq_form)
+    SeqRope    // ... which rotate q, k while they convert them: no k32_rope pass, the tape keeps them unrotated
+};
+inline bool linear_streams(LinearForm f) { return f == LinearForm::StreamF32Rows || f == LinearForm::StreamBf16Rows; }
+inline bool dw_wide(DwForm f) { return f >= DwForm::Wide && f <= DwForm::WideXbfDYbf; }
+inline bool dw_x_bf16(DwForm f) { return f == DwForm::WideXbf || f == DwForm::WideXbfDYbf; }
+inline bool dw_dy_bf16(DwForm f) { return f == DwForm::WideDYbf || f == DwForm::WideXbfDYbf; }
+inline bool attn_seq(TrainAttnForm f) { return f == TrainAttnForm::Seq || f == TrainAttnForm::SeqRope; }
+
+// y[n][m] = a[n][k] w[m][k]^T as the form function sees it.  ldw: row stride of the fp32 weight; *_al: 16-byte aligned (w_al: every
+// segment's weight); a_bf16: the token rows are stored as bf16
+struct LinShape { long n; int m, k, lda, ldw, wtrans; bool a_al, w_al, a_bf16; };
+inline bool linear_vec(const LinShape& q) {   // 16-byte operand loads: every form but F32 and Plain
+    return !q.wtrans && q.k % 64 == 0 && (q.lda & (q.a_bf16 ? 7 : 3)) == 0 && (q.ldw & 3) == 0 && q.a_al && q.w_al;
+}
+// stream: a bf16 fragment stream of the weight is wanted where the launch is big enough for the streamed 128 x 384 kernel
+inline LinearForm linear_form(bool bf16, const LinShape& q, bool stream) {
+    if (!bf16) return LinearForm::F32;
+    if (!linear_vec(q)) return LinearForm::Plain;
+    if (stream && q.n >= 1024 && q.m % 384 == 0) return q.a_bf16 ? LinearForm::StreamBf16Rows : LinearForm::StreamF32Rows;
+    if (q.n >= 1024 && q.m > 128) return LinearForm::Wide;
+    return q.n <= 2048 ? LinearForm::Small : LinearForm::Fast;
+}
+
+// dW[m][k] += dy[n][m]^T x[n][k] in n-slices whose partial sums go to part[nsplit][m][k] (+ [nsplit][m] of the bias gradient)
+struct DwShape { long n; int m, k, ldy, ldx; bool al; };   // al: dy and x 16-byte aligned
+inline bool dw_vec(const DwShape& q) { return ((q.ldy | q.m | q.ldx | q.k) & 7) == 0 && q.al; }
+// Slices of the k32_dw / k16_dw grid over n: enough to fill the chip ONCE with 128 x 128 tiles at two workgroups per CU (a
+// 384 x 384 weight is only 9 of them); more slices only add partial-sum traffic (113 slices of a 384 x 384 weight: 66 MB
+// written and read back)
+inline int dw_nsplit(long n, int m, int k, size_t part_floats) {
+    const int tiles = ((m + 127) / 128) * ((k + 127) / 128);
+    int nsplit = (int)((n + 511) / 512);
+    const int want = (512 + tiles - 1) / tiles;
+    if (nsplit > want) nsplit = want;
+    if (nsplit > 128) nsplit = 128;
+    if (nsplit < 1) nsplit = 1;
+    while (nsplit > 1 && (size_t)nsplit * m * (k + 1) > part_floats) --nsplit;
+    return nsplit;
+}
+inline DwForm dw_form(bool bf16, const DwShape& q, size_t part_floats, bool x_bf16, bool dy_bf16) {
+    if (!bf16) return DwForm::F32;
+    if (!dw_vec(q)) return DwForm::Plain;
+    if (q.n >= 4096 && (size_t)q.m * (q.k + 1) <= part_floats)
+        return x_bf16 ? (dy_bf16 ? DwForm::WideXbfDYbf : DwForm::WideXbf) : (dy_bf16 ? DwForm::WideDYbf : DwForm::Wide);
+    return DwForm::Fast;
+}
+// whether the pass also yields the bias gradient (column sums of dY, partials behind the dW partials); else launch32_colsum
+inline bool dw_bias_rides(DwForm f, const DwShape& q, size_t part_floats) {
+    return dw_wide(f) || (f == DwForm::Fast && (size_t)dw_nsplit(q.n, q.m, q.k, part_floats) * q.m * (q.k + 1) <= part_floats);
+}
+
+// slices of the fused element-wise backward + column-sum kernels; false: their partial sums do not fit part_floats
+inline bool slice_plan(long nrows, long tokens_per_group, int ncols, size_t part_floats, long* ng, int* rps, int* spg) {
+    *ng = (nrows + tokens_per_group - 1) / tokens_per_group;
+    *rps = 64;
+    while (*rps > 4 && *ng * ((tokens_per_group + *rps - 1) / *rps) < 256) *rps /= 2;   // a few hundred rows: still fill the chip
+    *spg = (int)((tokens_per_group + *rps - 1) / *rps);
+    while ((size_t)*ng * *spg * ncols > part_floats && *rps < (1 << 24)) {
+        *rps *= 2;
+        *spg = (int)((tokens_per_group + *rps - 1) / *rps);
+    }
+    return (size_t)*ng * *spg * ncols <= part_floats;
+}
+inline bool slices_fit(long nrows, long tokens_per_group, int ncols, size_t part_floats) {
+    long ng; int rps, spg;
+    return slice_plan(nrows, tokens_per_group, ncols, part_floats, &ng, &rps, &spg);
+}
+inline GateBwdForm gate_bwd_form(long nrows, long tokens_per_group, size_t part_floats) {
+    return slices_fit(nrows, tokens_per_group, kC, part_floats) ? GateBwdForm::Sums : GateBwdForm::MulColsum;
+}
+// adjacent: the scale chunk lies right behind the shift chunk in the modulation row (one pass writes both gradient chunks)
+inline LnBwdForm ln_bwd_form(long nrows, long tokens_per_group, size_t part_floats, bool adjacent) {
+    return adjacent && slices_fit(nrows, tokens_per_group, 2 * kC, part_floats) ? LnBwdForm::Sums : LnBwdForm::ColsumsLnBwd;
+}
+bool attn16_seq_form(const AxisMap& ax);   // k_attn16.hip: 129 .. 256 positions
+inline TrainAttnForm train_attn_form(bool bf16, const AxisMap& ax) {
+    return !bf16 ? TrainAttnForm::Exact : attn16_seq_form(ax) ? TrainAttnForm::SeqRope : TrainAttnForm::Chunked;
+}
+
 void launch32_ln_mod(const float* x, long nrows, const ModMap& mm, int shift_chunk, int scale_chunk, int affine, float eps,
-                     float* y, hipStream_t s, float* keep = nullptr, bool y_bf16 = false);   // keep: copy of x (training tape); y_bf16: y holds bf16 rows
-// exact fp32 products (k32_linear)
-void launch32_linear(const float* a, int lda, const float* w, int ldw, const float* bias, long n, int m, int k, int mode,
-                     float* c, int ldc, int col0, const ModMap& mm, int gate_chunk, int gated, float scalar, hipStream_t s,
-                     int wtrans = 0, float* c2 = nullptr);
-// the same layer with bf16-rounded operands on the bf16 MFMA, fp32 accumulation (the training step's train_precision = 16)
-void launch16_linear(const float* a, int lda, const float* w, int ldw, const float* bias, long n, int m, int k, int mode,
-                     float* c, int ldc, int col0, const ModMap& mm, int gate_chunk, int gated, float scalar, hipStream_t s,
-                     int wtrans = 0, float* c2 = nullptr,
-                     const void* wpack = nullptr,    // launch16_pack_wstream's bf16 fragment stream of w (k_wide16.hip)
-                     int flags = 0);                 // 1: a is bf16 rows (needs wpack), 2: c2 (mode 6) is written as bf16,
-                                                     // 4: the result of mode 7 is written as bf16
+                     float* y, hipStream_t s, float* keep, bool y_bf16);   // keep (nullable): copy of x (training tape); y_bf16: y holds bf16 rows
+// The linear layer (linear.h LinearParams): launch32_linear = the F32 form (the sampler's precision-32 path calls it directly).
+// Stream*: p.wpack from launch16_pack_wstream, p.a_bf16 as the form says; p.c_bf16 with mode kLinGeluBwd only.
+struct LinearParams;
+void launch32_linear(const LinearParams& p, hipStream_t s);
+void launch_linear(const LinearParams& p, LinearForm form, hipStream_t s);
+// bf16 fragment stream of a weight for k16_linear_wdma: W(col, kk), col < m (a multiple of 384), kk < k (a multiple of 64),
+// from nsrc <= 3 16-byte aligned fp32 matrices of row stride ld: turned == 0: src[col / seg] is [seg][k] (layers side by side along
+// the columns); turned == 1: src[kk / seg] is [seg][m] (dX = dY W: the contraction runs over the weights' rows).  out: m * k * 2 bytes.
+void launch16_pack_wstream(const float* const* src, int nsrc, int seg, int ld, int m, int k, int turned, void* out, hipStream_t s);
 // backward kernels of the training step (k_fp32_bwd.hip)
-// dW += dY^T X, exact fp32 products (k32_dw)
-void launch32_dw(const float* dy, int ldy, const float* x, int ldx, long n, int m, int k, float* dw, float* part,
-                 size_t part_floats, hipStream_t s);
-// ... with bf16-rounded operands.  db != nullptr: the bias gradient db[m] += column sums of dY may be computed by the same pass
-// (returns true if it was; otherwise the caller runs launch32_colsum)
-bool launch16_dw_seg(const float* dy, int ldy, const float* x, int ldx, long n, int mseg, int nseg, int k, float* const* dw,
-                     float* const* db, float* part, size_t part_floats, hipStream_t s,
-                     bool x_bf16 = false, bool dy_bf16 = false);   // nseg layers sharing x, dY side by side; *_bf16: stored as bf16 rows (wide kernel only)
-bool launch16_dw(const float* dy, int ldy, const float* x, int ldx, long n, int m, int k, float* dw, float* part,
-                 size_t part_floats, hipStream_t s, float* db = nullptr, bool x_bf16 = false,
-                 bool dy_bf16 = false);   // x_bf16 / dy_bf16: x / dy are bf16 rows (wide kernel only)
+// dW[j] += dY_j^T X of nseg <= 3 layers that share the input x and whose dY sit side by side (dy[n][j mseg + i]): one pass over x
+// and dY.  dw[j] / db[j] may be null; db[j] += column sums of dY_j where dw_bias_rides(form, ...) -- else the caller runs launch32_colsum.
+struct DwParams {
+    const float* dy; int ldy;
+    const float* x; int ldx;
+    long n; int mseg, nseg, k;
+    float* dw[3];
+    float* db[3];
+    float* part; size_t part_floats;
+};
+inline DwShape dw_shape(const DwParams& p) {
+    return DwShape{p.n, p.mseg * p.nseg, p.k, p.ldy, p.ldx, (((unsigned long long)p.dy | (unsigned long long)p.x) & 15) == 0};
+}
+void launch_dw(const DwParams& p, DwForm form, hipStream_t s);
 void launch32_colsum(const float* a, int lda, const float* b, int ldb, const float* roww, int mode, long nrows, int ncols,
                      long tokens_per_group, float eps, float* out, long ldo, float* part, size_t part_floats, hipStream_t s);
 void launch32_ln_bwd(const float* x, const float* dy, long nrows, const ModMap& mm, int scale_chunk, int affine, float eps,
@@ -294,18 +399,18 @@ void launch32_ln_bwd(const float* x, const float* dy, long nrows, const ModMap& 
 void launch32_gate_mul(const float* a, long nrows, const ModMap& mm, int gate_chunk, int gated, float* out, hipStream_t s);
 void launch32_attn_bwd(const float* qkv, int ld, const AxisMap& ax, const MaskMap& mk, const float* bias_k,
                        const float* bias_v, const float* inv_freq, const float* o, const float* dout, float* dqkv,
-                       float* stats, float* dbias, hipStream_t s, const float* lse_in = nullptr);
+                       float* stats, float* dbias, hipStream_t s, const float* lse_in);
 void launch32_rope_bwd(float* buf, long ntok, int ld, long pos_div, int pos_mod, const float* inv_freq, float qscale,
                        hipStream_t s);
 void launch32_loss_grad(const float* pred, const float* target, const float* mask, long per_sample, long B, float* den,
-                        float* dpred, hipStream_t s, float* scratch = nullptr, size_t scratch_floats = 0);
+                        float* dpred, hipStream_t s, float* scratch, size_t scratch_floats);
 void launch32_sum_frames(const float* a, int B, int T, int L, float* out, hipStream_t s);
 void launch32_ipa_bwd(const IpaAttnParams& f, const float* dfeat, float* dproj, float* dhw, float* qrec, float* dheadw,
-                      hipStream_t s, float* part = nullptr, size_t part_floats = 0);   // part: scratch for the sliced form
+                      hipStream_t s, float* part, size_t part_floats);   // part: scratch for the sliced form
 void launch32_gated_add(float* h, const float* u, long nrows, const ModMap& mm, int gate_chunk, int gated, hipStream_t s);
 void launch32_gated_sum(float* h, const float* x, const float* u, long nrows, const ModMap& mm, int gate_chunk, hipStream_t s);
 void launch32_gate_ln_mod(const float* xp, const float* up, long nrows, const ModMap& gm, int gate_chunk, const ModMap& mm,
-                          int shift_chunk, int scale_chunk, float eps, float* y, float* keep, hipStream_t s, bool y_bf16 = false);
+                          int shift_chunk, int scale_chunk, float eps, float* y, float* keep, hipStream_t s, bool y_bf16);
 void launch32_indicator(const int64_t* cm, long n, float* ind0, float* ind1, hipStream_t s);
 void launch32_embed_rows_bwd(const float* dx0, const int64_t* aatype, int ngroups, int B, int L, float* dw, hipStream_t s);
 void launch32_temb_bwd(const float* t_rows, int nrows, float tmul, const float* w0, const float* b0, const float* w2,
@@ -314,35 +419,43 @@ void launch32_rope(float* buf, long ntok, int ld, long pos_div, int pos_mod, con
 // out[nb][m] = x[nb][K] W[K][m], nb small and K long (split over K); false: partial buffer too small, nothing launched
 bool launch32_skinny_wt(const float* x, int ldx, const float* W, int ldw, int nb, int m, long K, float* out, float* part,
                         size_t part_floats, hipStream_t s);
-// fused element-wise backward + adaLN column sums (k_fp32_bwd.hip); false: partial buffer too small, nothing launched
-bool launch32_ln_bwd_sums(const float* x, const float* dy, long nrows, const ModMap& mm, int scale_chunk, float eps, float* dx,
-                          int accumulate, long tokens_per_group, float* out, long ldo, float* part, size_t part_floats, hipStream_t s);
-bool launch32_gate_bwd_sums(const float* dh, const float* u, long nrows, const ModMap& mm, int gate_chunk, float* du,
-                            long tokens_per_group, float* out, long ldo, float* part, size_t part_floats, hipStream_t s,
-                            bool du_bf16 = false);   // du_bf16: du is written as bf16 rows
-void launch32_transpose(const float* src, int rows, int cols, float* dst, hipStream_t s, int ldd = 0);   // dst[c][r] (ld ldd, default rows) = src[r][c]
-bool launch16_linear_seg3(const float* a, int lda, const float* const* w, int ldw, const float* const* bias, const float* scale,
-                          long n, int mseg, int k, float* c, int ldc, int col0, hipStream_t s, const void* wpack = nullptr,
-                          bool a_bf16 = false);   // a_bf16: `a` holds bf16 rows (lda in elements; the streamed kernel only)
-// bf16 fragment stream of a weight for k16_linear_wdma: W(col, kk), col < m (a multiple of 384), kk < k (a multiple of 64),
-// from nsrc <= 3 fp32 matrices of row stride ld: turned == 0: src[col / seg] is [seg][k] (layers side by side along the
-// columns); turned == 1: src[kk / seg] is [seg][m] (dX = dY W: the contraction runs over the weights' rows).
-// false: shape not eligible for the streamed kernel (nothing launched).  out: m * k * 2 bytes.
-bool launch16_pack_wstream(const float* const* src, int nsrc, int seg, int ld, long n, int m, int k, int turned, void* out, hipStream_t s);
-// bf16-operand (MFMA) attention of the training step, k_attn16.hip: same arguments as launch32_attn / launch32_attn_bwd; the
-// backward needs the forward's log-sum-exp tape (lse_in != nullptr).
-// seq_form: the sequence-resident kernels, on axes where attn16_seq_form(ax) (129 .. 256 positions); else the chunked ones.
-// rope_inside (sequence-resident kernels only): q, k of `qkv` are NOT rotated yet -- the kernels rotate them while they convert
-// them (no k32_rope pass); forward and backward of a sub-layer must agree on it
-bool attn16_seq_form(const AxisMap& ax);
-void launch16_attn(const float* qkv, int ld, const AxisMap& ax, const MaskMap& mk, const float* bias_k, const float* bias_v,
-                   const float* inv_freq, float* out, hipStream_t s, float* lse_out, bool seq_form, bool rope_inside);
-void launch16_attn_bwd(const float* qkv, int ld, const AxisMap& ax, const MaskMap& mk, const float* bias_k,
-                       const float* bias_v, const float* inv_freq, const float* o, const float* dout, float* dqkv,
-                       float* stats, float* dbias, hipStream_t s, const float* lse_in, bool seq_form, bool rope_inside,
-                       bool out_bf16 = false);   // out_bf16 (sequence-resident form only): dqkv is written as bf16 rows (ld in elements)
+// gated residual h_out = h_in + gate * u, backward: du = gate * dh (du_bf16: written as bf16 rows, Sums only);
+// out[g][0:384] += sum over group g of dh u.  part: partial sums (slice_plan)
+struct GateBwdParams {
+    const float *dh, *u;
+    long nrows; ModMap mm; int gate_chunk;
+    float* du; bool du_bf16;
+    long tokens_per_group; float* out; long ldo;
+    float* part; size_t part_floats;
+};
+void launch32_gate_bwd(const GateBwdParams& p, GateBwdForm form, hipStream_t s);
+// LN + modulate backward: dx (+)= LN'(dy (1 + scale)); dshift[g][0:384] += sum dy, dscale[g][0:384] += sum dy xhat (the group's
+// modulation-gradient row; Sums: the scale chunk right behind the shift chunk)
+struct LnBwdParams {
+    const float *x, *dy;
+    long nrows; ModMap mm; int scale_chunk; float eps;
+    float* dx; int accumulate;
+    long tokens_per_group; float *dshift, *dscale; long ldo;
+    float* part; size_t part_floats;
+};
+void launch32_ln_mod_bwd(const LnBwdParams& p, LnBwdForm form, hipStream_t s);
+void launch32_transpose(const float* src, int rows, int cols, float* dst, hipStream_t s, int ldd);   // dst[c][r] (ld ldd) = src[r][c]
+// Attention of the training step with its tape (lse: log-sum-exp per (token, head), written by the forward pass, read by the
+// backward pass).  Exact: k_fp32.hip / k_fp32_bwd.hip; the bf16-operand (MFMA) forms: k_attn16.hip.  dqkv_bf16 (Seq* only): dq | dk |
+// dv are written as bf16 rows (ld in elements).  Forward and backward of a sub-layer take the same form.
+struct TrainAttnParams {
+    const float* qkv; int ld;
+    AxisMap ax; MaskMap mk;
+    const float *bias_k, *bias_v, *inv_freq;
+    float *out, *lse;
+    const float* dout;                  // backward only, as what follows
+    float *dqkv, *stats, *dbias;
+    bool dqkv_bf16;
+};
+void launch_train_attn(const TrainAttnParams& p, TrainAttnForm form, hipStream_t s);
+void launch_train_attn_bwd(const TrainAttnParams& p, TrainAttnForm form, hipStream_t s);
 void launch32_attn(const float* qkv, int ld, const AxisMap& ax, const MaskMap& mk, const float* bias_k, const float* bias_v,
-                   const float* inv_freq, float* out, hipStream_t s, float* lse_out = nullptr);
+                   const float* inv_freq, float* out, hipStream_t s, float* lse_out);
 
 // optimiser (k_optim.hip)
 void launch_sumsq(const float* g, long n, float scale, float* partial, int nblocks, float* out, hipStream_t s);

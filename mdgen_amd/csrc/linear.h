@@ -5,6 +5,11 @@
 
 namespace mdg {
 
+// LinearParams::mode by name (host code; the kernels switch on the numbers)
+enum LinearMode : int {
+    kLinStore = 0, kLinGelu = 1, kLinGated = 2, kLinEuler = 3, kLinScaled = 4, kLinAccumulate = 5, kLinStoreGelu = 6, kLinGeluBwd = 7
+};
+
 // C[n][col0 + m] (ldc) = sum_k A[n][k] (lda) W[m][k] (ldw) + bias[m].
 struct LinearParams {
     const float* a; int lda;

@@ -12,9 +12,45 @@
 
 namespace {
 
-struct SubTapeAttn { float *h_in, *y, *qkv, *att, *u, *lse; };   // y = LN-modulate(h_in): the q/k/v layers' input, taped
-struct SubTapeMlp { float *h_in, *y, *pre, *hid, *u; };   // hid = gelu(pre): fc2's input, taped rather than recomputed
-struct SubTapeIpa { float *h_in, *proj, *feat, *stats; };
+// ---- the plan of a sub-layer: the form of every launch whose kernel depends on the operand mode, the row count, the axis or the
+// alignment of the weights (kernels.h form functions), made once before the sub-layer's first launch (plan_* below) and kept beside
+// its tape entry: the backward pass reads what the forward pass decided.
+enum class DxRoute {
+    Streamed,       // W^T as a bf16 fragment stream, packed in front of the product (launch16_pack_wstream, turned)
+    TurnedWeight,   // W^T as an fp32 matrix (turned()): the forward layers' kernels
+    Wtrans          // W as stored, LinearParams::wtrans
+};
+struct DxPlan { DxRoute route; LinearForm form; };
+struct DwPlan { DwForm form; bool bias_rides; };   // bias_rides: the pass yields the bias gradient too (kernels.h dw_bias_rides)
+struct AttnPlan {
+    bool rows16;                 // y and du are stored as bf16 rows (see plan_attn) ...
+    bool dqkv16;                 // ... and dq | dk | dv (sequence-resident attention only)
+    bool qkv_one_pass;           // q | k | v as one product of 1152 columns (form qkv[0]), else three
+    LinearForm qkv[3], out;
+    TrainAttnForm attn;
+    GateBwdForm gate;
+    LnBwdForm ln;
+    DxPlan dx_out, dx_qkv;       // dx_qkv / dw_qkv: bf16 operands: one product over q | k | v; fp32: each of the three
+    DwPlan dw_out, dw_qkv;
+};
+struct MlpPlan {
+    bool rows16;                 // y, hid, du and d pre are stored as bf16 rows
+    LinearForm fc1, fc2;
+    GateBwdForm gate;
+    LnBwdForm ln;
+    DxPlan dx_fc2, dx_fc1;
+    DwPlan dw_fc2, dw_fc1;
+};
+struct IpaPlan {                 // [j]: q | kv | q_points | kv_points (kIpaProjCols)
+    LinearForm proj[4], out;
+    DxPlan dx_proj[4], dx_out;
+    DwPlan dw_proj[4], dw_out;
+};
+struct FinalPlan { LinearForm lin; DxPlan dx; DwPlan dw; LnBwdForm ln; };
+
+struct SubTapeAttn { float *h_in, *y, *qkv, *att, *u, *lse; AttnPlan plan; };   // y = LN-modulate(h_in): the q/k/v layers' input, taped
+struct SubTapeMlp { float *h_in, *y, *pre, *hid, *u; MlpPlan plan; };   // hid = gelu(pre): fc2's input, taped rather than recomputed
+struct SubTapeIpa { float *h_in, *proj, *feat, *stats; IpaPlan plan; };
 
 struct Train {
     Run r;
@@ -22,7 +58,7 @@ struct Train {
     float* grads;
     const int64_t* goff;     // per weight slot; < 0: no gradient wanted
     // Operand mode of the call's linear layers / weight gradients (option train_precision): false = exact fp32 products
-    // (k32_linear / k32_dw), true = bf16-rounded operands on the bf16 MFMA with fp32 accumulation (launch16_linear / launch16_dw).
+    // (k32_linear / k32_dw), true = bf16-rounded operands on the bf16 MFMA with fp32 accumulation (the k16_* forms).
     bool bf16 = false;
     // scratch (backward)
     float *dh, *dy, *ytmp, *act, *stats, *part, *cpart, *dmod, *dhi, *dsilu, *wt;
@@ -119,6 +155,8 @@ struct Carver {
     }
 };
 
+constexpr size_t kPartFloats = (size_t)16 << 20;    // 64 MB of dW split partials
+constexpr size_t kCpartFloats = (size_t)4 << 20;    // ... of column-sum partials
 // all tape / scratch sizes in one place (used for the size query and for carving)
 // `two_streams`: the second instances of du / dhid / dqkv / dbias and of the partial-sum scratch exist only then (option train_streams = 2;
 // ~0.9 GB at ATLAS B1 T250 L256); with one stream the [1] pointers alias the [0] ones.
@@ -163,9 +201,9 @@ static size_t carve_train(Train* t, const mdgen_ctx* c, long B, long T, long L, 
     float* dbias[2];
     dbias[0] = cv.take(nseq_max * kH * 2 * kDH);
     dbias[1] = two_streams ? cv.take(nseq_max * kH * 2 * kDH) : dbias[0];
-    const size_t part_floats = (size_t)16 << 20;       // 64 MB of dW split partials
+    const size_t part_floats = kPartFloats;
     float* part = cv.take(part_floats);
-    const size_t cpart_floats = (size_t)4 << 20;
+    const size_t cpart_floats = kCpartFloats;
     float* cpart = cv.take(cpart_floats);
     float* part2 = two_streams ? cv.take(part_floats) : part;              // the second stream's partial sums
     float* cpart2 = two_streams ? cv.take(cpart_floats) : cpart;
@@ -186,54 +224,132 @@ static size_t carve_train(Train* t, const mdgen_ctx* c, long B, long T, long L, 
     return cv.off;
 }
 
-static const ModMap kNoMod{nullptr, 1, 1, 0, 0};
+// ---- the plans -------------------------------------------------------------------------------------------------------
+// Every activation the step's products read (tape, scratch, workspace) is carved at a 256-byte boundary and addressed at column
+// offsets that are multiples of four floats: the plans take them as 16-byte aligned (the launchers check).  What varies is the
+// alignment of the weights: a bound parameter buffer may put them anywhere (mdgen_train_bind_params).
+static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-// Whether the bf16 row stores below may be used: their consumers are the streamed / wide kernels only (k_wide16.hip), so the
-// producer must know before it writes that every consumer will take its launch.  Of the consumers' conditions, the rows (>= 4096,
-// launch16_dw_wide), the shapes and strides and the scratch sizes (part_floats, the slice plans) are fixed by the sub-layer; what
-// is not is the 16-byte alignment of its weights (launch16_pack_wstream): a bound parameter buffer may put them anywhere
-// (mdgen_train_bind_params).  `wide`: every weight of the sub-layer 16-byte aligned (sub_wide).
-static bool sub_wide(std::initializer_list<const float*> w) {
-    for (const float* p : w)
-        if ((uintptr_t)p & 15) return false;
-    return true;
+static DwPlan dw_plan(const Train& t, const DwShape& q, bool x_bf16, bool dy_bf16) {
+    const DwForm f = dw_form(t.bf16, q, t.part_floats, x_bf16, dy_bf16);
+    return DwPlan{f, dw_bias_rides(f, q, t.part_floats)};
 }
-// Whether a sub-layer with `nrows` rows stores its GEMM-only tensors as bf16 rows: the GELU output SubTapeMlp::hid, the taped
+// dX[n][K] = dY[n][M] (ldy) W of a layer W [M][K].  bf16-operand mode: the weight turned once per use -- as a bf16 fragment stream
+// for the streamed kernel, else as an fp32 matrix [K][M] (the contraction contiguous: turned()) for the forward layers' kernels
+static DxPlan dx_plan(bool bf16, long n, int M, int K, int ldy, bool w_al, bool dy_bf16) {
+    if (bf16 && M % 64 == 0 && (size_t)M * K <= (size_t)kF * kC) {
+        const LinearForm f = linear_form(true, LinShape{n, K, M, ldy, K, 0, true, w_al, dy_bf16}, true);
+        if (linear_streams(f)) return DxPlan{DxRoute::Streamed, f};
+        return DxPlan{DxRoute::TurnedWeight, linear_form(true, LinShape{n, K, M, ldy, M, 0, true, true, false}, false)};
+    }
+    return DxPlan{DxRoute::Wtrans, linear_form(bf16, LinShape{n, K, M, ldy, K, 1, true, w_al, false}, false)};
+}
+
+// Rows as bf16: a sub-layer with >= 4096 rows stores its GEMM-only tensors as bf16 rows: the GELU output SubTapeMlp::hid, the taped
 // LayerNorm + modulate output y (token rows of the q | k | v / fc1 products, X of their weight gradients), du = gate * dh, d pre =
 // d hid * gelu'(pre) and, on axes of the sequence-resident attention, dq | dk | dv.  Each is only ever the token operand of a dX
 // product and dY / X of a weight gradient, whose kernels round it to bf16 on its way into LDS anyway (k16_linear_wdma<true>,
 // k16_dw_wide<XBF, DYBF>): written rounded by its producer, the same values enter the MFMAs and half the bytes cross HBM two or
 // three times (ATLAS step: y 25.2 -> 24.6, dq | dk | dv -> 24.2, du -0.3, d pre -0.2 ms).  Weight and activation gradients are
 // unchanged; the bias gradients of the layers whose dY is stored rounded are column sums of the stored values.
-static bool rows_bf16(const Train& t, long nrows, bool wide) { return t.bf16 && nrows >= 4096 && wide; }
-
-// the call's linear layer (kernels.h launch32_linear / launch16_linear); wpack / flags: bf16 operands only
-static void step_linear(const Train& t, const float* a, int lda, const float* w, int ldw, const float* bias, long n, int m, int k,
-                        int mode, float* c, int ldc, int col0, float scalar, hipStream_t s, int wtrans = 0, float* c2 = nullptr,
-                        const void* wpack = nullptr, int flags = 0) {
-    if (t.bf16) launch16_linear(a, lda, w, ldw, bias, n, m, k, mode, c, ldc, col0, kNoMod, 0, 0, scalar, s, wtrans, c2, wpack, flags);
-    else launch32_linear(a, lda, w, ldw, bias, n, m, k, mode, c, ldc, col0, kNoMod, 0, 0, scalar, s, wtrans, c2);
+// Only the streamed / wide kernels read such rows, so a plan is first made with them and kept if every consumer's form is one of
+// those and the one-pass gate kernel writes du; else it is made again with fp32 rows.  ln_adjacent: kernels.h ln_bwd_form.
+static AttnPlan plan_attn(const Train& t, long n, const AxisMap& ax, long tpg, const bool (&w_al)[4], bool ln_adjacent) {
+    AttnPlan p{};
+    p.attn = train_attn_form(t.bf16, ax);
+    p.gate = gate_bwd_form(n, tpg, t.cpart_floats);
+    p.ln = ln_bwd_form(n, tpg, t.cpart_floats, ln_adjacent);
+    const bool w3_al = w_al[0] && w_al[1] && w_al[2];
+    for (int r16 = t.bf16 ? 1 : 0; r16 >= 0; --r16) {
+        p.rows16 = r16 != 0;
+        p.dqkv16 = p.rows16 && attn_seq(p.attn);
+        const LinearForm one = linear_form(t.bf16, LinShape{n, 3 * kC, kC, kC, kC, 0, true, w3_al, p.rows16}, true);
+        p.qkv_one_pass = t.bf16 && one != LinearForm::Plain;
+        for (int j = 0; j < 3; ++j)
+            p.qkv[j] = p.qkv_one_pass ? one : linear_form(t.bf16, LinShape{n, kC, kC, kC, kC, 0, true, w_al[j], false}, false);
+        p.out = linear_form(t.bf16, LinShape{n, kC, kC, kC, kC, 0, true, w_al[3], false}, true);
+        p.dx_out = dx_plan(t.bf16, n, kC, kC, kC, w_al[3], p.rows16);
+        p.dw_out = dw_plan(t, DwShape{n, kC, kC, kC, kC, true}, false, p.rows16);
+        // bf16 operands: q | k | v as one layer of 1152 outputs; fp32: three layers, each with this plan
+        const int mq = t.bf16 ? 3 * kC : kC;
+        p.dx_qkv = dx_plan(t.bf16, n, mq, kC, 3 * kC, w3_al, p.dqkv16);
+        p.dw_qkv = dw_plan(t, DwShape{n, mq, kC, 3 * kC, kC, true}, p.rows16, p.dqkv16);
+        if (!p.rows16 || (p.gate == GateBwdForm::Sums && p.qkv[0] == LinearForm::StreamBf16Rows &&
+                          p.dx_out.route == DxRoute::Streamed && dw_wide(p.dw_out.form) && dw_wide(p.dw_qkv.form) &&
+                          (!p.dqkv16 || p.dx_qkv.route == DxRoute::Streamed)))
+            break;
+    }
+    return p;
 }
-// the call's weight gradient (launch32_dw / launch16_dw); true: db was computed by the same pass
-static bool step_dw(const Train& t, const float* dy, int ldy, const float* x, int ldx, long n, int m, int k, float* dw, float* part,
-                    hipStream_t s, float* db = nullptr, bool x_bf16 = false, bool dy_bf16 = false) {
-    if (t.bf16) return launch16_dw(dy, ldy, x, ldx, n, m, k, dw, part, t.part_floats, s, db, x_bf16, dy_bf16);
-    launch32_dw(dy, ldy, x, ldx, n, m, k, dw, part, t.part_floats, s);
-    return false;
+static MlpPlan plan_mlp(const Train& t, long n, long tpg, const bool (&w_al)[2], bool ln_adjacent) {
+    MlpPlan p{};
+    p.gate = gate_bwd_form(n, tpg, t.cpart_floats);
+    p.ln = ln_bwd_form(n, tpg, t.cpart_floats, ln_adjacent);
+    for (int r16 = t.bf16 ? 1 : 0; r16 >= 0; --r16) {   // (y, hid, du and d pre alike)
+        p.rows16 = r16 != 0;
+        p.fc1 = linear_form(t.bf16, LinShape{n, kF, kC, kC, kC, 0, true, w_al[0], p.rows16}, true);
+        p.fc2 = linear_form(t.bf16, LinShape{n, kC, kF, kF, kF, 0, true, w_al[1], p.rows16}, true);
+        p.dx_fc2 = dx_plan(t.bf16, n, kC, kF, kC, w_al[1], p.rows16);
+        p.dw_fc2 = dw_plan(t, DwShape{n, kC, kF, kC, kF, true}, p.rows16, p.rows16);
+        p.dx_fc1 = dx_plan(t.bf16, n, kF, kC, kF, w_al[0], p.rows16);
+        p.dw_fc1 = dw_plan(t, DwShape{n, kF, kC, kF, kC, true}, p.rows16, p.rows16);
+        if (!p.rows16 || (p.gate == GateBwdForm::Sums && p.fc1 == LinearForm::StreamBf16Rows &&
+                          p.fc2 == LinearForm::StreamBf16Rows && p.dx_fc2.route == DxRoute::Streamed &&
+                          p.dx_fc1.route == DxRoute::Streamed && dw_wide(p.dw_fc2.form) && dw_wide(p.dw_fc1.form)))
+            break;
+    }
+    return p;
+}
+// the IPA block's linear layers (w_al: q | kv | q_points | kv_points | linear_out); their rows are fp32 always
+static IpaPlan plan_ipa(const Train& t, long n, const bool (&w_al)[5]) {
+    IpaPlan p{};
+    for (int j = 0; j < 4; ++j) {
+        const int m = kIpaProjCols[j].m;
+        p.proj[j] = linear_form(t.bf16, LinShape{n, m, kC, kC, kC, 0, true, w_al[j], false}, false);
+        p.dx_proj[j] = dx_plan(t.bf16, n, m, kC, kIpaProj, w_al[j], false);
+        p.dw_proj[j] = dw_plan(t, DwShape{n, m, kC, kIpaProj, kC, true}, false, false);
+    }
+    p.out = linear_form(t.bf16, LinShape{n, kC, kIpaFeat, kIpaFeat, kIpaFeat, 0, true, w_al[4], false}, false);
+    p.dx_out = dx_plan(t.bf16, n, kC, kIpaFeat, kC, w_al[4], false);
+    p.dw_out = dw_plan(t, DwShape{n, kC, kIpaFeat, kC, kIpaFeat, true}, false, false);
+    return p;
+}
+// the final layer: D outputs per token
+static FinalPlan plan_final(const Train& t, long n, int D, long tpg, bool w_al, bool ln_adjacent) {
+    FinalPlan p{};
+    p.lin = linear_form(t.bf16, LinShape{n, D, kC, kC, kC, 0, true, w_al, false}, false);
+    p.dx = dx_plan(t.bf16, n, D, kC, D, w_al, false);
+    p.dw = dw_plan(t, DwShape{n, D, kC, D, kC, true}, false, false);
+    p.ln = ln_bwd_form(n, tpg, t.cpart_floats, ln_adjacent);
+    return p;
 }
 
-// bf16-operand mode, launches big enough for the streamed 128 x 384 kernel: the weight W(col < m, kk < k) of ONE layer as a
-// bf16 fragment stream in the scratch t.wt (turned: the fp32 matrix is [k][m], dX = dY W).  nullptr: not eligible -- the
-// caller's launch then reads the fp32 weight.  The scratch is reused by the next call on the stream.
-static const void* wpack1(const Train& t, const float* w, int ld, long n, int m, int k, int turned) {
-    if (!t.bf16) return nullptr;
-    return launch16_pack_wstream(&w, 1, turned ? k : m, ld, n, m, k, turned, t.wt, t.r.s) ? t.wt : nullptr;
+// the call's linear layer in the form its plan gives
+static void step_linear(LinearParams p, LinearForm form, hipStream_t s) {
+    p.fast_gelu = form != LinearForm::F32;    // (see linear.h)
+    p.a_bf16 = form == LinearForm::StreamBf16Rows;
+    launch_linear(p, form, s);
+}
+// the call's weight gradient; the bias gradient too where the plan says it rides along
+static void step_dw(const DwParams& p, const DwPlan& pl, hipStream_t s) { launch_dw(p, pl.form, s); }
+static DwParams dw_op(const float* dy, int ldy, const float* x, int ldx, long n, int m, int k, float* dw, float* db, float* part,
+                      const Train& t) {
+    return DwParams{dy, ldy, x, ldx, n, m, 1, k, {dw, nullptr, nullptr}, {db, nullptr, nullptr}, part, t.part_floats};
+}
+// ... of a layer outside the sub-layers (embedders, adaLN heads, time embedder): planned where it is launched
+static void step_dw_now(const Train& t, const DwParams& p, hipStream_t s) { step_dw(p, dw_plan(t, dw_shape(p), false, false), s); }
+
+// the weight W(col < m, kk < k) of ONE layer as a bf16 fragment stream in the scratch t.wt for the streamed forms (turned: the fp32
+// matrix is [k][m], dX = dY W).  The scratch is reused by the next call on the stream.
+static const unsigned char* wpack1(const Train& t, const float* w, int ld, int m, int k, int turned) {
+    launch16_pack_wstream(&w, 1, turned ? k : m, ld, m, k, turned, t.wt, t.r.s);
+    return (const unsigned char*)t.wt;
 }
 
 // ---- forward sub-layers with tape ---------------------------------------------------------------------------------
 // LayerNorm + modulate of the residual stream into y, the stream's rows copied to the tape (h_in) -- with the previous sub-layer's
 // pending gated update formed on the way when there is one (Train::Pending)
-// y_bf16: y is stored as bf16 rows (rows_bf16: it is only ever a GEMM operand)
+// y_bf16: y is stored as bf16 rows (the plan's rows16: it is only ever a GEMM operand)
 static int ln_mod_tape(Train& t, const float* h, long nrows, const ModMap& mm, int shift, int scale, float* y, float* h_in,
                        bool y_bf16) {
     if (!t.pend.x) {
@@ -255,55 +371,72 @@ static void flush_pending(Train& t, float* h) {
     launch32_gated_sum(h, t.pend.x, t.pend.u, t.pend.nrows, t.pend.mm, t.pend.gate, t.r.s);
     t.pend = Train::Pending{};
 }
+static TrainAttnParams attn_op(const Train& t, const MhaW& m, const AxisMap& ax, const MaskMap& mk, const SubTapeAttn& tp) {
+    TrainAttnParams a{};
+    a.qkv = tp.qkv; a.ld = 3 * kC; a.ax = ax; a.mk = mk;
+    a.bias_k = t.w(m.slot.bias_k); a.bias_v = t.w(m.slot.bias_v); a.inv_freq = t.c->inv_freq;
+    a.out = tp.att; a.lse = tp.lse;
+    return a;
+}
 
+// tpg: tokens per modulation group (the backward's column sums; part of the plan)
 static int attn_fwd_tape(Train& t, const MhaW& m, float* h, long nrows, const AxisMap& ax, const ModMap& mm, int shift, int scale,
-                         int gate, const MaskMap& mk, long pos_div, int pos_mod, const SubTapeAttn& tp) {
+                         int gate, const MaskMap& mk, long pos_div, int pos_mod, long tpg, SubTapeAttn& tp) {
     const Run& r = t.r;
     const auto& p = m.slot;
-    const float *wq = t.w(p.q.w), *wk = t.w(p.k.w), *wv = t.w(p.v.w), *wo = t.w(p.o.w);
-    const float *bq = t.w(p.q.b), *bk = t.w(p.k.b), *bv = t.w(p.v.b), *bo = t.w(p.o.b);
-    const float *biask = t.w(p.bias_k), *biasv = t.w(p.bias_v);
-    const bool y16 = rows_bf16(t, nrows, sub_wide({wq, wk, wv, wo}));
-    if (int e = ln_mod_tape(t, h, nrows, mm, shift, scale, tp.y, tp.h_in, y16)) return e;     // y (taped), and the tape's copy of h
+    const float* w3[3] = {t.w(p.q.w), t.w(p.k.w), t.w(p.v.w)};
+    const float* b3[3] = {t.w(p.q.b), t.w(p.k.b), t.w(p.v.b)};
+    const float* wo = t.w(p.o.w);
+    const bool w_al[4] = {al16(w3[0]), al16(w3[1]), al16(w3[2]), al16(wo)};
+    const AttnPlan& pl = tp.plan = plan_attn(t, nrows, ax, tpg, w_al, scale == shift + 1);
+    if (int e = ln_mod_tape(t, h, nrows, mm, shift, scale, tp.y, tp.h_in, pl.rows16)) return e;     // y (taped), and the tape's copy of h
     const float qscale = 1.0f / std::sqrt((float)kDH);
-    const float* w3[3] = {wq, wk, wv};
-    const float* b3[3] = {bq, bk, bv};
-    const float s3[3] = {qscale, 1.0f, 1.0f};
-    // bf16 operands: one pass over y, the three weights as one fragment stream (k_wide16.hip) when the launch is big enough
-    const void* pk = t.bf16 && launch16_pack_wstream(w3, 3, kC, kC, nrows, 3 * kC, kC, 0, t.wt, r.s) ? t.wt : nullptr;
-    if (y16 && !pk) return fail(-7, "internal: bf16 LayerNorm output without the streamed q | k | v kernel (rows %ld)", nrows);
-    if (!t.bf16 || !launch16_linear_seg3(tp.y, kC, w3, kC, b3, s3, nrows, kC, kC, tp.qkv, 3 * kC, 0, r.s, pk, y16)) {
-        if (y16) return fail(-7, "internal: bf16 LayerNorm output without the one-pass q | k | v kernel (rows %ld)", nrows);
-        step_linear(t, tp.y, kC, wq, kC, bq, nrows, kC, kC, 4, tp.qkv, 3 * kC, 0, qscale, r.s);
-        step_linear(t, tp.y, kC, wk, kC, bk, nrows, kC, kC, 0, tp.qkv, 3 * kC, kC, 0.f, r.s);
-        step_linear(t, tp.y, kC, wv, kC, bv, nrows, kC, kC, 0, tp.qkv, 3 * kC, 2 * kC, 0.f, r.s);
+    if (pl.qkv_one_pass) {   // bf16 operands: one pass over y, c[n][j kC + i] = (y . w3[j][i] + b3[j][i]) * scale[j]
+        LinearParams q = lin_op(tp.y, kC, w3[0], kC, nullptr, nrows, 3 * kC, kC, tp.qkv, 3 * kC);
+        q.seg_cols = kC;
+        for (int j = 0; j < 3; ++j) { q.w_seg[j] = w3[j]; q.bias_seg[j] = b3[j]; q.scale_seg[j] = j == 0 ? qscale : 1.0f; }
+        if (linear_streams(pl.qkv[0])) {   // ... the three weights as one fragment stream (k_wide16.hip)
+            launch16_pack_wstream(w3, 3, kC, kC, 3 * kC, kC, 0, t.wt, r.s);
+            q.wpack = (const unsigned char*)t.wt;
+        }
+        step_linear(q, pl.qkv[0], r.s);
+    } else {
+        for (int j = 0; j < 3; ++j) {
+            LinearParams q = lin_op(tp.y, kC, w3[j], kC, b3[j], nrows, kC, kC, tp.qkv, 3 * kC);
+            q.col0 = j * kC;
+            if (j == 0) { q.mode = kLinScaled; q.scalar = qscale; }
+            step_linear(q, pl.qkv[j], r.s);
+        }
     }
     // (the sequence-resident bf16-operand kernels rotate q, k while they convert them: no RoPE pass, the tape keeps them unrotated)
-    const bool rope_inside = t.bf16 && attn16_seq_form(ax);
-    if (!rope_inside) launch32_rope(tp.qkv, nrows, 3 * kC, pos_div, pos_mod, t.c->inv_freq, r.s);
-    if (t.bf16) launch16_attn(tp.qkv, 3 * kC, ax, mk, biask, biasv, t.c->inv_freq, tp.att, r.s, tp.lse, attn16_seq_form(ax), rope_inside);
-    else launch32_attn(tp.qkv, 3 * kC, ax, mk, biask, biasv, t.c->inv_freq, tp.att, r.s, tp.lse);
+    if (pl.attn != TrainAttnForm::SeqRope) launch32_rope(tp.qkv, nrows, 3 * kC, pos_div, pos_mod, t.c->inv_freq, r.s);
+    launch_train_attn(attn_op(t, m, ax, mk, tp), pl.attn, r.s);
     // (the gated residual as an epilogue of this product, with u kept at a second address, was measured: the store phase is
     // what bounds the wide kernels, and the heavier epilogue cost 1.5 ms per step where the separate pass costs 1.3)
-    step_linear(t, tp.att, kC, wo, kC, bo, nrows, kC, kC, 0, tp.u, kC, 0, 0.f, r.s, 0, nullptr, wpack1(t, wo, kC, nrows, kC, kC, 0));
+    LinearParams o = lin_op(tp.att, kC, wo, kC, t.w(p.o.b), nrows, kC, kC, tp.u, kC);
+    if (linear_streams(pl.out)) o.wpack = wpack1(t, wo, kC, kC, kC, 0);
+    step_linear(o, pl.out, r.s);
     gated_update(t, h, tp.h_in, tp.u, nrows, mm, gate);
     LAUNCHCHK();
     return 0;
 }
 
-static int mlp_fwd_tape(Train& t, const FfnW& f, float* h, long nrows, const ModMap& mm, int shift, int scale, int gate,
-                        const SubTapeMlp& tp) {
+static int mlp_fwd_tape(Train& t, const FfnW& f, float* h, long nrows, const ModMap& mm, int shift, int scale, int gate, long tpg,
+                        SubTapeMlp& tp) {
     const Run& r = t.r;
-    const float *w1 = t.w(f.slot.fc1.w), *b1 = t.w(f.slot.fc1.b), *w2 = t.w(f.slot.fc2.w), *b2 = t.w(f.slot.fc2.b);
-    const bool wide = sub_wide({w1, w2});
-    const bool y16 = rows_bf16(t, nrows, wide);   // (y and hid = gelu(pre) alike)
-    if (int e = ln_mod_tape(t, h, nrows, mm, shift, scale, tp.y, tp.h_in, y16)) return e;     // y (taped), and the tape's copy of h
-    const void* pk1 = wpack1(t, w1, kC, nrows, kF, kC, 0);
-    if (y16 && !pk1) return fail(-7, "internal: bf16 LayerNorm output without the streamed fc1 kernel (rows %ld)", nrows);
-    step_linear(t, tp.y, kC, w1, kC, b1, nrows, kF, kC, 6, tp.pre, kF, 0, 0.f, r.s, 0, tp.hid, pk1, y16 ? 3 : 0);
-    const void* pk2 = wpack1(t, w2, kF, nrows, kC, kF, 0);
-    if (y16 && !pk2) return fail(-7, "internal: bf16 GELU output without the streamed fc2 kernel (rows %ld)", nrows);
-    step_linear(t, tp.hid, kF, w2, kF, b2, nrows, kC, kF, 0, tp.u, kC, 0, 0.f, r.s, 0, nullptr, pk2, y16 ? 1 : 0);
+    const float *w1 = t.w(f.slot.fc1.w), *w2 = t.w(f.slot.fc2.w);
+    const bool w_al[2] = {al16(w1), al16(w2)};
+    const MlpPlan& pl = tp.plan = plan_mlp(t, nrows, tpg, w_al, scale == shift + 1);
+    if (int e = ln_mod_tape(t, h, nrows, mm, shift, scale, tp.y, tp.h_in, pl.rows16)) return e;     // y (taped), and the tape's copy of h
+    LinearParams fc1 = lin_op(tp.y, kC, w1, kC, t.w(f.slot.fc1.b), nrows, kF, kC, tp.pre, kF);
+    fc1.mode = kLinStoreGelu;
+    fc1.c2 = tp.hid;               // hid = gelu(pre), as bf16 rows with the plan's rows16
+    fc1.c2_bf16 = pl.rows16;
+    if (linear_streams(pl.fc1)) fc1.wpack = wpack1(t, w1, kC, kF, kC, 0);
+    step_linear(fc1, pl.fc1, r.s);
+    LinearParams fc2 = lin_op(tp.hid, kF, w2, kF, t.w(f.slot.fc2.b), nrows, kC, kF, tp.u, kC);
+    if (linear_streams(pl.fc2)) fc2.wpack = wpack1(t, w2, kF, kC, kF, 0);
+    step_linear(fc2, pl.fc2, r.s);
     gated_update(t, h, tp.h_in, tp.u, nrows, mm, gate);
     LAUNCHCHK();
     return 0;
@@ -337,88 +470,86 @@ static const float* turned(Train& t, const float* const* w, int nseg, int rows, 
 }
 
 // ---- backward helpers ---------------------------------------------------------------------------------------------
-// y = x W^T + b  (the layer `lin`, W [M][K]):  dx (store / accumulate) = dy W;  dW += dy^T x;  db += colsum(dy)
-// gelu_pre != nullptr: dx = (dy W) * gelu'(gelu_pre) (same shape and row stride as dx; not with accumulate)
-static int lin_bwd(Train& t, const float* dy, int ldy, const float* x, int ldx, const Lin& lin, long n, int M, int K, float* dx,
-                   int ldx_out, bool accumulate, const float* gelu_pre = nullptr, bool x_bf16 = false, bool side_ok = true,
-                   bool dy_bf16 = false, bool dx_bf16 = false) {   // dx_bf16 (with gelu_pre only): dx is written as bf16 rows
-    hipStream_t s = t.r.s;
+// dX = dY W of nseg layers W_j [mseg][K] whose dY sit side by side (M = nseg mseg), along the plan's route.  q: the product's
+// operands but for the weight (a = dY, lda, n, c = dX, ldc, mode and its operands)
+static void step_dx(Train& t, LinearParams q, const float* const* w, int nseg, int mseg, int K, const DxPlan& pl) {
+    const int M = nseg * mseg;
+    q.m = K; q.k = M; q.w = w[0]; q.ldw = M;
+    if (pl.route == DxRoute::Streamed) {
+        launch16_pack_wstream(w, nseg, mseg, K, K, M, 1, t.wt, t.r.s);
+        q.wpack = (const unsigned char*)t.wt;
+    } else if (pl.route == DxRoute::TurnedWeight) {
+        q.w = turned(t, w, nseg, mseg, K);
+    } else {
+        q.ldw = K; q.wtrans = 1;
+    }
+    step_linear(q, pl.form, t.r.s);
+}
+// The backward of y = x W^T + b (the layer `lin`, W [M][K]):  dx (store / accumulate) = dy W;  dW += dy^T x;  db += colsum(dy)
+struct LinBwdOp {
+    const float* dy; int ldy;        // dY [n][M]
+    const float* x; int ldx;         // the layer's input [n][K]
+    float* dx; int ldx_out;          // dX [n][K]
+    bool accumulate;                 // dx += (the layer shares its input with the one before)
+    const float* gelu_pre;           // non-null: dx = (dy W) * gelu'(gelu_pre) (same shape and row stride as dx; not with accumulate)
+    bool dx_bf16;                    // ... written as bf16 rows
+    bool main_stream;                // dy is a buffer the main stream goes on updating in place (the IPA block's ungated residual):
+                                     // the weight gradient stays on the main stream
+};
+static int lin_bwd(Train& t, const Lin& lin, long n, int M, int K, const DxPlan& dxp, const DwPlan& dwp, const LinBwdOp& o) {
     const float* W = t.w(lin.w);
-    // dW / db: second stream (dy and x are complete at this point of the main stream).  side_ok = false: dy is a buffer the
-    // main stream goes on updating in place (the IPA block's ungated residual), the gradient stays on the main stream.
+    // dW / db: second stream (dy and x are complete at this point of the main stream)
     float* gb = t.grad(lin.b);
     float* gw = t.grad(lin.w);
-    hipStream_t sw = s;
+    hipStream_t sw = t.r.s;
     float *pt = t.part, *cpt = t.cpart;
-    if ((gw || gb) && side_ok)
+    if ((gw || gb) && !o.main_stream)
         if (int e = t.fork(&sw, &pt, &cpt)) return e;
-    const int mode = gelu_pre ? 7 : (accumulate ? 5 : 0);
-    float* c2 = const_cast<float*>(gelu_pre);
-    if (dx && t.bf16 && M % 64 == 0 && (size_t)M * K <= (size_t)kF * kC) {
-        // bf16-operand mode: the weight turned once per use -- as a bf16 fragment stream for the streamed kernel, else as
-        // an fp32 matrix [K][M] (the contraction contiguous) for the forward layers' kernels
-        if (const void* pk = wpack1(t, W, K, n, K, M, 1)) {
-            step_linear(t, dy, ldy, W, M, nullptr, n, K, M, mode, dx, ldx_out, 0, 0.f, s, 0, c2, pk, (dy_bf16 ? 1 : 0) | (dx_bf16 ? 4 : 0));
-        } else {
-            if (dy_bf16 || dx_bf16) return fail(-7, "internal: bf16 dY / dX rows without the streamed dX kernel (rows %ld)", n);
-            const float* wt = turned(t, &W, 1, M, K);
-            step_linear(t, dy, ldy, wt, M, nullptr, n, K, M, mode, dx, ldx_out, 0, 0.f, s, 0, c2);
-        }
-    } else if (dx) {
-        if (dy_bf16 || dx_bf16) return fail(-7, "internal: bf16 dY / dX rows outside the bf16-operand kernels (rows %ld)", n);
-        step_linear(t, dy, ldy, W, K, nullptr, n, K, M, mode, dx, ldx_out, 0, 0.f, s, 1, c2);
-    }
-    bool bias_done = false;
-    if (gw) bias_done = step_dw(t, dy, ldy, x, ldx, n, M, K, gw, pt, sw, gb, x_bf16, dy_bf16);
-    if (dy_bf16 && ((gw && !bias_done && gb) || (!gw && gb)))
-        return fail(-7, "internal: bf16 dY rows without the wide weight-gradient kernel (rows %ld)", n);
-    if (gb && !bias_done) launch32_colsum(dy, ldy, nullptr, 0, nullptr, 0, n, M, n, 0.f, gb, 0, cpt, t.cpart_floats, sw);
+    LinearParams q = lin_op(o.dy, o.ldy, nullptr, 0, nullptr, n, K, M, o.dx, o.ldx_out);
+    q.mode = o.gelu_pre ? kLinGeluBwd : o.accumulate ? kLinAccumulate : kLinStore;
+    q.c2 = const_cast<float*>(o.gelu_pre);
+    q.c_bf16 = o.dx_bf16;
+    step_dx(t, q, &W, 1, M, K, dxp);
+    // (dY stored as bf16 rows: only the wide pass reads them, so a bias gradient wanted alone takes that pass too, as q | k | v's does)
+    const bool pass = gw || (gb && dw_dy_bf16(dwp.form));
+    if (pass) step_dw(dw_op(o.dy, o.ldy, o.x, o.ldx, n, M, K, gw, gb, pt, t), dwp, sw);
+    if (gb && !(pass && dwp.bias_rides)) launch32_colsum(o.dy, o.ldy, nullptr, 0, nullptr, 0, n, M, n, 0.f, gb, 0, cpt, t.cpart_floats, sw);
     LAUNCHCHK();
     return 0;
 }
 
-// gated residual h_out = h_in + gate * u:  du = gate * dh (into t.du);  dgate[g] += sum_t dh * u
-// du16: t.du is written as bf16 rows (rows_bf16: it is only ever the token operand of the dX product and dY of the weight gradient
-// of the sub-layer's last linear layer)
-static int gate_bwd(const Train& t, const float* dh, const float* u, long nrows, const ModMap& mm, int gate_chunk,
-                    long tokens_per_group, long mod_ld, float* dmod_base, bool du16 = false) {
-    hipStream_t s = t.r.s;
-    if (launch32_gate_bwd_sums(dh, u, nrows, mm, gate_chunk, t.du, tokens_per_group, dmod_base + gate_chunk * kC, mod_ld, t.cpart,
-                               t.cpart_floats, s, du16))
-        return 0;
-    if (du16) return fail(-7, "internal: bf16 gated gradient without the one-pass gate kernel (rows %ld)", nrows);
-    launch32_gate_mul(dh, nrows, mm, gate_chunk, 1, t.du, s);
-    launch32_colsum(dh, kC, u, kC, nullptr, 1, nrows, kC, tokens_per_group, 0.f, dmod_base + gate_chunk * kC, mod_ld, t.cpart,
-                    t.cpart_floats, s);
-    return 0;
+// gated residual h_out = h_in + gate * u:  du = gate * dh (into t.du; du16: as bf16 rows -- it is only ever the token operand of the
+// dX product and dY of the weight gradient of the sub-layer's last linear layer);  dgate[g] += sum_t dh * u
+static void gate_bwd(const Train& t, GateBwdForm form, const float* dh, const float* u, long nrows, const ModMap& mm, int gate_chunk,
+                     long tokens_per_group, long mod_ld, float* dmod_base, bool du16) {
+    launch32_gate_bwd(GateBwdParams{dh, u, nrows, mm, gate_chunk, t.du, du16, tokens_per_group, dmod_base + gate_chunk * kC, mod_ld,
+                                    t.cpart, t.cpart_floats}, form, t.r.s);
 }
-
-// LN + modulate backward: dshift[g] += sum dy; dscale[g] += sum dy * xhat; dh += LN'(dy * (1 + scale))
-static void lnmod_bwd(const Train& t, const float* h_in, const float* dy, long nrows, const ModMap& mm, int shift_chunk,
+// LN + modulate backward: dshift[g] += sum dy; dscale[g] += sum dy * xhat; dh (+)= LN'(dy * (1 + scale))
+static void lnmod_bwd(const Train& t, LnBwdForm form, const float* h_in, const float* dy, long nrows, const ModMap& mm, int shift_chunk,
                       int scale_chunk, long tokens_per_group, long mod_ld, float* dmod_base, float* dh, bool accumulate) {
-    hipStream_t s = t.r.s;
-    if (scale_chunk == shift_chunk + 1 &&     // the two gradient chunks are neighbours in the modulation row: one pass
-        launch32_ln_bwd_sums(h_in, dy, nrows, mm, scale_chunk, 1e-6f, dh, accumulate ? 1 : 0, tokens_per_group,
-                             dmod_base + shift_chunk * kC, mod_ld, t.cpart, t.cpart_floats, s))
-        return;
-    launch32_colsum(dy, kC, nullptr, 0, nullptr, 0, nrows, kC, tokens_per_group, 0.f, dmod_base + shift_chunk * kC, mod_ld, t.cpart,
-                    t.cpart_floats, s);
-    launch32_colsum(dy, kC, h_in, kC, nullptr, 2, nrows, kC, tokens_per_group, 1e-6f, dmod_base + scale_chunk * kC, mod_ld, t.cpart,
-                    t.cpart_floats, s);
-    launch32_ln_bwd(h_in, dy, nrows, mm, scale_chunk, 0, 1e-6f, dh, accumulate ? 1 : 0, s);
+    launch32_ln_mod_bwd(LnBwdParams{h_in, dy, nrows, mm, scale_chunk, 1e-6f, dh, accumulate ? 1 : 0, tokens_per_group,
+                                    dmod_base + shift_chunk * kC, dmod_base + scale_chunk * kC, mod_ld, t.cpart, t.cpart_floats}, form, t.r.s);
 }
 
 // backward of one MLP sub-layer; dh is updated in place (dh_in = dh_out + ...)
 static int mlp_bwd(Train& t, const FfnW& f, float* dh, long nrows, const ModMap& mm, int shift, int scale, int gate, long tpg,
                    long mod_ld, float* dmod_base, const SubTapeMlp& tp) {
+    const MlpPlan& pl = tp.plan;   // hid, y, du = gate * dh and d pre as bf16 rows (rows16), or all of them fp32
     if (int e = t.begin_sub()) return e;
-    // (as mlp_fwd_tape decided the tape's storage): hid, y, du = gate * dh and d pre as bf16 rows, or all of them fp32
-    const bool r16 = rows_bf16(t, nrows, sub_wide({t.w(f.slot.fc1.w), t.w(f.slot.fc2.w)}));
-    if (int e = gate_bwd(t, dh, tp.u, nrows, mm, gate, tpg, mod_ld, dmod_base, r16)) return e;   // t.du = gate * dh
-    // d pre = (du W2) * gelu'(pre): the GELU derivative is the epilogue of the dX product
-    if (int e = lin_bwd(t, t.du, kC, tp.hid, kF, f.slot.fc2, nrows, kC, kF, t.dhid, kF, false, tp.pre, r16, true, r16, r16)) return e;
-    if (int e = lin_bwd(t, t.dhid, kF, tp.y, kC, f.slot.fc1, nrows, kF, kC, t.dy, kC, false, nullptr, r16, true, r16)) return e;
-    lnmod_bwd(t, tp.h_in, t.dy, nrows, mm, shift, scale, tpg, mod_ld, dmod_base, dh, true);
+    gate_bwd(t, pl.gate, dh, tp.u, nrows, mm, gate, tpg, mod_ld, dmod_base, pl.rows16);   // t.du = gate * dh
+    LinBwdOp fc2{};   // d pre = (du W2) * gelu'(pre) into t.dhid: the GELU derivative is the epilogue of the dX product
+    fc2.dy = t.du; fc2.ldy = kC;
+    fc2.x = tp.hid; fc2.ldx = kF;
+    fc2.dx = t.dhid; fc2.ldx_out = kF;
+    fc2.gelu_pre = tp.pre; fc2.dx_bf16 = pl.rows16;
+    if (int e = lin_bwd(t, f.slot.fc2, nrows, kC, kF, pl.dx_fc2, pl.dw_fc2, fc2)) return e;
+    LinBwdOp fc1{};   // t.dy = d pre W1
+    fc1.dy = t.dhid; fc1.ldy = kF;
+    fc1.x = tp.y; fc1.ldx = kC;
+    fc1.dx = t.dy; fc1.ldx_out = kC;
+    if (int e = lin_bwd(t, f.slot.fc1, nrows, kF, kC, pl.dx_fc1, pl.dw_fc1, fc1)) return e;
+    lnmod_bwd(t, pl.ln, tp.h_in, t.dy, nrows, mm, shift, scale, tpg, mod_ld, dmod_base, dh, true);
     LAUNCHCHK();
     return t.end_sub();
 }
@@ -429,19 +560,18 @@ static int attn_bwd(Train& t, const MhaW& m, float* dh, long nrows, const AxisMa
                     const SubTapeAttn& tp) {
     hipStream_t s = t.r.s;
     const auto& p = m.slot;
-    const float *wq = t.w(p.q.w), *wk = t.w(p.k.w), *wv = t.w(p.v.w), *wo = t.w(p.o.w);
-    const float *biask = t.w(p.bias_k), *biasv = t.w(p.bias_v);
+    const AttnPlan& pl = tp.plan;   // (as attn_fwd_tape stored the tape: y as bf16 rows or fp32, q and k rotated or not)
     if (int e = t.begin_sub()) return e;
-    const bool r16 = rows_bf16(t, nrows, sub_wide({wq, wk, wv, wo}));   // (as attn_fwd_tape decided the tape's storage: y)
-    if (int e = gate_bwd(t, dh, tp.u, nrows, mm, gate, tpg, mod_ld, dmod_base, r16)) return e;   // t.du
-    if (int e = lin_bwd(t, t.du, kC, tp.att, kC, p.o, nrows, kC, kC, t.dy, kC, false, nullptr, false, true, r16)) return e;   // t.dy = d att
-    // the sequence-resident kernels write dq | dk | dv as bf16 rows (rows_bf16)
-    const bool dq16 = attn16_seq_form(ax) && r16;
-    if (t.bf16)
-        launch16_attn_bwd(tp.qkv, 3 * kC, ax, mk, biask, biasv, t.c->inv_freq, tp.att, t.dy, t.dqkv, t.stats, t.dbias, s, tp.lse,
-                          attn16_seq_form(ax), attn16_seq_form(ax), dq16);   // (RoPE inside as the forward pass decided: attn_fwd_tape)
-    else
-        launch32_attn_bwd(tp.qkv, 3 * kC, ax, mk, biask, biasv, t.c->inv_freq, tp.att, t.dy, t.dqkv, t.stats, t.dbias, s, tp.lse);
+    gate_bwd(t, pl.gate, dh, tp.u, nrows, mm, gate, tpg, mod_ld, dmod_base, pl.rows16);   // t.du
+    LinBwdOp o{};   // t.dy = d att = du Wo
+    o.dy = t.du; o.ldy = kC;
+    o.x = tp.att; o.ldx = kC;
+    o.dx = t.dy; o.ldx_out = kC;
+    if (int e = lin_bwd(t, p.o, nrows, kC, kC, pl.dx_out, pl.dw_out, o)) return e;
+    TrainAttnParams a = attn_op(t, m, ax, mk, tp);
+    a.dout = t.dy; a.dqkv = t.dqkv; a.stats = t.stats; a.dbias = t.dbias;
+    a.dqkv_bf16 = pl.dqkv16;       // the sequence-resident kernels write dq | dk | dv as bf16 rows
+    launch_train_attn_bwd(a, pl.attn, s);
     // bias key / value: rows [seq][dk: head x 24 | dv: head x 24] summed over sequences = the (1, 1, C) tensors
     {
         float *gk = t.grad(p.bias_k), *gv = t.grad(p.bias_v);
@@ -452,43 +582,44 @@ static int attn_bwd(Train& t, const MhaW& m, float* dh, long nrows, const AxisMa
         if (gk) launch32_colsum(t.dbias, 2 * kC, nullptr, 0, nullptr, 0, ax.nseq, kC, ax.nseq, 0.f, gk, 0, cpt, t.cpart_floats, sw);
         if (gv) launch32_colsum(t.dbias + kC, 2 * kC, nullptr, 0, nullptr, 0, ax.nseq, kC, ax.nseq, 0.f, gv, 0, cpt, t.cpart_floats, sw);
     }
-    if (!t.bf16)    // (the bf16-operand attention backward stores dq, dk already taken back through RoPE)
+    if (pl.attn == TrainAttnForm::Exact)    // (the bf16-operand attention backward stores dq, dk already taken back through RoPE)
         launch32_rope_bwd(t.dqkv, nrows, 3 * kC, pos_div, pos_mod, t.c->inv_freq, 1.0f / std::sqrt((float)kDH), s);
+    const Lin l3[3] = {p.q, p.k, p.v};
     if (t.bf16) {
         // q | k | v as one layer of 1152 outputs: dy = dqkv [Wq; Wk; Wv] (one product with the contraction over all three,
-        // the weights turned side by side into the scratch), dW and db of all three from one pass over (dqkv, y)
-        const float* w3[3] = {wq, wk, wv};
-        float* gw3[3] = {t.grad(p.q.w), t.grad(p.k.w), t.grad(p.v.w)};
-        float* gb3[3] = {t.grad(p.q.b), t.grad(p.k.b), t.grad(p.v.b)};
-        const bool want_g = gw3[0] || gw3[1] || gw3[2] || gb3[0] || gb3[1] || gb3[2];
-        hipStream_t sw = s;
-        float *pt = t.part, *cpt = t.cpart;
-        if (want_g)                                    // (dqkv, y) are complete: the gradients go to the second stream
-            if (int e = t.fork(&sw, &pt, &cpt)) return e;
-        if (launch16_pack_wstream(w3, 3, kC, kC, nrows, kC, 3 * kC, 1, t.wt, s)) {
-            launch16_linear(t.dqkv, 3 * kC, wq, 3 * kC, nullptr, nrows, kC, 3 * kC, 0, t.dy, kC, 0, kNoMod, 0, 0, 0.f, s, 0, nullptr, t.wt,
-                            dq16 ? 1 : 0);
-        } else {
-            if (dq16) return fail(-7, "internal: bf16 q | k | v gradients without the streamed dX kernel (rows %ld)", nrows);
-            const float* wt = turned(t, w3, 3, kC, kC);
-            launch16_linear(t.dqkv, 3 * kC, wt, 3 * kC, nullptr, nrows, kC, 3 * kC, 0, t.dy, kC, 0, kNoMod, 0, 0, 0.f, s);
+        // the weights streamed or turned side by side into the scratch), dW and db of all three from one pass over (dqkv, y)
+        const float* w3[3] = {t.w(p.q.w), t.w(p.k.w), t.w(p.v.w)};
+        DwParams g = dw_op(t.dqkv, 3 * kC, tp.y, kC, nrows, kC, kC, nullptr, nullptr, t.part, t);
+        g.nseg = 3;
+        bool want_g = false, want_b = false;
+        for (int j = 0; j < 3; ++j) {
+            g.dw[j] = t.grad(l3[j].w); g.db[j] = t.grad(l3[j].b);
+            want_g = want_g || g.dw[j] || g.db[j];
+            want_b = want_b || g.db[j];
         }
+        hipStream_t sw = s;
+        float* cpt = t.cpart;
+        if (want_g)                                    // (dqkv, y) are complete: the gradients go to the second stream
+            if (int e = t.fork(&sw, &g.part, &cpt)) return e;
+        step_dx(t, lin_op(t.dqkv, 3 * kC, nullptr, 0, nullptr, nrows, 0, 0, t.dy, kC), w3, 3, kC, kC, pl.dx_qkv);
         if (want_g) {
-            const bool bias_done = launch16_dw_seg(t.dqkv, 3 * kC, tp.y, kC, nrows, kC, 3, kC, gw3, gb3, pt, t.part_floats, sw, r16, dq16);
-            if (dq16 && !bias_done && (gb3[0] || gb3[1] || gb3[2]))
-                return fail(-7, "internal: bf16 q | k | v gradients without the wide weight-gradient kernel (rows %ld)", nrows);
-            for (int j = 0; j < 3 && !bias_done; ++j)
-                if (gb3[j])
-                    launch32_colsum(t.dqkv + j * kC, 3 * kC, nullptr, 0, nullptr, 0, nrows, kC, nrows, 0.f, gb3[j], 0, cpt,
+            step_dw(g, pl.dw_qkv, sw);
+            for (int j = 0; j < 3 && !(want_b && pl.dw_qkv.bias_rides); ++j)
+                if (g.db[j])
+                    launch32_colsum(t.dqkv + j * kC, 3 * kC, nullptr, 0, nullptr, 0, nrows, kC, nrows, 0.f, g.db[j], 0, cpt,
                                     t.cpart_floats, sw);
         }
         LAUNCHCHK();
     } else {
-        if (int e = lin_bwd(t, t.dqkv, 3 * kC, tp.y, kC, p.q, nrows, kC, kC, t.dy, kC, false)) return e;
-        if (int e = lin_bwd(t, t.dqkv + kC, 3 * kC, tp.y, kC, p.k, nrows, kC, kC, t.dy, kC, true)) return e;
-        if (int e = lin_bwd(t, t.dqkv + 2 * kC, 3 * kC, tp.y, kC, p.v, nrows, kC, kC, t.dy, kC, true)) return e;
+        for (int j = 0; j < 3; ++j) {   // t.dy = dq Wq + dk Wk + dv Wv
+            LinBwdOp q{};
+            q.dy = t.dqkv + j * kC; q.ldy = 3 * kC;
+            q.x = tp.y; q.ldx = kC;
+            q.dx = t.dy; q.ldx_out = kC; q.accumulate = j > 0;
+            if (int e = lin_bwd(t, l3[j], nrows, kC, kC, pl.dx_qkv, pl.dw_qkv, q)) return e;
+        }
     }
-    lnmod_bwd(t, tp.h_in, t.dy, nrows, mm, shift, scale, tpg, mod_ld, dmod_base, dh, true);
+    lnmod_bwd(t, pl.ln, tp.h_in, t.dy, nrows, mm, shift, scale, tpg, mod_ld, dmod_base, dh, true);
     LAUNCHCHK();
     return t.end_sub();
 }
@@ -498,6 +629,7 @@ static int ipa_block_bwd(Train& t, const IpaW& w, const SubTapeIpa& tp, float* d
     const Run& r = t.r;
     hipStream_t s = r.s;
     const auto& p = w.slot;
+    const IpaPlan& pl = tp.plan;
     const long Mp = r.Mp;
     if (int e = t.begin_sub()) return e;
     float* dfeat = t.dhid;                    // [Mp][256]
@@ -506,7 +638,12 @@ static int ipa_block_bwd(Train& t, const IpaW& w, const SubTapeIpa& tp, float* d
     float* qrec = t.act;                      // [Mp][4][49]
     // linear_out (ungated residual: d u = d x_out)
     // (its dY is the residual stream's gradient itself, which this block updates in place below: main stream)
-    if (int e = lin_bwd(t, dhi, kC, tp.feat, kIpaFeat, p.out, Mp, kC, kIpaFeat, dfeat, kIpaFeat, false, nullptr, false, false)) return e;
+    LinBwdOp o{};
+    o.dy = dhi; o.ldy = kC;
+    o.x = tp.feat; o.ldx = kIpaFeat;
+    o.dx = dfeat; o.ldx_out = kIpaFeat;
+    o.main_stream = true;
+    if (int e = lin_bwd(t, p.out, Mp, kC, kIpaFeat, pl.dx_out, pl.dw_out, o)) return e;
     IpaAttnParams ap{};
     ap.proj = tp.proj; ap.rot = rot; ap.trans = trans;
     ap.mask_bl = (const float*)(r.ws + r.lay.mask_bl);
@@ -514,12 +651,16 @@ static int ipa_block_bwd(Train& t, const IpaW& w, const SubTapeIpa& tp, float* d
     ap.ngroups = r.B; ap.B = r.B; ap.L = r.L;
     launch32_ipa_bwd(ap, dfeat, dproj, dhw, qrec, t.grad(p.head_w), s, t.part, t.part_floats);
     LAUNCHCHK();
-    // the four input projections of xn = LN_affine(x_in)
-    launch32_ln_mod(tp.h_in, Mp, ModMap{w.gamma_beta, 1, 1, 0, 0}, 1, 0, 1, 1e-5f, t.ytmp, s);
-    if (int e = lin_bwd(t, dproj, kIpaProj, t.ytmp, kC, p.q, Mp, 128, kC, t.dy, kC, false)) return e;
-    if (int e = lin_bwd(t, dproj + 128, kIpaProj, t.ytmp, kC, p.kv, Mp, 256, kC, t.dy, kC, true)) return e;
-    if (int e = lin_bwd(t, dproj + 384, kIpaProj, t.ytmp, kC, p.q_points, Mp, 96, kC, t.dy, kC, true)) return e;
-    if (int e = lin_bwd(t, dproj + 480, kIpaProj, t.ytmp, kC, p.kv_points, Mp, 192, kC, t.dy, kC, true)) return e;
+    // the four input projections of xn = LN_affine(x_in): t.dy = sum_j dproj_j W_j
+    launch32_ln_mod(tp.h_in, Mp, ModMap{w.gamma_beta, 1, 1, 0, 0}, 1, 0, 1, 1e-5f, t.ytmp, s, nullptr, false);
+    const Lin lins[4] = {p.q, p.kv, p.q_points, p.kv_points};
+    for (int j = 0; j < 4; ++j) {
+        LinBwdOp q{};
+        q.dy = dproj + kIpaProjCols[j].col0; q.ldy = kIpaProj;
+        q.x = t.ytmp; q.ldx = kC;
+        q.dx = t.dy; q.ldx_out = kC; q.accumulate = j > 0;
+        if (int e = lin_bwd(t, lins[j], Mp, kIpaProjCols[j].m, kC, pl.dx_proj[j], pl.dw_proj[j], q)) return e;
+    }
     // affine LayerNorm (eps 1e-5): d gamma = sum dy * xhat, d beta = sum dy, d x
     if (float* g = t.grad(p.norm.w))
         launch32_colsum(t.dy, kC, tp.h_in, kC, nullptr, 2, Mp, kC, Mp, 1e-5f, g, 0, t.cpart, t.cpart_floats, s);
@@ -633,21 +774,24 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
     // one pass of the IPA stack over `hx` on the frames (rot, trans), taped into (ip, il, im); rel / w7 / b7: the
     // two-sided model's relative-frame input of this stream (latent_model.py:193-201), null for the one-sided model
     auto ipa_forward = [&](float* hx, const float* rel, const float* w7, const float* b7, const float* rot, const float* trans,
-                           const std::vector<SubTapeIpa>& ips, const std::vector<SubTapeAttn>& ils,
-                           const std::vector<SubTapeMlp>& ims) -> int {
+                           std::vector<SubTapeIpa>& ips, std::vector<SubTapeAttn>& ils, std::vector<SubTapeMlp>& ims) -> int {
         launch_ipa_init(c->aa_emb, r.aatype, rel, w7, b7, hx, r.B, r.B, r.L, s);
         for (int i = 0; i < nl; ++i) {
             const IpaW& w = c->ipa[i];
             const auto& p = w.slot;
             const ModMap mm{r.mod() + c->ipa_off(i), r.L, r.B, r.mod_step_stride, r.mod_group_stride};
-            const SubTapeIpa& tp = ips[i];
+            SubTapeIpa& tp = ips[i];
             const F32Bufs fb = f32_bufs(r);
+            const Lin lins[4] = {p.q, p.kv, p.q_points, p.kv_points};
+            const bool w_al[5] = {al16(t.w(p.q.w)), al16(t.w(p.kv.w)), al16(t.w(p.q_points.w)), al16(t.w(p.kv_points.w)), al16(t.w(p.out.w))};
+            const IpaPlan& pl = tp.plan = plan_ipa(t, Mp, w_al);
             HIPCHK(hipMemcpyAsync(tp.h_in, hx, (size_t)Mp * kC * 4, hipMemcpyDeviceToDevice, s));
-            launch32_ln_mod(hx, Mp, ModMap{w.gamma_beta, 1, 1, 0, 0}, 1, 0, 1, 1e-5f, fb.y, s);
-            step_linear(t, fb.y, kC, t.w(p.q.w), kC, t.w(p.q.b), Mp, 128, kC, 0, tp.proj, kIpaProj, 0, 0.f, s);
-            step_linear(t, fb.y, kC, t.w(p.kv.w), kC, t.w(p.kv.b), Mp, 256, kC, 0, tp.proj, kIpaProj, 128, 0.f, s);
-            step_linear(t, fb.y, kC, t.w(p.q_points.w), kC, t.w(p.q_points.b), Mp, 96, kC, 0, tp.proj, kIpaProj, 384, 0.f, s);
-            step_linear(t, fb.y, kC, t.w(p.kv_points.w), kC, t.w(p.kv_points.b), Mp, 192, kC, 0, tp.proj, kIpaProj, 480, 0.f, s);
+            launch32_ln_mod(hx, Mp, ModMap{w.gamma_beta, 1, 1, 0, 0}, 1, 0, 1, 1e-5f, fb.y, s, nullptr, false);
+            for (int j = 0; j < 4; ++j) {
+                LinearParams q = lin_op(fb.y, kC, t.w(lins[j].w), kC, t.w(lins[j].b), Mp, kIpaProjCols[j].m, kC, tp.proj, kIpaProj);
+                q.col0 = kIpaProjCols[j].col0;
+                step_linear(q, pl.proj[j], s);
+            }
             IpaAttnParams ap{};
             ap.proj = tp.proj; ap.rot = rot; ap.trans = trans;
             ap.mask_bl = (const float*)(r.ws + r.lay.mask_bl);
@@ -655,10 +799,12 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
             ap.ngroups = r.B; ap.B = r.B; ap.L = r.L;
             ap.part = t.part; ap.part_floats = t.part_floats;      // few groups: key loop sliced over workgroups
             launch_ipa_attn(ap, s);
-            step_linear(t, tp.feat, kIpaFeat, t.w(p.out.w), kIpaFeat, t.w(p.out.b), Mp, kC, kIpaFeat, 2, hx, kC, 0, 0.f, s);
+            LinearParams lo = lin_op(tp.feat, kIpaFeat, t.w(p.out.w), kIpaFeat, t.w(p.out.b), Mp, kC, kIpaFeat, hx, kC);
+            lo.mode = kLinGated;   // (gated = 0: the ungated residual hx += linear_out(feat))
+            step_linear(lo, pl.out, s);
             LAUNCHCHK();
-            if (int e = attn_fwd_tape(t, w.mha_l, hx, Mp, axI, mm, 0, 1, 2, mkI, 1, r.L, ils[i])) return e;
-            if (int e = mlp_fwd_tape(t, w.ffn, hx, Mp, mm, 3, 4, 5, ims[i])) return e;
+            if (int e = attn_fwd_tape(t, w.mha_l, hx, Mp, axI, mm, 0, 1, 2, mkI, 1, r.L, r.L, ils[i])) return e;
+            if (int e = mlp_fwd_tape(t, w.ffn, hx, Mp, mm, 3, 4, 5, r.L, ims[i])) return e;
         }
         return 0;
     };
@@ -701,18 +847,19 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
     for (int i = 0; i < nl; ++i) {
         const TrunkW& w = c->trunk[i];
         const ModMap mm{r.mod() + c->trunk_off(i), r.T * r.L, r.B, 0, r.mod_group_stride};
-        if (int e = attn_fwd_tape(t, w.mha_l, h, N, axL, mm, 0, 1, 2, mk, 1, r.L, t.tl[i])) return e;
-        if (int e = attn_fwd_tape(t, w.mha_t, h, N, axT, mm, 3, 4, 5, mk, r.L, r.T, t.tt[i])) return e;
-        if (int e = mlp_fwd_tape(t, w.ffn, h, N, mm, 6, 7, 8, t.tm[i])) return e;
+        if (int e = attn_fwd_tape(t, w.mha_l, h, N, axL, mm, 0, 1, 2, mk, 1, r.L, TL, t.tl[i])) return e;
+        if (int e = attn_fwd_tape(t, w.mha_t, h, N, axT, mm, 3, 4, 5, mk, r.L, r.T, TL, t.tt[i])) return e;
+        if (int e = mlp_fwd_tape(t, w.ffn, h, N, mm, 6, 7, 8, TL, t.tm[i])) return e;
     }
     t.defer_gate = false;
     flush_pending(t, h);
     LAUNCHCHK();
     const ModMap fm{r.mod() + c->final_off(), r.T * r.L, r.B, 0, r.mod_group_stride};
+    const FinalPlan fin = plan_final(t, N, r.D, TL, al16(t.w(c->slot.fin.w)), true);   // (fm: shift chunk 0, scale chunk 1)
     {
         const F32Bufs fb = f32_bufs(r);
-        launch32_ln_mod(h, N, fm, 0, 1, 0, 1e-6f, fb.y, s);
-        step_linear(t, fb.y, kC, t.w(c->slot.fin.w), kC, t.w(c->slot.fin.b), N, r.D, kC, 0, pred, r.D, 0, 0.f, s);
+        launch32_ln_mod(h, N, fm, 0, 1, 0, 1e-6f, fb.y, s, nullptr, false);
+        step_linear(lin_op(fb.y, kC, t.w(c->slot.fin.w), kC, t.w(c->slot.fin.b), N, r.D, kC, pred, r.D), fin.lin, s);
         launch_masked_mse(pred, target, loss_mask, loss, TL * r.D, r.B, s, t.cpart, t.cpart_floats);
         LAUNCHCHK();
     }
@@ -747,7 +894,7 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
         float *pt = t.part, *cpt = t.cpart;
         if (gw || gb)   // (the block's d mod rows are complete here and nothing writes them again)
             if (int e = t.fork(&sw, &pt, &cpt)) return e;
-        if (gw) step_dw(t, t.dmod + off, (int)modld, silu_bwd, kC, r.B, rows, kC, gw, pt, sw);
+        if (gw) step_dw_now(t, dw_op(t.dmod + off, (int)modld, silu_bwd, kC, r.B, rows, kC, gw, nullptr, pt, t), sw);
         if (gb) launch32_colsum(t.dmod + off, (int)modld, nullptr, 0, nullptr, 0, r.B, rows, r.B, 0.f, gb, 0, cpt, t.cpart_floats, sw);
         return 0;
     };
@@ -756,9 +903,13 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
     float* dpred = t.dqkv;   // [N][D] fits the (idle) dqkv scratch
     launch32_loss_grad(pred, target, loss_mask, TL * r.D, r.B, t.dsilu, dpred, s, t.cpart, t.cpart_floats);   // t.dsilu[0..B) = mask sums (scratch)
     {   // final layer: out = linear(modulate(LN(h)))
-        launch32_ln_mod(h, N, fm, 0, 1, 0, 1e-6f, t.ytmp, s);
-        if (int e = lin_bwd(t, dpred, r.D, t.ytmp, kC, c->slot.fin, N, r.D, kC, t.dy, kC, false)) return e;
-        lnmod_bwd(t, h, t.dy, N, fm, 0, 1, TL, modld, t.dmod + c->final_off(), t.dh, false);
+        launch32_ln_mod(h, N, fm, 0, 1, 0, 1e-6f, t.ytmp, s, nullptr, false);
+        LinBwdOp o{};   // t.dy = d pred W
+        o.dy = dpred; o.ldy = r.D;
+        o.x = t.ytmp; o.ldx = kC;
+        o.dx = t.dy; o.ldx_out = kC;
+        if (int e = lin_bwd(t, c->slot.fin, N, r.D, kC, fin.dx, fin.dw, o)) return e;
+        lnmod_bwd(t, fin.ln, h, t.dy, N, fm, 0, 1, TL, modld, t.dmod + c->final_off(), t.dh, false);
         if (int e = head(c->slot.fin_ada, c->final_off(), 2 * kC)) return e;
         LAUNCHCHK();
         if (int e = t.end_sub()) return e;
@@ -780,8 +931,8 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
             hipStream_t sw = s;
             float *pt = t.part, *cpt = t.cpart;
             if (int e = t.fork(&sw, &pt, &cpt)) return e;
-            if (float* g = t.grad(c->slot.latent.w)) step_dw(t, t.dh, kC, xt, r.D, N, kC, r.D, g, pt, sw);
-            if (float* g = t.grad(c->slot.cond.w)) step_dw(t, t.dh, kC, r.x_cond, r.D, N, kC, r.D, g, pt, sw);
+            if (float* g = t.grad(c->slot.latent.w)) step_dw_now(t, dw_op(t.dh, kC, xt, r.D, N, kC, r.D, g, nullptr, pt, t), sw);
+            if (float* g = t.grad(c->slot.cond.w)) step_dw_now(t, dw_op(t.dh, kC, r.x_cond, r.D, N, kC, r.D, g, nullptr, pt, t), sw);
             if (float* g = t.grad(c->slot.latent.b)) launch32_colsum(t.dh, kC, nullptr, 0, nullptr, 0, N, kC, N, 0.f, g, 0, cpt, t.cpart_floats, sw);
             if (float* g = t.grad(c->slot.cond.b)) launch32_colsum(t.dh, kC, nullptr, 0, nullptr, 0, N, kC, N, 0.f, g, 0, cpt, t.cpart_floats, sw);
         }
@@ -817,7 +968,7 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
         // stack input: aatype_to_emb[aatype] (+ latent_to_emb_{f,r}(rel7))
         if (float* g = t.grad(c->slot.aatype)) launch32_embed_rows_bwd(dhx, r.aatype, r.B, r.B, r.L, g, s);
         if (rel) {
-            if (float* g = t.grad(rel7.w)) step_dw(t, dhx, kC, rel, 7, Mp, kC, 7, g, t.part, s);
+            if (float* g = t.grad(rel7.w)) step_dw_now(t, dw_op(dhx, kC, rel, 7, Mp, kC, 7, g, nullptr, t.part, t), s);
             if (float* g = t.grad(rel7.b)) launch32_colsum(dhx, kC, nullptr, 0, nullptr, 0, Mp, kC, Mp, 0.f, g, 0, t.cpart, t.cpart_floats, s);
         }
         LAUNCHCHK();
@@ -835,12 +986,15 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
         float* h1 = emb + (size_t)r.B * 256;          // [B][384]
         float* dp1 = h1 + (size_t)r.B * kC;
         float* dp2 = dp1 + (size_t)r.B * kC;
-        if (!launch32_skinny_wt(t.dmod, (int)modld, c->ada_w, kC, r.B, kC, c->modrow, dst, t.cpart, t.cpart_floats, s))
-            step_linear(t, t.dmod, (int)modld, c->ada_w, kC, nullptr, r.B, kC, c->modrow, 0, dst, kC, 0, 0.f, s, 1);
+        if (!launch32_skinny_wt(t.dmod, (int)modld, c->ada_w, kC, r.B, kC, c->modrow, dst, t.cpart, t.cpart_floats, s)) {
+            LinearParams q = lin_op(t.dmod, (int)modld, c->ada_w, kC, nullptr, r.B, kC, c->modrow, dst, kC);
+            q.wtrans = 1;   // (W_ada as stored)
+            step_linear(q, linear_form(t.bf16, LinShape{q.n, q.m, q.k, q.lda, q.ldw, 1, true, true, false}, false), s);
+        }
         launch32_temb_bwd(tvals, r.B, c->d.time_multiplier, c->t_w0, c->t_b0, c->t_w2, c->t_b2, dst, emb, h1, dp1, dp2, s);
-        if (float* g = t.grad(c->slot.t2.w)) step_dw(t, dp2, kC, h1, kC, r.B, kC, kC, g, t.part, s);
+        if (float* g = t.grad(c->slot.t2.w)) step_dw_now(t, dw_op(dp2, kC, h1, kC, r.B, kC, kC, g, nullptr, t.part, t), s);
         if (float* g = t.grad(c->slot.t2.b)) launch32_colsum(dp2, kC, nullptr, 0, nullptr, 0, r.B, kC, r.B, 0.f, g, 0, t.cpart, t.cpart_floats, s);
-        if (float* g = t.grad(c->slot.t0.w)) step_dw(t, dp1, kC, emb, 256, r.B, kC, 256, g, t.part, s);
+        if (float* g = t.grad(c->slot.t0.w)) step_dw_now(t, dw_op(dp1, kC, emb, 256, r.B, kC, 256, g, nullptr, t.part, t), s);
         if (float* g = t.grad(c->slot.t0.b)) launch32_colsum(dp1, kC, nullptr, 0, nullptr, 0, r.B, kC, r.B, 0.f, g, 0, t.cpart, t.cpart_floats, s);
         LAUNCHCHK();
     }
@@ -895,19 +1049,20 @@ extern "C" int32_t mdgen_train_set_milestone_events(mdgen_ctx* c, void* const* e
     return 0;
 }
 
-// ---- test hooks: one linear layer / one weight gradient through the training step's dispatch ---------------------------
+// ---- test hooks: one linear layer / one weight gradient / one attention through the training step's form functions ---------
 extern "C" int32_t mdgen_debug_train_linear(int32_t precision, const float* a, int32_t lda, const float* w, int32_t ldw,
                                             const float* bias, int64_t n, int32_t m, int32_t k, float* c, int32_t ldc, void* scratch,
                                             void* stream) {
     NONNULL(a, w, c);
     if ((precision != 16 && precision != 32) || n < 1 || m < 1 || k < 1) return fail(-2, "precision 16 | 32; n, m, k >= 1");
     hipStream_t s = (hipStream_t)stream;
-    if (precision == 16) {
-        const void* pk = scratch && launch16_pack_wstream(&w, 1, m, ldw, n, m, k, 0, scratch, s) ? scratch : nullptr;
-        launch16_linear(a, lda, w, ldw, bias, n, m, k, 0, c, ldc, 0, kNoMod, 0, 0, 0.f, s, 0, nullptr, pk);
-    } else {
-        launch32_linear(a, lda, w, ldw, bias, n, m, k, 0, c, ldc, 0, kNoMod, 0, 0, 0.f, s);
+    LinearParams p = lin_op(a, lda, w, ldw, bias, n, m, k, c, ldc);
+    const LinearForm form = linear_form(precision == 16, LinShape{n, m, k, lda, ldw, 0, al16(a), al16(w), false}, scratch != nullptr);
+    if (linear_streams(form)) {
+        launch16_pack_wstream(&w, 1, m, ldw, m, k, 0, scratch, s);
+        p.wpack = (const unsigned char*)scratch;
     }
+    step_linear(p, form, s);
     LAUNCHCHK();
     return 0;
 }
@@ -917,10 +1072,11 @@ extern "C" int32_t mdgen_debug_train_dw(int32_t precision, const float* dy, int3
     if ((precision != 16 && precision != 32) || n < 1 || m < 1 || k < 1) return fail(-2, "precision 16 | 32; n, m, k >= 1");
     if (part_floats < (int64_t)2 * m * (k + 1)) return fail(-2, "part_floats must be >= 2 m (k + 1)");
     hipStream_t s = (hipStream_t)stream;
-    bool bias_done = false;
-    if (precision == 16) bias_done = launch16_dw(dy, ldy, x, ldx, n, m, k, dw, part, (size_t)part_floats, s, db);
-    else launch32_dw(dy, ldy, x, ldx, n, m, k, dw, part, (size_t)part_floats, s);
-    if (db && !bias_done) launch32_colsum(dy, ldy, nullptr, 0, nullptr, 0, n, m, n, 0.f, db, 0, part, (size_t)part_floats, s);
+    const DwParams p{dy, ldy, x, ldx, n, m, 1, k, {dw, nullptr, nullptr}, {db, nullptr, nullptr}, part, (size_t)part_floats};
+    const DwForm form = dw_form(precision == 16, dw_shape(p), p.part_floats, false, false);
+    launch_dw(p, form, s);
+    if (db && !dw_bias_rides(form, dw_shape(p), p.part_floats))
+        launch32_colsum(dy, ldy, nullptr, 0, nullptr, 0, n, m, n, 0.f, db, 0, part, (size_t)part_floats, s);
     LAUNCHCHK();
     return 0;
 }
@@ -935,23 +1091,118 @@ extern "C" int32_t mdgen_debug_train_attention(int32_t precision, const float* q
         return fail(-2, "precision 16 | 160 | 161 | 32; ntok, nseq, len, inner >= 1");
     hipStream_t s = (hipStream_t)stream;
     const AxisMap ax{nseq, len, inner, outer_stride, inner_stride, pos_stride};
-    // 16: the training step's attention form for the axis; 160: the chunked kernels for every length; 161: q, k given UNROTATED,
-    // the sequence-resident kernels rotate them (as the training step runs them)
-    const bool seq_form = precision != 160 && attn16_seq_form(ax);
-    const bool rope_inside = precision == 161;
-    if (precision == 160 || precision == 161) precision = 16;
-    const MaskMap mk{mask, 0};
-    // position of a token on this axis, as k32_rope_bwd wants it: (token / pos_div) % pos_mod
-    const long pos_div = pos_stride;
-    if (rope_inside && !seq_form) return fail(-2, "precision 161: only axes of 129 .. 256 positions rotate q, k inside the kernels");
-    if (precision == 16) {
-        launch16_attn(qkv, 3 * kC, ax, mk, bias_k, bias_v, inv_freq, out, s, lse, seq_form, rope_inside);
-        launch16_attn_bwd(qkv, 3 * kC, ax, mk, bias_k, bias_v, inv_freq, out, dout, dqkv, stats, dbias, s, lse, seq_form, rope_inside);
-    } else {
-        launch32_attn(qkv, 3 * kC, ax, mk, bias_k, bias_v, inv_freq, out, s, lse);
-        launch32_attn_bwd(qkv, 3 * kC, ax, mk, bias_k, bias_v, inv_freq, out, dout, dqkv, stats, dbias, s, lse);
-        launch32_rope_bwd(dqkv, ntok, 3 * kC, pos_div, len, inv_freq, 1.0f / std::sqrt((float)kDH), s);
-    }
+    // 32 / 16: the training step's attention form for the axis, q and k given rotated (so Seq where the step takes SeqRope);
+    // 160: the chunked kernels for every length; 161: q, k given UNROTATED, the sequence-resident kernels rotate them (as the
+    // training step runs them)
+    TrainAttnForm form = train_attn_form(precision != 32, ax);
+    if (precision == 161 && form != TrainAttnForm::SeqRope)
+        return fail(-2, "precision 161: only axes of 129 .. 256 positions rotate q, k inside the kernels");
+    if (precision == 16 && form == TrainAttnForm::SeqRope) form = TrainAttnForm::Seq;
+    if (precision == 160) form = TrainAttnForm::Chunked;
+    TrainAttnParams a{qkv, 3 * kC, ax, MaskMap{mask, 0}, bias_k, bias_v, inv_freq, out, lse, dout, dqkv, stats, dbias, false};
+    launch_train_attn(a, form, s);
+    launch_train_attn_bwd(a, form, s);
+    if (form == TrainAttnForm::Exact)   // position of a token on this axis, as k32_rope_bwd wants it: (token / pos_stride) % len
+        launch32_rope_bwd(dqkv, ntok, 3 * kC, pos_stride, len, inv_freq, 1.0f / std::sqrt((float)kDH), s);
     LAUNCHCHK();
+    return 0;
+}
+
+// ---- the plans of a step, host only ---------------------------------------------------------------------------------------
+namespace {
+const char* form_name(LinearForm f) {
+    static const char* const n[] = {"k32_linear", "k16_linear_wdma<false>", "k16_linear_wdma<true>", "k16_linear_wide",
+                                    "k16_linear_small", "k16_linear_fast", "k16_linear"};
+    return n[(int)f];
+}
+const char* form_name(DwForm f) {
+    static const char* const n[] = {"k32_dw", "k16_dw_wide<false, false>", "k16_dw_wide<true, false>", "k16_dw_wide<false, true>",
+                                    "k16_dw_wide<true, true>", "k16_dw<true>", "k16_dw<false>"};
+    return n[(int)f];
+}
+const char* form_name(TrainAttnForm f) {
+    static const char* const n[] = {"k32_attn", "k16_attn", "k16_attn_seq", "k16_attn_seq+rope"};
+    return n[(int)f];
+}
+const char* form_name(GateBwdForm f) { return f == GateBwdForm::Sums ? "k32_gate_bwd_sums" : "k32_gate_mul"; }
+const char* form_name(LnBwdForm f) { return f == LnBwdForm::Sums ? "k32_ln_bwd_sums" : "k32_ln_bwd"; }
+struct PlanJson {
+    char* buf;
+    size_t cap, len = 0;
+    void add(const char* fmt, ...) __attribute__((format(printf, 2, 3))) {
+        va_list ap;
+        va_start(ap, fmt);
+        const int n = len < cap ? vsnprintf(buf + len, cap - len, fmt, ap) : 0;
+        va_end(ap);
+        len = n < 0 || len + (size_t)n >= cap ? cap : len + (size_t)n;   // (cap: did not fit)
+    }
+    void dx(const char* key, const DxPlan& p) {
+        add(", \"%s\": [\"%s\", \"%s\"]", key, p.route == DxRoute::Streamed ? "streamed" : p.route == DxRoute::TurnedWeight ? "turned" : "wtrans",
+            form_name(p.form));
+    }
+    void dw(const char* key, const DwPlan& p) { add(", \"%s\": [\"%s\", %s]", key, form_name(p.form), p.bias_rides ? "true" : "false"); }
+    void attn(const char* key, const AttnPlan& p) {
+        add("\"%s\": {\"rows\": \"%s\", \"dqkv\": \"%s\", \"qkv\": [", key, p.rows16 ? "bf16" : "fp32", p.dqkv16 ? "bf16" : "fp32");
+        if (p.qkv_one_pass) add("\"%s\"", form_name(p.qkv[0]));
+        else add("\"%s\", \"%s\", \"%s\"", form_name(p.qkv[0]), form_name(p.qkv[1]), form_name(p.qkv[2]));
+        add("], \"attn\": \"%s\", \"out\": \"%s\", \"gate\": \"%s\", \"ln\": \"%s\"", form_name(p.attn), form_name(p.out), form_name(p.gate),
+            form_name(p.ln));
+        dx("dx_out", p.dx_out); dw("dw_out", p.dw_out); dx("dx_qkv", p.dx_qkv); dw("dw_qkv", p.dw_qkv);
+        add("}");
+    }
+    void mlp(const char* key, const MlpPlan& p) {
+        add("\"%s\": {\"rows\": \"%s\", \"fc1\": \"%s\", \"fc2\": \"%s\", \"gate\": \"%s\", \"ln\": \"%s\"", key, p.rows16 ? "bf16" : "fp32",
+            form_name(p.fc1), form_name(p.fc2), form_name(p.gate), form_name(p.ln));
+        dx("dx_fc2", p.dx_fc2); dw("dw_fc2", p.dw_fc2); dx("dx_fc1", p.dx_fc1); dw("dw_fc1", p.dw_fc1);
+        add("}");
+    }
+};
+}  // namespace
+
+extern "C" int32_t mdgen_debug_train_plan(const mdgen_shape* sh, int32_t tps_condition, int32_t num_layers, int32_t train_precision,
+                                          int32_t weight_misalign_bytes, char* buf, size_t buflen) {
+    if (!sh || !buf) return fail(-1, "null argument");
+    if (num_layers < 1 || num_layers > 8 || (train_precision != 16 && train_precision != 32) || sh->B < 1 || sh->T < 1 || sh->L < 1)
+        return fail(-2, "num_layers in 1..8, train_precision 16 | 32, B, T, L >= 1");
+    Train t;   // (the plan functions read the operand mode and the scratch sizes only)
+    t.bf16 = train_precision == 16;
+    t.part_floats = kPartFloats;
+    t.cpart_floats = kCpartFloats;
+    const bool al = (weight_misalign_bytes & 15) == 0;   // every weight of the step alike
+    const bool w_al[5] = {al, al, al, al, al};
+    const bool w4[4] = {al, al, al, al}, w2[2] = {al, al};
+    const long B = sh->B, T = sh->T, L = sh->L, N = B * T * L, Mp = B * L, TL = T * L;
+    const AxisMap axI{(int)B, (int)L, (int)B, 0, (int)L, 1};
+    const AxisMap axL{(int)(B * T), (int)L, (int)(B * T), 0, (int)L, 1};
+    const AxisMap axT{(int)(B * L), (int)T, (int)L, (int)(T * L), 1, (int)L};
+    PlanJson js{buf, buflen};
+    const IpaPlan ip = plan_ipa(t, Mp, w_al);
+    js.add("{\"rows\": {\"ipa\": %ld, \"trunk\": %ld}, \"ipa_block\": {\"proj\": [\"%s\", \"%s\", \"%s\", \"%s\"], \"out\": \"%s\"", Mp, N,
+           form_name(ip.proj[0]), form_name(ip.proj[1]), form_name(ip.proj[2]), form_name(ip.proj[3]), form_name(ip.out));
+    const char* const dxn[4] = {"dx_q", "dx_kv", "dx_q_points", "dx_kv_points"};
+    const char* const dwn[4] = {"dw_q", "dw_kv", "dw_q_points", "dw_kv_points"};
+    for (int j = 0; j < 4; ++j) {
+        js.dx(dxn[j], ip.dx_proj[j]);
+        js.dw(dwn[j], ip.dw_proj[j]);
+    }
+    js.dx("dx_out", ip.dx_out);
+    js.dw("dw_out", ip.dw_out);
+    js.add("}, ");
+    js.attn("ipa_attn", plan_attn(t, Mp, axI, L, w4, true));
+    js.add(", ");
+    js.mlp("ipa_mlp", plan_mlp(t, Mp, L, w2, true));
+    js.add(", ");
+    js.attn("trunk_attn_l", plan_attn(t, N, axL, TL, w4, true));
+    js.add(", ");
+    js.attn("trunk_attn_t", plan_attn(t, N, axT, TL, w4, true));
+    js.add(", ");
+    js.mlp("trunk_mlp", plan_mlp(t, N, TL, w2, true));
+    // (latent_dim: 21, 28 for the two-sided model -- mdgen_ctx_create's D; every sub-layer's scale chunk lies behind its shift chunk)
+    const FinalPlan fin = plan_final(t, N, tps_condition ? 28 : 21, TL, al, true);
+    js.add(", \"final\": {\"lin\": \"%s\", \"ln\": \"%s\"", form_name(fin.lin), form_name(fin.ln));
+    js.dx("dx", fin.dx);
+    js.dw("dw", fin.dw);
+    js.add("}}");
+    if (js.len >= js.cap) return fail(-7, "plan buffer too small (%zu bytes)", buflen);
     return 0;
 }
