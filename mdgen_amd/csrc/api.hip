@@ -78,6 +78,7 @@ struct MhaW {
     bf16x8 *wq = nullptr, *wk = nullptr, *wv_flash = nullptr, *wv_small = nullptr, *wo = nullptr;
     float *bq = nullptr, *bk = nullptr, *bv_flash = nullptr, *bv_small = nullptr, *bo = nullptr;
     float *bias_k = nullptr, *bias_v = nullptr;
+    uint32_t* l4tab = nullptr;   // bias key / value as k_ln_qkv_attn4 reads them (launch_l4_bias_table; written by mdgen_ctx_finalize)
     struct { Lin q, k, v, o; int bias_k = -1, bias_v = -1; } slot;
 };
 struct FfnW {
@@ -355,6 +356,7 @@ static int register_mha(mdgen_ctx* c, const std::string& pre, MhaW* m) {
     if (int r = c->dalloc(&m->wo, kPackCC)) return r;
     for (float** p : {&m->bq, &m->bk, &m->bv_flash, &m->bv_small, &m->bo, &m->bias_k, &m->bias_v})
         if (int r = c->dalloc(p, (size_t)kC)) return r;
+    if (int r = c->dalloc(&m->l4tab, (size_t)2 * kL4Tab)) return r;
     m->slot.q.w = SETTER(pre + "q_proj.weight", {
         WANT(kC, kC);
         launch_pack_rows(data, kC, c->map_qk, 12, kKS, qscale, m->wq, s);
@@ -666,6 +668,11 @@ extern "C" int32_t mdgen_ctx_finalize(mdgen_ctx* c, void* stream) {
         if (!w.provided) return fail(-5, "weight '%s' was not provided", w.name.c_str());
     if (!c->inv_freq_set) return fail(-5, "rot_emb.inv_freq was not provided");
     launch_rope_table(c->rope, c->inv_freq, kMaxPos + 1, (hipStream_t)stream);
+    LAUNCHCHK();
+    // tables that depend on two weights (the learned bias key and the rotary frequencies): after both, in stream order
+    auto l4tab = [&](const MhaW& m) { launch_l4_bias_table(m.bias_k, m.bias_v, c->rope, m.l4tab, (hipStream_t)stream); };
+    for (const TrunkW& t : c->trunk) l4tab(t.mha_l);
+    for (const IpaW& w : c->ipa) l4tab(w.mha_l);
     LAUNCHCHK();
     c->finalized = true;
     return 0;
@@ -1293,6 +1300,7 @@ static int attn_sublayer(const Run& r, const AttnPlan& pl, const MhaW& m, const 
         q.bv = m.bv_small;
         q.bias_k = m.bias_k;
         q.bias_v = m.bias_v;
+        q.l4tab = m.l4tab;
         q.mk = mk;
         q.obuf = r.obufp;
         if (pl.proj == ProjAt::Attention) {

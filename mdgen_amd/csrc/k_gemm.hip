@@ -21,15 +21,98 @@ constexpr int kPanelBytes = kPanel * kRowB;
 // holds, for its token, 12 features of each head = six rotary pairs (i, i+12): RoPE is lane-local
 // and the accumulators ARE the attention MFMA fragments (DESIGN.md "fragment layout").
 // =================================================================================================
-template <bool ROPE, int TT = 2>
+// ---- per-launch constants in LDS -----------------------------------------------------------------------------------------------
+// The permuted q / k / v biases and the rotary rows a panel needs are the same for every wave and every GEMM of a workgroup.  Fetched
+// from global memory where they are used -- after each GEMM, with nothing left to run beside the wait -- each fetch is an exposed L2
+// round trip in the wave's chain.  They are requested once at kernel start instead, together with the row table's loads, written to
+// LDS behind the barrier that follows (which waits for global loads anyway) and are visible after the barrier behind the LayerNorm
+// prologue; the epilogues read LDS.
+// Rotary rows are staged 144 bytes apart (128 used): a 16-lane pass of a ds_read_b128 over consecutive rows then touches sixteen
+// distinct 16-byte bank groups instead of two.
+constexpr int kRopeLds = kRopeRow + 4;
+constexpr int kBiasUnits = 3 * kC / 4;   // 16-byte units of the three bias vectors
+struct QkvStage {                        // k_ln_qkv<false, .>, k_ln_qkv8: rotary rows of the panel's 64 positions
+    float bias[3][kC];
+    float rope[kPanel][kRopeLds];
+};
+struct Attn4Stage {                      // k_ln_qkv_attn4: positions 0..3, and the bias key / value table (launch_l4_bias_table)
+    float bias[3][kC];
+    uint32_t tab[2][kL4Tab];
+    float rope[4][kRopeLds];
+};
+__device__ __forceinline__ const f32x4* stage_bias_src(const QkvParams& p, int u) {   // u < kBiasUnits
+    const float* b = u < kC / 4 ? p.bq : u < 2 * (kC / 4) ? p.bk : p.bv;
+    return reinterpret_cast<const f32x4*>(b) + (u % (kC / 4));
+}
+// NT threads; unit u = tid + i NT: biases, then 8 units per rotary row (position pos0 + row, at most len: as the epilogue clamps it)
+template <int NT>
+struct QkvStager {
+    static constexpr int kUnits = kBiasUnits + kPanel * 8, kPer = (kUnits + NT - 1) / NT;
+    f32x4 r[kPer];
+    __device__ __forceinline__ void load(const QkvParams& p, int pos0, int len, int tid) {
+#pragma unroll
+        for (int i = 0; i < kPer; ++i) {
+            int u = tid + i * NT;
+            if (u >= kUnits) u = kUnits - 1;   // (unconditional loads; the store below skips these)
+            const int v = u >= kBiasUnits ? u - kBiasUnits : 0;
+            int pos = pos0 + (v >> 3);
+            if (pos > len) pos = len;
+            const f32x4* rs = reinterpret_cast<const f32x4*>(p.rope + (long)pos * kRopeRow) + (v & 7);
+            r[i] = *(u < kBiasUnits ? stage_bias_src(p, u) : rs);
+        }
+    }
+    __device__ __forceinline__ void store(QkvStage* st, int tid) const {
+#pragma unroll
+        for (int i = 0; i < kPer; ++i) {
+            const int u = tid + i * NT;
+            if (u < kBiasUnits) {
+                reinterpret_cast<f32x4*>(&st->bias[0][0])[u] = r[i];
+            } else if (u < kUnits) {
+                const int v = u - kBiasUnits;
+                *reinterpret_cast<f32x4*>(&st->rope[v >> 3][4 * (v & 7)]) = r[i];
+            }
+        }
+    }
+};
+// 256 threads, two units each: biases (288), the table (96), rotary rows 0..3 (32)
+struct Attn4Stager {
+    static constexpr int kTab0 = kBiasUnits, kRope0 = kTab0 + 2 * kL4Tab / 4, kUnits = kRope0 + 4 * 8;
+    static_assert(kUnits <= 512 && kBiasUnits > 256, "two units per thread, the first always a bias unit");
+    f32x4 r[2];
+    __device__ __forceinline__ void load(const QkvParams& p, int tid) {
+        r[0] = *stage_bias_src(p, tid);
+        int u = tid + 256;
+        if (u >= kUnits) u = kUnits - 1;
+        const f32x4* src = u < kTab0    ? stage_bias_src(p, u < kTab0 ? u : 0)
+                           : u < kRope0 ? reinterpret_cast<const f32x4*>(p.l4tab) + (u - kTab0)
+                                        : reinterpret_cast<const f32x4*>(p.rope) + (u - kRope0);   // rows 0..3 are contiguous
+        r[1] = *src;
+    }
+    __device__ __forceinline__ void store(Attn4Stage* st, int tid) const {
+        reinterpret_cast<f32x4*>(&st->bias[0][0])[tid] = r[0];
+        const int u = tid + 256;
+        if (u < kTab0) {
+            reinterpret_cast<f32x4*>(&st->bias[0][0])[u] = r[1];
+        } else if (u < kRope0) {
+            reinterpret_cast<f32x4*>(&st->tab[0][0])[u - kTab0] = r[1];
+        } else if (u < kUnits) {
+            const int v = u - kRope0;
+            *reinterpret_cast<f32x4*>(&st->rope[v >> 3][4 * (v & 7)]) = r[1];
+        }
+    }
+};
+
+template <bool ROPE, int TT = 2, bool STAGED = false>
 __device__ __forceinline__ void epilogue_heads_T(const f32x16* acc /*[3 ft][TT]*/, const PanelRows* pr, int w,
-                                                 const float* __restrict__ bias_perm, const float* __restrict__ rope,
+                                                 const float* bias_perm, const float* rope,
                                                  bool small, int pos0, int len, int seq, int ntile, int tile0,
                                                  unsigned char* __restrict__ frag, __bf16* __restrict__ small_dst,
                                                  int which) {
     const int lane = lane_id(), hh = lane >> 5, tk = lane & 31;
     // All table reads of this epilogue (4 heads x 12 permuted biases, 2 rows x 12 rotary factors) are requested up
     // front as 16-byte loads: left inside the head loop each head paid its own L2 round trip (16 in sequence).
+    // bias_perm: the staged copy (QkvStage::bias); rope: STAGED: the panel's staged rotary rows (QkvStage::rope, by panel row), else
+    // the table in global memory, by position (SMALL layout).
     f32x4 bq[4][3];
     {
         const f32x4* bp = reinterpret_cast<const f32x4*>(bias_perm + (w * 2 + hh) * 48);
@@ -48,7 +131,7 @@ __device__ __forceinline__ void epilogue_heads_T(const f32x16* acc /*[3 ft][TT]*
         if (pos > len) pos = len;  // padding rows: any in-table position (values are never used)
         posv[tt] = pos;
         if (ROPE) {
-            const f32x4* rc = reinterpret_cast<const f32x4*>(rope + (long)pos * kRopeRow + 16 * hh);
+            const f32x4* rc = reinterpret_cast<const f32x4*>(STAGED ? rope + row * kRopeLds + 16 * hh : rope + (long)pos * kRopeRow + 16 * hh);
 #pragma unroll
             for (int i = 0; i < 4; ++i) rq[tt][i] = rc[i];
         }
@@ -113,7 +196,7 @@ __device__ __forceinline__ void epilogue_heads_T(const f32x16* acc /*[3 ft][TT]*
 // fragments of the P.V MFMA (lane = (d, half), register r = key slot) -- no data movement.
 template <int TT = 2>
 __device__ __forceinline__ void epilogue_v_flash(const f32x16* acc /*[TT][3 ft]*/, int w,
-                                                 const float* __restrict__ bias_perm, int seq, int ntile, int tile0,
+                                                 const float* bias_perm, int seq, int ntile, int tile0,
                                                  unsigned char* __restrict__ vf) {
     const int lane = lane_id(), hh = lane >> 5, n = lane & 31;
 #pragma unroll
@@ -251,6 +334,9 @@ extern "C" int mdgen_dev_attn4_stamps(void* host, size_t bytes) {
 template <bool SMALL, bool PRE = false>
 __global__ __launch_bounds__(256, 2) void k_ln_qkv(const QkvParams p) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[sizeof(PanelRows) + kPanelBytes];
+    __shared__ __attribute__((aligned(16))) unsigned char stage_[SMALL ? 16 : sizeof(QkvStage)];   // (SMALL layout: positions are token % len, not staged)
+    QkvStage* const stage = reinterpret_cast<QkvStage*>(stage_);
+    QkvStager<256> stager;
     PanelRows* pr = reinterpret_cast<PanelRows*>(smem);
     unsigned char* panel = smem + sizeof(PanelRows);
     int seq = 0, pos0 = 0, tile0 = 0;
@@ -261,6 +347,7 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv(const QkvParams p) {
         const int pn = blockIdx.x - seq * p.panels_per_seq;
         pos0 = pn * kPanel;
         tile0 = pn * 2;
+        stager.load(p, pos0, p.ax.len, threadIdx.x);
         setup_rows_axis(pr, p.ax, seq, pos0, p.mm);
         // key-validity words of this panel's two tiles for the attention kernel (kernels.h flash_vmask_*): the 64
         // lanes of wave 0 are the panel's 64 positions.  The sequence's last panel also writes the words behind it:
@@ -280,13 +367,15 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv(const QkvParams p) {
     }
     QKV_STAMP(0);
     __syncthreads();
+    if (!SMALL) stager.store(stage, threadIdx.x);   // visible after the barrier behind the LayerNorm prologue
     const int w = __builtin_amdgcn_readfirstlane(wave_id()), lane = lane_id();
+    const float *sbq = SMALL ? p.bq : stage->bias[0], *sbk = SMALL ? p.bk : stage->bias[1], *sbv = SMALL ? p.bv : stage->bias[2];
+    const float* srope = SMALL ? p.rope : &stage->rope[0][0];
     f32x16 acc[6];
     if (PRE) {
         prologue_bf16<kC>(panel, pr, p.obuf);
         __syncthreads();
-        zero_acc<6>(acc);
-        wave_gemm<2, 3, 24, false>(panel, kRowB, 0, 0, p.wo + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
+        wave_gemm<2, 3, 24, false, 4, true>(panel, kRowB, 0, 0, p.wo + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
         __syncthreads();   // every wave is done reading the panel: reuse it as four 12 KiB staging slabs
         epilogue_gate_residual_lds<3>(acc, pr, reinterpret_cast<float*>(panel) + w * (32 * 96), 96 * w, p.bo, p.mm, p.gate_chunk,
                                       true, p.h_rw);
@@ -298,28 +387,25 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv(const QkvParams p) {
     const int ntile = p.ax.ntile();
     const int len = p.ax.len;
     // ---- Q (heads 4w..4w+3), transposed
-    zero_acc<6>(acc);
-    wave_gemm<2, 3, 24, true>(panel, kRowB, 0, 0, p.wq + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
+    wave_gemm<2, 3, 24, true, 4, true>(panel, kRowB, 0, 0, p.wq + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
     QKV_STAMP(2);
-    epilogue_heads_T<true>(acc, pr, w, p.bq, p.rope, SMALL, pos0, len, seq, ntile, tile0, p.qf, p.qkv_small, 0);
+    epilogue_heads_T<true, 2, !SMALL>(acc, pr, w, sbq, srope, SMALL, pos0, len, seq, ntile, tile0, p.qf, p.qkv_small, 0);
     __builtin_amdgcn_sched_barrier(0);
     QKV_STAMP(3);
     // ---- K
-    zero_acc<6>(acc);
-    wave_gemm<2, 3, 24, true>(panel, kRowB, 0, 0, p.wk + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
+    wave_gemm<2, 3, 24, true, 4, true>(panel, kRowB, 0, 0, p.wk + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
     QKV_STAMP(4);
-    epilogue_heads_T<true>(acc, pr, w, p.bk, p.rope, SMALL, pos0, len, seq, ntile, tile0, p.kf, p.qkv_small, 1);
+    epilogue_heads_T<true, 2, !SMALL>(acc, pr, w, sbk, srope, SMALL, pos0, len, seq, ntile, tile0, p.kf, p.qkv_small, 1);
     __builtin_amdgcn_sched_barrier(0);
     QKV_STAMP(5);
     // ---- V
-    zero_acc<6>(acc);
     if (SMALL) {
-        wave_gemm<2, 3, 24, true>(panel, kRowB, 0, 0, p.wv + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
+        wave_gemm<2, 3, 24, true, 4, true>(panel, kRowB, 0, 0, p.wv + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
         epilogue_heads_T<false>(acc, pr, w, p.bv, nullptr, true, pos0, len, seq, ntile, tile0, nullptr, p.qkv_small, 2);
     } else {
-        wave_gemm<2, 3, 24, false>(panel, kRowB, 0, 0, p.wv + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
+        wave_gemm<2, 3, 24, false, 4, true>(panel, kRowB, 0, 0, p.wv + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
         QKV_STAMP(6);
-        epilogue_v_flash(acc, w, p.bv, seq, ntile, tile0, p.vf);
+        epilogue_v_flash(acc, w, sbv, seq, ntile, tile0, p.vf);
         if ((int)blockIdx.x - seq * p.panels_per_seq == p.panels_per_seq - 1) {   // the sequence's last panel
             __builtin_amdgcn_sched_barrier(0);   // after this wave's own K / V stores
             write_bias_slots(p, seq, w);
@@ -344,6 +430,27 @@ template <int J>
 __device__ __forceinline__ float quad_bcast(float v) {   // value of lane (quad base + J) in every lane of the quad
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), J * 0x55, 0xf, 0xf, true));
 }
+// acc + q * (k of lane quad base + J), the broadcast folded into the FMA's DPP operand: hipcc never folds update_dpp into its consumer
+// (one v_mov_b32_dpp + one v_fmac_f32 per term otherwise; DESIGN.md section 6, finding 29).  The same fused multiply-add, so the same bits.
+// hipcc does not know that these statements read another lane's register: it inserts NO wait states between a VALU write of `k` and
+// the DPP read (2 are required) -- every `k` goes through dpp_fence() first.
+template <int J>
+__device__ __forceinline__ float fmac_dpp(float acc, float k, float q) {
+    asm("v_fmac_f32_dpp %0, %1, %2 quad_perm:[%3,%3,%3,%3] row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(acc) : "v"(k), "v"(q), "n"(J));
+    return acc;
+}
+template <int J>
+__device__ __forceinline__ float mul_dpp(float k, float q) {   // q * (k of lane quad base + J)
+    float r;
+    asm("v_mul_f32_dpp %0, %1, %2 quad_perm:[%3,%3,%3,%3] row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(r) : "v"(k), "v"(q), "n"(J));
+    return r;
+}
+// the twelve values the following fmac_dpp / mul_dpp statements broadcast: written at least two wait states before the first DPP read
+__device__ __forceinline__ void dpp_fence(float (&k)[12]) {
+    asm volatile("s_nop 1"
+                 : "+v"(k[0]), "+v"(k[1]), "+v"(k[2]), "+v"(k[3]), "+v"(k[4]), "+v"(k[5]), "+v"(k[6]), "+v"(k[7]), "+v"(k[8]), "+v"(k[9]),
+                   "+v"(k[10]), "+v"(k[11]));
+}
 __device__ __forceinline__ float half_sum(float x) {   // x(lane) + x(lane ^ 32)
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
@@ -356,6 +463,22 @@ __device__ __forceinline__ void head_values(const f32x16* acc, int tt, int hd, c
         const int ap = 3 * hd + c, ft = ap >> 2, a = ap & 3;
 #pragma unroll
         for (int b = 0; b < 4; ++b) e[4 * c + b] = acc[ft * TT + tt][4 * a + b] + bq[c][b];
+    }
+}
+// The rotation of one rotary pair.  Left to the compiler, x2 c + x1 s is contracted into a fused multiply-add around either product,
+// and hipcc chooses by instantiation: around x2 c in the 64-row forms of k_ln_qkv_attn4, around x1 s in the 32-row form -- an ulp of
+// an fp32 value in front of a bf16 rounding, i.e. results that move with the compiler's choice whenever the code around them changes.
+// Written out, each form keeps the rounding it has had since it was introduced (X1S: the 32-row form's).
+template <bool X1S>
+__device__ __forceinline__ void rotate_pair(float x1, float x2, float c, float sn, float& e0, float& e1) {
+    const float a = x2 * sn;
+    e0 = __builtin_fmaf(x1, c, -a);
+    if (X1S) {
+        const float b = x1 * sn;
+        e1 = __builtin_fmaf(x2, c, b);
+    } else {
+        const float b = x2 * c;
+        e1 = __builtin_fmaf(x1, sn, b);
     }
 }
 __device__ __forceinline__ void load_head_bias(const float* bias_perm, int w, int hh, f32x4 (&bq)[4][3]) {
@@ -386,12 +509,15 @@ __global__ __launch_bounds__(512, 1) void k_ln_qkv8(const QkvParams p) {
     static_assert(!HALF || SPLIT, "32-row workgroups exist in the split form only");
     constexpr int TT = HALF ? 1 : 2, kRows = 32 * TT;
     __shared__ __attribute__((aligned(16))) unsigned char smem[sizeof(PanelRows) + kPanelBytes];
+    __shared__ __attribute__((aligned(16))) QkvStage stage;
+    QkvStager<512> stager;
     PanelRows* pr = reinterpret_cast<PanelRows*>(smem);
     unsigned char* panel = smem + sizeof(PanelRows);
     const int blk = SPLIT ? blockIdx.x >> 1 : blockIdx.x, half = SPLIT ? blockIdx.x & 1 : 0;
     const int seq = blk / p.panels_per_seq;
     const int pn = blk - seq * p.panels_per_seq;
     const int pos0 = pn * kRows, tile0 = pn * TT;
+    stager.load(p, pos0, p.ax.len, threadIdx.x);
     setup_rows_axis(pr, p.ax, seq, pos0, p.mm, kRows);
     if (wave_id() == 0 && half == 0) {   // key-validity words of this panel's tiles (as k_ln_qkv<false>)
         const int lane = lane_id(), len = p.ax.len, pos = pos0 + lane;
@@ -406,6 +532,7 @@ __global__ __launch_bounds__(512, 1) void k_ln_qkv8(const QkvParams p) {
         }
     }
     __syncthreads();
+    stager.store(&stage, threadIdx.x);   // visible after the barrier behind the LayerNorm prologue
     const int w8 = __builtin_amdgcn_readfirstlane(wave_id()), g = w8 >> 2, w = w8 & 3, lane = lane_id();
     if (HALF) {   // 32 rows: one batch of sixteen per wave group
         if (g == 0) prologue_ln<false, 0, 1>(panel, pr, p.h, p.mm, p.shift_chunk, p.scale_chunk, 1e-6f, w, lane);
@@ -422,24 +549,21 @@ __global__ __launch_bounds__(512, 1) void k_ln_qkv8(const QkvParams p) {
     const bool do_q = SPLIT ? half == 0 && g == 0 : g == 0, do_k = SPLIT ? half == 0 && g == 1 : g == 0;
     const bool do_v = SPLIT ? half == 1 && g == 0 : g == 1;
     if (do_q) {
-        zero_acc<3 * TT>(acc);
-        wave_gemm<TT, 3, 24, true>(panel, kRowB, 0, 0, p.wq + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
-        epilogue_heads_T<true, TT>(acc, pr, w, p.bq, p.rope, false, pos0, len, seq, ntile, tile0, p.qf, p.qkv_small, 0);
+        wave_gemm<TT, 3, 24, true, 4, true>(panel, kRowB, 0, 0, p.wq + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
+        epilogue_heads_T<true, TT, true>(acc, pr, w, stage.bias[0], &stage.rope[0][0], false, pos0, len, seq, ntile, tile0, p.qf, p.qkv_small, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
     if (do_k) {
-        zero_acc<3 * TT>(acc);
-        wave_gemm<TT, 3, 24, true>(panel, kRowB, 0, 0, p.wk + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
-        epilogue_heads_T<true, TT>(acc, pr, w, p.bk, p.rope, false, pos0, len, seq, ntile, tile0, p.kf, p.qkv_small, 1);
+        wave_gemm<TT, 3, 24, true, 4, true>(panel, kRowB, 0, 0, p.wk + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
+        epilogue_heads_T<true, TT, true>(acc, pr, w, stage.bias[1], &stage.rope[0][0], false, pos0, len, seq, ntile, tile0, p.kf, p.qkv_small, 1);
         if (last) {   // the learned bias key, after this wave's own K stores
             __builtin_amdgcn_sched_barrier(0);
             write_bias_slots(p, seq, w, true, false, TT);
         }
     }
     if (do_v) {
-        zero_acc<3 * TT>(acc);
-        wave_gemm<TT, 3, 24, false>(panel, kRowB, 0, 0, p.wv + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
-        epilogue_v_flash<TT>(acc, w, p.bv, seq, ntile, tile0, p.vf);
+        wave_gemm<TT, 3, 24, false, 4, true>(panel, kRowB, 0, 0, p.wv + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
+        epilogue_v_flash<TT>(acc, w, stage.bias[2], seq, ntile, tile0, p.vf);
         if (last) {   // the learned bias value, after this wave's own V^T stores
             __builtin_amdgcn_sched_barrier(0);
             write_bias_slots(p, seq, w, false, true, TT);
@@ -468,15 +592,19 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv_attn4(const QkvParams p) {
     // all 48 packed q registers live across that GEMM hipcc spilled ~90 registers per lane -- 180 MB of scratch
     // traffic per launch, more than the q/k/v stores this kernel exists to avoid.
     __shared__ uint32_t qstash[HALF ? 1 : 4][24][64];
+    __shared__ __attribute__((aligned(16))) Attn4Stage stage;   // (64-row form: 80 976 of the 81 920 bytes two workgroups per CU allow)
+    Attn4Stager stager;
     PanelRows* pr = reinterpret_cast<PanelRows*>(smem);
     unsigned char* panel = smem + sizeof(PanelRows);
     ATTN4_STAMP_DECL;
     ATTN4_STAMP(0);
+    stager.load(p, threadIdx.x);
     {
         const long row0 = (long)blockIdx.x * kRows, rend = row0 + kRows;
         setup_rows_linear(pr, row0, rend < p.nrows ? rend : p.nrows, p.mm);   // (HALF: rows 32 .. 63 of the panel are padding rows)
     }
     __syncthreads();
+    stager.store(&stage, threadIdx.x);   // visible after the barrier behind the LayerNorm prologue
     const int w = __builtin_amdgcn_readfirstlane(wave_id());
     constexpr int t0 = 0;
     if (HALF) prologue_ln<false, 0, 2>(panel, pr, p.h, p.mm, p.shift_chunk, p.scale_chunk, 1e-6f, w, lane_id());
@@ -486,7 +614,7 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv_attn4(const QkvParams p) {
     const int lane = lane_id(), hh = lane >> 5, tk = lane & 31;
     constexpr int L = 4;
     // per-token constants: token id, key validity of the own token; the rotary factors (position = token % 4)
-    // are re-read from the (L2-resident) table after each GEMM rather than held across it
+    // are re-read from the staged rows after each GEMM rather than held across it
     int tok[TT];
     float mval[TT];
 #pragma unroll
@@ -498,7 +626,7 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv_attn4(const QkvParams p) {
 #pragma unroll
         for (int tt = 0; tt < TT; ++tt) {
             const int tc = tok[tt] < 0 ? 0 : tok[tt];
-            const f32x4* rc = reinterpret_cast<const f32x4*>(p.rope + (long)(tc & (L - 1)) * kRopeRow + 16 * hh);
+            const f32x4* rc = reinterpret_cast<const f32x4*>(&stage.rope[tc & (L - 1)][16 * hh]);
 #pragma unroll
             for (int i = 0; i < 4; ++i) rq[tt][i] = rc[i];
         }
@@ -507,10 +635,9 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv_attn4(const QkvParams p) {
     f32x4 bb[4][3];
     f32x4 rq[TT][4];
     // ---- Q (heads 4w..4w+3): RoPE, keep as bf16 pairs (48 registers)
-    zero_acc<3 * TT>(acc);
-    wave_gemm<TT, 3, 24, true>(panel, kRowB, t0, 0, p.wq + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
+    wave_gemm<TT, 3, 24, true, 4, true>(panel, kRowB, t0, 0, p.wq + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
     ATTN4_STAMP(2);
-    load_head_bias(p.bq, w, hh, bb);
+    load_head_bias(stage.bias[0], w, hh, bb);
     load_rope(rq);
     uint32_t qp[TT][4][6];
 #pragma unroll
@@ -522,8 +649,9 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv_attn4(const QkvParams p) {
 #pragma unroll
             for (int q = 0; q < 6; ++q) {
                 const float c = rq[tt][q >> 2][q & 3], sn = rq[tt][2 + (q >> 2)][q & 3];
-                const float x1 = e[2 * q], x2 = e[2 * q + 1];
-                qp[tt][hd][q] = pack_bf16(x1 * c - x2 * sn, x2 * c + x1 * sn);
+                float r0, r1;
+                rotate_pair<HALF>(e[2 * q], e[2 * q + 1], c, sn, r0, r1);
+                qp[tt][hd][q] = pack_bf16(r0, r1);
             }
         }
     if constexpr (!HALF) {
@@ -535,10 +663,9 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv_attn4(const QkvParams p) {
     ATTN4_STAMP(3);
     __builtin_amdgcn_sched_barrier(0);
     // ---- K: RoPE in place, then the scores of the 4 keys of the quad + the bias key; softmax -> P (40 registers)
-    zero_acc<3 * TT>(acc);
-    wave_gemm<TT, 3, 24, true, HALF ? 4 : kAttn4KPF>(panel, kRowB, t0, 0, p.wk + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);   // (q is live)
+    wave_gemm<TT, 3, 24, true, HALF ? 4 : kAttn4KPF, true>(panel, kRowB, t0, 0, p.wk + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);   // (q is live)
     ATTN4_STAMP(4);
-    load_head_bias(p.bk, w, hh, bb);
+    load_head_bias(stage.bias[1], w, hh, bb);
     load_rope(rq);
     // pass 1: bias + RoPE IN PLACE in the accumulators (frees the bias / rotary registers before the scores)
 #pragma unroll
@@ -554,9 +681,10 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv_attn4(const QkvParams p) {
                 for (int b2 = 0; b2 < 2; ++b2) {   // values 4c + 2 b2, 4c + 2 b2 + 1 = rotary pair q = 2c + b2
                     const int q = 2 * c + b2;
                     const float cs = rq[tt][q >> 2][q & 3], sn = rq[tt][2 + (q >> 2)][q & 3];
-                    const float x1 = k[2 * q], x2 = k[2 * q + 1];
-                    acc[ft * TT + tt][4 * a + 2 * b2] = x1 * cs - x2 * sn;
-                    acc[ft * TT + tt][4 * a + 2 * b2 + 1] = x2 * cs + x1 * sn;
+                    float r0, r1;
+                    rotate_pair<HALF>(k[2 * q], k[2 * q + 1], cs, sn, r0, r1);
+                    acc[ft * TT + tt][4 * a + 2 * b2] = r0;
+                    acc[ft * TT + tt][4 * a + 2 * b2 + 1] = r1;
                 }
             }
         }
@@ -565,18 +693,16 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv_attn4(const QkvParams p) {
     // pass 2: scores against the 4 keys of the quad + the bias key, softmax -> P (40 registers)
     float P[TT][4][5];
     {
-        // learned bias key (mha.py:265-268), rotated at position L like every key (:356-357), rounded to bf16
-        const float* rcL = p.rope + (long)L * kRopeRow + 16 * hh;
+        // learned bias key (mha.py:265-268), rotated at position L like every key (:356-357), rounded to bf16: a function of the weights
+        // alone, computed when they are loaded (launch_l4_bias_table) and staged with the biases
 #pragma unroll
         for (int hd = 0; hd < 4; ++hd) {
-            const float* bk = p.bias_k + (4 * w + hd) * kDH;
+            const uint32_t* kt = &stage.tab[0][((2 * w + hh) * 4 + hd) * 6];
             float kb[12];
 #pragma unroll
             for (int q = 0; q < 6; ++q) {
-                const int i = 6 * hh + q;
-                const float x1 = bk[i], x2 = bk[i + 12], c = rcL[q], sn = rcL[8 + q];
-                kb[2 * q] = bf16_lo(pack_bf16(x1 * c - x2 * sn, 0.f));
-                kb[2 * q + 1] = bf16_lo(pack_bf16(x2 * c + x1 * sn, 0.f));
+                kb[2 * q] = bf16_lo(kt[q]);
+                kb[2 * q + 1] = bf16_hi(kt[q]);
             }
 #pragma unroll
             for (int tt = 0; tt < TT; ++tt) {
@@ -593,13 +719,22 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv_attn4(const QkvParams p) {
                     qf[2 * q] = bf16_lo(u);
                     qf[2 * q + 1] = bf16_hi(u);
                 }
-                float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+                // four independent chains (one per key of the quad) + the bias key's: a product, then eleven fused multiply-adds each
+                dpp_fence(k);
+                float s[5];
+                s[0] = mul_dpp<0>(k[0], qf[0]);
+                s[1] = mul_dpp<1>(k[0], qf[0]);
+                s[2] = mul_dpp<2>(k[0], qf[0]);
+                s[3] = mul_dpp<3>(k[0], qf[0]);
+                s[4] = 0.f;
 #pragma unroll
                 for (int i = 0; i < 12; ++i) {
-                    s[0] += qf[i] * quad_bcast<0>(k[i]);
-                    s[1] += qf[i] * quad_bcast<1>(k[i]);
-                    s[2] += qf[i] * quad_bcast<2>(k[i]);
-                    s[3] += qf[i] * quad_bcast<3>(k[i]);
+                    if (i > 0) {
+                        s[0] = fmac_dpp<0>(s[0], k[i], qf[i]);
+                        s[1] = fmac_dpp<1>(s[1], k[i], qf[i]);
+                        s[2] = fmac_dpp<2>(s[2], k[i], qf[i]);
+                        s[3] = fmac_dpp<3>(s[3], k[i], qf[i]);
+                    }
                     s[4] += qf[i] * kb[i];
                 }
 #pragma unroll
@@ -640,10 +775,9 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv_attn4(const QkvParams p) {
     }
     __builtin_amdgcn_sched_barrier(0);
     // ---- V (transposed as well: a lane holds features 12 hh .. 12 hh + 11 of each head of its token)
-    zero_acc<3 * TT>(acc);
-    wave_gemm<TT, 3, 24, true, HALF ? 4 : kAttn4VPF>(panel, kRowB, t0, 0, p.wv + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
+    wave_gemm<TT, 3, 24, true, HALF ? 4 : kAttn4VPF, true>(panel, kRowB, t0, 0, p.wv + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
     ATTN4_STAMP(7);
-    load_head_bias(p.bv, w, hh, bb);
+    load_head_bias(stage.bias[2], w, hh, bb);
     {
         float* Pf = &P[0][0][0];
 #pragma unroll
@@ -659,17 +793,30 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv_attn4(const QkvParams p) {
 #pragma unroll
     for (int hd = 0; hd < 4; ++hd) {
         const int head = 4 * w + hd;
+        const uint32_t* vt = &stage.tab[1][((2 * w + hh) * 4 + hd) * 6];
         float bvv[12];
 #pragma unroll
-        for (int i = 0; i < 12; ++i) bvv[i] = bf16_lo(pack_bf16(p.bias_v[head * kDH + 12 * hh + i], 0.f));
+        for (int q = 0; q < 6; ++q) {
+            bvv[2 * q] = bf16_lo(vt[q]);
+            bvv[2 * q + 1] = bf16_hi(vt[q]);
+        }
 #pragma unroll
         for (int tt = 0; tt < TT; ++tt) {
             float v[12], o[12];
             head_values<TT>(acc, tt, hd, bb[hd], v);
+            // o = P0 v(key 0) + P1 v(key 1) + P2 v(key 2) + P3 v(key 3) + P4 bias_v, in the order hipcc contracts that sum: the product of
+            // key 1 first, then keys 0, 2, 3 and the bias value as fused multiply-adds; twelve independent chains
+            dpp_fence(v);
 #pragma unroll
-            for (int i = 0; i < 12; ++i)
-                o[i] = P[tt][hd][0] * quad_bcast<0>(v[i]) + P[tt][hd][1] * quad_bcast<1>(v[i]) +
-                       P[tt][hd][2] * quad_bcast<2>(v[i]) + P[tt][hd][3] * quad_bcast<3>(v[i]) + P[tt][hd][4] * bvv[i];
+            for (int i = 0; i < 12; ++i) o[i] = mul_dpp<1>(v[i], P[tt][hd][1]);
+#pragma unroll
+            for (int i = 0; i < 12; ++i) o[i] = fmac_dpp<0>(o[i], v[i], P[tt][hd][0]);
+#pragma unroll
+            for (int i = 0; i < 12; ++i) o[i] = fmac_dpp<2>(o[i], v[i], P[tt][hd][2]);
+#pragma unroll
+            for (int i = 0; i < 12; ++i) o[i] = fmac_dpp<3>(o[i], v[i], P[tt][hd][3]);
+#pragma unroll
+            for (int i = 0; i < 12; ++i) o[i] = __builtin_fmaf(P[tt][hd][4], bvv[i], o[i]);
             if (PROJ) {
                 const bool ok = tok[tt] >= 0;   // padding rows enter the GEMM as zeros
 #pragma unroll
@@ -691,8 +838,7 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv_attn4(const QkvParams p) {
     ATTN4_STAMP(8);
     // (the epilogue's first batch of residual rows requested ahead of this GEMM, as k_flash_proj does: measured, no gain here -- 130.6
     // against 128-130 us per launch, 125.9k against 126.4k frames/s; profiles/r06_experiments.txt #6)
-    zero_acc<3 * TT>(acc);
-    wave_gemm<TT, 3, 24, false>(panel, kRowB, t0, 0, p.wo + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
+    wave_gemm<TT, 3, 24, false, 4, true>(panel, kRowB, t0, 0, p.wo + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
     ATTN4_STAMP(9);
     __syncthreads();   // every wave is done reading the panel: reuse it as four 12 KiB staging slabs
     if constexpr (HALF) {

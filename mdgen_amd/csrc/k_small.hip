@@ -73,6 +73,23 @@ __global__ void k_rope_table(float* __restrict__ rope, const float* __restrict__
     rope[(long)pos * kRopeRow + h * 16 + 8 + j] = sn;
 }
 
+// see kernels.h launch_l4_bias_table.  The rotation is written with the multiply / fused multiply-add split k_ln_qkv_attn4 used to
+// evaluate it with in every launch (mha.py:265-268, 356-357), so the table holds the values that kernel computed.
+__global__ void k_l4_bias_table(const float* __restrict__ bias_k, const float* __restrict__ bias_v, const float* __restrict__ rope,
+                                uint32_t* __restrict__ tab) {
+    const int i = threadIdx.x;
+    if (i >= kL4Tab) return;
+    const int q = i % 6, g = i / 6, hd = g & 3, hh = (g >> 2) & 1, w = g >> 3;
+    const float* bk = bias_k + (4 * w + hd) * kDH;
+    const float* rcL = rope + 4 * kRopeRow + 16 * hh;
+    const int j = 6 * hh + q;
+    const float x1 = bk[j], x2 = bk[j + 12], c = rcL[q], sn = rcL[8 + q];
+    const float a = x2 * sn, b = x1 * sn;
+    tab[i] = pack_bf16(__builtin_fmaf(x1, c, -a), __builtin_fmaf(x2, c, b));
+    const float* bv = bias_v + (4 * w + hd) * kDH + 12 * hh;
+    tab[kL4Tab + i] = pack_bf16(bv[2 * q], bv[2 * q + 1]);
+}
+
 __global__ void k_gather_f32(const float* __restrict__ src, const int* __restrict__ idx, float scale,
                              float* __restrict__ dst, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -654,6 +671,9 @@ void launch_adaln(const float* st, int nrows, const float* w, const float* b, in
 }
 void launch_rope_table(float* rope, const float* inv_freq, int npos, hipStream_t s) {
     hipLaunchKernelGGL(k_rope_table, dim3((npos * 16 + 255) / 256), dim3(256), 0, s, rope, inv_freq, npos);
+}
+void launch_l4_bias_table(const float* bias_k, const float* bias_v, const float* rope, uint32_t* tab, hipStream_t s) {
+    hipLaunchKernelGGL(k_l4_bias_table, dim3(1), dim3(256), 0, s, bias_k, bias_v, rope, tab);
 }
 void launch_gather_f32(const float* src, const int* idx, float scale, float* dst, int n, hipStream_t s) {
     hipLaunchKernelGGL(k_gather_f32, dim3((n + 255) / 256), dim3(256), 0, s, src, idx, scale, dst, n);

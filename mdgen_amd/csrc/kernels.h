@@ -20,6 +20,7 @@ struct QkvParams {
     int vmask_stride;
     // k_ln_qkv_attn4 only (residue axis, L == 4: attention inside the QKV kernel)
     const float *bias_k, *bias_v;   // learned bias key / value [384]
+    const uint32_t* l4tab;          // ... as the L == 4 kernel consumes them (launch_l4_bias_table), [2][kL4Tab] bf16 pairs
     MaskMap mk;                     // key-padding mask
     __bf16* obuf;                   // attention output [token][384] bf16 (PROJ == false)
     // k_ln_qkv_attn4<true>: the out-projection + gated residual of the same sub-layer, in the same kernel
@@ -469,6 +470,11 @@ void launch_temb(const float* t_rows, int nrows, float tmul, const float* w0, co
                  const float* b2, float* silu_out, hipStream_t s);
 void launch_adaln(const float* st, int nrows, const float* w, const float* b, int nout, float* mod, hipStream_t s);
 void launch_rope_table(float* rope, const float* inv_freq, int npos, hipStream_t s);
+// The learned bias key / value of the L == 4 residue-axis kernel (k_ln_qkv_attn4), functions of the weights alone: the key rotated at
+// position 4 and rounded to bf16, the value rounded to bf16, as bf16 pairs in the order a (wave w, lane half hh) reads them for its heads
+// 4w .. 4w+3: tab[((2w + hh) 4 + hd) 6 + q] = (value 2q, value 2q + 1) of the lane half's twelve; tab[kL4Tab + ...]: the bias value alike.
+constexpr int kL4Tab = 192;
+void launch_l4_bias_table(const float* bias_k, const float* bias_v, const float* rope, uint32_t* tab, hipStream_t s);
 void launch_gather_f32(const float* src, const int* idx, float scale, float* dst, int n, hipStream_t s);
 // part: 0 the weight rounded to bf16, 1 the bf16 of its rounding error (w - float(bf16(w))): the lo half of a bf16 pair
 void launch_pack_rows(const float* w, int ld, const int* rowmap, int nft, int ksteps, float scale, bf16x8* dst,

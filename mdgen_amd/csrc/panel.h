@@ -44,13 +44,18 @@ __device__ __forceinline__ bf16x8 panel_frag(const unsigned char* panel, const i
 // k-step ks+PF are requested (L2 -> VGPR) and the activation fragments of k-step ks+1 are read from LDS in a
 // scheduling region that precedes the MFMAs of k-step ks.  The loads stay ordinary loads, so hipcc itself
 // inserts exact counted waits (vmcnt(PF*FT)) -- no hand-counted asm waits, no stale-register hazards.
-template <int TT, int FT, int KSTEPS, bool TRANS, int PF = 4>
+// ZC: the accumulators start at zero -- the MFMAs of the first k-step take the INLINE CONSTANT 0 as C, and the caller zeroes
+// nothing (16 v_mov per accumulator tuple otherwise).  With that operand form hipcc does not mark the destination early-clobber and
+// may allocate it on top of a source that dies at the MFMA, which corrupts results (k_flash.hip scores()):
+// the first k-step's fragments therefore get a no-op use that depends on the MFMA's result.  (build.py check_isa still rejects any overlap.)
+template <int TT, int FT, int KSTEPS, bool TRANS, int PF = 4, bool ZC = false>
 __device__ __forceinline__ void wave_gemm(const unsigned char* panel, const int rowb, const int tile0, const int ks0,
                                           const bf16x8* __restrict__ wfrag, const int wtile_stride,
                                           f32x16* acc) {
     static_assert(PF < KSTEPS, "prefetch depth");
     bf16x8 wring[PF + 1][FT];
     bf16x8 aring[2][TT];
+    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int p = 0; p < PF; ++p)
 #pragma unroll
@@ -76,11 +81,18 @@ __device__ __forceinline__ void wave_gemm(const unsigned char* panel, const int 
             for (int f = 0; f < FT; ++f) {
                 if (TRANS)
                     acc[f * TT + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wring[ks % (PF + 1)][f], aring[ks & 1][t],
-                                                                             acc[f * TT + t], 0, 0, 0);
+                                                                             ZC && ks == 0 ? zero : acc[f * TT + t], 0, 0, 0);
                 else
                     acc[t * FT + f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aring[ks & 1][t], wring[ks % (PF + 1)][f],
-                                                                             acc[t * FT + f], 0, 0, 0);
+                                                                             ZC && ks == 0 ? zero : acc[t * FT + f], 0, 0, 0);
             }
+        if (ZC && ks == 0) {   // sources outlive the inline-constant-C MFMAs: a no-op use of both, tied to the MFMA's result
+#pragma unroll
+            for (int t = 0; t < TT; ++t)
+#pragma unroll
+                for (int f = 0; f < FT; ++f)
+                    asm volatile("" : "+v"(acc[TRANS ? f * TT + t : t * FT + f]) : "v"(wring[0][f]), "v"(aring[0][t]));
+        }
         __builtin_amdgcn_sched_barrier(0);
     }
 }
