@@ -961,6 +961,67 @@ static int for_each_view(const Run& r, int nv, int ns, F&& fn) {
 // token rows of the largest of them: what prepare() sizes its decisions by
 static long largest_view_rows(const Run& r, int nv) { return (long)((r.B + nv - 1) / nv) * r.T * r.L; }
 
+// ---- the model's geometry: every axis, mask and modulation map of the network, written here and nowhere else ----
+// Tokens are (b, t, l) in the trunk and (group, l) in the IPA stack (G = S * B groups: prepared step, batch element).
+// residue axis: one sequence of L tokens per frame (b, t)
+static AxisMap axis_res(long B, long T, long L) { return AxisMap{(int)(B * T), (int)L, (int)(B * T), 0, (int)L, 1}; }
+// temporal axis: one sequence of T tokens, L apart, per residue (b, l)
+static AxisMap axis_time(long B, long T, long L) { return AxisMap{(int)(B * L), (int)T, (int)L, (int)(T * L), 1, (int)L}; }
+// the IPA stack's residue axis
+static AxisMap axis_ipa(long G, long L) { return AxisMap{(int)G, (int)L, (int)G, 0, (int)L, 1}; }
+static AxisMap axis_res(const Run& r) { return axis_res(r.B, r.T, r.L); }
+static AxisMap axis_time(const Run& r) { return axis_time(r.B, r.T, r.L); }
+static AxisMap axis_ipa(const Run& r) { return axis_ipa((long)r.S * r.B, r.L); }
+// key-padding masks: the trunk's per token; the IPA stack's mask[b][0][l], compacted by prepare() / the training forward
+static MaskMap mask_trunk(const Run& r) { return MaskMap{r.mask, 0}; }
+static MaskMap mask_ipa(const Run& r) { return MaskMap{(const float*)(r.ws + r.lay.mask_bl), (long)r.B * r.L}; }
+// adaLN rows: the IPA layers' for all prepared steps at once (groups of L tokens), the trunk's and the final layer's of one step
+static ModMap mod_ipa(const Run& r, int i) {
+    return ModMap{r.mod() + r.c->ipa_off(i), r.L, r.B, r.mod_step_stride, r.mod_group_stride};
+}
+static ModMap mod_step(const Run& r, int off, int step) {
+    return ModMap{r.mod() + (long)step * r.mod_step_stride + off, r.T * r.L, r.B, 0, r.mod_group_stride};
+}
+static ModMap mod_trunk(const Run& r, int i, int step) { return mod_step(r, r.c->trunk_off(i), step); }
+static ModMap mod_final(const Run& r, int step) { return mod_step(r, r.c->final_off(), step); }
+// an affine LayerNorm as a modulation: the one row gamma - 1 | beta for every token
+static ModMap mod_affine(const float* gamma_beta) { return ModMap{gamma_beta, 1, 1, 0, 0}; }
+
+// One sub-layer's site: the rows it updates, its three adaLN chunks (shift, scale, gate = chunk0, +1, +2), the axis and mask of
+// an attention sub-layer, and in the training step the sub-layer's rows of d mod (dmod, addressed like mm.mod)
+struct Rows {
+    float* h;
+    long nrows;
+    ModMap mm;
+    int chunk0;
+    float* dmod;
+    AxisMap ax;      // (attention only)
+    MaskMap mk;
+    int shift() const { return chunk0; }
+    int scale() const { return chunk0 + 1; }
+    int gate() const { return chunk0 + 2; }
+    long tpg() const { return mm.tokens_per_group; }   // tokens per modulation group
+};
+// The sites of IPA layer i on the stream's rows h, and of trunk layer i at prepared step `step`; dmod: the call's d mod table (the
+// training step), or null.  The sampler, the training forward and the training backward all take a layer's sites from here.
+struct IpaSites { Rows attn, mlp; };
+struct TrunkSites { Rows l, t, mlp; };
+static IpaSites ipa_sites(const Run& r, int i, float* h, float* dmod) {
+    const ModMap mm = mod_ipa(r, i);
+    float* dm = dmod ? dmod + r.c->ipa_off(i) : nullptr;
+    return IpaSites{Rows{h, r.Mp, mm, 0, dm, axis_ipa(r), mask_ipa(r)}, Rows{h, r.Mp, mm, 3, dm}};
+}
+static TrunkSites trunk_sites(const Run& r, int i, int step, float* dmod) {
+    const ModMap mm = mod_trunk(r, i, step);
+    float* dm = dmod ? dmod + r.c->trunk_off(i) : nullptr;
+    return TrunkSites{Rows{r.h(), r.N, mm, 0, dm, axis_res(r), mask_trunk(r)}, Rows{r.h(), r.N, mm, 3, dm, axis_time(r), mask_trunk(r)},
+                      Rows{r.h(), r.N, mm, 6, dm}};
+}
+// ... of the final layer (shift, scale = chunks 0, 1; it has no gate)
+static Rows final_site(const Run& r, int step, float* dmod) {
+    return Rows{r.h(), r.N, mod_final(r, step), 0, dmod ? dmod + r.c->final_off() : nullptr};
+}
+
 // ---- fp32-operand path (option "precision" = 32; kernels in k_fp32.hip) ------------------------------------------
 struct F32Bufs {
     float *y, *qkv, *att, *hid, *feat;
@@ -1007,12 +1068,13 @@ static LinearParams lin_op_gated(LinearParams p, const ModMap& mm, int gate) {
 }
 
 // one attention sub-layer, fp32: LN + modulate -> q, k, v -> RoPE -> softmax attention -> out-projection + gated residual
-static int attn_sublayer_fp32(const Run& r, const MhaW& m, float* h, long nrows, const AxisMap& ax, const ModMap& mm, int shift,
-                              int scale, int gate, const MaskMap& mk, long pos_div, int pos_mod) {
+static int attn_sublayer_fp32(const Run& r, const MhaW& m, const Rows& rw) {
     const mdgen_ctx* c = r.c;
     const F32Bufs b = f32_bufs(r);
     const auto& p = m.slot;
-    launch32_ln_mod(h, nrows, mm, shift, scale, 0, 1e-6f, b.y, r.s, nullptr, false);
+    float* h = rw.h;
+    const long nrows = rw.nrows;
+    launch32_ln_mod(h, nrows, rw.mm, rw.shift(), rw.scale(), 0, 1e-6f, b.y, r.s, nullptr, false);
     LinearParams q = lin_op(b.y, kC, c->f32(p.q.w), kC, c->f32(p.q.b), nrows, kC, kC, b.qkv, 3 * kC);
     q.mode = kLinScaled;
     q.scalar = 1.0f / std::sqrt((float)kDH);   // mha.py:263 q *= head_dim ** -0.5
@@ -1023,21 +1085,64 @@ static int attn_sublayer_fp32(const Run& r, const MhaW& m, float* h, long nrows,
     launch32_linear(q, r.s);
     launch32_linear(k, r.s);
     launch32_linear(v, r.s);
-    launch32_rope(b.qkv, nrows, 3 * kC, pos_div, pos_mod, c->inv_freq, r.s);
-    launch32_attn(b.qkv, 3 * kC, ax, mk, c->f32(p.bias_k), c->f32(p.bias_v), c->inv_freq, b.att, r.s, nullptr);
-    launch32_linear(lin_op_gated(lin_op(b.att, kC, c->f32(p.o.w), kC, c->f32(p.o.b), nrows, kC, kC, h, kC), mm, gate), r.s);
+    launch32_rope(b.qkv, nrows, 3 * kC, rw.ax.pos_stride, rw.ax.len, c->inv_freq, r.s);   // position = (token / pos_stride) % len
+    launch32_attn(b.qkv, 3 * kC, rw.ax, rw.mk, c->f32(p.bias_k), c->f32(p.bias_v), c->inv_freq, b.att, r.s, nullptr);
+    launch32_linear(lin_op_gated(lin_op(b.att, kC, c->f32(p.o.w), kC, c->f32(p.o.b), nrows, kC, kC, h, kC), rw.mm, rw.gate()), r.s);
     LAUNCHCHK();
     return 0;
 }
 
-static int mlp_sublayer_fp32(const Run& r, const FfnW& f, float* h, long nrows, const ModMap& mm, int shift, int scale, int gate) {
+static int mlp_sublayer_fp32(const Run& r, const FfnW& f, const Rows& rw) {
     const mdgen_ctx* c = r.c;
     const F32Bufs b = f32_bufs(r);
-    launch32_ln_mod(h, nrows, mm, shift, scale, 0, 1e-6f, b.y, r.s, nullptr, false);
+    float* h = rw.h;
+    const long nrows = rw.nrows;
+    launch32_ln_mod(h, nrows, rw.mm, rw.shift(), rw.scale(), 0, 1e-6f, b.y, r.s, nullptr, false);
     LinearParams fc1 = lin_op(b.y, kC, c->f32(f.slot.fc1.w), kC, c->f32(f.slot.fc1.b), nrows, kF, kC, b.hid, kF);
     fc1.mode = kLinGelu;
     launch32_linear(fc1, r.s);
-    launch32_linear(lin_op_gated(lin_op(b.hid, kF, c->f32(f.slot.fc2.w), kF, c->f32(f.slot.fc2.b), nrows, kC, kF, h, kC), mm, gate), r.s);
+    launch32_linear(lin_op_gated(lin_op(b.hid, kF, c->f32(f.slot.fc2.w), kF, c->f32(f.slot.fc2.b), nrows, kC, kF, h, kC), rw.mm, rw.gate()), r.s);
+    LAUNCHCHK();
+    return 0;
+}
+
+// a linear layer in the form a plan gives it (kernels.h LinearForm; F32 = launch32_linear)
+static void step_linear(LinearParams p, LinearForm form, hipStream_t s) {
+    p.fast_gelu = form != LinearForm::F32;    // (see linear.h)
+    p.a_bf16 = form == LinearForm::StreamBf16Rows;
+    launch_linear(p, form, s);
+}
+
+// The IPA block of one layer on fp32 rows: hx += linear_out(point_attention(q | kv | q_points | kv_points of LN_affine(hx)))
+// (latent_model.py:373).  The precision-32 sampler runs it on workspace scratch with every layer in the F32 form; the training
+// forward on its tape (proj, feat, stats: read again by the backward) with the forms of its plan.
+struct IpaBlockOp {
+    float *y, *proj, *feat;          // LN output [Mp][384], projections [Mp][kIpaProj], attention features [Mp][kIpaFeat]
+    float* stats;                    // nullable: the attention's softmax statistics [Mp][4]
+    float* part;                     // nullable: split scratch of the attention's key loop (few groups)
+    size_t part_floats;
+    LinearForm proj_form[4], out_form;
+};
+static int ipa_block_fp32(const Run& r, const IpaW& w, float* hx, const float* rot, const float* trans, const IpaBlockOp& o) {
+    const mdgen_ctx* c = r.c;
+    const auto& p = w.slot;
+    launch32_ln_mod(hx, r.Mp, mod_affine(w.gamma_beta), 1, 0, 1, 1e-5f, o.y, r.s, nullptr, false);
+    const Lin* lins[4] = {&p.q, &p.kv, &p.q_points, &p.kv_points};
+    for (int j = 0; j < 4; ++j) {
+        LinearParams q = lin_op(o.y, kC, c->f32(lins[j]->w), kC, c->f32(lins[j]->b), r.Mp, kIpaProjCols[j].m, kC, o.proj, kIpaProj);
+        q.col0 = kIpaProjCols[j].col0;
+        step_linear(q, o.proj_form[j], r.s);
+    }
+    IpaAttnParams ap{};
+    ap.proj = o.proj; ap.rot = rot; ap.trans = trans;
+    ap.mask_bl = mask_ipa(r).mask;
+    ap.head_w = w.head_w; ap.feat = nullptr; ap.feat32 = o.feat; ap.stats = o.stats;
+    ap.ngroups = r.S * r.B; ap.B = r.B; ap.L = r.L;
+    ap.part = o.part; ap.part_floats = o.part_floats;
+    launch_ipa_attn(ap, r.s);
+    LinearParams lo = lin_op(o.feat, kIpaFeat, c->f32(p.out.w), kIpaFeat, c->f32(p.out.b), r.Mp, kC, kIpaFeat, hx, kC);
+    lo.mode = kLinGated;   // (gated = 0: the ungated residual hx += linear_out(feat))
+    step_linear(lo, o.out_form, r.s);
     LAUNCHCHK();
     return 0;
 }
@@ -1247,13 +1352,6 @@ static LayerPlan layer_plan(const Run& r, const AxisMap& axL, const AxisMap& axT
     return p;
 }
 
-// The rows a sub-layer updates and its three adaLN chunks (shift, scale, gate = chunk0, +1, +2)
-struct Rows {
-    float* h;
-    long nrows;
-    ModMap mm;
-    int chunk0;
-};
 // An out-projection + gated residual that another sub-layer's kernel runs in its prologue (attention output rows: r.obufp)
 struct OutProj {
     const bf16x8* w;
@@ -1262,10 +1360,11 @@ struct OutProj {
 };
 
 // pre: the previous sub-layer's out-projection (pl.qkv == QkvForm::PreProj only)
-static int attn_sublayer(const Run& r, const AttnPlan& pl, const MhaW& m, const Rows& rw, const AxisMap& ax, const MaskMap& mk,
-                         const OutProj& pre) {
+static int attn_sublayer(const Run& r, const AttnPlan& pl, const MhaW& m, const Rows& rw, const OutProj& pre) {
     if (int e = check_launch_rows(rw.nrows)) return e;
-    const int gate = rw.chunk0 + 2;
+    const AxisMap& ax = rw.ax;
+    const MaskMap& mk = rw.mk;
+    const int gate = rw.gate();
     QkvParams q{};
     q.h = rw.h;
     q.nrows = rw.nrows;
@@ -1465,46 +1564,22 @@ static int ipa_stack(const Run& r, float* hbuf, const float* rel7, const float* 
     mdgen_ctx* c = r.c;
     const int G = r.S * r.B;
     if (int e = launch(r, nullptr, [&] { launch_ipa_init(c->aa_emb, r.aatype, rel7, w7, b7, hbuf, G, r.B, r.L, r.s); })) return e;
-    AxisMap ax{G, r.L, G, 0, r.L, 1};
-    MaskMap mk{(const float*)(r.ws + r.lay.mask_bl), (long)r.B * r.L};
     for (int i = 0; i < c->nl; ++i) {
         const IpaW& w = c->ipa[i];
-        ModMap mm{r.mod() + c->ipa_off(i), r.L, r.B, r.mod_step_stride, r.mod_group_stride};
+        const IpaSites st = ipa_sites(r, i, hbuf, nullptr);
         if (c->opt_precision == 32) {   // ---- fp32 operands: ipa_norm -> four projections -> point attention -> linear_out
             const F32Bufs fb = f32_bufs(r);
-            const auto& p = w.slot;
-            float* proj = (float*)(r.ws + r.lay.ipa_proj);
-            launch32_ln_mod(hbuf, r.Mp, ModMap{w.gamma_beta, 1, 1, 0, 0}, 1, 0, 1, 1e-5f, fb.y, r.s, nullptr, false);
-            const Lin* lins[4] = {&p.q, &p.kv, &p.q_points, &p.kv_points};
-            for (int j = 0; j < 4; ++j) {
-                LinearParams q = lin_op(fb.y, kC, c->f32(lins[j]->w), kC, c->f32(lins[j]->b), r.Mp, kIpaProjCols[j].m, kC, proj, kIpaProj);
-                q.col0 = kIpaProjCols[j].col0;
-                launch32_linear(q, r.s);
-            }
-            IpaAttnParams ap{};
-            ap.proj = proj;
-            ap.rot = rot;
-            ap.trans = trans;
-            ap.mask_bl = (const float*)(r.ws + r.lay.mask_bl);
-            ap.head_w = w.head_w;
-            ap.feat = nullptr;
-            ap.feat32 = fb.feat;
-            ap.ngroups = G;
-            ap.B = r.B;
-            ap.L = r.L;
-            launch_ipa_attn(ap, r.s);
-            LinearParams lo = lin_op(fb.feat, kIpaFeat, c->f32(p.out.w), kIpaFeat, c->f32(p.out.b), r.Mp, kC, kIpaFeat, hbuf, kC);
-            lo.mode = kLinGated;   // (gated = 0: the ungated residual hbuf += linear_out(feat))
-            launch32_linear(lo, r.s);
-            LAUNCHCHK();
-            if (int e = attn_sublayer_fp32(r, w.mha_l, hbuf, r.Mp, ax, mm, 0, 1, 2, mk, 1, r.L)) return e;
-            if (int e = mlp_sublayer_fp32(r, w.ffn, hbuf, r.Mp, mm, 3, 4, 5)) return e;
+            const LinearForm f32 = LinearForm::F32;
+            const IpaBlockOp o{fb.y, (float*)(r.ws + r.lay.ipa_proj), fb.feat, nullptr, nullptr, 0, {f32, f32, f32, f32}, f32};
+            if (int e = ipa_block_fp32(r, w, hbuf, rot, trans, o)) return e;
+            if (int e = attn_sublayer_fp32(r, w.mha_l, st.attn)) return e;
+            if (int e = mlp_sublayer_fp32(r, w.ffn, st.mlp)) return e;
             continue;
         }
         LnLinearParams lp{};
         lp.h = hbuf;
         lp.nrows = r.Mp;
-        lp.mm = ModMap{w.gamma_beta, 1, 1, 0, 0};
+        lp.mm = mod_affine(w.gamma_beta);
         lp.w = w.wproj;
         lp.bias = w.bproj;
         lp.out = (float*)(r.ws + r.lay.ipa_proj);
@@ -1514,7 +1589,7 @@ static int ipa_stack(const Run& r, float* hbuf, const float* rel7, const float* 
         ap.proj = lp.out;
         ap.rot = rot;
         ap.trans = trans;
-        ap.mask_bl = (const float*)(r.ws + r.lay.mask_bl);
+        ap.mask_bl = mask_ipa(r).mask;
         ap.head_w = w.head_w;
         ap.feat = (__bf16*)(r.ws + r.lay.ipa_feat);
         ap.ngroups = G;
@@ -1524,16 +1599,16 @@ static int ipa_stack(const Run& r, float* hbuf, const float* rel7, const float* 
         ProjParams pp{};
         pp.h = hbuf;
         pp.nrows = r.Mp;
-        pp.mm = mm;
+        pp.mm = st.attn.mm;
         pp.gated = 0;
         pp.w = w.wout;
         pp.bias = w.bout;
         pp.a_bf16 = ap.feat;
         if (int e = launch(r, "ipa.linear_out", [&] { launch_proj(pp, ProjMode::Linear, r.s); })) return e;
         const OutProj none{};
-        if (int e = attn_sublayer(r, attn_plan(c, Pos::Ipa, ax, r.Mp, false, ProjAt::Own), w.mha_l, Rows{hbuf, r.Mp, mm, 0}, ax, mk, none)) return e;
+        if (int e = attn_sublayer(r, attn_plan(c, Pos::Ipa, st.attn.ax, r.Mp, false, ProjAt::Own), w.mha_l, st.attn, none)) return e;
         const MlpPlan mp = mlp_plan(c, false, r.Mp, false, MlpRowsForm::Plain, r.concurrent, r.split_cap, false);
-        if (int e = mlp_sublayer(r, mp, w.ffn, Rows{hbuf, r.Mp, mm, 3}, none, nullptr)) return e;
+        if (int e = mlp_sublayer(r, mp, w.ffn, st.mlp, none, nullptr)) return e;
     }
     return 0;
 }
@@ -1611,6 +1686,18 @@ static int prepare(Run& r, const float* t_dev, const float* t_host, long view_ro
     return 0;
 }
 
+// the token embedding of x into r.h() (latent_model.py:233-246), ipa_out: the IPA table's rows [B*L][384] of the step
+static EmbedParams embed_op(const Run& r, const float* x, const float* ipa_out) {
+    const mdgen_ctx* c = r.c;
+    EmbedParams e{};
+    e.x = x; e.x_cond = r.x_cond; e.x_cond_mask = r.x_cond_mask;
+    e.wl = c->wl; e.bl = c->bl; e.wc = c->wc; e.bc = c->bc; e.mask_emb = c->mask_emb;
+    e.wl_pack = c->wl_pack; e.wc_pack = c->wc_pack;
+    e.pos_embed = c->d.abs_pos_emb ? c->pos_embed : nullptr;
+    e.ipa_out = ipa_out; e.h = r.h(); e.N = r.N; e.T = r.T; e.L = r.L; e.D = r.D;
+    return e;
+}
+
 // One network evaluation at prepared step `step`: x -> velocity (out) or Euler update of x in place.
 // euler: the call runs the prepared steps 0 .. S-1 in order on this view (euler_steps).  Where embed_tail_runs(r), step i's last MLP
 // launch then writes step i + 1's token embedding into h, and step i + 1 launches no k_embed.
@@ -1618,44 +1705,22 @@ static int denoise_step(const Run& r, int step, float* x, float* out, int euler,
     mdgen_ctx* c = r.c;
     const bool embed_tail = euler && embed_tail_runs(r);
     float* h = r.h();
-    EmbedParams e{};
-    e.x = x;
-    e.x_cond = r.x_cond;
-    e.x_cond_mask = r.x_cond_mask;
-    e.wl = c->wl;
-    e.wl_pack = c->wl_pack;
-    e.wc_pack = c->wc_pack;
-    e.bl = c->bl;
-    e.wc = c->wc;
-    e.bc = c->bc;
-    e.mask_emb = c->mask_emb;
-    e.pos_embed = c->d.abs_pos_emb ? c->pos_embed : nullptr;
-    e.ipa_out = r.ipa_out_p + (long)step * r.ipa_step_stride;
-    e.h = h;
-    e.N = r.N;
-    e.T = r.T;
-    e.L = r.L;
-    e.D = r.D;
+    const EmbedParams e = embed_op(r, x, r.ipa_out_p + (long)step * r.ipa_step_stride);
     if (!(embed_tail && step > 0))
         if (int er = launch(r, "embed", [&] { launch_embed(e, r.s); })) return er;
     const size_t hbytes = (size_t)r.N * kC * 4;
     if (trace_h) HIPCHK(hipMemcpyAsync(trace_h, h, hbytes, hipMemcpyDeviceToDevice, r.s));
-    const float* modstep = r.mod() + (long)step * r.mod_step_stride;
-    AxisMap axL{r.B * r.T, r.L, r.B * r.T, 0, r.L, 1};
-    AxisMap axT{r.B * r.L, r.T, r.L, r.T * r.L, 1, r.L};
-    MaskMap mk{r.mask, 0};
     if (c->opt_precision == 32) {   // ---- fp32 operands (k_fp32.hip): same dataflow, one kernel per reference op group
         for (int i = 0; i < c->nl; ++i) {
             const TrunkW& w = c->trunk[i];
-            ModMap mm{modstep + c->trunk_off(i), r.T * r.L, r.B, 0, r.mod_group_stride};
-            if (int er = attn_sublayer_fp32(r, w.mha_l, h, r.N, axL, mm, 0, 1, 2, mk, 1, r.L)) return er;
-            if (int er = attn_sublayer_fp32(r, w.mha_t, h, r.N, axT, mm, 3, 4, 5, mk, r.L, r.T)) return er;
-            if (int er = mlp_sublayer_fp32(r, w.ffn, h, r.N, mm, 6, 7, 8)) return er;
+            const TrunkSites st = trunk_sites(r, i, step, nullptr);
+            if (int er = attn_sublayer_fp32(r, w.mha_l, st.l)) return er;
+            if (int er = attn_sublayer_fp32(r, w.mha_t, st.t)) return er;
+            if (int er = mlp_sublayer_fp32(r, w.ffn, st.mlp)) return er;
             if (trace_h) HIPCHK(hipMemcpyAsync(trace_h + (size_t)(i + 1) * r.N * kC, h, hbytes, hipMemcpyDeviceToDevice, r.s));
         }
         const F32Bufs fb = f32_bufs(r);
-        const ModMap fm{modstep + c->final_off(), r.T * r.L, r.B, 0, r.mod_group_stride};
-        launch32_ln_mod(h, r.N, fm, 0, 1, 0, 1e-6f, fb.y, r.s, nullptr, false);
+        launch32_ln_mod(h, r.N, mod_final(r, step), 0, 1, 0, 1e-6f, fb.y, r.s, nullptr, false);
         LinearParams fin = lin_op(fb.y, kC, c->f32(c->slot.fin.w), kC, c->f32(c->slot.fin.b), r.N, r.D, kC, euler ? x : out, r.D);
         fin.mode = euler ? kLinEuler : kLinStore;
         fin.scalar = dt;
@@ -1666,7 +1731,7 @@ static int denoise_step(const Run& r, int step, float* x, float* out, int euler,
     FinalParams f{};
     f.h = h;
     f.nrows = r.N;
-    f.mm = ModMap{modstep + c->final_off(), r.T * r.L, r.B, 0, r.mod_group_stride};
+    f.mm = mod_final(r, step);
     f.shift_chunk = 0;
     f.scale_chunk = 1;
     f.w = c->wfin;
@@ -1682,13 +1747,13 @@ static int denoise_step(const Run& r, int step, float* x, float* out, int euler,
     bool final_done = false;
     for (int i = 0; i < c->nl; ++i) {
         const TrunkW& w = c->trunk[i];
-        const ModMap mm{modstep + c->trunk_off(i), r.T * r.L, r.B, 0, r.mod_group_stride};
-        const LayerPlan pl = layer_plan(r, axL, axT, i == c->nl - 1 && !trace_h, embed_tail && step + 1 < r.S, tk.trace != nullptr);
-        const OutProj proj_l{w.mha_l.wo, w.mha_l.bo, 2}, proj_t{w.mha_t.wo, w.mha_t.bo, 5};
-        if (int er = attn_sublayer(r, pl.l, w.mha_l, Rows{h, r.N, mm, 0}, axL, mk, OutProj{})) return er;
-        if (int er = attn_sublayer(r, pl.t, w.mha_t, Rows{h, r.N, mm, 3}, axT, mk, proj_l)) return er;
+        const TrunkSites st = trunk_sites(r, i, step, nullptr);
+        const LayerPlan pl = layer_plan(r, st.l.ax, st.t.ax, i == c->nl - 1 && !trace_h, embed_tail && step + 1 < r.S, tk.trace != nullptr);
+        const OutProj proj_l{w.mha_l.wo, w.mha_l.bo, st.l.gate()}, proj_t{w.mha_t.wo, w.mha_t.bo, st.t.gate()};
+        if (int er = attn_sublayer(r, pl.l, w.mha_l, st.l, OutProj{})) return er;
+        if (int er = attn_sublayer(r, pl.t, w.mha_t, st.t, proj_l)) return er;
         tk.fold_sl = (long)step * c->nl + i;
-        if (int er = mlp_sublayer(r, pl.mlp, w.ffn, Rows{h, r.N, mm, 6}, proj_t, &tk)) return er;
+        if (int er = mlp_sublayer(r, pl.mlp, w.ffn, st.mlp, proj_t, &tk)) return er;
         tk.trace = nullptr;
         final_done = pl.mlp.use_rows && (pl.mlp.rows == MlpRowsForm::FoldFinal || pl.mlp.rows == MlpRowsForm::FoldFinalEmbed);
         if (trace_h) HIPCHK(hipMemcpyAsync(trace_h + (size_t)(i + 1) * r.N * kC, h, hbytes, hipMemcpyDeviceToDevice, r.s));
@@ -1697,7 +1762,9 @@ static int denoise_step(const Run& r, int step, float* x, float* out, int euler,
     return launch(r, "final_euler", [&] { launch_final(f, r.s); });
 }
 
-static int make_run(Run* r, mdgen_ctx* c, const mdgen_shape* sh, int S, int t_shared, void* ws, size_t ws_bytes,
+// reads_f32: the call reads the fp32 weight copies (the sampler with option precision = 32: f32_path(c); the training step always)
+static bool f32_path(const mdgen_ctx* c) { return c && c->opt_precision == 32; }
+static int make_run(Run* r, mdgen_ctx* c, const mdgen_shape* sh, int S, int t_shared, bool reads_f32, void* ws, size_t ws_bytes,
                     void* stream) {
     if (int e = check_shape(c, sh, S)) return e;
     if (!c->finalized) return fail(-6, "context not finalized (mdgen_ctx_finalize)");
@@ -1706,8 +1773,8 @@ static int make_run(Run* r, mdgen_ctx* c, const mdgen_shape* sh, int S, int t_sh
     if (ws_bytes < r->lay.total_bytes)
         return fail(-7, "workspace too small: %zu < %zu bytes", ws_bytes, r->lay.total_bytes);
     if (((uintptr_t)ws & 255) != 0) return fail(-7, "workspace must be 256-byte aligned");
-    if (c->opt_precision == 32 && !c->opt_keep_fp32) return fail(-6, "precision 32 requires option keep_fp32_weights");
-    if (c->opt_precision == 32)
+    if (reads_f32 && !c->opt_keep_fp32) return fail(-6, "precision 32 requires option keep_fp32_weights");
+    if (reads_f32)
         if (int e = check_f32_weights(c)) return e;
     r->c = c;
     r->B = sh->B;
@@ -1777,7 +1844,7 @@ extern "C" int32_t mdgen_denoiser_forward(mdgen_ctx* c, const mdgen_shape* sh, c
         return fail(-1, "null tensor argument");
     Run r{};
     const int t_shared = (sh && sh->B == 1) ? 1 : 0;
-    if (int e = make_run(&r, c, sh, 1, t_shared, ws, ws_bytes, stream)) return e;
+    if (int e = make_run(&r, c, sh, 1, t_shared, f32_path(c), ws, ws_bytes, stream)) return e;
     r.mask = mask;
     r.start_rot = start_rot;
     r.start_trans = start_trans;
@@ -1899,7 +1966,7 @@ extern "C" int32_t mdgen_sample_euler(mdgen_ctx* c, const mdgen_shape* sh, int32
     if (!x || !mask || !start_rot || !start_trans || !x_cond || !x_cond_mask || !aatype)
         return fail(-1, "null tensor argument");
     Run r{};
-    if (int e = make_run(&r, c, sh, S, 1, ws, ws_bytes, stream)) return e;
+    if (int e = make_run(&r, c, sh, S, 1, f32_path(c), ws, ws_bytes, stream)) return e;
     r.mask = mask;
     r.start_rot = start_rot;
     r.start_trans = start_trans;
@@ -1937,7 +2004,7 @@ extern "C" int32_t mdgen_rollout_euler(mdgen_ctx* c, const mdgen_shape* sh, int3
     if (n_blocks < 1) return fail(-2, "n_blocks must be >= 1");
     if (c && c->d.tps_condition) return fail(-2, "the block rollout is defined for forward-simulation models (sim_condition)");
     Run r{};
-    if (int e = make_run(&r, c, sh, S, 1, ws, ws_bytes, stream)) return e;
+    if (int e = make_run(&r, c, sh, S, 1, f32_path(c), ws, ws_bytes, stream)) return e;
     if ((long)n_blocks * sh->T > 2000000000L / ((long)sh->L * 42)) return fail(-2, "trajectory too long for one call");
     r.mask = mask;
     r.start_rot = cond_rots;
@@ -2058,7 +2125,7 @@ extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_st
     const int S = mode == 4 ? ode::kStages : fwd ? 1 : n_steps;
     const int t_shared = fwd ? (sh->B == 1 ? 1 : 0) : 1;
     Run r{};
-    if (int e = make_run(&r, c, sh, S, t_shared, (void*)4096, (size_t)1 << 60, nullptr)) return e;
+    if (int e = make_run(&r, c, sh, S, t_shared, f32_path(c), (void*)4096, (size_t)1 << 60, nullptr)) return e;
     float* fake = (float*)4096;   // never dereferenced: plan mode launches nothing
     r.mask = r.start_rot = r.start_trans = r.end_rot = r.end_trans = r.x_cond = fake;
     r.x_cond_mask = r.aatype = (const int64_t*)fake;

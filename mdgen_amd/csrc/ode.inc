@@ -242,7 +242,7 @@ extern "C" int32_t mdgen_sample_dopri5(mdgen_ctx* c, const mdgen_shape* sh, doub
     mdgen_ws_layout lay;
     if (int e = mdgen_workspace_layout(c, sh, ode::kStages, 1, &lay)) return e;
     Run r{};
-    if (int e = make_run(&r, c, sh, ode::kStages, 1, ws, lay.total_bytes, stream)) return e;
+    if (int e = make_run(&r, c, sh, ode::kStages, 1, f32_path(c), ws, lay.total_bytes, stream)) return e;
     r.mask = mask;
     r.start_rot = start_rot;
     r.start_trans = start_trans;

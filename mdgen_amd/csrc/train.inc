@@ -52,16 +52,32 @@ struct SubTapeAttn { float *h_in, *y, *qkv, *att, *u, *lse; AttnPlan plan; };   
 struct SubTapeMlp { float *h_in, *y, *pre, *hid, *u; MlpPlan plan; };   // hid = gelu(pre): fc2's input, taped rather than recomputed
 struct SubTapeIpa { float *h_in, *proj, *feat, *stats; IpaPlan plan; };
 
+// One pass of the IPA stack.  The one-sided model has one (on the start frames); the two-sided model two on shared weights, stream 0 =
+// x_r on the start frames, stream 1 = x_f on the end frames (latent_model.py:193-205), forward and backward in that order.
+struct IpaStream {
+    float *h, *dh;                        // residual rows [B*L][384] (workspace) and their gradient
+    const float* rel;                     // relative-frame input [B*L][7] of the two-sided model, else null ...
+    const float *w7, *b7;                 // ... its embedder as ipa_init reads it ...
+    Lin rel7;                             // ... and the embedder's gradient slots
+    const float *rot, *trans;             // the frames its point attention runs on
+    std::vector<SubTapeIpa> ip;           // the tape, per layer
+    std::vector<SubTapeAttn> il;
+    std::vector<SubTapeMlp> im;
+};
+
 struct Train {
     Run r;
     mdgen_ctx* c;
+    // the caller's tensors beyond those of the Run
+    const float *xt, *tvals, *target, *loss_mask;
+    float *loss, *pred;
     float* grads;
     const int64_t* goff;     // per weight slot; < 0: no gradient wanted
     // Operand mode of the call's linear layers / weight gradients (option train_precision): false = exact fp32 products
     // (k32_linear / k32_dw), true = bf16-rounded operands on the bf16 MFMA with fp32 accumulation (the k16_* forms).
     bool bf16 = false;
     // scratch (backward)
-    float *dh, *dy, *ytmp, *act, *stats, *part, *cpart, *dmod, *dhi, *dsilu, *wt;
+    float *dh, *dy, *ytmp, *act, *stats, *part, *cpart, *dmod, *dsilu, *wt;
     size_t part_floats, cpart_floats;
     // Second stream (option train_streams = 2).  The weight / bias gradients of the linear layers are off the critical path of
     // the backward pass (nothing reads them before the optimiser): they run on `side`, beside the dX products, the attention
@@ -123,24 +139,45 @@ struct Train {
         ++sub;
         return 0;
     }
-    // where a weight gradient whose operands are complete on the main stream NOW is to be launched
-    int fork(hipStream_t* sw, float** pt, float** cpt) {
-        *sw = r.s; *pt = part; *cpt = cpart;
-        if (!side) return 0;
+    // where a weight gradient whose operands are complete on the main stream NOW is to be launched, with the partial-sum scratch
+    // of that stream: the second stream if there is one and a gradient is wanted, else the main one
+    struct Fork { hipStream_t s; float *part, *cpart; };
+    int fork(bool wanted, Fork* f) {
+        *f = Fork{r.s, part, cpart};
+        if (!side || !wanted) return 0;
         hipEvent_t e = next_event();
         if (!e) return fail(-8, "hipEventCreate failed (training event pool)");
         HIPCHK(hipEventRecord(e, r.s));
         HIPCHK(hipStreamWaitEvent(side, e, 0));
-        *sw = side; *pt = part2; *cpt = cpart2;
+        *f = Fork{side, part2, cpart2};
         return 0;
     }
-    std::vector<SubTapeAttn> tl, tt, il;   // trunk residue / temporal attention, IPA-stack attention
-    std::vector<SubTapeMlp> tm, im;
-    std::vector<SubTapeIpa> ip;
-    std::vector<SubTapeAttn> il2;          // second IPA stream (two-sided model only)
-    std::vector<SubTapeMlp> im2;
-    std::vector<SubTapeIpa> ip2;
-    float *dhi2 = nullptr, *rel7 = nullptr;
+    // Milestones: when the gradients of a parameter group are complete the caller's event for it is recorded on the
+    // stream, so that its all-reduce can start on another stream while the rest of the backward pass runs
+    // (mdgen_train_set_milestone_events).  Order: 0 final layer | 1 .. nl trunk layers nl-1 .. 0 | nl+1 token
+    // embedders | nl+2 .. 2nl+1 IPA layers nl-1 .. 0 | 2nl+2 everything (embedding tables, time embedder).
+    int milestone = 0;
+    int mark() {
+        if (milestone < (int)c->milestone_events.size() && c->milestone_events[milestone]) {
+            hipStream_t ms = r.s;
+            if (side) {   // the group's gradients come from both streams: the second one waits for the main one and carries the event
+                hipEvent_t e = next_event();
+                if (!e) return fail(-8, "hipEventCreate failed (training event pool)");
+                HIPCHK(hipEventRecord(e, r.s));
+                HIPCHK(hipStreamWaitEvent(side, e, 0));
+                ms = side;
+            }
+            HIPCHK(hipEventRecord((hipEvent_t)c->milestone_events[milestone], ms));
+        }
+        ++milestone;
+        return 0;
+    }
+    std::vector<SubTapeAttn> tl, tt;       // the trunk's tape: residue / temporal attention, MLP
+    std::vector<SubTapeMlp> tm;
+    IpaStream st[2];
+    int nst = 1;
+    float* rel7 = nullptr;                 // x_f | x_r [2][B*L][7] (two-sided model)
+    FinalPlan fin{};                       // the final layer's plan, made in the forward pass
     const float* w(int slot) const { return c->f32(slot); }   // (every slot has its copy: check_f32_weights ran before the first launch)
     float* grad(int slot) const { return goff[slot] < 0 ? nullptr : grads + goff[slot]; }
 };
@@ -160,67 +197,59 @@ constexpr size_t kCpartFloats = (size_t)4 << 20;    // ... of column-sum partial
 // all tape / scratch sizes in one place (used for the size query and for carving)
 // `two_streams`: the second instances of du / dhid / dqkv / dbias and of the partial-sum scratch exist only then (option train_streams = 2;
 // ~0.9 GB at ATLAS B1 T250 L256); with one stream the [1] pointers alias the [0] ones.
-static size_t carve_train(Train* t, const mdgen_ctx* c, long B, long T, long L, unsigned char* base) {
+static size_t carve_train(Train* out, const mdgen_ctx* c, long B, long T, long L, unsigned char* base) {
+    Train query;   // (the size query carves into a Train of its own)
+    Train& t = out ? *out : query;
     const bool two_streams = c->opt_train_streams == 2;
     const long N = B * T * L, Mp = B * L, maxr = N > Mp ? N : Mp;
-    const int nl = c->nl;
     Carver cv{base};
     auto attn = [&](long rows) { SubTapeAttn a; a.h_in = cv.take(rows * kC); a.y = cv.take(rows * kC); a.qkv = cv.take(rows * 3 * kC); a.att = cv.take(rows * kC); a.u = cv.take(rows * kC); a.lse = cv.take(rows * kH); return a; };
     auto mlp = [&](long rows) { SubTapeMlp a; a.h_in = cv.take(rows * kC); a.y = cv.take(rows * kC); a.pre = cv.take(rows * kF); a.hid = cv.take(rows * kF); a.u = cv.take(rows * kC); return a; };
-    std::vector<SubTapeAttn> tl, tt, il, il2;
-    std::vector<SubTapeMlp> tm, im, im2;
-    std::vector<SubTapeIpa> ip, ip2;
-    const bool two = c->d.tps_condition != 0;
-    for (int i = 0; i < nl; ++i) {
-        tl.push_back(attn(N)); tt.push_back(attn(N)); tm.push_back(mlp(N));
-        SubTapeIpa s; s.h_in = cv.take(Mp * kC); s.proj = cv.take(Mp * kIpaProj); s.feat = cv.take(Mp * kIpaFeat); s.stats = cv.take(Mp * 4);
-        ip.push_back(s); il.push_back(attn(Mp)); im.push_back(mlp(Mp));
-        if (two) {
-            SubTapeIpa s2; s2.h_in = cv.take(Mp * kC); s2.proj = cv.take(Mp * kIpaProj); s2.feat = cv.take(Mp * kIpaFeat); s2.stats = cv.take(Mp * 4);
-            ip2.push_back(s2); il2.push_back(attn(Mp)); im2.push_back(mlp(Mp));
+    t.nst = c->d.tps_condition ? 2 : 1;
+    for (int i = 0; i < c->nl; ++i) {
+        t.tl.push_back(attn(N)); t.tt.push_back(attn(N)); t.tm.push_back(mlp(N));
+        for (int k = 0; k < t.nst; ++k) {
+            SubTapeIpa s; s.h_in = cv.take(Mp * kC); s.proj = cv.take(Mp * kIpaProj); s.feat = cv.take(Mp * kIpaFeat); s.stats = cv.take(Mp * 4);
+            t.st[k].ip.push_back(s); t.st[k].il.push_back(attn(Mp)); t.st[k].im.push_back(mlp(Mp));
         }
     }
-    float* dhi2 = two ? cv.take(Mp * kC) : nullptr;
-    float* rel7 = two ? cv.take(2 * Mp * 7) : nullptr;
-    float* dh = cv.take(N * kC);
-    float* dy = cv.take(maxr * kC);
-    float *dqkv[2], *dhid[2], *du[2];
+    if (t.nst == 2) {
+        t.st[1].dh = cv.take(Mp * kC);
+        t.rel7 = cv.take(2 * Mp * 7);
+        t.st[0].rel = t.rel7 + Mp * 7;   // x_r
+        t.st[1].rel = t.rel7;            // x_f
+    } else {
+        t.st[0].rel = nullptr;
+    }
+    t.dh = cv.take(N * kC);
+    t.dy = cv.take(maxr * kC);
     for (int p = 0; p < 2; ++p) {
         if (p == 1 && !two_streams) {
-            dqkv[1] = dqkv[0]; dhid[1] = dhid[0]; du[1] = du[0];
+            t.dqkv_[1] = t.dqkv_[0]; t.dhid_[1] = t.dhid_[0]; t.du_[1] = t.du_[0];
             break;
         }
-        dqkv[p] = cv.take(maxr * 3 * kC);
-        dhid[p] = cv.take(maxr * kF);
-        du[p] = cv.take(maxr * kC);
+        t.dqkv_[p] = cv.take(maxr * 3 * kC);
+        t.dhid_[p] = cv.take(maxr * kF);
+        t.du_[p] = cv.take(maxr * kC);
     }
-    float* ytmp = cv.take(maxr * kC);
-    float* act = cv.take(maxr * kF);
-    float* stats = cv.take(maxr * kH * 2);
+    t.dqkv = t.dqkv_[0]; t.dhid = t.dhid_[0]; t.du = t.du_[0];
+    t.ytmp = cv.take(maxr * kC);
+    t.act = cv.take(maxr * kF);
+    t.stats = cv.take(maxr * kH * 2);
     const long nseq_max = std::max(std::max(B * T, B * L), B);
-    float* dbias[2];
-    dbias[0] = cv.take(nseq_max * kH * 2 * kDH);
-    dbias[1] = two_streams ? cv.take(nseq_max * kH * 2 * kDH) : dbias[0];
-    const size_t part_floats = kPartFloats;
-    float* part = cv.take(part_floats);
-    const size_t cpart_floats = kCpartFloats;
-    float* cpart = cv.take(cpart_floats);
-    float* part2 = two_streams ? cv.take(part_floats) : part;              // the second stream's partial sums
-    float* cpart2 = two_streams ? cv.take(cpart_floats) : cpart;
-    float* dmod = cv.take((size_t)B * c->modrow);
-    float* dhi = cv.take(Mp * kC);
-    float* dsilu = cv.take((size_t)B * (kC * 4 + 256));
-    float* wt = cv.take((size_t)kF * kC);               // one transposed weight (lin_bwd, bf16-operand mode)
-    if (t) {
-        t->tl = tl; t->tt = tt; t->il = il; t->tm = tm; t->im = im; t->ip = ip;
-        t->il2 = il2; t->im2 = im2; t->ip2 = ip2; t->dhi2 = dhi2; t->rel7 = rel7;
-        t->dh = dh; t->dy = dy; t->ytmp = ytmp; t->act = act; t->stats = stats;
-        for (int p = 0; p < 2; ++p) { t->dqkv_[p] = dqkv[p]; t->dhid_[p] = dhid[p]; t->du_[p] = du[p]; }
-        t->dqkv = dqkv[0]; t->dhid = dhid[0]; t->du = du[0];
-        t->part2 = part2; t->cpart2 = cpart2;
-        t->dbias_[0] = dbias[0]; t->dbias_[1] = dbias[1]; t->dbias = dbias[0]; t->part = part; t->part_floats = part_floats; t->cpart = cpart; t->cpart_floats = cpart_floats;
-        t->dmod = dmod; t->dhi = dhi; t->dsilu = dsilu; t->wt = wt;
-    }
+    t.dbias_[0] = cv.take(nseq_max * kH * 2 * kDH);
+    t.dbias_[1] = two_streams ? cv.take(nseq_max * kH * 2 * kDH) : t.dbias_[0];
+    t.dbias = t.dbias_[0];
+    t.part_floats = kPartFloats;
+    t.part = cv.take(t.part_floats);
+    t.cpart_floats = kCpartFloats;
+    t.cpart = cv.take(t.cpart_floats);
+    t.part2 = two_streams ? cv.take(t.part_floats) : t.part;              // the second stream's partial sums
+    t.cpart2 = two_streams ? cv.take(t.cpart_floats) : t.cpart;
+    t.dmod = cv.take((size_t)B * c->modrow);
+    t.st[0].dh = cv.take(Mp * kC);
+    t.dsilu = cv.take((size_t)B * (kC * 4 + 256));
+    t.wt = cv.take((size_t)kF * kC);               // one transposed weight (lin_bwd, bf16-operand mode)
     return cv.off;
 }
 
@@ -253,12 +282,13 @@ static DxPlan dx_plan(bool bf16, long n, int M, int K, int ldy, bool w_al, bool 
 // three times (ATLAS step: y 25.2 -> 24.6, dq | dk | dv -> 24.2, du -0.3, d pre -0.2 ms).  Weight and activation gradients are
 // unchanged; the bias gradients of the layers whose dY is stored rounded are column sums of the stored values.
 // Only the streamed / wide kernels read such rows, so a plan is first made with them and kept if every consumer's form is one of
-// those and the one-pass gate kernel writes du; else it is made again with fp32 rows.  ln_adjacent: kernels.h ln_bwd_form.
-static AttnPlan plan_attn(const Train& t, long n, const AxisMap& ax, long tpg, const bool (&w_al)[4], bool ln_adjacent) {
+// those and the one-pass gate kernel writes du; else it is made again with fp32 rows.
+// (ln_bwd_form's `adjacent`: a site's scale chunk lies right behind its shift chunk, Rows::scale)
+static AttnPlan plan_attn(const Train& t, long n, const AxisMap& ax, long tpg, const bool (&w_al)[4]) {
     AttnPlan p{};
     p.attn = train_attn_form(t.bf16, ax);
     p.gate = gate_bwd_form(n, tpg, t.cpart_floats);
-    p.ln = ln_bwd_form(n, tpg, t.cpart_floats, ln_adjacent);
+    p.ln = ln_bwd_form(n, tpg, t.cpart_floats, true);
     const bool w3_al = w_al[0] && w_al[1] && w_al[2];
     for (int r16 = t.bf16 ? 1 : 0; r16 >= 0; --r16) {
         p.rows16 = r16 != 0;
@@ -281,10 +311,10 @@ static AttnPlan plan_attn(const Train& t, long n, const AxisMap& ax, long tpg, c
     }
     return p;
 }
-static MlpPlan plan_mlp(const Train& t, long n, long tpg, const bool (&w_al)[2], bool ln_adjacent) {
+static MlpPlan plan_mlp(const Train& t, long n, long tpg, const bool (&w_al)[2]) {
     MlpPlan p{};
     p.gate = gate_bwd_form(n, tpg, t.cpart_floats);
-    p.ln = ln_bwd_form(n, tpg, t.cpart_floats, ln_adjacent);
+    p.ln = ln_bwd_form(n, tpg, t.cpart_floats, true);
     for (int r16 = t.bf16 ? 1 : 0; r16 >= 0; --r16) {   // (y, hid, du and d pre alike)
         p.rows16 = r16 != 0;
         p.fc1 = linear_form(t.bf16, LinShape{n, kF, kC, kC, kC, 0, true, w_al[0], p.rows16}, true);
@@ -315,29 +345,22 @@ static IpaPlan plan_ipa(const Train& t, long n, const bool (&w_al)[5]) {
     return p;
 }
 // the final layer: D outputs per token
-static FinalPlan plan_final(const Train& t, long n, int D, long tpg, bool w_al, bool ln_adjacent) {
+static FinalPlan plan_final(const Train& t, long n, int D, long tpg, bool w_al) {
     FinalPlan p{};
     p.lin = linear_form(t.bf16, LinShape{n, D, kC, kC, kC, 0, true, w_al, false}, false);
     p.dx = dx_plan(t.bf16, n, D, kC, D, w_al, false);
     p.dw = dw_plan(t, DwShape{n, D, kC, D, kC, true}, false, false);
-    p.ln = ln_bwd_form(n, tpg, t.cpart_floats, ln_adjacent);
+    p.ln = ln_bwd_form(n, tpg, t.cpart_floats, true);
     return p;
 }
 
-// the call's linear layer in the form its plan gives
-static void step_linear(LinearParams p, LinearForm form, hipStream_t s) {
-    p.fast_gelu = form != LinearForm::F32;    // (see linear.h)
-    p.a_bf16 = form == LinearForm::StreamBf16Rows;
-    launch_linear(p, form, s);
-}
-// the call's weight gradient; the bias gradient too where the plan says it rides along
-static void step_dw(const DwParams& p, const DwPlan& pl, hipStream_t s) { launch_dw(p, pl.form, s); }
+// the operands of a weight gradient dW += dY^T X, db += colsum(dY) where the plan says the bias gradient rides along
 static DwParams dw_op(const float* dy, int ldy, const float* x, int ldx, long n, int m, int k, float* dw, float* db, float* part,
                       const Train& t) {
     return DwParams{dy, ldy, x, ldx, n, m, 1, k, {dw, nullptr, nullptr}, {db, nullptr, nullptr}, part, t.part_floats};
 }
 // ... of a layer outside the sub-layers (embedders, adaLN heads, time embedder): planned where it is launched
-static void step_dw_now(const Train& t, const DwParams& p, hipStream_t s) { step_dw(p, dw_plan(t, dw_shape(p), false, false), s); }
+static void step_dw_now(const Train& t, const DwParams& p, hipStream_t s) { launch_dw(p, dw_plan(t, dw_shape(p), false, false).form, s); }
 
 // the weight W(col < m, kk < k) of ONE layer as a bf16 fragment stream in the scratch t.wt for the streamed forms (turned: the fp32
 // matrix is [k][m], dX = dY W).  The scratch is reused by the next call on the stream.
@@ -350,46 +373,45 @@ static const unsigned char* wpack1(const Train& t, const float* w, int ld, int m
 // LayerNorm + modulate of the residual stream into y, the stream's rows copied to the tape (h_in) -- with the previous sub-layer's
 // pending gated update formed on the way when there is one (Train::Pending)
 // y_bf16: y is stored as bf16 rows (the plan's rows16: it is only ever a GEMM operand)
-static int ln_mod_tape(Train& t, const float* h, long nrows, const ModMap& mm, int shift, int scale, float* y, float* h_in,
-                       bool y_bf16) {
+static int ln_mod_tape(Train& t, const Rows& rw, float* y, float* h_in, bool y_bf16) {
     if (!t.pend.x) {
-        launch32_ln_mod(h, nrows, mm, shift, scale, 0, 1e-6f, y, t.r.s, h_in, y_bf16);
+        launch32_ln_mod(rw.h, rw.nrows, rw.mm, rw.shift(), rw.scale(), 0, 1e-6f, y, t.r.s, h_in, y_bf16);
         return 0;
     }
-    if (t.pend.nrows != nrows) return fail(-7, "internal: pending gated update of %ld rows before a LayerNorm of %ld", t.pend.nrows, nrows);
-    launch32_gate_ln_mod(t.pend.x, t.pend.u, nrows, t.pend.mm, t.pend.gate, mm, shift, scale, 1e-6f, y, h_in, t.r.s, y_bf16);
+    if (t.pend.nrows != rw.nrows)
+        return fail(-7, "internal: pending gated update of %ld rows before a LayerNorm of %ld", t.pend.nrows, rw.nrows);
+    launch32_gate_ln_mod(t.pend.x, t.pend.u, rw.nrows, t.pend.mm, t.pend.gate, rw.mm, rw.shift(), rw.scale(), 1e-6f, y, h_in, t.r.s, y_bf16);
     t.pend = Train::Pending{};
     return 0;
 }
 // the sub-layer's residual update h += gate * u, or its deferral (x = the sub-layer's taped input rows = the stream before it)
-static void gated_update(Train& t, float* h, const float* x, const float* u, long nrows, const ModMap& mm, int gate) {
-    if (t.defer_gate) t.pend = Train::Pending{x, u, mm, gate, nrows};
-    else launch32_gated_add(h, u, nrows, mm, gate, 1, t.r.s);
+static void gated_update(Train& t, const Rows& rw, const float* x, const float* u) {
+    if (t.defer_gate) t.pend = Train::Pending{x, u, rw.mm, rw.gate(), rw.nrows};
+    else launch32_gated_add(rw.h, u, rw.nrows, rw.mm, rw.gate(), 1, t.r.s);
 }
 static void flush_pending(Train& t, float* h) {
     if (!t.pend.x) return;
     launch32_gated_sum(h, t.pend.x, t.pend.u, t.pend.nrows, t.pend.mm, t.pend.gate, t.r.s);
     t.pend = Train::Pending{};
 }
-static TrainAttnParams attn_op(const Train& t, const MhaW& m, const AxisMap& ax, const MaskMap& mk, const SubTapeAttn& tp) {
+static TrainAttnParams attn_op(const Train& t, const MhaW& m, const Rows& rw, const SubTapeAttn& tp) {
     TrainAttnParams a{};
-    a.qkv = tp.qkv; a.ld = 3 * kC; a.ax = ax; a.mk = mk;
+    a.qkv = tp.qkv; a.ld = 3 * kC; a.ax = rw.ax; a.mk = rw.mk;
     a.bias_k = t.w(m.slot.bias_k); a.bias_v = t.w(m.slot.bias_v); a.inv_freq = t.c->inv_freq;
     a.out = tp.att; a.lse = tp.lse;
     return a;
 }
 
-// tpg: tokens per modulation group (the backward's column sums; part of the plan)
-static int attn_fwd_tape(Train& t, const MhaW& m, float* h, long nrows, const AxisMap& ax, const ModMap& mm, int shift, int scale,
-                         int gate, const MaskMap& mk, long pos_div, int pos_mod, long tpg, SubTapeAttn& tp) {
+static int attn_fwd_tape(Train& t, const MhaW& m, const Rows& rw, SubTapeAttn& tp) {
     const Run& r = t.r;
     const auto& p = m.slot;
+    const long nrows = rw.nrows;
     const float* w3[3] = {t.w(p.q.w), t.w(p.k.w), t.w(p.v.w)};
     const float* b3[3] = {t.w(p.q.b), t.w(p.k.b), t.w(p.v.b)};
     const float* wo = t.w(p.o.w);
     const bool w_al[4] = {al16(w3[0]), al16(w3[1]), al16(w3[2]), al16(wo)};
-    const AttnPlan& pl = tp.plan = plan_attn(t, nrows, ax, tpg, w_al, scale == shift + 1);
-    if (int e = ln_mod_tape(t, h, nrows, mm, shift, scale, tp.y, tp.h_in, pl.rows16)) return e;     // y (taped), and the tape's copy of h
+    const AttnPlan& pl = tp.plan = plan_attn(t, nrows, rw.ax, rw.tpg(), w_al);
+    if (int e = ln_mod_tape(t, rw, tp.y, tp.h_in, pl.rows16)) return e;     // y (taped), and the tape's copy of h
     const float qscale = 1.0f / std::sqrt((float)kDH);
     if (pl.qkv_one_pass) {   // bf16 operands: one pass over y, c[n][j kC + i] = (y . w3[j][i] + b3[j][i]) * scale[j]
         LinearParams q = lin_op(tp.y, kC, w3[0], kC, nullptr, nrows, 3 * kC, kC, tp.qkv, 3 * kC);
@@ -409,25 +431,26 @@ static int attn_fwd_tape(Train& t, const MhaW& m, float* h, long nrows, const Ax
         }
     }
     // (the sequence-resident bf16-operand kernels rotate q, k while they convert them: no RoPE pass, the tape keeps them unrotated)
-    if (pl.attn != TrainAttnForm::SeqRope) launch32_rope(tp.qkv, nrows, 3 * kC, pos_div, pos_mod, t.c->inv_freq, r.s);
-    launch_train_attn(attn_op(t, m, ax, mk, tp), pl.attn, r.s);
+    // (position of a token on the axis: (token / pos_stride) % len)
+    if (pl.attn != TrainAttnForm::SeqRope) launch32_rope(tp.qkv, nrows, 3 * kC, rw.ax.pos_stride, rw.ax.len, t.c->inv_freq, r.s);
+    launch_train_attn(attn_op(t, m, rw, tp), pl.attn, r.s);
     // (the gated residual as an epilogue of this product, with u kept at a second address, was measured: the store phase is
     // what bounds the wide kernels, and the heavier epilogue cost 1.5 ms per step where the separate pass costs 1.3)
     LinearParams o = lin_op(tp.att, kC, wo, kC, t.w(p.o.b), nrows, kC, kC, tp.u, kC);
     if (linear_streams(pl.out)) o.wpack = wpack1(t, wo, kC, kC, kC, 0);
     step_linear(o, pl.out, r.s);
-    gated_update(t, h, tp.h_in, tp.u, nrows, mm, gate);
+    gated_update(t, rw, tp.h_in, tp.u);
     LAUNCHCHK();
     return 0;
 }
 
-static int mlp_fwd_tape(Train& t, const FfnW& f, float* h, long nrows, const ModMap& mm, int shift, int scale, int gate, long tpg,
-                        SubTapeMlp& tp) {
+static int mlp_fwd_tape(Train& t, const FfnW& f, const Rows& rw, SubTapeMlp& tp) {
     const Run& r = t.r;
+    const long nrows = rw.nrows;
     const float *w1 = t.w(f.slot.fc1.w), *w2 = t.w(f.slot.fc2.w);
     const bool w_al[2] = {al16(w1), al16(w2)};
-    const MlpPlan& pl = tp.plan = plan_mlp(t, nrows, tpg, w_al, scale == shift + 1);
-    if (int e = ln_mod_tape(t, h, nrows, mm, shift, scale, tp.y, tp.h_in, pl.rows16)) return e;     // y (taped), and the tape's copy of h
+    const MlpPlan& pl = tp.plan = plan_mlp(t, nrows, rw.tpg(), w_al);
+    if (int e = ln_mod_tape(t, rw, tp.y, tp.h_in, pl.rows16)) return e;     // y (taped), and the tape's copy of h
     LinearParams fc1 = lin_op(tp.y, kC, w1, kC, t.w(f.slot.fc1.b), nrows, kF, kC, tp.pre, kF);
     fc1.mode = kLinStoreGelu;
     fc1.c2 = tp.hid;               // hid = gelu(pre), as bf16 rows with the plan's rows16
@@ -437,7 +460,7 @@ static int mlp_fwd_tape(Train& t, const FfnW& f, float* h, long nrows, const Mod
     LinearParams fc2 = lin_op(tp.hid, kF, w2, kF, t.w(f.slot.fc2.b), nrows, kC, kF, tp.u, kC);
     if (linear_streams(pl.fc2)) fc2.wpack = wpack1(t, w2, kF, kC, kF, 0);
     step_linear(fc2, pl.fc2, r.s);
-    gated_update(t, h, tp.h_in, tp.u, nrows, mm, gate);
+    gated_update(t, rw, tp.h_in, tp.u);
     LAUNCHCHK();
     return 0;
 }
@@ -501,10 +524,8 @@ static int lin_bwd(Train& t, const Lin& lin, long n, int M, int K, const DxPlan&
     // dW / db: second stream (dy and x are complete at this point of the main stream)
     float* gb = t.grad(lin.b);
     float* gw = t.grad(lin.w);
-    hipStream_t sw = t.r.s;
-    float *pt = t.part, *cpt = t.cpart;
-    if ((gw || gb) && !o.main_stream)
-        if (int e = t.fork(&sw, &pt, &cpt)) return e;
+    Train::Fork f;
+    if (int e = t.fork((gw || gb) && !o.main_stream, &f)) return e;
     LinearParams q = lin_op(o.dy, o.ldy, nullptr, 0, nullptr, n, K, M, o.dx, o.ldx_out);
     q.mode = o.gelu_pre ? kLinGeluBwd : o.accumulate ? kLinAccumulate : kLinStore;
     q.c2 = const_cast<float*>(o.gelu_pre);
@@ -512,32 +533,30 @@ static int lin_bwd(Train& t, const Lin& lin, long n, int M, int K, const DxPlan&
     step_dx(t, q, &W, 1, M, K, dxp);
     // (dY stored as bf16 rows: only the wide pass reads them, so a bias gradient wanted alone takes that pass too, as q | k | v's does)
     const bool pass = gw || (gb && dw_dy_bf16(dwp.form));
-    if (pass) step_dw(dw_op(o.dy, o.ldy, o.x, o.ldx, n, M, K, gw, gb, pt, t), dwp, sw);
-    if (gb && !(pass && dwp.bias_rides)) launch32_colsum(o.dy, o.ldy, nullptr, 0, nullptr, 0, n, M, n, 0.f, gb, 0, cpt, t.cpart_floats, sw);
+    if (pass) launch_dw(dw_op(o.dy, o.ldy, o.x, o.ldx, n, M, K, gw, gb, f.part, t), dwp.form, f.s);
+    if (gb && !(pass && dwp.bias_rides)) launch32_colsum(o.dy, o.ldy, nullptr, 0, nullptr, 0, n, M, n, 0.f, gb, 0, f.cpart, t.cpart_floats, f.s);
     LAUNCHCHK();
     return 0;
 }
 
 // gated residual h_out = h_in + gate * u:  du = gate * dh (into t.du; du16: as bf16 rows -- it is only ever the token operand of the
 // dX product and dY of the weight gradient of the sub-layer's last linear layer);  dgate[g] += sum_t dh * u
-static void gate_bwd(const Train& t, GateBwdForm form, const float* dh, const float* u, long nrows, const ModMap& mm, int gate_chunk,
-                     long tokens_per_group, long mod_ld, float* dmod_base, bool du16) {
-    launch32_gate_bwd(GateBwdParams{dh, u, nrows, mm, gate_chunk, t.du, du16, tokens_per_group, dmod_base + gate_chunk * kC, mod_ld,
+static void gate_bwd(const Train& t, GateBwdForm form, const Rows& rw, const float* dh, const float* u, bool du16) {
+    launch32_gate_bwd(GateBwdParams{dh, u, rw.nrows, rw.mm, rw.gate(), t.du, du16, rw.tpg(), rw.dmod + rw.gate() * kC, (long)t.c->modrow,
                                     t.cpart, t.cpart_floats}, form, t.r.s);
 }
 // LN + modulate backward: dshift[g] += sum dy; dscale[g] += sum dy * xhat; dh (+)= LN'(dy * (1 + scale))
-static void lnmod_bwd(const Train& t, LnBwdForm form, const float* h_in, const float* dy, long nrows, const ModMap& mm, int shift_chunk,
-                      int scale_chunk, long tokens_per_group, long mod_ld, float* dmod_base, float* dh, bool accumulate) {
-    launch32_ln_mod_bwd(LnBwdParams{h_in, dy, nrows, mm, scale_chunk, 1e-6f, dh, accumulate ? 1 : 0, tokens_per_group,
-                                    dmod_base + shift_chunk * kC, dmod_base + scale_chunk * kC, mod_ld, t.cpart, t.cpart_floats}, form, t.r.s);
+static void lnmod_bwd(const Train& t, LnBwdForm form, const Rows& rw, const float* h_in, const float* dy, float* dh, bool accumulate) {
+    launch32_ln_mod_bwd(LnBwdParams{h_in, dy, rw.nrows, rw.mm, rw.scale(), 1e-6f, dh, accumulate ? 1 : 0, rw.tpg(),
+                                    rw.dmod + rw.shift() * kC, rw.dmod + rw.scale() * kC, (long)t.c->modrow, t.cpart, t.cpart_floats}, form, t.r.s);
 }
 
 // backward of one MLP sub-layer; dh is updated in place (dh_in = dh_out + ...)
-static int mlp_bwd(Train& t, const FfnW& f, float* dh, long nrows, const ModMap& mm, int shift, int scale, int gate, long tpg,
-                   long mod_ld, float* dmod_base, const SubTapeMlp& tp) {
+static int mlp_bwd(Train& t, const FfnW& f, const Rows& rw, float* dh, const SubTapeMlp& tp) {
     const MlpPlan& pl = tp.plan;   // hid, y, du = gate * dh and d pre as bf16 rows (rows16), or all of them fp32
+    const long nrows = rw.nrows;
     if (int e = t.begin_sub()) return e;
-    gate_bwd(t, pl.gate, dh, tp.u, nrows, mm, gate, tpg, mod_ld, dmod_base, pl.rows16);   // t.du = gate * dh
+    gate_bwd(t, pl.gate, rw, dh, tp.u, pl.rows16);   // t.du = gate * dh
     LinBwdOp fc2{};   // d pre = (du W2) * gelu'(pre) into t.dhid: the GELU derivative is the epilogue of the dX product
     fc2.dy = t.du; fc2.ldy = kC;
     fc2.x = tp.hid; fc2.ldx = kF;
@@ -549,41 +568,39 @@ static int mlp_bwd(Train& t, const FfnW& f, float* dh, long nrows, const ModMap&
     fc1.x = tp.y; fc1.ldx = kC;
     fc1.dx = t.dy; fc1.ldx_out = kC;
     if (int e = lin_bwd(t, f.slot.fc1, nrows, kF, kC, pl.dx_fc1, pl.dw_fc1, fc1)) return e;
-    lnmod_bwd(t, pl.ln, tp.h_in, t.dy, nrows, mm, shift, scale, tpg, mod_ld, dmod_base, dh, true);
+    lnmod_bwd(t, pl.ln, rw, tp.h_in, t.dy, dh, true);
     LAUNCHCHK();
     return t.end_sub();
 }
 
 // backward of one attention sub-layer
-static int attn_bwd(Train& t, const MhaW& m, float* dh, long nrows, const AxisMap& ax, const ModMap& mm, int shift, int scale,
-                    int gate, const MaskMap& mk, long pos_div, int pos_mod, long tpg, long mod_ld, float* dmod_base,
-                    const SubTapeAttn& tp) {
+static int attn_bwd(Train& t, const MhaW& m, const Rows& rw, float* dh, const SubTapeAttn& tp) {
     hipStream_t s = t.r.s;
+    const long nrows = rw.nrows;
+    const AxisMap& ax = rw.ax;
     const auto& p = m.slot;
     const AttnPlan& pl = tp.plan;   // (as attn_fwd_tape stored the tape: y as bf16 rows or fp32, q and k rotated or not)
     if (int e = t.begin_sub()) return e;
-    gate_bwd(t, pl.gate, dh, tp.u, nrows, mm, gate, tpg, mod_ld, dmod_base, pl.rows16);   // t.du
+    gate_bwd(t, pl.gate, rw, dh, tp.u, pl.rows16);   // t.du
     LinBwdOp o{};   // t.dy = d att = du Wo
     o.dy = t.du; o.ldy = kC;
     o.x = tp.att; o.ldx = kC;
     o.dx = t.dy; o.ldx_out = kC;
     if (int e = lin_bwd(t, p.o, nrows, kC, kC, pl.dx_out, pl.dw_out, o)) return e;
-    TrainAttnParams a = attn_op(t, m, ax, mk, tp);
+    TrainAttnParams a = attn_op(t, m, rw, tp);
     a.dout = t.dy; a.dqkv = t.dqkv; a.stats = t.stats; a.dbias = t.dbias;
     a.dqkv_bf16 = pl.dqkv16;       // the sequence-resident kernels write dq | dk | dv as bf16 rows
     launch_train_attn_bwd(a, pl.attn, s);
     // bias key / value: rows [seq][dk: head x 24 | dv: head x 24] summed over sequences = the (1, 1, C) tensors
     {
         float *gk = t.grad(p.bias_k), *gv = t.grad(p.bias_v);
-        hipStream_t sw = s;
-        float *pt = t.part, *cpt = t.cpart;
-        if (gk || gv)
-            if (int e = t.fork(&sw, &pt, &cpt)) return e;
-        if (gk) launch32_colsum(t.dbias, 2 * kC, nullptr, 0, nullptr, 0, ax.nseq, kC, ax.nseq, 0.f, gk, 0, cpt, t.cpart_floats, sw);
-        if (gv) launch32_colsum(t.dbias + kC, 2 * kC, nullptr, 0, nullptr, 0, ax.nseq, kC, ax.nseq, 0.f, gv, 0, cpt, t.cpart_floats, sw);
+        Train::Fork f;
+        if (int e = t.fork(gk || gv, &f)) return e;
+        if (gk) launch32_colsum(t.dbias, 2 * kC, nullptr, 0, nullptr, 0, ax.nseq, kC, ax.nseq, 0.f, gk, 0, f.cpart, t.cpart_floats, f.s);
+        if (gv) launch32_colsum(t.dbias + kC, 2 * kC, nullptr, 0, nullptr, 0, ax.nseq, kC, ax.nseq, 0.f, gv, 0, f.cpart, t.cpart_floats, f.s);
     }
     if (pl.attn == TrainAttnForm::Exact)    // (the bf16-operand attention backward stores dq, dk already taken back through RoPE)
-        launch32_rope_bwd(t.dqkv, nrows, 3 * kC, pos_div, pos_mod, t.c->inv_freq, 1.0f / std::sqrt((float)kDH), s);
+        launch32_rope_bwd(t.dqkv, nrows, 3 * kC, ax.pos_stride, ax.len, t.c->inv_freq, 1.0f / std::sqrt((float)kDH), s);
     const Lin l3[3] = {p.q, p.k, p.v};
     if (t.bf16) {
         // q | k | v as one layer of 1152 outputs: dy = dqkv [Wq; Wk; Wv] (one product with the contraction over all three,
@@ -597,17 +614,16 @@ static int attn_bwd(Train& t, const MhaW& m, float* dh, long nrows, const AxisMa
             want_g = want_g || g.dw[j] || g.db[j];
             want_b = want_b || g.db[j];
         }
-        hipStream_t sw = s;
-        float* cpt = t.cpart;
-        if (want_g)                                    // (dqkv, y) are complete: the gradients go to the second stream
-            if (int e = t.fork(&sw, &g.part, &cpt)) return e;
+        Train::Fork f;                                 // (dqkv, y) are complete: the gradients go to the second stream
+        if (int e = t.fork(want_g, &f)) return e;
+        g.part = f.part;
         step_dx(t, lin_op(t.dqkv, 3 * kC, nullptr, 0, nullptr, nrows, 0, 0, t.dy, kC), w3, 3, kC, kC, pl.dx_qkv);
         if (want_g) {
-            step_dw(g, pl.dw_qkv, sw);
+            launch_dw(g, pl.dw_qkv.form, f.s);
             for (int j = 0; j < 3 && !(want_b && pl.dw_qkv.bias_rides); ++j)
                 if (g.db[j])
-                    launch32_colsum(t.dqkv + j * kC, 3 * kC, nullptr, 0, nullptr, 0, nrows, kC, nrows, 0.f, g.db[j], 0, cpt,
-                                    t.cpart_floats, sw);
+                    launch32_colsum(t.dqkv + j * kC, 3 * kC, nullptr, 0, nullptr, 0, nrows, kC, nrows, 0.f, g.db[j], 0, f.cpart,
+                                    t.cpart_floats, f.s);
         }
         LAUNCHCHK();
     } else {
@@ -619,18 +635,19 @@ static int attn_bwd(Train& t, const MhaW& m, float* dh, long nrows, const AxisMa
             if (int e = lin_bwd(t, l3[j], nrows, kC, kC, pl.dx_qkv, pl.dw_qkv, q)) return e;
         }
     }
-    lnmod_bwd(t, pl.ln, tp.h_in, t.dy, nrows, mm, shift, scale, tpg, mod_ld, dmod_base, dh, true);
+    lnmod_bwd(t, pl.ln, rw, tp.h_in, t.dy, dh, true);
     LAUNCHCHK();
     return t.end_sub();
 }
 
 // backward of the IPA block of layer i:  x_out = x_in + linear_out(ipa(LN_affine(x_in)))   (latent_model.py:373)
-static int ipa_block_bwd(Train& t, const IpaW& w, const SubTapeIpa& tp, float* dhi, const float* rot, const float* trans) {
+static int ipa_block_bwd(Train& t, const IpaW& w, const SubTapeIpa& tp, const IpaStream& st) {
     const Run& r = t.r;
     hipStream_t s = r.s;
     const auto& p = w.slot;
     const IpaPlan& pl = tp.plan;
     const long Mp = r.Mp;
+    float* dhi = st.dh;
     if (int e = t.begin_sub()) return e;
     float* dfeat = t.dhid;                    // [Mp][256]
     float* dproj = t.dqkv;                    // [Mp][672]
@@ -645,14 +662,14 @@ static int ipa_block_bwd(Train& t, const IpaW& w, const SubTapeIpa& tp, float* d
     o.main_stream = true;
     if (int e = lin_bwd(t, p.out, Mp, kC, kIpaFeat, pl.dx_out, pl.dw_out, o)) return e;
     IpaAttnParams ap{};
-    ap.proj = tp.proj; ap.rot = rot; ap.trans = trans;
-    ap.mask_bl = (const float*)(r.ws + r.lay.mask_bl);
+    ap.proj = tp.proj; ap.rot = st.rot; ap.trans = st.trans;
+    ap.mask_bl = mask_ipa(r).mask;
     ap.head_w = w.head_w; ap.feat = nullptr; ap.feat32 = tp.feat; ap.stats = tp.stats;
     ap.ngroups = r.B; ap.B = r.B; ap.L = r.L;
     launch32_ipa_bwd(ap, dfeat, dproj, dhw, qrec, t.grad(p.head_w), s, t.part, t.part_floats);
     LAUNCHCHK();
     // the four input projections of xn = LN_affine(x_in): t.dy = sum_j dproj_j W_j
-    launch32_ln_mod(tp.h_in, Mp, ModMap{w.gamma_beta, 1, 1, 0, 0}, 1, 0, 1, 1e-5f, t.ytmp, s, nullptr, false);
+    launch32_ln_mod(tp.h_in, Mp, mod_affine(w.gamma_beta), 1, 0, 1, 1e-5f, t.ytmp, s, nullptr, false);
     const Lin lins[4] = {p.q, p.kv, p.q_points, p.kv_points};
     for (int j = 0; j < 4; ++j) {
         LinBwdOp q{};
@@ -666,9 +683,325 @@ static int ipa_block_bwd(Train& t, const IpaW& w, const SubTapeIpa& tp, float* d
         launch32_colsum(t.dy, kC, tp.h_in, kC, nullptr, 2, Mp, kC, Mp, 1e-5f, g, 0, t.cpart, t.cpart_floats, s);
     if (float* g = t.grad(p.norm.b))
         launch32_colsum(t.dy, kC, nullptr, 0, nullptr, 0, Mp, kC, Mp, 0.f, g, 0, t.cpart, t.cpart_floats, s);
-    launch32_ln_bwd(tp.h_in, t.dy, Mp, ModMap{w.gamma_beta, 1, 1, 0, 0}, 0, 1, 1e-5f, dhi, 1, s);
+    launch32_ln_bwd(tp.h_in, t.dy, Mp, mod_affine(w.gamma_beta), 0, 1, 1e-5f, dhi, 1, s);
     LAUNCHCHK();
     return t.end_sub();
+}
+
+// ---- the phases of the step -----------------------------------------------------------------------------------------
+// the streams' operands beyond what carve_train gives them: rows, embedder, frames
+static void bind_ipa_streams(Train& t) {
+    const Run& r = t.r;
+    const mdgen_ctx* c = t.c;
+    IpaStream& a = t.st[0];
+    a.h = (float*)(r.ws + r.lay.ipa_out);   // IPA-stack residual stream [B*L][384] (G = B groups)
+    a.rot = r.start_rot; a.trans = r.start_trans;
+    a.w7 = a.b7 = nullptr;
+    a.rel7 = Lin{};
+    if (t.nst == 2) {   // the x_r stream runs on the start frames, the x_f stream on the end frames (latent_model.py:203-205)
+        a.w7 = c->wr7; a.b7 = c->br7; a.rel7 = c->slot.rel_r;
+        IpaStream& b = t.st[1];
+        b.h = (float*)(r.ws + r.lay.h_ipa);
+        b.rot = r.end_rot; b.trans = r.end_trans;
+        b.w7 = c->wf7; b.b7 = c->bf7; b.rel7 = c->slot.rel_f;
+    }
+}
+
+// the second stream of the call (option train_streams = 2)
+static int open_side_stream(Train& t) {
+    mdgen_ctx* c = t.c;
+    // (same priority as the caller's stream: with the second stream at the lowest OR the highest priority of the device's range
+    // the step took 53 / 60 ms instead of 30.7 -- profiles/r04_experiments.txt)
+    // (default stream priority: created with ANY other priority -- lowest or highest -- the step takes 51-54 ms instead of 27.4:
+    // profiles/r06_experiments.txt #19)
+    if (c->opt_train_streams == 2 && !c->train_side) HIPCHK(hipStreamCreateWithFlags(&c->train_side, hipStreamNonBlocking));
+    t.side = c->opt_train_streams == 2 ? c->train_side : nullptr;
+    return 0;
+}
+
+// Turned weights, start of the call (Train::tr_*): every image the previous call recorded, on the second stream beside the forward
+// pass; without a usable list this call records one.  `caller`: the stream on which the weights are final.
+static int prefetch_turned(Train& t, hipStream_t caller) {
+    mdgen_ctx* c = t.c;
+    if (!t.side || !t.bf16) return 0;
+    if (!(c->tr_plan_ok && c->tr_buf)) {
+        t.tr_record = true;
+        return 0;
+    }
+    hipEvent_t e0 = t.next_event(), e1 = t.next_event();
+    if (e0 && e1) {
+        HIPCHK(hipEventRecord(e0, caller));
+        HIPCHK(hipStreamWaitEvent(t.side, e0, 0));
+        for (const mdgen_ctx::TurnReq& q : c->tr_plan)
+            for (int j = 0; j < q.nseg; ++j)
+                launch32_transpose(q.w[j], q.rows, q.cols, c->tr_buf + q.off + (size_t)j * q.rows, t.side, q.nseg * q.rows);
+        HIPCHK(hipEventRecord(e1, t.side));
+        t.tr_done = e1;
+        t.tr_use = true;
+    }
+    return 0;
+}
+// ... end of the call: a list that was not used up is recorded anew by the next call; a recorded one becomes the next call's list
+static void finish_turned(Train& t) {
+    mdgen_ctx* c = t.c;
+    if (t.tr_use && t.tr_cursor != c->tr_plan.size()) c->tr_plan_ok = false;
+    if (!t.tr_record) return;
+    size_t off = 0;
+    for (mdgen_ctx::TurnReq& q : t.tr_new) {
+        q.off = off;
+        off += ((size_t)q.nseg * q.rows * q.cols + 63) & ~(size_t)63;
+    }
+    bool ok = !t.tr_new.empty();
+    if (ok && off > c->tr_buf_floats) {
+        if (c->tr_buf) (void)hipFree(c->tr_buf);
+        c->tr_buf = nullptr;
+        c->tr_buf_floats = 0;
+        if (hipMalloc((void**)&c->tr_buf, off * 4) == hipSuccess) c->tr_buf_floats = off;
+        else { (void)hipGetLastError(); ok = false; }
+    }
+    c->tr_plan = t.tr_new;
+    c->tr_plan_ok = ok;
+}
+
+// Join on EVERY exit path: whatever this call has launched on the second stream is ordered before what the caller enqueues next
+// on its own stream -- also when the call returns an error half-way (a caller that then zeroes or reuses `grads` or the tape
+// must not race with gradient kernels still running over there).  The error path's own HIP status is not reported twice.
+struct Join {
+    Train& t;
+    bool done = false;
+    int run() {
+        if (done || !t.side) return 0;
+        done = true;
+        hipEvent_t e = t.next_event();
+        if (!e) {   // no event to be had: fall back to a host-side wait for the second stream
+            (void)hipStreamSynchronize(t.side);
+            return 0;
+        }
+        if (hipEventRecord(e, t.side) != hipSuccess || hipStreamWaitEvent(t.r.s, e, 0) != hipSuccess) (void)hipStreamSynchronize(t.side);
+        return 0;
+    }
+    ~Join() { (void)run(); }
+};
+
+// one pass of the IPA stack over the stream's rows on its frames, taped
+static int ipa_forward(Train& t, IpaStream& st) {
+    const Run& r = t.r;
+    const mdgen_ctx* c = t.c;
+    hipStream_t s = r.s;
+    launch_ipa_init(c->aa_emb, r.aatype, st.rel, st.w7, st.b7, st.h, r.B, r.B, r.L, s);
+    for (int i = 0; i < c->nl; ++i) {
+        const IpaW& w = c->ipa[i];
+        const auto& p = w.slot;
+        const IpaSites site = ipa_sites(r, i, st.h, t.dmod);
+        SubTapeIpa& tp = st.ip[i];
+        const bool w_al[5] = {al16(t.w(p.q.w)), al16(t.w(p.kv.w)), al16(t.w(p.q_points.w)), al16(t.w(p.kv_points.w)), al16(t.w(p.out.w))};
+        const IpaPlan& pl = tp.plan = plan_ipa(t, r.Mp, w_al);
+        HIPCHK(hipMemcpyAsync(tp.h_in, st.h, (size_t)r.Mp * kC * 4, hipMemcpyDeviceToDevice, s));
+        // (few groups: the attention's key loop is sliced over workgroups, with t.part as its scratch)
+        const IpaBlockOp o{f32_bufs(r).y, tp.proj, tp.feat, tp.stats, t.part, t.part_floats,
+                           {pl.proj[0], pl.proj[1], pl.proj[2], pl.proj[3]}, pl.out};
+        if (int e = ipa_block_fp32(r, w, st.h, st.rot, st.trans, o)) return e;
+        if (int e = attn_fwd_tape(t, w.mha_l, site.attn, st.il[i])) return e;
+        if (int e = mlp_fwd_tape(t, w.ffn, site.mlp, st.im[i])) return e;
+    }
+    return 0;
+}
+
+// forward (fp32 path, with tape): tables, the IPA streams, token embedding, trunk, final layer and loss
+static int train_forward(Train& t) {
+    const Run& r = t.r;
+    mdgen_ctx* c = t.c;
+    hipStream_t s = r.s;
+    const long N = r.N, Mp = r.Mp, TL = (long)r.T * r.L;
+    {   // time embedding, adaLN table, compact mask  (as prepare(), per-sample t)
+        float* silu = (float*)(r.ws + r.lay.silu_t);
+        launch_temb(t.tvals, r.B, c->d.time_multiplier, c->t_w0, c->t_b0, c->t_w2, c->t_b2, silu, s);
+        launch_adaln(silu, r.B, c->ada_w, c->ada_b, c->modrow, r.mod(), s);
+        HIPCHK(hipMemcpy2DAsync(r.ws + r.lay.mask_bl, (size_t)r.L * 4, r.mask, (size_t)r.T * r.L * 4, (size_t)r.L * 4, r.B,
+                                hipMemcpyDeviceToDevice, s));
+        LAUNCHCHK();
+    }
+    if (t.nst == 2) {
+        // x_f = (start^-1 o end).to_tensor_7(), x_r = (end^-1 o start).to_tensor_7()   (latent_model.py:194-195)
+        if (r.rel7_in) {   // the caller's own to_tensor_7() outputs (quaternion sign as the reference's eigh chose it)
+            HIPCHK(hipMemcpyAsync(t.rel7, r.rel7_in, (size_t)2 * Mp * 7 * 4, hipMemcpyDeviceToDevice, s));
+        } else {
+            launch_rel7(r.start_rot, r.start_trans, r.end_rot, r.end_trans, t.rel7, Mp, s);
+            launch_rel7(r.end_rot, r.end_trans, r.start_rot, r.start_trans, t.rel7 + Mp * 7, Mp, s);
+            LAUNCHCHK();
+        }
+    }
+    for (int k = 0; k < t.nst; ++k)
+        if (int e = ipa_forward(t, t.st[k])) return e;
+    float* hi = t.st[0].h;
+    if (t.nst == 2) {
+        launch_add_inplace(hi, t.st[1].h, Mp * kC, s);
+        LAUNCHCHK();
+    }
+    float* h = r.h();
+    launch_embed(embed_op(r, t.xt, hi), s);
+    LAUNCHCHK();
+    t.defer_gate = true;   // the trunk's residual updates ride in the next sub-layer's LayerNorm launch
+    for (int i = 0; i < c->nl; ++i) {
+        const TrunkW& w = c->trunk[i];
+        const TrunkSites site = trunk_sites(r, i, 0, t.dmod);
+        if (int e = attn_fwd_tape(t, w.mha_l, site.l, t.tl[i])) return e;
+        if (int e = attn_fwd_tape(t, w.mha_t, site.t, t.tt[i])) return e;
+        if (int e = mlp_fwd_tape(t, w.ffn, site.mlp, t.tm[i])) return e;
+    }
+    t.defer_gate = false;
+    flush_pending(t, h);
+    LAUNCHCHK();
+    const Rows fs = final_site(r, 0, t.dmod);
+    t.fin = plan_final(t, N, r.D, fs.tpg(), al16(t.w(c->slot.fin.w)));
+    launch32_ln_mod(h, N, fs.mm, fs.shift(), fs.scale(), 0, 1e-6f, f32_bufs(r).y, s, nullptr, false);
+    step_linear(lin_op(f32_bufs(r).y, kC, t.w(c->slot.fin.w), kC, t.w(c->slot.fin.b), N, r.D, kC, t.pred, r.D), t.fin.lin, s);
+    launch_masked_mse(t.pred, t.target, t.loss_mask, t.loss, TL * r.D, r.B, s, t.cpart, t.cpart_floats);
+    LAUNCHCHK();
+    return 0;
+}
+
+// adaLN head of one parameter block: mod[b] = W_ada silu_t[b] + b_ada  (its d mod rows are complete once the
+// block's own backward is done)
+static int ada_head_bwd(Train& t, const Lin& ada, int off, int rows) {
+    const Run& r = t.r;
+    const float* silu = (const float*)(r.ws + r.lay.silu_t);
+    const int modld = (int)t.c->modrow;
+    float *gw = t.grad(ada.w), *gb = t.grad(ada.b);
+    Train::Fork f;   // (the block's d mod rows are complete here and nothing writes them again)
+    if (int e = t.fork(gw || gb, &f)) return e;
+    if (gw) step_dw_now(t, dw_op(t.dmod + off, modld, silu, kC, r.B, rows, kC, gw, nullptr, f.part, t), f.s);
+    if (gb) launch32_colsum(t.dmod + off, modld, nullptr, 0, nullptr, 0, r.B, rows, r.B, 0.f, gb, 0, f.cpart, t.cpart_floats, f.s);
+    return 0;
+}
+
+// final layer: out = linear(modulate(LN(h)))
+static int final_bwd(Train& t) {
+    const Run& r = t.r;
+    const mdgen_ctx* c = t.c;
+    hipStream_t s = r.s;
+    const long N = r.N, TL = (long)r.T * r.L;
+    float* h = r.h();
+    const Rows fs = final_site(r, 0, t.dmod);
+    if (int e = t.begin_sub()) return e;
+    float* dpred = t.dqkv;   // [N][D] fits the (idle) dqkv scratch
+    launch32_loss_grad(t.pred, t.target, t.loss_mask, TL * r.D, r.B, t.dsilu, dpred, s, t.cpart, t.cpart_floats);   // t.dsilu[0..B) = mask sums (scratch)
+    launch32_ln_mod(h, N, fs.mm, fs.shift(), fs.scale(), 0, 1e-6f, t.ytmp, s, nullptr, false);
+    LinBwdOp o{};   // t.dy = d pred W
+    o.dy = dpred; o.ldy = r.D;
+    o.x = t.ytmp; o.ldx = kC;
+    o.dx = t.dy; o.ldx_out = kC;
+    if (int e = lin_bwd(t, c->slot.fin, N, r.D, kC, t.fin.dx, t.fin.dw, o)) return e;
+    lnmod_bwd(t, t.fin.ln, fs, h, t.dy, t.dh, false);
+    if (int e = ada_head_bwd(t, c->slot.fin_ada, c->final_off(), 2 * kC)) return e;
+    LAUNCHCHK();
+    if (int e = t.end_sub()) return e;
+    return t.mark();
+}
+
+// token embedding (latent_model.py:233-246): h0 = Wl x + bl [+ pos] + Wc x_cond + bc + mask_emb[cm] + ipa_out[b, l]
+static int embed_bwd(Train& t) {
+    const Run& r = t.r;
+    const mdgen_ctx* c = t.c;
+    hipStream_t s = r.s;
+    const long N = r.N;
+    {   // (t.dh is final here: second stream)
+        Train::Fork f;
+        if (int e = t.fork(true, &f)) return e;
+        if (float* g = t.grad(c->slot.latent.w)) step_dw_now(t, dw_op(t.dh, kC, t.xt, r.D, N, kC, r.D, g, nullptr, f.part, t), f.s);
+        if (float* g = t.grad(c->slot.cond.w)) step_dw_now(t, dw_op(t.dh, kC, r.x_cond, r.D, N, kC, r.D, g, nullptr, f.part, t), f.s);
+        if (float* g = t.grad(c->slot.latent.b)) launch32_colsum(t.dh, kC, nullptr, 0, nullptr, 0, N, kC, N, 0.f, g, 0, f.cpart, t.cpart_floats, f.s);
+        if (float* g = t.grad(c->slot.cond.b)) launch32_colsum(t.dh, kC, nullptr, 0, nullptr, 0, N, kC, N, 0.f, g, 0, f.cpart, t.cpart_floats, f.s);
+    }
+    if (float* g = t.grad(c->slot.mask)) {
+        float* ind0 = t.stats;          // [N] + [N] floats fit the stats scratch (N * 32 floats)
+        float* ind1 = t.stats + N;
+        launch32_indicator(r.x_cond_mask, N, ind0, ind1, s);
+        launch32_colsum(t.dh, kC, nullptr, 0, ind0, 3, N, kC, N, 0.f, g, 0, t.cpart, t.cpart_floats, s);
+        launch32_colsum(t.dh, kC, nullptr, 0, ind1, 3, N, kC, N, 0.f, g + kC, 0, t.cpart, t.cpart_floats, s);
+    }
+    launch32_sum_frames(t.dh, r.B, r.T, r.L, t.st[0].dh, s);    // d ipa_out
+    LAUNCHCHK();
+    return t.mark();
+}
+
+// one pass of the IPA stack backwards.  last: the stream after which a layer's gradients are complete -- it runs the adaLN
+// heads and the milestones (the two-sided model's first stream leaves every layer's gradients half done)
+static int ipa_backward(Train& t, const IpaStream& st, bool last) {
+    const Run& r = t.r;
+    const mdgen_ctx* c = t.c;
+    hipStream_t s = r.s;
+    const long Mp = r.Mp;
+    for (int i = c->nl - 1; i >= 0; --i) {
+        const IpaW& w = c->ipa[i];
+        const IpaSites site = ipa_sites(r, i, st.h, t.dmod);
+        if (int e = mlp_bwd(t, w.ffn, site.mlp, st.dh, st.im[i])) return e;
+        if (int e = attn_bwd(t, w.mha_l, site.attn, st.dh, st.il[i])) return e;
+        if (int e = ipa_block_bwd(t, w, st.ip[i], st)) return e;
+        if (last) {
+            if (int e = ada_head_bwd(t, w.slot.ada, c->ipa_off(i), 6 * kC)) return e;
+            LAUNCHCHK();
+            if (int e = t.mark()) return e;
+        }
+    }
+    // stack input: aatype_to_emb[aatype] (+ latent_to_emb_{f,r}(rel7))
+    if (float* g = t.grad(c->slot.aatype)) launch32_embed_rows_bwd(st.dh, r.aatype, r.B, r.B, r.L, g, s);
+    if (st.rel) {
+        if (float* g = t.grad(st.rel7.w)) step_dw_now(t, dw_op(st.dh, kC, st.rel, 7, Mp, kC, 7, g, nullptr, t.part, t), s);
+        if (float* g = t.grad(st.rel7.b)) launch32_colsum(st.dh, kC, nullptr, 0, nullptr, 0, Mp, kC, Mp, 0.f, g, 0, t.cpart, t.cpart_floats, s);
+    }
+    LAUNCHCHK();
+    return 0;
+}
+
+// the time embedder behind all adaLN heads: d silu_t = d mod . W_ada
+static int time_embedder_bwd(Train& t) {
+    const Run& r = t.r;
+    const mdgen_ctx* c = t.c;
+    hipStream_t s = r.s;
+    const int modld = (int)c->modrow;
+    float* dst = t.dsilu;                         // [B][384]
+    float* emb = dst + (size_t)r.B * kC;          // [B][256]
+    float* h1 = emb + (size_t)r.B * 256;          // [B][384]
+    float* dp1 = h1 + (size_t)r.B * kC;
+    float* dp2 = dp1 + (size_t)r.B * kC;
+    if (!launch32_skinny_wt(t.dmod, modld, c->ada_w, kC, r.B, kC, c->modrow, dst, t.cpart, t.cpart_floats, s)) {
+        LinearParams q = lin_op(t.dmod, modld, c->ada_w, kC, nullptr, r.B, kC, c->modrow, dst, kC);
+        q.wtrans = 1;   // (W_ada as stored)
+        step_linear(q, linear_form(t.bf16, LinShape{q.n, q.m, q.k, q.lda, q.ldw, 1, true, true, false}, false), s);
+    }
+    launch32_temb_bwd(t.tvals, r.B, c->d.time_multiplier, c->t_w0, c->t_b0, c->t_w2, c->t_b2, dst, emb, h1, dp1, dp2, s);
+    if (float* g = t.grad(c->slot.t2.w)) step_dw_now(t, dw_op(dp2, kC, h1, kC, r.B, kC, kC, g, nullptr, t.part, t), s);
+    if (float* g = t.grad(c->slot.t2.b)) launch32_colsum(dp2, kC, nullptr, 0, nullptr, 0, r.B, kC, r.B, 0.f, g, 0, t.cpart, t.cpart_floats, s);
+    if (float* g = t.grad(c->slot.t0.w)) step_dw_now(t, dw_op(dp1, kC, emb, 256, r.B, kC, 256, g, nullptr, t.part, t), s);
+    if (float* g = t.grad(c->slot.t0.b)) launch32_colsum(dp1, kC, nullptr, 0, nullptr, 0, r.B, kC, r.B, 0.f, g, 0, t.cpart, t.cpart_floats, s);
+    LAUNCHCHK();
+    return t.mark();
+}
+
+// backward: final layer, trunk layers, token embedding, IPA streams, time embedder; a milestone (Train::mark) after each group
+static int train_backward(Train& t) {
+    const Run& r = t.r;
+    const mdgen_ctx* c = t.c;
+    HIPCHK(hipMemsetAsync(t.dmod, 0, (size_t)r.B * c->modrow * 4, r.s));
+    if (int e = final_bwd(t)) return e;
+    for (int i = c->nl - 1; i >= 0; --i) {
+        const TrunkW& w = c->trunk[i];
+        const TrunkSites site = trunk_sites(r, i, 0, t.dmod);
+        if (int e = mlp_bwd(t, w.ffn, site.mlp, t.dh, t.tm[i])) return e;
+        if (int e = attn_bwd(t, w.mha_t, site.t, t.dh, t.tt[i])) return e;
+        if (int e = attn_bwd(t, w.mha_l, site.l, t.dh, t.tl[i])) return e;
+        if (int e = ada_head_bwd(t, w.ada, c->trunk_off(i), 9 * kC)) return e;
+        LAUNCHCHK();
+        if (int e = t.mark()) return e;
+    }
+    if (int e = embed_bwd(t)) return e;
+    // IPA stack(s), tokens (b, l): groups of L tokens.  d ipa_out reaches both streams of the two-sided model unchanged.
+    for (int k = 1; k < t.nst; ++k)
+        HIPCHK(hipMemcpyAsync(t.st[k].dh, t.st[0].dh, (size_t)r.Mp * kC * 4, hipMemcpyDeviceToDevice, r.s));
+    for (int k = 0; k < t.nst; ++k)
+        if (int e = ipa_backward(t, t.st[k], k == t.nst - 1)) return e;
+    return time_embedder_bwd(t);
 }
 
 }  // namespace
@@ -696,327 +1029,26 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
     if (!c->opt_keep_fp32 || !c->any_f32()) return fail(-6, "the training step runs on the fp32 weight copies: option keep_fp32_weights");
     Train t;
     t.c = c;
+    t.xt = xt; t.tvals = tvals; t.target = target; t.loss_mask = loss_mask; t.loss = loss; t.pred = pred;
     t.grads = grads;
     t.goff = grad_offsets;
-    const int saved_precision = c->opt_precision;
-    c->opt_precision = 32;
-    struct Restore { mdgen_ctx* c; int p; ~Restore() { c->opt_precision = p; } } restore{c, saved_precision};
     // option train_precision = 16: the linear layers and weight gradients of this call multiply bf16-rounded operands on
     // the bf16 MFMA (fp32 accumulate, fp32 master weights, everything else fp32)
     t.bf16 = c->opt_train_precision == 16;
-    if (int e = make_run(&t.r, c, sh, 1, 0, ws, ws_bytes, stream)) return e;   // (with check_f32_weights: precision is 32 here)
+    if (int e = make_run(&t.r, c, sh, 1, 0, true, ws, ws_bytes, stream)) return e;   // (true: with check_f32_weights)
     Run& r = t.r;
     r.mask = mask; r.start_rot = start_rot; r.start_trans = start_trans; r.end_rot = two ? end_rot : nullptr; r.end_trans = two ? end_trans : nullptr; r.rel7_in = two ? rel7 : nullptr;
     r.x_cond = x_cond; r.x_cond_mask = x_cond_mask; r.aatype = aatype;
     if (((uintptr_t)tape & 255) != 0) return fail(-7, "tape must be 256-byte aligned");
     const size_t need = carve_train(&t, c, r.B, r.T, r.L, (unsigned char*)tape);
     if (tape_bytes < need) return fail(-7, "tape too small: %zu < %zu bytes", tape_bytes, need);
-    hipStream_t s = r.s;
-    // (same priority as the caller's stream: with the second stream at the lowest OR the highest priority of the device's range
-    // the step took 53 / 60 ms instead of 30.7 -- profiles/r04_experiments.txt)
-    // (default stream priority: created with ANY other priority -- lowest or highest -- the step takes 51-54 ms instead of 27.4:
-    // profiles/r06_experiments.txt #19)
-    if (c->opt_train_streams == 2 && !c->train_side) HIPCHK(hipStreamCreateWithFlags(&c->train_side, hipStreamNonBlocking));
-    t.side = c->opt_train_streams == 2 ? c->train_side : nullptr;
-    if (t.side && t.bf16) {
-        if (c->tr_plan_ok && c->tr_buf) {   // every turned weight of the call, on the second stream, beside the forward pass
-            hipEvent_t e0 = t.next_event(), e1 = t.next_event();
-            if (e0 && e1) {
-                HIPCHK(hipEventRecord(e0, (hipStream_t)stream));     // the weights are final on the caller's stream
-                HIPCHK(hipStreamWaitEvent(t.side, e0, 0));
-                for (const mdgen_ctx::TurnReq& q : c->tr_plan)
-                    for (int j = 0; j < q.nseg; ++j)
-                        launch32_transpose(q.w[j], q.rows, q.cols, c->tr_buf + q.off + (size_t)j * q.rows, t.side, q.nseg * q.rows);
-                HIPCHK(hipEventRecord(e1, t.side));
-                t.tr_done = e1;
-                t.tr_use = true;
-            }
-        } else {
-            t.tr_record = true;
-        }
-    }
-    // Join on EVERY exit path: whatever this call has launched on the second stream is ordered before what the caller enqueues next
-    // on its own stream -- also when the call returns an error half-way (a caller that then zeroes or reuses `grads` or the tape
-    // must not race with gradient kernels still running over there).  The error path's own HIP status is not reported twice.
-    struct Join {
-        Train& t;
-        hipStream_t s;
-        bool done = false;
-        int run() {
-            if (done || !t.side) return 0;
-            done = true;
-            hipEvent_t e = t.next_event();
-            if (!e) {   // no event to be had: fall back to a host-side wait for the second stream
-                (void)hipStreamSynchronize(t.side);
-                return 0;
-            }
-            if (hipEventRecord(e, t.side) != hipSuccess || hipStreamWaitEvent(s, e, 0) != hipSuccess) (void)hipStreamSynchronize(t.side);
-            return 0;
-        }
-        ~Join() { (void)run(); }
-    } join{t, s};
-    const int nl = c->nl;
-    const long N = r.N, Mp = r.Mp, TL = (long)r.T * r.L;
-    const long modld = c->modrow;
-
-    // ================= forward (fp32 path, with tape) =================
-    {   // time embedding, adaLN table, compact mask  (as prepare(), per-sample t)
-        float* silu = (float*)(r.ws + r.lay.silu_t);
-        launch_temb(tvals, r.B, c->d.time_multiplier, c->t_w0, c->t_b0, c->t_w2, c->t_b2, silu, s);
-        launch_adaln(silu, r.B, c->ada_w, c->ada_b, c->modrow, r.mod(), s);
-        HIPCHK(hipMemcpy2DAsync(r.ws + r.lay.mask_bl, (size_t)r.L * 4, r.mask, (size_t)r.T * r.L * 4, (size_t)r.L * 4, r.B,
-                                hipMemcpyDeviceToDevice, s));
-        LAUNCHCHK();
-    }
-    float* hi = (float*)(r.ws + r.lay.ipa_out);   // IPA-stack residual stream [B*L][384] (G = B groups)
-    const AxisMap axI{r.B, r.L, r.B, 0, r.L, 1};
-    const MaskMap mkI{(const float*)(r.ws + r.lay.mask_bl), (long)r.B * r.L};
-    // one pass of the IPA stack over `hx` on the frames (rot, trans), taped into (ip, il, im); rel / w7 / b7: the
-    // two-sided model's relative-frame input of this stream (latent_model.py:193-201), null for the one-sided model
-    auto ipa_forward = [&](float* hx, const float* rel, const float* w7, const float* b7, const float* rot, const float* trans,
-                           std::vector<SubTapeIpa>& ips, std::vector<SubTapeAttn>& ils, std::vector<SubTapeMlp>& ims) -> int {
-        launch_ipa_init(c->aa_emb, r.aatype, rel, w7, b7, hx, r.B, r.B, r.L, s);
-        for (int i = 0; i < nl; ++i) {
-            const IpaW& w = c->ipa[i];
-            const auto& p = w.slot;
-            const ModMap mm{r.mod() + c->ipa_off(i), r.L, r.B, r.mod_step_stride, r.mod_group_stride};
-            SubTapeIpa& tp = ips[i];
-            const F32Bufs fb = f32_bufs(r);
-            const Lin lins[4] = {p.q, p.kv, p.q_points, p.kv_points};
-            const bool w_al[5] = {al16(t.w(p.q.w)), al16(t.w(p.kv.w)), al16(t.w(p.q_points.w)), al16(t.w(p.kv_points.w)), al16(t.w(p.out.w))};
-            const IpaPlan& pl = tp.plan = plan_ipa(t, Mp, w_al);
-            HIPCHK(hipMemcpyAsync(tp.h_in, hx, (size_t)Mp * kC * 4, hipMemcpyDeviceToDevice, s));
-            launch32_ln_mod(hx, Mp, ModMap{w.gamma_beta, 1, 1, 0, 0}, 1, 0, 1, 1e-5f, fb.y, s, nullptr, false);
-            for (int j = 0; j < 4; ++j) {
-                LinearParams q = lin_op(fb.y, kC, t.w(lins[j].w), kC, t.w(lins[j].b), Mp, kIpaProjCols[j].m, kC, tp.proj, kIpaProj);
-                q.col0 = kIpaProjCols[j].col0;
-                step_linear(q, pl.proj[j], s);
-            }
-            IpaAttnParams ap{};
-            ap.proj = tp.proj; ap.rot = rot; ap.trans = trans;
-            ap.mask_bl = (const float*)(r.ws + r.lay.mask_bl);
-            ap.head_w = w.head_w; ap.feat = nullptr; ap.feat32 = tp.feat; ap.stats = tp.stats;
-            ap.ngroups = r.B; ap.B = r.B; ap.L = r.L;
-            ap.part = t.part; ap.part_floats = t.part_floats;      // few groups: key loop sliced over workgroups
-            launch_ipa_attn(ap, s);
-            LinearParams lo = lin_op(tp.feat, kIpaFeat, t.w(p.out.w), kIpaFeat, t.w(p.out.b), Mp, kC, kIpaFeat, hx, kC);
-            lo.mode = kLinGated;   // (gated = 0: the ungated residual hx += linear_out(feat))
-            step_linear(lo, pl.out, s);
-            LAUNCHCHK();
-            if (int e = attn_fwd_tape(t, w.mha_l, hx, Mp, axI, mm, 0, 1, 2, mkI, 1, r.L, r.L, ils[i])) return e;
-            if (int e = mlp_fwd_tape(t, w.ffn, hx, Mp, mm, 3, 4, 5, r.L, ims[i])) return e;
-        }
-        return 0;
-    };
-    float* hi2 = (float*)(r.ws + r.lay.h_ipa);
-    const float *rel_f = nullptr, *rel_r = nullptr;
-    if (!two) {
-        if (int e = ipa_forward(hi, nullptr, nullptr, nullptr, r.start_rot, r.start_trans, t.ip, t.il, t.im)) return e;
-    } else {
-        // x_f = (start^-1 o end).to_tensor_7(), x_r = (end^-1 o start).to_tensor_7()   (latent_model.py:194-195)
-        if (r.rel7_in) {   // the caller's own to_tensor_7() outputs (quaternion sign as the reference's eigh chose it)
-            HIPCHK(hipMemcpyAsync(t.rel7, r.rel7_in, (size_t)2 * Mp * 7 * 4, hipMemcpyDeviceToDevice, s));
-        } else {
-            launch_rel7(r.start_rot, r.start_trans, r.end_rot, r.end_trans, t.rel7, Mp, s);
-            launch_rel7(r.end_rot, r.end_trans, r.start_rot, r.start_trans, t.rel7 + Mp * 7, Mp, s);
-            LAUNCHCHK();
-        }
-        rel_f = t.rel7;
-        rel_r = t.rel7 + Mp * 7;
-        // the x_r stream runs on the start frames, the x_f stream on the end frames (latent_model.py:203-205)
-        if (int e = ipa_forward(hi, rel_r, c->wr7, c->br7, r.start_rot, r.start_trans, t.ip, t.il, t.im)) return e;
-        if (int e = ipa_forward(hi2, rel_f, c->wf7, c->bf7, r.end_rot, r.end_trans, t.ip2, t.il2, t.im2)) return e;
-        launch_add_inplace(hi, hi2, Mp * kC, s);
-        LAUNCHCHK();
-    }
-    float* h = r.h();
-    {
-        EmbedParams e{};
-        e.x = xt; e.x_cond = r.x_cond; e.x_cond_mask = r.x_cond_mask;
-        e.wl = c->wl; e.bl = c->bl; e.wc = c->wc; e.bc = c->bc; e.mask_emb = c->mask_emb;
-        e.wl_pack = c->wl_pack; e.wc_pack = c->wc_pack;
-        e.pos_embed = c->d.abs_pos_emb ? c->pos_embed : nullptr;
-        e.ipa_out = hi; e.h = h; e.N = N; e.T = r.T; e.L = r.L; e.D = r.D;
-        launch_embed(e, s);
-        LAUNCHCHK();
-    }
-    const AxisMap axL{r.B * r.T, r.L, r.B * r.T, 0, r.L, 1};
-    const AxisMap axT{r.B * r.L, r.T, r.L, r.T * r.L, 1, r.L};
-    const MaskMap mk{r.mask, 0};
-    t.defer_gate = true;   // the trunk's residual updates ride in the next sub-layer's LayerNorm launch
-    for (int i = 0; i < nl; ++i) {
-        const TrunkW& w = c->trunk[i];
-        const ModMap mm{r.mod() + c->trunk_off(i), r.T * r.L, r.B, 0, r.mod_group_stride};
-        if (int e = attn_fwd_tape(t, w.mha_l, h, N, axL, mm, 0, 1, 2, mk, 1, r.L, TL, t.tl[i])) return e;
-        if (int e = attn_fwd_tape(t, w.mha_t, h, N, axT, mm, 3, 4, 5, mk, r.L, r.T, TL, t.tt[i])) return e;
-        if (int e = mlp_fwd_tape(t, w.ffn, h, N, mm, 6, 7, 8, TL, t.tm[i])) return e;
-    }
-    t.defer_gate = false;
-    flush_pending(t, h);
-    LAUNCHCHK();
-    const ModMap fm{r.mod() + c->final_off(), r.T * r.L, r.B, 0, r.mod_group_stride};
-    const FinalPlan fin = plan_final(t, N, r.D, TL, al16(t.w(c->slot.fin.w)), true);   // (fm: shift chunk 0, scale chunk 1)
-    {
-        const F32Bufs fb = f32_bufs(r);
-        launch32_ln_mod(h, N, fm, 0, 1, 0, 1e-6f, fb.y, s, nullptr, false);
-        step_linear(lin_op(fb.y, kC, t.w(c->slot.fin.w), kC, t.w(c->slot.fin.b), N, r.D, kC, pred, r.D), fin.lin, s);
-        launch_masked_mse(pred, target, loss_mask, loss, TL * r.D, r.B, s, t.cpart, t.cpart_floats);
-        LAUNCHCHK();
-    }
-
-    // ================= backward =================
-    // Milestones: when the gradients of a parameter group are complete the caller's event for it is recorded on the
-    // stream, so that its all-reduce can start on another stream while the rest of the backward pass runs
-    // (mdgen_train_set_milestone_events).  Order: 0 final layer | 1 .. nl trunk layers nl-1 .. 0 | nl+1 token
-    // embedders | nl+2 .. 2nl+1 IPA layers nl-1 .. 0 | 2nl+2 everything (embedding tables, time embedder).
-    int milestone = 0;
-    auto mark = [&]() -> int {
-        if (milestone < (int)c->milestone_events.size() && c->milestone_events[milestone]) {
-            hipStream_t ms = s;
-            if (t.side) {   // the group's gradients come from both streams: the second one waits for the main one and carries the event
-                hipEvent_t e = t.next_event();
-                if (!e) return fail(-8, "hipEventCreate failed (training event pool)");
-                HIPCHK(hipEventRecord(e, s));
-                HIPCHK(hipStreamWaitEvent(t.side, e, 0));
-                ms = t.side;
-            }
-            HIPCHK(hipEventRecord((hipEvent_t)c->milestone_events[milestone], ms));
-        }
-        ++milestone;
-        return 0;
-    };
-    const float* silu_bwd = (const float*)(r.ws + r.lay.silu_t);
-    // adaLN head of one parameter block: mod[b] = W_ada silu_t[b] + b_ada  (its d mod rows are complete once the
-    // block's own backward is done)
-    auto head = [&](const Lin& ada, int off, int rows) -> int {
-        float *gw = t.grad(ada.w), *gb = t.grad(ada.b);
-        hipStream_t sw = s;
-        float *pt = t.part, *cpt = t.cpart;
-        if (gw || gb)   // (the block's d mod rows are complete here and nothing writes them again)
-            if (int e = t.fork(&sw, &pt, &cpt)) return e;
-        if (gw) step_dw_now(t, dw_op(t.dmod + off, (int)modld, silu_bwd, kC, r.B, rows, kC, gw, nullptr, pt, t), sw);
-        if (gb) launch32_colsum(t.dmod + off, (int)modld, nullptr, 0, nullptr, 0, r.B, rows, r.B, 0.f, gb, 0, cpt, t.cpart_floats, sw);
-        return 0;
-    };
-    HIPCHK(hipMemsetAsync(t.dmod, 0, (size_t)r.B * c->modrow * 4, s));
-    if (int e = t.begin_sub()) return e;
-    float* dpred = t.dqkv;   // [N][D] fits the (idle) dqkv scratch
-    launch32_loss_grad(pred, target, loss_mask, TL * r.D, r.B, t.dsilu, dpred, s, t.cpart, t.cpart_floats);   // t.dsilu[0..B) = mask sums (scratch)
-    {   // final layer: out = linear(modulate(LN(h)))
-        launch32_ln_mod(h, N, fm, 0, 1, 0, 1e-6f, t.ytmp, s, nullptr, false);
-        LinBwdOp o{};   // t.dy = d pred W
-        o.dy = dpred; o.ldy = r.D;
-        o.x = t.ytmp; o.ldx = kC;
-        o.dx = t.dy; o.ldx_out = kC;
-        if (int e = lin_bwd(t, c->slot.fin, N, r.D, kC, fin.dx, fin.dw, o)) return e;
-        lnmod_bwd(t, fin.ln, h, t.dy, N, fm, 0, 1, TL, modld, t.dmod + c->final_off(), t.dh, false);
-        if (int e = head(c->slot.fin_ada, c->final_off(), 2 * kC)) return e;
-        LAUNCHCHK();
-        if (int e = t.end_sub()) return e;
-        if (int e = mark()) return e;
-    }
-    for (int i = nl - 1; i >= 0; --i) {
-        const TrunkW& w = c->trunk[i];
-        const ModMap mm{r.mod() + c->trunk_off(i), r.T * r.L, r.B, 0, r.mod_group_stride};
-        float* dm = t.dmod + c->trunk_off(i);
-        if (int e = mlp_bwd(t, w.ffn, t.dh, N, mm, 6, 7, 8, TL, modld, dm, t.tm[i])) return e;
-        if (int e = attn_bwd(t, w.mha_t, t.dh, N, axT, mm, 3, 4, 5, mk, r.L, r.T, TL, modld, dm, t.tt[i])) return e;
-        if (int e = attn_bwd(t, w.mha_l, t.dh, N, axL, mm, 0, 1, 2, mk, 1, r.L, TL, modld, dm, t.tl[i])) return e;
-        if (int e = head(w.ada, c->trunk_off(i), 9 * kC)) return e;
-        LAUNCHCHK();
-        if (int e = mark()) return e;
-    }
-    {   // token embedding (latent_model.py:233-246): h0 = Wl x + bl [+ pos] + Wc x_cond + bc + mask_emb[cm] + ipa_out[b, l]
-        {   // (t.dh is final here: second stream)
-            hipStream_t sw = s;
-            float *pt = t.part, *cpt = t.cpart;
-            if (int e = t.fork(&sw, &pt, &cpt)) return e;
-            if (float* g = t.grad(c->slot.latent.w)) step_dw_now(t, dw_op(t.dh, kC, xt, r.D, N, kC, r.D, g, nullptr, pt, t), sw);
-            if (float* g = t.grad(c->slot.cond.w)) step_dw_now(t, dw_op(t.dh, kC, r.x_cond, r.D, N, kC, r.D, g, nullptr, pt, t), sw);
-            if (float* g = t.grad(c->slot.latent.b)) launch32_colsum(t.dh, kC, nullptr, 0, nullptr, 0, N, kC, N, 0.f, g, 0, cpt, t.cpart_floats, sw);
-            if (float* g = t.grad(c->slot.cond.b)) launch32_colsum(t.dh, kC, nullptr, 0, nullptr, 0, N, kC, N, 0.f, g, 0, cpt, t.cpart_floats, sw);
-        }
-        if (float* g = t.grad(c->slot.mask)) {
-            float* ind0 = t.stats;          // [N] + [N] floats fit the stats scratch (N * 32 floats)
-            float* ind1 = t.stats + N;
-            launch32_indicator(r.x_cond_mask, N, ind0, ind1, s);
-            launch32_colsum(t.dh, kC, nullptr, 0, ind0, 3, N, kC, N, 0.f, g, 0, t.cpart, t.cpart_floats, s);
-            launch32_colsum(t.dh, kC, nullptr, 0, ind1, 3, N, kC, N, 0.f, g + kC, 0, t.cpart, t.cpart_floats, s);
-        }
-        launch32_sum_frames(t.dh, r.B, r.T, r.L, t.dhi, s);    // d ipa_out
-        LAUNCHCHK();
-        if (int e = mark()) return e;
-    }
-    // IPA stack(s), tokens (b, l): groups of L tokens.  d ipa_out reaches both streams of the two-sided model unchanged.
-    if (two) HIPCHK(hipMemcpyAsync(t.dhi2, t.dhi, (size_t)Mp * kC * 4, hipMemcpyDeviceToDevice, s));
-    auto ipa_backward = [&](float* dhx, const float* rel, const Lin& rel7, const float* rot, const float* trans,
-                            const std::vector<SubTapeIpa>& ips, const std::vector<SubTapeAttn>& ils,
-                            const std::vector<SubTapeMlp>& ims, bool last) -> int {
-        for (int i = nl - 1; i >= 0; --i) {
-            const IpaW& w = c->ipa[i];
-            const ModMap mm{r.mod() + c->ipa_off(i), r.L, r.B, r.mod_step_stride, r.mod_group_stride};
-            float* dm = t.dmod + c->ipa_off(i);
-            if (int e = mlp_bwd(t, w.ffn, dhx, Mp, mm, 3, 4, 5, r.L, modld, dm, ims[i])) return e;
-            if (int e = attn_bwd(t, w.mha_l, dhx, Mp, axI, mm, 0, 1, 2, mkI, 1, r.L, r.L, modld, dm, ils[i])) return e;
-            if (int e = ipa_block_bwd(t, w, ips[i], dhx, rot, trans)) return e;
-            if (last) {   // (the two-sided model's first stream leaves this layer's gradients half done)
-                if (int e = head(w.slot.ada, c->ipa_off(i), 6 * kC)) return e;
-                LAUNCHCHK();
-                if (int e = mark()) return e;
-            }
-        }
-        // stack input: aatype_to_emb[aatype] (+ latent_to_emb_{f,r}(rel7))
-        if (float* g = t.grad(c->slot.aatype)) launch32_embed_rows_bwd(dhx, r.aatype, r.B, r.B, r.L, g, s);
-        if (rel) {
-            if (float* g = t.grad(rel7.w)) step_dw_now(t, dw_op(dhx, kC, rel, 7, Mp, kC, 7, g, nullptr, t.part, t), s);
-            if (float* g = t.grad(rel7.b)) launch32_colsum(dhx, kC, nullptr, 0, nullptr, 0, Mp, kC, Mp, 0.f, g, 0, t.cpart, t.cpart_floats, s);
-        }
-        LAUNCHCHK();
-        return 0;
-    };
-    if (!two) {
-        if (int e = ipa_backward(t.dhi, nullptr, Lin{}, r.start_rot, r.start_trans, t.ip, t.il, t.im, true)) return e;
-    } else {
-        if (int e = ipa_backward(t.dhi, rel_r, c->slot.rel_r, r.start_rot, r.start_trans, t.ip, t.il, t.im, false)) return e;
-        if (int e = ipa_backward(t.dhi2, rel_f, c->slot.rel_f, r.end_rot, r.end_trans, t.ip2, t.il2, t.im2, true)) return e;
-    }
-    {   // the time embedder behind all adaLN heads: d silu_t = d mod . W_ada
-        float* dst = t.dsilu;                         // [B][384]
-        float* emb = dst + (size_t)r.B * kC;          // [B][256]
-        float* h1 = emb + (size_t)r.B * 256;          // [B][384]
-        float* dp1 = h1 + (size_t)r.B * kC;
-        float* dp2 = dp1 + (size_t)r.B * kC;
-        if (!launch32_skinny_wt(t.dmod, (int)modld, c->ada_w, kC, r.B, kC, c->modrow, dst, t.cpart, t.cpart_floats, s)) {
-            LinearParams q = lin_op(t.dmod, (int)modld, c->ada_w, kC, nullptr, r.B, kC, c->modrow, dst, kC);
-            q.wtrans = 1;   // (W_ada as stored)
-            step_linear(q, linear_form(t.bf16, LinShape{q.n, q.m, q.k, q.lda, q.ldw, 1, true, true, false}, false), s);
-        }
-        launch32_temb_bwd(tvals, r.B, c->d.time_multiplier, c->t_w0, c->t_b0, c->t_w2, c->t_b2, dst, emb, h1, dp1, dp2, s);
-        if (float* g = t.grad(c->slot.t2.w)) step_dw_now(t, dw_op(dp2, kC, h1, kC, r.B, kC, kC, g, nullptr, t.part, t), s);
-        if (float* g = t.grad(c->slot.t2.b)) launch32_colsum(dp2, kC, nullptr, 0, nullptr, 0, r.B, kC, r.B, 0.f, g, 0, t.cpart, t.cpart_floats, s);
-        if (float* g = t.grad(c->slot.t0.w)) step_dw_now(t, dw_op(dp1, kC, emb, 256, r.B, kC, 256, g, nullptr, t.part, t), s);
-        if (float* g = t.grad(c->slot.t0.b)) launch32_colsum(dp1, kC, nullptr, 0, nullptr, 0, r.B, kC, r.B, 0.f, g, 0, t.cpart, t.cpart_floats, s);
-        LAUNCHCHK();
-    }
-    if (int e = mark()) return e;
-    if (t.tr_use && t.tr_cursor != c->tr_plan.size()) c->tr_plan_ok = false;   // the list was not used up: record anew next call
-    if (t.tr_record) {   // the list for the next call
-        size_t off = 0;
-        for (mdgen_ctx::TurnReq& q : t.tr_new) {
-            q.off = off;
-            off += ((size_t)q.nseg * q.rows * q.cols + 63) & ~(size_t)63;
-        }
-        bool ok = !t.tr_new.empty();
-        if (ok && off > c->tr_buf_floats) {
-            if (c->tr_buf) (void)hipFree(c->tr_buf);
-            c->tr_buf = nullptr;
-            c->tr_buf_floats = 0;
-            if (hipMalloc((void**)&c->tr_buf, off * 4) == hipSuccess) c->tr_buf_floats = off;
-            else { (void)hipGetLastError(); ok = false; }
-        }
-        c->tr_plan = t.tr_new;
-        c->tr_plan_ok = ok;
-    }
+    bind_ipa_streams(t);
+    if (int e = open_side_stream(t)) return e;
+    if (int e = prefetch_turned(t, (hipStream_t)stream)) return e;
+    Join join{t};
+    if (int e = train_forward(t)) return e;
+    if (int e = train_backward(t)) return e;
+    finish_turned(t);
     return join.run();   // (the destructor covers the error returns above)
 }
 
@@ -1172,9 +1204,6 @@ extern "C" int32_t mdgen_debug_train_plan(const mdgen_shape* sh, int32_t tps_con
     const bool w_al[5] = {al, al, al, al, al};
     const bool w4[4] = {al, al, al, al}, w2[2] = {al, al};
     const long B = sh->B, T = sh->T, L = sh->L, N = B * T * L, Mp = B * L, TL = T * L;
-    const AxisMap axI{(int)B, (int)L, (int)B, 0, (int)L, 1};
-    const AxisMap axL{(int)(B * T), (int)L, (int)(B * T), 0, (int)L, 1};
-    const AxisMap axT{(int)(B * L), (int)T, (int)L, (int)(T * L), 1, (int)L};
     PlanJson js{buf, buflen};
     const IpaPlan ip = plan_ipa(t, Mp, w_al);
     js.add("{\"rows\": {\"ipa\": %ld, \"trunk\": %ld}, \"ipa_block\": {\"proj\": [\"%s\", \"%s\", \"%s\", \"%s\"], \"out\": \"%s\"", Mp, N,
@@ -1188,17 +1217,17 @@ extern "C" int32_t mdgen_debug_train_plan(const mdgen_shape* sh, int32_t tps_con
     js.dx("dx_out", ip.dx_out);
     js.dw("dw_out", ip.dw_out);
     js.add("}, ");
-    js.attn("ipa_attn", plan_attn(t, Mp, axI, L, w4, true));
+    js.attn("ipa_attn", plan_attn(t, Mp, axis_ipa(B, L), L, w4));
     js.add(", ");
-    js.mlp("ipa_mlp", plan_mlp(t, Mp, L, w2, true));
+    js.mlp("ipa_mlp", plan_mlp(t, Mp, L, w2));
     js.add(", ");
-    js.attn("trunk_attn_l", plan_attn(t, N, axL, TL, w4, true));
+    js.attn("trunk_attn_l", plan_attn(t, N, axis_res(B, T, L), TL, w4));
     js.add(", ");
-    js.attn("trunk_attn_t", plan_attn(t, N, axT, TL, w4, true));
+    js.attn("trunk_attn_t", plan_attn(t, N, axis_time(B, T, L), TL, w4));
     js.add(", ");
-    js.mlp("trunk_mlp", plan_mlp(t, N, TL, w2, true));
+    js.mlp("trunk_mlp", plan_mlp(t, N, TL, w2));
     // (latent_dim: 21, 28 for the two-sided model -- mdgen_ctx_create's D; every sub-layer's scale chunk lies behind its shift chunk)
-    const FinalPlan fin = plan_final(t, N, tps_condition ? 28 : 21, TL, al, true);
+    const FinalPlan fin = plan_final(t, N, tps_condition ? 28 : 21, TL, al);
     js.add(", \"final\": {\"lin\": \"%s\", \"ln\": \"%s\"", form_name(fin.lin), form_name(fin.ln));
     js.dx("dx", fin.dx);
     js.dw("dw", fin.dw);
