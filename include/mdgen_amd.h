@@ -384,6 +384,30 @@ int32_t mdgen_debug_train_attention(int32_t precision, const float* qkv, int64_t
                                     const float* bias_k, const float* bias_v, const float* inv_freq, const float* dout,
                                     float* out, float* lse, float* dqkv, float* dbias, float* stats, void* stream);
 
+/* Test hook (GPU): the invariant point attention core alone (ipa.py:126-254 between the input projections and linear_out),
+ * forward + backward on raw fp32 device buffers, launched as the training step launches it.  M = ngroups * len token rows;
+ * group g uses the frames and the mask of sample g % nbatch (the sampler runs ngroups = steps * nbatch, the training step
+ * ngroups = nbatch).
+ *   proj[M][672]: linear_q (128: head * 32 + c) | linear_kv (256: head * 64 + [k 32 | v 32]) | linear_q_points (96: x | y | z
+ *   blocks of head * 8 + point) | linear_kv_points (192: x | y | z blocks of head * 16 + [k points 8 | v points 8]);
+ *   rot[nbatch][len][3][3], trans[nbatch][len][3], mask[nbatch][len] (0 = padded residue), head_w[4] (before the softplus);
+ *   part: scratch of part_floats floats for the slices of the key loop (forward [slices][M][4][58], backward
+ *   [slices][M][676]); NULL: one slice.  Fewer floats than the wanted slices need: fewer slices.
+ * Forward: feat[M][256] = o (128) | o_pt.x | o_pt.y | o_pt.z | |o_pt| (32 each), lse[M][4] = log-sum-exp of the logits;
+ *   feat_bf16 (nullable): [M][256] bf16, the same rows from a second launch as the bf16 sampler path makes it (one slice).
+ * Backward (dfeat[M][256] nullable: forward only; needs ngroups == nbatch): dproj[M][672], dhead_w[4] += d head_w (accumulated
+ *   into, as a parameter gradient); bwd_scratch: caller buffer of >= 200 * M floats (dhw[M][4] | the per-query record
+ *   [M][4][49]), NOT carved from `part`.
+ * *fwd_slices, *bwd_slices: the slices launched (bwd 0 without dfeat).  mdgen_debug_ipa_slices (host only, no HIP call): the same two
+ * counts for a shape and scratch size, and *fwd_tiled = 1 where the forward runs the LDS-tiled kernel, 0: one thread per
+ * (query, head).  tests/test_ipa_attention_{cpu,gpu}.py. */
+int32_t mdgen_debug_ipa_attention(const float* proj, const float* rot, const float* trans, const float* mask, const float* head_w,
+                                  int32_t ngroups, int32_t nbatch, int32_t len, float* part, int64_t part_floats,
+                                  const float* dfeat, float* feat, void* feat_bf16, float* lse, float* dproj, float* dhead_w,
+                                  float* bwd_scratch, int32_t* fwd_slices, int32_t* bwd_slices, void* stream);
+int32_t mdgen_debug_ipa_slices(int32_t ngroups, int32_t len, int32_t has_part, int64_t part_floats, int32_t* fwd_slices,
+                               int32_t* bwd_slices, int32_t* fwd_tiled);
+
 /* Host-only (no GPU): the plans of one mdgen_train_forward_backward call -- the kernel form of every launch whose kernel depends on
  * train_precision (16 | 32), the row count, the attention axis or the 16-byte alignment of the weights (weight_misalign_bytes: every
  * weight that many bytes off a 16-byte boundary, as a bound parameter buffer may put them; 0 = aligned).  Writes JSON: {"rows",

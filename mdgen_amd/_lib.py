@@ -16,6 +16,7 @@ EXPORTS = [
     "mdgen_last_error", "mdgen_abi_version", "mdgen_dev_build", "mdgen_ctx_create", "mdgen_ctx_destroy", "mdgen_ctx_set_weight",
     "mdgen_ctx_finalize", "mdgen_ctx_set_option", "mdgen_debug_view_plan", "mdgen_ctx_num_weights", "mdgen_ctx_weight_name", "mdgen_workspace_layout",
     "mdgen_denoiser_forward", "mdgen_sample_euler", "mdgen_rollout_euler", "mdgen_profile_enable", "mdgen_profile_report", "mdgen_profile_phase_trace", "mdgen_debug_dispatch_plan", "mdgen_debug_layout_maps", "mdgen_debug_mlp_stream_table", "mdgen_debug_train_linear", "mdgen_debug_train_dw", "mdgen_debug_train_attention", "mdgen_debug_train_plan",
+    "mdgen_debug_ipa_attention", "mdgen_debug_ipa_slices",
     "mdgen_rigid_compose", "mdgen_rigid_invert",
     "mdgen_rigid_apply", "mdgen_quat_to_rot", "mdgen_rot_to_quat", "mdgen_prep_latents",
     "mdgen_samples_to_atom14", "mdgen_atom14_to_cond", "mdgen_path_plan", "mdgen_masked_mse", "mdgen_from_3_points",
@@ -85,6 +86,8 @@ def _load():
     lib.mdgen_debug_train_dw.argtypes = [i32, vp, i32, vp, i32, i64, i32, i32, vp, vp, vp, i64, vp]
     lib.mdgen_debug_train_attention.argtypes = [i32, vp, i64, i32, i32, i32, i32, i32, i32] + [vp] * 11
     lib.mdgen_debug_train_plan.argtypes = [C.POINTER(Shape), i32, i32, i32, i32, C.c_char_p, sz]
+    lib.mdgen_debug_ipa_attention.argtypes = [vp] * 5 + [i32, i32, i32, vp, i64] + [vp] * 7 + [C.POINTER(i32), C.POINTER(i32), vp]
+    lib.mdgen_debug_ipa_slices.argtypes = [i32, i32, i32, i64] + [C.POINTER(i32)] * 3
     lib.mdgen_rigid_compose.argtypes = [i64] + [vp] * 7
     lib.mdgen_rigid_invert.argtypes = [i64] + [vp] * 5
     lib.mdgen_rigid_apply.argtypes = [i64, i64, vp, vp, vp, vp, i32, vp]

@@ -1169,7 +1169,6 @@ struct IpaBwdParams {
     int nsplit;
     float* part;
 };
-constexpr int kIpaPartRow = kIpaProj + 4;
 
 __global__ __launch_bounds__(256) void k32_ipa_bwd_q(const IpaBwdParams bp) {
     const IpaAttnParams& p = bp.f;
@@ -1458,11 +1457,7 @@ void launch32_ipa_bwd(const IpaAttnParams& f, const float* dfeat, float* dproj, 
     const long nblk = (long)f.ngroups * 4 * nqt;
     const long mtot = (long)f.ngroups * f.L;
     // enough slices for ~64 workgroups, at most one 32-row tile per slice, within the partial buffer
-    int nsplit = (int)((64 + nblk - 1) / nblk);
-    const int ntile = (f.L + 31) / 32;
-    if (nsplit > ntile) nsplit = ntile;
-    if (nsplit > 16) nsplit = 16;
-    while (nsplit > 1 && (!part || (size_t)nsplit * mtot * kIpaPartRow > part_floats)) --nsplit;
+    const int nsplit = ipa_bwd_nsplit(f.ngroups, f.L, part != nullptr, part_floats);
     IpaBwdParams bp{f, dfeat, dproj, dhw, qrec, nsplit, part};
     hipLaunchKernelGGL(k32_ipa_bwd_q, dim3((unsigned)nblk, (unsigned)nsplit), dim3(256), 0, s, bp);
     hipLaunchKernelGGL(k32_ipa_bwd_kv, dim3((unsigned)nblk, (unsigned)nsplit), dim3(256), 0, s, bp);

@@ -795,15 +795,11 @@ void launch_add_inplace(float* dst, const float* src, long n, hipStream_t s) {
     hipLaunchKernelGGL(k_add_inplace, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dst, src, n);
 }
 void launch_ipa_attn(const IpaAttnParams& p, hipStream_t s) {
-    if (p.L >= 24) {   // long sequences: keys staged through LDS, one thread per query
+    if (ipa_attn_tiled(p.L)) {   // long sequences: keys staged through LDS, one thread per query
         const int nqt = (p.L + 255) / 256;
         const long nblk = (long)p.ngroups * 4 * nqt, mtot = (long)p.ngroups * p.L;
         IpaAttnParams q = p;
-        int nsplit = p.part ? (int)((64 + nblk - 1) / nblk) : 1;     // ~64 workgroups, whole 32-key tiles per slice
-        const int ntile = (p.L + kIpaKT - 1) / kIpaKT;
-        if (nsplit > ntile) nsplit = ntile;
-        if (nsplit > 16) nsplit = 16;
-        while (nsplit > 1 && (size_t)nsplit * mtot * 4 * kIpaFwdRec > p.part_floats) --nsplit;
+        const int nsplit = ipa_fwd_nsplit(p.ngroups, p.L, p.part != nullptr, p.part_floats);   // ~64 workgroups, whole 32-key tiles per slice
         q.nsplit = nsplit;
         hipLaunchKernelGGL(k_ipa_attn_tiled, dim3((unsigned)nblk, (unsigned)nsplit), dim3(256), 0, s, q);
         if (nsplit > 1) hipLaunchKernelGGL(k_ipa_attn_merge, dim3((unsigned)((mtot * 4 + 255) / 256)), dim3(256), 0, s, q);

@@ -327,6 +327,29 @@ inline int dw_nsplit(long n, int m, int k, size_t part_floats) {
     while (nsplit > 1 && (size_t)nsplit * m * (k + 1) > part_floats) --nsplit;
     return nsplit;
 }
+// Invariant point attention (launch_ipa_attn, launch32_ipa_bwd): the per-thread kernel below 24 residues, the LDS-tiled one from
+// there; and the slices (blockIdx.y) that the tiled kernels cut their key loop (backward key pass: query loop) into when the
+// groups are few: enough for ~64 workgroups, at most one 32-row tile per slice, at most 16, and no more than part_floats holds
+// partial sums for.  A slice is ceil(tiles / nsplit) WHOLE tiles, so the last slices can lie past L (5 tiles in 4 slices of 2:
+// slice 3 is empty); an empty slice writes the neutral record (forward: m = -3e38, den = 0; backward: zeros).
+inline bool ipa_attn_tiled(int L) { return L >= 24; }
+constexpr int kIpaPartRow = kIpaProj + 4;   // backward partial row: dproj (672) | dhw (4)
+inline int ipa_slices(int ngroups, int L, bool has_part, size_t part_floats, size_t floats_per_slice) {
+    const int nqt = (L + 255) / 256;
+    const long nblk = (long)ngroups * 4 * nqt;
+    int nsplit = has_part ? (int)((64 + nblk - 1) / nblk) : 1;
+    const int ntile = (L + kIpaKT - 1) / kIpaKT;
+    if (nsplit > ntile) nsplit = ntile;
+    if (nsplit > 16) nsplit = 16;
+    while (nsplit > 1 && (size_t)nsplit * floats_per_slice > part_floats) --nsplit;
+    return nsplit;
+}
+inline int ipa_fwd_nsplit(int ngroups, int L, bool has_part, size_t part_floats) {   // part[nsplit][M][4][kIpaFwdRec]
+    return ipa_attn_tiled(L) ? ipa_slices(ngroups, L, has_part, part_floats, (size_t)ngroups * L * 4 * kIpaFwdRec) : 1;
+}
+inline int ipa_bwd_nsplit(int ngroups, int L, bool has_part, size_t part_floats) {   // part[nsplit][M][kIpaPartRow]
+    return ipa_slices(ngroups, L, has_part, part_floats, (size_t)ngroups * L * kIpaPartRow);
+}
 inline DwForm dw_form(bool bf16, const DwShape& q, size_t part_floats, bool x_bf16, bool dy_bf16) {
     if (!bf16) return DwForm::F32;
     if (!dw_vec(q)) return DwForm::Plain;

@@ -1140,6 +1140,61 @@ extern "C" int32_t mdgen_debug_train_attention(int32_t precision, const float* q
     return 0;
 }
 
+// The IPA point attention alone: launch_ipa_attn as ipa_block_fp32 fills it (features in fp32, lse, the split scratch) and
+// launch32_ipa_bwd as ipa_block_bwd does; feat_bf16: a second forward launch as the bf16 sampler path makes it (no scratch)
+extern "C" int32_t mdgen_debug_ipa_slices(int32_t ngroups, int32_t len, int32_t has_part, int64_t part_floats, int32_t* fwd_slices,
+                                          int32_t* bwd_slices, int32_t* fwd_tiled) {
+    if (!fwd_slices || !bwd_slices || !fwd_tiled) return fail(-1, "null argument");
+    if (ngroups < 1 || len < 1 || part_floats < 0) return fail(-2, "ngroups, len >= 1; part_floats >= 0");
+    *fwd_slices = ipa_fwd_nsplit(ngroups, len, has_part != 0, (size_t)part_floats);
+    *bwd_slices = ipa_bwd_nsplit(ngroups, len, has_part != 0, (size_t)part_floats);
+    *fwd_tiled = ipa_attn_tiled(len) ? 1 : 0;
+    return 0;
+}
+extern "C" int32_t mdgen_debug_ipa_attention(const float* proj, const float* rot, const float* trans, const float* mask,
+                                             const float* head_w, int32_t ngroups, int32_t nbatch, int32_t len, float* part,
+                                             int64_t part_floats, const float* dfeat, float* feat, void* feat_bf16, float* lse,
+                                             float* dproj, float* dhead_w, float* bwd_scratch, int32_t* fwd_slices,
+                                             int32_t* bwd_slices, void* stream) {
+    NONNULL(proj, rot, trans, mask, head_w, feat, lse);
+    if (!fwd_slices || !bwd_slices) return fail(-1, "null argument");
+    if (ngroups < 1 || nbatch < 1 || len < 1 || ngroups % nbatch != 0 || part_floats < 0)
+        return fail(-2, "ngroups, nbatch, len >= 1; ngroups a multiple of nbatch; part_floats >= 0");
+    if (dfeat && ngroups != nbatch) return fail(-2, "the backward runs with ngroups == nbatch only (the training step)");
+    if (dfeat) NONNULL(dproj, dhead_w, bwd_scratch);
+    hipStream_t s = (hipStream_t)stream;
+    const long M = (long)ngroups * len;
+    const size_t pf = part ? (size_t)part_floats : 0;
+    IpaAttnParams ap{};
+    ap.proj = proj; ap.rot = rot; ap.trans = trans;
+    ap.mask_bl = mask;
+    ap.head_w = head_w; ap.feat = nullptr; ap.feat32 = feat; ap.stats = lse;
+    ap.ngroups = ngroups; ap.B = nbatch; ap.L = len;
+    ap.part = part; ap.part_floats = pf;
+    *fwd_slices = ipa_fwd_nsplit(ngroups, len, part != nullptr, pf);
+    *bwd_slices = dfeat ? ipa_bwd_nsplit(ngroups, len, part != nullptr, pf) : 0;
+    launch_ipa_attn(ap, s);
+    if (feat_bf16) {
+        IpaAttnParams bp{};
+        bp.proj = proj; bp.rot = rot; bp.trans = trans;
+        bp.mask_bl = mask;
+        bp.head_w = head_w;
+        bp.feat = (__bf16*)feat_bf16;
+        bp.ngroups = ngroups; bp.B = nbatch; bp.L = len;
+        launch_ipa_attn(bp, s);
+    }
+    if (dfeat) {
+        IpaAttnParams bp{};   // as ipa_block_bwd fills it: the forward's tape, no forward scratch
+        bp.proj = proj; bp.rot = rot; bp.trans = trans;
+        bp.mask_bl = mask;
+        bp.head_w = head_w; bp.feat = nullptr; bp.feat32 = feat; bp.stats = lse;
+        bp.ngroups = ngroups; bp.B = nbatch; bp.L = len;
+        launch32_ipa_bwd(bp, dfeat, dproj, bwd_scratch, bwd_scratch + M * 4, dhead_w, s, part, pf);
+    }
+    LAUNCHCHK();
+    return 0;
+}
+
 // ---- the plans of a step, host only ---------------------------------------------------------------------------------------
 namespace {
 const char* form_name(LinearForm f) {
