@@ -302,6 +302,30 @@ int32_t mdgen_rollout_euler(mdgen_ctx* ctx, const mdgen_shape* shape, int32_t n_
                             const mdgen_residue_tables* tables, float* atom14,
                             void* workspace, size_t workspace_bytes, int32_t use_graph, void* stream);
 
+/* Trajectory upsampling: the window loop of `upsampling_inference.py:47-82` around `NewMDGenWrapper.inference`
+ * (`wrapper.py:283-365` prep_batch with --cond_interval, `:405-484` inference) in ONE call and -- with use_graph -- one
+ * hipGraph.  The B windows of a call are independent samples (windows are the batch axis); per window
+ *     x_cond, x_cond_mask, start frames = key frames at t = k * cond_interval, relative to key frame 0   (mdgen_prep_keyframes)
+ *     samples = Euler(zs, model(., start_frames = key frame 0))            (wrapper.py:439-447; exactly as mdgen_sample_euler)
+ *     atom14  = frames_torsions_to_atom14(key frame 0 o offsets, torsions)  (wrapper.py:456-478)
+ * The preparation is part of the graph and ordered before the sub-batch streams fork: a replay with new key frames in the
+ * same buffers gives new results.  Forward-simulation models only (sim_condition, latent_dim 21).
+ *   zs            (B, T, L, 21) fp32: noise on entry, samples[-1] on exit
+ *   mask          (B, T, L) fp32;  seqres (B, L) int64
+ *   key_*         K = ceil(T / cond_interval) key frames: rots (B,K,L,3,3), trans (B,K,L,3), torsions (B,K,L,7,2)
+ *   x_cond (B,T,L,21) fp32, x_cond_mask (B,T,L) int64, start_rot (B,L,3,3), start_trans (B,L,3)   caller-owned scratch
+ *   atom14        (B, T, L, 14, 3) fp32 out
+ * workspace: as mdgen_sample_euler (mdgen_workspace_layout with n_steps, t_shared = 1).
+ * Returns -1 for a null pointer; -2 for cond_interval < 1, a two-sided (tps_condition) context or a shape the sampler
+ * refuses -- all decided before any device call. */
+int32_t mdgen_upsample_euler(mdgen_ctx* ctx, const mdgen_shape* shape, int32_t n_steps, int32_t cond_interval,
+                             float* zs, const float* mask,
+                             const float* key_rots, const float* key_trans, const float* key_torsions,
+                             const int64_t* seqres,
+                             float* x_cond, int64_t* x_cond_mask, float* start_rot, float* start_trans,
+                             const mdgen_residue_tables* tables, float* atom14,
+                             void* workspace, size_t workspace_bytes, int32_t use_graph, void* stream);
+
 /* ---- measurement ----------------------------------------------------------------------------
  * Per-kernel-class timing with hipEvents recorded on the launch stream (bench.py's roofline leg).
  * While enabled, launches are bracketed by event pairs and hipGraph capture/replay is bypassed.
@@ -442,6 +466,19 @@ int32_t mdgen_from_3_points(int64_t n, const float* p_neg_x, const float* origin
 int32_t mdgen_prep_latents(const mdgen_shape* shape, int32_t tps, int32_t cond_interval, const float* rots, const float* trans,
                            const float* torsions, float* latents, float* x_cond, int64_t* x_cond_mask,
                            void* stream);
+
+/* Key-frame conditioning of the upsampling models: what `split_batch` (upsampling_inference.py:47-66) + `prep_batch` with
+ * --cond_interval (wrapper.py:304-309, 327, 343-344, 362) give, from the key frames alone.  With K = ceil(T / cond_interval)
+ * key frames key_rots (B,K,L,3,3), key_trans (B,K,L,3), key_torsions (B,K,L,7,2), key frame k standing at t = k * cond_interval:
+ *   x_cond (B,T,L,21)      row t = k * cond_interval: [quat(w>=0) of R_0^T R_k | R_0^T (t_k - t_0) | torsions(14)]; other rows 0
+ *   x_cond_mask (B,T,L)    int64, (t % cond_interval == 0)
+ *   start_rot (B,L,3,3), start_trans (B,L,3)   contiguous copies of key frame 0
+ * The offsets are the arithmetic of mdgen_prep_latents (one device function).  cond_interval >= T: K = 1, the plain
+ * forward-simulation conditioning; T need not be a multiple of cond_interval.  -1: null pointer; -2: cond_interval < 1 or a
+ * dimension < 1. */
+int32_t mdgen_prep_keyframes(const mdgen_shape* shape, int32_t cond_interval,
+                             const float* key_rots, const float* key_trans, const float* key_torsions,
+                             float* x_cond, int64_t* x_cond_mask, float* start_rot, float* start_trans, void* stream);
 
 /* `NewMDGenWrapper.inference` tail (wrapper.py:456-478) + `geometry.frames_torsions_to_atom14`
  * (geometry.py:61-79, 236-334): samples (B,T,L,D) + first-frame rigids (rot0 (B,L,3,3), trans0

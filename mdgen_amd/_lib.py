@@ -18,7 +18,7 @@ EXPORTS = [
     "mdgen_denoiser_forward", "mdgen_sample_euler", "mdgen_rollout_euler", "mdgen_profile_enable", "mdgen_profile_report", "mdgen_profile_phase_trace", "mdgen_debug_dispatch_plan", "mdgen_debug_layout_maps", "mdgen_debug_mlp_stream_table", "mdgen_debug_train_linear", "mdgen_debug_train_dw", "mdgen_debug_train_attention", "mdgen_debug_train_plan",
     "mdgen_debug_ipa_attention", "mdgen_debug_ipa_slices",
     "mdgen_rigid_compose", "mdgen_rigid_invert",
-    "mdgen_rigid_apply", "mdgen_quat_to_rot", "mdgen_rot_to_quat", "mdgen_prep_latents",
+    "mdgen_rigid_apply", "mdgen_quat_to_rot", "mdgen_rot_to_quat", "mdgen_prep_latents", "mdgen_prep_keyframes", "mdgen_upsample_euler",
     "mdgen_samples_to_atom14", "mdgen_atom14_to_cond", "mdgen_path_plan", "mdgen_masked_mse", "mdgen_from_3_points",
     "mdgen_grad_sumsq", "mdgen_adam_step", "mdgen_ema_update", "mdgen_train_workspace_bytes",
     "mdgen_train_forward_backward",
@@ -76,6 +76,7 @@ def _load():
     lib.mdgen_dopri5_workspace_bytes.argtypes = [vp, C.POINTER(Shape), C.POINTER(sz)]
     lib.mdgen_debug_dopri5_controller.argtypes = [vp, vp, i32, i32] + [vp] * 7
     lib.mdgen_rollout_euler.argtypes = [vp, C.POINTER(Shape), i32, i32] + [vp] * 8 + [C.POINTER(ResidueTables), vp, vp, sz, i32, vp]
+    lib.mdgen_upsample_euler.argtypes = [vp, C.POINTER(Shape), i32, i32] + [vp] * 10 + [C.POINTER(ResidueTables), vp, vp, sz, i32, vp]
     lib.mdgen_profile_enable.argtypes = [vp, i32]
     lib.mdgen_profile_phase_trace.argtypes = [vp, vp, i64]
     lib.mdgen_profile_report.argtypes = [vp, vp, C.c_char_p, sz]
@@ -94,6 +95,7 @@ def _load():
     lib.mdgen_quat_to_rot.argtypes = [i64, vp, i32, vp, vp]
     lib.mdgen_rot_to_quat.argtypes = [i64, vp, vp, vp]
     lib.mdgen_prep_latents.argtypes = [C.POINTER(Shape), i32, i32] + [vp] * 7
+    lib.mdgen_prep_keyframes.argtypes = [C.POINTER(Shape), i32] + [vp] * 8
     lib.mdgen_samples_to_atom14.argtypes = [C.POINTER(Shape), i32, i32] + [vp] * 10
     lib.mdgen_atom14_to_cond.argtypes = [i32, i32] + [vp] * 11
     lib.mdgen_from_3_points.argtypes = [i64] + [vp] * 6

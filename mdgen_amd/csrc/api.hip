@@ -2046,6 +2046,55 @@ extern "C" int32_t mdgen_rollout_euler(mdgen_ctx* c, const mdgen_shape* sh, int3
     return replay_or_capture(c, key, r.s, body);
 }
 
+// Trajectory upsampling (upsampling_inference.py:47-82 around wrapper.py:283-365, 405-484) as ONE call / ONE hipGraph:
+//   key frames (B, K, L) -> x_cond, x_cond_mask, start frames (k_prep_keyframes; no (B, T, L) window of zeros on the way)
+//   -> S Euler steps exactly as mdgen_sample_euler runs them -> atom14 relative to key frame 0.
+// The preparation kernel is enqueued on the call's stream ahead of euler_body, whose fork event is recorded after it: every
+// sub-batch stream sees the conditioning of THIS call, also when the graph is replayed on new key frames in the same buffers.
+extern "C" int32_t mdgen_upsample_euler(mdgen_ctx* c, const mdgen_shape* sh, int32_t S, int32_t cond_interval, float* zs,
+                                        const float* mask, const float* key_rots, const float* key_trans,
+                                        const float* key_torsions, const int64_t* seqres, float* x_cond, int64_t* x_cond_mask,
+                                        float* start_rot, float* start_trans, const mdgen_residue_tables* tb, float* atom14,
+                                        void* ws, size_t ws_bytes, int32_t use_graph, void* stream) {
+    if (!zs || !mask || !key_rots || !key_trans || !key_torsions || !seqres || !x_cond || !x_cond_mask || !start_rot ||
+        !start_trans || !tb || !atom14)
+        return fail(-1, "null tensor argument");
+    if (!tb->default_frames || !tb->lit_positions || !tb->atom14_group || !tb->atom14_mask) return fail(-1, "null residue table");
+    if (cond_interval < 1) return fail(-2, "cond_interval must be >= 1");
+    if (c && c->d.tps_condition) return fail(-2, "upsampling is defined for forward-simulation models (sim_condition)");
+    Run r{};
+    if (int e = make_run(&r, c, sh, S, 1, f32_path(c), ws, ws_bytes, stream)) return e;
+    r.mask = mask;
+    r.start_rot = start_rot;
+    r.start_trans = start_trans;
+    r.end_rot = nullptr;
+    r.end_trans = nullptr;
+    r.x_cond = x_cond;
+    r.x_cond_mask = x_cond_mask;
+    r.aatype = seqres;
+    std::vector<float> tg;
+    linspace01(S + 1, &tg);
+    const mdgen_residue_tables t = *tb;
+    auto body = [&]() -> int {
+        launch_prep_keyframes(r.B, r.T, r.L, cond_interval, key_rots, key_trans, key_torsions, x_cond, x_cond_mask, start_rot,
+                              start_trans, r.s);
+        LAUNCHCHK();
+        if (int e = euler_body(r, tg, zs)) return e;
+        launch_samples_to_atom14(r.B, r.T, r.L, r.D, 0, zs, start_rot, start_trans, seqres, t.default_frames, t.lit_positions,
+                                 t.atom14_group, t.atom14_mask, atom14, r.T, 0, r.s);
+        LAUNCHCHK();
+        return 0;
+    };
+    if (!use_graph || c->prof_on) return body();
+    std::vector<uint64_t> key = {2u, (uint64_t)sh->B, (uint64_t)sh->T, (uint64_t)sh->L, (uint64_t)S, (uint64_t)cond_interval,
+                                 (uint64_t)zs, (uint64_t)mask, (uint64_t)key_rots, (uint64_t)key_trans,
+                                 (uint64_t)key_torsions, (uint64_t)seqres, (uint64_t)x_cond, (uint64_t)x_cond_mask,
+                                 (uint64_t)start_rot, (uint64_t)start_trans, (uint64_t)atom14, (uint64_t)ws,
+                                 (uint64_t)n_streams(r), graph_option_key(c), (uint64_t)t.default_frames,
+                                 (uint64_t)t.lit_positions, (uint64_t)t.atom14_group, (uint64_t)t.atom14_mask};
+    return replay_or_capture(c, key, r.s, body);
+}
+
 #include "ode.inc"
 
 // ---------------------------------------------------------------------------------------------
@@ -2253,6 +2302,18 @@ extern "C" int32_t mdgen_prep_latents(const mdgen_shape* sh, int32_t tps, int32_
     if (cond_interval < 0) return fail(-2, "cond_interval must be >= 0 (0 = none)");
     launch_prep_latents(sh->B, sh->T, sh->L, tps, 0, cond_interval, rots, trans, torsions, latents, x_cond, x_cond_mask,
                         (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
+extern "C" int32_t mdgen_prep_keyframes(const mdgen_shape* sh, int32_t cond_interval, const float* key_rots,
+                                        const float* key_trans, const float* key_torsions, float* x_cond,
+                                        int64_t* x_cond_mask, float* start_rot, float* start_trans, void* stream) {
+    if (!sh) return fail(-1, "null shape");
+    NONNULL(key_rots, key_trans, key_torsions, x_cond, x_cond_mask, start_rot, start_trans);
+    if (sh->B < 1 || sh->T < 1 || sh->L < 1) return fail(-2, "B, T, L must be >= 1");
+    if (cond_interval < 1) return fail(-2, "cond_interval must be >= 1");
+    launch_prep_keyframes(sh->B, sh->T, sh->L, cond_interval, key_rots, key_trans, key_torsions, x_cond, x_cond_mask, start_rot,
+                          start_trans, (hipStream_t)stream);
     LAUNCHCHK();
     return 0;
 }

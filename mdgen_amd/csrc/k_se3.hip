@@ -262,6 +262,25 @@ __global__ void k_rel7(const float* r1, const float* t1, const float* r2, const 
     for (int k = 0; k < 3; ++k) out7[i * 7 + 4 + k] = tt[k];
 }
 
+// get_offsets (utils.py:7-14) of one frame: ref^-1 o rigid as [quat (w >= 0) | trans], ref = (R0, t0), rigid = (R, tt).
+// The ONE place this arithmetic lives: k_prep_latents and k_prep_keyframes both call it, so their rows agree bit for bit.
+__device__ __forceinline__ void frame_offset7(const float* R0, const float* t0, const float* R, const float* tt, float* o7) {
+    float R0t[9];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) R0t[3 * a + c] = R0[3 * c + a];
+    float Rr[9], it[3], d[3], q[4];
+    matmul3(R0t, R, Rr);
+    matTvec3(R0, t0, it);   // R0^T t0   (invert: -R0^T t0)
+    matvec3(R0t, tt, d);    // R0^T t
+    rot2quat(Rr, q);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o7[k] = q[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o7[4 + k] = d[k] - it[k];
+}
+
 // NewMDGenWrapper.prep_batch latents (wrapper.py:298-327,339-342,362) + get_offsets (utils.py:7-14)
 // BCAST: rots / trans / tors hold ONE frame per (b, l) that stands for every t (the rollout's conditioning frame
 // expanded over T, sim_inference.py:72-79) -- same arithmetic on the same values, without materialising the copies.
@@ -289,20 +308,7 @@ __global__ void k_prep_latents(int B, int T, int L, int tps, int bcast, int cond
         load_rot(rots + j * 9, R0);
 #pragma unroll
         for (int k = 0; k < 3; ++k) t0[k] = trans[j * 3 + k];
-        float R0t[9];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) R0t[3 * a + c] = R0[3 * c + a];
-        float Rr[9], it[3], d[3], q[4];
-        matmul3(R0t, R, Rr);
-        matTvec3(R0, t0, it);   // R0^T t0   (invert: -R0^T t0)
-        matvec3(R0t, tt, d);    // R0^T t
-        rot2quat(Rr, q);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) lat[ref * 7 + k] = q[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) lat[ref * 7 + 4 + k] = d[k] - it[k];
+        frame_offset7(R0, t0, R, tt, lat + ref * 7);
     }
     const int toff = tps ? 14 : 7;
 #pragma unroll
@@ -313,6 +319,47 @@ __global__ void k_prep_latents(int B, int T, int L, int tps, int bcast, int cond
         x_cond[i * D + k] = cond ? lat[k] : 0.f;
     }
     x_cond_mask[i] = cond ? 1 : 0;
+}
+
+// Key-frame conditioning of the upsampling models (upsampling_inference.py:47-66 + wrapper.py:304-309, 327, 343-344, 362) without
+// the (B, T, L) window of zeros and identity rotations: the key frames arrive as (B, K, L, ...) with K = ceil(T / cond_interval),
+// key frame k stands at t = k * cond_interval.  x_cond rows at those t: [offset to key frame 0 | torsions]; every other row 0.
+// start_rot / start_trans: contiguous copies of key frame 0 (what the IPA stack and k_samples_to_atom14 read).
+__global__ void k_prep_keyframes(int B, int T, int L, int K, int cond_interval, const float* key_rots, const float* key_trans,
+                                 const float* key_tors, float* x_cond, int64_t* x_cond_mask, float* start_rot, float* start_trans) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long N = (long)B * T * L;
+    if (i >= N) return;
+    const int l = (int)(i % L);
+    const int t = (int)((i / L) % T);
+    const int b = (int)(i / ((long)L * T));
+    const bool cond = t % cond_interval == 0;
+    x_cond_mask[i] = cond ? 1 : 0;
+    if (!cond) {
+        for (int k = 0; k < 21; ++k) x_cond[i * 21 + k] = 0.f;
+        return;
+    }
+    const long j0 = ((long)b * K) * L + l;                          // key frame 0 of this (b, l)
+    const long src = ((long)b * K + t / cond_interval) * L + l;     // t / cond_interval <= (T - 1) / cond_interval = K - 1
+    float R0[9], t0[3], R[9], tt[3], lat[21];
+    load_rot(key_rots + j0 * 9, R0);
+    load_rot(key_rots + src * 9, R);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        t0[k] = key_trans[j0 * 3 + k];
+        tt[k] = key_trans[src * 3 + k];
+    }
+    frame_offset7(R0, t0, R, tt, lat);
+#pragma unroll
+    for (int k = 0; k < 14; ++k) lat[7 + k] = key_tors[src * 14 + k];
+    for (int k = 0; k < 21; ++k) x_cond[i * 21 + k] = lat[k];
+    if (t == 0) {
+        const long o = (long)b * L + l;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) start_rot[o * 9 + k] = R0[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) start_trans[o * 3 + k] = t0[k];
+    }
 }
 
 // inference() tail (wrapper.py:456-478) + frames_torsions_to_atom14 (geometry.py:61-79,236-334)
@@ -497,6 +544,14 @@ void launch_prep_latents(int B, int T, int L, int tps, int bcast, int cond_inter
                          const float* tors, float* latents, float* x_cond, int64_t* x_cond_mask, hipStream_t s) {
     const long n = (long)B * T * L;
     hipLaunchKernelGGL(k_prep_latents, GRID1D(n), B, T, L, tps, bcast, cond_interval, rots, trans, tors, latents, x_cond, x_cond_mask);
+}
+void launch_prep_keyframes(int B, int T, int L, int cond_interval, const float* key_rots, const float* key_trans,
+                           const float* key_tors, float* x_cond, int64_t* x_cond_mask, float* start_rot, float* start_trans,
+                           hipStream_t s) {
+    const long n = (long)B * T * L;
+    const int K = (int)(((long)T + cond_interval - 1) / cond_interval);
+    hipLaunchKernelGGL(k_prep_keyframes, GRID1D(n), B, T, L, K, cond_interval, key_rots, key_trans, key_tors, x_cond, x_cond_mask,
+                       start_rot, start_trans);
 }
 void launch_samples_to_atom14(int B, int T, int L, int D, int tps, const float* samples, const float* rot0,
                               const float* trans0, const int64_t* seqres, const float* default_frames,

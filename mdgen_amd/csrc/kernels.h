@@ -544,6 +544,9 @@ void launch_from_3_points(long n, const float* pnx, const float* org, const floa
 void launch_rot_to_quat(long n, const float* rot, float* q, hipStream_t s);
 void launch_prep_latents(int B, int T, int L, int tps, int bcast, int cond_interval, const float* rots, const float* trans,
                          const float* tors, float* latents, float* x_cond, int64_t* x_cond_mask, hipStream_t s);
+void launch_prep_keyframes(int B, int T, int L, int cond_interval, const float* key_rots, const float* key_trans,
+                           const float* key_tors, float* x_cond, int64_t* x_cond_mask, float* start_rot, float* start_trans,
+                           hipStream_t s);
 void launch_samples_to_atom14(int B, int T, int L, int D, int tps, const float* samples, const float* rot0,
                               const float* trans0, const int64_t* seqres, const float* default_frames,
                               const float* lit_positions, const int64_t* atom14_group, const float* atom14_mask,

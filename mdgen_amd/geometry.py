@@ -46,6 +46,31 @@ def samples_to_atom14(samples, rot0, trans0, seqres, tps: bool):
     return out
 
 
+def prep_keyframes(key_rots, key_trans, key_torsions, num_frames: int, cond_interval: int):
+    """`mdgen_prep_keyframes`: the conditioning of an upsampling window from its key frames alone (upsampling_inference.py:47-66
+    + wrapper.py:304-309, 343-344).  key_* (B,K,L,...) with K = ceil(num_frames / cond_interval) -> dict(x_cond (B,T,L,21),
+    x_cond_mask (B,T,L) int64, start_rot (B,L,3,3), start_trans (B,L,3))."""
+    require_cuda(key_rots, key_trans, key_torsions)
+    T, c = int(num_frames), int(cond_interval)
+    if T < 1 or c < 1:
+        raise L.MdgenError(f"num_frames and cond_interval must be >= 1, got {num_frames}, {cond_interval}")
+    B, K, L_ = key_trans.shape[:3]
+    if K != -(-T // c) or tuple(key_rots.shape) != (B, K, L_, 3, 3) or tuple(key_torsions.shape) != (B, K, L_, 7, 2) or \
+            tuple(key_trans.shape) != (B, K, L_, 3):
+        raise L.MdgenError(f"key frames must be (B,K,L,...) with K = ceil({T} / {c}) = {-(-T // c)}: got rots "
+                           f"{tuple(key_rots.shape)}, trans {tuple(key_trans.shape)}, torsions {tuple(key_torsions.shape)}")
+    r = key_rots.to(torch.float32).contiguous()
+    t = key_trans.to(torch.float32).contiguous()
+    a = key_torsions.to(torch.float32).contiguous()
+    dev = r.device
+    out = {"x_cond": torch.empty(B, T, L_, 21, device=dev), "x_cond_mask": torch.empty(B, T, L_, dtype=torch.int64, device=dev),
+           "start_rot": torch.empty(B, L_, 3, 3, device=dev), "start_trans": torch.empty(B, L_, 3, device=dev)}
+    sh = L.Shape(B, T, L_)
+    launch(lib.mdgen_prep_keyframes, r, C.byref(sh), c, ptr(r), ptr(t), ptr(a), ptr(out["x_cond"]), ptr(out["x_cond_mask"]),
+           ptr(out["start_rot"]), ptr(out["start_trans"]))
+    return out
+
+
 def atom14_to_cond(atom14, seqres):
     """sim_inference.py:91-96: atom14 (B,L,14,3) -> dict(rots (B,L,3,3), trans (B,L,3), torsions (B,L,7,2),
     torsion_mask (B,L,7)) -- `atom14_to_frames` (geometry.py:218-231) and `atom37_to_torsions`

@@ -410,3 +410,74 @@ class LatentMDGenModel:
                 cur.wait_stream(self._side)
         nxt = {"rots": stg["rots"].clone(), "trans": stg["trans"].clone(), "torsions": stg["tors"].clone()}
         return stg["atom14"].clone(), stg["zs"].clone(), nxt
+
+    # ---- trajectory upsampling ---------------------------------------------------------------
+    def upsample_euler(self, zs, num_steps: int, cond_interval: int, mask, key_rots, key_trans, key_torsions, seqres, tables,
+                       use_graph: bool = True):
+        """`mdgen_upsample_euler`: key-frame conditioning -> S Euler steps -> atom14 in one call (one hipGraph).  zs (B,T,L,D)
+        noise, one window per batch element; mask (B,T,L); key_* the K = ceil(T / cond_interval) key frames of every window,
+        (B,K,L,...); seqres (B,L) int64; tables: dict of residue tables on the device (geometry.residue_tables).
+        Returns (atom14 (B,T,L,14,3), samples (B,T,L,D))."""
+        if self._pre_run is not None:
+            self._pre_run()
+        if self.cfg.tps_condition:
+            raise L.MdgenError("upsample_euler is defined for forward-simulation models (sim_condition)")
+        if zs.dim() != 4 or zs.shape[-1] != self.cfg.latent_dim:
+            raise L.MdgenError(f"zs must be (B,T,L,{self.cfg.latent_dim}), got {tuple(zs.shape)}")
+        B, T, L_, D = zs.shape
+        c = int(cond_interval)
+        if c < 1:
+            raise L.MdgenError(f"cond_interval must be >= 1, got {cond_interval}")
+        K = -(-T // c)
+        if tuple(key_rots.shape) != (B, K, L_, 3, 3) or tuple(key_trans.shape) != (B, K, L_, 3) or \
+                tuple(key_torsions.shape) != (B, K, L_, 7, 2):
+            raise L.MdgenError(f"key frames must be (B,K,L,...) with K = ceil(T / cond_interval) = {K}: got rots "
+                               f"{tuple(key_rots.shape)}, trans {tuple(key_trans.shape)}, torsions {tuple(key_torsions.shape)}")
+        if tuple(mask.shape) != (B, T, L_):
+            raise L.MdgenError(f"mask must be (B,T,L)={B, T, L_}, got {tuple(mask.shape)}")
+        require_cuda(zs, mask, key_rots, key_trans, key_torsions, seqres)
+        S = int(num_steps)
+        ws = self._workspace(B, T, L_, S, True)
+        key = ("upsample", B, T, L_, c)
+        stg = self._stage.get(key)
+        if stg is not None:
+            self._stage.move_to_end(key)
+        else:
+            while len(self._stage) >= self.max_cached_shapes:
+                self._stage.popitem(last=False)
+            dev = self.device
+            stg = dict(zs=torch.empty(B, T, L_, D, device=dev), mask=torch.empty(B, T, L_, device=dev),
+                       rots=torch.empty(B, K, L_, 3, 3, device=dev), trans=torch.empty(B, K, L_, 3, device=dev),
+                       tors=torch.empty(B, K, L_, 7, 2, device=dev), seqres=torch.empty(B, L_, dtype=torch.int64, device=dev),
+                       x_cond=torch.empty(B, T, L_, D, device=dev),
+                       x_cond_mask=torch.empty(B, T, L_, dtype=torch.int64, device=dev),
+                       sr=torch.empty(B, L_, 3, 3, device=dev), st=torch.empty(B, L_, 3, device=dev),
+                       atom14=torch.empty(B, T, L_, 14, 3, device=dev))
+            self._stage[key] = stg
+        stg["zs"].copy_(zs)
+        stg["mask"].copy_(mask)
+        stg["rots"].copy_(key_rots)
+        stg["trans"].copy_(key_trans)
+        stg["tors"].copy_(key_torsions)
+        stg["seqres"].copy_(seqres)
+        tb = L.ResidueTables(*[tables[n].data_ptr() for n in (
+            "default_frames", "lit_positions", "atom14_group", "atom14_mask", "atom37_to_atom14", "atom37_mask",
+            "chi_atom_indices", "chi_angles_mask")])
+        sh = L.Shape(B, T, L_)
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream()
+            if use_graph:
+                if self._side is None:
+                    self._side = torch.cuda.Stream(device=self.device)
+                self._side.wait_stream(cur)
+                stream = self._side
+            else:
+                stream = cur
+            check(lib.mdgen_upsample_euler(
+                self._ctx, C.byref(sh), S, c, ptr(stg["zs"]), ptr(stg["mask"]), ptr(stg["rots"]), ptr(stg["trans"]),
+                ptr(stg["tors"]), ptr(stg["seqres"]), ptr(stg["x_cond"]), ptr(stg["x_cond_mask"]), ptr(stg["sr"]),
+                ptr(stg["st"]), C.byref(tb), ptr(stg["atom14"]), ptr(ws), ws.numel(), int(use_graph),
+                C.c_void_p(stream.cuda_stream)))
+            if use_graph:
+                cur.wait_stream(self._side)
+        return stg["atom14"].clone(), stg["zs"].clone()

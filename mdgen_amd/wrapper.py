@@ -14,7 +14,7 @@ import torch
 from . import _lib as L
 from ._lib import lib, launch, ptr, require_cuda
 from .config import ModelConfig
-from .geometry import samples_to_atom14
+from .geometry import prep_keyframes, samples_to_atom14
 from .model import LatentMDGenModel
 from .rigid_utils import Rigid, Rotation
 from .transport import Sampler, create_transport
@@ -203,6 +203,61 @@ class NewMDGenWrapper:
         aa_out = batch["seqres"][:, None].expand(B, T, L_)
         self.last_samples = samples
         return atom14, aa_out
+
+    def upsample(self, batch, num_frames=None, zs=None, num_steps=None, use_graph=True, sampling_method=None, atol=1e-6,
+                 rtol=1e-3):
+        """Trajectory upsampling: sample the frames between key frames stored every `args.cond_interval` frames
+        (upsampling_inference.py:47-82 around `inference`, wrapper.py:405-484).  `batch` holds KEY FRAMES only, one window per
+        batch element: torsions (B,K,L,7,2), trans (B,K,L,3), rots (B,K,L,3,3), seqres (B,L), mask (B,L), with
+        K = ceil(T / cond_interval) and T = `num_frames` (default `args.num_frames`); key frame k is frame k * cond_interval of
+        its window.  Euler: one library call (`mdgen_upsample_euler`, one hipGraph).  `sampling_method="dopri5"`:
+        `mdgen_prep_keyframes` -> `sample_dopri5` -> `samples_to_atom14`, counts in `last_stats`.  The solver rules are
+        `inference()`'s.  Returns (atom14 (B,T,L,14,3), aa_out (B,T,L)); the latent samples are kept in `last_samples`."""
+        from .geometry import residue_tables
+        c = getattr(self.args, "cond_interval", None)
+        if not c:
+            raise L.MdgenError("upsample() needs a model trained with --cond_interval (args.cond_interval is not set)")
+        if self.args.tps_condition:
+            raise L.MdgenError("upsample() is defined for forward-simulation models (sim_condition), not two-sided ones")
+        c = int(c)
+        T = int(self.args.num_frames if num_frames is None else num_frames)
+        if c < 1 or T < 1:
+            raise L.MdgenError(f"num_frames and cond_interval must be >= 1, got {T}, {c}")
+        if sampling_method not in (None, "euler", "dopri5"):
+            raise L.MdgenError(f"sampling_method must be None, 'euler' or 'dopri5', got {sampling_method!r}")
+        if sampling_method == "dopri5" and num_steps is not None:
+            raise L.MdgenError("num_steps sets the fixed Euler grid; dopri5 chooses its own steps (pass one or the other)")
+        method = getattr(self.args, "sampling_method", "euler")
+        if sampling_method is None and num_steps is None and method != "euler":
+            raise L.MdgenError(f"checkpoint args say sampling_method={method!r}; pass sampling_method='dopri5' (CLI: "
+                               "--sampling_method dopri5) for the reference's solver, or num_steps=... (CLI: --num_steps) "
+                               "to sample with fixed-grid Euler")
+        tors = batch["torsions"].to(torch.float32)
+        trans = batch["trans"].to(torch.float32)
+        rots = batch["rots"].to(torch.float32)
+        require_cuda(tors, trans, rots)
+        if trans.dim() != 4:
+            raise L.MdgenError(f"key-frame batch: trans must be (B,K,L,3), got {tuple(trans.shape)}")
+        B, K, L_ = trans.shape[:3]
+        if K != -(-T // c):
+            raise L.MdgenError(f"{K} key frames per window, but num_frames={T} with cond_interval={c} needs "
+                               f"ceil({T} / {c}) = {-(-T // c)}")
+        dev = trans.device
+        if zs is None:
+            zs = torch.randn(B, T, L_, self.latent_dim, device=dev)
+        mask = batch["mask"].to(torch.float32).unsqueeze(1).expand(-1, T, -1)
+        if sampling_method == "dopri5":
+            prep = prep_keyframes(rots, trans, tors, T, c)
+            samples, self.last_stats = self.model.sample_dopri5(
+                zs, mask=mask.contiguous(), start_frames=(prep["start_rot"], prep["start_trans"]), x_cond=prep["x_cond"],
+                x_cond_mask=prep["x_cond_mask"], aatype=batch["seqres"], atol=atol, rtol=rtol)
+            atom14 = samples_to_atom14(samples, prep["start_rot"], prep["start_trans"], batch["seqres"], False)
+        else:
+            S = 49 if num_steps is None else int(num_steps)
+            atom14, samples = self.model.upsample_euler(zs, S, c, mask, rots, trans, tors, batch["seqres"],
+                                                        residue_tables(dev), use_graph=use_graph)
+        self.last_samples = samples
+        return atom14, batch["seqres"][:, None].expand(B, T, L_)
 
     def rollout(self, batch, num_frames: int, num_rollouts: int, num_steps=None, zs=None, use_graph=True,
                 return_next: bool = False):
