@@ -267,6 +267,36 @@ int32_t mdgen_debug_dopri5_controller(const double* init, const double* ratios, 
                                       float* probe, double* t0, double* dt, uint32_t* stage_bits, int32_t* accept,
                                       float* dense_s, int32_t* n_attempts);
 
+/* Fixed-grid Runge-Kutta sampling on t = linspace(0, 1, n_steps + 1) (fp32): `sample_ode(sampling_method='midpoint' | 'heun3' |
+ * 'rk4', num_steps = n_steps + 1)` -> torchdiffeq 0.2.x fixed_grid.py Midpoint, Heun3, RK4 (the 3/8 rule), one step per grid
+ * interval (integrators.py:106-113; formulas and rounding: csrc/ode.inc).  method: 1 midpoint (2 evaluations per step), 2 heun3
+ * (3), 3 rk4 (4).  Every sample sees the same time grid: a sample's solution does not depend on its batch mates.  Nothing
+ * synchronises and nothing is read back; with use_graph != 0 the whole solve is captured / replayed as ONE hipGraph (non-default
+ * stream; cached per shape, method, n_steps and pointers, like mdgen_sample_euler).  Both precision modes.
+ *   x            (B,T,L,D) fp32, 16-byte aligned: the noise on entry, the state at t = 1 on exit
+ *   workspace    mdgen_rk_workspace_bytes: the network workspace for the call's t-shared time rows (2 S, 3 S, 3 S + 1) + 4 velocities
+ * The state of a stage is formed inside the launch that embeds it (k_rk_embed) and never written to memory.
+ * Errors: -1 null argument, -2 unknown method or n_steps < 1, -7 alignment / workspace size. */
+int32_t mdgen_sample_rk(mdgen_ctx* ctx, const mdgen_shape* shape, int32_t method, int32_t n_steps, float* x, const float* mask,
+                        const float* start_rot, const float* start_trans,
+                        const float* end_rot, const float* end_trans, const float* rel7,
+                        const float* x_cond, const int64_t* x_cond_mask, const int64_t* aatype,
+                        void* workspace, size_t workspace_bytes, int32_t use_graph, void* stream);
+int32_t mdgen_rk_workspace_bytes(const mdgen_ctx* ctx, const mdgen_shape* shape, int32_t method, int32_t n_steps, size_t* bytes);
+
+/* Host-only test hook (no GPU): the time rows mdgen_sample_rk prepares for (method, n_steps) as fp32 bits (row_bits, room for
+ * cap_rows; *n_rows of them) and the row of every (step, stage): row_of[step * *n_stages + stage]. */
+int32_t mdgen_debug_rk_plan(int32_t method, int32_t n_steps, uint32_t* row_bits, int32_t cap_rows, int32_t* n_rows,
+                            int32_t* row_of, int32_t* n_stages);
+/* Test hook: the sampler's state-forming embedding kernel (k_rk_embed) alone.  State `stage` of a step of `method` with step size
+ * dt: 0 is y itself, 1 .. stages - 1 a stage input, `stages` the step's result in the storing form (the launch that opens the next
+ * step).  y (B,T,L,D): the step's y0, overwritten by the result in the storing form; k0 .. k3: the velocities of stages 1 .. 4
+ * (null where the state does not read one); ipa_out: [B L][384] rows or null; h out: [B T L][384].  Weights and abs_pos_emb: the
+ * context's. */
+int32_t mdgen_debug_rk_stage(mdgen_ctx* ctx, const mdgen_shape* shape, int32_t method, int32_t stage, float dt, float* y,
+                             const float* k0, const float* k1, const float* k2, const float* k3, const float* x_cond,
+                             const int64_t* x_cond_mask, const float* ipa_out, float* h, void* stream);
+
 /* Residue constant tables (device pointers; data of mdgen/residue_constants.py:1124-1216, 1367-1480), as the two
  * geometry entry points below take them one by one. */
 typedef struct mdgen_residue_tables {
@@ -350,7 +380,8 @@ int32_t mdgen_profile_report(mdgen_ctx* ctx, void* stream, char* buf, size_t buf
  * orchestration code (the code path of latent_model.py:212-260 / transport.py:408-451's replacements above) run in a plan mode
  * that skips every HIP call; a call the entry point refuses (trace_h with a batch of several launch views) is refused here too.  mode 0: mdgen_sample_euler as the product runs it (sub-batch streams); 1: mdgen_denoiser_forward;
  * 2: mdgen_sample_euler as it runs under mdgen_profile_enable (one stream); 3: mdgen_denoiser_forward with trace_h; 4: one attempted
- * step of mdgen_sample_dopri5 (n_steps ignored; adds "integrator": {class: launches}).  options: "name=value,..." with mdgen_ctx_set_option's
+ * step of mdgen_sample_dopri5; 5 / 6 / 7: one step of mdgen_sample_rk with method 1 / 2 / 3 (modes 4 .. 7: n_steps ignored; they add
+ * "integrator": {class: launches}).  options: "name=value,..." with mdgen_ctx_set_option's
  * names (bf16 path only).  ncu / xcd_round_robin: the two device facts mdgen_ctx_create would have probed (see "@context" of
  * mdgen_profile_report).  Writes {"streams": n, "prepare": {"<class>": launches, ...} (the step-invariant part: adaLN table, IPA stack, fold pack),
  * "views": [{"B": samples of the sub-batch view, "classes": {...}}, ...]} with the class names of mdgen_profile_report.  tests/test_dispatch_cpu.py sweeps shapes with it and fails when a combination of

@@ -25,6 +25,7 @@ EXPORTS = [
     "mdgen_train_num_milestones", "mdgen_train_bind_params",
     "mdgen_train_set_milestone_events",
     "mdgen_sample_dopri5", "mdgen_dopri5_workspace_bytes", "mdgen_debug_dopri5_controller",
+    "mdgen_sample_rk", "mdgen_rk_workspace_bytes", "mdgen_debug_rk_plan", "mdgen_debug_rk_stage",
 ]
 
 
@@ -75,6 +76,10 @@ def _load():
     lib.mdgen_sample_dopri5.argtypes = [vp, C.POINTER(Shape), f64, f64, i32] + [vp] * 10 + [vp, sz, C.POINTER(i32), vp, vp]
     lib.mdgen_dopri5_workspace_bytes.argtypes = [vp, C.POINTER(Shape), C.POINTER(sz)]
     lib.mdgen_debug_dopri5_controller.argtypes = [vp, vp, i32, i32] + [vp] * 7
+    lib.mdgen_sample_rk.argtypes = [vp, C.POINTER(Shape), i32, i32] + [vp] * 11 + [sz, i32, vp]
+    lib.mdgen_rk_workspace_bytes.argtypes = [vp, C.POINTER(Shape), i32, i32, C.POINTER(sz)]
+    lib.mdgen_debug_rk_plan.argtypes = [i32, i32, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)]
+    lib.mdgen_debug_rk_stage.argtypes = [vp, C.POINTER(Shape), i32, i32, C.c_float] + [vp] * 10
     lib.mdgen_rollout_euler.argtypes = [vp, C.POINTER(Shape), i32, i32] + [vp] * 8 + [C.POINTER(ResidueTables), vp, vp, sz, i32, vp]
     lib.mdgen_upsample_euler.argtypes = [vp, C.POINTER(Shape), i32, i32] + [vp] * 10 + [C.POINTER(ResidueTables), vp, vp, sz, i32, vp]
     lib.mdgen_profile_enable.argtypes = [vp, i32]
@@ -179,10 +184,28 @@ def train_plan(B, T, L_, tps=False, num_layers=1, train_precision=16, weight_mis
     return json.loads(buf.value.decode())
 
 
+RK_METHODS = {"midpoint": 1, "heun3": 2, "rk4": 3}   # include/mdgen_amd.h mdgen_sample_rk `method`
+RK_STAGES = {"midpoint": 2, "heun3": 3, "rk4": 4}    # network evaluations per step
+
+
+def rk_plan(method, S):
+    """`mdgen_debug_rk_plan` (host only): (time rows as a uint32 numpy array of fp32 bits, row index array [S][stages])."""
+    import numpy as np
+    code = RK_METHODS.get(method, method)
+    S = int(S)
+    cap = 4 * max(S, 1) + 1
+    bits = np.zeros(cap, dtype=np.uint32)
+    row_of = np.zeros(4 * max(S, 1), dtype=np.int32)
+    n_rows, n_st = C.c_int32(), C.c_int32()
+    check(lib.mdgen_debug_rk_plan(int(code), S, bits.ctypes.data, cap, C.byref(n_rows), row_of.ctypes.data, C.byref(n_st)))
+    return bits[:n_rows.value].copy(), row_of[:S * n_st.value].reshape(S, n_st.value).copy()
+
+
 def dispatch_plan(B, T, L_, n_steps=1, mode=0, tps=False, num_layers=5, ncu=256, xcd_round_robin=True, options=None):
     """`mdgen_debug_dispatch_plan` (host only): {"streams", "prepare": {kernel class: launches}, "views": [{"B", "classes"}]} of a call of this shape.
     mode 0: sample_euler (product path), 1: forward, 2: sample_euler under the profiler (one stream), 3: forward with trace_h,
-    4: one attempted step of sample_dopri5 (adds "integrator": {kernel class: launches})."""
+    4: one attempted step of sample_dopri5, 5 / 6 / 7: one midpoint / heun3 / rk4 step of sample_rk (modes 4 .. 7 add "integrator":
+    {kernel class: launches})."""
     import json
     buf = C.create_string_buffer(1 << 14)
     sh = Shape(B, T, L_)

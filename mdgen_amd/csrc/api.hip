@@ -905,7 +905,9 @@ struct Run {
     // embedding-as-tail: base rows [S][B*L][384] (step 0, first batch element of this view), null when off; floats between steps
     const float* embase_p;
     long embase_step_stride;
-    bool no_embed_tail;          // the call never runs the embedding-as-tail form (mdgen_sample_dopri5): prepare() skips its base rows
+    bool no_embed_tail;          // the call never runs the embedding-as-tail form (mdgen_sample_dopri5, mdgen_sample_rk): prepare() skips its base rows
+    const RkState* rk;           // stage descriptor of a fixed-grid Runge-Kutta evaluation (ode.inc): denoise_step embeds the state it
+                                 // describes (k_rk_embed) instead of x; pointers of THIS view.  Null: x is embedded as it is
     bool concurrent;             // a view whose launches run beside other views' on other streams: kernels that use the call's split
                                  // scratch (one launch at a time) stay off meanwhile (for_each_view)
     float* h() const { return hp; }
@@ -1706,8 +1708,11 @@ static int denoise_step(const Run& r, int step, float* x, float* out, int euler,
     const bool embed_tail = euler && embed_tail_runs(r);
     float* h = r.h();
     const EmbedParams e = embed_op(r, x, r.ipa_out_p + (long)step * r.ipa_step_stride);
-    if (!(embed_tail && step > 0))
+    if (r.rk) {
+        if (int er = launch(r, "rk_embed", [&] { launch_rk_embed(e, *r.rk, r.s); })) return er;
+    } else if (!(embed_tail && step > 0)) {
         if (int er = launch(r, "embed", [&] { launch_embed(e, r.s); })) return er;
+    }
     const size_t hbytes = (size_t)r.N * kC * 4;
     if (trace_h) HIPCHK(hipMemcpyAsync(trace_h, h, hbytes, hipMemcpyDeviceToDevice, r.s));
     if (c->opt_precision == 32) {   // ---- fp32 operands (k_fp32.hip): same dataflow, one kernel per reference op group
@@ -1813,6 +1818,7 @@ static int make_run(Run* r, mdgen_ctx* c, const mdgen_shape* sh, int S, int t_sh
     r->embase_p = nullptr;
     r->embase_step_stride = (long)sh->B * sh->L * kC;
     r->no_embed_tail = false;
+    r->rk = nullptr;
     r->concurrent = false;
     if (fold_on(c, r->N, t_shared, S)) {
         r->fold_streams = r->ws + r->lay.fold;
@@ -2104,10 +2110,11 @@ extern "C" int32_t mdgen_upsample_euler(mdgen_ctx* c, const mdgen_shape* sh, int
 // ode.inc dopri5_attempt) run in plan mode (g_dry) on a context that owns no device memory -- the same view loop, layer plans and
 // launch sites as a real call.  mode 0: mdgen_sample_euler as the product runs it (sub-batch streams);
 // 1: mdgen_denoiser_forward; 2: mdgen_sample_euler as mdgen_profile_enable sees it (one stream); 3: mdgen_denoiser_forward with trace_h;
-// 4: one attempted step of mdgen_sample_dopri5 (n_steps is ignored).  options: "name=value,..."
+// 4: one attempted step of mdgen_sample_dopri5; 5, 6, 7: one step of mdgen_sample_rk with method 1 (midpoint), 2 (heun3), 3 (rk4) (n_steps
+// is ignored in modes 4 .. 7).  options: "name=value,..."
 // (mdgen_ctx_set_option names).  ncu / xcd_round_robin: what mdgen_ctx_create would have found on the device.
 // Output: {"streams": n, "prepare": {"<class>": launches, ...}, "views": [{"B": samples of the view, "classes": {...}}, ...]}
-// and, mode 4, "integrator": {"ode_combine": 6, "ode_norm": 1}.
+// and, mode 4, "integrator": {"ode_combine": 6, "ode_norm": 1}; modes 5 .. 7, "integrator": {"ode_rk_update": 1}.
 static int plan_json(const DryPlan& plan, int B, int nv, int ns, bool integrator, char* buf, size_t buflen) {
     std::map<std::string, long> prep, integ;
     std::vector<std::map<std::string, long>> views(nv);
@@ -2139,8 +2146,9 @@ extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_st
                                              int32_t num_layers, int32_t ncu, int32_t xcd_round_robin, const char* options,
                                              char* buf, size_t buflen) {
     if (!sh || !buf || buflen < 64) return fail(-1, "null argument");
-    if (mode < 0 || mode > 4)
-        return fail(-2, "mode: 0 sample_euler, 1 forward, 2 sample_euler under the profiler, 3 forward with trace_h, 4 one dopri5 step");
+    if (mode < 0 || mode > 7)
+        return fail(-2, "mode: 0 sample_euler, 1 forward, 2 sample_euler under the profiler, 3 forward with trace_h, 4 one dopri5 step, "
+                        "5 / 6 / 7 one midpoint / heun3 / rk4 step");
     if (num_layers < 1 || num_layers > 8 || ncu < 1) return fail(-2, "num_layers in 1..8, ncu >= 1");
     mdgen_ctx ctx;   // no device memory, no streams: plan mode never touches them
     mdgen_ctx* c = &ctx;
@@ -2171,17 +2179,20 @@ extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_st
         ~Dry() { g_dry = nullptr; }
     } dry(&plan);
     const bool fwd = mode == 1 || mode == 3;
-    const int S = mode == 4 ? ode::kStages : fwd ? 1 : n_steps;
+    const bool rkm = mode >= 5;   // one step of mdgen_sample_rk, method mode - 4: its time rows
+    const int S = mode == 4 ? ode::kStages : rkm ? rk_method(mode - 4)->stages : fwd ? 1 : n_steps;
     const int t_shared = fwd ? (sh->B == 1 ? 1 : 0) : 1;
     Run r{};
     if (int e = make_run(&r, c, sh, S, t_shared, f32_path(c), (void*)4096, (size_t)1 << 60, nullptr)) return e;
     float* fake = (float*)4096;   // never dereferenced: plan mode launches nothing
     r.mask = r.start_rot = r.start_trans = r.end_rot = r.end_trans = r.x_cond = fake;
     r.x_cond_mask = r.aatype = (const int64_t*)fake;
-    const int ns = fwd || mode == 4 ? 1 : n_streams(r);
+    const int ns = fwd || mode >= 4 ? 1 : n_streams(r);
     const int nv = plan_views(r.B, r.T, r.L, ns);
     if (mode == 4) {
         if (int e = dopri5_plan(r, nv)) return e;
+    } else if (rkm) {
+        if (int e = rk_dispatch_plan(r, nv, mode - 4)) return e;
     } else if (fwd) {
         if (int e = forward_body(r, fake, fake, fake, mode == 3 ? fake : nullptr, nullptr)) return e;
     } else {
@@ -2189,7 +2200,7 @@ extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_st
         linspace01(S + 1, &tg);
         if (int e = euler_body(r, tg, fake)) return e;
     }
-    return plan_json(plan, r.B, nv, ns, mode == 4, buf, buflen);
+    return plan_json(plan, r.B, nv, ns, mode >= 4, buf, buflen);
 }
 
 // ---------------------------------------------------------------------------------------------

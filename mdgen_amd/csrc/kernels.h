@@ -532,6 +532,32 @@ void launch_ode_norm(const OdeNorm& p, long n, double* part, double* out, hipStr
 void launch_ode_dense(float* out, const float* y0, const float* y1, const float* f0, const float* f1, const float* ym, float dt,
                       float sfrac, long n, hipStream_t s);
 
+// fixed-grid Runge-Kutta sampler (k_rk.hip; tableau and orchestration in ode.inc).  A stage's state is never written to HBM: the
+// launch that embeds it forms it from y0 and the step's velocities.  RkForm: the arithmetic of one state, every written operation
+// one rounded fp32 operation (no contraction), k0 .. k3 = RkState::k[0 .. 3]:
+enum RkForm : int {
+    kRkY0 = 0,     // y0                                            (first stage of the first step)
+    kRkAxk,        // y0 + k0 * c0                                  (c0 already holds the step size)
+    kRkDtCk,       // y0 + dt * (c0 * k0)
+    kRkDtkC,       // y0 + (dt * k0) * c0
+    kRkDtLin2,     // y0 + dt * (c0 * k0 + c1 * k1)
+    kRkDtLin3,     // y0 + dt * ((c0 * k0 + c1 * k1) + c2 * k2)
+    kRk38,         // y0 + (((k0 + c0 * (k1 + k2)) + k3) * dt) * c1  (the 3/8 rule's result)
+    kRkForms
+};
+constexpr int kRkMaxK = 4;
+struct RkState {
+    int form, nk;                  // RkForm; velocities the form reads (k[0 .. nk - 1])
+    int store;                     // the state is the step's result y1: it is also stored over y (each element by the thread that read it)
+    float dt, c[3];
+    const float* k[kRkMaxK];
+    float* y;                      // y0 (B, T, L, D)
+};
+// k_embed on the state `st` describes (p.x is not read: st.y is); the kernel forms follow launch_embed's launch sizes
+void launch_rk_embed(const EmbedParams& p, const RkState& st, hipStream_t s);
+// y <- the state `st` describes, elementwise over n values (the result of the last step)
+void launch_rk_update(const RkState& st, long n, hipStream_t s);
+
 // SE(3) / pre / post (k_se3.hip)
 void launch_rigid_compose(long n, const float* r1, const float* t1, const float* r2, const float* t2, float* ro,
                           float* to, hipStream_t s);

@@ -1,4 +1,5 @@
-// ode.inc -- adaptive Dormand-Prince sampling (included by api.hip; kernels in k_ode.hip).
+// ode.inc -- the ODE solvers beyond the Euler rollout (included by api.hip): adaptive Dormand-Prince sampling (kernels in k_ode.hip),
+// then, further down, fixed-grid midpoint / heun3 / rk4 (kernels in k_rk.hip).
 //
 // The reference's NewMDGenWrapper.inference() integrates with the checkpoint's own `sampling_method` (wrapper.py:441-447), by
 // default 'dopri5' (parsing.py:102): transport.py:408-451 / integrators.py:74-113 call
@@ -369,4 +370,235 @@ static int dopri5_plan(Run& r, int nv) {
     Dopri5Ctl ctl;
     ctl.dt = 0.01;
     return dopri5_attempt(r, b, ctl, nv, largest_view_rows(r, nv), 1e-6, 1e-3);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Fixed-grid Runge-Kutta sampling: midpoint, heun3, rk4 on t = linspace(0, 1, S + 1)   (mdgen_sample_rk)
+// ---------------------------------------------------------------------------------------------
+// The reference's Sampler.sample_ode(sampling_method=...) hands the method name to torchdiffeq (integrators.py:106-113), whose
+// fixed-grid solvers (fixed_grid.py Midpoint, Heun3, RK4; rk_common.py rk3_step_func, rk4_alt_step_func -- the 3/8 rule) take one step
+// per grid interval.  With fp32 t0 = t[i], t1 = t[i + 1], dt = t1 - t0, f(t, y) = model(y, ones(B) t):
+//   midpoint  k1 = f(t0, y0); k2 = f(t0 + 0.5 dt, y0 + k1 (0.5 dt));                               y1 = y0 + dt k2
+//   heun3     k1 = f(t0, y0); k2 = f(t0 + dt/3, y0 + dt (k1/3)); k3 = f(t0 + 2 dt/3, y0 + dt (2/3 k2));   y1 = y0 + dt (k1/4 + 3/4 k3)
+//   rk4       k1 = f(t0, y0); k2 = f(t0 + dt/3, y0 + (dt k1)/3); k3 = f(t0 + 2 dt/3, y0 + dt (k2 - k1/3));
+//             k4 = f(t1, y0 + dt ((k1 - k2) + k3));                                                 y1 = y0 + (((k1 + 3 (k2 + k3)) + k4) dt) / 8
+// 1/3 and 2/3 are (float)(1.0 / 3), (float)(2.0 / 3); every written operation is one rounded fp32 operation.  The table below holds
+// each state of a step -- the stage inputs and the result -- as an RkForm (kernels.h) with its coefficients: another explicit
+// method whose states fit these forms is one more row.
+// Every sample sees the same time grid, so a sample's solution does not depend on its batch mates; nothing is read back, so the
+// whole solve is one hipGraph; the cost is S x stages network evaluations.
+// Orchestration: ONE prepare() for all the call's time rows (a stage at t1 and the next step's first stage share a row: 3 S + 1 rows
+// for rk4), then S x stages denoise_step(..., euler = 0) writing k_i through the FinalLayer tail, each starting with k_rk_embed on the
+// stage's RkState: stage inputs never reach HBM.  The first stage of step i + 1 forms y1 of step i and stores it over y0 (= the
+// caller's x); after the last step k_rk_update does.  Views run one after the other on the caller's stream (plan_views(..., 1)), as
+// in mdgen_sample_dopri5: the network launches take kernel forms the dispatch registry covers.
+namespace rk {
+const float kThird = (float)(1.0 / 3), kTwoThirds = (float)(2.0 / 3);
+struct Node {                  // one state of a step
+    float a;                   // model time t0 + a dt (0: t0 itself, 1: the grid's t1 itself); a result has none
+    int form;                  // RkForm
+    int ki[kRkMaxK];           // the stages whose velocities the form reads as k0 .. k3; -1 ends the list
+    float c[3];
+    bool c0_dt;                // c[0] is multiplied by dt on the host (one rounded fp32 product)
+};
+struct Method {
+    const char* name;
+    int stages;
+    Node stage[kRkMaxK];       // stage[0] is y0 itself
+    Node result;
+};
+const Method kMethods[] = {
+    {"midpoint", 2,
+     {{0.f, kRkY0, {-1, -1, -1, -1}, {}, false}, {0.5f, kRkAxk, {0, -1, -1, -1}, {0.5f}, true}},
+     {1.f, kRkAxk, {1, -1, -1, -1}, {1.f}, true}},
+    {"heun3", 3,
+     {{0.f, kRkY0, {-1, -1, -1, -1}, {}, false}, {kThird, kRkDtCk, {0, -1, -1, -1}, {kThird}, false},
+      {kTwoThirds, kRkDtCk, {1, -1, -1, -1}, {kTwoThirds}, false}},
+     {1.f, kRkDtLin2, {0, 2, -1, -1}, {0.25f, 0.75f}, false}},
+    {"rk4", 4,
+     {{0.f, kRkY0, {-1, -1, -1, -1}, {}, false}, {kThird, kRkDtkC, {0, -1, -1, -1}, {kThird}, false},
+      {kTwoThirds, kRkDtLin2, {1, 0, -1, -1}, {1.f, -kThird}, false}, {1.f, kRkDtLin3, {0, 1, 2, -1}, {1.f, -1.f, 1.f}, false}},
+     {1.f, kRk38, {0, 1, 2, 3}, {3.f, 0.125f}, false}},
+};
+constexpr int kNumMethods = (int)(sizeof(kMethods) / sizeof(kMethods[0]));
+}  // namespace rk
+
+// method codes of the C ABI: 1 midpoint, 2 heun3, 3 rk4
+static const rk::Method* rk_method(int code) { return code >= 1 && code <= rk::kNumMethods ? &rk::kMethods[code - 1] : nullptr; }
+
+// The prepared time rows of a solve and the row of every (step, stage)
+struct RkPlan {
+    std::vector<float> tg, rows;
+    std::vector<int> row_of;   // [S][stages]
+};
+static void rk_plan(const rk::Method& m, int S, RkPlan* p) {
+#pragma clang fp contract(off)
+    linspace01(S + 1, &p->tg);
+    p->rows.clear();
+    p->row_of.assign((size_t)S * m.stages, 0);
+    for (int i = 0; i < S; ++i) {
+        const float t0 = p->tg[i], t1 = p->tg[i + 1], dt = t1 - t0;
+        for (int j = 0; j < m.stages; ++j) {
+            const float a = m.stage[j].a;
+            if (j == 0 && i > 0 && m.stage[m.stages - 1].a == 1.f) {   // the previous step's last stage was evaluated at this t0
+                p->row_of[(size_t)i * m.stages] = (int)p->rows.size() - 1;
+                continue;
+            }
+            p->row_of[(size_t)i * m.stages + j] = (int)p->rows.size();
+            p->rows.push_back(a == 0.f ? t0 : a == 1.f ? t1 : t0 + a * dt);
+        }
+    }
+}
+
+// the device descriptor of state `n` of a step of size dt: y and k[stage] of the whole batch, shifted by `off` floats (a view)
+static RkState rk_state_of(const rk::Node& n, float dt, float* y, float* const* k, long off, bool store) {
+#pragma clang fp contract(off)
+    RkState s{};
+    s.form = n.form;
+    s.store = store ? 1 : 0;
+    s.dt = dt;
+    for (int q = 0; q < 3; ++q) s.c[q] = n.c[q];
+    if (n.c0_dt) s.c[0] = n.c[0] * dt;
+    for (s.nk = 0; s.nk < kRkMaxK && n.ki[s.nk] >= 0; ++s.nk) s.k[s.nk] = k[n.ki[s.nk]] + off;
+    s.y = y + off;
+    return s;
+}
+
+static int rk_layout(const mdgen_ctx* c, const mdgen_shape* sh, int method, int S, RkPlan* pl, mdgen_ws_layout* lay) {
+    const rk::Method* m = rk_method(method);
+    if (!m) return fail(-2, "method: 1 midpoint, 2 heun3, 3 rk4 (got %d)", method);
+    if (S < 1) return fail(-2, "n_steps must be >= 1");
+    if (S > 100000) return fail(-2, "n_steps too large");
+    rk_plan(*m, S, pl);
+    return mdgen_workspace_layout(c, sh, (int)pl->rows.size(), 1, lay);
+}
+
+extern "C" int32_t mdgen_rk_workspace_bytes(const mdgen_ctx* c, const mdgen_shape* sh, int32_t method, int32_t S, size_t* bytes) {
+    if (!bytes) return fail(-1, "null argument");
+    RkPlan pl;
+    mdgen_ws_layout lay;
+    if (int e = rk_layout(c, sh, method, S, &pl, &lay)) return e;
+    *bytes = align256(lay.total_bytes) + kRkMaxK * ode_state_bytes(c, sh) + 256;
+    return 0;
+}
+
+// the solve on a made run: y (= the caller's x) in place, k[stage] the velocities
+static int rk_body(const Run& r_in, const rk::Method& m, int S, const RkPlan& pl, int nv, float* y, float* const* k) {
+    Run r = r_in;
+    if (int e = ode_prepare(r, pl.rows.data(), (int)pl.rows.size(), largest_view_rows(r, nv))) return e;
+    const long per_b = (long)r.T * r.L * r.D;
+    for (int i = 0; i < S; ++i) {
+        const float dt = pl.tg[i + 1] - pl.tg[i], dt_prev = i > 0 ? pl.tg[i] - pl.tg[i - 1] : 0.f;
+        for (int j = 0; j < m.stages; ++j) {
+            // the first stage of step i > 0 forms the previous step's result and stores it over y
+            const bool first = j == 0;
+            const rk::Node& n = first && i > 0 ? m.result : m.stage[j];
+            const int row = pl.row_of[(size_t)i * m.stages + j];
+            const int e = for_each_view(r, nv, 1, [&](const Run& v, int b0) {
+                const long o = (long)b0 * per_b;
+                const RkState st = rk_state_of(n, first ? dt_prev : dt, y, k, o, first && i > 0);
+                Run vs = v;
+                vs.rk = &st;
+                return denoise_step(vs, row, y + o, k[j] + o, 0, 0.f, nullptr);
+            });
+            if (e) return e;
+        }
+    }
+    const RkState last = rk_state_of(m.result, pl.tg[S] - pl.tg[S - 1], y, k, 0, true);
+    return launch(r, "ode_rk_update", [&] { launch_rk_update(last, (long)r.N * r.D, r.s); });
+}
+
+extern "C" int32_t mdgen_sample_rk(mdgen_ctx* c, const mdgen_shape* sh, int32_t method, int32_t S, float* x, const float* mask,
+                                   const float* start_rot, const float* start_trans, const float* end_rot, const float* end_trans,
+                                   const float* rel7, const float* x_cond, const int64_t* x_cond_mask, const int64_t* aatype, void* ws,
+                                   size_t ws_bytes, int32_t use_graph, void* stream) {
+    if (!x || !mask || !start_rot || !start_trans || !x_cond || !x_cond_mask || !aatype) return fail(-1, "null argument");
+    RkPlan pl;
+    mdgen_ws_layout lay;
+    if (int e = rk_layout(c, sh, method, S, &pl, &lay)) return e;
+    const rk::Method& m = *rk_method(method);
+    if (((uintptr_t)x & 15) != 0) return fail(-7, "x must be 16-byte aligned");
+    const size_t sb = ode_state_bytes(c, sh), need = align256(lay.total_bytes) + kRkMaxK * sb + 256;
+    if (ws_bytes < need) return fail(-7, "workspace too small: %zu < %zu bytes (mdgen_rk_workspace_bytes)", ws_bytes, need);
+    Run r{};
+    if (int e = make_run(&r, c, sh, (int)pl.rows.size(), 1, f32_path(c), ws, lay.total_bytes, stream)) return e;
+    r.mask = mask;
+    r.start_rot = start_rot;
+    r.start_trans = start_trans;
+    r.end_rot = end_rot;
+    r.end_trans = end_trans;
+    r.rel7_in = rel7;
+    r.x_cond = x_cond;
+    r.x_cond_mask = x_cond_mask;
+    r.aatype = aatype;
+    r.no_embed_tail = true;
+    const int nv = c->opt_precision == 32 ? 1 : plan_views(r.B, r.T, r.L, 1);
+    if (nv == 0) return fail(-2, "sample too large for one launch");
+    float* k[kRkMaxK];
+    for (int j = 0; j < kRkMaxK; ++j) k[j] = (float*)((unsigned char*)ws + align256(lay.total_bytes) + (size_t)j * sb);
+    if (!use_graph || c->prof_on) return rk_body(r, m, S, pl, nv, x, k);
+    std::vector<uint64_t> key = {3u, (uint64_t)sh->B, (uint64_t)sh->T, (uint64_t)sh->L, (uint64_t)method, (uint64_t)S, (uint64_t)x,
+                                 (uint64_t)mask, (uint64_t)start_rot, (uint64_t)start_trans, (uint64_t)end_rot,
+                                 (uint64_t)end_trans, (uint64_t)x_cond, (uint64_t)x_cond_mask, (uint64_t)aatype,
+                                 (uint64_t)ws, graph_option_key(c), (uint64_t)rel7};
+    return replay_or_capture(c, key, r.s, [&]() { return rk_body(r, m, S, pl, nv, x, k); });
+}
+
+// Host-only test hook: the time rows mdgen_sample_rk prepares for (method, S), as fp32 bits, and the row of every (step, stage).
+// row_bits: room for cap_rows values; row_of: [S][stages].
+extern "C" int32_t mdgen_debug_rk_plan(int32_t method, int32_t S, uint32_t* row_bits, int32_t cap_rows, int32_t* n_rows,
+                                       int32_t* row_of, int32_t* n_stages) {
+    if (!row_bits || !n_rows || !row_of || !n_stages) return fail(-1, "null argument");
+    const rk::Method* m = rk_method(method);
+    if (!m) return fail(-2, "method: 1 midpoint, 2 heun3, 3 rk4 (got %d)", method);
+    if (S < 1) return fail(-2, "n_steps must be >= 1");
+    RkPlan pl;
+    rk_plan(*m, S, &pl);
+    *n_rows = (int32_t)pl.rows.size();
+    *n_stages = m->stages;
+    if (cap_rows < *n_rows) return fail(-7, "row buffer too small: %d < %d", cap_rows, *n_rows);
+    std::memcpy(row_bits, pl.rows.data(), pl.rows.size() * sizeof(float));
+    for (size_t i = 0; i < pl.row_of.size(); ++i) row_of[i] = pl.row_of[i];
+    return 0;
+}
+
+// Test hook: k_rk_embed alone.  State `stage` of a step of `method` with step size dt: 0 is y itself, 1 .. stages - 1 a stage input,
+// `stages` the step's result in the storing form (what the next step's first stage launches).  y (B, T, L, D) is the step's y0 (the
+// result is stored over it), k0 .. k3 the velocities of stages 1 .. 4 (those the state does not read may be null); ipa_out: [B L][384]
+// rows or null; h: [B T L][384].  The context's weights and its abs_pos_emb decide the rest, as in a sampler call.
+extern "C" int32_t mdgen_debug_rk_stage(mdgen_ctx* c, const mdgen_shape* sh, int32_t method, int32_t stage, float dt, float* y,
+                                        const float* k0, const float* k1, const float* k2, const float* k3, const float* x_cond,
+                                        const int64_t* x_cond_mask, const float* ipa_out, float* h, void* stream) {
+    if (!y || !x_cond || !x_cond_mask || !h) return fail(-1, "null argument");
+    const rk::Method* m = rk_method(method);
+    if (!m) return fail(-2, "method: 1 midpoint, 2 heun3, 3 rk4 (got %d)", method);
+    if (stage < 0 || stage > m->stages) return fail(-2, "stage must be in 0 .. %d", m->stages);
+    if (int e = check_shape(c, sh, 1)) return e;
+    if (!c->finalized) return fail(-6, "context not finalized (mdgen_ctx_finalize)");
+    float* k[kRkMaxK] = {const_cast<float*>(k0), const_cast<float*>(k1), const_cast<float*>(k2), const_cast<float*>(k3)};
+    const rk::Node& n = stage == m->stages ? m->result : m->stage[stage];
+    for (int q = 0; q < kRkMaxK && n.ki[q] >= 0; ++q)
+        if (!k[n.ki[q]]) return fail(-1, "the state reads k%d", n.ki[q]);
+    const RkState st = rk_state_of(n, dt, y, k, 0, stage == m->stages);
+    EmbedParams e{};
+    e.x = y; e.x_cond = x_cond; e.x_cond_mask = x_cond_mask;
+    e.wl = c->wl; e.bl = c->bl; e.wc = c->wc; e.bc = c->bc; e.mask_emb = c->mask_emb;
+    e.wl_pack = c->wl_pack; e.wc_pack = c->wc_pack;
+    e.pos_embed = c->d.abs_pos_emb ? c->pos_embed : nullptr;
+    e.ipa_out = ipa_out; e.h = h; e.N = (long)sh->B * sh->T * sh->L; e.T = sh->T; e.L = sh->L; e.D = c->D;
+    launch_rk_embed(e, st, (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
+
+// mdgen_debug_dispatch_plan modes 5 .. 7: one step of mdgen_sample_rk (methods 1 .. 3) on a made run, in plan mode
+static int rk_dispatch_plan(Run& r, int nv, int method) {
+    if (nv == 0) return fail(-2, "sample too large for one launch");
+    r.no_embed_tail = true;
+    const rk::Method& m = *rk_method(method);
+    RkPlan pl;
+    rk_plan(m, 1, &pl);
+    float* fake = (float*)4096;   // never dereferenced: plan mode launches nothing
+    float* k[kRkMaxK] = {fake, fake, fake, fake};
+    return rk_body(r, m, 1, pl, nv, fake, k);
 }

@@ -353,6 +353,90 @@ class LatentMDGenModel:
                 "steps": [(steps[2 * i], steps[2 * i + 1]) for i in range(acc)]}
         return x, info
 
+    # ---- fixed-grid Runge-Kutta ---------------------------------------------------------------
+    def sample_rk(self, zs, method: str, num_steps: int, mask=None, start_frames=None, end_frames=None, x_cond=None,
+                  x_cond_mask=None, aatype=None, use_graph: bool = True, rel_quats=None):
+        """`mdgen_sample_rk`: `method` in ("midpoint", "heun3", "rk4") with one step per interval of t = linspace(0, 1, S + 1),
+        S = `num_steps` (torchdiffeq 0.2.x fixed-grid solvers as transport.py:408-451 / integrators.py:106-113 call them): 2, 3, 4
+        network evaluations per step.  Every sample sees the same grid, so a sample's solution does not depend on its batch mates;
+        nothing synchronises, and with `use_graph` the whole solve is one hipGraph.  Returns x at t = 1."""
+        if self._pre_run is not None:
+            self._pre_run()
+        code = L.RK_METHODS.get(method)
+        if code is None:
+            raise L.MdgenError(f"method must be one of {sorted(L.RK_METHODS)}, got {method!r}")
+        S = int(num_steps)
+        if S < 1:
+            raise L.MdgenError(f"num_steps must be >= 1, got {num_steps}")
+        B, T, L_ = self._check_inputs(zs, mask, x_cond, x_cond_mask, aatype)
+        require_cuda(zs, mask, x_cond, x_cond_mask, aatype)
+        sr, st = _frames(start_frames)
+        er, et = _frames(end_frames)
+        if sr is None:
+            raise L.MdgenError("start_frames is required")
+        sh = L.Shape(B, T, L_)
+        nbytes = C.c_size_t()
+        check(lib.mdgen_rk_workspace_bytes(self._ctx, C.byref(sh), code, S, C.byref(nbytes)))
+        wkey = ("rk", B, T, L_)
+        ws = self._ws.get(wkey)
+        if ws is None or ws.numel() < nbytes.value:
+            while len(self._ws) >= self.max_cached_shapes:
+                self._ws.popitem(last=False)
+            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+            if self.poison_workspace:
+                ws.fill_(255)
+            self._ws[wkey] = ws
+        else:
+            self._ws.move_to_end(wkey)
+        key = (B, T, L_)
+        stg = self._stage.get(key)
+        if stg is not None:
+            self._stage.move_to_end(key)
+        else:   # persistent staging buffers (shared with sample_euler): stable device pointers => hipGraph replay
+            while len(self._stage) >= self.max_cached_shapes:
+                self._stage.popitem(last=False)
+            dev = self.device
+            stg = dict(
+                x=torch.empty(B, T, L_, self.cfg.latent_dim, device=dev), mask=torch.empty(B, T, L_, device=dev),
+                sr=torch.empty(B, L_, 3, 3, device=dev), st=torch.empty(B, L_, 3, device=dev),
+                er=torch.empty(B, L_, 3, 3, device=dev), et=torch.empty(B, L_, 3, device=dev),
+                x_cond=torch.empty(B, T, L_, self.cfg.latent_dim, device=dev),
+                x_cond_mask=torch.empty(B, T, L_, dtype=torch.int64, device=dev),
+                aatype=torch.empty(B, L_, dtype=torch.int64, device=dev),
+                rel7=torch.empty(2, B, L_, 7, device=dev) if self.cfg.tps_condition else None)
+            self._stage[key] = stg
+        stg["x"].copy_(zs)
+        stg["mask"].copy_(mask)
+        stg["sr"].copy_(sr)
+        stg["st"].copy_(st)
+        has_end = er is not None
+        if has_end:
+            stg["er"].copy_(er)
+            stg["et"].copy_(et)
+        stg["x_cond"].copy_(x_cond)
+        stg["x_cond_mask"].copy_(x_cond_mask)
+        stg["aatype"].copy_(aatype)
+        rel7 = self._rel7(rel_quats, B, L_)
+        if rel7 is not None:
+            stg["rel7"].copy_(rel7)
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream()
+            if use_graph:
+                if self._side is None:
+                    self._side = torch.cuda.Stream(device=self.device)
+                self._side.wait_stream(cur)
+                stream = self._side
+            else:
+                stream = cur
+            check(lib.mdgen_sample_rk(
+                self._ctx, C.byref(sh), code, S, ptr(stg["x"]), ptr(stg["mask"]), ptr(stg["sr"]), ptr(stg["st"]),
+                ptr(stg["er"]) if has_end else None, ptr(stg["et"]) if has_end else None,
+                ptr(stg["rel7"]) if rel7 is not None else None, ptr(stg["x_cond"]), ptr(stg["x_cond_mask"]), ptr(stg["aatype"]),
+                ptr(ws), ws.numel(), int(use_graph), C.c_void_p(stream.cuda_stream)))
+            if use_graph:
+                cur.wait_stream(self._side)
+        return stg["x"].clone()
+
     # ---- multi-block rollout -----------------------------------------------------------------
     def rollout_euler(self, zs, num_steps: int, mask, cond_rots, cond_trans, cond_torsions, seqres, tables,
                       use_graph: bool = True):

@@ -3,9 +3,11 @@
 
   --num_steps S      Euler steps per block (the reference samples with its checkpoint's `sampling_method`; a non-Euler
                      checkpoint is refused unless S or --sampling_method is given);
-  --sampling_method {euler,dopri5}   the solver: dopri5 is the reference's adaptive default (torchdiffeq, atol 1e-6,
-                     rtol 1e-3), run per block through `inference()` (one step size per call, shared by a --batch
-                     group); euler without --num_steps takes the reference's 49-step grid.  No flag: as before;
+  --sampling_method {euler,dopri5,midpoint,heun3,rk4}   the solver: dopri5 is the reference's adaptive default (torchdiffeq,
+                     atol 1e-6, rtol 1e-3), run per block through `inference()` (one step size per call, shared by a --batch
+                     group); euler without --num_steps takes the reference's 49-step grid; midpoint / heun3 / rk4 are
+                     torchdiffeq's fixed-grid solvers with --num_steps steps (default 24 / 16 / 12 = 48 network evaluations),
+                     one captured graph per block, each peptide of a --batch group solved as if alone.  No flag: as before;
   --batch N          peptides of equal length sampled together in one `inference()` call (the reference runs
                      B = 1, sim_inference.py:101-102; B = 16 is the regime BASELINE.json's metric is quoted on);
   --chunk_idx/--n_chunks   the reference's own sharding switches (tps_inference.py:17-18,160-161): this process
@@ -110,10 +112,10 @@ def sample_group(model, batch, args):
     """`num_rollouts` chained blocks for one batch; returns atom14 [B, R*T, L, 14, 3]."""
     method = getattr(args, "sampling_method", None)
     num_steps = 49 if method == "euler" and args.num_steps is None else args.num_steps
-    if hasattr(model, "rollout") and not getattr(args, "per_block", False) and method != "dopri5":
+    if hasattr(model, "rollout") and not getattr(args, "per_block", False) and method in (None, "euler"):
         return model.rollout(batch, args.num_frames, args.num_rollouts, num_steps=num_steps)
     out = []
-    for _ in range(args.num_rollouts):   # (dopri5: one inference() call per block; the device rollout is Euler only)
+    for _ in range(args.num_rollouts):   # (dopri5, midpoint, heun3, rk4: one inference() call per block; the device rollout is Euler only)
         atom14, batch = rollout(model, batch, args.num_frames, num_steps, sampling_method=method)
         out.append(atom14)
     return torch.cat(out, 1)
@@ -204,8 +206,8 @@ def build_parser():
     p.add_argument("--out_dir", type=str, default=".")
     p.add_argument("--split", type=str, default="splits/4AA_test.csv")
     p.add_argument("--num_steps", type=int, default=None,
-                   help="Euler steps per block (default: 49 = the reference's 50-point grid, Euler checkpoints only)")
-    p.add_argument("--sampling_method", choices=["euler", "dopri5"], default=None,
+                   help="solver steps per block (Euler default: 49 = the reference's 50-point grid, Euler checkpoints only)")
+    p.add_argument("--sampling_method", choices=["euler", "dopri5", "midpoint", "heun3", "rk4"], default=None,
                    help="solver (default: the checkpoint's, refused unless it is euler or --num_steps is given)")
     p.add_argument("--batch", type=int, default=1, help="peptides of equal length per inference() call")
     p.add_argument("--chunk_idx", type=int, default=0)
@@ -223,6 +225,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.sampling_method == "dopri5" and args.num_steps is not None:
         raise SystemExit("--num_steps sets the Euler grid; dopri5 chooses its own steps (pass one or the other)")
+    if args.num_steps is not None and args.num_steps < 1:
+        raise SystemExit(f"--num_steps must be >= 1, got {args.num_steps}")
     if args.no_frames or args.tps:
         raise SystemExit("--no_frames / --tps are outside this build's scope (see DESIGN.md)")
     import pandas as pd

@@ -65,9 +65,10 @@ def build_parser():
     p.add_argument("--start_frame", type=int, default=0, help="MD frame of {name}.npy used as the start state")
     p.add_argument("--end_frame", type=int, default=-1, help="MD frame of {name}.npy used as the end state")
     p.add_argument("--num_steps", type=int, default=None)
-    p.add_argument("--sampling_method", choices=["euler", "dopri5"], default=None,
+    p.add_argument("--sampling_method", choices=["euler", "dopri5", "midpoint", "heun3", "rk4"], default=None,
                    help="solver (default: the checkpoint's, refused unless it is euler or --num_steps is given); dopri5: "
-                        "the reference's adaptive solver, one step size per call shared by the --batch_size paths")
+                        "the reference's adaptive solver, one step size per call shared by the --batch_size paths; midpoint / heun3 / "
+                        "rk4: fixed-grid solvers with --num_steps steps (default 24 / 16 / 12)")
     p.add_argument("--synthetic", action="store_true")
     return p
 
@@ -115,6 +116,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.sampling_method == "dopri5" and args.num_steps is not None:
         raise SystemExit("--num_steps sets the Euler grid; dopri5 chooses its own steps (pass one or the other)")
+    if args.num_steps is not None and args.num_steps < 1:
+        raise SystemExit(f"--num_steps must be >= 1, got {args.num_steps}")
     rank, world, local_rank = dist_env()
     device = torch.device("cuda", local_rank)
     torch.cuda.set_device(device)

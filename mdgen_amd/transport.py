@@ -3,8 +3,9 @@
 -> `fn(x0, model_fn, **kw)` (transport.py:408-451, integrators.py:74-114).
 
 velocity prediction + GVP/Linear path => integration interval (t0, t1) = (0, 1) exactly
-(transport.py:95-124, 561-563).  Only the fixed-grid Euler solver is provided (dopri5, the SDE
-sampler and the likelihood path are outside the accelerated hot path).
+(transport.py:95-124, 561-563).  The fixed-grid solvers are provided here: Euler, midpoint, heun3 and rk4 (torchdiffeq's
+fixed_grid.py); adaptive dopri5 is `LatentMDGenModel.sample_dopri5`; the SDE sampler and the likelihood path are outside
+the accelerated hot path.
 """
 from __future__ import annotations
 
@@ -74,21 +75,64 @@ def create_transport(args=None, path_type="GVP", prediction="velocity", loss_wei
     return Transport(path_type, prediction)
 
 
+def linspace01(n):
+    """The library's fp32 time grid (csrc/api.hip linspace01): ATen's linspace formula with every operation rounded by itself,
+    t[i] = step * i below the midpoint and 1 - step * (n - 1 - i) from it on, step = 1 / (n - 1).  torch.linspace's CPU kernel
+    contracts step * i into an FMA and differs from it in the last bit of a few entries (4 of 50 at n = 50)."""
+    import numpy as np
+    one = np.float32(1.0)
+    step = one / np.float32(n - 1)
+    return torch.from_numpy(np.array([step * np.float32(i) if i < n // 2 else one - step * np.float32(n - 1 - i)
+                                      for i in range(n)], dtype=np.float32))
+
+
+def rk_step(method, f, t0, t1, y0):
+    """One step of torchdiffeq 0.2.x's fixed-grid `method` ("midpoint", "heun3", "rk4" -- the 3/8 rule) from (t0, y0) to t1, in
+    y0's dtype; t0, t1 are 0-dim tensors of that dtype, f(t, y) the drift.  Operation for operation what csrc/ode.inc restates
+    (fixed_grid.py Midpoint / Heun3 / RK4, rk_common.py rk3_step_func / rk4_alt_step_func)."""
+    dt = t1 - t0
+    third, two_thirds = (torch.tensor(1.0 / 3, dtype=y0.dtype, device=y0.device),
+                         torch.tensor(2.0 / 3, dtype=y0.dtype, device=y0.device))
+    k1 = f(t0, y0)
+    if method == "midpoint":
+        half_dt = 0.5 * dt
+        k2 = f(t0 + half_dt, y0 + k1 * half_dt)
+        return y0 + dt * k2
+    if method == "heun3":
+        k2 = f(t0 + dt * third, y0 + dt * (third * k1))
+        k3 = f(t0 + dt * two_thirds, y0 + dt * (two_thirds * k2))
+        return y0 + dt * (0.25 * k1 + 0.75 * k3)
+    if method == "rk4":
+        k2 = f(t0 + dt * third, y0 + (dt * k1) * third)
+        k3 = f(t0 + dt * two_thirds, y0 + dt * (k2 - k1 * third))
+        k4 = f(t1, y0 + dt * ((k1 - k2) + k3))
+        return y0 + (((k1 + 3 * (k2 + k3)) + k4) * dt) * 0.125
+    raise ValueError(f"unknown fixed-grid method {method!r}")
+
+
+RK_METHODS = ("midpoint", "heun3", "rk4")
+
+
 class Sampler:
     def __init__(self, transport: Transport):
         self.transport = transport
 
     def sample_ode(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3, reverse=False):
         """Returns fn(x0, model_fn, **model_kwargs).  `num_steps` is the number of grid points
-        (S = num_steps - 1 Euler steps), as in the reference.  The returned tensor holds only the final
+        (S = num_steps - 1 steps), as in the reference; `sampling_method`: "euler", "midpoint", "heun3" or "rk4", one step per
+        grid interval (torchdiffeq's fixed-grid solvers).  The returned tensor holds only the final
         state, shape [1, *x0.shape], so that the caller's `[-1]` (wrapper.py:447) is unchanged."""
-        if sampling_method != "euler":
+        if sampling_method != "euler" and sampling_method not in RK_METHODS:
             raise NotImplementedError(
-                "Sampler.sample_ode implements the fixed-grid Euler sampler (pass sampling_method='euler'); adaptive "
-                "dopri5 is NewMDGenWrapper.inference(..., sampling_method='dopri5') / LatentMDGenModel.sample_dopri5")
+                "Sampler.sample_ode implements the fixed-grid samplers (sampling_method='euler', 'midpoint', 'heun3', 'rk4'); "
+                "adaptive dopri5 is NewMDGenWrapper.inference(..., sampling_method='dopri5') / LatentMDGenModel.sample_dopri5")
         if reverse:
             raise NotImplementedError("reverse-time sampling is not used by the wrapper")
         S = int(num_steps) - 1
+        if sampling_method != "euler":
+            if S < 1:
+                raise ValueError(f"num_steps is the number of grid points: it must be >= 2, got {num_steps}")
+            return self._sample_rk(sampling_method, S)
 
         def _sample(x0, model_fn, **model_kwargs):
             from .model import LatentMDGenModel
@@ -107,6 +151,29 @@ class Sampler:
             for i in range(S):
                 t = torch.ones(x.shape[0], device=x.device) * tg[i]
                 x = x + (tg[i + 1] - tg[i]) * model_fn(x, t, **model_kwargs)
+            return x[None]
+
+        return _sample
+
+    @staticmethod
+    def _sample_rk(method, S):
+        def _sample(x0, model_fn, **model_kwargs):
+            from .model import LatentMDGenModel
+            fn, kw = model_fn, dict(model_kwargs)
+            use_graph = kw.pop("use_graph", True)
+            model_kwargs = dict(kw)
+            if isinstance(fn, partial):
+                kw = {**fn.keywords, **kw}
+                fn = fn.func
+            owner = getattr(fn, "__self__", None)
+            if isinstance(owner, LatentMDGenModel) and getattr(fn, "__name__", "") in ("forward", "forward_inference"):
+                return owner.sample_rk(x0, method, S, use_graph=use_graph, **kw)[None]
+            # generic drift (any callable): the same formulas in a host loop, in the callable's dtype, on the library's fp32 grid
+            tg = linspace01(S + 1).to(dtype=x0.dtype, device=x0.device)
+            ones = torch.ones(x0.shape[0], dtype=x0.dtype, device=x0.device)
+            x = x0
+            for i in range(S):
+                x = rk_step(method, lambda t, y: model_fn(y, ones * t, **model_kwargs), tg[i], tg[i + 1], x)
             return x[None]
 
         return _sample

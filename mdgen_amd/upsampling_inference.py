@@ -2,9 +2,10 @@
 (`--ckpt --data_dir --suffix --pdb_id --batch_size --out_dir --split`), plus
 
   --num_steps S      Euler steps per window (a non-Euler checkpoint is refused unless S or --sampling_method is given);
-  --sampling_method {euler,dopri5}   the solver: dopri5 is the reference's adaptive default (torchdiffeq, atol 1e-6,
-                     rtol 1e-3; one step size per call, shared by a --batch_size group); euler without --num_steps takes the
-                     reference's 49-step grid;
+  --sampling_method {euler,dopri5,midpoint,heun3,rk4}   the solver: dopri5 is the reference's adaptive default (torchdiffeq,
+                     atol 1e-6, rtol 1e-3; one step size per call, shared by a --batch_size group); euler without --num_steps
+                     takes the reference's 49-step grid; midpoint / heun3 / rk4: torchdiffeq's fixed-grid solvers with
+                     --num_steps steps (default 24 / 16 / 12 = 48 network evaluations);
   --precision {bf16,fp32}, --npy (also save the sampled array), --xtc (as `sim_inference.py`: refused before sampling
                      where mdtraj is missing);
   --synthetic        seeded weights instead of --ckpt, with --num_frames T / --cond_interval c (a checkpoint supplies both).
@@ -131,8 +132,8 @@ def build_parser():
     p.add_argument("--out_dir", type=str, default=".")
     p.add_argument("--split", type=str, default="splits/4AA_implicit_test.csv")
     p.add_argument("--num_steps", type=int, default=None,
-                   help="Euler steps per window (default: 49 = the reference's 50-point grid, Euler checkpoints only)")
-    p.add_argument("--sampling_method", choices=["euler", "dopri5"], default=None,
+                   help="solver steps per window (Euler default: 49 = the reference's 50-point grid, Euler checkpoints only)")
+    p.add_argument("--sampling_method", choices=["euler", "dopri5", "midpoint", "heun3", "rk4"], default=None,
                    help="solver (default: the checkpoint's, refused unless it is euler or --num_steps is given)")
     p.add_argument("--precision", choices=["bf16", "fp32"], default="bf16",
                    help="bf16 MFMA operands (default) or the fp32-operand tolerance mode (~10x slower)")
@@ -150,6 +151,8 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.sampling_method == "dopri5" and args.num_steps is not None:
         p.error("--num_steps sets the Euler grid; dopri5 chooses its own steps (pass one or the other)")
+    if args.num_steps is not None and args.num_steps < 1:
+        p.error(f"--num_steps must be >= 1, got {args.num_steps}")
     if not args.synthetic and (args.num_frames is not None or args.cond_interval is not None):
         p.error("--num_frames / --cond_interval go with --synthetic only (a checkpoint supplies its own)")
     if not args.synthetic and not args.ckpt:

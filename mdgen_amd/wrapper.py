@@ -17,11 +17,14 @@ from .config import ModelConfig
 from .geometry import prep_keyframes, samples_to_atom14
 from .model import LatentMDGenModel
 from .rigid_utils import Rigid, Rotation
-from .transport import Sampler, create_transport
+from .transport import RK_METHODS, Sampler, create_transport
 
 _BACKFILL = ["inpainting", "no_torsion", "hyena", "no_aa_emb", "supervise_all_torsions", "supervise_no_torsions",
              "design_key_frames", "no_design_torsion", "cond_interval", "mpnn", "dynamic_mpnn", "no_offsets",
              "no_frames", "design", "tps_condition", "sim_condition", "abs_pos_emb", "prepend_ipa", "oracle"]
+# steps of the fixed-grid Runge-Kutta solvers when num_steps is not given: 48 network evaluations each (Euler's default grid: 49)
+RK_DEFAULT_STEPS = {"midpoint": 24, "heun3": 16, "rk4": 12}
+_METHODS = (None, "euler", "dopri5") + RK_METHODS
 _UNSUPPORTED = ["inpainting", "hyena", "no_aa_emb", "design_key_frames", "mpnn", "dynamic_mpnn", "no_offsets",
                 "no_frames", "design", "no_torsion", "no_design_torsion", "interleave_ipa",
                 "abs_time_emb", "oracle", "no_rope"]
@@ -166,17 +169,22 @@ class NewMDGenWrapper:
         steps, wrapper.py:441-442 / transport.py:412), `rel_quats` (two-sided models): the relative-frame 7-vectors
         (2,B,L,7) as the caller's reference computes them (`LatentMDGenModel._rel7`; default: w >= 0 convention).
         `sampling_method="dopri5"`: the reference's adaptive solver (torchdiffeq dopri5 with `atol` / `rtol`,
-        `LatentMDGenModel.sample_dopri5`; one step size for the whole batch); its counts are kept in `last_stats`."""
+        `LatentMDGenModel.sample_dopri5`; one step size for the whole batch); its counts are kept in `last_stats`.
+        `sampling_method="midpoint" | "heun3" | "rk4"`: torchdiffeq's fixed-grid solvers with `num_steps` steps S on
+        linspace(0, 1, S + 1) (`LatentMDGenModel.sample_rk`, one hipGraph; default 24 / 16 / 12 steps = 48 network evaluations);
+        a sample's solution does not depend on its batch mates."""
         prep = self.prep_batch(batch)
         rigids = prep["rigids"]
         B, T, L_ = rigids.shape
         dev = prep["latents"].device
         if zs is None:
             zs = torch.randn(B, T, L_, self.latent_dim, device=dev)
-        if sampling_method not in (None, "euler", "dopri5"):
-            raise L.MdgenError(f"sampling_method must be None, 'euler' or 'dopri5', got {sampling_method!r}")
+        if sampling_method not in _METHODS:
+            raise L.MdgenError(f"sampling_method must be None, 'euler', 'dopri5', 'midpoint', 'heun3' or 'rk4', got {sampling_method!r}")
         if sampling_method == "dopri5" and num_steps is not None:
             raise L.MdgenError("num_steps sets the fixed Euler grid; dopri5 chooses its own steps (pass one or the other)")
+        if num_steps is not None and int(num_steps) < 1:
+            raise L.MdgenError(f"num_steps must be >= 1, got {num_steps}")
         # wrapper.py:441 samples with args.sampling_method (argparse default 'dopri5', parsing.py:102) on the
         # solver's own 50-point grid.  Without an explicit choice (sampling_method / num_steps) a non-Euler checkpoint is
         # rejected instead of being silently sampled with a different solver.
@@ -193,6 +201,10 @@ class NewMDGenWrapper:
             kw["rel_quats"] = rel_quats
         if sampling_method == "dopri5":
             samples, self.last_stats = self.model.sample_dopri5(zs, atol=atol, rtol=rtol, **kw)
+        elif sampling_method in RK_METHODS:
+            S = RK_DEFAULT_STEPS[sampling_method] if num_steps is None else int(num_steps)
+            sample_fn = self.transport_sampler.sample_ode(sampling_method=sampling_method, num_steps=S + 1)
+            samples = sample_fn(zs, partial(self.model.forward_inference, **kw), use_graph=use_graph)[-1]
         else:
             S = 49 if num_steps is None else int(num_steps)
             sample_fn = self.transport_sampler.sample_ode(sampling_method="euler", num_steps=S + 1)
@@ -211,7 +223,8 @@ class NewMDGenWrapper:
         batch element: torsions (B,K,L,7,2), trans (B,K,L,3), rots (B,K,L,3,3), seqres (B,L), mask (B,L), with
         K = ceil(T / cond_interval) and T = `num_frames` (default `args.num_frames`); key frame k is frame k * cond_interval of
         its window.  Euler: one library call (`mdgen_upsample_euler`, one hipGraph).  `sampling_method="dopri5"`:
-        `mdgen_prep_keyframes` -> `sample_dopri5` -> `samples_to_atom14`, counts in `last_stats`.  The solver rules are
+        `mdgen_prep_keyframes` -> `sample_dopri5` -> `samples_to_atom14`, counts in `last_stats`; "midpoint" | "heun3" | "rk4":
+        the same with `sample_rk` (`num_steps` steps, default 24 / 16 / 12).  The solver rules are
         `inference()`'s.  Returns (atom14 (B,T,L,14,3), aa_out (B,T,L)); the latent samples are kept in `last_samples`."""
         from .geometry import residue_tables
         c = getattr(self.args, "cond_interval", None)
@@ -223,10 +236,12 @@ class NewMDGenWrapper:
         T = int(self.args.num_frames if num_frames is None else num_frames)
         if c < 1 or T < 1:
             raise L.MdgenError(f"num_frames and cond_interval must be >= 1, got {T}, {c}")
-        if sampling_method not in (None, "euler", "dopri5"):
-            raise L.MdgenError(f"sampling_method must be None, 'euler' or 'dopri5', got {sampling_method!r}")
+        if sampling_method not in _METHODS:
+            raise L.MdgenError(f"sampling_method must be None, 'euler', 'dopri5', 'midpoint', 'heun3' or 'rk4', got {sampling_method!r}")
         if sampling_method == "dopri5" and num_steps is not None:
             raise L.MdgenError("num_steps sets the fixed Euler grid; dopri5 chooses its own steps (pass one or the other)")
+        if num_steps is not None and int(num_steps) < 1:
+            raise L.MdgenError(f"num_steps must be >= 1, got {num_steps}")
         method = getattr(self.args, "sampling_method", "euler")
         if sampling_method is None and num_steps is None and method != "euler":
             raise L.MdgenError(f"checkpoint args say sampling_method={method!r}; pass sampling_method='dopri5' (CLI: "
@@ -251,6 +266,13 @@ class NewMDGenWrapper:
             samples, self.last_stats = self.model.sample_dopri5(
                 zs, mask=mask.contiguous(), start_frames=(prep["start_rot"], prep["start_trans"]), x_cond=prep["x_cond"],
                 x_cond_mask=prep["x_cond_mask"], aatype=batch["seqres"], atol=atol, rtol=rtol)
+            atom14 = samples_to_atom14(samples, prep["start_rot"], prep["start_trans"], batch["seqres"], False)
+        elif sampling_method in RK_METHODS:
+            S = RK_DEFAULT_STEPS[sampling_method] if num_steps is None else int(num_steps)
+            prep = prep_keyframes(rots, trans, tors, T, c)
+            samples = self.model.sample_rk(
+                zs, sampling_method, S, mask=mask.contiguous(), start_frames=(prep["start_rot"], prep["start_trans"]),
+                x_cond=prep["x_cond"], x_cond_mask=prep["x_cond_mask"], aatype=batch["seqres"], use_graph=use_graph)
             atom14 = samples_to_atom14(samples, prep["start_rot"], prep["start_trans"], batch["seqres"], False)
         else:
             S = 49 if num_steps is None else int(num_steps)
