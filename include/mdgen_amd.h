@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 /* Bumped whenever a public struct or signature changes; mdgen_amd/_lib.py refuses a library whose version differs. */
-#define MDGEN_ABI_VERSION 7   /* 6: mdgen_ws_layout.split; 7: mdgen_ws_layout.fold */
+#define MDGEN_ABI_VERSION 8   /* 6: mdgen_ws_layout.split; 7: mdgen_ws_layout.fold; 8: mdgen_cond replaces nine pointer arguments */
 
 typedef struct mdgen_ctx mdgen_ctx;
 
@@ -201,25 +201,36 @@ const char* mdgen_ctx_weight_name(const mdgen_ctx* ctx, int32_t i);
 int32_t mdgen_workspace_layout(const mdgen_ctx* ctx, const mdgen_shape* shape, int32_t n_steps,
                                int32_t t_shared, mdgen_ws_layout* out);
 
+/* ---- conditioning ------------------------------------------------------------------------
+ * What every network evaluation reads besides x and t: the arguments mask, start_frames, end_frames, x_cond, x_cond_mask, aatype
+ * of `LatentMDGenModel.forward` (latent_model.py:212-216).  mask in {0,1}; x_cond_mask int64 in {0,1}; aatype int64 in [0,20];
+ * start / end frames: rot + trans, the fields of the reference's `Rigid`; end_* may be NULL unless tps_condition.
+ * rel7 (nullable; two-sided models only): the relative-frame inputs of latent_to_emb_f / _r exactly as the caller's reference
+ * computes them -- rel7[0] = (start^-1 o end).to_tensor_7(), rel7[1] = (end^-1 o start).to_tensor_7() (latent_model.py:193-195).
+ * Their quaternion SIGN is whatever torch.linalg.eigh returns (rigid_utils.py:191-210, never canonicalised on this path) and it
+ * reaches a Linear, so a checkpoint trained with the reference sees exactly its own inputs only when they are handed over; NULL:
+ * the library computes them from the frames with the sign fixed to w >= 0.
+ * A NULL struct or a NULL required field (all but end_rot, end_trans, rel7) is refused with -1. */
+typedef struct mdgen_cond {
+    const float*   mask;          /* (B,T,L) */
+    const float*   start_rot;     /* (B,L,3,3) */
+    const float*   start_trans;   /* (B,L,3) */
+    const float*   end_rot;       /* nullable unless tps_condition */
+    const float*   end_trans;
+    const float*   rel7;          /* nullable; (2,B,L,7) */
+    const float*   x_cond;        /* (B,T,L,D) */
+    const int64_t* x_cond_mask;   /* (B,T,L) */
+    const int64_t* aatype;        /* (B,L) */
+} mdgen_cond;
+
 /* ---- denoiser ----------------------------------------------------------------------------
  * `LatentMDGenModel.forward` / `.forward_inference` (latent_model.py:212-269), non-design path:
  *   out[B,T,L,D] = model(x, t, mask, start_frames, end_frames, x_cond, x_cond_mask, aatype)
- * x, x_cond, out: fp32 (B,T,L,D); t: fp32 (B); mask: fp32 (B,T,L) in {0,1};
- * x_cond_mask: int64 (B,T,L) in {0,1}; aatype: int64 (B,L) in [0,20];
- * start/end frames: rot (B,L,3,3) + trans (B,L,3) fp32 (the fields of the reference's `Rigid`);
- * end_* may be NULL unless tps_condition.  rel7 (nullable; two-sided models only): fp32 (2,B,L,7), the relative-frame inputs
- * of latent_to_emb_f / _r exactly as the caller's reference computes them -- rel7[0] = (start^-1 o end).to_tensor_7(),
- * rel7[1] = (end^-1 o start).to_tensor_7() (latent_model.py:193-195).  Their quaternion SIGN is whatever torch.linalg.eigh
- * returns (rigid_utils.py:191-210, never canonicalised on this path) and it reaches a Linear, so a checkpoint trained with
- * the reference sees exactly its own inputs only when they are handed over; NULL: the library computes them from the
- * frames with the sign fixed to w >= 0.  trace_h (nullable): fp32 [(num_layers+1)][N][384],
+ * x, out: fp32 (B,T,L,D); t: fp32 (B); the conditioning: mdgen_cond above.  trace_h (nullable): fp32 [(num_layers+1)][N][384],
  * the residual stream before layer 0 and after every trunk layer; trace_ipa (nullable): fp32
  * [B*L][384], the IPA-stack output (latent_model.py:245-246). */
 int32_t mdgen_denoiser_forward(mdgen_ctx* ctx, const mdgen_shape* shape,
-                               const float* x, const float* t, const float* mask,
-                               const float* start_rot, const float* start_trans,
-                               const float* end_rot, const float* end_trans, const float* rel7,
-                               const float* x_cond, const int64_t* x_cond_mask, const int64_t* aatype,
+                               const float* x, const float* t, const mdgen_cond* cond,
                                float* out, float* trace_h, float* trace_ipa,
                                void* workspace, size_t workspace_bytes, void* stream);
 
@@ -230,10 +241,7 @@ int32_t mdgen_denoiser_forward(mdgen_ctx* ctx, const mdgen_shape* shape,
  * wrapper.py:447).  use_graph=1 captures the whole rollout into a hipGraph on first use (keyed on
  * shape + pointers) and replays it afterwards; `stream` must then be a non-default stream. */
 int32_t mdgen_sample_euler(mdgen_ctx* ctx, const mdgen_shape* shape, int32_t n_steps,
-                           float* x, const float* mask,
-                           const float* start_rot, const float* start_trans,
-                           const float* end_rot, const float* end_trans, const float* rel7,
-                           const float* x_cond, const int64_t* x_cond_mask, const int64_t* aatype,
+                           float* x, const mdgen_cond* cond,
                            void* workspace, size_t workspace_bytes, int32_t use_graph, void* stream);
 
 /* The reference's default solver: `sample_ode(sampling_method='dopri5')` -> torchdiffeq 0.2.x
@@ -251,10 +259,7 @@ int32_t mdgen_sample_euler(mdgen_ctx* ctx, const mdgen_shape* shape, int32_t n_s
  * and `stream` is synchronised.  A stream that is being captured is refused (-8) before anything is enqueued.  Errors:
  * -9 non-finite norm / error ratio, -10 more than max_steps attempts, -11 dt underflow (t0 + dt == t0). */
 int32_t mdgen_sample_dopri5(mdgen_ctx* ctx, const mdgen_shape* shape, double atol, double rtol, int32_t max_steps,
-                            float* x, const float* mask,
-                            const float* start_rot, const float* start_trans,
-                            const float* end_rot, const float* end_trans, const float* rel7,
-                            const float* x_cond, const int64_t* x_cond_mask, const int64_t* aatype,
+                            float* x, const mdgen_cond* cond,
                             void* workspace, size_t workspace_bytes, int32_t* stats_host, double* steps_host, void* stream);
 int32_t mdgen_dopri5_workspace_bytes(const mdgen_ctx* ctx, const mdgen_shape* shape, size_t* bytes);
 
@@ -277,10 +282,7 @@ int32_t mdgen_debug_dopri5_controller(const double* init, const double* ratios, 
  *   workspace    mdgen_rk_workspace_bytes: the network workspace for the call's t-shared time rows (2 S, 3 S, 3 S + 1) + 4 velocities
  * The state of a stage is formed inside the launch that embeds it (k_rk_embed) and never written to memory.
  * Errors: -1 null argument, -2 unknown method or n_steps < 1, -7 alignment / workspace size. */
-int32_t mdgen_sample_rk(mdgen_ctx* ctx, const mdgen_shape* shape, int32_t method, int32_t n_steps, float* x, const float* mask,
-                        const float* start_rot, const float* start_trans,
-                        const float* end_rot, const float* end_trans, const float* rel7,
-                        const float* x_cond, const int64_t* x_cond_mask, const int64_t* aatype,
+int32_t mdgen_sample_rk(mdgen_ctx* ctx, const mdgen_shape* shape, int32_t method, int32_t n_steps, float* x, const mdgen_cond* cond,
                         void* workspace, size_t workspace_bytes, int32_t use_graph, void* stream);
 int32_t mdgen_rk_workspace_bytes(const mdgen_ctx* ctx, const mdgen_shape* shape, int32_t method, int32_t n_steps, size_t* bytes);
 
@@ -570,7 +572,7 @@ int32_t mdgen_ema_update(int64_t n, float* ema, const float* params, float decay
  * context's i-th state_dict key (mdgen_ctx_weight_name; -1 = do not compute / frozen).  Runs the fp32-operand form of
  * the network (option keep_fp32_weights must have been set before the weights were handed over), with a tape in
  * `tape` (mdgen_train_workspace_bytes; 256-byte aligned); `workspace` as for mdgen_denoiser_forward (n_steps 1,
- * t_shared 0).  Forward-simulation models (end_rot / end_trans NULL) and the two-sided TPS model (end frames
+ * t_shared 0).  Forward-simulation models (end_rot, end_trans, rel7 of `cond` are not read) and the two-sided TPS model (end frames
  * required; its IPA stack runs twice on shared weights, latent_model.py:193-205).  xt, target, loss_mask, pred:
  * (B,T,L,D); t, loss: (B). */
 int32_t mdgen_train_workspace_bytes(const mdgen_ctx* ctx, const mdgen_shape* shape, size_t* bytes);
@@ -587,10 +589,7 @@ int32_t mdgen_train_bind_params(mdgen_ctx* ctx, float* flat, const int64_t* offs
 int32_t mdgen_train_num_milestones(const mdgen_ctx* ctx);
 int32_t mdgen_train_set_milestone_events(mdgen_ctx* ctx, void* const* events, int32_t n);
 int32_t mdgen_train_forward_backward(mdgen_ctx* ctx, const mdgen_shape* shape, const float* xt, const float* t,
-                                     const float* mask, const float* start_rot, const float* start_trans,
-                                     const float* end_rot, const float* end_trans, const float* rel7,
-                                     const float* x_cond, const int64_t* x_cond_mask, const int64_t* aatype,
-                                     const float* target, const float* loss_mask, float* loss, float* pred,
+                                     const mdgen_cond* cond, const float* target, const float* loss_mask, float* loss, float* pred,
                                      float* grads, const int64_t* grad_offsets, void* workspace, size_t workspace_bytes,
                                      void* tape, size_t tape_bytes, void* stream);
 

@@ -10,7 +10,7 @@ import torch  # noqa: F401  -- must be imported first: provides the process-wide
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MDGEN_AMD_LIB", os.path.join(_HERE, "libmdgen_amd.so"))   # override: debugging builds only
 
-ABI_VERSION = 7   # include/mdgen_amd.h MDGEN_ABI_VERSION
+ABI_VERSION = 8   # include/mdgen_amd.h MDGEN_ABI_VERSION
 
 EXPORTS = [
     "mdgen_last_error", "mdgen_abi_version", "mdgen_dev_build", "mdgen_ctx_create", "mdgen_ctx_destroy", "mdgen_ctx_set_weight",
@@ -50,6 +50,17 @@ class ResidueTables(C.Structure):
         "default_frames", "lit_positions", "atom14_group", "atom14_mask", "atom37_to_atom14", "atom37_mask",
         "chi_atom_indices", "chi_angles_mask")]
 
+    @classmethod
+    def from_dict(cls, tables):
+        """From a dict of device tensors under the field names (geometry.residue_tables)."""
+        return cls(*[tables[n].data_ptr() for n, _ in cls._fields_])
+
+
+class Cond(C.Structure):
+    """mdgen_cond: the conditioning pointers of a network evaluation.  Build it with `cond()`."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "mask", "start_rot", "start_trans", "end_rot", "end_trans", "rel7", "x_cond", "x_cond_mask", "aatype")]
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -70,18 +81,22 @@ def _load():
     lib.mdgen_ctx_weight_name.argtypes = [vp, i32]
     lib.mdgen_ctx_weight_name.restype = C.c_char_p
     lib.mdgen_workspace_layout.argtypes = [vp, C.POINTER(Shape), i32, i32, C.POINTER(WsLayout)]
-    lib.mdgen_denoiser_forward.argtypes = [vp, C.POINTER(Shape)] + [vp] * 15 + [sz, vp]
-    lib.mdgen_sample_euler.argtypes = [vp, C.POINTER(Shape), i32] + [vp] * 11 + [sz, i32, vp]
+    ctx_shape, cond_p, ws_bytes = [vp, C.POINTER(Shape)], C.POINTER(Cond), [vp, sz]   # (ctx, shape) | mdgen_cond* | (workspace, bytes)
+    lib.mdgen_denoiser_forward.argtypes = ctx_shape + [vp, vp, cond_p] + [vp, vp, vp] + ws_bytes + [vp]   # x, t | out, trace_h, trace_ipa
+    lib.mdgen_sample_euler.argtypes = ctx_shape + [i32, vp, cond_p] + ws_bytes + [i32, vp]
     f64 = C.c_double
-    lib.mdgen_sample_dopri5.argtypes = [vp, C.POINTER(Shape), f64, f64, i32] + [vp] * 10 + [vp, sz, C.POINTER(i32), vp, vp]
+    lib.mdgen_sample_dopri5.argtypes = ctx_shape + [f64, f64, i32, vp, cond_p] + ws_bytes + [C.POINTER(i32), vp, vp]
     lib.mdgen_dopri5_workspace_bytes.argtypes = [vp, C.POINTER(Shape), C.POINTER(sz)]
     lib.mdgen_debug_dopri5_controller.argtypes = [vp, vp, i32, i32] + [vp] * 7
-    lib.mdgen_sample_rk.argtypes = [vp, C.POINTER(Shape), i32, i32] + [vp] * 11 + [sz, i32, vp]
+    lib.mdgen_sample_rk.argtypes = ctx_shape + [i32, i32, vp, cond_p] + ws_bytes + [i32, vp]
     lib.mdgen_rk_workspace_bytes.argtypes = [vp, C.POINTER(Shape), i32, i32, C.POINTER(sz)]
     lib.mdgen_debug_rk_plan.argtypes = [i32, i32, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)]
     lib.mdgen_debug_rk_stage.argtypes = [vp, C.POINTER(Shape), i32, i32, C.c_float] + [vp] * 10
-    lib.mdgen_rollout_euler.argtypes = [vp, C.POINTER(Shape), i32, i32] + [vp] * 8 + [C.POINTER(ResidueTables), vp, vp, sz, i32, vp]
-    lib.mdgen_upsample_euler.argtypes = [vp, C.POINTER(Shape), i32, i32] + [vp] * 10 + [C.POINTER(ResidueTables), vp, vp, sz, i32, vp]
+    tables_atom14 = [C.POINTER(ResidueTables), vp]
+    lib.mdgen_rollout_euler.argtypes = (ctx_shape + [i32, i32] + [vp, vp] + [vp, vp, vp] + [vp] + [vp, vp]   # zs, mask | cond frame | seqres | x_cond, its mask
+                                        + tables_atom14 + ws_bytes + [i32, vp])
+    lib.mdgen_upsample_euler.argtypes = (ctx_shape + [i32, i32] + [vp, vp] + [vp, vp, vp] + [vp] + [vp, vp] + [vp, vp]   # ... | key frames | ... | start_rot, start_trans
+                                         + tables_atom14 + ws_bytes + [i32, vp])
     lib.mdgen_profile_enable.argtypes = [vp, i32]
     lib.mdgen_profile_phase_trace.argtypes = [vp, vp, i64]
     lib.mdgen_profile_report.argtypes = [vp, vp, C.c_char_p, sz]
@@ -114,7 +129,8 @@ def _load():
     lib.mdgen_train_num_milestones.argtypes = [vp]
     lib.mdgen_train_bind_params.argtypes = [vp, vp, C.POINTER(i64)]
     lib.mdgen_train_set_milestone_events.argtypes = [vp, C.POINTER(vp), i32]
-    lib.mdgen_train_forward_backward.argtypes = [vp, C.POINTER(Shape)] + [vp] * 17 + [vp, sz, vp, sz, vp]
+    lib.mdgen_train_forward_backward.argtypes = (ctx_shape + [vp, vp, cond_p] + [vp, vp] + [vp, vp] + [vp, vp]   # xt, t | target, loss_mask | loss, pred | grads, offsets
+                                                 + ws_bytes + [vp, sz] + [vp])   # ... | tape, bytes | stream
     for n in EXPORTS:
         getattr(lib, n)
         if n not in ("mdgen_last_error", "mdgen_ctx_weight_name"):
@@ -155,6 +171,13 @@ def ptr(t, dtype=None):
     if not t.is_contiguous():
         raise MdgenError("tensor must be contiguous")
     return C.c_void_p(t.data_ptr())
+
+
+def cond(mask, start_rot, start_trans, end_rot, end_trans, rel7, x_cond, x_cond_mask, aatype):
+    """`Cond` of contiguous device tensors (None -> NULL); fp32, the last two int64.  Keep it alive across the call that takes it."""
+    f32, i64 = torch.float32, torch.int64
+    return Cond(*[ptr(t, dt) for t, dt in ((mask, f32), (start_rot, f32), (start_trans, f32), (end_rot, f32), (end_trans, f32),
+                                           (rel7, f32), (x_cond, f32), (x_cond_mask, i64), (aatype, i64))])
 
 
 def stream_ptr(device=None):

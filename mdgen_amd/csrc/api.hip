@@ -14,6 +14,7 @@
 #include <functional>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace mdg;
@@ -1827,6 +1828,27 @@ static int make_run(Run* r, mdgen_ctx* c, const mdgen_shape* sh, int S, int t_sh
     return 0;
 }
 
+// The conditioning of a call (include/mdgen_amd.h mdgen_cond): refused when the struct or a required field is null ...
+static_assert(sizeof(mdgen_cond) == 9 * sizeof(void*), "mdgen_cond is nine pointers (GraphKey::add_struct, _lib.py Cond)");
+static int check_cond(const mdgen_cond* cd) {
+    if (!cd) return fail(-1, "null conditioning (mdgen_cond)");
+    if (!cd->mask || !cd->start_rot || !cd->start_trans || !cd->x_cond || !cd->x_cond_mask || !cd->aatype)
+        return fail(-1, "null tensor argument");
+    return 0;
+}
+// ... and the one place that hands it to a made run
+static void bind_cond(Run& r, const mdgen_cond& cd) {
+    r.mask = cd.mask;
+    r.start_rot = cd.start_rot;
+    r.start_trans = cd.start_trans;
+    r.end_rot = cd.end_rot;
+    r.end_trans = cd.end_trans;
+    r.rel7_in = cd.rel7;
+    r.x_cond = cd.x_cond;
+    r.x_cond_mask = cd.x_cond_mask;
+    r.aatype = cd.aatype;
+}
+
 // mdgen_denoiser_forward on a made run: the batch's views one after the other on the caller's stream
 static int forward_body(Run& r, const float* x, const float* t, float* out, float* trace_h, float* trace_ipa) {
     const int nv = r.c->opt_precision == 32 ? 1 : plan_views(r.B, r.T, r.L, 1);
@@ -1842,24 +1864,14 @@ static int forward_body(Run& r, const float* x, const float* t, float* out, floa
 }
 
 extern "C" int32_t mdgen_denoiser_forward(mdgen_ctx* c, const mdgen_shape* sh, const float* x, const float* t,
-                                          const float* mask, const float* start_rot, const float* start_trans,
-                                          const float* end_rot, const float* end_trans, const float* rel7,
-                                          const float* x_cond, const int64_t* x_cond_mask, const int64_t* aatype, float* out,
-                                          float* trace_h, float* trace_ipa, void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !t || !mask || !start_rot || !start_trans || !x_cond || !x_cond_mask || !aatype || !out)
-        return fail(-1, "null tensor argument");
+                                          const mdgen_cond* cond, float* out, float* trace_h, float* trace_ipa, void* ws,
+                                          size_t ws_bytes, void* stream) {
+    if (!x || !t || !out) return fail(-1, "null tensor argument");
+    if (int e = check_cond(cond)) return e;
     Run r{};
     const int t_shared = (sh && sh->B == 1) ? 1 : 0;
     if (int e = make_run(&r, c, sh, 1, t_shared, f32_path(c), ws, ws_bytes, stream)) return e;
-    r.mask = mask;
-    r.start_rot = start_rot;
-    r.start_trans = start_trans;
-    r.end_rot = end_rot;
-    r.end_trans = end_trans;
-    r.rel7_in = rel7;
-    r.x_cond = x_cond;
-    r.x_cond_mask = x_cond_mask;
-    r.aatype = aatype;
+    bind_cond(r, *cond);
     return forward_body(r, x, t, out, trace_h, trace_ipa);
 }
 
@@ -1920,6 +1932,28 @@ static uint64_t graph_option_key(const mdgen_ctx* c) {
     return k;
 }
 
+// A graph's cache key: every value and every pointer that the captured body bakes into the graph.  A body reads its pointers from
+// structs (mdgen_cond, mdgen_residue_tables); those structs go into the key whole, word by word -- never a chosen subset of them.
+struct GraphKey {
+    std::vector<uint64_t> v;
+    GraphKey& add(uint64_t x) { v.push_back(x); return *this; }
+    GraphKey& ptr(const void* p) { return add((uint64_t)(uintptr_t)p); }
+    template <class T> GraphKey& add_struct(const T& t) {
+        static_assert(sizeof(T) % sizeof(uint64_t) == 0 && std::is_trivially_copyable<T>::value, "a struct of pointer-sized words");
+        const size_t n = v.size();
+        v.resize(n + sizeof(T) / sizeof(uint64_t));
+        std::memcpy(&v[n], &t, sizeof(T));
+        return *this;
+    }
+};
+// The part every capturing entry point shares: its tag, the shape, the conditioning it bound, the workspace and the options.  The entry
+// point adds its scalar arguments, its state / output pointers, its residue tables and, where its body forks, n_streams(r).
+static GraphKey graph_key(uint64_t tag, const Run& r, const mdgen_cond& cd) {
+    GraphKey k;
+    k.add(tag).add(r.B).add(r.T).add(r.L).add_struct(cd).ptr(r.ws).add(graph_option_key(r.c));
+    return k;
+}
+
 // Replay the cached hipGraph for `key`, or capture `body` (which enqueues work on `s`, possibly forking onto the
 // context's side streams and joining back) into a new one, cache it (LRU, 8 entries) and launch it.
 static int replay_or_capture(mdgen_ctx* c, const std::vector<uint64_t>& key, hipStream_t s, const std::function<int()>& body) {
@@ -1964,32 +1998,24 @@ static int replay_or_capture(mdgen_ctx* c, const std::vector<uint64_t>& key, hip
     return 0;
 }
 
-extern "C" int32_t mdgen_sample_euler(mdgen_ctx* c, const mdgen_shape* sh, int32_t S, float* x, const float* mask,
-                                      const float* start_rot, const float* start_trans, const float* end_rot,
-                                      const float* end_trans, const float* rel7, const float* x_cond,
-                                      const int64_t* x_cond_mask, const int64_t* aatype, void* ws, size_t ws_bytes,
-                                      int32_t use_graph, void* stream) {
-    if (!x || !mask || !start_rot || !start_trans || !x_cond || !x_cond_mask || !aatype)
-        return fail(-1, "null tensor argument");
+// The capture gate of every capturing entry point: `body` runs directly without use_graph and while profiling (see mdgen_profile_enable)
+static int run_or_replay(const Run& r, int use_graph, const GraphKey& key, const std::function<int()>& body) {
+    if (!use_graph || r.c->prof_on) return body();
+    return replay_or_capture(r.c, key.v, r.s, body);
+}
+
+extern "C" int32_t mdgen_sample_euler(mdgen_ctx* c, const mdgen_shape* sh, int32_t S, float* x, const mdgen_cond* cond, void* ws,
+                                      size_t ws_bytes, int32_t use_graph, void* stream) {
+    if (!x) return fail(-1, "null tensor argument");
+    if (int e = check_cond(cond)) return e;
     Run r{};
     if (int e = make_run(&r, c, sh, S, 1, f32_path(c), ws, ws_bytes, stream)) return e;
-    r.mask = mask;
-    r.start_rot = start_rot;
-    r.start_trans = start_trans;
-    r.end_rot = end_rot;
-    r.end_trans = end_trans;
-    r.rel7_in = rel7;
-    r.x_cond = x_cond;
-    r.x_cond_mask = x_cond_mask;
-    r.aatype = aatype;
+    bind_cond(r, *cond);
     std::vector<float> tg;
     linspace01(S + 1, &tg);   // integrators.py:88  th.linspace(t0, t1, num_steps)
-    if (!use_graph || c->prof_on) return euler_body(r, tg, x);
-    std::vector<uint64_t> key = {0u, (uint64_t)sh->B, (uint64_t)sh->T, (uint64_t)sh->L, (uint64_t)S, (uint64_t)x,
-                                 (uint64_t)mask, (uint64_t)start_rot, (uint64_t)start_trans, (uint64_t)end_rot,
-                                 (uint64_t)end_trans, (uint64_t)x_cond, (uint64_t)x_cond_mask, (uint64_t)aatype,
-                                 (uint64_t)ws, (uint64_t)n_streams(r), graph_option_key(c), (uint64_t)rel7};
-    return replay_or_capture(c, key, r.s, [&]() { return euler_body(r, tg, x); });
+    GraphKey key = graph_key(0, r, *cond);
+    key.add(S).ptr(x).add(n_streams(r));
+    return run_or_replay(r, use_graph, key, [&]() { return euler_body(r, tg, x); });
 }
 
 // Multi-block rollout (sim_inference.py:61-98, 110-113) as ONE call / ONE hipGraph: per block
@@ -2002,8 +2028,9 @@ extern "C" int32_t mdgen_rollout_euler(mdgen_ctx* c, const mdgen_shape* sh, int3
                                        const int64_t* seqres, float* x_cond, int64_t* x_cond_mask,
                                        const mdgen_residue_tables* tb, float* atom14, void* ws, size_t ws_bytes,
                                        int32_t use_graph, void* stream) {
-    if (!zs || !mask || !cond_rots || !cond_trans || !cond_torsions || !seqres || !x_cond || !x_cond_mask || !tb || !atom14)
-        return fail(-1, "null tensor argument");
+    if (!zs || !cond_torsions || !tb || !atom14) return fail(-1, "null tensor argument");
+    const mdgen_cond cd = {mask, cond_rots, cond_trans, nullptr, nullptr, nullptr, x_cond, x_cond_mask, seqres};
+    if (int e = check_cond(&cd)) return e;
     if (!tb->default_frames || !tb->lit_positions || !tb->atom14_group || !tb->atom14_mask || !tb->atom37_to_atom14 ||
         !tb->atom37_mask || !tb->chi_atom_indices || !tb->chi_angles_mask)
         return fail(-1, "null residue table");
@@ -2012,14 +2039,7 @@ extern "C" int32_t mdgen_rollout_euler(mdgen_ctx* c, const mdgen_shape* sh, int3
     Run r{};
     if (int e = make_run(&r, c, sh, S, 1, f32_path(c), ws, ws_bytes, stream)) return e;
     if ((long)n_blocks * sh->T > 2000000000L / ((long)sh->L * 42)) return fail(-2, "trajectory too long for one call");
-    r.mask = mask;
-    r.start_rot = cond_rots;
-    r.start_trans = cond_trans;
-    r.end_rot = nullptr;
-    r.end_trans = nullptr;
-    r.x_cond = x_cond;
-    r.x_cond_mask = x_cond_mask;
-    r.aatype = seqres;
+    bind_cond(r, cd);
     std::vector<float> tg;
     linspace01(S + 1, &tg);
     const mdgen_residue_tables t = *tb;
@@ -2043,13 +2063,9 @@ extern "C" int32_t mdgen_rollout_euler(mdgen_ctx* c, const mdgen_shape* sh, int3
         }
         return 0;
     };
-    if (!use_graph || c->prof_on) return body();
-    std::vector<uint64_t> key = {1u, (uint64_t)sh->B, (uint64_t)sh->T, (uint64_t)sh->L, (uint64_t)S, (uint64_t)n_blocks,
-                                 (uint64_t)zs, (uint64_t)mask, (uint64_t)cond_rots, (uint64_t)cond_trans,
-                                 (uint64_t)cond_torsions, (uint64_t)seqres, (uint64_t)x_cond, (uint64_t)x_cond_mask,
-                                 (uint64_t)atom14, (uint64_t)ws, (uint64_t)n_streams(r), graph_option_key(c),
-                                 (uint64_t)t.default_frames, (uint64_t)t.atom37_to_atom14};
-    return replay_or_capture(c, key, r.s, body);
+    GraphKey key = graph_key(1, r, cd);
+    key.add(S).add(n_blocks).ptr(zs).ptr(cond_torsions).ptr(atom14).add_struct(t).add(n_streams(r));
+    return run_or_replay(r, use_graph, key, body);
 }
 
 // Trajectory upsampling (upsampling_inference.py:47-82 around wrapper.py:283-365, 405-484) as ONE call / ONE hipGraph:
@@ -2062,22 +2078,15 @@ extern "C" int32_t mdgen_upsample_euler(mdgen_ctx* c, const mdgen_shape* sh, int
                                         const float* key_torsions, const int64_t* seqres, float* x_cond, int64_t* x_cond_mask,
                                         float* start_rot, float* start_trans, const mdgen_residue_tables* tb, float* atom14,
                                         void* ws, size_t ws_bytes, int32_t use_graph, void* stream) {
-    if (!zs || !mask || !key_rots || !key_trans || !key_torsions || !seqres || !x_cond || !x_cond_mask || !start_rot ||
-        !start_trans || !tb || !atom14)
-        return fail(-1, "null tensor argument");
+    if (!zs || !key_rots || !key_trans || !key_torsions || !tb || !atom14) return fail(-1, "null tensor argument");
+    const mdgen_cond cd = {mask, start_rot, start_trans, nullptr, nullptr, nullptr, x_cond, x_cond_mask, seqres};
+    if (int e = check_cond(&cd)) return e;
     if (!tb->default_frames || !tb->lit_positions || !tb->atom14_group || !tb->atom14_mask) return fail(-1, "null residue table");
     if (cond_interval < 1) return fail(-2, "cond_interval must be >= 1");
     if (c && c->d.tps_condition) return fail(-2, "upsampling is defined for forward-simulation models (sim_condition)");
     Run r{};
     if (int e = make_run(&r, c, sh, S, 1, f32_path(c), ws, ws_bytes, stream)) return e;
-    r.mask = mask;
-    r.start_rot = start_rot;
-    r.start_trans = start_trans;
-    r.end_rot = nullptr;
-    r.end_trans = nullptr;
-    r.x_cond = x_cond;
-    r.x_cond_mask = x_cond_mask;
-    r.aatype = seqres;
+    bind_cond(r, cd);
     std::vector<float> tg;
     linspace01(S + 1, &tg);
     const mdgen_residue_tables t = *tb;
@@ -2091,14 +2100,9 @@ extern "C" int32_t mdgen_upsample_euler(mdgen_ctx* c, const mdgen_shape* sh, int
         LAUNCHCHK();
         return 0;
     };
-    if (!use_graph || c->prof_on) return body();
-    std::vector<uint64_t> key = {2u, (uint64_t)sh->B, (uint64_t)sh->T, (uint64_t)sh->L, (uint64_t)S, (uint64_t)cond_interval,
-                                 (uint64_t)zs, (uint64_t)mask, (uint64_t)key_rots, (uint64_t)key_trans,
-                                 (uint64_t)key_torsions, (uint64_t)seqres, (uint64_t)x_cond, (uint64_t)x_cond_mask,
-                                 (uint64_t)start_rot, (uint64_t)start_trans, (uint64_t)atom14, (uint64_t)ws,
-                                 (uint64_t)n_streams(r), graph_option_key(c), (uint64_t)t.default_frames,
-                                 (uint64_t)t.lit_positions, (uint64_t)t.atom14_group, (uint64_t)t.atom14_mask};
-    return replay_or_capture(c, key, r.s, body);
+    GraphKey key = graph_key(2, r, cd);
+    key.add(S).add(cond_interval).ptr(zs).ptr(key_rots).ptr(key_trans).ptr(key_torsions).ptr(atom14).add_struct(t).add(n_streams(r));
+    return run_or_replay(r, use_graph, key, body);
 }
 
 #include "ode.inc"
@@ -2185,8 +2189,9 @@ extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_st
     Run r{};
     if (int e = make_run(&r, c, sh, S, t_shared, f32_path(c), (void*)4096, (size_t)1 << 60, nullptr)) return e;
     float* fake = (float*)4096;   // never dereferenced: plan mode launches nothing
-    r.mask = r.start_rot = r.start_trans = r.end_rot = r.end_trans = r.x_cond = fake;
-    r.x_cond_mask = r.aatype = (const int64_t*)fake;
+    const mdgen_cond cd = {fake, fake, fake, fake, fake, nullptr, fake, (const int64_t*)fake, (const int64_t*)fake};
+    if (int e = check_cond(&cd)) return e;
+    bind_cond(r, cd);
     const int ns = fwd || mode >= 4 ? 1 : n_streams(r);
     const int nv = plan_views(r.B, r.T, r.L, ns);
     if (mode == 4) {

@@ -219,12 +219,10 @@ static int ode_read(mdgen_ctx* c, const OdeBufs& b, hipStream_t s, double* v0, d
 }
 
 extern "C" int32_t mdgen_sample_dopri5(mdgen_ctx* c, const mdgen_shape* sh, double atol, double rtol, int32_t max_steps, float* x,
-                                       const float* mask, const float* start_rot, const float* start_trans, const float* end_rot,
-                                       const float* end_trans, const float* rel7, const float* x_cond, const int64_t* x_cond_mask,
-                                       const int64_t* aatype, void* ws, size_t ws_bytes, int32_t* stats_host, double* steps_host,
+                                       const mdgen_cond* cond, void* ws, size_t ws_bytes, int32_t* stats_host, double* steps_host,
                                        void* stream) {
-    if (!x || !mask || !start_rot || !start_trans || !x_cond || !x_cond_mask || !aatype || !stats_host)
-        return fail(-1, "null argument");
+    if (!x || !stats_host) return fail(-1, "null argument");
+    if (int e = check_cond(cond)) return e;
     stats_host[0] = stats_host[1] = stats_host[2] = 0;
     if (!(atol >= 0) || !(rtol >= 0) || !(atol + rtol > 0) || !std::isfinite(atol) || !std::isfinite(rtol))
         return fail(-2, "atol, rtol must be finite, >= 0, not both 0");
@@ -244,15 +242,7 @@ extern "C" int32_t mdgen_sample_dopri5(mdgen_ctx* c, const mdgen_shape* sh, doub
     if (int e = mdgen_workspace_layout(c, sh, ode::kStages, 1, &lay)) return e;
     Run r{};
     if (int e = make_run(&r, c, sh, ode::kStages, 1, f32_path(c), ws, lay.total_bytes, stream)) return e;
-    r.mask = mask;
-    r.start_rot = start_rot;
-    r.start_trans = start_trans;
-    r.end_rot = end_rot;
-    r.end_trans = end_trans;
-    r.rel7_in = rel7;
-    r.x_cond = x_cond;
-    r.x_cond_mask = x_cond_mask;
-    r.aatype = aatype;
+    bind_cond(r, *cond);
     r.no_embed_tail = true;
     if (!c->ode_host) HIPCHK(hipHostMalloc((void**)&c->ode_host, 2 * sizeof(double), hipHostMallocDefault));
     const int nv = c->opt_precision == 32 ? 1 : plan_views(r.B, r.T, r.L, 1);
@@ -508,11 +498,10 @@ static int rk_body(const Run& r_in, const rk::Method& m, int S, const RkPlan& pl
     return launch(r, "ode_rk_update", [&] { launch_rk_update(last, (long)r.N * r.D, r.s); });
 }
 
-extern "C" int32_t mdgen_sample_rk(mdgen_ctx* c, const mdgen_shape* sh, int32_t method, int32_t S, float* x, const float* mask,
-                                   const float* start_rot, const float* start_trans, const float* end_rot, const float* end_trans,
-                                   const float* rel7, const float* x_cond, const int64_t* x_cond_mask, const int64_t* aatype, void* ws,
-                                   size_t ws_bytes, int32_t use_graph, void* stream) {
-    if (!x || !mask || !start_rot || !start_trans || !x_cond || !x_cond_mask || !aatype) return fail(-1, "null argument");
+extern "C" int32_t mdgen_sample_rk(mdgen_ctx* c, const mdgen_shape* sh, int32_t method, int32_t S, float* x, const mdgen_cond* cond,
+                                   void* ws, size_t ws_bytes, int32_t use_graph, void* stream) {
+    if (!x) return fail(-1, "null argument");
+    if (int e = check_cond(cond)) return e;
     RkPlan pl;
     mdgen_ws_layout lay;
     if (int e = rk_layout(c, sh, method, S, &pl, &lay)) return e;
@@ -522,26 +511,15 @@ extern "C" int32_t mdgen_sample_rk(mdgen_ctx* c, const mdgen_shape* sh, int32_t 
     if (ws_bytes < need) return fail(-7, "workspace too small: %zu < %zu bytes (mdgen_rk_workspace_bytes)", ws_bytes, need);
     Run r{};
     if (int e = make_run(&r, c, sh, (int)pl.rows.size(), 1, f32_path(c), ws, lay.total_bytes, stream)) return e;
-    r.mask = mask;
-    r.start_rot = start_rot;
-    r.start_trans = start_trans;
-    r.end_rot = end_rot;
-    r.end_trans = end_trans;
-    r.rel7_in = rel7;
-    r.x_cond = x_cond;
-    r.x_cond_mask = x_cond_mask;
-    r.aatype = aatype;
+    bind_cond(r, *cond);
     r.no_embed_tail = true;
     const int nv = c->opt_precision == 32 ? 1 : plan_views(r.B, r.T, r.L, 1);
     if (nv == 0) return fail(-2, "sample too large for one launch");
     float* k[kRkMaxK];
     for (int j = 0; j < kRkMaxK; ++j) k[j] = (float*)((unsigned char*)ws + align256(lay.total_bytes) + (size_t)j * sb);
-    if (!use_graph || c->prof_on) return rk_body(r, m, S, pl, nv, x, k);
-    std::vector<uint64_t> key = {3u, (uint64_t)sh->B, (uint64_t)sh->T, (uint64_t)sh->L, (uint64_t)method, (uint64_t)S, (uint64_t)x,
-                                 (uint64_t)mask, (uint64_t)start_rot, (uint64_t)start_trans, (uint64_t)end_rot,
-                                 (uint64_t)end_trans, (uint64_t)x_cond, (uint64_t)x_cond_mask, (uint64_t)aatype,
-                                 (uint64_t)ws, graph_option_key(c), (uint64_t)rel7};
-    return replay_or_capture(c, key, r.s, [&]() { return rk_body(r, m, S, pl, nv, x, k); });
+    GraphKey key = graph_key(3, r, *cond);
+    key.add(method).add(S).ptr(x);   // (the body does not fork: no n_streams)
+    return run_or_replay(r, use_graph, key, [&]() { return rk_body(r, m, S, pl, nv, x, k); });
 }
 
 // Host-only test hook: the time rows mdgen_sample_rk prepares for (method, S), as fp32 bits, and the row of every (step, stage).

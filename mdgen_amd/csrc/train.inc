@@ -1014,18 +1014,17 @@ extern "C" int32_t mdgen_train_workspace_bytes(const mdgen_ctx* c, const mdgen_s
 }
 
 extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape* sh, const float* xt, const float* tvals,
-                                                const float* mask, const float* start_rot, const float* start_trans,
-                                                const float* end_rot, const float* end_trans, const float* rel7,
-                                                const float* x_cond, const int64_t* x_cond_mask, const int64_t* aatype,
-                                                const float* target, const float* loss_mask, float* loss, float* pred,
+                                                const mdgen_cond* cond, const float* target, const float* loss_mask, float* loss, float* pred,
                                                 float* grads, const int64_t* grad_offsets, void* ws, size_t ws_bytes,
                                                 void* tape, size_t tape_bytes, void* stream) {
-    if (!xt || !tvals || !mask || !start_rot || !start_trans || !x_cond || !x_cond_mask || !aatype || !target || !loss_mask ||
-        !loss || !pred || !grads || !grad_offsets || !tape)
+    if (!xt || !tvals || !target || !loss_mask || !loss || !pred || !grads || !grad_offsets || !tape)
         return fail(-1, "null tensor argument");
+    if (int e = check_cond(cond)) return e;
     if (!c) return fail(-1, "null context");
     const bool two = c->d.tps_condition != 0;
-    if (two && (!end_rot || !end_trans)) return fail(-2, "tps_condition requires end frames");
+    mdgen_cond cd = *cond;
+    if (!two) cd.end_rot = cd.end_trans = cd.rel7 = nullptr;   // a one-sided model reads neither
+    if (two && (!cd.end_rot || !cd.end_trans)) return fail(-2, "tps_condition requires end frames");
     if (!c->opt_keep_fp32 || !c->any_f32()) return fail(-6, "the training step runs on the fp32 weight copies: option keep_fp32_weights");
     Train t;
     t.c = c;
@@ -1037,8 +1036,7 @@ extern "C" int32_t mdgen_train_forward_backward(mdgen_ctx* c, const mdgen_shape*
     t.bf16 = c->opt_train_precision == 16;
     if (int e = make_run(&t.r, c, sh, 1, 0, true, ws, ws_bytes, stream)) return e;   // (true: with check_f32_weights)
     Run& r = t.r;
-    r.mask = mask; r.start_rot = start_rot; r.start_trans = start_trans; r.end_rot = two ? end_rot : nullptr; r.end_trans = two ? end_trans : nullptr; r.rel7_in = two ? rel7 : nullptr;
-    r.x_cond = x_cond; r.x_cond_mask = x_cond_mask; r.aatype = aatype;
+    bind_cond(r, cd);
     if (((uintptr_t)tape & 255) != 0) return fail(-7, "tape must be 256-byte aligned");
     const size_t need = carve_train(&t, c, r.B, r.T, r.L, (unsigned char*)tape);
     if (tape_bytes < need) return fail(-7, "tape too small: %zu < %zu bytes", tape_bytes, need);

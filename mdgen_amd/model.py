@@ -8,6 +8,7 @@ are what make hipGraph replay possible).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from collections import OrderedDict
 from typing import Dict, Optional
@@ -159,23 +160,49 @@ class LatentMDGenModel:
         check(lib.mdgen_workspace_layout(self._ctx, C.byref(sh), S, int(t_shared), C.byref(lay)))
         return lay
 
-    def _workspace(self, B, T, L_, S, t_shared):
-        key = (B, T, L_, S, int(t_shared))
-        ws = self._ws.get(key)
-        lay = self.workspace_layout(B, T, L_, S, t_shared)   # (options may have changed what the call needs: mlp_fold, precision)
-        if ws is not None and ws.numel() < lay.total_bytes:
-            del self._ws[key]
-            ws = None
-        if ws is None:
-            while len(self._ws) >= self.max_cached_shapes:
-                self._ws.popitem(last=False)                  # least recently used
-            ws = torch.empty(lay.total_bytes, dtype=torch.uint8, device=self.device)
+    def _cached(self, cache, key, make, stale=None):
+        """LRU get-or-create over `self._ws` / `self._stage` (at most max_cached_shapes entries each); an entry that `stale`
+        names is dropped and made again."""
+        v = cache.get(key)
+        if v is not None and stale is not None and stale(v):
+            del cache[key]
+            v = None
+        if v is None:
+            while len(cache) >= self.max_cached_shapes:
+                cache.popitem(last=False)                     # least recently used
+            v = cache[key] = make()
+        else:
+            cache.move_to_end(key)
+        return v
+
+    def _sized_workspace(self, key, nbytes):
+        """The workspace cached under `key`, of at least `nbytes` bytes."""
+        def make():
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             if self.poison_workspace:
                 ws.fill_(255)
-            self._ws[key] = ws
-        else:
-            self._ws.move_to_end(key)
-        return ws
+            return ws
+        return self._cached(self._ws, key, make, lambda ws: ws.numel() < nbytes)
+
+    def _workspace(self, B, T, L_, S, t_shared):
+        lay = self.workspace_layout(B, T, L_, S, t_shared)   # (options may have changed what the call needs: mlp_fold, precision)
+        return self._sized_workspace((B, T, L_, S, int(t_shared)), lay.total_bytes)
+
+    @contextlib.contextmanager
+    def _call_stream(self, use_graph: bool):
+        """Makes the model's device current and yields the hipStream_t a library call goes on: the current stream, or -- with
+        `use_graph`, since a capture needs a non-default stream -- the model's side stream, ordered after the current stream on entry
+        and ahead of it on exit."""
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream()
+            if not use_graph:
+                yield C.c_void_p(cur.cuda_stream)
+                return
+            if self._side is None:
+                self._side = torch.cuda.Stream(device=self.device)
+            self._side.wait_stream(cur)
+            yield C.c_void_p(self._side.cuda_stream)
+            cur.wait_stream(self._side)
 
     # ---- forward ----------------------------------------------------------------------------
     def _check_inputs(self, x, mask, x_cond, x_cond_mask, aatype):
@@ -225,10 +252,10 @@ class LatentMDGenModel:
         tr_i = torch.empty(B * L_, self.cfg.embed_dim, device=x.device) if return_trace else None
         sh = L.Shape(B, T, L_)
         rel7 = self._rel7(rel_quats, B, L_)
-        with torch.cuda.device(self.device):
-            check(lib.mdgen_denoiser_forward(self._ctx, C.byref(sh), ptr(x), ptr(t), ptr(mask), ptr(sr), ptr(st),
-                                             ptr(er), ptr(et), ptr(rel7), ptr(x_cond), ptr(x_cond_mask), ptr(aatype), ptr(out),
-                                             ptr(tr_h), ptr(tr_i), ptr(ws), ws.numel(), L.stream_ptr()))
+        cond = L.cond(mask, sr, st, er, et, rel7, x_cond, x_cond_mask, aatype)
+        with self._call_stream(False) as stream:
+            check(lib.mdgen_denoiser_forward(self._ctx, C.byref(sh), ptr(x), ptr(t), C.byref(cond), ptr(out), ptr(tr_h), ptr(tr_i),
+                                             ptr(ws), ws.numel(), stream))
         if return_trace:
             C_ = self.cfg.embed_dim
             trace = {"ipa_out": tr_i.view(B, L_, C_)}
@@ -240,71 +267,55 @@ class LatentMDGenModel:
     forward_inference = forward
     __call__ = forward
 
-    # ---- Euler rollout ----------------------------------------------------------------------
-    def sample_euler(self, zs, num_steps: int, mask=None, start_frames=None, end_frames=None, x_cond=None,
-                     x_cond_mask=None, aatype=None, use_graph: bool = True, rel_quats=None):
-        """x <- zs; for i < S: x += (t[i+1]-t[i]) * model(x, t[i]) on t = linspace(0,1,S+1); returns x.
-        (transport.py:408-451 + integrators.py:95-114 + torchdiffeq fixed-grid Euler.)"""
+    # ---- samplers ---------------------------------------------------------------------------
+    def _sampler_inputs(self, zs, mask, start_frames, end_frames, x_cond, x_cond_mask, aatype):
+        """The checks every conditioned sampler starts with -> (B, T, L, start rot, start trans, end rot | None, end trans | None)."""
         if self._pre_run is not None:
             self._pre_run()
         B, T, L_ = self._check_inputs(zs, mask, x_cond, x_cond_mask, aatype)
         require_cuda(zs, mask, x_cond, x_cond_mask, aatype)
-        S = int(num_steps)
         sr, st = _frames(start_frames)
-        er, et = _frames(end_frames)
         if sr is None:
             raise L.MdgenError("start_frames is required")
+        return (B, T, L_, sr, st) + _frames(end_frames)
+
+    def _staged(self, key, spec: dict, given: dict):
+        """The persistent staging set under `key` (stable device pointers => hipGraph replay): a buffer per name: (shape, dtype) of
+        `spec`, with the tensors of `given` copied into theirs (None: that buffer is left as it is)."""
+        stg = self._cached(self._stage, key, lambda: {
+            n: torch.empty(shape, dtype=dt, device=self.device) for n, (shape, dt) in spec.items()})
+        for n, t in given.items():
+            if t is not None:
+                stg[n].copy_(t)
+        return stg
+
+    def _stage_cond(self, zs, mask, sr, st, er, et, x_cond, x_cond_mask, aatype, rel_quats):
+        """Stages a call's state and conditioning in the buffers of its shape, one set for sample_euler and sample_rk
+        -> (the state buffer, the `L.Cond` of the others; NULL where the call gives none)."""
+        B, T, L_, D = zs.shape
+        f32, i64 = torch.float32, torch.int64
+        spec = dict(x=((B, T, L_, D), f32), mask=((B, T, L_), f32), sr=((B, L_, 3, 3), f32), st=((B, L_, 3), f32),
+                    er=((B, L_, 3, 3), f32), et=((B, L_, 3), f32), x_cond=((B, T, L_, D), f32), x_cond_mask=((B, T, L_), i64),
+                    aatype=((B, L_), i64))
+        if self.cfg.tps_condition:
+            spec["rel7"] = ((2, B, L_, 7), f32)
+        given = dict(mask=mask, sr=sr, st=st, er=er, et=et, rel7=self._rel7(rel_quats, B, L_), x_cond=x_cond,
+                     x_cond_mask=x_cond_mask, aatype=aatype)   # (in the order of L.Cond's fields)
+        stg = self._staged((B, T, L_), spec, dict(given, x=zs))
+        return stg["x"], L.cond(*[stg[n] if t is not None else None for n, t in given.items()])
+
+    def sample_euler(self, zs, num_steps: int, mask=None, start_frames=None, end_frames=None, x_cond=None,
+                     x_cond_mask=None, aatype=None, use_graph: bool = True, rel_quats=None):
+        """x <- zs; for i < S: x += (t[i+1]-t[i]) * model(x, t[i]) on t = linspace(0,1,S+1); returns x.
+        (transport.py:408-451 + integrators.py:95-114 + torchdiffeq fixed-grid Euler.)"""
+        B, T, L_, *frames = self._sampler_inputs(zs, mask, start_frames, end_frames, x_cond, x_cond_mask, aatype)
+        S = int(num_steps)
         ws = self._workspace(B, T, L_, S, True)
-        key = (B, T, L_)
-        stg = self._stage.get(key)
-        if stg is not None:
-            self._stage.move_to_end(key)
-        else:   # persistent staging buffers: stable device pointers => hipGraph replay
-            while len(self._stage) >= self.max_cached_shapes:
-                self._stage.popitem(last=False)
-            dev = self.device
-            stg = dict(
-                x=torch.empty(B, T, L_, self.cfg.latent_dim, device=dev), mask=torch.empty(B, T, L_, device=dev),
-                sr=torch.empty(B, L_, 3, 3, device=dev), st=torch.empty(B, L_, 3, device=dev),
-                er=torch.empty(B, L_, 3, 3, device=dev), et=torch.empty(B, L_, 3, device=dev),
-                x_cond=torch.empty(B, T, L_, self.cfg.latent_dim, device=dev),
-                x_cond_mask=torch.empty(B, T, L_, dtype=torch.int64, device=dev),
-                aatype=torch.empty(B, L_, dtype=torch.int64, device=dev),
-                rel7=torch.empty(2, B, L_, 7, device=dev) if self.cfg.tps_condition else None)
-            self._stage[key] = stg
-        stg["x"].copy_(zs)
-        stg["mask"].copy_(mask)
-        stg["sr"].copy_(sr)
-        stg["st"].copy_(st)
-        if er is not None:
-            stg["er"].copy_(er)
-            stg["et"].copy_(et)
-        stg["x_cond"].copy_(x_cond)
-        stg["x_cond_mask"].copy_(x_cond_mask)
-        stg["aatype"].copy_(aatype)
-        has_end = er is not None
-        rel7 = self._rel7(rel_quats, B, L_)
-        if rel7 is not None:
-            stg["rel7"].copy_(rel7)
+        x, cond = self._stage_cond(zs, mask, *frames, x_cond, x_cond_mask, aatype, rel_quats)
         sh = L.Shape(B, T, L_)
-        with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream()
-            if use_graph:
-                if self._side is None:
-                    self._side = torch.cuda.Stream(device=self.device)
-                self._side.wait_stream(cur)
-                stream = self._side
-            else:
-                stream = cur
-            check(lib.mdgen_sample_euler(
-                self._ctx, C.byref(sh), S, ptr(stg["x"]), ptr(stg["mask"]), ptr(stg["sr"]), ptr(stg["st"]),
-                ptr(stg["er"]) if has_end else None, ptr(stg["et"]) if has_end else None,
-                ptr(stg["rel7"]) if rel7 is not None else None, ptr(stg["x_cond"]),
-                ptr(stg["x_cond_mask"]), ptr(stg["aatype"]), ptr(ws), ws.numel(), int(use_graph),
-                C.c_void_p(stream.cuda_stream)))
-            if use_graph:
-                cur.wait_stream(self._side)
-        return stg["x"].clone()
+        with self._call_stream(use_graph) as stream:
+            check(lib.mdgen_sample_euler(self._ctx, C.byref(sh), S, ptr(x), C.byref(cond), ptr(ws), ws.numel(), int(use_graph), stream))
+        return x.clone()
 
     # ---- adaptive dopri5 ----------------------------------------------------------------------
     def sample_dopri5(self, zs, mask=None, start_frames=None, end_frames=None, x_cond=None, x_cond_mask=None, aatype=None,
@@ -313,41 +324,22 @@ class LatentMDGenModel:
         method='dopri5', atol=[atol], rtol=[rtol])[-1] (transport.py:408-451, integrators.py:74-113).  One step size for the
         whole batch (the error norm spans every element).  Returns (x at t = 1, stats) with stats = {"nfe", "accepted",
         "rejected", "steps": [(t0, dt) of every accepted step]}.  Synchronises the current stream once per attempted step."""
-        if self._pre_run is not None:
-            self._pre_run()
-        B, T, L_ = self._check_inputs(zs, mask, x_cond, x_cond_mask, aatype)
-        require_cuda(zs, mask, x_cond, x_cond_mask, aatype)
-        sr, st = _frames(start_frames)
-        er, et = _frames(end_frames)
-        if sr is None:
-            raise L.MdgenError("start_frames is required")
+        B, T, L_, sr, st, er, et = self._sampler_inputs(zs, mask, start_frames, end_frames, x_cond, x_cond_mask, aatype)
         sh = L.Shape(B, T, L_)
         nbytes = C.c_size_t()
         check(lib.mdgen_dopri5_workspace_bytes(self._ctx, C.byref(sh), C.byref(nbytes)))
-        key = ("dopri5", B, T, L_)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < nbytes.value:
-            while len(self._ws) >= self.max_cached_shapes:
-                self._ws.popitem(last=False)
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-            if self.poison_workspace:
-                ws.fill_(255)
-            self._ws[key] = ws
-        else:
-            self._ws.move_to_end(key)
+        ws = self._sized_workspace(("dopri5", B, T, L_), nbytes.value)
         x = zs.to(torch.float32).contiguous().clone()
         mask = mask.to(torch.float32).contiguous()
         x_cond = x_cond.to(torch.float32).contiguous()
         x_cond_mask = x_cond_mask.to(torch.int64).contiguous()
         aatype = aatype.to(torch.int64).contiguous()
-        rel7 = self._rel7(rel_quats, B, L_)
+        cond = L.cond(mask, sr, st, er, et, self._rel7(rel_quats, B, L_), x_cond, x_cond_mask, aatype)
         stats = (C.c_int32 * 3)()
         steps = (C.c_double * (2 * int(max_steps)))()
-        with torch.cuda.device(self.device):
-            check(lib.mdgen_sample_dopri5(
-                self._ctx, C.byref(sh), float(atol), float(rtol), int(max_steps), ptr(x), ptr(mask), ptr(sr), ptr(st),
-                ptr(er), ptr(et), ptr(rel7), ptr(x_cond), ptr(x_cond_mask), ptr(aatype), ptr(ws), ws.numel(), stats, steps,
-                L.stream_ptr()))
+        with self._call_stream(False) as stream:
+            check(lib.mdgen_sample_dopri5(self._ctx, C.byref(sh), float(atol), float(rtol), int(max_steps), ptr(x), C.byref(cond),
+                                          ptr(ws), ws.numel(), stats, steps, stream))
         acc = stats[1]
         info = {"nfe": stats[0], "accepted": acc, "rejected": stats[2],
                 "steps": [(steps[2 * i], steps[2 * i + 1]) for i in range(acc)]}
@@ -360,82 +352,21 @@ class LatentMDGenModel:
         S = `num_steps` (torchdiffeq 0.2.x fixed-grid solvers as transport.py:408-451 / integrators.py:106-113 call them): 2, 3, 4
         network evaluations per step.  Every sample sees the same grid, so a sample's solution does not depend on its batch mates;
         nothing synchronises, and with `use_graph` the whole solve is one hipGraph.  Returns x at t = 1."""
-        if self._pre_run is not None:
-            self._pre_run()
         code = L.RK_METHODS.get(method)
         if code is None:
             raise L.MdgenError(f"method must be one of {sorted(L.RK_METHODS)}, got {method!r}")
         S = int(num_steps)
         if S < 1:
             raise L.MdgenError(f"num_steps must be >= 1, got {num_steps}")
-        B, T, L_ = self._check_inputs(zs, mask, x_cond, x_cond_mask, aatype)
-        require_cuda(zs, mask, x_cond, x_cond_mask, aatype)
-        sr, st = _frames(start_frames)
-        er, et = _frames(end_frames)
-        if sr is None:
-            raise L.MdgenError("start_frames is required")
+        B, T, L_, *frames = self._sampler_inputs(zs, mask, start_frames, end_frames, x_cond, x_cond_mask, aatype)
         sh = L.Shape(B, T, L_)
         nbytes = C.c_size_t()
         check(lib.mdgen_rk_workspace_bytes(self._ctx, C.byref(sh), code, S, C.byref(nbytes)))
-        wkey = ("rk", B, T, L_)
-        ws = self._ws.get(wkey)
-        if ws is None or ws.numel() < nbytes.value:
-            while len(self._ws) >= self.max_cached_shapes:
-                self._ws.popitem(last=False)
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-            if self.poison_workspace:
-                ws.fill_(255)
-            self._ws[wkey] = ws
-        else:
-            self._ws.move_to_end(wkey)
-        key = (B, T, L_)
-        stg = self._stage.get(key)
-        if stg is not None:
-            self._stage.move_to_end(key)
-        else:   # persistent staging buffers (shared with sample_euler): stable device pointers => hipGraph replay
-            while len(self._stage) >= self.max_cached_shapes:
-                self._stage.popitem(last=False)
-            dev = self.device
-            stg = dict(
-                x=torch.empty(B, T, L_, self.cfg.latent_dim, device=dev), mask=torch.empty(B, T, L_, device=dev),
-                sr=torch.empty(B, L_, 3, 3, device=dev), st=torch.empty(B, L_, 3, device=dev),
-                er=torch.empty(B, L_, 3, 3, device=dev), et=torch.empty(B, L_, 3, device=dev),
-                x_cond=torch.empty(B, T, L_, self.cfg.latent_dim, device=dev),
-                x_cond_mask=torch.empty(B, T, L_, dtype=torch.int64, device=dev),
-                aatype=torch.empty(B, L_, dtype=torch.int64, device=dev),
-                rel7=torch.empty(2, B, L_, 7, device=dev) if self.cfg.tps_condition else None)
-            self._stage[key] = stg
-        stg["x"].copy_(zs)
-        stg["mask"].copy_(mask)
-        stg["sr"].copy_(sr)
-        stg["st"].copy_(st)
-        has_end = er is not None
-        if has_end:
-            stg["er"].copy_(er)
-            stg["et"].copy_(et)
-        stg["x_cond"].copy_(x_cond)
-        stg["x_cond_mask"].copy_(x_cond_mask)
-        stg["aatype"].copy_(aatype)
-        rel7 = self._rel7(rel_quats, B, L_)
-        if rel7 is not None:
-            stg["rel7"].copy_(rel7)
-        with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream()
-            if use_graph:
-                if self._side is None:
-                    self._side = torch.cuda.Stream(device=self.device)
-                self._side.wait_stream(cur)
-                stream = self._side
-            else:
-                stream = cur
-            check(lib.mdgen_sample_rk(
-                self._ctx, C.byref(sh), code, S, ptr(stg["x"]), ptr(stg["mask"]), ptr(stg["sr"]), ptr(stg["st"]),
-                ptr(stg["er"]) if has_end else None, ptr(stg["et"]) if has_end else None,
-                ptr(stg["rel7"]) if rel7 is not None else None, ptr(stg["x_cond"]), ptr(stg["x_cond_mask"]), ptr(stg["aatype"]),
-                ptr(ws), ws.numel(), int(use_graph), C.c_void_p(stream.cuda_stream)))
-            if use_graph:
-                cur.wait_stream(self._side)
-        return stg["x"].clone()
+        ws = self._sized_workspace(("rk", B, T, L_), nbytes.value)
+        x, cond = self._stage_cond(zs, mask, *frames, x_cond, x_cond_mask, aatype, rel_quats)
+        with self._call_stream(use_graph) as stream:
+            check(lib.mdgen_sample_rk(self._ctx, C.byref(sh), code, S, ptr(x), C.byref(cond), ptr(ws), ws.numel(), int(use_graph), stream))
+        return x.clone()
 
     # ---- multi-block rollout -----------------------------------------------------------------
     def rollout_euler(self, zs, num_steps: int, mask, cond_rots, cond_trans, cond_torsions, seqres, tables,
@@ -452,46 +383,19 @@ class LatentMDGenModel:
         require_cuda(zs, mask, cond_rots, cond_trans, cond_torsions, seqres)
         S = int(num_steps)
         ws = self._workspace(B, T, L_, S, True)
-        key = ("rollout", R, B, T, L_)
-        stg = self._stage.get(key)
-        if stg is not None:
-            self._stage.move_to_end(key)
-        else:
-            while len(self._stage) >= self.max_cached_shapes:
-                self._stage.popitem(last=False)
-            dev = self.device
-            stg = dict(zs=torch.empty(R, B, T, L_, D, device=dev), mask=torch.empty(B, T, L_, device=dev),
-                       rots=torch.empty(B, L_, 3, 3, device=dev), trans=torch.empty(B, L_, 3, device=dev),
-                       tors=torch.empty(B, L_, 7, 2, device=dev), seqres=torch.empty(B, L_, dtype=torch.int64, device=dev),
-                       x_cond=torch.empty(B, T, L_, D, device=dev),
-                       x_cond_mask=torch.empty(B, T, L_, dtype=torch.int64, device=dev),
-                       atom14=torch.empty(B, R * T, L_, 14, 3, device=dev))
-            self._stage[key] = stg
-        stg["zs"].copy_(zs)
-        stg["mask"].copy_(mask)
-        stg["rots"].copy_(cond_rots)
-        stg["trans"].copy_(cond_trans)
-        stg["tors"].copy_(cond_torsions)
-        stg["seqres"].copy_(seqres)
-        tb = L.ResidueTables(*[tables[n].data_ptr() for n in (
-            "default_frames", "lit_positions", "atom14_group", "atom14_mask", "atom37_to_atom14", "atom37_mask",
-            "chi_atom_indices", "chi_angles_mask")])
+        f32, i64 = torch.float32, torch.int64
+        spec = dict(zs=((R, B, T, L_, D), f32), mask=((B, T, L_), f32), rots=((B, L_, 3, 3), f32), trans=((B, L_, 3), f32),
+                    tors=((B, L_, 7, 2), f32), seqres=((B, L_), i64), x_cond=((B, T, L_, D), f32), x_cond_mask=((B, T, L_), i64),
+                    atom14=((B, R * T, L_, 14, 3), f32))
+        stg = self._staged(("rollout", R, B, T, L_), spec,
+                           dict(zs=zs, mask=mask, rots=cond_rots, trans=cond_trans, tors=cond_torsions, seqres=seqres))
+        tb = L.ResidueTables.from_dict(tables)
         sh = L.Shape(B, T, L_)
-        with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream()
-            if use_graph:
-                if self._side is None:
-                    self._side = torch.cuda.Stream(device=self.device)
-                self._side.wait_stream(cur)
-                stream = self._side
-            else:
-                stream = cur
+        with self._call_stream(use_graph) as stream:
             check(lib.mdgen_rollout_euler(
                 self._ctx, C.byref(sh), S, R, ptr(stg["zs"]), ptr(stg["mask"]), ptr(stg["rots"]), ptr(stg["trans"]),
                 ptr(stg["tors"]), ptr(stg["seqres"]), ptr(stg["x_cond"]), ptr(stg["x_cond_mask"]), C.byref(tb),
-                ptr(stg["atom14"]), ptr(ws), ws.numel(), int(use_graph), C.c_void_p(stream.cuda_stream)))
-            if use_graph:
-                cur.wait_stream(self._side)
+                ptr(stg["atom14"]), ptr(ws), ws.numel(), int(use_graph), stream))
         nxt = {"rots": stg["rots"].clone(), "trans": stg["trans"].clone(), "torsions": stg["tors"].clone()}
         return stg["atom14"].clone(), stg["zs"].clone(), nxt
 
@@ -522,46 +426,17 @@ class LatentMDGenModel:
         require_cuda(zs, mask, key_rots, key_trans, key_torsions, seqres)
         S = int(num_steps)
         ws = self._workspace(B, T, L_, S, True)
-        key = ("upsample", B, T, L_, c)
-        stg = self._stage.get(key)
-        if stg is not None:
-            self._stage.move_to_end(key)
-        else:
-            while len(self._stage) >= self.max_cached_shapes:
-                self._stage.popitem(last=False)
-            dev = self.device
-            stg = dict(zs=torch.empty(B, T, L_, D, device=dev), mask=torch.empty(B, T, L_, device=dev),
-                       rots=torch.empty(B, K, L_, 3, 3, device=dev), trans=torch.empty(B, K, L_, 3, device=dev),
-                       tors=torch.empty(B, K, L_, 7, 2, device=dev), seqres=torch.empty(B, L_, dtype=torch.int64, device=dev),
-                       x_cond=torch.empty(B, T, L_, D, device=dev),
-                       x_cond_mask=torch.empty(B, T, L_, dtype=torch.int64, device=dev),
-                       sr=torch.empty(B, L_, 3, 3, device=dev), st=torch.empty(B, L_, 3, device=dev),
-                       atom14=torch.empty(B, T, L_, 14, 3, device=dev))
-            self._stage[key] = stg
-        stg["zs"].copy_(zs)
-        stg["mask"].copy_(mask)
-        stg["rots"].copy_(key_rots)
-        stg["trans"].copy_(key_trans)
-        stg["tors"].copy_(key_torsions)
-        stg["seqres"].copy_(seqres)
-        tb = L.ResidueTables(*[tables[n].data_ptr() for n in (
-            "default_frames", "lit_positions", "atom14_group", "atom14_mask", "atom37_to_atom14", "atom37_mask",
-            "chi_atom_indices", "chi_angles_mask")])
+        f32, i64 = torch.float32, torch.int64
+        spec = dict(zs=((B, T, L_, D), f32), mask=((B, T, L_), f32), rots=((B, K, L_, 3, 3), f32), trans=((B, K, L_, 3), f32),
+                    tors=((B, K, L_, 7, 2), f32), seqres=((B, L_), i64), x_cond=((B, T, L_, D), f32), x_cond_mask=((B, T, L_), i64),
+                    sr=((B, L_, 3, 3), f32), st=((B, L_, 3), f32), atom14=((B, T, L_, 14, 3), f32))
+        stg = self._staged(("upsample", B, T, L_, c), spec,
+                           dict(zs=zs, mask=mask, rots=key_rots, trans=key_trans, tors=key_torsions, seqres=seqres))
+        tb = L.ResidueTables.from_dict(tables)
         sh = L.Shape(B, T, L_)
-        with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream()
-            if use_graph:
-                if self._side is None:
-                    self._side = torch.cuda.Stream(device=self.device)
-                self._side.wait_stream(cur)
-                stream = self._side
-            else:
-                stream = cur
+        with self._call_stream(use_graph) as stream:
             check(lib.mdgen_upsample_euler(
                 self._ctx, C.byref(sh), S, c, ptr(stg["zs"]), ptr(stg["mask"]), ptr(stg["rots"]), ptr(stg["trans"]),
                 ptr(stg["tors"]), ptr(stg["seqres"]), ptr(stg["x_cond"]), ptr(stg["x_cond_mask"]), ptr(stg["sr"]),
-                ptr(stg["st"]), C.byref(tb), ptr(stg["atom14"]), ptr(ws), ws.numel(), int(use_graph),
-                C.c_void_p(stream.cuda_stream)))
-            if use_graph:
-                cur.wait_stream(self._side)
+                ptr(stg["st"]), C.byref(tb), ptr(stg["atom14"]), ptr(ws), ws.numel(), int(use_graph), stream))
         return stg["atom14"].clone(), stg["zs"].clone()

@@ -174,11 +174,10 @@ class TrainableModel:
             self._tape_key = (B, T, L_)
         loss = torch.empty(B, device=self.device)
         pred = torch.empty_like(xt)
+        cond = L.cond(mask, sr, st, er, et, rel7, x_cond, x_cond_mask, aatype)
         with torch.cuda.device(self.device):
             check(lib.mdgen_train_forward_backward(
-                m._ctx, C.byref(sh), ptr(xt), ptr(t), ptr(mask), ptr(sr), ptr(st), ptr(er), ptr(et), ptr(rel7), ptr(x_cond),
-                ptr(x_cond_mask), ptr(aatype),
-                ptr(target), ptr(loss_mask), ptr(loss), ptr(pred), ptr(self.grads), self._goff, ptr(ws), ws.numel(),
+                m._ctx, C.byref(sh), ptr(xt), ptr(t), C.byref(cond), ptr(target), ptr(loss_mask), ptr(loss), ptr(pred), ptr(self.grads), self._goff, ptr(ws), ws.numel(),
                 ptr(self._tape), self._tape.numel(), L.stream_ptr()))
         return loss, pred
 

@@ -874,6 +874,46 @@ def test_multi_block_rollout_one_graph():
         assert rms < TOL_RMS * (r + 1) and mx < TOL_MAX * (r + 1)
 
 
+def test_rollout_graph_is_keyed_on_every_residue_table():
+    """A captured rollout bakes all eight residue-table pointers into its graph, so all eight belong to the graph's cache key: a
+    call that differs from a cached one ONLY in `lit_positions` (another buffer, 1.5 x the values) must capture its own graph, not
+    replay the one that reads the other table.  Two blocks, so that the table-dependent atom14 -> conditioning-frame step feeds a
+    second block.  Graph calls a, b, a: each equals its eager counterpart bit for bit, atom14 and samples."""
+    from mdgen_amd.config import ModelConfig
+    from mdgen_amd.geometry import residue_tables
+    from mdgen_amd.synthetic import synth_state_dict
+    dev = _cuda()
+    B, T, L_, S, R = 2, 12, 4, 2, 2
+    cfg = ModelConfig.forward_sim(num_frames=T, crop=4)
+    m = get_model(cfg, synth_state_dict(cfg, 9), ("rollout_tables", T))
+    gen = torch.Generator().manual_seed(31)
+    q = torch.randn(B, L_, 4, generator=gen)
+    w, x, y, z = (q / q.norm(dim=-1, keepdim=True)).unbind(-1)
+    rots = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                        2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                        2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], -1).view(B, L_, 3, 3).to(dev)
+    trans = torch.cumsum(2.2 * torch.randn(B, L_, 3, generator=gen), 1).to(dev)
+    tors = torch.randn(B, L_, 7, 2, generator=gen)
+    tors = (tors / tors.norm(dim=-1, keepdim=True)).to(dev)
+    seqres = torch.randint(0, 20, (B, L_), generator=gen).to(dev)
+    mask = torch.ones(B, T, L_, device=dev)
+    zs = torch.randn(R, B, T, L_, cfg.latent_dim, generator=gen).to(dev)
+    tables_a = residue_tables(dev)
+    tables_b = dict(tables_a)
+    tables_b["lit_positions"] = tables_a["lit_positions"] * 1.5
+
+    def run(tables, use_graph):
+        atom14, samples, _ = m.rollout_euler(zs, S, mask, rots, trans, tors, seqres, tables, use_graph=use_graph)
+        return atom14, samples
+    eager_a, eager_b = run(tables_a, False), run(tables_b, False)
+    assert torch.isfinite(eager_a[0]).all() and torch.isfinite(eager_b[0]).all()
+    assert not torch.equal(eager_a[0], eager_b[0])
+    for name, tables, eager in (("a", tables_a, eager_a), ("b", tables_b, eager_b), ("a again", tables_a, eager_a)):
+        atom14, samples = run(tables, True)
+        assert torch.equal(atom14, eager[0]), f"graph call {name}: atom14 is not the eager call's"
+        assert torch.equal(samples, eager[1]), f"graph call {name}: samples are not the eager call's"
+
+
 def test_many_views_beyond_the_32bit_offset_limit():
     """One launch addresses the residual stream with 32-bit byte offsets (token * 1536): at most 2 796 202 token rows.
     A batch of 45 ATLAS-size samples (2.88 M tokens) must therefore run as two sub-batch launch views

@@ -261,11 +261,12 @@ def test_dopri5_refuses_stream_capture_and_enqueues_nothing():
     sr, st = _frames(kw["start_frames"])
     args = [kw["mask"], sr, st, None, None, None, kw["x_cond"].contiguous(), kw["x_cond_mask"].contiguous(),
             kw["aatype"].to(torch.int64).contiguous()]
+    cond = L.Cond(*[L.ptr(a) for a in args])
     stats = (C.c_int32 * 3)(-1, -1, -1)
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
-        rc = L.lib.mdgen_sample_dopri5(w.model._ctx, C.byref(sh), 1e-6, 1e-3, 1000, L.ptr(x), *[L.ptr(a) for a in args],
+        rc = L.lib.mdgen_sample_dopri5(w.model._ctx, C.byref(sh), 1e-6, 1e-3, 1000, L.ptr(x), C.byref(cond),
                                        L.ptr(ws), ws.numel(), stats, None, L.stream_ptr())
         copy.copy_(x)                              # (something to capture: the graph is not empty)
     msg = L.lib.mdgen_last_error().decode()

@@ -112,11 +112,17 @@ def test_library_refuses_unknown_method_and_no_steps():
         assert lib.mdgen_rk_workspace_bytes(None, C.byref(sh), method, S, C.byref(nbytes)) == -2, (method, S)
         assert lib.mdgen_debug_rk_plan(method, S, bits.ctypes.data, 16, C.byref(n_rows), row_of.ctypes.data, C.byref(n_st)) == -2
         fake = C.c_void_p(4096)      # the method and the step count are judged before any pointer is followed
-        rc = lib.mdgen_sample_rk(None, C.byref(sh), method, S, *([fake] * 3), fake, None, None, None, fake, fake, fake, fake, 1 << 30,
-                                 0, None)
+        cond = L.Cond(mask=fake, start_rot=fake, start_trans=fake, x_cond=fake, x_cond_mask=fake, aatype=fake)
+        rc = lib.mdgen_sample_rk(None, C.byref(sh), method, S, fake, C.byref(cond), fake, 1 << 30, 0, None)
         assert rc == -2, (method, S, lib.mdgen_last_error())
     assert lib.mdgen_rk_workspace_bytes(None, C.byref(sh), 3, 4, None) == -1
-    assert lib.mdgen_sample_rk(None, C.byref(sh), 3, 4, None, *([None] * 10), 0, 0, None) == -1
+    # a null argument gives -1: a NULL conditioning struct, and a struct with a NULL required field
+    assert lib.mdgen_sample_rk(None, C.byref(sh), 3, 4, fake, None, fake, 1 << 30, 0, None) == -1
+    for missing in ("mask", "start_rot", "start_trans", "x_cond", "x_cond_mask", "aatype"):
+        cond = L.Cond(mask=fake, start_rot=fake, start_trans=fake, x_cond=fake, x_cond_mask=fake, aatype=fake)
+        setattr(cond, missing, None)
+        assert lib.mdgen_sample_rk(None, C.byref(sh), 3, 4, fake, C.byref(cond), fake, 1 << 30, 0, None) == -1, missing
+    assert lib.mdgen_sample_rk(None, C.byref(sh), 3, 4, None, None, None, 0, 0, None) == -1
     with pytest.raises(L.MdgenError, match="error -2"):
         L.rk_plan("rk4", 0)
     with pytest.raises(L.MdgenError, match="error -2"):

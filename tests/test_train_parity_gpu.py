@@ -259,9 +259,9 @@ def test_training_step_refuses_a_missing_fp32_copy_before_its_first_launch():
         loss, pred, grads = torch.empty(B, device=dev), torch.empty_like(g["xt"]), torch.zeros(16, device=dev)
         goff = (C.c_int64 * len(names))(*[-1] * len(names))
         torch.cuda.synchronize()
+        cond = L.Cond(ptr(g["mask"]), ptr(g["sR"]), ptr(g["st"]), None, None, None, ptr(g["x_cond"]), ptr(g["cm"]), ptr(g["aatype"]))
         rc = lib.mdgen_train_forward_backward(
-            m._ctx, C.byref(sh), ptr(g["xt"]), ptr(g["t"]), ptr(g["mask"]), ptr(g["sR"]), ptr(g["st"]), None, None, None,
-            ptr(g["x_cond"]), ptr(g["cm"]), ptr(g["aatype"]), ptr(g["ut"]), ptr(g["loss_mask"]), ptr(loss), ptr(pred), ptr(grads),
+            m._ctx, C.byref(sh), ptr(g["xt"]), ptr(g["t"]), C.byref(cond), ptr(g["ut"]), ptr(g["loss_mask"]), ptr(loss), ptr(pred), ptr(grads),
             goff, ptr(ws), ws.numel(), ptr(tape), tape.numel(), s)
         msg = lib.mdgen_last_error().decode()
         torch.cuda.synchronize()
