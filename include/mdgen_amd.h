@@ -358,6 +358,38 @@ int32_t mdgen_upsample_euler(mdgen_ctx* ctx, const mdgen_shape* shape, int32_t n
                              const mdgen_residue_tables* tables, float* atom14,
                              void* workspace, size_t workspace_bytes, int32_t use_graph, void* stream);
 
+/* mdgen_rollout_euler with a fixed-grid Runge-Kutta solve per block (method, n_steps: as mdgen_sample_rk) in the Euler loop's
+ * place: prep -> solve -> atom14 -> next conditioning frame for n_blocks blocks in ONE call and -- with use_graph -- one hipGraph
+ * (cached per method, n_steps, n_blocks, stride, pointers and residue tables).  Arguments as mdgen_rollout_euler, except
+ *   zs                block r's noise / samples (B,T,L,D) fp32 start at zs + r * zs_block_stride floats; zs 16-byte aligned
+ *   zs_block_stride   in floats; a multiple of 4 and >= B*T*L*D.  The solver's last update reads and writes a block's state 16
+ *                     bytes at a time, and B*T*L*D (D = 21) is a multiple of 4 only for some shapes: a (n_blocks,B,T,L,D) tensor
+ *                     without padding is accepted exactly when it is (stride = B*T*L*D); otherwise round the stride up.
+ *   workspace         mdgen_rk_workspace_bytes(shape, method, n_steps): one block's time rows are prepared again for every block
+ *                     (the IPA stack reads the block's conditioning frame)
+ * Errors, all decided before any device call: -1 null pointer; -2 unknown method, n_steps < 1, n_blocks < 1, a two-sided
+ * (tps_condition) context or a shape the sampler refuses; -7 zs alignment, zs_block_stride, workspace size. */
+int32_t mdgen_rollout_rk(mdgen_ctx* ctx, const mdgen_shape* shape, int32_t method, int32_t n_steps, int32_t n_blocks,
+                         float* zs, int64_t zs_block_stride, const float* mask,
+                         float* cond_rots, float* cond_trans, float* cond_torsions,
+                         const int64_t* seqres, float* x_cond, int64_t* x_cond_mask,
+                         const mdgen_residue_tables* tables, float* atom14,
+                         void* workspace, size_t workspace_bytes, int32_t use_graph, void* stream);
+
+/* mdgen_upsample_euler with a fixed-grid Runge-Kutta solve (method, n_steps: as mdgen_sample_rk): mdgen_prep_keyframes -> solve
+ * -> atom14 relative to key frame 0 in ONE call and -- with use_graph -- one hipGraph; a replay with new key frames in the same
+ * buffers gives new results.  Arguments as mdgen_upsample_euler; zs (B,T,L,21) must be 16-byte aligned (the only state of the
+ * call: no stride); workspace: mdgen_rk_workspace_bytes(shape, method, n_steps).
+ * Errors, all decided before any device call: -1 null pointer; -2 unknown method, n_steps < 1, cond_interval < 1, a two-sided
+ * context or a shape the sampler refuses; -7 zs alignment, workspace size. */
+int32_t mdgen_upsample_rk(mdgen_ctx* ctx, const mdgen_shape* shape, int32_t method, int32_t n_steps, int32_t cond_interval,
+                          float* zs, const float* mask,
+                          const float* key_rots, const float* key_trans, const float* key_torsions,
+                          const int64_t* seqres,
+                          float* x_cond, int64_t* x_cond_mask, float* start_rot, float* start_trans,
+                          const mdgen_residue_tables* tables, float* atom14,
+                          void* workspace, size_t workspace_bytes, int32_t use_graph, void* stream);
+
 /* ---- measurement ----------------------------------------------------------------------------
  * Per-kernel-class timing with hipEvents recorded on the launch stream (bench.py's roofline leg).
  * While enabled, launches are bracketed by event pairs and hipGraph capture/replay is bypassed.

@@ -26,6 +26,7 @@ EXPORTS = [
     "mdgen_train_set_milestone_events",
     "mdgen_sample_dopri5", "mdgen_dopri5_workspace_bytes", "mdgen_debug_dopri5_controller",
     "mdgen_sample_rk", "mdgen_rk_workspace_bytes", "mdgen_debug_rk_plan", "mdgen_debug_rk_stage",
+    "mdgen_rollout_rk", "mdgen_upsample_rk",
 ]
 
 
@@ -97,6 +98,10 @@ def _load():
                                         + tables_atom14 + ws_bytes + [i32, vp])
     lib.mdgen_upsample_euler.argtypes = (ctx_shape + [i32, i32] + [vp, vp] + [vp, vp, vp] + [vp] + [vp, vp] + [vp, vp]   # ... | key frames | ... | start_rot, start_trans
                                          + tables_atom14 + ws_bytes + [i32, vp])
+    lib.mdgen_rollout_rk.argtypes = (ctx_shape + [i32, i32, i32] + [vp, i64, vp] + [vp, vp, vp] + [vp] + [vp, vp]   # method, steps, blocks | zs, its block stride, mask | ...
+                                     + tables_atom14 + ws_bytes + [i32, vp])
+    lib.mdgen_upsample_rk.argtypes = (ctx_shape + [i32, i32, i32] + [vp, vp] + [vp, vp, vp] + [vp] + [vp, vp] + [vp, vp]   # as mdgen_upsample_euler after (method, steps, interval)
+                                      + tables_atom14 + ws_bytes + [i32, vp])
     lib.mdgen_profile_enable.argtypes = [vp, i32]
     lib.mdgen_profile_phase_trace.argtypes = [vp, vp, i64]
     lib.mdgen_profile_report.argtypes = [vp, vp, C.c_char_p, sz]

@@ -352,17 +352,9 @@ class LatentMDGenModel:
         S = `num_steps` (torchdiffeq 0.2.x fixed-grid solvers as transport.py:408-451 / integrators.py:106-113 call them): 2, 3, 4
         network evaluations per step.  Every sample sees the same grid, so a sample's solution does not depend on its batch mates;
         nothing synchronises, and with `use_graph` the whole solve is one hipGraph.  Returns x at t = 1."""
-        code = L.RK_METHODS.get(method)
-        if code is None:
-            raise L.MdgenError(f"method must be one of {sorted(L.RK_METHODS)}, got {method!r}")
-        S = int(num_steps)
-        if S < 1:
-            raise L.MdgenError(f"num_steps must be >= 1, got {num_steps}")
         B, T, L_, *frames = self._sampler_inputs(zs, mask, start_frames, end_frames, x_cond, x_cond_mask, aatype)
+        code, S, ws = self._rk_call(method, num_steps, B, T, L_)
         sh = L.Shape(B, T, L_)
-        nbytes = C.c_size_t()
-        check(lib.mdgen_rk_workspace_bytes(self._ctx, C.byref(sh), code, S, C.byref(nbytes)))
-        ws = self._sized_workspace(("rk", B, T, L_), nbytes.value)
         x, cond = self._stage_cond(zs, mask, *frames, x_cond, x_cond_mask, aatype, rel_quats)
         with self._call_stream(use_graph) as stream:
             check(lib.mdgen_sample_rk(self._ctx, C.byref(sh), code, S, ptr(x), C.byref(cond), ptr(ws), ws.numel(), int(use_graph), stream))
@@ -399,13 +391,55 @@ class LatentMDGenModel:
         nxt = {"rots": stg["rots"].clone(), "trans": stg["trans"].clone(), "torsions": stg["tors"].clone()}
         return stg["atom14"].clone(), stg["zs"].clone(), nxt
 
+    def _rk_call(self, method, num_steps, B, T, L_):
+        """(method code, S, workspace) of a fixed-grid Runge-Kutta call of this shape: one workspace for sample_rk and the drivers."""
+        code = L.RK_METHODS.get(method)
+        if code is None:
+            raise L.MdgenError(f"method must be one of {sorted(L.RK_METHODS)}, got {method!r}")
+        S = int(num_steps)
+        if S < 1:
+            raise L.MdgenError(f"num_steps must be >= 1, got {num_steps}")
+        sh = L.Shape(B, T, L_)
+        nbytes = C.c_size_t()
+        check(lib.mdgen_rk_workspace_bytes(self._ctx, C.byref(sh), code, S, C.byref(nbytes)))
+        return code, S, self._sized_workspace(("rk", B, T, L_), nbytes.value)
+
+    def rollout_rk(self, zs, method: str, num_steps: int, mask, cond_rots, cond_trans, cond_torsions, seqres, tables,
+                   use_graph: bool = True):
+        """`mdgen_rollout_rk`: `rollout_euler` with `method` in ("midpoint", "heun3", "rk4") solving every block in `num_steps`
+        steps (as `sample_rk`), still one call and one hipGraph.  Arguments and return values as `rollout_euler`.  The staged
+        noise keeps every block on 16 bytes (a block stride rounded up to 4 floats: B*T*L*D need not be a multiple of 4);
+        the padding never leaves this function."""
+        if self._pre_run is not None:
+            self._pre_run()
+        if zs.dim() != 5 or zs.shape[-1] != self.cfg.latent_dim:
+            raise L.MdgenError(f"zs must be (R,B,T,L,{self.cfg.latent_dim}), got {tuple(zs.shape)}")
+        R, B, T, L_, D = zs.shape
+        require_cuda(zs, mask, cond_rots, cond_trans, cond_torsions, seqres)
+        code, S, ws = self._rk_call(method, num_steps, B, T, L_)
+        blk = B * T * L_ * D
+        stride = (blk + 3) // 4 * 4
+        f32, i64 = torch.float32, torch.int64
+        spec = dict(zs=((R, stride), f32), mask=((B, T, L_), f32), rots=((B, L_, 3, 3), f32), trans=((B, L_, 3), f32),
+                    tors=((B, L_, 7, 2), f32), seqres=((B, L_), i64), x_cond=((B, T, L_, D), f32), x_cond_mask=((B, T, L_), i64),
+                    atom14=((B, R * T, L_, 14, 3), f32))
+        stg = self._staged(("rollout_rk", R, B, T, L_), spec,
+                           dict(mask=mask, rots=cond_rots, trans=cond_trans, tors=cond_torsions, seqres=seqres))
+        stg["zs"][:, :blk].copy_(zs.reshape(R, blk))
+        tb = L.ResidueTables.from_dict(tables)
+        sh = L.Shape(B, T, L_)
+        with self._call_stream(use_graph) as stream:
+            check(lib.mdgen_rollout_rk(
+                self._ctx, C.byref(sh), code, S, R, ptr(stg["zs"]), stride, ptr(stg["mask"]), ptr(stg["rots"]), ptr(stg["trans"]),
+                ptr(stg["tors"]), ptr(stg["seqres"]), ptr(stg["x_cond"]), ptr(stg["x_cond_mask"]), C.byref(tb),
+                ptr(stg["atom14"]), ptr(ws), ws.numel(), int(use_graph), stream))
+        nxt = {"rots": stg["rots"].clone(), "trans": stg["trans"].clone(), "torsions": stg["tors"].clone()}
+        return stg["atom14"].clone(), stg["zs"][:, :blk].reshape(R, B, T, L_, D).clone(), nxt
+
     # ---- trajectory upsampling ---------------------------------------------------------------
-    def upsample_euler(self, zs, num_steps: int, cond_interval: int, mask, key_rots, key_trans, key_torsions, seqres, tables,
-                       use_graph: bool = True):
-        """`mdgen_upsample_euler`: key-frame conditioning -> S Euler steps -> atom14 in one call (one hipGraph).  zs (B,T,L,D)
-        noise, one window per batch element; mask (B,T,L); key_* the K = ceil(T / cond_interval) key frames of every window,
-        (B,K,L,...); seqres (B,L) int64; tables: dict of residue tables on the device (geometry.residue_tables).
-        Returns (atom14 (B,T,L,14,3), samples (B,T,L,D))."""
+    def _stage_upsample(self, zs, cond_interval, mask, key_rots, key_trans, key_torsions, seqres):
+        """The checks of an upsampling call and its staging set (one per shape and interval, shared by the solvers)
+        -> (B, T, L, cond_interval, the staged buffers)."""
         if self._pre_run is not None:
             self._pre_run()
         if self.cfg.tps_condition:
@@ -424,19 +458,44 @@ class LatentMDGenModel:
         if tuple(mask.shape) != (B, T, L_):
             raise L.MdgenError(f"mask must be (B,T,L)={B, T, L_}, got {tuple(mask.shape)}")
         require_cuda(zs, mask, key_rots, key_trans, key_torsions, seqres)
-        S = int(num_steps)
-        ws = self._workspace(B, T, L_, S, True)
         f32, i64 = torch.float32, torch.int64
         spec = dict(zs=((B, T, L_, D), f32), mask=((B, T, L_), f32), rots=((B, K, L_, 3, 3), f32), trans=((B, K, L_, 3), f32),
                     tors=((B, K, L_, 7, 2), f32), seqres=((B, L_), i64), x_cond=((B, T, L_, D), f32), x_cond_mask=((B, T, L_), i64),
                     sr=((B, L_, 3, 3), f32), st=((B, L_, 3), f32), atom14=((B, T, L_, 14, 3), f32))
         stg = self._staged(("upsample", B, T, L_, c), spec,
                            dict(zs=zs, mask=mask, rots=key_rots, trans=key_trans, tors=key_torsions, seqres=seqres))
+        return B, T, L_, c, stg
+
+    def upsample_euler(self, zs, num_steps: int, cond_interval: int, mask, key_rots, key_trans, key_torsions, seqres, tables,
+                       use_graph: bool = True):
+        """`mdgen_upsample_euler`: key-frame conditioning -> S Euler steps -> atom14 in one call (one hipGraph).  zs (B,T,L,D)
+        noise, one window per batch element; mask (B,T,L); key_* the K = ceil(T / cond_interval) key frames of every window,
+        (B,K,L,...); seqres (B,L) int64; tables: dict of residue tables on the device (geometry.residue_tables).
+        Returns (atom14 (B,T,L,14,3), samples (B,T,L,D))."""
+        B, T, L_, c, stg = self._stage_upsample(zs, cond_interval, mask, key_rots, key_trans, key_torsions, seqres)
+        S = int(num_steps)
+        ws = self._workspace(B, T, L_, S, True)
         tb = L.ResidueTables.from_dict(tables)
         sh = L.Shape(B, T, L_)
         with self._call_stream(use_graph) as stream:
             check(lib.mdgen_upsample_euler(
                 self._ctx, C.byref(sh), S, c, ptr(stg["zs"]), ptr(stg["mask"]), ptr(stg["rots"]), ptr(stg["trans"]),
+                ptr(stg["tors"]), ptr(stg["seqres"]), ptr(stg["x_cond"]), ptr(stg["x_cond_mask"]), ptr(stg["sr"]),
+                ptr(stg["st"]), C.byref(tb), ptr(stg["atom14"]), ptr(ws), ws.numel(), int(use_graph), stream))
+        return stg["atom14"].clone(), stg["zs"].clone()
+
+    def upsample_rk(self, zs, method: str, num_steps: int, cond_interval: int, mask, key_rots, key_trans, key_torsions, seqres,
+                    tables, use_graph: bool = True):
+        """`mdgen_upsample_rk`: `upsample_euler` with `method` in ("midpoint", "heun3", "rk4") solving the windows in `num_steps`
+        steps (as `sample_rk`): key-frame conditioning -> solve -> atom14 in one call (one hipGraph).  Arguments and return
+        values as `upsample_euler`."""
+        B, T, L_, c, stg = self._stage_upsample(zs, cond_interval, mask, key_rots, key_trans, key_torsions, seqres)
+        code, S, ws = self._rk_call(method, num_steps, B, T, L_)
+        tb = L.ResidueTables.from_dict(tables)
+        sh = L.Shape(B, T, L_)
+        with self._call_stream(use_graph) as stream:
+            check(lib.mdgen_upsample_rk(
+                self._ctx, C.byref(sh), code, S, c, ptr(stg["zs"]), ptr(stg["mask"]), ptr(stg["rots"]), ptr(stg["trans"]),
                 ptr(stg["tors"]), ptr(stg["seqres"]), ptr(stg["x_cond"]), ptr(stg["x_cond_mask"]), ptr(stg["sr"]),
                 ptr(stg["st"]), C.byref(tb), ptr(stg["atom14"]), ptr(ws), ws.numel(), int(use_graph), stream))
         return stg["atom14"].clone(), stg["zs"].clone()

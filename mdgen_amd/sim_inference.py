@@ -4,10 +4,12 @@
   --num_steps S      Euler steps per block (the reference samples with its checkpoint's `sampling_method`; a non-Euler
                      checkpoint is refused unless S or --sampling_method is given);
   --sampling_method {euler,dopri5,midpoint,heun3,rk4}   the solver: dopri5 is the reference's adaptive default (torchdiffeq,
-                     atol 1e-6, rtol 1e-3), run per block through `inference()` (one step size per call, shared by a --batch
-                     group); euler without --num_steps takes the reference's 49-step grid; midpoint / heun3 / rk4 are
+                     atol 1e-6, rtol 1e-3), a host loop over the blocks inside `rollout()` (one step size per block, shared by a
+                     --batch group); euler without --num_steps takes the reference's 49-step grid; midpoint / heun3 / rk4 are
                      torchdiffeq's fixed-grid solvers with --num_steps steps (default 24 / 16 / 12 = 48 network evaluations),
-                     one captured graph per block, each peptide of a --batch group solved as if alone.  No flag: as before;
+                     all blocks of a group in one captured graph (`mdgen_rollout_rk`), each peptide of a --batch group solved as
+                     if alone.  No flag: as before;
+  --per_block        one `inference()` call per block from Python instead of the multi-block `rollout()`, whatever the solver;
   --batch N          peptides of equal length sampled together in one `inference()` call (the reference runs
                      B = 1, sim_inference.py:101-102; B = 16 is the regime BASELINE.json's metric is quoted on);
   --chunk_idx/--n_chunks   the reference's own sharding switches (tps_inference.py:17-18,160-161): this process
@@ -112,10 +114,16 @@ def sample_group(model, batch, args):
     """`num_rollouts` chained blocks for one batch; returns atom14 [B, R*T, L, 14, 3]."""
     method = getattr(args, "sampling_method", None)
     num_steps = 49 if method == "euler" and args.num_steps is None else args.num_steps
-    if hasattr(model, "rollout") and not getattr(args, "per_block", False) and method in (None, "euler"):
-        return model.rollout(batch, args.num_frames, args.num_rollouts, num_steps=num_steps)
+    if hasattr(model, "rollout") and not getattr(args, "per_block", False):
+        if method is None:   # (a model's rollout() need not know the keyword when no solver is named)
+            return model.rollout(batch, args.num_frames, args.num_rollouts, num_steps=num_steps)
+        atom14 = model.rollout(batch, args.num_frames, args.num_rollouts, num_steps=num_steps, sampling_method=method)
+        if method == "dopri5":
+            for b, st in enumerate(model.last_stats):
+                print(f"dopri5 block {b}: {st['nfe']} network evaluations ({st['accepted']} accepted, {st['rejected']} rejected steps)")
+        return atom14
     out = []
-    for _ in range(args.num_rollouts):   # (dopri5, midpoint, heun3, rk4: one inference() call per block; the device rollout is Euler only)
+    for _ in range(args.num_rollouts):   # --per_block: one inference() call per block from Python, whatever the solver
         atom14, batch = rollout(model, batch, args.num_frames, num_steps, sampling_method=method)
         out.append(atom14)
     return torch.cat(out, 1)

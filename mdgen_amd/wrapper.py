@@ -222,9 +222,9 @@ class NewMDGenWrapper:
         (upsampling_inference.py:47-82 around `inference`, wrapper.py:405-484).  `batch` holds KEY FRAMES only, one window per
         batch element: torsions (B,K,L,7,2), trans (B,K,L,3), rots (B,K,L,3,3), seqres (B,L), mask (B,L), with
         K = ceil(T / cond_interval) and T = `num_frames` (default `args.num_frames`); key frame k is frame k * cond_interval of
-        its window.  Euler: one library call (`mdgen_upsample_euler`, one hipGraph).  `sampling_method="dopri5"`:
-        `mdgen_prep_keyframes` -> `sample_dopri5` -> `samples_to_atom14`, counts in `last_stats`; "midpoint" | "heun3" | "rk4":
-        the same with `sample_rk` (`num_steps` steps, default 24 / 16 / 12).  The solver rules are
+        its window.  Euler: one library call (`mdgen_upsample_euler`, one hipGraph); "midpoint" | "heun3" | "rk4": likewise
+        (`mdgen_upsample_rk`; `num_steps` steps, default 24 / 16 / 12).  `sampling_method="dopri5"`:
+        `mdgen_prep_keyframes` -> `sample_dopri5` -> `samples_to_atom14`, counts in `last_stats`.  The solver rules are
         `inference()`'s.  Returns (atom14 (B,T,L,14,3), aa_out (B,T,L)); the latent samples are kept in `last_samples`."""
         from .geometry import residue_tables
         c = getattr(self.args, "cond_interval", None)
@@ -269,11 +269,8 @@ class NewMDGenWrapper:
             atom14 = samples_to_atom14(samples, prep["start_rot"], prep["start_trans"], batch["seqres"], False)
         elif sampling_method in RK_METHODS:
             S = RK_DEFAULT_STEPS[sampling_method] if num_steps is None else int(num_steps)
-            prep = prep_keyframes(rots, trans, tors, T, c)
-            samples = self.model.sample_rk(
-                zs, sampling_method, S, mask=mask.contiguous(), start_frames=(prep["start_rot"], prep["start_trans"]),
-                x_cond=prep["x_cond"], x_cond_mask=prep["x_cond_mask"], aatype=batch["seqres"], use_graph=use_graph)
-            atom14 = samples_to_atom14(samples, prep["start_rot"], prep["start_trans"], batch["seqres"], False)
+            atom14, samples = self.model.upsample_rk(zs, sampling_method, S, c, mask, rots, trans, tors, batch["seqres"],
+                                                     residue_tables(dev), use_graph=use_graph)
         else:
             S = 49 if num_steps is None else int(num_steps)
             atom14, samples = self.model.upsample_euler(zs, S, c, mask, rots, trans, tors, batch["seqres"],
@@ -281,21 +278,50 @@ class NewMDGenWrapper:
         self.last_samples = samples
         return atom14, batch["seqres"][:, None].expand(B, T, L_)
 
+    def _rollout_dopri5(self, batch, T, zs, atol, rtol):
+        """The blocks of `rollout()` with the adaptive solver: a host loop (dopri5 reads its error ratio back once per attempted
+        step, so it cannot be captured) of `inference()` -- prep_latents -> sample_dopri5 -> samples_to_atom14 -- and
+        `atom14_to_cond`, all on the device.  -> (atom14, samples (R,B,T,L,D), next conditioning frame, per-block stats)."""
+        from .geometry import atom14_to_cond
+        out, samples, stats = [], [], []
+        for z in zs:
+            ex = dict(batch)
+            ex["torsions"] = batch["torsions"].expand(-1, T, -1, -1, -1)
+            ex["trans"] = batch["trans"].expand(-1, T, -1, -1)
+            ex["rots"] = batch["rots"].expand(-1, T, -1, -1, -1)
+            atom14, _ = self.inference(ex, zs=z, sampling_method="dopri5", atol=atol, rtol=rtol)
+            nxt = atom14_to_cond(atom14[:, -1], batch["seqres"])
+            batch = dict(batch)
+            batch["trans"], batch["rots"], batch["torsions"] = nxt["trans"][:, None], nxt["rots"][:, None], nxt["torsions"][:, None]
+            out.append(atom14)
+            samples.append(self.last_samples)
+            stats.append(self.last_stats)
+        return torch.cat(out, 1), torch.stack(samples), nxt, stats
+
     def rollout(self, batch, num_frames: int, num_rollouts: int, num_steps=None, zs=None, use_graph=True,
-                return_next: bool = False):
+                return_next: bool = False, sampling_method=None, atol=1e-6, rtol=1e-3):
         """`num_rollouts` chained blocks of `num_frames` frames from the B = 1-frame conditioning batch of
         `sim_inference.get_batch` (torsions (B,1,L,7,2), trans (B,1,L,3), rots (B,1,L,3,3), seqres, mask (B,L)):
-        the loop of sim_inference.py:100-113 (`rollout` :61-98 per block) as ONE library call
-        (`mdgen_rollout_euler`), captured as one hipGraph.  `zs`: optional noise (num_rollouts, B, T, L, D)
-        (reference: a fresh device randn per block, wrapper.py:439).  Returns atom14 (B, num_rollouts*T, L, 14, 3)
-        [, the batch that would condition the next block]."""
+        the loop of sim_inference.py:100-113 (`rollout` :61-98 per block) as ONE library call, captured as one hipGraph:
+        `mdgen_rollout_euler` (`sampling_method` None or "euler"; None refuses a non-Euler checkpoint unless `num_steps` is
+        given) or `mdgen_rollout_rk` ("midpoint" | "heun3" | "rk4", `num_steps` steps per block, default 24 / 16 / 12).
+        "dopri5" (with `atol` / `rtol`, no `num_steps`) is a host loop over the blocks with the same device glue -- the solver
+        reads back once per attempted step -- and leaves a list of per-block counts in `last_stats`.  `zs`: optional noise
+        (num_rollouts, B, T, L, D); without it a block's noise is a fresh device randn (wrapper.py:439), drawn block by block
+        when a method is named.  Returns atom14 (B, num_rollouts*T, L, 14, 3) [, the batch that would condition the next
+        block]; the latent samples (num_rollouts, B, T, L, D) are kept in `last_samples`."""
         from .geometry import residue_tables
         if self.args.tps_condition or getattr(self.args, "cond_interval", None):
             raise L.MdgenError("rollout() is the forward-simulation driver (sim_condition models without cond_interval)")
+        if sampling_method not in _METHODS:
+            raise L.MdgenError(f"sampling_method must be None, 'euler', 'dopri5', 'midpoint', 'heun3' or 'rk4', got {sampling_method!r}")
+        if sampling_method == "dopri5" and num_steps is not None:
+            raise L.MdgenError("num_steps sets the fixed Euler grid; dopri5 chooses its own steps (pass one or the other)")
+        if num_steps is not None and int(num_steps) < 1:
+            raise L.MdgenError(f"num_steps must be >= 1, got {num_steps}")
         method = getattr(self.args, "sampling_method", "euler")
-        if num_steps is None and method != "euler":
+        if sampling_method is None and num_steps is None and method != "euler":
             raise L.MdgenError(f"checkpoint args say sampling_method={method!r}; pass num_steps=... to sample with Euler")
-        S = 49 if num_steps is None else int(num_steps)
         tors = batch["torsions"][:, 0].to(torch.float32)
         trans = batch["trans"][:, 0].to(torch.float32)
         rots = batch["rots"][:, 0].to(torch.float32)
@@ -303,11 +329,21 @@ class NewMDGenWrapper:
         B, L_ = trans.shape[:2]
         T, R = int(num_frames), int(num_rollouts)
         dev = trans.device
-        if zs is None:
+        if zs is None and sampling_method in (None, "euler"):
             zs = torch.randn(R, B, T, L_, self.latent_dim, device=dev)
+        elif zs is None:   # one draw per block, in block order: what the per-block loop of inference() calls draws
+            zs = torch.stack([torch.randn(B, T, L_, self.latent_dim, device=dev) for _ in range(R)])
         mask = batch["mask"].to(torch.float32).unsqueeze(1).expand(-1, T, -1)
-        atom14, samples, nxt = self.model.rollout_euler(zs, S, mask, rots, trans, tors, batch["seqres"],
-                                                        residue_tables(dev), use_graph=use_graph)
+        if sampling_method == "dopri5":
+            atom14, samples, nxt, self.last_stats = self._rollout_dopri5(batch, T, zs, atol, rtol)
+        elif sampling_method in RK_METHODS:
+            S = RK_DEFAULT_STEPS[sampling_method] if num_steps is None else int(num_steps)
+            atom14, samples, nxt = self.model.rollout_rk(zs, sampling_method, S, mask, rots, trans, tors, batch["seqres"],
+                                                         residue_tables(dev), use_graph=use_graph)
+        else:
+            S = 49 if num_steps is None else int(num_steps)
+            atom14, samples, nxt = self.model.rollout_euler(zs, S, mask, rots, trans, tors, batch["seqres"],
+                                                            residue_tables(dev), use_graph=use_graph)
         self.last_samples = samples
         if not return_next:
             return atom14
