@@ -10,16 +10,20 @@ forward-sim, crop 4, 1000 frames, batch 16, bf16 MFMA operands, S = 49 Euler ste
 hard-coded 50-point grid, wrapper.py:441-442).  Batches shard over ranks with no data-path collective
 (scaling = weak: every rank samples its own 16 x 1000 frames).
 
-The JSON line also carries
+A plain run does what the headline figure needs and no more: set-up, W warm-up steps, the K timed steps, the dump if asked
+for, the JSON line (`roofline`, `cpu_baseline` and `extra` are null in it).  `--full` adds the legs below, each a run of its own
+after the timed steps (about half a minute in all); `--no-roofline`, `--no-cpu-baseline` and `--no-extra` take single ones out again.
+
+With `--full` the JSON line also carries
   roofline     -- the dominant kernel (largest share of hipEvent time), its ALGORITHMIC flops per launch
                   divided by its average hipEvent-measured launch duration, vs the dense bf16 MFMA peak;
   cpu_baseline -- the CPU oracle (a port of the reference's PyTorch path, oracle/mdgen_oracle.py) timed on
                   this box's host cores on a bounded sample of the same workload;
-  extra        -- (1 GPU, default run) short legs for the other headline numbers, so that the driver's one bench line
+  extra        -- (1 GPU, default workload) short legs for the other headline numbers, so that one bench line
                   carries them: ATLAS crop 256 x 250 frames (north_star's second target), the TPS shard of configs[2],
                   the reference CLI's own B = 1 shape, the 10-block rollout rate (the region sim_inference.py:109-115
                   times), one DDP-less training step of configs[4]'s per-GPU shape, and a box probe (HBM copy rate,
-                  bf16 GEMM rate) that makes a slow box recognisable.  `--no-extra` skips them.
+                  bf16 GEMM rate) that makes a slow box recognisable.
 
 `--dump-outputs DIR` writes what the last timed step returned (float32 .npy files, see dump_outputs); the inputs are seeded,
 so the files of two builds run with the same arguments can be compared output for output.
@@ -439,7 +443,7 @@ def fake_sampler_main(a, rank, world):
         print(json.dumps(headline(a, world, B, T, L, a.euler_steps, dt, per_rank, False, data="none (fake sampler: test hook)")))
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -450,9 +454,13 @@ def main():
     ap.add_argument("--precision", choices=["bf16", "fp32"], default="bf16",
                     help="operand precision of the GEMM family / attention (fp32 = tolerance mode, ~10x slower)")
     ap.add_argument("--streams", type=int, default=None, help="library option 'streams' (default 2; 1 = single stream)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra legs (ATLAS, TPS, B = 1, rollout, training step, box probe)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the roofline of the dominant "
+                         "kernel, the CPU baseline and the extra legs (about half a minute more)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline leg")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the extra legs (ATLAS, TPS, B = 1, rollout, training step, box probe)")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="library run-time option (mdgen_ctx_set_option), e.g. mlp_path=1; repeatable")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -460,6 +468,27 @@ def main():
                          "atom14 and aa_out of inference(), and the sampled latents (wrapper.last_samples)")
     ap.add_argument("--fake-sampler", action="store_true", help=argparse.SUPPRESS)   # test hook, see fake_sampler_main
     ap.add_argument("--dist-selftest", action="store_true", help=argparse.SUPPRESS)  # one-rank RCCL self-test, see dist_selftest
+    return ap
+
+
+def legs_after_timing(a, rank, world):
+    """The legs that run after the timed steps, as a set of names: none in a plain run, and with `--full` each of `roofline`
+    (rank 0), `cpu_baseline` and `extra` (one process only; `extra` for the default bf16 workload only) unless its `--no-*`
+    option is given."""
+    legs = set()
+    if not a.full or rank != 0:
+        return legs
+    if not a.no_roofline:
+        legs.add("roofline")
+    if world == 1 and not a.no_cpu_baseline:
+        legs.add("cpu_baseline")
+    if world == 1 and not a.no_extra and a.precision == "bf16" and a.workload == "tetrapeptide_fwdsim_crop4_T1000_B16":
+        legs.add("extra")
+    return legs
+
+
+def main():
+    ap = build_parser()
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
@@ -545,8 +574,9 @@ def main():
         torch.cuda.synchronize()
         print("  eager re-run nonfinite:", int((~torch.isfinite(eager)).sum()), file=sys.stderr)
         raise AssertionError("non-finite atom14")
+    legs = legs_after_timing(a, rank, world)
     roof = None
-    if rank == 0 and not a.no_roofline:
+    if "roofline" in legs:
         # per-kernel-class durations measured with hipEvents on the launch stream (eager pass, graphs bypassed);
         # fp32 tolerance mode: its kernels (csrc/k_fp32.hip) are not priced against the bf16 MFMA peak -> None
         w.model.profile(True)
@@ -557,10 +587,10 @@ def main():
         if roof is not None:   # the whole call (all kernels, two streams, graph replay) against the same peak
             roof["whole_step_frac_of_mfma_peak"] = whole_step_frac(rep, B, T, L, dt / a.steps)
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if "cpu_baseline" in legs:
         cpu = cpu_baseline(cfg, sd, B, T, L, S, n_pad)
     extra = None
-    if rank == 0 and world == 1 and not a.no_extra and a.precision == "bf16" and a.workload == "tetrapeptide_fwdsim_crop4_T1000_B16":
+    if "extra" in legs:
         del w
         torch.cuda.empty_cache()
         extra = extra_legs(dev, dict(options, **({"streams": a.streams} if a.streams is not None else {})))
