@@ -299,6 +299,56 @@ int32_t mdgen_debug_rk_stage(mdgen_ctx* ctx, const mdgen_shape* shape, int32_t m
                              const float* k0, const float* k1, const float* k2, const float* k3, const float* x_cond,
                              const int64_t* x_cond_mask, const float* ipa_out, float* h, void* stream);
 
+/* SDE sampling: `Sampler.sample_sde(sampling_method='Euler' | 'Heun', diffusion_form=..., diffusion_norm=..., last_step=...,
+ * last_step_size=..., num_steps = n_points)` of transport.py:295-406 / integrators.py:5-72 for a velocity model on the Linear or GVP
+ * path (formulas and rounding: csrc/sde.inc).  t = linspace(t0, t1, n_points) in fp32 with t0 = sample_eps for SBDM, else 0, and
+ * t1 = 1 - last_step_size with a last step of non-zero size, else 1 - sample_eps; n_points - 1 stochastic steps of ONE size
+ * t[1] - t[0], then the last step at t1.  Network evaluations: n_points - 1 (Euler-Maruyama) or 2 (n_points - 1) (Heun), one more
+ * with a last step. */
+typedef struct mdgen_sde_opts {
+    int32_t method;           /* 1 Euler-Maruyama, 2 Heun */
+    int32_t path;             /* 0 Linear, 1 GVP (as mdgen_path_plan) */
+    int32_t diffusion_form;   /* 0 constant, 1 SBDM, 2 sigma, 3 linear, 4 decreasing, 5 increasing-decreasing (path.py:53-60) */
+    int32_t last_step;        /* 0 none, 1 Mean, 2 Tweedie, 3 Euler */
+    int32_t n_points;         /* the reference's num_steps: grid points */
+    double  diffusion_norm;
+    double  last_step_size;   /* in [0, 1); ignored without a last step */
+    double  sample_eps;       /* in [0, 1); SBDM needs it > 0 */
+} mdgen_sde_opts;
+/*   x            (B,T,L,D) fp32, 16-byte aligned: the initial state on entry, the sample on exit
+ *   noise        n_points - 1 tensors of (B,T,L,D) standard normals, 16-byte aligned; step i's starts at noise + i * noise_step_stride
+ *                floats.  The stride is a multiple of 4 and at least B T L D (a state ends on 16 bytes only for some shapes).  The
+ *                caller owns the noise: a replay with new noise in the same buffer gives a new sample.
+ *   workspace    mdgen_sde_workspace_bytes: the network workspace for the call's time rows + 2 velocities
+ * Every state is formed inside the launch that embeds it (k_sde_embed); nothing synchronises and nothing is read back, and with
+ * use_graph != 0 the solve is ONE hipGraph (non-default stream; cached per shape, options, stride and pointers).  Both precision modes.
+ * Errors, all decided on the host before any device call: -1 null argument; -2 unknown code, n_points < 2, last_step_size or
+ * sample_eps outside [0, 1), t0 >= t1, or a coefficient some state reads is not finite (the message names the time and the
+ * coefficient: SBDM with sample_eps = 0, Heun on the Linear path reaching t = 1); -7 alignment, stride or workspace size. */
+int32_t mdgen_sample_sde(mdgen_ctx* ctx, const mdgen_shape* shape, const mdgen_sde_opts* opts, float* x, const float* noise,
+                         int64_t noise_step_stride, const mdgen_cond* cond, void* workspace, size_t workspace_bytes,
+                         int32_t use_graph, void* stream);
+int32_t mdgen_sde_workspace_bytes(const mdgen_ctx* ctx, const mdgen_shape* shape, const mdgen_sde_opts* opts, size_t* bytes);
+
+/* Host-only test hook (no GPU): the plan of mdgen_sample_sde for `opts` as fp32 bits.  row_bits: the prepared time rows (room for
+ * cap_rows; *n_rows of them; a time equal to the row before it shares that row); coef_bits[row][4]: R = alpha / alpha',
+ * iV = 1 / (sigma^2 - R sigma' sigma), D, G = sqrtf(2 D); row_of[step * *n_stages + stage]; *last_row: the row of t1, -1 without a
+ * last step; scalar_bits[6]: dt, q = sqrtf(dt), 0.5 dt, the last step's size, Tweedie's 1 / alpha and sigma^2 / alpha. */
+int32_t mdgen_debug_sde_plan(const mdgen_sde_opts* opts, uint32_t* row_bits, uint32_t* coef_bits, int32_t cap_rows, int32_t* n_rows,
+                             int32_t* row_of, int32_t* n_stages, int32_t* last_row, uint32_t* scalar_bits);
+/* Host only: mdgen_debug_dispatch_plan's JSON for ONE step of mdgen_sample_sde with `opts` (n_points is taken as 2); "integrator":
+ * {"ode_sde_update": 1}. */
+int32_t mdgen_debug_sde_dispatch_plan(const mdgen_shape* shape, const mdgen_sde_opts* opts, int32_t tps_condition, int32_t num_layers,
+                                      int32_t ncu, int32_t xcd_round_robin, const char* options, char* buf, size_t buflen);
+/* Test hook: the state-forming embedding kernel (k_sde_embed) alone on one state of step `step` of the solve `opts` describes.
+ * state: 0 x itself, 1 x + noise term (Heun's xh of the first step), 2 the Euler-Maruyama step, 3 Heun's predictor, 4 Heun's result,
+ * 5 Heun's result + the noise term of step + 1; the last steps at t1: 6 Tweedie, 7 Euler, 8 Mean.  x (B,T,L,D) is overwritten by
+ * every state but 0 and 3; v0, v1: the velocities the state reads, xi: ONE step's noise (null where the state reads none);
+ * ipa_out: [B L][384] rows or null; h out: [B T L][384]. */
+int32_t mdgen_debug_sde_stage(mdgen_ctx* ctx, const mdgen_shape* shape, const mdgen_sde_opts* opts, int32_t state, int32_t step,
+                              float* x, const float* v0, const float* v1, const float* xi, const float* x_cond,
+                              const int64_t* x_cond_mask, const float* ipa_out, float* h, void* stream);
+
 /* Residue constant tables (device pointers; data of mdgen/residue_constants.py:1124-1216, 1367-1480), as the two
  * geometry entry points below take them one by one. */
 typedef struct mdgen_residue_tables {

@@ -27,6 +27,7 @@ EXPORTS = [
     "mdgen_sample_dopri5", "mdgen_dopri5_workspace_bytes", "mdgen_debug_dopri5_controller",
     "mdgen_sample_rk", "mdgen_rk_workspace_bytes", "mdgen_debug_rk_plan", "mdgen_debug_rk_stage",
     "mdgen_rollout_rk", "mdgen_upsample_rk",
+    "mdgen_sample_sde", "mdgen_sde_workspace_bytes", "mdgen_debug_sde_plan", "mdgen_debug_sde_dispatch_plan", "mdgen_debug_sde_stage",
 ]
 
 
@@ -63,6 +64,12 @@ class Cond(C.Structure):
         "mask", "start_rot", "start_trans", "end_rot", "end_trans", "rel7", "x_cond", "x_cond_mask", "aatype")]
 
 
+class SdeOpts(C.Structure):
+    """mdgen_sde_opts.  Build it with `sde_opts()`."""
+    _fields_ = ([(n, C.c_int32) for n in ("method", "path", "diffusion_form", "last_step", "n_points")]
+                + [(n, C.c_double) for n in ("diffusion_norm", "last_step_size", "sample_eps")])
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -93,6 +100,12 @@ def _load():
     lib.mdgen_rk_workspace_bytes.argtypes = [vp, C.POINTER(Shape), i32, i32, C.POINTER(sz)]
     lib.mdgen_debug_rk_plan.argtypes = [i32, i32, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)]
     lib.mdgen_debug_rk_stage.argtypes = [vp, C.POINTER(Shape), i32, i32, C.c_float] + [vp] * 10
+    sde_p = C.POINTER(SdeOpts)
+    lib.mdgen_sample_sde.argtypes = ctx_shape + [sde_p, vp, vp, i64, cond_p] + ws_bytes + [i32, vp]   # opts | x, noise, its step stride
+    lib.mdgen_sde_workspace_bytes.argtypes = [vp, C.POINTER(Shape), sde_p, C.POINTER(sz)]
+    lib.mdgen_debug_sde_plan.argtypes = [sde_p, vp, vp, i32, C.POINTER(i32), vp, C.POINTER(i32), C.POINTER(i32), vp]
+    lib.mdgen_debug_sde_dispatch_plan.argtypes = [C.POINTER(Shape), sde_p, i32, i32, i32, i32, C.c_char_p, C.c_char_p, sz]
+    lib.mdgen_debug_sde_stage.argtypes = [vp, C.POINTER(Shape), sde_p, i32, i32] + [vp] * 9
     tables_atom14 = [C.POINTER(ResidueTables), vp]
     lib.mdgen_rollout_euler.argtypes = (ctx_shape + [i32, i32] + [vp, vp] + [vp, vp, vp] + [vp] + [vp, vp]   # zs, mask | cond frame | seqres | x_cond, its mask
                                         + tables_atom14 + ws_bytes + [i32, vp])
@@ -227,6 +240,54 @@ def rk_plan(method, S):
     n_rows, n_st = C.c_int32(), C.c_int32()
     check(lib.mdgen_debug_rk_plan(int(code), S, bits.ctypes.data, cap, C.byref(n_rows), row_of.ctypes.data, C.byref(n_st)))
     return bits[:n_rows.value].copy(), row_of[:S * n_st.value].reshape(S, n_st.value).copy()
+
+
+# include/mdgen_amd.h mdgen_sde_opts: the reference's names (path.py:53-60 spells "inccreasing-decreasing") -> codes
+SDE_METHODS = {"Euler": 1, "Heun": 2}
+SDE_PATHS = {"Linear": 0, "GVP": 1}
+SDE_FORMS = {"constant": 0, "SBDM": 1, "sigma": 2, "linear": 3, "decreasing": 4, "inccreasing-decreasing": 5}
+SDE_LAST_STEPS = {None: 0, "Mean": 1, "Tweedie": 2, "Euler": 3}
+
+
+def sde_opts(sampling_method="Euler", path_type="GVP", diffusion_form="SBDM", diffusion_norm=1.0, last_step="Mean", last_step_size=0.04,
+             num_steps=250, sample_eps=0.0):
+    """`SdeOpts` from the reference's names (`num_steps`: grid points); an unknown name raises ValueError."""
+    codes = []
+    for what, table, name in (("sampling_method", SDE_METHODS, sampling_method), ("path_type", SDE_PATHS, path_type),
+                              ("diffusion_form", SDE_FORMS, diffusion_form), ("last_step", SDE_LAST_STEPS, last_step)):
+        if name not in table:
+            raise ValueError(f"{what} must be one of {list(table)}, got {name!r}")
+        codes.append(table[name])
+    return SdeOpts(*codes, int(num_steps), float(diffusion_norm), float(last_step_size), float(sample_eps))
+
+
+def sde_plan(opts):
+    """`mdgen_debug_sde_plan` (host only) -> dict: "rows" (uint32 fp32 bits), "coef" (uint32 [rows][4]: R, iV, D, G), "row_of"
+    [n_points - 1][stages], "last_row" (-1: no last step) and the scalars "dt", "q", "hdt", "h", "c0", "c1" as np.float32."""
+    import numpy as np
+    cap = 2 * max(opts.n_points, 2) + 1
+    rows = np.zeros(cap, dtype=np.uint32)
+    coef = np.zeros((cap, 4), dtype=np.uint32)
+    row_of = np.zeros(2 * max(opts.n_points, 2), dtype=np.int32)
+    sc = np.zeros(6, dtype=np.uint32)
+    n_rows, n_st, last = C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib.mdgen_debug_sde_plan(C.byref(opts), rows.ctypes.data, coef.ctypes.data, cap, C.byref(n_rows), row_of.ctypes.data,
+                                   C.byref(n_st), C.byref(last), sc.ctypes.data))
+    S = opts.n_points - 1
+    out = {"rows": rows[:n_rows.value].copy(), "coef": coef[:n_rows.value].copy(),
+           "row_of": row_of[:S * n_st.value].reshape(S, n_st.value).copy(), "last_row": last.value}
+    out.update(zip(("dt", "q", "hdt", "h", "c0", "c1"), sc.view(np.float32)))
+    return out
+
+
+def sde_dispatch_plan(B, T, L_, opts, tps=False, num_layers=5, ncu=256, xcd_round_robin=True, options=None):
+    """`mdgen_debug_sde_dispatch_plan` (host only): `dispatch_plan`'s dict for one step of sample_sde with `opts`."""
+    import json
+    buf = C.create_string_buffer(1 << 14)
+    sh = Shape(B, T, L_)
+    o = ",".join(f"{k}={int(v)}" for k, v in (options or {}).items()).encode()
+    check(lib.mdgen_debug_sde_dispatch_plan(C.byref(sh), C.byref(opts), int(tps), num_layers, ncu, int(xcd_round_robin), o, buf, len(buf)))
+    return json.loads(buf.value.decode())
 
 
 def dispatch_plan(B, T, L_, n_steps=1, mode=0, tps=False, num_layers=5, ncu=256, xcd_round_robin=True, options=None):

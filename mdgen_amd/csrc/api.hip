@@ -909,6 +909,7 @@ struct Run {
     bool no_embed_tail;          // the call never runs the embedding-as-tail form (mdgen_sample_dopri5, mdgen_sample_rk): prepare() skips its base rows
     const RkState* rk;           // stage descriptor of a fixed-grid Runge-Kutta evaluation (ode.inc): denoise_step embeds the state it
                                  // describes (k_rk_embed) instead of x; pointers of THIS view.  Null: x is embedded as it is
+    const SdeState* sde;         // the same for an SDE state (sde.inc, k_sde_embed); at most one of rk / sde is set
     bool concurrent;             // a view whose launches run beside other views' on other streams: kernels that use the call's split
                                  // scratch (one launch at a time) stay off meanwhile (for_each_view)
     float* h() const { return hp; }
@@ -1711,6 +1712,8 @@ static int denoise_step(const Run& r, int step, float* x, float* out, int euler,
     const EmbedParams e = embed_op(r, x, r.ipa_out_p + (long)step * r.ipa_step_stride);
     if (r.rk) {
         if (int er = launch(r, "rk_embed", [&] { launch_rk_embed(e, *r.rk, r.s); })) return er;
+    } else if (r.sde) {
+        if (int er = launch(r, "sde_embed", [&] { launch_sde_embed(e, *r.sde, r.s); })) return er;
     } else if (!(embed_tail && step > 0)) {
         if (int er = launch(r, "embed", [&] { launch_embed(e, r.s); })) return er;
     }
@@ -2106,6 +2109,7 @@ extern "C" int32_t mdgen_upsample_euler(mdgen_ctx* c, const mdgen_shape* sh, int
 }
 
 #include "ode.inc"
+#include "sde.inc"
 
 // ---------------------------------------------------------------------------------------------
 // dispatch plan (host only)
@@ -2146,16 +2150,9 @@ static int plan_json(const DryPlan& plan, int B, int nv, int ns, bool integrator
     return 0;
 }
 
-extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_steps, int32_t mode, int32_t tps_condition,
-                                             int32_t num_layers, int32_t ncu, int32_t xcd_round_robin, const char* options,
-                                             char* buf, size_t buflen) {
-    if (!sh || !buf || buflen < 64) return fail(-1, "null argument");
-    if (mode < 0 || mode > 7)
-        return fail(-2, "mode: 0 sample_euler, 1 forward, 2 sample_euler under the profiler, 3 forward with trace_h, 4 one dopri5 step, "
-                        "5 / 6 / 7 one midpoint / heun3 / rk4 step");
+// the context of a plan-mode run: no device memory, no streams (plan mode never touches them)
+static int dry_ctx(mdgen_ctx* c, int tps_condition, int num_layers, int ncu, int xcd_round_robin, bool prof_on, const char* options) {
     if (num_layers < 1 || num_layers > 8 || ncu < 1) return fail(-2, "num_layers in 1..8, ncu >= 1");
-    mdgen_ctx ctx;   // no device memory, no streams: plan mode never touches them
-    mdgen_ctx* c = &ctx;
     c->nl = num_layers;
     c->D = tps_condition ? 28 : 21;
     c->d.num_layers = num_layers;
@@ -2168,7 +2165,7 @@ extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_st
     c->finalized = true;
     c->ncu = ncu;
     c->xcd_round_robin = xcd_round_robin != 0;
-    c->prof_on = mode == 2;
+    c->prof_on = prof_on;
     for (std::string rest = options ? options : ""; !rest.empty();) {
         const size_t comma = rest.find(',');
         const std::string kv = rest.substr(0, comma);
@@ -2177,11 +2174,29 @@ extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_st
         if (eq == std::string::npos) return fail(-2, "options: name=value[,name=value...]");
         if (int e = mdgen_ctx_set_option(c, kv.substr(0, eq).c_str(), std::atoi(kv.c_str() + eq + 1))) return e;
     }
+    return 0;
+}
+struct DryScope {
+    DryScope(DryPlan* p) { g_dry = p; }
+    ~DryScope() { g_dry = nullptr; }
+};
+static mdgen_cond fake_cond() {   // never dereferenced: plan mode launches nothing
+    const float* fake = (const float*)4096;
+    return {fake, fake, fake, fake, fake, nullptr, fake, (const int64_t*)fake, (const int64_t*)fake};
+}
+
+extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_steps, int32_t mode, int32_t tps_condition,
+                                             int32_t num_layers, int32_t ncu, int32_t xcd_round_robin, const char* options,
+                                             char* buf, size_t buflen) {
+    if (!sh || !buf || buflen < 64) return fail(-1, "null argument");
+    if (mode < 0 || mode > 7)
+        return fail(-2, "mode: 0 sample_euler, 1 forward, 2 sample_euler under the profiler, 3 forward with trace_h, 4 one dopri5 step, "
+                        "5 / 6 / 7 one midpoint / heun3 / rk4 step");
+    mdgen_ctx ctx;
+    mdgen_ctx* c = &ctx;
+    if (int e = dry_ctx(c, tps_condition, num_layers, ncu, xcd_round_robin, mode == 2, options)) return e;
     DryPlan plan;
-    struct Dry {
-        Dry(DryPlan* p) { g_dry = p; }
-        ~Dry() { g_dry = nullptr; }
-    } dry(&plan);
+    DryScope dry(&plan);
     const bool fwd = mode == 1 || mode == 3;
     const bool rkm = mode >= 5;   // one step of mdgen_sample_rk, method mode - 4: its time rows
     const int S = mode == 4 ? ode::kStages : rkm ? rk_method(mode - 4)->stages : fwd ? 1 : n_steps;
@@ -2189,9 +2204,7 @@ extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_st
     Run r{};
     if (int e = make_run(&r, c, sh, S, t_shared, f32_path(c), (void*)4096, (size_t)1 << 60, nullptr)) return e;
     float* fake = (float*)4096;   // never dereferenced: plan mode launches nothing
-    const mdgen_cond cd = {fake, fake, fake, fake, fake, nullptr, fake, (const int64_t*)fake, (const int64_t*)fake};
-    if (int e = check_cond(&cd)) return e;
-    bind_cond(r, cd);
+    bind_cond(r, fake_cond());
     const int ns = fwd || mode >= 4 ? 1 : n_streams(r);
     const int nv = plan_views(r.B, r.T, r.L, ns);
     if (mode == 4) {
@@ -2206,6 +2219,33 @@ extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_st
         if (int e = euler_body(r, tg, fake)) return e;
     }
     return plan_json(plan, r.B, nv, ns, mode >= 4, buf, buflen);
+}
+
+// mdgen_debug_dispatch_plan for ONE step of mdgen_sample_sde with `opts` (n_points is taken as 2): the same JSON, "integrator":
+// {"ode_sde_update": 1}
+extern "C" int32_t mdgen_debug_sde_dispatch_plan(const mdgen_shape* sh, const mdgen_sde_opts* opts, int32_t tps_condition,
+                                                 int32_t num_layers, int32_t ncu, int32_t xcd_round_robin, const char* options,
+                                                 char* buf, size_t buflen) {
+    if (!sh || !opts || !buf || buflen < 64) return fail(-1, "null argument");
+    mdgen_sde_opts o = *opts;
+    o.n_points = 2;
+    SdePlan pl;
+    if (int e = sde_plan(o, &pl)) return e;
+    mdgen_ctx ctx;
+    mdgen_ctx* c = &ctx;
+    if (int e = dry_ctx(c, tps_condition, num_layers, ncu, xcd_round_robin, false, options)) return e;
+    DryPlan plan;
+    DryScope dry(&plan);
+    Run r{};
+    if (int e = make_run(&r, c, sh, (int)pl.rows.size(), 1, f32_path(c), (void*)4096, (size_t)1 << 60, nullptr)) return e;
+    bind_cond(r, fake_cond());
+    r.no_embed_tail = true;
+    const int nv = plan_views(r.B, r.T, r.L, 1);
+    if (nv == 0) return fail(-2, "sample too large for one launch");
+    float* fake = (float*)4096;
+    float* v[2] = {fake, fake};
+    if (int e = sde_body(r, o, pl, nv, fake, v, fake, 0)) return e;
+    return plan_json(plan, r.B, nv, 1, true, buf, buflen);
 }
 
 // ---------------------------------------------------------------------------------------------

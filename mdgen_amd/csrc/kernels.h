@@ -558,6 +558,34 @@ void launch_rk_embed(const EmbedParams& p, const RkState& st, hipStream_t s);
 // y <- the state `st` describes, elementwise over n values (the result of the last step)
 void launch_rk_update(const RkState& st, long n, hipStream_t s);
 
+// SDE sampler (k_sde.hip; plan and orchestration in sde.inc): the states of an Euler-Maruyama or Heun step, formed like the
+// Runge-Kutta states inside the launch that embeds them.  With the coefficients of evaluation time j (SdeState::R[j], iV[j], D[j])
+//   F_j(v, x) = v + D_j * (((R_j * v) - x) * iV_j)        (velocity + diffusion * score)
+// and xi the step's noise, every written operation one rounded fp32 operation:
+enum SdeForm : int {
+    kSdeX = 0,       // x                                                   (first evaluation of an Euler-Maruyama solve)
+    kSdeNoise,       // x + G * (xi * q)                                    (Heun: xh of the first step)
+    kSdeEm,          // (x + F_0(v0, x) * dt) + G * (xi * q)                (an Euler-Maruyama step)
+    kSdeDrift,       // x + dt * F_0(v0, x)                                 (Heun's predictor xp; the Mean last step, dt = its size)
+    kSdeHeun,        // x + hdt * (K1 + K2), K1 = F_0(v0, x), K2 = F_1(v1, x + dt * K1)
+    kSdeHeunNoise,   // kSdeHeun + G * (xi * q)                             (G, xi: the NEXT step's)
+    kSdeTweedie,     // x * c0 + c1 * (((R_0 * v0) - x) * iV_0)             (c0 = 1 / alpha, c1 = sigma^2 / alpha)
+    kSdeEuler,       // x + v0 * dt                                         (the Euler last step, dt = its size)
+    kSdeForms
+};
+struct SdeState {
+    int form;
+    int store;                     // the state is also stored over y (each element by the thread that read it)
+    float dt, hdt, q, G;           // step size, 0.5 dt, sqrtf(dt), sqrtf(2 D) of the noise term's time
+    float R[2], iV[2], D[2];       // coefficients of up to two evaluation times
+    float c[2];
+    const float* v[2];             // velocities; null where the form reads none
+    const float* xi;               // the noise of one step (B, T, L, D), or null
+    float* y;                      // x (B, T, L, D)
+};
+void launch_sde_embed(const EmbedParams& p, const SdeState& st, hipStream_t s);
+void launch_sde_update(const SdeState& st, long n, hipStream_t s);
+
 // SE(3) / pre / post (k_se3.hip)
 void launch_rigid_compose(long n, const float* r1, const float* t1, const float* r2, const float* t2, float* ro,
                           float* to, hipStream_t s);

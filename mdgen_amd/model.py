@@ -360,6 +360,41 @@ class LatentMDGenModel:
             check(lib.mdgen_sample_rk(self._ctx, C.byref(sh), code, S, ptr(x), C.byref(cond), ptr(ws), ws.numel(), int(use_graph), stream))
         return x.clone()
 
+    # ---- SDE: Euler-Maruyama / Heun --------------------------------------------------------------
+    def sample_sde(self, zs, opts, mask=None, start_frames=None, end_frames=None, x_cond=None, x_cond_mask=None, aatype=None,
+                   noise=None, use_graph: bool = True, rel_quats=None, noise_step_stride=None):
+        """`mdgen_sample_sde`: the reference's `Sampler.sample_sde` (transport.py:295-406) with `opts` = `_lib.sde_opts(
+        sampling_method, path_type, diffusion_form, diffusion_norm, last_step, last_step_size, num_steps, sample_eps)`:
+        n_points - 1 Euler-Maruyama or Heun steps on linspace(t0, t1, n_points), then the last step; n_points - 1 or
+        2 (n_points - 1) network evaluations, one more with a last step.  Nothing synchronises, and with `use_graph` the whole
+        solve is one hipGraph.  `noise`: (n_points - 1, B, T, L, D) standard normals, one tensor per step; None: drawn with
+        torch.randn from the device generator, so the same torch.manual_seed gives the same sample.  The noise is staged in a
+        persistent buffer of (n_points - 1) x state bytes (stable pointers: the graph is replayed with new noise in it) -- at
+        250 points and B 16 x T 1000 x L 4 that is 1.3 GB.  `noise_step_stride` (floats, a multiple of 4, at least one state;
+        default: one state rounded up to 4) is the distance between two steps' noise in that buffer.  Returns the sample."""
+        B, T, L_, *frames = self._sampler_inputs(zs, mask, start_frames, end_frames, x_cond, x_cond_mask, aatype)
+        D, S = zs.shape[-1], opts.n_points - 1
+        sh = L.Shape(B, T, L_)
+        nbytes = C.c_size_t()
+        check(lib.mdgen_sde_workspace_bytes(self._ctx, C.byref(sh), C.byref(opts), C.byref(nbytes)))   # (refuses bad options first)
+        ws = self._sized_workspace(("sde", B, T, L_), nbytes.value)
+        state = B * T * L_ * D
+        stride = (state + 3) // 4 * 4 if noise_step_stride is None else int(noise_step_stride)
+        if stride < state:
+            raise L.MdgenError(f"noise_step_stride {stride} is below one state of {state} floats")
+        if noise is not None and tuple(noise.shape) != (S, B, T, L_, D):
+            raise L.MdgenError(f"noise must be (n_points - 1, B, T, L, D) = {(S, B, T, L_, D)}, got {tuple(noise.shape)}")
+        x, cond = self._stage_cond(zs, mask, *frames, x_cond, x_cond_mask, aatype, rel_quats)
+        buf = self._staged(("sde_noise", S, stride), dict(noise=((S, stride), torch.float32)), {})["noise"]
+        if noise is None:
+            noise = torch.randn(S, B, T, L_, D, device=self.device)
+        require_cuda(noise)
+        buf[:, :state].copy_(noise.reshape(S, state))
+        with self._call_stream(use_graph) as stream:
+            check(lib.mdgen_sample_sde(self._ctx, C.byref(sh), C.byref(opts), ptr(x), ptr(buf), stride, C.byref(cond), ptr(ws), ws.numel(),
+                                       int(use_graph), stream))
+        return x.clone()
+
     # ---- multi-block rollout -----------------------------------------------------------------
     def rollout_euler(self, zs, num_steps: int, mask, cond_rots, cond_trans, cond_torsions, seqres, tables,
                       use_graph: bool = True):

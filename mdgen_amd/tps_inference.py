@@ -65,11 +65,13 @@ def build_parser():
     p.add_argument("--start_frame", type=int, default=0, help="MD frame of {name}.npy used as the start state")
     p.add_argument("--end_frame", type=int, default=-1, help="MD frame of {name}.npy used as the end state")
     p.add_argument("--num_steps", type=int, default=None)
-    p.add_argument("--sampling_method", choices=["euler", "dopri5", "midpoint", "heun3", "rk4"], default=None,
+    p.add_argument("--sampling_method", choices=["euler", "dopri5", "midpoint", "heun3", "rk4", "sde", "sde_heun"], default=None,
                    help="solver (default: the checkpoint's, refused unless it is euler or --num_steps is given); dopri5: "
                         "the reference's adaptive solver, one step size per call shared by the --batch_size paths; midpoint / heun3 / "
                         "rk4: fixed-grid solvers with --num_steps steps (default 24 / 16 / 12)")
     p.add_argument("--synthetic", action="store_true")
+    from .sim_inference import add_sde_arguments
+    add_sde_arguments(p)
     return p
 
 
@@ -79,7 +81,7 @@ def run(args, model, device, names_seqres, rank=0, world=1):
     import os
     from .geometry import restype_order
     from .pdb import atom14_to_pdb
-    from .sim_inference import select_names
+    from .sim_inference import sde_kwargs, select_names
     names = select_names(list(names_seqres), args.pdb_id, args.chunk_idx, args.n_chunks, rank, world)
     os.makedirs(args.out_dir, exist_ok=True)
     done = []
@@ -94,7 +96,7 @@ def run(args, model, device, names_seqres, rank=0, world=1):
             if method is None:
                 atom14s, _ = model.inference(batch, num_steps=args.num_steps)
             else:
-                atom14s, _ = model.inference(batch, num_steps=args.num_steps, sampling_method=method)
+                atom14s, _ = model.inference(batch, num_steps=args.num_steps, sampling_method=method, **sde_kwargs(args))
                 if method == "dopri5":
                     st = model.last_stats
                     print(f"{name} batch {i}: dopri5 {st['nfe']} network evaluations ({st['accepted']} accepted, "
@@ -110,7 +112,7 @@ def run(args, model, device, names_seqres, rank=0, world=1):
 def main(argv=None):
     import pandas as pd
     from .config import ModelConfig
-    from .sim_inference import dist_env
+    from .sim_inference import dist_env, sde_kwargs
     from .synthetic import synth_state_dict
     from .wrapper import NewMDGenWrapper
     args = build_parser().parse_args(argv)
@@ -118,6 +120,7 @@ def main(argv=None):
         raise SystemExit("--num_steps sets the Euler grid; dopri5 chooses its own steps (pass one or the other)")
     if args.num_steps is not None and args.num_steps < 1:
         raise SystemExit(f"--num_steps must be >= 1, got {args.num_steps}")
+    sde_kwargs(args)
     rank, world, local_rank = dist_env()
     device = torch.device("cuda", local_rank)
     torch.cuda.set_device(device)

@@ -2,10 +2,12 @@
 `create_transport(...)` -> `Sampler(transport).sample_ode(sampling_method='euler', num_steps=50)`
 -> `fn(x0, model_fn, **kw)` (transport.py:408-451, integrators.py:74-114).
 
-velocity prediction + GVP/Linear path => integration interval (t0, t1) = (0, 1) exactly
+velocity prediction + GVP/Linear path => the ODE's integration interval (t0, t1) = (0, 1) exactly
 (transport.py:95-124, 561-563).  The fixed-grid solvers are provided here: Euler, midpoint, heun3 and rk4 (torchdiffeq's
-fixed_grid.py); adaptive dopri5 is `LatentMDGenModel.sample_dopri5`; the SDE sampler and the likelihood path are outside
-the accelerated hot path.
+fixed_grid.py); adaptive dopri5 is `LatentMDGenModel.sample_dopri5`.  `Sampler.sample_sde` is the reference's stochastic sampler
+(transport.py:295-406, integrators.py:5-72: Euler-Maruyama or Heun, then a last step) -> `LatentMDGenModel.sample_sde`, one
+captured graph; its interval follows `check_interval(..., sde=True)` with the transport's `sample_eps`.  The likelihood path is
+outside the accelerated hot path.
 """
 from __future__ import annotations
 
@@ -15,16 +17,24 @@ import torch
 
 
 class Transport:
-    def __init__(self, path_type="GVP", prediction="velocity"):
+    def __init__(self, path_type="GVP", prediction="velocity", sample_eps=0):
         if prediction != "velocity":
             raise NotImplementedError("only velocity prediction is on the accelerated path")
         if path_type not in ("GVP", "Linear"):
             raise NotImplementedError("only GVP / Linear paths (t0, t1 = 0, 1)")
         self.path_type, self.prediction = path_type, prediction
-        self.train_eps = self.sample_eps = 0
+        self.train_eps, self.sample_eps = 0, (0 if sample_eps is None else sample_eps)
 
-    def check_interval(self, *a, **k):
-        return 0, 1
+    def check_interval(self, train_eps=0, sample_eps=0, *, diffusion_form="SBDM", sde=False, reverse=False, eval=False,
+                       last_step_size=0.0):
+        """transport.py:95-124 for a velocity model on the GVP / Linear path: (0, 1) for the ODE; for the SDE t0 = eps with the
+        SBDM diffusion (else 0) and t1 = 1 - last_step_size, or 1 - eps without a last step size."""
+        if not sde:
+            return (1, 0) if reverse else (0, 1)
+        eps = sample_eps if eval else train_eps
+        t0 = eps if diffusion_form == "SBDM" else 0
+        t1 = 1 - eps if last_step_size == 0 else 1 - last_step_size
+        return (1 - t0, 1 - t1) if reverse else (t0, t1)
 
     # ---- training target and loss, forward only (transport.py:126-189; SURVEY row t-3) ----------------------
     def sample(self, x1):
@@ -72,7 +82,8 @@ class Transport:
 
 def create_transport(args=None, path_type="GVP", prediction="velocity", loss_weight=None, train_eps=None,
                      sample_eps=None):
-    return Transport(path_type, prediction)
+    """`sample_eps` (default 0) is kept: the SDE sampler's SBDM diffusion needs it > 0."""
+    return Transport(path_type, prediction, sample_eps)
 
 
 def linspace01(n):
@@ -111,6 +122,43 @@ def rk_step(method, f, t0, t1, y0):
 
 
 RK_METHODS = ("midpoint", "heun3", "rk4")
+SDE_METHODS = ("sde", "sde_heun")   # wrapper / CLI names of Sampler.sample_sde(sampling_method="Euler" | "Heun")
+
+
+def sde_solve(f, x, noise, plan, method, last_step):
+    """The arithmetic of `mdgen_sample_sde` (csrc/sde.inc) as a host loop in x's dtype: f(t, x) the velocity model (t a 0-dim
+    tensor), noise[i] step i's standard normals, `plan` = `_lib.sde_plan(opts)` -- the library's fp32 time rows and coefficients.
+    With F(v, x; c) = v + D (((R v) - x) iV):  Euler-Maruyama x <- (x + F dt) + G (xi q);  Heun xh = x + G (xi q), K1 = F(f(xh)),
+    xp = xh + dt K1, K2 = F(f(xp); at t + dt), x <- xh + (0.5 dt) (K1 + K2);  then the last step at t1."""
+    import numpy as np
+    T = lambda v: torch.tensor(float(v), dtype=x.dtype, device=x.device)
+    rows, coef = plan["rows"].view(np.float32), plan["coef"].view(np.float32)
+    dt, q, hdt, h = (T(plan[k]) for k in ("dt", "q", "hdt", "h"))
+
+    def at(r):
+        return T(rows[r]), [T(c) for c in coef[r]]
+
+    def F(v, x_, c):
+        return v + c[2] * (((c[0] * v) - x_) * c[1])
+    for i, step_rows in enumerate(plan["row_of"]):
+        t, c = at(step_rows[0])
+        if method == "Euler":
+            x = (x + F(f(t, x), x, c) * dt) + c[3] * (noise[i] * q)
+        else:
+            xh = x + c[3] * (noise[i] * q)
+            k1 = F(f(t, xh), xh, c)
+            xp = xh + dt * k1
+            t2, c2 = at(step_rows[1])
+            x = xh + hdt * (k1 + F(f(t2, xp), xp, c2))
+    if last_step is None:
+        return x
+    t, c = at(plan["last_row"])
+    v = f(t, x)
+    if last_step == "Mean":
+        return x + F(v, x, c) * h
+    if last_step == "Tweedie":
+        return x * T(plan["c0"]) + T(plan["c1"]) * (((c[0] * v) - x) * c[1])
+    return x + v * h
 
 
 class Sampler:
@@ -175,5 +223,39 @@ class Sampler:
             for i in range(S):
                 x = rk_step(method, lambda t, y: model_fn(y, ones * t, **model_kwargs), tg[i], tg[i + 1], x)
             return x[None]
+
+        return _sample
+
+    def sample_sde(self, *, sampling_method="Euler", diffusion_form="SBDM", diffusion_norm=1.0, last_step="Mean",
+                   last_step_size=0.04, num_steps=250):
+        """The reference's signature and defaults (transport.py:347-406).  Returns fn(init, model_fn, **model_kwargs); `num_steps`
+        is the number of grid points: num_steps - 1 stochastic steps ("Euler": Euler-Maruyama, "Heun") on linspace(t0, t1,
+        num_steps), then `last_step` ("Mean", "Tweedie", "Euler" or None) at t1.  The default SBDM diffusion needs a transport
+        with sample_eps > 0 (`create_transport(..., sample_eps=1e-3)`): at 0 the plan is refused, as the reference's run ends in
+        NaN.  Build-specific keywords of fn: `noise` ((num_steps - 1, *init.shape) standard normals; default: drawn with
+        torch.randn on init's device) and `use_graph`.  The returned tensor holds only the final state, shape [1, *init.shape],
+        as `sample_ode` returns."""
+        from . import _lib as L
+        opts = L.sde_opts(sampling_method, self.transport.path_type, diffusion_form, diffusion_norm, last_step, last_step_size,
+                          num_steps, self.transport.sample_eps)
+        plan = L.sde_plan(opts)   # (refuses here, before any model call, what the library would refuse)
+
+        def _sample(init, model_fn, **model_kwargs):
+            from .model import LatentMDGenModel
+            fn, kw = model_fn, dict(model_kwargs)
+            use_graph = kw.pop("use_graph", True)
+            noise = kw.pop("noise", None)
+            model_kwargs = dict(kw)
+            if isinstance(fn, partial):
+                kw = {**fn.keywords, **kw}
+                fn = fn.func
+            owner = getattr(fn, "__self__", None)
+            if isinstance(owner, LatentMDGenModel) and getattr(fn, "__name__", "") in ("forward", "forward_inference"):
+                return owner.sample_sde(init, opts, noise=noise, use_graph=use_graph, **kw)[None]
+            # generic drift (any callable): the same formulas in a host loop, in init's dtype, on the library's grid and coefficients
+            if noise is None:
+                noise = torch.randn((opts.n_points - 1,) + tuple(init.shape), dtype=init.dtype, device=init.device)
+            ones = torch.ones(init.shape[0], dtype=init.dtype, device=init.device)
+            return sde_solve(lambda t, x: model_fn(x, ones * t, **model_kwargs), init, noise, plan, sampling_method, last_step)[None]
 
         return _sample

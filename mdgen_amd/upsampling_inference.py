@@ -2,7 +2,7 @@
 (`--ckpt --data_dir --suffix --pdb_id --batch_size --out_dir --split`), plus
 
   --num_steps S      Euler steps per window (a non-Euler checkpoint is refused unless S or --sampling_method is given);
-  --sampling_method {euler,dopri5,midpoint,heun3,rk4}   the solver: dopri5 is the reference's adaptive default (torchdiffeq,
+  --sampling_method {euler,dopri5,midpoint,heun3,rk4,sde,sde_heun}   the solver: dopri5 is the reference's adaptive default (torchdiffeq,
                      atol 1e-6, rtol 1e-3; one step size per call, shared by a --batch_size group); euler without --num_steps
                      takes the reference's 49-step grid; midpoint / heun3 / rk4: torchdiffeq's fixed-grid solvers with
                      --num_steps steps (default 24 / 16 / 12 = 48 network evaluations);
@@ -64,6 +64,7 @@ def key_frame_windows(arr, seqres_str, num_frames, cond_interval, device):
 
 def upsample_name(model, windows, args):
     """All windows of one name, `batch_size` at a time -> atom14 (n_windows * T, L, 14, 3)."""
+    from .sim_inference import sde_kwargs
     W = windows["trans"].shape[0]
     method = getattr(args, "sampling_method", None)
     num_steps = 49 if method == "euler" and args.num_steps is None else args.num_steps
@@ -73,7 +74,7 @@ def upsample_name(model, windows, args):
         if method is None:
             atom14, _ = model.upsample(kb, num_steps=num_steps)
         else:
-            atom14, _ = model.upsample(kb, num_steps=num_steps, sampling_method=method)
+            atom14, _ = model.upsample(kb, num_steps=num_steps, sampling_method=method, **sde_kwargs(args))
             if method == "dopri5":
                 st = model.last_stats
                 print(f"dopri5: {st['nfe']} network evaluations ({st['accepted']} accepted, {st['rejected']} rejected steps)")
@@ -133,7 +134,7 @@ def build_parser():
     p.add_argument("--split", type=str, default="splits/4AA_implicit_test.csv")
     p.add_argument("--num_steps", type=int, default=None,
                    help="solver steps per window (Euler default: 49 = the reference's 50-point grid, Euler checkpoints only)")
-    p.add_argument("--sampling_method", choices=["euler", "dopri5", "midpoint", "heun3", "rk4"], default=None,
+    p.add_argument("--sampling_method", choices=["euler", "dopri5", "midpoint", "heun3", "rk4", "sde", "sde_heun"], default=None,
                    help="solver (default: the checkpoint's, refused unless it is euler or --num_steps is given)")
     p.add_argument("--precision", choices=["bf16", "fp32"], default="bf16",
                    help="bf16 MFMA operands (default) or the fp32-operand tolerance mode (~10x slower)")
@@ -143,6 +144,8 @@ def build_parser():
     p.add_argument("--num_frames", type=int, default=None, help="frames per window (only with --synthetic; default 1000)")
     p.add_argument("--cond_interval", type=int, default=None,
                    help="frames between key frames (only with --synthetic; default 100)")
+    from .sim_inference import add_sde_arguments
+    add_sde_arguments(p)
     return p
 
 
@@ -153,6 +156,8 @@ def parse_args(argv=None):
         p.error("--num_steps sets the Euler grid; dopri5 chooses its own steps (pass one or the other)")
     if args.num_steps is not None and args.num_steps < 1:
         p.error(f"--num_steps must be >= 1, got {args.num_steps}")
+    from .sim_inference import sde_kwargs
+    sde_kwargs(args)
     if not args.synthetic and (args.num_frames is not None or args.cond_interval is not None):
         p.error("--num_frames / --cond_interval go with --synthetic only (a checkpoint supplies its own)")
     if not args.synthetic and not args.ckpt:

@@ -17,14 +17,20 @@ from .config import ModelConfig
 from .geometry import prep_keyframes, samples_to_atom14
 from .model import LatentMDGenModel
 from .rigid_utils import Rigid, Rotation
-from .transport import RK_METHODS, Sampler, create_transport
+from .transport import RK_METHODS, SDE_METHODS, Sampler, create_transport
 
 _BACKFILL = ["inpainting", "no_torsion", "hyena", "no_aa_emb", "supervise_all_torsions", "supervise_no_torsions",
              "design_key_frames", "no_design_torsion", "cond_interval", "mpnn", "dynamic_mpnn", "no_offsets",
              "no_frames", "design", "tps_condition", "sim_condition", "abs_pos_emb", "prepend_ipa", "oracle"]
 # steps of the fixed-grid Runge-Kutta solvers when num_steps is not given: 48 network evaluations each (Euler's default grid: 49)
 RK_DEFAULT_STEPS = {"midpoint": 24, "heun3": 16, "rk4": 12}
-_METHODS = (None, "euler", "dopri5") + RK_METHODS
+_METHODS = (None, "euler", "dopri5") + RK_METHODS + SDE_METHODS
+_METHODS_MSG = "sampling_method must be None, 'euler', 'dopri5', 'midpoint', 'heun3', 'rk4', 'sde' or 'sde_heun'"
+# the SDE sampler's options when `sde={...}` does not name them.  The reference's own defaults (SBDM, 250 points) need
+# sample_eps > 0; the "sigma" diffusion is finite on the whole interval with sample_eps = 0.  49 stochastic steps cost what Euler's
+# default grid costs (+ 1 evaluation for the last step); their sample quality has not been measured.
+SDE_DEFAULTS = dict(diffusion_form="sigma", diffusion_norm=1.0, last_step="Mean", last_step_size=0.04, sample_eps=0.0)
+SDE_DEFAULT_STEPS = 49
 _UNSUPPORTED = ["inpainting", "hyena", "no_aa_emb", "design_key_frames", "mpnn", "dynamic_mpnn", "no_offsets",
                 "no_frames", "design", "no_torsion", "no_design_torsion", "interleave_ipa",
                 "abs_time_emb", "oracle", "no_rope"]
@@ -162,8 +168,23 @@ class NewMDGenWrapper:
                                              mask=prep["loss_mask"], model_kwargs=prep["model_kwargs"], t=t, x0=x0)
         return out["loss"], out
 
+    def _sde_opts(self, sampling_method, num_steps, sde):
+        """`_lib.SdeOpts` of `sampling_method` "sde" (Euler-Maruyama) / "sde_heun" with `num_steps` stochastic steps (default 49)
+        and the options of `sde` over SDE_DEFAULTS; an unknown option or value raises before anything runs."""
+        unknown = set(sde or {}) - set(SDE_DEFAULTS)
+        if unknown:
+            raise L.MdgenError(f"sde options are {sorted(SDE_DEFAULTS)}, got {sorted(unknown)}")
+        S = SDE_DEFAULT_STEPS if num_steps is None else int(num_steps)
+        try:
+            opts = L.sde_opts("Euler" if sampling_method == "sde" else "Heun", self.args.path_type, num_steps=S + 1,
+                              **{**SDE_DEFAULTS, **(sde or {})})
+        except ValueError as e:
+            raise L.MdgenError(str(e)) from None
+        L.sde_plan(opts)   # (the library's own refusals: a non-finite coefficient, t0 >= t1)
+        return opts
+
     def inference(self, batch, zs=None, num_steps=None, use_graph=True, rel_quats=None, sampling_method=None, atol=1e-6,
-                  rtol=1e-3):
+                  rtol=1e-3, sde=None, noise=None):
         """wrapper.py:405-484.  Extra keywords (defaults reproduce the reference): `zs` explicit noise
         (reference: device randn, wrapper.py:439), `num_steps` Euler steps S (reference: 50 grid points = 49
         steps, wrapper.py:441-442 / transport.py:412), `rel_quats` (two-sided models): the relative-frame 7-vectors
@@ -172,7 +193,14 @@ class NewMDGenWrapper:
         `LatentMDGenModel.sample_dopri5`; one step size for the whole batch); its counts are kept in `last_stats`.
         `sampling_method="midpoint" | "heun3" | "rk4"`: torchdiffeq's fixed-grid solvers with `num_steps` steps S on
         linspace(0, 1, S + 1) (`LatentMDGenModel.sample_rk`, one hipGraph; default 24 / 16 / 12 steps = 48 network evaluations);
-        a sample's solution does not depend on its batch mates."""
+        a sample's solution does not depend on its batch mates.
+        `sampling_method="sde" | "sde_heun"`: the reference's `Sampler.sample_sde` with Euler-Maruyama / Heun steps
+        (`LatentMDGenModel.sample_sde`, one hipGraph): `num_steps` stochastic steps S (default 49) on S + 1 grid points, then the
+        last step; `sde`: a dict over SDE_DEFAULTS (diffusion_form "sigma", diffusion_norm 1, last_step "Mean", last_step_size
+        0.04, sample_eps 0); `noise`: optional (S, B, T, L, D) standard normals, default a device randn drawn after `zs`."""
+        opts = self._sde_opts(sampling_method, num_steps, sde) if sampling_method in SDE_METHODS else None
+        if opts is None and (sde is not None or noise is not None):
+            raise L.MdgenError("sde / noise are options of sampling_method='sde' | 'sde_heun'")
         prep = self.prep_batch(batch)
         rigids = prep["rigids"]
         B, T, L_ = rigids.shape
@@ -180,7 +208,7 @@ class NewMDGenWrapper:
         if zs is None:
             zs = torch.randn(B, T, L_, self.latent_dim, device=dev)
         if sampling_method not in _METHODS:
-            raise L.MdgenError(f"sampling_method must be None, 'euler', 'dopri5', 'midpoint', 'heun3' or 'rk4', got {sampling_method!r}")
+            raise L.MdgenError(f"{_METHODS_MSG}, got {sampling_method!r}")
         if sampling_method == "dopri5" and num_steps is not None:
             raise L.MdgenError("num_steps sets the fixed Euler grid; dopri5 chooses its own steps (pass one or the other)")
         if num_steps is not None and int(num_steps) < 1:
@@ -201,6 +229,8 @@ class NewMDGenWrapper:
             kw["rel_quats"] = rel_quats
         if sampling_method == "dopri5":
             samples, self.last_stats = self.model.sample_dopri5(zs, atol=atol, rtol=rtol, **kw)
+        elif opts is not None:
+            samples = self.model.sample_sde(zs, opts, noise=noise, use_graph=use_graph, **kw)
         elif sampling_method in RK_METHODS:
             S = RK_DEFAULT_STEPS[sampling_method] if num_steps is None else int(num_steps)
             sample_fn = self.transport_sampler.sample_ode(sampling_method=sampling_method, num_steps=S + 1)
@@ -217,15 +247,15 @@ class NewMDGenWrapper:
         return atom14, aa_out
 
     def upsample(self, batch, num_frames=None, zs=None, num_steps=None, use_graph=True, sampling_method=None, atol=1e-6,
-                 rtol=1e-3):
+                 rtol=1e-3, sde=None):
         """Trajectory upsampling: sample the frames between key frames stored every `args.cond_interval` frames
         (upsampling_inference.py:47-82 around `inference`, wrapper.py:405-484).  `batch` holds KEY FRAMES only, one window per
         batch element: torsions (B,K,L,7,2), trans (B,K,L,3), rots (B,K,L,3,3), seqres (B,L), mask (B,L), with
         K = ceil(T / cond_interval) and T = `num_frames` (default `args.num_frames`); key frame k is frame k * cond_interval of
         its window.  Euler: one library call (`mdgen_upsample_euler`, one hipGraph); "midpoint" | "heun3" | "rk4": likewise
         (`mdgen_upsample_rk`; `num_steps` steps, default 24 / 16 / 12).  `sampling_method="dopri5"`:
-        `mdgen_prep_keyframes` -> `sample_dopri5` -> `samples_to_atom14`, counts in `last_stats`.  The solver rules are
-        `inference()`'s.  Returns (atom14 (B,T,L,14,3), aa_out (B,T,L)); the latent samples are kept in `last_samples`."""
+        `mdgen_prep_keyframes` -> `sample_dopri5` -> `samples_to_atom14`, counts in `last_stats`; "sde" | "sde_heun" (with `sde`,
+        as `inference()`): the same three calls around `sample_sde`.  The solver rules are `inference()`'s.  Returns (atom14 (B,T,L,14,3), aa_out (B,T,L)); the latent samples are kept in `last_samples`."""
         from .geometry import residue_tables
         c = getattr(self.args, "cond_interval", None)
         if not c:
@@ -236,8 +266,11 @@ class NewMDGenWrapper:
         T = int(self.args.num_frames if num_frames is None else num_frames)
         if c < 1 or T < 1:
             raise L.MdgenError(f"num_frames and cond_interval must be >= 1, got {T}, {c}")
+        opts = self._sde_opts(sampling_method, num_steps, sde) if sampling_method in SDE_METHODS else None
+        if opts is None and sde is not None:
+            raise L.MdgenError("sde is an option of sampling_method='sde' | 'sde_heun'")
         if sampling_method not in _METHODS:
-            raise L.MdgenError(f"sampling_method must be None, 'euler', 'dopri5', 'midpoint', 'heun3' or 'rk4', got {sampling_method!r}")
+            raise L.MdgenError(f"{_METHODS_MSG}, got {sampling_method!r}")
         if sampling_method == "dopri5" and num_steps is not None:
             raise L.MdgenError("num_steps sets the fixed Euler grid; dopri5 chooses its own steps (pass one or the other)")
         if num_steps is not None and int(num_steps) < 1:
@@ -261,11 +294,14 @@ class NewMDGenWrapper:
         if zs is None:
             zs = torch.randn(B, T, L_, self.latent_dim, device=dev)
         mask = batch["mask"].to(torch.float32).unsqueeze(1).expand(-1, T, -1)
-        if sampling_method == "dopri5":
+        if sampling_method == "dopri5" or opts is not None:
             prep = prep_keyframes(rots, trans, tors, T, c)
-            samples, self.last_stats = self.model.sample_dopri5(
-                zs, mask=mask.contiguous(), start_frames=(prep["start_rot"], prep["start_trans"]), x_cond=prep["x_cond"],
-                x_cond_mask=prep["x_cond_mask"], aatype=batch["seqres"], atol=atol, rtol=rtol)
+            kw = dict(mask=mask.contiguous(), start_frames=(prep["start_rot"], prep["start_trans"]), x_cond=prep["x_cond"],
+                      x_cond_mask=prep["x_cond_mask"], aatype=batch["seqres"])
+            if opts is not None:
+                samples = self.model.sample_sde(zs, opts, use_graph=use_graph, **kw)
+            else:
+                samples, self.last_stats = self.model.sample_dopri5(zs, atol=atol, rtol=rtol, **kw)
             atom14 = samples_to_atom14(samples, prep["start_rot"], prep["start_trans"], batch["seqres"], False)
         elif sampling_method in RK_METHODS:
             S = RK_DEFAULT_STEPS[sampling_method] if num_steps is None else int(num_steps)
@@ -278,10 +314,11 @@ class NewMDGenWrapper:
         self.last_samples = samples
         return atom14, batch["seqres"][:, None].expand(B, T, L_)
 
-    def _rollout_dopri5(self, batch, T, zs, atol, rtol):
-        """The blocks of `rollout()` with the adaptive solver: a host loop (dopri5 reads its error ratio back once per attempted
-        step, so it cannot be captured) of `inference()` -- prep_latents -> sample_dopri5 -> samples_to_atom14 -- and
-        `atom14_to_cond`, all on the device.  -> (atom14, samples (R,B,T,L,D), next conditioning frame, per-block stats)."""
+    def _rollout_host_loop(self, batch, T, zs, **solver):
+        """The blocks of `rollout()` as a host loop of `inference(**solver)` -- prep_latents -> the solver -> samples_to_atom14 --
+        and `atom14_to_cond`, all on the device: the adaptive solver (dopri5 reads its error ratio back once per attempted step,
+        so it cannot be captured) and the SDE samplers (no fused driver).  -> (atom14, samples (R,B,T,L,D), next conditioning
+        frame, per-block stats)."""
         from .geometry import atom14_to_cond
         out, samples, stats = [], [], []
         for z in zs:
@@ -289,24 +326,25 @@ class NewMDGenWrapper:
             ex["torsions"] = batch["torsions"].expand(-1, T, -1, -1, -1)
             ex["trans"] = batch["trans"].expand(-1, T, -1, -1)
             ex["rots"] = batch["rots"].expand(-1, T, -1, -1, -1)
-            atom14, _ = self.inference(ex, zs=z, sampling_method="dopri5", atol=atol, rtol=rtol)
+            atom14, _ = self.inference(ex, zs=z, **solver)
             nxt = atom14_to_cond(atom14[:, -1], batch["seqres"])
             batch = dict(batch)
             batch["trans"], batch["rots"], batch["torsions"] = nxt["trans"][:, None], nxt["rots"][:, None], nxt["torsions"][:, None]
             out.append(atom14)
             samples.append(self.last_samples)
-            stats.append(self.last_stats)
+            stats.append(getattr(self, "last_stats", None))
         return torch.cat(out, 1), torch.stack(samples), nxt, stats
 
     def rollout(self, batch, num_frames: int, num_rollouts: int, num_steps=None, zs=None, use_graph=True,
-                return_next: bool = False, sampling_method=None, atol=1e-6, rtol=1e-3):
+                return_next: bool = False, sampling_method=None, atol=1e-6, rtol=1e-3, sde=None):
         """`num_rollouts` chained blocks of `num_frames` frames from the B = 1-frame conditioning batch of
         `sim_inference.get_batch` (torsions (B,1,L,7,2), trans (B,1,L,3), rots (B,1,L,3,3), seqres, mask (B,L)):
         the loop of sim_inference.py:100-113 (`rollout` :61-98 per block) as ONE library call, captured as one hipGraph:
         `mdgen_rollout_euler` (`sampling_method` None or "euler"; None refuses a non-Euler checkpoint unless `num_steps` is
         given) or `mdgen_rollout_rk` ("midpoint" | "heun3" | "rk4", `num_steps` steps per block, default 24 / 16 / 12).
         "dopri5" (with `atol` / `rtol`, no `num_steps`) is a host loop over the blocks with the same device glue -- the solver
-        reads back once per attempted step -- and leaves a list of per-block counts in `last_stats`.  `zs`: optional noise
+        reads back once per attempted step -- and leaves a list of per-block counts in `last_stats`; "sde" | "sde_heun" (with `sde`,
+        as `inference()`) run as the same host loop, one `sample_sde` graph per block.  `zs`: optional noise
         (num_rollouts, B, T, L, D); without it a block's noise is a fresh device randn (wrapper.py:439), drawn block by block
         when a method is named.  Returns atom14 (B, num_rollouts*T, L, 14, 3) [, the batch that would condition the next
         block]; the latent samples (num_rollouts, B, T, L, D) are kept in `last_samples`."""
@@ -314,7 +352,7 @@ class NewMDGenWrapper:
         if self.args.tps_condition or getattr(self.args, "cond_interval", None):
             raise L.MdgenError("rollout() is the forward-simulation driver (sim_condition models without cond_interval)")
         if sampling_method not in _METHODS:
-            raise L.MdgenError(f"sampling_method must be None, 'euler', 'dopri5', 'midpoint', 'heun3' or 'rk4', got {sampling_method!r}")
+            raise L.MdgenError(f"{_METHODS_MSG}, got {sampling_method!r}")
         if sampling_method == "dopri5" and num_steps is not None:
             raise L.MdgenError("num_steps sets the fixed Euler grid; dopri5 chooses its own steps (pass one or the other)")
         if num_steps is not None and int(num_steps) < 1:
@@ -335,7 +373,10 @@ class NewMDGenWrapper:
             zs = torch.stack([torch.randn(B, T, L_, self.latent_dim, device=dev) for _ in range(R)])
         mask = batch["mask"].to(torch.float32).unsqueeze(1).expand(-1, T, -1)
         if sampling_method == "dopri5":
-            atom14, samples, nxt, self.last_stats = self._rollout_dopri5(batch, T, zs, atol, rtol)
+            atom14, samples, nxt, self.last_stats = self._rollout_host_loop(batch, T, zs, sampling_method="dopri5", atol=atol, rtol=rtol)
+        elif sampling_method in SDE_METHODS:
+            atom14, samples, nxt, _ = self._rollout_host_loop(batch, T, zs, sampling_method=sampling_method, num_steps=num_steps,
+                                                              use_graph=use_graph, sde=sde)
         elif sampling_method in RK_METHODS:
             S = RK_DEFAULT_STEPS[sampling_method] if num_steps is None else int(num_steps)
             atom14, samples, nxt = self.model.rollout_rk(zs, sampling_method, S, mask, rots, trans, tors, batch["seqres"],
