@@ -1690,16 +1690,21 @@ static int prepare(Run& r, const float* t_dev, const float* t_host, long view_ro
     return 0;
 }
 
-// the token embedding of x into r.h() (latent_model.py:233-246), ipa_out: the IPA table's rows [B*L][384] of the step
-static EmbedParams embed_op(const Run& r, const float* x, const float* ipa_out) {
-    const mdgen_ctx* c = r.c;
+// the token embedding of x (B, T, L, D) into h (latent_model.py:233-246) with the context's weights and its abs_pos_emb; ipa_out: the
+// IPA table's rows [B*L][384] of the step
+static EmbedParams embed_params(const mdgen_ctx* c, const mdgen_shape& sh, const float* x, const float* x_cond, const int64_t* x_cond_mask,
+                                const float* ipa_out, float* h) {
     EmbedParams e{};
-    e.x = x; e.x_cond = r.x_cond; e.x_cond_mask = r.x_cond_mask;
+    e.x = x; e.x_cond = x_cond; e.x_cond_mask = x_cond_mask;
     e.wl = c->wl; e.bl = c->bl; e.wc = c->wc; e.bc = c->bc; e.mask_emb = c->mask_emb;
     e.wl_pack = c->wl_pack; e.wc_pack = c->wc_pack;
     e.pos_embed = c->d.abs_pos_emb ? c->pos_embed : nullptr;
-    e.ipa_out = ipa_out; e.h = r.h(); e.N = r.N; e.T = r.T; e.L = r.L; e.D = r.D;
+    e.ipa_out = ipa_out; e.h = h; e.N = (long)sh.B * sh.T * sh.L; e.T = sh.T; e.L = sh.L; e.D = c->D;
     return e;
+}
+// ... of a made run (a view: its own B), into r.h()
+static EmbedParams embed_op(const Run& r, const float* x, const float* ipa_out) {
+    return embed_params(r.c, mdgen_shape{r.B, r.T, r.L}, x, r.x_cond, r.x_cond_mask, ipa_out, r.h());
 }
 
 // One network evaluation at prepared step `step`: x -> velocity (out) or Euler update of x in place.
@@ -1823,6 +1828,7 @@ static int make_run(Run* r, mdgen_ctx* c, const mdgen_shape* sh, int S, int t_sh
     r->embase_step_stride = (long)sh->B * sh->L * kC;
     r->no_embed_tail = false;
     r->rk = nullptr;
+    r->sde = nullptr;
     r->concurrent = false;
     if (fold_on(c, r->N, t_shared, S)) {
         r->fold_streams = r->ws + r->lay.fold;
@@ -2021,95 +2027,9 @@ extern "C" int32_t mdgen_sample_euler(mdgen_ctx* c, const mdgen_shape* sh, int32
     return run_or_replay(r, use_graph, key, [&]() { return euler_body(r, tg, x); });
 }
 
-// Multi-block rollout (sim_inference.py:61-98, 110-113) as ONE call / ONE hipGraph: per block
-//   conditioning frame (B, L) expanded over T -> prep_batch latents (wrapper.py:298-342)
-//   -> S Euler steps from the block's noise (wrapper.py:439-447) -> atom14 (wrapper.py:456-478)
-//   -> last frame -> next block's conditioning frame (sim_inference.py:91-96),
-// nothing returning to the host in between.
-extern "C" int32_t mdgen_rollout_euler(mdgen_ctx* c, const mdgen_shape* sh, int32_t S, int32_t n_blocks, float* zs,
-                                       const float* mask, float* cond_rots, float* cond_trans, float* cond_torsions,
-                                       const int64_t* seqres, float* x_cond, int64_t* x_cond_mask,
-                                       const mdgen_residue_tables* tb, float* atom14, void* ws, size_t ws_bytes,
-                                       int32_t use_graph, void* stream) {
-    if (!zs || !cond_torsions || !tb || !atom14) return fail(-1, "null tensor argument");
-    const mdgen_cond cd = {mask, cond_rots, cond_trans, nullptr, nullptr, nullptr, x_cond, x_cond_mask, seqres};
-    if (int e = check_cond(&cd)) return e;
-    if (!tb->default_frames || !tb->lit_positions || !tb->atom14_group || !tb->atom14_mask || !tb->atom37_to_atom14 ||
-        !tb->atom37_mask || !tb->chi_atom_indices || !tb->chi_angles_mask)
-        return fail(-1, "null residue table");
-    if (n_blocks < 1) return fail(-2, "n_blocks must be >= 1");
-    if (c && c->d.tps_condition) return fail(-2, "the block rollout is defined for forward-simulation models (sim_condition)");
-    Run r{};
-    if (int e = make_run(&r, c, sh, S, 1, f32_path(c), ws, ws_bytes, stream)) return e;
-    if ((long)n_blocks * sh->T > 2000000000L / ((long)sh->L * 42)) return fail(-2, "trajectory too long for one call");
-    bind_cond(r, cd);
-    std::vector<float> tg;
-    linspace01(S + 1, &tg);
-    const mdgen_residue_tables t = *tb;
-    const long blk = (long)sh->B * sh->T * sh->L * r.D;
-    float* tmask_scratch = (float*)(r.ws + r.lay.rel7);   // (B, L, 7) fp32: fits the (unused, non-TPS) 2 x (B, L, 7) slot
-    auto body = [&]() -> int {
-        for (int b = 0; b < n_blocks; ++b) {
-            float* x = zs + (long)b * blk;
-            launch_prep_latents(r.B, r.T, r.L, 0, 1, 0, cond_rots, cond_trans, cond_torsions, nullptr, x_cond, x_cond_mask, r.s);
-            LAUNCHCHK();
-            if (int e = euler_body(r, tg, x)) return e;
-            launch_samples_to_atom14(r.B, r.T, r.L, r.D, 0, x, cond_rots, cond_trans, seqres, t.default_frames,
-                                     t.lit_positions, t.atom14_group, t.atom14_mask, atom14, n_blocks * r.T, b * r.T, r.s);
-            LAUNCHCHK();
-            // last frame of this block (frame b*T + T-1 of every trajectory) -> conditioning frame of the next
-            const float* last = atom14 + ((long)(b + 1) * r.T - 1) * r.L * 42;
-            launch_atom14_to_cond(r.B, r.L, last, (long)n_blocks * r.T * r.L * 42, seqres, t.atom37_to_atom14, t.atom37_mask,
-                                  t.chi_atom_indices, t.chi_angles_mask, cond_rots, cond_trans, cond_torsions,
-                                  tmask_scratch, r.s);
-            LAUNCHCHK();
-        }
-        return 0;
-    };
-    GraphKey key = graph_key(1, r, cd);
-    key.add(S).add(n_blocks).ptr(zs).ptr(cond_torsions).ptr(atom14).add_struct(t).add(n_streams(r));
-    return run_or_replay(r, use_graph, key, body);
-}
-
-// Trajectory upsampling (upsampling_inference.py:47-82 around wrapper.py:283-365, 405-484) as ONE call / ONE hipGraph:
-//   key frames (B, K, L) -> x_cond, x_cond_mask, start frames (k_prep_keyframes; no (B, T, L) window of zeros on the way)
-//   -> S Euler steps exactly as mdgen_sample_euler runs them -> atom14 relative to key frame 0.
-// The preparation kernel is enqueued on the call's stream ahead of euler_body, whose fork event is recorded after it: every
-// sub-batch stream sees the conditioning of THIS call, also when the graph is replayed on new key frames in the same buffers.
-extern "C" int32_t mdgen_upsample_euler(mdgen_ctx* c, const mdgen_shape* sh, int32_t S, int32_t cond_interval, float* zs,
-                                        const float* mask, const float* key_rots, const float* key_trans,
-                                        const float* key_torsions, const int64_t* seqres, float* x_cond, int64_t* x_cond_mask,
-                                        float* start_rot, float* start_trans, const mdgen_residue_tables* tb, float* atom14,
-                                        void* ws, size_t ws_bytes, int32_t use_graph, void* stream) {
-    if (!zs || !key_rots || !key_trans || !key_torsions || !tb || !atom14) return fail(-1, "null tensor argument");
-    const mdgen_cond cd = {mask, start_rot, start_trans, nullptr, nullptr, nullptr, x_cond, x_cond_mask, seqres};
-    if (int e = check_cond(&cd)) return e;
-    if (!tb->default_frames || !tb->lit_positions || !tb->atom14_group || !tb->atom14_mask) return fail(-1, "null residue table");
-    if (cond_interval < 1) return fail(-2, "cond_interval must be >= 1");
-    if (c && c->d.tps_condition) return fail(-2, "upsampling is defined for forward-simulation models (sim_condition)");
-    Run r{};
-    if (int e = make_run(&r, c, sh, S, 1, f32_path(c), ws, ws_bytes, stream)) return e;
-    bind_cond(r, cd);
-    std::vector<float> tg;
-    linspace01(S + 1, &tg);
-    const mdgen_residue_tables t = *tb;
-    auto body = [&]() -> int {
-        launch_prep_keyframes(r.B, r.T, r.L, cond_interval, key_rots, key_trans, key_torsions, x_cond, x_cond_mask, start_rot,
-                              start_trans, r.s);
-        LAUNCHCHK();
-        if (int e = euler_body(r, tg, zs)) return e;
-        launch_samples_to_atom14(r.B, r.T, r.L, r.D, 0, zs, start_rot, start_trans, seqres, t.default_frames, t.lit_positions,
-                                 t.atom14_group, t.atom14_mask, atom14, r.T, 0, r.s);
-        LAUNCHCHK();
-        return 0;
-    };
-    GraphKey key = graph_key(2, r, cd);
-    key.add(S).add(cond_interval).ptr(zs).ptr(key_rots).ptr(key_trans).ptr(key_torsions).ptr(atom14).add_struct(t).add(n_streams(r));
-    return run_or_replay(r, use_graph, key, body);
-}
-
 #include "ode.inc"
 #include "sde.inc"
+#include "drivers.inc"
 
 // ---------------------------------------------------------------------------------------------
 // dispatch plan (host only)
@@ -2176,14 +2096,26 @@ static int dry_ctx(mdgen_ctx* c, int tps_condition, int num_layers, int ncu, int
     }
     return 0;
 }
-struct DryScope {
-    DryScope(DryPlan* p) { g_dry = p; }
-    ~DryScope() { g_dry = nullptr; }
-};
 static mdgen_cond fake_cond() {   // never dereferenced: plan mode launches nothing
     const float* fake = (const float*)4096;
     return {fake, fake, fake, fake, fake, nullptr, fake, (const int64_t*)fake, (const int64_t*)fake};
 }
+// A plan-mode call of S prepared time rows: its context, the launches it records while it lives, and its made run with a workspace
+// and a conditioning that are never followed.
+struct DryCall {
+    mdgen_ctx ctx;
+    DryPlan plan;
+    Run r{};
+    ~DryCall() { g_dry = nullptr; }
+    int open(const mdgen_shape* sh, int S, int t_shared, int tps_condition, int num_layers, int ncu, int xcd_round_robin, bool prof_on,
+             const char* options) {
+        if (int e = dry_ctx(&ctx, tps_condition, num_layers, ncu, xcd_round_robin, prof_on, options)) return e;
+        g_dry = &plan;
+        if (int e = make_run(&r, &ctx, sh, S, t_shared, f32_path(&ctx), (void*)4096, (size_t)1 << 60, nullptr)) return e;
+        bind_cond(r, fake_cond());
+        return 0;
+    }
+};
 
 extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_steps, int32_t mode, int32_t tps_condition,
                                              int32_t num_layers, int32_t ncu, int32_t xcd_round_robin, const char* options,
@@ -2192,19 +2124,14 @@ extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_st
     if (mode < 0 || mode > 7)
         return fail(-2, "mode: 0 sample_euler, 1 forward, 2 sample_euler under the profiler, 3 forward with trace_h, 4 one dopri5 step, "
                         "5 / 6 / 7 one midpoint / heun3 / rk4 step");
-    mdgen_ctx ctx;
-    mdgen_ctx* c = &ctx;
-    if (int e = dry_ctx(c, tps_condition, num_layers, ncu, xcd_round_robin, mode == 2, options)) return e;
-    DryPlan plan;
-    DryScope dry(&plan);
     const bool fwd = mode == 1 || mode == 3;
     const bool rkm = mode >= 5;   // one step of mdgen_sample_rk, method mode - 4: its time rows
     const int S = mode == 4 ? ode::kStages : rkm ? rk_method(mode - 4)->stages : fwd ? 1 : n_steps;
     const int t_shared = fwd ? (sh->B == 1 ? 1 : 0) : 1;
-    Run r{};
-    if (int e = make_run(&r, c, sh, S, t_shared, f32_path(c), (void*)4096, (size_t)1 << 60, nullptr)) return e;
+    DryCall dry;
+    if (int e = dry.open(sh, S, t_shared, tps_condition, num_layers, ncu, xcd_round_robin, mode == 2, options)) return e;
+    Run& r = dry.r;
     float* fake = (float*)4096;   // never dereferenced: plan mode launches nothing
-    bind_cond(r, fake_cond());
     const int ns = fwd || mode >= 4 ? 1 : n_streams(r);
     const int nv = plan_views(r.B, r.T, r.L, ns);
     if (mode == 4) {
@@ -2218,7 +2145,7 @@ extern "C" int32_t mdgen_debug_dispatch_plan(const mdgen_shape* sh, int32_t n_st
         linspace01(S + 1, &tg);
         if (int e = euler_body(r, tg, fake)) return e;
     }
-    return plan_json(plan, r.B, nv, ns, mode >= 4, buf, buflen);
+    return plan_json(dry.plan, r.B, nv, ns, mode >= 4, buf, buflen);
 }
 
 // mdgen_debug_dispatch_plan for ONE step of mdgen_sample_sde with `opts` (n_points is taken as 2): the same JSON, "integrator":
@@ -2231,21 +2158,16 @@ extern "C" int32_t mdgen_debug_sde_dispatch_plan(const mdgen_shape* sh, const md
     o.n_points = 2;
     SdePlan pl;
     if (int e = sde_plan(o, &pl)) return e;
-    mdgen_ctx ctx;
-    mdgen_ctx* c = &ctx;
-    if (int e = dry_ctx(c, tps_condition, num_layers, ncu, xcd_round_robin, false, options)) return e;
-    DryPlan plan;
-    DryScope dry(&plan);
-    Run r{};
-    if (int e = make_run(&r, c, sh, (int)pl.rows.size(), 1, f32_path(c), (void*)4096, (size_t)1 << 60, nullptr)) return e;
-    bind_cond(r, fake_cond());
+    DryCall dry;
+    if (int e = dry.open(sh, (int)pl.rows.size(), 1, tps_condition, num_layers, ncu, xcd_round_robin, false, options)) return e;
+    Run& r = dry.r;
     r.no_embed_tail = true;
     const int nv = plan_views(r.B, r.T, r.L, 1);
     if (nv == 0) return fail(-2, "sample too large for one launch");
     float* fake = (float*)4096;
     float* v[2] = {fake, fake};
     if (int e = sde_body(r, o, pl, nv, fake, v, fake, 0)) return e;
-    return plan_json(plan, r.B, nv, 1, true, buf, buflen);
+    return plan_json(dry.plan, r.B, nv, 1, true, buf, buflen);
 }
 
 // ---------------------------------------------------------------------------------------------

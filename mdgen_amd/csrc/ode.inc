@@ -503,7 +503,7 @@ static int rk_body(const Run& r_in, const rk::Method& m, int S, const RkPlan& pl
     return launch(r, "ode_rk_update", [&] { launch_rk_update(last, (long)r.N * r.D, r.s); });
 }
 
-// What mdgen_sample_rk, mdgen_rollout_rk and mdgen_upsample_rk share once their own arguments are judged: the plan, the made run
+// What mdgen_sample_rk, mdgen_rollout_rk and mdgen_upsample_rk (drivers.inc) share once their own arguments are judged: the plan, the made run
 // with the call's conditioning bound, its launch views and the four velocity buffers behind the network workspace.  `state` is
 // the buffer k_rk_update will see (16-byte accesses).  Every refusal comes before make_run, the first to touch the device.
 struct RkCall {
@@ -543,93 +543,6 @@ extern "C" int32_t mdgen_sample_rk(mdgen_ctx* c, const mdgen_shape* sh, int32_t 
     return run_or_replay(q.r, use_graph, key, [&]() { return q.solve(S, x); });
 }
 
-// The fused drivers of api.hip with a fixed-grid Runge-Kutta solve in the Euler loop's place: the same glue kernels around rk_body,
-// which prepares its own time rows on the stream -- per block, because the IPA stack reads the block's conditioning frame.
-//
-// mdgen_rollout_rk: block b's state is zs + b * stride floats.  k_rk_update reads and writes the state 16 bytes at a time, and a
-// block of B T L D floats (D = 21) ends on 16 bytes only for some shapes (T = 250, L = 251: B T L D % 4 == 2), so the caller
-// chooses the stride: a multiple of 4 floats, at least one block.
-extern "C" int32_t mdgen_rollout_rk(mdgen_ctx* c, const mdgen_shape* sh, int32_t method, int32_t S, int32_t n_blocks, float* zs,
-                                    int64_t stride, const float* mask, float* cond_rots, float* cond_trans, float* cond_torsions,
-                                    const int64_t* seqres, float* x_cond, int64_t* x_cond_mask, const mdgen_residue_tables* tb,
-                                    float* atom14, void* ws, size_t ws_bytes, int32_t use_graph, void* stream) {
-    if (!sh || !zs || !cond_torsions || !tb || !atom14 || !ws) return fail(-1, "null argument");
-    const mdgen_cond cd = {mask, cond_rots, cond_trans, nullptr, nullptr, nullptr, x_cond, x_cond_mask, seqres};
-    if (int e = check_cond(&cd)) return e;
-    if (!tb->default_frames || !tb->lit_positions || !tb->atom14_group || !tb->atom14_mask || !tb->atom37_to_atom14 ||
-        !tb->atom37_mask || !tb->chi_atom_indices || !tb->chi_angles_mask)
-        return fail(-1, "null residue table");
-    if (int e = rk_check(method, S)) return e;
-    if (n_blocks < 1) return fail(-2, "n_blocks must be >= 1");
-    if (c && c->d.tps_condition) return fail(-2, "the block rollout is defined for forward-simulation models (sim_condition)");
-    if (sh->B < 1 || sh->T < 1 || sh->L < 1) return fail(-2, "B, T, L must be >= 1");
-    if ((long)n_blocks * sh->T > 2000000000L / ((long)sh->L * 42)) return fail(-2, "trajectory too long for one call");
-    const long blk = (long)sh->B * sh->T * sh->L * (c ? c->D : 21);   // (forward-simulation latents: 21 floats a token)
-    if (((uintptr_t)zs & 15) != 0) return fail(-7, "zs must be 16-byte aligned");
-    if (stride % 4 != 0) return fail(-7, "zs_block_stride must be a multiple of 4 floats (got %lld)", (long long)stride);
-    if (stride < blk) return fail(-7, "zs_block_stride %lld is below one block of %ld floats", (long long)stride, blk);
-    RkCall q;
-    if (int e = rk_open(&q, c, sh, method, S, zs, cd, ws, ws_bytes, stream)) return e;
-    const Run& r = q.r;
-    const mdgen_residue_tables t = *tb;
-    float* tmask_scratch = (float*)(r.ws + r.lay.rel7);   // (B, L, 7) fp32: fits the (unused, non-TPS) 2 x (B, L, 7) slot
-    auto body = [&]() -> int {
-        for (int b = 0; b < n_blocks; ++b) {
-            float* x = zs + (long)b * stride;
-            launch_prep_latents(r.B, r.T, r.L, 0, 1, 0, cond_rots, cond_trans, cond_torsions, nullptr, x_cond, x_cond_mask, r.s);
-            LAUNCHCHK();
-            if (int e = q.solve(S, x)) return e;
-            launch_samples_to_atom14(r.B, r.T, r.L, r.D, 0, x, cond_rots, cond_trans, seqres, t.default_frames,
-                                     t.lit_positions, t.atom14_group, t.atom14_mask, atom14, n_blocks * r.T, b * r.T, r.s);
-            LAUNCHCHK();
-            // last frame of this block -> conditioning frame of the next (as mdgen_rollout_euler)
-            const float* last = atom14 + ((long)(b + 1) * r.T - 1) * r.L * 42;
-            launch_atom14_to_cond(r.B, r.L, last, (long)n_blocks * r.T * r.L * 42, seqres, t.atom37_to_atom14, t.atom37_mask,
-                                  t.chi_atom_indices, t.chi_angles_mask, cond_rots, cond_trans, cond_torsions,
-                                  tmask_scratch, r.s);
-            LAUNCHCHK();
-        }
-        return 0;
-    };
-    GraphKey key = graph_key(4, r, cd);
-    key.add(method).add(S).add(n_blocks).add((uint64_t)stride).ptr(zs).ptr(cond_torsions).ptr(atom14).add_struct(t);
-    return run_or_replay(r, use_graph, key, body);   // (the body does not fork: no n_streams)
-}
-
-// mdgen_upsample_rk: the preparation kernel is enqueued ahead of rk_body on the call's one stream, so a replay with new key frames
-// in the same buffers conditions on those.
-extern "C" int32_t mdgen_upsample_rk(mdgen_ctx* c, const mdgen_shape* sh, int32_t method, int32_t S, int32_t cond_interval, float* zs,
-                                     const float* mask, const float* key_rots, const float* key_trans, const float* key_torsions,
-                                     const int64_t* seqres, float* x_cond, int64_t* x_cond_mask, float* start_rot,
-                                     float* start_trans, const mdgen_residue_tables* tb, float* atom14, void* ws, size_t ws_bytes,
-                                     int32_t use_graph, void* stream) {
-    if (!sh || !zs || !key_rots || !key_trans || !key_torsions || !tb || !atom14 || !ws) return fail(-1, "null argument");
-    const mdgen_cond cd = {mask, start_rot, start_trans, nullptr, nullptr, nullptr, x_cond, x_cond_mask, seqres};
-    if (int e = check_cond(&cd)) return e;
-    if (!tb->default_frames || !tb->lit_positions || !tb->atom14_group || !tb->atom14_mask) return fail(-1, "null residue table");
-    if (int e = rk_check(method, S)) return e;
-    if (cond_interval < 1) return fail(-2, "cond_interval must be >= 1");
-    if (c && c->d.tps_condition) return fail(-2, "upsampling is defined for forward-simulation models (sim_condition)");
-    if (((uintptr_t)zs & 15) != 0) return fail(-7, "zs must be 16-byte aligned");
-    RkCall q;
-    if (int e = rk_open(&q, c, sh, method, S, zs, cd, ws, ws_bytes, stream)) return e;
-    const Run& r = q.r;
-    const mdgen_residue_tables t = *tb;
-    auto body = [&]() -> int {
-        launch_prep_keyframes(r.B, r.T, r.L, cond_interval, key_rots, key_trans, key_torsions, x_cond, x_cond_mask, start_rot,
-                              start_trans, r.s);
-        LAUNCHCHK();
-        if (int e = q.solve(S, zs)) return e;
-        launch_samples_to_atom14(r.B, r.T, r.L, r.D, 0, zs, start_rot, start_trans, seqres, t.default_frames, t.lit_positions,
-                                 t.atom14_group, t.atom14_mask, atom14, r.T, 0, r.s);
-        LAUNCHCHK();
-        return 0;
-    };
-    GraphKey key = graph_key(5, r, cd);
-    key.add(method).add(S).add(cond_interval).ptr(zs).ptr(key_rots).ptr(key_trans).ptr(key_torsions).ptr(atom14).add_struct(t);
-    return run_or_replay(r, use_graph, key, body);   // (the body does not fork: no n_streams)
-}
-
 // Host-only test hook: the time rows mdgen_sample_rk prepares for (method, S), as fp32 bits, and the row of every (step, stage).
 // row_bits: room for cap_rows values; row_of: [S][stages].
 extern "C" int32_t mdgen_debug_rk_plan(int32_t method, int32_t S, uint32_t* row_bits, int32_t cap_rows, int32_t* n_rows,
@@ -666,13 +579,7 @@ extern "C" int32_t mdgen_debug_rk_stage(mdgen_ctx* c, const mdgen_shape* sh, int
     for (int q = 0; q < kRkMaxK && n.ki[q] >= 0; ++q)
         if (!k[n.ki[q]]) return fail(-1, "the state reads k%d", n.ki[q]);
     const RkState st = rk_state_of(n, dt, y, k, 0, stage == m->stages);
-    EmbedParams e{};
-    e.x = y; e.x_cond = x_cond; e.x_cond_mask = x_cond_mask;
-    e.wl = c->wl; e.bl = c->bl; e.wc = c->wc; e.bc = c->bc; e.mask_emb = c->mask_emb;
-    e.wl_pack = c->wl_pack; e.wc_pack = c->wc_pack;
-    e.pos_embed = c->d.abs_pos_emb ? c->pos_embed : nullptr;
-    e.ipa_out = ipa_out; e.h = h; e.N = (long)sh->B * sh->T * sh->L; e.T = sh->T; e.L = sh->L; e.D = c->D;
-    launch_rk_embed(e, st, (hipStream_t)stream);
+    launch_rk_embed(embed_params(c, *sh, y, x_cond, x_cond_mask, ipa_out, h), st, (hipStream_t)stream);
     LAUNCHCHK();
     return 0;
 }

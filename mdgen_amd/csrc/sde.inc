@@ -314,13 +314,7 @@ extern "C" int32_t mdgen_debug_sde_stage(mdgen_ctx* c, const mdgen_shape* sh, co
     case 5: st = sde_state_of(pl, kSdeHeunNoise, true, r0, r1, pl.row_of[(size_t)(step + 1) * 2], pl.dt, x, v0, v1, xi); break;
     default: st = sde_last_of(*o, pl, x, vv); break;
     }
-    EmbedParams e{};
-    e.x = x; e.x_cond = x_cond; e.x_cond_mask = x_cond_mask;
-    e.wl = c->wl; e.bl = c->bl; e.wc = c->wc; e.bc = c->bc; e.mask_emb = c->mask_emb;
-    e.wl_pack = c->wl_pack; e.wc_pack = c->wc_pack;
-    e.pos_embed = c->d.abs_pos_emb ? c->pos_embed : nullptr;
-    e.ipa_out = ipa_out; e.h = h; e.N = (long)sh->B * sh->T * sh->L; e.T = sh->T; e.L = sh->L; e.D = c->D;
-    launch_sde_embed(e, st, (hipStream_t)stream);
+    launch_sde_embed(embed_params(c, *sh, x, x_cond, x_cond_mask, ipa_out, h), st, (hipStream_t)stream);
     LAUNCHCHK();
     return 0;
 }

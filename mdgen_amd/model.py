@@ -353,7 +353,7 @@ class LatentMDGenModel:
         network evaluations per step.  Every sample sees the same grid, so a sample's solution does not depend on its batch mates;
         nothing synchronises, and with `use_graph` the whole solve is one hipGraph.  Returns x at t = 1."""
         B, T, L_, *frames = self._sampler_inputs(zs, mask, start_frames, end_frames, x_cond, x_cond_mask, aatype)
-        code, S, ws = self._rk_call(method, num_steps, B, T, L_)
+        (code, S), ws = self._rk_call(method, num_steps, B, T, L_)
         sh = L.Shape(B, T, L_)
         x, cond = self._stage_cond(zs, mask, *frames, x_cond, x_cond_mask, aatype, rel_quats)
         with self._call_stream(use_graph) as stream:
@@ -402,32 +402,42 @@ class LatentMDGenModel:
         of sim_inference.py:100-113.  zs (R,B,T,L,D) noise; mask (B,T,L); cond_* the first conditioning frame
         (B,L,...); seqres (B,L) int64; tables: dict of residue tables on the device (geometry.residue_tables).
         Returns (atom14 (B, R*T, L, 14, 3), samples (R,B,T,L,D), next conditioning frame dict)."""
+        S = int(num_steps)
+        return self._rollout("rollout", lib.mdgen_rollout_euler, lambda *shape: ((S,), self._workspace(*shape, S, True)), False,
+                             zs, mask, cond_rots, cond_trans, cond_torsions, seqres, tables, use_graph)
+
+    def _rollout(self, key, fn, call, pad, zs, mask, cond_rots, cond_trans, cond_torsions, seqres, tables, use_graph):
+        """The body of rollout_euler / rollout_rk on the staging set `key`: the library function `fn`, and `call(B, T, L)` ->
+        (fn's scalar arguments ahead of the block count, the workspace).  `pad`: the staged noise keeps every block on 16 bytes
+        -- a block stride rounded up to 4 floats, handed to `fn` after zs -- where B*T*L*D is no multiple of 4; else the blocks
+        lie contiguous and `fn` takes no stride."""
         if self._pre_run is not None:
             self._pre_run()
         if zs.dim() != 5 or zs.shape[-1] != self.cfg.latent_dim:
             raise L.MdgenError(f"zs must be (R,B,T,L,{self.cfg.latent_dim}), got {tuple(zs.shape)}")
         R, B, T, L_, D = zs.shape
         require_cuda(zs, mask, cond_rots, cond_trans, cond_torsions, seqres)
-        S = int(num_steps)
-        ws = self._workspace(B, T, L_, S, True)
+        scalars, ws = call(B, T, L_)
+        blk = B * T * L_ * D
+        stride = (blk + 3) // 4 * 4 if pad else blk
         f32, i64 = torch.float32, torch.int64
-        spec = dict(zs=((R, B, T, L_, D), f32), mask=((B, T, L_), f32), rots=((B, L_, 3, 3), f32), trans=((B, L_, 3), f32),
-                    tors=((B, L_, 7, 2), f32), seqres=((B, L_), i64), x_cond=((B, T, L_, D), f32), x_cond_mask=((B, T, L_), i64),
-                    atom14=((B, R * T, L_, 14, 3), f32))
-        stg = self._staged(("rollout", R, B, T, L_), spec,
-                           dict(zs=zs, mask=mask, rots=cond_rots, trans=cond_trans, tors=cond_torsions, seqres=seqres))
+        spec = dict(zs=((R, stride) if pad else (R, B, T, L_, D), f32), mask=((B, T, L_), f32), rots=((B, L_, 3, 3), f32),
+                    trans=((B, L_, 3), f32), tors=((B, L_, 7, 2), f32), seqres=((B, L_), i64), x_cond=((B, T, L_, D), f32),
+                    x_cond_mask=((B, T, L_), i64), atom14=((B, R * T, L_, 14, 3), f32))
+        stg = self._staged((key, R, B, T, L_), spec, dict(mask=mask, rots=cond_rots, trans=cond_trans, tors=cond_torsions, seqres=seqres))
+        staged_zs = stg["zs"].view(R, stride)[:, :blk]
+        staged_zs.copy_(zs.reshape(R, blk))
         tb = L.ResidueTables.from_dict(tables)
         sh = L.Shape(B, T, L_)
         with self._call_stream(use_graph) as stream:
-            check(lib.mdgen_rollout_euler(
-                self._ctx, C.byref(sh), S, R, ptr(stg["zs"]), ptr(stg["mask"]), ptr(stg["rots"]), ptr(stg["trans"]),
-                ptr(stg["tors"]), ptr(stg["seqres"]), ptr(stg["x_cond"]), ptr(stg["x_cond_mask"]), C.byref(tb),
-                ptr(stg["atom14"]), ptr(ws), ws.numel(), int(use_graph), stream))
+            check(fn(self._ctx, C.byref(sh), *scalars, R, ptr(stg["zs"]), *([stride] if pad else []), ptr(stg["mask"]),
+                     ptr(stg["rots"]), ptr(stg["trans"]), ptr(stg["tors"]), ptr(stg["seqres"]), ptr(stg["x_cond"]),
+                     ptr(stg["x_cond_mask"]), C.byref(tb), ptr(stg["atom14"]), ptr(ws), ws.numel(), int(use_graph), stream))
         nxt = {"rots": stg["rots"].clone(), "trans": stg["trans"].clone(), "torsions": stg["tors"].clone()}
-        return stg["atom14"].clone(), stg["zs"].clone(), nxt
+        return stg["atom14"].clone(), staged_zs.reshape(R, B, T, L_, D).clone(), nxt
 
     def _rk_call(self, method, num_steps, B, T, L_):
-        """(method code, S, workspace) of a fixed-grid Runge-Kutta call of this shape: one workspace for sample_rk and the drivers."""
+        """((method code, S), workspace) of a fixed-grid Runge-Kutta call of this shape: one workspace for sample_rk and the drivers."""
         code = L.RK_METHODS.get(method)
         if code is None:
             raise L.MdgenError(f"method must be one of {sorted(L.RK_METHODS)}, got {method!r}")
@@ -437,44 +447,21 @@ class LatentMDGenModel:
         sh = L.Shape(B, T, L_)
         nbytes = C.c_size_t()
         check(lib.mdgen_rk_workspace_bytes(self._ctx, C.byref(sh), code, S, C.byref(nbytes)))
-        return code, S, self._sized_workspace(("rk", B, T, L_), nbytes.value)
+        return (code, S), self._sized_workspace(("rk", B, T, L_), nbytes.value)
 
     def rollout_rk(self, zs, method: str, num_steps: int, mask, cond_rots, cond_trans, cond_torsions, seqres, tables,
                    use_graph: bool = True):
         """`mdgen_rollout_rk`: `rollout_euler` with `method` in ("midpoint", "heun3", "rk4") solving every block in `num_steps`
         steps (as `sample_rk`), still one call and one hipGraph.  Arguments and return values as `rollout_euler`.  The staged
-        noise keeps every block on 16 bytes (a block stride rounded up to 4 floats: B*T*L*D need not be a multiple of 4);
-        the padding never leaves this function."""
-        if self._pre_run is not None:
-            self._pre_run()
-        if zs.dim() != 5 or zs.shape[-1] != self.cfg.latent_dim:
-            raise L.MdgenError(f"zs must be (R,B,T,L,{self.cfg.latent_dim}), got {tuple(zs.shape)}")
-        R, B, T, L_, D = zs.shape
-        require_cuda(zs, mask, cond_rots, cond_trans, cond_torsions, seqres)
-        code, S, ws = self._rk_call(method, num_steps, B, T, L_)
-        blk = B * T * L_ * D
-        stride = (blk + 3) // 4 * 4
-        f32, i64 = torch.float32, torch.int64
-        spec = dict(zs=((R, stride), f32), mask=((B, T, L_), f32), rots=((B, L_, 3, 3), f32), trans=((B, L_, 3), f32),
-                    tors=((B, L_, 7, 2), f32), seqres=((B, L_), i64), x_cond=((B, T, L_, D), f32), x_cond_mask=((B, T, L_), i64),
-                    atom14=((B, R * T, L_, 14, 3), f32))
-        stg = self._staged(("rollout_rk", R, B, T, L_), spec,
-                           dict(mask=mask, rots=cond_rots, trans=cond_trans, tors=cond_torsions, seqres=seqres))
-        stg["zs"][:, :blk].copy_(zs.reshape(R, blk))
-        tb = L.ResidueTables.from_dict(tables)
-        sh = L.Shape(B, T, L_)
-        with self._call_stream(use_graph) as stream:
-            check(lib.mdgen_rollout_rk(
-                self._ctx, C.byref(sh), code, S, R, ptr(stg["zs"]), stride, ptr(stg["mask"]), ptr(stg["rots"]), ptr(stg["trans"]),
-                ptr(stg["tors"]), ptr(stg["seqres"]), ptr(stg["x_cond"]), ptr(stg["x_cond_mask"]), C.byref(tb),
-                ptr(stg["atom14"]), ptr(ws), ws.numel(), int(use_graph), stream))
-        nxt = {"rots": stg["rots"].clone(), "trans": stg["trans"].clone(), "torsions": stg["tors"].clone()}
-        return stg["atom14"].clone(), stg["zs"][:, :blk].reshape(R, B, T, L_, D).clone(), nxt
+        noise is padded (`_rollout`); the padding never leaves this class."""
+        return self._rollout("rollout_rk", lib.mdgen_rollout_rk, lambda *shape: self._rk_call(method, num_steps, *shape), True,
+                             zs, mask, cond_rots, cond_trans, cond_torsions, seqres, tables, use_graph)
 
     # ---- trajectory upsampling ---------------------------------------------------------------
-    def _stage_upsample(self, zs, cond_interval, mask, key_rots, key_trans, key_torsions, seqres):
-        """The checks of an upsampling call and its staging set (one per shape and interval, shared by the solvers)
-        -> (B, T, L, cond_interval, the staged buffers)."""
+    def _upsample(self, fn, call, zs, cond_interval, mask, key_rots, key_trans, key_torsions, seqres, tables, use_graph):
+        """The body of upsample_euler / upsample_rk: the checks of an upsampling call, its staging set (one per shape and
+        interval, shared by the solvers) and the library function `fn`; `call(B, T, L)` -> (fn's scalar arguments ahead of the
+        interval, the workspace)."""
         if self._pre_run is not None:
             self._pre_run()
         if self.cfg.tps_condition:
@@ -499,7 +486,14 @@ class LatentMDGenModel:
                     sr=((B, L_, 3, 3), f32), st=((B, L_, 3), f32), atom14=((B, T, L_, 14, 3), f32))
         stg = self._staged(("upsample", B, T, L_, c), spec,
                            dict(zs=zs, mask=mask, rots=key_rots, trans=key_trans, tors=key_torsions, seqres=seqres))
-        return B, T, L_, c, stg
+        scalars, ws = call(B, T, L_)
+        tb = L.ResidueTables.from_dict(tables)
+        sh = L.Shape(B, T, L_)
+        with self._call_stream(use_graph) as stream:
+            check(fn(self._ctx, C.byref(sh), *scalars, c, ptr(stg["zs"]), ptr(stg["mask"]), ptr(stg["rots"]), ptr(stg["trans"]),
+                     ptr(stg["tors"]), ptr(stg["seqres"]), ptr(stg["x_cond"]), ptr(stg["x_cond_mask"]), ptr(stg["sr"]),
+                     ptr(stg["st"]), C.byref(tb), ptr(stg["atom14"]), ptr(ws), ws.numel(), int(use_graph), stream))
+        return stg["atom14"].clone(), stg["zs"].clone()
 
     def upsample_euler(self, zs, num_steps: int, cond_interval: int, mask, key_rots, key_trans, key_torsions, seqres, tables,
                        use_graph: bool = True):
@@ -507,30 +501,14 @@ class LatentMDGenModel:
         noise, one window per batch element; mask (B,T,L); key_* the K = ceil(T / cond_interval) key frames of every window,
         (B,K,L,...); seqres (B,L) int64; tables: dict of residue tables on the device (geometry.residue_tables).
         Returns (atom14 (B,T,L,14,3), samples (B,T,L,D))."""
-        B, T, L_, c, stg = self._stage_upsample(zs, cond_interval, mask, key_rots, key_trans, key_torsions, seqres)
         S = int(num_steps)
-        ws = self._workspace(B, T, L_, S, True)
-        tb = L.ResidueTables.from_dict(tables)
-        sh = L.Shape(B, T, L_)
-        with self._call_stream(use_graph) as stream:
-            check(lib.mdgen_upsample_euler(
-                self._ctx, C.byref(sh), S, c, ptr(stg["zs"]), ptr(stg["mask"]), ptr(stg["rots"]), ptr(stg["trans"]),
-                ptr(stg["tors"]), ptr(stg["seqres"]), ptr(stg["x_cond"]), ptr(stg["x_cond_mask"]), ptr(stg["sr"]),
-                ptr(stg["st"]), C.byref(tb), ptr(stg["atom14"]), ptr(ws), ws.numel(), int(use_graph), stream))
-        return stg["atom14"].clone(), stg["zs"].clone()
+        return self._upsample(lib.mdgen_upsample_euler, lambda *shape: ((S,), self._workspace(*shape, S, True)),
+                              zs, cond_interval, mask, key_rots, key_trans, key_torsions, seqres, tables, use_graph)
 
     def upsample_rk(self, zs, method: str, num_steps: int, cond_interval: int, mask, key_rots, key_trans, key_torsions, seqres,
                     tables, use_graph: bool = True):
         """`mdgen_upsample_rk`: `upsample_euler` with `method` in ("midpoint", "heun3", "rk4") solving the windows in `num_steps`
         steps (as `sample_rk`): key-frame conditioning -> solve -> atom14 in one call (one hipGraph).  Arguments and return
         values as `upsample_euler`."""
-        B, T, L_, c, stg = self._stage_upsample(zs, cond_interval, mask, key_rots, key_trans, key_torsions, seqres)
-        code, S, ws = self._rk_call(method, num_steps, B, T, L_)
-        tb = L.ResidueTables.from_dict(tables)
-        sh = L.Shape(B, T, L_)
-        with self._call_stream(use_graph) as stream:
-            check(lib.mdgen_upsample_rk(
-                self._ctx, C.byref(sh), code, S, c, ptr(stg["zs"]), ptr(stg["mask"]), ptr(stg["rots"]), ptr(stg["trans"]),
-                ptr(stg["tors"]), ptr(stg["seqres"]), ptr(stg["x_cond"]), ptr(stg["x_cond_mask"]), ptr(stg["sr"]),
-                ptr(stg["st"]), C.byref(tb), ptr(stg["atom14"]), ptr(ws), ws.numel(), int(use_graph), stream))
-        return stg["atom14"].clone(), stg["zs"].clone()
+        return self._upsample(lib.mdgen_upsample_rk, lambda *shape: self._rk_call(method, num_steps, *shape),
+                              zs, cond_interval, mask, key_rots, key_trans, key_torsions, seqres, tables, use_graph)

@@ -37,6 +37,8 @@ from typing import Dict, List, Sequence
 import numpy as np
 import torch
 
+from .solver import add_solver_arguments, sde_kwargs, solver_kwargs  # noqa: F401 (sde_kwargs stays importable from here)
+
 
 # ---- work selection (pure host logic; covered by the CPU / gloo tests) -------------------------------------------
 def select_names(all_names: Sequence[str], pdb_id: Sequence[str] = (), chunk_idx: int = 0, n_chunks: int = 1,
@@ -85,43 +87,19 @@ def collate(batches):
     return {k: torch.cat([b[k] for b in batches], 0) for k in batches[0]}
 
 
-def add_sde_arguments(p):
-    """The options of --sampling_method sde / sde_heun (Sampler.sample_sde's; unset ones take the wrapper's SDE_DEFAULTS)."""
-    p.add_argument("--diffusion_form", default=None,
-                   choices=["constant", "SBDM", "sigma", "linear", "decreasing", "inccreasing-decreasing"],
-                   help="sde / sde_heun: the diffusion coefficient's form (default sigma; SBDM needs --sample_eps > 0)")
-    p.add_argument("--diffusion_norm", type=float, default=None, help="sde / sde_heun: the diffusion coefficient's magnitude (default 1)")
-    p.add_argument("--last_step", default=None, choices=["Mean", "Tweedie", "Euler", "none"],
-                   help="sde / sde_heun: the deterministic last step (default Mean)")
-    p.add_argument("--last_step_size", type=float, default=None, help="sde / sde_heun: the last step's size (default 0.04)")
-    p.add_argument("--sample_eps", type=float, default=None, help="sde / sde_heun: the interval's margin (default 0)")
-
-
-def sde_kwargs(args):
-    """{} or {"sde": {...}} for inference() / rollout() / upsample() from the options above; they go with sde / sde_heun only."""
-    given = {k: getattr(args, k, None) for k in ("diffusion_form", "diffusion_norm", "last_step", "last_step_size", "sample_eps")}
-    given = {k: (None if k == "last_step" and v == "none" else v) for k, v in given.items() if v is not None}
-    if getattr(args, "sampling_method", None) not in ("sde", "sde_heun"):
-        if given:
-            raise SystemExit("--" + ", --".join(given) + ": options of --sampling_method sde / sde_heun")
-        return {}
-    return {"sde": given}
-
-
 def rollout(model, batch, num_frames, num_steps, zs=None, sampling_method=None, **solver):
-    """sim_inference.rollout (:61-98) with the glue on the device."""
+    """sim_inference.rollout (:61-98) with the glue on the device.  `solver`: further keywords of inference() for a named method."""
     from .geometry import atom14_to_cond
     ex = dict(batch)
     ex["torsions"] = batch["torsions"].expand(-1, num_frames, -1, -1, -1)
     ex["trans"] = batch["trans"].expand(-1, num_frames, -1, -1)
     ex["rots"] = batch["rots"].expand(-1, num_frames, -1, -1, -1)
-    if sampling_method is None:
-        atom14, _ = model.inference(ex, zs=zs, num_steps=num_steps)
-    else:
-        atom14, _ = model.inference(ex, zs=zs, num_steps=num_steps, sampling_method=sampling_method, **solver)
-        if sampling_method == "dopri5":
-            st = model.last_stats
-            print(f"dopri5: {st['nfe']} network evaluations ({st['accepted']} accepted, {st['rejected']} rejected steps)")
+    if sampling_method is not None:   # (a model's inference() need not know the keyword when no solver is named)
+        solver["sampling_method"] = sampling_method
+    atom14, _ = model.inference(ex, zs=zs, num_steps=num_steps, **solver)
+    if sampling_method == "dopri5":
+        st = model.last_stats
+        print(f"dopri5: {st['nfe']} network evaluations ({st['accepted']} accepted, {st['rejected']} rejected steps)")
     c = atom14_to_cond(atom14[:, -1], batch["seqres"])
     new = dict(batch)
     new["trans"], new["rots"], new["torsions"] = c["trans"][:, None], c["rots"][:, None], c["torsions"][:, None]
@@ -135,19 +113,17 @@ def make_group_batch(names, arrs, seqres, device):
 
 def sample_group(model, batch, args):
     """`num_rollouts` chained blocks for one batch; returns atom14 [B, R*T, L, 14, 3]."""
-    method = getattr(args, "sampling_method", None)
-    num_steps = 49 if method == "euler" and args.num_steps is None else args.num_steps
+    kw = solver_kwargs(args)   # (no solver named: num_steps alone -- a model's rollout() need not know the other keywords)
     if hasattr(model, "rollout") and not getattr(args, "per_block", False):
-        if method is None:   # (a model's rollout() need not know the keyword when no solver is named)
-            return model.rollout(batch, args.num_frames, args.num_rollouts, num_steps=num_steps)
-        atom14 = model.rollout(batch, args.num_frames, args.num_rollouts, num_steps=num_steps, sampling_method=method, **sde_kwargs(args))
-        if method == "dopri5":
+        atom14 = model.rollout(batch, args.num_frames, args.num_rollouts, **kw)
+        if kw.get("sampling_method") == "dopri5":
             for b, st in enumerate(model.last_stats):
                 print(f"dopri5 block {b}: {st['nfe']} network evaluations ({st['accepted']} accepted, {st['rejected']} rejected steps)")
         return atom14
     out = []
+    num_steps = kw.pop("num_steps")
     for _ in range(args.num_rollouts):   # --per_block: one inference() call per block from Python, whatever the solver
-        atom14, batch = rollout(model, batch, args.num_frames, num_steps, sampling_method=method, **sde_kwargs(args))
+        atom14, batch = rollout(model, batch, args.num_frames, num_steps, **kw)
         out.append(atom14)
     return torch.cat(out, 1)
 
@@ -236,10 +212,7 @@ def build_parser():
     p.add_argument("--xtc", action="store_true")
     p.add_argument("--out_dir", type=str, default=".")
     p.add_argument("--split", type=str, default="splits/4AA_test.csv")
-    p.add_argument("--num_steps", type=int, default=None,
-                   help="solver steps per block (Euler default: 49 = the reference's 50-point grid, Euler checkpoints only)")
-    p.add_argument("--sampling_method", choices=["euler", "dopri5", "midpoint", "heun3", "rk4", "sde", "sde_heun"], default=None,
-                   help="solver (default: the checkpoint's, refused unless it is euler or --num_steps is given)")
+    add_solver_arguments(p, per="block")
     p.add_argument("--batch", type=int, default=1, help="peptides of equal length per inference() call")
     p.add_argument("--chunk_idx", type=int, default=0)
     p.add_argument("--n_chunks", type=int, default=1)
@@ -249,17 +222,12 @@ def build_parser():
                    help="bf16 MFMA operands (default) or the fp32-operand tolerance mode (~10x slower)")
     p.add_argument("--synthetic", action="store_true", help="seeded synthetic weights instead of --sim_ckpt")
     p.add_argument("--npy", action="store_true", help="also save the sampled atom14 array as .npy")
-    add_sde_arguments(p)
     return p
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    if args.sampling_method == "dopri5" and args.num_steps is not None:
-        raise SystemExit("--num_steps sets the Euler grid; dopri5 chooses its own steps (pass one or the other)")
-    if args.num_steps is not None and args.num_steps < 1:
-        raise SystemExit(f"--num_steps must be >= 1, got {args.num_steps}")
-    sde_kwargs(args)
+    solver_kwargs(args)   # (the command line's solver refusals, before anything is loaded)
     if args.no_frames or args.tps:
         raise SystemExit("--no_frames / --tps are outside this build's scope (see DESIGN.md)")
     import pandas as pd

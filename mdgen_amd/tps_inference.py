@@ -12,6 +12,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from .solver import add_solver_arguments, solver_kwargs
+
 
 def get_sample(start_arr, end_arr, seqres_str: str, num_frames: int, device="cuda"):
     """start_arr / end_arr: atom14 coordinates [1, L, 14, 3] (or [L, 14, 3]) of the two end states, Angstrom.
@@ -64,14 +66,8 @@ def build_parser():
     p.add_argument("--n_chunks", type=int, default=1)
     p.add_argument("--start_frame", type=int, default=0, help="MD frame of {name}.npy used as the start state")
     p.add_argument("--end_frame", type=int, default=-1, help="MD frame of {name}.npy used as the end state")
-    p.add_argument("--num_steps", type=int, default=None)
-    p.add_argument("--sampling_method", choices=["euler", "dopri5", "midpoint", "heun3", "rk4", "sde", "sde_heun"], default=None,
-                   help="solver (default: the checkpoint's, refused unless it is euler or --num_steps is given); dopri5: "
-                        "the reference's adaptive solver, one step size per call shared by the --batch_size paths; midpoint / heun3 / "
-                        "rk4: fixed-grid solvers with --num_steps steps (default 24 / 16 / 12)")
+    add_solver_arguments(p, per="batch of paths")
     p.add_argument("--synthetic", action="store_true")
-    from .sim_inference import add_sde_arguments
-    add_sde_arguments(p)
     return p
 
 
@@ -81,7 +77,8 @@ def run(args, model, device, names_seqres, rank=0, world=1):
     import os
     from .geometry import restype_order
     from .pdb import atom14_to_pdb
-    from .sim_inference import sde_kwargs, select_names
+    from .sim_inference import select_names
+    kw = solver_kwargs(args)
     names = select_names(list(names_seqres), args.pdb_id, args.chunk_idx, args.n_chunks, rank, world)
     os.makedirs(args.out_dir, exist_ok=True)
     done = []
@@ -92,15 +89,11 @@ def run(args, model, device, names_seqres, rank=0, world=1):
         batch = collate([one] * args.batch_size)
         aat = np.array([restype_order[c] for c in seq])
         for i in range(args.num_batches):
-            method = getattr(args, "sampling_method", None)
-            if method is None:
-                atom14s, _ = model.inference(batch, num_steps=args.num_steps)
-            else:
-                atom14s, _ = model.inference(batch, num_steps=args.num_steps, sampling_method=method, **sde_kwargs(args))
-                if method == "dopri5":
-                    st = model.last_stats
-                    print(f"{name} batch {i}: dopri5 {st['nfe']} network evaluations ({st['accepted']} accepted, "
-                          f"{st['rejected']} rejected steps)")
+            atom14s, _ = model.inference(batch, **kw)
+            if kw.get("sampling_method") == "dopri5":
+                st = model.last_stats
+                print(f"{name} batch {i}: dopri5 {st['nfe']} network evaluations ({st['accepted']} accepted, "
+                      f"{st['rejected']} rejected steps)")
             host = atom14s.cpu().numpy()
             for j in range(args.batch_size):
                 idx = i * args.batch_size + j
@@ -112,15 +105,11 @@ def run(args, model, device, names_seqres, rank=0, world=1):
 def main(argv=None):
     import pandas as pd
     from .config import ModelConfig
-    from .sim_inference import dist_env, sde_kwargs
+    from .sim_inference import dist_env
     from .synthetic import synth_state_dict
     from .wrapper import NewMDGenWrapper
     args = build_parser().parse_args(argv)
-    if args.sampling_method == "dopri5" and args.num_steps is not None:
-        raise SystemExit("--num_steps sets the Euler grid; dopri5 chooses its own steps (pass one or the other)")
-    if args.num_steps is not None and args.num_steps < 1:
-        raise SystemExit(f"--num_steps must be >= 1, got {args.num_steps}")
-    sde_kwargs(args)
+    solver_kwargs(args)   # (the command line's solver refusals, before anything is loaded)
     rank, world, local_rank = dist_env()
     device = torch.device("cuda", local_rank)
     torch.cuda.set_device(device)

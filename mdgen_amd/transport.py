@@ -161,6 +161,24 @@ def sde_solve(f, x, noise, plan, method, last_step):
     return x + v * h
 
 
+def owning_model(model_fn, model_kwargs):
+    """What a sampler closure is asked to run: (owner, kw, use_graph, model_kwargs) with `owner` the `LatentMDGenModel` whose
+    `forward` / `forward_inference` -- possibly inside a `functools.partial` -- `model_fn` is, and `kw` its merged keywords; owner
+    None for a generic callable, which takes the returned `model_kwargs`.  `use_graph` is the build-specific keyword (capture /
+    replay the solve as a hipGraph), popped from both."""
+    from .model import LatentMDGenModel
+    fn, kw = model_fn, dict(model_kwargs)
+    use_graph = kw.pop("use_graph", True)
+    model_kwargs = dict(kw)
+    if isinstance(fn, partial):
+        kw = {**fn.keywords, **kw}
+        fn = fn.func
+    owner = getattr(fn, "__self__", None)
+    if not (isinstance(owner, LatentMDGenModel) and getattr(fn, "__name__", "") in ("forward", "forward_inference")):
+        owner = None
+    return owner, kw, use_graph, model_kwargs
+
+
 class Sampler:
     def __init__(self, transport: Transport):
         self.transport = transport
@@ -183,15 +201,8 @@ class Sampler:
             return self._sample_rk(sampling_method, S)
 
         def _sample(x0, model_fn, **model_kwargs):
-            from .model import LatentMDGenModel
-            fn, kw = model_fn, dict(model_kwargs)
-            use_graph = kw.pop("use_graph", True)   # build-specific keyword: capture / replay the rollout as a hipGraph
-            model_kwargs = dict(kw)
-            if isinstance(fn, partial):
-                kw = {**fn.keywords, **kw}
-                fn = fn.func
-            owner = getattr(fn, "__self__", None)
-            if isinstance(owner, LatentMDGenModel) and getattr(fn, "__name__", "") in ("forward", "forward_inference"):
+            owner, kw, use_graph, model_kwargs = owning_model(model_fn, model_kwargs)
+            if owner is not None:
                 return owner.sample_euler(x0, S, use_graph=use_graph, **kw)[None]
             # generic drift (any callable): explicit Euler on the host side, x stays on the device
             tg = torch.linspace(0, 1, S + 1)
@@ -206,15 +217,8 @@ class Sampler:
     @staticmethod
     def _sample_rk(method, S):
         def _sample(x0, model_fn, **model_kwargs):
-            from .model import LatentMDGenModel
-            fn, kw = model_fn, dict(model_kwargs)
-            use_graph = kw.pop("use_graph", True)
-            model_kwargs = dict(kw)
-            if isinstance(fn, partial):
-                kw = {**fn.keywords, **kw}
-                fn = fn.func
-            owner = getattr(fn, "__self__", None)
-            if isinstance(owner, LatentMDGenModel) and getattr(fn, "__name__", "") in ("forward", "forward_inference"):
+            owner, kw, use_graph, model_kwargs = owning_model(model_fn, model_kwargs)
+            if owner is not None:
                 return owner.sample_rk(x0, method, S, use_graph=use_graph, **kw)[None]
             # generic drift (any callable): the same formulas in a host loop, in the callable's dtype, on the library's fp32 grid
             tg = linspace01(S + 1).to(dtype=x0.dtype, device=x0.device)
@@ -241,16 +245,9 @@ class Sampler:
         plan = L.sde_plan(opts)   # (refuses here, before any model call, what the library would refuse)
 
         def _sample(init, model_fn, **model_kwargs):
-            from .model import LatentMDGenModel
-            fn, kw = model_fn, dict(model_kwargs)
-            use_graph = kw.pop("use_graph", True)
-            noise = kw.pop("noise", None)
-            model_kwargs = dict(kw)
-            if isinstance(fn, partial):
-                kw = {**fn.keywords, **kw}
-                fn = fn.func
-            owner = getattr(fn, "__self__", None)
-            if isinstance(owner, LatentMDGenModel) and getattr(fn, "__name__", "") in ("forward", "forward_inference"):
+            noise = model_kwargs.pop("noise", None)   # (`model_kwargs` is this call's own dict)
+            owner, kw, use_graph, model_kwargs = owning_model(model_fn, model_kwargs)
+            if owner is not None:
                 return owner.sample_sde(init, opts, noise=noise, use_graph=use_graph, **kw)[None]
             # generic drift (any callable): the same formulas in a host loop, in init's dtype, on the library's grid and coefficients
             if noise is None:

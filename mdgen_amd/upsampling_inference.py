@@ -29,6 +29,8 @@ import time
 import numpy as np
 import torch
 
+from .solver import add_solver_arguments, solver_kwargs
+
 
 def split_windows(n_key: int, num_frames: int, cond_interval: int):
     """(n_windows, K): `n_key` key frames, one every `cond_interval` frames, cut into windows of `num_frames` frames.
@@ -64,20 +66,15 @@ def key_frame_windows(arr, seqres_str, num_frames, cond_interval, device):
 
 def upsample_name(model, windows, args):
     """All windows of one name, `batch_size` at a time -> atom14 (n_windows * T, L, 14, 3)."""
-    from .sim_inference import sde_kwargs
     W = windows["trans"].shape[0]
-    method = getattr(args, "sampling_method", None)
-    num_steps = 49 if method == "euler" and args.num_steps is None else args.num_steps
+    kw = solver_kwargs(args)
     out = []
     for i in range(0, W, max(1, args.batch_size)):
         kb = {k: v[i:i + args.batch_size] for k, v in windows.items()}
-        if method is None:
-            atom14, _ = model.upsample(kb, num_steps=num_steps)
-        else:
-            atom14, _ = model.upsample(kb, num_steps=num_steps, sampling_method=method, **sde_kwargs(args))
-            if method == "dopri5":
-                st = model.last_stats
-                print(f"dopri5: {st['nfe']} network evaluations ({st['accepted']} accepted, {st['rejected']} rejected steps)")
+        atom14, _ = model.upsample(kb, **kw)
+        if kw.get("sampling_method") == "dopri5":
+            st = model.last_stats
+            print(f"dopri5: {st['nfe']} network evaluations ({st['accepted']} accepted, {st['rejected']} rejected steps)")
         out.append(atom14.reshape(-1, *atom14.shape[2:]))
     return torch.cat(out, 0)
 
@@ -132,10 +129,7 @@ def build_parser():
     p.add_argument("--batch_size", type=int, default=1, help="windows per upsample() call")
     p.add_argument("--out_dir", type=str, default=".")
     p.add_argument("--split", type=str, default="splits/4AA_implicit_test.csv")
-    p.add_argument("--num_steps", type=int, default=None,
-                   help="solver steps per window (Euler default: 49 = the reference's 50-point grid, Euler checkpoints only)")
-    p.add_argument("--sampling_method", choices=["euler", "dopri5", "midpoint", "heun3", "rk4", "sde", "sde_heun"], default=None,
-                   help="solver (default: the checkpoint's, refused unless it is euler or --num_steps is given)")
+    add_solver_arguments(p, per="window")
     p.add_argument("--precision", choices=["bf16", "fp32"], default="bf16",
                    help="bf16 MFMA operands (default) or the fp32-operand tolerance mode (~10x slower)")
     p.add_argument("--xtc", action="store_true")
@@ -144,20 +138,13 @@ def build_parser():
     p.add_argument("--num_frames", type=int, default=None, help="frames per window (only with --synthetic; default 1000)")
     p.add_argument("--cond_interval", type=int, default=None,
                    help="frames between key frames (only with --synthetic; default 100)")
-    from .sim_inference import add_sde_arguments
-    add_sde_arguments(p)
     return p
 
 
 def parse_args(argv=None):
     p = build_parser()
     args = p.parse_args(argv)
-    if args.sampling_method == "dopri5" and args.num_steps is not None:
-        p.error("--num_steps sets the Euler grid; dopri5 chooses its own steps (pass one or the other)")
-    if args.num_steps is not None and args.num_steps < 1:
-        p.error(f"--num_steps must be >= 1, got {args.num_steps}")
-    from .sim_inference import sde_kwargs
-    sde_kwargs(args)
+    solver_kwargs(args, p.error)
     if not args.synthetic and (args.num_frames is not None or args.cond_interval is not None):
         p.error("--num_frames / --cond_interval go with --synthetic only (a checkpoint supplies its own)")
     if not args.synthetic and not args.ckpt:

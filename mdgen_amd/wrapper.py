@@ -17,20 +17,12 @@ from .config import ModelConfig
 from .geometry import prep_keyframes, samples_to_atom14
 from .model import LatentMDGenModel
 from .rigid_utils import Rigid, Rotation
-from .transport import RK_METHODS, SDE_METHODS, Sampler, create_transport
+from .solver import RK_DEFAULT_STEPS, SDE_DEFAULT_STEPS, SDE_DEFAULTS, resolve_solver, sde_opts  # noqa: F401 (the defaults are named from here)
+from .transport import Sampler, create_transport
 
 _BACKFILL = ["inpainting", "no_torsion", "hyena", "no_aa_emb", "supervise_all_torsions", "supervise_no_torsions",
              "design_key_frames", "no_design_torsion", "cond_interval", "mpnn", "dynamic_mpnn", "no_offsets",
              "no_frames", "design", "tps_condition", "sim_condition", "abs_pos_emb", "prepend_ipa", "oracle"]
-# steps of the fixed-grid Runge-Kutta solvers when num_steps is not given: 48 network evaluations each (Euler's default grid: 49)
-RK_DEFAULT_STEPS = {"midpoint": 24, "heun3": 16, "rk4": 12}
-_METHODS = (None, "euler", "dopri5") + RK_METHODS + SDE_METHODS
-_METHODS_MSG = "sampling_method must be None, 'euler', 'dopri5', 'midpoint', 'heun3', 'rk4', 'sde' or 'sde_heun'"
-# the SDE sampler's options when `sde={...}` does not name them.  The reference's own defaults (SBDM, 250 points) need
-# sample_eps > 0; the "sigma" diffusion is finite on the whole interval with sample_eps = 0.  49 stochastic steps cost what Euler's
-# default grid costs (+ 1 evaluation for the last step); their sample quality has not been measured.
-SDE_DEFAULTS = dict(diffusion_form="sigma", diffusion_norm=1.0, last_step="Mean", last_step_size=0.04, sample_eps=0.0)
-SDE_DEFAULT_STEPS = 49
 _UNSUPPORTED = ["inpainting", "hyena", "no_aa_emb", "design_key_frames", "mpnn", "dynamic_mpnn", "no_offsets",
                 "no_frames", "design", "no_torsion", "no_design_torsion", "interleave_ipa",
                 "abs_time_emb", "oracle", "no_rope"]
@@ -168,20 +160,13 @@ class NewMDGenWrapper:
                                              mask=prep["loss_mask"], model_kwargs=prep["model_kwargs"], t=t, x0=x0)
         return out["loss"], out
 
+    def _solver(self, sampling_method, num_steps, atol, rtol, sde, noise=None):
+        """The call's `solver.SolverChoice` (every refusal about solver arguments is `resolve_solver`'s)."""
+        return resolve_solver(getattr(self.args, "sampling_method", "euler"), sampling_method, num_steps, atol, rtol, sde,
+                              getattr(self.args, "path_type", "GVP"), noise)
+
     def _sde_opts(self, sampling_method, num_steps, sde):
-        """`_lib.SdeOpts` of `sampling_method` "sde" (Euler-Maruyama) / "sde_heun" with `num_steps` stochastic steps (default 49)
-        and the options of `sde` over SDE_DEFAULTS; an unknown option or value raises before anything runs."""
-        unknown = set(sde or {}) - set(SDE_DEFAULTS)
-        if unknown:
-            raise L.MdgenError(f"sde options are {sorted(SDE_DEFAULTS)}, got {sorted(unknown)}")
-        S = SDE_DEFAULT_STEPS if num_steps is None else int(num_steps)
-        try:
-            opts = L.sde_opts("Euler" if sampling_method == "sde" else "Heun", self.args.path_type, num_steps=S + 1,
-                              **{**SDE_DEFAULTS, **(sde or {})})
-        except ValueError as e:
-            raise L.MdgenError(str(e)) from None
-        L.sde_plan(opts)   # (the library's own refusals: a non-finite coefficient, t0 >= t1)
-        return opts
+        return sde_opts(sampling_method, num_steps, sde, self.args.path_type)
 
     def inference(self, batch, zs=None, num_steps=None, use_graph=True, rel_quats=None, sampling_method=None, atol=1e-6,
                   rtol=1e-3, sde=None, noise=None):
@@ -197,47 +182,31 @@ class NewMDGenWrapper:
         `sampling_method="sde" | "sde_heun"`: the reference's `Sampler.sample_sde` with Euler-Maruyama / Heun steps
         (`LatentMDGenModel.sample_sde`, one hipGraph): `num_steps` stochastic steps S (default 49) on S + 1 grid points, then the
         last step; `sde`: a dict over SDE_DEFAULTS (diffusion_form "sigma", diffusion_norm 1, last_step "Mean", last_step_size
-        0.04, sample_eps 0); `noise`: optional (S, B, T, L, D) standard normals, default a device randn drawn after `zs`."""
-        opts = self._sde_opts(sampling_method, num_steps, sde) if sampling_method in SDE_METHODS else None
-        if opts is None and (sde is not None or noise is not None):
-            raise L.MdgenError("sde / noise are options of sampling_method='sde' | 'sde_heun'")
+        0.04, sample_eps 0); `noise`: optional (S, B, T, L, D) standard normals, default a device randn drawn after `zs`.
+        The solver arguments are judged by `solver.resolve_solver`, before the batch is touched."""
+        choice = self._solver(sampling_method, num_steps, atol, rtol, sde, noise)
+        return self._inference(batch, choice, zs=zs, use_graph=use_graph, rel_quats=rel_quats, noise=noise)
+
+    def _inference(self, batch, choice, zs=None, use_graph=True, rel_quats=None, noise=None):
+        """`inference()` with its solver resolved."""
         prep = self.prep_batch(batch)
         rigids = prep["rigids"]
         B, T, L_ = rigids.shape
         dev = prep["latents"].device
         if zs is None:
             zs = torch.randn(B, T, L_, self.latent_dim, device=dev)
-        if sampling_method not in _METHODS:
-            raise L.MdgenError(f"{_METHODS_MSG}, got {sampling_method!r}")
-        if sampling_method == "dopri5" and num_steps is not None:
-            raise L.MdgenError("num_steps sets the fixed Euler grid; dopri5 chooses its own steps (pass one or the other)")
-        if num_steps is not None and int(num_steps) < 1:
-            raise L.MdgenError(f"num_steps must be >= 1, got {num_steps}")
-        # wrapper.py:441 samples with args.sampling_method (argparse default 'dopri5', parsing.py:102) on the
-        # solver's own 50-point grid.  Without an explicit choice (sampling_method / num_steps) a non-Euler checkpoint is
-        # rejected instead of being silently sampled with a different solver.
-        method = getattr(self.args, "sampling_method", "euler")
-        if sampling_method is None and num_steps is None and method != "euler":
-            raise L.MdgenError(f"checkpoint args say sampling_method={method!r}; pass sampling_method='dopri5' (CLI: "
-                               "--sampling_method dopri5) for the reference's solver, or num_steps=... (CLI: --num_steps) "
-                               "to sample with fixed-grid Euler")
         kw = dict(prep["model_kwargs"])
         kw["mask"] = kw["mask"].contiguous()
         if not self.args.tps_condition:
             kw["end_frames"] = None
         if rel_quats is not None:
             kw["rel_quats"] = rel_quats
-        if sampling_method == "dopri5":
-            samples, self.last_stats = self.model.sample_dopri5(zs, atol=atol, rtol=rtol, **kw)
-        elif opts is not None:
-            samples = self.model.sample_sde(zs, opts, noise=noise, use_graph=use_graph, **kw)
-        elif sampling_method in RK_METHODS:
-            S = RK_DEFAULT_STEPS[sampling_method] if num_steps is None else int(num_steps)
-            sample_fn = self.transport_sampler.sample_ode(sampling_method=sampling_method, num_steps=S + 1)
-            samples = sample_fn(zs, partial(self.model.forward_inference, **kw), use_graph=use_graph)[-1]
-        else:
-            S = 49 if num_steps is None else int(num_steps)
-            sample_fn = self.transport_sampler.sample_ode(sampling_method="euler", num_steps=S + 1)
+        if choice.kind == "dopri5":
+            samples, self.last_stats = self.model.sample_dopri5(zs, atol=choice.atol, rtol=choice.rtol, **kw)
+        elif choice.kind == "sde":
+            samples = self.model.sample_sde(zs, choice.sde_opts, noise=noise, use_graph=use_graph, **kw)
+        else:   # "euler" | "rk": the transport's fixed-grid samplers
+            sample_fn = self.transport_sampler.sample_ode(sampling_method=choice.method, num_steps=choice.steps + 1)
             samples = sample_fn(zs, partial(self.model.forward_inference, **kw), use_graph=use_graph)[-1]
         r0 = rigids[:, 0]
         atom14 = samples_to_atom14(samples, r0.get_rots().get_rot_mats(), r0.get_trans(), batch["seqres"],
@@ -266,20 +235,7 @@ class NewMDGenWrapper:
         T = int(self.args.num_frames if num_frames is None else num_frames)
         if c < 1 or T < 1:
             raise L.MdgenError(f"num_frames and cond_interval must be >= 1, got {T}, {c}")
-        opts = self._sde_opts(sampling_method, num_steps, sde) if sampling_method in SDE_METHODS else None
-        if opts is None and sde is not None:
-            raise L.MdgenError("sde is an option of sampling_method='sde' | 'sde_heun'")
-        if sampling_method not in _METHODS:
-            raise L.MdgenError(f"{_METHODS_MSG}, got {sampling_method!r}")
-        if sampling_method == "dopri5" and num_steps is not None:
-            raise L.MdgenError("num_steps sets the fixed Euler grid; dopri5 chooses its own steps (pass one or the other)")
-        if num_steps is not None and int(num_steps) < 1:
-            raise L.MdgenError(f"num_steps must be >= 1, got {num_steps}")
-        method = getattr(self.args, "sampling_method", "euler")
-        if sampling_method is None and num_steps is None and method != "euler":
-            raise L.MdgenError(f"checkpoint args say sampling_method={method!r}; pass sampling_method='dopri5' (CLI: "
-                               "--sampling_method dopri5) for the reference's solver, or num_steps=... (CLI: --num_steps) "
-                               "to sample with fixed-grid Euler")
+        choice = self._solver(sampling_method, num_steps, atol, rtol, sde)
         tors = batch["torsions"].to(torch.float32)
         trans = batch["trans"].to(torch.float32)
         rots = batch["rots"].to(torch.float32)
@@ -294,28 +250,26 @@ class NewMDGenWrapper:
         if zs is None:
             zs = torch.randn(B, T, L_, self.latent_dim, device=dev)
         mask = batch["mask"].to(torch.float32).unsqueeze(1).expand(-1, T, -1)
-        if sampling_method == "dopri5" or opts is not None:
+        if choice.kind in ("dopri5", "sde"):
             prep = prep_keyframes(rots, trans, tors, T, c)
             kw = dict(mask=mask.contiguous(), start_frames=(prep["start_rot"], prep["start_trans"]), x_cond=prep["x_cond"],
                       x_cond_mask=prep["x_cond_mask"], aatype=batch["seqres"])
-            if opts is not None:
-                samples = self.model.sample_sde(zs, opts, use_graph=use_graph, **kw)
+            if choice.kind == "sde":
+                samples = self.model.sample_sde(zs, choice.sde_opts, use_graph=use_graph, **kw)
             else:
-                samples, self.last_stats = self.model.sample_dopri5(zs, atol=atol, rtol=rtol, **kw)
+                samples, self.last_stats = self.model.sample_dopri5(zs, atol=choice.atol, rtol=choice.rtol, **kw)
             atom14 = samples_to_atom14(samples, prep["start_rot"], prep["start_trans"], batch["seqres"], False)
-        elif sampling_method in RK_METHODS:
-            S = RK_DEFAULT_STEPS[sampling_method] if num_steps is None else int(num_steps)
-            atom14, samples = self.model.upsample_rk(zs, sampling_method, S, c, mask, rots, trans, tors, batch["seqres"],
+        elif choice.kind == "rk":
+            atom14, samples = self.model.upsample_rk(zs, choice.method, choice.steps, c, mask, rots, trans, tors, batch["seqres"],
                                                      residue_tables(dev), use_graph=use_graph)
         else:
-            S = 49 if num_steps is None else int(num_steps)
-            atom14, samples = self.model.upsample_euler(zs, S, c, mask, rots, trans, tors, batch["seqres"],
+            atom14, samples = self.model.upsample_euler(zs, choice.steps, c, mask, rots, trans, tors, batch["seqres"],
                                                         residue_tables(dev), use_graph=use_graph)
         self.last_samples = samples
         return atom14, batch["seqres"][:, None].expand(B, T, L_)
 
-    def _rollout_host_loop(self, batch, T, zs, **solver):
-        """The blocks of `rollout()` as a host loop of `inference(**solver)` -- prep_latents -> the solver -> samples_to_atom14 --
+    def _rollout_host_loop(self, batch, T, zs, choice, use_graph):
+        """The blocks of `rollout()` as a host loop of `inference()` with the resolved `choice` -- prep_latents -> the solver -> samples_to_atom14 --
         and `atom14_to_cond`, all on the device: the adaptive solver (dopri5 reads its error ratio back once per attempted step,
         so it cannot be captured) and the SDE samplers (no fused driver).  -> (atom14, samples (R,B,T,L,D), next conditioning
         frame, per-block stats)."""
@@ -326,7 +280,7 @@ class NewMDGenWrapper:
             ex["torsions"] = batch["torsions"].expand(-1, T, -1, -1, -1)
             ex["trans"] = batch["trans"].expand(-1, T, -1, -1)
             ex["rots"] = batch["rots"].expand(-1, T, -1, -1, -1)
-            atom14, _ = self.inference(ex, zs=z, **solver)
+            atom14, _ = self._inference(ex, choice, zs=z, use_graph=use_graph)
             nxt = atom14_to_cond(atom14[:, -1], batch["seqres"])
             batch = dict(batch)
             batch["trans"], batch["rots"], batch["torsions"] = nxt["trans"][:, None], nxt["rots"][:, None], nxt["torsions"][:, None]
@@ -351,15 +305,7 @@ class NewMDGenWrapper:
         from .geometry import residue_tables
         if self.args.tps_condition or getattr(self.args, "cond_interval", None):
             raise L.MdgenError("rollout() is the forward-simulation driver (sim_condition models without cond_interval)")
-        if sampling_method not in _METHODS:
-            raise L.MdgenError(f"{_METHODS_MSG}, got {sampling_method!r}")
-        if sampling_method == "dopri5" and num_steps is not None:
-            raise L.MdgenError("num_steps sets the fixed Euler grid; dopri5 chooses its own steps (pass one or the other)")
-        if num_steps is not None and int(num_steps) < 1:
-            raise L.MdgenError(f"num_steps must be >= 1, got {num_steps}")
-        method = getattr(self.args, "sampling_method", "euler")
-        if sampling_method is None and num_steps is None and method != "euler":
-            raise L.MdgenError(f"checkpoint args say sampling_method={method!r}; pass num_steps=... to sample with Euler")
+        choice = self._solver(sampling_method, num_steps, atol, rtol, sde)
         tors = batch["torsions"][:, 0].to(torch.float32)
         trans = batch["trans"][:, 0].to(torch.float32)
         rots = batch["rots"][:, 0].to(torch.float32)
@@ -367,23 +313,20 @@ class NewMDGenWrapper:
         B, L_ = trans.shape[:2]
         T, R = int(num_frames), int(num_rollouts)
         dev = trans.device
-        if zs is None and sampling_method in (None, "euler"):
+        if zs is None and choice.kind == "euler":
             zs = torch.randn(R, B, T, L_, self.latent_dim, device=dev)
         elif zs is None:   # one draw per block, in block order: what the per-block loop of inference() calls draws
             zs = torch.stack([torch.randn(B, T, L_, self.latent_dim, device=dev) for _ in range(R)])
         mask = batch["mask"].to(torch.float32).unsqueeze(1).expand(-1, T, -1)
-        if sampling_method == "dopri5":
-            atom14, samples, nxt, self.last_stats = self._rollout_host_loop(batch, T, zs, sampling_method="dopri5", atol=atol, rtol=rtol)
-        elif sampling_method in SDE_METHODS:
-            atom14, samples, nxt, _ = self._rollout_host_loop(batch, T, zs, sampling_method=sampling_method, num_steps=num_steps,
-                                                              use_graph=use_graph, sde=sde)
-        elif sampling_method in RK_METHODS:
-            S = RK_DEFAULT_STEPS[sampling_method] if num_steps is None else int(num_steps)
-            atom14, samples, nxt = self.model.rollout_rk(zs, sampling_method, S, mask, rots, trans, tors, batch["seqres"],
+        if choice.kind in ("dopri5", "sde"):
+            atom14, samples, nxt, stats = self._rollout_host_loop(batch, T, zs, choice, use_graph)
+            if choice.kind == "dopri5":
+                self.last_stats = stats
+        elif choice.kind == "rk":
+            atom14, samples, nxt = self.model.rollout_rk(zs, choice.method, choice.steps, mask, rots, trans, tors, batch["seqres"],
                                                          residue_tables(dev), use_graph=use_graph)
         else:
-            S = 49 if num_steps is None else int(num_steps)
-            atom14, samples, nxt = self.model.rollout_euler(zs, S, mask, rots, trans, tors, batch["seqres"],
+            atom14, samples, nxt = self.model.rollout_euler(zs, choice.steps, mask, rots, trans, tors, batch["seqres"],
                                                             residue_tables(dev), use_graph=use_graph)
         self.last_samples = samples
         if not return_next:
