@@ -349,6 +349,44 @@ int32_t mdgen_debug_sde_stage(mdgen_ctx* ctx, const mdgen_shape* shape, const md
                               float* x, const float* v0, const float* v1, const float* xi, const float* x_cond,
                               const int64_t* x_cond_mask, const float* ipa_out, float* h, void* stream);
 
+/* SDE sampling with the noise generated inside the kernels: mdgen_sample_sde without `noise` and `noise_step_stride`.  No buffer of
+ * (n_points - 1) x state floats exists; the kernels that read a step's noise compute it, element by element, with a counter-based
+ * generator (csrc/philox.h) from
+ *   rng   a device pointer, 8-byte aligned, to four uint64 words {seed, sample_base, block_base, 0}, read INSIDE the kernels: a replay
+ *         of the captured graph draws from whatever the words hold then.  Write them on the call's stream before the call.
+ * The stream, so that an outside caller can reproduce it.  The deviate of element (b, t, l, d) of the (B,T,L,D) state, stochastic
+ * step i (0-based; Heun's noise term of step i is step i's), block k of a driver call (0 for this entry point):
+ *   counter  c0 = (t L + l) D + d           the element within its sample (a shape with T L D >= 2^32 is refused, -2)
+ *            c1 = sample_base + b           b: the position in the WHOLE call's batch
+ *            c2 = i
+ *            c3 = block_base + k            every word mod 2^32
+ *   key      {seed & 0xffffffff, seed >> 32}
+ *   w        = Philox4x32-10(counter; key): multipliers 0xD2511F53 (on c0), 0xCD9E8D57 (on c2), key increments 0x9E3779B9,
+ *              0xBB67AE85, ten rounds (Random123's philox4x32; mdgen_debug_philox is the same function on the host)
+ *   u1       = ((w0 >> 9) + 0.5) 2^-23      exact in fp32, in (0, 1), at least 2^-24: |xi| <= 5.77
+ *   u2       = (w1 >> 8) 2^-24              exact in fp32, in [0, 1)
+ *   xi       = sqrtf(-2 logf(u1)) * cosf(6.2831855f * u2)     fp32, every operation rounded once, accurate math functions
+ * w2 and w3 are unused: a value depends on its coordinates alone -- not on the batch a sample travels in (give the sample its
+ * sample_base), on how the library splits the batch, or on the kernel form a launch size picks.
+ * Refusals, plan, workspace (mdgen_sde_workspace_bytes) and launch sequence are mdgen_sample_sde's; the graph is cached per shape,
+ * options and pointers (x, rng).  Further errors: -1 rng null; -7 rng alignment. */
+int32_t mdgen_sample_sde_rng(mdgen_ctx* ctx, const mdgen_shape* shape, const mdgen_sde_opts* opts, float* x, const uint64_t* rng,
+                             const mdgen_cond* cond, void* workspace, size_t workspace_bytes, int32_t use_graph, void* stream);
+/* Test hook: xi of ONE stochastic step `step` of block `block` under the words at `rng`, (B,T,L,latent_dim) fp32 to `out` (16-byte
+ * aligned), through the device function the sampler's kernels call (the elementwise kernel's generator form on a zero state). */
+int32_t mdgen_debug_sde_noise(const mdgen_shape* shape, int32_t latent_dim, const uint64_t* rng, int32_t step, int32_t block,
+                              float* out, void* stream);
+/* Test hook: mdgen_debug_sde_stage with the generator in xi's place: states 1 and 2 draw the noise of step `step`, state 5 that of
+ * step `step` + 1, of block `block`; the other states read no noise and run exactly as mdgen_debug_sde_stage runs them. */
+int32_t mdgen_debug_sde_stage_rng(mdgen_ctx* ctx, const mdgen_shape* shape, const mdgen_sde_opts* opts, int32_t state, int32_t step,
+                                  int32_t block, float* x, const float* v0, const float* v1, const uint64_t* rng,
+                                  const float* x_cond, const int64_t* x_cond_mask, const float* ipa_out, float* h, void* stream);
+/* Host only: the number of captured hipGraphs the context holds (at most 8, least recently used evicted): a replay leaves it as it
+ * is, a capture adds one. */
+int32_t mdgen_debug_graph_count(const mdgen_ctx* ctx, int32_t* count);
+/* Host only: out[4] = Philox4x32-10(ctr[4]; key[2]), csrc/philox.h compiled for the host. */
+int32_t mdgen_debug_philox(const uint32_t* ctr, const uint32_t* key, uint32_t* out);
+
 /* Residue constant tables (device pointers; data of mdgen/residue_constants.py:1124-1216, 1367-1480), as the two
  * geometry entry points below take them one by one. */
 typedef struct mdgen_residue_tables {
@@ -439,6 +477,25 @@ int32_t mdgen_upsample_rk(mdgen_ctx* ctx, const mdgen_shape* shape, int32_t meth
                           float* x_cond, int64_t* x_cond_mask, float* start_rot, float* start_trans,
                           const mdgen_residue_tables* tables, float* atom14,
                           void* workspace, size_t workspace_bytes, int32_t use_graph, void* stream);
+
+/* mdgen_rollout_rk / mdgen_upsample_rk with the SDE solve of mdgen_sample_sde_rng (opts, rng: as there) in the Runge-Kutta solve's
+ * place: ONE call and -- with use_graph -- one hipGraph (cached per options, n_blocks / cond_interval, stride and pointers, rng's
+ * among them).  No noise is staged: block k of a rollout draws with counter word c3 = block_base + k, an upsampling call with
+ * c3 = block_base.  The other arguments, the workspace rule (mdgen_sde_workspace_bytes) and the errors are the Runge-Kutta
+ * drivers', with mdgen_sample_sde's option refusals (-2) in the method's and n_steps' place; all decided before any device call. */
+int32_t mdgen_rollout_sde(mdgen_ctx* ctx, const mdgen_shape* shape, const mdgen_sde_opts* opts, const uint64_t* rng, int32_t n_blocks,
+                          float* zs, int64_t zs_block_stride, const float* mask,
+                          float* cond_rots, float* cond_trans, float* cond_torsions,
+                          const int64_t* seqres, float* x_cond, int64_t* x_cond_mask,
+                          const mdgen_residue_tables* tables, float* atom14,
+                          void* workspace, size_t workspace_bytes, int32_t use_graph, void* stream);
+int32_t mdgen_upsample_sde(mdgen_ctx* ctx, const mdgen_shape* shape, const mdgen_sde_opts* opts, const uint64_t* rng,
+                           int32_t cond_interval, float* zs, const float* mask,
+                           const float* key_rots, const float* key_trans, const float* key_torsions,
+                           const int64_t* seqres,
+                           float* x_cond, int64_t* x_cond_mask, float* start_rot, float* start_trans,
+                           const mdgen_residue_tables* tables, float* atom14,
+                           void* workspace, size_t workspace_bytes, int32_t use_graph, void* stream);
 
 /* ---- measurement ----------------------------------------------------------------------------
  * Per-kernel-class timing with hipEvents recorded on the launch stream (bench.py's roofline leg).

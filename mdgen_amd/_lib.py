@@ -28,6 +28,7 @@ EXPORTS = [
     "mdgen_sample_rk", "mdgen_rk_workspace_bytes", "mdgen_debug_rk_plan", "mdgen_debug_rk_stage",
     "mdgen_rollout_rk", "mdgen_upsample_rk",
     "mdgen_sample_sde", "mdgen_sde_workspace_bytes", "mdgen_debug_sde_plan", "mdgen_debug_sde_dispatch_plan", "mdgen_debug_sde_stage",
+    "mdgen_sample_sde_rng", "mdgen_debug_sde_noise", "mdgen_debug_sde_stage_rng", "mdgen_debug_philox", "mdgen_rollout_sde", "mdgen_upsample_sde", "mdgen_debug_graph_count",
 ]
 
 
@@ -106,6 +107,11 @@ def _load():
     lib.mdgen_debug_sde_plan.argtypes = [sde_p, vp, vp, i32, C.POINTER(i32), vp, C.POINTER(i32), C.POINTER(i32), vp]
     lib.mdgen_debug_sde_dispatch_plan.argtypes = [C.POINTER(Shape), sde_p, i32, i32, i32, i32, C.c_char_p, C.c_char_p, sz]
     lib.mdgen_debug_sde_stage.argtypes = [vp, C.POINTER(Shape), sde_p, i32, i32] + [vp] * 9
+    lib.mdgen_sample_sde_rng.argtypes = ctx_shape + [sde_p, vp, vp, cond_p] + ws_bytes + [i32, vp]   # opts | x, rng words
+    lib.mdgen_debug_sde_noise.argtypes = [C.POINTER(Shape), i32, vp, i32, i32, vp, vp]
+    lib.mdgen_debug_sde_stage_rng.argtypes = [vp, C.POINTER(Shape), sde_p, i32, i32, i32] + [vp] * 9
+    lib.mdgen_debug_philox.argtypes = [vp, vp, vp]
+    lib.mdgen_debug_graph_count.argtypes = [vp, C.POINTER(i32)]
     tables_atom14 = [C.POINTER(ResidueTables), vp]
     lib.mdgen_rollout_euler.argtypes = (ctx_shape + [i32, i32] + [vp, vp] + [vp, vp, vp] + [vp] + [vp, vp]   # zs, mask | cond frame | seqres | x_cond, its mask
                                         + tables_atom14 + ws_bytes + [i32, vp])
@@ -115,6 +121,10 @@ def _load():
                                      + tables_atom14 + ws_bytes + [i32, vp])
     lib.mdgen_upsample_rk.argtypes = (ctx_shape + [i32, i32, i32] + [vp, vp] + [vp, vp, vp] + [vp] + [vp, vp] + [vp, vp]   # as mdgen_upsample_euler after (method, steps, interval)
                                       + tables_atom14 + ws_bytes + [i32, vp])
+    lib.mdgen_rollout_sde.argtypes = (ctx_shape + [sde_p, vp, i32] + [vp, i64, vp] + [vp, vp, vp] + [vp] + [vp, vp]   # as mdgen_rollout_rk after (opts, rng, blocks)
+                                      + tables_atom14 + ws_bytes + [i32, vp])
+    lib.mdgen_upsample_sde.argtypes = (ctx_shape + [sde_p, vp, i32] + [vp, vp] + [vp, vp, vp] + [vp] + [vp, vp] + [vp, vp]   # as mdgen_upsample_rk after (opts, rng, interval)
+                                       + tables_atom14 + ws_bytes + [i32, vp])
     lib.mdgen_profile_enable.argtypes = [vp, i32]
     lib.mdgen_profile_phase_trace.argtypes = [vp, vp, i64]
     lib.mdgen_profile_report.argtypes = [vp, vp, C.c_char_p, sz]
@@ -277,6 +287,33 @@ def sde_plan(opts):
     out = {"rows": rows[:n_rows.value].copy(), "coef": coef[:n_rows.value].copy(),
            "row_of": row_of[:S * n_st.value].reshape(S, n_st.value).copy(), "last_row": last.value}
     out.update(zip(("dt", "q", "hdt", "h", "c0", "c1"), sc.view(np.float32)))
+    return out
+
+
+def philox(ctr, key):
+    """`mdgen_debug_philox` (host only): Philox4x32-10 of the four counter words under the two key words -> uint32[4]."""
+    import numpy as np
+    c, k, out = np.asarray(ctr, dtype=np.uint32).copy(), np.asarray(key, dtype=np.uint32).copy(), np.zeros(4, dtype=np.uint32)
+    if c.shape != (4,) or k.shape != (2,):
+        raise ValueError("philox takes four counter words and two key words")
+    check(lib.mdgen_debug_philox(c.ctypes.data, k.ctypes.data, out.ctypes.data))
+    return out
+
+
+def rng_words(seed, sample_base=0, block_base=0):
+    """The four words {seed, sample_base, block_base, 0} of mdgen_sample_sde_rng's `rng` as an int64 CPU tensor (bit patterns of the
+    unsigned words: the seed mod 2^64, the bases mod 2^32); copy it into the call's device buffer on the call's stream."""
+    def signed(v, bits):
+        v = int(v) % (1 << bits)
+        return v - (1 << 64) if v >= 1 << 63 else v
+    return torch.tensor([signed(seed, 64), signed(sample_base, 32), signed(block_base, 32), 0], dtype=torch.int64)
+
+
+def sde_noise(B, T, L_, D, rng, step, block=0):
+    """`mdgen_debug_sde_noise`: the (B, T, L, D) noise of stochastic step `step` of block `block` under the device words `rng`."""
+    out = torch.empty(B, T, L_, D, device=rng.device)
+    sh = Shape(B, T, L_)
+    launch(lib.mdgen_debug_sde_noise, rng, C.byref(sh), int(D), ptr(rng, torch.int64), int(step), int(block), ptr(out))
     return out
 
 

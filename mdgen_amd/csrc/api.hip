@@ -3,6 +3,7 @@
 #include "../../include/mdgen_amd.h"
 #include "kernels.h"
 #include "linear.h"
+#include "philox.h"
 
 #include <algorithm>
 #include <cmath>
@@ -2007,6 +2008,13 @@ static int replay_or_capture(mdgen_ctx* c, const std::vector<uint64_t>& key, hip
     return 0;
 }
 
+// Test hook (host only): how many captured graphs the context holds (at most 8: replay_or_capture's LRU)
+extern "C" int32_t mdgen_debug_graph_count(const mdgen_ctx* c, int32_t* count) {
+    if (!c || !count) return fail(-1, "null argument");
+    *count = (int32_t)c->graphs.size();
+    return 0;
+}
+
 // The capture gate of every capturing entry point: `body` runs directly without use_graph and while profiling (see mdgen_profile_enable)
 static int run_or_replay(const Run& r, int use_graph, const GraphKey& key, const std::function<int()>& body) {
     if (!use_graph || r.c->prof_on) return body();
@@ -2166,7 +2174,7 @@ extern "C" int32_t mdgen_debug_sde_dispatch_plan(const mdgen_shape* sh, const md
     if (nv == 0) return fail(-2, "sample too large for one launch");
     float* fake = (float*)4096;
     float* v[2] = {fake, fake};
-    if (int e = sde_body(r, o, pl, nv, fake, v, fake, 0)) return e;
+    if (int e = sde_body(r, o, pl, nv, fake, v, SdeNoise{fake, 0, nullptr, 0})) return e;
     return plan_json(dry.plan, r.B, nv, 1, true, buf, buflen);
 }
 

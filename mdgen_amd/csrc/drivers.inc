@@ -1,6 +1,7 @@
-// -*- c++ -*-  The fused drivers (included by api.hip after ode.inc): the Euler and the Runge-Kutta entry point of a driver share its
-// refusals and its captured body -- the glue kernels around a solve -- and differ in the solve: euler_body on the entry point's time
-// grid, or RkCall::solve (ode.inc), which prepares its own time rows on the stream.
+// -*- c++ -*-  The fused drivers (included by api.hip after ode.inc and sde.inc): the Euler, the Runge-Kutta and the SDE entry point
+// of a driver share its refusals and its captured body -- the glue kernels around a solve -- and differ in the solve: euler_body on
+// the entry point's time grid, or RkCall::solve (ode.inc) / SdeCall::solve (sde.inc, with generated noise), which prepare their own
+// time rows on the stream.
 
 // the conditioning a driver fills from the caller's buffers: start frames alone (forward-simulation models)
 static mdgen_cond driver_cond(const float* mask, const float* rot, const float* trans, const float* x_cond, const int64_t* x_cond_mask,
@@ -110,6 +111,32 @@ extern "C" int32_t mdgen_rollout_rk(mdgen_ctx* c, const mdgen_shape* sh, int32_t
                        x_cond_mask, *tb, atom14, [&](float* x) { return q.solve(S, x); });
 }
 
+// mdgen_rollout_rk with the SDE solve (sde.inc) per block, its noise generated in the kernels: block b draws with counter word
+// block_base + b, so the call needs no noise at all.  The refusals are mdgen_rollout_rk's with sde_plan's in rk_check's place.
+extern "C" int32_t mdgen_rollout_sde(mdgen_ctx* c, const mdgen_shape* sh, const mdgen_sde_opts* o, const uint64_t* rng, int32_t n_blocks,
+                                     float* zs, int64_t stride, const float* mask, float* cond_rots, float* cond_trans,
+                                     float* cond_torsions, const int64_t* seqres, float* x_cond, int64_t* x_cond_mask,
+                                     const mdgen_residue_tables* tb, float* atom14, void* ws, size_t ws_bytes, int32_t use_graph,
+                                     void* stream) {
+    if (!sh || !o || !rng || !zs || !cond_torsions || !tb || !atom14 || !ws) return fail(-1, "null argument");
+    const mdgen_cond cd = driver_cond(mask, cond_rots, cond_trans, x_cond, x_cond_mask, seqres);
+    if (int e = driver_check_pointers(cd, tb, true)) return e;
+    if (int e = sde_check(o)) return e;
+    if (int e = driver_check_model(c, n_blocks, "n_blocks", "the block rollout")) return e;
+    if (sh->B < 1 || sh->T < 1 || sh->L < 1) return fail(-2, "B, T, L must be >= 1");
+    if (int e = rollout_too_long(sh, n_blocks)) return e;
+    const long blk = (long)sh->B * sh->T * sh->L * (c ? c->D : 21);
+    if (stride % 4 != 0) return fail(-7, "zs_block_stride must be a multiple of 4 floats (got %lld)", (long long)stride);
+    if (stride < blk) return fail(-7, "zs_block_stride %lld is below one block of %ld floats", (long long)stride, blk);
+    SdeCall q;
+    if (int e = sde_open(&q, c, sh, o, zs, SdeNoise{nullptr, 0, rng, 0}, cd, ws, ws_bytes, stream)) return e;
+    GraphKey key = graph_key(8, q.r, cd);
+    key.add_struct(q.key).add(n_blocks).add((uint64_t)stride).ptr(rng);
+    return rollout_run(q.r, use_graph, key, 0, n_blocks, zs, (long)stride, cond_rots, cond_trans, cond_torsions, seqres, x_cond,
+                       x_cond_mask, *tb, atom14,
+                       [&](float* x) { return q.solve(x, SdeNoise{nullptr, 0, rng, (int)((x - zs) / stride)}); });
+}
+
 // Trajectory upsampling (upsampling_inference.py:47-82 around wrapper.py:283-365, 405-484) as ONE call / ONE hipGraph:
 //   key frames (B, K, L) -> x_cond, x_cond_mask, start frames (k_prep_keyframes; no (B, T, L) window of zeros on the way)
 //   -> the solve, exactly as mdgen_sample_euler / mdgen_sample_rk run it -> atom14 relative to key frame 0.
@@ -172,4 +199,24 @@ extern "C" int32_t mdgen_upsample_rk(mdgen_ctx* c, const mdgen_shape* sh, int32_
     key.add(method).add(S).add(cond_interval);
     return upsample_run(q.r, use_graph, key, 0, cond_interval, zs, key_rots, key_trans, key_torsions, seqres, x_cond, x_cond_mask,
                         start_rot, start_trans, *tb, atom14, [&](float* x) { return q.solve(S, x); });
+}
+
+// mdgen_upsample_rk with the SDE solve, its noise generated in the kernels (block counter word: block_base)
+extern "C" int32_t mdgen_upsample_sde(mdgen_ctx* c, const mdgen_shape* sh, const mdgen_sde_opts* o, const uint64_t* rng,
+                                      int32_t cond_interval, float* zs, const float* mask, const float* key_rots, const float* key_trans,
+                                      const float* key_torsions, const int64_t* seqres, float* x_cond, int64_t* x_cond_mask,
+                                      float* start_rot, float* start_trans, const mdgen_residue_tables* tb, float* atom14, void* ws,
+                                      size_t ws_bytes, int32_t use_graph, void* stream) {
+    if (!sh || !o || !rng || !zs || !key_rots || !key_trans || !key_torsions || !tb || !atom14 || !ws) return fail(-1, "null argument");
+    const mdgen_cond cd = driver_cond(mask, start_rot, start_trans, x_cond, x_cond_mask, seqres);
+    if (int e = driver_check_pointers(cd, tb, false)) return e;
+    if (int e = sde_check(o)) return e;
+    if (int e = driver_check_model(c, cond_interval, "cond_interval", "upsampling")) return e;
+    const SdeNoise nz{nullptr, 0, rng, 0};
+    SdeCall q;
+    if (int e = sde_open(&q, c, sh, o, zs, nz, cd, ws, ws_bytes, stream)) return e;
+    GraphKey key = graph_key(9, q.r, cd);
+    key.add_struct(q.key).add(cond_interval).ptr(rng);
+    return upsample_run(q.r, use_graph, key, 0, cond_interval, zs, key_rots, key_trans, key_torsions, seqres, x_cond, x_cond_mask,
+                        start_rot, start_trans, *tb, atom14, [&](float* x) { return q.solve(x, nz); });
 }

@@ -30,13 +30,13 @@ template <bool POS, bool IPA, int kEmbTok>
 __global__ __launch_bounds__(256) void k_rk_embed(const EmbedParams p, const RkState st) {
     const float* const ops[kRkMaxK] = {st.nk > 0 ? st.k[0] : nullptr, st.nk > 1 ? st.k[1] : nullptr, st.nk > 2 ? st.k[2] : nullptr,
                                        st.nk > 3 ? st.k[3] : nullptr};
-    state_embed<POS, IPA, kEmbTok>(p, st.y, st.store, ops, [&](float y0, const float* k) { return rk_state(st, y0, k[0], k[1], k[2], k[3]); });
+    state_embed<POS, IPA, kEmbTok>(p, st.y, st.store, ops, [&](float y0, const float* k, long) { return rk_state(st, y0, k[0], k[1], k[2], k[3]); });
 }
 
 __global__ __launch_bounds__(256) void k_rk_update(const RkState st, long n) {
     const float* const ops[kRkMaxK] = {st.nk > 0 ? st.k[0] : nullptr, st.nk > 1 ? st.k[1] : nullptr, st.nk > 2 ? st.k[2] : nullptr,
                                        st.nk > 3 ? st.k[3] : nullptr};
-    state_update(st.y, ops, n, [&](float y0, const float* k) { return rk_state(st, y0, k[0], k[1], k[2], k[3]); });
+    state_update(st.y, ops, n, [&](float y0, const float* k, long) { return rk_state(st, y0, k[0], k[1], k[2], k[3]); });
 }
 
 void launch_rk_embed(const EmbedParams& p, const RkState& st, hipStream_t s) { MDG_LAUNCH_STATE_EMBED(k_rk_embed, p, st, s); }

@@ -582,6 +582,11 @@ struct SdeState {
     const float* v[2];             // velocities; null where the form reads none
     const float* xi;               // the noise of one step (B, T, L, D), or null
     float* y;                      // x (B, T, L, D)
+    // the generated noise (philox.h) in the buffer's place: with `rng` the noise-reading forms compute xi at the element's coordinates
+    const uint64_t* rng;           // device: {seed, sample_base, block_base, 0}, read inside the kernel; null: xi is read from the buffer
+    int step, block;               // counter words c2 and (added to block_base) c3
+    int b0;                        // the first sample of the launch within the call's batch (a view: set by its loop)
+    unsigned per_b;                // T L D: elements of one sample
 };
 void launch_sde_embed(const EmbedParams& p, const SdeState& st, hipStream_t s);
 void launch_sde_update(const SdeState& st, long n, hipStream_t s);

@@ -1,4 +1,4 @@
-// sde.inc -- included by api.hip after ode.inc: the SDE sampler (mdgen_sample_sde)
+// sde.inc -- included by api.hip after ode.inc: the SDE sampler (mdgen_sample_sde, mdgen_sample_sde_rng)
 // ---------------------------------------------------------------------------------------------
 // Euler-Maruyama and Heun on t = linspace(t0, t1, n_points), then a last step
 // ---------------------------------------------------------------------------------------------
@@ -20,7 +20,9 @@
 // never divides.  A plan with a non-finite coefficient that a state reads is refused (SBDM at sample_eps = 0 evaluates pi / (2 tan 0);
 // Heun on the Linear path without a last step reaches t = 1 where sigma = 0).
 // Orchestration as rk_body: ONE prepare() for all time rows, the states formed inside the embedding launches (k_sde_embed), views
-// one after the other on the caller's stream, nothing read back: the whole solve is one hipGraph.  The caller owns the noise.
+// one after the other on the caller's stream, nothing read back: the whole solve is one hipGraph.  The caller owns the noise: a staged
+// buffer (mdgen_sample_sde), or four seed words on the device from which the kernels generate it (philox.h: mdgen_sample_sde_rng and
+// the fused drivers mdgen_rollout_sde / mdgen_upsample_sde of drivers.inc).
 struct SdeCoef {
     float R, iV, D, G;
 };
@@ -173,15 +175,30 @@ static SdeState sde_state_of(const SdePlan& pl, int form, bool store, int r0, in
     return s;
 }
 
+// Where a solve's noise comes from: the caller's buffer (step i's at buf + i * stride), or -- rng: the device words {seed,
+// sample_base, block_base, 0} -- philox.h evaluated in the kernels at (element, sample, step, block_base + block)
+struct SdeNoise {
+    const float* buf;
+    long stride;
+    const uint64_t* rng;
+    int block;
+};
+// `s`, a noise-reading state, with step `step`'s noise
+static SdeState with_noise(SdeState s, const SdeNoise& nz, int step) {
+    if (nz.rng) { s.rng = nz.rng; s.step = step; s.block = nz.block; }
+    else s.xi = nz.buf + (long)step * nz.stride;
+    return s;
+}
+
 // the state the first launch after step i (0 <= i < S) forms: the step's result, for Heun with the next step's noise term where
 // there is a next step
-static SdeState sde_result_of(const mdgen_sde_opts& o, const SdePlan& pl, int i, float* x, float* const* v, const float* noise, long stride) {
+static SdeState sde_result_of(const mdgen_sde_opts& o, const SdePlan& pl, int i, float* x, float* const* v, const SdeNoise& nz) {
     const int S = o.n_points - 1;
     if (o.method == 1)
-        return sde_state_of(pl, kSdeEm, true, pl.row_of[i], -1, pl.row_of[i], pl.dt, x, v[0], nullptr, noise + (long)i * stride);
+        return with_noise(sde_state_of(pl, kSdeEm, true, pl.row_of[i], -1, pl.row_of[i], pl.dt, x, v[0], nullptr, nullptr), nz, i);
     const int r0 = pl.row_of[(size_t)i * 2], r1 = pl.row_of[(size_t)i * 2 + 1];
     if (i + 1 < S)
-        return sde_state_of(pl, kSdeHeunNoise, true, r0, r1, pl.row_of[(size_t)(i + 1) * 2], pl.dt, x, v[0], v[1], noise + (long)(i + 1) * stride);
+        return with_noise(sde_state_of(pl, kSdeHeunNoise, true, r0, r1, pl.row_of[(size_t)(i + 1) * 2], pl.dt, x, v[0], v[1], nullptr), nz, i + 1);
     return sde_state_of(pl, kSdeHeun, true, r0, r1, -1, pl.dt, x, v[0], v[1], nullptr);
 }
 static SdeState sde_last_of(const mdgen_sde_opts& o, const SdePlan& pl, float* x, float* const* v) {
@@ -189,9 +206,8 @@ static SdeState sde_last_of(const mdgen_sde_opts& o, const SdePlan& pl, float* x
     return sde_state_of(pl, form, true, pl.last_row, -1, -1, pl.h, x, v[0], nullptr, nullptr);
 }
 
-// the solve on a made run: x in place, v[0 .. 1] the velocities, step i's noise at noise + i * stride
-static int sde_body(const Run& r_in, const mdgen_sde_opts& o, const SdePlan& pl, int nv, float* x, float* const* v, const float* noise,
-                    long stride) {
+// the solve on a made run: x in place, v[0 .. 1] the velocities, the noise from `nz`
+static int sde_body(const Run& r_in, const mdgen_sde_opts& o, const SdePlan& pl, int nv, float* x, float* const* v, const SdeNoise& nz) {
     Run r = r_in;
     if (int e = ode_prepare(r, pl.rows.data(), (int)pl.rows.size(), largest_view_rows(r, nv))) return e;
     const long per_b = (long)r.T * r.L * r.D;
@@ -205,61 +221,141 @@ static int sde_body(const Run& r_in, const mdgen_sde_opts& o, const SdePlan& pl,
             for (int j = 0; j < 2; ++j)
                 if (st.v[j]) st.v[j] += off;
             if (st.xi) st.xi += off;
+            st.b0 = b0;
+            st.per_b = (unsigned)per_b;
             Run vs = vw;
             vs.sde = &st;
             return denoise_step(vs, row, x + off, out + off, 0, 0.f, nullptr);
         });
     };
+    auto update = [&](SdeState st) {   // the whole call's state in one launch
+        st.per_b = (unsigned)per_b;
+        return launch(r, "ode_sde_update", [&] { launch_sde_update(st, (long)r.N * r.D, r.s); });
+    };
     for (int i = 0; i < S; ++i) {
         // the first launch of step i forms the previous step's result (Heun: with this step's noise term) and stores it over x
-        const SdeState first = i > 0 ? sde_result_of(o, pl, i - 1, x, v, noise, stride)
+        const SdeState first = i > 0 ? sde_result_of(o, pl, i - 1, x, v, nz)
                                : o.method == 1 ? sde_state_of(pl, kSdeX, false, -1, -1, -1, pl.dt, x, nullptr, nullptr, nullptr)
-                                               : sde_state_of(pl, kSdeNoise, true, -1, -1, pl.row_of[0], pl.dt, x, nullptr, nullptr, noise);
+                                               : with_noise(sde_state_of(pl, kSdeNoise, true, -1, -1, pl.row_of[0], pl.dt, x, nullptr, nullptr, nullptr), nz, 0);
         if (int e = eval(first, pl.row_of[(size_t)i * pl.stages], v[0])) return e;
         if (o.method == 2) {   // the predictor xp: in registers only
             const SdeState xp = sde_state_of(pl, kSdeDrift, false, pl.row_of[(size_t)i * 2], -1, -1, pl.dt, x, v[0], nullptr, nullptr);
             if (int e = eval(xp, pl.row_of[(size_t)i * 2 + 1], v[1])) return e;
         }
     }
-    const SdeState res = sde_result_of(o, pl, S - 1, x, v, noise, stride);
-    if (o.last_step == 0) return launch(r, "ode_sde_update", [&] { launch_sde_update(res, (long)r.N * r.D, r.s); });
+    const SdeState res = sde_result_of(o, pl, S - 1, x, v, nz);
+    if (o.last_step == 0) return update(res);
     if (int e = eval(res, pl.last_row, v[0])) return e;
-    const SdeState last = sde_last_of(o, pl, x, v);
-    return launch(r, "ode_sde_update", [&] { launch_sde_update(last, (long)r.N * r.D, r.s); });
+    return update(sde_last_of(o, pl, x, v));
+}
+
+// What mdgen_sample_sde, mdgen_sample_sde_rng, mdgen_rollout_sde and mdgen_upsample_sde share once their own arguments are judged (as
+// RkCall, ode.inc): the plan, the made run with the call's conditioning bound, its launch views, the two velocity buffers behind
+// the network workspace and the options as they enter a graph key.  `state` is the buffer k_sde_update will see (16-byte accesses).
+// Every refusal comes before make_run, the first to touch the device.
+struct SdeCall {
+    mdgen_sde_opts o, key;
+    SdePlan pl;
+    Run r;
+    int nv;
+    float* v[2];
+    int solve(float* x, const SdeNoise& nz) const { return sde_body(r, o, pl, nv, x, v, nz); }
+};
+static int sde_open(SdeCall* q, mdgen_ctx* c, const mdgen_shape* sh, const mdgen_sde_opts* o, const float* state, const SdeNoise& nz,
+                    const mdgen_cond& cd, void* ws, size_t ws_bytes, void* stream) {
+    if (!sh) return fail(-1, "null argument");
+    if (int e = sde_plan(*o, &q->pl)) return e;
+    q->o = *o;
+    if (nz.rng) {
+        if (((uintptr_t)state & 15) != 0) return fail(-7, "x must be 16-byte aligned");
+        if (((uintptr_t)nz.rng & 7) != 0) return fail(-7, "rng must be 8-byte aligned");
+        // counter word c0 is the element's index within its sample
+        if (sh->T > 0 && sh->L > 0 && (uint64_t)sh->T * sh->L * (c ? c->D : 21) >= (1ull << 32))
+            return fail(-2, "T * L * D = %llu elements of one sample do not fit the generator's 32-bit element counter",
+                        (unsigned long long)sh->T * sh->L * (c ? c->D : 21));
+    } else {
+        if (((uintptr_t)state & 15) != 0 || ((uintptr_t)nz.buf & 15) != 0) return fail(-7, "x and noise must be 16-byte aligned");
+        // k_sde_update reads a step's noise 16 bytes at a time, and a state of B T L D floats ends on 16 bytes only for some shapes:
+        // the caller chooses the stride (as zs_block_stride of mdgen_rollout_rk)
+        const long n = (long)sh->B * sh->T * sh->L * (c ? c->D : 21);
+        if (nz.stride % 4 != 0) return fail(-7, "noise_step_stride must be a multiple of 4 floats (got %lld)", (long long)nz.stride);
+        if (nz.stride < n) return fail(-7, "noise_step_stride %lld is below one state of %ld floats", (long long)nz.stride, n);
+    }
+    mdgen_ws_layout lay;
+    if (int e = mdgen_workspace_layout(c, sh, (int)q->pl.rows.size(), 1, &lay)) return e;
+    const size_t sb = ode_state_bytes(c, sh), need = align256(lay.total_bytes) + 2 * sb + 256;
+    if (ws_bytes < need) return fail(-7, "workspace too small: %zu < %zu bytes (mdgen_sde_workspace_bytes)", ws_bytes, need);
+    q->r = Run{};
+    if (int e = make_run(&q->r, c, sh, (int)q->pl.rows.size(), 1, f32_path(c), ws, lay.total_bytes, stream)) return e;
+    bind_cond(q->r, cd);
+    q->r.no_embed_tail = true;
+    q->nv = c->opt_precision == 32 ? 1 : plan_views(sh->B, sh->T, sh->L, 1);
+    if (q->nv == 0) return fail(-2, "sample too large for one launch");
+    for (int j = 0; j < 2; ++j) q->v[j] = (float*)((unsigned char*)ws + align256(lay.total_bytes) + (size_t)j * sb);
+    mdgen_sde_opts& k = q->key;   // (field by field: the struct's padding does not reach the key)
+    std::memset(&k, 0, sizeof(k));
+    k.method = o->method; k.path = o->path; k.diffusion_form = o->diffusion_form; k.last_step = o->last_step; k.n_points = o->n_points;
+    k.diffusion_norm = o->diffusion_norm; k.last_step_size = o->last_step_size; k.sample_eps = o->sample_eps;
+    return 0;
 }
 
 extern "C" int32_t mdgen_sample_sde(mdgen_ctx* c, const mdgen_shape* sh, const mdgen_sde_opts* o, float* x, const float* noise,
                                     int64_t stride, const mdgen_cond* cond, void* ws, size_t ws_bytes, int32_t use_graph, void* stream) {
     if (!x || !noise || !o) return fail(-1, "null argument");
     if (int e = check_cond(cond)) return e;
-    if (!sh) return fail(-1, "null argument");
-    SdePlan pl;
-    if (int e = sde_plan(*o, &pl)) return e;
-    if (((uintptr_t)x & 15) != 0 || ((uintptr_t)noise & 15) != 0) return fail(-7, "x and noise must be 16-byte aligned");
-    // k_sde_update reads a step's noise 16 bytes at a time, and a state of B T L D floats ends on 16 bytes only for some shapes: the
-    // caller chooses the stride (as zs_block_stride of mdgen_rollout_rk)
-    const long state = (long)sh->B * sh->T * sh->L * (c ? c->D : 21);
-    if (stride % 4 != 0) return fail(-7, "noise_step_stride must be a multiple of 4 floats (got %lld)", (long long)stride);
-    if (stride < state) return fail(-7, "noise_step_stride %lld is below one state of %ld floats", (long long)stride, state);
-    mdgen_ws_layout lay;
-    if (int e = mdgen_workspace_layout(c, sh, (int)pl.rows.size(), 1, &lay)) return e;
-    const size_t sb = ode_state_bytes(c, sh), need = align256(lay.total_bytes) + 2 * sb + 256;
-    if (ws_bytes < need) return fail(-7, "workspace too small: %zu < %zu bytes (mdgen_sde_workspace_bytes)", ws_bytes, need);
-    Run r{};
-    if (int e = make_run(&r, c, sh, (int)pl.rows.size(), 1, f32_path(c), ws, lay.total_bytes, stream)) return e;
-    bind_cond(r, *cond);
-    r.no_embed_tail = true;
-    const int nv = c->opt_precision == 32 ? 1 : plan_views(sh->B, sh->T, sh->L, 1);
-    if (nv == 0) return fail(-2, "sample too large for one launch");
-    float* v[2];
-    for (int j = 0; j < 2; ++j) v[j] = (float*)((unsigned char*)ws + align256(lay.total_bytes) + (size_t)j * sb);
-    mdgen_sde_opts k{};   // (field by field: the struct's padding does not reach the key)
-    std::memset(&k, 0, sizeof(k));
-    k.method = o->method; k.path = o->path; k.diffusion_form = o->diffusion_form; k.last_step = o->last_step; k.n_points = o->n_points;
-    k.diffusion_norm = o->diffusion_norm; k.last_step_size = o->last_step_size; k.sample_eps = o->sample_eps;
-    GraphKey key = graph_key(6, r, *cond);
-    key.add_struct(k).add((uint64_t)stride).ptr(x).ptr(noise);   // (the body does not fork: no n_streams)
-    return run_or_replay(r, use_graph, key, [&]() { return sde_body(r, *o, pl, nv, x, v, noise, (long)stride); });
+    const SdeNoise nz{noise, (long)stride, nullptr, 0};
+    SdeCall q;
+    if (int e = sde_open(&q, c, sh, o, x, nz, *cond, ws, ws_bytes, stream)) return e;
+    GraphKey key = graph_key(6, q.r, *cond);
+    key.add_struct(q.key).add((uint64_t)stride).ptr(x).ptr(noise);   // (the body does not fork: no n_streams)
+    return run_or_replay(q.r, use_graph, key, [&]() { return q.solve(x, nz); });
+}
+
+// mdgen_sample_sde with the noise generated in the kernels: no buffer, no stride.  The seed words are read on the device, so the key
+// holds their address and a replay draws what they hold then.
+extern "C" int32_t mdgen_sample_sde_rng(mdgen_ctx* c, const mdgen_shape* sh, const mdgen_sde_opts* o, float* x, const uint64_t* rng,
+                                        const mdgen_cond* cond, void* ws, size_t ws_bytes, int32_t use_graph, void* stream) {
+    if (!x || !rng || !o) return fail(-1, "null argument");
+    if (int e = check_cond(cond)) return e;
+    const SdeNoise nz{nullptr, 0, rng, 0};
+    SdeCall q;
+    if (int e = sde_open(&q, c, sh, o, x, nz, *cond, ws, ws_bytes, stream)) return e;
+    GraphKey key = graph_key(7, q.r, *cond);
+    key.add_struct(q.key).ptr(x).ptr(rng);
+    return run_or_replay(q.r, use_graph, key, [&]() { return q.solve(x, nz); });
+}
+
+// Test hook: one step's generated noise, xi (B, T, L, D) to `out` -- k_sde_update's generator instantiation forming 0 + 1 * (xi * 1).
+extern "C" int32_t mdgen_debug_sde_noise(const mdgen_shape* sh, int32_t latent_dim, const uint64_t* rng, int32_t step, int32_t block,
+                                         float* out, void* stream) {
+    if (!sh || !rng || !out) return fail(-1, "null argument");
+    if (sh->B < 1 || sh->T < 1 || sh->L < 1 || latent_dim < 1) return fail(-2, "B, T, L, latent_dim must be >= 1");
+    if ((uint64_t)sh->T * sh->L * latent_dim >= (1ull << 32)) return fail(-2, "T * L * D does not fit the generator's 32-bit element counter");
+    if (((uintptr_t)out & 15) != 0 || ((uintptr_t)rng & 7) != 0) return fail(-7, "out must be 16-byte aligned, rng 8-byte aligned");
+    const long n = (long)sh->B * sh->T * sh->L * latent_dim;
+    SdeState st{};
+    st.form = kSdeNoise;
+    st.store = 1;
+    st.q = st.G = 1.f;
+    st.y = out;
+    st.rng = rng;
+    st.step = step;
+    st.block = block;
+    st.per_b = (unsigned)((long)sh->T * sh->L * latent_dim);
+    HIPCHK(hipMemsetAsync(out, 0, (size_t)n * sizeof(float), (hipStream_t)stream));
+    launch_sde_update(st, n, (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
+
+// Host-only test hook: philox.h's Philox4x32-10 compiled for the host.  ctr[4], key[2] -> out[4].
+extern "C" int32_t mdgen_debug_philox(const uint32_t* ctr, const uint32_t* key, uint32_t* out) {
+    if (!ctr || !key || !out) return fail(-1, "null argument");
+    const uint32_t c[4] = {ctr[0], ctr[1], ctr[2], ctr[3]}, k[2] = {key[0], key[1]};
+    uint32_t w[4];
+    philox4x32_10(c, k, w);
+    std::memcpy(out, w, sizeof(w));
+    return 0;
 }
 
 // Host-only test hook: the plan of mdgen_sample_sde for `o`, as fp32 bits.  row_bits[cap_rows], coef_bits[cap_rows][4] (R, iV, D, G per
@@ -285,10 +381,11 @@ extern "C" int32_t mdgen_debug_sde_plan(const mdgen_sde_opts* o, uint32_t* row_b
 // Test hook: k_sde_embed alone on one state of the solve `o` describes.  state: an SdeForm (kernels.h) of step `step` -- 0 x, 1 x +
 // noise term, 2 the Euler-Maruyama step, 3 Heun's predictor, 4 Heun's result, 5 Heun's result + the noise term of step + 1 -- or a last
 // step at t1: 6 Tweedie, 7 Euler, 8 Mean.  x (B, T, L, D) is overwritten by every state but 0 and 3; v0, v1, xi: what the state reads
-// (xi: ONE step's noise).
-extern "C" int32_t mdgen_debug_sde_stage(mdgen_ctx* c, const mdgen_shape* sh, const mdgen_sde_opts* o, int32_t state, int32_t step, float* x,
-                                         const float* v0, const float* v1, const float* xi, const float* x_cond, const int64_t* x_cond_mask,
-                                         const float* ipa_out, float* h, void* stream) {
+// (xi: ONE step's noise); with `rng` the noise-reading states generate theirs: the noise of step `step` (states 1, 2) or `step` + 1
+// (state 5) of block `block`.
+static int sde_stage(mdgen_ctx* c, const mdgen_shape* sh, const mdgen_sde_opts* o, int state, int step, float* x, const float* v0,
+                     const float* v1, const float* xi, const uint64_t* rng, int block, const float* x_cond, const int64_t* x_cond_mask,
+                     const float* ipa_out, float* h, void* stream) {
     if (!x || !x_cond || !x_cond_mask || !h || !o) return fail(-1, "null argument");
     SdePlan pl;
     if (int e = sde_plan(*o, &pl)) return e;
@@ -301,20 +398,34 @@ extern "C" int32_t mdgen_debug_sde_stage(mdgen_ctx* c, const mdgen_shape* sh, co
     if (int e = check_shape(c, sh, 1)) return e;
     if (!c->finalized) return fail(-6, "context not finalized (mdgen_ctx_finalize)");
     const bool reads_v0 = state >= 2, reads_v1 = state == 4 || state == 5, reads_xi = state == 1 || state == 2 || state == 5;
-    if ((reads_v0 && !v0) || (reads_v1 && !v1) || (reads_xi && !xi)) return fail(-1, "the state reads an operand that is null");
+    if ((reads_v0 && !v0) || (reads_v1 && !v1) || (reads_xi && !xi && !rng)) return fail(-1, "the state reads an operand that is null");
     float* vv[2] = {const_cast<float*>(v0), const_cast<float*>(v1)};
     const int r0 = pl.row_of[(size_t)step * pl.stages], r1 = pl.stages == 2 ? pl.row_of[(size_t)step * 2 + 1] : -1;
+    const SdeNoise nz{xi, 0, rng, block};   // (stride 0: xi is the one step's noise whichever step the state names)
     SdeState st;
     switch (state) {
     case 0: st = sde_state_of(pl, kSdeX, false, -1, -1, -1, pl.dt, x, nullptr, nullptr, nullptr); break;
-    case 1: st = sde_state_of(pl, kSdeNoise, true, -1, -1, r0, pl.dt, x, nullptr, nullptr, xi); break;
-    case 2: st = sde_state_of(pl, kSdeEm, true, r0, -1, r0, pl.dt, x, v0, nullptr, xi); break;
+    case 1: st = with_noise(sde_state_of(pl, kSdeNoise, true, -1, -1, r0, pl.dt, x, nullptr, nullptr, nullptr), nz, step); break;
+    case 2: st = with_noise(sde_state_of(pl, kSdeEm, true, r0, -1, r0, pl.dt, x, v0, nullptr, nullptr), nz, step); break;
     case 3: st = sde_state_of(pl, kSdeDrift, false, r0, -1, -1, pl.dt, x, v0, nullptr, nullptr); break;
     case 4: st = sde_state_of(pl, kSdeHeun, true, r0, r1, -1, pl.dt, x, v0, v1, nullptr); break;
-    case 5: st = sde_state_of(pl, kSdeHeunNoise, true, r0, r1, pl.row_of[(size_t)(step + 1) * 2], pl.dt, x, v0, v1, xi); break;
+    case 5: st = with_noise(sde_state_of(pl, kSdeHeunNoise, true, r0, r1, pl.row_of[(size_t)(step + 1) * 2], pl.dt, x, v0, v1, nullptr), nz, step + 1); break;
     default: st = sde_last_of(*o, pl, x, vv); break;
     }
+    st.per_b = (unsigned)((long)sh->T * sh->L * c->D);
     launch_sde_embed(embed_params(c, *sh, x, x_cond, x_cond_mask, ipa_out, h), st, (hipStream_t)stream);
     LAUNCHCHK();
     return 0;
+}
+extern "C" int32_t mdgen_debug_sde_stage(mdgen_ctx* c, const mdgen_shape* sh, const mdgen_sde_opts* o, int32_t state, int32_t step, float* x,
+                                         const float* v0, const float* v1, const float* xi, const float* x_cond, const int64_t* x_cond_mask,
+                                         const float* ipa_out, float* h, void* stream) {
+    return sde_stage(c, sh, o, state, step, x, v0, v1, xi, nullptr, 0, x_cond, x_cond_mask, ipa_out, h, stream);
+}
+extern "C" int32_t mdgen_debug_sde_stage_rng(mdgen_ctx* c, const mdgen_shape* sh, const mdgen_sde_opts* o, int32_t state, int32_t step,
+                                             int32_t block, float* x, const float* v0, const float* v1, const uint64_t* rng,
+                                             const float* x_cond, const int64_t* x_cond_mask, const float* ipa_out, float* h, void* stream) {
+    if (!rng) return fail(-1, "null argument");
+    if (((uintptr_t)rng & 7) != 0) return fail(-7, "rng must be 8-byte aligned");
+    return sde_stage(c, sh, o, state, step, x, v0, v1, nullptr, rng, block, x_cond, x_cond_mask, ipa_out, h, stream);
 }

@@ -4,8 +4,9 @@
 //                 the token's D values from y and up to NOPS read-only operands (velocities, noise) with the caller's `value`,
 //                 stages them in LDS and embeds them; a storing state is also written over y.
 //   state_update  the same arithmetic without the embedding, elementwise over n values.
-// `value(y, o)` is called with the element of y and of every operand (0 where `ops[j]` is null); what it computes, and in which
-// order it rounds, belongs to the caller -- this file holds no arithmetic on the state.
+// `value(y, o, e)` is called with the element of y and of every operand (0 where `ops[j]` is null) and the element's flat index e
+// in y (k_sde.hip generates its noise there; k_rk.hip ignores it); what it computes, and in which order it rounds, belongs to the
+// caller -- this file holds no arithmetic on the state.
 #pragma once
 #include "kernels.h"
 
@@ -57,7 +58,7 @@ __device__ __forceinline__ void state_embed(const EmbedParams& p, float* y, int 
             if (i >= kEmbTok * 28) break;
             const int tk = i / 28, d = i % 28;
             const bool ok = tok0 + tk < p.N && d < p.D;
-            const float v = value(a[it], kv[it]);
+            const float v = value(a[it], kv[it], (tok0 + tk) * p.D + d);   // (an index past the state: its value is discarded below)
             xs[tk * kEmbLd + d] = ok ? v : 0.f;
             cs[tk * kEmbLd + d] = ok ? b[it] : 0.f;
             if (ok && b[it] != 0.f) atomicOr(&ms[tk], 2);
@@ -162,14 +163,15 @@ __device__ __forceinline__ void state_update(float* y, const float* const (&ops)
         float ox[NOPS], oy[NOPS], oz[NOPS], ow[NOPS];
 #pragma unroll
         for (int j = 0; j < NOPS; ++j) { ox[j] = k[j].x; oy[j] = k[j].y; oz[j] = k[j].z; ow[j] = k[j].w; }
-        reinterpret_cast<float4*>(y)[i] = make_float4(value(a.x, ox), value(a.y, oy), value(a.z, oz), value(a.w, ow));
+        const long e = i << 2;
+        reinterpret_cast<float4*>(y)[i] = make_float4(value(a.x, ox, e), value(a.y, oy, e + 1), value(a.z, oz, e + 2), value(a.w, ow, e + 3));
     }
     const long r = (n4 << 2) + i;
     if (i < (n & 3)) {
         float k[NOPS];
 #pragma unroll
         for (int j = 0; j < NOPS; ++j) k[j] = ops[j] ? ops[j][r] : 0.f;
-        y[r] = value(y[r], k);
+        y[r] = value(y[r], k, r);
     }
 }
 

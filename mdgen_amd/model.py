@@ -154,6 +154,12 @@ class LatentMDGenModel:
         return rep
 
     # ---- workspace --------------------------------------------------------------------------
+    def graph_count(self) -> int:
+        """`mdgen_debug_graph_count`: the captured hipGraphs the context holds."""
+        n = C.c_int32()
+        check(lib.mdgen_debug_graph_count(self._ctx, C.byref(n)))
+        return n.value
+
     def workspace_layout(self, B, T, L_, S, t_shared):
         lay = L.WsLayout()
         sh = L.Shape(B, T, L_)
@@ -362,7 +368,7 @@ class LatentMDGenModel:
 
     # ---- SDE: Euler-Maruyama / Heun --------------------------------------------------------------
     def sample_sde(self, zs, opts, mask=None, start_frames=None, end_frames=None, x_cond=None, x_cond_mask=None, aatype=None,
-                   noise=None, use_graph: bool = True, rel_quats=None, noise_step_stride=None):
+                   noise=None, use_graph: bool = True, rel_quats=None, noise_step_stride=None, rng=None):
         """`mdgen_sample_sde`: the reference's `Sampler.sample_sde` (transport.py:295-406) with `opts` = `_lib.sde_opts(
         sampling_method, path_type, diffusion_form, diffusion_norm, last_step, last_step_size, num_steps, sample_eps)`:
         n_points - 1 Euler-Maruyama or Heun steps on linspace(t0, t1, n_points), then the last step; n_points - 1 or
@@ -371,13 +377,24 @@ class LatentMDGenModel:
         torch.randn from the device generator, so the same torch.manual_seed gives the same sample.  The noise is staged in a
         persistent buffer of (n_points - 1) x state bytes (stable pointers: the graph is replayed with new noise in it) -- at
         250 points and B 16 x T 1000 x L 4 that is 1.3 GB.  `noise_step_stride` (floats, a multiple of 4, at least one state;
-        default: one state rounded up to 4) is the distance between two steps' noise in that buffer.  Returns the sample."""
+        default: one state rounded up to 4) is the distance between two steps' noise in that buffer.
+        `rng`: a device int64 tensor of four words {seed, sample_base, block_base, 0} (`_lib.rng_words`) in the noise's place
+        (`mdgen_sample_sde_rng`): the kernels generate the noise from it (Philox, include/mdgen_amd.h) and nothing is staged; the
+        words are read on the device, so write them on the current stream before the call and keep the tensor for replays.
+        Returns the sample."""
         B, T, L_, *frames = self._sampler_inputs(zs, mask, start_frames, end_frames, x_cond, x_cond_mask, aatype)
         D, S = zs.shape[-1], opts.n_points - 1
         sh = L.Shape(B, T, L_)
-        nbytes = C.c_size_t()
-        check(lib.mdgen_sde_workspace_bytes(self._ctx, C.byref(sh), C.byref(opts), C.byref(nbytes)))   # (refuses bad options first)
-        ws = self._sized_workspace(("sde", B, T, L_), nbytes.value)
+        ws = self._sde_workspace(opts, B, T, L_)
+        if rng is not None:
+            if noise is not None or noise_step_stride is not None:
+                raise L.MdgenError("rng generates the noise in the kernels: it goes without noise / noise_step_stride")
+            self._check_rng(rng)
+            x, cond = self._stage_cond(zs, mask, *frames, x_cond, x_cond_mask, aatype, rel_quats)
+            with self._call_stream(use_graph) as stream:
+                check(lib.mdgen_sample_sde_rng(self._ctx, C.byref(sh), C.byref(opts), ptr(x), ptr(rng), C.byref(cond), ptr(ws), ws.numel(),
+                                               int(use_graph), stream))
+            return x.clone()
         state = B * T * L_ * D
         stride = (state + 3) // 4 * 4 if noise_step_stride is None else int(noise_step_stride)
         if stride < state:
@@ -394,6 +411,19 @@ class LatentMDGenModel:
             check(lib.mdgen_sample_sde(self._ctx, C.byref(sh), C.byref(opts), ptr(x), ptr(buf), stride, C.byref(cond), ptr(ws), ws.numel(),
                                        int(use_graph), stream))
         return x.clone()
+
+    def _sde_workspace(self, opts, B, T, L_):
+        """The workspace of an SDE call of this shape (`mdgen_sde_workspace_bytes` refuses bad options first): one for sample_sde
+        and the drivers."""
+        sh = L.Shape(B, T, L_)
+        nbytes = C.c_size_t()
+        check(lib.mdgen_sde_workspace_bytes(self._ctx, C.byref(sh), C.byref(opts), C.byref(nbytes)))
+        return self._sized_workspace(("sde", B, T, L_), nbytes.value)
+
+    def _check_rng(self, rng):
+        require_cuda(rng)
+        if rng.dtype != torch.int64 or tuple(rng.shape) != (4,) or not rng.is_contiguous():
+            raise L.MdgenError("rng must be a contiguous device int64 tensor of four words (_lib.rng_words)")
 
     # ---- multi-block rollout -----------------------------------------------------------------
     def rollout_euler(self, zs, num_steps: int, mask, cond_rots, cond_trans, cond_torsions, seqres, tables,
@@ -457,6 +487,15 @@ class LatentMDGenModel:
         return self._rollout("rollout_rk", lib.mdgen_rollout_rk, lambda *shape: self._rk_call(method, num_steps, *shape), True,
                              zs, mask, cond_rots, cond_trans, cond_torsions, seqres, tables, use_graph)
 
+    def rollout_sde(self, zs, opts, rng, mask, cond_rots, cond_trans, cond_torsions, seqres, tables, use_graph: bool = True):
+        """`mdgen_rollout_sde`: `rollout_rk` with the SDE solve of `sample_sde(..., rng=rng)` per block -- block k draws its noise
+        with the counter word block_base + k -- still one call and one hipGraph, and no noise is staged.  Arguments and return
+        values as `rollout_euler`."""
+        self._check_rng(rng)
+        return self._rollout("rollout_rk", lib.mdgen_rollout_sde,
+                             lambda *shape: ((C.byref(opts), ptr(rng)), self._sde_workspace(opts, *shape)), True,
+                             zs, mask, cond_rots, cond_trans, cond_torsions, seqres, tables, use_graph)
+
     # ---- trajectory upsampling ---------------------------------------------------------------
     def _upsample(self, fn, call, zs, cond_interval, mask, key_rots, key_trans, key_torsions, seqres, tables, use_graph):
         """The body of upsample_euler / upsample_rk: the checks of an upsampling call, its staging set (one per shape and
@@ -511,4 +550,12 @@ class LatentMDGenModel:
         steps (as `sample_rk`): key-frame conditioning -> solve -> atom14 in one call (one hipGraph).  Arguments and return
         values as `upsample_euler`."""
         return self._upsample(lib.mdgen_upsample_rk, lambda *shape: self._rk_call(method, num_steps, *shape),
+                              zs, cond_interval, mask, key_rots, key_trans, key_torsions, seqres, tables, use_graph)
+
+    def upsample_sde(self, zs, opts, rng, cond_interval: int, mask, key_rots, key_trans, key_torsions, seqres, tables,
+                     use_graph: bool = True):
+        """`mdgen_upsample_sde`: `upsample_rk` with the SDE solve of `sample_sde(..., rng=rng)`: key-frame conditioning -> solve ->
+        atom14 in one call (one hipGraph), no noise staged.  Arguments and return values as `upsample_euler`."""
+        self._check_rng(rng)
+        return self._upsample(lib.mdgen_upsample_sde, lambda *shape: ((C.byref(opts), ptr(rng)), self._sde_workspace(opts, *shape)),
                               zs, cond_interval, mask, key_rots, key_trans, key_torsions, seqres, tables, use_graph)

@@ -111,9 +111,13 @@ def make_group_batch(names, arrs, seqres, device):
     return collate([get_batch(arrs[n], seqres[n], device) for n in names])
 
 
-def sample_group(model, batch, args):
-    """`num_rollouts` chained blocks for one batch; returns atom14 [B, R*T, L, 14, 3]."""
+def sample_group(model, batch, args, sample_base=0):
+    """`num_rollouts` chained blocks for one batch; returns atom14 [B, R*T, L, 14, 3].  `sample_base`: the index of the batch's
+    first peptide within the split -- with --sde_seed the sample index of its generated noise, so that a peptide draws the same
+    noise whichever rank or chunk samples it."""
     kw = solver_kwargs(args)   # (no solver named: num_steps alone -- a model's rollout() need not know the other keywords)
+    if "rng_seed" in kw:
+        kw["rng_sample_base"] = sample_base
     if hasattr(model, "rollout") and not getattr(args, "per_block", False):
         atom14 = model.rollout(batch, args.num_frames, args.num_rollouts, **kw)
         if kw.get("sampling_method") == "dopri5":
@@ -122,7 +126,9 @@ def sample_group(model, batch, args):
         return atom14
     out = []
     num_steps = kw.pop("num_steps")
-    for _ in range(args.num_rollouts):   # --per_block: one inference() call per block from Python, whatever the solver
+    for b in range(args.num_rollouts):   # --per_block: one inference() call per block from Python, whatever the solver
+        if "rng_seed" in kw:
+            kw["rng_block_base"] = b
         atom14, batch = rollout(model, batch, args.num_frames, num_steps, **kw)
         out.append(atom14)
     return torch.cat(out, 1)
@@ -165,6 +171,7 @@ def run(args, model, device, names_seqres, rank=0, world=1, batch_fn=make_group_
         require_xtc_writer()
     names = select_names(list(names_seqres), args.pdb_id, args.chunk_idx, args.n_chunks, rank, world)
     seqres = {n: names_seqres[n] for n in names}
+    split_index = {n: i for i, n in enumerate(names_seqres)}
     os.makedirs(args.out_dir, exist_ok=True)
     total_frames, total_s = 0, 0.0
     if dist is not None:
@@ -174,7 +181,8 @@ def run(args, model, device, names_seqres, rank=0, world=1, batch_fn=make_group_
         batch = batch_fn(group, arrs, seqres, device)
         sync()
         start = time.time()
-        all_atom14 = sample_group(model, batch, args)
+        all_atom14 = sample_group(model, batch, args, **({} if getattr(args, "sde_seed", None) is None
+                                                         else {"sample_base": split_index[group[0]]}))
         sync()
         dur = time.time() - start
         nfr = len(group) * args.num_rollouts * args.num_frames

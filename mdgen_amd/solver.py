@@ -29,6 +29,7 @@ class SolverChoice:
     atol: float
     rtol: float
     sde_opts: Any = None       # the checked `_lib.SdeOpts` of kind "sde"
+    rng_seed: Optional[int] = None   # kind "sde": the kernels generate the noise from this seed (None: staged noise)
 
 
 def sde_opts(sampling_method, num_steps, sde, path_type):
@@ -48,7 +49,7 @@ def sde_opts(sampling_method, num_steps, sde, path_type):
 
 
 def resolve_solver(checkpoint_method, sampling_method=None, num_steps=None, atol=1e-6, rtol=1e-3, sde=None, path_type="GVP",
-                   noise=None) -> SolverChoice:
+                   noise=None, rng_seed=None, rng_sample_base=0, rng_block_base=0) -> SolverChoice:
     """The solver of one call.  `checkpoint_method`: the checkpoint's `args.sampling_method`; the rest as `inference()` takes them.
     The reference samples with the checkpoint's method (argparse default 'dopri5', parsing.py:102) on the solver's own 50-point
     grid (wrapper.py:441): without an explicit choice (`sampling_method` / `num_steps`) a non-Euler checkpoint is refused instead of
@@ -67,12 +68,22 @@ def resolve_solver(checkpoint_method, sampling_method=None, num_steps=None, atol
                          "to sample with fixed-grid Euler")
     if sampling_method not in SDE_METHODS and (sde is not None or noise is not None):
         raise MdgenError("sde / noise are options of sampling_method='sde' | 'sde_heun'")
+    if rng_seed is None and (rng_sample_base or rng_block_base):
+        raise MdgenError("rng_sample_base / rng_block_base are indices of the generated noise: they go with rng_seed")
+    if rng_seed is not None:
+        if sampling_method not in SDE_METHODS:
+            raise MdgenError("rng_seed is an option of sampling_method='sde' | 'sde_heun'")
+        if noise is not None:
+            raise MdgenError("rng_seed generates the noise in the kernels; noise supplies it (pass one or the other)")
+        rng_seed = int(rng_seed)
+        if int(rng_sample_base) < 0 or int(rng_block_base) < 0:
+            raise MdgenError("rng_sample_base and rng_block_base must be >= 0")
     method = sampling_method or "euler"
     if method == "dopri5":
         return SolverChoice("dopri5", method, None, atol, rtol)
     if method in SDE_METHODS:
         opts = sde_opts(method, num_steps, sde, path_type)
-        return SolverChoice("sde", method, opts.n_points - 1, atol, rtol, opts)
+        return SolverChoice("sde", method, opts.n_points - 1, atol, rtol, opts, rng_seed)
     default = RK_DEFAULT_STEPS[method] if method in RK_METHODS else EULER_DEFAULT_STEPS
     return SolverChoice("rk" if method in RK_METHODS else "euler", method, default if num_steps is None else int(num_steps), atol, rtol)
 
@@ -102,18 +113,23 @@ def add_solver_arguments(p, per="call"):
                    help="sde / sde_heun: the deterministic last step (default Mean)")
     p.add_argument("--last_step_size", type=float, default=None, help="sde / sde_heun: the last step's size (default 0.04)")
     p.add_argument("--sample_eps", type=float, default=None, help="sde / sde_heun: the interval's margin (default 0)")
+    p.add_argument("--sde_seed", type=int, default=None,
+                   help="sde / sde_heun: generate the noise inside the kernels from this seed (Philox; no staged noise buffer, "
+                        "rollouts and upsampling in one graph; a peptide's noise does not depend on the rank that samples it)")
 
 
 def sde_kwargs(args):
-    """{} or {"sde": {...}} from the SDE options; they go with sde / sde_heun only (else: SystemExit with the message, in all three
-    command lines)."""
+    """{} or {"sde": {...}} (with "rng_seed" for --sde_seed) from the SDE options; they go with sde / sde_heun only (else: SystemExit
+    with the message, in all three command lines)."""
     given = {k: getattr(args, k, None) for k in _SDE_OPTIONS}
     given = {k: (None if k == "last_step" and v == "none" else v) for k, v in given.items() if v is not None}
+    seed = getattr(args, "sde_seed", None)
     if getattr(args, "sampling_method", None) not in SDE_METHODS:
-        if given:
-            _exit("--" + ", --".join(given) + ": options of --sampling_method sde / sde_heun")
+        named = list(given) + (["sde_seed"] if seed is not None else [])
+        if named:
+            _exit("--" + ", --".join(named) + ": options of --sampling_method sde / sde_heun")
         return {}
-    return {"sde": given}
+    return {"sde": given, **({} if seed is None else {"rng_seed": seed})}
 
 
 def solver_kwargs(args, error=_exit):

@@ -82,6 +82,7 @@ def run(args, model, device, names_seqres, rank=0, world=1):
     names = select_names(list(names_seqres), args.pdb_id, args.chunk_idx, args.n_chunks, rank, world)
     os.makedirs(args.out_dir, exist_ok=True)
     done = []
+    split_index = {n: i for i, n in enumerate(names_seqres)}
     for name in names:
         arr = np.lib.format.open_memmap(f"{args.data_dir}/{name}{args.suffix}.npy", "r")
         seq = names_seqres[name]
@@ -89,6 +90,8 @@ def run(args, model, device, names_seqres, rank=0, world=1):
         batch = collate([one] * args.batch_size)
         aat = np.array([restype_order[c] for c in seq])
         for i in range(args.num_batches):
+            if "rng_seed" in kw:   # --sde_seed: path idx of the peptide at index p of the split draws at (sample idx, block p),
+                kw.update(rng_sample_base=i * args.batch_size, rng_block_base=split_index[name])   # whichever rank samples it
             atom14s, _ = model.inference(batch, **kw)
             if kw.get("sampling_method") == "dopri5":
                 st = model.last_stats

@@ -237,8 +237,10 @@ class Sampler:
         num_steps), then `last_step` ("Mean", "Tweedie", "Euler" or None) at t1.  The default SBDM diffusion needs a transport
         with sample_eps > 0 (`create_transport(..., sample_eps=1e-3)`): at 0 the plan is refused, as the reference's run ends in
         NaN.  Build-specific keywords of fn: `noise` ((num_steps - 1, *init.shape) standard normals; default: drawn with
-        torch.randn on init's device) and `use_graph`.  The returned tensor holds only the final state, shape [1, *init.shape],
-        as `sample_ode` returns."""
+        torch.randn on init's device), `use_graph`, and -- in `noise`'s place -- `rng_seed` [, `rng_sample_base`, `rng_block_base`]: the
+        Philox noise of `mdgen_sample_sde_rng` (include/mdgen_amd.h), generated in the kernels for the library's model and by
+        `mdgen_amd.philox.sde_noise`, the numpy restatement of the same stream, for any other callable (init: (B, T, L, D)).  The
+        returned tensor holds only the final state, shape [1, *init.shape], as `sample_ode` returns."""
         from . import _lib as L
         opts = L.sde_opts(sampling_method, self.transport.path_type, diffusion_form, diffusion_norm, last_step, last_step_size,
                           num_steps, self.transport.sample_eps)
@@ -246,10 +248,21 @@ class Sampler:
 
         def _sample(init, model_fn, **model_kwargs):
             noise = model_kwargs.pop("noise", None)   # (`model_kwargs` is this call's own dict)
+            seed = model_kwargs.pop("rng_seed", None)
+            bases = model_kwargs.pop("rng_sample_base", 0), model_kwargs.pop("rng_block_base", 0)
+            if seed is not None and noise is not None:
+                raise L.MdgenError("rng_seed generates the noise; noise supplies it (pass one or the other)")
             owner, kw, use_graph, model_kwargs = owning_model(model_fn, model_kwargs)
             if owner is not None:
-                return owner.sample_sde(init, opts, noise=noise, use_graph=use_graph, **kw)[None]
+                rng = None if seed is None else owner._staged(("sde_rng",), dict(rng=((4,), torch.int64)),
+                                                              dict(rng=L.rng_words(seed, *bases)))["rng"]
+                return owner.sample_sde(init, opts, noise=noise, use_graph=use_graph, rng=rng, **kw)[None]
             # generic drift (any callable): the same formulas in a host loop, in init's dtype, on the library's grid and coefficients
+            if seed is not None:
+                from .philox import sde_noise
+                S = opts.n_points - 1
+                noise = torch.stack([torch.from_numpy(sde_noise(tuple(init.shape), seed, i, bases[1], bases[0])) for i in range(S)])
+                noise = noise.to(device=init.device, dtype=init.dtype)
             if noise is None:
                 noise = torch.randn((opts.n_points - 1,) + tuple(init.shape), dtype=init.dtype, device=init.device)
             ones = torch.ones(init.shape[0], dtype=init.dtype, device=init.device)

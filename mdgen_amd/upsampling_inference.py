@@ -64,13 +64,17 @@ def key_frame_windows(arr, seqres_str, num_frames, cond_interval, device):
             "mask": torch.ones(n_windows, L_, device=device)}
 
 
-def upsample_name(model, windows, args):
-    """All windows of one name, `batch_size` at a time -> atom14 (n_windows * T, L, 14, 3)."""
+def upsample_name(model, windows, args, name_index=0):
+    """All windows of one name, `batch_size` at a time -> atom14 (n_windows * T, L, 14, 3).  `name_index`: the name's index within
+    the split; with --sde_seed window i draws its generated noise at (sample i, block name_index), whichever rank and batch size
+    sample it."""
     W = windows["trans"].shape[0]
     kw = solver_kwargs(args)
     out = []
     for i in range(0, W, max(1, args.batch_size)):
         kb = {k: v[i:i + args.batch_size] for k, v in windows.items()}
+        if "rng_seed" in kw:
+            kw.update(rng_sample_base=i, rng_block_base=name_index)
         atom14, _ = model.upsample(kb, **kw)
         if kw.get("sampling_method") == "dopri5":
             st = model.last_stats
@@ -93,6 +97,7 @@ def run(args, model, device, names_seqres, rank=0, world=1, sync=None):
     names = select_names(list(names_seqres), args.pdb_id, 0, 1, rank, world)
     os.makedirs(args.out_dir, exist_ok=True)
     done, total_frames, total_s = [], 0, 0.0
+    split_index = {n: i for i, n in enumerate(names_seqres)}
     for name in names:
         arr = np.lib.format.open_memmap(f"{args.data_dir}/{name}{args.suffix}.npy", "r")
         windows = key_frame_windows(arr, names_seqres[name], T, c, device)
@@ -101,7 +106,8 @@ def run(args, model, device, names_seqres, rank=0, world=1, sync=None):
             continue
         sync()
         start = time.time()
-        atom14 = upsample_name(model, windows, args)
+        atom14 = upsample_name(model, windows, args, **({} if getattr(args, "sde_seed", None) is None
+                                                        else {"name_index": split_index[name]}))
         sync()
         dur = time.time() - start
         nfr = atom14.shape[0]

@@ -160,16 +160,26 @@ class NewMDGenWrapper:
                                              mask=prep["loss_mask"], model_kwargs=prep["model_kwargs"], t=t, x0=x0)
         return out["loss"], out
 
-    def _solver(self, sampling_method, num_steps, atol, rtol, sde, noise=None):
+    def _solver(self, sampling_method, num_steps, atol, rtol, sde, noise=None, rng_seed=None, rng_sample_base=0, rng_block_base=0):
         """The call's `solver.SolverChoice` (every refusal about solver arguments is `resolve_solver`'s)."""
         return resolve_solver(getattr(self.args, "sampling_method", "euler"), sampling_method, num_steps, atol, rtol, sde,
-                              getattr(self.args, "path_type", "GVP"), noise)
+                              getattr(self.args, "path_type", "GVP"), noise, rng_seed, rng_sample_base, rng_block_base)
+
+    def _rng(self, choice, sample_base, block_base):
+        """The wrapper's four device words {seed, sample_base, block_base, 0} (`mdgen_sample_sde_rng`), written on the current
+        stream for this call; None without `rng_seed`.  One buffer for every call: a captured graph reads it at replay."""
+        if choice.rng_seed is None:
+            return None
+        if getattr(self, "_rng_words", None) is None:
+            self._rng_words = torch.zeros(4, dtype=torch.int64, device=self.device)
+        self._rng_words.copy_(L.rng_words(choice.rng_seed, sample_base, block_base))
+        return self._rng_words
 
     def _sde_opts(self, sampling_method, num_steps, sde):
         return sde_opts(sampling_method, num_steps, sde, self.args.path_type)
 
     def inference(self, batch, zs=None, num_steps=None, use_graph=True, rel_quats=None, sampling_method=None, atol=1e-6,
-                  rtol=1e-3, sde=None, noise=None):
+                  rtol=1e-3, sde=None, noise=None, rng_seed=None, rng_sample_base=0, rng_block_base=0):
         """wrapper.py:405-484.  Extra keywords (defaults reproduce the reference): `zs` explicit noise
         (reference: device randn, wrapper.py:439), `num_steps` Euler steps S (reference: 50 grid points = 49
         steps, wrapper.py:441-442 / transport.py:412), `rel_quats` (two-sided models): the relative-frame 7-vectors
@@ -183,11 +193,16 @@ class NewMDGenWrapper:
         (`LatentMDGenModel.sample_sde`, one hipGraph): `num_steps` stochastic steps S (default 49) on S + 1 grid points, then the
         last step; `sde`: a dict over SDE_DEFAULTS (diffusion_form "sigma", diffusion_norm 1, last_step "Mean", last_step_size
         0.04, sample_eps 0); `noise`: optional (S, B, T, L, D) standard normals, default a device randn drawn after `zs`.
+        `rng_seed` (sde / sde_heun, never with `noise`): the kernels generate the noise from this 64-bit seed with Philox4x32-10
+        at each element's coordinates (`mdgen_sample_sde_rng`, include/mdgen_amd.h) -- no (S, B, T, L, D) buffer exists, and the
+        noise of sample b is that of sample index `rng_sample_base` + b, of block index `rng_block_base`: whichever batch a
+        sample travels in, the same indices give it the same noise.
         The solver arguments are judged by `solver.resolve_solver`, before the batch is touched."""
-        choice = self._solver(sampling_method, num_steps, atol, rtol, sde, noise)
-        return self._inference(batch, choice, zs=zs, use_graph=use_graph, rel_quats=rel_quats, noise=noise)
+        choice = self._solver(sampling_method, num_steps, atol, rtol, sde, noise, rng_seed, rng_sample_base, rng_block_base)
+        return self._inference(batch, choice, zs=zs, use_graph=use_graph, rel_quats=rel_quats, noise=noise,
+                               rng=self._rng(choice, rng_sample_base, rng_block_base))
 
-    def _inference(self, batch, choice, zs=None, use_graph=True, rel_quats=None, noise=None):
+    def _inference(self, batch, choice, zs=None, use_graph=True, rel_quats=None, noise=None, rng=None):
         """`inference()` with its solver resolved."""
         prep = self.prep_batch(batch)
         rigids = prep["rigids"]
@@ -204,7 +219,7 @@ class NewMDGenWrapper:
         if choice.kind == "dopri5":
             samples, self.last_stats = self.model.sample_dopri5(zs, atol=choice.atol, rtol=choice.rtol, **kw)
         elif choice.kind == "sde":
-            samples = self.model.sample_sde(zs, choice.sde_opts, noise=noise, use_graph=use_graph, **kw)
+            samples = self.model.sample_sde(zs, choice.sde_opts, noise=noise, use_graph=use_graph, rng=rng, **kw)
         else:   # "euler" | "rk": the transport's fixed-grid samplers
             sample_fn = self.transport_sampler.sample_ode(sampling_method=choice.method, num_steps=choice.steps + 1)
             samples = sample_fn(zs, partial(self.model.forward_inference, **kw), use_graph=use_graph)[-1]
@@ -216,7 +231,7 @@ class NewMDGenWrapper:
         return atom14, aa_out
 
     def upsample(self, batch, num_frames=None, zs=None, num_steps=None, use_graph=True, sampling_method=None, atol=1e-6,
-                 rtol=1e-3, sde=None):
+                 rtol=1e-3, sde=None, rng_seed=None, rng_sample_base=0, rng_block_base=0):
         """Trajectory upsampling: sample the frames between key frames stored every `args.cond_interval` frames
         (upsampling_inference.py:47-82 around `inference`, wrapper.py:405-484).  `batch` holds KEY FRAMES only, one window per
         batch element: torsions (B,K,L,7,2), trans (B,K,L,3), rots (B,K,L,3,3), seqres (B,L), mask (B,L), with
@@ -224,7 +239,9 @@ class NewMDGenWrapper:
         its window.  Euler: one library call (`mdgen_upsample_euler`, one hipGraph); "midpoint" | "heun3" | "rk4": likewise
         (`mdgen_upsample_rk`; `num_steps` steps, default 24 / 16 / 12).  `sampling_method="dopri5"`:
         `mdgen_prep_keyframes` -> `sample_dopri5` -> `samples_to_atom14`, counts in `last_stats`; "sde" | "sde_heun" (with `sde`,
-        as `inference()`): the same three calls around `sample_sde`.  The solver rules are `inference()`'s.  Returns (atom14 (B,T,L,14,3), aa_out (B,T,L)); the latent samples are kept in `last_samples`."""
+        as `inference()`): the same three calls around `sample_sde` -- or, with `rng_seed` (`rng_sample_base`, `rng_block_base`: as
+        `inference()`), one library call and one hipGraph like the other fixed-grid solvers (`mdgen_upsample_sde`), the noise
+        generated in the kernels.  The solver rules are `inference()`'s.  Returns (atom14 (B,T,L,14,3), aa_out (B,T,L)); the latent samples are kept in `last_samples`."""
         from .geometry import residue_tables
         c = getattr(self.args, "cond_interval", None)
         if not c:
@@ -235,7 +252,7 @@ class NewMDGenWrapper:
         T = int(self.args.num_frames if num_frames is None else num_frames)
         if c < 1 or T < 1:
             raise L.MdgenError(f"num_frames and cond_interval must be >= 1, got {T}, {c}")
-        choice = self._solver(sampling_method, num_steps, atol, rtol, sde)
+        choice = self._solver(sampling_method, num_steps, atol, rtol, sde, None, rng_seed, rng_sample_base, rng_block_base)
         tors = batch["torsions"].to(torch.float32)
         trans = batch["trans"].to(torch.float32)
         rots = batch["rots"].to(torch.float32)
@@ -250,7 +267,10 @@ class NewMDGenWrapper:
         if zs is None:
             zs = torch.randn(B, T, L_, self.latent_dim, device=dev)
         mask = batch["mask"].to(torch.float32).unsqueeze(1).expand(-1, T, -1)
-        if choice.kind in ("dopri5", "sde"):
+        if choice.kind == "sde" and choice.rng_seed is not None:
+            atom14, samples = self.model.upsample_sde(zs, choice.sde_opts, self._rng(choice, rng_sample_base, rng_block_base), c, mask,
+                                                      rots, trans, tors, batch["seqres"], residue_tables(dev), use_graph=use_graph)
+        elif choice.kind in ("dopri5", "sde"):
             prep = prep_keyframes(rots, trans, tors, T, c)
             kw = dict(mask=mask.contiguous(), start_frames=(prep["start_rot"], prep["start_trans"]), x_cond=prep["x_cond"],
                       x_cond_mask=prep["x_cond_mask"], aatype=batch["seqres"])
@@ -271,7 +291,7 @@ class NewMDGenWrapper:
     def _rollout_host_loop(self, batch, T, zs, choice, use_graph):
         """The blocks of `rollout()` as a host loop of `inference()` with the resolved `choice` -- prep_latents -> the solver -> samples_to_atom14 --
         and `atom14_to_cond`, all on the device: the adaptive solver (dopri5 reads its error ratio back once per attempted step,
-        so it cannot be captured) and the SDE samplers (no fused driver).  -> (atom14, samples (R,B,T,L,D), next conditioning
+        so it cannot be captured) and the SDE samplers with staged noise (their fused driver generates its noise: `rng_seed`).  -> (atom14, samples (R,B,T,L,D), next conditioning
         frame, per-block stats)."""
         from .geometry import atom14_to_cond
         out, samples, stats = [], [], []
@@ -290,7 +310,8 @@ class NewMDGenWrapper:
         return torch.cat(out, 1), torch.stack(samples), nxt, stats
 
     def rollout(self, batch, num_frames: int, num_rollouts: int, num_steps=None, zs=None, use_graph=True,
-                return_next: bool = False, sampling_method=None, atol=1e-6, rtol=1e-3, sde=None):
+                return_next: bool = False, sampling_method=None, atol=1e-6, rtol=1e-3, sde=None, rng_seed=None, rng_sample_base=0,
+                rng_block_base=0):
         """`num_rollouts` chained blocks of `num_frames` frames from the B = 1-frame conditioning batch of
         `sim_inference.get_batch` (torsions (B,1,L,7,2), trans (B,1,L,3), rots (B,1,L,3,3), seqres, mask (B,L)):
         the loop of sim_inference.py:100-113 (`rollout` :61-98 per block) as ONE library call, captured as one hipGraph:
@@ -298,14 +319,16 @@ class NewMDGenWrapper:
         given) or `mdgen_rollout_rk` ("midpoint" | "heun3" | "rk4", `num_steps` steps per block, default 24 / 16 / 12).
         "dopri5" (with `atol` / `rtol`, no `num_steps`) is a host loop over the blocks with the same device glue -- the solver
         reads back once per attempted step -- and leaves a list of per-block counts in `last_stats`; "sde" | "sde_heun" (with `sde`,
-        as `inference()`) run as the same host loop, one `sample_sde` graph per block.  `zs`: optional noise
+        as `inference()`) run as the same host loop, one `sample_sde` graph per block -- or, with `rng_seed`, as ONE library call
+        and one hipGraph (`mdgen_rollout_sde`): the kernels generate the noise, block k's with the block index `rng_block_base` + k
+        and sample b's with the sample index `rng_sample_base` + b (as `inference()`).  `zs`: optional noise
         (num_rollouts, B, T, L, D); without it a block's noise is a fresh device randn (wrapper.py:439), drawn block by block
         when a method is named.  Returns atom14 (B, num_rollouts*T, L, 14, 3) [, the batch that would condition the next
         block]; the latent samples (num_rollouts, B, T, L, D) are kept in `last_samples`."""
         from .geometry import residue_tables
         if self.args.tps_condition or getattr(self.args, "cond_interval", None):
             raise L.MdgenError("rollout() is the forward-simulation driver (sim_condition models without cond_interval)")
-        choice = self._solver(sampling_method, num_steps, atol, rtol, sde)
+        choice = self._solver(sampling_method, num_steps, atol, rtol, sde, None, rng_seed, rng_sample_base, rng_block_base)
         tors = batch["torsions"][:, 0].to(torch.float32)
         trans = batch["trans"][:, 0].to(torch.float32)
         rots = batch["rots"][:, 0].to(torch.float32)
@@ -318,7 +341,10 @@ class NewMDGenWrapper:
         elif zs is None:   # one draw per block, in block order: what the per-block loop of inference() calls draws
             zs = torch.stack([torch.randn(B, T, L_, self.latent_dim, device=dev) for _ in range(R)])
         mask = batch["mask"].to(torch.float32).unsqueeze(1).expand(-1, T, -1)
-        if choice.kind in ("dopri5", "sde"):
+        if choice.kind == "sde" and choice.rng_seed is not None:
+            atom14, samples, nxt = self.model.rollout_sde(zs, choice.sde_opts, self._rng(choice, rng_sample_base, rng_block_base), mask,
+                                                          rots, trans, tors, batch["seqres"], residue_tables(dev), use_graph=use_graph)
+        elif choice.kind in ("dopri5", "sde"):
             atom14, samples, nxt, stats = self._rollout_host_loop(batch, T, zs, choice, use_graph)
             if choice.kind == "dopri5":
                 self.last_stats = stats
