@@ -36,8 +36,8 @@ extern "C" {
 
 typedef struct mdgen_ctx mdgen_ctx;
 
-/* 0 for a product library; 1 if the .so was built with a kernel experiment switch (csrc/dev.h, scripts/micro/): timing-only
- * builds whose results may be wrong.  mdgen_amd/_lib.py loads such a library only when MDGEN_AMD_LIB names it explicitly. */
+/* 0 for a product library; 1 if the .so was built with a kernel experiment switch (csrc/dev.h, scripts/micro/): measurement
+ * builds with cycle stamps in the kernels.  mdgen_amd/_lib.py loads such a library only when MDGEN_AMD_LIB names it explicitly. */
 int32_t mdgen_dev_build(void);
 
 /* Model hyper-parameters (reference argparse flags, mdgen/parsing.py:79-120). */

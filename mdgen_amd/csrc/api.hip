@@ -55,7 +55,7 @@ static thread_local DryPlan* g_dry = nullptr;
 
 extern "C" const char* mdgen_last_error(void) { return g_err; }
 extern "C" int32_t mdgen_abi_version(void) { return MDGEN_ABI_VERSION; }
-// 0 for a product library; 1 when this .so was built with an experiment switch (csrc/dev.h) -- its results may be wrong
+// 0 for a product library; 1 when this .so was built with an experiment switch (csrc/dev.h): cycle stamps in the kernels
 extern "C" int32_t mdgen_dev_build(void) {
 #ifdef MDGEN_DEV_BUILD
     return 1;
@@ -1251,11 +1251,7 @@ static QkvForm qkv_form(const mdgen_ctx* c, const AxisMap& ax) {
 // the whole L == 4 residue sub-layer in one kernel: launches of at most one 32-row workgroup per CU (B <= 2 at T 1000, the IPA
 // stack) take half panels, twice the CUs at work (option small_split)
 static Attn4Form attn4_fused_form(const mdgen_ctx* c, long nrows) {
-#ifdef MDGEN_DEV_ATTN4_FULL   // (experiment build, A/B of the half-panel form: every launch takes 64-row panels)
-    return Attn4Form::Fused;
-#else
     return c->opt_small_split && (nrows + 31) / 32 <= c->ncu ? Attn4Form::FusedHalf : Attn4Form::Fused;
-#endif
 }
 // k_flash_proj owns a (sequence, 64-query chunk) for all 16 heads: four times the work of a k_flash workgroup, a quarter of the
 // workgroups.  It pays where those still fill the chip (cfg-2: 1024 per launch, ATLAS: 1000 / 1024); small launches (B = 1: 64,

@@ -37,43 +37,6 @@ constexpr int kTrB = 144;      // bytes of one feature row of a transposed tile:
 constexpr int kChunk = 64;     // streamed rows per LDS fill
 constexpr float kMasked = -3.0e38f;
 
-// experiment switches (csrc/dev.h; product builds define none): what one ingredient of the chunk loop costs
-#ifdef MDGEN_DEV_ATTN16_NOEXP
-#define A16_EXP2(x) (x)
-#else
-#define A16_EXP2(x) __builtin_amdgcn_exp2f(x)
-#endif
-#ifdef MDGEN_DEV_ATTN16_NOMMA
-#define A16_MMA(a, b, c) (c)
-#else
-#define A16_MMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
-#endif
-#ifdef MDGEN_DEV_ATTN16_NOBAR
-#define A16_BARRIER() asm volatile("" ::: "memory")
-#else
-#define A16_BARRIER() __syncthreads()
-#endif
-#ifdef MDGEN_DEV_ATTN16_SEQNOLOAD   // k16_attn_bwd_seq: the fill's global loads / all but one tile of each pass / the result stores left out
-#define A16_SEQ_NOLOAD true
-#else
-#define A16_SEQ_NOLOAD false
-#endif
-#ifdef MDGEN_DEV_ATTN16_SEQNOLOOP
-#define A16_SEQ_NOLOOP true
-#else
-#define A16_SEQ_NOLOOP false
-#endif
-#ifdef MDGEN_DEV_ATTN16_SEQNOSTORE
-#define A16_SEQ_NOSTORE true
-#else
-#define A16_SEQ_NOSTORE false
-#endif
-#ifdef MDGEN_DEV_ATTN16_NOSTAGE
-#define A16_STAGE(c0) ((c0) == 0)
-#else
-#define A16_STAGE(c0) true
-#endif
-
 // Position, in the contraction order of a chained B operand, of row rho (0..31) of a tile: accumulator register
 // 8 s + j of lane-half hh holds row mfma_row(8 s + j, hh) and becomes element (k-step s, 8 hh + j).
 __device__ __forceinline__ int perm_pos(int rho) {
@@ -277,9 +240,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k16_attn(const float
     float mrun = kMasked, den = 0.f;
     fetch(0);
     for (int c0 = 0; c0 < len + 1; c0 += kChunk) {
-        A16_BARRIER();
-        if (!A16_STAGE(c0)) {
-        } else if (it.on) {
+        __syncthreads();
+        if (it.on) {
 #pragma unroll
             for (int e = 0; e < 2; ++e)
                 if (c0 + 2 * it.pair + e == len) {   // the bias key / value (LDS table, ready after the first barrier)
@@ -291,25 +253,25 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k16_attn(const float
         } else if (it.scalar) {
             sM[tid - 192] = mval;
         }
-        A16_BARRIER();
-        if (A16_STAGE(c0 + kChunk) && c0 + kChunk < len + 1) fetch(c0 + kChunk);
+        __syncthreads();
+        if (c0 + kChunk < len + 1) fetch(c0 + kChunk);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             if (c0 + 32 * t > len) break;
             f32x16 s = rows_from(sM + 32 * t, hh, 1.0f);
             const unsigned char* kr = sK + (32 * t + l31) * kRowB + hh * 16;
-            s = A16_MMA(lds_frag(kr), q.f0, s);
-            s = A16_MMA(lds_frag(kr + 32), q.f1, s);
+            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(kr), q.f0, s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(kr + 32), q.f1, s, 0, 0, 0);
             float tmax = s[0];
 #pragma unroll
             for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, s[r]);
             const float mnew = fmaxf(mrun, half_max(tmax));
-            const float alpha = A16_EXP2((mrun - mnew) * kLog2e);
+            const float alpha = __builtin_amdgcn_exp2f((mrun - mnew) * kLog2e);
             mrun = mnew;
             float sum = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                s[r] = A16_EXP2((s[r] - mnew) * kLog2e);
+                s[r] = __builtin_amdgcn_exp2f((s[r] - mnew) * kLog2e);
                 sum += s[r];
                 o[r] *= alpha;
             }
@@ -317,8 +279,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k16_attn(const float
             bf16x8 p0, p1;
             chain(s, p0, p1);
             const unsigned char* vr = sVt + l31 * kTrB + 64 * t + hh * 16;
-            o = A16_MMA(lds_frag(vr), p0, o);
-            o = A16_MMA(lds_frag(vr + 32), p1, o);
+            o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(vr), p0, o, 0, 0, 0);
+            o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(vr + 32), p1, o, 0, 0, 0);
         }
     }
     den = half_sum(den);
@@ -384,9 +346,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k16_attn_bwd_q(const
     for (int r = 0; r < 16; ++r) dq[r] = opaque_zero();
     fetch(0);
     for (int c0 = 0; c0 < len + 1; c0 += kChunk) {
-        A16_BARRIER();
-        if (!A16_STAGE(c0)) {
-        } else if (it.on) {
+        __syncthreads();
+        if (it.on) {
 #pragma unroll
             for (int e = 0; e < 2; ++e)
                 if (c0 + 2 * it.pair + e == len) {
@@ -399,8 +360,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k16_attn_bwd_q(const
         } else if (it.scalar) {
             sM[tid - 192] = mval;
         }
-        A16_BARRIER();
-        if (A16_STAGE(c0 + kChunk) && c0 + kChunk < len + 1) fetch(c0 + kChunk);
+        __syncthreads();
+        if (c0 + kChunk < len + 1) fetch(c0 + kChunk);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             if (c0 + 32 * t > len) break;
@@ -410,17 +371,17 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k16_attn_bwd_q(const
             for (int r = 0; r < 16; ++r) dp[r] = -delta;
             const unsigned char* kr = sK + (32 * t + l31) * kRowB + hh * 16;
             const unsigned char* vr = sV + (32 * t + l31) * kRowB + hh * 16;
-            s = A16_MMA(lds_frag(kr), q.f0, s);
-            s = A16_MMA(lds_frag(kr + 32), q.f1, s);
-            dp = A16_MMA(lds_frag(vr), dO.f0, dp);
-            dp = A16_MMA(lds_frag(vr + 32), dO.f1, dp);
+            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(kr), q.f0, s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(kr + 32), q.f1, s, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(vr), dO.f0, dp, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(vr + 32), dO.f1, dp, 0, 0, 0);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) s[r] = A16_EXP2((s[r] - lse) * kLog2e) * dp[r];
+            for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f((s[r] - lse) * kLog2e) * dp[r];
             bf16x8 d0, d1;
             chain(s, d0, d1);
             const unsigned char* tr = sKt + l31 * kTrB + 64 * t + hh * 16;
-            dq = A16_MMA(lds_frag(tr), d0, dq);
-            dq = A16_MMA(lds_frag(tr + 32), d1, dq);
+            dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(tr), d0, dq, 0, 0, 0);
+            dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(tr + 32), d1, dq, 0, 0, 0);
         }
     }
     unrope(dq, qi < len ? qi : len - 1, inv_freq, hh, 0.20412414523193151f);   // back through RoPE and the q scale 24^-1/2
@@ -501,9 +462,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k16_attn_bwd_kv(cons
 #pragma unroll
     for (int r = 0; r < 16; ++r) dk[r] = dv[r] = opaque_zero();
     for (int c0 = 0; c0 < len; c0 += kChunk) {
-        A16_BARRIER();
-        if (!A16_STAGE(c0)) {
-        } else if (it.on) {
+        __syncthreads();
+        if (it.on) {
             put_rowmajor(sQ, it, qf);
             put_rowmajor(sdO, it, df);
             put_transposed(sQt, it, qf);
@@ -512,8 +472,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k16_attn_bwd_kv(cons
             sLse[tid - 192] = lval;
             sDel[tid - 192] = dval;
         }
-        A16_BARRIER();
-        if (A16_STAGE(c0 + kChunk) && c0 + kChunk < len) fetch(c0 + kChunk);
+        __syncthreads();
+        if (c0 + kChunk < len) fetch(c0 + kChunk);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             if (c0 + 32 * t >= len) break;
@@ -521,13 +481,13 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k16_attn_bwd_kv(cons
             f32x16 dp = rows_from(sDel + 32 * t, hh, -1.0f);
             const unsigned char* qr = sQ + (32 * t + l31) * kRowB + hh * 16;
             const unsigned char* dr = sdO + (32 * t + l31) * kRowB + hh * 16;
-            s = A16_MMA(lds_frag(qr), k.f0, s);
-            s = A16_MMA(lds_frag(qr + 32), k.f1, s);
-            dp = A16_MMA(lds_frag(dr), v.f0, dp);
-            dp = A16_MMA(lds_frag(dr + 32), v.f1, dp);
+            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(qr), k.f0, s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(qr + 32), k.f1, s, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(dr), v.f0, dp, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(dr + 32), v.f1, dp, 0, 0, 0);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                s[r] = valid ? A16_EXP2(s[r] * kLog2e) : 0.f;
+                s[r] = valid ? __builtin_amdgcn_exp2f(s[r] * kLog2e) : 0.f;
                 dp[r] *= s[r];
             }
             bf16x8 p0, p1, d0, d1;
@@ -535,10 +495,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k16_attn_bwd_kv(cons
             chain(dp, d0, d1);
             const unsigned char* dt = sdOt + l31 * kTrB + 64 * t + hh * 16;
             const unsigned char* qt = sQt + l31 * kTrB + 64 * t + hh * 16;
-            dv = A16_MMA(lds_frag(dt), p0, dv);
-            dv = A16_MMA(lds_frag(dt + 32), p1, dv);
-            dk = A16_MMA(lds_frag(qt), d0, dk);
-            dk = A16_MMA(lds_frag(qt + 32), d1, dk);
+            dv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(dt), p0, dv, 0, 0, 0);
+            dv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(dt + 32), p1, dv, 0, 0, 0);
+            dk = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(qt), d0, dk, 0, 0, 0);
+            dk = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(qt + 32), d1, dk, 0, 0, 0);
         }
     }
     f32x16 dku = dk;    // real keys: back through RoPE at their position (the bias key's own path below keeps dk)
@@ -753,7 +713,7 @@ __device__ __forceinline__ void attn_bwd_seq_q(unsigned char* lds, const Wg g, c
         for (int x = 0; x < 2; ++x) {
             const int r = r0 + x;
             kf[x][0] = kf[x][1] = vf[x][0] = vf[x][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (r < len && !A16_SEQ_NOLOAD) {
+            if (r < len) {
                 const float* row = qkv + (tok0 + (long)r * pstr) * ld + g.hd * kDH + 4 * qq;
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
@@ -792,21 +752,21 @@ __device__ __forceinline__ void attn_bwd_seq_q(unsigned char* lds, const Wg g, c
         const unsigned char* kr = sK + (32 * t + l31) * kRowB + hh * 16;
         const unsigned char* vr = sV + (32 * t + l31) * kRowB + hh * 16;
         const bf16x8 k0 = lds_frag(kr), k1 = lds_frag(kr + 32), v0 = lds_frag(vr), v1 = lds_frag(vr + 32);
-        s = A16_MMA(k0, q.f0, s);
-        dp = A16_MMA(v0, dO.f0, zero);
-        s = A16_MMA(k1, q.f1, s);
-        dp = A16_MMA(v1, dO.f1, dp);
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k0, q.f0, s, 0, 0, 0);
+        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v0, dO.f0, zero, 0, 0, 0);
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1, q.f1, s, 0, 0, 0);
+        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v1, dO.f1, dp, 0, 0, 0);
         asm volatile("" ::"v"(v0), "v"(v1), "v"(dO.f0), "v"(dO.f1));   // sources outlive the inline-constant-C MFMA (common.h opaque_zero)
     };
     f32x16 s, dp;
     scores(0, s, dp);
-    for (int t = 0; t < (A16_SEQ_NOLOOP ? 1 : nkt); ++t) {
+    for (int t = 0; t < nkt; ++t) {
         const unsigned char* tr = sKt + l31 * kTrKB + 64 * t + hh * 16;
         const bf16x8 t0 = lds_frag(tr), t1 = lds_frag(tr + 32);
         f32x16 sn, dpn;
         scores(t + 1 < nkt ? t + 1 : t, sn, dpn);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = A16_EXP2(s[r]) * dp[r];   // p = 2^(s2 - lse2),  d s = p (d p - delta)
+        for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r]) * dp[r];   // p = 2^(s2 - lse2),  d s = p (d p - delta)
         bf16x8 d0, d1;
         chain(s, d0, d1);
 #pragma unroll
@@ -814,13 +774,13 @@ __device__ __forceinline__ void attn_bwd_seq_q(unsigned char* lds, const Wg g, c
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA
             __builtin_amdgcn_sched_group_barrier(0x402, 10, 0);  // ten VALU / transcendental
         }
-        dq = A16_MMA(t0, d0, dq);
-        dq = A16_MMA(t1, d1, dq);
+        dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t0, d0, dq, 0, 0, 0);
+        dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t1, d1, dq, 0, 0, 0);
         s = sn;
         dp = dpn;
     }
     unrope_fast(dq, own < len ? own : len - 1, inv_freq, hh, 0.20412414523193151f);   // back through RoPE and the q scale 24^-1/2
-    if (own < len && !A16_SEQ_NOSTORE) store_grad(dqkv, qtok * ld + g.hd * kDH + 4 * hh, dq, out16);
+    if (own < len) store_grad(dqkv, qtok * ld + g.hd * kDH + 4 * hh, dq, out16);
 }
 
 // key pass: real keys write dqkv[:, 384:1152] (dk taken back through RoPE); the bias key writes dbias[seq][dk rotated back | dv]
@@ -846,7 +806,7 @@ __device__ __forceinline__ void attn_bwd_seq_kv(unsigned char* lds, const Wg g, 
     // per query row: -lse2 and -delta = -(dO . O)  (one thread per row; its 24 + 24 floats are lines the fill below reads too)
     if (tid < 32 * nqt) {
         float nl = kMasked, nd = 0.f;   // beyond len: p = 2^-inf = 0
-        if (tid < len && !A16_SEQ_NOLOAD) {
+        if (tid < len) {
             const long t = tok0 + (long)tid * pstr;
             nl = -kLog2e * lse_in[t * kH + g.hd];
             const float* dr = dout + t * kC + g.hd * kDH;
@@ -870,7 +830,7 @@ __device__ __forceinline__ void attn_bwd_seq_kv(unsigned char* lds, const Wg g, 
         for (int x = 0; x < 2; ++x) {
             const int r = r0 + x;
             qf[x][0] = qf[x][1] = df[x][0] = df[x][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (r < len && !A16_SEQ_NOLOAD) {
+            if (r < len) {
                 const long t = tok0 + (long)r * pstr;
                 const float* row = qkv + t * ld + g.hd * kDH + 4 * qq;
 #pragma unroll
@@ -925,19 +885,19 @@ __device__ __forceinline__ void attn_bwd_seq_kv(unsigned char* lds, const Wg g, 
             const unsigned char* qr = sQ + (32 * t + l31) * kRowB + hh * 16;
             const unsigned char* dr = sdO + (32 * t + l31) * kRowB + hh * 16;
             const bf16x8 q0 = lds_frag(qr), q1 = lds_frag(qr + 32), e0 = lds_frag(dr), e1 = lds_frag(dr + 32);
-            s = A16_MMA(q0, k.f0, s);
-            dp = A16_MMA(e0, v.f0, dp);
-            s = A16_MMA(q1, k.f1, s);
-            dp = A16_MMA(e1, v.f1, dp);
+            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(q0, k.f0, s, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(e0, v.f0, dp, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(q1, k.f1, s, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(e1, v.f1, dp, 0, 0, 0);
         };
         // (not software-pipelined: with the next tile's scores in flight the kernel needs 132 registers, one workgroup per CU; at
         // 128 the second workgroup's waves fill this wave's waits)
-        for (int t = t0; t < (A16_SEQ_NOLOOP ? t0 + 1 : t1); ++t) {
+        for (int t = t0; t < t1; ++t) {
             f32x16 s, dp;
             scores(t, s, dp);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                s[r] = A16_EXP2(s[r]);
+                s[r] = __builtin_amdgcn_exp2f(s[r]);
                 dp[r] *= s[r];
             }
             bf16x8 p0, p1, d0, d1;
@@ -946,10 +906,10 @@ __device__ __forceinline__ void attn_bwd_seq_kv(unsigned char* lds, const Wg g, 
             const unsigned char* dt = sdOt + l31 * kTrQB + 64 * t + hh * 16;
             const unsigned char* qt = sQt + l31 * kTrQB + 64 * t + hh * 16;
             const bf16x8 a0 = lds_frag(dt), a1 = lds_frag(dt + 32), b0 = lds_frag(qt), b1 = lds_frag(qt + 32);
-            dv = A16_MMA(a0, p0, dv);
-            dk = A16_MMA(b0, d0, dk);
-            dv = A16_MMA(a1, p1, dv);
-            dk = A16_MMA(b1, d1, dk);
+            dv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, p0, dv, 0, 0, 0);
+            dk = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, d0, dk, 0, 0, 0);
+            dv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, p1, dv, 0, 0, 0);
+            dk = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, d1, dk, 0, 0, 0);
         }
     };
     auto bias_row = [&](float* slot, const f32x16& dk, const f32x16& dv) {   // the bias key's two lanes: raw (dk | dv) into a slot
@@ -967,7 +927,7 @@ __device__ __forceinline__ void attn_bwd_seq_kv(unsigned char* lds, const Wg g, 
         key_pass(w, 0, nqt, dk, dv);
         if (own == len) bias_row(sRed, dk, dv);
         unrope_fast(dk, own < len ? own : 0, inv_freq, hh, kLn2);   // the Q images carry q log2(e)
-        if (own < len && !A16_SEQ_NOSTORE) {
+        if (own < len) {
             const long e0 = (tok0 + (long)own * pstr) * ld + kC + g.hd * kDH + 4 * hh;
             store_grad(dqkv, e0, dk, out16);
             store_grad(dqkv, e0 + kC, dv, out16);
@@ -1085,18 +1045,18 @@ __global__ __launch_bounds__(512, 2) void k16_attn_seq(const float* __restrict__
     for (int t = 0; t < nkt; ++t) {
         f32x16 s = rows_from(sM + 32 * t, hh, 1.0f);
         const unsigned char* kr = sK + (32 * t + l31) * kRowB + hh * 16;
-        s = A16_MMA(lds_frag(kr), q.f0, s);
-        s = A16_MMA(lds_frag(kr + 32), q.f1, s);
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(kr), q.f0, s, 0, 0, 0);
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(kr + 32), q.f1, s, 0, 0, 0);
         float tmax = s[0];
 #pragma unroll
         for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, s[r]);
         const float mnew = fmaxf(mrun, half_max(tmax));
-        const float alpha = A16_EXP2(mrun - mnew);
+        const float alpha = __builtin_amdgcn_exp2f(mrun - mnew);
         mrun = mnew;
         float sum = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            s[r] = A16_EXP2(s[r] - mnew);
+            s[r] = __builtin_amdgcn_exp2f(s[r] - mnew);
             sum += s[r];
             o[r] *= alpha;
         }
@@ -1104,8 +1064,8 @@ __global__ __launch_bounds__(512, 2) void k16_attn_seq(const float* __restrict__
         bf16x8 p0, p1;
         chain(s, p0, p1);
         const unsigned char* vr = sVt + l31 * kTrKB + 64 * t + hh * 16;
-        o = A16_MMA(lds_frag(vr), p0, o);
-        o = A16_MMA(lds_frag(vr + 32), p1, o);
+        o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(vr), p0, o, 0, 0, 0);
+        o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(vr + 32), p1, o, 0, 0, 0);
     }
     den = half_sum(den);
     if (qi >= len) return;

@@ -147,14 +147,8 @@ __device__ __forceinline__ void block(const KTile& kn, const QTile& qn, f32x16& 
     for (int j = 0; j < 16; ++j) e[j] = __builtin_amdgcn_exp2f(s[j]);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-#ifdef MDGEN_DEV_FLASH_TRUNC   // (experiment) P truncated to bf16 by one v_perm_b32 per pair instead of v_cvt_pk_bf16_f32: the softmax
-                               // denominator is the sum of the SAME truncated P (ones row of V^T), so the -1/2 ulp bias cancels to first order
-        pc.p0[j] = __builtin_amdgcn_perm(__float_as_uint(e[2 * j + 1]), __float_as_uint(e[2 * j]), 0x07060302u);
-        pc.p1[j] = __builtin_amdgcn_perm(__float_as_uint(e[9 + 2 * j]), __float_as_uint(e[8 + 2 * j]), 0x07060302u);
-#else
         pc.p0[j] = pack_bf16(e[2 * j], e[2 * j + 1]);
         pc.p1[j] = pack_bf16(e[8 + 2 * j], e[9 + 2 * j]);
-#endif
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -386,11 +380,9 @@ __device__ __forceinline__ void flash_job(const FlashParams p, const int seq, co
             else if constexpr (j < NQ - 1) block(kc, q[j + 1], s[(j + 1) & 1], vc, pt[(j - 1) & 1], h[j - 1].o, s[j & 1], pt[j & 1]);
             else block(kn, q[0], s[0], vc, pt[(j - 1) & 1], h[j - 1].o, s[j & 1], pt[j & 1]);
             __builtin_amdgcn_sched_barrier(0);
-#ifndef MDGEN_DEV_FLASH_NOLOAD   // (timing experiments only: scripts/micro/flash_variants.sh)
             if constexpr (j == 0) issue_v(vprev, kRobust ? ti + 1 : phys(ti + 1));      // V(t-1) is consumed: refill its slot
             if constexpr (j == NQ - 2) issue_k(kc, kRobust ? ti + 2 : phys(ti + 2));    // K(t) has served its last query tile
             if constexpr (j == 0 || j == NQ - 2) __builtin_amdgcn_sched_barrier(0);
-#endif
         });
     };
     // The whole (head, 32 NQ queries) job over key tiles 0 .. nt - 1; returns with the last pair's PV MFMAs issued.
@@ -524,9 +516,6 @@ __device__ __forceinline__ void flash_job(const FlashParams p, const int seq, co
         }
         FLASH_STAMP(9, (unsigned long long)__builtin_amdgcn_ballot_w64(bad));
         robust_needed = __builtin_amdgcn_ballot_w64(bad) != 0;
-#ifdef MDGEN_DEV_FLASH_NOFALLBACK   // (experiments only: shows what the fixed anchor alone does to overflowing scores)
-        robust_needed = false;
-#endif
     }
     if (robust_needed) {   // wave-uniform; start over with a moving shift
 #pragma unroll
@@ -640,23 +629,17 @@ __global__ __launch_bounds__(256, 2) void k_flash_proj(const FlashProjParams p) 
     FPROJ_STAMP(5, __builtin_amdgcn_s_memtime());
     const int lane = lane_id();
     f32x16 acc[6];
-#ifndef MDGEN_DEV_FLASH_NOEARLY   // as k_flash_proj8: the first batch of residual rows requested ahead of the GEMM (ATLAS +0.8 % end to end,
-                                  // profiles/r06_experiments.txt #3)
+    // as k_flash_proj8: the first batch of residual rows requested ahead of the GEMM (ATLAS +0.8 % end to end,
+    // profiles/r06_experiments.txt #3)
     EpiPre<8> ep;
     epi_rmw_request<8>(0, 0, pr, 96 * w, p.h, ep);
     __builtin_amdgcn_sched_barrier(0);
-#endif
     zero_acc<6>(acc);
     wave_gemm<2, 3, 24, false>(panel, kC * 2, 0, 0, p.wo + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
     FPROJ_STAMP(6, __builtin_amdgcn_s_memtime());
     __syncthreads();   // every wave is done reading the panel: reuse it as four 12 KiB staging slabs
-#ifndef MDGEN_DEV_FLASH_NOEARLY
     epilogue_gate_residual_lds_pre<3>(acc, pr, reinterpret_cast<float*>(panel) + w * (32 * 96), 96 * w, p.bo, p.mm, p.gate_chunk, true,
                                       p.h, ep);
-#else
-    epilogue_gate_residual_lds<3>(acc, pr, reinterpret_cast<float*>(panel) + w * (32 * 96), 96 * w, p.bo, p.mm, p.gate_chunk, true,
-                                  p.h);
-#endif
     FPROJ_STAMP(7, __builtin_amdgcn_s_memtime());
     FPROJ_STAMP(9, __builtin_amdgcn_s_memrealtime());
 }
@@ -700,51 +683,37 @@ __global__ __launch_bounds__(512, 1) void k_flash_proj8(const FlashProjParams p)
     }
 #pragma unroll 1
     for (int pass = 0; pass < 2; ++pass) {
-#ifndef MDGEN_DEV_FLASH_NOPRIO
         // The two waves of a SIMD (w8, w8 + 4) take turns at static priority, the second-dispatched one first: the arbiter otherwise serves
         // the older wave on every conflict (MI355X_MICROARCH "two waves per SIMD"), both waves walk their jobs in step and each one's
         // prologue / anchor / store phases meet the other's.  One flip per job, none inside the loop.  k_flash_proj8 204.3 / 205.8 ->
         // 195.4 / 196.3 us per launch at cfg-2 (profiles/r06_experiments.txt #2); a fixed priority for waves 4..7 alone: no change.
         if ((w8 >= 4) == (pass == 0)) __builtin_amdgcn_s_setprio(1);
         else __builtin_amdgcn_s_setprio(0);
-#endif
         const int head = 8 * pass + w8;
         FlashPre<NQ> pre;
         flash_prefetch<NQ>(p.f, seq, head, qc, pre);
         flash_job<NQ>(p.f, seq, head, qc, w8, pre, FlashStorePanel{(lds_byte*)panel, head});
     }
-#ifndef MDGEN_DEV_FLASH_NOPRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     __syncthreads();   // the attention output of all 16 heads is in the panel
     const int lane = lane_id();
     f32x16 acc[6];
-#ifndef MDGEN_DEV_FLASH_NOEARLY
     // the residual rows of the epilogue's first batch are requested BEFORE the out-projection GEMM (they do not depend on it), and every
     // later batch before the stores of the one ahead of it: 204 -> 200-201 us per launch at cfg-2 (profiles/r06_experiments.txt #2)
     EpiPre<8> ep;
     epi_rmw_request<8>(0, 0, &pr[g], 96 * w, p.h, ep);
     __builtin_amdgcn_sched_barrier(0);
-#endif
     zero_acc<6>(acc);
     wave_gemm<2, 3, 24, false>(panel, kC * 2, 2 * g, 0, p.wo + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
     __syncthreads();   // every wave is done reading the panel: reuse it as eight 12 KiB staging slabs
-#ifndef MDGEN_DEV_FLASH_NOEARLY
     epilogue_gate_residual_lds_pre<3>(acc, &pr[g], reinterpret_cast<float*>(panel) + w8 * (32 * 96), 96 * w, p.bo, p.mm, p.gate_chunk, true,
                                       p.h, ep);
-#else
-    epilogue_gate_residual_lds<3>(acc, &pr[g], reinterpret_cast<float*>(panel) + w8 * (32 * 96), 96 * w, p.bo, p.mm, p.gate_chunk, true,
-                                  p.h);
-#endif
 }
 
 // Measured (cfg-2 / cfg-4, same box, back to back): NQ = 4 runs 160-162 / 76 us, NQ = 2 160-164 / 76 us -- a tie; 2 keeps
 // three waves per SIMD and is faster on short sequences (IPA stack: 10 vs 14 us).
-#ifndef MDGEN_FLASH_NQ
-#define MDGEN_FLASH_NQ 2
-#endif
 void launch_flash(const FlashParams& p, hipStream_t s) {
-    constexpr int NQ = MDGEN_FLASH_NQ;
+    constexpr int NQ = 2;
     const int nqc = (p.ax.len + 32 * NQ - 1) / (32 * NQ);
     const int npair8 = (p.ax.nseq * 4 + 7) / 8;   // (sequence, head group) pairs, in groups of 8 (one per XCD)
     hipLaunchKernelGGL(k_flash<NQ>, dim3(npair8 * nqc * 8), dim3(256), 0, s, p);

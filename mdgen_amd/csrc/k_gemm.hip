@@ -303,7 +303,7 @@ extern "C" int mdgen_dev_qkv_stamps(void* host, size_t bytes) {
     if (!SMALL && lane_id() == 0 && (long)blockIdx.x * 4 + wave_id() < 16384)                                  \
     g_qkv_stamps[((long)blockIdx.x * 4 + wave_id()) * 8 + (slot)] = __builtin_amdgcn_s_memtime()
 // k_ln_qkv_attn4: [wave][16]: 0 start, 1 LN prologue, 2 Q GEMM, 3 Q epilogue, 4 K GEMM, 5 K RoPE, 6 scores + softmax, 7 V GEMM, 8 P V +
-// panel, 9 out-projection GEMM, 10 end (scripts/r05/attn4_stamps.py)
+// panel, 9 out-projection GEMM, 10 end (scripts/micro/attn4_stamps.py)
 __device__ unsigned long long g_attn4_stamps[8192 * 16];
 extern "C" int mdgen_dev_attn4_stamps(void* host, size_t bytes) {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_attn4_stamps), bytes);
@@ -1068,7 +1068,7 @@ constexpr int kW2S = 96 * 64;   // bf16x8 elements between two feature tiles of 
 template <bool NEXT>
 __device__ __forceinline__ void stage_x(const unsigned char* panel, const bf16x8* __restrict__ w1c, const XPre& pre, f32x16* a1,
                                         const float* b1c, f32x4& b0, const bf16x8* __restrict__ w2n,
-                                        const unsigned char* hrn, YPre& nxt, unsigned long long* midstamp = nullptr) {
+                                        const unsigned char* hrn, YPre& nxt) {
     // Weight fragments come from L2 with ~600 cycles of latency under load (in-kernel stamps: a k-step took 210 cycles
     // with three fragments in flight, 64 of them matrix-pipe time; with five 170), so the number in flight sets the
     // pace: kPFX, as many as the register file allows (six spill).
@@ -1100,9 +1100,6 @@ __device__ __forceinline__ void stage_x(const unsigned char* panel, const bf16x8
         for (int t = 0; t < 2; ++t)
             a1[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wring[ks % (PF + 1)], aring[ks & 1][t], a1[t], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-#ifdef MDGEN_DEV_MLP_STAMPX   // (experiment build, scripts/micro/mlp_stampx.py: a stamp half-way through one fc1 stage)
-        if (midstamp && ks == 11) *midstamp = __builtin_amdgcn_s_memtime();
-#endif
     }
 }
 
@@ -1228,15 +1225,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp(const MlpParams p) {
         const unsigned char* hr = (c & 1) ? hb0 : hb1;     // fc2(c - 1) reads it
         // X(c): fc1 of chunk c; requests the first fc2(c - 1) operands
         zero_acc<2>(a1);
-#ifdef MDGEN_DEV_MLP_STAMPX
-        unsigned long long mid = 0;
-        if (c == 5) stamp(p, 25);   // after the barrier, before fc1(5)
-        stage_x<true>(panel, w1l + (size_t)c * W1C, xp, a1, b1l + c * kHC, b0, w2l + (size_t)8 * (c - 1) * 64, hr, yp,
-                      c == 5 ? &mid : nullptr);
-        if (c == 5) stamp(p, 30, mid);
-#else
         stage_x<true>(panel, w1l + (size_t)c * W1C, xp, a1, b1l + c * kHC, b0, w2l + (size_t)8 * (c - 1) * 64, hr, yp);
-#endif
         stamp(p, 1 + 2 * c);
         // Y(c): GELU(c) -> hw  ||  fc2(c - 1) from hr; requests the first operands of X(c + 1) (clamped at the end)
         const int cn = c + 1 < kNChunk ? c + 1 : c;
@@ -1275,7 +1264,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp(const MlpParams p) {
 // same atomic add tells it that it is last, then agent-scope atomic loads.  Correct for any placement.  The S workgroups of a panel
 // are nevertheless placed on ONE XCD (equal blockIdx % 8; the context's placement probe checks the residue -> XCD rule and the
 // launcher only picks the form where it holds): that is where the form pays.
-#ifdef MDGEN_DEV_MLP8_STAMPS   // (experiment build, scripts/r06/mlp8_stamps.py: per-wave s_memtime stamps of k_mlp8, held in SGPRs, one store branch)
+#ifdef MDGEN_DEV_MLP8_STAMPS   // (experiment build, scripts/micro/mlp8_stamps.py: per-wave s_memtime stamps of k_mlp8, held in SGPRs, one store branch)
 __device__ unsigned long long g_mlp8_stamps[8192 * 16];
 extern "C" int mdgen_dev_mlp8_stamps(void* host, size_t bytes) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mlp8_stamps), bytes); }
 #define MLP8_STAMP_DECL unsigned long long m8st[12] = {}

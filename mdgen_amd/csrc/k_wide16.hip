@@ -26,16 +26,14 @@ constexpr int kWideRows = 128, kWideCols = 384, kWideBK = 64, kWideRowB = 144;
 constexpr int kWideP = kWideRows * kWideRowB, kWideQ = kWideCols * kWideRowB;   // bytes of one buffer's P / Q tile
 
 // acc[t][u] += P[64 wr + 32 t .. ][0..63] . Q[96 wc + 32 u .. ][0..63]^T over the four 16-wide k-steps of the LDS tiles.
-// `issue(ks)` runs in front of each k-step's MFMAs (a hook for the stamps build; spreading the next step's sixteen global
-// loads over the four k-steps instead of issuing them in one block before the MFMAs was measured and is not kept: the last
-// quarter then leaves late and the conversion phase waits out its whole latency, 48.8 vs 47.7 ms per training step).
-template <typename Issue>
+// (Spreading the next step's sixteen global loads over the four k-steps instead of issuing them in one block before the
+// MFMAs was measured and is not kept: the last quarter then leaves late and the conversion phase waits out its whole
+// latency, 48.8 vs 47.7 ms per training step.)
 __device__ __forceinline__ void wide_mma(const unsigned char* P, const unsigned char* Q, f32x16 (&acc)[2][3], int wr, int wc,
-                                         int lane, Issue issue) {
+                                         int lane) {
     const int i = lane & 31, kh = lane >> 5;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-        issue(ks);
         bf16x8 a[2], b[3];
 #pragma unroll
         for (int t = 0; t < 2; ++t) a[t] = *reinterpret_cast<const bf16x8*>(P + (wr * 64 + t * 32 + i) * kWideRowB + ks * 32 + kh * 16);
@@ -51,13 +49,6 @@ __device__ __forceinline__ void wide_mma(const unsigned char* P, const unsigned 
 __device__ __forceinline__ u32x2 pack4(float a, float b, float c, float d) { return u32x2{pack_bf16(a, b), pack_bf16(c, d)}; }
 
 }  // namespace
-
-#ifdef MDGEN_DEV_WIDE_STAMPS
-__device__ unsigned long long g_wide_stamps[512 * 2 * 24];   // s_memtime stamps of waves 0 and 5 of the first 512 workgroups
-extern "C" int mdgen_dev_wide_stamps(unsigned long long* host, int n) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_wide_stamps), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
-}
-#endif
 
 // Tile order as in k16_linear_fast: the column groups of one 128-row slice run back to back on one XCD.
 // Requires (launcher): k % 64 == 0, 16-byte aligned operands and row strides, weight stored [m][k].
@@ -108,59 +99,19 @@ __device__ __forceinline__ void linear_wide_tile(const LinearParams& p, int vb, 
         for (int q = 0; q < 12; ++q)
             *reinterpret_cast<u32x2*>(Q + (r0 + 32 * q) * kWideRowB + piece * 8) = pack4(wv[q][0], wv[q][1], wv[q][2], wv[q][3]);
     };
-#ifdef MDGEN_DEV_WIDE_STAMPS
-    unsigned long long st[24];
-    int sti = 0;
-#define WIDE_STAMP() do { if (sti < 24) st[sti++] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define WIDE_STAMP() do { } while (0)
-#endif
-    WIDE_STAMP();
     fetch(0);
     stage(0);
     __syncthreads();
-    WIDE_STAMP();
     int buf = 0;
     for (int k0 = 0; k0 < p.k; k0 += kWideBK, buf ^= 1) {
         const bool more = k0 + kWideBK < p.k;
         const unsigned char* P = lds + buf * (kWideP + kWideQ);
-#if defined(MDGEN_DEV_WIDE_NOMMA)
         if (more) fetch(k0 + kWideBK);
-#elif defined(MDGEN_DEV_WIDE_NOLOAD)
-        wide_mma(P, P + kWideP, acc, wr, wc, lane, [](int) {});
-#else
-#if defined(MDGEN_DEV_WIDE_STAMPS)
-        wide_mma(P, P + kWideP, acc, wr, wc, lane, [&](int ks) {
-            if (k0 < 3 * kWideBK) WIDE_STAMP();
-            if (more) fetch_quarter(k0 + kWideBK, ks);
-        });
-#else
-        if (more) fetch(k0 + kWideBK);
-        wide_mma(P, P + kWideP, acc, wr, wc, lane, [](int) {});
-#endif
-#endif
-#ifdef MDGEN_DEV_WIDE_STAMPS
-        if (k0 < 3 * kWideBK) WIDE_STAMP();
-        if (more) stage(buf ^ 1);
-        if (k0 < 3 * kWideBK) WIDE_STAMP();
-        __syncthreads();
-        if (k0 < 3 * kWideBK) WIDE_STAMP();
-#else
+        wide_mma(P, P + kWideP, acc, wr, wc, lane);
         if (more) stage(buf ^ 1);
         __syncthreads();
-#endif
     }
-#ifdef MDGEN_DEV_WIDE_NOSTORE
-    if (acc[0][0][0] == 1.2345e33f) linear_epilogue(p, acc, row0, colt, wr, wc);
-    else if (tid == 0 && acc[1][2][5] == 5.4321e33f) p.c[row0] = 0.f;
-#else
     linear_epilogue(p, acc, row0, colt, wr, wc);
-#endif
-#ifdef MDGEN_DEV_WIDE_STAMPS
-    WIDE_STAMP();
-    if (p.k == 384 && p.m == 384 && !p.seg_cols && vb < 512 && (tid & 63) == 0 && (w == 0 || w == 5))
-        for (int i = 0; i < 24; ++i) g_wide_stamps[(vb * 2 + (w ? 1 : 0)) * 24 + i] = i < sti ? st[i] : 0ull;
-#endif
 }
 
 // (A persistent form -- 256 workgroups walking the tiles, so that a tile's store phase could overlap the next tile's loads --
@@ -172,7 +123,7 @@ __global__ __launch_bounds__(512) void k16_linear_wide(const LinearParams p, int
 }
 
 // ---- the same tile with the weight brought in by LDS-DMA ---------------------------------------------------------------
-// What the ablation builds of k16_linear_wide show: per CU, the time of the global loads that return
+// What the ablation builds of k16_linear_wide showed: per CU, the time of the global loads that return
 // through the register file and the time of the LDS-fed MFMA part ADD UP (35 + 75 -> 122 us).  Three quarters of those
 // register-returned bytes are the weight, which every workgroup re-reads (from L2) and re-rounds to bf16.  Here it is
 // rounded and laid out ONCE per use by k16_pack_wstream -- 1 KiB MFMA B-operand fragments in exactly the order a
@@ -448,7 +399,7 @@ __global__ __launch_bounds__(512) void k16_dw_wide(const float* __restrict__ dy,
         const bool more = n0 + kWideBK < nhi;
         const unsigned char* P = lds + buf * (kWideP + kWideQ);
         if (more) fetch(n0 + kWideBK);
-        wide_mma(P, P + kWideP, acc, wr, wc, lane, [](int) {});
+        wide_mma(P, P + kWideP, acc, wr, wc, lane);
         if (more) stage(buf ^ 1);
         __syncthreads();
     }

@@ -113,15 +113,8 @@ __device__ __forceinline__ void rows_load(const float* __restrict__ x, int tok, 
     const unsigned tokc = tok < 0 ? 0u : (unsigned)tok;
     const unsigned char* xb = reinterpret_cast<const unsigned char*>(x);
     const unsigned off = tokc * (unsigned)(kC * 4) + (unsigned)hh * 16u;
-#ifdef MDGEN_DEV_ROWS_COALESCED   // (experiment build: the same 48 KiB per wave read as 48 fully coalesced 1 KiB requests -- WRONG values,
-                                  // timing only: does the 32-byte-per-row request pattern cost HBM efficiency?)
-    const unsigned offc = (tokc & ~31u) * (unsigned)(kC * 4) + (unsigned)lane_id() * 16u;
-#pragma unroll
-    for (int i = 0; i < 48; ++i) v[i] = *reinterpret_cast<const f32x4*>(xb + offc + 1024u * i);
-#else
 #pragma unroll
     for (int i = 0; i < 48; ++i) v[i] = *reinterpret_cast<const f32x4*>(xb + off + 32u * i);
-#endif
 }
 __device__ __forceinline__ void rows_norm(const f32x4 (&v)[48], int tok, const ModMap mm, int shift_chunk, int scale_chunk,
                                           float eps, bf16x8 (&xf)[24]) {

@@ -1,5 +1,6 @@
 """GPU: the training step's attention kernels alone (mdgen_debug_train_attention, bf16 operands) at the ATLAS per-GPU shape,
-both axes, N repetitions -- to be run under rocprofv3 --stats (scripts/r04/attn16_variants.sh), product or experiment library."""
+both axes, N repetitions -- to be run under rocprofv3 --kernel-trace --stats for per-kernel averages (product library):
+    python scripts/micro/attn16_run.py [repetitions] [precision]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch

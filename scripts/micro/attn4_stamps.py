@@ -1,7 +1,7 @@
 """Dev tool (GPU): phase stamps of k_ln_qkv_attn4<true> (the L = 4 residue-axis sub-layer in one kernel) from the
-`KFILE=k_gemm KPFX=QKV bash scripts/micro/flash_variants.sh STAMPS` experiment build.
+`KFILE=k_gemm KPFX=QKV bash scripts/micro/dev_build.sh STAMPS` experiment build.
 
-    MDGEN_AMD_LIB=gpurun_out/dev_libs/libmdgen_amd_STAMPS.so python scripts/r05/attn4_stamps.py [workload]"""
+    MDGEN_AMD_LIB=build/dev_libs/libmdgen_amd_STAMPS.so python scripts/micro/attn4_stamps.py [workload]"""
 import ctypes as C
 import os
 import sys

@@ -1,7 +1,7 @@
 """Dev tool (GPU): per-wave cycle stamps of the attention kernel from the -DMDGEN_DEV_FLASH_STAMPS experiment build.
 
-    bash scripts/micro/flash_variants.sh STAMPS
-    MDGEN_AMD_LIB=gpurun_out/dev_libs/libmdgen_amd_STAMPS.so python scripts/micro/flash_stamps.py [workload]
+    bash scripts/micro/dev_build.sh STAMPS
+    MDGEN_AMD_LIB=build/dev_libs/libmdgen_amd_STAMPS.so python scripts/micro/flash_stamps.py [workload]
 
 Prints the shader clock actually sustained inside the kernel (s_memtime ticks per s_memrealtime tick, the latter a
 constant 100 MHz), the cycles one wave spends per (32-key, 32-query) pair in the loop, and the prologue / epilogue."""
@@ -25,6 +25,7 @@ cfg = ModelConfig(crop=L, num_frames=T, abs_pos_emb=abs_pos, sim_condition=True)
 w = NewMDGenWrapper(cfg, device=dev)
 w.model.load_state_dict(synth_state_dict(cfg, 0))
 w.model.set_option("streams", 1)
+w.model.set_option("flash_proj", 0)   # k_flash, the kernel this script reads (k_flash_proj: fproj_stamps.py)
 batch = bench.synth_batch(B, T, L, n_pad, dev, seed=100)
 zs = torch.randn(B, T, L, 21, generator=torch.Generator().manual_seed(137)).to(dev)
 w.inference(batch, zs=zs, num_steps=2, use_graph=False)

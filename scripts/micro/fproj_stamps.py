@@ -1,7 +1,7 @@
 """Dev tool (GPU): per-wave cycle stamps of k_flash_proj from the -DMDGEN_DEV_FLASH_STAMPS experiment build.
 
-    bash scripts/micro/flash_variants.sh STAMPS
-    MDGEN_AMD_LIB=gpurun_out/dev_libs/libmdgen_amd_STAMPS.so python scripts/r05/fproj_stamps.py [workload] [option=value ...]
+    bash scripts/micro/dev_build.sh STAMPS
+    MDGEN_AMD_LIB=build/dev_libs/libmdgen_amd_STAMPS.so python scripts/micro/fproj_stamps.py [workload] [option=value ...]
 
 Per wave: the four head-group jobs, the barrier wait, the out-projection GEMM, the residual epilogue; the shader clock
 (s_memtime ticks per 100 MHz s_memrealtime tick) and how the workgroups' lifetimes tile the launch."""
@@ -27,6 +27,7 @@ w = NewMDGenWrapper(cfg, device=dev)
 w.model.load_state_dict(synth_state_dict(cfg, 0))
 w.model.set_option("streams", 1)
 w.model.set_option("flash_proj", 2)
+w.model.set_option("flash_proj_form", 4)   # k_flash_proj, the stamped kernel (long sequences would take k_flash_proj8)
 for k, v in opts.items():
     w.model.set_option(k, v)
 batch = bench.synth_batch(B, T, L, n_pad, dev, seed=100)

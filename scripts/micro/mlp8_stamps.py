@@ -1,6 +1,6 @@
 """Dev tool (GPU): phase stamps of k_mlp8 (the eight-wave panel MLP kernel of the small launches; split form at B = 1) from the
-`KFILE=k_gemm KPFX=MLP8 bash scripts/micro/flash_variants.sh STAMPS` experiment build (stamps held in SGPRs, one store branch).
-    MDGEN_AMD_LIB=gpurun_out/dev_libs/libmdgen_amd_STAMPS.so python scripts/r06/mlp8_stamps.py [workload]"""
+`KFILE=k_gemm KPFX=MLP8 bash scripts/micro/dev_build.sh STAMPS` experiment build (stamps held in SGPRs, one store branch).
+    MDGEN_AMD_LIB=build/dev_libs/libmdgen_amd_STAMPS.so python scripts/micro/mlp8_stamps.py [workload]"""
 import ctypes as C
 import os
 import sys

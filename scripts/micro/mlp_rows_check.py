@@ -67,7 +67,8 @@ def timing(wl, S, path, streams=1, trace=False):
             print(f"    fused out-projection: rows + 24 blocks {np.mean(t[:, 6] - t[:, 0]):8.0f}  residual epilogue (keep) {np.mean(t[:, 7] - t[:, 6]):8.0f}  LayerNorm from registers {np.mean(t[:, 1] - t[:, 7]):8.0f} ticks")
         start = t[:, 0] - t0
         print(f"    wave start: first round <= {np.percentile(start, 45):.0f}, later median {np.percentile(start, 80):.0f}; lifetime mean {(t[:, 5] - t[:, 0]).mean():.0f}")
-        np.save(os.path.join(ROOT, "gpurun_out", "mlp_rows_trace.npy"), t)
+        os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
+        np.save(os.path.join(ROOT, "build", "mlp_rows_trace.npy"), t)
     return a
 
 a0 = timing("tetrapeptide_fwdsim_crop4_T1000_B16", 3, 0)

@@ -1,6 +1,6 @@
 """GPU: option train_streams 1 vs 2 -- same kernels, same summation orders: the gradients must be bit-identical."""
 import os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from mdgen_amd.config import ModelConfig
 from mdgen_amd.synthetic import synth_state_dict, synth_forward_inputs

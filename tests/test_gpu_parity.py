@@ -368,8 +368,8 @@ def test_attention_fixed_anchor_and_robust_loops_agree():
     P (the two shifts differ by a non-integer, so the mantissas of P differ): rel-L2 ~2e-3, the size of the bf16 error
     of the whole forward.  (b) With the q / k projections scaled so that scores move by hundreds of log2 units between
     key tiles, the fixed anchor overflows: the fallback must kick in and the result must stay finite and agree with the
-    robust loop (the experiment build -DMDGEN_DEV_FLASH_NOFALLBACK fails exactly here with non-finite outputs:
-    profiles/r02_flash_variants.txt).  (c) Padded residues (first tile fully masked on the time
+    robust loop (the round-2 build without the fallback, a switch since retired, produced non-finite outputs exactly
+    here: profiles/r02_flash_variants.txt).  (c) Padded residues (first tile fully masked on the time
     axis) take the robust loop from the start: covered by the n_pad > 0 shapes here and in the ATLAS goldens."""
     from mdgen_amd.config import ModelConfig
     from mdgen_amd.synthetic import synth_state_dict, synth_forward_inputs
