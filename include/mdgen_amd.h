@@ -674,6 +674,31 @@ int32_t mdgen_atom14_to_cond(int32_t B, int32_t L, const float* atom14, const in
                              float* rots, float* trans, float* torsions, float* torsion_mask,
                              void* stream);
 
+/* The text `mdgen.utils.atom14_to_pdb` writes (utils.py:58-102 -> protein.py:321-443) for M frames of one sequence, formatted
+ * on the device: per frame `MODEL <model_base + m>` (unpadded), one ATOM record per present atom in (residue, atom37) order, a
+ * TER record, `ENDMDL`; byte for byte what mdgen_amd/pdb.py frames_to_pdb_string gives for frames model_base .. model_base + M - 1
+ * of a trajectory.  An atom37 slot is present when (|x| + |y|) + |z| > 1e-7f (fp32, that order) of its gathered, masked position
+ * (utils.py:77).  A coordinate prints as Python's f"{x:>8.3f}": n = rint((double) x * 1000) (exact product, ties to even), then
+ * |n| / 1000, '.', |n| % 1000 in three digits, '-' when signbit(x); it fits its field when x is finite and
+ * -999999 <= n <= 9999999.  The kernels know no names:
+ *   atom14        (M, L, 14, 3) fp32;  aatype int64 (L), in [0, 20];  atom37_to_atom14 int64 [21][37], atom37_mask [21][37]
+ *   templates     uint8 [L][37][81]: the 80-column ATOM record of (residue, atom37 slot) + '\n' with the serial (columns 7-11) and
+ *                 the coordinates (columns 31-54) blank;  ter_template uint8 [81]: the TER record of the last residue, serial blank
+ *                 (mdgen_amd/pdb.py record_templates)
+ *   offsets       int64 [M + 1] out: frame m's text is text[offsets[m] .. offsets[m + 1]); no alignment of either is assumed
+ *   text          uint8 [text_capacity] out; M * (27 + 81 * (A + 1) + 7) bytes always suffice, A = atoms atom37_mask gives the sequence
+ *   status        int64 [2] out: [0] coordinates that do not fit their field (+ one per frame whose TER serial passes 99999, + one
+ *                 per table entry out of range); [1] the bytes needed, offsets[M]
+ * Three launches on `stream` (count, one-workgroup scan, format; csrc/k_pdb.hip), nothing synchronises.  The format pass writes
+ * NOTHING when status[0] > 0 or offsets[M] > text_capacity: the caller reads status back once and, for a trajectory with a field
+ * that overflows, formats on the host, where such fields come out as the reference writes them.
+ * -1: null pointer; -2: M < 1, L < 1, L > 9999 (the residue number has four columns), model_base < 0, text_capacity < 0. */
+int32_t mdgen_pdb_format(int64_t M, int32_t L, int64_t model_base, const float* atom14, const int64_t* aatype,
+                         const int64_t* atom37_to_atom14, const float* atom37_mask,
+                         const uint8_t* templates, const uint8_t* ter_template,
+                         int64_t* offsets /* M + 1 */, uint8_t* text, int64_t text_capacity,
+                         int64_t* status /* [2]: records that do not fit, bytes needed */, void* stream);
+
 /* Flow-matching training target (transport.py:138-189 `training_losses`, velocity model; path.py:113-135 `plan`
  * with GVPCPlan :177-187 or the linear ICPlan): per sample b with time t[b],
  *   xt = alpha x1 + sigma x0,  ut = alpha' x1 + sigma' x0;   GVP: alpha = sin(pi t/2), sigma = cos(pi t/2);

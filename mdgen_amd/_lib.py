@@ -19,7 +19,7 @@ EXPORTS = [
     "mdgen_debug_ipa_attention", "mdgen_debug_ipa_slices",
     "mdgen_rigid_compose", "mdgen_rigid_invert",
     "mdgen_rigid_apply", "mdgen_quat_to_rot", "mdgen_rot_to_quat", "mdgen_prep_latents", "mdgen_prep_keyframes", "mdgen_upsample_euler",
-    "mdgen_samples_to_atom14", "mdgen_atom14_to_cond", "mdgen_path_plan", "mdgen_masked_mse", "mdgen_from_3_points",
+    "mdgen_samples_to_atom14", "mdgen_atom14_to_cond", "mdgen_pdb_format", "mdgen_path_plan", "mdgen_masked_mse", "mdgen_from_3_points",
     "mdgen_grad_sumsq", "mdgen_adam_step", "mdgen_ema_update", "mdgen_train_workspace_bytes",
     "mdgen_train_forward_backward",
     "mdgen_train_num_milestones", "mdgen_train_bind_params",
@@ -146,6 +146,7 @@ def _load():
     lib.mdgen_prep_keyframes.argtypes = [C.POINTER(Shape), i32] + [vp] * 8
     lib.mdgen_samples_to_atom14.argtypes = [C.POINTER(Shape), i32, i32] + [vp] * 10
     lib.mdgen_atom14_to_cond.argtypes = [i32, i32] + [vp] * 11
+    lib.mdgen_pdb_format.argtypes = [i64, i32, i64] + [vp] * 8 + [i64, vp, vp]   # M, L, model_base | ... text, its capacity, status
     lib.mdgen_from_3_points.argtypes = [i64] + [vp] * 6
     lib.mdgen_path_plan.argtypes = [i64, i64, i32] + [vp] * 6
     lib.mdgen_masked_mse.argtypes = [i64, i64] + [vp] * 5

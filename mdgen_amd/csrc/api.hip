@@ -2324,6 +2324,20 @@ extern "C" int32_t mdgen_atom14_to_cond(int32_t B, int32_t L, const float* atom1
     LAUNCHCHK();
     return 0;
 }
+extern "C" int32_t mdgen_pdb_format(int64_t M, int32_t L, int64_t model_base, const float* atom14, const int64_t* aatype,
+                                    const int64_t* a37to14, const float* a37mask, const uint8_t* templates,
+                                    const uint8_t* ter_template, int64_t* offsets, uint8_t* text, int64_t text_capacity,
+                                    int64_t* status, void* stream) {
+    NONNULL(atom14, aatype, a37to14, a37mask, templates, ter_template, offsets, text, status);
+    if (M < 1 || L < 1 || L > 9999) return fail(-2, "M must be >= 1 and L in 1 .. 9999 (the residue number has four columns)");
+    if (model_base < 0 || model_base > INT64_MAX - M) return fail(-2, "model_base must be >= 0 (and model_base + M fit int64)");
+    if (text_capacity < 0) return fail(-2, "text_capacity must be >= 0");
+    HIPCHK(hipMemsetAsync(status, 0, 2 * sizeof(int64_t), (hipStream_t)stream));
+    launch_pdb_format(M, L, model_base, atom14, aatype, a37to14, a37mask, templates, ter_template, offsets, text, text_capacity,
+                      status, (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
 
 // ---------------------------------------------------------------------------------------------
 // flow-matching training target and loss (forward only)

@@ -614,4 +614,9 @@ void launch_atom14_to_cond(int B, int L, const float* atom14, long in_bstride, c
                            const int64_t* a37to14, const float* a37mask, const int64_t* chi_idx, const float* chi_mask,
                            float* rots, float* trans, float* tors, float* tmask, hipStream_t s);
 
+// multi-model PDB text (k_pdb.hip): count -> scan -> format; status[0] must be zero on entry
+void launch_pdb_format(long M, int L, long model_base, const float* atom14, const int64_t* aatype, const int64_t* a37to14,
+                       const float* a37mask, const uint8_t* templates, const uint8_t* ter_template, int64_t* offsets,
+                       uint8_t* text, long text_capacity, int64_t* status, hipStream_t s);
+
 }  // namespace mdg

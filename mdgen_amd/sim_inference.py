@@ -188,10 +188,11 @@ def run(args, model, device, names_seqres, rank=0, world=1, batch_fn=make_group_
         nfr = len(group) * args.num_rollouts * args.num_frames
         total_frames, total_s = total_frames + nfr, total_s + dur
         print(f"{','.join(group)}: {nfr / dur:.1f} frames/s ({dur:.3f} s, batch {len(group)})")
-        host = all_atom14.cpu().numpy()
+        # a device tensor is formatted on the device (pdb.py); the host copy is made only for what needs one
+        host = all_atom14.cpu().numpy() if args.npy or not all_atom14.is_cuda else None
         for i, n in enumerate(group):
             aat = np.array([restype_order[c] for c in seqres[n]])
-            atom14_to_pdb(host[i], aat, os.path.join(args.out_dir, f"{n}.pdb"))
+            atom14_to_pdb(all_atom14[i] if all_atom14.is_cuda else host[i], aat, os.path.join(args.out_dir, f"{n}.pdb"))
             if getattr(args, "xtc", False):
                 write_xtc(os.path.join(args.out_dir, f"{n}.pdb"), os.path.join(args.out_dir, f"{n}.xtc"))
             if args.npy:

@@ -97,10 +97,10 @@ def run(args, model, device, names_seqres, rank=0, world=1):
                 st = model.last_stats
                 print(f"{name} batch {i}: dopri5 {st['nfe']} network evaluations ({st['accepted']} accepted, "
                       f"{st['rejected']} rejected steps)")
-            host = atom14s.cpu().numpy()
+            paths = atom14s if atom14s.is_cuda else atom14s.cpu().numpy()   # (a device tensor is formatted on the device, pdb.py)
             for j in range(args.batch_size):
                 idx = i * args.batch_size + j
-                atom14_to_pdb(host[j], aat, os.path.join(args.out_dir, f"{name}_{idx}.pdb"))
+                atom14_to_pdb(paths[j], aat, os.path.join(args.out_dir, f"{name}_{idx}.pdb"))
         done.append(name)
     return {"names": done, "paths": len(done) * args.num_batches * args.batch_size}
 

@@ -114,10 +114,11 @@ def run(args, model, device, names_seqres, rank=0, world=1, sync=None):
         total_frames, total_s = total_frames + nfr, total_s + dur
         print(f"{name}: {nfr / dur:.1f} frames/s ({dur:.3f} s, {windows['trans'].shape[0]} windows of {T} frames, "
               f"batch {args.batch_size})")
-        host = atom14.cpu().numpy()
+        # a device tensor is formatted on the device (pdb.py); the host copy is made only for what needs one
+        host = atom14.cpu().numpy() if args.npy or not atom14.is_cuda else None
         aat = np.array([restype_order[ch] for ch in names_seqres[name]])
         path = os.path.join(args.out_dir, f"{name}.pdb")
-        atom14_to_pdb(host, aat, path)
+        atom14_to_pdb(atom14 if atom14.is_cuda else host, aat, path)
         if getattr(args, "xtc", False):
             write_xtc(path, os.path.join(args.out_dir, f"{name}.xtc"))
         if args.npy:
