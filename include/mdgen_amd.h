@@ -699,6 +699,43 @@ int32_t mdgen_pdb_format(int64_t M, int32_t L, int64_t model_base, const float* 
                          int64_t* offsets /* M + 1 */, uint8_t* text, int64_t text_capacity,
                          int64_t* status /* [2]: records that do not fit, bytes needed */, void* stream);
 
+/* Analysis of a sampled trajectory on the device (csrc/k_analysis.hip; mdgen_amd/analysis.py): the parts of the reference's
+ * scripts/analyze_peptide_sim.py that need no third-party estimator.  All three run on `stream` and synchronise nothing.  The index
+ * tables `quad` and `pairs` are HOST arrays: they are checked here and travel as kernel arguments; every other pointer is device
+ * memory.  Every refusal is decided before any device call.  NF = 0 succeeds and writes nothing.
+ *
+ * mdgen_traj_dihedrals: angles[f][j] = the IUPAC dihedral of atoms quad[j][0 .. 3] of frame f, in fp32:
+ *   b1 = p1 - p0, b2 = p2 - p1, b3 = p3 - p2, c1 = b2 x b3, c2 = b1 x b2, atan2(|b2| (b1 . c1), c1 . c2); 0 when both arguments
+ *   are zero (coincident or collinear atoms), never NaN for finite input.
+ *   atom14 (F, L, 14, 3) fp32;  quad int32 [NF][4], indices into a frame's L * 14 atoms;  angles (F, NF) fp32 out.
+ * -1: null pointer; -2: F < 1, L < 1, NF < 0 or > 32768, a quadruple index outside 0 .. L * 14 - 1. */
+int32_t mdgen_traj_dihedrals(int64_t F, int32_t L, int32_t NF, const float* atom14, const int32_t* quad /* host */,
+                             float* angles, void* stream);
+
+/* mdgen_traj_histograms: NF one-dimensional histograms of the columns of angles (F, NF) and P two-dimensional ones of the column
+ * pairs (pairs[p][0], pairs[p][1]), in one launch per 64 pairs.  edges1 fp64 [bins1 + 1] and edges2 fp64 [bins2 + 1] are ascending
+ * bin edges (np.linspace(-np.pi, np.pi, bins + 1) for the reference's histograms).  A value x, widened to fp64, goes to bin
+ * searchsorted(edges, x, 'right') - 1, a value equal to the last edge to the last bin, a value outside [edges[0], edges[bins]] (or
+ * NaN) nowhere: it is counted in dropped.  float32(pi) > np.pi is such a value, as it is for np.histogram.  A 2-D sample is dropped
+ * when either coordinate is.
+ *   hist1 int64 [NF][bins1], hist2 int64 [P][bins2][bins2] (first index: the pair's first feature), dropped int64 [NF + P]
+ *   (features, then pairs): all three are zeroed and filled.  Counts gather per workgroup in LDS (integer atomics), then in global memory.
+ * -1: null pointer; -2: F < 1, bins1 < 1 or > 16384, bins2 < 1 or > 128, NF or P < 0 or > 32768, a pair index outside 0 .. NF - 1. */
+int32_t mdgen_traj_histograms(int64_t F, int32_t NF, const float* angles, int32_t bins1, const double* edges1, int32_t P,
+                              const int32_t* pairs /* host */, int32_t bins2, const double* edges2, int64_t* hist1,
+                              int64_t* hist2, int64_t* dropped, void* stream);
+
+/* mdgen_traj_acov: for every column f of angles (n, NF) and lag k = 0 .. K
+ *   acov[f][k] = (sum_{t = 0}^{n - k - 1} sin a_t sin a_{t + k} + cos a_t cos a_{t + k}) / (n - k)
+ * -- statsmodels' acovf(sin) + acovf(cos) with demean=False, adjusted=True -- and mean_sin[f], mean_cos[f], the means over t.
+ * sin and cos are evaluated in fp64 and rounded to fp32 once; products and sums of 256 samples are fp32, everything beyond is fp64
+ * in a fixed order, without floating-point atomics: two calls give the same bits.
+ *   acov fp64 [NF][K + 1], mean_sin, mean_cos fp64 [NF] out;  workspace: mdgen_traj_acov_workspace_bytes(n, NF, K), 16-byte aligned.
+ * -1: null pointer; -2: n < 1, K < 0, K > n - 1, NF < 0 or > 32768, NF * (K + 1) beyond one launch; -3: workspace too small. */
+int32_t mdgen_traj_acov_workspace_bytes(int64_t n, int32_t NF, int64_t K, size_t* bytes);
+int32_t mdgen_traj_acov(int64_t n, int32_t NF, int64_t K, const float* angles, double* acov, double* mean_sin, double* mean_cos,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* Flow-matching training target (transport.py:138-189 `training_losses`, velocity model; path.py:113-135 `plan`
  * with GVPCPlan :177-187 or the linear ICPlan): per sample b with time t[b],
  *   xt = alpha x1 + sigma x0,  ut = alpha' x1 + sigma' x0;   GVP: alpha = sin(pi t/2), sigma = cos(pi t/2);

@@ -29,6 +29,7 @@ EXPORTS = [
     "mdgen_rollout_rk", "mdgen_upsample_rk",
     "mdgen_sample_sde", "mdgen_sde_workspace_bytes", "mdgen_debug_sde_plan", "mdgen_debug_sde_dispatch_plan", "mdgen_debug_sde_stage",
     "mdgen_sample_sde_rng", "mdgen_debug_sde_noise", "mdgen_debug_sde_stage_rng", "mdgen_debug_philox", "mdgen_rollout_sde", "mdgen_upsample_sde", "mdgen_debug_graph_count",
+    "mdgen_traj_dihedrals", "mdgen_traj_histograms", "mdgen_traj_acov", "mdgen_traj_acov_workspace_bytes",
 ]
 
 
@@ -147,6 +148,10 @@ def _load():
     lib.mdgen_samples_to_atom14.argtypes = [C.POINTER(Shape), i32, i32] + [vp] * 10
     lib.mdgen_atom14_to_cond.argtypes = [i32, i32] + [vp] * 11
     lib.mdgen_pdb_format.argtypes = [i64, i32, i64] + [vp] * 8 + [i64, vp, vp]   # M, L, model_base | ... text, its capacity, status
+    lib.mdgen_traj_dihedrals.argtypes = [i64, i32, i32, vp, vp, vp, vp]   # F, L, NF | atom14, quad (host), angles
+    lib.mdgen_traj_histograms.argtypes = [i64, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]   # F, NF, angles | bins1, edges1 | P, pairs (host) | bins2, edges2 | ...
+    lib.mdgen_traj_acov_workspace_bytes.argtypes = [i64, i32, i64, C.POINTER(sz)]
+    lib.mdgen_traj_acov.argtypes = [i64, i32, i64, vp, vp, vp, vp, vp, sz, vp]   # n, NF, K | angles, acov, mean_sin, mean_cos | workspace, bytes
     lib.mdgen_from_3_points.argtypes = [i64] + [vp] * 6
     lib.mdgen_path_plan.argtypes = [i64, i64, i32] + [vp] * 6
     lib.mdgen_masked_mse.argtypes = [i64, i64] + [vp] * 5

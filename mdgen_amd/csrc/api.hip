@@ -2340,6 +2340,81 @@ extern "C" int32_t mdgen_pdb_format(int64_t M, int32_t L, int64_t model_base, co
 }
 
 // ---------------------------------------------------------------------------------------------
+// trajectory analysis (k_analysis.hip): every refusal is decided on the host, before a device call
+// ---------------------------------------------------------------------------------------------
+constexpr int64_t kTrajMaxFrames = (int64_t)1 << 40;
+constexpr int32_t kTrajMaxFeatures = 32768;
+
+extern "C" int32_t mdgen_traj_dihedrals(int64_t F, int32_t L, int32_t NF, const float* atom14, const int32_t* quad, float* angles,
+                                        void* stream) {
+    if (F < 1 || F > kTrajMaxFrames) return fail(-2, "F must be in 1 .. 2^40");
+    if (L < 1 || L > (1 << 20)) return fail(-2, "L must be in 1 .. 2^20");
+    if (NF < 0 || NF > kTrajMaxFeatures) return fail(-2, "NF must be in 0 .. 32768");
+    if (NF == 0) return 0;
+    NONNULL(atom14, quad, angles);
+    for (int64_t i = 0; i < (int64_t)NF * 4; ++i)
+        if (quad[i] < 0 || quad[i] >= L * 14)
+            return fail(-2, "quad[%lld][%d] = %d is outside the frame's %d atoms", (long long)(i / 4), (int)(i % 4), quad[i], L * 14);
+    launch_dihedrals(F, L, NF, atom14, quad, angles, (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
+
+extern "C" int32_t mdgen_traj_histograms(int64_t F, int32_t NF, const float* angles, int32_t bins1, const double* edges1, int32_t P,
+                                         const int32_t* pairs, int32_t bins2, const double* edges2, int64_t* hist1, int64_t* hist2,
+                                         int64_t* dropped, void* stream) {
+    if (F < 1 || F > kTrajMaxFrames) return fail(-2, "F must be in 1 .. 2^40");
+    if (NF < 0 || NF > kTrajMaxFeatures) return fail(-2, "NF must be in 0 .. 32768");
+    if (P < 0 || P > kTrajMaxFeatures) return fail(-2, "P must be in 0 .. 32768");
+    if (bins1 < 1 || bins1 > kHistMaxCells) return fail(-2, "bins1 must be in 1 .. %d", kHistMaxCells);
+    if (bins2 < 1 || bins2 * (int64_t)bins2 > kHistMaxCells) return fail(-2, "bins2 must be in 1 .. 128");
+    if (NF == 0 && P > 0) return fail(-2, "pairs of no features");
+    if (NF == 0) return 0;
+    NONNULL(angles, edges1, hist1, dropped);
+    if (P > 0) {
+        NONNULL(pairs, edges2, hist2);
+    }
+    for (int64_t i = 0; i < (int64_t)P * 2; ++i)
+        if (pairs[i] < 0 || pairs[i] >= NF)
+            return fail(-2, "pairs[%lld][%d] = %d is outside the %d features", (long long)(i / 2), (int)(i % 2), pairs[i], NF);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(hist1, 0, (size_t)NF * bins1 * sizeof(int64_t), s));
+    if (P > 0) HIPCHK(hipMemsetAsync(hist2, 0, (size_t)P * bins2 * bins2 * sizeof(int64_t), s));
+    HIPCHK(hipMemsetAsync(dropped, 0, (size_t)(NF + P) * sizeof(int64_t), s));
+    launch_torsion_hist(F, NF, angles, bins1, edges1, P, pairs, bins2, edges2, hist1, hist2, dropped, s);
+    LAUNCHCHK();
+    return 0;
+}
+
+static int traj_acov_shape(int64_t n, int32_t NF, int64_t K) {
+    if (n < 1 || n > kTrajMaxFrames) return fail(-2, "n must be in 1 .. 2^40");
+    if (NF < 0 || NF > kTrajMaxFeatures) return fail(-2, "NF must be in 0 .. 32768");
+    if (K < 0 || K > n - 1) return fail(-2, "K must be in 0 .. n - 1 (n = %lld, K = %lld)", (long long)n, (long long)K);
+    if (NF > 0 && acov_groups(n, NF, K) >= ((int64_t)1 << 31)) return fail(-2, "NF * (K + 1) is beyond one launch's grid");
+    return 0;
+}
+
+extern "C" int32_t mdgen_traj_acov_workspace_bytes(int64_t n, int32_t NF, int64_t K, size_t* bytes) {
+    NONNULL(bytes);
+    if (int rc = traj_acov_shape(n, NF, K)) return rc;
+    *bytes = NF == 0 ? 0 : acov_workspace_bytes(n, NF, K);
+    return 0;
+}
+
+extern "C" int32_t mdgen_traj_acov(int64_t n, int32_t NF, int64_t K, const float* angles, double* acov, double* mean_sin,
+                                   double* mean_cos, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = traj_acov_shape(n, NF, K)) return rc;
+    if (NF == 0) return 0;
+    NONNULL(angles, acov, mean_sin, mean_cos, workspace);
+    const size_t need = acov_workspace_bytes(n, NF, K);
+    if (workspace_bytes < need) return fail(-3, "workspace too small: %zu < %zu", workspace_bytes, need);
+    if ((uintptr_t)workspace % 16) return fail(-2, "workspace must be 16-byte aligned");
+    launch_sincos_acov(n, NF, K, angles, acov, mean_sin, mean_cos, workspace, (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // flow-matching training target and loss (forward only)
 // ---------------------------------------------------------------------------------------------
 extern "C" int32_t mdgen_path_plan(int64_t B, int64_t per_sample, int32_t path_type, const float* t, const float* x0,

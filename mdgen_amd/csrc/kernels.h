@@ -619,4 +619,25 @@ void launch_pdb_format(long M, int L, long model_base, const float* atom14, cons
                        const float* a37mask, const uint8_t* templates, const uint8_t* ter_template, int64_t* offsets,
                        uint8_t* text, long text_capacity, int64_t* status, hipStream_t s);
 
+// trajectory analysis (k_analysis.hip).  The index tables are HOST arrays, checked by the caller: they travel as kernel arguments,
+// kQuadChunk quadruples / kPairChunk pairs a launch.
+constexpr int kQuadChunk = 64;
+constexpr int kPairChunk = 64;
+constexpr int kHistMaxCells = 16384;   // ints of LDS a histogram may take: bins1 and bins2 * bins2
+struct QuadChunk {
+    int q[kQuadChunk][4];
+};
+struct PairChunk {
+    int p[kPairChunk][2];
+};
+void launch_dihedrals(long F, int L, int NF, const float* atom14, const int32_t* quad_host, float* angles, hipStream_t s);
+// hist1 [NF][bins1], hist2 [P][bins2][bins2] and dropped [NF + P] must be zero on entry
+void launch_torsion_hist(long F, int NF, const float* angles, int bins1, const double* edges1, int P, const int32_t* pairs_host,
+                         int bins2, const double* edges2, int64_t* hist1, int64_t* hist2, int64_t* dropped, hipStream_t s);
+int acov_splits(long n, int NF, long K);
+size_t acov_workspace_bytes(long n, int NF, long K);
+long acov_groups(long n, int NF, long K);   // workgroups of k_sincos_acov
+void launch_sincos_acov(long n, int NF, long K, const float* angles, double* acov, double* mean_sin, double* mean_cos, void* ws,
+                        hipStream_t s);
+
 }  // namespace mdg

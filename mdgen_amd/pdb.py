@@ -120,6 +120,42 @@ def frames_to_pdb_string(atom14: np.ndarray, aatype: np.ndarray) -> str:
     return "\n".join(out) + "\n"
 
 
+def pdb_to_atom14(path, aatype) -> np.ndarray:
+    """The inverse of `atom14_to_pdb` for this project's own files: float32 [M, L, 14, 3] of the M models of `path`, the
+    coordinates as printed (three decimals), absent atoms zero.  It reads the fixed columns `_atom_record` writes -- atom name
+    13-16, residue number 23-26, x / y / z 31-54 -- and nothing else of the PDB format; host only, NumPy only."""
+    t = residue_tables()
+    aatype = _checked_aatype(aatype)
+    L = aatype.shape[0]
+    lines = open(path, "rb").read().split(b"\n")
+    is_atom = np.fromiter((ln.startswith(b"ATOM") for ln in lines), bool, len(lines))
+    is_model = np.fromiter((ln.startswith(b"MODEL") for ln in lines), bool, len(lines))
+    M = int(is_model.sum())
+    out = np.zeros((M, L, 14, 3), np.float32)
+    if not is_atom.any():
+        return out
+    model = (np.cumsum(is_model) - 1)[is_atom]
+    short = [i for i in np.nonzero(is_atom)[0] if len(lines[i]) < 54]
+    if short or model.min() < 0:
+        raise ValueError(f"{path}: an ATOM record is shorter than 54 columns, or stands in front of the first MODEL line")
+    rec = np.frombuffer(b"".join(lines[i][:54] for i in np.nonzero(is_atom)[0]), np.uint8).reshape(-1, 54)
+    res = np.ascontiguousarray(rec[:, 22:26]).view("S4").ravel().astype(np.int64)
+    names = np.char.strip(np.ascontiguousarray(rec[:, 12:16]).view("S4").ravel())
+    k37_of = {str(a).encode(): k for k, a in enumerate(t["atom_types"])}
+    uniq, inv = np.unique(names, return_inverse=True)
+    unknown = [u.decode() for u in uniq if u not in k37_of]
+    if unknown or res.min() < 0 or res.max() >= L:
+        raise ValueError(f"{path}: atom names {unknown} or residue numbers outside 0 .. {L - 1}: not this sequence's file")
+    k37 = np.array([k37_of[u] for u in uniq], np.int64)[inv]
+    aa = aatype[res]
+    if not np.all(np.asarray(t["atom37_mask"])[aa, k37] > 0):
+        raise ValueError(f"{path}: an atom that its residue type does not have: not this sequence's file")
+    slot = np.asarray(t["atom37_to_atom14"])[aa, k37]
+    for c in range(3):
+        out[model, res, slot, c] = np.ascontiguousarray(rec[:, 30 + 8 * c:38 + 8 * c]).view("S8").ravel().astype(np.float64)
+    return out
+
+
 def sequence_atoms(aatype) -> int:
     """Atoms `atom37_mask` gives the sequence: the most ATOM records a frame can have."""
     return int(np.asarray(residue_tables()["atom37_mask"])[_checked_aatype(aatype)].sum())

@@ -16,7 +16,11 @@
                      handles chunk `chunk_idx` of `n_chunks` of the split.  Under `torch.distributed.run`
                      (RANK / WORLD_SIZE in the environment) the chunk is further sharded over the ranks -- one
                      process per GPU, no data-path collective (mdgen_amd/sharding.py);
-  --synthetic        seeded weights instead of --sim_ckpt;  --npy  also save the sampled array.
+  --synthetic        seeded weights instead of --sim_ckpt;  --npy  also save the sampled array;
+  --analyze          after each group is sampled, `mdgen_amd.analysis.analyze` runs on the device tensor against the peptide's
+                     conditioning array (the MD trajectory `{data_dir}/{name}{suffix}.npy`): torsion JSDs and decorrelation curves,
+                     `{out_dir}/analysis.pkl` = {name: result} at the end.  Its time is outside the reported frames/s and printed
+                     on its own line.
 
 The rollout (sim_inference.py:61-98) stays on the device: each block's last frame becomes the next block's
 conditioning frame through `mdgen_atom14_to_cond` (no D->H->D round trip).  Output, as the reference
@@ -174,6 +178,7 @@ def run(args, model, device, names_seqres, rank=0, world=1, batch_fn=make_group_
     split_index = {n: i for i, n in enumerate(names_seqres)}
     os.makedirs(args.out_dir, exist_ok=True)
     total_frames, total_s = 0, 0.0
+    analysis, analysis_s = {}, 0.0
     if dist is not None:
         dist.barrier()
     for group in group_batches(names, seqres, args.batch):
@@ -197,10 +202,22 @@ def run(args, model, device, names_seqres, rank=0, world=1, batch_fn=make_group_
                 write_xtc(os.path.join(args.out_dir, f"{n}.pdb"), os.path.join(args.out_dir, f"{n}.xtc"))
             if args.npy:
                 np.save(os.path.join(args.out_dir, f"{n}.npy"), host[i])
+            if getattr(args, "analyze", False):
+                from .analysis import analyze
+                sync()
+                start = time.time()
+                analysis[n] = analyze(all_atom14[i], arrs[n], aat)
+                sync()
+                analysis_s += time.time() - start
     job_s = max_over_ranks(total_s, dist)
     job_frames = sum_over_ranks(total_frames, dist)
     if dist is not None:
         dist.barrier()
+    if getattr(args, "analyze", False):
+        import pickle
+        with open(os.path.join(args.out_dir, "analysis.pkl" if world == 1 else f"analysis.rank{rank}.pkl"), "wb") as f:
+            pickle.dump(analysis, f)
+        print(f"analysis: {len(analysis)} peptides in {analysis_s:.3f} s (not part of the frames/s above)")
     if job_s > 0:
         print(f"rank {rank}/{world}: {len(names)} peptides, {total_frames} frames in {total_s:.3f} s; "
               f"job: {job_frames / job_s:.1f} frames/s")
@@ -231,6 +248,8 @@ def build_parser():
                    help="bf16 MFMA operands (default) or the fp32-operand tolerance mode (~10x slower)")
     p.add_argument("--synthetic", action="store_true", help="seeded synthetic weights instead of --sim_ckpt")
     p.add_argument("--npy", action="store_true", help="also save the sampled atom14 array as .npy")
+    p.add_argument("--analyze", action="store_true",
+                   help="torsion JSDs and decorrelation curves against the conditioning trajectory -> {out_dir}/analysis.pkl")
     return p
 
 

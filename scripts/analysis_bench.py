@@ -1,0 +1,131 @@
+"""Time of each leg of the trajectory analysis, device events around enqueued work, one JSON line per leg:
+
+  dihedrals     `mdgen_traj_dihedrals`: F = 100 000 frames of a tetrapeptide, 16 torsions (and L = 8, 35 torsions)
+  histograms    `mdgen_traj_histograms`: the 100-bin histograms of every torsion and two 50 x 50 ones, same F
+  acov          `mdgen_traj_acov` at the sampler's size (n 1e5, K 1000, NF 25) and at the reference's MD size (n 1e6, K 1e5)
+  fft           the same autocovariance through torch.fft on the same device (fp32, zero-padded to 2^ceil(log2(2 n))): for scale
+  numpy         the same through np.fft on the host (fp64), sampler size only: what a script without the device would do
+
+    python scripts/analysis_bench.py [--leg all|dihedrals|histograms|acov|fft|numpy] [--size sampler|md|both] [--reps 5]
+
+acov reports multiply-adds (2 n' (K + 1) NF with n' the mean number of terms per lag) over time and that rate's share of the
+fp32 vector peak (157.3 TFLOP/s = 78.6e12 multiply-adds / s)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+SIZES = {"sampler": (100000, 1000, 25), "md": (1000000, 100000, 25)}
+FMA_PEAK = 256 * 4 * 32 * 2.4e9
+
+
+def timed_ms(fn, reps):
+    """Best and median of `reps` event-timed calls after one warm-up."""
+    fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return min(ms), float(np.median(ms))
+
+
+def angles(n, NF, dev):
+    g = torch.Generator().manual_seed(0)
+    x = torch.cumsum(0.2 * torch.randn(n, NF, generator=g), 0)
+    return torch.atan2(torch.sin(x), torch.cos(x)).to(dev).contiguous()
+
+
+def macs(n, K, NF):
+    k = np.arange(K + 1, dtype=np.float64)
+    return 2.0 * NF * float((n - k).sum())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--leg", default="all", choices=["all", "dihedrals", "histograms", "acov", "fft", "numpy"])
+    ap.add_argument("--size", default="both", choices=["sampler", "md", "both"])
+    ap.add_argument("--reps", type=int, default=5)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("analysis_bench needs the GPU: there is nothing to time without one")
+    from mdgen_amd import analysis as A
+    dev = torch.device("cuda")
+    want = lambda leg: a.leg in ("all", leg)   # noqa: E731
+    sizes = [s for s in SIZES if a.size in ("both", s)]
+    F = 100000
+    if want("dihedrals") or want("histograms"):
+        for seq in ([3, 10, 1, 8], [3, 10, 1, 8, 17, 11, 6, 13]):
+            aat = np.array(seq)
+            labels, quad = A.torsion_features(aat)
+            atom14 = (torch.randn(F, len(aat), 14, 3, generator=torch.Generator().manual_seed(1)) * 3).to(dev)
+            ang = torch.empty(F, len(quad), device=dev)
+            if want("dihedrals"):
+                best, med = timed_ms(lambda: A.dihedrals_into(atom14, quad, ang), a.reps * 4)
+                print(json.dumps({"leg": "dihedrals", "F": F, "L": len(aat), "NF": len(quad), "ms_best": best, "ms_median": med,
+                                  "GB_per_s": (atom14.numel() + ang.numel()) * 4 / best / 1e6}))
+            if want("histograms"):
+                A.dihedrals_into(atom14, quad, ang)
+                pairs = np.array(A.DEFAULT_PAIRS, np.int32)
+                e1, e2 = (torch.from_numpy(A.hist_edges(b)).to(dev) for b in (A.BINS_1D, A.BINS_2D))
+                h1 = torch.empty(len(quad), A.BINS_1D, dtype=torch.int64, device=dev)
+                h2 = torch.empty(2, A.BINS_2D, A.BINS_2D, dtype=torch.int64, device=dev)
+                dr = torch.empty(len(quad) + 2, dtype=torch.int64, device=dev)
+                best, med = timed_ms(lambda: A.histograms_into(ang, pairs, A.BINS_1D, e1, A.BINS_2D, e2, h1, h2, dr), a.reps * 4)
+                print(json.dumps({"leg": "histograms", "F": F, "NF": len(quad), "P": 2, "ms_best": best, "ms_median": med}))
+    for size in sizes:
+        n, K, NF = SIZES[size]
+        ang = angles(n, NF, dev)
+        if want("acov"):
+            ws = torch.empty(A.acov_workspace_bytes(n, NF, K), dtype=torch.uint8, device=dev)
+            acov = torch.empty(NF, K + 1, dtype=torch.float64, device=dev)
+            ms_, mc_ = torch.empty(NF, dtype=torch.float64, device=dev), torch.empty(NF, dtype=torch.float64, device=dev)
+            best, med = timed_ms(lambda: A.acov_into(ang, K, acov, ms_, mc_, ws), a.reps)
+            rate = macs(n, K, NF) / (best * 1e-3)
+            print(json.dumps({"leg": "acov", "size": size, "n": n, "K": K, "NF": NF, "ms_best": best, "ms_median": med,
+                              "workspace_MB": ws.numel() / 1e6, "fma_per_s": rate, "share_of_fp32_vector_peak": rate / FMA_PEAK}))
+        if want("fft"):
+            m = 1 << int(np.ceil(np.log2(2 * n)))
+
+            def via_fft():
+                out = 0
+                for x in (torch.sin(ang), torch.cos(ang)):
+                    f = torch.fft.rfft(x.t().contiguous(), m)
+                    out = out + torch.fft.irfft(f * f.conj(), m)[:, :K + 1]
+                return out / (n - torch.arange(K + 1, device=dev))
+            best, med = timed_ms(via_fft, a.reps)
+            print(json.dumps({"leg": "fft", "size": size, "n": n, "K": K, "NF": NF, "fft_points": m, "dtype": "float32",
+                              "ms_best": best, "ms_median": med}))
+            if want("acov"):   # what the fp32 FFT costs in accuracy, beside the kernel, against the fp64 FFT on the host (one feature)
+                a64 = ang[:, :1].double().cpu().numpy()
+                ref = np.zeros(K + 1)
+                for x in (np.sin(a64[:, 0]), np.cos(a64[:, 0])):
+                    f = np.fft.rfft(x, m)
+                    ref += np.fft.irfft(f * np.conj(f), m)[:K + 1]
+                ref /= n - np.arange(K + 1)
+                print(json.dumps({"leg": "accuracy", "size": size, "max_abs_err_kernel": float(np.abs(acov[0].cpu().numpy() - ref).max()),
+                                  "max_abs_err_torch_fft_fp32": float(np.abs(via_fft()[0].double().cpu().numpy() - ref).max())}))
+        if want("numpy") and size == "sampler":
+            host = ang.double().cpu().numpy()
+            m = 1 << int(np.ceil(np.log2(2 * n)))
+            t0 = time.perf_counter()
+            out = np.zeros((K + 1, NF))
+            for x in (np.sin(host), np.cos(host)):
+                f = np.fft.rfft(x, m, axis=0)
+                out += np.fft.irfft(f * np.conj(f), m, axis=0)[:K + 1]
+            dt = time.perf_counter() - t0
+            print(json.dumps({"leg": "numpy", "size": size, "n": n, "K": K, "NF": NF, "dtype": "float64", "ms": dt * 1e3}))
+
+
+if __name__ == "__main__":
+    main()
