@@ -280,7 +280,8 @@ int32_t mdgen_debug_dopri5_controller(const double* init, const double* ratios, 
  * stream; cached per shape, method, n_steps and pointers, like mdgen_sample_euler).  Both precision modes.
  *   x            (B,T,L,D) fp32, 16-byte aligned: the noise on entry, the state at t = 1 on exit
  *   workspace    mdgen_rk_workspace_bytes: the network workspace for the call's t-shared time rows (2 S, 3 S, 3 S + 1) + 4 velocities
- * The state of a stage is formed inside the launch that embeds it (k_rk_embed) and never written to memory.
+ * The state of a stage is formed inside the launch that embeds it (k_rk_embed: the token-embedding kernel's own body on a state
+ * computed in its staging prologue) and never written to memory.
  * Errors: -1 null argument, -2 unknown method or n_steps < 1, -7 alignment / workspace size. */
 int32_t mdgen_sample_rk(mdgen_ctx* ctx, const mdgen_shape* shape, int32_t method, int32_t n_steps, float* x, const mdgen_cond* cond,
                         void* workspace, size_t workspace_bytes, int32_t use_graph, void* stream);

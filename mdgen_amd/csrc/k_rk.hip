@@ -1,9 +1,9 @@
 // k_rk.hip -- the device side of the fixed-grid Runge-Kutta sampler (ode.inc: midpoint, heun3, rk4 on t = linspace(0, 1, S + 1)).
-//   k_rk_embed   the token embedding (k_embed, k_small.hip) of a state that exists only inside the launch: the staging prologue forms
-//                the token's D values from y0 and up to four velocities (RkState), stages them in LDS and embeds them.  The first stage
-//                of step i + 1 is the launch that forms y1 of step i: it also stores y1 over y0.
+//   k_rk_embed   k_embed's body (state_embed.h) on a state that exists only inside the launch: the staging prologue forms the token's
+//                D values from y0 and up to four velocities (RkState), stages them in LDS and embeds them.  The first stage of step
+//                i + 1 is the launch that forms y1 of step i: it also stores y1 over y0.
 //   k_rk_update  the same arithmetic without the embedding: the result of the last step.
-// Both bodies are state_embed.h's (shared with k_sde.hip); this file holds the arithmetic of the states.
+// Both bodies are state_embed.h's (shared with k_small.hip and k_sde.hip); this file holds the arithmetic of the states.
 // A network evaluation outside the Euler graph otherwise starts with k_embed reading a state that a separate k_ode_combine launch
 // has just written: one launch and one round trip of the state through HBM per evaluation.
 // Every written operation of a state is one rounded fp32 operation (the formulas are torchdiffeq's fixed_grid.py / rk_common.py,
@@ -30,7 +30,7 @@ template <bool POS, bool IPA, int kEmbTok>
 __global__ __launch_bounds__(256) void k_rk_embed(const EmbedParams p, const RkState st) {
     const float* const ops[kRkMaxK] = {st.nk > 0 ? st.k[0] : nullptr, st.nk > 1 ? st.k[1] : nullptr, st.nk > 2 ? st.k[2] : nullptr,
                                        st.nk > 3 ? st.k[3] : nullptr};
-    state_embed<POS, IPA, kEmbTok>(p, st.y, st.store, ops, [&](float y0, const float* k, long) { return rk_state(st, y0, k[0], k[1], k[2], k[3]); });
+    state_embed<POS, IPA, kEmbTok>(p, st.y, st.store ? st.y : nullptr, ops, [&](float y0, const float* k, long) { return rk_state(st, y0, k[0], k[1], k[2], k[3]); });
 }
 
 __global__ __launch_bounds__(256) void k_rk_update(const RkState st, long n) {
@@ -39,12 +39,14 @@ __global__ __launch_bounds__(256) void k_rk_update(const RkState st, long n) {
     state_update(st.y, ops, n, [&](float y0, const float* k, long) { return rk_state(st, y0, k[0], k[1], k[2], k[3]); });
 }
 
-void launch_rk_embed(const EmbedParams& p, const RkState& st, hipStream_t s) { MDG_LAUNCH_STATE_EMBED(k_rk_embed, p, st, s); }
+void launch_rk_embed(const EmbedParams& p, const RkState& st, hipStream_t s) {
+    embed_dispatch(p, [&](auto pos, auto ipa, auto tok, dim3 g) {
+        hipLaunchKernelGGL((k_rk_embed<decltype(pos)::value, decltype(ipa)::value, decltype(tok)::value>), g, dim3(256), 0, s, p, st);
+    });
+}
 
 void launch_rk_update(const RkState& st, long n, hipStream_t s) {
-    const long n4 = n >> 2;
-    const long nb = (n4 + 255) / 256;
-    hipLaunchKernelGGL(k_rk_update, dim3((unsigned)(nb > 0 ? nb : 1)), dim3(256), 0, s, st, n);
+    hipLaunchKernelGGL(k_rk_update, state_update_grid(n), dim3(256), 0, s, st, n);
 }
 
 }  // namespace mdg

@@ -70,12 +70,12 @@ __device__ __forceinline__ float sde_noise(const SdeRng& g, long e) {
 template <bool RNG, bool POS, bool IPA, int kEmbTok>
 __device__ __forceinline__ void sde_embed(const EmbedParams& p, const SdeState& st) {
     const float* const ops[3] = {st.v[0], st.v[1], RNG ? nullptr : st.xi};
+    float* const store = st.store ? st.y : nullptr;
     if constexpr (RNG) {
         const SdeRng g = sde_rng_of(st);
-        state_embed<POS, IPA, kEmbTok>(p, st.y, st.store, ops,
-                                       [&](float x, const float* o, long e) { return sde_state(st, x, o[0], o[1], sde_noise(g, e)); });
+        state_embed<POS, IPA, kEmbTok>(p, st.y, store, ops, [&](float x, const float* o, long e) { return sde_state(st, x, o[0], o[1], sde_noise(g, e)); });
     } else {
-        state_embed<POS, IPA, kEmbTok>(p, st.y, st.store, ops, [&](float x, const float* o, long) { return sde_state(st, x, o[0], o[1], o[2]); });
+        state_embed<POS, IPA, kEmbTok>(p, st.y, store, ops, [&](float x, const float* o, long) { return sde_state(st, x, o[0], o[1], o[2]); });
     }
 }
 template <bool POS, bool IPA, int kEmbTok>
@@ -100,14 +100,16 @@ __global__ __launch_bounds__(256) void k_sde_update(const SdeState st, long n) {
 
 // (only a noise-reading state carries st.rng: sde.inc with_noise)
 void launch_sde_embed(const EmbedParams& p, const SdeState& st, hipStream_t s) {
-    if (st.rng) MDG_LAUNCH_STATE_EMBED(k_sde_embed_rng, p, st, s);
-    else MDG_LAUNCH_STATE_EMBED(k_sde_embed, p, st, s);
+    embed_dispatch(p, [&](auto pos, auto ipa, auto tok, dim3 g) {
+        constexpr bool POS = decltype(pos)::value, IPA = decltype(ipa)::value;
+        constexpr int kEmbTok = decltype(tok)::value;
+        if (st.rng) hipLaunchKernelGGL((k_sde_embed_rng<POS, IPA, kEmbTok>), g, dim3(256), 0, s, p, st);
+        else hipLaunchKernelGGL((k_sde_embed<POS, IPA, kEmbTok>), g, dim3(256), 0, s, p, st);
+    });
 }
 
 void launch_sde_update(const SdeState& st, long n, hipStream_t s) {
-    const long n4 = n >> 2;
-    const long nb = (n4 + 255) / 256;
-    const dim3 g((unsigned)(nb > 0 ? nb : 1));
+    const dim3 g = state_update_grid(n);
     if (st.rng) hipLaunchKernelGGL(k_sde_update<true>, g, dim3(256), 0, s, st, n);
     else hipLaunchKernelGGL(k_sde_update<false>, g, dim3(256), 0, s, st, n);
 }

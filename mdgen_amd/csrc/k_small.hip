@@ -1,5 +1,5 @@
 // k_small.hip -- step-invariant / token-embedding / IPA kernels (HBM- or latency-bound, fp32).
-#include "kernels.h"
+#include "state_embed.h"
 
 namespace mdg {
 
@@ -121,148 +121,12 @@ __global__ void k_pack_rows(const float* __restrict__ w, int ld, const int* __re
     dst[i] = v;
 }
 
-// -------------------------------------------------------------------------------------------------
-// Token embedding (latent_model.py:233-246):
-//   h = latent_to_emb(x) [+ pos_embed[l]] + cond_to_emb(x_cond) + mask_to_emb[x_cond_mask] + ipa_out[b,l]
-// A [N x D] . [D x 384] product with D = 21 / 28: far too thin for the bf16 path's panels, and as a per-channel dot
-// product on the VALU (round 1) it ran at 0.9 TB/s of its 98 MB output.  Here it is an fp32 MFMA job:
-// v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulate -- the reference's arithmetic), D = tokens x channels.
-// Workgroup = 128 tokens (4 row tiles) x 384 channels; wave w owns channels 96 w .. 96 w + 95 and keeps its slices
-// of both weight matrices in registers (2 x 3 tiles x 14 k-steps); token rows are staged once in LDS (row stride 29
-// floats: the per-k column reads are conflict-free).  cond_to_emb is skipped for row tiles whose x_cond rows are all
-// zero (every non-conditioning frame).  The epilogue adds bias, mask embedding, pos_embed / ipa_out rows (requested
-// four token rows ahead) and stores 128-byte row segments.
-// -------------------------------------------------------------------------------------------------
-constexpr int kEmbLd = 29, kEmbK = 14;
-// POS / IPA: pos_embed / ipa_out present (compile-time so that their loads are unconditional).
-// kEmbTok: tokens per workgroup -- 128 when that still makes a few hundred workgroups; 32 (one row tile per workgroup) for the
-// small launches (B = 1, the TPS shard), whose time is one workgroup's latency: 40 -> ~17 us at 12 800 tokens.
+// Token embedding: the body, its design notes and its launch sizes are state_embed.h's (shared with the samplers' state kernels
+// k_rk_embed / k_sde_embed, which embed a state they form themselves).  Here the state is p.x as it stands: no operands, nothing stored.
 template <bool POS, bool IPA, int kEmbTok>
 __global__ __launch_bounds__(256) void k_embed(const EmbedParams p) {
-    __shared__ float xs[kEmbTok * kEmbLd];
-    __shared__ float cs[kEmbTok * kEmbLd];
-    __shared__ int ms[kEmbTok];     // bit0: x_cond_mask, bit1: x_cond row has a non-zero
-    __shared__ int tpos[kEmbTok];   // l * kC                 (row of pos_embed)
-    __shared__ int tipa[kEmbTok];   // (b * L + l) * kC       (row of ipa_out)
-    const int tid = threadIdx.x;
-    const long tok0 = (long)blockIdx.x * kEmbTok;
-    if (tid < kEmbTok) {
-        long t = tok0 + tid;
-        t = t < p.N ? t : p.N - 1;
-        const int l = (int)(t % p.L), b = (int)(t / ((long)p.T * p.L));
-        ms[tid] = 0;
-        tpos[tid] = l * kC;
-        tipa[tid] = (b * p.L + l) * kC;
-    }
-    __syncthreads();
-    {   // stage x / x_cond rows: unconditional clamped loads, all in flight together
-        constexpr int NIT = (kEmbTok * 28 + 255) / 256;
-        float a[NIT], b[NIT];
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int i0 = tid + 256 * it;
-            const int i = i0 < kEmbTok * 28 ? i0 : kEmbTok * 28 - 1;   // (32-token workgroups: 3.5 rounds)
-            const int tk = i / 28, d = i % 28;
-            long t = tok0 + tk;
-            t = t < p.N ? t : p.N - 1;
-            const int dc = d < p.D ? d : 0;
-            a[it] = p.x[t * p.D + dc];
-            b[it] = p.x_cond[t * p.D + dc];
-        }
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int i = tid + 256 * it;
-            if (i >= kEmbTok * 28) break;
-            const int tk = i / 28, d = i % 28;
-            const bool ok = tok0 + tk < p.N && d < p.D;
-            xs[tk * kEmbLd + d] = ok ? a[it] : 0.f;
-            cs[tk * kEmbLd + d] = ok ? b[it] : 0.f;
-            if (ok && b[it] != 0.f) atomicOr(&ms[tk], 2);
-        }
-    }
-    const int w = __builtin_amdgcn_readfirstlane(wave_id()), lane = lane_id(), hh = lane >> 5, j = lane & 31;
-    const int nk = (p.D + 1) >> 1;
-    // B operands (k = 2 ks + hh, column = channel): this wave's three channel tiles of both weight matrices
-    // (from the packed copies, k_pack_embed: one 256-byte request per (tile, k-step) instead of 64 lines 84 bytes apart --
-    // 168 such gathers per lane were the fixed cost of every workgroup)
-    float wl[3][kEmbK], wc[3][kEmbK], b0[3], me0[3], me1[3];
-#pragma unroll
-    for (int ct = 0; ct < 3; ++ct) {
-        const int c = 96 * w + 32 * ct + j;
-#pragma unroll
-        for (int ks = 0; ks < kEmbK; ++ks) {
-            const int o = ((w * 3 + ct) * kEmbK + ks) * 64 + lane;
-            wl[ct][ks] = p.wl_pack[o];
-            wc[ct][ks] = p.wc_pack[o];
-        }
-        b0[ct] = p.bl[c] + p.bc[c];
-        me0[ct] = p.mask_emb[c];
-        me1[ct] = p.mask_emb[kC + c];
-    }
-    __syncthreads();
-    if (tid < kEmbTok) {
-        const long t = tok0 + tid;
-        if (t < p.N && p.x_cond_mask[t]) ms[tid] |= 1;
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int rt = 0; rt < kEmbTok / 32; ++rt) {
-        if (tok0 + rt * 32 >= p.N) break;
-        f32x16 acc[3];
-#pragma unroll
-        for (int ct = 0; ct < 3; ++ct)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ct][r] = 0.f;
-        const float* xr = xs + (rt * 32 + j) * kEmbLd + hh;
-#pragma unroll
-        for (int ks = 0; ks < kEmbK; ++ks) {
-            if (ks < nk) {
-                const float a = xr[2 * ks];
-#pragma unroll
-                for (int ct = 0; ct < 3; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wl[ct][ks], acc[ct], 0, 0, 0);
-            }
-        }
-        if (__builtin_amdgcn_ballot_w64((ms[rt * 32 + j] & 2) != 0) != 0) {   // some token of this tile is conditioned
-            const float* cr = cs + (rt * 32 + j) * kEmbLd + hh;
-#pragma unroll
-            for (int ks = 0; ks < kEmbK; ++ks) {
-                if (ks < nk) {
-                    const float a = cr[2 * ks];
-#pragma unroll
-                    for (int ct = 0; ct < 3; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wc[ct][ks], acc[ct], 0, 0, 0);
-                }
-            }
-        }
-        // epilogue: register r of lane-half hh is token row mfma_row(r, hh) of the tile, lane j its channel
-#pragma unroll
-        for (int r0 = 0; r0 < 16; r0 += 4) {
-            float add[4][3];
-            int mrow[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int tk = rt * 32 + mfma_row(r0 + u, hh);
-                mrow[u] = ms[tk];
-                const int op = tpos[tk], oi = tipa[tk];
-#pragma unroll
-                for (int ct = 0; ct < 3; ++ct) {
-                    const int c = 96 * w + 32 * ct + j;
-                    float v = 0.f;
-                    if (POS) v += p.pos_embed[op + c];
-                    if (IPA) v += p.ipa_out[oi + c];
-                    add[u][ct] = v;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const long t = tok0 + rt * 32 + mfma_row(r0 + u, hh);
-                if (t < p.N) {
-#pragma unroll
-                    for (int ct = 0; ct < 3; ++ct)
-                        p.h[t * kC + 96 * w + 32 * ct + j] = acc[ct][r0 + u] + b0[ct] + ((mrow[u] & 1) ? me1[ct] : me0[ct]) + add[u][ct];
-                }
-            }
-        }
-    }
+    const float* const ops[1] = {nullptr};
+    state_embed<POS, IPA, kEmbTok>(p, p.x, nullptr, ops, [](float x, const float*, long) { return x; });
 }
 
 // IPA-stack input (latent_model.py:184-187 / 193-201): h[g,l] = aatype_emb[aatype[b,l]]
@@ -763,20 +627,9 @@ void launch_pack_embed(const float* w, int D, float* pack, hipStream_t s) {
     hipLaunchKernelGGL(k_pack_embed, dim3(4 * 3 * kEmbK), dim3(64), 0, s, w, D, pack);
 }
 void launch_embed(const EmbedParams& p, hipStream_t s) {
-    const dim3 b(256);
-    if ((p.N + 127) / 128 >= 384) {
-        const dim3 g((unsigned)((p.N + 127) / 128));
-        if (p.pos_embed && p.ipa_out) hipLaunchKernelGGL((k_embed<true, true, 128>), g, b, 0, s, p);
-        else if (p.pos_embed) hipLaunchKernelGGL((k_embed<true, false, 128>), g, b, 0, s, p);
-        else if (p.ipa_out) hipLaunchKernelGGL((k_embed<false, true, 128>), g, b, 0, s, p);
-        else hipLaunchKernelGGL((k_embed<false, false, 128>), g, b, 0, s, p);
-    } else {
-        const dim3 g((unsigned)((p.N + 31) / 32));
-        if (p.pos_embed && p.ipa_out) hipLaunchKernelGGL((k_embed<true, true, 32>), g, b, 0, s, p);
-        else if (p.pos_embed) hipLaunchKernelGGL((k_embed<true, false, 32>), g, b, 0, s, p);
-        else if (p.ipa_out) hipLaunchKernelGGL((k_embed<false, true, 32>), g, b, 0, s, p);
-        else hipLaunchKernelGGL((k_embed<false, false, 32>), g, b, 0, s, p);
-    }
+    embed_dispatch(p, [&](auto pos, auto ipa, auto tok, dim3 g) {
+        hipLaunchKernelGGL((k_embed<decltype(pos)::value, decltype(ipa)::value, decltype(tok)::value>), g, dim3(256), 0, s, p);
+    });
 }
 void launch_ipa_init(const float* aa_emb, const int64_t* aatype, const float* rel7, const float* w7, const float* b7,
                      float* h, int ngroups, int B, int L, hipStream_t s) {

@@ -553,7 +553,8 @@ struct RkState {
     const float* k[kRkMaxK];
     float* y;                      // y0 (B, T, L, D)
 };
-// k_embed on the state `st` describes (p.x is not read: st.y is); the kernel forms follow launch_embed's launch sizes
+// k_embed on the state `st` describes -- literally: one device body (state_embed.h) and one launch selection (embed_dispatch) serve
+// k_embed, this kernel and k_sde_embed.  p.x is not read: st.y is
 void launch_rk_embed(const EmbedParams& p, const RkState& st, hipStream_t s);
 // y <- the state `st` describes, elementwise over n values (the result of the last step)
 void launch_rk_update(const RkState& st, long n, hipStream_t s);

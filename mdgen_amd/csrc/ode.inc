@@ -440,8 +440,63 @@ static void rk_plan(const rk::Method& m, int S, RkPlan* p) {
     }
 }
 
-// the device descriptor of state `n` of a step of size dt: y and k[stage] of the whole batch, shifted by `off` floats (a view)
-static RkState rk_state_of(const rk::Node& n, float dt, float* y, float* const* k, long off, bool store) {
+// ---- what a Runge-Kutta call and an SDE call (sde.inc) share: the workspace, the made run, a state's evaluation view by view ----
+// the network workspace of `lay`, then `nvel` velocity buffers of one state each
+static size_t grid_ws_bytes(const mdgen_ctx* c, const mdgen_shape* sh, const mdgen_ws_layout& lay, int nvel) {
+    return align256(lay.total_bytes) + (size_t)nvel * ode_state_bytes(c, sh) + 256;
+}
+// The made run with the call's conditioning bound, its launch views and the velocity buffers behind the network workspace.
+// `lay`: the layout for the call's `rows` time rows; `sizer`: the entry point that sizes the workspace.  Every refusal, the
+// caller's and these, comes before make_run, the first to touch the device.
+struct GridCall {
+    Run r;
+    int nv;
+    float* vel[kRkMaxK];
+};
+static int grid_open(GridCall* q, const mdgen_ws_layout& lay, int rows, int nvel, const char* sizer, mdgen_ctx* c, const mdgen_shape* sh,
+                     const mdgen_cond& cd, void* ws, size_t ws_bytes, void* stream) {
+    const size_t need = grid_ws_bytes(c, sh, lay, nvel);
+    if (ws_bytes < need) return fail(-7, "workspace too small: %zu < %zu bytes (%s)", ws_bytes, need, sizer);
+    q->r = Run{};
+    if (int e = make_run(&q->r, c, sh, rows, 1, f32_path(c), ws, lay.total_bytes, stream)) return e;
+    bind_cond(q->r, cd);
+    q->r.no_embed_tail = true;
+    q->nv = c->opt_precision == 32 ? 1 : plan_views(sh->B, sh->T, sh->L, 1);
+    if (q->nv == 0) return fail(-2, "sample too large for one launch");
+    for (int j = 0; j < nvel; ++j) q->vel[j] = (float*)((unsigned char*)ws + align256(lay.total_bytes) + (size_t)j * ode_state_bytes(c, sh));
+    return 0;
+}
+
+// a view's share of a state descriptor: its pointers moved by the view's offset `off` = b0 * per_b floats
+static void to_view(Run& v, RkState& s, long off, int, long) {
+    s.y += off;
+    for (int j = 0; j < s.nk; ++j) s.k[j] += off;
+    v.rk = &s;
+}
+static void to_view(Run& v, SdeState& s, long off, int b0, long per_b) {
+    s.y += off;
+    for (int j = 0; j < 2; ++j)
+        if (s.v[j]) s.v[j] += off;
+    if (s.xi) s.xi += off;
+    s.b0 = b0;
+    s.per_b = (unsigned)per_b;
+    v.sde = &s;
+}
+// one network evaluation of the state `proto` describes (of the whole batch) at time row `row`, the velocity to `out`
+template <class State>
+static int eval_state(const Run& r, int nv, const State& proto, int row, float* out) {
+    const long per_b = (long)r.T * r.L * r.D;
+    return for_each_view(r, nv, 1, [&](const Run& v, int b0) {
+        const long off = (long)b0 * per_b;
+        State st = proto;
+        Run vs = v;
+        to_view(vs, st, off, b0, per_b);
+        return denoise_step(vs, row, st.y, out + off, 0, 0.f, nullptr);
+    });
+}
+
+// the device descriptor of state `n` of a step of size dt: y and k[stage] of the whole batch
+static RkState rk_state_of(const rk::Node& n, float dt, float* y, float* const* k, bool store) {
 #pragma clang fp contract(off)
     RkState s{};
     s.form = n.form;
@@ -449,8 +504,8 @@ static RkState rk_state_of(const rk::Node& n, float dt, float* y, float* const* 
     s.dt = dt;
     for (int q = 0; q < 3; ++q) s.c[q] = n.c[q];
     if (n.c0_dt) s.c[0] = n.c[0] * dt;
-    for (s.nk = 0; s.nk < kRkMaxK && n.ki[s.nk] >= 0; ++s.nk) s.k[s.nk] = k[n.ki[s.nk]] + off;
-    s.y = y + off;
+    for (s.nk = 0; s.nk < kRkMaxK && n.ki[s.nk] >= 0; ++s.nk) s.k[s.nk] = k[n.ki[s.nk]];
+    s.y = y;
     return s;
 }
 
@@ -473,7 +528,7 @@ extern "C" int32_t mdgen_rk_workspace_bytes(const mdgen_ctx* c, const mdgen_shap
     RkPlan pl;
     mdgen_ws_layout lay;
     if (int e = rk_layout(c, sh, method, S, &pl, &lay)) return e;
-    *bytes = align256(lay.total_bytes) + kRkMaxK * ode_state_bytes(c, sh) + 256;
+    *bytes = grid_ws_bytes(c, sh, lay, kRkMaxK);
     return 0;
 }
 
@@ -481,38 +536,26 @@ extern "C" int32_t mdgen_rk_workspace_bytes(const mdgen_ctx* c, const mdgen_shap
 static int rk_body(const Run& r_in, const rk::Method& m, int S, const RkPlan& pl, int nv, float* y, float* const* k) {
     Run r = r_in;
     if (int e = ode_prepare(r, pl.rows.data(), (int)pl.rows.size(), largest_view_rows(r, nv))) return e;
-    const long per_b = (long)r.T * r.L * r.D;
     for (int i = 0; i < S; ++i) {
         const float dt = pl.tg[i + 1] - pl.tg[i], dt_prev = i > 0 ? pl.tg[i] - pl.tg[i - 1] : 0.f;
         for (int j = 0; j < m.stages; ++j) {
             // the first stage of step i > 0 forms the previous step's result and stores it over y
             const bool first = j == 0;
             const rk::Node& n = first && i > 0 ? m.result : m.stage[j];
-            const int row = pl.row_of[(size_t)i * m.stages + j];
-            const int e = for_each_view(r, nv, 1, [&](const Run& v, int b0) {
-                const long o = (long)b0 * per_b;
-                const RkState st = rk_state_of(n, first ? dt_prev : dt, y, k, o, first && i > 0);
-                Run vs = v;
-                vs.rk = &st;
-                return denoise_step(vs, row, y + o, k[j] + o, 0, 0.f, nullptr);
-            });
-            if (e) return e;
+            const RkState st = rk_state_of(n, first ? dt_prev : dt, y, k, first && i > 0);
+            if (int e = eval_state(r, nv, st, pl.row_of[(size_t)i * m.stages + j], k[j])) return e;
         }
     }
-    const RkState last = rk_state_of(m.result, pl.tg[S] - pl.tg[S - 1], y, k, 0, true);
+    const RkState last = rk_state_of(m.result, pl.tg[S] - pl.tg[S - 1], y, k, true);
     return launch(r, "ode_rk_update", [&] { launch_rk_update(last, (long)r.N * r.D, r.s); });
 }
 
-// What mdgen_sample_rk, mdgen_rollout_rk and mdgen_upsample_rk (drivers.inc) share once their own arguments are judged: the plan, the made run
-// with the call's conditioning bound, its launch views and the four velocity buffers behind the network workspace.  `state` is
-// the buffer k_rk_update will see (16-byte accesses).  Every refusal comes before make_run, the first to touch the device.
-struct RkCall {
+// What mdgen_sample_rk, mdgen_rollout_rk and mdgen_upsample_rk (drivers.inc) share once their own arguments are judged: the plan and the
+// GridCall with the four velocity buffers.  `state` is the buffer k_rk_update will see (16-byte accesses).
+struct RkCall : GridCall {
     const rk::Method* m;
     RkPlan pl;
-    Run r;
-    int nv;
-    float* k[kRkMaxK];
-    int solve(int S, float* y) const { return rk_body(r, *m, S, pl, nv, y, k); }
+    int solve(int S, float* y) const { return rk_body(r, *m, S, pl, nv, y, vel); }
 };
 static int rk_open(RkCall* q, mdgen_ctx* c, const mdgen_shape* sh, int method, int S, const float* state, const mdgen_cond& cd,
                    void* ws, size_t ws_bytes, void* stream) {
@@ -520,16 +563,7 @@ static int rk_open(RkCall* q, mdgen_ctx* c, const mdgen_shape* sh, int method, i
     if (int e = rk_layout(c, sh, method, S, &q->pl, &lay)) return e;
     q->m = rk_method(method);
     if (((uintptr_t)state & 15) != 0) return fail(-7, "x must be 16-byte aligned");
-    const size_t sb = ode_state_bytes(c, sh), need = align256(lay.total_bytes) + kRkMaxK * sb + 256;
-    if (ws_bytes < need) return fail(-7, "workspace too small: %zu < %zu bytes (mdgen_rk_workspace_bytes)", ws_bytes, need);
-    q->r = Run{};
-    if (int e = make_run(&q->r, c, sh, (int)q->pl.rows.size(), 1, f32_path(c), ws, lay.total_bytes, stream)) return e;
-    bind_cond(q->r, cd);
-    q->r.no_embed_tail = true;
-    q->nv = c->opt_precision == 32 ? 1 : plan_views(sh->B, sh->T, sh->L, 1);
-    if (q->nv == 0) return fail(-2, "sample too large for one launch");
-    for (int j = 0; j < kRkMaxK; ++j) q->k[j] = (float*)((unsigned char*)ws + align256(lay.total_bytes) + (size_t)j * sb);
-    return 0;
+    return grid_open(q, lay, (int)q->pl.rows.size(), kRkMaxK, "mdgen_rk_workspace_bytes", c, sh, cd, ws, ws_bytes, stream);
 }
 
 extern "C" int32_t mdgen_sample_rk(mdgen_ctx* c, const mdgen_shape* sh, int32_t method, int32_t S, float* x, const mdgen_cond* cond,
@@ -548,9 +582,8 @@ extern "C" int32_t mdgen_sample_rk(mdgen_ctx* c, const mdgen_shape* sh, int32_t 
 extern "C" int32_t mdgen_debug_rk_plan(int32_t method, int32_t S, uint32_t* row_bits, int32_t cap_rows, int32_t* n_rows,
                                        int32_t* row_of, int32_t* n_stages) {
     if (!row_bits || !n_rows || !row_of || !n_stages) return fail(-1, "null argument");
+    if (int e = rk_check(method, S)) return e;
     const rk::Method* m = rk_method(method);
-    if (!m) return fail(-2, "method: 1 midpoint, 2 heun3, 3 rk4 (got %d)", method);
-    if (S < 1) return fail(-2, "n_steps must be >= 1");
     RkPlan pl;
     rk_plan(*m, S, &pl);
     *n_rows = (int32_t)pl.rows.size();
@@ -578,7 +611,7 @@ extern "C" int32_t mdgen_debug_rk_stage(mdgen_ctx* c, const mdgen_shape* sh, int
     const rk::Node& n = stage == m->stages ? m->result : m->stage[stage];
     for (int q = 0; q < kRkMaxK && n.ki[q] >= 0; ++q)
         if (!k[n.ki[q]]) return fail(-1, "the state reads k%d", n.ki[q]);
-    const RkState st = rk_state_of(n, dt, y, k, 0, stage == m->stages);
+    const RkState st = rk_state_of(n, dt, y, k, stage == m->stages);
     launch_rk_embed(embed_params(c, *sh, y, x_cond, x_cond_mask, ipa_out, h), st, (hipStream_t)stream);
     LAUNCHCHK();
     return 0;

@@ -152,7 +152,7 @@ extern "C" int32_t mdgen_sde_workspace_bytes(const mdgen_ctx* c, const mdgen_sha
     mdgen_ws_layout lay;
     if (int e = sde_plan(*o, &pl)) return e;
     if (int e = mdgen_workspace_layout(c, sh, (int)pl.rows.size(), 1, &lay)) return e;
-    *bytes = align256(lay.total_bytes) + 2 * ode_state_bytes(c, sh) + 256;
+    *bytes = grid_ws_bytes(c, sh, lay, 2);
     return 0;
 }
 
@@ -212,22 +212,6 @@ static int sde_body(const Run& r_in, const mdgen_sde_opts& o, const SdePlan& pl,
     if (int e = ode_prepare(r, pl.rows.data(), (int)pl.rows.size(), largest_view_rows(r, nv))) return e;
     const long per_b = (long)r.T * r.L * r.D;
     const int S = o.n_points - 1;
-    // one network evaluation of the state `proto` describes at time row `row`, the velocity to `out`
-    auto eval = [&](const SdeState& proto, int row, float* out) {
-        return for_each_view(r, nv, 1, [&](const Run& vw, int b0) {
-            const long off = (long)b0 * per_b;
-            SdeState st = proto;
-            st.y += off;
-            for (int j = 0; j < 2; ++j)
-                if (st.v[j]) st.v[j] += off;
-            if (st.xi) st.xi += off;
-            st.b0 = b0;
-            st.per_b = (unsigned)per_b;
-            Run vs = vw;
-            vs.sde = &st;
-            return denoise_step(vs, row, x + off, out + off, 0, 0.f, nullptr);
-        });
-    };
     auto update = [&](SdeState st) {   // the whole call's state in one launch
         st.per_b = (unsigned)per_b;
         return launch(r, "ode_sde_update", [&] { launch_sde_update(st, (long)r.N * r.D, r.s); });
@@ -237,29 +221,25 @@ static int sde_body(const Run& r_in, const mdgen_sde_opts& o, const SdePlan& pl,
         const SdeState first = i > 0 ? sde_result_of(o, pl, i - 1, x, v, nz)
                                : o.method == 1 ? sde_state_of(pl, kSdeX, false, -1, -1, -1, pl.dt, x, nullptr, nullptr, nullptr)
                                                : with_noise(sde_state_of(pl, kSdeNoise, true, -1, -1, pl.row_of[0], pl.dt, x, nullptr, nullptr, nullptr), nz, 0);
-        if (int e = eval(first, pl.row_of[(size_t)i * pl.stages], v[0])) return e;
+        if (int e = eval_state(r, nv, first, pl.row_of[(size_t)i * pl.stages], v[0])) return e;
         if (o.method == 2) {   // the predictor xp: in registers only
             const SdeState xp = sde_state_of(pl, kSdeDrift, false, pl.row_of[(size_t)i * 2], -1, -1, pl.dt, x, v[0], nullptr, nullptr);
-            if (int e = eval(xp, pl.row_of[(size_t)i * 2 + 1], v[1])) return e;
+            if (int e = eval_state(r, nv, xp, pl.row_of[(size_t)i * 2 + 1], v[1])) return e;
         }
     }
     const SdeState res = sde_result_of(o, pl, S - 1, x, v, nz);
     if (o.last_step == 0) return update(res);
-    if (int e = eval(res, pl.last_row, v[0])) return e;
+    if (int e = eval_state(r, nv, res, pl.last_row, v[0])) return e;
     return update(sde_last_of(o, pl, x, v));
 }
 
 // What mdgen_sample_sde, mdgen_sample_sde_rng, mdgen_rollout_sde and mdgen_upsample_sde share once their own arguments are judged (as
-// RkCall, ode.inc): the plan, the made run with the call's conditioning bound, its launch views, the two velocity buffers behind
-// the network workspace and the options as they enter a graph key.  `state` is the buffer k_sde_update will see (16-byte accesses).
-// Every refusal comes before make_run, the first to touch the device.
-struct SdeCall {
+// RkCall, ode.inc): the plan, the GridCall with two velocity buffers and the options as they enter a graph key.  `state` is the
+// buffer k_sde_update will see (16-byte accesses).
+struct SdeCall : GridCall {
     mdgen_sde_opts o, key;
     SdePlan pl;
-    Run r;
-    int nv;
-    float* v[2];
-    int solve(float* x, const SdeNoise& nz) const { return sde_body(r, o, pl, nv, x, v, nz); }
+    int solve(float* x, const SdeNoise& nz) const { return sde_body(r, o, pl, nv, x, vel, nz); }
 };
 static int sde_open(SdeCall* q, mdgen_ctx* c, const mdgen_shape* sh, const mdgen_sde_opts* o, const float* state, const SdeNoise& nz,
                     const mdgen_cond& cd, void* ws, size_t ws_bytes, void* stream) {
@@ -283,15 +263,7 @@ static int sde_open(SdeCall* q, mdgen_ctx* c, const mdgen_shape* sh, const mdgen
     }
     mdgen_ws_layout lay;
     if (int e = mdgen_workspace_layout(c, sh, (int)q->pl.rows.size(), 1, &lay)) return e;
-    const size_t sb = ode_state_bytes(c, sh), need = align256(lay.total_bytes) + 2 * sb + 256;
-    if (ws_bytes < need) return fail(-7, "workspace too small: %zu < %zu bytes (mdgen_sde_workspace_bytes)", ws_bytes, need);
-    q->r = Run{};
-    if (int e = make_run(&q->r, c, sh, (int)q->pl.rows.size(), 1, f32_path(c), ws, lay.total_bytes, stream)) return e;
-    bind_cond(q->r, cd);
-    q->r.no_embed_tail = true;
-    q->nv = c->opt_precision == 32 ? 1 : plan_views(sh->B, sh->T, sh->L, 1);
-    if (q->nv == 0) return fail(-2, "sample too large for one launch");
-    for (int j = 0; j < 2; ++j) q->v[j] = (float*)((unsigned char*)ws + align256(lay.total_bytes) + (size_t)j * sb);
+    if (int e = grid_open(q, lay, (int)q->pl.rows.size(), 2, "mdgen_sde_workspace_bytes", c, sh, cd, ws, ws_bytes, stream)) return e;
     mdgen_sde_opts& k = q->key;   // (field by field: the struct's padding does not reach the key)
     std::memset(&k, 0, sizeof(k));
     k.method = o->method; k.path = o->path; k.diffusion_form = o->diffusion_form; k.last_step = o->last_step; k.n_points = o->n_points;

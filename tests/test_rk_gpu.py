@@ -167,6 +167,54 @@ def test_rk_embed_kernel_vs_fp64(shape, tps, abs_pos):
     print(f"{shape} D {D} pos {abs_pos}: worst h error / fp32 floor: row max x{worst[0]:.2f}, rel-L2 x{worst[1]:.2f} (gate x{FACTOR:.0f})")
 
 
+# ---- 5b: one embedding body -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("abs_pos", [True, False])
+@pytest.mark.parametrize("tps", [False, True])
+@pytest.mark.parametrize("shape", STAGE_SHAPES)
+def test_embed_kernels_share_one_body_bit_for_bit(shape, tps, abs_pos):
+    """k_embed, k_rk_embed on the state y0 itself and k_sde_embed on the state x itself are one device body (csrc/state_embed.h): on
+    the same inputs the three write the same h bit for bit, and none of them touches x.  The shapes are a partial 32-token tile,
+    132 tokens (32-token workgroups, partial last one) and 49 950 tokens (just past the 384 x 128 threshold: 128-token workgroups,
+    partial last one); "tiles" leaves whole tiles unconditioned, so the cond_to_emb skip runs in all three."""
+    import sde_ref
+    from mdgen_amd import _lib as L
+    from mdgen_amd.synthetic import synth_forward_inputs
+    dev = _cuda()
+    B, T, L_ = shape
+    model, _ = _embed_model(tps, abs_pos, L_)
+    D = model.cfg.latent_dim
+    N = B * T * L_
+    inp = synth_forward_inputs(model.cfg, B, T, L_, 0, 3000 * B + L_)
+    gen = torch.Generator().manual_seed(3000 * B + L_)
+    x = inp["x"].to(dev)
+    sh = L.Shape(B, T, L_)
+    o = L.sde_opts("Euler", "GVP", "sigma", 1.0, "Mean", 0.04, 6, 0.0)
+    for kind in ("frame0", "tiles"):
+        x_cond, xcm = _cond_pattern(kind, B, T, L_, D, gen)
+        xc_dev, xcm_dev = x_cond.to(dev), xcm.to(dev)
+        x_fwd = x.clone()
+        _, tr = model.forward(x=x_fwd, t=inp["t"].to(dev), mask=inp["mask"].to(dev),
+                              start_frames=(inp["start_rot"].to(dev), inp["start_trans"].to(dev)),
+                              end_frames=(inp["end_rot"].to(dev), inp["end_trans"].to(dev)) if tps else None,
+                              x_cond=xc_dev, x_cond_mask=xcm_dev, aatype=inp["aatype"].to(dev), return_trace=True)
+        h_embed = tr["h0"].reshape(N, 384)
+        ipa_dev = tr["ipa_out"].reshape(B * L_, 384).contiguous()
+        x_rk, x_sde = x.clone(), x.clone()
+        h_rk = torch.full((N, 384), float("nan"), device=dev)
+        h_sde = torch.full((N, 384), float("nan"), device=dev)
+        with torch.cuda.device(dev):
+            L.check(L.lib.mdgen_debug_rk_stage(model._ctx, C.byref(sh), R.METHODS["rk4"], 0, DT, L.ptr(x_rk), None, None, None, None,
+                                               L.ptr(xc_dev), L.ptr(xcm_dev), L.ptr(ipa_dev), L.ptr(h_rk), L.stream_ptr()))
+            L.check(L.lib.mdgen_debug_sde_stage(model._ctx, C.byref(sh), C.byref(o), sde_ref.X, 0, L.ptr(x_sde), None, None, None,
+                                                L.ptr(xc_dev), L.ptr(xcm_dev), L.ptr(ipa_dev), L.ptr(h_sde), L.stream_ptr()))
+        torch.cuda.synchronize()
+        tag = (shape, tps, abs_pos, kind)
+        assert torch.isfinite(h_embed).all(), tag
+        assert torch.equal(h_rk, h_embed), (tag, "k_rk_embed", float((h_rk - h_embed).abs().max()))
+        assert torch.equal(h_sde, h_embed), (tag, "k_sde_embed", float((h_sde - h_embed).abs().max()))
+        assert torch.equal(x_fwd, x) and torch.equal(x_rk, x) and torch.equal(x_sde, x), tag
+
+
 # ---- 6: whole solve, fp32 mode, against the oracle ----------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _oracle_setup(tps):
