@@ -737,6 +737,60 @@ int32_t mdgen_traj_acov_workspace_bytes(int64_t n, int32_t NF, int64_t K, size_t
 int32_t mdgen_traj_acov(int64_t n, int32_t NF, int64_t K, const float* angles, double* acov, double* mean_sin, double* mean_cos,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* tICA of a trajectory's torsion angles (csrc/k_tica.hip; mdgen_amd/analysis.py tica_fit / tica_transform): the parts of the
+ * reference's `pyemma.coordinates.tica(lag, kinetic_map=True)` (scripts/analyze_peptide_sim.py:104-150) that scale with the
+ * trajectory length.  The four entries follow the conventions above: they run on `stream` and synchronise nothing, every refusal is
+ * decided before any device call (-1 null pointer, -2 bad shape, -3 workspace too small), NF = 0 / NS = 0 / P = 0 succeeds and
+ * writes nothing, no floating-point atomics, two calls give the same bits.
+ *
+ * Features.  For angles (n, NF) fp32 in `torsion_features`' order, frame t has x_t in R^D, D = 2 NF, x[2j] = cos a_j,
+ * x[2j + 1] = sin a_j -- pyemma's cossin=True interleaving as the maintainers recall it, unchecked; tICA's results do not depend on
+ * the order beyond rounding.  cos and sin are evaluated in fp64 and rounded to fp32 once.
+ * Moments at lag tau.  With m = n - tau, X = x[0 .. m), Y = x[tau .. n):  sx = sum X, sy = sum Y, cxx = X'X, cyy = Y'Y, cxy = X'Y,
+ * raw (un-centred).
+ * Estimator (host, NumPy fp64: analysis.tica_solve; pyemma's defaults reversible, var_cutoff 0.95, epsilon 1e-6):
+ *   mu = (sx + sy) / 2m,  C0 = (cxx + cyy) / 2m - mu mu',  Ctau = (cxy + cxy') / 2m - mu mu';
+ *   C0 = Q S Q', the eigenvalues s > epsilon kept, rank r their number, L = Q_r S_r^(-1/2);
+ *   L' Ctau L = R diag(lambda) R', lambda descending;  W = (L R) diag(lambda), the kinetic map; in every column of W the entry of
+ *   largest magnitude is positive (the first such entry on ties);  dim = the smallest d with
+ *   sum_{i<d} lambda_i^2 / sum lambda_i^2 >= 0.95;  transform: (x_t - mu) W[:, :d].
+ *
+ * mdgen_traj_lagged_moments: sx, sy fp64 [D], cxx, cyy, cxy fp64 [D][D] of angles (n, NF) at `lag`, 0 <= lag <= n - 1.
+ *   1 <= NF <= 64: tetrapeptides have at most 22 torsions; ATLAS-size proteins are not this tool's subject and are refused.
+ *   Products and sums of 64 frames are fp32, everything beyond is fp64; per-workgroup partial sums go to the workspace and are added
+ *   in a fixed order.  At lag 0 the three matrices are equal to the bit, and so are sx and sy.
+ *   workspace: mdgen_traj_lagged_moments_workspace_bytes(n, NF, lag), 16-byte aligned.
+ * -2: n < 1, lag < 0 or > n - 1, NF < 0 or > 64. */
+int32_t mdgen_traj_lagged_moments_workspace_bytes(int64_t n, int32_t NF, int64_t lag, size_t* bytes);
+int32_t mdgen_traj_lagged_moments(int64_t n, int32_t NF, int64_t lag, const float* angles, double* sx, double* sy, double* cxx,
+                                  double* cyy, double* cxy, void* workspace, size_t workspace_bytes, void* stream);
+
+/* mdgen_traj_project: out[t][c] = sum_j (x_t[j] - mean[j]) W[j][c] for the features x_t of angles (n, NF): the subtraction first,
+ * then fp32 FMAs with j ascending.  mean fp32 [D], W fp32 [D][d] row-major, out (n, d) fp32.
+ * -2: n < 1, NF < 0 or > 64, d < 1 or > D. */
+int32_t mdgen_traj_project(int64_t n, int32_t NF, int32_t d, const float* angles, const float* mean, const float* W, float* out,
+                           void* stream);
+
+/* mdgen_traj_series_acov: for every column s of x (n, NS) fp32 and lag k = 0 .. K
+ *   acov[s][k] = sum_{t = 0}^{n - k - 1} x_t x_{t + k} / (n - k)
+ * -- statsmodels' acovf(demean=False, adjusted=True) -- and mean[s], the mean over t.  mdgen_traj_acov's kernel body on one row,
+ * the same refusals and launch limit, the same precision rule (fp32 over at most 256 samples, fp64 beyond, fixed order) -- here
+ * fp32 over 8 samples: a series with an offset has products of one sign, whose fp32 rounding errors add up instead of cancelling.
+ *   acov fp64 [NS][K + 1], mean fp64 [NS] out;  workspace: mdgen_traj_series_acov_workspace_bytes(n, NS, K), 16-byte aligned. */
+int32_t mdgen_traj_series_acov_workspace_bytes(int64_t n, int32_t NS, int64_t K, size_t* bytes);
+int32_t mdgen_traj_series_acov(int64_t n, int32_t NS, int64_t K, const float* x, double* acov, double* mean, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
+/* mdgen_traj_histograms_xy: P two-dimensional histograms of the column pairs (pairs[p][0], pairs[p][1]) of values (F, NC) fp32, with
+ * an edge table per pair and per axis: edges_x, edges_y fp64 [P][bins + 1], ascending (mdgen_traj_histograms has one table for both
+ * axes of every pair).  The same binning rule: searchsorted(edges, x, 'right') - 1 of the value widened to fp64, the last edge in the
+ * last bin, a value outside (or NaN) in no bin; a sample with such a coordinate is counted in dropped.
+ *   hist2 int64 [P][bins][bins] (first index: the pair's first column), dropped int64 [P]: both are zeroed and filled.
+ * -2: F < 1, NC < 1 or > 32768, P < 0 or > 32768, bins < 1 or > 128, a pair index outside 0 .. NC - 1. */
+int32_t mdgen_traj_histograms_xy(int64_t F, int32_t NC, const float* values, int32_t P, const int32_t* pairs /* host */,
+                                 int32_t bins, const double* edges_x, const double* edges_y, int64_t* hist2, int64_t* dropped,
+                                 void* stream);
+
 /* Flow-matching training target (transport.py:138-189 `training_losses`, velocity model; path.py:113-135 `plan`
  * with GVPCPlan :177-187 or the linear ICPlan): per sample b with time t[b],
  *   xt = alpha x1 + sigma x0,  ut = alpha' x1 + sigma' x0;   GVP: alpha = sin(pi t/2), sigma = cos(pi t/2);

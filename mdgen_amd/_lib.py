@@ -30,6 +30,8 @@ EXPORTS = [
     "mdgen_sample_sde", "mdgen_sde_workspace_bytes", "mdgen_debug_sde_plan", "mdgen_debug_sde_dispatch_plan", "mdgen_debug_sde_stage",
     "mdgen_sample_sde_rng", "mdgen_debug_sde_noise", "mdgen_debug_sde_stage_rng", "mdgen_debug_philox", "mdgen_rollout_sde", "mdgen_upsample_sde", "mdgen_debug_graph_count",
     "mdgen_traj_dihedrals", "mdgen_traj_histograms", "mdgen_traj_acov", "mdgen_traj_acov_workspace_bytes",
+    "mdgen_traj_lagged_moments", "mdgen_traj_lagged_moments_workspace_bytes", "mdgen_traj_project", "mdgen_traj_series_acov",
+    "mdgen_traj_series_acov_workspace_bytes", "mdgen_traj_histograms_xy",
 ]
 
 
@@ -152,6 +154,12 @@ def _load():
     lib.mdgen_traj_histograms.argtypes = [i64, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]   # F, NF, angles | bins1, edges1 | P, pairs (host) | bins2, edges2 | ...
     lib.mdgen_traj_acov_workspace_bytes.argtypes = [i64, i32, i64, C.POINTER(sz)]
     lib.mdgen_traj_acov.argtypes = [i64, i32, i64, vp, vp, vp, vp, vp, sz, vp]   # n, NF, K | angles, acov, mean_sin, mean_cos | workspace, bytes
+    lib.mdgen_traj_lagged_moments_workspace_bytes.argtypes = [i64, i32, i64, C.POINTER(sz)]
+    lib.mdgen_traj_lagged_moments.argtypes = [i64, i32, i64, vp, vp, vp, vp, vp, vp, vp, sz, vp]   # n, NF, lag | angles | sx, sy, cxx, cyy, cxy | workspace, bytes
+    lib.mdgen_traj_project.argtypes = [i64, i32, i32, vp, vp, vp, vp, vp]   # n, NF, d | angles, mean, W, out
+    lib.mdgen_traj_series_acov_workspace_bytes.argtypes = [i64, i32, i64, C.POINTER(sz)]
+    lib.mdgen_traj_series_acov.argtypes = [i64, i32, i64, vp, vp, vp, vp, sz, vp]   # n, NS, K | x, acov, mean | workspace, bytes
+    lib.mdgen_traj_histograms_xy.argtypes = [i64, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]   # F, NC, values | P, pairs (host) | bins, edges_x, edges_y | hist2, dropped
     lib.mdgen_from_3_points.argtypes = [i64] + [vp] * 6
     lib.mdgen_path_plan.argtypes = [i64, i64, i32] + [vp] * 6
     lib.mdgen_masked_mse.argtypes = [i64, i64] + [vp] * 5

@@ -4,11 +4,18 @@ distance against the MD trajectory, and the sin/cos autocovariance behind the "d
 csrc/k_analysis.hip (`mdgen_traj_dihedrals`, `mdgen_traj_histograms`, `mdgen_traj_acov`, include/mdgen_amd.h); the arrays are on
 the device when the sampler returns and stay there until the counts and curves, a few kilobytes, are copied back.
 
-Out of scope: the tICA, k-means and MSM entries of the reference's result (`TICA-*`, `tica`, `msm`, `pcca`, ...), which pyemma's
-estimators define; plots; reading or writing XTC files.
+tICA (`tica_fit`, `tica_transform`; csrc/k_tica.hip: `mdgen_traj_lagged_moments`, `mdgen_traj_project`, `mdgen_traj_series_acov`,
+`mdgen_traj_histograms_xy`) is a closed-form estimator and is built, opt-in (`analyze(tica=True)`): lagged second moments of the
+cos/sin torsion features and the projection on the device, the D x D symmetric eigenproblem (D <= 128) in NumPy fp64 on the host.
 
-`torsion_features` imports without torch; the functions on tensors import torch and the library when they are called."""
+Out of scope: the k-means, MSM and PCCA+ entries of the reference's result (`msm`, `pcca`, metastable states, ...), which pyemma's
+seeded estimators define; plots; reading or writing XTC files.
+
+`torsion_features` and `tica_solve` import without torch; the functions on tensors import torch and the library when they are
+called."""
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import numpy as np
 
@@ -19,6 +26,8 @@ BINS_2D = 50                   # :57
 DEFAULT_PAIRS = ((1, 2), (3, 4))   # :56 `for i in [1, 3]: [:, i:i+2]`
 MD_NLAG = 100000               # :68
 NLAG = 1000                    # :87
+TICA_LAG = 1000                # mdgen/analysis.py get_tica: pyemma.coordinates.tica(lag=1000, kinetic_map=True)
+TICA_MAX_FEATURES = 64         # include/mdgen_amd.h mdgen_traj_lagged_moments: NF <= 64
 
 
 # ---- features -------------------------------------------------------------------------------------------------------
@@ -195,7 +204,275 @@ def decorrelation(angles, nlag):
     return (acov - base) / (1.0 - base)
 
 
-def analyze(traj_atom14, ref_atom14, aatype, nlag=NLAG, ref_nlag=None, pairs=DEFAULT_PAIRS, decorr=True) -> dict:
+# ---- tICA -----------------------------------------------------------------------------------------------------------
+# Features.  For angles (n, NF) in `torsion_features`' order, frame t has x_t in R^D, D = 2 NF, x[2j] = cos a_j, x[2j + 1] = sin a_j:
+# pyemma's cossin=True interleaving as the maintainers recall it, unchecked like the label order; tICA's results do not depend on
+# the order beyond rounding.  cos and sin are evaluated in fp64 and rounded to fp32 once.
+# Moments at lag tau.  m = n - tau, X = x[0 .. m), Y = x[tau .. n): sx = sum X, sy = sum Y, cxx = X'X, cyy = Y'Y, cxy = X'Y, raw fp64.
+class TicaModel(NamedTuple):
+    """What `tica_solve` returns: `lag`; `mean` fp64 [D]; `eigenvalues` fp64 [rank], descending; `W` fp64 [D][rank], the kinetic
+    map; `dim`, the number of components that hold `var_cutoff` of the kinetic variance; `rank` of C0."""
+    lag: int
+    mean: np.ndarray
+    eigenvalues: np.ndarray
+    W: np.ndarray
+    dim: int
+    rank: int
+
+    def as_dict(self) -> dict:
+        """Plain NumPy arrays and ints (what `analyze` stores: it unpickles without this package); `TicaModel(**d)` inverts it."""
+        return {"lag": int(self.lag), "mean": np.array(self.mean), "eigenvalues": np.array(self.eigenvalues), "W": np.array(self.W),
+                "dim": int(self.dim), "rank": int(self.rank)}
+
+
+def tica_solve(m, sx, sy, cxx, cyy, cxy, epsilon=1e-6, var_cutoff=0.95, lag=0) -> TicaModel:
+    """The estimator of `pyemma.coordinates.tica(lag, kinetic_map=True)` (defaults: reversible, var_cutoff 0.95, epsilon 1e-6) from
+    the raw moments of m lagged pairs, in NumPy fp64:
+
+      mu = (sx + sy) / 2m,  C0 = (cxx + cyy) / 2m - mu mu',  Ctau = (cxy + cxy') / 2m - mu mu'
+      C0 = Q S Q'; the eigenvalues s > epsilon are kept, rank r is their number, L = Q_r S_r^(-1/2)
+      L' Ctau L = R diag(lambda) R', lambda descending;  W = (L R) diag(lambda): the kinetic map
+      sign: in every column of W the entry of largest magnitude is positive (the first such entry on ties)
+      dim: the smallest d with sum_{i<d} lambda_i^2 / sum lambda_i^2 >= var_cutoff
+      transform: (x_t - mu) W[:, :d]
+
+    ValueError when rank < 2 (`TICA-0,1` needs two components)."""
+    m = int(m)
+    if m < 1:
+        raise ValueError(f"tica_solve needs m >= 1 lagged pairs, got {m}")
+    sx, sy = np.asarray(sx, np.float64).ravel(), np.asarray(sy, np.float64).ravel()
+    D = sx.shape[0]
+    cxx, cyy, cxy = (np.asarray(c, np.float64).reshape(D, D) for c in (cxx, cyy, cxy))
+    mu = (sx + sy) / (2.0 * m)
+    c0 = (cxx + cyy) / (2.0 * m) - np.outer(mu, mu)
+    ct = (cxy + cxy.T) / (2.0 * m) - np.outer(mu, mu)
+    s, q = np.linalg.eigh((c0 + c0.T) / 2.0)
+    keep = np.flatnonzero(s > epsilon)[::-1]          # descending
+    rank = int(keep.size)
+    if rank < 2:
+        raise ValueError(f"tICA needs a covariance of rank >= 2: rank {rank} of {D} features (eigenvalues above {epsilon:g})")
+    L = q[:, keep] / np.sqrt(s[keep])
+    mt = L.T @ ct @ L
+    lam, r = np.linalg.eigh((mt + mt.T) / 2.0)
+    lam, r = lam[::-1].copy(), r[:, ::-1]
+    W = (L @ r) * lam
+    big = np.argmax(np.abs(W), axis=0)                # (the first entry of largest magnitude)
+    W = W * np.where(W[big, np.arange(rank)] < 0, -1.0, 1.0)
+    share = np.cumsum(lam * lam) / np.sum(lam * lam)
+    dim = int(min(np.searchsorted(share, var_cutoff, "left") + 1, rank))
+    return TicaModel(int(lag), mu, lam, np.ascontiguousarray(W), dim, rank)
+
+
+def _check_tica_shape(n, NF, lag):
+    if not 1 <= NF <= TICA_MAX_FEATURES:
+        raise ValueError(f"tICA takes 1 .. {TICA_MAX_FEATURES} torsions, got {NF}")
+    if lag < 0 or lag > n - 1:
+        raise ValueError(f"lag must be in 0 .. n - 1 (n = {n}, lag = {lag})")
+
+
+def lagged_moments_workspace_bytes(n, NF, lag) -> int:
+    import ctypes as C
+    from ._lib import check, lib
+    b = C.c_size_t()
+    check(lib.mdgen_traj_lagged_moments_workspace_bytes(int(n), int(NF), int(lag), C.byref(b)))
+    return int(b.value)
+
+
+def lagged_moments_into(angles, lag, sx, sy, cxx, cyy, cxy, workspace) -> None:
+    """One `mdgen_traj_lagged_moments` call: angles (n, NF) fp32; sx, sy [D], cxx, cyy, cxy [D, D] fp64 written, D = 2 NF;
+    `workspace` a uint8 tensor of `lagged_moments_workspace_bytes(n, NF, lag)`."""
+    import torch
+    from ._lib import launch, lib, ptr
+    n, NF = int(angles.shape[0]), int(angles.shape[1])
+    D = 2 * NF
+    _check_tica_shape(n, NF, int(lag))
+    if sx.numel() < D or sy.numel() < D or min(cxx.numel(), cyy.numel(), cxy.numel()) < D * D:
+        raise ValueError("sx, sy need D elements, cxx, cyy, cxy D * D")
+    f64 = torch.float64
+    launch(lib.mdgen_traj_lagged_moments, angles, n, NF, int(lag), ptr(angles, torch.float32), ptr(sx, f64), ptr(sy, f64),
+           ptr(cxx, f64), ptr(cyy, f64), ptr(cxy, f64), ptr(workspace, torch.uint8), int(workspace.numel()))
+
+
+def lagged_moments(angles, lag):
+    """(sx [D], sy [D], cxx, cyy, cxy [D, D]) fp64 device tensors of angles (n, NF): the raw moments of the cos/sin features at
+    `lag` (the section's head), 0 <= lag <= n - 1, 1 <= NF <= 64."""
+    import torch
+    angles = _device_f32(angles)
+    n, NF = int(angles.shape[0]), int(angles.shape[1])
+    _check_tica_shape(n, NF, int(lag))
+    dev, D = angles.device, 2 * NF
+    ws = torch.empty(max(lagged_moments_workspace_bytes(n, NF, lag), 1), dtype=torch.uint8, device=dev)
+    sx, sy = torch.empty(D, dtype=torch.float64, device=dev), torch.empty(D, dtype=torch.float64, device=dev)
+    cxx, cyy, cxy = (torch.empty(D, D, dtype=torch.float64, device=dev) for _ in range(3))
+    lagged_moments_into(angles, lag, sx, sy, cxx, cyy, cxy, ws)
+    return sx, sy, cxx, cyy, cxy
+
+
+def tica_fit(angles, lag=TICA_LAG, epsilon=1e-6, var_cutoff=0.95) -> TicaModel:
+    """tICA of angles (n, NF), a CUDA tensor: the moments on the device, `tica_solve` on the host.  ValueError, before any launch,
+    when n - lag < 2 (one lagged pair has no covariance)."""
+    n, NF, lag = int(angles.shape[0]), int(angles.shape[1]), int(lag)
+    if lag < 0 or n - lag < 2:
+        raise ValueError(f"tICA at lag {lag} needs at least lag + 2 frames, got {n}")
+    _check_tica_shape(n, NF, lag)
+    parts = [p.cpu().numpy() for p in lagged_moments(angles, lag)]
+    return tica_solve(n - lag, *parts, epsilon=epsilon, var_cutoff=var_cutoff, lag=lag)
+
+
+def project_into(angles, mean, W, out) -> None:
+    """One `mdgen_traj_project` call: angles (n, NF) fp32, mean [D] and W [D, d] fp32 device tensors, out (n, d) fp32 written."""
+    import torch
+    from ._lib import launch, lib, ptr
+    n, NF = int(angles.shape[0]), int(angles.shape[1])
+    D = 2 * NF
+    d = int(W.numel() // D) if D else 0
+    if not 1 <= NF <= TICA_MAX_FEATURES:
+        raise ValueError(f"tICA takes 1 .. {TICA_MAX_FEATURES} torsions, got {NF}")
+    if W.ndim != 2 or W.shape[0] != D or not 1 <= d <= D:
+        raise ValueError(f"W {tuple(W.shape)}: expected [D, d] with D = {D} and 1 <= d <= D")
+    if mean.numel() != D or out.numel() < n * d:
+        raise ValueError("mean needs D elements, out n * d")
+    f32 = torch.float32
+    launch(lib.mdgen_traj_project, angles, n, NF, d, ptr(angles, f32), ptr(mean, f32), ptr(W, f32), ptr(out, f32))
+
+
+def tica_transform(model, angles, dim=None):
+    """(n, d) fp32 device tensor: (x_t - mean) W[:, :d] of angles (n, NF), d = `dim` or the model's; `mean` and `W` are rounded to
+    fp32 once, the subtraction comes first, then fp32 FMAs over the features in ascending order.  `model`: a TicaModel or its dict."""
+    import torch
+    if isinstance(model, dict):
+        model = TicaModel(**model)
+    d = int(model.dim if dim is None else dim)
+    if not 1 <= d <= model.rank:
+        raise ValueError(f"dim must be in 1 .. rank = {model.rank}, got {d}")
+    if 2 * int(angles.shape[1]) != model.mean.shape[0]:
+        raise ValueError(f"the model has {model.mean.shape[0]} features, the angles give {2 * int(angles.shape[1])}")
+    angles = _device_f32(angles)
+    dev = angles.device
+    mean = torch.from_numpy(np.asarray(model.mean, np.float64).astype(np.float32)).to(dev)
+    W = torch.from_numpy(np.ascontiguousarray(np.asarray(model.W, np.float64)[:, :d]).astype(np.float32)).to(dev)
+    out = torch.empty(int(angles.shape[0]), d, dtype=torch.float32, device=dev)
+    project_into(angles, mean, W, out)
+    return out
+
+
+def series_acov_workspace_bytes(n, NS, nlag) -> int:
+    import ctypes as C
+    from ._lib import check, lib
+    b = C.c_size_t()
+    check(lib.mdgen_traj_series_acov_workspace_bytes(int(n), int(NS), int(nlag), C.byref(b)))
+    return int(b.value)
+
+
+def series_acov_into(x, nlag, acov, mean, workspace) -> None:
+    """One `mdgen_traj_series_acov` call: x (n, NS) fp32; acov [NS, nlag + 1], mean [NS] fp64 written; `workspace` a uint8 tensor
+    of `series_acov_workspace_bytes(n, NS, nlag)`."""
+    import torch
+    from ._lib import launch, lib, ptr
+    n, NS = int(x.shape[0]), int(x.shape[1])
+    if acov.numel() < NS * (max(int(nlag), 0) + 1) or mean.numel() < NS:
+        raise ValueError("acov needs NS * (nlag + 1) elements, mean NS")
+    launch(lib.mdgen_traj_series_acov, x, n, NS, int(nlag), ptr(x, torch.float32), ptr(acov, torch.float64), ptr(mean, torch.float64),
+           ptr(workspace, torch.uint8), int(workspace.numel()))
+
+
+def series_acov(x, nlag):
+    """(acov [NS, nlag + 1], mean [NS]) fp64 device tensors of the series x (n, NS) -- or (n,), one series:
+    acov[s, k] = sum_{t < n - k} x_t x_{t+k} / (n - k), statsmodels' acovf(demean=False, adjusted=True).  nlag <= n - 1."""
+    import torch
+    x = _device_f32(x)
+    if x.ndim == 1:
+        x = x[:, None].contiguous()
+    n, NS = int(x.shape[0]), int(x.shape[1])
+    dev = x.device
+    ws = torch.empty(max(series_acov_workspace_bytes(n, NS, nlag), 1), dtype=torch.uint8, device=dev)
+    acov = torch.empty(NS, int(nlag) + 1, dtype=torch.float64, device=dev)
+    mean = torch.empty(NS, dtype=torch.float64, device=dev)
+    series_acov_into(x, nlag, acov, mean, ws)
+    return acov, mean
+
+
+def range_edges(lo, hi, bins):
+    """The fp64 bin edges of `np.histogram(range=(lo, hi), bins=bins)`; a degenerate range lo == hi becomes (lo - 0.5, hi + 0.5),
+    as NumPy makes it."""
+    lo, hi = float(lo), float(hi)
+    if lo == hi:
+        lo, hi = lo - 0.5, hi + 0.5
+    return np.linspace(lo, hi, int(bins) + 1)
+
+
+def histograms_xy_into(values, pairs, bins, edges_x, edges_y, hist2, dropped) -> None:
+    """One `mdgen_traj_histograms_xy` call: values (F, NC) fp32, `pairs` a host int32 [P, 2] array, edges_x and edges_y fp64
+    [P, bins + 1] device tensors; hist2 [P, bins, bins] and dropped [P] int64 are zeroed and filled."""
+    import torch
+    from ._lib import launch, lib, ptr
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    F, NC, P = int(values.shape[0]), int(values.shape[1]), int(pairs.shape[0])
+    if hist2.numel() < P * bins * bins or dropped.numel() < P:
+        raise ValueError("hist2 needs P * bins^2 elements, dropped P")
+    if edges_x.numel() != P * (bins + 1) or edges_y.numel() != P * (bins + 1):
+        raise ValueError("edges need P * (bins + 1) elements")
+    launch(lib.mdgen_traj_histograms_xy, values, F, NC, ptr(values, torch.float32), P, pairs.ctypes.data, int(bins),
+           ptr(edges_x, torch.float64), ptr(edges_y, torch.float64), ptr(hist2, torch.int64), ptr(dropped, torch.int64))
+
+
+def histogram2d_xy(values, pairs, bins, ranges):
+    """(hist2 [P, bins, bins], dropped [P]) int64 NumPy arrays: `np.histogram2d(x, y, bins=bins, range=ranges[p])` of the columns
+    (x, y) = pairs[p] of values (F, NC), widened to fp64, with `ranges[p]` = ((x_lo, x_hi), (y_lo, y_hi)) of its own per pair."""
+    import torch
+    values = _device_f32(values)
+    dev = values.device
+    pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
+    P = pairs.shape[0]
+    if len(ranges) != P:
+        raise ValueError("one ((x_lo, x_hi), (y_lo, y_hi)) per pair")
+    ex = np.stack([range_edges(*r[0], bins) for r in ranges]) if P else np.zeros((0, bins + 1))
+    ey = np.stack([range_edges(*r[1], bins) for r in ranges]) if P else np.zeros((0, bins + 1))
+    h2 = torch.empty(P, bins, bins, dtype=torch.int64, device=dev)
+    dr = torch.empty(P, dtype=torch.int64, device=dev)
+    histograms_xy_into(values, pairs, int(bins), torch.from_numpy(ex).to(dev), torch.from_numpy(ey).to(dev), h2, dr)
+    return h2.cpu().numpy(), dr.cpu().numpy()
+
+
+def _hist1d_range(values, column, lo, hi, bins):
+    """`np.histogram(values[:, column], bins=bins, range=(lo, hi))[0]` through `mdgen_traj_histograms`."""
+    import torch
+    col = values[:, column:column + 1].contiguous()
+    dev = col.device
+    e = torch.from_numpy(range_edges(lo, hi, bins)).to(dev)
+    h1 = torch.empty(1, bins, dtype=torch.int64, device=dev)
+    dr = torch.empty(1, dtype=torch.int64, device=dev)
+    histograms_into(col, np.zeros((0, 2), np.int32), bins, e, 1, e[:2].contiguous(), h1, h1[:0], dr)
+    return h1[0].cpu().numpy()
+
+
+def tica_entries(a_traj, a_ref, lag=TICA_LAG, nlag=NLAG, ref_nlag=None, decorr=True) -> dict:
+    """The tICA part of the reference's result (analyze_peptide_sim.py:104-150) from the two angle tensors: fit on the MD angles,
+    transform both.  {"TICA-0", "TICA-0,1"} JSDs, "model" (`TicaModel.as_dict()`) and, with `decorr`, "md_tica" / "our_tica": the
+    autocovariance of component 0, fp32, neither demeaned nor normalised, as the reference stores it."""
+    import torch
+    model = tica_fit(a_ref, lag)
+    d = max(model.dim, 2)
+    y_ref, y_traj = tica_transform(model, a_ref, d), tica_transform(model, a_traj, d)
+    lo = torch.minimum(y_ref[:, :2].amin(0), y_traj[:, :2].amin(0)).double().cpu().numpy()   # (fp32 widened: plumbing)
+    hi = torch.maximum(y_ref[:, :2].amax(0), y_traj[:, :2].amax(0)).double().cpu().numpy()
+    out = {"model": model.as_dict()}
+    out["TICA-0"] = jsd(_hist1d_range(y_ref, 0, lo[0], hi[0], BINS_1D), _hist1d_range(y_traj, 0, lo[0], hi[0], BINS_1D))
+    rng = [((lo[0], hi[0]), (lo[1], hi[1]))]
+    r2, _ = histogram2d_xy(y_ref, [(0, 1)], BINS_2D, rng)
+    t2, _ = histogram2d_xy(y_traj, [(0, 1)], BINS_2D, rng)
+    out["TICA-0,1"] = jsd(r2[0], t2[0])
+    if decorr:
+        n, n_ref = int(y_traj.shape[0]), int(y_ref.shape[0])
+        k_ref = min(MD_NLAG if ref_nlag is None else int(ref_nlag), n_ref - 1)
+        k = min(int(nlag), n - 1)
+        out["md_tica"] = series_acov(y_ref[:, 0].contiguous(), k_ref)[0][0].cpu().numpy().astype(np.float32)
+        out["our_tica"] = series_acov(y_traj[:, 0].contiguous(), k)[0][0].cpu().numpy().astype(np.float32)
+    return out
+
+
+def analyze(traj_atom14, ref_atom14, aatype, nlag=NLAG, ref_nlag=None, pairs=DEFAULT_PAIRS, decorr=True, tica=False,
+            tica_lag=TICA_LAG) -> dict:
     """The reference's per-peptide result for a sampled trajectory `traj_atom14` (F, L, 14, 3) against the MD trajectory
     `ref_atom14` (F_ref, L, 14, 3) -- a CUDA tensor, or an array that is copied to traj_atom14's device:
 
@@ -206,12 +483,23 @@ def analyze(traj_atom14, ref_atom14, aatype, nlag=NLAG, ref_nlag=None, pairs=DEF
       "our_decorrelation"  {label: fp32 array [nlag + 1]} of `decorrelation` (nlag clamped to F - 1)
       "md_decorrelation"   the same of the MD trajectory, ref_nlag = min(100000, F_ref - 1) by default
 
-    The last two only with `decorr`.  Plain Python and NumPy objects only.  The reference's tICA / MSM entries are not computed."""
+    The last two only with `decorr`.  With `tica` (`tica_entries`: fitted on the MD trajectory at lag `tica_lag`), after these:
+    JSD["TICA-0"] (100 bins over the two trajectories' common range of component 0) and JSD["TICA-0,1"] (50 x 50), with `decorr`
+    our_decorrelation["tica"] / md_decorrelation["tica"], and
+
+      "tica_model"         `TicaModel.as_dict()`: lag, mean, eigenvalues, W, dim, rank
+
+    ValueError when the MD trajectory has fewer than tica_lag + 2 frames, no torsions or more than 64, or a covariance of rank < 2.
+    Plain Python and NumPy objects only.  The reference's k-means / MSM / PCCA+ entries are not computed."""
     aat = _checked_aatype(aatype.cpu().numpy() if hasattr(aatype, "cpu") else aatype)
     traj = _device_f32(traj_atom14)
     ref = _device_f32(ref_atom14, traj.device)
     labels, _ = torsion_features(aat)
     NF = len(labels)
+    if tica:   # (what tica_fit would refuse, before any launch)
+        if int(tica_lag) < 0 or int(ref.shape[0]) - int(tica_lag) < 2:
+            raise ValueError(f"tICA at lag {int(tica_lag)} needs at least lag + 2 frames, got {int(ref.shape[0])}")
+        _check_tica_shape(int(ref.shape[0]), NF, int(tica_lag))
     out = {"features": list(labels), "JSD": {}}
     a_traj, a_ref = featurize(traj, aat), featurize(ref, aat)
     pairs = [(int(a), int(b)) for a, b in pairs if 0 <= int(a) < NF and 0 <= int(b) < NF]
@@ -230,4 +518,10 @@ def analyze(traj_atom14, ref_atom14, aatype, nlag=NLAG, ref_nlag=None, pairs=DEF
         our = decorrelation(a_traj, k).cpu().numpy().astype(np.float32) if NF else np.zeros((0, k + 1), np.float32)
         out["our_decorrelation"] = {lab: our[i] for i, lab in enumerate(labels)}
         out["md_decorrelation"] = {lab: md[i] for i, lab in enumerate(labels)}
+    if tica:
+        t = tica_entries(a_traj, a_ref, tica_lag, nlag, ref_nlag, decorr)
+        out["JSD"]["TICA-0"], out["JSD"]["TICA-0,1"] = t["TICA-0"], t["TICA-0,1"]
+        if decorr:
+            out["our_decorrelation"]["tica"], out["md_decorrelation"]["tica"] = t["our_tica"], t["md_tica"]
+        out["tica_model"] = t["model"]
     return out

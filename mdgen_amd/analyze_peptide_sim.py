@@ -7,11 +7,15 @@
   --pdb_id ...       the peptides (default: every name of the split with a trajectory in --pdbdir);
   --truncate N       only the first N sampled frames;  --no_decorr  skip the decorrelation curves;
   --save / --save_name   pickle {name: result} to `{pdbdir}/{save_name}`;
-  --no_msm           REQUIRED: the tICA / k-means / MSM part of the reference's result is defined by pyemma's estimators and is
+  --tica [--tica_lag N]   also the tICA entries (`analyze(tica=True)`: JSD "TICA-0" / "TICA-0,1", the "tica" decorrelation
+                     curves, "tica_model"), fitted on the MD trajectory at lag N (default 1000).  A peptide whose MD trajectory
+                     is too short for the lag (or whose covariance has rank < 2) is named on stderr and gets the other entries;
+  --no_msm           REQUIRED: the k-means / MSM / PCCA+ part of the reference's result is defined by pyemma's estimators and is
                      not computed here.  Without the flag the command is refused before anything is read (exit status 2), so that
                      a pipeline that needs those entries does not find out afterwards;  --no_traj_msm is accepted.
 
-Per peptide the result is `mdgen_amd.analysis.analyze`'s dict: "features", "JSD", "our_decorrelation", "md_decorrelation".
+Per peptide the result is `mdgen_amd.analysis.analyze`'s dict: "features", "JSD", "our_decorrelation", "md_decorrelation"
+(and "tica_model" with --tica).
 No plots (--plot does not exist), no XTC files."""
 from __future__ import annotations
 
@@ -37,6 +41,8 @@ def build_parser():
     p.add_argument("--save_name", type=str, default="out.pkl")
     p.add_argument("--no_msm", action="store_true")
     p.add_argument("--no_traj_msm", action="store_true")
+    p.add_argument("--tica", action="store_true")
+    p.add_argument("--tica_lag", type=int, default=1000)
     return p
 
 
@@ -66,6 +72,18 @@ def load_trajectory(path, aatype):
     return np.load(path, mmap_mode="r") if path.endswith(".npy") else pdb_to_atom14(path, aatype)
 
 
+def analyze_one(name, traj, ref, aatype, tica=False, tica_lag=1000, **kw):
+    """`analyze`; a peptide whose tICA is refused (MD trajectory too short for the lag, rank < 2, no torsions) is named on stderr
+    and analysed without the tICA entries."""
+    from .analysis import analyze
+    if tica:
+        try:
+            return analyze(traj, ref, aatype, tica=True, tica_lag=tica_lag, **kw)
+        except ValueError as e:
+            print(f"{name}: no tICA entries: {e}", file=sys.stderr)
+    return analyze(traj, ref, aatype, **kw)
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     require_no_msm(args)
@@ -85,7 +103,6 @@ def main(argv=None):
             raise SystemExit(f"error: no MD trajectory of {n}: {p} does not exist")
     print("number of trajectories", len(names))
     import torch
-    from .analysis import analyze
     from .geometry import restype_order
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     out = {}
@@ -95,7 +112,8 @@ def main(argv=None):
         if args.truncate:
             traj = traj[:args.truncate]
         traj = torch.from_numpy(np.array(traj, np.float32)).to(device)   # (a copy: the memory map is read-only)
-        out[n] = analyze(traj, np.load(refs[n], mmap_mode="r"), aat, decorr=not args.no_decorr)
+        out[n] = analyze_one(n, traj, np.load(refs[n], mmap_mode="r"), aat, decorr=not args.no_decorr, tica=args.tica,
+                             tica_lag=args.tica_lag)
         jsd = out[n]["JSD"]
         print(f"{n}: {len(out[n]['features'])} torsions, mean JSD {np.mean(list(jsd.values())) if jsd else float('nan'):.4f}")
     if args.save:

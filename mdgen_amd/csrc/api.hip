@@ -2414,6 +2414,87 @@ extern "C" int32_t mdgen_traj_acov(int64_t n, int32_t NF, int64_t K, const float
     return 0;
 }
 
+// tICA (k_tica.hip): the same conventions
+static int traj_moments_shape(int64_t n, int32_t NF, int64_t lag) {
+    if (n < 1 || n > kTrajMaxFrames) return fail(-2, "n must be in 1 .. 2^40");
+    if (NF < 0 || NF > kTicaMaxFeatures) return fail(-2, "NF must be in 0 .. %d", kTicaMaxFeatures);
+    if (lag < 0 || lag > n - 1) return fail(-2, "lag must be in 0 .. n - 1 (n = %lld, lag = %lld)", (long long)n, (long long)lag);
+    return 0;
+}
+
+extern "C" int32_t mdgen_traj_lagged_moments_workspace_bytes(int64_t n, int32_t NF, int64_t lag, size_t* bytes) {
+    NONNULL(bytes);
+    if (int rc = traj_moments_shape(n, NF, lag)) return rc;
+    *bytes = NF == 0 ? 0 : moments_workspace_bytes(n, NF, lag);
+    return 0;
+}
+
+extern "C" int32_t mdgen_traj_lagged_moments(int64_t n, int32_t NF, int64_t lag, const float* angles, double* sx, double* sy,
+                                             double* cxx, double* cyy, double* cxy, void* workspace, size_t workspace_bytes,
+                                             void* stream) {
+    if (int rc = traj_moments_shape(n, NF, lag)) return rc;
+    if (NF == 0) return 0;
+    NONNULL(angles, sx, sy, cxx, cyy, cxy, workspace);
+    const size_t need = moments_workspace_bytes(n, NF, lag);
+    if (workspace_bytes < need) return fail(-3, "workspace too small: %zu < %zu", workspace_bytes, need);
+    if ((uintptr_t)workspace % 16) return fail(-2, "workspace must be 16-byte aligned");
+    launch_lagged_moments(n, NF, lag, angles, sx, sy, cxx, cyy, cxy, workspace, (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
+
+extern "C" int32_t mdgen_traj_project(int64_t n, int32_t NF, int32_t d, const float* angles, const float* mean, const float* W,
+                                      float* out, void* stream) {
+    if (n < 1 || n > kTrajMaxFrames) return fail(-2, "n must be in 1 .. 2^40");
+    if (NF < 0 || NF > kTicaMaxFeatures) return fail(-2, "NF must be in 0 .. %d", kTicaMaxFeatures);
+    if (NF == 0) return 0;
+    if (d < 1 || d > 2 * NF) return fail(-2, "d must be in 1 .. 2 NF (NF = %d, d = %d)", NF, d);
+    NONNULL(angles, mean, W, out);
+    launch_project(n, NF, d, angles, mean, W, out, (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
+
+extern "C" int32_t mdgen_traj_series_acov_workspace_bytes(int64_t n, int32_t NS, int64_t K, size_t* bytes) {
+    NONNULL(bytes);
+    if (int rc = traj_acov_shape(n, NS, K)) return rc;
+    *bytes = NS == 0 ? 0 : series_acov_workspace_bytes(n, NS, K);
+    return 0;
+}
+
+extern "C" int32_t mdgen_traj_series_acov(int64_t n, int32_t NS, int64_t K, const float* x, double* acov, double* mean,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = traj_acov_shape(n, NS, K)) return rc;
+    if (NS == 0) return 0;
+    NONNULL(x, acov, mean, workspace);
+    const size_t need = series_acov_workspace_bytes(n, NS, K);
+    if (workspace_bytes < need) return fail(-3, "workspace too small: %zu < %zu", workspace_bytes, need);
+    if ((uintptr_t)workspace % 16) return fail(-2, "workspace must be 16-byte aligned");
+    launch_series_acov(n, NS, K, x, acov, mean, workspace, (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
+
+extern "C" int32_t mdgen_traj_histograms_xy(int64_t F, int32_t NC, const float* values, int32_t P, const int32_t* pairs, int32_t bins,
+                                            const double* edges_x, const double* edges_y, int64_t* hist2, int64_t* dropped,
+                                            void* stream) {
+    if (F < 1 || F > kTrajMaxFrames) return fail(-2, "F must be in 1 .. 2^40");
+    if (NC < 1 || NC > kTrajMaxFeatures) return fail(-2, "NC must be in 1 .. 32768");
+    if (P < 0 || P > kTrajMaxFeatures) return fail(-2, "P must be in 0 .. 32768");
+    if (bins < 1 || bins * (int64_t)bins > kHistMaxCells) return fail(-2, "bins must be in 1 .. 128");
+    if (P == 0) return 0;
+    NONNULL(values, pairs, edges_x, edges_y, hist2, dropped);
+    for (int64_t i = 0; i < (int64_t)P * 2; ++i)
+        if (pairs[i] < 0 || pairs[i] >= NC)
+            return fail(-2, "pairs[%lld][%d] = %d is outside the %d columns", (long long)(i / 2), (int)(i % 2), pairs[i], NC);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(hist2, 0, (size_t)P * bins * bins * sizeof(int64_t), s));
+    HIPCHK(hipMemsetAsync(dropped, 0, (size_t)P * sizeof(int64_t), s));
+    launch_hist_xy(F, NC, values, P, pairs, bins, edges_x, edges_y, hist2, dropped, s);
+    LAUNCHCHK();
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // flow-matching training target and loss (forward only)
 // ---------------------------------------------------------------------------------------------

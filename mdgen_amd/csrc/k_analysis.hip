@@ -6,9 +6,10 @@
 //   k_sincos_prep    angles [n][NF] -> sin, cos as fp32 rows [NF][n] (evaluated in fp64, rounded once)
 //   k_sincos_acov    one workgroup per (feature, lag block of 256, split of the time tiles): direct evaluation from LDS, an
 //                    8 x 8 register block per thread; fp32 over 256 samples, fp64 beyond; partial sums to the workspace
+//                    (the body is acov_body<2> of analysis.h, which k_tica.hip runs on one row)
 //   k_acov_finish    partial sums added in split order, divided by n - k;  k_sincos_mean: the per-feature means
 // No floating-point atomics anywhere: every sum has a fixed order, two calls give the same bits.
-#include "kernels.h"
+#include "analysis.h"
 
 namespace mdg {
 
@@ -60,18 +61,6 @@ void launch_dihedrals(long F, int L, int NF, const float* atom14, const int32_t*
 }
 
 // ---- histograms -----------------------------------------------------------------------------------------------------
-// searchsorted(e, x, 'right') - 1 with x == e[bins] in the last bin; -1: outside [e[0], e[bins]] (or NaN).  The guess is the
-// uniform-bin arithmetic, the table decides.
-__device__ __forceinline__ int hist_bin(double x, const double* __restrict__ e, int bins) {
-    const double lo = e[0], hi = e[bins];
-    if (!(x >= lo && x <= hi)) return -1;
-    int b = hi > lo ? (int)((x - lo) / (hi - lo) * bins) : 0;
-    b = b < 0 ? 0 : (b > bins - 1 ? bins - 1 : b);
-    while (b > 0 && x < e[b]) --b;
-    while (b < bins - 1 && x >= e[b + 1]) ++b;
-    return b;
-}
-
 // blockIdx.y: histogram unit -- u < n1: the 1-D histogram of feature u; else pair u - n1 of this launch's chunk.
 // blockIdx.x: frames [x * chunk, (x + 1) * chunk).  Dynamic LDS: max(bins1, bins2 * bins2) ints.
 __global__ __launch_bounds__(256) void k_torsion_hist(const float* __restrict__ angles, long F, int NF, long chunk, int n1, int bins1,
@@ -141,14 +130,6 @@ void launch_torsion_hist(long F, int NF, const float* angles, int bins1, const d
 }
 
 // ---- sin/cos autocovariance -----------------------------------------------------------------------------------------
-constexpr int kAcTT = 2048;                     // samples t of a time tile
-constexpr int kAcLB = 256;                      // lags of a lag block
-constexpr int kAcR = 8;                         // lags per thread (and samples per inner step)
-constexpr int kAcGroups = kAcLB / kAcR;         // 32 lag groups ...
-constexpr int kAcStrips = 256 / kAcGroups;      // ... x 8 strips of the tile
-constexpr int kAcStrip = kAcTT / kAcStrips;     // 256 samples: the length of an fp32 partial sum (x 2: sin and cos)
-constexpr int kAcWin = kAcTT + kAcLB;           // floats of a tile's lag window ...
-constexpr int kAcWinPad = kAcWin + 4 * (kAcWin / 64);   // ... and with 16 bytes of padding behind every 256 (ac_win)
 constexpr long kAcTargetGroups = 2048;          // workgroups wanted on the chip (8 a CU)
 constexpr int kAcMaxSplits = 64;
 
@@ -207,88 +188,10 @@ __global__ __launch_bounds__(256) void k_sincos_mean(const float* __restrict__ S
     }
 }
 
-// Where float i of the lag window lives.  A lane reads its 8 new window values as two ds_read_b128, lanes 32 bytes apart: unpadded,
-// lanes l and l + 8 of a 16-lane group meet on one bank (256 bytes apart); the padding moves lane l + 8 to the other half of the slot.
-__device__ __forceinline__ int ac_win(int i) { return i + 4 * (i >> 6); }
-
-// acc[r] += sum_u a[u] * w[u + r]: 8 samples x 8 lags from 8 + 16 registers
-__device__ __forceinline__ void ac_block(const float4& a0, const float4& a1, const float4& l0, const float4& l1, const float4& h0,
-                                         const float4& h1, float (&acc)[kAcR]) {
-    const float a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-    const float w[16] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w, h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-#pragma unroll
-        for (int r = 0; r < kAcR; ++r) acc[r] = fmaf(a[u], w[u + r], acc[r]);
-}
-
-// Workgroup (lag block lb, split sp, feature f): lags k0 .. k0 + 255, time tiles sp, sp + S, ... of those that hold a t with
-// t + k0 < n.  A tile stages x[t0 .. t0 + TT) and x[t0 + k0 .. t0 + k0 + TT + LB) of the sin and of the cos row, zero beyond n: the
-// products past the series' end vanish without a branch.  Thread (strip st, lag group lg) walks 256 samples of the tile 8 at a time
-// against a 16-wide sliding window, for its 8 lags.
+// acov_body<2> (analysis.h): the sin row and the cos row of feature f, their products summed
 __global__ __launch_bounds__(256) void k_sincos_acov(const float* __restrict__ S, const float* __restrict__ Cc, long n, long K,
                                                      int splits, int lag_blocks, double* __restrict__ partial) {
-    __shared__ __attribute__((aligned(16))) float aS[kAcTT], aC[kAcTT], bS[kAcWinPad], bC[kAcWinPad];
-    __shared__ double red[kAcStrips][kAcLB];
-    const long bid = blockIdx.x;
-    const int lb = (int)(bid % lag_blocks);
-    const int sp = (int)((bid / lag_blocks) % splits);
-    const long f = bid / ((long)lag_blocks * splits);
-    const long k0 = (long)lb * kAcLB;
-    const long tiles = (n - k0 + kAcTT - 1) / kAcTT;   // k0 <= K <= n - 1: at least one
-    const int lg = threadIdx.x & (kAcGroups - 1), st = threadIdx.x / kAcGroups;
-    const float* rowS = S + f * n;
-    const float* rowC = Cc + f * n;
-    double acc64[kAcR];
-#pragma unroll
-    for (int r = 0; r < kAcR; ++r) acc64[r] = 0.0;
-    for (long tile = sp; tile < tiles; tile += splits) {
-        const long t0 = tile * kAcTT;
-        __syncthreads();
-        for (int i = threadIdx.x; i < kAcTT; i += 256) {
-            const long g = t0 + i;
-            aS[i] = g < n ? rowS[g] : 0.f;
-            aC[i] = g < n ? rowC[g] : 0.f;
-        }
-        for (int i = threadIdx.x; i < kAcTT + kAcLB; i += 256) {
-            const long g = t0 + k0 + i;
-            bS[ac_win(i)] = g < n ? rowS[g] : 0.f;
-            bC[ac_win(i)] = g < n ? rowC[g] : 0.f;
-        }
-        __syncthreads();
-        float acc[kAcR];
-#pragma unroll
-        for (int r = 0; r < kAcR; ++r) acc[r] = 0.f;
-        const float4* pa = (const float4*)(aS + st * kAcStrip);
-        const float4* pc = (const float4*)(aC + st * kAcStrip);
-        const int w0 = st * kAcStrip + lg * kAcR;   // the thread's window starts here; last read: float 1792 + 248 + 248 + 15 = 2303
-        float4 ls0 = *(const float4*)(bS + ac_win(w0)), ls1 = *(const float4*)(bS + ac_win(w0) + 4);
-        float4 lc0 = *(const float4*)(bC + ac_win(w0)), lc1 = *(const float4*)(bC + ac_win(w0) + 4);
-#pragma unroll 2
-        for (int j = 0; j < kAcStrip / 8; ++j) {
-            const int w = ac_win(w0 + 8 * j + 8);    // (8 floats from a multiple of 8 never straddle a pad)
-            const float4 hs0 = *(const float4*)(bS + w), hs1 = *(const float4*)(bS + w + 4);
-            const float4 hc0 = *(const float4*)(bC + w), hc1 = *(const float4*)(bC + w + 4);
-            ac_block(pa[2 * j], pa[2 * j + 1], ls0, ls1, hs0, hs1, acc);
-            ac_block(pc[2 * j], pc[2 * j + 1], lc0, lc1, hc0, hc1, acc);
-            ls0 = hs0;
-            ls1 = hs1;
-            lc0 = hc0;
-            lc1 = hc1;
-        }
-#pragma unroll
-        for (int r = 0; r < kAcR; ++r) acc64[r] += (double)acc[r];
-    }
-#pragma unroll
-    for (int r = 0; r < kAcR; ++r) red[st][lg * kAcR + r] = acc64[r];
-    __syncthreads();
-    const long k = k0 + threadIdx.x;
-    if (k <= K) {
-        double sum = red[0][threadIdx.x];
-#pragma unroll
-        for (int q = 1; q < kAcStrips; ++q) sum += red[q][threadIdx.x];
-        partial[(f * splits + sp) * (K + 1) + k] = sum;   // every (f, sp, k) is written: zero where the split has no tile
-    }
+    acov_body<2>(S, Cc, n, K, splits, lag_blocks, partial);
 }
 
 __global__ __launch_bounds__(256) void k_acov_finish(const double* __restrict__ partial, long n, long K, int NF, int splits,
@@ -302,6 +205,12 @@ __global__ __launch_bounds__(256) void k_acov_finish(const double* __restrict__ 
     }
 }
 
+void launch_acov_finish(const double* partial, long n, long K, int NF, int splits, double* acov, hipStream_t s) {
+    const long fin = ((long)NF * (K + 1) + 255) / 256;
+    hipLaunchKernelGGL(k_acov_finish, dim3((unsigned)(fin < (1l << 20) ? fin : (1l << 20))), dim3(256), 0, s, partial, n, K, NF, splits,
+                       acov);
+}
+
 void launch_sincos_acov(long n, int NF, long K, const float* angles, double* acov, double* mean_sin, double* mean_cos, void* ws,
                         hipStream_t s) {
     const int splits = acov_splits(n, NF, K);
@@ -313,9 +222,7 @@ void launch_sincos_acov(long n, int NF, long K, const float* angles, double* aco
     hipLaunchKernelGGL(k_sincos_prep, dim3((unsigned)(want < (1l << 20) ? want : (1l << 20))), dim3(256), 0, s, angles, n, NF, S, Cc);
     hipLaunchKernelGGL(k_sincos_mean, dim3((unsigned)NF), dim3(256), 0, s, S, Cc, n, mean_sin, mean_cos);
     hipLaunchKernelGGL(k_sincos_acov, dim3((unsigned)acov_groups(n, NF, K)), dim3(256), 0, s, S, Cc, n, K, splits, lag_blocks, partial);
-    const long fin = ((long)NF * (K + 1) + 255) / 256;
-    hipLaunchKernelGGL(k_acov_finish, dim3((unsigned)(fin < (1l << 20) ? fin : (1l << 20))), dim3(256), 0, s, partial, n, K, NF, splits,
-                       acov);
+    launch_acov_finish(partial, n, K, NF, splits, acov, s);
 }
 
 }  // namespace mdg

@@ -640,5 +640,20 @@ size_t acov_workspace_bytes(long n, int NF, long K);
 long acov_groups(long n, int NF, long K);   // workgroups of k_sincos_acov
 void launch_sincos_acov(long n, int NF, long K, const float* angles, double* acov, double* mean_sin, double* mean_cos, void* ws,
                         hipStream_t s);
+// acov[f][k] = (sum over the splits, in split order, of partial[f][split][k]) / (n - k)
+void launch_acov_finish(const double* partial, long n, long K, int NF, int splits, double* acov, hipStream_t s);
+
+// tICA (k_tica.hip): lagged second moments of the cos/sin features, the projection, a plain series' autocovariance, and 2-D
+// histograms with an edge table per pair and axis
+constexpr int kTicaMaxFeatures = 64;   // torsions: D = 2 NF <= 128 features
+size_t moments_workspace_bytes(long n, int NF, long lag);
+void launch_lagged_moments(long n, int NF, long lag, const float* angles, double* sx, double* sy, double* cxx, double* cyy, double* cxy,
+                           void* ws, hipStream_t s);
+void launch_project(long n, int NF, int d, const float* angles, const float* mean, const float* W, float* out, hipStream_t s);
+size_t series_acov_workspace_bytes(long n, int NS, long K);
+void launch_series_acov(long n, int NS, long K, const float* x, double* acov, double* mean, void* ws, hipStream_t s);
+// hist2 [P][bins][bins] and dropped [P] must be zero on entry
+void launch_hist_xy(long F, int NC, const float* values, int P, const int32_t* pairs_host, int bins, const double* edges_x,
+                    const double* edges_y, int64_t* hist2, int64_t* dropped, hipStream_t s);
 
 }  // namespace mdg

@@ -20,7 +20,8 @@
   --analyze          after each group is sampled, `mdgen_amd.analysis.analyze` runs on the device tensor against the peptide's
                      conditioning array (the MD trajectory `{data_dir}/{name}{suffix}.npy`): torsion JSDs and decorrelation curves,
                      `{out_dir}/analysis.pkl` = {name: result} at the end.  Its time is outside the reported frames/s and printed
-                     on its own line.
+                     on its own line.  --tica [--tica_lag N]  adds `analyze(tica=True)`'s entries; a peptide whose MD trajectory is
+                     too short for the lag is named on stderr and keeps its torsion entries.
 
 The rollout (sim_inference.py:61-98) stays on the device: each block's last frame becomes the next block's
 conditioning frame through `mdgen_atom14_to_cond` (no D->H->D round trip).  Output, as the reference
@@ -203,10 +204,11 @@ def run(args, model, device, names_seqres, rank=0, world=1, batch_fn=make_group_
             if args.npy:
                 np.save(os.path.join(args.out_dir, f"{n}.npy"), host[i])
             if getattr(args, "analyze", False):
-                from .analysis import analyze
+                from .analyze_peptide_sim import analyze_one
                 sync()
                 start = time.time()
-                analysis[n] = analyze(all_atom14[i], arrs[n], aat)
+                analysis[n] = analyze_one(n, all_atom14[i], arrs[n], aat, tica=getattr(args, "tica", False),
+                                          tica_lag=getattr(args, "tica_lag", 1000))
                 sync()
                 analysis_s += time.time() - start
     job_s = max_over_ranks(total_s, dist)
@@ -250,6 +252,10 @@ def build_parser():
     p.add_argument("--npy", action="store_true", help="also save the sampled atom14 array as .npy")
     p.add_argument("--analyze", action="store_true",
                    help="torsion JSDs and decorrelation curves against the conditioning trajectory -> {out_dir}/analysis.pkl")
+    p.add_argument("--tica", action="store_true",
+                   help="with --analyze: also the tICA entries (TICA-0 / TICA-0,1 JSDs, 'tica' curves, tica_model); a peptide whose "
+                        "MD trajectory is too short for the lag is named on stderr and keeps its torsion entries")
+    p.add_argument("--tica_lag", type=int, default=1000, help="the tICA lag in frames of the MD trajectory (reference: 1000)")
     return p
 
 

@@ -5,8 +5,17 @@
   acov          `mdgen_traj_acov` at the sampler's size (n 1e5, K 1000, NF 25) and at the reference's MD size (n 1e6, K 1e5)
   fft           the same autocovariance through torch.fft on the same device (fp32, zero-padded to 2^ceil(log2(2 n))): for scale
   numpy         the same through np.fft on the host (fp64), sampler size only: what a script without the device would do
+  moments       `mdgen_traj_lagged_moments`: n = 1e5 and 1e6 frames, NF 25 (D = 50 features), lag 1000
+  project       `mdgen_traj_project`: n = 1e6, NF 25, d = 2 and d = 10
+  series        `mdgen_traj_series_acov`: one series at the sampler's size (n 1e5, K 1000) and at the MD size (n 1e6, K 1e5)
+  tica          `analyze(tica=True)` of one tetrapeptide, 1e5 sampled frames against 1e6 MD frames, beside `analyze()` without it
 
-    python scripts/analysis_bench.py [--leg all|dihedrals|histograms|acov|fft|numpy] [--size sampler|md|both] [--reps 5]
+Beside each of the last four, `numpy_ms`: the same definition in NumPy fp64 on the host, the copy of the device array to the host
+included (moments: cos / sin, three matrix products and two sums; project: cos / sin, the centred product; series: np.fft; tica:
+the tICA entries -- moments, solver, two projections, four histograms, two autocovariances -- from the angles).
+
+    python scripts/analysis_bench.py [--leg all|dihedrals|histograms|acov|fft|numpy|moments|project|series|tica] [--size sampler|md|both]
+                                     [--reps 5]
 
 acov reports multiply-adds (2 n' (K + 1) NF with n' the mean number of terms per lag) over time and that rate's share of the
 fp32 vector peak (157.3 TFLOP/s = 78.6e12 multiply-adds / s)."""
@@ -51,9 +60,106 @@ def macs(n, K, NF):
     return 2.0 * NF * float((n - k).sum())
 
 
+def host_features(ang):
+    """fp64 cos / sin features of a device angle tensor, interleaved: the copy to the host is part of what is timed."""
+    a = ang.double().cpu().numpy()
+    x = np.empty((a.shape[0], 2 * a.shape[1]))
+    x[:, 0::2], x[:, 1::2] = np.cos(a), np.sin(a)
+    return x
+
+
+def host_acov(x, K):
+    n = x.shape[0]
+    m = 1 << int(np.ceil(np.log2(2 * n)))
+    f = np.fft.rfft(x, m)
+    return np.fft.irfft(f * np.conj(f), m)[:K + 1] / (n - np.arange(K + 1))
+
+
+def host_ms(fn):
+    t0 = time.perf_counter()
+    fn()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def tica_legs(a, A, dev, want):
+    NF, lag = 25, 1000
+    for n in (100000, 1000000):
+        if not (want("moments") or (n == 1000000 and want("project"))):
+            continue
+        ang = angles(n, NF, dev)
+        D, m = 2 * NF, n - lag
+        if want("moments"):
+            ws = torch.empty(A.lagged_moments_workspace_bytes(n, NF, lag), dtype=torch.uint8, device=dev)
+            sx, sy = (torch.empty(D, dtype=torch.float64, device=dev) for _ in range(2))
+            cxx, cyy, cxy = (torch.empty(D, D, dtype=torch.float64, device=dev) for _ in range(3))
+            best, med = timed_ms(lambda: A.lagged_moments_into(ang, lag, sx, sy, cxx, cyy, cxy, ws), a.reps)
+
+            def on_host():
+                x = host_features(ang)
+                X, Y = x[:m], x[lag:]
+                return X.sum(0), Y.sum(0), X.T @ X, Y.T @ Y, X.T @ Y
+            ref = on_host()
+            err = max(float(np.abs(g.cpu().numpy() - w).max()) / m for g, w in zip((sx, sy, cxx, cyy, cxy), ref))
+            rate = 3.0 * D * D * m / (best * 1e-3)
+            print(json.dumps({"leg": "moments", "n": n, "NF": NF, "lag": lag, "ms_best": best, "ms_median": med,
+                              "workspace_MB": ws.numel() / 1e6, "fma_per_s": rate, "share_of_fp32_vector_peak": rate / FMA_PEAK,
+                              "feature_read_GB_per_s": 2 * n * D * 4 / best / 1e6, "max_abs_err_over_m": err,
+                              "numpy_ms": host_ms(on_host)}))
+        if want("project") and n == 1000000:
+            g = torch.Generator().manual_seed(2)
+            mean = (0.3 * torch.randn(D, generator=g)).to(dev)
+            for d in (2, 10):
+                W = torch.randn(D, d, generator=g).to(dev)
+                out = torch.empty(n, d, device=dev)
+                best, med = timed_ms(lambda: A.project_into(ang, mean, W, out), a.reps)
+                on_host = lambda: (host_features(ang) - mean.double().cpu().numpy()) @ W.double().cpu().numpy()   # noqa: E731
+                err = float(np.abs(out.cpu().numpy() - on_host()).max())
+                print(json.dumps({"leg": "project", "n": n, "NF": NF, "d": d, "ms_best": best, "ms_median": med,
+                                  "GB_per_s": (ang.numel() + out.numel()) * 4 / best / 1e6, "max_abs_err": err,
+                                  "numpy_ms": host_ms(on_host)}))
+    if want("series"):
+        for size in [s for s in SIZES if a.size in ("both", s)]:
+            n, K, _ = SIZES[size]
+            x = (3.0 * angles(n, 1, dev) + 0.5).contiguous()
+            ws = torch.empty(A.series_acov_workspace_bytes(n, 1, K), dtype=torch.uint8, device=dev)
+            acov = torch.empty(1, K + 1, dtype=torch.float64, device=dev)
+            mean = torch.empty(1, dtype=torch.float64, device=dev)
+            best, med = timed_ms(lambda: A.series_acov_into(x, K, acov, mean, ws), a.reps)
+            on_host = lambda: host_acov(x[:, 0].double().cpu().numpy(), K)   # noqa: E731
+            err = float(np.abs(acov[0].cpu().numpy() - on_host()).max())
+            rate = macs(n, K, 1) / 2 / (best * 1e-3)
+            print(json.dumps({"leg": "series", "size": size, "n": n, "K": K, "NS": 1, "ms_best": best, "ms_median": med,
+                              "fma_per_s": rate, "share_of_fp32_vector_peak": rate / FMA_PEAK, "max_abs_err": err,
+                              "numpy_ms": host_ms(on_host)}))
+    if want("tica"):
+        aat = np.array([3, 10, 1, 8])
+        g = torch.Generator(device=dev).manual_seed(3)
+        traj = torch.randn(100000, 4, 14, 3, generator=g, device=dev) * 3
+        ref = torch.randn(1000000, 4, 14, 3, generator=g, device=dev) * 3
+        plain_best, plain_med = timed_ms(lambda: A.analyze(traj, ref, aat), max(a.reps // 2, 1))
+        best, med = timed_ms(lambda: A.analyze(traj, ref, aat, tica=True), max(a.reps // 2, 1))
+        a_traj, a_ref = A.featurize(traj, aat), A.featurize(ref, aat)
+
+        def on_host():
+            xr, xt = host_features(a_ref), host_features(a_traj)
+            mm = xr.shape[0] - A.TICA_LAG
+            X, Y = xr[:mm], xr[A.TICA_LAG:]
+            model = A.tica_solve(mm, X.sum(0), Y.sum(0), X.T @ X, Y.T @ Y, X.T @ Y, lag=A.TICA_LAG)
+            yr, yt = ((x - model.mean) @ model.W[:, :max(model.dim, 2)] for x in (xr, xt))
+            lo, hi = np.minimum(yr[:, :2].min(0), yt[:, :2].min(0)), np.maximum(yr[:, :2].max(0), yt[:, :2].max(0))
+            rng = ((lo[0], hi[0]), (lo[1], hi[1]))
+            j1 = A.jsd(*(np.histogram(y[:, 0], range=rng[0], bins=100)[0] for y in (yr, yt)))
+            j2 = A.jsd(*(np.histogram2d(y[:, 0], y[:, 1], range=rng, bins=50)[0] for y in (yr, yt)))
+            return j1, j2, host_acov(yr[:, 0], A.MD_NLAG), host_acov(yt[:, 0], A.NLAG)
+        print(json.dumps({"leg": "tica", "frames": 100000, "md_frames": 1000000, "NF": a_ref.shape[1], "tica_lag": A.TICA_LAG,
+                          "analyze_ms_best": plain_best, "analyze_ms_median": plain_med, "analyze_tica_ms_best": best,
+                          "analyze_tica_ms_median": med, "tica_part_ms": best - plain_best, "numpy_ms": host_ms(on_host)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", default="all", choices=["all", "dihedrals", "histograms", "acov", "fft", "numpy"])
+    ap.add_argument("--leg", default="all", choices=["all", "dihedrals", "histograms", "acov", "fft", "numpy", "moments", "project",
+                                                     "series", "tica"])
     ap.add_argument("--size", default="both", choices=["sampler", "md", "both"])
     ap.add_argument("--reps", type=int, default=5)
     a = ap.parse_args()
@@ -125,6 +231,7 @@ def main():
                 out += np.fft.irfft(f * np.conj(f), m, axis=0)[:K + 1]
             dt = time.perf_counter() - t0
             print(json.dumps({"leg": "numpy", "size": size, "n": n, "K": K, "NF": NF, "dtype": "float64", "ms": dt * 1e3}))
+    tica_legs(a, A, dev, want)
 
 
 if __name__ == "__main__":
