@@ -782,6 +782,13 @@ static bool embed_base_on(const mdgen_ctx* c, long nrows, int t_shared, int S) {
 }
 
 static size_t frag_bytes(long nseq, int len) { return (size_t)nseq * kH * (len / 32 + 1) * kFragBytes; }
+// K tiles are stored compact and packed back to back (kFragK each: three quarters of a Q / V^T tile's allocation) ...
+static size_t k_frag_bytes(long nseq, int len) { return (size_t)nseq * kH * (len / 32 + 1) * kFragK; }
+// ... so nothing of a tile's own allocation lies behind the last K fragment any more, while k_flash loads K tiles ahead of their
+// use UNCONDITIONALLY: up to two tiles past the end of a (sequence, head), whose values it never uses but which must be mapped (and
+// are kept finite: prepare() zeroes the region).  The region therefore ends with this slack -- two tiles, rounded up to 4 KiB.
+constexpr size_t kFragSlackK = 4096;
+static_assert(kFragSlackK >= 2 * (size_t)kFragK, "k_flash reads up to two K tiles past the last fragment");
 
 // The panel prologues / epilogues (csrc/panel.h) address the residual stream as a uniform base + a 32-bit byte
 // offset token * 1536, so ONE launch may cover at most kMaxViewTokens token rows.  Larger batches are run as
@@ -836,19 +843,25 @@ extern "C" int32_t mdgen_workspace_layout(const mdgen_ctx* c, const mdgen_shape*
     const long N = B * T * L, Mp = (long)S * B * L, R = t_shared ? S : (long)S * B;
     const long maxrows = N > Mp ? N : Mp;
     size_t fq = (size_t)maxrows * 3 * kC * 2;  // SMALL layout lives in the q region
-    size_t fkv = 0;
-    auto upd = [&](size_t b) { if (b > fq) fq = b; if (b > fkv) fkv = b; };
-    upd(frag_bytes(B * L, (int)T));
+    size_t fkv = 0, fk = 0;   // V^T region (the key-validity words live in its tiles' slack, kernels.h), K region
+    auto upd = [&](long nseq, int len) {
+        const size_t b = frag_bytes(nseq, len), k = k_frag_bytes(nseq, len);
+        if (b > fq) fq = b;
+        if (b > fkv) fkv = b;
+        if (k > fk) fk = k;
+    };
+    upd(B * L, (int)T);
     if (L > 8) {
-        upd(frag_bytes(B * T, (int)L));
-        upd(frag_bytes((long)S * B, (int)L));
+        upd(B * T, (int)L);
+        upd((long)S * B, (int)L);
     }
     if (fkv == 0) fkv = 256;
+    fk += kFragSlackK;
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t a = off; off += align256(bytes); return a; };
     o->h = take((size_t)N * kC * 4);
     o->qf = take(fq);
-    o->kf = take(fkv);
+    o->kf = take(fk);
     o->vf = take(fkv);
     o->obuf = take((size_t)maxrows * kC * 2);
     o->mod = take((size_t)R * c->modrow * 4);
@@ -939,7 +952,7 @@ static Run sub_run(const Run& r, int b0, int Bs, hipStream_t stream) {
     const size_t per_b_kv = per_b_fragT > per_b_fragL ? per_b_fragT : per_b_fragL;
     const size_t per_b_q = per_b_small > per_b_kv ? per_b_small : per_b_kv;
     v.qfp = r.qfp + (size_t)b0 * per_b_q;
-    v.kfp = r.kfp + (size_t)b0 * per_b_kv;
+    v.kfp = r.kfp + (size_t)b0 * (per_b_kv / kFragBytes * kFragK);   // (K tiles are kFragK apart)
     v.vfp = r.vfp + (size_t)b0 * per_b_kv;
     v.modp = r.modp + (long)b0 * r.mod_group_stride;
     v.ipa_out_p = r.ipa_out_p + (long)b0 * r.L * kC;

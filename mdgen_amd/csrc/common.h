@@ -15,10 +15,11 @@ constexpr int kF = 1536;       // ffn dim (4C)
 constexpr int kIpaProj = 672;  // linear_q(128) | linear_kv(256) | linear_q_points(96) | linear_kv_points(192)
 constexpr int kIpaFeat = 256;  // o(128) | o_pt.x(32) | o_pt.y(32) | o_pt.z(32) | |o_pt|(32)
 // Attention operand fragments of one (seq, head, 32-position tile).  Q: k-step 0 (64 lanes x 16 B) + k-step 1 (64 x 8 B).
-// K: both k-steps 64 x 16 B -- k-step 1 carries 4 features, the constant 1.0 twice (slots 4, 5) and 2 zeros.  V^T: [k-step 2]
-// [key half 2][row d 0..24][16 B], row 24 all ones (it accumulates the softmax denominator).
-constexpr int kFragQ = 1536, kFragK = 2048, kFragV = 1600;
-constexpr int kFragBytes = 2048;  // allocation size of a fragment tile (the largest of the three)
+// K: the same compact form -- as an MFMA operand its k-step 1 is 4 features, the constant 1.0 twice (slots 4, 5) and 2 zeros, but only
+// the features are stored; k_flash keeps the constants in registers.  V^T: [k-step 2][key half 2][row d 0..24][16 B], row 24 all
+// ones (it accumulates the softmax denominator).
+constexpr int kFragQ = 1536, kFragK = 1536, kFragV = 1600;
+constexpr int kFragBytes = 2048;  // allocation size of a Q or V^T fragment tile (a K tile is allocated kFragK, see api.hip k_frag_bytes)
 constexpr int kMaxFlashTiles = 260;   // key tiles per sequence k_flash supports (len <= 8319)
 constexpr int kRopeRow = 32;   // floats per position of the rotary table: [2 halves][cos 6 | pad 2 | sin 6 | pad 2]
 constexpr int kPanel = 64;     // token rows per GEMM panel (workgroup)

@@ -7,7 +7,9 @@
 // (mha.py:399-405) are not reproduced.
 //
 // Operand fragments are produced by k_ln_qkv in exactly the register layout the MFMAs want
-// (DESIGN.md "fragment layout"), so this kernel issues only fully-coalesced 16-byte loads:
+// (DESIGN.md "fragment layout"), so this kernel issues only fully-coalesced 16-byte and 8-byte loads.  K and Q tiles are stored
+// COMPACT (1536 B: k-step 0 as 64 x 16 B, then the four real bf16 of k-step 1 as 64 x 8 B); the other half of k-step 1 is the same
+// for every tile -- K: 1.0, 1.0, 0, 0, Q: the shift slots and zeros -- and lives in registers only:
 //   S^T[key][q] = K-frag (A) x Q-frag (B)      2 x mfma_32x32x16 (d = 24 padded to 32)
 //   O^T[d][q]  += V^T-frag (A) x P^T (B)       2 x mfma_32x32x16, P^T = exp2(S^T - M) packed in place
 // A lane owns one query column (q = lane&31) and half of the tile's keys.  One wave = one head x 64 queries (two
@@ -53,8 +55,16 @@ __device__ __forceinline__ bf16x8 frag8(const unsigned char* p) {  // 4 real bf1
 // sinks each load to its first use and every tile pays a full L2 round trip.
 struct KTile {
     u32x4 k0;   // K k-step 0: 8 bf16
-    u32x4 k1;   // K k-step 1: 4 bf16, the constant 1.0 twice (slots 4, 5: they pick up -M = -(hi + lo) from Q), 2 zeros
+    u32x4 k1;   // K k-step 1: 4 bf16 (loaded), the constant 1.0 twice (slots 4, 5: they pick up -M = -(hi + lo) from Q), 2 zeros.
+                // The constant dwords are NOT in memory: a slot's k1[2], k1[3] are set once (k_consts) and the loads of later
+                // tiles define only k1[0], k1[1] of the same registers
 };
+// The constant half of a K slot's k-step 1.  Opaque, so that hipcc keeps the two dwords in the slot's registers across the
+// loop instead of rematerialising them with a v_mov pair per tile (the loop is bound by VALU issue).
+__device__ __forceinline__ void k_consts(KTile& t) {
+    t.k1 = u32x4{0u, 0u, 0x3f803f80u, 0u};
+    asm volatile("" : "+v"(t.k1));
+}
 struct VTile {
     u32x4 v0;   // V^T k-step 0
     u32x4 v1;   // V^T k-step 1
@@ -257,7 +267,8 @@ struct FlashPre {
     u32x4 kb0;       // the learned bias key's K slot (len a multiple of 32: it sits alone in the last tile, see flash_job)
     u32x2 kb1;
     f32x4 bvl[3];    // this lane half's 12 features of the learned bias value
-    KTile k0t;       // K tile 0 (the anchor)
+    u32x4 k0t0;      // K tile 0 (the anchor): k-step 0 ...
+    u32x2 k0t1;      // ... and the loaded half of k-step 1
     uint32_t vmw;    // key-validity words of tiles 0..63 (lane i = tile i)
 };
 
@@ -284,17 +295,17 @@ __device__ __forceinline__ void flash_prefetch(const FlashParams p, const int se
     // value row are requested here, with Q, so that their round trip is hidden (requested at their use they cost more than
     // the tile they save)
     const bool bias_alone = (len & 31) == 0 && len >= 32;
-    const unsigned char* kb = p.kf + (ftile + (bias_alone ? (len >> 5) : 0)) * kFragK + hh * 32 * 16;   // key slot 0 of this lane half
-    pre.kb0 = *reinterpret_cast<const u32x4*>(kb);
-    pre.kb1 = *reinterpret_cast<const u32x2*>(kb + 1024);
+    const unsigned char* kb = p.kf + (ftile + (bias_alone ? (len >> 5) : 0)) * kFragK;   // key slot 0 of this lane half = lane 32 hh
+    pre.kb0 = *reinterpret_cast<const u32x4*>(kb + hh * 32 * 16);
+    pre.kb1 = *reinterpret_cast<const u32x2*>(kb + 1024 + hh * 32 * 8);
     const f32x4* bv = reinterpret_cast<const f32x4*>(p.bias_v + head * kDH + hh * 12);
     pre.bvl[0] = bv[0];
     pre.bvl[1] = bv[1];
     pre.bvl[2] = bv[2];
     // K tile 0 is wanted first (the anchor): requested together with Q, so that its round trip overlaps the validity-word read
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(flash_uniform_ptr(p.kf + ftile * kFragK), 0, 0x7fffffff, 0x00020000);
-    pre.k0t.k0 = __builtin_amdgcn_raw_buffer_load_b128(krs, lane * 16, 0, 0);
-    pre.k0t.k1 = __builtin_amdgcn_raw_buffer_load_b128(krs, lane * 16 + 1024, 0, 0);
+    pre.k0t0 = __builtin_amdgcn_raw_buffer_load_b128(krs, lane * 16, 0, 0);
+    pre.k0t1 = __builtin_amdgcn_raw_buffer_load_b64(krs, lane * 8 + 1024, 0, 0);
     // per-tile key-validity words (key-padding mask; the bias key at position len is always valid; positions > len are
     // invalid): written by k_ln_qkv, read 64 tiles at a time into ONE register (lane i = tile i of the window) and picked out
     // with v_readlane.  No LDS, no barrier: the four waves of a workgroup never meet in the loop.
@@ -325,21 +336,26 @@ __device__ __forceinline__ void flash_job(const FlashParams p, const int seq, co
     // ---- K / V^T streams: one buffer descriptor each (wave-uniform base = this (sequence, head)'s first tile), a
     // constant per-lane byte offset, and the tile offset as the scalar offset of the load.  V^T: rows d <= 24 are
     // lanes of the fragment (row 24 = ones); the lanes of rows d > 24 point far out of range and read zeros.
-    // Loads are UNCONDITIONAL: tiles past the end of this (sequence, head) read whatever follows in the fragment
-    // buffer (finite bf16 of the next head, or the tail) and their results are never used.
+    // Loads are UNCONDITIONAL: up to two tiles past the end of this (sequence, head) read whatever follows in the fragment
+    // buffer (finite bf16 of the next head, or the zeroed slack the workspace layout keeps behind the K region: api.hip
+    // kFragSlackK) and their results are never used.
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(flash_uniform_ptr(p.kf + ftile * kFragK), 0, 0x7fffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(flash_uniform_ptr(p.vf + ftile * kFragV), 0, 0x7fffffff, 0x00020000);
-    const int koff = lane * 16;
+    const int koff = lane * 16, koff1 = lane * 8 + 1024;
     const int voff = ql <= kDH ? hh * 400 + ql * 16 : (int)0x80000000;
     auto issue_k = [&](KTile& t, int kt) __attribute__((always_inline)) {
         t.k0 = __builtin_amdgcn_raw_buffer_load_b128(krs, koff, kt * kFragK, 0);
-        t.k1 = __builtin_amdgcn_raw_buffer_load_b128(krs, koff + 1024, kt * kFragK, 0);
+        const u32x2 r = __builtin_amdgcn_raw_buffer_load_b64(krs, koff1, kt * kFragK, 0);   // k1[2], k1[3]: the slot's constants
+        t.k1[0] = r[0];
+        t.k1[1] = r[1];
     };
     auto issue_v = [&](VTile& t, int kt) __attribute__((always_inline)) {
         t.v0 = __builtin_amdgcn_raw_buffer_load_b128(vrs, voff, kt * kFragV, 0);
         t.v1 = __builtin_amdgcn_raw_buffer_load_b128(vrs, voff + 800, kt * kFragV, 0);
     };
-    const KTile k0t = pre.k0t;
+    KTile k0t;
+    k0t.k0 = pre.k0t0;
+    k0t.k1 = u32x4{pre.k0t1[0], pre.k0t1[1], 0x3f803f80u, 0u};
     const uint32_t* vmrow = p.vmask + (long)seq * p.vmask_stride;
     uint32_t vmw = pre.vmw;
 
@@ -395,6 +411,8 @@ __device__ __forceinline__ void flash_job(const FlashParams p, const int seq, co
             for (int r = 0; r < 16; ++r) h[j].o[r] = opaque_zero();
         pt[(NQ - 1) & 1].p0 = pt[(NQ - 1) & 1].p1 = u32x4{0u, 0u, 0u, 0u};   // "previous pair" of the very first block: P = 0
         if (nt > 64) vmw = vmrow[lane];          // (a re-run after a long fast loop: back to the first window)
+        k_consts(kx);
+        k_consts(ky);
         issue_k(kx, phys(0));
         issue_v(vy, phys(0));    // stands in for "V(-1)": any finite values (its P is zero)
         issue_k(ky, phys(1));

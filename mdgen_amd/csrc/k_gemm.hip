@@ -102,7 +102,14 @@ struct Attn4Stager {
     }
 };
 
-template <bool ROPE, int TT = 2, bool STAGED = false>
+template <bool X1S>
+__device__ __forceinline__ void rotate_pair(float x1, float x2, float c, float sn, float& e0, float& e1);   // (below)
+// FLASH layout: which product of a rotary pair's x2 c + x1 s sits inside the fused multiply-add (rotate_pair).  Left to the compiler
+// the choice moves with the code around it -- it did when the K stores of this epilogue changed -- so each kernel form states the one
+// its results have had so far: kRopeX2C: around x2 c everywhere; kRopeHead0X1S: around x1 s for the wave's first head, x2 c for the
+// others (the 32-position form k_ln_qkv8<true, true>).  kRopeFree: the SMALL layout's code, as it was.
+enum RopeForm { kRopeFree, kRopeX2C, kRopeHead0X1S };
+template <bool ROPE, int TT = 2, bool STAGED = false, RopeForm RF = kRopeFree>
 __device__ __forceinline__ void epilogue_heads_T(const f32x16* acc /*[3 ft][TT]*/, const PanelRows* pr, int w,
                                                  const float* bias_perm, const float* rope,
                                                  bool small, int pos0, int len, int seq, int ntile, int tile0,
@@ -162,8 +169,14 @@ __device__ __forceinline__ void epilogue_heads_T(const f32x16* acc /*[3 ft][TT]*
 #pragma unroll
                 for (int p = 0; p < 6; ++p) {
                     const float x1 = e[2 * p], x2 = e[2 * p + 1];
-                    e[2 * p] = x1 * cs[p] - x2 * sn[p];
-                    e[2 * p + 1] = x2 * cs[p] + x1 * sn[p];
+                    if (RF == kRopeFree) {
+                        e[2 * p] = x1 * cs[p] - x2 * sn[p];
+                        e[2 * p + 1] = x2 * cs[p] + x1 * sn[p];
+                    } else if (RF == kRopeHead0X1S && hd == 0) {
+                        rotate_pair<false>(x1, x2, cs[p], sn[p], e[2 * p], e[2 * p + 1]);
+                    } else {
+                        rotate_pair<true>(x1, x2, cs[p], sn[p], e[2 * p], e[2 * p + 1]);
+                    }
                 }
             }
             uint32_t u[6];
@@ -178,10 +191,12 @@ __device__ __forceinline__ void epilogue_heads_T(const f32x16* acc /*[3 ft][TT]*
                     d[2] = u32x2{u[4], u[5]};
                 }
             } else if (tile < ntile) {
-                if (which == 1) {   // K: k-step 1 is a full 16-byte slot; slots 4, 5 = 1.0: they pick up Q's -M (bf16 pair)
+                // Q and K have the same compact tile: k-step 1 holds the lane's four real bf16 only.  K's constant slots (4, 5 = 1.0:
+                // they pick up Q's -M, a bf16 pair) and both operands' zero slots are supplied in registers by the attention kernel
+                if (which == 1) {
                     unsigned char* base = frag + ((long)(seq * kH + head) * ntile + tile) * kFragK;
                     *reinterpret_cast<u32x4*>(base + lane * 16) = u32x4{u[0], u[1], u[2], u[3]};
-                    *reinterpret_cast<u32x4*>(base + 1024 + lane * 16) = u32x4{u[4], u[5], 0x3f803f80u, 0u};
+                    *reinterpret_cast<u32x2*>(base + 1024 + lane * 8) = u32x2{u[4], u[5]};
                 } else {
                     unsigned char* base = frag + ((long)(seq * kH + head) * ntile + tile) * kFragQ;
                     *reinterpret_cast<u32x4*>(base + lane * 16) = u32x4{u[0], u[1], u[2], u[3]};
@@ -247,12 +262,12 @@ __device__ __forceinline__ void write_bias_slots(const QkvParams& p, int seq, in
 #pragma unroll
         for (int hd = 0; hd < 4; ++hd) {
             const long ft = (long)(seq * kH + 4 * w + hd) * nt + kt;
-            u32x4* kd = reinterpret_cast<u32x4*>(p.kf + ft * kFragK);
+            unsigned char* kd = p.kf + ft * kFragK;
             u32x4* vd = reinterpret_cast<u32x4*>(p.vf + ft * kFragV);
             const u32x4 z = {0u, 0u, 0u, 0u}, ones = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
-            if (do_k) {
-                kd[lane] = z;
-                kd[64 + lane] = u32x4{0u, 0u, 0x3f803f80u, 0u};
+            if (do_k) {   // the compact K tile: k-step 0 (64 x 16 B), then k-step 1 (64 x 8 B)
+                *reinterpret_cast<u32x4*>(kd + lane * 16) = z;
+                *reinterpret_cast<u32x2*>(kd + 1024 + lane * 8) = u32x2{0u, 0u};
             }
             const int r0 = lane, r1 = 64 + lane;   // 16-byte rows of the V^T fragment: [k-step 2][key half 2][25]
             if (do_v) {
@@ -277,8 +292,7 @@ __device__ __forceinline__ void write_bias_slots(const QkvParams& p, int seq, in
         unsigned char* base = p.kf + ((long)(seq * kH + head) * nt + kt) * kFragK;
         *reinterpret_cast<u32x4*>(base + (hh * 32 + sl) * 16) =
             u32x4{pack_bf16(e[0], e[1]), pack_bf16(e[2], e[3]), pack_bf16(e[4], e[5]), pack_bf16(e[6], e[7])};
-        *reinterpret_cast<u32x4*>(base + 1024 + (hh * 32 + sl) * 16) =
-            u32x4{pack_bf16(e[8], e[9]), pack_bf16(e[10], e[11]), 0x3f803f80u, 0u};
+        *reinterpret_cast<u32x2*>(base + 1024 + (hh * 32 + sl) * 8) = u32x2{pack_bf16(e[8], e[9]), pack_bf16(e[10], e[11])};
     }
     if (do_v && lane < kDH) {   // V^T: row d = lane; key slot sl = register r of lane-half hk: r = (sl & 3) + 4 (sl >> 3)
         const int d = lane;
@@ -389,13 +403,13 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv(const QkvParams p) {
     // ---- Q (heads 4w..4w+3), transposed
     wave_gemm<2, 3, 24, true, 4, true>(panel, kRowB, 0, 0, p.wq + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
     QKV_STAMP(2);
-    epilogue_heads_T<true, 2, !SMALL>(acc, pr, w, sbq, srope, SMALL, pos0, len, seq, ntile, tile0, p.qf, p.qkv_small, 0);
+    epilogue_heads_T<true, 2, !SMALL, SMALL ? kRopeFree : kRopeX2C>(acc, pr, w, sbq, srope, SMALL, pos0, len, seq, ntile, tile0, p.qf, p.qkv_small, 0);
     __builtin_amdgcn_sched_barrier(0);
     QKV_STAMP(3);
     // ---- K
     wave_gemm<2, 3, 24, true, 4, true>(panel, kRowB, 0, 0, p.wk + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
     QKV_STAMP(4);
-    epilogue_heads_T<true, 2, !SMALL>(acc, pr, w, sbk, srope, SMALL, pos0, len, seq, ntile, tile0, p.kf, p.qkv_small, 1);
+    epilogue_heads_T<true, 2, !SMALL, SMALL ? kRopeFree : kRopeX2C>(acc, pr, w, sbk, srope, SMALL, pos0, len, seq, ntile, tile0, p.kf, p.qkv_small, 1);
     __builtin_amdgcn_sched_barrier(0);
     QKV_STAMP(5);
     // ---- V
@@ -550,12 +564,12 @@ __global__ __launch_bounds__(512, 1) void k_ln_qkv8(const QkvParams p) {
     const bool do_v = SPLIT ? half == 1 && g == 0 : g == 1;
     if (do_q) {
         wave_gemm<TT, 3, 24, true, 4, true>(panel, kRowB, 0, 0, p.wq + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
-        epilogue_heads_T<true, TT, true>(acc, pr, w, stage.bias[0], &stage.rope[0][0], false, pos0, len, seq, ntile, tile0, p.qf, p.qkv_small, 0);
+        epilogue_heads_T<true, TT, true, HALF ? kRopeHead0X1S : kRopeX2C>(acc, pr, w, stage.bias[0], &stage.rope[0][0], false, pos0, len, seq, ntile, tile0, p.qf, p.qkv_small, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
     if (do_k) {
         wave_gemm<TT, 3, 24, true, 4, true>(panel, kRowB, 0, 0, p.wk + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
-        epilogue_heads_T<true, TT, true>(acc, pr, w, stage.bias[1], &stage.rope[0][0], false, pos0, len, seq, ntile, tile0, p.kf, p.qkv_small, 1);
+        epilogue_heads_T<true, TT, true, HALF ? kRopeHead0X1S : kRopeX2C>(acc, pr, w, stage.bias[1], &stage.rope[0][0], false, pos0, len, seq, ntile, tile0, p.kf, p.qkv_small, 1);
         if (last) {   // the learned bias key, after this wave's own K stores
             __builtin_amdgcn_sched_barrier(0);
             write_bias_slots(p, seq, w, true, false, TT);
