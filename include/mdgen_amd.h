@@ -791,6 +791,49 @@ int32_t mdgen_traj_histograms_xy(int64_t F, int32_t NC, const float* values, int
                                  int32_t bins, const double* edges_x, const double* edges_y, int64_t* hist2, int64_t* dropped,
                                  void* stream);
 
+/* k-means and the Markov-state-model counts of a trajectory (csrc/k_msm.hip; mdgen_amd/analysis.py kmeans_fit / count_matrix): the
+ * parts of the reference's k-means -> MSM -> PCCA+ chain (mdgen/analysis.py get_kmeans / get_msm) that scale with the trajectory
+ * length.  The k x k estimators are the host's (mdgen_amd/msm.py, NumPy fp64).  The conventions above: the entries run on `stream`
+ * and synchronise nothing, read nothing back, every refusal is decided before any device call and leaves the outputs untouched
+ * (-1 null pointer, -2 bad shape, -3 workspace too small), no floating-point atomics, two calls give the same bits.
+ *
+ * x (n, d) fp32 row-major, 1 <= d <= 128;  centers fp32 [k][d], 1 <= k <= 256;  n <= 2^40.
+ * Distance: dist2(x_t, c) = sum_j (x_tj - c_j)^2 in the direct form -- the fp32 difference, then fp32 FMAs over j ascending.
+ *
+ * mdgen_traj_kmeans_assign: assign[t] = the index of the centre of smallest dist2, ties to the lowest index; dist2[t] that distance
+ *   (dist2 may be NULL).  This is also the discretisation of a trajectory by fitted centres.
+ *
+ * mdgen_traj_kmeans_step: one Lloyd iteration.  state int32 [2] = {done flag, steps taken} and cost fp64 [2] = {this step's, the
+ *   previous step's} live on the device; a call that finds the done flag set changes nothing.  Otherwise: assign as above;
+ *   cost = sum_t dist2_t, the fp32 values added in fp64; sums fp64 [k][d] = per-cluster sums of the fp32 rows, counts int64 [k];
+ *   centers[c] = fp32(sums[c] / counts[c]), an empty cluster keeps its centre; cost[1] <- cost[0] <- cost; steps + 1; the done flag
+ *   is set when steps >= 1 before the call and |cost[1] - cost[0]| <= tol * cost[0].  Sums and cost: per-workgroup partial sums
+ *   added in a fixed order.  Zero state and cost before the first step.
+ *   workspace: mdgen_traj_kmeans_step_workspace_bytes(n, d, k), 16-byte aligned.  -2 also: tol < 0 or NaN.
+ *
+ * mdgen_traj_kmeans_pp: rounds r0 .. r1 - 1 of k-means++ with the caller's uniforms u (HOST fp64 [k], each in [0, 1)).
+ *   Round 0: chosen[0] = floor(u[0] n), mind2[t] = +inf.  Round r >= 1: mind2[t] = min(mind2[t], dist2(x_t, x_chosen[r - 1]));
+ *   total = sum_t mind2[t] in fp64 (256 points in a tree, the 256-point sums in order); chosen[r] = the smallest i with
+ *   sum_{t <= i} mind2[t] > u[r] total, or floor(u[r] n) when total == 0.  chosen int64 [k] and mind2 fp32 [n] stay on the device
+ *   between rounds and calls: 0 <= r0 <= r1 <= k.  After round k - 1 the rows x[chosen] are the initial centres.
+ *   workspace: mdgen_traj_kmeans_pp_workspace_bytes(n, d, k), 16-byte aligned.
+ *
+ * mdgen_traj_count_matrix: counts[i][j] = #{t < n - lag : dtraj[t] = i, dtraj[t + lag] = j}, the sliding-window count; a pair with
+ *   either state outside [0, k) is counted in dropped[0].  counts int64 [k][k] and dropped are zeroed and filled (integer atomics,
+ *   per workgroup in LDS where k <= 110: exact and order-independent).  lag >= n gives zeros.  -2: n < 1, lag < 0, k < 1 or > 256. */
+int32_t mdgen_traj_kmeans_assign(int64_t n, int32_t d, int32_t k, const float* x, const float* centers, int32_t* assign,
+                                 float* dist2 /* or NULL */, void* stream);
+int32_t mdgen_traj_kmeans_step_workspace_bytes(int64_t n, int32_t d, int32_t k, size_t* bytes);
+int32_t mdgen_traj_kmeans_step(int64_t n, int32_t d, int32_t k, const float* x, float* centers /* in/out */, int32_t* assign,
+                               double* sums, int64_t* counts, double* cost /* [2] in/out */, int32_t* state /* [2] in/out */,
+                               double tol, void* workspace, size_t workspace_bytes, void* stream);
+int32_t mdgen_traj_kmeans_pp_workspace_bytes(int64_t n, int32_t d, int32_t k, size_t* bytes);
+int32_t mdgen_traj_kmeans_pp(int64_t n, int32_t d, int32_t k, const float* x, const double* u /* host */, int32_t r0, int32_t r1,
+                             int64_t* chosen /* [k] in/out */, float* mind2 /* [n] in/out */, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int32_t mdgen_traj_count_matrix(int64_t n, int64_t lag, int32_t k, const int32_t* dtraj, int64_t* counts, int64_t* dropped,
+                                void* stream);
+
 /* Flow-matching training target (transport.py:138-189 `training_losses`, velocity model; path.py:113-135 `plan`
  * with GVPCPlan :177-187 or the linear ICPlan): per sample b with time t[b],
  *   xt = alpha x1 + sigma x0,  ut = alpha' x1 + sigma' x0;   GVP: alpha = sin(pi t/2), sigma = cos(pi t/2);

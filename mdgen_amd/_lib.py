@@ -32,6 +32,8 @@ EXPORTS = [
     "mdgen_traj_dihedrals", "mdgen_traj_histograms", "mdgen_traj_acov", "mdgen_traj_acov_workspace_bytes",
     "mdgen_traj_lagged_moments", "mdgen_traj_lagged_moments_workspace_bytes", "mdgen_traj_project", "mdgen_traj_series_acov",
     "mdgen_traj_series_acov_workspace_bytes", "mdgen_traj_histograms_xy",
+    "mdgen_traj_kmeans_assign", "mdgen_traj_kmeans_step", "mdgen_traj_kmeans_step_workspace_bytes", "mdgen_traj_kmeans_pp",
+    "mdgen_traj_kmeans_pp_workspace_bytes", "mdgen_traj_count_matrix",
 ]
 
 
@@ -160,6 +162,12 @@ def _load():
     lib.mdgen_traj_series_acov_workspace_bytes.argtypes = [i64, i32, i64, C.POINTER(sz)]
     lib.mdgen_traj_series_acov.argtypes = [i64, i32, i64, vp, vp, vp, vp, sz, vp]   # n, NS, K | x, acov, mean | workspace, bytes
     lib.mdgen_traj_histograms_xy.argtypes = [i64, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]   # F, NC, values | P, pairs (host) | bins, edges_x, edges_y | hist2, dropped
+    lib.mdgen_traj_kmeans_assign.argtypes = [i64, i32, i32, vp, vp, vp, vp, vp]   # n, d, k | x, centers, assign, dist2 (or None)
+    lib.mdgen_traj_kmeans_step_workspace_bytes.argtypes = [i64, i32, i32, C.POINTER(sz)]
+    lib.mdgen_traj_kmeans_step.argtypes = [i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp, sz, vp]   # n, d, k | x, centers, assign | sums, counts, cost, state | tol | workspace, bytes
+    lib.mdgen_traj_kmeans_pp_workspace_bytes.argtypes = [i64, i32, i32, C.POINTER(sz)]
+    lib.mdgen_traj_kmeans_pp.argtypes = [i64, i32, i32, vp, vp, i32, i32, vp, vp, vp, sz, vp]   # n, d, k | x, u (host) | r0, r1 | chosen, mind2 | workspace, bytes
+    lib.mdgen_traj_count_matrix.argtypes = [i64, i64, i32, vp, vp, vp, vp]   # n, lag, k | dtraj, counts, dropped
     lib.mdgen_from_3_points.argtypes = [i64] + [vp] * 6
     lib.mdgen_path_plan.argtypes = [i64, i64, i32] + [vp] * 6
     lib.mdgen_masked_mse.argtypes = [i64, i64] + [vp] * 5

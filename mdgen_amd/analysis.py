@@ -8,8 +8,14 @@ tICA (`tica_fit`, `tica_transform`; csrc/k_tica.hip: `mdgen_traj_lagged_moments`
 `mdgen_traj_histograms_xy`) is a closed-form estimator and is built, opt-in (`analyze(tica=True)`): lagged second moments of the
 cos/sin torsion features and the projection on the device, the D x D symmetric eigenproblem (D <= 128) in NumPy fp64 on the host.
 
-Out of scope: the k-means, MSM and PCCA+ entries of the reference's result (`msm`, `pcca`, metastable states, ...), which pyemma's
-seeded estimators define; plots; reading or writing XTC files.
+k-means, the MSM and PCCA+ (`kmeans_fit`, `kmeans_assign`, `count_matrix`, `msm_entries`; csrc/k_msm.hip: `mdgen_traj_kmeans_assign`,
+`mdgen_traj_kmeans_step`, `mdgen_traj_kmeans_pp`, `mdgen_traj_count_matrix`) are built, opt-in (`analyze(msm=True)`): k-means++ and
+Lloyd's iteration on the MD trajectory's tICA projection and every count matrix on the device, the k x k estimators (k <= 256:
+connected set, reversible maximum likelihood, PCCA+) in NumPy fp64 on the host, mdgen_amd/msm.py.  Every rule is restated there and
+in the README; pyemma is not installed where this was written, and agreement with its seeded estimators is unverified.
+
+Out of scope: the Nelder-Mead refinement of PCCA+, pyemma object pickles (the estimators are stored as plain dicts), plots,
+`analyze_peptide_tps`; reading or writing XTC files.
 
 `torsion_features` and `tica_solve` import without torch; the functions on tensors import torch and the library when they are
 called."""
@@ -28,6 +34,15 @@ MD_NLAG = 100000               # :68
 NLAG = 1000                    # :87
 TICA_LAG = 1000                # mdgen/analysis.py get_tica: pyemma.coordinates.tica(lag=1000, kinetic_map=True)
 TICA_MAX_FEATURES = 64         # include/mdgen_amd.h mdgen_traj_lagged_moments: NF <= 64
+KMEANS_K = 100                 # mdgen/analysis.py get_kmeans: cluster_kmeans(k=100, max_iter=100, fixed_seed=137)
+KMEANS_MAX_ITER = 100
+KMEANS_TOL = 1e-5              # pyemma's default tolerance
+KMEANS_SEED = 137
+KMEANS_MAX_DIM = 128           # include/mdgen_amd.h mdgen_traj_kmeans_*: d <= 128, k <= 256
+KMEANS_MAX_K = 256
+MSM_STATES = 10                # get_msm(nstates=10)
+MD_MSM_LAG = 1000              # get_msm(lag=1000)
+MSM_LAG = 10                   # analyze_peptide_sim.py --msm_lag
 
 
 # ---- features -------------------------------------------------------------------------------------------------------
@@ -446,10 +461,11 @@ def _hist1d_range(values, column, lo, hi, bins):
     return h1[0].cpu().numpy()
 
 
-def tica_entries(a_traj, a_ref, lag=TICA_LAG, nlag=NLAG, ref_nlag=None, decorr=True) -> dict:
+def tica_entries(a_traj, a_ref, lag=TICA_LAG, nlag=NLAG, ref_nlag=None, decorr=True, projections=False) -> dict:
     """The tICA part of the reference's result (analyze_peptide_sim.py:104-150) from the two angle tensors: fit on the MD angles,
     transform both.  {"TICA-0", "TICA-0,1"} JSDs, "model" (`TicaModel.as_dict()`) and, with `decorr`, "md_tica" / "our_tica": the
-    autocovariance of component 0, fp32, neither demeaned nor normalised, as the reference stores it."""
+    autocovariance of component 0, fp32, neither demeaned nor normalised, as the reference stores it.  With `projections` also "y_ref" /
+    "y_traj", the (n, max(dim, 2)) fp32 device tensors of `tica_transform`."""
     import torch
     model = tica_fit(a_ref, lag)
     d = max(model.dim, 2)
@@ -468,11 +484,247 @@ def tica_entries(a_traj, a_ref, lag=TICA_LAG, nlag=NLAG, ref_nlag=None, decorr=T
         k = min(int(nlag), n - 1)
         out["md_tica"] = series_acov(y_ref[:, 0].contiguous(), k_ref)[0][0].cpu().numpy().astype(np.float32)
         out["our_tica"] = series_acov(y_traj[:, 0].contiguous(), k)[0][0].cpu().numpy().astype(np.float32)
+    if projections:
+        out["y_ref"], out["y_traj"] = y_ref, y_traj
+    return out
+
+
+# ---- k-means, count matrices, the MSM chain --------------------------------------------------------------------------
+# Distance: dist2(x, c) = sum_j (x_j - c_j)^2, the fp32 difference and fp32 FMAs over j ascending; the nearest centre is the one of
+# smallest dist2, ties to the lowest index.  x (n, d) fp32 with 1 <= d <= 128, centres fp32 [k, d] with 1 <= k <= 256.
+def _check_kmeans_shape(n, d, k):
+    if n < 1:
+        raise ValueError("k-means needs at least one point")
+    if not 1 <= d <= KMEANS_MAX_DIM:
+        raise ValueError(f"k-means takes 1 .. {KMEANS_MAX_DIM} dimensions, got {d}")
+    if not 1 <= k <= KMEANS_MAX_K:
+        raise ValueError(f"k-means takes 1 .. {KMEANS_MAX_K} centres, got {k}")
+
+
+def _workspace_bytes(fn, *shape) -> int:
+    import ctypes as C
+    from ._lib import check
+    b = C.c_size_t()
+    check(fn(*[int(v) for v in shape], C.byref(b)))
+    return int(b.value)
+
+
+def kmeans_step_workspace_bytes(n, d, k) -> int:
+    from ._lib import lib
+    return _workspace_bytes(lib.mdgen_traj_kmeans_step_workspace_bytes, n, d, k)
+
+
+def kmeans_pp_workspace_bytes(n, d, k) -> int:
+    from ._lib import lib
+    return _workspace_bytes(lib.mdgen_traj_kmeans_pp_workspace_bytes, n, d, k)
+
+
+def kmeans_assign_into(x, centers, assign, dist2=None) -> None:
+    """One `mdgen_traj_kmeans_assign` call: x (n, d) and centers (k, d) fp32; assign int32 [n] and, when given, dist2 fp32 [n]
+    written."""
+    import torch
+    from ._lib import launch, lib, ptr
+    n, d, k = int(x.shape[0]), int(x.shape[1]), int(centers.shape[0])
+    _check_kmeans_shape(n, d, k)
+    if centers.ndim != 2 or int(centers.shape[1]) != d or assign.numel() < n or (dist2 is not None and dist2.numel() < n):
+        raise ValueError("centers must be [k, d]; assign and dist2 need n elements")
+    launch(lib.mdgen_traj_kmeans_assign, x, n, d, k, ptr(x, torch.float32), ptr(centers, torch.float32), ptr(assign, torch.int32),
+           ptr(dist2, torch.float32))
+
+
+def kmeans_assign(x, centers, dist2=False):
+    """The index of every point's nearest centre, an int32 device tensor [n] -- the discretisation of a trajectory, what
+    `kmeans.transform` gives the reference; with `dist2` also the fp32 squared distances."""
+    import torch
+    x = _device_f32(x)
+    centers = _device_f32(centers, x.device)
+    assign = torch.empty(int(x.shape[0]), dtype=torch.int32, device=x.device)
+    d2 = torch.empty(int(x.shape[0]), dtype=torch.float32, device=x.device) if dist2 else None
+    kmeans_assign_into(x, centers, assign, d2)
+    return (assign, d2) if dist2 else assign
+
+
+def kmeans_step_into(x, centers, assign, sums, counts, cost, state, tol, workspace) -> None:
+    """One `mdgen_traj_kmeans_step` call, a Lloyd iteration (include/mdgen_amd.h): centers (k, d) fp32 updated in place; assign
+    int32 [n], sums fp64 [k, d], counts int64 [k] written; cost fp64 [2] and state int32 [2] (done flag, steps taken) carried from
+    step to step on the device -- zero both before the first.  A step that finds the flag set changes nothing."""
+    import torch
+    from ._lib import launch, lib, ptr
+    n, d, k = int(x.shape[0]), int(x.shape[1]), int(centers.shape[0])
+    _check_kmeans_shape(n, d, k)
+    if centers.ndim != 2 or int(centers.shape[1]) != d or assign.numel() < n or sums.numel() < k * d or counts.numel() < k:
+        raise ValueError("centers must be [k, d]; assign needs n elements, sums k * d, counts k")
+    if cost.numel() < 2 or state.numel() < 2:
+        raise ValueError("cost and state need 2 elements")
+    launch(lib.mdgen_traj_kmeans_step, x, n, d, k, ptr(x, torch.float32), ptr(centers, torch.float32), ptr(assign, torch.int32),
+           ptr(sums, torch.float64), ptr(counts, torch.int64), ptr(cost, torch.float64), ptr(state, torch.int32), float(tol),
+           ptr(workspace, torch.uint8), int(workspace.numel()))
+
+
+def kmeans_pp_into(x, k, u, r0, r1, chosen, mind2, workspace) -> None:
+    """One `mdgen_traj_kmeans_pp` call: rounds r0 .. r1 - 1 of k-means++ on x (n, d) with the host uniforms u fp64 [k];
+    chosen int64 [k] and mind2 fp32 [n] live on the device between rounds."""
+    import torch
+    from ._lib import launch, lib, ptr
+    n, d, k = int(x.shape[0]), int(x.shape[1]), int(k)
+    _check_kmeans_shape(n, d, k)
+    u = np.ascontiguousarray(u, np.float64).ravel()
+    if u.shape[0] < k or chosen.numel() < k or mind2.numel() < n:
+        raise ValueError("u and chosen need k elements, mind2 n")
+    launch(lib.mdgen_traj_kmeans_pp, x, n, d, k, ptr(x, torch.float32), u.ctypes.data, int(r0), int(r1), ptr(chosen, torch.int64),
+           ptr(mind2, torch.float32), ptr(workspace, torch.uint8), int(workspace.numel()))
+
+
+def kmeans_pp(x, k, u):
+    """k-means++ seeding in one call: the int64 device tensor [k] of chosen point indices.  Round 0 takes floor(u[0] n); round r
+    takes the smallest i with sum_{t <= i} mind2[t] > u[r] sum_t mind2[t], mind2 the squared distance to the nearest point chosen
+    so far (floor(u[r] n) when that sum is zero)."""
+    import torch
+    x = _device_f32(x)
+    n, d = int(x.shape[0]), int(x.shape[1])
+    _check_kmeans_shape(n, d, int(k))
+    chosen = torch.zeros(int(k), dtype=torch.int64, device=x.device)
+    mind2 = torch.empty(n, dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(kmeans_pp_workspace_bytes(n, d, k), 16), dtype=torch.uint8, device=x.device)
+    kmeans_pp_into(x, k, u, 0, int(k), chosen, mind2, ws)
+    return chosen
+
+
+def kmeans_fit(x, k=KMEANS_K, max_iter=KMEANS_MAX_ITER, tol=KMEANS_TOL, seed=KMEANS_SEED) -> dict:
+    """k-means of x (n, d), a CUDA tensor, as the reference asks for it (`cluster_kmeans(k=100, max_iter=100, fixed_seed=137)`),
+    restated: u = np.random.default_rng(seed).random(k) drives k-means++ (`kmeans_pp`), the rows x[chosen] are the initial
+    centres, then at most `max_iter` Lloyd steps (`kmeans_step_into`), stopping after the step whose cost differs from the previous
+    step's by at most tol * cost.  All steps are launched back to back -- the done flag lives on the device -- and read back once.
+
+    {"centers" fp32 [k, d], "dim" d, "steps", "cost" (of the last step, measured before its update), "cost_history" fp64 [steps],
+    "seed", "chosen" int64 [k]}.  ValueError when k > n."""
+    import torch
+    x = _device_f32(x)
+    n, d, k = int(x.shape[0]), int(x.shape[1]), int(k)
+    _check_kmeans_shape(n, d, k)
+    if k > n:
+        raise ValueError(f"k-means with {k} centres needs at least as many points, got {n}")
+    dev = x.device
+    u = np.random.default_rng(int(seed)).random(k)
+    chosen = kmeans_pp(x, k, u)
+    centers = x.index_select(0, chosen).contiguous()
+    assign = torch.empty(n, dtype=torch.int32, device=dev)
+    sums = torch.empty(k, d, dtype=torch.float64, device=dev)
+    counts = torch.empty(k, dtype=torch.int64, device=dev)
+    cost = torch.zeros(2, dtype=torch.float64, device=dev)
+    state = torch.zeros(2, dtype=torch.int32, device=dev)
+    history = torch.zeros(max(int(max_iter), 1), dtype=torch.float64, device=dev)
+    ws = torch.empty(max(kmeans_step_workspace_bytes(n, d, k), 16), dtype=torch.uint8, device=dev)
+    for i in range(int(max_iter)):
+        kmeans_step_into(x, centers, assign, sums, counts, cost, state, tol, ws)
+        history[i:i + 1].copy_(cost[:1])
+    steps = int(state.cpu()[1])
+    history = history.cpu().numpy()[:steps].copy()
+    return {"centers": centers.cpu().numpy(), "dim": d, "steps": steps, "cost": float(history[-1]) if steps else 0.0,
+            "cost_history": history, "seed": int(seed), "chosen": chosen.cpu().numpy()}
+
+
+def count_matrix_into(dtraj, lag, k, counts, dropped) -> None:
+    """One `mdgen_traj_count_matrix` call: dtraj int32 [n]; counts int64 [k, k] and dropped int64 [1] are zeroed and filled."""
+    import torch
+    from ._lib import launch, lib, ptr
+    if not 1 <= int(k) <= KMEANS_MAX_K:
+        raise ValueError(f"a count matrix takes 1 .. {KMEANS_MAX_K} states, got {k}")
+    if int(lag) < 0:
+        raise ValueError(f"lag must be >= 0, got {lag}")
+    if counts.numel() < int(k) * int(k) or dropped.numel() < 1:
+        raise ValueError("counts needs k * k elements, dropped 1")
+    launch(lib.mdgen_traj_count_matrix, dtraj, int(dtraj.numel()), int(lag), int(k), ptr(dtraj, torch.int32), ptr(counts, torch.int64),
+           ptr(dropped, torch.int64))
+
+
+def count_matrix(dtraj, lag, k):
+    """(counts int64 [k, k], dropped) as a NumPy array and an int: counts[i, j] = #{t < n - lag: dtraj[t] = i, dtraj[t + lag] = j},
+    the sliding-window count of pyemma's default; a pair with a state outside 0 .. k - 1 is counted in `dropped`.  dtraj: an int32
+    CUDA tensor [n]."""
+    import torch
+    dev = dtraj.device
+    counts = torch.empty(int(k), int(k), dtype=torch.int64, device=dev)
+    dropped = torch.empty(1, dtype=torch.int64, device=dev)
+    count_matrix_into(dtraj.contiguous(), lag, k, counts, dropped)
+    return counts.cpu().numpy(), int(dropped.cpu()[0])
+
+
+def _filled(active_set, values, nstates, base):
+    """The reference's `np.eye(nstates)` / `np.zeros(nstates)` filled through an estimator's active set
+    (analyze_peptide_sim.py:169-179)."""
+    out = np.array(base, np.float64)
+    active_set = np.asarray(active_set)
+    if out.ndim == 2:
+        out[np.ix_(active_set, active_set)] = values
+    else:
+        out[active_set] = values
+    return out
+
+
+def msm_entries(y_traj, y_ref, k=KMEANS_K, nstates=MSM_STATES, md_lag=MD_MSM_LAG, traj_lag=MSM_LAG, traj_msm=True, seed=KMEANS_SEED,
+                name=None) -> dict:
+    """The k-means / MSM / PCCA+ part of the reference's result (analyze_peptide_sim.py:153-197; mdgen/analysis.py get_kmeans,
+    get_msm, discretize) from the tICA projections y_ref (MD) and y_traj (sampled), (n, d) fp32 CUDA tensors:
+
+      1. `kmeans_fit(y_ref, k, seed=seed)`;  2. both trajectories discretised (`kmeans_assign`);
+      3. the MD dtraj's count matrix at `md_lag` (device);  4. `msm.estimate_msm` -- ValueError unless all k microstates are in
+      its active set, as the reference asserts;  5. `msm.pcca(nstates)`;
+      6. the coarse MSM from the lumped count matrix M' C M (M the k x nstates indicator of the assignments: exactly the count
+         matrix of the lumped dtraj);  7. both dtrajs lumped, their occupancies from lag-0 counts (device);
+      8. with `traj_msm`: the lumped sampled dtraj counted at `traj_lag` (device) and `msm.estimate_msm`.  When that alone fails
+         (no transition counts), its three entries are left out and `name` is written to stderr.
+
+    Keys, in order: kmeans, msm, pcca, cmsm, traj_metastable_probs, ref_metastable_probs, msm_transition_matrix, pcca_pi, msm_pi,
+    and traj_msm, traj_transition_matrix, traj_pi.  Estimators are plain dicts of NumPy arrays and ints."""
+    import sys
+    import torch
+    from . import msm as M
+    k, nstates = int(k), int(nstates)
+    if not 1 <= nstates <= k:
+        raise ValueError(f"{nstates} metastable states of {k} microstates")
+    y_ref = _device_f32(y_ref)
+    y_traj = _device_f32(y_traj, y_ref.device)
+    km = kmeans_fit(y_ref, k, seed=seed)
+    centers = torch.from_numpy(km["centers"]).to(y_ref.device)
+    d_ref, d_traj = kmeans_assign(y_ref, centers), kmeans_assign(y_traj, centers)
+    C, _ = count_matrix(d_ref, md_lag, k)
+    if C.sum() == 0:
+        raise ValueError(f"no transition counts: the MD trajectory has {int(y_ref.shape[0])} frames, the MSM lag is {int(md_lag)}")
+    model = M.estimate_msm(C, md_lag)
+    if len(model["active_set"]) != k:
+        raise ValueError(f"only {len(model['active_set'])} of {k} microstates are in the MSM's connected set at lag {int(md_lag)}")
+    pc = M.pcca(model["transition_matrix"], model["pi"], nstates)
+    meta = pc["metastable_assignments"]
+    lump = np.zeros((k, nstates), np.int64)
+    lump[np.arange(k), meta] = 1
+    cmsm = M.estimate_msm(lump.T @ C @ lump, md_lag)
+    meta_dev = torch.from_numpy(meta.astype(np.int32)).to(y_ref.device)
+    l_ref, l_traj = meta_dev[d_ref.long()].contiguous(), meta_dev[d_traj.long()].contiguous()
+    out = {"kmeans": {key: km[key] for key in ("centers", "dim", "steps", "cost", "seed")}, "msm": model, "pcca": pc, "cmsm": cmsm}
+    out["traj_metastable_probs"] = np.diag(count_matrix(l_traj, 0, nstates)[0]) / float(l_traj.numel())
+    out["ref_metastable_probs"] = np.diag(count_matrix(l_ref, 0, nstates)[0]) / float(l_ref.numel())
+    out["msm_transition_matrix"] = _filled(cmsm["active_set"], cmsm["transition_matrix"], nstates, np.eye(nstates))
+    out["pcca_pi"] = pc["pi_coarse"]
+    out["msm_pi"] = _filled(cmsm["active_set"], cmsm["pi"], nstates, np.zeros(nstates))
+    if traj_msm:
+        try:
+            Ct, _ = count_matrix(l_traj, traj_lag, nstates)
+            if Ct.sum() == 0:
+                raise ValueError(f"no transition counts: {int(l_traj.numel())} sampled frames, lag {int(traj_lag)}")
+            tm = M.estimate_msm(Ct, traj_lag)
+        except ValueError as e:
+            print(f"{name if name is not None else 'sampled trajectory'}: no traj_msm entries: {e}", file=sys.stderr)
+        else:
+            out["traj_msm"] = tm
+            out["traj_transition_matrix"] = _filled(tm["active_set"], tm["transition_matrix"], nstates, np.eye(nstates))
+            out["traj_pi"] = _filled(tm["active_set"], tm["pi"], nstates, np.zeros(nstates))
     return out
 
 
 def analyze(traj_atom14, ref_atom14, aatype, nlag=NLAG, ref_nlag=None, pairs=DEFAULT_PAIRS, decorr=True, tica=False,
-            tica_lag=TICA_LAG) -> dict:
+            tica_lag=TICA_LAG, msm=False, msm_k=KMEANS_K, msm_states=MSM_STATES, md_msm_lag=MD_MSM_LAG, msm_lag=MSM_LAG,
+            traj_msm=True, kmeans_seed=KMEANS_SEED, name=None) -> dict:
     """The reference's per-peptide result for a sampled trajectory `traj_atom14` (F, L, 14, 3) against the MD trajectory
     `ref_atom14` (F_ref, L, 14, 3) -- a CUDA tensor, or an array that is copied to traj_atom14's device:
 
@@ -489,13 +741,22 @@ def analyze(traj_atom14, ref_atom14, aatype, nlag=NLAG, ref_nlag=None, pairs=DEF
 
       "tica_model"         `TicaModel.as_dict()`: lag, mean, eigenvalues, W, dim, rank
 
-    ValueError when the MD trajectory has fewer than tica_lag + 2 frames, no torsions or more than 64, or a covariance of rank < 2.
-    Plain Python and NumPy objects only.  The reference's k-means / MSM / PCCA+ entries are not computed."""
+    With `msm` (which implies `tica`; `msm_entries` on the projections at the model's `dim`, k-means with `msm_k` centres and
+    `kmeans_seed`, PCCA+ into `msm_states` sets, the MD MSM at lag `md_msm_lag`, the sampled trajectory's at `msm_lag`), after these
+    and in this order: "kmeans" {centers, dim, steps, cost, seed}, "msm", "pcca", "cmsm", "traj_metastable_probs",
+    "ref_metastable_probs", "msm_transition_matrix", "pcca_pi", "msm_pi" and, unless `traj_msm` is False, "traj_msm",
+    "traj_transition_matrix", "traj_pi" (left out, with `name` on stderr, when only the sampled trajectory's MSM cannot be
+    estimated).  The estimators are the plain dicts of mdgen_amd/msm.py.
+
+    ValueError when the MD trajectory has fewer than tica_lag + 2 frames, no torsions or more than 64, or a covariance of rank < 2;
+    with `msm` also when it has fewer frames than centres, no pair of frames md_msm_lag apart, or a microstate outside the MSM's
+    connected set.  Plain Python and NumPy objects only."""
     aat = _checked_aatype(aatype.cpu().numpy() if hasattr(aatype, "cpu") else aatype)
     traj = _device_f32(traj_atom14)
     ref = _device_f32(ref_atom14, traj.device)
     labels, _ = torsion_features(aat)
     NF = len(labels)
+    tica = bool(tica or msm)
     if tica:   # (what tica_fit would refuse, before any launch)
         if int(tica_lag) < 0 or int(ref.shape[0]) - int(tica_lag) < 2:
             raise ValueError(f"tICA at lag {int(tica_lag)} needs at least lag + 2 frames, got {int(ref.shape[0])}")
@@ -519,9 +780,13 @@ def analyze(traj_atom14, ref_atom14, aatype, nlag=NLAG, ref_nlag=None, pairs=DEF
         out["our_decorrelation"] = {lab: our[i] for i, lab in enumerate(labels)}
         out["md_decorrelation"] = {lab: md[i] for i, lab in enumerate(labels)}
     if tica:
-        t = tica_entries(a_traj, a_ref, tica_lag, nlag, ref_nlag, decorr)
+        t = tica_entries(a_traj, a_ref, tica_lag, nlag, ref_nlag, decorr, projections=bool(msm))
         out["JSD"]["TICA-0"], out["JSD"]["TICA-0,1"] = t["TICA-0"], t["TICA-0,1"]
         if decorr:
             out["our_decorrelation"]["tica"], out["md_decorrelation"]["tica"] = t["our_tica"], t["md_tica"]
         out["tica_model"] = t["model"]
+        if msm:
+            dim = t["model"]["dim"]      # (the reference's tica.transform has the model's dim columns)
+            out.update(msm_entries(t["y_traj"][:, :dim].contiguous(), t["y_ref"][:, :dim].contiguous(), msm_k, msm_states,
+                                   md_msm_lag, msm_lag, traj_msm, kmeans_seed, name))
     return out

@@ -10,12 +10,19 @@
   --tica [--tica_lag N]   also the tICA entries (`analyze(tica=True)`: JSD "TICA-0" / "TICA-0,1", the "tica" decorrelation
                      curves, "tica_model"), fitted on the MD trajectory at lag N (default 1000).  A peptide whose MD trajectory
                      is too short for the lag (or whose covariance has rank < 2) is named on stderr and gets the other entries;
-  --no_msm           REQUIRED: the k-means / MSM / PCCA+ part of the reference's result is defined by pyemma's estimators and is
-                     not computed here.  Without the flag the command is refused before anything is read (exit status 2), so that
-                     a pipeline that needs those entries does not find out afterwards;  --no_traj_msm is accepted.
+  --msm              also the k-means / MSM / PCCA+ entries (`analyze(msm=True)`, which implies --tica): "kmeans", "msm", "pcca",
+                     "cmsm", the metastable-state occupancies, the coarse transition matrix and stationary distributions, by this
+                     project's restatement of the estimators (mdgen_amd/msm.py; agreement with pyemma is unverified).
+                     --msm_k N (100) microstates, --msm_states N (10) metastable states, --md_msm_lag N (1000) the MD MSM's lag,
+                     --msm_lag N (10) the sampled trajectory's, --kmeans_seed N (137);  --no_traj_msm skips the sampled
+                     trajectory's own MSM.  A peptide whose MSM is refused (a microstate outside the connected set, too few
+                     frames) is named on stderr and gets the other entries;
+  --no_msm           without the MSM entries.  One of --msm and --no_msm is REQUIRED (they exclude each other): with neither the
+                     command is refused before anything is read (exit status 2), so that a pipeline that expects the reference's
+                     pyemma objects does not find out afterwards.
 
 Per peptide the result is `mdgen_amd.analysis.analyze`'s dict: "features", "JSD", "our_decorrelation", "md_decorrelation"
-(and "tica_model" with --tica).
+(and "tica_model" with --tica, the MSM entries with --msm).
 No plots (--plot does not exist), no XTC files."""
 from __future__ import annotations
 
@@ -39,8 +46,15 @@ def build_parser():
     p.add_argument("--no_decorr", action="store_true")
     p.add_argument("--save", action="store_true")
     p.add_argument("--save_name", type=str, default="out.pkl")
-    p.add_argument("--no_msm", action="store_true")
+    which = p.add_mutually_exclusive_group()
+    which.add_argument("--no_msm", action="store_true")
+    which.add_argument("--msm", action="store_true")
     p.add_argument("--no_traj_msm", action="store_true")
+    p.add_argument("--msm_k", type=int, default=100)
+    p.add_argument("--msm_states", type=int, default=10)
+    p.add_argument("--md_msm_lag", type=int, default=1000)
+    p.add_argument("--msm_lag", type=int, default=10)
+    p.add_argument("--kmeans_seed", type=int, default=137)
     p.add_argument("--tica", action="store_true")
     p.add_argument("--tica_lag", type=int, default=1000)
     return p
@@ -48,7 +62,7 @@ def build_parser():
 
 def require_no_msm(args):
     """The policy of `sim_inference.require_xtc_writer`: what cannot be delivered is refused before any work is done."""
-    if not args.no_msm:
+    if not args.no_msm and not args.msm:
         print("error: the tICA / MSM analysis needs pyemma (the reference's dependency for its estimators), which this project "
               "does not use; run with --no_msm for the torsion JSDs and the decorrelation curves", file=sys.stderr)
         raise SystemExit(2)
@@ -72,10 +86,22 @@ def load_trajectory(path, aatype):
     return np.load(path, mmap_mode="r") if path.endswith(".npy") else pdb_to_atom14(path, aatype)
 
 
-def analyze_one(name, traj, ref, aatype, tica=False, tica_lag=1000, **kw):
+def msm_options(args) -> dict:
+    """`analyze`'s MSM keywords from the parsed options."""
+    return dict(msm=True, msm_k=args.msm_k, msm_states=args.msm_states, md_msm_lag=args.md_msm_lag, msm_lag=args.msm_lag,
+                traj_msm=not args.no_traj_msm, kmeans_seed=args.kmeans_seed)
+
+
+def analyze_one(name, traj, ref, aatype, tica=False, tica_lag=1000, msm=None, **kw):
     """`analyze`; a peptide whose tICA is refused (MD trajectory too short for the lag, rank < 2, no torsions) is named on stderr
-    and analysed without the tICA entries."""
+    and analysed without the tICA entries.  `msm`: `msm_options`' dict or None; a peptide whose MSM is refused is named on stderr
+    and analysed without the MSM entries."""
     from .analysis import analyze
+    if msm:
+        try:
+            return analyze(traj, ref, aatype, tica=True, tica_lag=tica_lag, name=name, **msm, **kw)
+        except ValueError as e:
+            print(f"{name}: no MSM entries: {e}", file=sys.stderr)
     if tica:
         try:
             return analyze(traj, ref, aatype, tica=True, tica_lag=tica_lag, **kw)
@@ -112,8 +138,8 @@ def main(argv=None):
         if args.truncate:
             traj = traj[:args.truncate]
         traj = torch.from_numpy(np.array(traj, np.float32)).to(device)   # (a copy: the memory map is read-only)
-        out[n] = analyze_one(n, traj, np.load(refs[n], mmap_mode="r"), aat, decorr=not args.no_decorr, tica=args.tica,
-                             tica_lag=args.tica_lag)
+        out[n] = analyze_one(n, traj, np.load(refs[n], mmap_mode="r"), aat, decorr=not args.no_decorr, tica=args.tica or args.msm,
+                             tica_lag=args.tica_lag, msm=msm_options(args) if args.msm else None)
         jsd = out[n]["JSD"]
         print(f"{n}: {len(out[n]['features'])} torsions, mean JSD {np.mean(list(jsd.values())) if jsd else float('nan'):.4f}")
     if args.save:

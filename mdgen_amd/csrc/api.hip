@@ -2508,6 +2508,81 @@ extern "C" int32_t mdgen_traj_histograms_xy(int64_t F, int32_t NC, const float* 
     return 0;
 }
 
+// k-means / MSM (k_msm.hip): the same conventions
+static int traj_kmeans_shape(int64_t n, int32_t d, int32_t k) {
+    if (n < 1 || n > kTrajMaxFrames) return fail(-2, "n must be in 1 .. 2^40");
+    if (d < 1 || d > kKmMaxDim) return fail(-2, "d must be in 1 .. %d", kKmMaxDim);
+    if (k < 1 || k > kKmMaxCenters) return fail(-2, "k must be in 1 .. %d", kKmMaxCenters);
+    return 0;
+}
+
+extern "C" int32_t mdgen_traj_kmeans_assign(int64_t n, int32_t d, int32_t k, const float* x, const float* centers, int32_t* assign,
+                                            float* dist2, void* stream) {
+    if (int rc = traj_kmeans_shape(n, d, k)) return rc;
+    NONNULL(x, centers, assign);
+    launch_kmeans_assign(n, d, k, x, centers, assign, dist2, (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
+
+extern "C" int32_t mdgen_traj_kmeans_step_workspace_bytes(int64_t n, int32_t d, int32_t k, size_t* bytes) {
+    NONNULL(bytes);
+    if (int rc = traj_kmeans_shape(n, d, k)) return rc;
+    *bytes = kmeans_step_workspace_bytes(n, d, k);
+    return 0;
+}
+
+extern "C" int32_t mdgen_traj_kmeans_step(int64_t n, int32_t d, int32_t k, const float* x, float* centers, int32_t* assign,
+                                          double* sums, int64_t* counts, double* cost, int32_t* state, double tol, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    if (int rc = traj_kmeans_shape(n, d, k)) return rc;
+    if (!(tol >= 0.0)) return fail(-2, "tol must be >= 0");
+    NONNULL(x, centers, assign, sums, counts, cost, state, workspace);
+    const size_t need = kmeans_step_workspace_bytes(n, d, k);
+    if (workspace_bytes < need) return fail(-3, "workspace too small: %zu < %zu", workspace_bytes, need);
+    if ((uintptr_t)workspace % 16) return fail(-2, "workspace must be 16-byte aligned");
+    launch_kmeans_step(n, d, k, x, centers, assign, sums, counts, cost, state, tol, workspace, (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
+
+extern "C" int32_t mdgen_traj_kmeans_pp_workspace_bytes(int64_t n, int32_t d, int32_t k, size_t* bytes) {
+    NONNULL(bytes);
+    if (int rc = traj_kmeans_shape(n, d, k)) return rc;
+    *bytes = kmeans_pp_workspace_bytes(n);
+    return 0;
+}
+
+extern "C" int32_t mdgen_traj_kmeans_pp(int64_t n, int32_t d, int32_t k, const float* x, const double* u, int32_t r0, int32_t r1,
+                                        int64_t* chosen, float* mind2, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = traj_kmeans_shape(n, d, k)) return rc;
+    if (r0 < 0 || r0 > r1 || r1 > k) return fail(-2, "rounds must satisfy 0 <= r0 <= r1 <= k (r0 = %d, r1 = %d, k = %d)", r0, r1, k);
+    NONNULL(x, u, chosen, mind2, workspace);
+    for (int32_t r = r0; r < r1; ++r)
+        if (!(u[r] >= 0.0 && u[r] < 1.0)) return fail(-2, "u[%d] = %g is outside [0, 1)", r, u[r]);
+    const size_t need = kmeans_pp_workspace_bytes(n);
+    if (workspace_bytes < need) return fail(-3, "workspace too small: %zu < %zu", workspace_bytes, need);
+    if ((uintptr_t)workspace % 16) return fail(-2, "workspace must be 16-byte aligned");
+    launch_kmeans_pp(n, d, x, u, r0, r1, chosen, mind2, workspace, (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
+
+extern "C" int32_t mdgen_traj_count_matrix(int64_t n, int64_t lag, int32_t k, const int32_t* dtraj, int64_t* counts,
+                                           int64_t* dropped, void* stream) {
+    if (n < 1 || n > kTrajMaxFrames) return fail(-2, "n must be in 1 .. 2^40");
+    if (lag < 0) return fail(-2, "lag must be >= 0 (lag = %lld)", (long long)lag);
+    if (k < 1 || k > kKmMaxCenters) return fail(-2, "k must be in 1 .. %d", kKmMaxCenters);
+    NONNULL(dtraj, counts, dropped);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(counts, 0, (size_t)k * k * sizeof(int64_t), s));
+    HIPCHK(hipMemsetAsync(dropped, 0, sizeof(int64_t), s));
+    if (lag >= n) return 0;   // no pair: all zeros
+    launch_count_matrix(n, lag, k, dtraj, counts, dropped, s);
+    LAUNCHCHK();
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // flow-matching training target and loss (forward only)
 // ---------------------------------------------------------------------------------------------

@@ -656,4 +656,18 @@ void launch_series_acov(long n, int NS, long K, const float* x, double* acov, do
 void launch_hist_xy(long F, int NC, const float* values, int P, const int32_t* pairs_host, int bins, const double* edges_x,
                     const double* edges_y, int64_t* hist2, int64_t* dropped, hipStream_t s);
 
+// k-means / MSM (k_msm.hip): the nearest centre of every point, one Lloyd step, k-means++ rounds and the sliding-window count matrix
+constexpr int kKmMaxDim = 128;       // d: tICA components
+constexpr int kKmMaxCenters = 256;   // k
+size_t kmeans_step_workspace_bytes(long n, int d, int k);
+size_t kmeans_pp_workspace_bytes(long n);
+void launch_kmeans_assign(long n, int d, int k, const float* x, const float* centers, int32_t* assign, float* dist2, hipStream_t s);
+void launch_kmeans_step(long n, int d, int k, const float* x, float* centers, int32_t* assign, double* sums, int64_t* counts,
+                        double* cost, int32_t* state, double tol, void* ws, hipStream_t s);
+// rounds r0 .. r1 - 1; u_host [k] in [0, 1)
+void launch_kmeans_pp(long n, int d, const float* x, const double* u_host, int r0, int r1, int64_t* chosen, float* mind2, void* ws,
+                      hipStream_t s);
+// counts [k][k] and dropped [1] must be zero on entry; lag < n
+void launch_count_matrix(long n, long lag, int k, const int32_t* dtraj, int64_t* counts, int64_t* dropped, hipStream_t s);
+
 }  // namespace mdg

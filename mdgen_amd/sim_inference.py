@@ -21,7 +21,9 @@
                      conditioning array (the MD trajectory `{data_dir}/{name}{suffix}.npy`): torsion JSDs and decorrelation curves,
                      `{out_dir}/analysis.pkl` = {name: result} at the end.  Its time is outside the reported frames/s and printed
                      on its own line.  --tica [--tica_lag N]  adds `analyze(tica=True)`'s entries; a peptide whose MD trajectory is
-                     too short for the lag is named on stderr and keeps its torsion entries.
+                     too short for the lag is named on stderr and keeps its torsion entries.  --msm  adds `analyze(msm=True)`'s
+                     k-means / MSM / PCCA+ entries (and the tICA ones) with `analyze_peptide_sim`'s --msm_k, --msm_states,
+                     --md_msm_lag, --msm_lag, --kmeans_seed, --no_traj_msm; a peptide whose MSM is refused is named likewise.
 
 The rollout (sim_inference.py:61-98) stays on the device: each block's last frame becomes the next block's
 conditioning frame through `mdgen_atom14_to_cond` (no D->H->D round trip).  Output, as the reference
@@ -204,11 +206,12 @@ def run(args, model, device, names_seqres, rank=0, world=1, batch_fn=make_group_
             if args.npy:
                 np.save(os.path.join(args.out_dir, f"{n}.npy"), host[i])
             if getattr(args, "analyze", False):
-                from .analyze_peptide_sim import analyze_one
+                from .analyze_peptide_sim import analyze_one, msm_options
                 sync()
                 start = time.time()
-                analysis[n] = analyze_one(n, all_atom14[i], arrs[n], aat, tica=getattr(args, "tica", False),
-                                          tica_lag=getattr(args, "tica_lag", 1000))
+                with_msm = getattr(args, "msm", False)
+                analysis[n] = analyze_one(n, all_atom14[i], arrs[n], aat, tica=getattr(args, "tica", False) or with_msm,
+                                          tica_lag=getattr(args, "tica_lag", 1000), msm=msm_options(args) if with_msm else None)
                 sync()
                 analysis_s += time.time() - start
     job_s = max_over_ranks(total_s, dist)
@@ -256,6 +259,15 @@ def build_parser():
                    help="with --analyze: also the tICA entries (TICA-0 / TICA-0,1 JSDs, 'tica' curves, tica_model); a peptide whose "
                         "MD trajectory is too short for the lag is named on stderr and keeps its torsion entries")
     p.add_argument("--tica_lag", type=int, default=1000, help="the tICA lag in frames of the MD trajectory (reference: 1000)")
+    p.add_argument("--msm", action="store_true",
+                   help="with --analyze: also the k-means / MSM / PCCA+ entries (implies --tica); a peptide whose MSM is refused is "
+                        "named on stderr and keeps its other entries")
+    p.add_argument("--msm_k", type=int, default=100, help="k-means microstates (reference: 100)")
+    p.add_argument("--msm_states", type=int, default=10, help="PCCA+ metastable states (reference: 10)")
+    p.add_argument("--md_msm_lag", type=int, default=1000, help="the MD trajectory's MSM lag in frames (reference: 1000)")
+    p.add_argument("--msm_lag", type=int, default=10, help="the sampled trajectory's MSM lag in frames (reference: 10)")
+    p.add_argument("--kmeans_seed", type=int, default=137, help="seed of the k-means++ uniforms (reference: fixed_seed=137)")
+    p.add_argument("--no_traj_msm", action="store_true", help="skip the sampled trajectory's own MSM")
     return p
 
 

@@ -9,12 +9,19 @@
   project       `mdgen_traj_project`: n = 1e6, NF 25, d = 2 and d = 10
   series        `mdgen_traj_series_acov`: one series at the sampler's size (n 1e5, K 1000) and at the MD size (n 1e6, K 1e5)
   tica          `analyze(tica=True)` of one tetrapeptide, 1e5 sampled frames against 1e6 MD frames, beside `analyze()` without it
+  kmeans_pp     `mdgen_traj_kmeans_pp`: all 100 rounds on n = 1e6 points of d = 10 components (the MD trajectory's tICA projection)
+  kmeans_step   `mdgen_traj_kmeans_step`: one Lloyd iteration at the same size, k = 100; beside it `numpy_step_ms_1e5`, the same step in
+                NumPy fp64 on the host at 1e5 points
+  kmeans_fit    `kmeans_fit`: k-means++ and 100 step launches with the one read-back, wall time
+  count_matrix  `mdgen_traj_count_matrix`: the 1e6-frame dtraj at lag 1000, k = 100 (LDS counters) and k = 256 (global ones)
+  msm           `analyze(msm=True)` beside `analyze(tica=True)`, the same trajectories as `tica`; `host_ms`: the estimators alone
 
 Beside each of the last four, `numpy_ms`: the same definition in NumPy fp64 on the host, the copy of the device array to the host
 included (moments: cos / sin, three matrix products and two sums; project: cos / sin, the centred product; series: np.fft; tica:
 the tICA entries -- moments, solver, two projections, four histograms, two autocovariances -- from the angles).
 
-    python scripts/analysis_bench.py [--leg all|dihedrals|histograms|acov|fft|numpy|moments|project|series|tica] [--size sampler|md|both]
+    python scripts/analysis_bench.py [--leg all|dihedrals|histograms|acov|fft|numpy|moments|project|series|tica|kmeans_pp|kmeans_step|kmeans_fit|
+                                           count_matrix|msm] [--size sampler|md|both]
                                      [--reps 5]
 
 acov reports multiply-adds (2 n' (K + 1) NF with n' the mean number of terms per lag) over time and that rate's share of the
@@ -156,10 +163,107 @@ def tica_legs(a, A, dev, want):
                           "analyze_tica_ms_median": med, "tica_part_ms": best - plain_best, "numpy_ms": host_ms(on_host)}))
 
 
+def wall_ms(fn, reps):
+    """Best and median wall time of `reps` calls, the device idle before and after each."""
+    fn()
+    ms = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return min(ms), float(np.median(ms))
+
+
+def host_lloyd_step(x, c):
+    """One Lloyd step in NumPy fp64 (distances in blocks of 1e4 points)."""
+    x, c = x.astype(np.float64), c.astype(np.float64)
+    arg = np.empty(len(x), np.int64)
+    cost = 0.0
+    for i in range(0, len(x), 10000):
+        D = ((x[i:i + 10000, None, :] - c[None]) ** 2).sum(-1)
+        arg[i:i + 10000] = D.argmin(1)
+        cost += D.min(1).sum()
+    sums = np.zeros_like(c)
+    np.add.at(sums, arg, x)
+    counts = np.bincount(arg, minlength=len(c))
+    return np.where(counts[:, None] > 0, sums / np.maximum(counts, 1)[:, None], c), cost
+
+
+def msm_legs(a, A, dev, want):
+    n, d, k = 1000000, 10, 100
+    if any(want(leg) for leg in ("kmeans_pp", "kmeans_step", "kmeans_fit", "count_matrix")):
+        x = angles(n, d, dev)
+        u = np.random.default_rng(A.KMEANS_SEED).random(k)
+        chosen = A.kmeans_pp(x, k, u)
+        centers0 = x.index_select(0, chosen).contiguous()
+    if want("kmeans_pp"):
+        ch = torch.zeros(k, dtype=torch.int64, device=dev)
+        mind2 = torch.empty(n, device=dev)
+        ws = torch.empty(A.kmeans_pp_workspace_bytes(n, d, k), dtype=torch.uint8, device=dev)
+        best, med = timed_ms(lambda: A.kmeans_pp_into(x, k, u, 0, k, ch, mind2, ws), a.reps)
+        print(json.dumps({"leg": "kmeans_pp", "n": n, "d": d, "k": k, "ms_best": best, "ms_median": med, "ms_per_round": best / k,
+                          "distinct": int(ch.unique().numel())}))
+    if want("kmeans_step"):
+        centers = centers0.clone()
+        assign = torch.empty(n, dtype=torch.int32, device=dev)
+        sums = torch.empty(k, d, dtype=torch.float64, device=dev)
+        counts = torch.empty(k, dtype=torch.int64, device=dev)
+        cost, state = torch.zeros(2, dtype=torch.float64, device=dev), torch.zeros(2, dtype=torch.int32, device=dev)
+        ws = torch.empty(A.kmeans_step_workspace_bytes(n, d, k), dtype=torch.uint8, device=dev)
+
+        def step():
+            centers.copy_(centers0)
+            state.zero_()
+            A.kmeans_step_into(x, centers, assign, sums, counts, cost, state, 0.0, ws)
+        best, med = timed_ms(step, a.reps)
+        xs, cs = x[:100000].cpu().numpy(), centers0.cpu().numpy()
+        print(json.dumps({"leg": "kmeans_step", "n": n, "d": d, "k": k, "ms_best": best, "ms_median": med,
+                          "workspace_MB": ws.numel() / 1e6, "distance_fma_per_s": float(n) * k * d / (best * 1e-3),
+                          "share_of_fp32_vector_peak": float(n) * k * d / (best * 1e-3) / FMA_PEAK,
+                          "numpy_step_ms_1e5": host_ms(lambda: host_lloyd_step(xs, cs))}))
+    if want("kmeans_fit"):
+        fit = A.kmeans_fit(x, k)
+        best, med = wall_ms(lambda: A.kmeans_fit(x, k), max(a.reps // 2, 1))
+        print(json.dumps({"leg": "kmeans_fit", "n": n, "d": d, "k": k, "max_iter": A.KMEANS_MAX_ITER, "steps": fit["steps"],
+                          "wall_ms_best": best, "wall_ms_median": med}))
+    if want("count_matrix"):
+        for kk in (100, 256):
+            cen = x[torch.randperm(n, generator=torch.Generator().manual_seed(4))[:kk].to(dev)].contiguous()
+            dtraj = A.kmeans_assign(x, cen)
+            cm = torch.empty(kk, kk, dtype=torch.int64, device=dev)
+            dr = torch.empty(1, dtype=torch.int64, device=dev)
+            best, med = timed_ms(lambda: A.count_matrix_into(dtraj, 1000, kk, cm, dr), a.reps * 4)
+            abest, _ = timed_ms(lambda: A.kmeans_assign(x, cen), a.reps)
+            print(json.dumps({"leg": "count_matrix", "n": n, "lag": 1000, "k": kk, "ms_best": best, "ms_median": med,
+                              "nonzero_cells": int((cm > 0).sum()), "assign_ms_best": abest}))
+    if want("msm"):
+        from mdgen_amd import msm as M
+        aat = np.array([3, 10, 1, 8])
+        g = torch.Generator(device=dev).manual_seed(3)
+        traj = torch.randn(100000, 4, 14, 3, generator=g, device=dev) * 3
+        ref = torch.randn(1000000, 4, 14, 3, generator=g, device=dev) * 3
+        reps = max(a.reps // 2, 1)
+        tica_best, tica_med = wall_ms(lambda: A.analyze(traj, ref, aat, tica=True), reps)
+        best, med = wall_ms(lambda: A.analyze(traj, ref, aat, msm=True), reps)
+        out = A.analyze(traj, ref, aat, msm=True)      # (frames drawn independently: every microstate reaches every other)
+
+        def on_host():
+            C = out["msm"]["count_matrix"]
+            m = M.estimate_msm(C, A.MD_MSM_LAG)
+            M.pcca(m["transition_matrix"], m["pi"], A.MSM_STATES)
+        print(json.dumps({"leg": "msm", "frames": 100000, "md_frames": 1000000, "dim": out["kmeans"]["dim"], "k": A.KMEANS_K,
+                          "kmeans_steps": out["kmeans"]["steps"], "analyze_tica_wall_ms_best": tica_best,
+                          "analyze_tica_wall_ms_median": tica_med, "analyze_msm_wall_ms_best": best, "analyze_msm_wall_ms_median": med,
+                          "msm_part_ms": best - tica_best, "host_ms": host_ms(on_host)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--leg", default="all", choices=["all", "dihedrals", "histograms", "acov", "fft", "numpy", "moments", "project",
-                                                     "series", "tica"])
+                                                     "series", "tica", "kmeans_pp", "kmeans_step", "kmeans_fit", "count_matrix",
+                                                     "msm"])
     ap.add_argument("--size", default="both", choices=["sampler", "md", "both"])
     ap.add_argument("--reps", type=int, default=5)
     a = ap.parse_args()
@@ -232,6 +336,7 @@ def main():
             dt = time.perf_counter() - t0
             print(json.dumps({"leg": "numpy", "size": size, "n": n, "K": K, "NF": NF, "dtype": "float64", "ms": dt * 1e3}))
     tica_legs(a, A, dev, want)
+    msm_legs(a, A, dev, want)
 
 
 if __name__ == "__main__":
