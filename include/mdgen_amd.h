@@ -834,6 +834,38 @@ int32_t mdgen_traj_kmeans_pp(int64_t n, int32_t d, int32_t k, const float* x, co
 int32_t mdgen_traj_count_matrix(int64_t n, int64_t lag, int32_t k, const int32_t* dtraj, int64_t* counts, int64_t* dropped,
                                 void* stream);
 
+/* Transition paths of a Markov-state model (csrc/k_tps.hip; mdgen_amd/analysis.py tp_sample): the reference's `sample_tp`
+ * (mdgen/analysis.py:61-76) and, with a scoring set, `get_tp_likelihood(...).prod(-1)` (:79-95) of every sampled path.  The
+ * conventions of the mdgen_traj_* entries: it runs on `stream`, synchronises nothing and reads nothing back; every refusal is
+ * decided before any device call and leaves the outputs untouched; no atomics, two calls give the same bits.
+ *
+ * mdgen_tp_sample: n_samples paths of length N of the k-state chain Ta, pinned at paths[s][0] = start and paths[s][N - 1] = end.
+ *   Ta fp64 [k][k] row-stochastic;  Ba fp64 [N][k] the bridge table, Ba[m][i] = (Ta^m)[i][end] (msm.bridge_table: Ba[0] = e_end,
+ *   Ba[m] = Ta Ba[m - 1]);  both device memory.  One thread per path.
+ *   The draw, for t = 1 .. N - 2 from state a = paths[s][t - 1]:
+ *     w_j = Ta[a][j] * Ba[N - t - 1][j]        each product rounded to fp64 before it is added (no contraction into an FMA)
+ *     c_j = c_{j-1} + w_j                      j ascending, c_{-1} = 0
+ *     u   = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53 53 bits, exact, in [0, 1); x = Philox4x32-10(counter; key) (mdgen_sample_sde_rng's
+ *                                              generator) with
+ *       counter  c0 = sample & 0xffffffff, c1 = sample >> 32, c2 = t, c3 = stream_id;   sample = sample_base + s mod 2^64
+ *       key      {seed & 0xffffffff, seed >> 32}                                        x2, x3 are unused
+ *     paths[s][t] = the smallest j with c_j > u * c_{k-1} (one rounded fp64 product); if rounding leaves none, the largest j with
+ *                   w_j > 0.
+ *   A path depends on (seed, stream_id, sample) alone: not on n_samples, on the launch shape or on the other paths of the call.
+ *   c_{k-1} = 0 (or NaN) cannot occur when Ba[N - 1][start] > 0; where it does, positions t .. N - 1 of that path are -1 and its
+ *   prob is 0.
+ *   Scoring set (kb >= 1; kb = 0: none, and Tb, Bb, phi, prob are ignored): Tb fp64 [kb][kb] and Bb fp64 [N][kb], its bridge table
+ *   to phi[end], device memory; phi int32 [k], a HOST array, checked here: state i of Ta is state phi[i] of Tb.
+ *     prob[s] = prod_{t = 1}^{N - 1} Tb[pa][pb] * Bb[N - t - 1][pb] / Bb[N - t][pa],  pa = phi[paths[s][t - 1]], pb = phi[paths[s][t]],
+ *   evaluated left to right, a NaN factor (0 / 0) counting as 0 and t ascending: `get_tp_likelihood(phi(paths), Tb).prod(-1)`.
+ *   paths int32 [n_samples][N] out;  prob fp64 [n_samples] out (scoring set only).
+ * -1: null pointer (Ta, Ba, paths; with kb >= 1 also Tb, Bb, phi, prob); -2: n_samples < 1 or > 2^40, N < 2 or > 4096, k < 1 or
+ * > 64, kb < 0 or > 64, start or end outside 0 .. k - 1, an entry of phi outside 0 .. kb - 1. */
+int32_t mdgen_tp_sample(int64_t n_samples, int32_t N, int32_t k, const double* Ta, const double* Ba, int32_t start, int32_t end,
+                        uint64_t seed, uint32_t stream_id, uint64_t sample_base, int32_t kb, const double* Tb /* or NULL */,
+                        const double* Bb /* or NULL */, const int32_t* phi /* host, or NULL */, int32_t* paths,
+                        double* prob /* or NULL */, void* stream);
+
 /* Flow-matching training target (transport.py:138-189 `training_losses`, velocity model; path.py:113-135 `plan`
  * with GVPCPlan :177-187 or the linear ICPlan): per sample b with time t[b],
  *   xt = alpha x1 + sigma x0,  ut = alpha' x1 + sigma' x0;   GVP: alpha = sin(pi t/2), sigma = cos(pi t/2);

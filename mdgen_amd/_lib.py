@@ -33,7 +33,7 @@ EXPORTS = [
     "mdgen_traj_lagged_moments", "mdgen_traj_lagged_moments_workspace_bytes", "mdgen_traj_project", "mdgen_traj_series_acov",
     "mdgen_traj_series_acov_workspace_bytes", "mdgen_traj_histograms_xy",
     "mdgen_traj_kmeans_assign", "mdgen_traj_kmeans_step", "mdgen_traj_kmeans_step_workspace_bytes", "mdgen_traj_kmeans_pp",
-    "mdgen_traj_kmeans_pp_workspace_bytes", "mdgen_traj_count_matrix",
+    "mdgen_traj_kmeans_pp_workspace_bytes", "mdgen_traj_count_matrix", "mdgen_tp_sample",
 ]
 
 
@@ -168,6 +168,8 @@ def _load():
     lib.mdgen_traj_kmeans_pp_workspace_bytes.argtypes = [i64, i32, i32, C.POINTER(sz)]
     lib.mdgen_traj_kmeans_pp.argtypes = [i64, i32, i32, vp, vp, i32, i32, vp, vp, vp, sz, vp]   # n, d, k | x, u (host) | r0, r1 | chosen, mind2 | workspace, bytes
     lib.mdgen_traj_count_matrix.argtypes = [i64, i64, i32, vp, vp, vp, vp]   # n, lag, k | dtraj, counts, dropped
+    u32, u64 = C.c_uint32, C.c_uint64
+    lib.mdgen_tp_sample.argtypes = [i64, i32, i32, vp, vp, i32, i32, u64, u32, u64, i32, vp, vp, vp, vp, vp, vp]   # n_samples, N, k | Ta, Ba | start, end | seed, stream_id, sample_base | kb, Tb, Bb, phi (host) | paths, prob
     lib.mdgen_from_3_points.argtypes = [i64] + [vp] * 6
     lib.mdgen_path_plan.argtypes = [i64, i64, i32] + [vp] * 6
     lib.mdgen_masked_mse.argtypes = [i64, i64] + [vp] * 5

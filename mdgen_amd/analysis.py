@@ -14,8 +14,13 @@ Lloyd's iteration on the MD trajectory's tICA projection and every count matrix 
 connected set, reversible maximum likelihood, PCCA+) in NumPy fp64 on the host, mdgen_amd/msm.py.  Every rule is restated there and
 in the README; pyemma is not installed where this was written, and agreement with its seeded estimators is unverified.
 
-Out of scope: the Nelder-Mead refinement of PCCA+, pyemma object pickles (the estimators are stored as plain dicts), plots,
-`analyze_peptide_tps`; reading or writing XTC files.
+Transition paths (`tp_sample`, `tp_sample_into`; csrc/k_tps.hip: `mdgen_tp_sample`): the reference's `sample_tp` -- paths of an MSM
+pinned at a start and an end state -- and their likelihood under a second MSM, a thread per path; `md_msm`, the MD half of
+`msm_entries`, is what `tps_inference --msm` builds its metadata from, and `python -m mdgen_amd.analyze_peptide_tps` scores the
+sampled paths.
+
+Out of scope: the Nelder-Mead refinement of PCCA+, pyemma object pickles (the estimators are stored as plain dicts), plots, TPT
+fluxes; reading or writing XTC files.
 
 `torsion_features` and `tica_solve` import without torch; the functions on tensors import torch and the library when they are
 called."""
@@ -662,6 +667,42 @@ def _filled(active_set, values, nstates, base):
     return out
 
 
+def md_msm(y_ref, k=KMEANS_K, nstates=MSM_STATES, md_lag=MD_MSM_LAG, seed=KMEANS_SEED):
+    """The MD half of `msm_entries` -- its steps 1 and 3 .. 6, which need no sampled trajectory -- from the MD trajectory's tICA
+    projection y_ref (n, d), an fp32 CUDA tensor: (entries, d_ref).  `entries`: {"kmeans", "msm", "pcca", "cmsm"}, plain dicts;
+    `d_ref`: the MD trajectory's microstate dtraj, an int32 device tensor [n].  The ValueErrors are `msm_entries`'."""
+    import torch
+    from . import msm as M
+    k, nstates = int(k), int(nstates)
+    if not 1 <= nstates <= k:
+        raise ValueError(f"{nstates} metastable states of {k} microstates")
+    y_ref = _device_f32(y_ref)
+    km = kmeans_fit(y_ref, k, seed=seed)
+    centers = torch.from_numpy(km["centers"]).to(y_ref.device)
+    d_ref = kmeans_assign(y_ref, centers)
+    C, _ = count_matrix(d_ref, md_lag, k)
+    if C.sum() == 0:
+        raise ValueError(f"no transition counts: the MD trajectory has {int(y_ref.shape[0])} frames, the MSM lag is {int(md_lag)}")
+    model = M.estimate_msm(C, md_lag)
+    if len(model["active_set"]) != k:
+        raise ValueError(f"only {len(model['active_set'])} of {k} microstates are in the MSM's connected set at lag {int(md_lag)}")
+    pc = M.pcca(model["transition_matrix"], model["pi"], nstates)
+    lump = np.zeros((k, nstates), np.int64)
+    lump[np.arange(k), pc["metastable_assignments"]] = 1
+    cmsm = M.estimate_msm(lump.T @ C @ lump, md_lag)
+    return {"kmeans": {key: km[key] for key in ("centers", "dim", "steps", "cost", "seed")}, "msm": model, "pcca": pc, "cmsm": cmsm}, d_ref
+
+
+def lumped(y, centers, meta):
+    """The metastable-state dtraj of the projection y (n, d): `kmeans_assign` by the fitted `centers`, then the PCCA+ assignment
+    `meta` [k] of every microstate -- the reference's `discretize`.  (microstates, metastable states), int32 device tensors [n]."""
+    import torch
+    y = _device_f32(y)
+    d = kmeans_assign(y, torch.from_numpy(np.asarray(centers, np.float32)).to(y.device))
+    meta_dev = torch.from_numpy(np.asarray(meta).astype(np.int32)).to(y.device)
+    return d, meta_dev[d.long()].contiguous()
+
+
 def msm_entries(y_traj, y_ref, k=KMEANS_K, nstates=MSM_STATES, md_lag=MD_MSM_LAG, traj_lag=MSM_LAG, traj_msm=True, seed=KMEANS_SEED,
                 name=None) -> dict:
     """The k-means / MSM / PCCA+ part of the reference's result (analyze_peptide_sim.py:153-197; mdgen/analysis.py get_kmeans,
@@ -675,8 +716,9 @@ def msm_entries(y_traj, y_ref, k=KMEANS_K, nstates=MSM_STATES, md_lag=MD_MSM_LAG
       8. with `traj_msm`: the lumped sampled dtraj counted at `traj_lag` (device) and `msm.estimate_msm`.  When that alone fails
          (no transition counts), its three entries are left out and `name` is written to stderr.
 
-    Keys, in order: kmeans, msm, pcca, cmsm, traj_metastable_probs, ref_metastable_probs, msm_transition_matrix, pcca_pi, msm_pi,
-    and traj_msm, traj_transition_matrix, traj_pi.  Estimators are plain dicts of NumPy arrays and ints."""
+    Steps 1 and 3 .. 6 are `md_msm`'s.  Keys, in order: kmeans, msm, pcca, cmsm, traj_metastable_probs, ref_metastable_probs,
+    msm_transition_matrix, pcca_pi, msm_pi, and traj_msm, traj_transition_matrix, traj_pi.  Estimators are plain dicts of NumPy
+    arrays and ints."""
     import sys
     import torch
     from . import msm as M
@@ -685,23 +727,11 @@ def msm_entries(y_traj, y_ref, k=KMEANS_K, nstates=MSM_STATES, md_lag=MD_MSM_LAG
         raise ValueError(f"{nstates} metastable states of {k} microstates")
     y_ref = _device_f32(y_ref)
     y_traj = _device_f32(y_traj, y_ref.device)
-    km = kmeans_fit(y_ref, k, seed=seed)
-    centers = torch.from_numpy(km["centers"]).to(y_ref.device)
-    d_ref, d_traj = kmeans_assign(y_ref, centers), kmeans_assign(y_traj, centers)
-    C, _ = count_matrix(d_ref, md_lag, k)
-    if C.sum() == 0:
-        raise ValueError(f"no transition counts: the MD trajectory has {int(y_ref.shape[0])} frames, the MSM lag is {int(md_lag)}")
-    model = M.estimate_msm(C, md_lag)
-    if len(model["active_set"]) != k:
-        raise ValueError(f"only {len(model['active_set'])} of {k} microstates are in the MSM's connected set at lag {int(md_lag)}")
-    pc = M.pcca(model["transition_matrix"], model["pi"], nstates)
-    meta = pc["metastable_assignments"]
-    lump = np.zeros((k, nstates), np.int64)
-    lump[np.arange(k), meta] = 1
-    cmsm = M.estimate_msm(lump.T @ C @ lump, md_lag)
-    meta_dev = torch.from_numpy(meta.astype(np.int32)).to(y_ref.device)
-    l_ref, l_traj = meta_dev[d_ref.long()].contiguous(), meta_dev[d_traj.long()].contiguous()
-    out = {"kmeans": {key: km[key] for key in ("centers", "dim", "steps", "cost", "seed")}, "msm": model, "pcca": pc, "cmsm": cmsm}
+    out, d_ref = md_msm(y_ref, k, nstates, md_lag, seed)
+    pc, cmsm = out["pcca"], out["cmsm"]
+    meta_dev = torch.from_numpy(pc["metastable_assignments"].astype(np.int32)).to(y_ref.device)
+    l_ref = meta_dev[d_ref.long()].contiguous()
+    _, l_traj = lumped(y_traj, out["kmeans"]["centers"], pc["metastable_assignments"])
     out["traj_metastable_probs"] = np.diag(count_matrix(l_traj, 0, nstates)[0]) / float(l_traj.numel())
     out["ref_metastable_probs"] = np.diag(count_matrix(l_ref, 0, nstates)[0]) / float(l_ref.numel())
     out["msm_transition_matrix"] = _filled(cmsm["active_set"], cmsm["transition_matrix"], nstates, np.eye(nstates))
@@ -720,6 +750,79 @@ def msm_entries(y_traj, y_ref, k=KMEANS_K, nstates=MSM_STATES, md_lag=MD_MSM_LAG
             out["traj_transition_matrix"] = _filled(tm["active_set"], tm["transition_matrix"], nstates, np.eye(nstates))
             out["traj_pi"] = _filled(tm["active_set"], tm["pi"], nstates, np.zeros(nstates))
     return out
+
+
+# ---- transition paths ------------------------------------------------------------------------------------------------
+TP_MAX_STATES = 64             # include/mdgen_amd.h mdgen_tp_sample: k, kb <= 64, 2 <= N <= 4096
+TP_MAX_LEN = 4096
+
+
+def _check_tp_shape(n_samples, N, k, start, end):
+    if n_samples < 1:
+        raise ValueError(f"at least one path, got {n_samples}")
+    if not 2 <= N <= TP_MAX_LEN:
+        raise ValueError(f"a path has 2 .. {TP_MAX_LEN} frames, got {N}")
+    if not 1 <= k <= TP_MAX_STATES:
+        raise ValueError(f"the bridge sampler takes 1 .. {TP_MAX_STATES} states, got {k}")
+    if not (0 <= start < k and 0 <= end < k):
+        raise ValueError(f"start {start} / end {end} outside the {k} states")
+
+
+def tp_sample_into(Ta, Ba, start, end, seed, stream, paths, sample_base=0, Tb=None, Bb=None, phi=None, prob=None) -> None:
+    """One `mdgen_tp_sample` call on paths' device and current stream: Ta [k, k] and Ba [N, k] fp64 device tensors
+    (`msm.bridge_table(Ta, end, N)`); paths int32 [n_samples, N] written.  With the scoring set -- Tb [kb, kb], Bb [N, kb]
+    (`msm.bridge_table(Tb, phi[end], N)`) fp64 device tensors, `phi` a host int32 [k] array -- also prob fp64 [n_samples]."""
+    import torch
+    from ._lib import launch, lib, ptr
+    n_samples, N, k = int(paths.shape[0]), int(paths.shape[1]), int(Ta.shape[0])
+    _check_tp_shape(n_samples, N, k, int(start), int(end))
+    f64 = torch.float64
+    if Ta.ndim != 2 or int(Ta.shape[1]) != k or Ba.numel() != N * k:
+        raise ValueError("Ta must be [k, k], Ba [N, k]")
+    kb, phi_p = 0, None
+    if Tb is not None:
+        kb = int(Tb.shape[0])
+        phi = np.ascontiguousarray(phi, np.int32).ravel()
+        if not 1 <= kb <= TP_MAX_STATES or Tb.ndim != 2 or int(Tb.shape[1]) != kb or Bb.numel() != N * kb or phi.shape[0] != k:
+            raise ValueError(f"Tb must be [kb, kb] with kb <= {TP_MAX_STATES}, Bb [N, kb], phi [k]")
+        if prob is None or prob.numel() < n_samples:
+            raise ValueError("prob needs n_samples elements")
+        phi_p = phi.ctypes.data
+    launch(lib.mdgen_tp_sample, paths, n_samples, N, k, ptr(Ta, f64), ptr(Ba, f64), int(start), int(end), int(seed) % (1 << 64),
+           int(stream) % (1 << 32), int(sample_base) % (1 << 64), kb, ptr(Tb, f64) if kb else None, ptr(Bb, f64) if kb else None,
+           phi_p, ptr(paths, torch.int32), ptr(prob, f64) if kb else None)
+
+
+def tp_sample(Ta, start, end, N, n_samples, seed, stream, score=None, sample_base=0, device=None):
+    """The reference's `sample_tp(Ta, start, end, N, n_samples)` on the device: paths int32 [n_samples, N] as a NumPy array, every
+    path a draw of the chain Ta (fp64 [k, k], matrix indices) pinned at `start` and `end`; path s depends on (seed, stream,
+    sample_base + s) alone (include/mdgen_amd.h mdgen_tp_sample states the draw).  With `score` = (Tb, phi) -- a scoring matrix and
+    the index map from Ta's states into Tb's -- (paths, prob): prob fp64 [n_samples] = `msm.tp_likelihood(phi[paths], Tb).prod(-1)`.
+    ValueError when `end` cannot be reached from `start` in N - 1 steps."""
+    import torch
+    from . import msm as M
+    Ta = np.ascontiguousarray(Ta, np.float64)
+    k, N, n_samples, start, end = Ta.shape[0], int(N), int(n_samples), int(start), int(end)
+    if Ta.ndim != 2 or Ta.shape[1] != k:
+        raise ValueError(f"transition matrix {Ta.shape}: expected [k, k]")
+    _check_tp_shape(n_samples, N, k, start, end)
+    Ba = M.bridge_table(Ta, end, N)
+    if not Ba[N - 1, start] > 0:
+        raise ValueError(f"end state not reachable in N - 1 steps: (Ta^{N - 1})[{start}, {end}] = {Ba[N - 1, start]}")
+    if score is not None:
+        Tb, phi = np.ascontiguousarray(score[0], np.float64), np.ascontiguousarray(score[1], np.int32).ravel()
+        if Tb.ndim != 2 or Tb.shape[0] != Tb.shape[1] or not 1 <= Tb.shape[0] <= TP_MAX_STATES:
+            raise ValueError(f"scoring matrix {Tb.shape}: expected [kb, kb], kb <= {TP_MAX_STATES}")
+        if phi.shape[0] != k or phi.min() < 0 or phi.max() >= Tb.shape[0]:
+            raise ValueError(f"phi {phi.shape}: expected {k} indices into {Tb.shape[0]} states")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    paths = torch.empty(n_samples, N, dtype=torch.int32, device=dev)
+    kw = {}
+    if score is not None:
+        kw = dict(Tb=torch.from_numpy(Tb).to(dev), Bb=torch.from_numpy(M.bridge_table(Tb, int(phi[end]), N)).to(dev), phi=phi,
+                  prob=torch.empty(n_samples, dtype=torch.float64, device=dev))
+    tp_sample_into(torch.from_numpy(Ta).to(dev), torch.from_numpy(Ba).to(dev), start, end, seed, stream, paths, sample_base, **kw)
+    return (paths.cpu().numpy(), kw["prob"].cpu().numpy()) if score is not None else paths.cpu().numpy()
 
 
 def analyze(traj_atom14, ref_atom14, aatype, nlag=NLAG, ref_nlag=None, pairs=DEFAULT_PAIRS, decorr=True, tica=False,

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libmdgen_amd.so")
-SOURCES = ["api.hip", "k_gemm.hip", "k_rows.hip", "k_flash.hip", "k_small.hip", "k_se3.hip", "k_fp32.hip", "k_optim.hip", "k_fp32_bwd.hip", "k_attn16.hip", "k_wide16.hip", "k_ode.hip", "k_rk.hip", "k_sde.hip", "k_pdb.hip", "k_analysis.hip", "k_tica.hip", "k_msm.hip"]
+SOURCES = ["api.hip", "k_gemm.hip", "k_rows.hip", "k_flash.hip", "k_small.hip", "k_se3.hip", "k_fp32.hip", "k_optim.hip", "k_fp32_bwd.hip", "k_attn16.hip", "k_wide16.hip", "k_ode.hip", "k_rk.hip", "k_sde.hip", "k_pdb.hip", "k_analysis.hip", "k_tica.hip", "k_msm.hip", "k_tps.hip"]
 HEADERS = ["common.h", "dev.h", "panel.h", "rows.h", "linear.h", "kernels.h", "train.inc", "ode.inc", "sde.inc", "drivers.inc", "state_embed.h", "philox.h", "analysis.h", os.path.join("..", "..", "include", "mdgen_amd.h")]
 # -fno-slp-vectorize: keeps hipcc from fusing scalar fp32 math into v_pk_{mul,add,fma}_f32.  On MI355X those
 # packed ops (a) are an anti-lever beside MFMAs (MI355X_MICROARCH "price of one filler") and (b) produced
@@ -24,7 +24,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", 
          "-Wno-unused-function", "-Wno-pass-failed"]
 # per-file extras.  k_flash: no NaN-aware code in it, and without this every fmaxf on an MFMA result gets a
 # canonicalising v_max(x, x) in front (15 extra VALU per key tile in a VALU-bound loop).
-EXTRA = {"k_flash.hip": ["-fno-honor-nans"]}
+# k_tps: the bridge sampler's products are rounded before they are added (include/mdgen_amd.h mdgen_tp_sample), so that a NumPy
+# restatement reproduces the paths: no contraction into FMAs.
+EXTRA = {"k_flash.hip": ["-fno-honor-nans"], "k_tps.hip": ["-ffp-contract=off"]}
 
 
 def flags_for(src: str):

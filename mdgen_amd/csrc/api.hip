@@ -2583,6 +2583,32 @@ extern "C" int32_t mdgen_traj_count_matrix(int64_t n, int64_t lag, int32_t k, co
     return 0;
 }
 
+// transition paths (k_tps.hip): the same conventions; phi is a host array, checked here
+extern "C" int32_t mdgen_tp_sample(int64_t n_samples, int32_t N, int32_t k, const double* Ta, const double* Ba, int32_t start,
+                                   int32_t end, uint64_t seed, uint32_t stream_id, uint64_t sample_base, int32_t kb,
+                                   const double* Tb, const double* Bb, const int32_t* phi, int32_t* paths, double* prob,
+                                   void* stream) {
+    if (n_samples < 1 || n_samples > kTrajMaxFrames) return fail(-2, "n_samples must be in 1 .. 2^40");
+    if (N < 2 || N > kTpMaxLen) return fail(-2, "N must be in 2 .. %d", kTpMaxLen);
+    if (k < 1 || k > kTpMaxStates) return fail(-2, "k must be in 1 .. %d", kTpMaxStates);
+    if (kb < 0 || kb > kTpMaxStates) return fail(-2, "kb must be in 1 .. %d (0: no scoring set)", kTpMaxStates);
+    if (start < 0 || start >= k || end < 0 || end >= k)
+        return fail(-2, "start = %d / end = %d is outside the %d states", start, end, k);
+    NONNULL(Ta, Ba, paths);
+    TpPhi map = {};
+    if (kb > 0) {
+        NONNULL(Tb, Bb, phi, prob);
+        for (int32_t i = 0; i < k; ++i) {
+            if (phi[i] < 0 || phi[i] >= kb) return fail(-2, "phi[%d] = %d is outside the %d scoring states", i, phi[i], kb);
+            map.v[i] = (uint8_t)phi[i];
+        }
+    }
+    launch_tp_sample(n_samples, N, k, Ta, Ba, start, end, seed, stream_id, sample_base, kb, Tb, Bb, map, paths, prob,
+                     (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // flow-matching training target and loss (forward only)
 // ---------------------------------------------------------------------------------------------

@@ -670,4 +670,15 @@ void launch_kmeans_pp(long n, int d, const float* x, const double* u_host, int r
 // counts [k][k] and dropped [1] must be zero on entry; lag < n
 void launch_count_matrix(long n, long lag, int k, const int32_t* dtraj, int64_t* counts, int64_t* dropped, hipStream_t s);
 
+// transition paths (k_tps.hip): Markov-bridge paths of a k-state chain and their likelihood under a second chain of kb states
+constexpr int kTpMaxStates = 64;     // k, kb
+constexpr int kTpMaxLen = 4096;      // N
+struct TpPhi {                       // the checked host map from Ta's states into Tb's: it travels as a kernel argument
+    uint8_t v[kTpMaxStates];
+};
+// kb = 0: no scoring set (Tb, Bb, prob unused)
+void launch_tp_sample(long n_samples, int N, int k, const double* Ta, const double* Ba, int start, int end, uint64_t seed,
+                      uint32_t stream_id, uint64_t sample_base, int kb, const double* Tb, const double* Bb, const TpPhi& phi,
+                      int32_t* paths, double* prob, hipStream_t s);
+
 }  // namespace mdg

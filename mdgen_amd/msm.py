@@ -8,6 +8,10 @@ itself, and k-means before it, are the device's (mdgen_amd/analysis.py count_mat
 Left out on purpose: pyemma refines the PCCA+ transformation with a Nelder-Mead search after the inner simplex algorithm -- here the
 inner simplex result is final; Bayesian / HMM estimators, error bars, plots.
 
+The transition-path estimators of the reference's mdgen/analysis.py and tps_inference.py:110-127 are here too (`bridge_table`,
+`tp_likelihood`, `state_probs`, `bridge_exact`, `tps_endpoints`); the bridge paths themselves are sampled on the device
+(mdgen_amd/analysis.py tp_sample; csrc/k_tps.hip).
+
 Imports without torch or scipy.  Estimator results are plain dicts of NumPy arrays and ints."""
 from __future__ import annotations
 
@@ -148,3 +152,113 @@ def least_flux_pair(cmsm):
     a, b = np.unravel_index(int(np.argmin(flux)), flux.shape)
     active = np.asarray(cmsm["active_set"])
     return int(active[a]), int(active[b])
+
+
+# ---- transition paths ------------------------------------------------------------------------------------------------
+# A path of length N of a chain T pinned at both ends (a Markov bridge) leaves state a at step t = 1 .. N - 1 for state b with
+# probability T[a, b] B[N - t - 1][b] / B[N - t][a], B[m][i] = (T^m)[i, end]: the reference's `sample_tp` and `get_tp_likelihood`
+# (mdgen/analysis.py:61-95), which evaluate both powers with `np.linalg.matrix_power` at every step.
+def bridge_table(T, end, N):
+    """B fp64 [N, k]: B[0] = e_end, B[m] = T @ B[m - 1], so B[m][i] = (T^m)[i, end] -- the reference's
+    `matrix_power(T, m)[:, end]` up to rounding."""
+    T = np.asarray(T, np.float64)
+    k, N, end = T.shape[0], int(N), int(end)
+    if T.ndim != 2 or T.shape[1] != k or k < 1:
+        raise ValueError(f"transition matrix {T.shape}: expected [k, k], k >= 1")
+    if N < 1 or not 0 <= end < k:
+        raise ValueError(f"bridge table of {N} rows to state {end} of {k}")
+    B = np.zeros((N, k))
+    B[0, end] = 1.0
+    for m in range(1, N):
+        B[m] = T @ B[m - 1]
+    return B
+
+
+def tp_likelihood(tp, T):
+    """fp64 [P, N - 1]: the reference's `get_tp_likelihood(tp, T)`, literally.  With s_N = tp[0, -1] -- the FIRST path's last
+    state, for every path -- and B = bridge_table(T, s_N, N), step t = i + 1 has probability T[a, b] B[N - t - 1][b] / B[N - t][a],
+    a = tp[:, i], b = tp[:, i + 1]; NaN (0 / 0: a state that cannot reach s_N) becomes 0."""
+    tp = np.asarray(tp, np.int64)
+    T = np.asarray(T, np.float64)
+    if tp.ndim != 2 or tp.shape[0] < 1 or tp.shape[1] < 2:
+        raise ValueError(f"paths {tp.shape}: expected [P, N], P >= 1, N >= 2")
+    N = tp.shape[1]
+    B = bridge_table(T, int(tp[0, -1]), N)
+    out = np.empty((tp.shape[0], N - 1))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for i in range(N - 1):
+            t = i + 1
+            a, b = tp[:, i], tp[:, i + 1]
+            out[:, i] = T[a, b] * B[N - t - 1][b] / B[N - t][a]
+    out[np.isnan(out)] = 0
+    return out
+
+
+def state_probs(tp, num_states=10):
+    """The reference's `get_state_probs`: bincount(tp, minlength=num_states) / its sum."""
+    counts = np.bincount(np.asarray(tp, np.int64).reshape(-1), minlength=int(num_states))
+    return counts / counts.sum()
+
+
+def bridge_exact(Ta, start, end, N, Tb=None, phi=None):
+    """The exact expectations that the reference estimates from 1000 sampled bridge paths of Ta (length N, start -> end):
+
+      Z_a = (Ta^(N-1))[start, end];   "occupancy"[j] = (1 / N) sum_{t=0}^{N-1} (Ta^t)[start, j] (Ta^(N-1-t))[j, end] / Z_a,
+      the expected share of a path's N frames spent in state j (what `state_probs` of the sampled paths estimates).
+
+    With a scoring matrix Tb and the index map phi from Ta's states into Tb's (identity when None), Tb'[i, j] = Tb[phi i, phi j],
+    Z_b = (Tb^(N-1))[phi start, phi end], o the elementwise product:
+
+      "prob" = ((Ta o Tb')^(N-1))[start, end] / (Z_a Z_b)     the mean of `tp_likelihood(phi(paths), Tb).prod(-1)` (0 when Z_b = 0)
+      "valid_rate" = ((Ta o [Tb' > 0])^(N-1))[start, end] / Z_a     the share of paths with a positive product
+      "valid_prob" = prob / valid_rate                        the mean over those (NaN when there are none)
+
+    {"Z", "occupancy"} and, with Tb, {"prob", "valid_rate", "valid_prob"}.  ValueError when Z_a = 0."""
+    Ta = np.asarray(Ta, np.float64)
+    k, N, start, end = Ta.shape[0], int(N), int(start), int(end)
+    if Ta.ndim != 2 or Ta.shape[1] != k or N < 2 or not (0 <= start < k and 0 <= end < k):
+        raise ValueError(f"bridge of length {N} from {start} to {end} on {Ta.shape}")
+
+    def forward(M):      # F[t] = e_start' M^t
+        F = np.zeros((N, k))
+        F[0, start] = 1.0
+        for t in range(1, N):
+            F[t] = F[t - 1] @ M
+        return F
+    Fa, Ba = forward(Ta), bridge_table(Ta, end, N)
+    Z = float(Ba[N - 1, start])
+    if not Z > 0:
+        raise ValueError(f"end state not reachable in N - 1 steps: (Ta^{N - 1})[{start}, {end}] = {Z}")
+    out = {"Z": Z, "occupancy": (Fa * Ba[::-1]).sum(0) / (N * Z)}
+    if Tb is not None:
+        Tb = np.asarray(Tb, np.float64)
+        phi = np.arange(k) if phi is None else np.asarray(phi, np.int64)
+        if phi.shape != (k,) or phi.min() < 0 or phi.max() >= Tb.shape[0]:
+            raise ValueError(f"phi {phi.shape}: expected {k} indices into {Tb.shape[0]} states")
+        Tbp = Tb[np.ix_(phi, phi)]
+        Zb = float(bridge_table(Tb, int(phi[end]), N)[N - 1, int(phi[start])])
+        valid = float(forward(Ta * (Tbp > 0))[N - 1, end]) / Z
+        prob = float(forward(Ta * Tbp)[N - 1, end]) / (Z * Zb) if Zb > 0 else 0.0
+        out.update(prob=prob, valid_rate=valid, valid_prob=prob / valid if valid > 0 else float("nan"))
+    return out
+
+
+def tps_endpoints(cmsm, meta, ref_dtraj, n_paths, seed, stream):
+    """(start_state, end_state, start_idx int64 [n_paths], end_idx int64 [n_paths]) as the reference's tps_inference.py:110-127
+    chooses them: the states are `least_flux_pair(cmsm)`; ref_discrete = meta[ref_dtraj] (the MD trajectory's metastable states);
+    every path draws one frame of the start state and one of the end state.  rng = np.random.default_rng([seed, stream]); per
+    path, in order, start_idxs[rng.integers(len(start_idxs))] and then end_idxs[rng.integers(len(end_idxs))].  (The reference draws
+    from NumPy's unseeded global state: the frames here are reproducible and not the reference's draw for draw.)  ValueError when
+    the MD trajectory has no frame in either state -- the reference prints and skips the peptide."""
+    start_state, end_state = least_flux_pair(cmsm)
+    ref_discrete = np.asarray(meta, np.int64)[np.asarray(ref_dtraj, np.int64)]
+    start_idxs, end_idxs = np.flatnonzero(ref_discrete == start_state), np.flatnonzero(ref_discrete == end_state)
+    if len(start_idxs) == 0 or len(end_idxs) == 0:
+        raise ValueError(f"no start or end state found: {len(start_idxs)} frames in state {start_state}, {len(end_idxs)} in "
+                         f"state {end_state}")
+    rng = np.random.default_rng([int(seed), int(stream)])
+    si, ei = np.empty(int(n_paths), np.int64), np.empty(int(n_paths), np.int64)
+    for p in range(int(n_paths)):
+        si[p] = start_idxs[rng.integers(len(start_idxs))]
+        ei[p] = end_idxs[rng.integers(len(end_idxs))]
+    return start_state, end_state, si, ei

@@ -1,6 +1,7 @@
 """The SDE sampler's generated noise on the host: a numpy restatement of csrc/philox.h and of the counter layout stated in
 include/mdgen_amd.h (mdgen_sample_sde_rng).  `Sampler.sample_sde`'s host loop over a generic callable draws from it, so that
-loop and the library's kernels integrate the same noise (to the rounding of logf / cosf: the words and u1, u2 are exact)."""
+loop and the library's kernels integrate the same noise (to the rounding of logf / cosf: the words and u1, u2 are exact).
+`bridge_uniform` is the uniform of the transition-path sampler (mdgen_tp_sample, csrc/k_tps.hip), exact as well."""
 from __future__ import annotations
 
 import numpy as np
@@ -40,3 +41,16 @@ def sde_noise(shape, seed, step, block_base=0, sample_base=0, block=0):
     b = ((np.arange(B, dtype=np.uint64) + np.uint64(int(sample_base) % (1 << 32))) & _MASK)[:, None]
     w = philox4x32_10(el, b, int(step) % (1 << 32), (int(block_base) + int(block)) % (1 << 32), seed & 0xFFFFFFFF, seed >> 32)
     return normal(w[0], w[1]).reshape(B, T, L, D)
+
+
+def bridge_uniform(seed, stream, sample, t):
+    """u fp64 in [0, 1) of the bridge sampler (include/mdgen_amd.h mdgen_tp_sample) for path `sample` (a 64-bit index:
+    sample_base + the position in the call) at step `t`, both broadcastable integer arrays: the words x0, x1 at the counter
+    (sample low word, sample high word, t, stream) under the key {seed low word, seed high word};
+    u = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53, 53 bits, exact."""
+    seed = int(seed) % (1 << 64)
+    sample = np.asarray(sample).astype(np.uint64)
+    w = philox4x32_10(sample & _MASK, sample >> np.uint64(32), np.asarray(t).astype(np.uint64) & _MASK, int(stream) % (1 << 32),
+                      seed & 0xFFFFFFFF, seed >> 32)
+    hi, lo = (w[0] >> np.uint32(5)).astype(np.uint64), (w[1] >> np.uint32(6)).astype(np.uint64)
+    return ((hi << np.uint64(26)) + lo).astype(np.float64) * 2.0 ** -53

@@ -15,13 +15,18 @@
   kmeans_fit    `kmeans_fit`: k-means++ and 100 step launches with the one read-back, wall time
   count_matrix  `mdgen_traj_count_matrix`: the 1e6-frame dtraj at lag 1000, k = 100 (LDS counters) and k = 256 (global ones)
   msm           `analyze(msm=True)` beside `analyze(tica=True)`, the same trajectories as `tica`; `host_ms`: the estimators alone
+  tps           `mdgen_tp_sample` (10 states, scored under a second 10-state chain) at (n_samples, N) = (1000, 11) and (1e6, 101):
+                the kernel alone (events), `tp_sample` with its tables' upload and the paths' copy back (wall), and `numpy_ms`, the
+                vectorised NumPy restatement of tests/tps_ref.py with `msm.tp_likelihood` on the same box; then one
+                `analyze_peptide_tps.analyze_tps` peptide at the reference's size: 1000 paths x 100 frames, a 1e6-frame replica,
+                seven replica lengths (wall; `metadata_wall_ms`: `tps_inference.build_metadata` of the 1e6-frame MD trajectory)
 
 Beside each of the last four, `numpy_ms`: the same definition in NumPy fp64 on the host, the copy of the device array to the host
 included (moments: cos / sin, three matrix products and two sums; project: cos / sin, the centred product; series: np.fft; tica:
 the tICA entries -- moments, solver, two projections, four histograms, two autocovariances -- from the angles).
 
     python scripts/analysis_bench.py [--leg all|dihedrals|histograms|acov|fft|numpy|moments|project|series|tica|kmeans_pp|kmeans_step|kmeans_fit|
-                                           count_matrix|msm] [--size sampler|md|both]
+                                           count_matrix|msm|tps] [--size sampler|md|both]
                                      [--reps 5]
 
 acov reports multiply-adds (2 n' (K + 1) NF with n' the mean number of terms per lag) over time and that rate's share of the
@@ -259,11 +264,62 @@ def msm_legs(a, A, dev, want):
                           "msm_part_ms": best - tica_best, "host_ms": host_ms(on_host)}))
 
 
+def tps_legs(a, A, dev, want):
+    if not want("tps"):
+        return
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import tps_ref as R
+    from mdgen_amd import analyze_peptide_tps as tps
+    from mdgen_amd import msm as M
+    from mdgen_amd.tps_inference import build_metadata
+    k = 10
+    Ta, Tb, phi = R.chain(k, 1, 0.2), R.chain(k, 2, 0.1), np.arange(k, dtype=np.int32)[::-1].copy()
+    start, end = 0, k - 1
+    for n, N in ((1000, 11), (1000000, 101)):
+        Ba, Bb = M.bridge_table(Ta, end, N), M.bridge_table(Tb, int(phi[end]), N)
+        dTa, dBa, dTb, dBb = (torch.from_numpy(x).to(dev) for x in (Ta, Ba, Tb, Bb))
+        paths = torch.empty(n, N, dtype=torch.int32, device=dev)
+        prob = torch.empty(n, dtype=torch.float64, device=dev)
+        reps = a.reps * 4 if n == 1000 else a.reps
+        best, med = timed_ms(lambda: A.tp_sample_into(dTa, dBa, start, end, 137, 0, paths, Tb=dTb, Bb=dBb, phi=phi, prob=prob), reps)
+        wbest, wmed = wall_ms(lambda: A.tp_sample(Ta, start, end, N, n, 137, 0, score=(Tb, phi)), reps)
+
+        def on_host():
+            p = R.sample(Ta, M.bridge_table(Ta, end, N), start, end, n, 137, 0)
+            return p, M.tp_likelihood(phi[p], Tb).prod(-1)
+        t0 = time.perf_counter()
+        hp, hq = on_host()
+        numpy_ms = (time.perf_counter() - t0) * 1e3
+        same = bool(np.array_equal(hp, paths.cpu().numpy()) and np.allclose(hq, prob.cpu().numpy(), rtol=1e-12, atol=0))
+        print(json.dumps({"leg": "tps", "what": "sampler", "n_samples": n, "N": N, "k": k, "kernel_ms_best": best,
+                          "kernel_ms_median": med, "steps_per_s": float(n) * (N - 2) / (best * 1e-3), "tp_sample_wall_ms_best": wbest,
+                          "tp_sample_wall_ms_median": wmed, "numpy_ms": numpy_ms, "equal_to_numpy": same}))
+    # one peptide of analyze_peptide_tps at the reference's size (frames drawn independently: every microstate reaches every other)
+    aat = np.array([3, 10, 1, 8])
+    g = torch.Generator(device=dev).manual_seed(3)
+    md = torch.randn(1000000, 4, 14, 3, generator=g, device=dev) * 3
+    t0 = time.perf_counter()
+    pkl = build_metadata(md, aat, device=dev)
+    torch.cuda.synchronize()
+    meta_ms = (time.perf_counter() - t0) * 1e3
+    del md
+    s_state, e_state, si, ei = M.tps_endpoints(pkl["cmsm"], pkl["pcca"]["metastable_assignments"], pkl["ref_kmeans"], 1000, 137, 0)
+    records = [{"start_state": s_state, "end_state": e_state}] * 1000
+    gen = (torch.randn(1000, 100, 4, 14, 3, generator=g, device=dev) * 3).cpu().numpy()
+    rep = (torch.randn(1000000, 4, 14, 3, generator=g, device=dev) * 3).cpu().numpy()
+    kept = gen[:, tps.strided_frames(100, 10)]
+    best, med = wall_ms(lambda: tps.analyze_tps("bench", pkl, records, kept, aat, rep, device=dev), max(a.reps // 2, 1))
+    nbest, _ = wall_ms(lambda: tps.analyze_tps("bench", pkl, records, kept, aat, None, device=dev), max(a.reps // 2, 1))
+    print(json.dumps({"leg": "tps", "what": "analyze_peptide_tps", "paths": 1000, "frames": 100, "kept": kept.shape[1],
+                      "replica_frames": 1000000, "rep_lens": len(tps.REP_LENS), "n_samples": 1000, "wall_ms_best": best,
+                      "wall_ms_median": med, "without_replica_wall_ms_best": nbest, "metadata_wall_ms": meta_ms}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--leg", default="all", choices=["all", "dihedrals", "histograms", "acov", "fft", "numpy", "moments", "project",
                                                      "series", "tica", "kmeans_pp", "kmeans_step", "kmeans_fit", "count_matrix",
-                                                     "msm"])
+                                                     "msm", "tps"])
     ap.add_argument("--size", default="both", choices=["sampler", "md", "both"])
     ap.add_argument("--reps", type=int, default=5)
     a = ap.parse_args()
@@ -337,6 +393,7 @@ def main():
             print(json.dumps({"leg": "numpy", "size": size, "n": n, "K": K, "NF": NF, "dtype": "float64", "ms": dt * 1e3}))
     tica_legs(a, A, dev, want)
     msm_legs(a, A, dev, want)
+    tps_legs(a, A, dev, want)
 
 
 if __name__ == "__main__":
