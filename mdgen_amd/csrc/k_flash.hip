@@ -34,7 +34,18 @@
 //     has its operands ready when the block starts, and the two neighbours belong to the other query tile;
 //   * K / V^T are streamed with buffer loads (SGPR descriptor + constant per-lane offset + scalar tile offset: no
 //     address arithmetic on the VALU), one tile ahead; V^T rows d > 24 are out-of-range lanes, which read zeros;
-//   * per-tile key-validity words live in one VGPR (lane i = tile i of a 64-tile window), fetched with v_readlane;
+//   * NO key-padding mask in the fixed-anchor loop.  The reference masks scores (masked_fill(-inf)): a masked key adds exactly zero
+//     to numerator and denominator.  Here the PRODUCER of the fragments supplies that zero (k_gemm.hip epilogue_v_flash,
+//     write_bias_slots): every V^T entry of an invalid key slot -- a token the key-padding mask removes, or a slot behind the bias
+//     key in the sequence's last tile -- is zero, the entry of the ones row included (row 24 is 1.0 at VALID slots only), so
+//     whatever finite P the slot gets adds P * 0 = 0 to O and to the denominator.  K of an invalid slot is finite: a masked token
+//     keeps its own, the slots behind the bias key hold the bias key's (a score the row has anyway; zeros would score -M and
+//     overflow bf16 under an anchor far below zero).  A P that overflows at an invalid slot gives inf * 0 = NaN in the
+//     accumulators, which the exponent-bit tests behind the loop catch like any other overflow: the job is redone in the robust
+//     loop, which still masks scores;
+//   * per-tile key-validity words (still written by k_ln_qkv) are read by the anchor prologue (tile 0's word: the anchor is the max
+//     over VALID keys), the only-the-bias-key test, and the robust loop: one VGPR (lane i = tile i of a 64-tile window), fetched
+//     with v_readlane;
 //   * the learned bias key is an ordinary entry of the fragments (key slot len, written by k_ln_qkv).
 #include "kernels.h"
 #include "panel.h"
@@ -57,7 +68,9 @@ struct KTile {
     u32x4 k0;   // K k-step 0: 8 bf16
     u32x4 k1;   // K k-step 1: 4 bf16 (loaded), the constant 1.0 twice (slots 4, 5: they pick up -M = -(hi + lo) from Q), 2 zeros.
                 // The constant dwords are NOT in memory: a slot's k1[2], k1[3] are set once (k_consts) and the loads of later
-                // tiles define only k1[0], k1[1] of the same registers
+                // tiles define only k1[0], k1[1] of the same registers.
+                // Every key slot of a tile holds FINITE values, invalid slots too (masked tokens: their own K; slots behind the bias key:
+                // the bias key's), so that an unmasked score is never NaN by itself
 };
 // The constant half of a K slot's k-step 1.  Opaque, so that hipcc keeps the two dwords in the slot's registers across the
 // loop instead of rematerialising them with a v_mov pair per tile (the loop is bound by VALU issue).
@@ -68,6 +81,8 @@ __device__ __forceinline__ void k_consts(KTile& t) {
 struct VTile {
     u32x4 v0;   // V^T k-step 0
     u32x4 v1;   // V^T k-step 1
+                // An INVALID key slot is zero in all 25 rows (row 24, the denominator's, is 1.0 at valid slots only): this is the
+                // key-padding mask of the fixed-anchor loop
 };
 struct QTile {
     bf16x8 q0, q1;   // k-steps 0 / 1 of one 32-query tile; k-step-1 slots 4, 5 of the lanes hh == 0 carry -M
@@ -109,8 +124,9 @@ __device__ __forceinline__ float set_shift(QTile& q, float m, int hh) {
 // up to 127 + kAnchor above that max still give a finite P, terms more than 126 - kAnchor below it flush to zero.
 constexpr float kAnchor = 63.f;
 
-// Key-padding mask of one tile: `vm` = validity bits of its 32 keys (wave-uniform, in an SGPR).  Only ever runs for
-// the last tile of a sequence and for padded residues; the shift is asm volatile so that none of it is hoisted.
+// Key-padding mask of one tile's scores: `vm` = validity bits of its 32 keys (wave-uniform, in an SGPR).  Anchor prologue (tile 0)
+// and robust loop only -- the fixed-anchor loop relies on the zeroed V^T entries of invalid slots instead; the shift is asm volatile
+// so that none of it is hoisted.
 __device__ __forceinline__ void mask_scores(f32x16& s, uint32_t vm, int hh) {
     uint32_t vmh;
     asm volatile("v_lshrrev_b32 %0, %1, %2" : "=v"(vmh) : "v"(4 * hh), "s"(vm));
@@ -335,7 +351,7 @@ __device__ __forceinline__ void flash_job(const FlashParams p, const int seq, co
 
     // ---- K / V^T streams: one buffer descriptor each (wave-uniform base = this (sequence, head)'s first tile), a
     // constant per-lane byte offset, and the tile offset as the scalar offset of the load.  V^T: rows d <= 24 are
-    // lanes of the fragment (row 24 = ones); the lanes of rows d > 24 point far out of range and read zeros.
+    // lanes of the fragment (row 24 = 1.0 at the valid key slots); the lanes of rows d > 24 point far out of range and read zeros.
     // Loads are UNCONDITIONAL: up to two tiles past the end of this (sequence, head) read whatever follows in the fragment
     // buffer (finite bf16 of the next head, or the zeroed slack the workspace layout keeps behind the K region: api.hip
     // kFragSlackK) and their results are never used.
@@ -345,6 +361,10 @@ __device__ __forceinline__ void flash_job(const FlashParams p, const int seq, co
     const int voff = ql <= kDH ? hh * 400 + ql * 16 : (int)0x80000000;
     auto issue_k = [&](KTile& t, int kt) __attribute__((always_inline)) {
         t.k0 = __builtin_amdgcn_raw_buffer_load_b128(krs, koff, kt * kFragK, 0);
+        // (opaque re-definition of the slot's tuple in front of the partial load: without it hipcc, in a loop body that is now one basic
+        // block, carries the loaded pair and the constants as separate values, rebuilds the tuple twice per iteration with six v_mov
+        // and WAITS for the 8-byte load it has just issued)
+        asm volatile("" : "+v"(t.k1));
         const u32x2 r = __builtin_amdgcn_raw_buffer_load_b64(krs, koff1, kt * kFragK, 0);   // k1[2], k1[3]: the slot's constants
         t.k1[0] = r[0];
         t.k1[1] = r[1];
@@ -375,7 +395,8 @@ __device__ __forceinline__ void flash_job(const FlashParams p, const int seq, co
     // k_flash_proj showed the first job of a launch's first round at 1.7x the time of a warm one); staggered, the 16 chunks pull
     // the whole fragment set into L2 at once and each misses on a sixteenth of it.  A sum over all keys does not care about the
     // order (the shift is fixed before the loop); the robust loop keeps the natural order (rot = 0), as do sequences of more than
-    // 64 tiles (the validity words arrive in 64-tile windows).
+    // 64 tiles (a limit from when this loop read the validity words, which arrive in 64-tile windows; kept, so that such sequences
+    // are summed in the order they always were).
     int rot = 0, nrun = 1;
     auto phys = [&](int i) __attribute__((always_inline)) {
         const int t = i + rot;
@@ -383,14 +404,14 @@ __device__ __forceinline__ void flash_job(const FlashParams p, const int seq, co
     };
     auto tile = [&](auto robust, int ti, KTile& kc, KTile& kn, VTile& vc, VTile& vprev) __attribute__((always_inline)) {
         constexpr bool kRobust = decltype(robust)::value;
-        const int t = kRobust ? ti : phys(ti);
-        const uint32_t vm = __builtin_amdgcn_readlane(vmw, t & 63);
+        // the fixed-anchor loop masks nothing: the V^T entries of an invalid key slot are zero, the denominator row's included
+        uint32_t vm = 0xffffffffu;
+        if constexpr (kRobust) vm = __builtin_amdgcn_readlane(vmw, ti & 63);
         static_for<NQ>([&](auto J) __attribute__((always_inline)) {
             constexpr int j = decltype(J)::value;
             // pair (t, j): scores in s[j & 1].  Block: s[(j+1) & 1] <- scores of the next pair; O of the previous
             // pair's query tile += its V P; pt[j & 1] <- exp(s[j & 1])
             if constexpr (kRobust) softmax_stats(h[j], s[j & 1], q[j], vm, hh);
-            else if (vm != 0xffffffffu) mask_scores(s[j & 1], vm, hh);
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (j == 0) block(kc, q[1], s[1], vprev, pt[(NQ - 1) & 1], h[NQ - 1].o, s[0], pt[0]);
             else if constexpr (j < NQ - 1) block(kc, q[j + 1], s[(j + 1) & 1], vc, pt[(j - 1) & 1], h[j - 1].o, s[j & 1], pt[j & 1]);
@@ -403,6 +424,7 @@ __device__ __forceinline__ void flash_job(const FlashParams p, const int seq, co
     };
     // The whole (head, 32 NQ queries) job over key tiles 0 .. nt - 1; returns with the last pair's PV MFMAs issued.
     auto run = [&](auto robust, const int nt, const int rot_) __attribute__((always_inline)) {
+        constexpr bool kRobust = decltype(robust)::value;   // only the robust loop reads the validity words, in 64-tile windows
         rot = rot_;
         nrun = nt;
 #pragma unroll
@@ -410,7 +432,7 @@ __device__ __forceinline__ void flash_job(const FlashParams p, const int seq, co
 #pragma unroll
             for (int r = 0; r < 16; ++r) h[j].o[r] = opaque_zero();
         pt[(NQ - 1) & 1].p0 = pt[(NQ - 1) & 1].p1 = u32x4{0u, 0u, 0u, 0u};   // "previous pair" of the very first block: P = 0
-        if (nt > 64) vmw = vmrow[lane];          // (a re-run after a long fast loop: back to the first window)
+        if constexpr (kRobust) vmw = vmrow[lane];   // the first window again: not kept in a register across the fixed-anchor loop
         k_consts(kx);
         k_consts(ky);
         issue_k(kx, phys(0));
@@ -423,13 +445,13 @@ __device__ __forceinline__ void flash_job(const FlashParams p, const int seq, co
         // different registers in the two halves and copy it mid-chain); an odd tile count gets a tail tile.
         int t = 0;
         for (; t + 1 < nt; t += 2) {
-            if ((t & 63) == 0 && t) vmw = vmrow[t + lane];
+            if (kRobust && (t & 63) == 0 && t) vmw = vmrow[t + lane];
             tile(robust, t, kx, ky, vx, vy);
             tile(robust, t + 1, ky, kx, vy, vx);
         }
         const bf16x8 lp0 = __builtin_bit_cast(bf16x8, pt[(NQ - 1) & 1].p0), lp1 = __builtin_bit_cast(bf16x8, pt[(NQ - 1) & 1].p1);
         if (t < nt) {
-            if ((t & 63) == 0 && t) vmw = vmrow[t + lane];
+            if (kRobust && (t & 63) == 0 && t) vmw = vmrow[t + lane];
             tile(robust, t, kx, ky, vx, vy);
             // pending: P of the last tile's last pair with V(last) = vx
             h[NQ - 1].o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vx.v0), __builtin_bit_cast(bf16x8, pt[(NQ - 1) & 1].p0), h[NQ - 1].o, 0, 0, 0);

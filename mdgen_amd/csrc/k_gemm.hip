@@ -207,13 +207,40 @@ __device__ __forceinline__ void epilogue_heads_T(const f32x16* acc /*[3 ft][TT]*
     }
 }
 
+// Validity of a panel's keys (FLASH layout): bit i = position pos0 + i is a valid key -- a real token the key-padding mask keeps, or
+// the learned bias key at position len; positions > len are invalid.  The 64 lanes of a wave are the panel's 64 positions, so every
+// wave can take the ballot for itself (a wave-uniform SGPR pair); bits 32 tt .. 32 tt + 31 are the key-validity word of tile tt.
+__device__ __forceinline__ unsigned long long panel_key_validity(const QkvParams& p, int seq, int pos0) {
+    const int len = p.ax.len, pos = pos0 + lane_id();
+    const float mv = p.mk.at(p.ax.token(seq, pos < len ? pos : len - 1));
+    return __ballot(pos == len || (pos < len && mv != 0.f));
+}
+// Select masks of a V^T fragment row (lane half hk) for a tile with validity word vm: dword j of the row's two 16-byte pieces holds
+// the keys of registers 2 j, 2 j + 1, register r = key slot (r & 3) + 4 hk + 8 (r >> 2); 0xffff over a valid key's bf16, 0 elsewhere.
+__device__ __forceinline__ void v_valid_dwords(uint32_t vm, int hk, uint32_t (&m)[8]) {
+    const uint32_t vmh = vm >> (4 * hk);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int r0 = 2 * j, r1 = 2 * j + 1;
+        const uint32_t lo = (vmh >> ((r0 & 3) + 8 * (r0 >> 2))) & 1u, hi = (vmh >> ((r1 & 3) + 8 * (r1 >> 2))) & 1u;
+        m[j] = ((0u - lo) & 0x0000ffffu) | ((0u - hi) & 0xffff0000u);
+    }
+}
+
 // V for the FLASH layout: non-transposed D[token][feature]; the accumulators are the V^T
 // fragments of the P.V MFMA (lane = (d, half), register r = key slot) -- no data movement.
+// `valid` (panel_key_validity): every V^T entry of an INVALID key slot is stored as zero, the entry of the denominator row 24
+// included (1.0 at valid slots only) -- the attention kernel's fixed-anchor loop does not mask scores: whatever finite P an invalid
+// slot gets meets zeros in the PV MFMA.  A fully valid tile (all but a sequence's last tile and tiles with padded residues) takes
+// the wave-uniform branch without the select.
 template <int TT = 2>
 __device__ __forceinline__ void epilogue_v_flash(const f32x16* acc /*[TT][3 ft]*/, int w,
                                                  const float* bias_perm, int seq, int ntile, int tile0,
-                                                 unsigned char* __restrict__ vf) {
+                                                 unsigned char* __restrict__ vf, unsigned long long valid) {
     const int lane = lane_id(), hh = lane >> 5, n = lane & 31;
+    uint32_t vm[TT];
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) vm[tt] = __builtin_amdgcn_readfirstlane((uint32_t)(valid >> (32 * tt)));
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const int col = 32 * j + n;
@@ -226,20 +253,38 @@ __device__ __forceinline__ void epilogue_v_flash(const f32x16* acc /*[TT][3 ft]*
             if (tile < ntile) {
                 unsigned char* base = vf + ((long)(seq * kH + head) * ntile + tile) * kFragV + hh * 400 + d * 16;
                 const f32x16 a = acc[tt * 3 + j];
-                *reinterpret_cast<u32x4*>(base) = u32x4{pack_bf16(a[0] + b, a[1] + b), pack_bf16(a[2] + b, a[3] + b),
-                                                         pack_bf16(a[4] + b, a[5] + b), pack_bf16(a[6] + b, a[7] + b)};
-                *reinterpret_cast<u32x4*>(base + 800) =
-                    u32x4{pack_bf16(a[8] + b, a[9] + b), pack_bf16(a[10] + b, a[11] + b),
-                          pack_bf16(a[12] + b, a[13] + b), pack_bf16(a[14] + b, a[15] + b)};
+                u32x4 v0 = u32x4{pack_bf16(a[0] + b, a[1] + b), pack_bf16(a[2] + b, a[3] + b),
+                                 pack_bf16(a[4] + b, a[5] + b), pack_bf16(a[6] + b, a[7] + b)};
+                u32x4 v1 = u32x4{pack_bf16(a[8] + b, a[9] + b), pack_bf16(a[10] + b, a[11] + b),
+                                 pack_bf16(a[12] + b, a[13] + b), pack_bf16(a[14] + b, a[15] + b)};
+                if (vm[tt] != 0xffffffffu) {   // wave-uniform
+                    uint32_t m[8];
+                    v_valid_dwords(vm[tt], hh, m);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        v0[i] &= m[i];
+                        v1[i] &= m[4 + i];
+                    }
+                }
+                *reinterpret_cast<u32x4*>(base) = v0;
+                *reinterpret_cast<u32x4*>(base + 800) = v1;
             }
         }
     }
-    if (lane < 32) {   // row 24 of every fragment this wave owns: 4 heads x 2 tiles x 2 key halves x 2 k-steps, all ones
+    if (lane < 32) {   // row 24 of every fragment this wave owns: 4 heads x 2 tiles x 2 key halves x 2 k-steps: 1.0 at the valid key slots
         const int hd = lane & 3, tt = (lane >> 2) & 1, h2 = (lane >> 3) & 1, ks = lane >> 4;
         const int tile = tile0 + tt;
-        if (tt < TT && tile < ntile)
-            *reinterpret_cast<u32x4*>(vf + ((long)(seq * kH + 4 * w + hd) * ntile + tile) * kFragV + ks * 800 + h2 * 400 + kDH * 16) =
-                u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
+        if (tt < TT && tile < ntile) {
+            u32x4 ones = u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
+            const uint32_t vml = tt == 0 ? vm[0] : vm[TT - 1];
+            if (vml != 0xffffffffu) {
+                uint32_t m[8];
+                v_valid_dwords(vml, h2, m);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) ones[i] &= ks ? m[4 + i] : m[i];
+            }
+            *reinterpret_cast<u32x4*>(vf + ((long)(seq * kH + 4 * w + hd) * ntile + tile) * kFragV + ks * 800 + h2 * 400 + kDH * 16) = ones;
+        }
     }
 }
 
@@ -248,37 +293,32 @@ __device__ __forceinline__ void epilogue_v_flash(const f32x16* acc /*[TT][3 ft]*
 // fragment layout covers len + 1 keys).  Written by the workgroup of a sequence's last panel, wave w for its heads
 // 4w..4w+3, AFTER the same wave's K / V epilogues (which may have stored padding-row values into that slot: same wave,
 // same address, program order).  The attention kernel then needs no special case for it.
+// The key slots BEHIND it (positions > len, the rest of the sequence's last tile) are invalid: their V^T entries are zero (the panel
+// epilogue; the tile of its own below), which is all the fixed-anchor loop asks of them, and their K is the bias key's -- a score
+// the row has anyway, so a slot that contributes nothing cannot be the one whose P overflows (zeros there would score -M).
 // do_k / do_v: the K / V^T half only (k_ln_qkv8: the two halves are written by different waves).
 // tpp: 32-position tiles per panel (2; 1 for the 32-row workgroups of k_ln_qkv8<true, true>)
 __device__ __forceinline__ void write_bias_slots(const QkvParams& p, int seq, int w, bool do_k = true, bool do_v = true, int tpp = 2) {
     const int lane = lane_id();
     const int len = p.ax.len, nt = p.ax.ntile();
     const int kt = len >> 5, sl = len & 31;
-    if (kt >= tpp * p.panels_per_seq) {
+    if (do_v && kt >= tpp * p.panels_per_seq) {
         // len is a multiple of 64: the bias key starts a tile of its own, which no panel epilogue has touched.  Its
-        // other 31 key slots are masked, but the PV MFMA still multiplies their V^T entries by P = 0 -- stale bytes
-        // that decode to NaN / inf would poison the sum -- and the all-ones row 24 must exist for the bias key's own P
-        // to reach the denominator.  So: zero both fragments, then the ones row, then (below) the bias slots.
+        // other 31 key slots are invalid: zeros in every V^T row (stale bytes that decode to NaN / inf would poison the
+        // PV MFMA's sum), and the denominator row 24 holds 1.0 at the bias key's slot 0 only.  Then (below) the bias slot.
 #pragma unroll
         for (int hd = 0; hd < 4; ++hd) {
             const long ft = (long)(seq * kH + 4 * w + hd) * nt + kt;
-            unsigned char* kd = p.kf + ft * kFragK;
             u32x4* vd = reinterpret_cast<u32x4*>(p.vf + ft * kFragV);
-            const u32x4 z = {0u, 0u, 0u, 0u}, ones = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
-            if (do_k) {   // the compact K tile: k-step 0 (64 x 16 B), then k-step 1 (64 x 8 B)
-                *reinterpret_cast<u32x4*>(kd + lane * 16) = z;
-                *reinterpret_cast<u32x2*>(kd + 1024 + lane * 8) = u32x2{0u, 0u};
-            }
-            const int r0 = lane, r1 = 64 + lane;   // 16-byte rows of the V^T fragment: [k-step 2][key half 2][25]
-            if (do_v) {
-                vd[r0] = (r0 % 25) == kDH ? ones : z;
-                if (r1 < 100) vd[r1] = (r1 % 25) == kDH ? ones : z;
-            }
+            const u32x4 z = {0u, 0u, 0u, 0u}, one0 = {0x00003f80u, 0u, 0u, 0u};
+            const int r0 = lane, r1 = 64 + lane;   // 16-byte rows of the V^T fragment: [k-step 2][key half 2][25]; slot 0 = first bf16 of row 24
+            vd[r0] = r0 == kDH ? one0 : z;
+            if (r1 < 100) vd[r1] = z;
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    if (do_k && lane < 8) {   // K: (half hh, head hd) -> 12 rotated values = 16 B (k-step 0) + 8 B (k-step 1) of key slot sl
-        const int hd = lane & 3, hh = lane >> 2, head = 4 * w + hd;
+    if (do_k) {   // K: (half hh, head hd) -> 12 rotated values = 16 B (k-step 0) + 8 B (k-step 1), to key slots sl .. 31 (eight lanes per slot)
+        const int hd = lane & 3, hh = (lane >> 2) & 1, head = 4 * w + hd;
         const float* bk = p.bias_k + head * kDH;
         const float* rc = p.rope + (long)len * kRopeRow + 16 * hh;
         float e[12];
@@ -290,9 +330,16 @@ __device__ __forceinline__ void write_bias_slots(const QkvParams& p, int seq, in
             e[2 * pp + 1] = x2 * c + x1 * sn;
         }
         unsigned char* base = p.kf + ((long)(seq * kH + head) * nt + kt) * kFragK;
-        *reinterpret_cast<u32x4*>(base + (hh * 32 + sl) * 16) =
-            u32x4{pack_bf16(e[0], e[1]), pack_bf16(e[2], e[3]), pack_bf16(e[4], e[5]), pack_bf16(e[6], e[7])};
-        *reinterpret_cast<u32x2*>(base + 1024 + (hh * 32 + sl) * 8) = u32x2{pack_bf16(e[8], e[9]), pack_bf16(e[10], e[11])};
+        const u32x4 k0 = u32x4{pack_bf16(e[0], e[1]), pack_bf16(e[2], e[3]), pack_bf16(e[4], e[5]), pack_bf16(e[6], e[7])};
+        const u32x2 k1 = u32x2{pack_bf16(e[8], e[9]), pack_bf16(e[10], e[11])};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int s = sl + (lane >> 3) + 8 * i;
+            if (s < 32) {
+                *reinterpret_cast<u32x4*>(base + (hh * 32 + s) * 16) = k0;
+                *reinterpret_cast<u32x2*>(base + 1024 + (hh * 32 + s) * 8) = k1;
+            }
+        }
     }
     if (do_v && lane < kDH) {   // V^T: row d = lane; key slot sl = register r of lane-half hk: r = (sl & 3) + 4 (sl >> 3)
         const int d = lane;
@@ -354,6 +401,7 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv(const QkvParams p) {
     PanelRows* pr = reinterpret_cast<PanelRows*>(smem);
     unsigned char* panel = smem + sizeof(PanelRows);
     int seq = 0, pos0 = 0, tile0 = 0;
+    unsigned long long valid = ~0ull;   // (FLASH layout) validity of the panel's 64 key positions: every wave takes the ballot for itself
     if (SMALL) {
         setup_rows_linear(pr, (long)blockIdx.x * kPanel, p.nrows, p.mm);
     } else {
@@ -366,10 +414,10 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv(const QkvParams p) {
         // key-validity words of this panel's two tiles for the attention kernel (kernels.h flash_vmask_*): the 64
         // lanes of wave 0 are the panel's 64 positions.  The sequence's last panel also writes the words behind it:
         // zeros, except the bias key's when it starts a tile of its own (len a multiple of 64).
+        valid = panel_key_validity(p, seq, pos0);
         if (wave_id() == 0) {
-            const int lane = lane_id(), len = p.ax.len, pos = pos0 + lane;
-            const float mv = p.mk.at(p.ax.token(seq, pos < len ? pos : len - 1));
-            const unsigned long long bal = __ballot(pos == len || (pos < len && mv != 0.f));
+            const int lane = lane_id(), len = p.ax.len;
+            const unsigned long long bal = valid;
             uint32_t* vm = p.vmask + (long)seq * p.vmask_stride;
             if (lane < 2) vm[tile0 + lane] = (uint32_t)(bal >> (32 * lane));
             if (pn == p.panels_per_seq - 1) {
@@ -419,7 +467,7 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv(const QkvParams p) {
     } else {
         wave_gemm<2, 3, 24, false, 4, true>(panel, kRowB, 0, 0, p.wv + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
         QKV_STAMP(6);
-        epilogue_v_flash(acc, w, sbv, seq, ntile, tile0, p.vf);
+        epilogue_v_flash(acc, w, sbv, seq, ntile, tile0, p.vf, valid);
         if ((int)blockIdx.x - seq * p.panels_per_seq == p.panels_per_seq - 1) {   // the sequence's last panel
             __builtin_amdgcn_sched_barrier(0);   // after this wave's own K / V stores
             write_bias_slots(p, seq, w);
@@ -533,10 +581,10 @@ __global__ __launch_bounds__(512, 1) void k_ln_qkv8(const QkvParams p) {
     const int pos0 = pn * kRows, tile0 = pn * TT;
     stager.load(p, pos0, p.ax.len, threadIdx.x);
     setup_rows_axis(pr, p.ax, seq, pos0, p.mm, kRows);
+    const unsigned long long valid = panel_key_validity(p, seq, pos0);   // (the v waves need it, wherever they are)
     if (wave_id() == 0 && half == 0) {   // key-validity words of this panel's tiles (as k_ln_qkv<false>)
-        const int lane = lane_id(), len = p.ax.len, pos = pos0 + lane;
-        const float mv = p.mk.at(p.ax.token(seq, pos < len ? pos : len - 1));
-        const unsigned long long bal = __ballot(pos == len || (pos < len && mv != 0.f));
+        const int lane = lane_id(), len = p.ax.len;
+        const unsigned long long bal = valid;
         uint32_t* vm = p.vmask + (long)seq * p.vmask_stride;
         if (lane < TT) vm[tile0 + lane] = (uint32_t)(bal >> (32 * lane));
         if (pn == p.panels_per_seq - 1) {
@@ -577,7 +625,7 @@ __global__ __launch_bounds__(512, 1) void k_ln_qkv8(const QkvParams p) {
     }
     if (do_v) {
         wave_gemm<TT, 3, 24, false, 4, true>(panel, kRowB, 0, 0, p.wv + (size_t)(3 * w) * 24 * 64 + lane, 24 * 64, acc);
-        epilogue_v_flash<TT>(acc, w, stage.bias[2], seq, ntile, tile0, p.vf);
+        epilogue_v_flash<TT>(acc, w, stage.bias[2], seq, ntile, tile0, p.vf, valid);
         if (last) {   // the learned bias value, after this wave's own V^T stores
             __builtin_amdgcn_sched_barrier(0);
             write_bias_slots(p, seq, w, false, true, TT);
