@@ -866,6 +866,56 @@ int32_t mdgen_tp_sample(int64_t n_samples, int32_t N, int32_t k, const double* T
                         const double* Bb /* or NULL */, const int32_t* phi /* host, or NULL */, int32_t* paths,
                         double* prob /* or NULL */, void* stream);
 
+/* Cartesian ensemble statistics of protein trajectories (csrc/k_ensemble.hip; mdgen_amd/ensemble.py): superposition, per-atom mean
+ * and covariance (RMSF), all-pairs RMSD and contact counts -- the parts of an AlphaFlow-style ensemble evaluation that scale with
+ * frames x atoms or frames x frames.  Every quantity is defined here by its equation; agreement with AlphaFlow's script and with
+ * mdtraj is unverified.  Units: Angstrom.  The conventions of the mdgen_traj_* entries: coordinates x (F, A, 3) fp32 contiguous
+ * device memory (the sampler's (T, L, 14, 3) is A = 14 L; atom subsets are made by the caller, the kernels are dense); the entries run
+ * on `stream`, every refusal is decided before any launch and leaves the outputs untouched (-1 null pointer, -2 bad shape or value,
+ * -3 workspace too small), no floating-point atomics, every fp sum has a fixed order, two calls give the same bits.  Entries with a
+ * workspace synchronise nothing and read nothing back; mdgen_ens_superpose alone copies w to the host, see there.
+ *
+ * mdgen_ens_superpose: every frame rotated and translated onto `ref` (A, 3) fp32 under the weights w fp32 [A].  3 <= A <= 16384,
+ *   1 <= F <= 2^40.  w is device memory and is CHECKED ON THE HOST: the entry copies it back on `stream` and synchronises that stream
+ *   once before its launch (it cannot be captured into a graph); -2 unless every w is finite and >= 0 and at least 3 are > 0.
+ *   Per frame, in fp64 from the fp32 values:
+ *     cx = sum_a w_a x_a / sum_a w_a,  cr likewise of ref;   H = sum_a w_a (x_a - cx)(ref_a - cr)^T
+ *     R  = the proper rotation (det +1) minimising sum_a w_a |R (x_a - cx) - (ref_a - cr)|^2: the unit quaternion that is the
+ *          eigenvector of the largest eigenvalue of Horn's 4 x 4 matrix N(H), by cyclic Jacobi in fp64 (csrc/ensemble.h).  No 3 x 3
+ *          SVD, no reflection case: a mirror image of ref still gets a proper rotation.
+ *     rmsd = sqrt(sum_a w_a |R (x_a - cx) - (ref_a - cr)|^2 / sum_a w_a), summed directly in fp64 (not from the eigenvalue).
+ *   out_a = R (x_a - cx) + cr in fp32 -- cx, cr and R rounded to fp32, one subtraction, three FMAs ending on cr -- for every atom
+ *   with exists[a] != 0 (uint8 [A]; NULL: every atom); the other atoms are copied unchanged (atom14 padding slots stay zero).
+ *   out (F, A, 3) may be x.  rot fp64 [F][9] row-major and rmsd fp64 [F] may each be NULL.
+ *   Up to A = 256 a wave owns a frame (four frames a workgroup), beyond a workgroup does.
+ *
+ * mdgen_ens_moments: mean fp64 [A][3] and cov fp64 [A][3][3] of every atom over the frames (divided by F), accumulated in fp64 about
+ *   frame 0: u_t = x_t - x_0, mean = x_0 + mean(u), cov = mean(u u^T) - mean(u) mean(u)^T.  F = 1 gives cov = 0 exactly.
+ *   1 <= A <= 16384, 1 <= F <= 2^40.  workspace: mdgen_ens_moments_workspace_bytes(F, A) (partial sums, 18 MB at the most),
+ *   16-byte aligned.  RMSF_a = sqrt(trace cov_a).
+ *
+ * mdgen_ens_pairwise_d2: d2[i][j] = sum over atoms and axes of (xa_i - xb_j)^2 for every frame i of xa (Fa, A, 3) and j of xb
+ *   (Fb, A, 3), in the direct form -- the fp32 difference, then one chain of fp32 FMAs over the 3 A coordinates ascending (the
+ *   distance of mdgen_traj_kmeans_assign).  sums fp64 [2]: sums[0] = sum_ij sqrt((double)d2 / A), sums[1] = sum_ij (double)d2 / A,
+ *   over all Fa Fb pairs (xa == xb: the zero diagonal included).  d2 fp32 [Fa][Fb] may be NULL: then nothing of that size exists
+ *   and the sums have the same bits.  1 <= Fa, Fb <= 2^20 - 1, 1 <= A <= 16384.
+ *   workspace: mdgen_ens_pairwise_d2_workspace_bytes(Fa, Fb, A) (1 MB at the most), 16-byte aligned.
+ *   Tiles of 128 x 64 frames, 24 coordinates staged in LDS at a time, 8 x 4 pairs a thread.
+ *
+ * mdgen_ens_contact_counts: counts[i][j] = #{t : d2_t(i, j) < cutoff2} over ca (F, N, 3), with d2 = fmaf(dz, dz, fmaf(dy, dy, dx dx))
+ *   of the three fp32 differences.  counts int32 [N][N] is zeroed and filled (integer atomics: exact in any order); it is
+ *   symmetric, and its diagonal is F when cutoff2 > 0.  1 <= N <= 4096, 1 <= F <= 2^31 - 1; -2 also: cutoff2 negative, NaN or
+ *   infinite. */
+int32_t mdgen_ens_superpose(int64_t F, int32_t A, const float* x, const float* ref, const float* w, const uint8_t* exists /* or NULL */,
+                            float* out, double* rot /* or NULL */, double* rmsd /* or NULL */, void* stream);
+int32_t mdgen_ens_moments_workspace_bytes(int64_t F, int32_t A, size_t* bytes);
+int32_t mdgen_ens_moments(int64_t F, int32_t A, const float* x, double* mean, double* cov, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int32_t mdgen_ens_pairwise_d2_workspace_bytes(int64_t Fa, int64_t Fb, int32_t A, size_t* bytes);
+int32_t mdgen_ens_pairwise_d2(int64_t Fa, int64_t Fb, int32_t A, const float* xa, const float* xb, float* d2 /* or NULL */,
+                              double* sums, void* workspace, size_t workspace_bytes, void* stream);
+int32_t mdgen_ens_contact_counts(int64_t F, int32_t N, const float* ca, float cutoff2, int32_t* counts, void* stream);
+
 /* Flow-matching training target (transport.py:138-189 `training_losses`, velocity model; path.py:113-135 `plan`
  * with GVPCPlan :177-187 or the linear ICPlan): per sample b with time t[b],
  *   xt = alpha x1 + sigma x0,  ut = alpha' x1 + sigma' x0;   GVP: alpha = sin(pi t/2), sigma = cos(pi t/2);

@@ -34,6 +34,8 @@ EXPORTS = [
     "mdgen_traj_series_acov_workspace_bytes", "mdgen_traj_histograms_xy",
     "mdgen_traj_kmeans_assign", "mdgen_traj_kmeans_step", "mdgen_traj_kmeans_step_workspace_bytes", "mdgen_traj_kmeans_pp",
     "mdgen_traj_kmeans_pp_workspace_bytes", "mdgen_traj_count_matrix", "mdgen_tp_sample",
+    "mdgen_ens_superpose", "mdgen_ens_moments", "mdgen_ens_moments_workspace_bytes", "mdgen_ens_pairwise_d2",
+    "mdgen_ens_pairwise_d2_workspace_bytes", "mdgen_ens_contact_counts",
 ]
 
 
@@ -170,6 +172,12 @@ def _load():
     lib.mdgen_traj_count_matrix.argtypes = [i64, i64, i32, vp, vp, vp, vp]   # n, lag, k | dtraj, counts, dropped
     u32, u64 = C.c_uint32, C.c_uint64
     lib.mdgen_tp_sample.argtypes = [i64, i32, i32, vp, vp, i32, i32, u64, u32, u64, i32, vp, vp, vp, vp, vp, vp]   # n_samples, N, k | Ta, Ba | start, end | seed, stream_id, sample_base | kb, Tb, Bb, phi (host) | paths, prob
+    lib.mdgen_ens_superpose.argtypes = [i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]   # F, A | x, ref, w, exists (or None) | out, rot, rmsd (or None)
+    lib.mdgen_ens_moments_workspace_bytes.argtypes = [i64, i32, C.POINTER(sz)]
+    lib.mdgen_ens_moments.argtypes = [i64, i32, vp, vp, vp, vp, sz, vp]   # F, A | x, mean, cov | workspace, bytes
+    lib.mdgen_ens_pairwise_d2_workspace_bytes.argtypes = [i64, i64, i32, C.POINTER(sz)]
+    lib.mdgen_ens_pairwise_d2.argtypes = [i64, i64, i32, vp, vp, vp, vp, vp, sz, vp]   # Fa, Fb, A | xa, xb, d2 (or None), sums | workspace, bytes
+    lib.mdgen_ens_contact_counts.argtypes = [i64, i32, vp, C.c_float, vp, vp]   # F, N | ca, cutoff2, counts
     lib.mdgen_from_3_points.argtypes = [i64] + [vp] * 6
     lib.mdgen_path_plan.argtypes = [i64, i64, i32] + [vp] * 6
     lib.mdgen_masked_mse.argtypes = [i64, i64] + [vp] * 5

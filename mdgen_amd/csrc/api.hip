@@ -2609,6 +2609,89 @@ extern "C" int32_t mdgen_tp_sample(int64_t n_samples, int32_t N, int32_t k, cons
     return 0;
 }
 
+// Cartesian ensemble statistics (k_ensemble.hip): the same conventions, but for mdgen_ens_superpose's weight check
+static int ens_frames_atoms(int64_t F, int32_t A, int32_t min_atoms) {
+    if (F < 1 || F > kTrajMaxFrames) return fail(-2, "F must be in 1 .. 2^40");
+    if (A < min_atoms || A > kEnsMaxAtoms) return fail(-2, "A must be in %d .. %d", min_atoms, kEnsMaxAtoms);
+    return 0;
+}
+
+extern "C" int32_t mdgen_ens_superpose(int64_t F, int32_t A, const float* x, const float* ref, const float* w, const uint8_t* exists,
+                                       float* out, double* rot, double* rmsd, void* stream) {
+    if (int rc = ens_frames_atoms(F, A, 3)) return rc;
+    NONNULL(x, ref, w, out);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<float> hw((size_t)A);
+    HIPCHK(hipMemcpyAsync(hw.data(), w, (size_t)A * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    int positive = 0;
+    for (int32_t a = 0; a < A; ++a) {
+        if (!(hw[a] >= 0.f) || std::isinf(hw[a])) return fail(-2, "w[%d] = %g: weights must be finite and >= 0", a, (double)hw[a]);
+        positive += hw[a] > 0.f;
+    }
+    if (positive < 3) return fail(-2, "a superposition needs at least 3 atoms of positive weight, got %d", positive);
+    launch_ens_superpose(F, A, x, ref, w, exists, out, rot, rmsd, s);
+    LAUNCHCHK();
+    return 0;
+}
+
+extern "C" int32_t mdgen_ens_moments_workspace_bytes(int64_t F, int32_t A, size_t* bytes) {
+    NONNULL(bytes);
+    if (int rc = ens_frames_atoms(F, A, 1)) return rc;
+    *bytes = ens_moments_workspace_bytes(F, A);
+    return 0;
+}
+
+extern "C" int32_t mdgen_ens_moments(int64_t F, int32_t A, const float* x, double* mean, double* cov, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    if (int rc = ens_frames_atoms(F, A, 1)) return rc;
+    NONNULL(x, mean, cov, workspace);
+    const size_t need = ens_moments_workspace_bytes(F, A);
+    if (workspace_bytes < need) return fail(-3, "workspace too small: %zu < %zu", workspace_bytes, need);
+    if ((uintptr_t)workspace % 16) return fail(-2, "workspace must be 16-byte aligned");
+    launch_ens_moments(F, A, x, mean, cov, workspace, (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
+
+static int ens_pairwise_shape(int64_t Fa, int64_t Fb, int32_t A) {
+    if (Fa < 1 || Fa > kEnsMaxPairFrames || Fb < 1 || Fb > kEnsMaxPairFrames)
+        return fail(-2, "Fa and Fb must be in 1 .. 2^20 - 1 (Fa = %lld, Fb = %lld)", (long long)Fa, (long long)Fb);
+    if (A < 1 || A > kEnsMaxAtoms) return fail(-2, "A must be in 1 .. %d", kEnsMaxAtoms);
+    return 0;
+}
+
+extern "C" int32_t mdgen_ens_pairwise_d2_workspace_bytes(int64_t Fa, int64_t Fb, int32_t A, size_t* bytes) {
+    NONNULL(bytes);
+    if (int rc = ens_pairwise_shape(Fa, Fb, A)) return rc;
+    *bytes = ens_pairwise_workspace_bytes(Fa, Fb);
+    return 0;
+}
+
+extern "C" int32_t mdgen_ens_pairwise_d2(int64_t Fa, int64_t Fb, int32_t A, const float* xa, const float* xb, float* d2, double* sums,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = ens_pairwise_shape(Fa, Fb, A)) return rc;
+    NONNULL(xa, xb, sums, workspace);
+    const size_t need = ens_pairwise_workspace_bytes(Fa, Fb);
+    if (workspace_bytes < need) return fail(-3, "workspace too small: %zu < %zu", workspace_bytes, need);
+    if ((uintptr_t)workspace % 16) return fail(-2, "workspace must be 16-byte aligned");
+    launch_ens_pairwise_d2(Fa, Fb, A, xa, xb, d2, sums, workspace, (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
+
+extern "C" int32_t mdgen_ens_contact_counts(int64_t F, int32_t N, const float* ca, float cutoff2, int32_t* counts, void* stream) {
+    if (F < 1 || F > INT32_MAX) return fail(-2, "F must be in 1 .. 2^31 - 1");
+    if (N < 1 || N > kEnsMaxResidues) return fail(-2, "N must be in 1 .. %d", kEnsMaxResidues);
+    if (!(cutoff2 >= 0.f) || std::isinf(cutoff2)) return fail(-2, "cutoff2 = %g: the squared cutoff must be finite and >= 0", (double)cutoff2);
+    NONNULL(ca, counts);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(counts, 0, (size_t)N * N * sizeof(int32_t), s));
+    launch_ens_contact_counts(F, N, ca, cutoff2, counts, s);
+    LAUNCHCHK();
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // flow-matching training target and loss (forward only)
 // ---------------------------------------------------------------------------------------------

@@ -681,4 +681,23 @@ void launch_tp_sample(long n_samples, int N, int k, const double* Ta, const doub
                       uint32_t stream_id, uint64_t sample_base, int kb, const double* Tb, const double* Bb, const TpPhi& phi,
                       int32_t* paths, double* prob, hipStream_t s);
 
+// Cartesian ensemble statistics (k_ensemble.hip): superposition, per-atom moments, all-pairs squared distances, contact counts
+constexpr int kEnsMaxAtoms = 16384;             // A
+constexpr long kEnsMaxPairFrames = (1l << 20) - 1;   // Fa, Fb of the all-pairs distances
+constexpr int kEnsMaxResidues = 4096;           // N of the contact counts
+constexpr int kEnsWaveAtoms = 256;              // superposition: up to here a wave owns a frame, beyond a workgroup does
+constexpr int kEnsPairTileA = 128;              // all-pairs distances: xa frames of a tile ...
+constexpr int kEnsPairTileB = 64;               // ... xb frames ...
+constexpr int kEnsPairChunk = 24;               // ... and the coordinates staged at a time
+// w is device memory and has passed the caller's check (>= 0, three positive)
+void launch_ens_superpose(long F, int A, const float* x, const float* ref, const float* w, const uint8_t* exists, float* out,
+                          double* rot, double* rmsd, hipStream_t s);
+size_t ens_moments_workspace_bytes(long F, int A);
+void launch_ens_moments(long F, int A, const float* x, double* mean, double* cov, void* ws, hipStream_t s);
+size_t ens_pairwise_workspace_bytes(long Fa, long Fb);
+void launch_ens_pairwise_d2(long Fa, long Fb, int A, const float* xa, const float* xb, float* d2, double* sums, void* ws,
+                            hipStream_t s);
+// counts [N][N] must be zero on entry
+void launch_ens_contact_counts(long F, int N, const float* ca, float cutoff2, int32_t* counts, hipStream_t s);
+
 }  // namespace mdg

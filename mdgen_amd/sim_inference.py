@@ -24,6 +24,11 @@
                      too short for the lag is named on stderr and keeps its torsion entries.  --msm  adds `analyze(msm=True)`'s
                      k-means / MSM / PCCA+ entries (and the tICA ones) with `analyze_peptide_sim`'s --msm_k, --msm_states,
                      --md_msm_lag, --msm_lag, --kmeans_seed, --no_traj_msm; a peptide whose MSM is refused is named likewise.
+                     --ensemble  adds `mdgen_amd.ensemble.analyze_ensemble`'s dict (Cartesian ensemble statistics against the same
+                     MD trajectory) under `analysis[name]["ensemble"]`, on the device tensor the sampler left there;
+  --superpose        each written trajectory (PDB and --npy) is superposed on its own first frame over its existing atoms,
+                     unweighted, on the device before it is formatted (`mdgen_ens_superpose`): the reference's
+                     `traj.superpose(traj)`.  Off by default.
 
 The rollout (sim_inference.py:61-98) stays on the device: each block's last frame becomes the next block's
 conditioning frame through `mdgen_atom14_to_cond` (no D->H->D round trip).  Output, as the reference
@@ -200,11 +205,15 @@ def run(args, model, device, names_seqres, rank=0, world=1, batch_fn=make_group_
         host = all_atom14.cpu().numpy() if args.npy or not all_atom14.is_cuda else None
         for i, n in enumerate(group):
             aat = np.array([restype_order[c] for c in seqres[n]])
-            atom14_to_pdb(all_atom14[i] if all_atom14.is_cuda else host[i], aat, os.path.join(args.out_dir, f"{n}.pdb"))
+            written = all_atom14[i] if all_atom14.is_cuda else host[i]
+            if getattr(args, "superpose", False):
+                from .ensemble import superpose_on_first
+                written = superpose_on_first(all_atom14[i], aat)
+            atom14_to_pdb(written, aat, os.path.join(args.out_dir, f"{n}.pdb"))
             if getattr(args, "xtc", False):
                 write_xtc(os.path.join(args.out_dir, f"{n}.pdb"), os.path.join(args.out_dir, f"{n}.xtc"))
             if args.npy:
-                np.save(os.path.join(args.out_dir, f"{n}.npy"), host[i])
+                np.save(os.path.join(args.out_dir, f"{n}.npy"), written.cpu().numpy() if getattr(args, "superpose", False) else host[i])
             if getattr(args, "analyze", False):
                 from .analyze_peptide_sim import analyze_one, msm_options
                 sync()
@@ -212,6 +221,9 @@ def run(args, model, device, names_seqres, rank=0, world=1, batch_fn=make_group_
                 with_msm = getattr(args, "msm", False)
                 analysis[n] = analyze_one(n, all_atom14[i], arrs[n], aat, tica=getattr(args, "tica", False) or with_msm,
                                           tica_lag=getattr(args, "tica_lag", 1000), msm=msm_options(args) if with_msm else None)
+                if getattr(args, "ensemble", False):
+                    from .ensemble import analyze_ensemble
+                    analysis[n]["ensemble"] = analyze_ensemble(all_atom14[i], arrs[n], aat)
                 sync()
                 analysis_s += time.time() - start
     job_s = max_over_ranks(total_s, dist)
@@ -268,6 +280,12 @@ def build_parser():
     p.add_argument("--msm_lag", type=int, default=10, help="the sampled trajectory's MSM lag in frames (reference: 10)")
     p.add_argument("--kmeans_seed", type=int, default=137, help="seed of the k-means++ uniforms (reference: fixed_seed=137)")
     p.add_argument("--no_traj_msm", action="store_true", help="skip the sampled trajectory's own MSM")
+    p.add_argument("--ensemble", action="store_true",
+                   help="with --analyze: also mdgen_amd.ensemble.analyze_ensemble's dict (RMSF, pairwise RMSD, Gaussian W2, contacts, "
+                        "PCA) under analysis[name]['ensemble']")
+    p.add_argument("--superpose", action="store_true",
+                   help="superpose each written trajectory (PDB and --npy) on its own first frame over its existing atoms, on the "
+                        "device (the reference's traj.superpose(traj))")
     return p
 
 
@@ -289,16 +307,17 @@ def main(argv=None):
         if not dist_.is_initialized():
             dist_.init_process_group("nccl", device_id=device)
         dist = dist_
+    df = pd.read_csv(args.split, index_col="name")
+    names_seqres = {str(n): df.seqres[n] for n in df.index}
     if args.synthetic:
-        cfg = ModelConfig.forward_sim(num_frames=args.num_frames)
+        # (the position table of the seeded model covers the split's longest sequence: 4 for the tetrapeptide splits, as before)
+        cfg = ModelConfig.forward_sim(num_frames=args.num_frames, crop=max([4] + [len(s) for s in names_seqres.values()]))
         model = NewMDGenWrapper(cfg, device=device, precision=args.precision)
         model.model.load_state_dict(synth_state_dict(cfg, 0))
     else:
         if not args.sim_ckpt:
             raise SystemExit("--sim_ckpt is required (or --synthetic)")
         model = NewMDGenWrapper.load_from_checkpoint(args.sim_ckpt, device=device, precision=args.precision)
-    df = pd.read_csv(args.split, index_col="name")
-    names_seqres = {str(n): df.seqres[n] for n in df.index}
     return run(args, model, device, names_seqres, rank, world, sync=torch.cuda.synchronize, dist=dist)
 
 

@@ -16,7 +16,8 @@ ref_kmeans) as plain dicts and arrays, and read back from there when it exists; 
 Without `--msm` the two MD frames are given explicitly (--start_frame, --end_frame) and every path shares them.
 
 The geometry (atom14 -> frames, torsions) runs on the device through the same glue kernel the forward-simulation rollout uses
-(`mdgen_atom14_to_cond`).  No XTC files, no superposition of the written paths."""
+(`mdgen_atom14_to_cond`).  No XTC files.  `--superpose` (off by default) superposes every written path (PDB and --npy) on its own
+first frame over its existing atoms, unweighted, on the device before it is formatted (`mdgen_ens_superpose`)."""
 from __future__ import annotations
 
 import numpy as np
@@ -87,6 +88,8 @@ def build_parser():
     p.add_argument("--npy", action="store_true", help="also write every path as {name}_{idx}.npy")
     add_solver_arguments(p, per="batch of paths")
     p.add_argument("--synthetic", action="store_true")
+    p.add_argument("--superpose", action="store_true", help="superpose each written trajectory (PDB and --npy) on its own first frame over its existing atoms, on the device "
+                        "(the reference's traj.superpose(traj))")
     return p
 
 
@@ -166,6 +169,9 @@ def run(args, model, device, names_seqres, rank=0, world=1):
                 st = model.last_stats
                 print(f"{name} batch {i}: dopri5 {st['nfe']} network evaluations ({st['accepted']} accepted, "
                       f"{st['rejected']} rejected steps)")
+            if getattr(args, "superpose", False):
+                from .ensemble import superpose_on_first
+                atom14s = torch.stack([superpose_on_first(a, aat) for a in atom14s])
             paths = atom14s if atom14s.is_cuda else atom14s.cpu().numpy()   # (a device tensor is formatted on the device, pdb.py)
             for j in range(args.batch_size):
                 idx = i * args.batch_size + j

@@ -8,7 +8,9 @@
                      --num_steps steps (default 24 / 16 / 12 = 48 network evaluations);
   --precision {bf16,fp32}, --npy (also save the sampled array), --xtc (as `sim_inference.py`: refused before sampling
                      where mdtraj is missing);
-  --synthetic        seeded weights instead of --ckpt, with --num_frames T / --cond_interval c (a checkpoint supplies both).
+  --synthetic        seeded weights instead of --ckpt, with --num_frames T / --cond_interval c (a checkpoint supplies both);
+  --superpose        the written trajectory (PDB and --npy) is superposed on its own first frame over its existing atoms, on the
+                     device before it is formatted (`mdgen_ens_superpose`; the reference's `traj.superpose(traj)`).  Off by default.
 
 Under `torch.distributed.run` the names of the split are sharded over the ranks (`sim_inference.dist_env` / `select_names`).
 
@@ -114,9 +116,12 @@ def run(args, model, device, names_seqres, rank=0, world=1, sync=None):
         total_frames, total_s = total_frames + nfr, total_s + dur
         print(f"{name}: {nfr / dur:.1f} frames/s ({dur:.3f} s, {windows['trans'].shape[0]} windows of {T} frames, "
               f"batch {args.batch_size})")
+        aat = np.array([restype_order[ch] for ch in names_seqres[name]])
+        if getattr(args, "superpose", False):
+            from .ensemble import superpose_on_first
+            atom14 = superpose_on_first(atom14, aat)
         # a device tensor is formatted on the device (pdb.py); the host copy is made only for what needs one
         host = atom14.cpu().numpy() if args.npy or not atom14.is_cuda else None
-        aat = np.array([restype_order[ch] for ch in names_seqres[name]])
         path = os.path.join(args.out_dir, f"{name}.pdb")
         atom14_to_pdb(atom14 if atom14.is_cuda else host, aat, path)
         if getattr(args, "xtc", False):
@@ -145,6 +150,8 @@ def build_parser():
     p.add_argument("--num_frames", type=int, default=None, help="frames per window (only with --synthetic; default 1000)")
     p.add_argument("--cond_interval", type=int, default=None,
                    help="frames between key frames (only with --synthetic; default 100)")
+    p.add_argument("--superpose", action="store_true", help="superpose each written trajectory (PDB and --npy) on its own first frame over its existing atoms, on the device "
+                        "(the reference's traj.superpose(traj))")
     return p
 
 

@@ -20,13 +20,19 @@
                 vectorised NumPy restatement of tests/tps_ref.py with `msm.tp_likelihood` on the same box; then one
                 `analyze_peptide_tps.analyze_tps` peptide at the reference's size: 1000 paths x 100 frames, a 1e6-frame replica,
                 seven replica lengths (wall; `metadata_wall_ms`: `tps_inference.build_metadata` of the 1e6-frame MD trajectory)
+  ensemble      the `mdgen_ens_*` kernels and `analyze_ensemble` at the ATLAS size -- 250 sampled frames against 30 003 MD frames of
+                256 residues (3 584 atom14 slots, 256 C-alphas) -- and `mdgen_ens_superpose` at 1e6 frames x 56 atoms.  Beside
+                `mdgen_ens_pairwise_d2` the plain torch expression on the same box: `torch.cdist` on [F, 3A] in chunks of 2 048
+                rows with the same two fp64 sums, in its matrix-product mode (`torch_cdist_mm_ms`) and in its direct mode
+                (`torch_cdist_direct_ms`); beside `mdgen_ens_contact_counts` a chunked torch comparison (512 frames at a time).
+                Not part of `--leg all` (it allocates 1.3 GB of coordinates).
 
 Beside each of the last four, `numpy_ms`: the same definition in NumPy fp64 on the host, the copy of the device array to the host
 included (moments: cos / sin, three matrix products and two sums; project: cos / sin, the centred product; series: np.fft; tica:
 the tICA entries -- moments, solver, two projections, four histograms, two autocovariances -- from the angles).
 
     python scripts/analysis_bench.py [--leg all|dihedrals|histograms|acov|fft|numpy|moments|project|series|tica|kmeans_pp|kmeans_step|kmeans_fit|
-                                           count_matrix|msm|tps] [--size sampler|md|both]
+                                           count_matrix|msm|tps|ensemble] [--size sampler|md|both]
                                      [--reps 5]
 
 acov reports multiply-adds (2 n' (K + 1) NF with n' the mean number of terms per lag) over time and that rate's share of the
@@ -315,11 +321,94 @@ def tps_legs(a, A, dev, want):
                       "wall_ms_median": med, "without_replica_wall_ms_best": nbest, "metadata_wall_ms": meta_ms}))
 
 
+def ensemble_legs(a, dev):
+    from mdgen_amd import ensemble as E
+    L, T, F = 256, 250, 30003
+    g = torch.Generator(device=dev).manual_seed(7)
+    aat = np.random.default_rng(7).integers(0, 20, size=L)
+    w, ex = E.fit_weights(aat, "heavy")
+    mask = torch.from_numpy(ex.reshape(L, 14, 1).astype(np.float32)).to(dev)
+    idx = torch.arange(L, device=dev, dtype=torch.float32)
+    ca = torch.stack([2.3 * torch.cos(idx * 1.75), 2.3 * torch.sin(idx * 1.75), 1.5 * idx], -1)
+    ca = ca + torch.cumsum(torch.randn(L, 3, generator=g, device=dev) * 2.0, 0)        # a wandering chain: ~30 A across
+    base = ca[:, None, :] + torch.randn(L, 14, 3, generator=g, device=dev) * 1.8
+    md = (base + torch.randn(F, L, 1, 3, generator=g, device=dev) * 1.0 + torch.randn(F, L, 14, 3, generator=g, device=dev) * 0.3) * mask
+    tr = (base + torch.randn(T, L, 1, 3, generator=g, device=dev) * 0.8 + torch.randn(T, L, 14, 3, generator=g, device=dev) * 0.3) * mask
+    x = md.reshape(F, L * 14, 3)
+    wd, exd = torch.from_numpy(w).to(dev), torch.from_numpy(ex).to(dev)
+    out = torch.empty_like(x)
+    best, med = timed_ms(lambda: E.superpose_into(x, x[0], wd, exd, out), a.reps)
+    print(json.dumps({"leg": "ensemble", "what": "superpose", "F": F, "A": L * 14, "ms_best": best, "ms_median": med,
+                      "GB_per_s": 2 * x.numel() * 4 / best / 1e6}))
+    mean, cov = torch.empty(L * 14, 3, dtype=torch.float64, device=dev), torch.empty(L * 14, 3, 3, dtype=torch.float64, device=dev)
+    ws = torch.empty(E.moments_workspace_bytes(F, L * 14), dtype=torch.uint8, device=dev)
+    best, med = timed_ms(lambda: E.moments_into(out, mean, cov, ws), a.reps)
+    print(json.dumps({"leg": "ensemble", "what": "moments", "F": F, "A": L * 14, "ms_best": best, "ms_median": med,
+                      "GB_per_s": x.numel() * 4 / best / 1e6}))
+    del out
+    small = torch.randn(1000000, 56, 3, generator=g, device=dev) * 5
+    w56, o56 = torch.ones(56, device=dev), torch.empty(1000000, 56, 3, device=dev)
+    best, med = timed_ms(lambda: E.superpose_into(small, small[0], w56, None, o56), a.reps)
+    print(json.dumps({"leg": "ensemble", "what": "superpose", "F": 1000000, "A": 56, "ms_best": best, "ms_median": med,
+                      "GB_per_s": 2 * small.numel() * 4 / best / 1e6}))
+    del small, o56
+    ca_md, ca_tr = md[:, :, 1].contiguous(), tr[:, :, 1].contiguous()
+    sums = torch.empty(2, dtype=torch.float64, device=dev)
+    c2 = float(E.cutoff2_f32(8.0))
+
+    def cdist_sums(xa, xb, mode):
+        A_ = xa.shape[1]
+        fa, fb = xa.reshape(len(xa), -1), xb.reshape(len(xb), -1)
+        s0 = torch.zeros((), dtype=torch.float64, device=dev)
+        s1 = torch.zeros((), dtype=torch.float64, device=dev)
+        for i in range(0, len(fa), 2048):
+            d = torch.cdist(fa[i:i + 2048], fb, compute_mode=mode)
+            s0 += (d.double() / np.sqrt(A_)).sum()
+            s1 += (d.double() ** 2 / A_).sum()
+        return torch.stack([s0, s1])
+    wide = (ca_md.repeat(1, 4, 1) + torch.randn(F, 1024, 3, generator=g, device=dev) * 0.5).contiguous()
+    for name, xa, xb in (("sampled x md", ca_tr, ca_md), ("md x md", ca_md, ca_md), ("md x md, A = 1024", wide, wide)):
+        Fa, Fb, A_ = len(xa), len(xb), xa.shape[1]
+        ws = torch.empty(E.pairwise_workspace_bytes(Fa, Fb, A_), dtype=torch.uint8, device=dev)
+        best, med = timed_ms(lambda: E.pairwise_d2_into(xa, xb, None, sums, ws), a.reps)
+        got = sums.cpu().numpy()
+        rate = float(Fa) * Fb * 3 * A_ / (best * 1e-3)
+        rec = {"leg": "ensemble", "what": "pairwise_d2", "shape": name, "Fa": Fa, "Fb": Fb, "A": A_, "ms_best": best, "ms_median": med,
+               "fma_per_s": rate, "share_of_fp32_vector_peak": rate / FMA_PEAK}
+        for key, mode in (("torch_cdist_mm_ms", "use_mm_for_euclid_dist"), ("torch_cdist_direct_ms", "donot_use_mm_for_euclid_dist")):
+            tb, _ = timed_ms(lambda: cdist_sums(xa, xb, mode), max(a.reps // 2, 1))
+            ref = cdist_sums(xa, xb, mode).cpu().numpy()
+            rec[key] = tb
+            rec[key.replace("_ms", "_rel_diff")] = float(np.abs(ref - got).max() / np.abs(got).max())
+        print(json.dumps(rec))
+    del wide
+    counts = torch.empty(L, L, dtype=torch.int32, device=dev)
+
+    def torch_contacts(ca_):
+        acc = torch.zeros(L, L, dtype=torch.int64, device=dev)
+        for i in range(0, len(ca_), 512):
+            c = ca_[i:i + 512]
+            d = c[:, :, None, :] - c[:, None, :, :]
+            acc += ((d * d).sum(-1) < c2).sum(0)
+        return acc
+    for name, ca_ in (("sampled", ca_tr), ("md", ca_md)):
+        best, med = timed_ms(lambda: E.contact_counts_into(ca_, 8.0, counts), a.reps)
+        tb, _ = timed_ms(lambda: torch_contacts(ca_), max(a.reps // 2, 1))
+        diff = int((torch_contacts(ca_) - counts).abs().max())
+        print(json.dumps({"leg": "ensemble", "what": "contact_counts", "shape": name, "F": len(ca_), "N": L, "ms_best": best,
+                          "ms_median": med, "torch_chunked_ms": tb, "max_count_diff_to_torch": diff,
+                          "contact_share": float(counts.double().mean() / len(ca_))}))
+    for pca in (False, True):
+        best, med = wall_ms(lambda: E.analyze_ensemble(tr, md, aat, pca=pca), max(a.reps // 2, 1))
+        print(json.dumps({"leg": "ensemble", "what": "analyze_ensemble", "pca": pca, "T": T, "F": F, "L": L, "wall_ms_best": best,
+                          "wall_ms_median": med}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--leg", default="all", choices=["all", "dihedrals", "histograms", "acov", "fft", "numpy", "moments", "project",
                                                      "series", "tica", "kmeans_pp", "kmeans_step", "kmeans_fit", "count_matrix",
-                                                     "msm", "tps"])
+                                                     "msm", "tps", "ensemble"])
     ap.add_argument("--size", default="both", choices=["sampler", "md", "both"])
     ap.add_argument("--reps", type=int, default=5)
     a = ap.parse_args()
@@ -327,6 +416,8 @@ def main():
         raise SystemExit("analysis_bench needs the GPU: there is nothing to time without one")
     from mdgen_amd import analysis as A
     dev = torch.device("cuda")
+    if a.leg == "ensemble":
+        return ensemble_legs(a, dev)
     want = lambda leg: a.leg in ("all", leg)   # noqa: E731
     sizes = [s for s in SIZES if a.size in ("both", s)]
     F = 100000
