@@ -867,8 +867,8 @@ int32_t mdgen_tp_sample(int64_t n_samples, int32_t N, int32_t k, const double* T
                         double* prob /* or NULL */, void* stream);
 
 /* Cartesian ensemble statistics of protein trajectories (csrc/k_ensemble.hip; mdgen_amd/ensemble.py): superposition, per-atom mean
- * and covariance (RMSF), all-pairs RMSD and contact counts -- the parts of an AlphaFlow-style ensemble evaluation that scale with
- * frames x atoms or frames x frames.  Every quantity is defined here by its equation; agreement with AlphaFlow's script and with
+ * and covariance (RMSF), all-pairs RMSD, contact counts and Shrake-Rupley surface counts -- the parts of an AlphaFlow-style ensemble
+ * evaluation that scale with frames x atoms or frames x frames.  Every quantity is defined here by its equation; agreement with AlphaFlow's script and with
  * mdtraj is unverified.  Units: Angstrom.  The conventions of the mdgen_traj_* entries: coordinates x (F, A, 3) fp32 contiguous
  * device memory (the sampler's (T, L, 14, 3) is A = 14 L; atom subsets are made by the caller, the kernels are dense); the entries run
  * on `stream`, every refusal is decided before any launch and leaves the outputs untouched (-1 null pointer, -2 bad shape or value,
@@ -905,7 +905,23 @@ int32_t mdgen_tp_sample(int64_t n_samples, int32_t N, int32_t k, const double* T
  * mdgen_ens_contact_counts: counts[i][j] = #{t : d2_t(i, j) < cutoff2} over ca (F, N, 3), with d2 = fmaf(dz, dz, fmaf(dy, dy, dx dx))
  *   of the three fp32 differences.  counts int32 [N][N] is zeroed and filled (integer atomics: exact in any order); it is
  *   symmetric, and its diagonal is F when cutoff2 > 0.  1 <= N <= 4096, 1 <= F <= 2^31 - 1; -2 also: cutoff2 negative, NaN or
- *   infinite. */
+ *   infinite.
+ *
+ * mdgen_ens_sasa_counts: Shrake-Rupley.  counts[f][i] = the number of the P sphere points of atom i of frame f that no other atom
+ *   buries; the solvent-accessible area of the atom is 4 pi R_i^2 counts / P.  counts int32 [F][A] device memory, every entry
+ *   written.  radius fp32 [A] and points fp32 [P][3] are HOST arrays (as phi of mdgen_tp_sample): the entry checks them and stages
+ *   them on `stream` into the workspace, with R and R2 below; pageable memory, which the runtime has read when the entry returns.
+ *   1 <= A <= 16384, 1 <= P <= 4096, 1 <= F <= 2^31 - 1; -2 also: probe or a radius NaN or outside 0 .. 16, a point that is not
+ *   finite or whose norm (in fp64) is further than 1e-3 from 1.  workspace: mdgen_ens_sasa_workspace_bytes(A, P), 16-byte aligned.
+ *     existence   an atom with radius[a] == 0 does not exist: its count is 0 and it buries nothing (atom14 padding slots hold zeros
+ *                 and are no atoms at the origin).  Otherwise R_a = radius[a] + probe (one fp32 add), R2_a = R_a R_a (one fp32
+ *                 multiply, rounded).
+ *     point k of atom i   q = (fmaf(R_i, u_kx, c_ix), fmaf(R_i, u_ky, c_iy), fmaf(R_i, u_kz, c_iz))
+ *     buried      iff some existing j != i has d2 < R2_j, d2 = fmaf(dz, dz, fmaf(dy, dy, dx dx)) of the three fp32 differences
+ *                 q - c_j: the distance of mdgen_ens_contact_counts.
+ *     counts[f][i] = #{k : point k of atom i is not buried}.  Integers, independent of any order: two calls give the same bits.
+ *   A wave owns an atom: it compacts the atoms within reach (|c_i - c_j| < R_i + R_j, kept with slack: the counts are those of the
+ *   definition above) into a list of 512 in LDS, and tests every point against all atoms when more are within reach. */
 int32_t mdgen_ens_superpose(int64_t F, int32_t A, const float* x, const float* ref, const float* w, const uint8_t* exists /* or NULL */,
                             float* out, double* rot /* or NULL */, double* rmsd /* or NULL */, void* stream);
 int32_t mdgen_ens_moments_workspace_bytes(int64_t F, int32_t A, size_t* bytes);
@@ -915,6 +931,10 @@ int32_t mdgen_ens_pairwise_d2_workspace_bytes(int64_t Fa, int64_t Fb, int32_t A,
 int32_t mdgen_ens_pairwise_d2(int64_t Fa, int64_t Fb, int32_t A, const float* xa, const float* xb, float* d2 /* or NULL */,
                               double* sums, void* workspace, size_t workspace_bytes, void* stream);
 int32_t mdgen_ens_contact_counts(int64_t F, int32_t N, const float* ca, float cutoff2, int32_t* counts, void* stream);
+int32_t mdgen_ens_sasa_workspace_bytes(int32_t A, int32_t P, size_t* bytes);
+int32_t mdgen_ens_sasa_counts(int64_t F, int32_t A, int32_t P, const float* x, const float* radius /* host */,
+                              const float* points /* host */, float probe, int32_t* counts, void* workspace, size_t workspace_bytes,
+                              void* stream);
 
 /* Flow-matching training target (transport.py:138-189 `training_losses`, velocity model; path.py:113-135 `plan`
  * with GVPCPlan :177-187 or the linear ICPlan): per sample b with time t[b],

@@ -35,7 +35,7 @@ EXPORTS = [
     "mdgen_traj_kmeans_assign", "mdgen_traj_kmeans_step", "mdgen_traj_kmeans_step_workspace_bytes", "mdgen_traj_kmeans_pp",
     "mdgen_traj_kmeans_pp_workspace_bytes", "mdgen_traj_count_matrix", "mdgen_tp_sample",
     "mdgen_ens_superpose", "mdgen_ens_moments", "mdgen_ens_moments_workspace_bytes", "mdgen_ens_pairwise_d2",
-    "mdgen_ens_pairwise_d2_workspace_bytes", "mdgen_ens_contact_counts",
+    "mdgen_ens_pairwise_d2_workspace_bytes", "mdgen_ens_contact_counts", "mdgen_ens_sasa_workspace_bytes", "mdgen_ens_sasa_counts",
 ]
 
 
@@ -178,6 +178,8 @@ def _load():
     lib.mdgen_ens_pairwise_d2_workspace_bytes.argtypes = [i64, i64, i32, C.POINTER(sz)]
     lib.mdgen_ens_pairwise_d2.argtypes = [i64, i64, i32, vp, vp, vp, vp, vp, sz, vp]   # Fa, Fb, A | xa, xb, d2 (or None), sums | workspace, bytes
     lib.mdgen_ens_contact_counts.argtypes = [i64, i32, vp, C.c_float, vp, vp]   # F, N | ca, cutoff2, counts
+    lib.mdgen_ens_sasa_workspace_bytes.argtypes = [i32, i32, C.POINTER(sz)]
+    lib.mdgen_ens_sasa_counts.argtypes = [i64, i32, i32, vp, vp, vp, C.c_float, vp, vp, sz, vp]   # F, A, P | x, radius (host), points (host), probe | counts | workspace, bytes
     lib.mdgen_from_3_points.argtypes = [i64] + [vp] * 6
     lib.mdgen_path_plan.argtypes = [i64, i64, i32] + [vp] * 6
     lib.mdgen_masked_mse.argtypes = [i64, i64] + [vp] * 5

@@ -7,10 +7,13 @@
   --ref_suffixes ... the replicas concatenated as the MD ensemble, e.g. `_R1 _R2 _R3`; its first frame is the reference structure;
   --pdb_id ...       the proteins (default: every name of the split);
   --fit heavy|ca     superpose over the existing heavy atoms (default) or the C-alphas;  --cutoff A  contact cutoff (8);
-  --no_pca           without the PCA entries;  --save  pickle {name: result} to `{pdbdir}/ensemble.pkl`.
+  --no_pca           without the PCA entries;  --save  pickle {name: result} to `{pdbdir}/ensemble.pkl`;
+  --sasa             with the solvent-accessible-surface entries (residue areas, exposure probabilities, exposed-residue Jaccard,
+                     exposure mutual information and its Spearman correlation), under --probe A (2.8), --sasa_points N (960),
+                     --sasa_threshold A^2 (2.0) and --sasa_atoms sidechain|all.
 
 A protein whose files are missing or whose shapes disagree is named on stderr and skipped.  The result is a dict of plain NumPy
-arrays and floats per protein (it loads without this package).  No plots, no XTC files, no solvent-accessible surface area."""
+arrays and floats per protein (it loads without this package).  No plots, no XTC files."""
 from __future__ import annotations
 
 import argparse
@@ -35,7 +38,30 @@ def build_parser():
     p.add_argument("--cutoff", type=float, default=8.0)
     p.add_argument("--no_pca", action="store_true")
     p.add_argument("--save", action="store_true")
+    add_sasa_arguments(p)
     return p
+
+
+def add_sasa_arguments(p):
+    """--sasa and its options, for every command line that calls `analyze_ensemble`."""
+    p.add_argument("--sasa", action="store_true", help="also the solvent-accessible-surface entries of analyze_ensemble")
+    p.add_argument("--probe", type=float, default=2.8, help="probe radius in Angstrom")
+    p.add_argument("--sasa_points", type=int, default=960, help="sphere points per atom")
+    p.add_argument("--sasa_threshold", type=float, default=2.0, help="a residue is exposed above this area (A^2)")
+    p.add_argument("--sasa_atoms", choices=["sidechain", "all"], default="sidechain")
+
+
+def sasa_options(args) -> dict:
+    """The keyword arguments `analyze_ensemble` takes for --sasa: none without it.  Bad values end the run before any file is read."""
+    if not getattr(args, "sasa", False):
+        return {}
+    if not (np.isfinite(args.probe) and 0 <= args.probe <= 16):
+        raise SystemExit(f"error: --probe must be in 0 .. 16, got {args.probe}")
+    if not 1 <= args.sasa_points <= 4096:
+        raise SystemExit(f"error: --sasa_points must be in 1 .. 4096, got {args.sasa_points}")
+    if not np.isfinite(args.sasa_threshold):
+        raise SystemExit(f"error: --sasa_threshold must be finite, got {args.sasa_threshold}")
+    return dict(sasa=True, probe=args.probe, n_points=args.sasa_points, sasa_threshold=args.sasa_threshold, sasa_atoms=args.sasa_atoms)
 
 
 def load_protein(args, name, seq):
@@ -73,6 +99,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if not (np.isfinite(args.cutoff) and args.cutoff > 0):
         raise SystemExit(f"error: --cutoff must be positive, got {args.cutoff}")
+    sasa = sasa_options(args)
     seqres = read_split(args.split)
     names = list(args.pdb_id) if args.pdb_id else list(seqres)
     unknown = [n for n in names if n not in seqres]
@@ -86,11 +113,12 @@ def main(argv=None):
             print(f"{n}: skipped: {got}", file=sys.stderr)
             continue
         traj, ref, aat = got
-        out[n] = ensemble.analyze_ensemble(traj, ref, aat, fit=args.fit, cutoff=args.cutoff, pca=not args.no_pca)
+        out[n] = ensemble.analyze_ensemble(traj, ref, aat, fit=args.fit, cutoff=args.cutoff, pca=not args.no_pca, **sasa)
         r = out[n]
         print(f"{n}: {traj.shape[0]} frames against {ref.shape[0]}: RMSF r {r['rmsf_pearson']:.3f}, pairwise RMSD "
               f"{r['mean_pairwise_rmsd']:.2f} (MD {r['ref_mean_pairwise_rmsd']:.2f}), RMWD {r['emd_total']:.2f}, weak contacts J "
-              f"{r['weak_contacts_jaccard']:.2f}, transient {r['transient_contacts_jaccard']:.2f}")
+              f"{r['weak_contacts_jaccard']:.2f}, transient {r['transient_contacts_jaccard']:.2f}"
+              + (f", exposed residues J {r['exposed_residue_jaccard']:.2f}, exposure MI rho {r['exposed_mi_spearman']:.2f}" if sasa else ""))
     print(f"{len(out)} of {len(names)} proteins analysed")
     if args.save:
         with open(os.path.join(args.pdbdir, "ensemble.pkl"), "wb") as f:

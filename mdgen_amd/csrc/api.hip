@@ -2692,6 +2692,52 @@ extern "C" int32_t mdgen_ens_contact_counts(int64_t F, int32_t N, const float* c
     return 0;
 }
 
+static int ens_sasa_shape(int32_t A, int32_t P) {
+    if (A < 1 || A > kEnsMaxAtoms) return fail(-2, "A must be in 1 .. %d", kEnsMaxAtoms);
+    if (P < 1 || P > kEnsSasaMaxPoints) return fail(-2, "P must be in 1 .. %d", kEnsSasaMaxPoints);
+    return 0;
+}
+
+extern "C" int32_t mdgen_ens_sasa_workspace_bytes(int32_t A, int32_t P, size_t* bytes) {
+    NONNULL(bytes);
+    if (int rc = ens_sasa_shape(A, P)) return rc;
+    *bytes = ens_sasa_workspace_bytes(A, P);
+    return 0;
+}
+
+// radius and points are host arrays, checked here and staged into the workspace with R = radius + probe and R2 = R R
+extern "C" int32_t mdgen_ens_sasa_counts(int64_t F, int32_t A, int32_t P, const float* x, const float* radius, const float* points,
+                                         float probe, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+    if (F < 1 || F > INT32_MAX) return fail(-2, "F must be in 1 .. 2^31 - 1");
+    if (int rc = ens_sasa_shape(A, P)) return rc;
+    if (!(probe >= 0.f && probe <= kEnsSasaMaxRadius)) return fail(-2, "probe = %g: the probe radius must be in 0 .. 16", (double)probe);
+    NONNULL(x, radius, points, counts, workspace);
+    const size_t need = ens_sasa_workspace_bytes(A, P);
+    if (workspace_bytes < need) return fail(-3, "workspace too small: %zu < %zu", workspace_bytes, need);
+    if ((uintptr_t)workspace % 16) return fail(-2, "workspace must be 16-byte aligned");
+    std::vector<float> host(need / sizeof(float), 0.f);
+    float *R = host.data(), *R2 = R + A, *pts = R2 + A;
+    for (int32_t a = 0; a < A; ++a) {
+        const float r = radius[a];
+        if (!(r >= 0.f && r <= kEnsSasaMaxRadius)) return fail(-2, "radius[%d] = %g: a radius must be in 0 .. 16 (0: no atom)", a, (double)r);
+        R[a] = r == 0.f ? 0.f : r + probe;   // one fp32 add, one fp32 multiply
+        R2[a] = R[a] * R[a];
+    }
+    for (int32_t k = 0; k < P; ++k) {
+        const double u0 = points[3 * k], u1 = points[3 * k + 1], u2 = points[3 * k + 2];
+        const double norm = std::sqrt(u0 * u0 + u1 * u1 + u2 * u2);
+        if (!(std::fabs(norm - 1.0) <= 1e-3))
+            return fail(-2, "points[%d] = (%g, %g, %g) is not a unit vector (|u| = %g)", k, u0, u1, u2, norm);
+        for (int ax = 0; ax < 3; ++ax) pts[(size_t)ax * P + k] = points[3 * k + ax];
+    }
+    hipStream_t s = (hipStream_t)stream;
+    // (pageable host memory: the runtime has taken the bytes when the call returns)
+    HIPCHK(hipMemcpyAsync(workspace, host.data(), need, hipMemcpyHostToDevice, s));
+    launch_ens_sasa_counts(F, A, P, x, (const float*)workspace, counts, s);
+    LAUNCHCHK();
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // flow-matching training target and loss (forward only)
 // ---------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // k_ensemble.hip -- Cartesian ensemble statistics of protein trajectories (mdgen_ens_superpose / _moments / _pairwise_d2 /
-// _contact_counts; mdgen_amd/ensemble.py): everything that scales with frames x atoms or frames x frames.  The 3 x 3 matrix
+// _contact_counts / _sasa_counts; mdgen_amd/ensemble.py): everything that scales with frames x atoms or frames x frames.  The 3 x 3 matrix
 // square roots of the Gaussian Wasserstein distance, the PCA eigenproblem and the assignment problem are the host's.
 //   k_superpose<W>   W waves own a frame (W = 1: four frames a workgroup, A <= 256; W = 4: a workgroup a frame).  Three passes over
 //                    the frame's atoms, all sums fp64: the weighted centroids, H about them, then the rotated atoms and the rmsd.
@@ -17,6 +17,11 @@
 //   k_contacts       workgroup (64 x 64 block of residue pairs on or above the diagonal, split of the frames): 8 frames of the
 //                    two residue blocks pass through LDS axis-major, a thread counts its 4 x 4 pairs in registers and adds them
 //                    to counts[i][j] (and counts[j][i] off the diagonal blocks) with integer atomics: exact in any order
+//   k_sasa           Shrake-Rupley counts (mdgen_ens_sasa_counts): a wave owns an (frame, atom).  Its lanes scan the frame's atoms 64
+//                    at a time and compact those within reach -- |c_i - c_j| < R_i + R_j, with slack -- by ballot into the wave's
+//                    LDS list of (x, y, z, R2), 512 entries; then a lane owns every 64th sphere point, tests the neighbour that
+//                    buried its previous point first and leaves the list at the first burying one.  A list that would overflow
+//                    is dropped whole and every point is tested against all atoms.  Integers: exact in any order
 // No floating-point atomics: every fp sum has a fixed order, two calls give the same bits.
 #include "ensemble.h"
 #include "kernels.h"
@@ -444,6 +449,112 @@ void launch_ens_contact_counts(long F, int N, const float* ca, float cutoff2, in
     const long chunk = (F + S - 1) / S;
     S = (F + chunk - 1) / chunk;
     hipLaunchKernelGGL(k_contacts, dim3(pairs, (unsigned)S), dim3(256), 0, s, F, N, ca, cutoff2, chunk, nb, counts);
+}
+
+// ---- Shrake-Rupley solvent-accessible surface ------------------------------------------------------------------------
+constexpr int kSasaWaves = 4;                // waves of a workgroup, an atom each
+constexpr long kSasaMaxGroups = 1l << 20;
+// The cull keeps j when |c_i - c_j| <= (R_i + R_j) kSasaCullScale + kSasaCullAbs (max |coordinate| + 32).  A point of i is within
+// R_i (1 + 1e-3) (the unit tolerance of the points) + sqrt(3) 2^-24 max|q| (its rounding) of c_i, and a burying j within
+// R_j (1 + a few 2^-24) of the point: every such j is closer to i than the cut, whose own fp32 rounding is a few 2^-24 relative.
+constexpr float kSasaCullScale = 1.002f;
+constexpr float kSasaCullAbs = 4e-7f;
+
+// workspace, fp32: R [A] (0: no atom), R2 [A], then the points axis-major, px [P], py [P], pz [P]
+size_t ens_sasa_workspace_bytes(int A, int P) { return (((size_t)2 * A + (size_t)3 * P) * sizeof(float) + 15) / 16 * 16; }
+
+// writes made by the wave's lanes to its own LDS list are read by its other lanes from here on (LDS is in order within a wave)
+__device__ __forceinline__ void sasa_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ bool sasa_buries(float qx, float qy, float qz, float4 nb) {
+    const float dx = qx - nb.x, dy = qy - nb.y, dz = qz - nb.z;
+    return fmaf(dz, dz, fmaf(dy, dy, dx * dx)) < nb.w;
+}
+
+__global__ __launch_bounds__(256) void k_sasa(long F, int A, int P, const float* __restrict__ x, const float* __restrict__ R,
+                                              const float* __restrict__ R2, const float* __restrict__ px,
+                                              const float* __restrict__ py, const float* __restrict__ pz, int* __restrict__ counts) {
+    __shared__ float4 lists[kSasaWaves][kEnsSasaMaxNeighbours];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float4* list = lists[wave];
+    const long total = F * (long)A;
+    // (no workgroup barrier below: the waves' trip counts differ)
+    for (long item = (long)blockIdx.x * kSasaWaves + wave; item < total; item += (long)gridDim.x * kSasaWaves) {
+        const long f = item / A;
+        const int i = (int)(item - f * A);
+        const float Ri = R[i];
+        if (Ri == 0.f) {                     // no atom here (the same for every lane)
+            if (lane == 0) counts[item] = 0;
+            continue;
+        }
+        const float* xf = x + f * A * 3;
+        const float cx = xf[3 * i], cy = xf[3 * i + 1], cz = xf[3 * i + 2];
+        const float mi = fmaxf(fmaxf(fabsf(cx), fabsf(cy)), fabsf(cz));
+        // the atoms that can bury a point of i, compacted by ballot in atom order; more than the list holds: none is kept and
+        // every point is tested against all atoms instead
+        int cnt = 0;
+        bool over = false;
+        for (int j0 = 0; j0 < A; j0 += 64) {
+            const int j = j0 + lane;
+            bool keep = false;
+            float4 v = {0.f, 0.f, 0.f, 0.f};
+            if (j < A) {
+                const float Rj = R[j];
+                v.x = xf[3 * j], v.y = xf[3 * j + 1], v.z = xf[3 * j + 2], v.w = R2[j];
+                const float dx = cx - v.x, dy = cy - v.y, dz = cz - v.z;
+                const float dd = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+                const float m = fmaxf(mi, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fabsf(v.z)));
+                const float cut = fmaf(Ri + Rj, kSasaCullScale, kSasaCullAbs * (m + 32.f));
+                keep = Rj != 0.f && j != i && !(dd > cut * cut);   // (a NaN distance is kept: it buries nothing either way)
+            }
+            const unsigned long long mask = __ballot(keep);
+            const int n = __popcll(mask);
+            if (cnt + n > kEnsSasaMaxNeighbours) {
+                over = true;
+                break;
+            }
+            if (keep) list[cnt + __popcll(mask & ((1ull << lane) - 1ull))] = v;
+            cnt += n;
+        }
+        sasa_wave_sync();
+        int open = 0, last = 0;
+        for (int k0 = 0; k0 < P; k0 += 64) {
+            const int k = k0 + lane;
+            bool exposed = false;
+            if (k < P) {
+                const float qx = fmaf(Ri, px[k], cx), qy = fmaf(Ri, py[k], cy), qz = fmaf(Ri, pz[k], cz);
+                bool buried = false;
+                if (!over) {
+                    if (cnt > 0) buried = sasa_buries(qx, qy, qz, list[last]);   // what buried this lane's previous point
+                    for (int n = 0; n < cnt && !buried; ++n)
+                        if (sasa_buries(qx, qy, qz, list[n])) {
+                            buried = true;
+                            last = n;
+                        }
+                } else {
+                    for (int j = 0; j < A && !buried; ++j) {    // (R2 = 0 where no atom is: d2 < 0 never holds)
+                        const float4 v = {xf[3 * j], xf[3 * j + 1], xf[3 * j + 2], R2[j]};
+                        buried = j != i && sasa_buries(qx, qy, qz, v);
+                    }
+                }
+                exposed = !buried;
+            }
+            open += __popcll(__ballot(exposed));
+        }
+        if (lane == 0) counts[item] = open;
+        sasa_wave_sync();                    // the list is read to the end before the next atom's is written
+    }
+}
+
+void launch_ens_sasa_counts(long F, int A, int P, const float* x, const float* ws, int32_t* counts, hipStream_t s) {
+    const float *R = ws, *R2 = ws + A, *px = ws + 2 * (size_t)A, *py = px + P, *pz = py + P;
+    const long g = (F * (long)A + kSasaWaves - 1) / kSasaWaves;
+    hipLaunchKernelGGL(k_sasa, dim3((unsigned)(g < kSasaMaxGroups ? g : kSasaMaxGroups)), dim3(256), 0, s, F, A, P, x, R, R2, px, py,
+                       pz, counts);
 }
 
 }  // namespace mdg

@@ -699,5 +699,11 @@ void launch_ens_pairwise_d2(long Fa, long Fb, int A, const float* xa, const floa
                             hipStream_t s);
 // counts [N][N] must be zero on entry
 void launch_ens_contact_counts(long F, int N, const float* ca, float cutoff2, int32_t* counts, hipStream_t s);
+// Shrake-Rupley counts: ws holds fp32 R [A] (0: no atom), R2 [A] and the points axis-major [3][P], staged by the caller
+constexpr int kEnsSasaMaxPoints = 4096;         // P
+constexpr int kEnsSasaMaxNeighbours = 512;      // a wave's LDS neighbour list; more within reach: every atom is tested instead
+constexpr float kEnsSasaMaxRadius = 16.f;       // every radius, and the probe
+size_t ens_sasa_workspace_bytes(int A, int P);
+void launch_ens_sasa_counts(long F, int A, int P, const float* x, const float* ws, int32_t* counts, hipStream_t s);
 
 }  // namespace mdg

@@ -1,16 +1,19 @@
 """Cartesian ensemble statistics of protein trajectories on the device: what an AlphaFlow-style ensemble evaluation is made of --
 superposition on a reference structure, per-atom RMSF, mean pairwise RMSD within and between ensembles, the per-atom Gaussian
-Wasserstein distance, contact-probability maps with weak and transient contacts, and PCA of the C-alpha coordinates.  The kernels
-are csrc/k_ensemble.hip (`mdgen_ens_superpose`, `mdgen_ens_moments`, `mdgen_ens_pairwise_d2`, `mdgen_ens_contact_counts`,
-include/mdgen_amd.h); the 3 x 3 matrix square roots, the 3N x 3N eigenproblem and the assignment problem are NumPy / SciPy fp64
-on the host.  Units are Angstrom.
+Wasserstein distance, contact-probability maps with weak and transient contacts, PCA of the C-alpha coordinates, and -- on request --
+Shrake-Rupley solvent-accessible surface areas with the exposed-residue set and the mutual information of the exposure bits built
+on them.  The kernels are csrc/k_ensemble.hip (`mdgen_ens_superpose`, `mdgen_ens_moments`, `mdgen_ens_pairwise_d2`,
+`mdgen_ens_contact_counts`, `mdgen_ens_sasa_counts`, include/mdgen_amd.h); the 3 x 3 matrix square roots, the 3N x 3N
+eigenproblem, the assignment problem and the L x L mutual-information table are NumPy / SciPy fp64 on the host.  Units are Angstrom.
 
 Every quantity is defined by its equation in include/mdgen_amd.h and in the docstrings here.  AlphaFlow's evaluation script and
-mdtraj are not installed where this was written: agreement with that script and with `mdtraj.superpose` / `mdtraj.rmsf` is
-unverified.  Out of scope: solvent-accessible surface area (and the exposed-residue and mutual-information entries built on it),
-XTC output, plots, and a Gram-matrix form of the pairwise distances.
+mdtraj are not installed where this was written: agreement with that script and with `mdtraj.superpose` / `mdtraj.rmsf` /
+`mdtraj.shrake_rupley` is unverified (the surface defaults -- probe 2.8 A, side-chain area above 2.0 A^2 -- follow the AlphaFlow
+paper's description); the yardstick is the NumPy restatement in tests/.  Out of scope: XTC output, plots, and a Gram-matrix form
+of the pairwise distances.
 
-`gaussian_w2`, `pca_w2`, `jaccard` and `contact_sets` import without torch; the functions on tensors import torch and the library
+`gaussian_w2`, `pca_w2`, `jaccard`, `contact_sets`, `sphere_points`, `atom_radii`, `mi_from_counts`, `spearman` and `exposed_sets`
+import without torch; the functions on tensors import torch and the library
 when they are called."""
 from __future__ import annotations
 
@@ -33,6 +36,15 @@ CA_SLOT = 1                     # atom14 slot of the C-alpha
 CUTOFF = 8.0                    # contact cutoff between C-alphas
 WEAK_BELOW = 0.9
 TRANSIENT_ABOVE = 0.1
+MAX_SASA_POINTS = 4096          # csrc/kernels.h kEnsSasaMaxPoints: P of mdgen_ens_sasa_counts
+MAX_SASA_RADIUS = 16.0          # kEnsSasaMaxRadius: every radius, and the probe
+SASA_NEIGHBOURS = 512           # kEnsSasaMaxNeighbours: a wave's neighbour list; more within reach: every atom is tested
+SASA_SCAN = 64                  # the atoms a wave scans at a time
+SASA_COUNT_BYTES = 64 << 20     # the int32 counts of one call of `sasa_counts` / `residue_sasa`
+BONDI_RADII = {"C": 1.70, "N": 1.55, "O": 1.52, "S": 1.80}
+SIDECHAIN_SLOT = 4              # atom14 slots 0 .. 3 are N, CA, C, O
+SASA_PROBE = 2.8                # `analyze_ensemble`'s defaults: the probe radius, and the side-chain area (A^2) above which a
+SASA_THRESHOLD = 2.0            # residue counts as exposed
 
 
 # ---- shapes ----------------------------------------------------------------------------------------------------------
@@ -243,6 +255,195 @@ def contact_counts(ca, cutoff=CUTOFF) -> np.ndarray:
     return counts.cpu().numpy()
 
 
+# ---- solvent-accessible surface --------------------------------------------------------------------------------------
+def _check_sasa_shape(F, A, P, probe):
+    if not 1 <= F <= MAX_CONTACT_FRAMES:
+        raise ValueError(f"surface counts take 1 .. 2^31 - 1 frames, got {F}")
+    if not 1 <= A <= MAX_ATOMS:
+        raise ValueError(f"the number of atoms must be in 1 .. {MAX_ATOMS}, got {A}")
+    if not 1 <= P <= MAX_SASA_POINTS:
+        raise ValueError(f"the number of sphere points must be in 1 .. {MAX_SASA_POINTS}, got {P}")
+    if not (np.isfinite(probe) and 0 <= probe <= MAX_SASA_RADIUS):
+        raise ValueError(f"the probe radius must be in 0 .. {MAX_SASA_RADIUS:g}, got {probe}")
+
+
+def sphere_points(n) -> np.ndarray:
+    """fp32 [n, 3]: the golden-section spiral on the unit sphere, computed in fp64 and rounded to fp32 once.
+    y_i = (2 i + 1) / n - 1, r_i = sqrt(1 - y_i^2), phi_i = i pi (3 - sqrt 5); point (cos phi_i r_i, y_i, sin phi_i r_i)."""
+    n = int(n)
+    if not 1 <= n <= MAX_SASA_POINTS:
+        raise ValueError(f"the number of sphere points must be in 1 .. {MAX_SASA_POINTS}, got {n}")
+    i = np.arange(n, dtype=np.float64)
+    y = (2.0 * i + 1.0) / n - 1.0
+    r = np.sqrt(1.0 - y * y)
+    phi = i * (np.pi * (3.0 - np.sqrt(5.0)))
+    return np.stack([np.cos(phi) * r, y, np.sin(phi) * r], -1).astype(np.float32)
+
+
+def atom_radii(aatype) -> np.ndarray:
+    """fp32 [14 L]: the Bondi radius of every atom14 slot of a sequence by its element -- the first letter of the atom's name,
+    `atom_types[atom14_to_atom37]` -- C 1.70, N 1.55, O 1.52, S 1.80 A; 0 where `atom14_mask` is 0 (no atom)."""
+    t = residue_tables()
+    aatype = _checked_aatype(aatype)
+    names = np.asarray(t["atom_types"])[np.asarray(t["atom14_to_atom37"])[aatype]]          # [L, 14]
+    mask = np.asarray(t["atom14_mask"])[aatype] != 0
+    rad = np.zeros(names.shape, np.float32)
+    for slot in np.argwhere(mask):
+        rad[tuple(slot)] = BONDI_RADII[str(names[tuple(slot)])[0]]
+    return rad.reshape(-1)
+
+
+def sasa_workspace_bytes(A, P) -> int:
+    import ctypes
+    from ._lib import check, lib
+    _check_sasa_shape(1, int(A), int(P), 0.0)
+    n = ctypes.c_size_t()
+    check(lib.mdgen_ens_sasa_workspace_bytes(int(A), int(P), ctypes.byref(n)))
+    return int(n.value)
+
+
+def _host_f32(a, shape, what):
+    a = np.ascontiguousarray(np.asarray(a, np.float32))
+    if a.shape != shape:
+        raise ValueError(f"{what} must have shape {shape}, got {a.shape}")
+    return a
+
+
+def sasa_counts_into(x, radius, points, probe, counts, workspace) -> None:
+    """One `mdgen_ens_sasa_counts` call: x (F, A, 3) fp32 on the device; radius [A] and points [P, 3] HOST arrays (NumPy); counts
+    int32 with F * A elements, every one written; workspace: `sasa_workspace_bytes(A, P)` bytes of uint8 on the device."""
+    import torch
+    from ._lib import launch, lib, ptr
+    F, A = int(x.shape[0]), int(x.shape[1])
+    points = np.asarray(points, np.float32)
+    P = int(points.shape[0]) if points.ndim == 2 else 0
+    _check_sasa_shape(F, A, P, probe)
+    radius, points = _host_f32(radius, (A,), "radius"), _host_f32(points, (P, 3), "points")
+    if counts.numel() < F * A:
+        raise ValueError("counts needs F * A elements")
+    launch(lib.mdgen_ens_sasa_counts, x, F, A, P, ptr(x, torch.float32), radius.ctypes.data, points.ctypes.data, float(probe),
+           ptr(counts, torch.int32), ptr(workspace, torch.uint8), int(workspace.numel()))
+
+
+def _sasa_chunk(A, chunk=None):
+    """Frames of one call: what `chunk` says, else as many as keep the call's int32 counts within SASA_COUNT_BYTES."""
+    return max(1, SASA_COUNT_BYTES // (4 * int(A))) if chunk is None else max(1, int(chunk))
+
+
+def sasa_counts(x, radius, n_points=960, probe=1.4, chunk=None):
+    """counts int32 [F, A], a device tensor: the number of the `n_points` points of `sphere_points` on the sphere of radius
+    radius[a] + probe about atom a of frame f that no other atom buries (include/mdgen_amd.h `mdgen_ens_sasa_counts`); 0 where
+    radius[a] == 0.  The area is 4 pi (radius + probe)^2 counts / n_points.  One call per `chunk` frames (default: 64 MB of counts
+    a call); a frame's counts do not depend on the chunk it falls in."""
+    import torch
+    x = _coords(x)
+    F, A = int(x.shape[0]), int(x.shape[1])
+    points = sphere_points(n_points)
+    _check_sasa_shape(F, A, len(points), probe)
+    counts = torch.empty(F, A, dtype=torch.int32, device=x.device)
+    ws = torch.empty(sasa_workspace_bytes(A, len(points)), dtype=torch.uint8, device=x.device)
+    step = _sasa_chunk(A, chunk)
+    for f0 in range(0, F, step):
+        sasa_counts_into(x[f0:f0 + step], radius, points, probe, counts[f0:f0 + step], ws)
+    return counts
+
+
+def sasa_areas(radius, probe, n_points, select=None) -> np.ndarray:
+    """fp64 [A]: the area 4 pi R_a^2 / n_points of one point of atom a, R_a = radius[a] + probe the fp32 sum taken to fp64; 0 where
+    there is no atom (radius 0) or `select` [A] is False."""
+    radius = np.asarray(radius, np.float32)
+    R = np.where(radius != 0, radius + np.float32(probe), np.float32(0)).astype(np.float32).astype(np.float64)
+    area = 4.0 * np.pi * R * R / int(n_points)
+    return area if select is None else np.where(np.asarray(select, bool), area, 0.0)
+
+
+def residue_sasa(atom14, aatype, atoms="sidechain", probe=2.8, n_points=960):
+    """fp64 [F, L], a device tensor: the solvent-accessible area (A^2) of every residue of atom14 (F, L, 14, 3) in every frame --
+    `sasa_counts` over all existing atoms with `atom_radii`, then the areas 4 pi R_a^2 counts / n_points of the residue's selected
+    atoms added: atoms "sidechain" the atom14 slots >= 4 (glycine has none: area 0), "all" every existing atom.  Frame chunks of at
+    most 64 MB of counts: no [F, 14 L] array exists."""
+    import torch
+    if atoms not in ("sidechain", "all"):
+        raise ValueError(f"atoms must be 'sidechain' or 'all', got {atoms!r}")
+    aatype = _checked_aatype(aatype)
+    L = int(aatype.shape[0])
+    x = _coords(atom14)
+    F, A = int(x.shape[0]), int(x.shape[1])
+    if A != 14 * L:
+        raise ValueError(f"{L} residues need {14 * L} atom14 slots, got {A}")
+    radius, points = atom_radii(aatype), sphere_points(n_points)
+    _check_sasa_shape(F, A, len(points), probe)
+    select = np.tile(np.arange(14) >= (SIDECHAIN_SLOT if atoms == "sidechain" else 0), L)
+    m = np.zeros((A, L))
+    m[np.arange(A), np.arange(A) // 14] = sasa_areas(radius, probe, len(points), select)
+    m = torch.from_numpy(m).to(x.device)
+    step = _sasa_chunk(A)
+    counts = torch.empty(min(step, F), A, dtype=torch.int32, device=x.device)
+    ws = torch.empty(sasa_workspace_bytes(A, len(points)), dtype=torch.uint8, device=x.device)
+    out = torch.empty(F, L, dtype=torch.float64, device=x.device)
+    for f0 in range(0, F, step):
+        n = min(step, F - f0)
+        sasa_counts_into(x[f0:f0 + n], radius, points, probe, counts[:n], ws)
+        out[f0:f0 + n] = counts[:n].double() @ m
+    return out
+
+
+def exposure_mi(exposed, chunk=65536) -> np.ndarray:
+    """fp64 [L, L] (NumPy), in nats: the mutual information of the exposure bits of every pair of residues over the frames of
+    `exposed`, bool [F, L] (a torch tensor on any device, or NumPy: then on the host).  n_i = sum_t e_ti and n11 = E^T E are
+    formed where the tensor is, in chunks of frames, as fp64 matmuls (exact: integers below 2^53); the four joint probabilities
+    are p11 = n11 / F, p10 = (n_i - n11) / F, p01 = (n_j - n11) / F, p00 = 1 - p11 - p10 - p01 from the integers;
+    MI = sum_ab p_ab ln(p_ab / (p_a p_b)), a term with p_ab = 0 being 0.  The diagonal is the entropy of e_i."""
+    if isinstance(exposed, np.ndarray):
+        e = exposed.astype(bool)
+        F, L = e.shape
+        n11 = np.zeros((L, L))
+        for f0 in range(0, F, int(chunk)):
+            y = e[f0:f0 + int(chunk)].astype(np.float64)
+            n11 += y.T @ y
+    else:
+        import torch
+        F, L = int(exposed.shape[0]), int(exposed.shape[1])
+        acc = torch.zeros(L, L, dtype=torch.float64, device=exposed.device)
+        for f0 in range(0, F, int(chunk)):
+            y = (exposed[f0:f0 + int(chunk)] != 0).double()
+            acc += y.T @ y
+        n11 = acc.cpu().numpy()
+    return mi_from_counts(n11, F)
+
+
+def mi_from_counts(n11, F) -> np.ndarray:
+    """`exposure_mi` from n11 = E^T E [L, L] (its diagonal is n_i) and the number of frames."""
+    n11 = np.rint(np.asarray(n11, np.float64))
+    n = np.diag(n11).copy()
+    cells = ((n11, n[:, None], n[None, :]),                                  # (joint count, count of a, count of b)
+             (n[:, None] - n11, n[:, None], F - n[None, :]),
+             (n[None, :] - n11, F - n[:, None], n[None, :]),
+             (F - n[:, None] - n[None, :] + n11, F - n[:, None], F - n[None, :]))
+    mi = np.zeros_like(n11)
+    for nab, na, nb in cells:
+        nab, na, nb = np.broadcast_arrays(nab, na, nb)
+        live = nab > 0
+        pab = nab[live] / F
+        mi[live] += pab * np.log(pab / ((na[live] / F) * (nb[live] / F)))
+    return mi
+
+
+def spearman(a, b) -> float:
+    """Spearman's rank correlation: `pearson` of the average ranks (ties share the mean of their ranks); NaN when either side is
+    constant."""
+    def ranks(v):
+        _, inverse, count = np.unique(np.asarray(v, np.float64).ravel(), return_inverse=True, return_counts=True)
+        return (np.cumsum(count) - (count - 1) / 2.0)[inverse]
+    return pearson(ranks(a), ranks(b))
+
+
+def exposed_sets(prob, exposed_in_ref) -> np.ndarray:
+    """bool [L]: the residues that are not exposed in the reference structure and whose exposure probability is > 0.1 -- the
+    *transient* rule of `contact_sets`."""
+    return ~np.asarray(exposed_in_ref, bool) & (np.asarray(prob, np.float64) > TRANSIENT_ABOVE)
+
+
 # ---- host side: NumPy fp64 -------------------------------------------------------------------------------------------
 def _sqrtm_psd(m):
     """Square roots of symmetric positive semi-definite matrices [..., 3, 3] by eigh; tiny negative eigenvalues clipped to 0."""
@@ -356,7 +557,8 @@ def superpose_on_first(atom14, aatype):
     return superpose(atom14, first, weights=torch.from_numpy(w), exists=ex)
 
 
-def analyze_ensemble(traj_atom14, ref_atom14, aatype, fit="heavy", cutoff=CUTOFF, pca=True) -> dict:
+def analyze_ensemble(traj_atom14, ref_atom14, aatype, fit="heavy", cutoff=CUTOFF, pca=True, sasa=False, probe=SASA_PROBE, n_points=960,
+                     sasa_threshold=SASA_THRESHOLD, sasa_atoms="sidechain") -> dict:
     """The ensemble statistics of a sampled trajectory (T, L, 14, 3) against an MD ensemble (F, L, 14, 3), both superposed on frame 0
     of the MD ensemble over the existing heavy atoms (`fit="heavy"`) or the C-alphas (`fit="ca"`).  Plain NumPy arrays and floats:
       ca_rmsf, ref_ca_rmsf [L]; atom_rmsf, ref_atom_rmsf [L, 14] (0 where no atom); rmsf_pearson (of the C-alpha RMSFs);
@@ -368,7 +570,14 @@ def analyze_ensemble(traj_atom14, ref_atom14, aatype, fit="heavy", cutoff=CUTOFF
       weak_contacts_jaccard, transient_contacts_jaccard: `contact_sets` of the MD and of the sampled probabilities, both against
         the contacts of the reference structure (frame 0 of the MD ensemble), compared by `jaccard`;
       with `pca`: pca_w2_ref (both ensembles on the MD ensemble's first two components), pca_w2_joint (on those of the two
-        ensembles stacked, MD first), pca_explained [2] (of the MD ensemble's)."""
+        ensembles stacked, MD first), pca_explained [2] (of the MD ensemble's);
+      with `sasa`, after those (`residue_sasa` of the superposed coordinates with `probe`, `n_points`, `sasa_atoms`):
+        residue_sasa_mean, ref_residue_sasa_mean [L] (A^2, over the frames);
+        exposure_prob, ref_exposure_prob [L]: the share of frames in which the residue's area is > `sasa_threshold`;
+        exposed_residue_jaccard: `exposed_sets` -- the residues not exposed in the reference structure (frame 0 of the MD
+          ensemble) with exposure probability > 0.1 -- of the MD and of the sampled probabilities, compared by `jaccard`;
+        exposed_mi, ref_exposed_mi [L, L]: `exposure_mi` of the exposure bits (nats);
+        exposed_mi_spearman: `spearman` of the two matrices over the pairs i < j."""
     import torch
     aatype = _checked_aatype(aatype)
     L = int(aatype.shape[0])
@@ -407,4 +616,20 @@ def analyze_ensemble(traj_atom14, ref_atom14, aatype, fit="heavy", cutoff=CUTOFF
         fit_j = pca_fit(torch.cat([ca_r, ca_x], 0))
         out["pca_w2_joint"] = pca_w2(pca_project(ca_x, fit_j), pca_project(ca_r, fit_j))
         out["pca_explained"] = fit_r["explained"][:2].copy()
+    if sasa:
+        if not np.isfinite(sasa_threshold):
+            raise ValueError(f"sasa_threshold must be finite, got {sasa_threshold}")
+        bits, prob = {}, {}
+        for pre, coords in (("", x), ("ref_", r)):
+            area = residue_sasa(coords, aatype, atoms=sasa_atoms, probe=probe, n_points=n_points)     # [frames, L] fp64, on the device
+            bits[pre] = area > float(sasa_threshold)
+            out[pre + "residue_sasa_mean"] = area.mean(0).cpu().numpy()
+            prob[pre] = bits[pre].sum(0).cpu().numpy() / float(area.shape[0])
+        out["exposure_prob"], out["ref_exposure_prob"] = prob[""], prob["ref_"]
+        in_ref = bits["ref_"][0].cpu().numpy()
+        out["exposed_residue_jaccard"] = jaccard(exposed_sets(out["ref_exposure_prob"], in_ref),
+                                                 exposed_sets(out["exposure_prob"], in_ref))
+        out["exposed_mi"], out["ref_exposed_mi"] = exposure_mi(bits[""]), exposure_mi(bits["ref_"])
+        upper = np.triu_indices(L, 1)
+        out["exposed_mi_spearman"] = spearman(out["exposed_mi"][upper], out["ref_exposed_mi"][upper])
     return out

@@ -25,7 +25,8 @@
                      k-means / MSM / PCCA+ entries (and the tICA ones) with `analyze_peptide_sim`'s --msm_k, --msm_states,
                      --md_msm_lag, --msm_lag, --kmeans_seed, --no_traj_msm; a peptide whose MSM is refused is named likewise.
                      --ensemble  adds `mdgen_amd.ensemble.analyze_ensemble`'s dict (Cartesian ensemble statistics against the same
-                     MD trajectory) under `analysis[name]["ensemble"]`, on the device tensor the sampler left there;
+                     MD trajectory) under `analysis[name]["ensemble"]`, on the device tensor the sampler left there; --sasa (with
+                     --probe, --sasa_points, --sasa_threshold, --sasa_atoms, as `analyze_ensembles`) adds its surface entries;
   --superpose        each written trajectory (PDB and --npy) is superposed on its own first frame over its existing atoms,
                      unweighted, on the device before it is formatted (`mdgen_ens_superpose`): the reference's
                      `traj.superpose(traj)`.  Off by default.
@@ -223,7 +224,8 @@ def run(args, model, device, names_seqres, rank=0, world=1, batch_fn=make_group_
                                           tica_lag=getattr(args, "tica_lag", 1000), msm=msm_options(args) if with_msm else None)
                 if getattr(args, "ensemble", False):
                     from .ensemble import analyze_ensemble
-                    analysis[n]["ensemble"] = analyze_ensemble(all_atom14[i], arrs[n], aat)
+                    from .analyze_ensembles import sasa_options
+                    analysis[n]["ensemble"] = analyze_ensemble(all_atom14[i], arrs[n], aat, **sasa_options(args))
                 sync()
                 analysis_s += time.time() - start
     job_s = max_over_ranks(total_s, dist)
@@ -282,7 +284,9 @@ def build_parser():
     p.add_argument("--no_traj_msm", action="store_true", help="skip the sampled trajectory's own MSM")
     p.add_argument("--ensemble", action="store_true",
                    help="with --analyze: also mdgen_amd.ensemble.analyze_ensemble's dict (RMSF, pairwise RMSD, Gaussian W2, contacts, "
-                        "PCA) under analysis[name]['ensemble']")
+                        "PCA) under analysis[name]['ensemble']; with --sasa also the solvent-accessible-surface entries")
+    from .analyze_ensembles import add_sasa_arguments
+    add_sasa_arguments(p)
     p.add_argument("--superpose", action="store_true",
                    help="superpose each written trajectory (PDB and --npy) on its own first frame over its existing atoms, on the "
                         "device (the reference's traj.superpose(traj))")

@@ -25,15 +25,21 @@
                 `mdgen_ens_pairwise_d2` the plain torch expression on the same box: `torch.cdist` on [F, 3A] in chunks of 2 048
                 rows with the same two fp64 sums, in its matrix-product mode (`torch_cdist_mm_ms`) and in its direct mode
                 (`torch_cdist_direct_ms`); beside `mdgen_ens_contact_counts` a chunked torch comparison (512 frames at a time).
-                Not part of `--leg all` (it allocates 1.3 GB of coordinates).
+                `sasa_counts`: `mdgen_ens_sasa_counts` over the 250 and the 30 003 frames (P = 960, probe 2.8 A, Bondi radii, existing
+                atoms by `atom14_mask`); beside each a chunked torch restatement of the same counts on the same box, run on the
+                first `--sasa_torch_frames` frames only (it is far slower: `torch_ms_per_frame` against `ms_per_frame`) with the
+                number of entries that differ there (torch need not fuse the multiply-adds: borderline points may differ).  Then
+                `analyze_ensemble` without and with `sasa=True`.
+                Not part of `--leg all` (it allocates 1.3 GB of coordinates).  `--leg sasa`: the `sasa_counts` records and the two
+                `analyze_ensemble(pca=False)` wall times alone.
 
 Beside each of the last four, `numpy_ms`: the same definition in NumPy fp64 on the host, the copy of the device array to the host
 included (moments: cos / sin, three matrix products and two sums; project: cos / sin, the centred product; series: np.fft; tica:
 the tICA entries -- moments, solver, two projections, four histograms, two autocovariances -- from the angles).
 
     python scripts/analysis_bench.py [--leg all|dihedrals|histograms|acov|fft|numpy|moments|project|series|tica|kmeans_pp|kmeans_step|kmeans_fit|
-                                           count_matrix|msm|tps|ensemble] [--size sampler|md|both]
-                                     [--reps 5]
+                                           count_matrix|msm|tps|ensemble|sasa] [--size sampler|md|both]
+                                     [--reps 5] [--sasa_torch_frames 4]
 
 acov reports multiply-adds (2 n' (K + 1) NF with n' the mean number of terms per lag) over time and that rate's share of the
 fp32 vector peak (157.3 TFLOP/s = 78.6e12 multiply-adds / s)."""
@@ -334,6 +340,8 @@ def ensemble_legs(a, dev):
     base = ca[:, None, :] + torch.randn(L, 14, 3, generator=g, device=dev) * 1.8
     md = (base + torch.randn(F, L, 1, 3, generator=g, device=dev) * 1.0 + torch.randn(F, L, 14, 3, generator=g, device=dev) * 0.3) * mask
     tr = (base + torch.randn(T, L, 1, 3, generator=g, device=dev) * 0.8 + torch.randn(T, L, 14, 3, generator=g, device=dev) * 0.3) * mask
+    if a.leg == "sasa":
+        return sasa_records(a, dev, tr, md, aat)
     x = md.reshape(F, L * 14, 3)
     wd, exd = torch.from_numpy(w).to(dev), torch.from_numpy(ex).to(dev)
     out = torch.empty_like(x)
@@ -402,21 +410,73 @@ def ensemble_legs(a, dev):
         best, med = wall_ms(lambda: E.analyze_ensemble(tr, md, aat, pca=pca), max(a.reps // 2, 1))
         print(json.dumps({"leg": "ensemble", "what": "analyze_ensemble", "pca": pca, "T": T, "F": F, "L": L, "wall_ms_best": best,
                           "wall_ms_median": med}))
+    sasa_records(a, dev, tr, md, aat, with_plain=False)
+
+
+def torch_sasa_counts(x, rad, pts, probe, atoms_at_a_time=16):
+    """The counts of `mdgen_ens_sasa_counts` as plain torch expressions, frame by frame and 16 atoms at a time."""
+    dev = x.device
+    live = torch.from_numpy(np.flatnonzero(rad != 0)).to(dev)
+    R = torch.from_numpy((rad[rad != 0] + np.float32(probe)).astype(np.float32)).to(dev)
+    R2 = R * R
+    u = torch.from_numpy(pts).to(dev)
+    counts = torch.zeros(x.shape[0], x.shape[1], dtype=torch.int32, device=dev)
+    n = len(live)
+    for f in range(x.shape[0]):
+        c = x[f, live]
+        for i0 in range(0, n, atoms_at_a_time):
+            k = min(atoms_at_a_time, n - i0)
+            q = c[i0:i0 + k, None, :] + R[i0:i0 + k, None, None] * u[None]                      # [k, P, 3]
+            d = q[:, :, None, 0] - c[None, None, :, 0]
+            d2 = d * d
+            for ax in (1, 2):
+                d = q[:, :, None, ax] - c[None, None, :, ax]
+                d2 += d * d
+            hit = d2 < R2[None, None, :]
+            own = torch.arange(k, device=dev)
+            hit[own, :, i0 + own] = False
+            counts[f, live[i0:i0 + k]] = (~hit.any(-1)).sum(-1).to(torch.int32)
+    return counts
+
+
+def sasa_records(a, dev, tr, md, aat, with_plain=True):
+    from mdgen_amd import ensemble as E
+    L, P, probe = len(aat), 960, 2.8
+    rad, pts = E.atom_radii(aat), E.sphere_points(P)
+    ws = torch.empty(E.sasa_workspace_bytes(L * 14, P), dtype=torch.uint8, device=dev)
+    for name, coords in (("sampled", tr), ("md", md)):
+        x = coords.reshape(len(coords), L * 14, 3)
+        counts = torch.empty(len(x), L * 14, dtype=torch.int32, device=dev)
+        best, med = timed_ms(lambda: E.sasa_counts_into(x, rad, pts, probe, counts, ws), a.reps)
+        nt = min(a.sasa_torch_frames, len(x))
+        tb, _ = timed_ms(lambda: torch_sasa_counts(x[:nt], rad, pts, probe), 1)
+        diff = int((torch_sasa_counts(x[:nt], rad, pts, probe) != counts[:nt]).sum())
+        live = int((rad != 0).sum())
+        print(json.dumps({"leg": "ensemble", "what": "sasa_counts", "shape": name, "F": len(x), "A": L * 14, "existing_atoms": live,
+                          "P": P, "probe": probe, "ms_best": best, "ms_median": med, "ms_per_frame": best / len(x),
+                          "torch_frames": nt, "torch_ms": tb, "torch_ms_per_frame": tb / nt,
+                          "entries_differing_from_torch": diff, "entries_compared": nt * L * 14,
+                          "exposed_share": float(counts.double().sum() / (len(x) * live * P))}))
+    for sasa in ((False, True) if with_plain else (True,)):
+        best, med = wall_ms(lambda: E.analyze_ensemble(tr, md, aat, pca=False, sasa=sasa), max(a.reps // 2, 1))
+        print(json.dumps({"leg": "ensemble", "what": "analyze_ensemble", "pca": False, "sasa": sasa, "T": len(tr), "F": len(md), "L": L,
+                          "wall_ms_best": best, "wall_ms_median": med}))
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--leg", default="all", choices=["all", "dihedrals", "histograms", "acov", "fft", "numpy", "moments", "project",
                                                      "series", "tica", "kmeans_pp", "kmeans_step", "kmeans_fit", "count_matrix",
-                                                     "msm", "tps", "ensemble"])
+                                                     "msm", "tps", "ensemble", "sasa"])
     ap.add_argument("--size", default="both", choices=["sampler", "md", "both"])
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sasa_torch_frames", type=int, default=4, help="ensemble / sasa legs: frames of the torch restatement of the counts")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("analysis_bench needs the GPU: there is nothing to time without one")
     from mdgen_amd import analysis as A
     dev = torch.device("cuda")
-    if a.leg == "ensemble":
+    if a.leg in ("ensemble", "sasa"):
         return ensemble_legs(a, dev)
     want = lambda leg: a.leg in ("all", leg)   # noqa: E731
     sizes = [s for s in SIZES if a.size in ("both", s)]
